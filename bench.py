@@ -1,16 +1,23 @@
 #!/usr/bin/env python3
 """bench.py -- the hot path's headline metric on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, runs W warm-up steps, times K steps and prints the headline line (metric, value, unit,
+ms_per_step, ...).  `--full` adds everything else below -- roofline, roofline_linear_scan, extra, cpu_baseline --
+each still subject to its own --no-* switch.  `--dump-outputs DIR` writes the framebuffer of the last timed step
+(rank 0's gathered W x H x 3 fp32 sample sums, what rt_render_hip hands its caller) as DIR/rgb_sum.npy; the inputs
+(scene, seed) are fixed by the arguments, so two builds can be compared output for output.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts N rank processes itself (one per
 GPU; this process never touches the GPU, each rank checks that its device exists).
 
 `--tiles-abi` times the multi-GPU path the C ABI exports instead: ONE process, rt_render_hip_tiles over
 `--gpus N` devices (one stream per device, ncclCommInitAll, ONE ncclGather, row placement, one copy to the
-caller's host buffer).  At N = 1 the default mode also reports it, next to the headline, under `extra`.
+caller's host buffer).  At N = 1 the default mode with `--full` also reports it, next to the headline,
+under `extra`.
 
 One STEP = one full frame of the workload: every rank renders its interleaved row tiles
 with the HIP kernel (through the C ABI, into a torch tensor on torch's current stream),
@@ -24,6 +31,8 @@ blur, sky gradient), 1920x1080, 1024 spp, depth 50.  Scaling is STRONG: the same
 split over N GPUs.
 
 metric   Msamples/s = W*H*spp / step seconds / 1e6          (whole job, all ranks)
+
+--full only:
 roofline fp32 vector ALU (not HBM, not MFMA: the path is a scalar-per-lane bounce loop).
          achieved = algorithmic flops of one launch / mean launch time (HIP events on the launch
          stream around each timed step's render launches), flops from SURVEY.md 8(d)'s accounting
@@ -103,7 +112,31 @@ def parse_args(argv=None):
     ap.add_argument("--no-overlap", action="store_true", help="N > 1: every step waits for its own gather (default: a frame's "
                     "gather overlaps the next frame's render)")
     ap.add_argument("--tiles-abi", action="store_true", help="one process: rt_render_hip_tiles (C ABI) over --gpus N devices")
+    ap.add_argument("--full", action="store_true", help="besides the headline: roofline (with the counting kernel's event "
+                    "counts), the linear-scan leg, the other BASELINE configurations and the CPU baseline (each subject to "
+                    "its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's framebuffer (rank 0's "
+                    "W x H x 3 fp32 sample sums) as DIR/rgb_sum.npy")
     return ap.parse_args(argv)
+
+
+DUMP_MAX_BYTES = 60 * 10**6  # --dump-outputs: all arrays together, under 64 MB with the .npy headers
+
+
+def dump_outputs(dirname, np, **arrays):
+    """--dump-outputs: each array as DIR/<name>.npy, float32 / float64 as computed.  An array over the cap is replaced by a
+    fixed sample of its rows (seeded, sorted: the same rows in every run of the same arguments)."""
+    os.makedirs(dirname, exist_ok=True)
+    budget = DUMP_MAX_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        if a.nbytes > budget:
+            row_bytes = a.nbytes // a.shape[0]
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], budget // row_bytes, replace=False))
+            a = np.ascontiguousarray(a[rows])
+            print(f"bench.py: {name} is {a.shape[0]} sampled rows (seed 0) of the output", file=sys.stderr, flush=True)
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def spawn_ranks(args) -> int:
@@ -248,6 +281,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
     kernel_ms = [a.elapsed_time(b) for a, b in events]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, np, rgb_sum=img.cpu().numpy())
 
     samples_per_step = scene.width * scene.height * scene.spp
     ms_per_step = elapsed / args.steps * 1e3
@@ -289,24 +324,30 @@ def main():
         mean = float(img.mean().item()) / scene.spp
         result["config"]["frame_mean_radiance"] = round(mean, 5)
         assert np.isfinite(mean) and 0.2 < mean < 0.8, mean
-        k_ms = float(np.mean(kernel_ms))
-        result["roofline"] = roofline_of(rtmi, scene, mine, args, chunk, world, k_ms, np)
-        if world == 1 and not args.no_linear and not args.no_counts and args.variant == 0:
-            result["roofline_linear_scan"] = linear_scan_leg(rtmi, scene, base, local, stream, torch, np)
-        if world == 1 and not args.no_extra:
-            result["extra"] = extra_configs(rtmi, dev_index, args.seed, local, stream, torch, np)
-            try:  # the multi-GPU path the C ABI exports, on this one GPU: what its plumbing costs per frame
-                result["extra"]["tiles_abi_1gpu"] = tiles_abi_frames(rtmi, scene, base, [dev_index], 3, np, reference=img.cpu().numpy())[0]
-            except Exception as e:  # never lose the bench line over an extra
-                result["extra"]["tiles_abi_1gpu"] = {"error": repr(e)}
-        # ---- CPU baseline (reported only): the reference's own render() on this host's cores
-        if world == 1 and not args.no_cpu_baseline:
-            result["cpu_baseline"] = cpu_baseline(rtmi, args)
+        if args.full:
+            full_legs(result, rtmi, scene, base, mine, local, img, stream, args, chunk, world, dev_index, kernel_ms, torch, np)
         print(json.dumps(result), flush=True)
 
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def full_legs(result, rtmi, scene, base, mine, local, img, stream, args, chunk, world, dev_index, kernel_ms, torch, np):
+    """--full: rank 0's measurements beyond the headline, each its own runs after the timed region, into `result`."""
+    k_ms = float(np.mean(kernel_ms))
+    result["roofline"] = roofline_of(rtmi, scene, mine, args, chunk, world, k_ms, np)
+    if world == 1 and not args.no_linear and not args.no_counts and args.variant == 0:
+        result["roofline_linear_scan"] = linear_scan_leg(rtmi, scene, base, local, stream, torch, np)
+    if world == 1 and not args.no_extra:
+        result["extra"] = extra_configs(rtmi, dev_index, args.seed, local, stream, torch, np)
+        try:  # the multi-GPU path the C ABI exports, on this one GPU: what its plumbing costs per frame
+            result["extra"]["tiles_abi_1gpu"] = tiles_abi_frames(rtmi, scene, base, [dev_index], 3, np, reference=img.cpu().numpy())[0]
+        except Exception as e:  # never lose the bench line over an extra
+            result["extra"]["tiles_abi_1gpu"] = {"error": repr(e)}
+    # ---- CPU baseline (reported only): the reference's own render() on this host's cores
+    if world == 1 and not args.no_cpu_baseline:
+        result["cpu_baseline"] = cpu_baseline(rtmi, args)
 
 
 class stdout_to_stderr:
@@ -381,6 +422,8 @@ def tiles_abi_main(args) -> int:
         img = scene.render_tiles(devices=devices, opts=base, stats=st)  # synchronous: returns with the frame in host memory
         kern.append(st.kernel_ms), gath.append(st.gather_ms)
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, np, rgb_sum=img)
     n = scene.width * scene.height * scene.spp
     result = {
         "metric": "Msamples/sec (WxHxspp)", "value": round(n / (elapsed / args.steps) / 1e6, 3), "unit": "Msamples/s",

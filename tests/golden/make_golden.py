@@ -5,6 +5,7 @@
 
 * scenes/*.json           the reference's gpu-version scene files (data, not source), re-serialised
                           through rt_scene_load_json -> rt_scene_to_json (normalised text)
+* scenes_as_shipped/*.json  the same four files byte for byte as the reference ships them
 * rtiow_seed7.json        the RTIOW scene of rt_scene_rtiow(7) the vectors below were made on
 * ref_three_sphere.npz    64x36x16spp fp64 image + 2048 per-sample radiance triples from the
                           COMPILED REFERENCE (oracle/_ref, cmake-cpu-version sources + hooked rand())
@@ -32,10 +33,14 @@ SEED = 2023
 
 def normalise_scenes():
     os.makedirs(os.path.join(HERE, "scenes"), exist_ok=True)
+    os.makedirs(os.path.join(HERE, "scenes_as_shipped"), exist_ok=True)
     for name in ("sample_scene", "basic_scene", "blue", "blue2"):
         sc = rtmi.Scene.load(os.path.join(REF, name + ".json"))
         with open(os.path.join(HERE, "scenes", name + ".json"), "w") as f:
             f.write(sc.to_json())
+        with open(os.path.join(REF, name + ".json"), "rb") as src, \
+                open(os.path.join(HERE, "scenes_as_shipped", name + ".json"), "wb") as f:
+            f.write(src.read())
         print("scene", name, sc.info.num_prims, "objects")
 
 

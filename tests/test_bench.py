@@ -1,5 +1,5 @@
-"""CPU-side checks of bench.py: the rank launcher's refusal path, the flop accounting constants and the
-CPU-baseline leg (the only part of bench.py that may use oracle/)."""
+"""Checks of bench.py.  CPU side: the rank launcher's refusal path, the flop accounting constants, the CPU-baseline leg
+(the only part of bench.py that may use oracle/) and --dump-outputs' cap.  GPU: a plain run and a --full run."""
 import os
 import subprocess
 import sys
@@ -85,3 +85,59 @@ def test_cpu_baseline_leg_runs_on_all_cores(rtmi):
         assert "sampling_spread" in legs["ii_reference_all_cores"]
         if "error" not in legs.get("i_stock_single_thread", {"error": 1}):
             assert legs["i_stock_single_thread"]["Msamples_per_s_per_core"] > 0
+
+
+def test_plain_run_is_lean_by_default():
+    """The extra legs are behind --full; --dump-outputs is off unless given."""
+    b = _bench()
+    a = b.parse_args([])
+    assert not a.full and a.dump_outputs is None
+    a = b.parse_args(["--full", "--dump-outputs", "d"])
+    assert a.full and a.dump_outputs == "d"
+
+
+def test_dump_outputs_caps_with_a_fixed_row_sample(tmp_path, monkeypatch):
+    import numpy as np
+    b = _bench()
+    img = np.arange(40 * 7 * 3, dtype=np.float32).reshape(40, 7, 3)
+    b.dump_outputs(str(tmp_path / "whole"), np, rgb_sum=img)
+    np.testing.assert_array_equal(np.load(tmp_path / "whole" / "rgb_sum.npy"), img)
+    monkeypatch.setattr(b, "DUMP_MAX_BYTES", 10 * 7 * 3 * 4)
+    b.dump_outputs(str(tmp_path / "a"), np, rgb_sum=img)
+    b.dump_outputs(str(tmp_path / "b"), np, rgb_sum=img)
+    got = np.load(tmp_path / "a" / "rgb_sum.npy")
+    assert got.shape == (10, 7, 3) and got.dtype == np.float32
+    np.testing.assert_array_equal(got, np.load(tmp_path / "b" / "rgb_sum.npy"))
+    rows = got[:, 0, 0].astype(np.int64) // 21
+    assert list(rows) == sorted(set(rows)) and all(np.array_equal(img[r], g) for r, g in zip(rows, got))
+
+
+def _bench_line(args, timeout=600):
+    import json
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True, timeout=timeout)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, p.stdout
+    return json.loads(lines[0])
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_the_last_frame(rtmi, tmp_path):
+    """A plain run: the headline fields only, --steps timed steps, and DIR/rgb_sum.npy equal to the unsharded frame."""
+    import numpy as np
+    small = ["--width", "96", "--height", "54", "--spp", "8"]
+    r = _bench_line(["--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)] + small)
+    assert r["steps"] == 2 and r["ms_per_step"] > 0 and r["unit"] == "Msamples/s" and r["higher_is_better"] is True
+    assert r["dtype"] == "f32" and r["value"] > 0
+    assert not {"roofline", "roofline_linear_scan", "extra", "cpu_baseline"} & set(r)
+    got = np.load(tmp_path / "rgb_sum.npy")
+    want = rtmi.Scene.rtiow(7, 96, 54, 8, 50).render(rtmi.Opts(seed=2023))
+    assert got.dtype == np.float32 and got.shape == (54, 96, 3)
+    np.testing.assert_array_equal(got, want)
+
+
+@pytest.mark.gpu
+def test_full_run_keeps_the_roofline_legs():
+    r = _bench_line(["--gpus", "1", "--steps", "1", "--warmup", "0", "--full", "--no-extra", "--no-cpu-baseline",
+                     "--width", "96", "--height", "54", "--spp", "8"])
+    assert r["roofline"]["flops_per_launch"] > 0 and r["roofline_linear_scan"]["kernel_variant"] == 16

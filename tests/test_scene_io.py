@@ -38,11 +38,9 @@ def test_reference_scene_files_parse(rtmi, golden_dir):
     assert sc.materials()["fuzz"][0] == np.float32(0.5)
 
 
-def test_reference_scene_files_parse_in_place(rtmi):
-    """Where the reference checkout exists (this container), its files parse as shipped."""
-    ref = "/root/reference/gpu-version"
-    if not os.path.isdir(ref):
-        pytest.skip("reference checkout not present")
+def test_reference_scene_files_parse_in_place(rtmi, golden_dir):
+    """The reference's files parse as shipped (byte-for-byte copies under tests/golden/scenes_as_shipped)."""
+    ref = os.path.join(golden_dir, "scenes_as_shipped")
     for name in ("sample_scene.json", "basic_scene.json", "blue.json", "blue2.json"):
         sc = rtmi.Scene.load(os.path.join(ref, name))
         raw = json.load(open(os.path.join(ref, name)))
