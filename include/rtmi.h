@@ -367,12 +367,13 @@ int rt_render_hip_device(const rt_scene *s, const rt_opts *o, void *d_rgb_sum, v
 int rt_render_hip(const rt_scene *s, const rt_opts *o, float *rgb_sum, rt_stats *stats);
 
 /* One frame on n_devices GPUs of this node (SURVEY.md 8(b) "Threading", 8(e); the reference's only multi-GPU
- * mechanism is one renderer process per GPU per animation FRAME, gpu-version/blue.py:23-32).  Row tile t
- * (o->tile_rows rows, default 8) is rendered by devices[t mod n] on a stream of its own -- the launch
- * rt_render_hip_device makes for that shard -- then ONE ncclGather (rccl.h:745, root = devices[0]) collects the
- * dense local buffers and a kernel on the root places the rows; rgb_sum (host, H*W*3 floats) receives the frame.
- * The result is bit-identical to rt_render_hip for every n.  devices == NULL means ordinals 0..n-1; the list must
- * not repeat a device.  o->device, tile_first and tile_stride are ignored (the call sets them per device).
+ * mechanism is one renderer process per GPU per animation FRAME, gpu-version/blue.py:23-32).  The row tiles
+ * (o->tile_rows rows, default 8) are dealt out as rt_shard_deal() says; devices[r] renders shard r on a stream of
+ * its own -- the launch rt_render_hip_device makes for that shard -- then ONE ncclGather (rccl.h:745, root =
+ * devices[0]) collects the dense local buffers and a kernel on the root places the rows; rgb_sum (host, H*W*3
+ * floats) receives the frame.  The result is bit-identical to rt_render_hip for every n.  devices == NULL means
+ * ordinals 0..n-1; the list must not repeat a device.  o->device, tile_first, tile_stride and tile_rotate are
+ * ignored (the call sets them per device).
  * Streams, RCCL communicators (ncclCommInitAll, ~0.1 s once per device list) and buffers are kept between calls;
  * rt_tiles_shutdown() releases them.  RCCL is loaded with dlopen at the first call: librtmi.so does not link it. */
 int rt_render_hip_tiles(const rt_scene *s, const rt_opts *o, const int *devices, int n_devices,

@@ -6,7 +6,7 @@
 // plus --rtiow [--scene-seed S] (the hard-coded random_scene() of main.cpp:125-172),
 // --seed, -o, --device, --chunk, --dump-json.  Timing goes to stderr like the reference's
 // when() markers (rtweekend.cuh:40).
-// --gpus N renders ONE frame on the first N GPUs of the node: row tiles interleaved over the devices, one
+// --gpus N renders ONE frame on the first N GPUs of the node: row tiles dealt out to the devices, one
 // RCCL gather (rt_render_hip_tiles); the image is the same bytes as with one GPU.  (The reference's blue.py
 // instead starts one process per GPU per animation frame; rtmi-frames is that shape.)
 // Resumable rendering: --acc-out FILE saves the exact pixel sums, --acc-in FILE continues from them

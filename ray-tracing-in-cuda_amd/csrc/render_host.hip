@@ -18,6 +18,7 @@
 
 #include "device_scene.h"
 #include "scene.hpp"
+#include "shard.h"
 
 #ifndef RT_WAVES_PER_SIMD
 #define RT_WAVES_PER_SIMD 7
@@ -833,16 +834,6 @@ struct Shard {
     int tile_rows, tile_first, tile_stride, tile_rotate, num_tiles, local_tiles, local_rows;
 };
 
-// the k-th row tile of a shard (rt_opts.tile_rotate: plain interleave, rotated interleave, or there-and-back); grows with k
-static inline long long shard_tile(const Shard &sh, int k) {
-    if (sh.tile_rotate == 2)  // ranks 0 .. N-1, then N-1 .. 0: two tiles per group of 2 N
-        return (long long)(k >> 1) * 2 * sh.tile_stride + ((k & 1) ? 2 * sh.tile_stride - 1 - sh.tile_first : sh.tile_first);
-    if (!sh.tile_rotate) return sh.tile_first + (long long)k * sh.tile_stride;
-    int j = (sh.tile_first - k) % sh.tile_stride;
-    if (j < 0) j += sh.tile_stride;
-    return (long long)k * sh.tile_stride + j;
-}
-
 static int shard_of(const Scene &s, const rt_opts *o, Shard &sh) {
     sh.tile_rows = (o && o->tile_rows > 0) ? o->tile_rows : 8;
     sh.tile_first = o ? o->tile_first : 0;
@@ -859,9 +850,9 @@ static int shard_of(const Scene &s, const rt_opts *o, Shard &sh) {
     }
     sh.local_tiles = 0;
     sh.local_rows = 0;
-    // (only the last group of tile_stride tiles can be incomplete, so a shard's tiles are its local tiles 0 .. local_tiles - 1)
+    // (shard.h: the shard's tiles are its local tiles 0 .. local_tiles - 1)
     for (int k = 0;; ++k) {
-        const long long t64 = shard_tile(sh, k);
+        const long long t64 = shard_tile<long long>(sh.tile_first, sh.tile_stride, sh.tile_rotate, k);
         if (t64 >= sh.num_tiles) break;
         const int t = (int)t64;
         int rows = s.height - t * sh.tile_rows;
@@ -873,8 +864,9 @@ static int shard_of(const Scene &s, const rt_opts *o, Shard &sh) {
 }
 
 static int shard_global_row(const Shard &sh, int local_row) {
-    int tl = local_row / sh.tile_rows;
-    return (int)shard_tile(sh, tl) * sh.tile_rows + (local_row - tl * sh.tile_rows);
+    const int tl = local_row / sh.tile_rows;
+    const int t = (int)shard_tile<long long>(sh.tile_first, sh.tile_stride, sh.tile_rotate, tl);
+    return t * sh.tile_rows + (local_row - tl * sh.tile_rows);
 }
 
 }  // namespace rtmi

@@ -46,6 +46,7 @@
 #include "device_scene.h"
 #include "philox.h"
 #include "rt_trig.h"
+#include "shard.h"
 #include "../../include/rtmi.h"
 
 // minimum resident waves per SIMD the register allocator must leave room for (8 <=> 64 VGPRs)
@@ -312,14 +313,7 @@ __global__ __launch_bounds__(256, RT_WAVES_PER_SIMD) void render_kernel(const Re
         hx = x0 + (lane & 7);
         hlr = band * 8 + (lane >> 3);
         const int htl = hlr / tile_rows;
-        int tile = tile_first + htl * tile_stride;
-        if (tile_rotate == 2) {  // there and back (include/rtmi.h, rt_opts.tile_rotate)
-            tile = (htl >> 1) * 2 * tile_stride + ((htl & 1) ? 2 * tile_stride - 1 - tile_first : tile_first);
-        } else if (tile_rotate) {  // rotated interleave
-            int j = (tile_first - htl) % tile_stride;
-            if (j < 0) j += tile_stride;
-            tile = htl * tile_stride + j;
-        }
+        const int tile = shard_tile<int>(tile_first, tile_stride, tile_rotate, htl);
         hy = tile * tile_rows + (hlr - htl * tile_rows);
         hvalid = (hx < P.width && hlr < local_rows && hy < P.height) ? 1 : 0;
     };

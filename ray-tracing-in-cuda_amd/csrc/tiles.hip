@@ -2,11 +2,12 @@
 //
 // The reference's only multi-GPU mechanism is one renderer PROCESS per GPU per animation frame
 // (gpu-version/blue.py:23-32, CUDA_VISIBLE_DEVICES=k); it has no collective.  Here one frame is split:
-// row tile t (tile_rows full-width rows) belongs to device t mod N, every device renders its tiles into a
-// dense local buffer on its own stream (the same rt_render_hip_device a single GPU runs, shard geometry in
-// rt_opts), ONE ncclGather (rccl.h:745; xGMI peer-to-peer, one message per peer) brings the buffers to the
-// first device, a small kernel there puts the rows where they belong, and one copy hands the frame to the
-// caller.  Single process, single host thread: every launch is asynchronous, so the devices run concurrently.
+// its row tiles (tile_rows full-width rows each) are dealt out to the N devices as rt_shard_deal() picks
+// (rt_opts.tile_rotate, shard.h), every device renders its tiles into a dense local buffer on its own stream
+// (the same rt_render_hip_device a single GPU runs, shard geometry in rt_opts), ONE ncclGather (rccl.h:745;
+// xGMI peer-to-peer, one message per peer) brings the buffers to the first device, a small kernel there puts
+// the rows where they belong, and one copy hands the frame to the caller.  Single process, single host thread:
+// every launch is asynchronous, so the devices run concurrently.
 //
 // RCCL is looked up at run time (dlopen) the first time more than the render is needed: a process that has
 // already loaded an RCCL (PyTorch bundles one) keeps using that one, and single-GPU consumers of librtmi.so
@@ -22,6 +23,7 @@
 #include <vector>
 
 #include "scene.hpp"
+#include "shard.h"
 
 namespace rtmi {
 
@@ -79,28 +81,22 @@ static RcclApi *rccl_api() {
         }                                                                                                               \
     } while (0)
 
-// gathered[rank][pad_rows][W][3] (each rank's local rows dense; which rank owns tile t of the frame, and as which of its
-// local tiles, follows rt_opts.tile_rotate: 0 plain interleave, 1 rotated, 2 there and back)  ->  full[H][W][3].  One thread
-// per float; consecutive threads read and write consecutive floats.
+// gathered[rank][pad_rows][W][3] (each rank's local rows dense, cut as rt_opts.tile_rotate = `deal` says)  ->  full[H][W][3].
+// One thread per float of `gathered`; consecutive threads read and write consecutive floats.  The shards partition the tiles
+// and a shard's tiles increase with its local tile (shard.h), so a local row whose image row y is inside the frame is one of
+// the shard's rows (y < H also means that its tile is), and every image row is written exactly once.
 __global__ __launch_bounds__(256) void place_rows_kernel(const float *__restrict__ gathered, float *__restrict__ full,
                                                          int height, int row_floats, int tile_rows, int n_ranks,
-                                                         int pad_rows, int rotate) {
+                                                         int pad_rows, int deal) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    const size_t total = (size_t)height * row_floats;
-    if (i >= total) return;
-    const int y = (int)(i / row_floats);
-    const int c = (int)(i - (size_t)y * row_floats);
-    const int t = y / tile_rows;
-    int rank = t % n_ranks, local_tile = t / n_ranks;
-    if (rotate == 1) {
-        rank = (t % n_ranks + t / n_ranks) % n_ranks;
-    } else if (rotate == 2) {
-        const int p = t % (2 * n_ranks), back = p >= n_ranks ? 1 : 0;
-        rank = back ? 2 * n_ranks - 1 - p : p;
-        local_tile = 2 * (t / (2 * n_ranks)) + back;
-    }
-    const int local_row = local_tile * tile_rows + (y - t * tile_rows);
-    full[i] = gathered[((size_t)rank * pad_rows + local_row) * row_floats + c];
+    if (i >= (size_t)n_ranks * pad_rows * row_floats) return;
+    const size_t row = i / row_floats;
+    const int c = (int)(i - row * row_floats);
+    const int rank = (int)(row / pad_rows), local_row = (int)(row - (size_t)rank * pad_rows);
+    const int k = local_row / tile_rows;
+    const long long t = shard_tile<long long>(rank, n_ranks, deal, k);
+    const long long y = t * tile_rows + (local_row - k * tile_rows);
+    if (y < height) full[(size_t)y * row_floats + c] = gathered[i];
 }
 
 // Per device-list state that outlives a call: streams, communicators (ncclCommInitAll costs ~100 ms), buffers.
@@ -175,6 +171,48 @@ static int ensure(float *&buf, size_t &have, size_t want) {
     return RT_OK;
 }
 
+// the frame cut into n_ranks shards with `deal` (rt_opts.tile_rotate; negative: an error of rt_shard_deal): shard[r] = base with
+// tile_first = r, and pad_rows = the rows of the largest shard (every rank's buffer is padded to it: the gather is uniform)
+static int cut_shards(const rt_scene *sc, const rt_opts &base, int n_ranks, int deal, std::vector<rt_opts> &shard,
+                      int &pad_rows) {
+    if (deal < 0) return -deal;
+    shard.assign(n_ranks, base);
+    pad_rows = 0;
+    for (int r = 0; r < n_ranks; ++r) {
+        shard[r].tile_first = r, shard[r].tile_stride = n_ranks, shard[r].tile_rotate = deal;
+        const int rows = rt_shard_rows(sc, &shard[r]);
+        if (rows < 0) return -rows;
+        pad_rows = std::max(pad_rows, rows);
+    }
+    return RT_OK;
+}
+
+// gathered[n_ranks][pad_rows][W][3], the shards `deal` cuts  ->  full[H][W][3], on `stream`
+static int place_rows(const rt_scene *sc, int tile_rows, int n_ranks, int deal, int pad_rows, const float *gathered,
+                      float *full, hipStream_t stream) {
+    if (deal < 0 || deal > 2) {
+        set_error("rt_shard_place_rows_device: tile_rotate %d", deal);
+        return RT_ERR_ARG;
+    }
+    rt_opts base;
+    rt_opts_default(&base);
+    base.tile_rows = tile_rows;
+    std::vector<rt_opts> shard;
+    int worst = 0;
+    if (int rc = cut_shards(sc, base, n_ranks, deal, shard, worst)) return rc;
+    if (pad_rows < worst) {
+        set_error("rt_shard_place_rows_device: pad_rows %d is smaller than the largest shard (%d rows)", pad_rows, worst);
+        return RT_ERR_ARG;
+    }
+    const int row_floats = sc->s.width * 3;
+    const size_t total = (size_t)n_ranks * pad_rows * row_floats;
+    if (!total) return RT_OK;
+    hipLaunchKernelGGL(place_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, gathered, full,
+                       sc->s.height, row_floats, tile_rows, n_ranks, pad_rows, deal);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
 }  // namespace rtmi
 
 using namespace rtmi;
@@ -226,18 +264,11 @@ extern "C" int rt_render_hip_tiles(const rt_scene *sc, const rt_opts *o, const i
     TileGroup *g = gp.get();
     std::lock_guard<std::mutex> frame(g->mu);
     const int N = n_devices;
-    // shard geometry: rank r owns row tiles r, r + N, ...; buffers padded to the largest shard (the gather is uniform)
-    std::vector<rt_opts> shard(N, base);
+    std::vector<rt_opts> shard;
     int pad_rows = 0;
-    for (int r = 0; r < N; ++r) {
-        shard[r].device = devs[r];
-        shard[r].tile_first = r;
-        shard[r].tile_stride = N;
-        shard[r].tile_rotate = rt_shard_deal(sc, &base, N);
-        const int rows = rt_shard_rows(sc, &shard[r]);
-        if (rows < 0) return -rows;
-        pad_rows = std::max(pad_rows, rows);
-    }
+    const int deal = rt_shard_deal(sc, &base, N);
+    if (int rc = cut_shards(sc, base, N, deal, shard, pad_rows)) return rc;
+    for (int r = 0; r < N; ++r) shard[r].device = devs[r];
     const size_t local_floats = (size_t)pad_rows * row_floats;
 
     // ---- per-device state.  A failure anywhere in the set-up releases the whole group: the next call starts over.
@@ -314,12 +345,9 @@ extern "C" int rt_render_hip_tiles(const rt_scene *sc, const rt_opts *o, const i
     NCCL_TRY(api, api->GroupEnd());
     // ---- rows to their image positions, frame to the caller
     HIP_TRY(hipSetDevice(devs[0]));
+    rc = place_rows(sc, base.tile_rows, N, deal, pad_rows, g->gathered, g->full, g->streams[0]);
+    if (rc) return rc;
     const size_t total = (size_t)H * row_floats;
-    if (total) {
-        hipLaunchKernelGGL(place_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, g->streams[0], g->gathered,
-                           g->full, H, (int)row_floats, base.tile_rows, N, pad_rows, N > 1 ? 1 : 0);
-        HIP_TRY(hipGetLastError());
-    }
     HIP_TRY(hipEventRecord(g->ev_done, g->streams[0]));
     HIP_TRY(hipMemcpyAsync(rgb_sum, g->full, total * sizeof(float), hipMemcpyDeviceToHost, g->streams[0]));
     for (int r = 0; r < N; ++r) {
@@ -362,35 +390,8 @@ extern "C" int rt_shard_place_rows_device(const rt_scene *sc, const rt_opts *o, 
         return RT_ERR_ARG;
     }
     const int tile_rows = (o && o->tile_rows > 0) ? o->tile_rows : 8;
-    const int rotate = (o && n_ranks > 1) ? o->tile_rotate : 0;  // how the ranks' shards were cut (rt_opts.tile_rotate)
-    if (rotate < 0 || rotate > 2) {
-        set_error("rt_shard_place_rows_device: tile_rotate %d", rotate);
-        return RT_ERR_ARG;
-    }
-    const int W = sc->s.width, H = sc->s.height;
-    const int tiles = (H + tile_rows - 1) / tile_rows;
-    const int need = ((tiles + n_ranks - 1) / n_ranks) * tile_rows;  // rows of the largest shard, rounded up to whole tiles
-    if (pad_rows < std::min(need, H)) {
-        // the exact requirement is max over ranks of rt_shard_rows(); `need` over-estimates it by < tile_rows
-        rt_opts probe;
-        rt_opts_default(&probe);
-        probe.tile_rows = tile_rows, probe.tile_stride = n_ranks, probe.tile_rotate = rotate;
-        int worst = 0;
-        for (int r = 0; r < n_ranks; ++r) {
-            probe.tile_first = r;
-            worst = std::max(worst, rt_shard_rows(sc, &probe));
-        }
-        if (pad_rows < worst) {
-            set_error("rt_shard_place_rows_device: pad_rows %d is smaller than the largest shard (%d rows)", pad_rows, worst);
-            return RT_ERR_ARG;
-        }
-    }
-    const size_t total = (size_t)H * W * 3;
-    if (!total) return RT_OK;
-    hipLaunchKernelGGL(place_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const float *)d_gathered, (float *)d_full, H, W * 3, tile_rows, n_ranks, pad_rows, rotate);
-    HIP_TRY(hipGetLastError());
-    return RT_OK;
+    const int deal = (o && n_ranks > 1) ? o->tile_rotate : 0;  // how the ranks' shards were cut (rt_opts.tile_rotate)
+    return place_rows(sc, tile_rows, n_ranks, deal, pad_rows, (const float *)d_gathered, (float *)d_full, (hipStream_t)stream);
 }
 
 // release the streams, communicators and buffers rt_render_hip_tiles keeps between calls (a group with a frame in flight

@@ -2,9 +2,9 @@
 
 The reference's only multi-GPU mechanism is one renderer PROCESS per GPU per animation
 frame (gpu-version/blue.py:23-32, CUDA_VISIBLE_DEVICES=k); nothing is exchanged.  Here one
-frame is split: row tile t (tile_rows full-width rows) belongs to rank (t + t // world) mod world
-(an interleave whose phase rotates from one group of `world` tiles to the next), so sky rows and
-ground rows are spread evenly and no rank keeps one row phase of the image; pixels are independent and the RNG is keyed
+frame is split: its row tiles (tile_rows full-width rows) are dealt out to the ranks as
+rt_opts.tile_rotate says (include/rtmi.h; rt_shard_deal picks the deal rt_render_hip_tiles uses),
+and the library computes which rows a rank owns; pixels are independent and the RNG is keyed
 by the GLOBAL pixel id, so the assembled image is bit-identical for every world size.
 The only communication is ONE gather of the rank-local row buffers to the root
 (torch.distributed.gather -> ncclGather over xGMI with the nccl (= RCCL) backend, gloo in
@@ -19,10 +19,9 @@ import torch.distributed as dist
 from . import Opts
 
 
-def shard_opts(base: Opts, rank: int, world: int, deal: int | None = None) -> Opts:
-    """rt_opts of one rank: its share of the frame's row tiles.  `deal` = rt_opts.tile_rotate (include/rtmi.h: 0 plain
-    interleave, 1 rotated, 2 there and back); None keeps base.tile_rotate when it is set, else the rotated interleave --
-    callers that know the scene pass scene.shard_deal(base, world), what rt_render_hip_tiles uses."""
+def shard_opts(base: Opts, rank: int, world: int) -> Opts:
+    """rt_opts of one rank: its share of the frame's row tiles, dealt as base.tile_rotate says (callers set it to
+    scene.shard_deal(base, world), the deal rt_render_hip_tiles uses)."""
     o = Opts()
     for name, _ in Opts._fields_:
         setattr(o, name, getattr(base, name))
@@ -30,10 +29,6 @@ def shard_opts(base: Opts, rank: int, world: int, deal: int | None = None) -> Op
     o.tile_stride = world
     if world <= 1:
         o.tile_rotate = 0
-    elif deal is not None:
-        o.tile_rotate = deal
-    elif not base.tile_rotate:
-        o.tile_rotate = 1
     return o
 
 
@@ -54,7 +49,7 @@ def gather_framebuffer(local: torch.Tensor, scene, base: Opts, rank: int, world:
     if world == 1:
         full = out if out is not None else torch.empty((scene.height, scene.width, 3), dtype=local.dtype,
                                                        device=local.device)
-        rows = _rows_on(scene, base, 0, 1, local.device)
+        _, rows = _gather_indices(scene, base, 1, scene.height, local.device)
         full.index_copy_(0, rows, local[: len(rows)])
         return full
     send = local.cpu() if via_host else local
@@ -127,7 +122,9 @@ _INDEX_CACHE: dict = {}
 
 
 def _gather_indices(scene, base: Opts, world: int, padded_rows: int, device):
-    key = (id(scene), scene.height, base.tile_rows, world, padded_rows, str(device))
+    """(rows of the receive buffer [world][padded_rows] that hold shard rows, their image rows) as tensors on `device`.
+    Cached (the gather runs every step) under what they depend on: not the scene, only its height."""
+    key = (scene.height, base.tile_rows, world, base.tile_rotate, padded_rows, str(device))
     t = _INDEX_CACHE.get(key)
     if t is None:
         src, dst_rows = [], []
@@ -137,19 +134,6 @@ def _gather_indices(scene, base: Opts, world: int, padded_rows: int, device):
             dst_rows.append(np.asarray(rows, dtype=np.int64))
         t = (torch.as_tensor(np.concatenate(src), device=device), torch.as_tensor(np.concatenate(dst_rows), device=device))
         _INDEX_CACHE[key] = t
-    return t
-
-
-_ROWS_CACHE: dict = {}
-
-
-def _rows_on(scene, base: Opts, r: int, world: int, device) -> torch.Tensor:
-    """Global row indices of rank r's shard as a tensor on `device` (cached: the gather runs every step)."""
-    key = (id(scene), scene.height, base.tile_rows, r, world, str(device))
-    t = _ROWS_CACHE.get(key)
-    if t is None:
-        t = torch.as_tensor(scene.shard_global_rows(shard_opts(base, r, world)), device=device)
-        _ROWS_CACHE[key] = t
     return t
 
 

@@ -4,6 +4,8 @@
 * ``oracle/_ref/libref_cpu.so`` -- the reference's own cmake-cpu-version sources compiled
   with a hooked rand() (ref_harness.cpp); spheres + lambertian/metal/dielectric only.
 
+and tile_owner(), the tests' one restatement of how a frame's row tiles are dealt out to shards.
+
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg import this.
 """
 from __future__ import annotations
@@ -302,3 +304,15 @@ def ref_write_color(rgb_sum, spp):
     out = (C.c_int * 3)()
     ref_lib().ref_write_color(_d3(rgb_sum), spp, out)
     return list(out)
+
+
+def tile_owner(t, world, deal):
+    """Rank that owns row tile t (an int or an array) when a frame's tiles are dealt out to `world` ranks with
+    rt_opts.tile_rotate = deal, restated from include/rtmi.h: 0 plain interleave, 1 rotated, 2 there and back."""
+    t = np.asarray(t)
+    if deal == 1:
+        return (t + t // world) % world
+    if deal == 2:
+        p = t % (2 * world)
+        return np.where(p < world, p, 2 * world - 1 - p)
+    return t % world

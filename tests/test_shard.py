@@ -6,6 +6,7 @@ import pytest
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
+from rtcheck import tile_owner
 
 
 def test_shard_geometry(rtmi, scenes_dir):
@@ -19,20 +20,21 @@ def test_shard_geometry(rtmi, scenes_dir):
         for r in range(world):
             rows = sc.shard_global_rows(rtmi.Opts(tile_first=r, tile_stride=world))
             # tile t -> rank t mod world, rows of a tile stay together and ascending
-            assert all(((y // 8) % world) == r for y in rows)
+            assert (tile_owner(np.asarray(rows) // 8, world, 0) == r).all()
             assert list(rows) == sorted(rows)
             allrows += list(rows)
         assert sorted(allrows) == list(range(45))
         seen.append(world)
-    # the rotated interleave (rt_opts.tile_rotate: what rt_render_hip_tiles and bench.py use): tile t -> rank (t + t // world)
-    # mod world -- one tile of every group of `world` tiles per rank, a different one from group to group
+    # the rotated interleave (rt_opts.tile_rotate = 1; what rt_render_hip_tiles and bench.py use for frames of >= 4 N^2
+    # tiles): tile t -> rank (t + t // world) mod world -- one tile of every group of `world` tiles per rank, a different one
+    # from group to group
     for world in (2, 3, 4, 8):
         allrows, counts = [], []
         for r in range(world):
             o = rtmi.Opts(tile_first=r, tile_stride=world, tile_rotate=1)
             rows = sc.shard_global_rows(o)
             t = np.asarray(rows) // 8
-            assert np.array_equal((t + t // world) % world, np.full(len(rows), r))
+            assert np.array_equal(tile_owner(t, world, 1), np.full(len(rows), r))
             assert list(rows) == sorted(rows) and sc.shard_rows(o) == len(rows)
             if len(set(t)) > 1:
                 assert len(set(t % world)) > 1                      # not one row phase for itself
@@ -46,8 +48,7 @@ def test_shard_geometry(rtmi, scenes_dir):
             o = rtmi.Opts(tile_first=r, tile_stride=world, tile_rotate=2)
             rows = sc.shard_global_rows(o)
             t = np.asarray(rows) // 8
-            p = t % (2 * world)
-            assert np.array_equal(np.where(p < world, p, 2 * world - 1 - p), np.full(len(rows), r))
+            assert np.array_equal(tile_owner(t, world, 2), np.full(len(rows), r))
             assert list(rows) == sorted(rows) and sc.shard_rows(o) == len(rows)
             allrows += list(rows)
             counts.append(len(set(t)))
@@ -67,6 +68,27 @@ def test_shard_geometry(rtmi, scenes_dir):
     assert sc.shard_rows(rtmi.Opts(tile_rows=32, tile_first=5, tile_stride=8)) == 0
     with pytest.raises(rtmi.RtmiError):
         sc.shard_rows(rtmi.Opts(tile_first=3, tile_stride=2))
+
+
+@pytest.mark.parametrize("world", range(2, 9))
+def test_shard_deal_partitions_the_frame(rtmi, scenes_dir, world):
+    """rt_shard_deal on either side of its threshold (4 N^2 tiles of 8 rows; each side once with a ragged last tile): the deal
+    it picks, and for that deal the ranks' rows partition the frame, ascend within a rank, and lie on the tiles tile_owner
+    gives the rank."""
+    edge = 4 * world * world
+    for tiles, short in ((edge - 1, 0), (edge - 1, 3), (edge, 0), (edge, 5)):
+        h = tiles * 8 - short
+        sc = rtmi.Scene.load(os.path.join(scenes_dir, "three_sphere.json"))
+        sc.override(width=8, height=h, spp=1)
+        deal = sc.shard_deal(rtmi.Opts(tile_rows=8), world)
+        assert deal == (1 if tiles >= edge else 2)
+        allrows = []
+        for r in range(world):
+            rows = sc.shard_global_rows(rtmi.Opts(tile_rows=8, tile_first=r, tile_stride=world, tile_rotate=deal))
+            assert (np.diff(rows) > 0).all()
+            assert (tile_owner(rows // 8, world, deal) == r).all()
+            allrows.append(rows)
+        assert np.array_equal(np.sort(np.concatenate(allrows)), np.arange(h))
 
 
 def test_host_scatter_rows(rtmi, scenes_dir):
@@ -97,34 +119,30 @@ def _worker(rank, world, port, height, tile_rows, q):
     try:
         sc = rtmi.Scene.load(os.path.join(root, "ray-tracing-in-cuda_amd", "scenes", "three_sphere.json"))
         sc.override(width=24, height=height, spp=2)
-        base = rtmi.Opts(seed=11, tile_rows=tile_rows)
-        mine = rdist.shard_opts(base, rank, world)
         # stand-in for the GPU render of this rank's rows (CPU test): the checker's image rows
         full_ref, _ = rtcheck.oracle_render(sc, seed=11, threads=1)
-        local = rdist.alloc_local(sc, base, world, "cpu")
-        rows = sc.shard_global_rows(mine)
-        local[: len(rows)] = torch.from_numpy(full_ref[rows])
-        full = rdist.gather_framebuffer(local, sc, base, rank, world)
+        frames = [full_ref, full_ref * 2.0 + 1.0]
         ok = True
-        if rank == 0:
-            ok = bool(np.array_equal(full.numpy(), full_ref))
-        else:
-            assert full is None
-        # the two-phase form bench.py pipelines (a frame's gather travels while the next frame renders): two frames in
-        # flight in two local buffers and two receive slots, placed in order; every deal of the tiles (rt_opts.tile_rotate)
+        # every deal of the tiles (rt_opts.tile_rotate), one after the other on the same scene
         for deal in (0, 1, 2):
-            b2 = rdist.shard_opts(base, 0, 1)
-            b2.tile_rotate = deal
-            m2 = rdist.shard_opts(b2, rank, world)
-            rows2 = sc.shard_global_rows(m2)
-            bufs = [rdist.alloc_local(sc, b2, world, "cpu") for _ in range(2)]
-            frames = [full_ref, full_ref * 2.0 + 1.0]
+            base = rtmi.Opts(seed=11, tile_rows=tile_rows, tile_rotate=deal)
+            rows = sc.shard_global_rows(rdist.shard_opts(base, rank, world))
+            local = rdist.alloc_local(sc, base, world, "cpu")
+            local[: len(rows)] = torch.from_numpy(full_ref[rows])
+            full = rdist.gather_framebuffer(local, sc, base, rank, world)
+            if rank == 0:
+                ok = ok and bool(np.array_equal(full.numpy(), full_ref))
+            else:
+                assert full is None
+            # the two-phase form bench.py pipelines (a frame's gather travels while the next frame renders): two frames in
+            # flight in two local buffers and two receive slots, placed in order
+            bufs = [rdist.alloc_local(sc, base, world, "cpu") for _ in range(2)]
             pend = []
             for i in range(2):
-                bufs[i][: len(rows2)] = torch.from_numpy(frames[i][rows2])
+                bufs[i][: len(rows)] = torch.from_numpy(frames[i][rows])
                 pend.append(rdist.gather_begin(bufs[i], rank, world, slot=i))
             for i in range(2):
-                got = rdist.gather_end(pend[i], sc, b2, rank, world, bufs[i].shape[0], "cpu")
+                got = rdist.gather_end(pend[i], sc, base, rank, world, bufs[i].shape[0], "cpu")
                 if rank == 0:
                     ok = ok and bool(np.array_equal(got.numpy(), frames[i]))
                 else:
@@ -135,18 +153,28 @@ def _worker(rank, world, port, height, tile_rows, q):
         dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("height,tile_rows", [(32, 8), (29, 8), (20, 4)])
-def test_gather_world2_gloo(height, tile_rows):
+def _gather_gloo(world, height, tile_rows):
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = 29500 + (os.getpid() + height + tile_rows) % 2000
-    procs = [ctx.Process(target=_worker, args=(r, 2, port, height, tile_rows, q)) for r in range(2)]
+    procs = [ctx.Process(target=_worker, args=(r, world, port, height, tile_rows, q)) for r in range(world)]
     for p in procs:
         p.start()
     for p in procs:
         p.join(120)
         assert p.exitcode == 0
     assert q.get(timeout=5) is True
+
+
+@pytest.mark.parametrize("height,tile_rows", [(32, 8), (29, 8), (20, 4)])
+def test_gather_world2_gloo(height, tile_rows):
+    _gather_gloo(2, height, tile_rows)
+
+
+def test_gather_world3_gloo():
+    """6 tiles of 8 rows (the last one 5), which deals 0, 1 and 2 give to the 3 ranks in three different ways (at world 2
+    deals 1 and 2 coincide)."""
+    _gather_gloo(3, 45, 8)
 
 
 def test_gather_world1_no_comm(rtmi, scenes_dir):

@@ -1,9 +1,10 @@
-"""rt_render_hip_tiles: one frame on several GPUs behind the C ABI (row tiles interleaved over the devices, ONE
-ncclGather to the first, a placement kernel there).  A test box has one GPU: the n = 1 call runs the whole path
+"""rt_render_hip_tiles: one frame on several GPUs behind the C ABI (row tiles dealt out to the devices as rt_shard_deal
+picks, ONE ncclGather to the first, a placement kernel there).  A test box has one GPU: the n = 1 call runs the whole path
 -- per-device stream, ncclCommInitAll, ncclGather, placement kernel -- and the N > 1 row placement is checked by
 laying N shards out the way the gather delivers them."""
 import numpy as np
 import pytest
+from rtcheck import tile_owner
 
 SEED = 2023
 
@@ -46,47 +47,58 @@ def test_tiles_argument_errors(rtmi):
             sc.render_tiles([0, 0])
 
 
-def _owner(t, world, rotate):
-    """rank of row tile t (include/rtmi.h, rt_opts.tile_rotate)"""
-    if rotate == 1:
-        return (t + t // world) % world
-    if rotate == 2:
-        p = t % (2 * world)
-        return np.where(p < world, p, 2 * world - 1 - p)
-    return t % world
+def _gathered_and_placed(rtmi, sc, world, tile_rows, deal):
+    """The shards of `deal` rendered on one device into [rank][pad_rows][W][3] (as the gather delivers them; NaN padding),
+    then placed by rt_shard_place_rows_device into a frame [H][W][3].  Returns (gathered, pad_rows, frame), on the device."""
+    import torch
+    shards = [rtmi.Opts(seed=SEED, tile_rows=tile_rows, tile_first=r, tile_stride=world, tile_rotate=deal)
+              for r in range(world)]
+    pad = max(sc.shard_rows(o) for o in shards)
+    gathered = torch.full((world, pad, sc.width, 3), float("nan"), dtype=torch.float32, device="cuda:0")
+    for r, o in enumerate(shards):
+        if sc.shard_rows(o):
+            sc.render_device(o, gathered[r].data_ptr(), torch.cuda.current_stream().cuda_stream)
+    full = torch.empty((sc.height, sc.width, 3), dtype=torch.float32, device="cuda:0")
+    sc.place_rows_device(rtmi.Opts(tile_rows=tile_rows, tile_rotate=deal), world, pad, gathered.data_ptr(), full.data_ptr(),
+                         torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    return gathered, pad, full
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("rotate", [2, 1, 0])
 @pytest.mark.parametrize("world,tile_rows,h", [(2, 8, 54), (3, 8, 45), (8, 8, 1080 // 4), (5, 16, 77), (8, 4, 30)])
 def test_gathered_layout_placement_kernel(rtmi, world, tile_rows, h, rotate):
-    """What the root does after the gather, for N > 1: shards laid out [rank][pad_rows][W][3] -> the frame.  rotate = 1 is
-    the split rt_render_hip_tiles and bench.py use (rt_opts.tile_rotate: tile t belongs to shard (t + t // N) mod N)."""
-    import torch
+    """What the root does after the gather, for N > 1: shards laid out [rank][pad_rows][W][3] -> the frame, for every deal
+    of the tiles (rt_opts.tile_rotate; tile_owner restates which shard owns tile t)."""
     sc = rtmi.Scene.rtiow(7, 120, h, 2, 50)
     want = sc.render(rtmi.Opts(seed=SEED))
-    shards = [rtmi.Opts(seed=SEED, tile_rows=tile_rows, tile_first=r, tile_stride=world, tile_rotate=rotate) for r in range(world)]
     owners = np.full(h, -1)
-    for r, o in enumerate(shards):  # every row belongs to exactly one shard; tile t to shard (t + t // N) % N or t % N
-        rows = sc.shard_global_rows(o)
+    for r in range(world):  # every row belongs to exactly one shard, the one tile_owner names
+        rows = sc.shard_global_rows(rtmi.Opts(tile_rows=tile_rows, tile_first=r, tile_stride=world, tile_rotate=rotate))
         assert (owners[rows] == -1).all()
         owners[rows] = r
-        t = np.asarray(rows) // tile_rows
-        assert np.array_equal(_owner(t, world, rotate), np.full(len(rows), r))
+        assert np.array_equal(tile_owner(np.asarray(rows) // tile_rows, world, rotate), np.full(len(rows), r))
     assert (owners >= 0).all()
-    pad = max(sc.shard_rows(o) for o in shards)
-    gathered = torch.full((world, pad, 120, 3), float("nan"), dtype=torch.float32, device="cuda:0")
-    for r, o in enumerate(shards):
-        rows = sc.shard_rows(o)
-        if rows:
-            sc.render_device(o, gathered[r].data_ptr(), torch.cuda.current_stream().cuda_stream)
-    full = torch.empty((h, 120, 3), dtype=torch.float32, device="cuda:0")
-    sc.place_rows_device(rtmi.Opts(tile_rows=tile_rows, tile_rotate=rotate), world, pad, gathered.data_ptr(), full.data_ptr(),
-                         torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
+    gathered, pad, full = _gathered_and_placed(rtmi, sc, world, tile_rows, rotate)
     assert np.array_equal(full.cpu().numpy(), want)
     with pytest.raises(rtmi.RtmiError, match="pad_rows"):
-        sc.place_rows_device(rtmi.Opts(tile_rows=tile_rows, tile_rotate=rotate), world, pad - 1, gathered.data_ptr(), full.data_ptr(), 0)
+        sc.place_rows_device(rtmi.Opts(tile_rows=tile_rows, tile_rotate=rotate), world, pad - 1, gathered.data_ptr(),
+                             full.data_ptr(), 0)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("world,h", [(2, 117), (2, 120), (2, 125), (2, 128), (3, 280), (3, 288), (8, 1080), (8, 2040),
+                                     (8, 2048)])
+def test_tiles_recipe_on_one_device(rtmi, world, h):
+    """rt_render_hip_tiles's recipe for N devices, on one: cut with the deal rt_shard_deal picks (either side of its
+    threshold of 4 N^2 tiles; 1080 rows on 8: 135 tiles, there and back), render every shard, place them with that same
+    deal -> the unsharded frame, bit for bit."""
+    sc = rtmi.Scene.rtiow(7, 16, h, 2, 50)
+    deal = sc.shard_deal(rtmi.Opts(tile_rows=8), world)
+    assert deal == (1 if -(-h // 8) >= 4 * world * world else 2)
+    _, _, full = _gathered_and_placed(rtmi, sc, world, 8, deal)
+    assert np.array_equal(full.cpu().numpy(), sc.render(rtmi.Opts(seed=SEED)))
 
 
 @pytest.mark.gpu
