@@ -166,6 +166,29 @@ int rt_scene_set_background(rt_scene *s, const float rgb[3], uint32_t flags);
  * consumes, so images differ from p = 0 by noise, not bit for bit.  p = 0 (default) switches it off;
  * JSON: top-level "russian_roulette": p. */
 int rt_scene_set_russian_roulette(rt_scene *s, float p);
+/* Light sampling (next-event estimation): every lambertian vertex and every metal vertex with fuzz >= 0.05 whose
+ * continuation is traced also samples one emitter -- chosen in proportion to its power (area x mean emission luminance)
+ * -- and checks its visibility with a shadow ray; the light sample and the BSDF sample are combined by multiple
+ * importance sampling (power heuristic).  Sampled emitters: spheres (uniform in the cone they subtend), axis-aligned
+ * rects and cylinder tubes with a rigid transform (uniform by area) whose material is a diffuse_light with a solid or
+ * checker texture (rt_scene_get_lights lists them); every other emitter is still reached by the BSDF sample alone.
+ * Unbiased against on = 0 at the same max_depth and russian_roulette, with far less noise in scenes lit by small emitters;
+ * images differ from on = 0 by noise, not bit for bit.  A scene with light sampling on and at least one sampled emitter
+ * renders through the light-sampling kernels (rt_opts.variant 0, 16, 36 or 44; rt_stats.kernel_variant reports the
+ * layout | 256); other variants and rt_render_hip_count refuse it.  on = 0 (default) switches it off; JSON: top-level
+ * "light_sampling": true. */
+int rt_scene_set_light_sampling(rt_scene *s, int on);
+int rt_scene_get_light_sampling(const rt_scene *s); /* 1, 0, or -rt_status */
+typedef struct rt_light {
+    int32_t prim;        /* index into the primitive list                      */
+    int32_t shape;       /* rt_prim_type: sphere, xy / xz / yz rect or cylinder */
+    float probability;   /* selection probability (the list sums to 1)         */
+    float area;          /* surface area (the cylinder's tube)                 */
+    float emission[3];   /* emission (a checker texture: its even colour)      */
+    float emission_odd[3]; /* a checker texture's odd colour (else = emission) */
+} rt_light;
+/* the emitters light sampling samples, in list order (whether or not it is on) -> count, or -rt_status */
+int rt_scene_get_lights(const rt_scene *s, rt_light *out, int cap);
 /* camera(lookfrom, lookat, vup, vfov, aspect, aperture, focus_dist) camera.cuh:9-15;
  * aspect <= 0 -> width/height, focus_dist <= 0 -> |lookfrom-lookat| (parser.hpp:122-124) */
 int rt_scene_set_camera(rt_scene *s, const float lookfrom[3], const float lookat[3],

@@ -240,6 +240,8 @@ public:
     }
     // Russian roulette (4_0_path_tracing.py's p_RR): survival probability per bounce, 0 = off
     void set_russian_roulette(float p) { check(rt_scene_set_russian_roulette(s_, p), "set_russian_roulette"); }
+    // light sampling: next-event estimation + MIS at lambertian and fuzzy-metal vertices (rt_scene_set_light_sampling)
+    void set_light_sampling(bool on) { check(rt_scene_set_light_sampling(s_, on ? 1 : 0), "set_light_sampling"); }
     // progressive rendering: adds samples [first, first + count) to the caller's exact pixel sums
     // (resized and zeroed when empty) and returns the framebuffer of the updated sums
     std::vector<float> accumulate(std::vector<int64_t> &acc, int first, int count, const rt_opts *opts = nullptr,

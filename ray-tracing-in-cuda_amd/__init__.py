@@ -50,6 +50,10 @@ MATERIAL_DTYPE = np.dtype(
     [("type", "<i4"), ("texture", "<i4"), ("albedo", "<f4", (3,)), ("fuzz", "<f4"), ("ir", "<f4")]
 )
 TEXTURE_DTYPE = np.dtype([("type", "<i4"), ("c0", "<f4", (3,)), ("c1", "<f4", (3,))])
+LIGHT_DTYPE = np.dtype(
+    [("prim", "<i4"), ("shape", "<i4"), ("probability", "<f4"), ("area", "<f4"), ("emission", "<f4", (3,)),
+     ("emission_odd", "<f4", (3,))]
+)
 
 
 class RtmiError(RuntimeError):
@@ -190,6 +194,9 @@ _sig("rt_render_hip_tiles", C.c_int, _p, C.POINTER(Opts), C.POINTER(C.c_int), C.
 _sig("rt_tiles_shutdown", None)
 _sig("rt_shard_place_rows_device", C.c_int, _p, C.POINTER(Opts), C.c_int, C.c_int, _p, _p, _p)
 _sig("rt_scene_set_russian_roulette", C.c_int, _p, C.c_float)
+_sig("rt_scene_set_light_sampling", C.c_int, _p, C.c_int)
+_sig("rt_scene_get_light_sampling", C.c_int, _p)
+_sig("rt_scene_get_lights", C.c_int, _p, _p, C.c_int)
 _sig("rt_render_hip_count", C.c_int, _p, C.POINTER(Opts), _p, C.POINTER(Stats))
 _sig("rt_scene_table_info", C.c_int, _p, C.POINTER(TableInfo))
 _sig("rt_scene_table_image", C.c_int, _p, _p, C.c_int)
@@ -219,6 +226,7 @@ C_SYMBOLS = [
     "rt_acc_to_rgb", "rt_shard_scatter_rows", "rt_write_ppm",
     "rt_quantize_rgb8", "rt_philox4x32_10", "rt_aabb_hit", "rt_sample_stream", "rt_write_png",
     "rt_scene_output_file", "rt_scene_rotate_cylinders", "rt_scene_set_output_file", "rt_scene_dna", "rt_scene_clone",
+    "rt_scene_set_light_sampling", "rt_scene_get_light_sampling", "rt_scene_get_lights",
 ]
 
 
@@ -288,6 +296,14 @@ class Scene:
     def set_russian_roulette(self, p: float):
         """Survival probability per bounce (4_0_path_tracing.py's p_RR); 0 switches it off."""
         _check(_lib.rt_scene_set_russian_roulette(self._h, float(p)), "set_russian_roulette")
+
+    def set_light_sampling(self, on: bool = True):
+        """Next-event estimation with MIS (include/rtmi.h, rt_scene_set_light_sampling); False switches it off."""
+        _check(_lib.rt_scene_set_light_sampling(self._h, 1 if on else 0), "set_light_sampling")
+
+    @property
+    def light_sampling(self) -> bool:
+        return _check_id(_lib.rt_scene_get_light_sampling(self._h), "get_light_sampling") != 0
 
     def camera(self, lookfrom, lookat, vup, vfov, aspect_ratio=0.0, aperture=0.0, focus_dist=0.0):
         _check(_lib.rt_scene_set_camera(self._h, _v3(lookfrom), _v3(lookat), _v3(vup), vfov, aspect_ratio,
@@ -426,6 +442,10 @@ class Scene:
 
     def textures(self) -> np.ndarray:
         return self._table(_lib.rt_scene_get_textures, TEXTURE_DTYPE)
+
+    def lights(self) -> np.ndarray:
+        """The emitters light sampling samples (LIGHT_DTYPE records), whether or not it is switched on."""
+        return self._table(_lib.rt_scene_get_lights, LIGHT_DTYPE)
 
     @property
     def output_file(self) -> str:

@@ -148,6 +148,30 @@ rt_scene *rt_scene_new(int width, int height, int spp, int max_depth) {
     return s;
 }
 
+int rt_scene_set_light_sampling(rt_scene *s, int on) {
+    if (bad_scene(s, "rt_scene_set_light_sampling")) return RT_ERR_ARG;
+    s->s.light_sampling = on != 0;
+    s->s.touch();
+    return RT_OK;
+}
+
+int rt_scene_get_light_sampling(const rt_scene *s) {
+    if (bad_scene(s, "rt_scene_get_light_sampling")) return -RT_ERR_ARG;
+    return s->s.light_sampling ? 1 : 0;
+}
+
+int rt_scene_get_lights(const rt_scene *s, rt_light *out, int cap) {
+    if (bad_scene(s, "rt_scene_get_lights")) return -RT_ERR_ARG;
+    const std::vector<SceneLight> lights = scene_lights(s->s);
+    for (int i = 0; out && i < cap && i < (int)lights.size(); ++i) {
+        const SceneLight &l = lights[(size_t)i];
+        rt_light &o = out[i];
+        o.prim = l.prim, o.shape = l.type, o.probability = (float)l.prob, o.area = (float)l.area;
+        for (int c = 0; c < 3; ++c) o.emission[c] = l.even[c], o.emission_odd[c] = l.odd[c];
+    }
+    return (int)lights.size();
+}
+
 int rt_scene_set_russian_roulette(rt_scene *s, float p) {
     if (bad_scene(s, "rt_scene_set_russian_roulette")) return RT_ERR_ARG;
     if (!(p >= 0.0f && p <= 1.0f)) {

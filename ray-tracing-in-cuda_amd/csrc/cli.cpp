@@ -40,7 +40,7 @@ static int usage(const char *argv0) {
     fprintf(stderr,
             "usage: %s [-f scene.json | --rtiow] [-w W] [-h H] [-d DEPTH] [-spp N] [-o out.ppm]\n"
             "          [--seed S] [--scene-seed S] [--device N] [--chunk N] [--dump-json file] [--count] [--no-png]\n"
-            "          [--acc-in sums.bin] [--acc-out sums.bin] [--spp-begin FIRST] [--rr SURVIVAL_PROBABILITY]\n"
+            "          [--acc-in sums.bin] [--acc-out sums.bin] [--spp-begin FIRST] [--rr SURVIVAL_PROBABILITY] [--nee]\n"
             "          [--gpus N] [--tile-rows R]\n",
             argv0);
     return 2;
@@ -52,6 +52,7 @@ int main(int argc, char **argv) {
     std::string dump_json, acc_in, acc_out;
     long long spp_begin = -1;
     double rr = -1.0;  // Russian roulette: keep the scene file's setting
+    bool nee = false;  // light sampling: on if the scene file or --nee says so
     bool rtiow = false, have_file = false, count = false, no_png = false;
     int w = 0, h = 0, depth = 0, spp = 0, device = 0, chunk = 0, gpus = 0, tile_rows = 0;
     unsigned long long seed = 2023;
@@ -81,6 +82,7 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--acc-out")) acc_out = need("--acc-out");
         else if (!strcmp(argv[i], "--spp-begin")) spp_begin = atoll(need("--spp-begin"));
         else if (!strcmp(argv[i], "--rr")) rr = atof(need("--rr"));
+        else if (!strcmp(argv[i], "--nee")) nee = true;
         else if (!strcmp(argv[i], "--rtiow")) rtiow = true;
         else if (!strcmp(argv[i], "--count")) count = true;
         else if (!strcmp(argv[i], "--no-png")) no_png = true;
@@ -100,6 +102,10 @@ int main(int argc, char **argv) {
         return 1;
     }
     if (rt_scene_override(sc, w, h, spp, depth) != RT_OK) {
+        fprintf(stderr, "rtmi: %s\n", rt_last_error());
+        return 1;
+    }
+    if (nee && rt_scene_set_light_sampling(sc, 1) != RT_OK) {
         fprintf(stderr, "rtmi: %s\n", rt_last_error());
         return 1;
     }

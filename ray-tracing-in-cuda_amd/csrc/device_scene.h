@@ -17,6 +17,13 @@
 //     tri     [nt]  2 x float4   {material(bits), list index(bits), u1.x, u1.y} {u2.x, u2.y, u3.x, u3.y}
 //     mat     [nm]  3 x float4   {kind(bits), p0, p1, p2} {c0.xyz, p3} {c1.xyz, 0}
 //     image   texels of the image textures, one 32-bit word each (r | g << 8 | b << 16), row-major
+//   LIGHT part (only with light sampling on and at least one sampled emitter; global memory, read by the light-sampling kernels)
+//     light   [nl]  7 x float4   {shape(bits): 0 sphere, 1 rect, 2 cylinder, grouped id(bits), selection probability, 1/area}
+//                                {emission even.rgb, checker(bits)} {emission odd.rgb, 0}, then the geometry:
+//                                sphere {c.xyz, |r|}; rect {a0, a1, b0, b1} {k, axis(bits), 0, 0}; cylinder o2w rows 0..2,
+//                                {|radius|, zmin, zmax, 0}
+//     alias   [nl]  1 x float4   {threshold, alias light(bits), 0, 0}: one draw u picks i = floor(u nl), then i or its alias
+//     slot    [ns + nr + nc + nt] one 32-bit word per grouped primitive id: its light, -1 = not a sampled light
 //
 // Primitives are grouped by type (spheres, rects, cylinders), each group in list
 // order; the original list index is kept for the reference's tie rule (a later
@@ -32,6 +39,9 @@
 
 // spheres per cluster of the sphere table (a cluster occupies RT_CLUSTER + 1 slots, the last one never hit)
 #define RT_CLUSTER 8
+
+// records per light of the light table (light sampling)
+#define RT_LIGHT_STRIDE 7
 
 // records per cylinder / triangle of the hot tables: the primitive, then its bounding box (2 records)
 #define RT_CYL_STRIDE 6
@@ -129,6 +139,8 @@ struct RenderParams {
     int32_t tiles_x;         // 8-pixel tile columns
     int32_t bands;           // 8-row bands in the shard
     int32_t num_items;       // work items = tiles_x * bands * num_chunks (one wave each)
+    // light sampling (render_nee_kernel only; nl == 0: the scene has no LIGHT part)
+    int32_t nl, off_light, off_alias, off_lslot;
 };
 
 struct DevCounters {

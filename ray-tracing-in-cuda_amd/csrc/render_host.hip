@@ -28,6 +28,10 @@ namespace rtmi {
 bool launch_render(const RenderParams &P, const void *image, unsigned long long *acc, unsigned int *queue,
                    DevCounters *counters, size_t lds_bytes, unsigned grid, hipStream_t stream, unsigned variant, bool ext);
 int blocks_per_cu(unsigned variant, bool count, size_t lds_bytes, bool ext);
+bool launch_render_nee(const RenderParams &P, const void *image, unsigned long long *acc, unsigned int *queue, size_t lds_bytes,
+                       unsigned grid, hipStream_t stream, unsigned variant);
+bool variant_has_nee(unsigned variant);
+int blocks_per_cu_nee(unsigned variant, size_t lds_bytes);
 bool variant_has_ext(unsigned variant);
 bool variant_has_count(unsigned variant);
 bool has_ablations();
@@ -331,7 +335,10 @@ static bool pack_scene_once(const Scene &s, DeviceSceneCache &c, std::vector<cha
     // sphere entries per tier and <= 4095 other entries per cell).
     std::vector<uint32_t> grid_cells;   // compact: (first item << 12) | (n_near << 6) | n_all;  wide: {first item, n_near | n_all << 10 | n_other << 20}
     std::vector<uint32_t> grid_items;   // sphere slots (a cell's near-tier entries first), then grouped ids of the other primitives
-    bool grid_wide = !sphere_only || ns_slots >= 65536 || knob_set("RTMI_FORCE_WIDE");  // (the knob: measurement)
+    // light sampling runs in the general kernels alone (render_nee_kernel: the linear scan and the wide-table walks), so a
+    // sphere-only scene that has lights to sample gets the wide tables; with nothing to sample the image stays as it was
+    const std::vector<SceneLight> lights = s.light_sampling ? scene_lights(s) : std::vector<SceneLight>();
+    bool grid_wide = !sphere_only || ns_slots >= 65536 || !lights.empty() || knob_set("RTMI_FORCE_WIDE");  // (the knob: measurement)
     float grid_min[3] = {0, 0, 0}, grid_size[3] = {1, 1, 1};
     int grid_n[3] = {0, 0, 0};
     float grid_ob2[2] = {0.0f, 0.0f}, grid_shrink = 0.0f;
@@ -571,6 +578,16 @@ static bool pack_scene_once(const Scene &s, DeviceSceneCache &c, std::vector<cha
     for (size_t k = 0; k < s.images.size(); ++k) {
         image_word[k] = off * 4;
         off += (int)(((size_t)s.images[k].rows * s.images[k].cols + 3) / 4);
+    }
+    // the LIGHT part (device_scene.h): light records, alias table, light slot of every grouped primitive id
+    if (!lights.empty()) {
+        L.nl = (int)lights.size();
+        L.off_light = off;
+        off += RT_LIGHT_STRIDE * L.nl;
+        L.off_alias = off;
+        off += L.nl;
+        L.off_lslot = off;
+        off += (ns_slots + L.nr + L.nc + L.nt + 3) / 4;
     }
     c.image.assign((size_t)(off > 0 ? off : 1) * 4, 0.0f);
     float *I = c.image.data();
@@ -816,6 +833,57 @@ static bool pack_scene_once(const Scene &s, DeviceSceneCache &c, std::vector<cha
         if (slots[k] >= 0) rec4(L.off_sph_cold + k)[3] = kind_of(s.prims[slots[k]].material);
     for (int k = 0; k < L.nr; ++k) rec4(L.off_rect_cold + k)[2] = kind_of(s.prims[rec[k]].material);
     for (int k = 0; k < L.nc; ++k) rec4(L.off_cyl_cold + 4 * k)[14] = kind_of(s.prims[cyl[k]].material);
+    if (L.nl > 0) {
+        std::vector<int> group_id(s.prims.size(), -1);
+        for (int k = 0; k < ns_slots; ++k)
+            if (slots[k] >= 0) group_id[(size_t)slots[k]] = k;
+        for (int k = 0; k < L.nr; ++k) group_id[(size_t)rec[k]] = ns_slots + k;
+        for (int k = 0; k < L.nc; ++k) group_id[(size_t)cyl[k]] = ns_slots + L.nr + k;
+        int32_t *slot = reinterpret_cast<int32_t *>(rec4(L.off_lslot));
+        for (int k = 0; k < ns_slots + L.nr + L.nc + L.nt; ++k) slot[k] = -1;
+        for (int i = 0; i < L.nl; ++i) {
+            const SceneLight &l = lights[(size_t)i];
+            const rt_prim &p = s.prims[(size_t)l.prim];
+            const int gid = group_id[(size_t)l.prim];
+            slot[gid] = i;
+            float *r = rec4(L.off_light + RT_LIGHT_STRIDE * i);
+            const int shape = p.type == RT_PRIM_SPHERE ? 0 : (p.type == RT_PRIM_CYLINDER ? 2 : 1);
+            r[0] = bits(shape), r[1] = bits(gid), r[2] = (float)l.prob, r[3] = (float)(1.0 / l.area);
+            for (int c3 = 0; c3 < 3; ++c3) r[4 + c3] = l.even[c3], r[8 + c3] = l.odd[c3];
+            r[7] = bits(l.checker ? 1 : 0);
+            float *g = r + 12;
+            if (shape == 0) {
+                g[0] = p.f[0], g[1] = p.f[1], g[2] = p.f[2], g[3] = std::fabs(p.f[3]);
+            } else if (shape == 1) {
+                g[0] = p.f[0], g[1] = p.f[1], g[2] = p.f[2], g[3] = p.f[3];
+                g[4] = p.f[4], g[5] = bits(p.type - RT_PRIM_XY_RECT);
+            } else {
+                memcpy(g, p.m, 12 * sizeof(float));
+                g[12] = std::fabs(p.f[0]), g[13] = p.f[1], g[14] = p.f[2];
+            }
+        }
+        // alias table (Vose): one uniform draw picks bucket i = floor(u n), then i itself below the threshold, else its alias
+        std::vector<double> w(lights.size());
+        std::vector<int> small, large;
+        for (size_t i = 0; i < lights.size(); ++i) {
+            w[i] = lights[i].prob * (double)L.nl;
+            (w[i] < 1.0 ? small : large).push_back((int)i);
+        }
+        std::vector<float> thr(lights.size(), 1.0f);
+        std::vector<int> alias(lights.size());
+        for (size_t i = 0; i < lights.size(); ++i) alias[i] = (int)i;
+        while (!small.empty() && !large.empty()) {
+            const int a = small.back(), b = large.back();
+            small.pop_back();
+            thr[(size_t)a] = (float)w[(size_t)a], alias[(size_t)a] = b;
+            w[(size_t)b] -= 1.0 - w[(size_t)a];
+            if (w[(size_t)b] < 1.0) large.pop_back(), small.push_back(b);
+        }
+        for (int i = 0; i < L.nl; ++i) {
+            float *a = rec4(L.off_alias + i);
+            a[0] = thr[(size_t)i], a[1] = bits(alias[(size_t)i]);
+        }
+    }
     c.packed_version = s.version;
     return true;
 }
@@ -969,6 +1037,7 @@ int rt_scene_table_info(const rt_scene *sc, rt_table_info *out) {
     out->off_rect_hot = L.off_rect_hot, out->off_cyl_hot = L.off_cyl_hot, out->off_tri_hot = L.off_tri_hot;
     out->hot_bytes_grid = L.hot_vec4_grid * 16;
     out->kernel_variant = (int32_t)pick_variant(L, false, (size_t)knob("RTMI_GLOBAL_TABLE_BYTES", (double)kLdsTableBytes));
+    if (L.nl > 0) out->kernel_variant |= 256;  // light sampling: the layout's light-sampling kernel
     return RT_OK;
 }
 
@@ -1204,6 +1273,13 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     const bool sphere_only = P.nr + P.nc + P.nt == 0 && !ext;
     auto pick = [&](bool counting) -> unsigned { return pick_variant(P, counting, global_threshold); };
     if (variant == 0) variant = pick(count);
+    // light sampling on and something to sample: the layout's light-sampling kernel (built with triangles and textures)
+    const bool nee = P.nl > 0;
+    if (nee && (count || !variant_has_nee(variant))) {
+        set_error("%s: this scene has light sampling on, which the %s (the light-sampling kernels are variants 0, 16, 36 and 44)",
+                  count ? "rt_render_hip_count" : "kernel variant", count ? "counting kernels do not carry" : "requested variant does not carry");
+        return RT_ERR_ARG;
+    }
     // the counting kernels exist for the grid walks (3-D) and two ablation searches: anything else is counted by the kernel
     // variant 0 would run (reported in stats->kernel_variant / cull_mode)
     if (count && !variant_has_count(variant)) variant = (variant == 2) ? 6u : pick(true);
@@ -1233,6 +1309,7 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
         return RT_ERR_LIMIT;
     }
     if (force_ext && variant_has_ext(variant) && P.grid_wide) ext = true;
+    if (nee) ext = true;
     const size_t hot_bytes = hot_bytes_of(variant);
     const size_t lds_bytes = ((variant & 8u) ? 0 : hot_bytes) + acc_lds;
     if (knob_set("RTMI_DEBUG_LAYOUT")) {
@@ -1273,7 +1350,8 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
         HIP_TRY(hipGetDeviceProperties(&prop, device));
         ent->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     }
-    const unsigned long long resident = (unsigned long long)ent->num_cus * blocks_per_cu(variant, count, lds_bytes, ext);
+    const unsigned long long resident =
+        (unsigned long long)ent->num_cus * (nee ? blocks_per_cu_nee(variant, lds_bytes) : blocks_per_cu(variant, count, lds_bytes, ext));
     const unsigned long long need_blocks = (items64 + 3) / 4;
     const unsigned long long grid64 = need_blocks < resident ? (need_blocks ? need_blocks : 1) : resident;
 
@@ -1324,7 +1402,8 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
             launch_item_params(d_queue, ip, stream);
         }
         if (s.max_depth > 0) {
-            if (!launch_render(P, ent->d_image, ent->d_acc, d_queue, d_cnt, lds_bytes, (unsigned)grid64, stream, variant, ext)) {
+            if (nee ? !launch_render_nee(P, ent->d_image, ent->d_acc, d_queue, lds_bytes, (unsigned)grid64, stream, variant)
+                    : !launch_render(P, ent->d_image, ent->d_acc, d_queue, d_cnt, lds_bytes, (unsigned)grid64, stream, variant, ext)) {
                 set_error("kernel variant %u has no %s build", variant, count ? "counting" : (ext ? "triangle / texture" : "such"));
                 return RT_ERR_LIMIT;
             }
@@ -1342,7 +1421,7 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     HIP_TRY(hipGetLastError());
 
     if (stats) {
-        stats->kernel_variant = (int32_t)variant;  // what variant 0 (or a counting call) resolved to
+        stats->kernel_variant = (int32_t)(variant | (nee ? 256u : 0u));  // what variant 0 (or a counting call) resolved to (| 256: light sampling)
         HIP_TRY(hipEventRecord(ev2, stream));
         lock.unlock();
         HIP_TRY(hipEventSynchronize(ev2));

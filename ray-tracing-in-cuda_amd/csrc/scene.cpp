@@ -534,6 +534,10 @@ int scene_from_json(const char *text, size_t len, Scene &s, const char *base_dir
         if (!(p >= 0.0 && p <= 1.0)) r.fail("top level: \"russian_roulette\" must be a probability in [0, 1]");
         else s.rr_p = (float)p;
     }
+    if (const JsonValue *f = root.find("light_sampling")) {
+        if (f->kind != JsonValue::Bool) r.fail("top level: \"light_sampling\" must be a boolean");
+        else s.light_sampling = f->b;
+    }
 
     // camera, parser.hpp:113-141
     const JsonValue *cam = root.find("camera");
@@ -788,6 +792,7 @@ std::string scene_to_json(const Scene &s) {
     o += std::string("  \"sky_gradient\": ") + ((s.flags & RT_FLAG_SKY_GRADIENT) ? "true" : "false") + ",\n";
     o += std::string("  \"defocus_blur\": ") + ((s.flags & RT_FLAG_DEFOCUS_BLUR) ? "true" : "false") + ",\n";
     if (s.rr_p > 0.0f) o += "  \"russian_roulette\": " + json_double((double)s.rr_p) + ",\n";
+    if (s.light_sampling) o += "  \"light_sampling\": true,\n";
     o += "  \"camera\": {\"lookfrom\": ";
     put_vec3d(o, s.cam.lookfrom);
     o += ", \"lookat\": ";
@@ -1008,6 +1013,57 @@ void scene_rtiow(Scene &s, uint32_t seed, int width, int height, int spp, int ma
     add_sphere(-4, 1, 0, 1.0, add_mat(RT_MAT_LAMBERTIAN, add_tex_solid(0.4, 0.2, 0.1), 0, 0, 0, 0, 0));
     add_sphere(4, 1, 0, 1.0, add_mat(RT_MAT_METAL, -1, 0.7, 0.6, 0.5, 0.0, 0));
     s.touch();
+}
+
+}  // namespace rtmi
+
+namespace rtmi {
+
+std::vector<SceneLight> scene_lights(const Scene &s) {
+    std::vector<SceneLight> out;
+    const double pi = std::acos(-1.0);
+    auto luminance = [](const float *c) { return 0.2126 * c[0] + 0.7152 * c[1] + 0.0722 * c[2]; };
+    for (size_t i = 0; i < s.prims.size(); ++i) {
+        const rt_prim &p = s.prims[i];
+        if (p.material < 0 || p.material >= (int)s.mats.size()) continue;
+        const rt_material &m = s.mats[(size_t)p.material];
+        if (m.type != RT_MAT_DIFFUSE_LIGHT || m.texture < 0 || m.texture >= (int)s.texs.size()) continue;
+        const rt_texture &t = s.texs[(size_t)m.texture];
+        if (t.type != RT_TEX_SOLID && t.type != RT_TEX_CHECKER) continue;  // image-textured emitters stay BSDF-only
+        SceneLight l;
+        l.prim = (int)i, l.type = p.type;
+        l.checker = t.type == RT_TEX_CHECKER;
+        for (int c = 0; c < 3; ++c) l.even[c] = t.c0[c], l.odd[c] = l.checker ? t.c1[c] : t.c0[c];
+        switch (p.type) {
+        case RT_PRIM_SPHERE: l.area = 4.0 * pi * (double)p.f[3] * (double)p.f[3]; break;
+        case RT_PRIM_XY_RECT:
+        case RT_PRIM_XZ_RECT:
+        case RT_PRIM_YZ_RECT: l.area = ((double)p.f[1] - p.f[0]) * ((double)p.f[3] - p.f[2]); break;
+        case RT_PRIM_CYLINDER: {
+            // the kernel samples the tube in object space and maps the point through o2w: only a rigid transform keeps the
+            // density uniform by area (R R^T = I)
+            bool rigid = true;
+            for (int a = 0; a < 3; ++a)
+                for (int b = 0; b < 3; ++b) {
+                    double d = 0.0;
+                    for (int k = 0; k < 3; ++k) d += (double)p.m[4 * a + k] * p.m[4 * b + k];
+                    if (std::fabs(d - (a == b ? 1.0 : 0.0)) > 1e-4) rigid = false;
+                }
+            if (!rigid) continue;
+            l.area = 2.0 * pi * std::fabs((double)p.f[0]) * ((double)p.f[2] - p.f[1]);
+            break;
+        }
+        default: continue;  // triangles stay BSDF-only
+        }
+        const double power = l.area * 0.5 * (luminance(l.even) + luminance(l.odd));
+        if (!(l.area > 0.0) || !(power > 0.0) || !std::isfinite(power)) continue;
+        l.prob = power;
+        out.push_back(l);
+    }
+    double total = 0.0;
+    for (const SceneLight &l : out) total += l.prob;
+    for (SceneLight &l : out) l.prob /= total;
+    return out;
 }
 
 }  // namespace rtmi

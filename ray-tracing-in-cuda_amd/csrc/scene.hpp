@@ -43,6 +43,7 @@ struct Scene {
     float background[3] = {0, 0, 0};
     uint32_t flags = 0;
     float rr_p = 0.0f;  // Russian-roulette survival probability per bounce, 0 = off
+    bool light_sampling = false;  // next-event estimation + MIS (rt_scene_set_light_sampling)
     std::string output_file = "main.png";  // parser.hpp:566-567 default
     CameraParams cam;
     std::vector<rt_prim> prims;
@@ -55,6 +56,17 @@ struct Scene {
 
     void touch() { ++version; }
 };
+
+// the emitters that light sampling samples (spheres, axis-aligned rects and rigid cylinder tubes whose material is a
+// diffuse_light with a solid or checker texture and nonzero power), in list order, with their selection probabilities
+// (proportional to area x mean emission luminance)
+struct SceneLight {
+    int prim = 0, type = 0;  // list index, rt_prim_type
+    double area = 0.0, prob = 0.0;
+    float even[3] = {0, 0, 0}, odd[3] = {0, 0, 0};
+    bool checker = false;
+};
+std::vector<SceneLight> scene_lights(const Scene &s);
 
 // derive the camera frame (camera.cuh:9-29) in fp64, round once to fp32
 void derive_camera(const Scene &s, rt_camera *out);

@@ -1,0 +1,302 @@
+"""Light sampling (next-event estimation + MIS, rt_scene_set_light_sampling) on the GPU: an analytic known answer,
+unbiasedness against the plain estimator, the variance it buys, and the bit-exact invariants every kernel keeps."""
+import os
+import subprocess
+import sys
+import textwrap
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "ray-tracing-in-cuda_amd")
+SCENES = os.path.join(PKG, "scenes")
+GOLDEN = os.path.join(ROOT, "tests", "golden", "scenes_as_shipped")
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def rtmi():
+    sys.path.insert(0, ROOT)
+    from __graft_entry__ import load_package
+    mod = load_package()
+    if mod.device_count() < 1:
+        pytest.skip("no HIP device")
+    return mod
+
+
+# ---- the analytic scene: a lambertian floor under a parallel emissive rectangle ---------------------------------------
+RHO, LE, H = 0.5, 4.0, 2.0
+LX, LZ = (-1.0, 1.0), (-1.0, 1.0)
+
+
+def analytic_scene(rtmi, w=64, h=36, spp=256):
+    sc = rtmi.Scene.new(w, h, spp, 2)  # camera -> floor -> light: the direct term alone
+    sc.set_background((0, 0, 0), sky_gradient=False, defocus_blur=False)
+    sc.camera((2.5, 1.2, -1.5), (2.5, 0.0, 0.0), (0, 1, 0), 50.0)
+    sc.xz_rect(-50, 50, -50, 50, 0.0, sc.lambertian((RHO, RHO, RHO)))
+    sc.xz_rect(LX[0], LX[1], LZ[0], LZ[1], H, sc.diffuse_light((LE, LE, LE)))
+    return sc
+
+
+def _ff_corner(a, b, h):
+    """form factor from a point to a parallel rectangle [0, a] x [0, b] at height h above it (signed for a, b < 0)"""
+    A, B = np.abs(a) / h, np.abs(b) / h
+    f = (A / np.sqrt(1 + A * A) * np.arctan(B / np.sqrt(1 + A * A)) + B / np.sqrt(1 + B * B) * np.arctan(A / np.sqrt(1 + B * B)))
+    return np.sign(a) * np.sign(b) * f / (2 * np.pi)
+
+
+def analytic_expected(sc, q=6):
+    """rho L F(P) averaged over each pixel's footprint (q x q jitter quadrature); NaN where a ray misses the floor"""
+    cam = sc.get_camera()
+    org, ll = np.array(cam.origin, np.float64), np.array(cam.lower_left, np.float64)
+    hor, ver = np.array(cam.horizontal, np.float64), np.array(cam.vertical, np.float64)
+    W, Hh = sc.width, sc.height
+    xi = (np.arange(q) + 0.5) / q
+    u = (np.arange(W)[None, :, None, None] + xi[None, None, :, None]) / (W - 1)
+    v = (np.arange(Hh)[:, None, None, None] + xi[None, None, None, :]) / (Hh - 1)
+    d = ll + u[..., None] * hor + v[..., None] * ver - org
+    t = -org[1] / d[..., 1]
+    px, pz = org[0] + t * d[..., 0], org[2] + t * d[..., 2]
+    F = (_ff_corner(LX[1] - px, LZ[1] - pz, H) - _ff_corner(LX[0] - px, LZ[1] - pz, H)
+         - _ff_corner(LX[1] - px, LZ[0] - pz, H) + _ff_corner(LX[0] - px, LZ[0] - pz, H))
+    val = RHO * LE * F
+    val[~(t > 0)] = np.nan
+    return val.mean(axis=(2, 3))
+
+
+def _mean(sc, img):
+    return img.astype(np.float64).mean(axis=2) / sc.spp
+
+
+def test_analytic_known_answer(rtmi):
+    sc = analytic_scene(rtmi)
+    exp = analytic_expected(sc)
+    ok = np.isfinite(exp) & (exp > 1e-3)
+    assert ok.mean() > 0.9
+    plain = [_mean(sc, sc.render(rtmi.Opts(seed=s))) for s in range(4)]
+    # the test against today's estimator: the frame mean within 3 sigma of the closed form
+    pm = np.array([p[ok].mean() for p in plain])
+    se = pm.std(ddof=1) / np.sqrt(len(pm))
+    assert abs(pm.mean() - exp[ok].mean()) < 3 * se + 1e-4, (pm.mean(), exp[ok].mean(), se)
+    sc.set_light_sampling(True)
+    st = rtmi.Stats()
+    nee = _mean(sc, sc.render(rtmi.Opts(seed=0), st))
+    assert st.kernel_variant & 256
+    rel_nee = np.sqrt(np.mean(((nee - exp) / exp)[ok] ** 2))
+    rel_plain = np.sqrt(np.mean(((plain[0] - exp) / exp)[ok] ** 2))
+    print(f"analytic: RMS relative error per pixel at 256 spp: plain {rel_plain:.4f}, light sampling {rel_nee:.4f}")
+    assert rel_nee < 0.05 and rel_nee <= 0.25 * rel_plain, (rel_nee, rel_plain)
+
+
+# ---- unbiasedness against the plain estimator ----------------------------------------------------------------------------
+MATERIALS = ["lambert", "checker", "metal0.3", "metal1.0"]
+LIGHTS = ["xy", "xz", "yz", "sphere", "cylinder"]
+
+
+def pair_scene(rtmi, mat, light, w=64, h=36, spp=256, depth=6):
+    sc = rtmi.Scene.new(w, h, spp, depth)
+    sc.set_background((0.02, 0.02, 0.03), sky_gradient=False, defocus_blur=False)
+    sc.camera((0.0, 2.5, 6.0), (0.0, 0.5, 0.0), (0, 1, 0), 45.0)
+    if mat == "lambert":
+        m = sc.lambertian((0.6, 0.5, 0.4))
+    elif mat == "checker":
+        m = sc.lambertian(sc.checker_texture((0.8, 0.8, 0.8), (0.1, 0.3, 0.1)))
+    else:
+        m = sc.metal((0.8, 0.7, 0.6), float(mat[5:]))
+    sc.xz_rect(-20, 20, -20, 20, 0.0, m)
+    sc.sphere((-1.2, 0.6, 0.5), 0.6, sc.lambertian((0.3, 0.5, 0.7)))
+    sc.sphere((1.3, 0.5, 0.8), 0.5, m)
+    e = sc.diffuse_light((6.0, 5.0, 4.0))
+    if light == "xy":
+        sc.xy_rect(-0.5, 0.5, 1.0, 2.0, -1.5, e)
+    elif light == "xz":
+        sc.xz_rect(-0.6, 0.6, -0.6, 0.6, 2.5, e)
+    elif light == "yz":
+        sc.yz_rect(0.5, 1.5, -0.5, 0.5, 2.5, e)
+    elif light == "sphere":
+        sc.sphere((0.3, 2.2, -0.5), 0.3, e)
+    else:
+        sc.cylinder(0.15, -0.8, 0.8, e, rotate=((1.0, 0.3, 0.2), 70.0), translate=(0.2, 1.8, -0.6))
+    return sc
+
+
+def shipped(rtmi, path, w=64, h=36, spp=256, depth=None):
+    sc = rtmi.Scene.load(path)
+    sc.override(w, h, spp, depth or 0)
+    return sc
+
+
+def seeds_of(rtmi, sc, n=8, nee=False):
+    sc.set_light_sampling(nee)
+    return np.stack([_mean(sc, sc.render(rtmi.Opts(seed=1000 + s))) for s in range(n)])
+
+
+def compare(a, b, tag, spp=256, c_max=6.0):
+    """a, b: [seed, H, W] per-pixel means of the plain and the light-sampling estimator.  4 x 4 block z-scores and the frame mean.
+    Where the plain estimator reaches a light only by rare BSDF hits (a small light far away), its spread over 8 seeds can be
+    zero while its mean still owes the light's share, so the block's standard error is floored by the Poisson error of the hits
+    that would carry the difference: |delta| c_max / (samples per block x seeds), c_max the largest emission."""
+    n, Hh, W = a.shape
+    hb, wb = Hh // 4 * 4, W // 4 * 4
+    blk = lambda x: x[:, :hb, :wb].reshape(n, hb // 4, 4, wb // 4, 4).mean(axis=(2, 4))
+    A, B = blk(a), blk(b)
+    delta = np.abs(A.mean(0) - B.mean(0))
+    se = np.sqrt(A.var(axis=0, ddof=1) / n + B.var(axis=0, ddof=1) / n + delta * c_max / (16 * spp * n))
+    z = (A.mean(0) - B.mean(0)) / np.maximum(se, 1e-7)
+    fa, fb = a.mean(axis=(1, 2)), b.mean(axis=(1, 2))
+    fz = (fa.mean() - fb.mean()) / max(np.sqrt(fa.var(ddof=1) / n + fb.var(ddof=1) / n), 1e-9)
+    print(f"{tag}: max |block z| {np.abs(z).max():.2f}, frame z {fz:.2f}")
+    assert np.abs(z).max() < 5.0, (tag, float(np.abs(z).max()))
+    assert abs(fz) < 3.0, (tag, fz)
+
+
+@pytest.mark.parametrize("mat", MATERIALS)
+@pytest.mark.parametrize("light", LIGHTS)
+def test_unbiased_per_pair(rtmi, mat, light):
+    sc = pair_scene(rtmi, mat, light)
+    assert len(sc.lights()) == 1
+    compare(seeds_of(rtmi, sc), seeds_of(rtmi, sc, nee=True), f"{mat} x {light}")
+
+
+def test_unbiased_with_roulette_and_short_paths(rtmi):
+    sc = pair_scene(rtmi, "metal1.0", "xz")
+    sc.set_russian_roulette(0.9)
+    compare(seeds_of(rtmi, sc), seeds_of(rtmi, sc, nee=True), "roulette 0.9", c_max=6.0 / 0.9)
+    sc = pair_scene(rtmi, "lambert", "sphere", depth=2)
+    compare(seeds_of(rtmi, sc), seeds_of(rtmi, sc, nee=True), "max_depth 2")
+
+
+
+@pytest.mark.parametrize("name", ["mixed_emissive", "blue"])
+def test_unbiased_and_less_noisy_on_the_emissive_scenes(rtmi, name):
+    path = os.path.join(SCENES, "mixed_emissive.json") if name == "mixed_emissive" else os.path.join(GOLDEN, "blue.json")
+    sc = shipped(rtmi, path)
+    a, b = seeds_of(rtmi, sc), seeds_of(rtmi, sc, nee=True)
+    compare(a, b, name)
+    va, vb = a.var(axis=0, ddof=1), b.var(axis=0, ddof=1)
+    lit = va > 0
+    ratio = float(np.median(va[lit] / np.maximum(vb[lit], 1e-12)))
+    print(f"{name}: median per-pixel variance plain / light sampling = {ratio:.2f}")
+    # measured on the MI355X: mixed_emissive 3.8, blue 1.09 -- blue's rings light fuzz-0.5 metal, whose narrow lobe the BSDF
+    # sample already finds; the light sample must at least not add noise there
+    assert ratio >= (1.5 if name == "mixed_emissive" else 1.0), ratio
+
+
+def test_variance_ratio_analytic(rtmi):
+    sc = analytic_scene(rtmi)
+    a, b = seeds_of(rtmi, sc), seeds_of(rtmi, sc, nee=True)
+    va, vb = a.var(axis=0, ddof=1), b.var(axis=0, ddof=1)
+    lit = va > 0
+    ratio = float(np.median(va[lit] / np.maximum(vb[lit], 1e-12)))
+    print(f"analytic: median per-pixel variance plain / light sampling = {ratio:.1f}")
+    assert ratio >= 10.0, ratio
+
+
+# ---- bit-exact invariants with light sampling on -------------------------------------------------------------------------
+def many_lights(rtmi, w=64, h=36, spp=32):
+    rng = np.random.default_rng(3)
+    sc = rtmi.Scene.new(w, h, spp, 8)
+    sc.set_background((0.0, 0.0, 0.0), sky_gradient=False, defocus_blur=False)
+    sc.camera((0, 6, 14), (0, 0, 0), (0, 1, 0), 45.0)
+    sc.xz_rect(-30, 30, -30, 30, 0.0, sc.lambertian(sc.checker_texture((0.7, 0.7, 0.7), (0.2, 0.2, 0.2))))
+    for i in range(200):
+        c = (float(rng.uniform(-8, 8)), float(rng.uniform(0.2, 3)), float(rng.uniform(-8, 4)))
+        if i % 3 == 0:
+            sc.sphere(c, 0.15, sc.diffuse_light(tuple(float(x) for x in rng.uniform(1, 6, 3))))
+        elif i % 3 == 1:
+            sc.sphere(c, 0.2, sc.lambertian(tuple(float(x) for x in rng.uniform(0.2, 0.9, 3))))
+        else:
+            sc.xy_rect(c[0], c[0] + 0.3, c[1], c[1] + 0.3, c[2], sc.diffuse_light((3.0, 2.0, 1.0)))
+    sc.set_light_sampling(True)
+    return sc
+
+
+def mixed(rtmi, spp=32):
+    sc = rtmi.Scene.load(os.path.join(SCENES, "mixed_emissive.json"))
+    sc.override(64, 36, spp)
+    sc.set_light_sampling(True)
+    return sc
+
+
+def test_layouts_give_the_same_bytes(rtmi):
+    for sc in (mixed(rtmi), many_lights(rtmi)):
+        imgs = {}
+        for v in (16, 36, 44):
+            st = rtmi.Stats()
+            imgs[v] = sc.render(rtmi.Opts(seed=9, variant=v), st)
+            assert st.kernel_variant == v | 256
+        assert np.array_equal(imgs[16], imgs[36]) and np.array_equal(imgs[16], imgs[44])
+        st = rtmi.Stats()
+        assert np.array_equal(sc.render(rtmi.Opts(seed=9), st), imgs[16]) and st.kernel_variant in (272, 292, 300)
+
+
+def test_splits_chunks_shards_and_seeds(rtmi):
+    sc = mixed(rtmi, spp=64)
+    ref = sc.render(rtmi.Opts(seed=4))
+    assert np.array_equal(sc.render(rtmi.Opts(seed=4)), ref)
+    assert not np.array_equal(sc.render(rtmi.Opts(seed=5)), ref)
+    acc, _ = sc.accumulate(None, rtmi.Opts(seed=4, sample_first=0, sample_count=24))
+    acc, img = sc.accumulate(acc, rtmi.Opts(seed=4, sample_first=24, sample_count=40))
+    assert np.array_equal(img, ref)
+    assert np.array_equal(sc.render(rtmi.Opts(seed=4, spp_chunk=16)), sc.render(rtmi.Opts(seed=4, spp_chunk=64)))
+    for rot in (0, 1, 2):
+        full = np.zeros_like(ref)
+        for r in range(3):
+            o = rtmi.Opts(seed=4, tile_first=r, tile_stride=3, tile_rotate=rot, tile_rows=4)
+            full[sc.shard_global_rows(o)] = sc.render(o)
+        assert np.array_equal(full, sc.render(rtmi.Opts(seed=4, tile_rows=4))), rot
+
+
+def test_switch_on_with_nothing_to_sample(rtmi):
+    rt = rtmi.Scene.rtiow(7, 96, 54, 4, 10)
+    tri = rtmi.Scene.new(64, 36, 8, 6)
+    tri.set_background((0.1, 0.1, 0.1), sky_gradient=False, defocus_blur=False)
+    tri.camera((0, 1, 4), (0, 0.5, 0), (0, 1, 0), 50.0)
+    tri.xz_rect(-5, 5, -5, 5, 0.0, tri.lambertian((0.5, 0.5, 0.5)))
+    tri.triangle((-1, 1.5, -1), (1, 1.5, -1), (0, 1.5, 1), tri.diffuse_light((4.0, 4.0, 4.0)))
+    tri.xy_rect(-1, 1, 0, 1, -2, tri.diffuse_light(tri.image_texture(np.full((2, 2, 3), 200, np.uint8))))
+    for sc in (rt, tri):
+        assert len(sc.lights()) == 0
+        st0, st1 = rtmi.Stats(), rtmi.Stats()
+        off = sc.render(rtmi.Opts(seed=2), st0)
+        sc.set_light_sampling(True)
+        on = sc.render(rtmi.Opts(seed=2), st1)
+        assert np.array_equal(off, on) and st0.kernel_variant == st1.kernel_variant < 256
+
+
+def test_refusals(rtmi):
+    sc = mixed(rtmi, spp=4)
+    variants = [2, 6] + ([1, 40, 17, 24, 32, 64, 128] if rtmi.has_ablations() else [])
+    for v in variants:
+        with pytest.raises(rtmi.RtmiError) as e:
+            sc.render(rtmi.Opts(variant=v))
+        assert e.value.status == 1, v
+    if rtmi.has_ablations():
+        with pytest.raises(rtmi.RtmiError) as e:
+            sc.count()
+        assert e.value.status == 1
+
+
+_PRODUCT = textwrap.dedent("""
+    import os, sys
+    import numpy as np
+    sys.path.insert(0, %r)
+    from __graft_entry__ import load_package
+    rtmi = load_package()
+    assert not rtmi.has_ablations()
+    sc = rtmi.Scene.load(os.path.join(%r, "mixed_emissive.json")); sc.override(64, 36, 16); sc.set_light_sampling(True)
+    st = rtmi.Stats()
+    np.save(sys.argv[1], sc.render(rtmi.Opts(seed=11), st))
+    assert st.kernel_variant & 256, st.kernel_variant
+""") % (ROOT, SCENES)
+
+
+def test_product_build_renders_the_same_bytes(rtmi, tmp_path):
+    out = str(tmp_path / "prod.npy")
+    env = dict(os.environ, RTMI_LIB=os.path.join(PKG, "librtmi_product.so"))
+    p = subprocess.run([sys.executable, "-c", _PRODUCT, out], capture_output=True, text=True, env=env, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    sc = mixed(rtmi, spp=16)
+    assert np.array_equal(np.load(out), sc.render(rtmi.Opts(seed=11)))
