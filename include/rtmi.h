@@ -461,7 +461,8 @@ const char *rt_last_error(void);
 const char *rt_status_string(int status);
 int rt_abi_version(void);
 /* sizeof of the ABI structs as this library was compiled (binding self-checks):
- * 0 rt_opts, 1 rt_stats, 2 rt_prim, 3 rt_material, 4 rt_texture, 5 rt_camera, 6 rt_scene_info, 7 rt_table_info; else 0 */
+ * 0 rt_opts, 1 rt_stats, 2 rt_prim, 3 rt_material, 4 rt_texture, 5 rt_camera, 6 rt_scene_info, 7 rt_table_info,
+ * 8 rt_adaptive, 9 rt_adaptive_stats; else 0 */
 size_t rt_struct_size(int which);
 /* number of usable gfx950 devices, or -rt_status */
 int rt_device_count(void);
@@ -477,6 +478,44 @@ void rt_sample_stream(uint64_t seed, uint32_t pixel, uint32_t sample, uint32_t *
 /* slab test, gpu-version/aabb.hpp:15-29 (host evaluation of the device helper's formula) */
 int rt_aabb_hit(const float bmin[3], const float bmax[3], const float orig[3], const float dir[3],
                 float t_min, float t_max);
+
+/* ---- adaptive sampling --------------------------------------------------- */
+
+/* Per-tile sample counts driven by a noise target.  Every 8x8 tile starts with min_spp samples; after each pass a
+ * tile whose noise estimate is within `threshold` (or that has reached max_spp) is retired and the others double
+ * their samples: n_0 = min_spp, n_{k+1} = min(2 n_k, max_spp).  The samples of a pass go half to one accumulator
+ * plane (A) and half to another (B); the noise of a pixel is estimated from the two half-sums, in fp64:
+ *     a_c = SA_c 2^-24 / nA,  b_c = SB_c 2^-24 / nB,  m_c = (SA_c + SB_c) 2^-24 / n
+ *     d = (|a_r - b_r| + |a_g - b_g|) + |a_b - b_b|,  M = max((m_r + m_g) + m_b, 1e-4)
+ *     converged  <=>  d * d <= (4 T T) M              (d / (2 sqrt M) <= T)
+ * and a tile converges when all its on-image pixels do.  threshold = 0 retires tiles at max_spp only.
+ * A tile that stops after n samples holds exactly the sums of samples [0, n): bit for bit what rt_render_hip gives
+ * that tile at spp = n. */
+typedef struct rt_adaptive {
+    int32_t min_spp;    /* samples of the first pass, every tile; >= 2 */
+    int32_t max_spp;    /* cap per tile; 0 -> the scene's spp; >= min_spp */
+    float   threshold;  /* noise target (metric above); >= 0 and finite; 0 -> every tile runs to max_spp */
+} rt_adaptive;
+
+typedef struct rt_adaptive_stats {
+    int32_t passes;
+    int32_t tiles;            /* 8x8 tiles of the frame */
+    int32_t spp_after[32];    /* n_k: samples per active tile after pass k */
+    int32_t active[32];       /* tiles rendered in pass k */
+    uint64_t samples;         /* pixel samples rendered: sum of spp_map over on-image pixels */
+    double kernel_ms;         /* render + estimate kernels, hipEvent time */
+} rt_adaptive_stats;
+
+/* rgb_sum (host, H*W*3 floats): rgb_sum[(y*W+x)*3+c] is the fp32 conversion of the pixel's exact sum over its own
+ * spp_map[y*W+x] samples [0, n) (host, H*W int32).  The whole frame on o->device; o->tile_stride must be <= 1 and
+ * o->sample_first / sample_count 0 (the schedule owns the samples).  o->variant: 0 or any rendering variant.  Light
+ * sampling follows the scene's switch.  RT_ERR_ARG for bad arguments, checked before any device access; st may be NULL. */
+int rt_render_hip_adaptive(const rt_scene *s, const rt_opts *o, const rt_adaptive *a,
+                           float *rgb_sum, int32_t *spp_map, rt_adaptive_stats *st);
+/* the same into DEVICE buffers on `stream` (hipStream_t as void*); returns when the frame is done (the schedule reads the
+ * active tile count back once per pass) */
+int rt_render_hip_adaptive_device(const rt_scene *s, const rt_opts *o, const rt_adaptive *a,
+                                  void *d_rgb_sum, void *d_spp_map, void *stream, rt_adaptive_stats *st);
 
 #ifdef __cplusplus
 }

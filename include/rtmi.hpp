@@ -258,6 +258,15 @@ public:
         check(rt_render_hip_accumulate(s_, &o, acc.data(), img.data(), stats), "accumulate");
         return img;
     }
+    // adaptive sampling (rt_render_hip_adaptive): W*H*3 sums of each pixel's own spp_map[y*W + x] samples, row 0 = bottom
+    std::vector<float> render_adaptive(const rt_adaptive &a, std::vector<int32_t> &spp_map, const rt_opts *opts = nullptr,
+                                       rt_adaptive_stats *stats = nullptr) const {
+        const rt_scene_info i = info();
+        std::vector<float> img((size_t)i.width * i.height * 3);
+        spp_map.assign((size_t)i.width * i.height, 0);
+        check(rt_render_hip_adaptive(s_, opts, &a, img.data(), spp_map.data(), stats), "render_adaptive");
+        return img;
+    }
     rt_scene *handle() const { return s_; }
 
 private:

@@ -137,6 +137,24 @@ class TableInfo(C.Structure):
     ]
 
 
+class Adaptive(C.Structure):
+    """rt_adaptive (include/rtmi.h): the noise target of an adaptive render."""
+    _fields_ = [("min_spp", C.c_int32), ("max_spp", C.c_int32), ("threshold", C.c_float)]
+
+
+class AdaptiveStats(C.Structure):
+    """rt_adaptive_stats (include/rtmi.h): the schedule an adaptive render ran."""
+    _fields_ = [
+        ("passes", C.c_int32), ("tiles", C.c_int32), ("spp_after", C.c_int32 * 32), ("active", C.c_int32 * 32),
+        ("samples", C.c_uint64), ("kernel_ms", C.c_double),
+    ]
+
+    def as_dict(self):
+        n = self.passes
+        return {"passes": n, "tiles": self.tiles, "spp_after": list(self.spp_after[:n]), "active": list(self.active[:n]),
+                "samples": self.samples, "kernel_ms": self.kernel_ms}
+
+
 def _sig(name, restype, *argtypes):
     fn = getattr(_lib, name)
     fn.restype = restype
@@ -202,6 +220,8 @@ _sig("rt_scene_table_info", C.c_int, _p, C.POINTER(TableInfo))
 _sig("rt_scene_table_image", C.c_int, _p, _p, C.c_int)
 _sig("rt_render_hip_accumulate", C.c_int, _p, C.POINTER(Opts), _p, _p, C.POINTER(Stats))
 _sig("rt_acc_to_rgb", None, _p, _p, C.c_size_t)
+_sig("rt_render_hip_adaptive", C.c_int, _p, C.POINTER(Opts), C.POINTER(Adaptive), _p, _p, C.POINTER(AdaptiveStats))
+_sig("rt_render_hip_adaptive_device", C.c_int, _p, C.POINTER(Opts), C.POINTER(Adaptive), _p, _p, _p, C.POINTER(AdaptiveStats))
 _sig("rt_shard_scatter_rows", C.c_int, _p, C.POINTER(Opts), _p, _p)
 _sig("rt_write_ppm", C.c_int, C.c_char_p, _p, C.c_int, C.c_int, C.c_int)
 _sig("rt_quantize_rgb8", C.c_int, _p, C.c_int, C.c_int, C.c_int, C.c_int, _p)
@@ -227,6 +247,7 @@ C_SYMBOLS = [
     "rt_quantize_rgb8", "rt_philox4x32_10", "rt_aabb_hit", "rt_sample_stream", "rt_write_png",
     "rt_scene_output_file", "rt_scene_rotate_cylinders", "rt_scene_set_output_file", "rt_scene_dna", "rt_scene_clone",
     "rt_scene_set_light_sampling", "rt_scene_get_light_sampling", "rt_scene_get_lights",
+    "rt_render_hip_adaptive", "rt_render_hip_adaptive_device",
 ]
 
 
@@ -481,6 +502,19 @@ class Scene:
         st = stats if stats is not None else Stats()
         _check(_lib.rt_render_hip(self._h, C.byref(opts), out.ctypes.data_as(C.c_void_p), C.byref(st)), "rt_render_hip")
         return out
+
+    def render_adaptive(self, threshold: float, min_spp: int = 16, max_spp: int = 0, opts: Opts | None = None):
+        """Adaptive sampling (rt_render_hip_adaptive): every 8x8 tile doubles its samples from min_spp until its noise
+        estimate is within `threshold` or it reaches max_spp (0: the scene's spp).  Returns (rgb_sum, spp_map, stats): the
+        (H, W, 3) fp32 sums of each pixel's own spp_map[y, x] samples [0, n), the (H, W) int32 counts and AdaptiveStats."""
+        opts = opts or Opts()
+        a = Adaptive(min_spp=int(min_spp), max_spp=int(max_spp), threshold=float(threshold))
+        out = np.empty((self.height, self.width, 3), dtype=np.float32)
+        spp = np.empty((self.height, self.width), dtype=np.int32)
+        st = AdaptiveStats()
+        _check(_lib.rt_render_hip_adaptive(self._h, C.byref(opts), C.byref(a), out.ctypes.data_as(C.c_void_p),
+                                           spp.ctypes.data_as(C.c_void_p), C.byref(st)), "rt_render_hip_adaptive")
+        return out, spp, st
 
     def render_tiles(self, devices=None, opts: Opts | None = None, stats: Stats | None = None, n: int | None = None,
                      out: np.ndarray | None = None):

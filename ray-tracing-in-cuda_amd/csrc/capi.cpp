@@ -47,6 +47,8 @@ size_t rt_struct_size(int which) {
     case 5: return sizeof(rt_camera);
     case 6: return sizeof(rt_scene_info);
     case 7: return sizeof(rt_table_info);
+    case 8: return sizeof(rt_adaptive);
+    case 9: return sizeof(rt_adaptive_stats);
     default: return 0;
     }
 }

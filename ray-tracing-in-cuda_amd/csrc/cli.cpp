@@ -12,6 +12,8 @@
 // Resumable rendering: --acc-out FILE saves the exact pixel sums, --acc-in FILE continues from them
 // (-spp is then the number of samples to ADD; --spp-begin overrides the first sample index).  Any
 // split of a sample range into runs writes the same main.ppm as one run over the whole range.
+// Adaptive sampling: --adaptive T [--min-spp N] [--max-spp N] gives every 8x8 tile samples until its noise estimate is
+// within T (rt_render_hip_adaptive); each pixel is written rescaled to the scene's spp (sum * spp / n).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -41,7 +43,7 @@ static int usage(const char *argv0) {
             "usage: %s [-f scene.json | --rtiow] [-w W] [-h H] [-d DEPTH] [-spp N] [-o out.ppm]\n"
             "          [--seed S] [--scene-seed S] [--device N] [--chunk N] [--dump-json file] [--count] [--no-png]\n"
             "          [--acc-in sums.bin] [--acc-out sums.bin] [--spp-begin FIRST] [--rr SURVIVAL_PROBABILITY] [--nee]\n"
-            "          [--gpus N] [--tile-rows R]\n",
+            "          [--gpus N] [--tile-rows R] [--adaptive THRESHOLD [--min-spp N] [--max-spp N]]\n",
             argv0);
     return 2;
 }
@@ -54,6 +56,10 @@ int main(int argc, char **argv) {
     double rr = -1.0;  // Russian roulette: keep the scene file's setting
     bool nee = false;  // light sampling: on if the scene file or --nee says so
     bool rtiow = false, have_file = false, count = false, no_png = false;
+    double adaptive = -1.0;  // noise target of adaptive sampling, < 0: off
+    bool have_adaptive = false;
+    int min_spp = 16, max_spp = 0;
+    bool have_min = false, have_max = false;
     int w = 0, h = 0, depth = 0, spp = 0, device = 0, chunk = 0, gpus = 0, tile_rows = 0;
     unsigned long long seed = 2023;
     unsigned scene_seed = 7;  // srand(7), main.cpp:119
@@ -83,6 +89,18 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--spp-begin")) spp_begin = atoll(need("--spp-begin"));
         else if (!strcmp(argv[i], "--rr")) rr = atof(need("--rr"));
         else if (!strcmp(argv[i], "--nee")) nee = true;
+        else if (!strcmp(argv[i], "--adaptive")) {
+            const char *v = need("--adaptive");
+            char *end = nullptr;
+            adaptive = strtod(v, &end);
+            have_adaptive = true;
+            if (end == v || *end != '\0' || !(adaptive >= 0.0) || adaptive > 3.4e38) {
+                fprintf(stderr, "rtmi: --adaptive needs a finite threshold >= 0, got '%s'\n", v);
+                return 2;
+            }
+        }
+        else if (!strcmp(argv[i], "--min-spp")) min_spp = atoi(need("--min-spp")), have_min = true;
+        else if (!strcmp(argv[i], "--max-spp")) max_spp = atoi(need("--max-spp")), have_max = true;
         else if (!strcmp(argv[i], "--rtiow")) rtiow = true;
         else if (!strcmp(argv[i], "--count")) count = true;
         else if (!strcmp(argv[i], "--no-png")) no_png = true;
@@ -91,6 +109,20 @@ int main(int argc, char **argv) {
             fprintf(stderr, "unknown argument '%s'\n", argv[i]);
             return usage(argv[0]);
         }
+    }
+    const bool progressive = !acc_in.empty() || !acc_out.empty() || spp_begin >= 0;
+    if (!have_adaptive && (have_min || have_max)) {
+        fprintf(stderr, "rtmi: --min-spp and --max-spp belong to --adaptive\n");
+        return 2;
+    }
+    if (have_adaptive && (gpus > 0 || progressive || count)) {
+        fprintf(stderr, "rtmi: --adaptive renders one frame on one device: it cannot be combined with %s\n",
+                gpus > 0 ? "--gpus" : (count ? "--count" : "--acc-in/--acc-out/--spp-begin"));
+        return 2;
+    }
+    if (have_adaptive && (min_spp < 2 || max_spp < 0 || (max_spp > 0 && max_spp < min_spp))) {
+        fprintf(stderr, "rtmi: --min-spp must be >= 2 and --max-spp 0 (the scene's spp) or >= --min-spp\n");
+        return 2;
     }
     double t0 = now_s();
     rt_scene *sc;
@@ -140,7 +172,6 @@ int main(int argc, char **argv) {
     std::vector<float> img((size_t)info.width * info.height * 3);
     int total_spp = info.samples_per_pixel;  // divisor of the written image
     int rc;
-    const bool progressive = !acc_in.empty() || !acc_out.empty() || spp_begin >= 0;
     if (progressive && gpus > 0) {
         fprintf(stderr, "rtmi: --gpus cannot be combined with --acc-in/--acc-out/--spp-begin\n");
         return 2;
@@ -200,6 +231,24 @@ int main(int argc, char **argv) {
         }
         if (rc == RT_OK)
             fprintf(stderr, "progressive: samples [%lld, %d) added, image holds %d spp\n", spp_begin, total_spp, total_spp);
+    } else if (have_adaptive) {
+        rt_adaptive a = {min_spp, max_spp, (float)adaptive};
+        rt_adaptive_stats ast;
+        std::vector<int32_t> spp_map((size_t)info.width * info.height);
+        rc = rt_render_hip_adaptive(sc, &o, &a, img.data(), spp_map.data(), &ast);
+        if (rc == RT_OK) {
+            // rescale every pixel to the scene's spp, so that the writers' division applies
+            for (size_t p = 0; p < spp_map.size(); ++p)
+                for (int c = 0; c < 3; ++c)
+                    img[p * 3 + c] = (float)((double)img[p * 3 + c] * total_spp / spp_map[p]);
+            const int cap = max_spp > 0 ? max_spp : info.samples_per_pixel;
+            const double full = (double)info.width * info.height * cap;
+            fprintf(stderr, "adaptive: threshold %g, %d passes, active tiles per pass (of %d):", adaptive, ast.passes, ast.tiles);
+            for (int k = 0; k < ast.passes; ++k) fprintf(stderr, " %d@%d", ast.active[k], ast.spp_after[k]);
+            fprintf(stderr, "\nadaptive: %llu pixel samples of %.0f at %d spp (%.1f %% saved), %.3f ms\n", (unsigned long long)ast.samples,
+                    full, cap, 100.0 * (1.0 - (double)ast.samples / full), ast.kernel_ms);
+            st.kernel_ms = ast.kernel_ms, st.upload_ms = 0;
+        }
     } else if (gpus > 0) {
         if (count) {
             fprintf(stderr, "rtmi: --count is a single-device diagnostic; drop --gpus\n");

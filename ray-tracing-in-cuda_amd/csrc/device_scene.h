@@ -79,10 +79,15 @@ enum MatKind : int32_t {
 // memory behind the queue counter (16 ints at queue[RT_ITEM_PARAMS_AT], written by a one-thread kernel before the
 // render launch; layout in item_params_kernel) and are read there, instead of occupying 14 SGPRs for the whole launch.
 #define RT_ITEM_PARAMS_AT 16
+// Adaptive sampling (rt_render_hip_adaptive): a launch with n_list != 0 renders only the tiles listed at queue[RT_TILE_LIST_AT ..
+// + n_list), one word per tile: band << 16 | x0 (x0 = 8 x tile column); item i is chunk i / n_list of tile list[i % n_list].
+// Such a launch carries tiles_x = n_list and bands = 1, which makes the plain decode compute i % n_list and i / n_list.
+#define RT_TILE_LIST_AT 64
 struct ItemParams {
     int32_t tiles_x, bands, num_items, sample_first, sample_count, spp_chunk, n_big, n_med, q_med, q_small;
     int32_t tile_rows, tile_first, tile_stride, local_rows;
     int32_t tile_rotate;  // how the tiles are dealt out to the shards (rt_opts.tile_rotate; shard.h)
+    int32_t n_list = 0;   // 0: every tile of the shard; else the length of the tile list
 };
 
 // kernel parameter block (passed by value: lands in SGPRs / the kernarg segment)

@@ -1111,6 +1111,15 @@
                     c_x0 = (int)(item % tiles_x) * 8;
                     c_band = (int)((item / tiles_x) % bands);
                     const int chunk = (int)(item / (tiles_x * bands));
+                    if (ic.w != 0) {
+                        // a tile list of n_list = ic.w tiles (adaptive sampling, device_scene.h).  The host sets tiles_x = n_list
+                        // and bands = 1 for such a launch, so c_x0 / 8 is item % n_list and chunk is item / n_list: no division
+                        // of its own, one scalar 16-byte load (the list word's quad) behind the ipar4 barrier
+                        const int4 t = ipar4((RT_TILE_LIST_AT - RT_ITEM_PARAMS_AT) / 4 + (c_x0 >> 5));
+                        const int q = (c_x0 >> 3) & 3;
+                        const int w = q == 0 ? t.x : q == 1 ? t.y : q == 2 ? t.z : t.w;
+                        c_x0 = w & 0xffff, c_band = w >> 16;
+                    }
                     int s_stop;  // sample range: big chunks first, shorter and shorter ones towards the end of the queue
                     if (chunk < n_big) {
                         c_sbegin = sample_first + chunk * spp_chunk;

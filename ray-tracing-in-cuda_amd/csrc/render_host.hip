@@ -37,6 +37,11 @@ bool variant_has_count(unsigned variant);
 bool has_ablations();
 void launch_finalize(const unsigned long long *acc, float *out, size_t n, hipStream_t stream);
 void launch_item_params(unsigned int *queue, const ItemParams &ip, hipStream_t stream);
+void launch_adaptive_estimate(const long long *A, const long long *B, const unsigned int *list, int n_list, unsigned int *next_list,
+                              unsigned int *next_count, int *tile_n, int width, int height, int tiles_x, int nA, int nB, int n,
+                              bool retire_all, bool use_metric, double t4, hipStream_t stream);
+void launch_adaptive_merge(const long long *A, const long long *B, const int *tile_n, float *out, int *spp_map, int width, int height,
+                           int tiles_x, hipStream_t stream);
 int set_max_dynamic_lds(size_t bytes);
 bool variant_exists(unsigned variant);
 int variant_cull_mode(unsigned variant);
@@ -60,6 +65,10 @@ struct DeviceEntry {
     DevCounters *d_counters = nullptr;
     float *d_out = nullptr;  // framebuffer of the host-buffer entry points (rt_render_hip), kept between calls
     size_t out_bytes = 0;
+    char *d_adapt = nullptr;  // adaptive sampling: accumulator plane B, next tile list, tile counts, list counter
+    size_t adapt_bytes = 0;
+    int *d_spp = nullptr;     // spp_map of rt_render_hip_adaptive (host-buffer entry point)
+    size_t spp_bytes = 0;
     int num_cus = 0;
 };
 
@@ -81,6 +90,8 @@ struct DeviceSceneCache {
             if (e.d_acc) (void)hipFree(e.d_acc);
             if (e.d_counters) (void)hipFree(e.d_counters);
             if (e.d_out) (void)hipFree(e.d_out);
+            if (e.d_adapt) (void)hipFree(e.d_adapt);
+            if (e.d_spp) (void)hipFree(e.d_spp);
         }
         if (have) (void)hipSetDevice(cur);
     }
@@ -1053,33 +1064,18 @@ int rt_scene_table_image(const rt_scene *sc, float *dst, int cap_floats) {
     return info.image_floats;
 }
 
-static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, void *stream_v, rt_stats *stats,
-                       long long *h_acc, bool count) {
-    if (!sc || (!d_rgb_sum && !h_acc)) {
-        set_error("rt_render_hip_device: null scene or output pointer");
-        return RT_ERR_ARG;
-    }
-    const Scene &s = sc->s;
-    int rc = scene_validate(s);
-    if (rc) return rc;
-    Shard sh;
-    rc = shard_of(s, o, sh);
-    if (rc) return rc;
-    if (stats) {
-        memset(stats, 0, sizeof *stats);
-        stats->local_rows = sh.local_rows;
-    }
-    if (sh.local_rows == 0) return RT_OK;
+// How a launch cuts samples [first, first + sample_count) of `tiles` tiles into work items (ItemParams); spp_chunk_opt: rt_opts.spp_chunk
+struct ChunkPlan {
+    int spp_chunk, num_chunks, n_big, n_med, q_med, q_small, orphan_max;
+};
 
-    int sample_first = o ? o->sample_first : 0;
-    int sample_count = (o && o->sample_count > 0) ? o->sample_count : s.spp;
+static ChunkPlan plan_chunks(long long tiles, int sample_count, int spp_chunk_opt) {
     // samples per work item: scheduling only (the pixel sum is exact).  64 and 128 measure the same on MI355X for
     // frames that fill the chip (199.8 / 200.2 ms; 256: 204.3) and 128 halves the accumulator traffic -- one 1.5 KB
     // tile flush and a handful of orphaned paths per item; small frames get smaller chunks so that there are a few items per
     // resident wave (a 400x225 frame has 1450 tiles for ~6000 resident waves)
-    int spp_chunk = (o && o->spp_chunk > 0) ? o->spp_chunk : 0;
+    int spp_chunk = spp_chunk_opt > 0 ? spp_chunk_opt : 0;
     if (spp_chunk == 0) {
-        const long long tiles = (long long)((s.width + 7) / 8) * ((sh.local_rows + 7) / 8);
         // 8 items per resident wave, down to 4 samples each: the cost of a tile varies by two orders of magnitude (sky against a
         // triangle mesh), and a wave's share evens out only over several items (20 000 triangles at 1280 x 720 x 16: 31.2 ms
         // with 4 items of 8 samples per wave, 24.6 with 8 of 4; 20 000 spheres 10.1 either way)
@@ -1115,7 +1111,6 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     int n_big = sample_count / spp_chunk, n_med = 0, q_med = spp_chunk, q_small = spp_chunk;
     int num_chunks, orphan_max = 12;
     {
-        const long long tiles = (long long)((s.width + 7) / 8) * ((sh.local_rows + 7) / 8);
         const double r = 256.0 * 4 * RT_WAVES_PER_SIMD / (double)std::max(1LL, tiles);
         const int rem = sample_count - n_big * spp_chunk;
         int rest = rem;  // samples after the big chunks
@@ -1143,6 +1138,39 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
         // orphans: waiting for an item's last paths costs short items more (render_kernel.hip, step 4)
         orphan_max = orphan_env >= 0 ? std::min(63, orphan_env) : (r >= 0.5 ? 63 : 12);
     }
+    return ChunkPlan{spp_chunk, num_chunks, n_big, n_med, q_med, q_small, orphan_max};
+}
+
+// adaptive sampling (rt_render_hip_adaptive_device): the schedule that replaces render_impl's single launch
+struct AdaptiveRun {
+    const rt_adaptive *a;
+    int max_spp;          // resolved (0 -> the scene's spp)
+    int *d_spp_map;
+    rt_adaptive_stats *st;
+};
+
+static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, void *stream_v, rt_stats *stats,
+                       long long *h_acc, bool count, const AdaptiveRun *ad = nullptr) {
+    if (!sc || (!d_rgb_sum && !h_acc)) {
+        set_error("rt_render_hip_device: null scene or output pointer");
+        return RT_ERR_ARG;
+    }
+    const Scene &s = sc->s;
+    int rc = scene_validate(s);
+    if (rc) return rc;
+    Shard sh;
+    rc = shard_of(s, o, sh);
+    if (rc) return rc;
+    if (stats) {
+        memset(stats, 0, sizeof *stats);
+        stats->local_rows = sh.local_rows;
+    }
+    if (sh.local_rows == 0) return RT_OK;
+
+    int sample_first = o ? o->sample_first : 0;
+    int sample_count = (o && o->sample_count > 0) ? o->sample_count : s.spp;
+    const ChunkPlan plan = plan_chunks((long long)((s.width + 7) / 8) * ((sh.local_rows + 7) / 8), sample_count,
+                                       o ? o->spp_chunk : 0);
     if (sample_first < 0) {
         set_error("sample_first must be >= 0");
         return RT_ERR_ARG;
@@ -1250,9 +1278,9 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     P.tile_rows = sh.tile_rows, P.tile_first = sh.tile_first, P.tile_stride = sh.tile_stride;
     P.num_tiles = sh.num_tiles, P.local_rows = sh.local_rows;
     P.sample_first = sample_first, P.sample_count = sample_count;
-    P.spp_chunk = spp_chunk, P.num_chunks = num_chunks;
-    P.n_big = n_big, P.n_med = n_med, P.q_med = q_med, P.q_small = q_small;
-    P.orphan_max = orphan_max;
+    P.spp_chunk = plan.spp_chunk, P.num_chunks = plan.num_chunks;
+    P.n_big = plan.n_big, P.n_med = plan.n_med, P.q_med = plan.q_med, P.q_small = plan.q_small;
+    P.orphan_max = plan.orphan_max;
     uint64_t seed = o ? o->seed : 0;
     P.seed_lo = (uint32_t)seed, P.seed_hi = (uint32_t)(seed >> 32);
     P.tiles_x = (s.width + 7) / 8;
@@ -1338,13 +1366,13 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
         return RT_ERR_LIMIT;
     }
     const size_t plane = (size_t)sh.local_rows * s.width * 3;
-    const unsigned long long items64 = (unsigned long long)P.tiles_x * P.bands * num_chunks;
+    const unsigned long long items64 = (unsigned long long)P.tiles_x * P.bands * plan.num_chunks;
     if (items64 > 0x7fffffffull) {
         set_error("%llu work items exceed the queue counter", items64);
         return RT_ERR_LIMIT;
     }
     P.num_items = (int)items64;
-    // persistent launch: enough workgroups to fill the chip, never more than the work needs
+    // persistent launches: enough workgroups to fill the chip, never more than the work needs
     if (ent->num_cus == 0) {
         hipDeviceProp_t prop;
         HIP_TRY(hipGetDeviceProperties(&prop, device));
@@ -1352,8 +1380,6 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     }
     const unsigned long long resident =
         (unsigned long long)ent->num_cus * (nee ? blocks_per_cu_nee(variant, lds_bytes) : blocks_per_cu(variant, count, lds_bytes, ext));
-    const unsigned long long need_blocks = (items64 + 3) / 4;
-    const unsigned long long grid64 = need_blocks < resident ? (need_blocks ? need_blocks : 1) : resident;
 
     float *d_out = (float *)d_rgb_sum;
     DevCounters *d_cnt = nullptr;
@@ -1368,45 +1394,134 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     }
     if (stats) HIP_TRY(hipEventRecord(ev1, stream));
 
+    // accumulators, then (256-byte aligned: the kernel reads the ItemParams with 16-byte loads) the queue counter and the
+    // ItemParams, and for adaptive sampling the tile list.  They belong to this (scene, device): concurrent renders of ONE
+    // scene object on one device must share a stream (different scene objects, or clones, are independent)
+    const size_t queue_off = (plane * sizeof(unsigned long long) + 255) & ~(size_t)255;
+    const long long frame_tiles = (long long)P.tiles_x * P.bands;
+    const size_t need = queue_off + (ad ? (((size_t)(RT_TILE_LIST_AT + frame_tiles) * 4 + 255) & ~(size_t)255) : 256);
+    // one render launch: samples [first, first + n) of every tile of the shard (n_list = 0), or of the n_list tiles listed at
+    // queue[RT_TILE_LIST_AT] (the kernel's item decode then reads tiles_x as n_list and bands as 1)
+    auto enqueue = [&](unsigned long long *acc, unsigned int *d_queue, int first, int n, int n_list, const ChunkPlan &pl) -> int {
+        RenderParams Q = P;
+        Q.sample_first = first, Q.sample_count = n;
+        Q.spp_chunk = pl.spp_chunk, Q.num_chunks = pl.num_chunks;
+        Q.n_big = pl.n_big, Q.n_med = pl.n_med, Q.q_med = pl.q_med, Q.q_small = pl.q_small;
+        Q.orphan_max = pl.orphan_max;
+        const unsigned long long items = (unsigned long long)(n_list ? n_list : frame_tiles) * pl.num_chunks;
+        if (items > 0x7fffffffull) {
+            set_error("%llu work items exceed the queue counter", items);
+            return RT_ERR_LIMIT;
+        }
+        Q.num_items = (int)items;
+        {  // what a wave reads when it fetches or flushes an item (kept out of the kernel's SGPRs)
+            ItemParams ip;
+            ip.tiles_x = n_list ? n_list : Q.tiles_x, ip.bands = n_list ? 1 : Q.bands, ip.num_items = Q.num_items;
+            ip.sample_first = Q.sample_first, ip.sample_count = Q.sample_count, ip.spp_chunk = Q.spp_chunk;
+            ip.n_big = Q.n_big, ip.n_med = Q.n_med, ip.q_med = Q.q_med, ip.q_small = Q.q_small;
+            ip.tile_rows = Q.tile_rows, ip.tile_first = Q.tile_first, ip.tile_stride = Q.tile_stride;
+            ip.tile_rotate = sh.tile_rotate;
+            ip.local_rows = Q.local_rows;
+            ip.n_list = n_list;
+            launch_item_params(d_queue, ip, stream);
+        }
+        // persistent launch: enough workgroups to fill the chip, never more than the work needs
+        const unsigned long long need_blocks = (items + 3) / 4;
+        const unsigned long long grid = need_blocks < resident ? (need_blocks ? need_blocks : 1) : resident;
+        if (nee ? !launch_render_nee(Q, ent->d_image, acc, d_queue, lds_bytes, (unsigned)grid, stream, variant)
+                : !launch_render(Q, ent->d_image, acc, d_queue, d_cnt, lds_bytes, (unsigned)grid, stream, variant, ext)) {
+            set_error("kernel variant %u has no %s build", variant, count ? "counting" : (ext ? "triangle / texture" : "such"));
+            return RT_ERR_LIMIT;
+        }
+        return RT_OK;
+    };
+    auto ensure = [&](auto *&buf, size_t &have, size_t bytes) -> int {  // a kept device buffer of at least `bytes`
+        if (have < bytes) {
+            if (buf) HIP_TRY(hipFree(buf));
+            buf = nullptr, have = 0;
+            HIP_TRY(hipMalloc((void **)&buf, bytes));
+            have = bytes;
+        }
+        return RT_OK;
+    };
+
     int launches = 0;
-    if (s.max_depth <= 0 && !h_acc) {
+    if (ad) {
+        // ---- adaptive sampling.  Pass k renders samples [n_{k-1}, n_k) of the active tiles, the first half into plane A
+        // (ent->d_acc), the rest into plane B; the estimate kernel then retires the tiles that meet the noise target (or
+        // max_spp) and lists the others for the next pass.  The host reads the list's length back once per pass, to size
+        // the next launches: a stream synchronisation, i.e. the launch gap of a pass (~tens of us, <= 23 passes).
+        rc = ensure(ent->d_acc, ent->acc_bytes, need);
+        if (rc) return rc;
+        const size_t b_off = 0, list_off = queue_off, tn_off = list_off + (size_t)frame_tiles * 4;
+        const size_t cnt_off = tn_off + (size_t)frame_tiles * 4;
+        rc = ensure(ent->d_adapt, ent->adapt_bytes, cnt_off + 256);
+        if (rc) return rc;
+        HIP_TRY(hipMemsetAsync(ent->d_acc, 0, need, stream));
+        HIP_TRY(hipMemsetAsync(ent->d_adapt, 0, cnt_off + 256, stream));
+        long long *dA = reinterpret_cast<long long *>(ent->d_acc);
+        long long *dB = reinterpret_cast<long long *>(ent->d_adapt + b_off);
+        unsigned int *d_queue = reinterpret_cast<unsigned int *>(reinterpret_cast<char *>(ent->d_acc) + queue_off);
+        unsigned int *d_list = d_queue + RT_TILE_LIST_AT;
+        unsigned int *d_next = reinterpret_cast<unsigned int *>(ent->d_adapt + list_off);
+        int *d_tn = reinterpret_cast<int *>(ent->d_adapt + tn_off);
+        unsigned int *d_next_count = reinterpret_cast<unsigned int *>(ent->d_adapt + cnt_off);
+        std::vector<unsigned int> all((size_t)frame_tiles);  // every tile: band << 16 | x0
+        for (long long t = 0; t < frame_tiles; ++t) all[(size_t)t] = (unsigned)((t / P.tiles_x) << 16 | (t % P.tiles_x) * 8);
+        HIP_TRY(hipMemcpyAsync(d_list, all.data(), all.size() * 4, hipMemcpyHostToDevice, stream));
+        const double T = (double)ad->a->threshold;
+        const double t4 = (4.0 * T) * T;
+        rt_adaptive_stats &st = *ad->st;
+        int n_active = (int)frame_tiles, prev = 0, nA = 0, nB = 0;
+        for (int k = 0; n_active > 0; ++k) {
+            const int n = k == 0 ? ad->a->min_spp : (int)std::min(2LL * prev, (long long)ad->max_spp);
+            const int delta = n - prev, half = delta / 2;
+            for (int h = 0; h < 2 && s.max_depth > 0; ++h) {  // (max_depth <= 0: every sample is black, main.cpp:20,42)
+                const int first = h ? prev + half : prev, len = h ? delta - half : half;
+                if (len == 0) continue;
+                HIP_TRY(hipMemsetAsync(d_queue, 0, 4, stream));
+                rc = enqueue(h ? reinterpret_cast<unsigned long long *>(dB) : reinterpret_cast<unsigned long long *>(dA), d_queue, first,
+                             len, n_active, plan_chunks(n_active, len, o ? o->spp_chunk : 0));
+                if (rc) return rc;
+                ++launches;
+            }
+            nA += half, nB += delta - half;
+            HIP_TRY(hipMemsetAsync(d_next_count, 0, 4, stream));
+            launch_adaptive_estimate(dA, dB, d_list, n_active, d_next, d_next_count, d_tn, s.width, s.height, P.tiles_x, nA, nB, n,
+                                     n == ad->max_spp, T > 0.0, t4, stream);
+            ++launches;
+            unsigned int next = 0;
+            HIP_TRY(hipMemcpyAsync(&next, d_next_count, 4, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
+            st.spp_after[k] = n, st.active[k] = n_active, st.passes = k + 1;
+            n_active = (int)next;
+            if (n_active > 0) HIP_TRY(hipMemcpyAsync(d_list, d_next, (size_t)n_active * 4, hipMemcpyDeviceToDevice, stream));
+            prev = n;
+        }
+        launch_adaptive_merge(dA, dB, d_tn, d_out, ad->d_spp_map, s.width, s.height, P.tiles_x, stream);
+        ++launches;
+        std::vector<int> tn((size_t)frame_tiles);
+        HIP_TRY(hipMemcpyAsync(tn.data(), d_tn, tn.size() * 4, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        st.tiles = (int32_t)frame_tiles;
+        st.samples = 0;
+        for (long long t = 0; t < frame_tiles; ++t) {
+            const int x0 = (int)(t % P.tiles_x) * 8, y0 = (int)(t / P.tiles_x) * 8;
+            st.samples += (uint64_t)tn[(size_t)t] * (uint64_t)(std::min(8, s.width - x0) * std::min(8, s.height - y0));
+        }
+    } else if (s.max_depth <= 0 && !h_acc) {
         // while (depth > 0) never runs: every sample is black (main.cpp:20,42)
         HIP_TRY(hipMemsetAsync(d_out, 0, plane * sizeof(float), stream));
     } else {
-        // accumulators + the work-queue counter behind them, cleared together.  They belong to this
-        // (scene, device): concurrent renders of ONE scene object on one device must share a stream
-        // (different scene objects, or clones, are independent)
-        // accumulators, then (256-byte aligned: the kernel reads the ItemParams with 16-byte loads) the queue
-        // counter and the ItemParams
-        const size_t queue_off = (plane * sizeof(unsigned long long) + 255) & ~(size_t)255;
-        const size_t need = queue_off + 256;
-        if (ent->acc_bytes < need) {
-            if (ent->d_acc) HIP_TRY(hipFree(ent->d_acc));
-            ent->d_acc = nullptr;
-            ent->acc_bytes = 0;
-            HIP_TRY(hipMalloc((void **)&ent->d_acc, need));
-            ent->acc_bytes = need;
-        }
+        rc = ensure(ent->d_acc, ent->acc_bytes, need);
+        if (rc) return rc;
         HIP_TRY(hipMemsetAsync(ent->d_acc, 0, need, stream));
         // progressive rendering: continue from the caller's exact sums
         if (h_acc) HIP_TRY(hipMemcpyAsync(ent->d_acc, h_acc, plane * sizeof(long long), hipMemcpyHostToDevice, stream));
         unsigned int *d_queue = reinterpret_cast<unsigned int *>(reinterpret_cast<char *>(ent->d_acc) + queue_off);
-        {  // what a wave reads when it fetches or flushes an item (kept out of the kernel's SGPRs)
-            ItemParams ip;
-            ip.tiles_x = P.tiles_x, ip.bands = P.bands, ip.num_items = P.num_items;
-            ip.sample_first = P.sample_first, ip.sample_count = P.sample_count, ip.spp_chunk = P.spp_chunk;
-            ip.n_big = P.n_big, ip.n_med = P.n_med, ip.q_med = P.q_med, ip.q_small = P.q_small;
-            ip.tile_rows = P.tile_rows, ip.tile_first = P.tile_first, ip.tile_stride = P.tile_stride;
-            ip.tile_rotate = sh.tile_rotate;
-            ip.local_rows = P.local_rows;
-            launch_item_params(d_queue, ip, stream);
-        }
         if (s.max_depth > 0) {
-            if (nee ? !launch_render_nee(P, ent->d_image, ent->d_acc, d_queue, lds_bytes, (unsigned)grid64, stream, variant)
-                    : !launch_render(P, ent->d_image, ent->d_acc, d_queue, d_cnt, lds_bytes, (unsigned)grid64, stream, variant, ext)) {
-                set_error("kernel variant %u has no %s build", variant, count ? "counting" : (ext ? "triangle / texture" : "such"));
-                return RT_ERR_LIMIT;
-            }
+            rc = enqueue(ent->d_acc, d_queue, sample_first, sample_count, 0, plan);
+            if (rc) return rc;
             ++launches;
         }
         if (d_out) {
@@ -1487,7 +1602,7 @@ int rt_render_hip_device(const rt_scene *s, const rt_opts *o, void *d_rgb_sum, v
 }
 
 static int render_host_buffer(const rt_scene *sc, const rt_opts *o, float *rgb_sum, rt_stats *stats, bool count,
-                              long long *h_acc = nullptr) {
+                              long long *h_acc = nullptr, AdaptiveRun *ad = nullptr, int32_t *spp_map = nullptr) {
     if (!sc) {
         set_error("null scene");
         return RT_ERR_ARG;
@@ -1547,10 +1662,21 @@ static int render_host_buffer(const rt_scene *sc, const rt_opts *o, float *rgb_s
             ent->out_bytes = bytes;
         }
         d_out = ent->d_out;
+        if (ad) {  // ... and so is the sample-count map of the adaptive entry point
+            const size_t spp_bytes = bytes / 3 / sizeof(float) * sizeof(int32_t);
+            if (ent->spp_bytes < spp_bytes) {
+                if (ent->d_spp) HIP_TRY(hipFree(ent->d_spp));
+                ent->d_spp = nullptr, ent->spp_bytes = 0;
+                HIP_TRY(hipMalloc((void **)&ent->d_spp, spp_bytes));
+                ent->spp_bytes = spp_bytes;
+            }
+            ad->d_spp_map = ent->d_spp;
+        }
     }
-    rc = bytes ? render_impl(sc, o, d_out, nullptr, stats ? stats : &local, h_acc, count) : RT_OK;
+    rc = bytes ? render_impl(sc, o, d_out, nullptr, stats ? stats : &local, h_acc, count, ad) : RT_OK;
     if (rc == RT_OK && rgb_sum && bytes) {
         hipError_t e = hipMemcpy(rgb_sum, d_out, bytes, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && ad) e = hipMemcpy(spp_map, ad->d_spp_map, bytes / 3 / sizeof(float) * sizeof(int32_t), hipMemcpyDeviceToHost);
         if (e != hipSuccess) {
             set_error("hipMemcpy D2H failed: %s", hipGetErrorString(e));
             rc = RT_ERR_HIP;
@@ -1565,6 +1691,81 @@ int rt_render_hip(const rt_scene *s, const rt_opts *o, float *rgb_sum, rt_stats 
 
 int rt_render_hip_count(const rt_scene *s, const rt_opts *o, float *rgb_sum, rt_stats *stats) {
     return render_host_buffer(s, o, rgb_sum, stats, true);
+}
+
+// the arguments of the adaptive entry points, checked before any device access; fills the options of the run (samples [0, max_spp))
+static int adaptive_args(const rt_scene *sc, const rt_opts *o, const rt_adaptive *a, const void *rgb_sum, const void *spp_map,
+                         rt_opts &run, int &max_spp) {
+    if (!sc || !a || !rgb_sum || !spp_map) {
+        set_error("rt_render_hip_adaptive: null scene, schedule or output pointer");
+        return RT_ERR_ARG;
+    }
+    max_spp = a->max_spp ? a->max_spp : sc->s.spp;
+    if (a->min_spp < 2 || max_spp < a->min_spp) {
+        set_error("rt_render_hip_adaptive: min_spp %d must be >= 2 and max_spp %d >= min_spp", a->min_spp, max_spp);
+        return RT_ERR_ARG;
+    }
+    if (!(a->threshold >= 0.0f) || !std::isfinite(a->threshold)) {
+        set_error("rt_render_hip_adaptive: threshold must be finite and >= 0");
+        return RT_ERR_ARG;
+    }
+    if (max_spp > RT_MAX_SAMPLES_PER_PIXEL) {  // (render_impl's cap on the samples of a pixel)
+        set_error("max_spp %d exceeds %d samples per pixel, the range over which the fixed-point pixel sums are exact", max_spp,
+                  RT_MAX_SAMPLES_PER_PIXEL);
+        return RT_ERR_LIMIT;
+    }
+    if (o) {
+        run = *o;
+    } else {
+        rt_opts_default(&run);
+    }
+    if (run.tile_stride > 1) {
+        set_error("rt_render_hip_adaptive renders whole frames: tile_stride must be <= 1");
+        return RT_ERR_ARG;
+    }
+    if (run.sample_first != 0 || run.sample_count != 0) {
+        set_error("rt_render_hip_adaptive: the schedule owns the samples (sample_first and sample_count must be 0)");
+        return RT_ERR_ARG;
+    }
+    if (!variant_exists(run.variant)) {
+        set_error("unknown kernel variant %u", run.variant);
+        return RT_ERR_ARG;
+    }
+    run.tile_first = 0, run.tile_stride = 1;
+    run.sample_count = max_spp;
+    return RT_OK;
+}
+
+int rt_render_hip_adaptive_device(const rt_scene *s, const rt_opts *o, const rt_adaptive *a, void *d_rgb_sum, void *d_spp_map,
+                                  void *stream, rt_adaptive_stats *st) {
+    rt_opts run;
+    int max_spp = 0;
+    int rc = adaptive_args(s, o, a, d_rgb_sum, d_spp_map, run, max_spp);
+    if (rc) return rc;
+    rt_adaptive_stats local_st;
+    if (!st) st = &local_st;
+    memset(st, 0, sizeof *st);
+    AdaptiveRun ad{a, max_spp, static_cast<int *>(d_spp_map), st};
+    rt_stats stats;
+    rc = render_impl(s, &run, d_rgb_sum, stream, &stats, nullptr, false, &ad);
+    st->kernel_ms = stats.kernel_ms;
+    return rc;
+}
+
+int rt_render_hip_adaptive(const rt_scene *s, const rt_opts *o, const rt_adaptive *a, float *rgb_sum, int32_t *spp_map,
+                           rt_adaptive_stats *st) {
+    rt_opts run;
+    int max_spp = 0;
+    int rc = adaptive_args(s, o, a, rgb_sum, spp_map, run, max_spp);
+    if (rc) return rc;
+    rt_adaptive_stats local_st;
+    if (!st) st = &local_st;
+    memset(st, 0, sizeof *st);
+    AdaptiveRun ad{a, max_spp, nullptr, st};
+    rt_stats stats;
+    rc = render_host_buffer(s, &run, rgb_sum, &stats, false, nullptr, &ad, spp_map);
+    st->kernel_ms = stats.kernel_ms;
+    return rc;
 }
 
 int rt_render_hip_accumulate(const rt_scene *s, const rt_opts *o, int64_t *acc, float *rgb_sum, rt_stats *stats) {

@@ -475,9 +475,9 @@ bool variant_exists(unsigned variant) { return variant == 0 || variant_cull_mode
 __global__ void item_params_kernel(unsigned int *queue, ItemParams ip) {
     int *dst = reinterpret_cast<int *>(queue) + RT_ITEM_PARAMS_AT;
     // quad 0: tiles_x, bands, num_items, sample_first; quad 1: sample_count, spp_chunk, n_big, n_med;
-    // quad 2: q_med, q_small, tile_rotate, -; quad 3: tile_rows, tile_first, tile_stride, local_rows
+    // quad 2: q_med, q_small, tile_rotate, n_list; quad 3: tile_rows, tile_first, tile_stride, local_rows
     const int v[16] = {ip.tiles_x, ip.bands, ip.num_items, ip.sample_first, ip.sample_count, ip.spp_chunk, ip.n_big,
-                       ip.n_med, ip.q_med, ip.q_small, ip.tile_rotate, 0, ip.tile_rows, ip.tile_first, ip.tile_stride, ip.local_rows};
+                       ip.n_med, ip.q_med, ip.q_small, ip.tile_rotate, ip.n_list, ip.tile_rows, ip.tile_first, ip.tile_stride, ip.local_rows};
     for (int k = 0; k < 16; ++k) dst[k] = v[k];
 }
 
