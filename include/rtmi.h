@@ -257,7 +257,7 @@ int rt_scene_get_textures(const rt_scene *s, rt_texture *out, int cap);   /* -> 
 /* The device tables the host builds for a scene (no GPU needed: host logic tests, tools).  The reference rebuilds its object
  * graph on the device (move_to_device<<<1,1>>>, main.cu:374-446); here the host flattens the scene into ONE image of 16-byte
  * records -- sphere slots, the other primitives' records and boxes, the uniform grid over every primitive type (cells + lists),
- * cold records, materials -- which one memcpy uploads (csrc/device_scene.h, csrc/render_host.hip pack_scene). */
+ * cold records, materials -- which one memcpy uploads (csrc/device_scene.h, csrc/pack.hip pack_scene). */
 typedef struct rt_table_info {
     int32_t image_floats;      /* size of the image (rt_scene_table_image) */
     int32_t grid_wide;         /* 1: wide tables (32-bit entries, two words per cell: every primitive type listed); 0: compact

@@ -1,5 +1,5 @@
-// Device-side scene image shared between the host packer (render_hip.hip, host
-// part) and the kernel.  One contiguous buffer, 16-byte records:
+// Device-side scene image shared between the host packer (pack.hip) and the
+// kernel.  One contiguous buffer, 16-byte records:
 //
 //   HOT part (copied into LDS by every workgroup; everything the primitive loop reads)
 //     sphere  [ns + 4]  1 x float4   {cx, cy, cz, r*r}   big spheres first, then Morton-ordered
@@ -116,20 +116,23 @@ struct RenderParams {
     int32_t nr_a, nc_a, nt_a;
     int32_t off_tri_hot, off_tri_cold;
     int32_t ns_pad;          // sphere slots incl. never-hit padding (= ns)
-    int32_t np;              // leading slots that are always tested (big spheres), multiple of 8
+    int32_t np;              // leading slots that are always tested (big spheres), padded to a multiple of 4
     int32_t ncl;             // clusters of 8 slots after the prefix, each with a bounding box
-    int32_t cluster;         // spheres per culling cluster (a multiple of 4, chosen per scene by the packer)
+    int32_t cluster;         // spheres per culling cluster (RT_CLUSTER)
     int32_t off_box;         // 2 float4 per cluster: {min.xyz,_}, {max.xyz,_}
     int32_t ngr, off_gbox;   // outer boxes over RT_GROUP consecutive clusters
     int32_t nwin, off_wbox;  // window boxes over 64 consecutive clusters (64 / RT_GROUP outer boxes)
     // range tables: per window {box min.xyz}, {1 / slab width .xyz}, then per enabled axis RT_SLABS^2 64-bit masks
     int32_t off_rtab, rt_stride, rt_axes;  // float4 offset, float4 records per window, enabled axes (bit a)
-    // uniform grid over the clustered spheres (CULL == 5): 4 header records, cells (one 32-bit word each: first item << 8 |
-    // count), items (16-bit sphere slots); grid_cells == 0: the scene has no grid (no clustered spheres, or a cell with
-    // more than 255 spheres)
+    // uniform grid over the clustered spheres and the listed other primitives (the grid walks, CULL == 5, 6, 7): 4 header
+    // records, then the cells and their lists in the format of grid_wide; grid_cells == 0: the scene has no grid (nothing listed)
     int32_t off_grid, off_grid_cells, off_grid_items, grid_cells;
-    int32_t grid_wide;       // 1: wide grid tables (65536 sphere slots or more): 32-bit list entries, two 32-bit words per cell {first
-                             // entry, (n_near << 8) | n_all}, up to 1023 cells per axis and 255 entries per cell (CULL == 7, global memory)
+    int32_t grid_wide;       // 0: compact tables: 16-bit list entries, one 32-bit word per cell (first << 12 | n_near << 6 | n_all), up to 255
+                             // cells per axis and 63 entries per cell (CULL == 5, 6; sphere-only scenes whose tables fit LDS).
+                             // 1: wide tables: 32-bit list entries, two 32-bit words per cell {first entry, n_near | n_all << 10 |
+                             // n_other << 20}, up to 1023 cells per axis, 1023 sphere entries per tier and 4095 other entries per cell
+                             // (CULL == 7; scenes with other primitives or image textures, 65536 sphere slots or more, light
+                             // sampling, or compact tables beyond the LDS budget)
     int32_t grid_sheet;      // 1: the grid is one cell high (ny == 1): the walk steps along x and z only (CULL == 6)
     int32_t hot_vec4_grid;   // float4 count of the hot part through the grid tables (what the grid-walk kernel stages)
     int32_t hot_vec4_tables; // float4 count of the hot part including the range tables (what the range-table kernel stages)

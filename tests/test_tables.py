@@ -1,4 +1,4 @@
-"""Host logic of the candidate search (no GPU): the tables pack_scene (csrc/render_host.hip) builds, read back through
+"""Host logic of the candidate search (no GPU): the tables pack_scene (csrc/pack.hip) builds, read back through
 rt_scene_table_info / rt_scene_table_image and checked against the geometry.  The kernel only finds what a cell lists, so the
 invariant that matters is COVERAGE: every cell a primitive's exact box touches lists it (the lists are built from grown boxes:
 a superset), in the tier a ray origin near the cloud reads -- or the primitive is in the always-tested part of its table."""
