@@ -179,6 +179,18 @@ int rt_scene_set_russian_roulette(rt_scene *s, float p);
  * "light_sampling": true. */
 int rt_scene_set_light_sampling(rt_scene *s, int on);
 int rt_scene_get_light_sampling(const rt_scene *s); /* 1, 0, or -rt_status */
+/* Nested grid: a second grid level for scenes whose geometry is clustered (a detailed mesh standing in a room).  The candidate
+ * search is one uniform grid whose cell comes from the extent of all primitives; a cell that a dense mesh overfills can only
+ * hand its members to the set that is tested for every query.  With on = 1 such a scene -- one whose flat tables have a cell
+ * list longer than the nesting threshold (64 entries), or lost primitives through an overflowing cell -- is packed in the wide
+ * format with every cell above the threshold NESTED: it gets a sub-grid of its own, sized from what it holds (at most 32 cells
+ * per axis, one level), and the walk steps through the sub-cells while the ray is inside it.  Such a scene renders through
+ * kernel variant 52 (rt_opts.variant 0 or 52; 16 and 24 still scan it; the other grid variants fail with RT_ERR_ARG), to the
+ * same image bit for bit.  A scene with nothing to nest keeps its tables, its kernel and its bytes.  Not combined with light
+ * sampling: a nested scene with light sampling on and an emitter to sample fails to render with RT_ERR_ARG.
+ * on = 0 (default) switches it off; JSON: top-level "nested_grid": true. */
+int rt_scene_set_nested_grid(rt_scene *s, int on);
+int rt_scene_get_nested_grid(const rt_scene *s); /* 1, 0, or -rt_status */
 typedef struct rt_light {
     int32_t prim;        /* index into the primitive list                      */
     int32_t shape;       /* rt_prim_type: sphere, xy / xz / yz rect or cylinder */
@@ -261,7 +273,8 @@ int rt_scene_get_textures(const rt_scene *s, rt_texture *out, int cap);   /* -> 
 typedef struct rt_table_info {
     int32_t image_floats;      /* size of the image (rt_scene_table_image) */
     int32_t grid_wide;         /* 1: wide tables (32-bit entries, two words per cell: every primitive type listed); 0: compact
-                                  (sphere-only scenes whose tables fit LDS: 16-bit entries, one word per cell) */
+                                  (sphere-only scenes whose tables fit LDS: 16-bit entries, one word per cell); 2: wide tables
+                                  with nested cells (rt_scene_nested_info; grid_cells counts the top level's) */
     int32_t grid_sheet;        /* compact tables, grid one cell high */
     int32_t grid_cells, grid_n[3];
     float grid_min[3], grid_size[3];
@@ -273,9 +286,26 @@ typedef struct rt_table_info {
     int32_t off_sph_cold, off_rect_cold, off_cyl_cold, off_tri_cold; /* cold records: {.., material, list index, kind} */
     int32_t off_rect_hot, off_cyl_hot, off_tri_hot;
     int32_t hot_bytes_grid;    /* what a grid-walk kernel stages into LDS */
-    int32_t kernel_variant;    /* what rt_opts.variant = 0 renders this scene with (2, 6, 16, 36 or 44) */
+    int32_t kernel_variant;    /* what rt_opts.variant = 0 renders this scene with (2, 6, 16, 36, 44 or 52) */
 } rt_table_info;
 int rt_scene_table_info(const rt_scene *s, rt_table_info *out);
+/* The nested cells of the scene's tables (rt_scene_set_nested_grid); all zero while the tables are flat.  A nested cell's header
+ * in the cell table is {index of its sub-grid, 1023} (n_near = 1023 with n_all = 0: no plain cell has n_near > n_all).  Sub-grid
+ * i is the four records at off_sub_grids + 4 i: {min.xyz, first cell (bits)} {1 / size.xyz, 0} {size.xyz, 0} {nx, ny, nz (bits), 0};
+ * its cells are the nx ny nz headers from `first cell` on in the cell table (same numbering as the top level: they follow its
+ * grid_cells headers, from first_sub_cell), in the wide format, and their lists lie in the item table. */
+typedef struct rt_nested_info {
+    int32_t cells;           /* nested cells (= sub-grids) */
+    int32_t sub_cells;       /* cells of all sub-grids */
+    int64_t sub_items;       /* list entries of all sub-cells */
+    int32_t off_sub_grids;   /* record (float4) offset of the sub-grid records */
+    int32_t off_sub_cells;   /* record offset of the first sub-cell header (two headers per record) */
+    int32_t first_sub_cell;  /* ... and its index in the cell table */
+    int32_t threshold;       /* a cell with more list entries (near + far spheres + others) was nested */
+    int32_t axis_cap;        /* most cells per axis of a sub-grid */
+    int32_t longest;         /* longest list of a cell a walk can meet (plain cells and sub-cells) */
+} rt_nested_info;
+int rt_scene_nested_info(const rt_scene *s, rt_nested_info *out);
 /* copies min(cap_floats, image_floats) floats of the image; returns image_floats, or -rt_status */
 int rt_scene_table_image(const rt_scene *s, float *out, int cap_floats);
 
@@ -315,6 +345,7 @@ typedef struct rt_opts {
                               44  the same with the tables in global memory (scenes too large for LDS: no size limit)
                               16  no culling: the reference's linear hittable_list scan (a handful of primitives of several
                                   types; also the definition the other kernels' images are held to)
+                              52  the walk of 44 over tables with nested cells (rt_scene_set_nested_grid)
                              (rt_stats.kernel_variant reports the choice).  Libraries built with RTMI_ABLATIONS (the default
                              build: rt_has_ablations()) also carry measurement variants with the same image, bit for bit:
                                1 = 6 with strict one-lane-per-pixel ownership, 40 = 6 with its tables in global memory,
@@ -352,9 +383,9 @@ typedef struct rt_stats {
     /* rt_render_hip_tiles only: kernel_ms above is the SLOWEST device's render launches */
     uint64_t lane_cands;  /* culling by range tables: candidate clusters per LANE before the per-cluster box test;
                              grid: cell steps per LANE (lane_groups = lanes that entered the grid, lane_clusters =
-                             sphere tests per LANE) */
+                             sphere tests per LANE); a step into or inside the sub-grid of a nested cell counts as a cell step */
     int32_t cull_mode;    /* candidate search of the kernel that ran: 5 uniform grid (6: its walk along x and z only, for a
-                             grid one cell high), 3 range tables, 2 box hierarchy per lane, 1 wave votes, 0 none (flat scan) */
+                             grid one cell high; 7: over the wide tables; 8: over wide tables with nested cells), 3 range tables, 2 box hierarchy per lane, 1 wave votes, 0 none (flat scan) */
     int32_t cull_windows; /* windows of 64 clusters */
     double gather_ms;     /* root device: end of its own render -> assembled frame (ncclGather + row placement,
                              includes waiting for slower peers) */
@@ -462,13 +493,13 @@ const char *rt_status_string(int status);
 int rt_abi_version(void);
 /* sizeof of the ABI structs as this library was compiled (binding self-checks):
  * 0 rt_opts, 1 rt_stats, 2 rt_prim, 3 rt_material, 4 rt_texture, 5 rt_camera, 6 rt_scene_info, 7 rt_table_info,
- * 8 rt_adaptive, 9 rt_adaptive_stats; else 0 */
+ * 8 rt_adaptive, 9 rt_adaptive_stats, 10 rt_nested_info; else 0 */
 size_t rt_struct_size(int which);
 /* number of usable gfx950 devices, or -rt_status */
 int rt_device_count(void);
 /* 1 if this library carries the measurement variants of rt_opts.variant and the counting kernels of rt_render_hip_count
  * (the default build; `make ABLATIONS=0` builds the six product kernels alone: same ABI, rt_render_hip_count then
- * fails with RT_ERR_LIMIT and rt_opts.variant accepts 0, 2, 6, 16, 36, 44) */
+ * fails with RT_ERR_LIMIT and rt_opts.variant accepts 0, 2, 6, 16, 36, 44, 52) */
 int rt_has_ablations(void);
 /* Philox4x32-10 block (seeds every (pixel, sample) stream), for known-answer tests */
 void rt_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);

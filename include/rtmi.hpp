@@ -242,6 +242,9 @@ public:
     void set_russian_roulette(float p) { check(rt_scene_set_russian_roulette(s_, p), "set_russian_roulette"); }
     // light sampling: next-event estimation + MIS at lambertian and fuzzy-metal vertices (rt_scene_set_light_sampling)
     void set_light_sampling(bool on) { check(rt_scene_set_light_sampling(s_, on ? 1 : 0), "set_light_sampling"); }
+    // nested grid: overfull cells of the candidate grid get a sub-grid of their own (rt_scene_set_nested_grid)
+    void set_nested_grid(bool on) { check(rt_scene_set_nested_grid(s_, on ? 1 : 0), "set_nested_grid"); }
+    bool nested_grid() const { return rt_scene_get_nested_grid(s_) > 0; }
     // progressive rendering: adds samples [first, first + count) to the caller's exact pixel sums
     // (resized and zeroed when empty) and returns the framebuffer of the updated sums
     std::vector<float> accumulate(std::vector<int64_t> &acc, int first, int count, const rt_opts *opts = nullptr,

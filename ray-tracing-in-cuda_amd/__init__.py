@@ -137,6 +137,15 @@ class TableInfo(C.Structure):
     ]
 
 
+class NestedInfo(C.Structure):
+    """rt_nested_info (include/rtmi.h): the nested cells of a scene's tables; all zero while they are flat."""
+    _fields_ = [
+        ("cells", C.c_int32), ("sub_cells", C.c_int32), ("sub_items", C.c_int64),
+        ("off_sub_grids", C.c_int32), ("off_sub_cells", C.c_int32), ("first_sub_cell", C.c_int32),
+        ("threshold", C.c_int32), ("axis_cap", C.c_int32), ("longest", C.c_int32),
+    ]
+
+
 class Adaptive(C.Structure):
     """rt_adaptive (include/rtmi.h): the noise target of an adaptive render."""
     _fields_ = [("min_spp", C.c_int32), ("max_spp", C.c_int32), ("threshold", C.c_float)]
@@ -215,6 +224,9 @@ _sig("rt_scene_set_russian_roulette", C.c_int, _p, C.c_float)
 _sig("rt_scene_set_light_sampling", C.c_int, _p, C.c_int)
 _sig("rt_scene_get_light_sampling", C.c_int, _p)
 _sig("rt_scene_get_lights", C.c_int, _p, _p, C.c_int)
+_sig("rt_scene_set_nested_grid", C.c_int, _p, C.c_int)
+_sig("rt_scene_get_nested_grid", C.c_int, _p)
+_sig("rt_scene_nested_info", C.c_int, _p, C.POINTER(NestedInfo))
 _sig("rt_render_hip_count", C.c_int, _p, C.POINTER(Opts), _p, C.POINTER(Stats))
 _sig("rt_scene_table_info", C.c_int, _p, C.POINTER(TableInfo))
 _sig("rt_scene_table_image", C.c_int, _p, _p, C.c_int)
@@ -248,6 +260,7 @@ C_SYMBOLS = [
     "rt_scene_output_file", "rt_scene_rotate_cylinders", "rt_scene_set_output_file", "rt_scene_dna", "rt_scene_clone",
     "rt_scene_set_light_sampling", "rt_scene_get_light_sampling", "rt_scene_get_lights",
     "rt_render_hip_adaptive", "rt_render_hip_adaptive_device",
+    "rt_scene_set_nested_grid", "rt_scene_get_nested_grid", "rt_scene_nested_info",
 ]
 
 
@@ -325,6 +338,20 @@ class Scene:
     @property
     def light_sampling(self) -> bool:
         return _check_id(_lib.rt_scene_get_light_sampling(self._h), "get_light_sampling") != 0
+
+    def set_nested_grid(self, on: bool = True):
+        """A second grid level for clustered geometry (include/rtmi.h, rt_scene_set_nested_grid); False switches it off."""
+        _check(_lib.rt_scene_set_nested_grid(self._h, 1 if on else 0), "set_nested_grid")
+
+    @property
+    def nested_grid(self) -> bool:
+        return _check_id(_lib.rt_scene_get_nested_grid(self._h), "get_nested_grid") != 0
+
+    def nested_info(self) -> NestedInfo:
+        """The nested cells of this scene's tables (no GPU needed); all zero while the tables are flat."""
+        t = NestedInfo()
+        _check(_lib.rt_scene_nested_info(self._h, C.byref(t)), "rt_scene_nested_info")
+        return t
 
     def camera(self, lookfrom, lookat, vup, vfov, aspect_ratio=0.0, aperture=0.0, focus_dist=0.0):
         _check(_lib.rt_scene_set_camera(self._h, _v3(lookfrom), _v3(lookat), _v3(vup), vfov, aspect_ratio,

@@ -49,6 +49,7 @@ size_t rt_struct_size(int which) {
     case 7: return sizeof(rt_table_info);
     case 8: return sizeof(rt_adaptive);
     case 9: return sizeof(rt_adaptive_stats);
+    case 10: return sizeof(rt_nested_info);
     default: return 0;
     }
 }
@@ -160,6 +161,18 @@ int rt_scene_set_light_sampling(rt_scene *s, int on) {
 int rt_scene_get_light_sampling(const rt_scene *s) {
     if (bad_scene(s, "rt_scene_get_light_sampling")) return -RT_ERR_ARG;
     return s->s.light_sampling ? 1 : 0;
+}
+
+int rt_scene_set_nested_grid(rt_scene *s, int on) {
+    if (bad_scene(s, "rt_scene_set_nested_grid")) return RT_ERR_ARG;
+    s->s.nested_grid = on != 0;
+    s->s.touch();
+    return RT_OK;
+}
+
+int rt_scene_get_nested_grid(const rt_scene *s) {
+    if (bad_scene(s, "rt_scene_get_nested_grid")) return -RT_ERR_ARG;
+    return s->s.nested_grid ? 1 : 0;
 }
 
 int rt_scene_get_lights(const rt_scene *s, rt_light *out, int cap) {

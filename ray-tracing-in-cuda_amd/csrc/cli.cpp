@@ -43,6 +43,7 @@ static int usage(const char *argv0) {
             "usage: %s [-f scene.json | --rtiow] [-w W] [-h H] [-d DEPTH] [-spp N] [-o out.ppm]\n"
             "          [--seed S] [--scene-seed S] [--device N] [--chunk N] [--dump-json file] [--count] [--no-png]\n"
             "          [--acc-in sums.bin] [--acc-out sums.bin] [--spp-begin FIRST] [--rr SURVIVAL_PROBABILITY] [--nee]\n"
+            "          [--nested-grid]\n"
             "          [--gpus N] [--tile-rows R] [--adaptive THRESHOLD [--min-spp N] [--max-spp N]]\n",
             argv0);
     return 2;
@@ -55,6 +56,7 @@ int main(int argc, char **argv) {
     long long spp_begin = -1;
     double rr = -1.0;  // Russian roulette: keep the scene file's setting
     bool nee = false;  // light sampling: on if the scene file or --nee says so
+    bool nested = false;  // nested grid: on if the scene file or --nested-grid says so
     bool rtiow = false, have_file = false, count = false, no_png = false;
     double adaptive = -1.0;  // noise target of adaptive sampling, < 0: off
     bool have_adaptive = false;
@@ -89,6 +91,7 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--spp-begin")) spp_begin = atoll(need("--spp-begin"));
         else if (!strcmp(argv[i], "--rr")) rr = atof(need("--rr"));
         else if (!strcmp(argv[i], "--nee")) nee = true;
+        else if (!strcmp(argv[i], "--nested-grid")) nested = true;
         else if (!strcmp(argv[i], "--adaptive")) {
             const char *v = need("--adaptive");
             char *end = nullptr;
@@ -138,6 +141,10 @@ int main(int argc, char **argv) {
         return 1;
     }
     if (nee && rt_scene_set_light_sampling(sc, 1) != RT_OK) {
+        fprintf(stderr, "rtmi: %s\n", rt_last_error());
+        return 1;
+    }
+    if (nested && rt_scene_set_nested_grid(sc, 1) != RT_OK) {
         fprintf(stderr, "rtmi: %s\n", rt_last_error());
         return 1;
     }

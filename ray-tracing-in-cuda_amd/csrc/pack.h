@@ -31,8 +31,15 @@ constexpr double knob(const char *, double fallback) { return fallback; }
 constexpr bool knob_set(const char *) { return false; }
 #endif
 
+// The nested cells of a packing (rt_nested_info of include/rtmi.h): all zero when the tables are flat
+struct NestedInfo {
+    int32_t cells = 0, sub_cells = 0;
+    long long sub_items = 0;
+    int32_t off_sub_grids = 0, off_sub_cells = 0, first_sub_cell = 0, threshold = 0, axis_cap = 0, longest = 0;
+};
+
 // Packs the scene's tables into `image` (float4 records) and the packer's fields of `layout` (counts, offsets, table
 // format; the per-launch fields stay zero).  RT_OK, or RT_ERR_LIMIT (set_error) when no round of packing succeeds.
-int pack_scene(const Scene &s, std::vector<float> &image, RenderParams &layout);
+int pack_scene(const Scene &s, std::vector<float> &image, RenderParams &layout, NestedInfo *nested = nullptr);
 
 }  // namespace rtmi

@@ -257,7 +257,17 @@ struct Grid {
     int n[3] = {0, 0, 0};
     float ob2[2] = {0.0f, 0.0f}, shrink = 0.0f;
     std::vector<OBox> listed_box;  // grown boxes of the listed others (also what their box tests read)
+    // nested cells (build_grid with a nesting threshold): the cells of every sub-grid follow the top-level ones in `cells`,
+    // their lists are in `items`; subs: 4 records per nested cell, in the order of the top-level header {min.xyz, first
+    // cell (bits)} {1/size.xyz, 0} {size.xyz, 0} {nx, ny, nz (bits), 0}
+    std::vector<float> subs;
+    int top_cells = 0;  // cells of the top level (= cells.size() / 2 without nested cells)
+    size_t sub_items = 0, longest = 0;  // list entries of the sub-cells; the longest list (near + far + others) a walk can meet
+    bool demoted = false;               // fill_cells forced the members of an overflowing cell
 };
+
+// a nested cell's header word 1 (n_near = 1023 > n_all = 0 never occurs in a plain cell); word 0 = its sub-grid (index into subs / 16)
+constexpr uint32_t kNestedMark = 1023u;
 
 // per clustered sphere: the radius of its near-tier and far-tier listing
 struct Growth {
@@ -386,8 +396,139 @@ enum class Fill {
     more_forced,  // primitives were added to `forced`: pack again
 };
 
-// The cells' lists in g's format
-Fill fill_cells(const Scene &s, const SphereSlots &S, const OtherPrims &O, const Growth &gr, Grid &g, std::vector<char> &forced) {
+// One nested cell's sub-grid.  It spans the part of the cell that its entries' grown balls / boxes reach (a mesh is a thin
+// slab of its cell) and is sized from the entries by the spacing rule of size_grid (their centres, clipped to that box), at
+// most `cap` cells per axis and 8 sub-cells per entry; every entry is listed in the sub-cells its grown ball / box touches --
+// the growth of the top level, whose walk term is that of the larger cell.  Appends to g.cells / items / subs.
+// False: a sub-cell's list overflows the wide format (its members are then in `forced`).
+bool nest_cell(const Scene &s, const SphereSlots &S, const OtherPrims &O, const Growth &gr, Grid &g, std::vector<char> &forced,
+               const int cell_idx[3], const std::vector<uint32_t> &near, const std::vector<uint32_t> &far,
+               const std::vector<uint32_t> &others, int cap) {
+    double clo[3], chi[3];
+    for (int a = 0; a < 3; ++a)
+        clo[a] = (double)g.min[a] + (double)g.size[a] * cell_idx[a], chi[a] = (double)g.min[a] + (double)g.size[a] * (cell_idx[a] + 1);
+    const int ns = S.ns();
+    const double cell_lo[3] = {clo[0], clo[1], clo[2]}, cell_hi[3] = {chi[0], chi[1], chi[2]};
+    auto rest_of = [&](uint32_t slot) { return (size_t)(((int)slot - S.np) / (RT_CLUSTER + 1) * RT_CLUSTER + ((int)slot - S.np) % (RT_CLUSTER + 1)); };
+    {  // what the entries reach of the cell
+        double rlo[3] = {1e300, 1e300, 1e300}, rhi[3] = {-1e300, -1e300, -1e300};
+        for (const std::vector<uint32_t> *v : {&near, &far})
+            for (uint32_t slot : *v) {
+                const size_t k = rest_of(slot);
+                for (int a = 0; a < 3; ++a) {
+                    const double c = (double)s.prims[S.rest[k]].f[a];
+                    rlo[a] = std::min(rlo[a], c - gr.far[k]), rhi[a] = std::max(rhi[a], c + gr.far[k]);
+                }
+            }
+        for (uint32_t gid : others) {
+            const OBox &b = g.listed_box[(size_t)O.oidx[O.prim_of_gid((int)gid, ns)]];
+            for (int a = 0; a < 3; ++a) rlo[a] = std::min(rlo[a], b.lo[a]), rhi[a] = std::max(rhi[a], b.hi[a]);
+        }
+        for (int a = 0; a < 3; ++a) {
+            clo[a] = std::min(std::max(rlo[a], cell_lo[a]), cell_hi[a]), chi[a] = std::max(std::min(rhi[a], cell_hi[a]), cell_lo[a]);
+            if (!(chi[a] - clo[a] > 1e-6 * (cell_hi[a] - cell_lo[a]))) clo[a] = cell_lo[a], chi[a] = cell_hi[a];  // (degenerate: the whole cell)
+        }
+    }
+    double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
+    auto add_point = [&](const double *c) {
+        for (int a = 0; a < 3; ++a) {
+            const double x = std::min(std::max(c[a], clo[a]), chi[a]);
+            lo[a] = std::min(lo[a], x), hi[a] = std::max(hi[a], x);
+        }
+    };
+    for (const std::vector<uint32_t> *v : {&near, &far})
+        for (uint32_t slot : *v) {
+            const float *sp = s.prims[S.slots[slot]].f;
+            const double c[3] = {sp[0], sp[1], sp[2]};
+            add_point(c);
+        }
+    for (uint32_t gid : others) {
+        const OBox &b = O.obox[(size_t)O.oidx[O.prim_of_gid((int)gid, ns)]];
+        const double c[3] = {0.5 * (b.lo[0] + b.hi[0]), 0.5 * (b.lo[1] + b.hi[1]), 0.5 * (b.lo[2] + b.hi[2])};
+        add_point(c);
+    }
+    const size_t count = near.size() + far.size() + others.size();
+    double ext[3], big = 0.0, measure = 1.0;
+    for (int a = 0; a < 3; ++a) ext[a] = hi[a] - lo[a], big = std::max(big, ext[a]);
+    int dims = 0, n[3];
+    bool spread[3];
+    for (int a = 0; a < 3; ++a) {
+        spread[a] = ext[a] > 0.05 * big;
+        if (spread[a]) ++dims, measure *= ext[a];
+    }
+    double cell = dims ? std::pow(measure / (double)count, 1.0 / dims) * (dims == 3 ? 0.85 : 1.25) : 1.0;
+    if (!(cell > 0.0)) cell = 1.0;
+    for (;;) {
+        long long total = 1;
+        for (int a = 0; a < 3; ++a) {
+            n[a] = spread[a] ? (int)std::min((double)cap, std::max(1.0, std::ceil((chi[a] - clo[a]) / cell))) : 1;
+            total *= n[a];
+        }
+        if (total <= 8LL * (long long)count) break;
+        cell *= 1.3;
+    }
+    float smin[3], ssize[3];
+    for (int a = 0; a < 3; ++a) smin[a] = (float)clo[a], ssize[a] = (float)((chi[a] - clo[a]) / n[a]);
+    auto cell_of = [&](int a, double x) {
+        const int i = (int)std::floor((x - (double)smin[a]) / (double)ssize[a]);
+        return std::min(std::max(i, 0), n[a] - 1);
+    };
+    const size_t n_sub = (size_t)n[0] * n[1] * n[2];
+    std::vector<std::vector<uint32_t>> lists(n_sub), extra(n_sub), olist(n_sub);
+    for (int tier = 0; tier < 2; ++tier)
+        for (uint32_t slot : tier ? far : near) {
+            const size_t k = rest_of(slot);
+            int c0[3], c1[3], n0[3], n1[3];
+            for (int a = 0; a < 3; ++a) {
+                const double c = (double)s.prims[S.rest[k]].f[a];
+                c0[a] = cell_of(a, c - gr.far[k]), c1[a] = cell_of(a, c + gr.far[k]);
+                n0[a] = cell_of(a, c - gr.near[k]), n1[a] = cell_of(a, c + gr.near[k]);
+            }
+            for (int iz = c0[2]; iz <= c1[2]; ++iz)
+                for (int iy = c0[1]; iy <= c1[1]; ++iy)
+                    for (int ix = c0[0]; ix <= c1[0]; ++ix) {
+                        // (an entry of the outer cell's far tier stays in the far tier of every sub-cell)
+                        const bool nr = tier == 0 && ix >= n0[0] && ix <= n1[0] && iy >= n0[1] && iy <= n1[1] && iz >= n0[2] && iz <= n1[2];
+                        (nr ? lists : extra)[((size_t)iz * n[1] + iy) * n[0] + ix].push_back(slot);
+                    }
+        }
+    for (uint32_t gid : others) {
+        const OBox &b = g.listed_box[(size_t)O.oidx[O.prim_of_gid((int)gid, ns)]];
+        int c0[3], c1[3];
+        for (int a = 0; a < 3; ++a) c0[a] = cell_of(a, b.lo[a]), c1[a] = cell_of(a, b.hi[a]);
+        for (int iz = c0[2]; iz <= c1[2]; ++iz)
+            for (int iy = c0[1]; iy <= c1[1]; ++iy)
+                for (int ix = c0[0]; ix <= c1[0]; ++ix) olist[((size_t)iz * n[1] + iy) * n[0] + ix].push_back(gid);
+    }
+    const uint32_t first_cell = (uint32_t)(g.cells.size() / 2);
+    bool ok = true;
+    for (size_t c = 0; c < n_sub; ++c) {
+        const size_t n_near = lists[c].size(), n_all = n_near + extra[c].size(), n_other = olist[c].size();
+        if (n_all > 1023 || n_other > 4095 || g.items.size() + n_all + n_other >= ((size_t)1 << 30)) {
+            ok = false;  // one level of nesting: a clump even here is tested for every query, as in the flat tables
+            for (uint32_t slot : lists[c]) forced[S.slots[slot]] = 1;
+            for (uint32_t slot : extra[c]) forced[S.slots[slot]] = 1;
+            for (uint32_t gid : olist[c]) forced[O.prim_of_gid((int)gid, ns)] = 1;
+            continue;
+        }
+        g.cells.push_back((uint32_t)g.items.size());
+        g.cells.push_back((uint32_t)n_near | ((uint32_t)n_all << 10) | ((uint32_t)n_other << 20));
+        g.items.insert(g.items.end(), lists[c].begin(), lists[c].end());
+        g.items.insert(g.items.end(), extra[c].begin(), extra[c].end());
+        g.items.insert(g.items.end(), olist[c].begin(), olist[c].end());
+        g.sub_items += n_all + n_other;
+        g.longest = std::max(g.longest, n_all + n_other);
+    }
+    float rec[16] = {};
+    for (int a = 0; a < 3; ++a) rec[a] = smin[a], rec[4 + a] = ssize[a] > 0.0f ? 1.0f / ssize[a] : 0.0f, rec[8 + a] = ssize[a], rec[12 + a] = bits(n[a]);
+    rec[3] = bits((int32_t)first_cell);
+    g.subs.insert(g.subs.end(), rec, rec + 16);
+    return ok;
+}
+
+// The cells' lists in g's format.  nest_over > 0 (wide tables): a cell whose list is longer becomes a nested cell (nest_cell).
+Fill fill_cells(const Scene &s, const SphereSlots &S, const OtherPrims &O, const Growth &gr, Grid &g, std::vector<char> &forced,
+                size_t nest_over = 0, int nest_cap = 0) {
     const size_t max_per_cell = g.wide ? 1023 : 63, max_other = 4095;
     const size_t max_items = g.wide ? ((size_t)1 << 30) : ((size_t)1 << 20);
     const int nx = g.n[0], ny = g.n[1], nz = g.n[2];
@@ -431,12 +572,22 @@ Fill fill_cells(const Scene &s, const SphereSlots &S, const OtherPrims &O, const
     }
     if (too_wide) return Fill::more_forced;
     g.cells.resize(lists.size() * (g.wide ? 2 : 1));
+    g.top_cells = (int)lists.size();
+    if (nest_over > 0 && (lists.size() & 1)) g.cells.resize(g.cells.size() + 2), ++g.top_cells;  // (an empty cell: the sub-cells start on a record)
     bool overflow = false;
     for (size_t cidx = 0; cidx < lists.size(); ++cidx) {
         const size_t n_near = lists[cidx].size(), n_all = n_near + extra[cidx].size(), n_other = olist[cidx].size();
+        if (nest_over > 0 && n_all + n_other > nest_over) {
+            const int cell_idx[3] = {(int)(cidx % (size_t)nx), (int)(cidx / (size_t)nx % (size_t)ny), (int)(cidx / ((size_t)nx * ny))};
+            g.cells[2 * cidx] = (uint32_t)(g.subs.size() / 16), g.cells[2 * cidx + 1] = kNestedMark;
+            if (!nest_cell(s, S, O, gr, g, forced, cell_idx, lists[cidx], extra[cidx], olist[cidx], nest_cap)) overflow = true, g.demoted = true;
+            continue;
+        }
+        g.longest = std::max(g.longest, n_all + n_other);
         if (n_all > max_per_cell || n_other > max_other || g.items.size() + n_all + n_other >= max_items) {
             overflow = true;
             if (g.wide) {  // a clump even for the wide tables: its members are tested for every query from now on
+                g.demoted = true;
                 for (uint32_t slot : lists[cidx]) forced[S.slots[slot]] = 1;
                 for (uint32_t slot : extra[cidx]) forced[S.slots[slot]] = 1;
                 for (uint32_t gid : olist[cidx]) forced[O.prim_of_gid((int)gid, S.ns())] = 1;
@@ -460,8 +611,9 @@ int lay_out_hot(RenderParams &L, const Grid &g);
 
 // The grid in the wide format if `wide`, else compact, falling back to wide when a compact list overflows or the compact
 // tables would not leave the kernel its full occupancy.  L: the counts.  False: more primitives were forced, pack again.
+// nest_over > 0 (with `wide`): cells with longer lists become nested cells.
 bool build_grid(const Scene &s, const SphereSlots &S, const OtherPrims &O, const RenderParams &L, bool wide,
-                std::vector<char> &forced, Grid &g) {
+                std::vector<char> &forced, Grid &g, size_t nest_over, int nest_cap) {
     size_t n_listed = S.rest.size();
     for (char l : O.listed) n_listed += l ? 1 : 0;
     g = Grid();
@@ -469,7 +621,7 @@ bool build_grid(const Scene &s, const SphereSlots &S, const OtherPrims &O, const
     if (n_listed == 0) return true;  // no grid: empty tables, n = {0, 0, 0}
     for (;;) {
         const Growth gr = size_grid(s, S, O, n_listed, g);
-        const Fill f = fill_cells(s, S, O, gr, g, forced);
+        const Fill f = fill_cells(s, S, O, gr, g, forced, g.wide ? nest_over : 0, nest_cap);
         if (f == Fill::more_forced) return false;
         if (g.wide) return true;
         RenderParams with = L;  // (the offsets these compact tables would give)
@@ -500,6 +652,10 @@ int lay_out_hot(RenderParams &L, const Grid &g) {
     off += ((int)g.cells.size() + 3) / 4;
     L.off_grid_items = off;
     off += g.wide ? ((int)g.items.size() + 1 + 3) / 4 : ((int)g.items.size() + 1 + 7) / 8;  // (+ 1: the pair test reads one entry past a list)
+    if (!g.subs.empty()) {  // the sub-grid records of the nested cells, each one 64-byte line (the header's record 3 holds the offset)
+        off = (off + 3) & ~3;
+        off += (int)(g.subs.size() / 4);
+    }
     return off;
 }
 
@@ -696,6 +852,11 @@ void write_grid(float *I, const RenderParams &L, const Grid &gr) {
         g[12 + a] = bits(gr.n[a]);
     }
     g[3] = gr.ob2[0], g[7] = gr.ob2[1], g[11] = gr.shrink;
+    if (!gr.subs.empty()) {
+        const int off_sub = (L.off_grid_items + ((int)gr.items.size() + 1 + 3) / 4 + 3) & ~3;
+        g[15] = bits(off_sub);
+        memcpy(rec4(I, off_sub), gr.subs.data(), gr.subs.size() * sizeof(float));
+    }
     if (!gr.cells.empty()) memcpy(rec4(I, L.off_grid_cells), gr.cells.data(), gr.cells.size() * sizeof(uint32_t));
     if (gr.items.empty()) return;
     if (gr.wide) {
@@ -870,10 +1031,18 @@ void write_lights(float *I, const RenderParams &L, const Scene &s, const SphereS
     }
 }
 
+// what a round tells pack_scene beside the image
+struct PackNote {
+    bool demoted = false;  // (this or an earlier round) the members of an overflowing cell were forced
+    size_t longest = 0;    // the longest list (near + far + others) of a cell a walk can meet
+    NestedInfo nested;
+};
+
 // ---- one round ---------------------------------------------------------------------------------
 // forced: primitives that must be tested for every query whatever their size (members of a cell whose list overflowed in an
 // earlier round).  False, with more primitives added to `forced`, when the grid could not list them.
-bool pack_round(const Scene &s, std::vector<char> &forced, std::vector<float> &image, RenderParams &L) {
+bool pack_round(const Scene &s, std::vector<char> &forced, std::vector<float> &image, RenderParams &L, size_t nest_over, int nest_cap,
+                PackNote &note) {
     std::vector<int> sph, rec, cyl, tri;
     for (size_t i = 0; i < s.prims.size(); ++i) {
         switch (s.prims[i].type) {
@@ -900,10 +1069,14 @@ bool pack_round(const Scene &s, std::vector<char> &forced, std::vector<float> &i
     L.nl = (int)lights.size();
 
     Grid g;
-    const bool wide = !sphere_only || S.ns() >= 65536 || !lights.empty() || knob_set("RTMI_FORCE_WIDE");  // (the knob: measurement)
-    if (!build_grid(s, S, O, L, wide, forced, g)) return false;
-    L.grid_cells = (int)(g.cells.size() / (g.wide ? 2 : 1));
-    L.grid_wide = g.wide ? 1 : 0;
+    const bool wide = !sphere_only || S.ns() >= 65536 || !lights.empty() || nest_over > 0 || knob_set("RTMI_FORCE_WIDE");  // (the knob: measurement)
+    const bool built = build_grid(s, S, O, L, wide, forced, g, nest_over, nest_cap);
+    note.demoted = note.demoted || g.demoted;
+    if (!built) return false;
+    note.longest = g.longest;
+    const bool nested = !g.subs.empty();
+    L.grid_cells = nested ? g.n[0] * g.n[1] * g.n[2] : (int)(g.cells.size() / (g.wide ? 2 : 1));
+    L.grid_wide = g.wide ? (nested ? 2 : 1) : 0;
     L.grid_sheet = (!g.cells.empty() && g.n[1] == 1 && !g.wide) ? 1 : 0;
     std::vector<int> image_word;
     const int records = lay_out_image(L, g, s, image_word);
@@ -922,18 +1095,54 @@ bool pack_round(const Scene &s, std::vector<char> &forced, std::vector<float> &i
     write_texels(I, s, image_word);
     write_materials(I, L, s, S, O, image_word);
     if (L.nl > 0) write_lights(I, L, s, S, O, lights);
+    note.nested = NestedInfo();
+    if (nested) {
+        note.nested.cells = (int)(g.subs.size() / 16);
+        note.nested.sub_cells = (int)(g.cells.size() / 2) - g.top_cells;
+        note.nested.sub_items = (long long)g.sub_items;
+        note.nested.off_sub_grids = __builtin_bit_cast(int32_t, rec4(I, L.off_grid)[15]);
+        note.nested.off_sub_cells = L.off_grid_cells + g.top_cells / 2;  // (two cells per record; top_cells is even here)
+        note.nested.first_sub_cell = g.top_cells;
+        note.nested.threshold = (int)nest_over, note.nested.axis_cap = nest_cap;
+        note.nested.longest = (int)g.longest;
+    }
     return true;
 }
 
 }  // namespace
 
-int pack_scene(const Scene &s, std::vector<float> &image, RenderParams &layout) {
+int pack_scene(const Scene &s, std::vector<float> &image, RenderParams &layout, NestedInfo *nested_out) {
     // a cell's list that overflows even the wide tables (more than a thousand primitives through one cell: a clump) moves its
     // members to the always-tested set and the tables are rebuilt: in the limit the scene is scanned, which is the reference's
     // algorithm.  Every round removes at least one primitive from the lists, and real scenes need none.
     std::vector<char> forced(s.prims.size(), 0);
-    for (size_t round = 0; round <= s.prims.size(); ++round)
-        if (pack_round(s, forced, image, layout)) return RT_OK;
+    PackNote note;
+    if (nested_out) *nested_out = NestedInfo();
+    bool packed = false;
+    for (size_t round = 0; round <= s.prims.size() && !packed; ++round) packed = pack_round(s, forced, image, layout, 0, 0, note);
+    // The nested grid (rt_scene_set_nested_grid): only a scene whose flat tables have a cell longer than the threshold, or lost
+    // primitives to the always-tested set through an overflowing cell, is packed again -- wide, from a clean slate, with such
+    // cells nested.  If that packing nests nothing (every clump was a clump in its sub-grid too), the flat tables stand.
+    if (packed && s.nested_grid) {
+        // Threshold and cap: an evenly spread mesh gives the flat grid lists of 17.8 entries on average, 32 at most, and the walk
+        // is tuned to those; twice the longest keeps every such scene flat.  Sweep in DESIGN 7c.
+        const size_t nest_over = (size_t)std::max(1.0, knob("RTMI_NEST_OVER", 64.0));
+        const int nest_cap = (int)std::min(1023.0, std::max(1.0, knob("RTMI_NEST_CAP", 32.0)));
+        if (note.demoted || note.longest > nest_over) {
+            std::vector<char> forced2(s.prims.size(), 0);
+            std::vector<float> image2;
+            RenderParams layout2;
+            PackNote note2;
+            bool packed2 = false;
+            for (size_t round = 0; round <= s.prims.size() && !packed2; ++round)
+                packed2 = pack_round(s, forced2, image2, layout2, nest_over, nest_cap, note2);
+            if (packed2 && note2.nested.cells > 0) {
+                image = std::move(image2), layout = layout2;
+                if (nested_out) *nested_out = note2.nested;
+            }
+        }
+    }
+    if (packed) return RT_OK;
     set_error("packing the scene tables: %zu rounds left primitives unlisted", s.prims.size() + 1);
     return RT_ERR_LIMIT;
 }

@@ -4,7 +4,9 @@
 // kernel's parameters by reference changes the order of the kernel-argument loads and with it the register allocation).
 // Not a header of its own: it needs the kernel's scope (P, image, acc, queue, counters and the template arguments).
     extern __shared__ float4 lds[];
-    constexpr bool GRID = CULL == 5 || CULL == 6 || CULL == 7, SHEET = CULL == 6, WIDE = CULL == 7;
+    constexpr bool GRID = CULL == 5 || CULL == 6 || CULL == 7 || CULL == 8, SHEET = CULL == 6, WIDE = CULL == 7 || CULL == 8;
+    constexpr bool NEST = CULL == 8;  // wide tables with nested cells (rt_scene_set_nested_grid)
+    static_assert(!NEST || (SCALAR && !SPH), "the nested walk reads its tables from global memory, in the general builds");
     constexpr int CSIZE = RT_CLUSTER;
     static_assert(!(CULL == 5 || CULL == 6) || SPH, "the compact grid tables list spheres only");
     static_assert(!(SPH && EXT), "image textures and triangles come with the general builds");
@@ -472,9 +474,24 @@
                 constexpr bool OTHERS = WIDE && !SPH;
                 const uint32_t *g_items32 = reinterpret_cast<const uint32_t *>(g_items);
                 int ko = 0, koend = 0;  // OTHERS: the entries of the cell's other primitives still to test
+                // NEST: a nested cell's header is {its sub-grid, 1023} (n_near = 1023 > n_all = 0: no list looks like that).  A lane
+                // that steps into one walks the sub-grid front to back, clipped to its stay in the outer cell, and then takes up
+                // the outer walk where it left it.  sub >= 0: the sub-grid this lane is about to enter; in_sub: it walks one, and
+                // o_*: the outer walk's state meanwhile; t_cur: the ray parameter at which the lane entered its outer cell.
+                int sub = -1;
+                bool in_sub = false;
+                float t_cur = 0.0f, o_tmx = 0.0f, o_tmy = 0.0f, o_tmz = 0.0f, o_texit = 0.0f;
+                uint32_t o_rem = 0;
+                int o_ci = 0;
                 auto cell_list = [&](int cell, int &first, int &end) {  // a cell's list entries [first, end) of this lane's tier
                     if (WIDE) {
                         const uint2 h = reinterpret_cast<const uint2 *>(g_cells)[cell];
+                        if constexpr (NEST) {
+                            if (h.y == 1023u) {
+                                sub = (int)h.x, first = end = 0, ko = koend = 0;
+                                return;
+                            }
+                        }
                         first = (int)h.x, end = first + (int)((h.y >> cnt_shift) & CNT_MASK);
                         if (OTHERS) ko = (int)h.x + (int)((h.y >> 10) & CNT_MASK), koend = ko + (int)(h.y >> 20);
                     } else {
@@ -524,14 +541,15 @@
                         rem = (uint32_t)(dx > 0.0f ? gnx - 1 - ix : ix) | (SHEET ? 0u : (uint32_t)(dy > 0.0f ? gny - 1 - iy : iy) << REM_BITS) |
                               (uint32_t)(dz > 0.0f ? gnz - 1 - iz : iz) << (2 * REM_BITS);
                         cell_list(ci, k, kend);
+                        if constexpr (NEST) t_cur = tn;
                         if (COUNT && t_res == 0.0f) c_lane_groups++, c_group_maxpop += tier_far ? 1u : 0u;
                     }
                 }
                 if (COUNT && far_scan) c_query_maxpop++;
                 t_res = 0.0f;
                 // |size / d| per axis: what one step adds to the leave distance
-                const float dtx = g_size.x * fabsf(bp.idx), dty = g_size.y * fabsf(bp.idy), dtz = g_size.z * fabsf(bp.idz);
-                const int sx = dx > 0.0f ? 1 : -1, sy = dy > 0.0f ? gnx : -gnx, sz = SHEET ? (dz > 0.0f ? gnx : -gnx) : (dz > 0.0f ? gnx * gny : -(gnx * gny));
+                float dtx = g_size.x * fabsf(bp.idx), dty = g_size.y * fabsf(bp.idy), dtz = g_size.z * fabsf(bp.idz);
+                int sx = dx > 0.0f ? 1 : -1, sy = dy > 0.0f ? gnx : -gnx, sz = SHEET ? (dz > 0.0f ? gnx : -gnx) : (dz > 0.0f ? gnx * gny : -(gnx * gny));
                 // cell by cell: the wave first drains the lists of the cells its lanes stand in (one sphere per lane and
                 // pass), then every lane steps (measured: 47.4 ms against 54.8 for one flattened loop in which a lane either
                 // tests or steps, RTIOW 256 spp)
@@ -544,6 +562,42 @@
 #endif
                 if (RT_PRIO_W != RT_PRIO_Q) __builtin_amdgcn_s_setprio(RT_PRIO_W);
                 while (__builtin_amdgcn_ballot_w64(live) != 0ull) {
+                    if constexpr (NEST) {
+                        if (live && sub >= 0) {
+                            // into the sub-grid of the nested cell this lane stands in: one 64-byte line per lane {min, first
+                            // cell} {1 / size} {size} {n}.  The sub-grid spans what the cell's entries reach of the outer cell
+                            // (grown, like the lists); the walk through it is the outer walk's code on this state, over the
+                            // part of the ray's stay in the outer cell that lies inside those bounds.  Sub-cells are never nested.
+                            const float4 *sg = image + (__float_as_int(gh[3].w) + 4 * sub);
+                            const float4 s_min = sg[0], s_inv = sg[1], s_size = sg[2], s_n = sg[3];
+                            const int snx = __float_as_int(s_n.x), sny = __float_as_int(s_n.y), snz = __float_as_int(s_n.z);
+                            o_tmx = tmx, o_tmy = tmy, o_tmz = tmz, o_texit = t_exit, o_rem = rem, o_ci = ci;
+                            // (exact slab distances, as at the grid's bounds; a ray that misses the sub-grid gets t_exit = -inf,
+                            //  which ends the sub-grid's walk at its first step)
+                            const float lx = (s_min.x - ox) * bp.idx, ux = (fmaf((float)snx, s_size.x, s_min.x) - ox) * bp.idx;
+                            const float ly = (s_min.y - oy) * bp.idy, uy = (fmaf((float)sny, s_size.y, s_min.y) - oy) * bp.idy;
+                            const float lz = (s_min.z - oz) * bp.idz, uz = (fmaf((float)snz, s_size.z, s_min.z) - oz) * bp.idz;
+                            const float t_in = fmaxf(fmaxf(fmaxf(fminf(lx, ux), fminf(ly, uy)), t_cur), fminf(lz, uz));
+                            t_exit = fminf(fminf(fminf(t_exit, fminf(fminf(tmx, tmy), tmz)), fminf(fmaxf(lx, ux), fmaxf(ly, uy))), fmaxf(lz, uz));
+                            const bool miss = t_in > fminf(t_exit, best_t * 1.0001f);
+                            const float px = fmaf(t_in, dx, ox), py = fmaf(t_in, dy, oy), pz = fmaf(t_in, dz, oz);
+                            const int ix = min(max((int)floorf((px - s_min.x) * s_inv.x), 0), snx - 1);
+                            const int iy = min(max((int)floorf((py - s_min.y) * s_inv.y), 0), sny - 1);
+                            const int iz = min(max((int)floorf((pz - s_min.z) * s_inv.z), 0), snz - 1);
+                            ci = __float_as_int(s_min.w) + (iz * sny + iy) * snx + ix;
+                            tmx = dx == 0.0f ? INFINITY : (fmaf((float)(ix + (dx > 0.0f ? 1 : 0)), s_size.x, s_min.x) - ox) * bp.idx;
+                            tmy = dy == 0.0f ? INFINITY : (fmaf((float)(iy + (dy > 0.0f ? 1 : 0)), s_size.y, s_min.y) - oy) * bp.idy;
+                            tmz = dz == 0.0f ? INFINITY : (fmaf((float)(iz + (dz > 0.0f ? 1 : 0)), s_size.z, s_min.z) - oz) * bp.idz;
+                            rem = (uint32_t)(dx > 0.0f ? snx - 1 - ix : ix) | (uint32_t)(dy > 0.0f ? sny - 1 - iy : iy) << REM_BITS |
+                                  (uint32_t)(dz > 0.0f ? snz - 1 - iz : iz) << (2 * REM_BITS);
+                            dtx = s_size.x * fabsf(bp.idx), dty = s_size.y * fabsf(bp.idy), dtz = s_size.z * fabsf(bp.idz);
+                            sx = dx > 0.0f ? 1 : -1, sy = dy > 0.0f ? snx : -snx, sz = dz > 0.0f ? snx * sny : -(snx * sny);
+                            in_sub = true, sub = -1;
+                            if (miss) t_exit = -INFINITY;
+                            else cell_list(ci, k, kend);
+                            if (COUNT) c_lane_cands++;
+                        }
+                    }
                     while (__builtin_amdgcn_ballot_w64(k < kend) != 0ull) {
                         if (COUNT) c_clusters++;
                         // two list entries per pass: both index reads, then both record reads, are in flight together, and a
@@ -611,6 +665,20 @@
                     const bool cut = RT_WALK_TAIL > 0 && mask_count(walking) <= RT_WALK_TAIL &&
                                      mask_count(__builtin_amdgcn_ballot_w64(active) & ~walking) >= RT_WALK_WAITING;
                     if (live && !(k < kend) && !(OTHERS && ko < koend)) {
+                        if constexpr (NEST) {
+                            if (in_sub) {
+                                // the sub-grid's walk is over where the outer walk's would be (past the ray's stay in the outer
+                                // cell, which is t_exit here, or past a hit, or at the sub-grid's last cell): back to the outer one
+                                const float tn_s = fminf(fminf(tmx, tmy), tmz);
+                                const int sh_s = tmx == tn_s ? 0 : (tmy == tn_s ? REM_BITS : 2 * REM_BITS);
+                                if (tn_s > fminf(t_exit, best_t * 1.0001f) || ((rem >> sh_s) & REM_MASK) == 0u) {
+                                    tmx = o_tmx, tmy = o_tmy, tmz = o_tmz, t_exit = o_texit, rem = o_rem, ci = o_ci;
+                                    dtx = g_size.x * fabsf(bp.idx), dty = g_size.y * fabsf(bp.idy), dtz = g_size.z * fabsf(bp.idz);
+                                    sx = dx > 0.0f ? 1 : -1, sy = dy > 0.0f ? gnx : -gnx, sz = dz > 0.0f ? gnx * gny : -(gnx * gny);
+                                    in_sub = false;
+                                }
+                            }
+                        }
                         const float tnext = SHEET ? fminf(tmx, tmz) : fminf(fminf(tmx, tmy), tmz);
                         const bool xle = tmx == tnext, yle = !SHEET && !xle && tmy == tnext;
                         const int sh = xle ? 0 : (yle ? REM_BITS : 2 * REM_BITS);
@@ -624,6 +692,9 @@
                             tmx += xle ? dtx : 0.0f, tmz += (xle || yle) ? 0.0f : dtz;
                             if (!SHEET) tmy += yle ? dty : 0.0f;
                             rem -= 1u << sh;
+                            if constexpr (NEST) {
+                                if (!in_sub) t_cur = tnext;
+                            }
                             cell_list(ci, k, kend);
                             if (COUNT) c_lane_cands++;
                         }

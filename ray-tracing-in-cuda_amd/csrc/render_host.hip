@@ -78,6 +78,7 @@ struct DeviceSceneCache {
     uint64_t packed_version = 0;
     std::vector<float> image;  // float4 records
     RenderParams layout;       // ns/nr/nc/nm + offsets filled by pack
+    NestedInfo nested;         // the nested cells of that packing (all zero: flat tables)
     ~DeviceSceneCache() {
         int cur = 0;
         bool have = hipGetDevice(&cur) == hipSuccess;
@@ -118,10 +119,12 @@ static int ensure_packed(const Scene &s, DeviceSceneCache &cache) {
     if (cache.packed_version == s.version) return RT_OK;
     std::vector<float> image;
     RenderParams layout;
-    int rc = pack_scene(s, image, layout);
+    NestedInfo nested;
+    int rc = pack_scene(s, image, layout, &nested);
     if (rc) return rc;
     cache.image = std::move(image);
     cache.layout = layout;
+    cache.nested = nested;
     cache.packed_version = s.version;
     return RT_OK;
 }
@@ -267,6 +270,7 @@ int rt_device_count(void) {
 // what rt_opts.variant = 0 stands for in a scene with these tables
 static unsigned pick_variant(const RenderParams &P, bool counting, size_t lds_table_bytes) {
     if (!P.grid_wide) return P.grid_sheet ? 2u : 6u;
+    if (P.grid_wide == 2) return 52u;  // nested cells: the walk over global memory (such scenes are large)
     const size_t grid_bytes = (size_t)P.hot_vec4_grid * 16, scan_bytes = (size_t)(P.hot_vec4 - (P.off_box - P.off_grid)) * 16;
     // a handful of primitives of several types, none of them listed in a grid: the plain scan is the same search without
     // the per-query set-up (sample_scene.json: 54 against 79 ms)
@@ -313,6 +317,25 @@ static int read_tables(const rt_scene *sc, rt_table_info *out, float *dst, int c
 }
 
 int rt_scene_table_info(const rt_scene *sc, rt_table_info *out) { return read_tables(sc, out, nullptr, 0); }
+
+int rt_scene_nested_info(const rt_scene *sc, rt_nested_info *out) {
+    if (!sc || !out) {
+        set_error("rt_scene_nested_info: null argument");
+        return RT_ERR_ARG;
+    }
+    int rc = scene_validate(sc->s);
+    if (rc) return rc;
+    DeviceSceneCache &cache = cache_of(sc->s);
+    std::lock_guard<std::mutex> lock(cache.mu);
+    rc = ensure_packed(sc->s, cache);
+    if (rc) return rc;
+    const NestedInfo &n = cache.nested;
+    memset(out, 0, sizeof *out);
+    out->cells = n.cells, out->sub_cells = n.sub_cells, out->sub_items = n.sub_items;
+    out->off_sub_grids = n.off_sub_grids, out->off_sub_cells = n.off_sub_cells, out->first_sub_cell = n.first_sub_cell;
+    out->threshold = n.threshold, out->axis_cap = n.axis_cap, out->longest = n.longest;
+    return RT_OK;
+}
 
 int rt_scene_table_image(const rt_scene *sc, float *dst, int cap_floats) {
     rt_table_info info;
@@ -684,7 +707,7 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     P.tiles_x = (s.width + 7) / 8;
     P.bands = (sh.local_rows + 7) / 8;
 
-    // ---- which kernel.  LDS per workgroup: the hot tables (unless the variant reads them from global memory: bit 3) + one
+    // ---- which kernel.  LDS per workgroup: the hot tables (unless the variant reads them from global memory: bit 3, and variant 52) + one
     // tile accumulator per wave.  The tables live in LDS while that leaves room for the kernel's full occupancy
     // (RT_WAVES_PER_SIMD workgroups per CU); larger scenes run the same walk over global memory (4000 spheres 6.7 vs 19 ms),
     // which has no size limit.  The packer has chosen the table format (device_scene.h): COMPACT for sphere-only scenes whose
@@ -692,7 +715,7 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     const size_t acc_lds = kAccLds;
     auto hot_bytes_of = [&](unsigned v) {  // (each candidate search stages the part of the hot tables it reads)
         const int mode = variant_cull_mode(v);
-        if (mode == 5 || mode == 6 || mode == 7) return (size_t)P.hot_vec4_grid * 16;
+        if (mode == 5 || mode == 6 || mode == 7 || mode == 8) return (size_t)P.hot_vec4_grid * 16;
         return (size_t)((mode == 3 ? P.hot_vec4_tables : P.hot_vec4) - (P.off_box - P.off_grid)) * 16;  // (without the grid tables)
     };
     static const size_t global_threshold = (size_t)knob("RTMI_GLOBAL_TABLE_BYTES", (double)kLdsTableBytes);
@@ -701,6 +724,10 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     if (variant == 0) variant = pick(count);
     // light sampling on and something to sample: the layout's light-sampling kernel (built with triangles and textures)
     const bool nee = P.nl > 0;
+    if (nee && P.grid_wide == 2) {
+        set_error("this scene has the nested grid and light sampling on, which no kernel combines: switch one of them off");
+        return RT_ERR_ARG;
+    }
     if (nee && (count || !variant_has_nee(variant))) {
         set_error("%s: this scene has light sampling on, which the %s (the light-sampling kernels are variants 0, 16, 36 and 44)",
                   count ? "rt_render_hip_count" : "kernel variant", count ? "counting kernels do not carry" : "requested variant does not carry");
@@ -711,6 +738,16 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     if (count && !variant_has_count(variant)) variant = (variant == 2) ? 6u : pick(true);
     if (count && variant == 2) variant = 6;
     const int mode = variant_cull_mode(variant);
+    // nested cells are walked by variant 52 alone, and variant 52 walks nothing else; the linear scans read no grid
+    if (mode == 8 && P.grid_wide != 2) {
+        set_error("kernel variant %u walks tables with nested cells, which this scene does not have (rt_scene_set_nested_grid, and a "
+                  "cell to nest): use variant 0", variant);
+        return RT_ERR_ARG;
+    }
+    if (P.grid_wide == 2 && mode >= 5 && mode != 8) {
+        set_error("kernel variant %u does not walk the nested cells of this scene's tables: use variant 0, 52 or the linear scans 16 / 24", variant);
+        return RT_ERR_ARG;
+    }
     if ((mode == 5 || mode == 6) && P.grid_wide) {
         set_error("kernel variant %u reads the compact grid tables of a sphere-only scene that fits LDS; this scene has the wide ones "
                   "(other primitives, textures, 65536 sphere slots or more, or tables beyond %zu bytes): use variant 0, 36 or 44",
@@ -737,14 +774,15 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     if (force_ext && variant_has_ext(variant) && P.grid_wide) ext = true;
     if (nee) ext = true;
     const size_t hot_bytes = hot_bytes_of(variant);
-    const size_t lds_bytes = ((variant & 8u) ? 0 : hot_bytes) + acc_lds;
+    const bool tables_global = (variant & 8u) != 0 || mode == 8;
+    const size_t lds_bytes = (tables_global ? 0 : hot_bytes) + acc_lds;
     if (knob_set("RTMI_DEBUG_LAYOUT")) {
         const float *g = cache.image.data() + (size_t)P.off_grid * 4;
         int gn[3];
         memcpy(gn, g + 12, sizeof gn);
         fprintf(stderr, "variant %u: LDS %zu bytes per workgroup (tables %zu); %d prefix slots, %d clusters of %d; always-tested others %d + %d + %d "
                 "of %d + %d + %d; %s grid %d x %d x %d = %d cells, cell %.3f x %.3f x %.3f (vec4 records: cells %d, lists %d)\n",
-                variant, lds_bytes, (variant & 8u) ? (size_t)0 : hot_bytes, P.np, P.ncl, P.cluster, P.nr_a, P.nc_a, P.nt_a, P.nr, P.nc, P.nt,
+                variant, lds_bytes, tables_global ? (size_t)0 : hot_bytes, P.np, P.ncl, P.cluster, P.nr_a, P.nc_a, P.nt_a, P.nr, P.nc, P.nt,
                 P.grid_wide ? "wide" : "compact", gn[0], gn[1], gn[2], P.grid_cells,
                 g[8], g[9], g[10], P.off_grid_items - P.off_grid_cells, P.hot_vec4_grid - P.off_grid_items);
     }

@@ -245,6 +245,8 @@ __device__ __forceinline__ float cone_one_minus_cos(float r2, float c2) {
 //              other scene.  Its cells also list the rectangles, cylinders and triangles (taichi-version/bvh.py:109-199
 //              indexes every hittable): a lane tests what its cells list; only the oversized primitives (the RTIOW ground,
 //              a room's walls) are tested for every query
+//           8  the walk of 7 over wide tables with NESTED cells (rt_scene_set_nested_grid): a cell that clustered geometry
+//              overfills carries a sub-grid, which the lane walks while its ray is inside the cell.  Tables in global memory only
 //           ablations (RTMI_ABLATIONS builds): 3 range tables, 2 two-level box hierarchy per lane (round 1's default), 1 wave
 //           votes per cluster box (aabb.hpp:15-29 + __any), 0 no culling: the reference's linear hittable_list scan
 // EXT:      the Taichi renderer's extras -- triangles (taichi-version/hittable.py:38-71) and image textures read at the
@@ -278,6 +280,19 @@ __global__ __launch_bounds__(256, RT_NEE_WAVES_PER_SIMD) void render_nee_kernel(
 #include "render_body.h"
 }
 
+// nested grid (rt_scene_set_nested_grid): the global-memory walk over wide tables with nested cells (CULL 8), plain and with
+// triangles / image textures, and its counting build.  A kernel of its own, like the light-sampling one: the render_kernel
+// instances of a product build stay the eight they were.
+template <bool COUNT, bool EXT>
+__global__ __launch_bounds__(256, RT_WAVES_PER_SIMD) void render_nested_kernel(const RenderParams P, const float4 *__restrict__ image,
+                                                            unsigned long long *__restrict__ acc,
+                                                            unsigned int *__restrict__ queue,
+                                                            DevCounters *__restrict__ counters) {
+    constexpr bool POOL = true, SCALAR = true, SPH = false, NEE = false;
+    constexpr int CULL = 8;
+#include "render_body.h"
+}
+
 // fixed-point pixel sums -> fp32 framebuffer (rgb_sum[(row*W + x)*3 + c]); every store
 // instruction writes 256 contiguous bytes
 __global__ __launch_bounds__(256) void finalize_kernel(const unsigned long long *__restrict__ acc,
@@ -294,6 +309,10 @@ template __global__ void render_kernel<RT_ISA_ONLY>(const RenderParams, const fl
 // ... and one light-sampling instance (RT_ISA_ONLY_NEE = SCALAR, CULL)
 template __global__ void render_nee_kernel<RT_ISA_ONLY_NEE>(const RenderParams, const float4 *__restrict__, unsigned long long *__restrict__,
                                                             unsigned int *__restrict__, DevCounters *__restrict__);
+#elif defined(RT_ISA_ONLY_NESTED)
+// ... and one nested-grid instance (RT_ISA_ONLY_NESTED = COUNT, EXT)
+template __global__ void render_nested_kernel<RT_ISA_ONLY_NESTED>(const RenderParams, const float4 *__restrict__, unsigned long long *__restrict__,
+                                                                  unsigned int *__restrict__, DevCounters *__restrict__);
 #else
 // ---------------------------------------------------------------- launchers used by render_host.hip
 // X(variant id, POOL, SCALAR, CULL, SPH).  The host resolves variant 0 to one of the five PRODUCT instances:
@@ -303,7 +322,8 @@ template __global__ void render_nee_kernel<RT_ISA_ONLY_NEE>(const RenderParams, 
 //       (nothing is listed in a grid there; sample_scene.json 54 ms against 79 ms for 36 with its empty grid), and the
 //       definition every other kernel's image is held to
 // and 36, 44 and 16 also exist with EXT (triangles, image textures): eight render_kernel instances in a product build
-// (make ABLATIONS=0).  The default build (RTMI_ABLATIONS=1: tests, bench.py) adds the measurement variants -- same image, bit for
+// (make ABLATIONS=0), beside the light-sampling kernels and variant 52, the nested-grid walk (render_nested_kernel: scenes with
+// the nested grid on and a cell to nest; plain and EXT in every build, its counting build with RTMI_ABLATIONS).  The default build (RTMI_ABLATIONS=1: tests, bench.py) adds the measurement variants -- same image, bit for
 // bit -- and the counting kernels:
 //    1  variant 6 with strict one-lane-per-pixel ownership       40  variant 6 with its tables in global memory
 //   17  variant 16 with strict ownership                         24  variant 16 with its tables in global memory
@@ -349,6 +369,8 @@ template __global__ void render_nee_kernel<RT_ISA_ONLY_NEE>(const RenderParams, 
 #define RT_VARIANT_TABLE(X) RT_PRODUCT_TABLE(X) RT_ABLATION_TABLE(X)
 #define RT_EXT_TABLE(X) RT_PRODUCT_EXT_TABLE(X) RT_ABLATION_EXT_TABLE(X)
 
+constexpr unsigned kNestedVariant = 52;  // render_nested_kernel
+
 bool has_ablations() { return RTMI_ABLATIONS != 0; }
 
 // launches the instance of a RESOLVED variant (never 0); false: no such build
@@ -356,6 +378,20 @@ bool launch_render(const RenderParams &P, const void *image, unsigned long long 
                    DevCounters *counters, size_t lds_bytes, unsigned grid, hipStream_t stream, unsigned variant, bool ext) {
     const float4 *img = (const float4 *)image;
     const dim3 g(grid), t(256);
+    if (variant == kNestedVariant) {
+        if (counters) {
+#if RTMI_ABLATIONS
+            hipLaunchKernelGGL((render_nested_kernel<true, true>), g, t, lds_bytes, stream, P, img, acc, queue, counters);
+            return true;
+#else
+            return false;
+#endif
+        }
+        DevCounters *no_counters = nullptr;
+        if (ext) hipLaunchKernelGGL((render_nested_kernel<false, true>), g, t, lds_bytes, stream, P, img, acc, queue, no_counters);
+        else hipLaunchKernelGGL((render_nested_kernel<false, false>), g, t, lds_bytes, stream, P, img, acc, queue, no_counters);
+        return true;
+    }
     if (counters) {
 #define RT_LAUNCH_COUNT(V, SCALAR, CULL, EXT, SPH)                                                                                         \
     if (variant == V) {                                                                                                                     \
@@ -425,7 +461,13 @@ int blocks_per_cu_nee(unsigned variant, size_t lds_bytes) {
 int blocks_per_cu(unsigned variant, bool count, size_t lds_bytes, bool ext) {
     int n = 0;
     hipError_t e = hipErrorInvalidValue;
-    if (count) {
+    if (variant == kNestedVariant) {
+#if RTMI_ABLATIONS
+        if (count) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, render_nested_kernel<true, true>, 256, lds_bytes);
+#endif
+        if (!count && ext) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, render_nested_kernel<false, true>, 256, lds_bytes);
+        if (!count && !ext) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, render_nested_kernel<false, false>, 256, lds_bytes);
+    } else if (count) {
 #define RT_OCC_COUNT(V, SCALAR, CULL, EXT, SPH) \
     if (variant == V) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, render_kernel<true, true, SCALAR, CULL, EXT, SPH>, 256, lds_bytes);
         RT_COUNT_TABLE(RT_OCC_COUNT)
@@ -446,6 +488,7 @@ int blocks_per_cu(unsigned variant, bool count, size_t lds_bytes, bool ext) {
 
 // candidate search of a variant (the CULL template argument): decides how much of the hot table is staged; -1: no such build
 int variant_cull_mode(unsigned variant) {
+    if (variant == kNestedVariant) return 8;
 #define RT_MODE(V, POOL, SCALAR, CULL, SPH) \
     if (variant == V) return CULL;
     RT_VARIANT_TABLE(RT_MODE)
@@ -455,6 +498,7 @@ int variant_cull_mode(unsigned variant) {
 
 // does the variant have a build with triangles and image textures?
 bool variant_has_ext(unsigned variant) {
+    if (variant == kNestedVariant) return true;
 #define RT_HAS_EXT(V, POOL, SCALAR, CULL, SPH) \
     if (variant == V) return true;
     RT_EXT_TABLE(RT_HAS_EXT)
@@ -463,6 +507,7 @@ bool variant_has_ext(unsigned variant) {
 }
 
 bool variant_has_count(unsigned variant) {
+    if (variant == kNestedVariant) return RTMI_ABLATIONS != 0;
 #define RT_HAS_COUNT(V, SCALAR, CULL, EXT, SPH) \
     if (variant == V) return true;
     RT_COUNT_TABLE(RT_HAS_COUNT)

@@ -538,6 +538,10 @@ int scene_from_json(const char *text, size_t len, Scene &s, const char *base_dir
         if (f->kind != JsonValue::Bool) r.fail("top level: \"light_sampling\" must be a boolean");
         else s.light_sampling = f->b;
     }
+    if (const JsonValue *f = root.find("nested_grid")) {
+        if (f->kind != JsonValue::Bool) r.fail("top level: \"nested_grid\" must be a boolean");
+        else s.nested_grid = f->b;
+    }
 
     // camera, parser.hpp:113-141
     const JsonValue *cam = root.find("camera");
@@ -793,6 +797,7 @@ std::string scene_to_json(const Scene &s) {
     o += std::string("  \"defocus_blur\": ") + ((s.flags & RT_FLAG_DEFOCUS_BLUR) ? "true" : "false") + ",\n";
     if (s.rr_p > 0.0f) o += "  \"russian_roulette\": " + json_double((double)s.rr_p) + ",\n";
     if (s.light_sampling) o += "  \"light_sampling\": true,\n";
+    if (s.nested_grid) o += "  \"nested_grid\": true,\n";
     o += "  \"camera\": {\"lookfrom\": ";
     put_vec3d(o, s.cam.lookfrom);
     o += ", \"lookat\": ";

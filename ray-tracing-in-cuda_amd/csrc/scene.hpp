@@ -44,6 +44,7 @@ struct Scene {
     uint32_t flags = 0;
     float rr_p = 0.0f;  // Russian-roulette survival probability per bounce, 0 = off
     bool light_sampling = false;  // next-event estimation + MIS (rt_scene_set_light_sampling)
+    bool nested_grid = false;     // overfull grid cells get a sub-grid (rt_scene_set_nested_grid)
     std::string output_file = "main.png";  // parser.hpp:566-567 default
     CameraParams cam;
     std::vector<rt_prim> prims;
