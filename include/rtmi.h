@@ -493,7 +493,7 @@ const char *rt_status_string(int status);
 int rt_abi_version(void);
 /* sizeof of the ABI structs as this library was compiled (binding self-checks):
  * 0 rt_opts, 1 rt_stats, 2 rt_prim, 3 rt_material, 4 rt_texture, 5 rt_camera, 6 rt_scene_info, 7 rt_table_info,
- * 8 rt_adaptive, 9 rt_adaptive_stats, 10 rt_nested_info; else 0 */
+ * 8 rt_adaptive, 9 rt_adaptive_stats, 10 rt_nested_info, 16 rt_denoise; else 0 */
 size_t rt_struct_size(int which);
 /* number of usable gfx950 devices, or -rt_status */
 int rt_device_count(void);
@@ -547,6 +547,71 @@ int rt_render_hip_adaptive(const rt_scene *s, const rt_opts *o, const rt_adaptiv
  * active tile count back once per pass) */
 int rt_render_hip_adaptive_device(const rt_scene *s, const rt_opts *o, const rt_adaptive *a,
                                   void *d_rgb_sum, void *d_spp_map, void *stream, rt_adaptive_stats *st);
+
+/* ---- first-hit feature buffers and the denoiser --------------------------- */
+
+/* A feature sample is an ordinary sample up to its first closest-hit query: the same (seed, pixel, sample) stream, jitter,
+ * lens draw, camera ray and candidate search.  There the path ends and, in place of radiance, adds one triple to the
+ * pixel's exact fixed-point sum (no Russian-roulette draw, no light sample, no scatter; max_depth plays no part):
+ *   RT_FEATURE_ALBEDO  hit: lambertian / diffuse_light: the texture's value at the hit (solid, checker, image); metal: albedo;
+ *                           dielectric: (1, 1, 1).  miss: what the miss gives a fresh path (sky gradient or background)
+ *   RT_FEATURE_NORMAL  hit: the hit record's normal, turned against the ray (not re-normalised).  miss: (0, 0, 0)
+ *   RT_FEATURE_DEPTH   hit: (t of the hit record, 1, 0).  miss: (0, 0, 0) -- channel 1 sums to the samples that hit (coverage)
+ * The albedo pass of a scene is therefore, bit for bit, the render of its clone whose every material is a diffuse_light
+ * on the same texture. */
+typedef enum rt_feature {
+    RT_FEATURE_ALBEDO = 0,
+    RT_FEATURE_NORMAL = 1,
+    RT_FEATURE_DEPTH = 2
+} rt_feature;
+
+/* One feature pass: `sum` (host, rt_shard_rows()*W*3 floats, local rows dense, as rt_render_hip) receives the fp32
+ * conversion of the exact sums over samples [o->sample_first, + o->sample_count) (0 -> the scene's spp).  Honours the shard
+ * fields and spp_chunk like rt_render_hip; every split of a sample range and every row shard composes exactly.
+ * o->variant names the LAYOUT: 0 (the scene's default), 16 / 24 (linear scan, tables in LDS / global memory), 36 / 44 (wide
+ * grid walk) or 52 (nested walk); a scene with compact tables (variants 2, 6) runs the linear scan, in LDS while it fits and
+ * from global memory beyond (no size limit); every layout gives the same bytes.  Other variants fail with RT_ERR_ARG.  Light
+ * sampling and Russian roulette do not bear on a feature.  rt_stats.kernel_variant reports the layout | 512.
+ * RT_ERR_ARG for a null pointer or a feature outside 0..2, checked before any device access; stats may be NULL. */
+int rt_render_hip_feature(const rt_scene *s, const rt_opts *o, int feature, float *sum, rt_stats *stats);
+/* the same into a DEVICE buffer on `stream` (hipStream_t as void*), asynchronous when stats == NULL (rt_render_hip_device) */
+int rt_render_hip_feature_device(const rt_scene *s, const rt_opts *o, int feature, void *d_sum, void *stream,
+                                 rt_stats *stats);
+
+/* Edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) on the demodulated image (mean colour / first-hit albedo),
+ * guided by the three feature sums.  The definition -- prepare, weights, order of the taps, pixels without coverage -- is
+ * DESIGN.md section 7d; every operation in it is a single fp32 + - x / min max in a fixed order, so a numpy float32
+ * restatement reproduces the output bit for bit.
+ * A sigma of 0 means its default (sigma_color 0.5, sigma_normal 0.125, sigma_depth 0.05: measured).  iterations counts the passes, pass i with
+ * taps 2^i pixels apart: 0 .. 10, where 0 passes returns the input bits; RT_DENOISE_DEFAULT_ITERATIONS (-1) means the
+ * default, 3 -- as does a NULL rt_denoise, which is all defaults.  (0 cannot stand for both "no pass" and "the default":
+ * for this one field the default has a value of its own.)  rt_struct_size(16) reports sizeof(rt_denoise): index 11 and
+ * its neighbours are left to the structs of the scene and render interface. */
+#define RT_DENOISE_DEFAULT_ITERATIONS (-1)
+typedef struct rt_denoise {
+    int32_t iterations;   /* passes; 0 .. 10, or RT_DENOISE_DEFAULT_ITERATIONS                                    */
+    float sigma_color;    /* colour term: |e - e'| of the demodulated colours against sqrt(l^2 + 1/16), l the centre's
+                             r + g + b; halves from pass to pass                                                     */
+    float sigma_normal;   /* normal term: |n - n'| of the mean normals                                               */
+    float sigma_depth;    /* depth term: |t - t'| / t of the mean hit distances                                      */
+} rt_denoise;
+
+/* rgb_sum (host, H*W*3 floats): a frame of rt_render_hip over `spp` samples per pixel, or -- spp_map != NULL (H*W int32,
+ * spp then ignored) -- a frame of rt_render_hip_adaptive with its per-pixel sample counts (an entry < 1 counts as 1).
+ * albedo_sum, normal_sum, depth_sum: the three passes of rt_render_hip_feature over feature_spp samples each, whole frames.
+ * out_rgb_sum (must not overlap an input) receives the filtered frame, again a SUM over the pixel's samples:
+ * rt_write_ppm, rt_write_png and rt_quantize_rgb8 take it unchanged.  ms (may be NULL): hipEvent time of the kernels.
+ * RT_ERR_ARG, checked before any device access, for: a null buffer, a size <= 0 (or > 65536), spp <= 0 without an spp_map,
+ * feature_spp <= 0, a negative or non-finite sigma, iterations outside -1 .. 10. */
+int rt_denoise_hip(int width, int height, const float *rgb_sum, int spp, const int32_t *spp_map, const float *albedo_sum,
+                   const float *normal_sum, const float *depth_sum, int feature_spp, const rt_denoise *p, int device,
+                   float *out_rgb_sum, double *ms);
+/* the same on DEVICE buffers of device `device`, enqueued on `stream` (hipStream_t as void*); asynchronous when ms == NULL.
+ * Scratch buffers (three planes of 16 bytes per pixel) are kept per device between calls: overlapping calls on one
+ * device must share a stream. */
+int rt_denoise_hip_device(int width, int height, const void *d_rgb_sum, int spp, const void *d_spp_map,
+                          const void *d_albedo_sum, const void *d_normal_sum, const void *d_depth_sum, int feature_spp,
+                          const rt_denoise *p, int device, void *d_out_rgb_sum, void *stream, double *ms);
 
 #ifdef __cplusplus
 }

@@ -270,6 +270,30 @@ public:
         check(rt_render_hip_adaptive(s_, opts, &a, img.data(), spp_map.data(), stats), "render_adaptive");
         return img;
     }
+    // one first-hit feature pass (rt_render_hip_feature): local_rows*W*3 sums over the samples of `opts`
+    std::vector<float> render_feature(rt_feature feature, const rt_opts *opts = nullptr, rt_stats *stats = nullptr) const {
+        const rt_scene_info i = info();
+        const int rows = opts ? rt_shard_rows(s_, opts) : i.height;
+        if (rows < 0) throw error(-rows, "render_feature");
+        std::vector<float> sum((size_t)rows * i.width * 3);
+        check(rt_render_hip_feature(s_, opts, (int)feature, sum.data(), stats), "render_feature");
+        return sum;
+    }
+    // the edge-avoiding filter on a whole frame of this scene (rt_denoise_hip); spp_map: the per-pixel counts of render_adaptive
+    std::vector<float> denoise(const std::vector<float> &rgb_sum, int spp, const std::vector<float> &albedo_sum,
+                               const std::vector<float> &normal_sum, const std::vector<float> &depth_sum, int feature_spp,
+                               const rt_denoise *params = nullptr, const std::vector<int32_t> *spp_map = nullptr, int device = 0,
+                               double *ms = nullptr) const {
+        const rt_scene_info i = info();
+        const size_t n = (size_t)i.width * i.height * 3;
+        if (rgb_sum.size() != n || albedo_sum.size() != n || normal_sum.size() != n || depth_sum.size() != n ||
+            (spp_map && spp_map->size() * 3 != n))
+            throw error(RT_ERR_ARG, "denoise: buffer sizes");
+        std::vector<float> out(n);
+        check(rt_denoise_hip(i.width, i.height, rgb_sum.data(), spp, spp_map ? spp_map->data() : nullptr, albedo_sum.data(),
+                             normal_sum.data(), depth_sum.data(), feature_spp, params, device, out.data(), ms), "denoise");
+        return out;
+    }
     rt_scene *handle() const { return s_; }
 
 private:

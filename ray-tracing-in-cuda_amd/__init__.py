@@ -164,6 +164,15 @@ class AdaptiveStats(C.Structure):
                 "samples": self.samples, "kernel_ms": self.kernel_ms}
 
 
+class Denoise(C.Structure):
+    """rt_denoise (include/rtmi.h): the filter's parameters; a sigma of 0 is its default, iterations -1 the default count."""
+    _fields_ = [("iterations", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float)]
+
+
+FEATURE_ALBEDO, FEATURE_NORMAL, FEATURE_DEPTH = 0, 1, 2
+DENOISE_DEFAULT_ITERATIONS = -1
+
+
 def _sig(name, restype, *argtypes):
     fn = getattr(_lib, name)
     fn.restype = restype
@@ -242,6 +251,12 @@ _sig("rt_scene_output_file", C.c_char_p, _p)
 _sig("rt_philox4x32_10", None, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32))
 _sig("rt_aabb_hit", C.c_int, _f3, _f3, _f3, _f3, C.c_float, C.c_float)
 _sig("rt_sample_stream", None, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_int)
+_sig("rt_render_hip_feature", C.c_int, _p, C.POINTER(Opts), C.c_int, _p, C.POINTER(Stats))
+_sig("rt_render_hip_feature_device", C.c_int, _p, C.POINTER(Opts), C.c_int, _p, _p, C.POINTER(Stats))
+_sig("rt_denoise_hip", C.c_int, C.c_int, C.c_int, _p, C.c_int, _p, _p, _p, _p, C.c_int, C.POINTER(Denoise), C.c_int, _p,
+     C.POINTER(C.c_double))
+_sig("rt_denoise_hip_device", C.c_int, C.c_int, C.c_int, _p, C.c_int, _p, _p, _p, _p, C.c_int, C.POINTER(Denoise), C.c_int, _p, _p,
+     C.POINTER(C.c_double))
 
 C_SYMBOLS = [
     "rt_last_error", "rt_status_string", "rt_abi_version", "rt_struct_size", "rt_device_count", "rt_has_ablations", "rt_opts_default",
@@ -261,6 +276,7 @@ C_SYMBOLS = [
     "rt_scene_set_light_sampling", "rt_scene_get_light_sampling", "rt_scene_get_lights",
     "rt_render_hip_adaptive", "rt_render_hip_adaptive_device",
     "rt_scene_set_nested_grid", "rt_scene_get_nested_grid", "rt_scene_nested_info",
+    "rt_render_hip_feature", "rt_render_hip_feature_device", "rt_denoise_hip", "rt_denoise_hip_device",
 ]
 
 
@@ -543,6 +559,17 @@ class Scene:
                                            spp.ctypes.data_as(C.c_void_p), C.byref(st)), "rt_render_hip_adaptive")
         return out, spp, st
 
+    def render_feature(self, feature: int, opts: Opts | None = None, stats: Stats | None = None) -> np.ndarray:
+        """One first-hit feature pass (rt_render_hip_feature): FEATURE_ALBEDO, FEATURE_NORMAL or FEATURE_DEPTH (t, coverage,
+        0).  (local_rows, W, 3) fp32 SUMS over the samples of `opts` (sample_count 0: the scene's spp), rows as render()."""
+        opts = opts or Opts()
+        rows = self.shard_rows(opts)
+        out = np.empty((rows, self.width, 3), dtype=np.float32)
+        st = stats if stats is not None else Stats()
+        _check(_lib.rt_render_hip_feature(self._h, C.byref(opts), int(feature), out.ctypes.data_as(C.c_void_p), C.byref(st)),
+               "rt_render_hip_feature")
+        return out
+
     def render_tiles(self, devices=None, opts: Opts | None = None, stats: Stats | None = None, n: int | None = None,
                      out: np.ndarray | None = None):
         """One frame over several GPUs of this node: row tiles dealt out to `devices` (ordinals; None =
@@ -629,6 +656,38 @@ def acc_to_rgb(acc: np.ndarray) -> np.ndarray:
     acc = np.ascontiguousarray(acc, dtype=np.int64)
     out = np.empty(acc.shape, dtype=np.float32)
     _lib.rt_acc_to_rgb(acc.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), acc.size)
+    return out
+
+
+def denoise(rgb_sum, spp, albedo_sum, normal_sum, depth_sum, feature_spp, *, spp_map=None, iterations=None, sigma_color=0.0,
+            sigma_normal=0.0, sigma_depth=0.0, device=0, timing=None):
+    """Edge-avoiding a-trous filter (rt_denoise_hip) of an (H, W, 3) frame of SUMS over `spp` samples per pixel -- or over
+    spp_map[y, x] samples (an (H, W) int32 array, as render_adaptive returns) -- guided by the three feature passes of
+    Scene.render_feature over feature_spp samples.  iterations None: the default; 0: the input bits.  A sigma of 0: its
+    default.  Returns the filtered sums, which the writers take unchanged.  timing: a list that receives the kernels' ms."""
+    rgb = np.ascontiguousarray(rgb_sum, dtype=np.float32)
+    if rgb.ndim != 3 or rgb.shape[2] != 3:
+        raise ValueError("denoise: rgb_sum must have shape (height, width, 3)")
+    planes = [np.ascontiguousarray(a, dtype=np.float32) for a in (albedo_sum, normal_sum, depth_sum)]
+    for a in planes:
+        if a.shape != rgb.shape:
+            raise ValueError("denoise: the feature sums must have the frame's shape")
+    h, w = rgb.shape[:2]
+    m = None
+    if spp_map is not None:
+        m = np.ascontiguousarray(spp_map, dtype=np.int32)
+        if m.shape != (h, w):
+            raise ValueError("denoise: spp_map must have shape (height, width)")
+    p = Denoise(iterations=DENOISE_DEFAULT_ITERATIONS if iterations is None else int(iterations), sigma_color=float(sigma_color),
+                sigma_normal=float(sigma_normal), sigma_depth=float(sigma_depth))
+    out = np.empty_like(rgb)
+    ms = C.c_double(0.0)
+    _check(_lib.rt_denoise_hip(w, h, rgb.ctypes.data_as(C.c_void_p), int(spp), m.ctypes.data_as(C.c_void_p) if m is not None else None,
+                               planes[0].ctypes.data_as(C.c_void_p), planes[1].ctypes.data_as(C.c_void_p),
+                               planes[2].ctypes.data_as(C.c_void_p), int(feature_spp), C.byref(p), int(device),
+                               out.ctypes.data_as(C.c_void_p), C.byref(ms)), "rt_denoise_hip")
+    if timing is not None:
+        timing.append(ms.value)
     return out
 
 

@@ -50,6 +50,7 @@ size_t rt_struct_size(int which) {
     case 8: return sizeof(rt_adaptive);
     case 9: return sizeof(rt_adaptive_stats);
     case 10: return sizeof(rt_nested_info);
+    case 16: return sizeof(rt_denoise);  // (11 .. 15 stay 0: the next structs of the scene / render interface)
     default: return 0;
     }
 }

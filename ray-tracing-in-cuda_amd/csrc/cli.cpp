@@ -14,6 +14,7 @@
 // split of a sample range into runs writes the same main.ppm as one run over the whole range.
 // Adaptive sampling: --adaptive T [--min-spp N] [--max-spp N] gives every 8x8 tile samples until its noise estimate is
 // within T (rt_render_hip_adaptive); each pixel is written rescaled to the scene's spp (sum * spp / n).
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -44,7 +45,8 @@ static int usage(const char *argv0) {
             "          [--seed S] [--scene-seed S] [--device N] [--chunk N] [--dump-json file] [--count] [--no-png]\n"
             "          [--acc-in sums.bin] [--acc-out sums.bin] [--spp-begin FIRST] [--rr SURVIVAL_PROBABILITY] [--nee]\n"
             "          [--nested-grid]\n"
-            "          [--gpus N] [--tile-rows R] [--adaptive THRESHOLD [--min-spp N] [--max-spp N]]\n",
+            "          [--gpus N] [--tile-rows R] [--adaptive THRESHOLD [--min-spp N] [--max-spp N]]\n"
+            "          [--denoise] [--aov PREFIX] [--feature-spp N]\n",
             argv0);
     return 2;
 }
@@ -61,6 +63,9 @@ int main(int argc, char **argv) {
     double adaptive = -1.0;  // noise target of adaptive sampling, < 0: off
     bool have_adaptive = false;
     int min_spp = 16, max_spp = 0;
+    bool denoise = false;     // filter what is written (rt_denoise_hip, default parameters)
+    std::string aov_prefix;   // write PREFIX_albedo.png, PREFIX_normal.png, PREFIX_depth.png
+    int feature_spp = 0;      // samples of the feature passes, 0: min(spp, 16)
     bool have_min = false, have_max = false;
     int w = 0, h = 0, depth = 0, spp = 0, device = 0, chunk = 0, gpus = 0, tile_rows = 0;
     unsigned long long seed = 2023;
@@ -104,6 +109,18 @@ int main(int argc, char **argv) {
         }
         else if (!strcmp(argv[i], "--min-spp")) min_spp = atoi(need("--min-spp")), have_min = true;
         else if (!strcmp(argv[i], "--max-spp")) max_spp = atoi(need("--max-spp")), have_max = true;
+        else if (!strcmp(argv[i], "--denoise")) denoise = true;
+        else if (!strcmp(argv[i], "--aov")) aov_prefix = need("--aov");
+        else if (!strcmp(argv[i], "--feature-spp")) {
+            const char *v = need("--feature-spp");
+            char *end = nullptr;
+            const long n = strtol(v, &end, 10);
+            if (end == v || *end != '\0' || n < 1 || n > (1 << 23)) {
+                fprintf(stderr, "rtmi: --feature-spp needs a sample count in 1 .. 8388608, got '%s'\n", v);
+                return 2;
+            }
+            feature_spp = (int)n;
+        }
         else if (!strcmp(argv[i], "--rtiow")) rtiow = true;
         else if (!strcmp(argv[i], "--count")) count = true;
         else if (!strcmp(argv[i], "--no-png")) no_png = true;
@@ -125,6 +142,14 @@ int main(int argc, char **argv) {
     }
     if (have_adaptive && (min_spp < 2 || max_spp < 0 || (max_spp > 0 && max_spp < min_spp))) {
         fprintf(stderr, "rtmi: --min-spp must be >= 2 and --max-spp 0 (the scene's spp) or >= --min-spp\n");
+        return 2;
+    }
+    if (feature_spp > 0 && !denoise && aov_prefix.empty()) {
+        fprintf(stderr, "rtmi: --feature-spp belongs to --denoise or --aov\n");
+        return 2;
+    }
+    if ((denoise || !aov_prefix.empty()) && (gpus > 0 || count)) {
+        fprintf(stderr, "rtmi: --denoise and --aov render their feature passes on one device: drop %s\n", gpus > 0 ? "--gpus" : "--count");
         return 2;
     }
     double t0 = now_s();
@@ -279,6 +304,51 @@ int main(int argc, char **argv) {
         fprintf(stderr, "counts: samples %llu queries %llu prim_tests %llu hits %llu misses %llu draws %llu\n",
                 (unsigned long long)st.samples, (unsigned long long)st.queries, (unsigned long long)st.prim_tests,
                 (unsigned long long)st.hits, (unsigned long long)st.misses, (unsigned long long)st.rng_draws);
+    if (denoise || !aov_prefix.empty()) {
+        // the three first-hit feature passes (same seed: the samples [0, n) of the frame's own streams), then the filter
+        const int nf = feature_spp > 0 ? feature_spp : std::min(info.samples_per_pixel, 16);
+        rt_opts fo = o;
+        fo.sample_first = 0, fo.sample_count = nf;
+        std::vector<float> feat[3];
+        double feat_ms = 0.0;
+        for (int f = 0; f < 3; ++f) {
+            feat[f].resize(img.size());
+            rt_stats fs;
+            if (rt_render_hip_feature(sc, &fo, f, feat[f].data(), &fs) != RT_OK) {
+                fprintf(stderr, "rtmi: feature pass failed: %s\n", rt_last_error());
+                return 1;
+            }
+            feat_ms += fs.kernel_ms;
+        }
+        fprintf(stderr, "features: albedo, normal, depth at %d spp, %.3f ms\n", nf, feat_ms);
+        if (denoise) {
+            std::vector<float> out(img.size());
+            double ms = 0.0;
+            if (rt_denoise_hip(info.width, info.height, img.data(), total_spp, nullptr, feat[0].data(), feat[1].data(), feat[2].data(), nf,
+                               nullptr, device, out.data(), &ms) != RT_OK) {
+                fprintf(stderr, "rtmi: denoise failed: %s\n", rt_last_error());
+                return 1;
+            }
+            img.swap(out);
+            fprintf(stderr, "denoise: %.3f ms\n", ms);
+        }
+        if (!aov_prefix.empty()) {
+            // normal: 0.5 n + 0.5; depth: mean t scaled so that the frame's largest is 1, in every channel
+            float tmax = 0.0f;
+            for (size_t p = 0; p < img.size(); p += 3) tmax = std::max(tmax, feat[2][p]);
+            for (size_t p = 0; p < img.size(); p += 3) {
+                const float t = tmax > 0.0f ? feat[2][p] / tmax * (float)nf : 0.0f;
+                for (int c = 0; c < 3; ++c) feat[1][p + c] = 0.5f * feat[1][p + c] + 0.5f * (float)nf;
+                feat[2][p] = feat[2][p + 1] = feat[2][p + 2] = t;
+            }
+            const char *names[3] = {"_albedo.png", "_normal.png", "_depth.png"};
+            for (int f = 0; f < 3; ++f)
+                if (rt_write_png((aov_prefix + names[f]).c_str(), feat[f].data(), info.width, info.height, nf, 0) != RT_OK) {
+                    fprintf(stderr, "rtmi: %s\n", rt_last_error());
+                    return 1;
+                }
+        }
+    }
     if (rt_write_ppm(out_file.c_str(), img.data(), info.width, info.height, total_spp) != RT_OK) {
         fprintf(stderr, "rtmi: %s\n", rt_last_error());
         return 1;

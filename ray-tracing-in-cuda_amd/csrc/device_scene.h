@@ -115,7 +115,8 @@ struct RenderParams {
     // room's walls); the rest is listed in the cells of the wide grid tables.  The searches without a grid test all of them.
     int32_t nr_a, nc_a, nt_a;
     int32_t off_tri_hot, off_tri_cold;
-    int32_t ns_pad;          // sphere slots incl. never-hit padding (= ns)
+    int32_t feature;         // render_feature_kernel: the first-hit feature of this launch (RT_FEATURE_*, include/rtmi.h); no other
+                             // kernel reads it (the word was a copy of ns that nothing read)
     int32_t np;              // leading slots that are always tested (big spheres), padded to a multiple of 4
     int32_t ncl;             // clusters of 8 slots after the prefix, each with a bounding box
     int32_t cluster;         // spheres per culling cluster (RT_CLUSTER)

@@ -1060,7 +1060,7 @@ bool pack_round(const Scene &s, std::vector<char> &forced, std::vector<float> &i
     const std::vector<SceneLight> lights = s.light_sampling ? scene_lights(s) : std::vector<SceneLight>();
 
     memset(&L, 0, sizeof L);
-    L.ns = L.ns_pad = S.ns(), L.np = S.np, L.ncl = S.n_clusters, L.cluster = RT_CLUSTER;
+    L.ns = S.ns(), L.feature = 0, L.np = S.np, L.ncl = S.n_clusters, L.cluster = RT_CLUSTER;
     L.nr = (int)O.rec.size(), L.nc = (int)O.cyl.size(), L.nt = (int)O.tri.size(), L.nm = (int)s.mats.size();
     L.nr_a = O.nr_a, L.nc_a = O.nc_a, L.nt_a = O.nt_a;
     L.ngr = (S.n_clusters + RT_GROUP - 1) / RT_GROUP;        // RT_GROUP consecutive clusters share an outer box

@@ -1,5 +1,5 @@
-// The body of the render kernels (render_kernel.hip): included INSIDE render_kernel and render_nee_kernel, after their
-// template arguments and a constexpr NEE.  As text rather than a force-inlined device function, so that the render_kernel
+// The body of the render kernels (render_kernel.hip): included INSIDE render_kernel, render_nee_kernel, render_nested_kernel and
+// render_feature_kernel, after their template arguments and a constexpr NEE and AOV.  As text rather than a force-inlined device function, so that the render_kernel
 // instances compile to the very instructions they did before light sampling came (a device function that takes the
 // kernel's parameters by reference changes the order of the kernel-argument loads and with it the register allocation).
 // Not a header of its own: it needs the kernel's scope (P, image, acc, queue, counters and the template arguments).
@@ -1069,6 +1069,23 @@
                     else if (kind == MK_DIELECTRIC) c_scatter2++;
                     else c_scatter3++;
                 }
+                if constexpr (AOV) {
+                    // first-hit feature (render_feature_kernel): the path ends here and adds one triple in place of radiance --
+                    // the texture value under the hit (metal: its albedo, dielectric: white), the face-turned normal, or (t, 1, 0)
+                    if (P.feature == RT_FEATURE_ALBEDO) {
+                        const float4 q1 = M[1], q2 = M[2];
+                        const bool odd = (kind == MK_LAMBERT_CHECKER || kind == MK_LIGHT_CHECKER) && checker_odd(px, py, pz);
+                        L_r = odd ? q2.x : q1.x, L_g = odd ? q2.y : q1.y, L_b = odd ? q2.z : q1.z;
+                        if (kind == MK_LAMBERT_IMAGE || kind == MK_LIGHT_IMAGE) L_r = tex_r, L_g = tex_g, L_b = tex_b;
+                        if (kind == MK_DIELECTRIC) L_r = L_g = L_b = 1.0f;
+                    } else if (P.feature == RT_FEATURE_NORMAL) {
+                        L_r = nx, L_g = ny, L_b = nz;
+                    } else {
+                        L_r = best_t, L_g = 1.0f, L_b = 0.0f;
+                    }
+                    path_done = true;
+                    kind = -1;
+                } else
                 if (kind >= MK_LIGHT_SOLID) {  // diffuse_light: emitted, never scatters (material.cuh:161-182, main.cu:48-58)
                     const float4 q1 = M[1], q2 = M[2];
                     const bool odd = kind == MK_LIGHT_CHECKER && checker_odd(px, py, pz);
@@ -1111,6 +1128,9 @@
                     bg_r = P.background[0], bg_g = P.background[1], bg_b = P.background[2];
                 }
                 L_r = beta_r * bg_r, L_g = beta_g * bg_g, L_b = beta_b * bg_b;
+                if constexpr (AOV) {  // a miss: the albedo pass keeps the background (beta = 1), normal and depth add zeros
+                    if (P.feature != RT_FEATURE_ALBEDO) L_r = L_g = L_b = 0.0f;
+                }
                 path_done = true;
                 if (COUNT) c_misses++;
             }
@@ -1416,7 +1436,7 @@
         // Russian roulette before the next query (4_0_path_tracing.py:45-46; include/rtmi.h,
         // rt_scene_set_russian_roulette): a path that does not survive keeps what it has collected (a new one:
         // nothing, so there is nothing to add); a survivor's throughput is divided by p at once
-        if (P.rr_p > 0.0f) {
+        if (!AOV && P.rr_p > 0.0f) {  // (a feature sample ends at its first query: no roulette draw)
             if (started) {
                 if (rng_next<COUNT>(rng) > P.rr_p) active = false;
                 beta_r = beta_g = beta_b = 1.0f / P.rr_p;

@@ -30,6 +30,9 @@ int blocks_per_cu(unsigned variant, bool count, size_t lds_bytes, bool ext);
 bool launch_render_nee(const RenderParams &P, const void *image, unsigned long long *acc, unsigned int *queue, size_t lds_bytes,
                        unsigned grid, hipStream_t stream, unsigned variant);
 bool variant_has_nee(unsigned variant);
+bool launch_render_feature(const RenderParams &P, const void *image, unsigned long long *acc, unsigned int *queue, size_t lds_bytes,
+                           unsigned grid, hipStream_t stream, unsigned layout);
+int blocks_per_cu_feature(unsigned layout, size_t lds_bytes);
 int blocks_per_cu_nee(unsigned variant, size_t lds_bytes);
 bool variant_has_ext(unsigned variant);
 bool variant_has_count(unsigned variant);
@@ -441,6 +444,7 @@ struct Launcher {
     unsigned long long resident;  // workgroups that fill the chip
     unsigned variant;
     bool ext, nee, count;
+    int feature;  // >= 0: a feature pass (render_feature_kernel of layout `variant`)
 
     int enqueue(unsigned long long *acc, unsigned int *d_queue, int first, int n, int n_list, const ChunkPlan &pl) const {
         RenderParams Q = P;
@@ -468,6 +472,14 @@ struct Launcher {
         // persistent launch: enough workgroups to fill the chip, never more than the work needs
         const unsigned long long need_blocks = (items + 3) / 4;
         const unsigned long long grid = need_blocks < resident ? (need_blocks ? need_blocks : 1) : resident;
+        if (feature >= 0) {
+            Q.feature = feature;
+            if (!launch_render_feature(Q, ent->d_image, acc, d_queue, lds_bytes, (unsigned)grid, stream, variant)) {
+                set_error("layout %u has no feature kernel", variant);
+                return RT_ERR_LIMIT;
+            }
+            return RT_OK;
+        }
         if (nee ? !launch_render_nee(Q, ent->d_image, acc, d_queue, lds_bytes, (unsigned)grid, stream, variant)
                 : !launch_render(Q, ent->d_image, acc, d_queue, d_cnt, lds_bytes, (unsigned)grid, stream, variant, ext)) {
             set_error("kernel variant %u has no %s build", variant, count ? "counting" : (ext ? "triangle / texture" : "such"));
@@ -599,7 +611,7 @@ static int read_counters(const DevCounters *d_cnt, const RenderParams &P, unsign
 }
 
 static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, void *stream_v, rt_stats *stats,
-                       long long *h_acc, bool count, const AdaptiveRun *ad = nullptr) {
+                       long long *h_acc, bool count, const AdaptiveRun *ad = nullptr, int feature = -1) {
     if (!sc || (!d_rgb_sum && !h_acc)) {
         set_error("rt_render_hip_device: null scene or output pointer");
         return RT_ERR_ARG;
@@ -633,7 +645,14 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     }
 
     unsigned variant = o ? o->variant : 0;
-    if (!variant_exists(variant)) {
+    if (feature >= 0) {
+        // a feature pass names a LAYOUT: the scene's own (0, or 2 / 6 for compact tables), or one a feature kernel is built for
+        const unsigned ok[] = {0u, 2u, 6u, 16u, 24u, 36u, 44u, 52u};
+        if (std::find(std::begin(ok), std::end(ok), variant) == std::end(ok)) {
+            set_error("rt_render_hip_feature: layout %u (0, 16, 24, 36, 44 or 52; 2 and 6 run the linear scan)", variant);
+            return RT_ERR_ARG;
+        }
+    } else if (!variant_exists(variant)) {
         set_error("unknown kernel variant %u%s", variant, has_ablations() ? "" : " (this library was built without the measurement variants: make ABLATIONS=1)");
         return RT_ERR_ARG;
     }
@@ -693,8 +712,8 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     RenderParams P = cache.layout;
     for (int i = 0; i < 3; ++i) P.background[i] = s.background[i];
     P.flags = s.flags;
-    P.rr_p = s.rr_p;
-    P.width = s.width, P.height = s.height, P.max_depth = s.max_depth;
+    P.rr_p = feature >= 0 ? 0.0f : s.rr_p;  // (a feature sample ends at its first query: no roulette, any max_depth)
+    P.width = s.width, P.height = s.height, P.max_depth = feature >= 0 ? 1 : s.max_depth;
     P.inv_wm1 = 1.0f / (float)(s.width - 1), P.inv_hm1 = 1.0f / (float)(s.height - 1);  // IEEE fp32 divisions, as the checker's
     P.tile_rows = sh.tile_rows, P.tile_first = sh.tile_first, P.tile_stride = sh.tile_stride;
     P.num_tiles = sh.num_tiles, P.local_rows = sh.local_rows;
@@ -713,8 +732,7 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     // which has no size limit.  The packer has chosen the table format (device_scene.h): COMPACT for sphere-only scenes whose
     // tables fit that LDS budget, WIDE for every other scene.
     const size_t acc_lds = kAccLds;
-    auto hot_bytes_of = [&](unsigned v) {  // (each candidate search stages the part of the hot tables it reads)
-        const int mode = variant_cull_mode(v);
+    auto hot_bytes_of = [&](int mode) {  // (each candidate search stages the part of the hot tables it reads)
         if (mode == 5 || mode == 6 || mode == 7 || mode == 8) return (size_t)P.hot_vec4_grid * 16;
         return (size_t)((mode == 3 ? P.hot_vec4_tables : P.hot_vec4) - (P.off_box - P.off_grid)) * 16;  // (without the grid tables)
     };
@@ -723,7 +741,16 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     auto pick = [&](bool counting) -> unsigned { return pick_variant(P, counting, global_threshold); };
     if (variant == 0) variant = pick(count);
     // light sampling on and something to sample: the layout's light-sampling kernel (built with triangles and textures)
-    const bool nee = P.nl > 0;
+    const bool nee = P.nl > 0 && feature < 0;
+    if (feature >= 0 && (variant == 2 || variant == 6)) {
+        // compact tables list spheres for the sphere-only kernels; a feature pass is one query per sample and scans the list
+        // instead -- staged in LDS while that fits the table budget, from global memory beyond (no size limit)
+        if (P.grid_wide) {
+            set_error("layout %u reads the compact grid tables, which this scene does not have: use 0", variant);
+            return RT_ERR_LIMIT;
+        }
+        variant = (size_t)(P.hot_vec4 - (P.off_box - P.off_grid)) * 16 <= global_threshold ? 16u : 24u;
+    }
     if (nee && P.grid_wide == 2) {
         set_error("this scene has the nested grid and light sampling on, which no kernel combines: switch one of them off");
         return RT_ERR_ARG;
@@ -737,7 +764,8 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     // variant 0 would run (reported in stats->kernel_variant / cull_mode)
     if (count && !variant_has_count(variant)) variant = (variant == 2) ? 6u : pick(true);
     if (count && variant == 2) variant = 6;
-    const int mode = variant_cull_mode(variant);
+    // (the feature layouts exist in every build; variant 24 as a render variant only with RTMI_ABLATIONS)
+    const int mode = feature >= 0 ? (variant == 52 ? 8 : (variant == 36 || variant == 44) ? 7 : 0) : variant_cull_mode(variant);
     // nested cells are walked by variant 52 alone, and variant 52 walks nothing else; the linear scans read no grid
     if (mode == 8 && P.grid_wide != 2) {
         set_error("kernel variant %u walks tables with nested cells, which this scene does not have (rt_scene_set_nested_grid, and a "
@@ -763,7 +791,8 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
         set_error("kernel variant 2 walks a grid that is one cell high, which this scene does not have");
         return RT_ERR_LIMIT;
     }
-    if (ext && !variant_has_ext(variant)) {
+    if (feature >= 0) ext = true;  // (the feature kernels are general builds)
+    if (feature < 0 && ext && !variant_has_ext(variant)) {
         set_error("kernel variant %u has no build with triangles / image textures (variants 0, 36, 44 and the linear scans 16 / 24 have)", variant);
         return RT_ERR_LIMIT;
     }
@@ -773,7 +802,7 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     }
     if (force_ext && variant_has_ext(variant) && P.grid_wide) ext = true;
     if (nee) ext = true;
-    const size_t hot_bytes = hot_bytes_of(variant);
+    const size_t hot_bytes = hot_bytes_of(mode);
     const bool tables_global = (variant & 8u) != 0 || mode == 8;
     const size_t lds_bytes = (tables_global ? 0 : hot_bytes) + acc_lds;
     if (knob_set("RTMI_DEBUG_LAYOUT")) {
@@ -815,7 +844,9 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
         ent->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     }
     const unsigned long long resident =
-        (unsigned long long)ent->num_cus * (nee ? blocks_per_cu_nee(variant, lds_bytes) : blocks_per_cu(variant, count, lds_bytes, ext));
+        (unsigned long long)ent->num_cus * (feature >= 0 ? blocks_per_cu_feature(variant, lds_bytes)
+                                            : nee  ? blocks_per_cu_nee(variant, lds_bytes)
+                                                   : blocks_per_cu(variant, count, lds_bytes, ext));
 
     float *d_out = (float *)d_rgb_sum;
     DevCounters *d_cnt = nullptr;
@@ -836,13 +867,13 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     const size_t queue_off = (plane * sizeof(unsigned long long) + 255) & ~(size_t)255;
     const long long frame_tiles = (long long)P.tiles_x * P.bands;
     const size_t need = queue_off + (ad ? (((size_t)(RT_TILE_LIST_AT + frame_tiles) * 4 + 255) & ~(size_t)255) : 256);
-    const Launcher launch{P, sh, ent, d_cnt, stream, lds_bytes, resident, variant, ext, nee, count};
+    const Launcher launch{P, sh, ent, d_cnt, stream, lds_bytes, resident, variant, ext, nee, count, feature};
 
     int launches = 0;
     if (ad) {
         rc = run_adaptive(launch, *ad, s, queue_off, need, d_out, o ? o->spp_chunk : 0, launches);
         if (rc) return rc;
-    } else if (s.max_depth <= 0 && !h_acc) {
+    } else if (s.max_depth <= 0 && !h_acc && feature < 0) {
         // while (depth > 0) never runs: every sample is black (main.cpp:20,42)
         HIP_TRY(hipMemsetAsync(d_out, 0, plane * sizeof(float), stream));
     } else {
@@ -852,7 +883,7 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
         // progressive rendering: continue from the caller's exact sums
         if (h_acc) HIP_TRY(hipMemcpyAsync(ent->d_acc, h_acc, plane * sizeof(long long), hipMemcpyHostToDevice, stream));
         unsigned int *d_queue = reinterpret_cast<unsigned int *>(reinterpret_cast<char *>(ent->d_acc) + queue_off);
-        if (s.max_depth > 0) {
+        if (s.max_depth > 0 || feature >= 0) {
             rc = launch.enqueue(ent->d_acc, d_queue, sample_first, sample_count, 0, plan);
             if (rc) return rc;
             ++launches;
@@ -869,7 +900,8 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     HIP_TRY(hipGetLastError());
 
     if (stats) {
-        stats->kernel_variant = (int32_t)(variant | (nee ? 256u : 0u));  // what variant 0 (or a counting call) resolved to (| 256: light sampling)
+        // what variant 0 (or a counting call) resolved to (| 256: light sampling, | 512: a feature pass)
+        stats->kernel_variant = (int32_t)(variant | (nee ? 256u : 0u) | (feature >= 0 ? 512u : 0u));
         HIP_TRY(hipEventRecord(ev2, stream));
         lock.unlock();
         HIP_TRY(hipEventSynchronize(ev2));
@@ -889,7 +921,7 @@ int rt_render_hip_device(const rt_scene *s, const rt_opts *o, void *d_rgb_sum, v
 }
 
 static int render_host_buffer(const rt_scene *sc, const rt_opts *o, float *rgb_sum, rt_stats *stats, bool count,
-                              long long *h_acc = nullptr, AdaptiveRun *ad = nullptr, int32_t *spp_map = nullptr) {
+                              long long *h_acc = nullptr, AdaptiveRun *ad = nullptr, int32_t *spp_map = nullptr, int feature = -1) {
     if (!sc) {
         set_error("null scene");
         return RT_ERR_ARG;
@@ -926,7 +958,7 @@ static int render_host_buffer(const rt_scene *sc, const rt_opts *o, float *rgb_s
             ad->d_spp_map = ent->d_spp;
         }
     }
-    rc = bytes ? render_impl(sc, o, d_out, nullptr, stats ? stats : &local, h_acc, count, ad) : RT_OK;
+    rc = bytes ? render_impl(sc, o, d_out, nullptr, stats ? stats : &local, h_acc, count, ad, feature) : RT_OK;
     if (rc == RT_OK && rgb_sum && bytes) {
         hipError_t e = hipMemcpy(rgb_sum, d_out, bytes, hipMemcpyDeviceToHost);
         if (e == hipSuccess && ad) e = hipMemcpy(spp_map, ad->d_spp_map, bytes / 3 / sizeof(float) * sizeof(int32_t), hipMemcpyDeviceToHost);
@@ -1019,6 +1051,31 @@ int rt_render_hip_adaptive(const rt_scene *s, const rt_opts *o, const rt_adaptiv
     rc = render_host_buffer(s, &run, rgb_sum, &stats, false, nullptr, &ad, spp_map);
     st->kernel_ms = stats.kernel_ms;
     return rc;
+}
+
+// the arguments of the feature entry points, checked before any device access
+static int feature_args(const rt_scene *sc, int feature, const void *sum) {
+    if (!sc || !sum) {
+        set_error("rt_render_hip_feature: null scene or output pointer");
+        return RT_ERR_ARG;
+    }
+    if (feature < RT_FEATURE_ALBEDO || feature > RT_FEATURE_DEPTH) {
+        set_error("rt_render_hip_feature: feature %d (0 albedo, 1 normal, 2 depth)", feature);
+        return RT_ERR_ARG;
+    }
+    return RT_OK;
+}
+
+int rt_render_hip_feature(const rt_scene *s, const rt_opts *o, int feature, float *sum, rt_stats *stats) {
+    int rc = feature_args(s, feature, sum);
+    if (rc) return rc;
+    return render_host_buffer(s, o, sum, stats, false, nullptr, nullptr, nullptr, feature);
+}
+
+int rt_render_hip_feature_device(const rt_scene *s, const rt_opts *o, int feature, void *d_sum, void *stream, rt_stats *stats) {
+    int rc = feature_args(s, feature, d_sum);
+    if (rc) return rc;
+    return render_impl(s, o, d_sum, stream, stats, nullptr, false, nullptr, feature);
 }
 
 int rt_render_hip_accumulate(const rt_scene *s, const rt_opts *o, int64_t *acc, float *rgb_sum, rt_stats *stats) {

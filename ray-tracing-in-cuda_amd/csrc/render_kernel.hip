@@ -265,7 +265,7 @@ __global__ __launch_bounds__(256, RT_WAVES_PER_SIMD) void render_kernel(const Re
                                                      unsigned long long *__restrict__ acc,
                                                      unsigned int *__restrict__ queue,
                                                      DevCounters *__restrict__ counters) {
-    constexpr bool NEE = false;
+    constexpr bool NEE = false, AOV = false;
 #include "render_body.h"
 }
 
@@ -276,7 +276,7 @@ __global__ __launch_bounds__(256, RT_NEE_WAVES_PER_SIMD) void render_nee_kernel(
                                                          unsigned long long *__restrict__ acc,
                                                          unsigned int *__restrict__ queue,
                                                          DevCounters *__restrict__ counters) {
-    constexpr bool COUNT = false, POOL = true, EXT = true, SPH = false, NEE = true;
+    constexpr bool COUNT = false, POOL = true, EXT = true, SPH = false, NEE = true, AOV = false;
 #include "render_body.h"
 }
 
@@ -288,8 +288,21 @@ __global__ __launch_bounds__(256, RT_WAVES_PER_SIMD) void render_nested_kernel(c
                                                             unsigned long long *__restrict__ acc,
                                                             unsigned int *__restrict__ queue,
                                                             DevCounters *__restrict__ counters) {
-    constexpr bool POOL = true, SCALAR = true, SPH = false, NEE = false;
+    constexpr bool POOL = true, SCALAR = true, SPH = false, NEE = false, AOV = false;
     constexpr int CULL = 8;
+#include "render_body.h"
+}
+
+// first-hit feature passes (rt_render_hip_feature): a sample runs as in render_kernel up to its first closest-hit query -- same
+// stream, jitter, lens draw, camera ray and walk -- and there adds the feature P.feature selects (a launch value) in place of
+// radiance.  One query per sample, so the general builds (triangles, image textures) serve every scene: the linear scan (CULL 0),
+// the wide grid walk (7) and the nested walk (8), tables in LDS or in global memory (SCALAR).
+template <bool SCALAR, int CULL>
+__global__ __launch_bounds__(256, RT_WAVES_PER_SIMD) void render_feature_kernel(const RenderParams P, const float4 *__restrict__ image,
+                                                             unsigned long long *__restrict__ acc,
+                                                             unsigned int *__restrict__ queue,
+                                                             DevCounters *__restrict__ counters) {
+    constexpr bool COUNT = false, POOL = true, EXT = true, SPH = false, NEE = false, AOV = true;
 #include "render_body.h"
 }
 
@@ -313,6 +326,10 @@ template __global__ void render_nee_kernel<RT_ISA_ONLY_NEE>(const RenderParams, 
 // ... and one nested-grid instance (RT_ISA_ONLY_NESTED = COUNT, EXT)
 template __global__ void render_nested_kernel<RT_ISA_ONLY_NESTED>(const RenderParams, const float4 *__restrict__, unsigned long long *__restrict__,
                                                                   unsigned int *__restrict__, DevCounters *__restrict__);
+#elif defined(RT_ISA_ONLY_AOV)
+// ... and one feature instance (RT_ISA_ONLY_AOV = SCALAR, CULL)
+template __global__ void render_feature_kernel<RT_ISA_ONLY_AOV>(const RenderParams, const float4 *__restrict__, unsigned long long *__restrict__,
+                                                                unsigned int *__restrict__, DevCounters *__restrict__);
 #else
 // ---------------------------------------------------------------- launchers used by render_host.hip
 // X(variant id, POOL, SCALAR, CULL, SPH).  The host resolves variant 0 to one of the five PRODUCT instances:
@@ -366,6 +383,14 @@ template __global__ void render_nested_kernel<RT_ISA_ONLY_NESTED>(const RenderPa
     X(36, false, 7)     \
     X(44, true, 7)      \
     X(16, false, 0)
+// feature kernels (render_feature_kernel, every build): X(layout, SCALAR, CULL) -- the layouts of variant 0's general scenes, the
+// nested walk, and the linear scan over global memory (24) for compact-table scenes whose scan tables do not fit LDS
+#define RT_FEATURE_TABLE(X) \
+    X(36, false, 7)         \
+    X(44, true, 7)          \
+    X(16, false, 0)         \
+    X(24, true, 0)          \
+    X(52, true, 8)
 #define RT_VARIANT_TABLE(X) RT_PRODUCT_TABLE(X) RT_ABLATION_TABLE(X)
 #define RT_EXT_TABLE(X) RT_PRODUCT_EXT_TABLE(X) RT_ABLATION_EXT_TABLE(X)
 
@@ -436,6 +461,31 @@ bool launch_render_nee(const RenderParams &P, const void *image, unsigned long l
     RT_NEE_TABLE(RT_LAUNCH_NEE)
 #undef RT_LAUNCH_NEE
     return false;
+}
+
+// launches the feature kernel of a layout (RT_FEATURE_TABLE); false: no such build
+bool launch_render_feature(const RenderParams &P, const void *image, unsigned long long *acc, unsigned int *queue, size_t lds_bytes,
+                           unsigned grid, hipStream_t stream, unsigned layout) {
+    const float4 *img = (const float4 *)image;
+    DevCounters *none = nullptr;
+#define RT_LAUNCH_AOV(V, SCALAR, CULL)                                                                                        \
+    if (layout == V) {                                                                                                         \
+        hipLaunchKernelGGL((render_feature_kernel<SCALAR, CULL>), dim3(grid), dim3(256), lds_bytes, stream, P, img, acc, queue, none); \
+        return true;                                                                                                           \
+    }
+    RT_FEATURE_TABLE(RT_LAUNCH_AOV)
+#undef RT_LAUNCH_AOV
+    return false;
+}
+
+int blocks_per_cu_feature(unsigned layout, size_t lds_bytes) {
+    int n = 0;
+    hipError_t e = hipErrorInvalidValue;
+#define RT_OCC_AOV(V, SCALAR, CULL) \
+    if (layout == V) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, render_feature_kernel<SCALAR, CULL>, 256, lds_bytes);
+    RT_FEATURE_TABLE(RT_OCC_AOV)
+#undef RT_OCC_AOV
+    return (e == hipSuccess && n > 0) ? n : 4;
 }
 
 bool variant_has_nee(unsigned variant) {
@@ -550,9 +600,12 @@ int set_max_dynamic_lds(size_t bytes) {
 #define RT_ATTR_NEE(V, SCALAR, CULL) RT_ATTR1((render_nee_kernel<SCALAR, CULL>))
     RT_NEE_TABLE(RT_ATTR_NEE)
 #undef RT_ATTR_NEE
+#define RT_ATTR_AOV(V, SCALAR, CULL) RT_ATTR1((render_feature_kernel<SCALAR, CULL>))
+    RT_FEATURE_TABLE(RT_ATTR_AOV)
+#undef RT_ATTR_AOV
 #undef RT_ATTR1
     return 0;
 }
-#endif  // RT_ISA_ONLY, RT_ISA_ONLY_NEE
+#endif  // RT_ISA_ONLY, RT_ISA_ONLY_NEE, RT_ISA_ONLY_NESTED, RT_ISA_ONLY_AOV
 
 }  // namespace rtmi
