@@ -199,8 +199,44 @@ typedef struct rt_light {
     float emission[3];   /* emission (a checker texture: its even colour)      */
     float emission_odd[3]; /* a checker texture's odd colour (else = emission) */
 } rt_light;
-/* the emitters light sampling samples, in list order (whether or not it is on) -> count, or -rt_status */
+/* the emitters light sampling samples, in list order (whether or not it is on) -> count, or -rt_status.  An environment
+ * with something to sample comes last: prim = -1, shape = RT_LIGHT_ENVIRONMENT, area = 4 pi, emission = its mean radiance. */
 int rt_scene_get_lights(const rt_scene *s, rt_light *out, int cap);
+#define RT_LIGHT_ENVIRONMENT 100 /* rt_light.shape of the environment (outside rt_prim_type's values) */
+
+/* ---- environment map (image-based lighting) -------------------------------
+ * rows x cols fp32 RGB texels (finite, >= 0) in lat-long layout: row 0 is the zenith (+y), rows go down to -y, columns go
+ * round in azimuth.  For a unit direction d
+ *     v = acos(d.y) / pi,                          row = min(int(v rows), rows - 1)
+ *     u = frac((atan2(-d.z, d.x) + pi) / 2 pi + rotate_deg / 360),   col = min(int(u cols), cols - 1)
+ * (the sphere's u, v of object.cuh:87-93; every step one fp32 operation, acos / atan2 the fixed sequences of the hit
+ * record's texture coordinates), and the radiance is scale x texel[row][col] (nearest texel, as image textures).  With an
+ * environment set a ray that misses everything returns throughput x radiance(d) in place of the background and the sky
+ * gradient, with no extra random draw: a map of one colour c at scale 1 renders the bytes of background = c.
+ * With light sampling on (rt_scene_set_light_sampling) the environment is one more sampled emitter: directions are drawn in
+ * proportion to luminance x solid angle, piecewise constant over texels (a marginal CDF over rows and a conditional CDF per
+ * row, built in fp64, stored as fp32; uniform in solid angle inside the texel; pdf = pmf(texel) / solid angle of the row's
+ * texels; zero-luminance texels are never drawn).  Its selection weight is r^2 x scale x sum(luminance x solid angle), r the
+ * radius of the primitives' bounding sphere.  Its shadow ray has no far end; a BSDF ray from a light-sampled vertex that
+ * escapes is weighted by the power heuristic.  Scenes with an environment get the wide tables and render through kernels of
+ * their own (rt_opts.variant 0, 16, 36 or 44; rt_stats.kernel_variant reports layout | 1024, | 256 with light samples); other
+ * variants, rt_render_hip_count and scenes whose tables have nested cells fail with RT_ERR_ARG.
+ * rows = 0 clears the environment.  RT_ERR_ARG for bad arguments, RT_ERR_SCENE for negative or non-finite texels,
+ * RT_ERR_LIMIT beyond 2^25 texels.  JSON: top-level "environment": {"file": path, "scale": s, "rotate": deg} or
+ * {"rows": r, "cols": c, "data": [r x c x 3 numbers], ...}. */
+int rt_scene_set_environment(rt_scene *s, int rows, int cols, const float *rgb, float scale, float rotate_deg);
+/* the same from a file: Radiance .hdr (RGBE: flat or new-style run-length scanlines, "-Y H +X W"), PFM ("PF", either
+ * endianness), or an 8-bit PNG / PPM as an LDR map (byte / 255).  RT_ERR_IO / RT_ERR_SCENE for unreadable or malformed files. */
+int rt_scene_set_environment_file(rt_scene *s, const char *path, float scale, float rotate_deg);
+/* size (rows = cols = 0: none), scale, rotation and, if rgb != NULL, the rows x cols x 3 texels; any pointer may be NULL */
+int rt_scene_get_environment(const rt_scene *s, int *rows, int *cols, float *scale, float *rotate_deg, float *rgb,
+                             size_t cap_floats);
+/* Host evaluations of the device functions (no GPU needed).  eval: radiance and sampling density (per steradian) of
+ * direction dir, which is normalised in fp64 and rounded to fp32 first.  sample: the direction the sampler draws from
+ * (u1, u2) in [0, 1)^2 -- u1: row, then cos(theta) within its band; u2: column, then azimuth within the texel -- with the
+ * radiance and density eval gives that direction (pdf 0 when the map has nothing to sample). */
+int rt_environment_eval(const rt_scene *s, const float dir[3], float rgb[3], float *pdf);
+int rt_environment_sample(const rt_scene *s, float u1, float u2, float dir[3], float rgb[3], float *pdf);
 /* camera(lookfrom, lookat, vup, vfov, aspect, aperture, focus_dist) camera.cuh:9-15;
  * aspect <= 0 -> width/height, focus_dist <= 0 -> |lookfrom-lookat| (parser.hpp:122-124) */
 int rt_scene_set_camera(rt_scene *s, const float lookfrom[3], const float lookat[3],
@@ -286,7 +322,8 @@ typedef struct rt_table_info {
     int32_t off_sph_cold, off_rect_cold, off_cyl_cold, off_tri_cold; /* cold records: {.., material, list index, kind} */
     int32_t off_rect_hot, off_cyl_hot, off_tri_hot;
     int32_t hot_bytes_grid;    /* what a grid-walk kernel stages into LDS */
-    int32_t kernel_variant;    /* what rt_opts.variant = 0 renders this scene with (2, 6, 16, 36, 44 or 52) */
+    int32_t kernel_variant;    /* what rt_opts.variant = 0 renders this scene with (2, 6, 16, 36, 44 or 52; | 256 light sampling,
+                                  | 1024 an environment map) */
 } rt_table_info;
 int rt_scene_table_info(const rt_scene *s, rt_table_info *out);
 /* The nested cells of the scene's tables (rt_scene_set_nested_grid); all zero while the tables are flat.  A nested cell's header
@@ -572,6 +609,8 @@ typedef enum rt_feature {
  * grid walk) or 52 (nested walk); a scene with compact tables (variants 2, 6) runs the linear scan, in LDS while it fits and
  * from global memory beyond (no size limit); every layout gives the same bytes.  Other variants fail with RT_ERR_ARG.  Light
  * sampling and Russian roulette do not bear on a feature.  rt_stats.kernel_variant reports the layout | 512.
+ * A scene with an environment map: the albedo pass gives the map's radiance on a miss (what the miss gives a fresh path), normal
+ * and depth give zeros; layouts 0, 16, 36 and 44 (the layout | 512 | 1024).
  * RT_ERR_ARG for a null pointer or a feature outside 0..2, checked before any device access; stats may be NULL. */
 int rt_render_hip_feature(const rt_scene *s, const rt_opts *o, int feature, float *sum, rt_stats *stats);
 /* the same into a DEVICE buffer on `stream` (hipStream_t as void*), asynchronous when stats == NULL (rt_render_hip_device) */

@@ -245,6 +245,18 @@ public:
     // nested grid: overfull cells of the candidate grid get a sub-grid of their own (rt_scene_set_nested_grid)
     void set_nested_grid(bool on) { check(rt_scene_set_nested_grid(s_, on ? 1 : 0), "set_nested_grid"); }
     bool nested_grid() const { return rt_scene_get_nested_grid(s_) > 0; }
+    // environment map: rows x cols x 3 floats in lat-long layout, or a .hdr / .pfm / .png / .ppm file (rt_scene_set_environment)
+    void set_environment(int rows, int cols, const float *rgb, float scale = 1.0f, float rotate_deg = 0.0f) {
+        check(rt_scene_set_environment(s_, rows, cols, rgb, scale, rotate_deg), "set_environment");
+    }
+    void set_environment(const std::string &path, float scale = 1.0f, float rotate_deg = 0.0f) {
+        check(rt_scene_set_environment_file(s_, path.c_str(), scale, rotate_deg), "set_environment");
+    }
+    void clear_environment() { check(rt_scene_set_environment(s_, 0, 0, nullptr, 1.0f, 0.0f), "clear_environment"); }
+    bool has_environment() const {
+        int rows = 0;
+        return rt_scene_get_environment(s_, &rows, nullptr, nullptr, nullptr, nullptr, 0) == RT_OK && rows > 0;
+    }
     // progressive rendering: adds samples [first, first + count) to the caller's exact pixel sums
     // (resized and zeroed when empty) and returns the framebuffer of the updated sums
     std::vector<float> accumulate(std::vector<int64_t> &acc, int first, int count, const rt_opts *opts = nullptr,

@@ -50,6 +50,7 @@ MATERIAL_DTYPE = np.dtype(
     [("type", "<i4"), ("texture", "<i4"), ("albedo", "<f4", (3,)), ("fuzz", "<f4"), ("ir", "<f4")]
 )
 TEXTURE_DTYPE = np.dtype([("type", "<i4"), ("c0", "<f4", (3,)), ("c1", "<f4", (3,))])
+LIGHT_ENVIRONMENT = 100  # rt_light.shape of the environment map (RT_LIGHT_ENVIRONMENT)
 LIGHT_DTYPE = np.dtype(
     [("prim", "<i4"), ("shape", "<i4"), ("probability", "<f4"), ("area", "<f4"), ("emission", "<f4", (3,)),
      ("emission_odd", "<f4", (3,))]
@@ -233,6 +234,12 @@ _sig("rt_scene_set_russian_roulette", C.c_int, _p, C.c_float)
 _sig("rt_scene_set_light_sampling", C.c_int, _p, C.c_int)
 _sig("rt_scene_get_light_sampling", C.c_int, _p)
 _sig("rt_scene_get_lights", C.c_int, _p, _p, C.c_int)
+_sig("rt_scene_set_environment", C.c_int, _p, C.c_int, C.c_int, _p, C.c_float, C.c_float)
+_sig("rt_scene_set_environment_file", C.c_int, _p, C.c_char_p, C.c_float, C.c_float)
+_sig("rt_scene_get_environment", C.c_int, _p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float), _p,
+     C.c_size_t)
+_sig("rt_environment_eval", C.c_int, _p, _f3, _f3, C.POINTER(C.c_float))
+_sig("rt_environment_sample", C.c_int, _p, C.c_float, C.c_float, _f3, _f3, C.POINTER(C.c_float))
 _sig("rt_scene_set_nested_grid", C.c_int, _p, C.c_int)
 _sig("rt_scene_get_nested_grid", C.c_int, _p)
 _sig("rt_scene_nested_info", C.c_int, _p, C.POINTER(NestedInfo))
@@ -276,6 +283,8 @@ C_SYMBOLS = [
     "rt_scene_set_light_sampling", "rt_scene_get_light_sampling", "rt_scene_get_lights",
     "rt_render_hip_adaptive", "rt_render_hip_adaptive_device",
     "rt_scene_set_nested_grid", "rt_scene_get_nested_grid", "rt_scene_nested_info",
+    "rt_scene_set_environment", "rt_scene_set_environment_file", "rt_scene_get_environment", "rt_environment_eval",
+    "rt_environment_sample",
     "rt_render_hip_feature", "rt_render_hip_feature_device", "rt_denoise_hip", "rt_denoise_hip_device",
 ]
 
@@ -354,6 +363,44 @@ class Scene:
     @property
     def light_sampling(self) -> bool:
         return _check_id(_lib.rt_scene_get_light_sampling(self._h), "get_light_sampling") != 0
+
+    def set_environment(self, rgb=None, scale: float = 1.0, rotate: float = 0.0, file: str = None):
+        """Environment map (include/rtmi.h, rt_scene_set_environment): ``rgb`` is a rows x cols x 3 float array in lat-long
+        layout (row 0 = +y), or ``file`` names a .hdr / .pfm / .png / .ppm; neither clears the environment."""
+        if file is not None:
+            _check(_lib.rt_scene_set_environment_file(self._h, os.fsencode(file), float(scale), float(rotate)), "set_environment")
+            return
+        if rgb is None:
+            _check(_lib.rt_scene_set_environment(self._h, 0, 0, None, 1.0, 0.0), "set_environment")
+            return
+        a = np.ascontiguousarray(rgb, dtype=np.float32)
+        if a.ndim != 3 or a.shape[2] != 3:
+            raise ValueError("environment: a rows x cols x 3 array")
+        _check(_lib.rt_scene_set_environment(self._h, a.shape[0], a.shape[1], a.ctypes.data_as(C.c_void_p), float(scale), float(rotate)),
+               "set_environment")
+
+    @property
+    def environment(self):
+        """(texels as a rows x cols x 3 float32 array, scale, rotate), or None."""
+        rows, cols, scale, rot = C.c_int(), C.c_int(), C.c_float(), C.c_float()
+        _check(_lib.rt_scene_get_environment(self._h, C.byref(rows), C.byref(cols), C.byref(scale), C.byref(rot), None, 0), "get_environment")
+        if rows.value == 0:
+            return None
+        a = np.empty((rows.value, cols.value, 3), np.float32)
+        _check(_lib.rt_scene_get_environment(self._h, None, None, None, None, a.ctypes.data_as(C.c_void_p), a.size), "get_environment")
+        return a, scale.value, rot.value
+
+    def environment_eval(self, direction):
+        """Host evaluation of the device lookup: (rgb, pdf) of a direction."""
+        rgb, pdf = (C.c_float * 3)(), C.c_float()
+        _check(_lib.rt_environment_eval(self._h, _v3(direction), rgb, C.byref(pdf)), "environment_eval")
+        return np.array(rgb[:], np.float32), np.float32(pdf.value)
+
+    def environment_sample(self, u1: float, u2: float):
+        """Host evaluation of the device sampler: (direction, rgb, pdf) for two uniforms in [0, 1)."""
+        d, rgb, pdf = (C.c_float * 3)(), (C.c_float * 3)(), C.c_float()
+        _check(_lib.rt_environment_sample(self._h, float(u1), float(u2), d, rgb, C.byref(pdf)), "environment_sample")
+        return np.array(d[:], np.float32), np.array(rgb[:], np.float32), np.float32(pdf.value)
 
     def set_nested_grid(self, on: bool = True):
         """A second grid level for clustered geometry (include/rtmi.h, rt_scene_set_nested_grid); False switches it off."""

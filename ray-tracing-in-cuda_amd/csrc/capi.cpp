@@ -9,6 +9,7 @@
 #include <string>
 
 #include "philox.h"
+#include "rt_env.h"
 #include "scene.hpp"
 
 using namespace rtmi;
@@ -733,6 +734,87 @@ int rt_aabb_hit(const float bmin[3], const float bmax[3], const float orig[3], c
         if (t_max <= t_min) return 0;
     }
     return 1;
+}
+
+// ---- environment map: the scene interface and the host evaluations of the device functions of rt_env.h (no GPU needed)
+static EnvView env_host_view(const Scene &s) {
+    const SceneEnvironment &e = *s.env;
+    return EnvView{e.rgb.data(), e.marg.data(), e.cond.data(), e.band.data(), e.ct.data(), e.rows, e.cols, s.env_scale, env_uoff(s.env_rotate)};
+}
+
+int rt_scene_set_environment(rt_scene *s, int rows, int cols, const float *rgb, float scale, float rotate_deg) {
+    if (!s) {
+        set_error("rt_scene_set_environment: null scene");
+        return RT_ERR_ARG;
+    }
+    return set_environment(s->s, rows, cols, rgb, scale, rotate_deg, "");
+}
+
+int rt_scene_set_environment_file(rt_scene *s, const char *path, float scale, float rotate_deg) {
+    if (!s || !path) {
+        set_error("rt_scene_set_environment_file: null scene or path");
+        return RT_ERR_ARG;
+    }
+    return set_environment_file(s->s, path, scale, rotate_deg);
+}
+
+int rt_scene_get_environment(const rt_scene *s, int *rows, int *cols, float *scale, float *rotate_deg, float *rgb, size_t cap_floats) {
+    if (!s) {
+        set_error("rt_scene_get_environment: null scene");
+        return RT_ERR_ARG;
+    }
+    const SceneEnvironment *e = s->s.env.get();
+    if (rows) *rows = e ? e->rows : 0;
+    if (cols) *cols = e ? e->cols : 0;
+    if (scale) *scale = s->s.env_scale;
+    if (rotate_deg) *rotate_deg = s->s.env_rotate;
+    if (e && rgb) {
+        if (cap_floats < e->rgb.size()) {
+            set_error("rt_scene_get_environment: buffer of %zu floats, the map needs %zu", cap_floats, e->rgb.size());
+            return RT_ERR_ARG;
+        }
+        memcpy(rgb, e->rgb.data(), e->rgb.size() * sizeof(float));
+    }
+    return RT_OK;
+}
+
+int rt_environment_eval(const rt_scene *s, const float dir[3], float rgb[3], float *pdf) {
+    if (!s || !dir || !s->s.env) {
+        set_error("rt_environment_eval: null argument, or a scene without an environment");
+        return RT_ERR_ARG;
+    }
+    const double len = std::sqrt((double)dir[0] * dir[0] + (double)dir[1] * dir[1] + (double)dir[2] * dir[2]);
+    if (!(len > 0.0) || !std::isfinite(len)) {
+        set_error("rt_environment_eval: direction of length %g", len);
+        return RT_ERR_ARG;
+    }
+    const EnvView E = env_host_view(s->s);
+    float r, g, b, p;
+    env_eval(E, (float)(dir[0] / len), (float)(dir[1] / len), (float)(dir[2] / len), r, g, b, p);
+    if (rgb) rgb[0] = r, rgb[1] = g, rgb[2] = b;
+    if (pdf) *pdf = p;
+    return RT_OK;
+}
+
+int rt_environment_sample(const rt_scene *s, float u1, float u2, float dir[3], float rgb[3], float *pdf) {
+    if (!s || !dir || !s->s.env) {
+        set_error("rt_environment_sample: null argument, or a scene without an environment");
+        return RT_ERR_ARG;
+    }
+    if (!(u1 >= 0.0f && u1 < 1.0f && u2 >= 0.0f && u2 < 1.0f)) {
+        set_error("rt_environment_sample: u1, u2 must lie in [0, 1)");
+        return RT_ERR_ARG;
+    }
+    const EnvView E = env_host_view(s->s);
+    float r = 0, g = 0, b = 0, p = 0;
+    dir[0] = 0, dir[1] = 1, dir[2] = 0;
+    if (s->s.env->flux > 0.0) {  // (an all-zero map has nothing to draw: pdf 0)
+        env_sample(E, u1, u2, dir[0], dir[1], dir[2]);
+        env_eval(E, dir[0], dir[1], dir[2], r, g, b, p);
+    }
+    if (rgb) rgb[0] = r, rgb[1] = g, rgb[2] = b;
+    if (pdf) *pdf = p;
+    return RT_OK;
 }
 
 }  // extern "C"

@@ -14,6 +14,8 @@
 // split of a sample range into runs writes the same main.ppm as one run over the whole range.
 // Adaptive sampling: --adaptive T [--min-spp N] [--max-spp N] gives every 8x8 tile samples until its noise estimate is
 // within T (rt_render_hip_adaptive); each pixel is written rescaled to the scene's spp (sum * spp / n).
+// Environment map: --env FILE [--env-scale S] [--env-rotate DEG] lights the scene with a lat-long .hdr / .pfm / .png / .ppm
+// panorama (rt_scene_set_environment_file); with --nee its bright texels are sampled.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -44,7 +46,7 @@ static int usage(const char *argv0) {
             "usage: %s [-f scene.json | --rtiow] [-w W] [-h H] [-d DEPTH] [-spp N] [-o out.ppm]\n"
             "          [--seed S] [--scene-seed S] [--device N] [--chunk N] [--dump-json file] [--count] [--no-png]\n"
             "          [--acc-in sums.bin] [--acc-out sums.bin] [--spp-begin FIRST] [--rr SURVIVAL_PROBABILITY] [--nee]\n"
-            "          [--nested-grid]\n"
+            "          [--nested-grid] [--env map.hdr [--env-scale S] [--env-rotate DEG]]\n"
             "          [--gpus N] [--tile-rows R] [--adaptive THRESHOLD [--min-spp N] [--max-spp N]]\n"
             "          [--denoise] [--aov PREFIX] [--feature-spp N]\n",
             argv0);
@@ -59,6 +61,9 @@ int main(int argc, char **argv) {
     double rr = -1.0;  // Russian roulette: keep the scene file's setting
     bool nee = false;  // light sampling: on if the scene file or --nee says so
     bool nested = false;  // nested grid: on if the scene file or --nested-grid says so
+    std::string env_file;  // environment map: replaces the scene file's
+    double env_scale = 1.0, env_rotate = 0.0;
+    bool have_env_opts = false;
     bool rtiow = false, have_file = false, count = false, no_png = false;
     double adaptive = -1.0;  // noise target of adaptive sampling, < 0: off
     bool have_adaptive = false;
@@ -97,6 +102,9 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--rr")) rr = atof(need("--rr"));
         else if (!strcmp(argv[i], "--nee")) nee = true;
         else if (!strcmp(argv[i], "--nested-grid")) nested = true;
+        else if (!strcmp(argv[i], "--env")) env_file = need("--env");
+        else if (!strcmp(argv[i], "--env-scale")) env_scale = atof(need("--env-scale")), have_env_opts = true;
+        else if (!strcmp(argv[i], "--env-rotate")) env_rotate = atof(need("--env-rotate")), have_env_opts = true;
         else if (!strcmp(argv[i], "--adaptive")) {
             const char *v = need("--adaptive");
             char *end = nullptr;
@@ -144,6 +152,10 @@ int main(int argc, char **argv) {
         fprintf(stderr, "rtmi: --min-spp must be >= 2 and --max-spp 0 (the scene's spp) or >= --min-spp\n");
         return 2;
     }
+    if (have_env_opts && env_file.empty()) {
+        fprintf(stderr, "rtmi: --env-scale and --env-rotate belong to --env\n");
+        return 2;
+    }
     if (feature_spp > 0 && !denoise && aov_prefix.empty()) {
         fprintf(stderr, "rtmi: --feature-spp belongs to --denoise or --aov\n");
         return 2;
@@ -166,6 +178,10 @@ int main(int argc, char **argv) {
         return 1;
     }
     if (nee && rt_scene_set_light_sampling(sc, 1) != RT_OK) {
+        fprintf(stderr, "rtmi: %s\n", rt_last_error());
+        return 1;
+    }
+    if (!env_file.empty() && rt_scene_set_environment_file(sc, env_file.c_str(), (float)env_scale, (float)env_rotate) != RT_OK) {
         fprintf(stderr, "rtmi: %s\n", rt_last_error());
         return 1;
     }

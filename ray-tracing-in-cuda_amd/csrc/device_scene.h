@@ -24,6 +24,8 @@
 //                                {|radius|, zmin, zmax, 0}
 //     alias   [nl]  1 x float4   {threshold, alias light(bits), 0, 0}: one draw u picks i = floor(u nl), then i or its alias
 //     slot    [ns + nr + nc + nt] one 32-bit word per grouped primitive id: its light, -1 = not a sampled light
+//     (an environment that is sampled is the last light: {3, -1, selection probability, 1 / 4 pi}, no geometry)
+//   ENVIRONMENT part (only with an environment map; global memory, read by the environment kernels): rt_env.h
 //
 // Primitives are grouped by type (spheres, rects, cylinders), each group in list
 // order; the original list index is kept for the reference's tie rule (a later
@@ -150,6 +152,12 @@ struct RenderParams {
     int32_t num_items;       // work items = tiles_x * bands * num_chunks (one wave each)
     // light sampling (render_nee_kernel only; nl == 0: the scene has no LIGHT part)
     int32_t nl, off_light, off_alias, off_lslot;
+    // environment map (the environment kernels only; env_rows == 0: none).  Offsets in fp32 WORDS of the image (rt_env.h: texels,
+    // marginal CDF, conditional CDFs, texel solid angle per row, cos(theta) at the row borders)
+    int32_t env_rows, env_cols;
+    float env_scale, env_uoff;
+    int32_t off_env_tex, off_env_marg, off_env_cond, off_env_band, off_env_ct;
+    float env_sel;           // selection probability of the environment's entry in the light table (the last one); 0: not sampled
 };
 
 struct DevCounters {

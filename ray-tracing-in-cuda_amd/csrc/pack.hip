@@ -703,6 +703,17 @@ int lay_out_image(RenderParams &L, const Grid &g, const Scene &s, std::vector<in
         L.off_lslot = off;
         off += (L.ns + L.nr + L.nc + L.nt + 3) / 4;
     }
+    // the ENVIRONMENT part (rt_env.h): texels, then the sampler's tables -- fp32 WORD offsets; global memory only, read by the
+    // environment kernels.  -1: the words would not fit an int32 offset
+    if (s.env) {
+        const long long R = s.env->rows, C = s.env->cols;
+        long long w = (long long)off * 4;
+        L.env_rows = (int)R, L.env_cols = (int)C;
+        const long long tex = w, marg = tex + 3 * R * C, cond = marg + (R + 1), band = cond + R * (C + 1), ct = band + R, end = ct + (R + 1);
+        if (end + 4 > (long long)INT32_MAX) return -1;
+        L.off_env_tex = (int)tex, L.off_env_marg = (int)marg, L.off_env_cond = (int)cond, L.off_env_band = (int)band, L.off_env_ct = (int)ct;
+        off = (int)((end + 3) / 4);
+    }
     return off;
 }
 
@@ -989,6 +1000,11 @@ void write_lights(float *I, const RenderParams &L, const Scene &s, const SphereS
     for (int k = 0; k < L.ns + L.nr + L.nc + L.nt; ++k) slot[k] = -1;
     for (int i = 0; i < L.nl; ++i) {
         const SceneLight &l = lights[(size_t)i];
+        if (l.prim < 0) {  // the environment: shape 3, no primitive, no geometry (rt_env.h samples it)
+            float *r = rec4(I, L.off_light + RT_LIGHT_STRIDE * i);
+            r[0] = bits(3), r[1] = bits(-1), r[2] = (float)l.prob, r[3] = (float)(1.0 / l.area);
+            continue;
+        }
         const rt_prim &p = s.prims[(size_t)l.prim];
         const int gid = group_id[(size_t)l.prim];
         slot[gid] = i;
@@ -1031,8 +1047,19 @@ void write_lights(float *I, const RenderParams &L, const Scene &s, const SphereS
     }
 }
 
+// the environment's texels and sampling tables, as the host evaluation reads them
+void write_environment(float *I, const RenderParams &L, const Scene &s) {
+    const SceneEnvironment &e = *s.env;
+    memcpy(I + L.off_env_tex, e.rgb.data(), e.rgb.size() * sizeof(float));
+    memcpy(I + L.off_env_marg, e.marg.data(), e.marg.size() * sizeof(float));
+    memcpy(I + L.off_env_cond, e.cond.data(), e.cond.size() * sizeof(float));
+    memcpy(I + L.off_env_band, e.band.data(), e.band.size() * sizeof(float));
+    memcpy(I + L.off_env_ct, e.ct.data(), e.ct.size() * sizeof(float));
+}
+
 // what a round tells pack_scene beside the image
 struct PackNote {
+    bool too_large = false;  // the environment's tables end beyond an int32 word offset
     bool demoted = false;  // (this or an earlier round) the members of an overflowing cell were forced
     size_t longest = 0;    // the longest list (near + far + others) of a cell a walk can meet
     NestedInfo nested;
@@ -1069,7 +1096,8 @@ bool pack_round(const Scene &s, std::vector<char> &forced, std::vector<float> &i
     L.nl = (int)lights.size();
 
     Grid g;
-    const bool wide = !sphere_only || S.ns() >= 65536 || !lights.empty() || nest_over > 0 || knob_set("RTMI_FORCE_WIDE");  // (the knob: measurement)
+    // (an environment, like light sampling, runs in general kernels of its own: wide tables)
+    const bool wide = !sphere_only || S.ns() >= 65536 || !lights.empty() || s.env || nest_over > 0 || knob_set("RTMI_FORCE_WIDE");  // (the knob: measurement)
     const bool built = build_grid(s, S, O, L, wide, forced, g, nest_over, nest_cap);
     note.demoted = note.demoted || g.demoted;
     if (!built) return false;
@@ -1080,6 +1108,14 @@ bool pack_round(const Scene &s, std::vector<char> &forced, std::vector<float> &i
     L.grid_sheet = (!g.cells.empty() && g.n[1] == 1 && !g.wide) ? 1 : 0;
     std::vector<int> image_word;
     const int records = lay_out_image(L, g, s, image_word);
+    if (records < 0) {
+        note.too_large = true;
+        return true;
+    }
+    if (s.env) {
+        L.env_scale = s.env_scale, L.env_uoff = env_uoff(s.env_rotate);
+        if (!lights.empty() && lights.back().prim < 0) L.env_sel = (float)lights.back().prob;
+    }
 
     image.assign((size_t)(records > 0 ? records : 1) * 4, 0.0f);
     float *I = image.data();
@@ -1095,6 +1131,7 @@ bool pack_round(const Scene &s, std::vector<char> &forced, std::vector<float> &i
     write_texels(I, s, image_word);
     write_materials(I, L, s, S, O, image_word);
     if (L.nl > 0) write_lights(I, L, s, S, O, lights);
+    if (s.env) write_environment(I, L, s);
     note.nested = NestedInfo();
     if (nested) {
         note.nested.cells = (int)(g.subs.size() / 16);
@@ -1120,6 +1157,10 @@ int pack_scene(const Scene &s, std::vector<float> &image, RenderParams &layout, 
     if (nested_out) *nested_out = NestedInfo();
     bool packed = false;
     for (size_t round = 0; round <= s.prims.size() && !packed; ++round) packed = pack_round(s, forced, image, layout, 0, 0, note);
+    if (note.too_large) {
+        set_error("the environment map's tables end beyond the int32 word offsets of the scene image");
+        return RT_ERR_LIMIT;
+    }
     // The nested grid (rt_scene_set_nested_grid): only a scene whose flat tables have a cell longer than the threshold, or lost
     // primitives to the always-tested set through an overflowing cell, is packed again -- wide, from a clean slate, with such
     // cells nested.  If that packing nests nothing (every clump was a clump in its sub-grid too), the flat tables stand.
@@ -1136,7 +1177,7 @@ int pack_scene(const Scene &s, std::vector<float> &image, RenderParams &layout, 
             bool packed2 = false;
             for (size_t round = 0; round <= s.prims.size() && !packed2; ++round)
                 packed2 = pack_round(s, forced2, image2, layout2, nest_over, nest_cap, note2);
-            if (packed2 && note2.nested.cells > 0) {
+            if (packed2 && !note2.too_large && note2.nested.cells > 0) {
                 image = std::move(image2), layout = layout2;
                 if (nested_out) *nested_out = note2.nested;
             }

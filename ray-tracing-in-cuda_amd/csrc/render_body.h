@@ -1,5 +1,5 @@
-// The body of the render kernels (render_kernel.hip): included INSIDE render_kernel, render_nee_kernel, render_nested_kernel and
-// render_feature_kernel, after their template arguments and a constexpr NEE and AOV.  As text rather than a force-inlined device function, so that the render_kernel
+// The body of the render kernels (render_kernel.hip): included INSIDE render_kernel, render_nee_kernel, render_nested_kernel,
+// render_feature_kernel and render_env_kernel (render_env.hip), after their template arguments and a constexpr NEE, AOV and ENV.  As text rather than a force-inlined device function, so that the render_kernel
 // instances compile to the very instructions they did before light sampling came (a device function that takes the
 // kernel's parameters by reference changes the order of the kernel-argument loads and with it the register allocation).
 // Not a header of its own: it needs the kernel's scope (P, image, acc, queue, counters and the template arguments).
@@ -130,6 +130,12 @@
     int shadow = 0;
     float cdx = 0, cdy = 0, cdz = 0, pend_r = 0, pend_g = 0, pend_b = 0;
     const int *lslot = reinterpret_cast<const int *>(image + P.off_lslot);
+    // ENV: the environment's tables (rt_env.h), built where they are used from launch values (wave-uniform)
+    auto env_view = [&]() -> EnvView {
+        const float *w = reinterpret_cast<const float *>(image);
+        return EnvView{w + P.off_env_tex, w + P.off_env_marg, w + P.off_env_cond, w + P.off_env_band, w + P.off_env_ct,
+                       P.env_rows, P.env_cols, P.env_scale, P.env_uoff};
+    };
     // where this lane's live path adds its sample: >= 0 the tile-local pixel (0 .. 63) in the current item's accumulator; < 0 the
     // path outlived its item (an orphan): ~cur_p is its dense local pixel index for a direct global add
     int cur_p = lane;
@@ -167,7 +173,8 @@
             // ---- closest-hit query over the LDS-resident list (hittable_list::hit,
             // object.cuh:23-37).  Wave-uniform trip counts; `best_id` is the grouped id.
             // (a shadow ray ends just short of its light point y = o + d: any hit before that occludes)
-            float best_t = (NEE && shadow != 0) ? 0.999f : INFINITY;
+            // (ENV: the shadow ray towards the environment -- shadow bit 2 -- has no far end)
+            float best_t = (NEE && shadow != 0 && !(ENV && (shadow & 4) != 0)) ? 0.999f : INFINITY;
             int best_id = -1;
 
             // spheres: sphere::hit, object.cuh:47-75.  Early-outs that need no sqrt:
@@ -944,7 +951,7 @@
                 // point; then the continuation comes back (or, behind an absorbed metal vertex, the path ends)
                 nee_add = best_id < 0;
                 L_r = pend_r, L_g = pend_g, L_b = pend_b;
-                if (shadow == 2) active = false;
+                if ((ENV ? (shadow & 3) : shadow) == 2) active = false;
                 dx = cdx, dy = cdy, dz = cdz;
                 ra = dot3(dx, dy, dz, dx, dy, dz);
                 rinv_a = 1.0f / ra;
@@ -1120,6 +1127,20 @@
             } else {
                 // miss: main.cpp:36-38 (sky) or main.cu:63 (constant background)
                 float bg_r, bg_g, bg_b;
+                float env_w = 1.0f;  // ENV + NEE: the MIS weight of a BSDF ray that escapes
+                if constexpr (ENV) {
+                    // the environment in place of both: radiance and the light strategy's density through the one lookup
+                    const EnvView EV = env_view();
+                    float pe;
+                    env_eval(EV, inv_len * dx, inv_len * dy, inv_len * dz, bg_r, bg_g, bg_b, pe);
+                    if (NEE && mis_pdf >= 0.0f) {
+                        const float pl = P.env_sel * pe;
+                        if (pl > 0.0f) {
+                            const float q = pl / mis_pdf;
+                            env_w = mis_pdf > 0.0f ? 1.0f / fmaf(q, q, 1.0f) : 0.0f;
+                        }
+                    }
+                } else
                 if (P.flags & RT_FLAG_SKY_GRADIENT) {
                     const float t = 0.5f * (inv_len * dy + 1.0f);
                     const float omt = 1.0f - t;
@@ -1128,6 +1149,7 @@
                     bg_r = P.background[0], bg_g = P.background[1], bg_b = P.background[2];
                 }
                 L_r = beta_r * bg_r, L_g = beta_g * bg_g, L_b = beta_b * bg_b;
+                if constexpr (ENV && NEE) L_r *= env_w, L_g *= env_w, L_b *= env_w;
                 if constexpr (AOV) {  // a miss: the albedo pass keeps the background (beta = 1), normal and depth add zeros
                     if (P.feature != RT_FEATURE_ALBEDO) L_r = L_g = L_b = 0.0f;
                 }
@@ -1469,7 +1491,16 @@
             const float4 h = lr[0];
             const int shape = __float_as_int(h.x);
             float ldx = 0, ldy = 0, ldz = 0, pl = 0;  // y - p and the light strategy's solid-angle density of that direction
-            if (shape == 0) {  // sphere: a direction uniform in the cone it subtends, then the nearer intersection
+            float ev_r = 0, ev_g = 0, ev_b = 0;       // ENV: the environment's radiance in the sampled direction
+            if (ENV && shape == 3) {
+                // the environment: u1 -> row and cos(theta) within its band, u2 -> column and azimuth within the texel; radiance
+                // and density of the direction as it came out, through the lookup a BSDF ray that escapes goes through
+                const EnvView EV = env_view();
+                float pe;
+                env_sample(EV, u1, u2, ldx, ldy, ldz);
+                env_eval(EV, ldx, ldy, ldz, ev_r, ev_g, ev_b, pe);
+                pl = h.z * pe;
+            } else if (shape == 0) {  // sphere: a direction uniform in the cone it subtends, then the nearer intersection
                 const float4 g = lr[3];
                 const float wx = g.x - px, wy = g.y - py, wz = g.z - pz;
                 const float c2 = dot3(wx, wy, wz, wx, wy, wz), r2 = g.w * g.w;
@@ -1533,6 +1564,10 @@
                 pend_b = vb_b * (odd ? e1.z : e0.z) * wgt;
                 // the lane's next query is the shadow ray from p to y; the continuation waits
                 shadow = nee_end ? 2 : 1;
+                if (ENV && shape == 3) {
+                    pend_r = vb_r * ev_r * wgt, pend_g = vb_g * ev_g * wgt, pend_b = vb_b * ev_b * wgt;
+                    shadow |= 4;
+                }
                 cdx = dx, cdy = dy, cdz = dz;
                 ox = px, oy = py, oz = pz;
                 dx = ldx, dy = ldy, dz = ldz;

@@ -34,6 +34,10 @@ bool launch_render_feature(const RenderParams &P, const void *image, unsigned lo
                            unsigned grid, hipStream_t stream, unsigned layout);
 int blocks_per_cu_feature(unsigned layout, size_t lds_bytes);
 int blocks_per_cu_nee(unsigned variant, size_t lds_bytes);
+bool launch_render_env(const RenderParams &P, const void *image, unsigned long long *acc, unsigned int *queue, size_t lds_bytes,
+                       unsigned grid, hipStream_t stream, unsigned layout, bool nee, bool feature);
+bool layout_has_env(unsigned layout);
+int blocks_per_cu_env(unsigned layout, size_t lds_bytes, bool nee, bool feature);
 bool variant_has_ext(unsigned variant);
 bool variant_has_count(unsigned variant);
 bool has_ablations();
@@ -315,6 +319,7 @@ static int read_tables(const rt_scene *sc, rt_table_info *out, float *dst, int c
     out->hot_bytes_grid = L.hot_vec4_grid * 16;
     out->kernel_variant = (int32_t)pick_variant(L, false, (size_t)knob("RTMI_GLOBAL_TABLE_BYTES", (double)kLdsTableBytes));
     if (L.nl > 0) out->kernel_variant |= 256;  // light sampling: the layout's light-sampling kernel
+    if (L.env_rows > 0) out->kernel_variant |= 1024;  // an environment map: the layout's environment kernel
     if (dst && cap_floats > 0) memcpy(dst, cache.image.data(), sizeof(float) * std::min((size_t)cap_floats, cache.image.size()));
     return RT_OK;
 }
@@ -444,6 +449,7 @@ struct Launcher {
     unsigned long long resident;  // workgroups that fill the chip
     unsigned variant;
     bool ext, nee, count;
+    bool env;     // an environment map: render_env_kernel of layout `variant` (plain, light sampling or feature pass)
     int feature;  // >= 0: a feature pass (render_feature_kernel of layout `variant`)
 
     int enqueue(unsigned long long *acc, unsigned int *d_queue, int first, int n, int n_list, const ChunkPlan &pl) const {
@@ -472,6 +478,14 @@ struct Launcher {
         // persistent launch: enough workgroups to fill the chip, never more than the work needs
         const unsigned long long need_blocks = (items + 3) / 4;
         const unsigned long long grid = need_blocks < resident ? (need_blocks ? need_blocks : 1) : resident;
+        if (env) {
+            if (feature >= 0) Q.feature = feature;
+            if (!launch_render_env(Q, ent->d_image, acc, d_queue, lds_bytes, (unsigned)grid, stream, variant, nee, feature >= 0)) {
+                set_error("layout %u has no environment kernel", variant);
+                return RT_ERR_ARG;
+            }
+            return RT_OK;
+        }
         if (feature >= 0) {
             Q.feature = feature;
             if (!launch_render_feature(Q, ent->d_image, acc, d_queue, lds_bytes, (unsigned)grid, stream, variant)) {
@@ -751,6 +765,17 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
         }
         variant = (size_t)(P.hot_vec4 - (P.off_box - P.off_grid)) * 16 <= global_threshold ? 16u : 24u;
     }
+    // an environment map: kernels of their own, for the general layouts
+    const bool env = P.env_rows > 0;
+    if (env && P.grid_wide == 2) {
+        set_error("this scene has the nested grid and an environment map, which no kernel combines: switch one of them off");
+        return RT_ERR_ARG;
+    }
+    if (env && (count || !layout_has_env(variant))) {
+        set_error("%s: this scene has an environment map, which the %s (the environment kernels are variants 0, 16, 36 and 44)",
+                  count ? "rt_render_hip_count" : "kernel variant", count ? "counting kernels do not carry" : "requested variant does not carry");
+        return RT_ERR_ARG;
+    }
     if (nee && P.grid_wide == 2) {
         set_error("this scene has the nested grid and light sampling on, which no kernel combines: switch one of them off");
         return RT_ERR_ARG;
@@ -801,7 +826,7 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
         return RT_ERR_LIMIT;
     }
     if (force_ext && variant_has_ext(variant) && P.grid_wide) ext = true;
-    if (nee) ext = true;
+    if (nee || env) ext = true;
     const size_t hot_bytes = hot_bytes_of(mode);
     const bool tables_global = (variant & 8u) != 0 || mode == 8;
     const size_t lds_bytes = (tables_global ? 0 : hot_bytes) + acc_lds;
@@ -844,7 +869,8 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
         ent->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     }
     const unsigned long long resident =
-        (unsigned long long)ent->num_cus * (feature >= 0 ? blocks_per_cu_feature(variant, lds_bytes)
+        (unsigned long long)ent->num_cus * (env          ? blocks_per_cu_env(variant, lds_bytes, nee, feature >= 0)
+                                            : feature >= 0 ? blocks_per_cu_feature(variant, lds_bytes)
                                             : nee  ? blocks_per_cu_nee(variant, lds_bytes)
                                                    : blocks_per_cu(variant, count, lds_bytes, ext));
 
@@ -867,7 +893,7 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     const size_t queue_off = (plane * sizeof(unsigned long long) + 255) & ~(size_t)255;
     const long long frame_tiles = (long long)P.tiles_x * P.bands;
     const size_t need = queue_off + (ad ? (((size_t)(RT_TILE_LIST_AT + frame_tiles) * 4 + 255) & ~(size_t)255) : 256);
-    const Launcher launch{P, sh, ent, d_cnt, stream, lds_bytes, resident, variant, ext, nee, count, feature};
+    const Launcher launch{P, sh, ent, d_cnt, stream, lds_bytes, resident, variant, ext, nee, count, env, feature};
 
     int launches = 0;
     if (ad) {
@@ -900,8 +926,8 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     HIP_TRY(hipGetLastError());
 
     if (stats) {
-        // what variant 0 (or a counting call) resolved to (| 256: light sampling, | 512: a feature pass)
-        stats->kernel_variant = (int32_t)(variant | (nee ? 256u : 0u) | (feature >= 0 ? 512u : 0u));
+        // what variant 0 (or a counting call) resolved to (| 256: light sampling, | 512: a feature pass, | 1024: an environment map)
+        stats->kernel_variant = (int32_t)(variant | (nee ? 256u : 0u) | (feature >= 0 ? 512u : 0u) | (env ? 1024u : 0u));
         HIP_TRY(hipEventRecord(ev2, stream));
         lock.unlock();
         HIP_TRY(hipEventSynchronize(ev2));

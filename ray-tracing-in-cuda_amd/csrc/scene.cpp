@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstring>
 
+#include "env_read.hpp"
 #include "json.hpp"
 #include "png_read.hpp"
 #include "philox.h"
@@ -286,9 +287,7 @@ static int read_ppm(const char *path, int &rows, int &cols, std::vector<uint8_t>
     return RT_OK;
 }
 
-int add_image_texture_file(Scene &s, const char *path) {
-    int rows = 0, cols = 0;
-    std::vector<uint8_t> rgb;
+int read_image_file(const char *path, int &rows, int &cols, std::vector<uint8_t> &rgb) {
     // PNG by signature (8-bit, non-interlaced), else PPM
     bool is_png = false;
     if (FILE *fp = fopen(path, "rb")) {
@@ -306,12 +305,18 @@ int add_image_texture_file(Scene &s, const char *path) {
             std::string err;
             if (!png::read(file, rows, cols, rgb, err)) {
                 set_error("%s: %s", path, err.c_str());
-                return -RT_ERR_IO;
+                return RT_ERR_IO;
             }
-            return add_image_texture(s, rows, cols, rgb.data(), path);
+            return RT_OK;
         }
     }
-    int rc = read_ppm(path, rows, cols, rgb);
+    return read_ppm(path, rows, cols, rgb);
+}
+
+int add_image_texture_file(Scene &s, const char *path) {
+    int rows = 0, cols = 0;
+    std::vector<uint8_t> rgb;
+    int rc = read_image_file(path, rows, cols, rgb);
     if (rc) return -rc;
     return add_image_texture(s, rows, cols, rgb.data(), path);
 }
@@ -542,6 +547,44 @@ int scene_from_json(const char *text, size_t len, Scene &s, const char *base_dir
         if (f->kind != JsonValue::Bool) r.fail("top level: \"nested_grid\" must be a boolean");
         else s.nested_grid = f->b;
     }
+    // "environment": {"file": path} or {"rows", "cols", "data": [rows x cols x 3 numbers]}, with optional "scale", "rotate"
+    int env_rc = RT_OK;
+    if (const JsonValue *e = root.find("environment")) {
+        if (!e->is_object()) r.fail("top level: \"environment\" must be an object");
+        else {
+            const double scale = e->find("scale") ? r.num(*e, "scale", "environment") : 1.0;
+            const double rotate = e->find("rotate") ? r.num(*e, "rotate", "environment") : 0.0;
+            const JsonValue *f = e->find("file");
+            if (f && !f->is_string()) r.fail("environment: \"file\" must be a string");
+            else if (r.ok && f) {
+                env_rc = set_environment_file(s, resolve(f->str).c_str(), (float)scale, (float)rotate);
+                if (env_rc == RT_OK) {  // (written back as given)
+                    auto named = std::make_shared<SceneEnvironment>(*s.env);
+                    named->file = f->str;
+                    s.env = named;
+                }
+            } else if (r.ok) {
+                const int rows = r.integer(*e, "rows", "environment"), cols = r.integer(*e, "cols", "environment");
+                const JsonValue *d = e->find("data");
+                if (r.ok && (rows < 1 || cols < 1)) r.fail("environment: \"rows\" and \"cols\" must be positive");
+                if (r.ok && (long long)rows * cols > kEnvMaxTexels) {
+                    set_error("environment map of %d x %d texels exceeds the limit of %lld", rows, cols, kEnvMaxTexels);
+                    return RT_ERR_LIMIT;
+                }
+                if (r.ok && (!d || !d->is_array() || d->arr.size() != (size_t)rows * (size_t)cols * 3))
+                    r.fail("environment: \"data\" must be an array of rows x cols x 3 numbers");
+                if (r.ok) {
+                    std::vector<float> rgb(d->arr.size());
+                    for (size_t i = 0; i < rgb.size() && r.ok; ++i) {
+                        if (!d->arr[i].is_number()) r.fail("environment: \"data\" entry %zu is not a number", i);
+                        else rgb[i] = (float)d->arr[i].num;
+                    }
+                    if (r.ok) env_rc = set_environment(s, rows, cols, rgb.data(), (float)scale, (float)rotate, "");
+                }
+            }
+        }
+    }
+    if (r.ok && env_rc != RT_OK) return env_rc == RT_ERR_ARG ? RT_ERR_SCENE : env_rc;
 
     // camera, parser.hpp:113-141
     const JsonValue *cam = root.find("camera");
@@ -798,6 +841,16 @@ std::string scene_to_json(const Scene &s) {
     if (s.rr_p > 0.0f) o += "  \"russian_roulette\": " + json_double((double)s.rr_p) + ",\n";
     if (s.light_sampling) o += "  \"light_sampling\": true,\n";
     if (s.nested_grid) o += "  \"nested_grid\": true,\n";
+    if (s.env) {
+        o += "  \"environment\": {";
+        if (!s.env->file.empty()) o += "\"file\": " + json_escape(s.env->file);
+        else {
+            o += "\"rows\": " + std::to_string(s.env->rows) + ", \"cols\": " + std::to_string(s.env->cols) + ", \"data\": [";
+            for (size_t i = 0; i < s.env->rgb.size(); ++i) o += (i ? ", " : "") + json_float(s.env->rgb[i]);
+            o += "]";
+        }
+        o += ", \"scale\": " + json_float(s.env_scale) + ", \"rotate\": " + json_float(s.env_rotate) + "},\n";
+    }
     o += "  \"camera\": {\"lookfrom\": ";
     put_vec3d(o, s.cam.lookfrom);
     o += ", \"lookat\": ";
@@ -1065,10 +1118,226 @@ std::vector<SceneLight> scene_lights(const Scene &s) {
         l.prob = power;
         out.push_back(l);
     }
+    // the environment, last: r^2 x scale x sum of luminance x solid angle, r the radius of the primitives' bounding sphere --
+    // the flux through that sphere's cross-section up to pi, as area x luminance is an area emitter's up to pi
+    if (s.env && s.env->flux > 0.0 && s.env_scale > 0.0f) {
+        const double r = scene_bound_radius(s);
+        const double power = r * r * (double)s.env_scale * s.env->flux;
+        if (power > 0.0 && std::isfinite(power)) {
+            SceneLight l;
+            l.prim = -1, l.type = RT_LIGHT_ENVIRONMENT;
+            l.area = 4.0 * pi;
+            l.prob = power;
+            // (reported emission: the mean radiance over the sphere)
+            double mean[3] = {0, 0, 0};
+            for (int i = 0; i < s.env->rows; ++i)
+                for (int j = 0; j < s.env->cols; ++j)
+                    for (int c = 0; c < 3; ++c) mean[c] += (double)s.env->rgb[3 * ((size_t)i * s.env->cols + j) + c] * s.env->band[(size_t)i];
+            for (int c = 0; c < 3; ++c) l.even[c] = l.odd[c] = (float)((double)s.env_scale * mean[c] / (4.0 * pi));
+            out.push_back(l);
+        }
+    }
     double total = 0.0;
     for (const SceneLight &l : out) total += l.prob;
     for (SceneLight &l : out) l.prob /= total;
     return out;
+}
+
+}  // namespace rtmi
+
+// ---------------------------------------------------------------- environment map: validation, the sampling
+// tables (rt_env.h says what they hold) and the file formats
+namespace rtmi {
+
+float env_uoff(float rotate_deg) {
+    double t = (double)rotate_deg / 360.0;
+    t -= std::floor(t);
+    const float f = (float)t;
+    return f < 1.0f ? f : 0.0f;
+}
+
+static bool env_args(float scale, float rotate_deg) {
+    if (!(scale >= 0.0f) || !std::isfinite(scale)) {
+        set_error("environment: scale %g must be finite and >= 0", (double)scale);
+        return false;
+    }
+    if (!std::isfinite(rotate_deg)) {
+        set_error("environment: rotate must be finite");
+        return false;
+    }
+    return true;
+}
+
+// takes the texels over (rgb is moved from)
+static int install_environment(Scene &s, int rows, int cols, std::vector<float> &&rgb, float scale, float rotate_deg,
+                               const std::string &file) {
+    for (size_t i = 0; i < rgb.size(); ++i)
+        if (!(rgb[i] >= 0.0f) || !std::isfinite(rgb[i])) {
+            set_error("environment: texel value %zu (%g) is negative or not finite", i, (double)rgb[i]);
+            return RT_ERR_SCENE;
+        }
+    auto e = std::make_shared<SceneEnvironment>();
+    e->rows = rows, e->cols = cols, e->file = file;
+    e->rgb = std::move(rgb);
+    // the tables, in fp64, stored as fp32: weight of a texel = luminance x the exact solid angle of its row band / cols
+    const double pi = std::acos(-1.0);
+    e->ct.resize((size_t)rows + 1);
+    std::vector<double> ctd((size_t)rows + 1);
+    for (int i = 0; i <= rows; ++i) ctd[(size_t)i] = i == 0 ? 1.0 : (i == rows ? -1.0 : std::cos(pi * (double)i / (double)rows));
+    for (int i = 0; i <= rows; ++i) e->ct[(size_t)i] = (float)ctd[(size_t)i];
+    e->band.resize((size_t)rows);
+    std::vector<double> bandd((size_t)rows), row_sum((size_t)rows, 0.0);
+    for (int i = 0; i < rows; ++i) {
+        bandd[(size_t)i] = (2.0 * pi / (double)cols) * (ctd[(size_t)i] - ctd[(size_t)i + 1]);
+        e->band[(size_t)i] = (float)bandd[(size_t)i];
+    }
+    auto lum = [&](size_t texel) {
+        const float *t = e->rgb.data() + 3 * texel;
+        return 0.2126 * t[0] + 0.7152 * t[1] + 0.0722 * t[2];
+    };
+    double total = 0.0;
+    for (int i = 0; i < rows; ++i) {
+        double acc = 0.0;
+        for (int j = 0; j < cols; ++j) acc += lum((size_t)i * cols + j);
+        row_sum[(size_t)i] = acc * bandd[(size_t)i];
+        total += row_sum[(size_t)i];
+    }
+    if (!std::isfinite(total)) {
+        set_error("environment: the texels' total is not finite");
+        return RT_ERR_SCENE;
+    }
+    e->flux = total;
+    e->marg.assign((size_t)rows + 1, 0.0f);
+    e->cond.assign((size_t)rows * ((size_t)cols + 1), 0.0f);
+    if (total > 0.0) {
+        double cum = 0.0;
+        for (int i = 0; i < rows; ++i) {
+            cum += row_sum[(size_t)i];
+            e->marg[(size_t)i + 1] = (float)std::fmin(cum / total, 1.0);
+            if (!(row_sum[(size_t)i] > 0.0)) continue;
+            float *c = e->cond.data() + (size_t)i * ((size_t)cols + 1);
+            const double rs = row_sum[(size_t)i] / bandd[(size_t)i];
+            double cc = 0.0;
+            for (int j = 0; j < cols; ++j) {
+                cc += lum((size_t)i * cols + j);
+                c[j + 1] = (float)std::fmin(cc / rs, 1.0);
+            }
+            c[cols] = 1.0f;
+        }
+        e->marg[(size_t)rows] = 1.0f;
+    }
+    s.env = std::move(e);
+    s.env_scale = scale, s.env_rotate = rotate_deg;
+    s.touch();
+    return RT_OK;
+}
+
+static int env_size(long long rows, long long cols) {
+    if (rows < 1 || cols < 1) {
+        set_error("environment: %lld x %lld texels", rows, cols);
+        return RT_ERR_ARG;
+    }
+    if (rows > kEnvMaxTexels || cols > kEnvMaxTexels || rows * cols > kEnvMaxTexels) {
+        set_error("environment map of %lld x %lld texels exceeds the limit of %lld", rows, cols, kEnvMaxTexels);
+        return RT_ERR_LIMIT;
+    }
+    return RT_OK;
+}
+
+int set_environment(Scene &s, int rows, int cols, const float *rgb, float scale, float rotate_deg, const std::string &file) {
+    if (rows == 0) {
+        s.env.reset();
+        s.env_scale = 1.0f, s.env_rotate = 0.0f;
+        s.touch();
+        return RT_OK;
+    }
+    int rc = env_size(rows, cols);
+    if (rc) return rc;
+    if (!rgb) {
+        set_error("environment: null texels");
+        return RT_ERR_ARG;
+    }
+    if (!env_args(scale, rotate_deg)) return RT_ERR_ARG;
+    std::vector<float> copy(rgb, rgb + (size_t)rows * (size_t)cols * 3);
+    return install_environment(s, rows, cols, std::move(copy), scale, rotate_deg, file);
+}
+
+int set_environment_file(Scene &s, const char *path, float scale, float rotate_deg) {
+    if (!env_args(scale, rotate_deg)) return RT_ERR_ARG;
+    std::vector<uint8_t> file;
+    FILE *fp = fopen(path, "rb");
+    if (!fp) {
+        set_error("cannot open environment map '%s'", path);
+        return RT_ERR_IO;
+    }
+    unsigned char head[4] = {0, 0, 0, 0};
+    const size_t got = fread(head, 1, 4, fp);
+    const std::vector<uint8_t> magic(head, head + got);
+    const bool hdr = envfile::is_hdr(magic), pfm = envfile::is_pfm(magic);
+    if (hdr || pfm) {
+        file.assign(head, head + got);
+        unsigned char chunk[65536];
+        size_t n;
+        while ((n = fread(chunk, 1, sizeof chunk, fp)) > 0) file.insert(file.end(), chunk, chunk + n);
+    }
+    fclose(fp);
+    int rows = 0, cols = 0;
+    std::vector<float> rgb;
+    if (hdr || pfm) {
+        std::string err;
+        const int rc = hdr ? envfile::read_hdr(file, kEnvMaxTexels, rows, cols, rgb, err) : envfile::read_pfm(file, kEnvMaxTexels, rows, cols, rgb, err);
+        if (rc) {
+            set_error("%s: %s", path, err.c_str());
+            return rc;
+        }
+    } else {  // an 8-bit image (PNG / PPM) as an LDR map: byte / 255, as image textures read their texels
+        std::vector<uint8_t> bytes;
+        int rc = read_image_file(path, rows, cols, bytes);
+        if (rc) return rc;
+        rc = env_size(rows, cols);
+        if (rc) return rc;
+        rgb.resize(bytes.size());
+        for (size_t i = 0; i < bytes.size(); ++i) rgb[i] = (float)bytes[i] / 255.0f;
+    }
+    return install_environment(s, rows, cols, std::move(rgb), scale, rotate_deg, path);
+}
+
+double scene_bound_radius(const Scene &s) {
+    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    auto add = [&](double x, double y, double z) {
+        const double p[3] = {x, y, z};
+        for (int a = 0; a < 3; ++a) lo[a] = std::fmin(lo[a], p[a]), hi[a] = std::fmax(hi[a], p[a]);
+    };
+    for (const rt_prim &p : s.prims) {
+        switch (p.type) {
+        case RT_PRIM_SPHERE: {
+            const double r = std::fabs((double)p.f[3]);
+            add(p.f[0] - r, p.f[1] - r, p.f[2] - r), add(p.f[0] + r, p.f[1] + r, p.f[2] + r);
+            break;
+        }
+        case RT_PRIM_XY_RECT: add(p.f[0], p.f[2], p.f[4]), add(p.f[1], p.f[3], p.f[4]); break;
+        case RT_PRIM_XZ_RECT: add(p.f[0], p.f[4], p.f[2]), add(p.f[1], p.f[4], p.f[3]); break;
+        case RT_PRIM_YZ_RECT: add(p.f[4], p.f[0], p.f[2]), add(p.f[4], p.f[1], p.f[3]); break;
+        case RT_PRIM_CYLINDER: {
+            const double r = std::fabs((double)p.f[0]);
+            for (int k = 0; k < 8; ++k) {
+                const double q[3] = {(k & 1) ? r : -r, (k & 2) ? r : -r, (k & 4) ? (double)p.f[2] : (double)p.f[1]};
+                double w[3];
+                for (int a = 0; a < 3; ++a) w[a] = p.m[4 * a] * q[0] + p.m[4 * a + 1] * q[1] + p.m[4 * a + 2] * q[2] + p.m[4 * a + 3];
+                add(w[0], w[1], w[2]);
+            }
+            break;
+        }
+        case RT_PRIM_TRIANGLE:
+            for (int k = 0; k < 3; ++k) add(p.m[3 * k], p.m[3 * k + 1], p.m[3 * k + 2]);
+            break;
+        default: break;
+        }
+    }
+    if (!(hi[0] >= lo[0])) return 0.0;
+    double d2 = 0.0;
+    for (int a = 0; a < 3; ++a) d2 += (hi[a] - lo[a]) * (hi[a] - lo[a]);
+    return 0.5 * std::sqrt(d2);
 }
 
 }  // namespace rtmi

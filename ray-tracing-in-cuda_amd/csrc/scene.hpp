@@ -36,6 +36,16 @@ struct SceneImage {
     std::string file;  // where it was read from ("" = given inline), for serialisation
 };
 
+// An environment map: rows x cols fp32 RGB texels in lat-long layout (row 0 = the zenith, +y) and the sampling
+// tables built from them (csrc/rt_env.h says what they hold).  Immutable once built: clones share it.
+struct SceneEnvironment {
+    int rows = 0, cols = 0;
+    std::vector<float> rgb;
+    std::vector<float> marg, cond, band, ct;
+    double flux = 0.0;  // sum over texels of luminance x solid angle (scale 1); 0: nothing to sample
+    std::string file;   // where it was read from ("" = given inline), for serialisation
+};
+
 struct DeviceSceneCache;  // owned by the render module
 
 struct Scene {
@@ -52,6 +62,8 @@ struct Scene {
     std::vector<rt_material> mats;
     std::vector<rt_texture> texs;
     std::vector<SceneImage> images;  // referenced by RT_TEX_IMAGE textures (c0[0] = index)
+    std::shared_ptr<const SceneEnvironment> env;  // null: no environment (a miss gives the background / the sky)
+    float env_scale = 1.0f, env_rotate = 0.0f;    // radiance = scale x texel; degrees about +y
     uint64_t version = 1;  // bumped on every mutation; invalidates device caches
     std::shared_ptr<DeviceSceneCache> dev;
 
@@ -62,7 +74,7 @@ struct Scene {
 // diffuse_light with a solid or checker texture and nonzero power), in list order, with their selection probabilities
 // (proportional to area x mean emission luminance)
 struct SceneLight {
-    int prim = 0, type = 0;  // list index, rt_prim_type
+    int prim = 0, type = 0;  // list index, rt_prim_type; the environment (always last): -1, RT_LIGHT_ENVIRONMENT
     double area = 0.0, prob = 0.0;
     float even[3] = {0, 0, 0}, odd[3] = {0, 0, 0};
     bool checker = false;
@@ -85,6 +97,15 @@ int add_cylinder(Scene &s, float radius, float zmin, float zmax, int material, c
 // -> texture id / triangles added / prim id, or -rt_status
 int add_image_texture(Scene &s, int rows, int cols, const uint8_t *rgb, const std::string &file);
 int add_image_texture_file(Scene &s, const char *path);
+// an 8-bit image file (PNG by signature, else PPM) -> RT_OK or an rt_status
+int read_image_file(const char *path, int &rows, int &cols, std::vector<uint8_t> &rgb);
+
+// the environment map (scene.cpp).  set_environment: rows = 0 clears; file: what to_json writes in place of the texels ("" = inline)
+constexpr long long kEnvMaxTexels = 1LL << 25;
+int set_environment(Scene &s, int rows, int cols, const float *rgb, float scale, float rotate_deg, const std::string &file);
+int set_environment_file(Scene &s, const char *path, float scale, float rotate_deg);
+float env_uoff(float rotate_deg);           // the rotation as the lookup's offset of u, in [0, 1)
+double scene_bound_radius(const Scene &s);  // radius of the bounding sphere of the primitives (of their boxes' union)
 int add_triangle(Scene &s, const float v1[3], const float v2[3], const float v3[3], const float uv1[2], const float uv2[2],
                  const float uv3[2], int material);
 int add_obj(Scene &s, const char *path, int material, float scale, const float matrix[9], const float translate[3]);
