@@ -1,0 +1,710 @@
+"""An independent statement of the path estimators of DESIGN 7a (light sampling + MIS) and 7e (environment maps), in NumPy,
+vectorised over a batch of samples, at a floating type of the caller's choice (float64: the reference; float32: the same
+formulas at the kernel's precision, used to measure how many samples sit on a branch).
+
+Test infrastructure only.  It is written from the definitions -- DESIGN 2 (the integrator, the order of the draws), 7a, 7e,
+and the reference's primitive and material definitions -- with libm's arccos / arctan2, plain closest-hit loops over the
+primitive list and no fused operations.  It shares no code with the kernels or with oracle/rt_oracle.c.
+
+Inputs are the product's exported tables (Scene.prims / materials / textures / lights / get_camera / info / environment),
+the light alias table and the environment's CDF tables as the packed image stores them (table_image, found by content), and
+the uniforms of rtmi.sample_stream.  Out of scope: triangles, image textures, the nested grid.
+
+trace() returns, per sample, the radiance, an event signature (one row of integers: per vertex the primitive hit, what the
+material did, the checker parity, the roulette outcome, the light and texel picked and whether through the alias, the shadow
+ray's verdict, how an emitter hit was weighted; two samples took the same branches iff their rows are equal; tally() counts the
+special vertices of a batch from it) and the number of draws consumed.
+"""
+import numpy as np
+
+SPHERE, XY_RECT, XZ_RECT, YZ_RECT, CYLINDER, TRIANGLE = range(6)
+LAMBERTIAN, METAL, DIELECTRIC, DIFFUSE_LIGHT = range(4)
+SOLID, CHECKER, IMAGE = range(3)
+ENVIRONMENT = 100
+T_MIN = 0.001           # hittable_list::hit's t_min of every query
+SHADOW_T_MAX = 0.999    # a shadow ray ends just short of its light point
+METAL_MIN_FUZZ = 0.05   # metal vertices below this fuzz take no light sample
+
+# event codes of the signature
+EV_MISS, EV_EMIT, EV_LAMBERT, EV_METAL, EV_METAL_ABSORBED, EV_REFLECT, EV_REFRACT = range(7)
+NONE = -9
+# the signature's columns: two per sample (draws consumed, the first roulette), then one block per vertex
+SAMPLE_COLUMNS = 2
+C_PRIM, C_MISS_TEXEL, C_PARITY, C_EVENT, C_ROULETTE, C_LIGHT, C_TEXEL, C_SHADOW, C_HIT_WEIGHT, C_ALIAS = range(10)
+VERTEX_COLUMNS = 10
+# C_SHADOW: the light sample reached its light / was occluded / had zero weight (no shadow ray) / was not made because the
+# vertex lies inside the sphere light it picked
+SHADOW_CLEAR, SHADOW_OCCLUDED, SHADOW_NONE, SHADOW_INSIDE = range(4)
+# C_HIT_WEIGHT, on an emitter hit: weighted by MIS / full weight because the ray's vertex took no light sample (a camera ray, a
+# dielectric, a near-mirror, an emitter that is no listed light) / full weight because the ray started inside the sphere light
+HIT_MIS, HIT_UNSAMPLED, HIT_FROM_INSIDE = range(3)
+
+
+# ---------------------------------------------------------------------------------------------------------------- tables
+def find_alias_table(image, lights):
+    """(threshold[nl], alias[nl]) of the packed image: the light records are found by their content (selection probability and
+    emission of every light at the record stride of 7 x 4 words), the alias table follows the last record."""
+    nl = len(lights)
+    w = np.ascontiguousarray(image, np.float32).reshape(-1)
+    bits = w.view(np.int32)
+    stride = 28
+    prob = lights["probability"].astype(np.float32)
+    cand = np.flatnonzero(w[2::4] == prob[0]) * 4
+    starts = []
+    for k in cand:
+        if k + stride * nl + 4 * nl > w.size:
+            continue
+        rec = w[k:k + stride * nl].reshape(nl, stride)
+        area = lights["shape"] != ENVIRONMENT  # (the environment's record holds no emission)
+        if (np.array_equal(rec[:, 2], prob) and np.array_equal(rec[area, 4:7], lights["emission"][area])
+                and np.array_equal(rec[area, 8:11], lights["emission_odd"][area])
+                and np.allclose(rec[:, 3], 1.0 / lights["area"].astype(np.float64), rtol=1e-6)):
+            starts.append(int(k))
+    if len(starts) != 1:
+        raise AssertionError(f"light records found {len(starts)} times in the packed image")
+    at = starts[0] + stride * nl
+    thr = w[at:at + 4 * nl:4].copy()
+    ali = bits[at + 1:at + 4 * nl:4].copy()
+    return thr, ali
+
+
+def find_env_tables(image, texels):
+    """(marg, cond, band, ct) as the packed image holds them behind the texels (fp32)"""
+    rows, cols = texels.shape[:2]
+    w = np.ascontiguousarray(image, np.float32).reshape(-1)
+    env = texels.reshape(-1)
+    n = env.size
+    tail = (rows + 1) + rows * (cols + 1) + rows + (rows + 1)
+    starts = []
+    for k in np.flatnonzero(w[:w.size - n - tail + 1] == env[0]):
+        if k % 4 or not np.array_equal(w[k:k + n], env):
+            continue
+        at = k + n
+        # (a 1 x 1 map is three words: the tables behind it decide which match is the environment)
+        if w[at] == 0 and w[at + rows] == 1 and w[at + tail - rows - 1] == 1 and w[at + tail - 1] == -1:
+            starts.append(int(at))
+    if len(starts) != 1:
+        raise AssertionError(f"environment texels found {len(starts)} times in the packed image")
+    at = starts[0]
+    marg = w[at:at + rows + 1].copy(); at += rows + 1
+    cond = w[at:at + rows * (cols + 1)].reshape(rows, cols + 1).copy(); at += rows * (cols + 1)
+    band = w[at:at + rows].copy(); at += rows
+    ct = w[at:at + rows + 1].copy()
+    return marg, cond, band, ct
+
+
+class RefScene:
+    """What trace() reads, taken from a product Scene."""
+
+    def __init__(self, sc, nee=None):
+        info = sc.info
+        self.width, self.height, self.max_depth = info.width, info.height, info.max_depth
+        self.flags, self.background, self.rr = info.flags, np.array(info.background[:], np.float32), np.float32(info.russian_roulette)
+        cam = sc.get_camera()
+        self.cam = {k: np.array(getattr(cam, k)[:], np.float32) for k in ("origin", "lower_left", "horizontal", "vertical", "u", "v")}
+        self.lens_radius = np.float32(cam.lens_radius)
+        self.prims, self.mats, self.texs = sc.prims(), sc.materials(), sc.textures()
+        for p in self.prims:
+            if p["type"] == TRIANGLE:
+                raise ValueError("triangles are out of this reference's scope")
+        for m in self.mats:
+            if m["type"] in (LAMBERTIAN, DIFFUSE_LIGHT) and self.texs[m["texture"]]["type"] == IMAGE:
+                raise ValueError("image textures are out of this reference's scope")
+        self.env = None
+        environment = sc.environment
+        self.nee = sc.light_sampling if nee is None else bool(nee)
+        self.lights = sc.lights() if self.nee else sc.lights()[:0]
+        image = sc.table_image() if (environment is not None or len(self.lights)) else None
+        if environment is not None:
+            tex, scale, rotate = environment
+            t = float(rotate) / 360.0
+            t -= np.floor(t)
+            uoff = np.float32(t)
+            marg, cond, band, ct = find_env_tables(image, tex)
+            self.env = dict(tex=tex, scale=np.float32(scale), uoff=uoff if uoff < 1 else np.float32(0), marg=marg, cond=cond, band=band, ct=ct)
+        self.thr = self.alias = None
+        if len(self.lights):
+            if not sc.light_sampling:
+                raise ValueError("the alias table only exists while the scene's light sampling is on")
+            self.thr, self.alias = find_alias_table(image, self.lights)
+        self.light_of_prim = {int(l["prim"]): i for i, l in enumerate(self.lights) if l["prim"] >= 0}
+
+
+def uniforms(rtmi, seed, width, height, first, count, n):
+    """uint32 words [count * height * width][n] of rtmi.sample_stream, samples ordered (sample, y, x)"""
+    out = np.empty((count, height * width, n), np.uint32)
+    for k in range(count):
+        for pix in range(height * width):
+            out[k, pix] = rtmi.sample_stream(seed, pix, first + k, n)
+    return out.reshape(-1, n)
+
+
+# ---------------------------------------------------------------------------------------------------------------- geometry
+def _dot(a, b):
+    return (a * b).sum(axis=-1)
+
+
+def _unit(a):
+    return a / np.sqrt(_dot(a, a))[:, None]
+
+
+def _rect_axes(ptype):
+    # (plane axis, first in-plane axis, second in-plane axis): xy_rect z = k, xz_rect y = k, yz_rect x = k
+    return {XY_RECT: (2, 0, 1), XZ_RECT: (1, 0, 2), YZ_RECT: (0, 1, 2)}[int(ptype)]
+
+
+def _affine(m, T):
+    m = np.asarray(m, T).reshape(3, 4)
+    return m[:, :3], m[:, 3]
+
+
+def _prim_t(p, o, d, dd, t_min, best, T):
+    """ray parameter at which the primitive's own hit() accepts the ray within [t_min, best], NaN where it does not"""
+    nan = T(np.nan)
+    ty = int(p["type"])
+    f = p["f"].astype(T)
+    with np.errstate(all="ignore"):
+        if ty == SPHERE:
+            oc = o - f[:3]
+            hb = _dot(oc, d)
+            disc = hb * hb - dd * (_dot(oc, oc) - f[3] * f[3])
+            sq = np.sqrt(np.maximum(disc, 0))
+            r1, r2 = (-hb - sq) / dd, (-hb + sq) / dd
+            first = (r1 >= t_min) & (r1 <= best)
+            return np.where(disc < 0, nan, np.where(first, r1, r2))
+        if ty in (XY_RECT, XZ_RECT, YZ_RECT):
+            ka, aa, ba = _rect_axes(ty)
+            t = (f[4] - o[:, ka]) / d[:, ka]
+            a, b = o[:, aa] + t * d[:, aa], o[:, ba] + t * d[:, ba]
+            inside = (a >= f[0]) & (a <= f[1]) & (b >= f[2]) & (b <= f[3])
+            return np.where(inside, t, nan)
+        # open tube about the object-space z axis
+        R, tr = _affine(p["m_inv"], T)
+        oo, od = o @ R.T + tr, d @ R.T
+        A = od[:, 0] ** 2 + od[:, 1] ** 2
+        B = 2 * (od[:, 0] * oo[:, 0] + od[:, 1] * oo[:, 1])
+        Cq = oo[:, 0] ** 2 + oo[:, 1] ** 2 - f[0] * f[0]
+        delta = B * B - 4 * A * Cq
+        sq = np.sqrt(np.maximum(delta, 0))
+        ta, tb = -0.5 * (B - sq) / A, -0.5 * (B + sq) / A
+        t0, t1 = np.minimum(ta, tb), np.maximum(ta, tb)
+        in_z = lambda t: (oo[:, 2] + t * od[:, 2] >= f[1]) & (oo[:, 2] + t * od[:, 2] <= f[2])
+        near_ok = (t0 >= t_min) & (t0 <= best) & in_z(t0)   # the near wall, within range and between the ends
+        far_ok = (t1 >= t_min) & (t1 <= best) & in_z(t1)    # else the far wall (seen through an open end, or from inside)
+        t = np.where(near_ok, t0, np.where(far_ok, t1, nan))
+        # the near root beyond the range ends the test (cylinder::hit returns before it tries the far one)
+        t = np.where((delta < 0) | (t0 > best) | (t1 < t_min), nan, t)
+        return t
+
+
+def closest_hit(S, o, d, t_max, T):
+    """hittable_list::hit: primitives in list order, a hit is accepted while t_min <= t <= the closest so far (ties: the later)"""
+    n = len(o)
+    best = np.full(n, t_max, T) if np.isscalar(t_max) else t_max.astype(T).copy()
+    idx = np.full(n, -1, np.int64)
+    dd = _dot(d, d)
+    t_min = T(T_MIN)
+    for i, p in enumerate(S.prims):
+        t = _prim_t(p, o, d, dd, t_min, best, T)
+        with np.errstate(invalid="ignore"):
+            ok = (t >= t_min) & (t <= best)
+        best = np.where(ok, t, best)
+        idx = np.where(ok, i, idx)
+    return best, idx
+
+
+def hit_record(S, o, d, t, idx, T):
+    """point and face-turned normal of accepted hits; front = the ray meets the outward side"""
+    p = o + t[:, None] * d
+    n_out = np.zeros_like(o)
+    for i in np.unique(idx):
+        m = idx == i
+        pr = S.prims[i]
+        ty, f = int(pr["type"]), pr["f"].astype(T)
+        if ty == SPHERE:
+            n_out[m] = (p[m] - f[:3]) / f[3]
+        elif ty == CYLINDER:
+            R, tr = _affine(pr["m_inv"], T)
+            op = p[m] @ R.T + tr
+            radial = np.stack([op[:, 0], op[:, 1], np.zeros_like(op[:, 0])], axis=1)
+            radial /= np.sqrt(_dot(radial, radial))[:, None]
+            n_out[m] = radial @ R  # apply_normal: the transpose of the inverse
+        else:
+            n_out[m, _rect_axes(ty)[0]] = 1
+    front = _dot(d, n_out) < 0
+    return p, np.where(front[:, None], n_out, -n_out), front
+
+
+def checker_odd(p, T):
+    """sign of sin(10x) sin(10y) sin(10z) < 0, as the parity of the three floors (a zero factor: even)"""
+    k = np.floor(T(10) * p / T(np.pi)).astype(np.int64).sum(axis=1)
+    return (k % 2 != 0) & ~(p == 0).any(axis=1)
+
+
+def texture_value(S, tex, p, T):
+    out = np.zeros_like(p)
+    for ti in np.unique(tex):
+        m = tex == ti
+        t = S.texs[ti]
+        c0, c1 = t["c0"].astype(T), t["c1"].astype(T)
+        out[m] = np.where(checker_odd(p[m], T)[:, None], c1, c0) if t["type"] == CHECKER else c0
+    return out
+
+
+def metal_pdf(w, r, f, T):
+    """solid-angle density at unit w of d = r + f s, s uniform in the unit ball: the length of the ray t w inside the ball of
+    radius f about r, weighted by t^2 and normalised by the ball's volume"""
+    wr = _dot(w, r)
+    disc = wr * wr - (1 - f * f)
+    sq = np.sqrt(np.maximum(disc, 0))
+    t1, t0 = wr + sq, np.maximum(wr - sq, 0)
+    pdf = (t1 ** 3 - t0 ** 3) / (4 * T(np.pi) * f ** 3)
+    return np.where((disc >= 0) & (t1 > 0), pdf, 0).astype(T)
+
+
+# ---------------------------------------------------------------------------------------------------------------- environment
+def env_texel(E, d, T):
+    rows, cols = E["tex"].shape[:2]
+    pi = T(np.pi)
+    v = np.arccos(np.clip(d[:, 1], -1, 1)) / pi
+    row = np.clip((v * rows).astype(np.int64), 0, rows - 1)
+    u = (np.arctan2(-d[:, 2], d[:, 0]) + pi) / (2 * pi) + T(E["uoff"])
+    u = u - np.floor(u)
+    col = np.clip((u * cols).astype(np.int64), 0, cols - 1)
+    return row, col
+
+
+def env_eval(E, d, T):
+    """radiance and sampling density of unit directions, through the one lookup both strategies use"""
+    row, col = env_texel(E, d, T)
+    rad = T(E["scale"]) * E["tex"][row, col].astype(T)
+    pm = E["marg"].astype(T)[row + 1] - E["marg"].astype(T)[row]
+    cond = E["cond"].astype(T)
+    pc = cond[row, col + 1] - cond[row, col]
+    return rad, pm * pc / E["band"].astype(T)[row], row * E["tex"].shape[1] + col
+
+
+def env_sample(E, u1, u2, T):
+    rows, cols = E["tex"].shape[:2]
+    marg, cond, ct = E["marg"].astype(T), E["cond"].astype(T), E["ct"].astype(T)
+    row = np.clip(np.searchsorted(marg[:rows], u1, side="right") - 1, 0, rows - 1)  # the last entry <= u1
+    m0, m1 = marg[row], marg[row + 1]
+    with np.errstate(all="ignore"):
+        a1 = np.where(m1 > m0, (u1 - m0) / (m1 - m0), T(0.5))
+        col = np.zeros(len(row), np.int64)
+        for r in np.unique(row):
+            col[row == r] = np.searchsorted(cond[r, :cols], u2[row == r], side="right") - 1
+        col = col.clip(0, cols - 1)
+        c0, c1 = cond[row, col], cond[row, col + 1]
+        a2 = np.where(c1 > c0, (u2 - c0) / (c1 - c0), T(0.5))
+    cth = ct[row] + a1 * (ct[row + 1] - ct[row])
+    sth = np.sqrt(np.maximum(0, 1 - cth * cth))
+    u = (col + a2) / cols - T(E["uoff"])
+    u = u - np.floor(u)
+    phi = 2 * T(np.pi) * u - T(np.pi)
+    return np.stack([sth * np.cos(phi), cth, -sth * np.sin(phi)], axis=1).astype(T)
+
+
+# ---------------------------------------------------------------------------------------------------------------- light sampling
+def inside_sphere_light(S, li, p, T):
+    """is p inside (or on) sphere light li: c^2 <= r^2, where the cone of directions towards it is the whole sphere"""
+    f = S.prims[S.lights[li]["prim"]]["f"].astype(T)
+    return ~(_dot(f[:3] - p, f[:3] - p) > f[3] * f[3])
+
+
+def light_pdf_of_hit(S, li, o, d, t, n, T):
+    """the light strategy's solid-angle density of the direction of a ray from o that hit light li at parameter t (normal n)"""
+    L = S.lights[li]
+    sel = T(L["probability"])
+    if L["shape"] == SPHERE:
+        f = S.prims[L["prim"]]["f"].astype(T)
+        c2, r2 = _dot(f[:3] - o, f[:3] - o), f[3] * f[3]
+        with np.errstate(all="ignore"):
+            cos_max = np.sqrt(np.maximum(0, 1 - r2 / c2))
+            pdf = sel / (2 * T(np.pi) * (r2 / c2) / (1 + cos_max))
+        return np.where(inside_sphere_light(S, li, o, T), 0, pdf)
+    dist2 = t * t * _dot(d, d)
+    cos_l = np.abs(_dot(n, d)) / np.sqrt(_dot(d, d))
+    with np.errstate(all="ignore"):
+        return sel / T(L["area"]) * dist2 / cos_l
+
+
+def sample_light(S, li, p, u1, u2, T, perturb=()):
+    """for the vertices p that picked light li: (vector from p to the light point (a unit direction for the environment),
+    the light strategy's solid-angle density there, the emitted radiance towards p, the texel picked or NONE)"""
+    L = S.lights[li]
+    sel, pi = T(L["probability"]), T(np.pi)
+    n = len(p)
+    texel = np.full(n, NONE, np.int64)
+    if L["shape"] == ENVIRONMENT:
+        ld = env_sample(S.env, u1, u2, T)
+        rad, pe, texel = env_eval(S.env, ld, T)
+        return ld, sel * pe, rad, texel
+    pr = S.prims[L["prim"]]
+    f = pr["f"].astype(T)
+    if L["shape"] == SPHERE:
+        # a direction uniform in the cone the sphere subtends (u1: the polar angle, u2: the azimuth, in the frame of
+        # Duff et al. 2017 about the axis), then the nearer intersection
+        w = f[:3] - p
+        c2, r2 = _dot(w, w), f[3] * f[3]
+        with np.errstate(all="ignore"):
+            q = r2 / c2
+            omc = q / (1 + np.sqrt(np.maximum(0, 1 - q)))
+            cth = 1 - u1 * omc
+            sth2 = np.maximum(0, 1 - cth * cth)
+            sth = np.sqrt(sth2)
+            phi = 2 * pi * u2
+            c = np.sqrt(c2)
+            a = w / c[:, None]
+            sg = np.copysign(T(1), a[:, 2])
+            fa = -1 / (sg + a[:, 2])
+            fb = a[:, 0] * a[:, 1] * fa
+            t1 = np.stack([1 + sg * a[:, 0] ** 2 * fa, sg * fb, -sg * a[:, 0]], axis=1)
+            t2 = np.stack([fb, sg + a[:, 1] ** 2 * fa, -a[:, 1]], axis=1)
+            e = (sth * np.cos(phi))[:, None] * t1 + (sth * np.sin(phi))[:, None] * t2 + cth[:, None] * a
+            dist = c * cth - np.sqrt(np.maximum(0, r2 - c2 * sth2))
+            ld = dist[:, None] * e
+            pl = sel / (2 * pi * omc)
+        outside = ~inside_sphere_light(S, li, p, T)  # a vertex inside the sphere takes no sample of it
+        ld, pl = np.where(outside[:, None], ld, 0), np.where(outside, pl, 0)
+    else:
+        if L["shape"] == CYLINDER:
+            R, tr = _affine(pr["m"], T)
+            phi = 2 * pi * u1
+            q = np.stack([np.abs(f[0]) * np.cos(phi), np.abs(f[0]) * np.sin(phi), f[1] + u2 * (f[2] - f[1])], axis=1)
+            y = q @ R.T + tr
+            ln = np.stack([np.cos(phi), np.sin(phi), np.zeros_like(phi)], axis=1) @ R.T
+        else:
+            ka, aa, ba = _rect_axes(L["shape"])
+            y = np.zeros((n, 3), T)
+            y[:, aa], y[:, ba], y[:, ka] = f[0] + u1 * (f[1] - f[0]), f[2] + u2 * (f[3] - f[2]), f[4]
+            ln = np.zeros((n, 3), T)
+            ln[:, ka] = 1
+        ld = y - p
+        d2 = _dot(ld, ld)
+        with np.errstate(all="ignore"):
+            cos_l = np.abs(_dot(ln, ld)) / np.sqrt(d2)
+            if "no_cos" in perturb:
+                cos_l = np.ones_like(cos_l)
+            pl = sel / T(L["area"]) * d2 / cos_l
+    odd = checker_odd(p + ld, T)
+    rad = np.where(odd[:, None], L["emission_odd"].astype(T), L["emission"].astype(T))
+    return ld.astype(T), pl.astype(T), rad, texel
+
+
+# ---------------------------------------------------------------------------------------------------------------- the integrator
+class _Draws:
+    """the per-sample cursor over the uniforms of the sample's own stream"""
+
+    def __init__(self, words, T):
+        self.u = (words >> 8).astype(T) * T(2.0 ** -24)
+        self.at = np.zeros(len(words), np.int64)
+        self.limit = words.shape[1]
+
+    def next(self, who):
+        """one uniform for the samples `who` (indices)"""
+        v = self.u[who, np.minimum(self.at[who], self.limit - 1)]
+        self.at[who] += 1
+        return v
+
+    def reject(self, who, dims, T):
+        """rejection sampling from (-1, 1)^dims to the open unit ball, for the samples `who`"""
+        out = np.zeros((len(who), 3), T)
+        todo = np.arange(len(who))
+        while len(todo):
+            c = np.stack([2 * self.next(who[todo]) - 1 for _ in range(dims)], axis=1)
+            ok = _dot(c, c) < 1
+            out[todo[ok], :dims] = c[ok]
+            todo = todo[~ok]
+            if (self.at[who] > self.limit + 64).any():
+                raise RuntimeError("a rejection loop ran far beyond the requested draws")
+        return out
+
+
+def trace(S, words, first_pixel=0, dtype=np.float64, perturb=()):
+    """One sample per row of `words` (the sample's stream as uint32 words), pixel ids first_pixel, first_pixel + 1, ... modulo the
+    frame.  Returns (rgb [N][3], signature [N][*] int64, draws consumed [N])."""
+    T = dtype
+    N = len(words)
+    D = _Draws(words, T)
+    W, H = S.width, S.height
+    pix = (first_pixel + np.arange(N)) % (W * H)
+    everyone = np.arange(N)
+    rr, pi = T(S.rr), T(np.pi)
+    cam = {k: v.astype(T) for k, v in S.cam.items()}
+    sig = [np.full((N, SAMPLE_COLUMNS), NONE, np.int64)]
+
+    def note(column, who, values):
+        sig[-1][who, column] = values
+
+    # camera::get_ray: the jitter, then the lens sample where blur is on
+    s = ((pix % W).astype(T) + D.next(everyone)) / T(W - 1)
+    t = ((pix // W).astype(T) + D.next(everyone)) / T(H - 1)
+    off = np.zeros((N, 3), T)
+    if S.flags & 2:
+        lens = T(S.lens_radius) * D.reject(everyone, 2, T)
+        off = lens[:, :1] * cam["u"] + lens[:, 1:2] * cam["v"]
+    o = cam["origin"] + off
+    d = cam["lower_left"] + s[:, None] * cam["horizontal"] + t[:, None] * cam["vertical"] - cam["origin"] - off
+    beta = np.ones((N, 3), T)
+    rgb = np.zeros((N, 3), T)
+    depth = np.full(N, S.max_depth, np.int64)
+    mis = np.full(N, -1, T)  # density of the BSDF sample that made the ray; < 0: its vertex took no light sample
+    alive = depth > 0
+    if rr > 0:  # roulette before the first query as before every other
+        lost = D.next(everyone) > rr
+        note(1, everyone, lost)
+        alive &= ~lost
+        beta = beta / rr
+
+    while alive.any():
+        who = np.flatnonzero(alive)
+        oo, dd = o[who], d[who]
+        t_hit, idx = closest_hit(S, oo, dd, np.inf, T)
+        sig.append(np.full((N, VERTEX_COLUMNS), NONE, np.int64))
+        note(C_PRIM, who, idx)
+        # ---- a miss ends the path with the background
+        miss = idx < 0
+        if miss.any():
+            m = who[miss]
+            ud = _unit(dd[miss])
+            if S.env is not None:
+                bg, pe, texel = env_eval(S.env, ud, T)
+                note(C_MISS_TEXEL, m, texel)
+                if len(S.lights) and S.lights[-1]["shape"] == ENVIRONMENT:
+                    pl = T(S.lights[-1]["probability"]) * pe
+                    bg = bg * _mis_bsdf(mis[m], pl, perturb)[:, None]
+            elif S.flags & 1:
+                tt = 0.5 * (ud[:, 1] + 1)
+                bg = (1 - tt)[:, None] * np.ones(3, T) + tt[:, None] * np.array([0.5, 0.7, 1.0], T)
+            else:
+                bg = np.broadcast_to(S.background.astype(T), (len(m), 3))
+            rgb[m] += beta[m] * bg
+            alive[m] = False
+        if miss.all():
+            continue
+        who, oo, dd, t_hit, idx = who[~miss], oo[~miss], dd[~miss], t_hit[~miss], idx[~miss]
+        p, n, front = hit_record(S, oo, dd, t_hit, idx, T)
+        mat = S.prims["material"][idx]
+        kind = S.mats["type"][mat]
+        tex = S.mats["texture"][mat]
+        checker = np.isin(kind, (LAMBERTIAN, DIFFUSE_LIGHT)) & (S.texs["type"][np.maximum(tex, 0)] == CHECKER)
+        note(C_PARITY, who, np.where(checker, checker_odd(p, T), NONE))
+        event = np.full(len(who), NONE, np.int64)
+        # ---- an emitter ends the path with what it emits
+        em = kind == DIFFUSE_LIGHT
+        if em.any():
+            m = who[em]
+            Le = texture_value(S, tex[em], p[em], T)
+            wgt = np.ones(em.sum(), T)
+            how = np.full(em.sum(), HIT_UNSAMPLED, np.int64)
+            for li in {S.light_of_prim.get(int(i), -1) for i in np.unique(idx[em])} - {-1}:
+                sel = idx[em] == S.lights[li]["prim"]
+                pl = light_pdf_of_hit(S, li, oo[em][sel], dd[em][sel], t_hit[em][sel], n[em][sel], T)
+                wgt[sel] = _mis_bsdf(mis[m][sel], pl, perturb)
+                inside = inside_sphere_light(S, li, oo[em][sel], T) if S.lights[li]["shape"] == SPHERE else np.zeros(sel.sum(), bool)
+                how[sel] = np.where(mis[m][sel] < 0, HIT_UNSAMPLED, np.where(inside, HIT_FROM_INSIDE, HIT_MIS))
+            note(C_HIT_WEIGHT, m, how)
+            rgb[m] += beta[m] * Le * wgt[:, None]
+            alive[m] = False
+            event[em] = EV_EMIT
+        # ---- the scatter step
+        new_d = np.zeros_like(dd)
+        att = np.ones_like(dd)
+        scattered = ~em
+        pdf_b = np.full(len(who), -1, T)
+        refl_dir = np.zeros_like(dd)       # metal: the mirror direction of its lobe
+        fuzz = np.zeros(len(who), T)       # metal: its fuzz (0: a lambertian vertex)
+        takes_light = np.zeros(len(who), bool)
+        lam = kind == LAMBERTIAN
+        if lam.any():
+            sph = D.reject(who[lam], 3, T)
+            nd = n[lam] + _unit(sph)
+            tiny = (np.abs(nd) < 1e-8).all(axis=1)
+            nd[tiny] = n[lam][tiny]
+            new_d[lam], att[lam] = nd, texture_value(S, tex[lam], p[lam], T)
+            event[lam] = EV_LAMBERT
+            takes_light[lam] = True
+            pdf_b[lam] = np.maximum(0, _dot(_unit(nd), n[lam])) / pi
+        met = kind == METAL
+        if met.any():
+            ud = _unit(dd[met])
+            r = ud - 2 * _dot(ud, n[met])[:, None] * n[met]
+            fz = S.mats["fuzz"][mat[met]].astype(T)
+            nd = r + fz[:, None] * D.reject(who[met], 3, T)
+            up = _dot(nd, n[met]) > 0
+            new_d[met], att[met] = nd, S.mats["albedo"][mat[met]].astype(T)
+            scattered[met] = up
+            event[met] = np.where(up, EV_METAL, EV_METAL_ABSORBED)
+            refl_dir[met], fuzz[met] = r, fz
+            takes_light[met] = S.mats["fuzz"][mat[met]] >= np.float32(METAL_MIN_FUZZ)
+            for f in np.unique(fz[takes_light[met]]):
+                sel = np.flatnonzero(met)[(fz == f) & up]
+                pdf_b[sel] = metal_pdf(_unit(new_d[sel]), refl_dir[sel], f, T)
+        die = kind == DIELECTRIC
+        if die.any():
+            ir = S.mats["ir"][mat[die]].astype(T)
+            ratio = np.where(front[die], 1 / ir, ir)
+            ud, nn = _unit(dd[die]), n[die]
+            cos_t = np.minimum(-_dot(ud, nn), 1)
+            sin_t = np.sqrt(np.maximum(0, 1 - cos_t * cos_t))
+            reflect = ratio * sin_t > 1
+            can = np.flatnonzero(~reflect)
+            if len(can):  # the uniform is drawn only where refraction is possible
+                r0 = ((1 - ratio[can]) / (1 + ratio[can])) ** 2
+                schlick = r0 + (1 - r0) * (1 - cos_t[can]) ** 5
+                reflect[can] = schlick > D.next(who[die][can])
+            perp = ratio[:, None] * (ud + cos_t[:, None] * nn)
+            refracted = perp - np.sqrt(np.abs(1 - _dot(perp, perp)))[:, None] * nn
+            new_d[die] = np.where(reflect[:, None], ud - 2 * _dot(ud, nn)[:, None] * nn, refracted)
+            event[die] = np.where(reflect, EV_REFLECT, EV_REFRACT)
+        note(C_EVENT, who, event)
+        if not S.nee or len(S.lights) == 0:
+            takes_light[:] = False
+        # ---- what goes on: depth, then the roulette of the next query
+        go = ~em & scattered
+        carried = beta[who] * att                      # the throughput the continuation carries
+        depth[who[go]] -= 1
+        go_on = go & (depth[who] > 0)
+        absorbed = ~em & ~scattered                    # (a metal direction below the surface)
+        # an absorbed metal vertex samples its light where its continuation would have been traced, with a roulette draw of its own
+        draws_rr = go_on | (absorbed & takes_light & (depth[who] > 1))
+        survived = draws_rr.copy()
+        if rr > 0 and draws_rr.any():
+            k = np.flatnonzero(draws_rr)
+            lost = D.next(who[k]) > rr
+            note(C_ROULETTE, who[k], lost)
+            survived[k] = ~lost
+            carried[k] = carried[k] / rr
+        alive[who] = go_on & survived
+        beta[who] = carried
+        o[who], d[who] = p, new_d
+        mis[who] = np.where(takes_light, pdf_b, -1)
+        # ---- the light sample
+        ls = np.flatnonzero(takes_light & survived & draws_rr & (len(S.lights) > 0))
+        if len(ls) == 0:
+            continue
+        m = who[ls]
+        if "skip_draw" in perturb:
+            D.at[m] += 1
+        u0, u1, u2 = D.next(m), D.next(m), D.next(m)
+        nl = len(S.lights)
+        xs = u0 * nl
+        pick = np.minimum(xs.astype(np.int64), nl - 1)
+        aliased = xs - pick >= S.thr.astype(T)[pick]
+        pick = np.where(aliased, S.alias[pick], pick)
+        note(C_LIGHT, m, pick)
+        note(C_ALIAS, m, aliased)
+        ld = np.zeros((len(m), 3), T)
+        pl = np.zeros(len(m), T)
+        Le = np.zeros((len(m), 3), T)
+        texel = np.full(len(m), NONE, np.int64)
+        inside = np.zeros(len(m), bool)
+        for li in np.unique(pick):
+            sel = pick == li
+            ld[sel], pl[sel], Le[sel], texel[sel] = sample_light(S, li, p[ls][sel], u1[sel], u2[sel], T, perturb)
+            if S.lights[li]["shape"] == SPHERE:
+                inside[sel] = inside_sphere_light(S, li, p[ls][sel], T)
+        note(C_TEXEL, m, texel)
+        d2 = _dot(ld, ld)
+        with np.errstate(all="ignore"):
+            w = ld / np.sqrt(d2)[:, None]
+            wn = _dot(w, n[ls])
+            pb = np.where(fuzz[ls] > 0, 0, wn / pi)
+            for f in np.unique(fuzz[ls][fuzz[ls] > 0]):
+                sel = fuzz[ls] == f
+                pb[sel] = metal_pdf(w[sel], refl_dir[ls][sel], f, T)
+            pb = np.where(wn > 0, pb, 0)
+            # f cos / p_l times the power heuristic's p_l^2 / (p_l^2 + pdf_b^2); f cos = albedo x pdf_b for both materials
+            weight = pb * pl / (pl + pb if "mis_unsquared" in perturb else pl * pl + pb * pb)
+        usable = (pl > 0) & (pb > 0) & (d2 > 0) & np.isfinite(weight) & (weight > 0)
+        verdict = np.where(inside, SHADOW_INSIDE, SHADOW_NONE)
+        if usable.any():
+            k = np.flatnonzero(usable)
+            is_env = S.lights["shape"][pick[k]] == ENVIRONMENT
+            far = np.where(is_env, T(np.inf), T(SHADOW_T_MAX))
+            _, blocker = closest_hit(S, p[ls][k], ld[k], far, T)
+            verdict[k] = np.where(blocker >= 0, SHADOW_OCCLUDED, SHADOW_CLEAR)
+            clear = k[blocker < 0]
+            through = carried[ls][clear]
+            if "no_rr_light" in perturb and rr > 0:
+                through = through * rr
+            rgb[m[clear]] += through * Le[clear] * weight[clear][:, None]
+        note(C_SHADOW, m, verdict)
+
+    sig[0][:, 0] = D.at
+    return rgb, np.concatenate(sig, axis=1), D.at.copy()
+
+
+def same_signature(a, b):
+    """per sample: did two runs over the same draws take the same branches (rows equal, the shorter one padded)"""
+    w = max(a.shape[1], b.shape[1])
+    pad = lambda s: np.pad(s, ((0, 0), (0, w - s.shape[1])), constant_values=NONE)
+    return (pad(a) == pad(b)).all(axis=1)
+
+
+def tally(sig):
+    """How often the special vertices of DESIGN 7a occurred in a batch, read from its signatures, so that a test of such a case can
+    assert that the case was there: light samples not made because the vertex lies inside the sphere light it picked, and BSDF
+    hits on that light from inside kept at weight 1; absorbed metal vertices that took a light sample all the same; dielectric
+    vertices, the light samples they took (none, by definition) and the emitter hits of their rays at full weight; light picks
+    that went to the bucket's own light and to its alias."""
+    v = sig[:, SAMPLE_COLUMNS:].reshape(len(sig), -1, VERTEX_COLUMNS)
+    event, light, shadow, how, alias = (v[:, :, c] for c in (C_EVENT, C_LIGHT, C_SHADOW, C_HIT_WEIGHT, C_ALIAS))
+    glass = np.isin(event, (EV_REFLECT, EV_REFRACT))
+    return dict(inside_no_sample=int((shadow == SHADOW_INSIDE).sum()), inside_full_weight_hits=int((how == HIT_FROM_INSIDE).sum()),
+                absorbed_metal_light_samples=int(((event == EV_METAL_ABSORBED) & (light != NONE)).sum()),
+                dielectric_vertices=int(glass.sum()), dielectric_light_samples=int((glass & (light != NONE)).sum()),
+                dielectric_full_weight_hits=int((glass[:, :-1] & (how[:, 1:] == HIT_UNSAMPLED)).sum()),
+                bucket_picks=int((alias == 0).sum()), alias_picks=int((alias == 1).sum()))
+
+
+def _mis_bsdf(pdf_b, pl, perturb=()):
+    """weight of a BSDF ray's emitter hit or escape: pdf_b^2 / (pdf_b^2 + p_l^2); 1 where the vertex took no light sample
+    (pdf_b < 0) or the light strategy cannot produce the direction"""
+    with np.errstate(all="ignore"):
+        if "mis_unsquared" in perturb:
+            w = pdf_b / (pdf_b + pl)
+        else:
+            w = pdf_b * pdf_b / (pdf_b * pdf_b + pl * pl)
+    w = np.where(pdf_b > 0, w, 0)
+    return np.where((pdf_b >= 0) & (pl > 0), w, 1).astype(pl.dtype)
+
+
+def implied_alias_probability(thr, alias):
+    """(thr_i + sum over j with alias_j = i of (1 - thr_j)) / n: the probability with which one uniform draw picks light i"""
+    thr = thr.astype(np.float64)
+    n = len(thr)
+    p = thr.copy()
+    np.add.at(p, alias, 1.0 - thr)
+    return p / n
+
+
+# ---------------------------------------------------------------------------------------------------------------- the comparison
+def reference(S, words):
+    """the fp64 radiance, which samples took the same branches at fp32 (the stable ones), the draws consumed, and the tally of the
+    fp64 run's special vertices"""
+    rgb, sig64, draws = trace(S, words)
+    _, sig32, _ = trace(S, words, dtype=np.float32)
+    return rgb, same_signature(sig64, sig32), draws, tally(sig64)
+
+
+def judge(got, ref, stable):
+    """The figures the per-sample assertions read.  got / ref: [N][3].
+    share: samples within 1e-4 max(1, |ref|) in every channel (gate G2's number, scaled for emitters brighter than 1);
+    z: per channel, mean(got - ref) in units of std(got - ref) / sqrt(N); bias_ok: |mean| < 5 std / sqrt(N) + 1e-6"""
+    diff = got.astype(np.float64) - ref
+    within = (np.abs(diff) <= 1e-4 * np.maximum(1.0, np.abs(ref))).all(axis=1)
+    n = len(ref)
+    mean, se = diff.mean(axis=0), diff.std(axis=0) / np.sqrt(n)
+    return dict(share=float(within.mean()), median=float(np.median(np.abs(diff).max(axis=1))),
+                share_stable=float(within[stable].mean()), flips=float(1 - stable.mean()),
+                z=(mean / np.maximum(se, 1e-300)) * (np.abs(mean) > 0), bias_ok=bool((np.abs(mean) < 5 * se + 1e-6).all()),
+                mean_diff=mean)
+
+
+def row(name, j, base=None):
+    z = " ".join(f"{v:+.2f}" for v in j["z"])
+    b = "" if base is None else f" | plain stable {100 * base:7.3f} %"
+    return (f"{name:40s} | within {100 * j['share']:7.3f} % | median {j['median']:.2e} | flips {100 * j['flips']:.3f} % | "
+            f"stable within {100 * j['share_stable']:7.3f} %{b} | max |mean diff| {np.abs(j['mean_diff']).max():.1e}, z {z}")

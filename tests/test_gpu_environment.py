@@ -8,6 +8,7 @@ import sys
 import numpy as np
 import pytest
 
+from nee_scenes import PATCH_ROWS, PATCH_COLS, patch_expected, patch_scene
 from test_gpu_light_sampling import compare
 from test_nested_grid import dense_room
 
@@ -235,24 +236,12 @@ def test_unbiased_against_the_textured_sphere(rtmi):
 
 # ---- known answer ------------------------------------------------------------------------------------------------------------
 def test_known_answer_under_a_small_bright_patch(rtmi):
-    rows, cols, RHO, L = 32, 64, 0.5, 50.0
-    env = np.zeros((rows, cols, 3), np.float32)
-    env[4:6, 10:13] = L
+    rows, cols = PATCH_ROWS, PATCH_COLS
     # the patch: < 1 % of the upper hemisphere
     band = (2 * np.pi / cols) * (np.cos(np.pi * np.arange(rows) / rows) - np.cos(np.pi * (np.arange(rows) + 1) / rows))
     assert 3 * band[4:6].sum() < 0.01 * 2 * np.pi
-    # rho / pi x sum L cos(theta) dOmega by sub-texel quadrature (the floor's normal is +y: cos(theta) = d.y)
-    q = 64
-    expected = 0.0
-    for i in (4, 5):
-        th = np.pi * (i + (np.arange(q) + 0.5) / q) / rows
-        expected += 3 * (2 * np.pi / cols) * np.sum(L * np.cos(th) * np.sin(th)) * (np.pi / rows / q)
-    expected *= RHO / np.pi
-    sc = rtmi.Scene.new(64, 36, 256, 2)  # camera -> floor -> environment: the direct term alone
-    sc.set_background((0, 0, 0), sky_gradient=False, defocus_blur=False)
-    sc.camera((2.5, 1.2, -1.5), (2.5, 0.0, 0.0), (0, 1, 0), 50.0)
-    sc.xz_rect(-50, 50, -50, 50, 0.0, sc.lambertian((RHO, RHO, RHO)))
-    sc.set_environment(env, 1.0, 40.0)
+    expected = patch_expected()
+    sc = patch_scene(rtmi)
     mean = lambda img: img.astype(np.float64).mean(axis=2) / sc.spp
     stats = {}
     for nee in (False, True):

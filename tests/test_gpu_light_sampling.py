@@ -13,6 +13,8 @@ PKG = os.path.join(ROOT, "ray-tracing-in-cuda_amd")
 SCENES = os.path.join(PKG, "scenes")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "scenes_as_shipped")
 
+from nee_scenes import RHO, LE, H, LX, LZ, analytic_scene, analytic_expected, pair_scene, many_lights  # noqa: F401 (shared with test_nee_reference.py)
+
 pytestmark = pytest.mark.gpu
 
 
@@ -24,46 +26,6 @@ def rtmi():
     if mod.device_count() < 1:
         pytest.skip("no HIP device")
     return mod
-
-
-# ---- the analytic scene: a lambertian floor under a parallel emissive rectangle ---------------------------------------
-RHO, LE, H = 0.5, 4.0, 2.0
-LX, LZ = (-1.0, 1.0), (-1.0, 1.0)
-
-
-def analytic_scene(rtmi, w=64, h=36, spp=256):
-    sc = rtmi.Scene.new(w, h, spp, 2)  # camera -> floor -> light: the direct term alone
-    sc.set_background((0, 0, 0), sky_gradient=False, defocus_blur=False)
-    sc.camera((2.5, 1.2, -1.5), (2.5, 0.0, 0.0), (0, 1, 0), 50.0)
-    sc.xz_rect(-50, 50, -50, 50, 0.0, sc.lambertian((RHO, RHO, RHO)))
-    sc.xz_rect(LX[0], LX[1], LZ[0], LZ[1], H, sc.diffuse_light((LE, LE, LE)))
-    return sc
-
-
-def _ff_corner(a, b, h):
-    """form factor from a point to a parallel rectangle [0, a] x [0, b] at height h above it (signed for a, b < 0)"""
-    A, B = np.abs(a) / h, np.abs(b) / h
-    f = (A / np.sqrt(1 + A * A) * np.arctan(B / np.sqrt(1 + A * A)) + B / np.sqrt(1 + B * B) * np.arctan(A / np.sqrt(1 + B * B)))
-    return np.sign(a) * np.sign(b) * f / (2 * np.pi)
-
-
-def analytic_expected(sc, q=6):
-    """rho L F(P) averaged over each pixel's footprint (q x q jitter quadrature); NaN where a ray misses the floor"""
-    cam = sc.get_camera()
-    org, ll = np.array(cam.origin, np.float64), np.array(cam.lower_left, np.float64)
-    hor, ver = np.array(cam.horizontal, np.float64), np.array(cam.vertical, np.float64)
-    W, Hh = sc.width, sc.height
-    xi = (np.arange(q) + 0.5) / q
-    u = (np.arange(W)[None, :, None, None] + xi[None, None, :, None]) / (W - 1)
-    v = (np.arange(Hh)[:, None, None, None] + xi[None, None, None, :]) / (Hh - 1)
-    d = ll + u[..., None] * hor + v[..., None] * ver - org
-    t = -org[1] / d[..., 1]
-    px, pz = org[0] + t * d[..., 0], org[2] + t * d[..., 2]
-    F = (_ff_corner(LX[1] - px, LZ[1] - pz, H) - _ff_corner(LX[0] - px, LZ[1] - pz, H)
-         - _ff_corner(LX[1] - px, LZ[0] - pz, H) + _ff_corner(LX[0] - px, LZ[0] - pz, H))
-    val = RHO * LE * F
-    val[~(t > 0)] = np.nan
-    return val.mean(axis=(2, 3))
 
 
 def _mean(sc, img):
@@ -93,33 +55,6 @@ def test_analytic_known_answer(rtmi):
 # ---- unbiasedness against the plain estimator ----------------------------------------------------------------------------
 MATERIALS = ["lambert", "checker", "metal0.3", "metal1.0"]
 LIGHTS = ["xy", "xz", "yz", "sphere", "cylinder"]
-
-
-def pair_scene(rtmi, mat, light, w=64, h=36, spp=256, depth=6):
-    sc = rtmi.Scene.new(w, h, spp, depth)
-    sc.set_background((0.02, 0.02, 0.03), sky_gradient=False, defocus_blur=False)
-    sc.camera((0.0, 2.5, 6.0), (0.0, 0.5, 0.0), (0, 1, 0), 45.0)
-    if mat == "lambert":
-        m = sc.lambertian((0.6, 0.5, 0.4))
-    elif mat == "checker":
-        m = sc.lambertian(sc.checker_texture((0.8, 0.8, 0.8), (0.1, 0.3, 0.1)))
-    else:
-        m = sc.metal((0.8, 0.7, 0.6), float(mat[5:]))
-    sc.xz_rect(-20, 20, -20, 20, 0.0, m)
-    sc.sphere((-1.2, 0.6, 0.5), 0.6, sc.lambertian((0.3, 0.5, 0.7)))
-    sc.sphere((1.3, 0.5, 0.8), 0.5, m)
-    e = sc.diffuse_light((6.0, 5.0, 4.0))
-    if light == "xy":
-        sc.xy_rect(-0.5, 0.5, 1.0, 2.0, -1.5, e)
-    elif light == "xz":
-        sc.xz_rect(-0.6, 0.6, -0.6, 0.6, 2.5, e)
-    elif light == "yz":
-        sc.yz_rect(0.5, 1.5, -0.5, 0.5, 2.5, e)
-    elif light == "sphere":
-        sc.sphere((0.3, 2.2, -0.5), 0.3, e)
-    else:
-        sc.cylinder(0.15, -0.8, 0.8, e, rotate=((1.0, 0.3, 0.2), 70.0), translate=(0.2, 1.8, -0.6))
-    return sc
 
 
 def shipped(rtmi, path, w=64, h=36, spp=256, depth=None):
@@ -195,24 +130,6 @@ def test_variance_ratio_analytic(rtmi):
 
 
 # ---- bit-exact invariants with light sampling on -------------------------------------------------------------------------
-def many_lights(rtmi, w=64, h=36, spp=32):
-    rng = np.random.default_rng(3)
-    sc = rtmi.Scene.new(w, h, spp, 8)
-    sc.set_background((0.0, 0.0, 0.0), sky_gradient=False, defocus_blur=False)
-    sc.camera((0, 6, 14), (0, 0, 0), (0, 1, 0), 45.0)
-    sc.xz_rect(-30, 30, -30, 30, 0.0, sc.lambertian(sc.checker_texture((0.7, 0.7, 0.7), (0.2, 0.2, 0.2))))
-    for i in range(200):
-        c = (float(rng.uniform(-8, 8)), float(rng.uniform(0.2, 3)), float(rng.uniform(-8, 4)))
-        if i % 3 == 0:
-            sc.sphere(c, 0.15, sc.diffuse_light(tuple(float(x) for x in rng.uniform(1, 6, 3))))
-        elif i % 3 == 1:
-            sc.sphere(c, 0.2, sc.lambertian(tuple(float(x) for x in rng.uniform(0.2, 0.9, 3))))
-        else:
-            sc.xy_rect(c[0], c[0] + 0.3, c[1], c[1] + 0.3, c[2], sc.diffuse_light((3.0, 2.0, 1.0)))
-    sc.set_light_sampling(True)
-    return sc
-
-
 def mixed(rtmi, spp=32):
     sc = rtmi.Scene.load(os.path.join(SCENES, "mixed_emissive.json"))
     sc.override(64, 36, spp)
