@@ -237,6 +237,44 @@ int rt_scene_get_environment(const rt_scene *s, int *rows, int *cols, float *sca
  * radiance and density eval gives that direction (pdf 0 when the map has nothing to sample). */
 int rt_environment_eval(const rt_scene *s, const float dir[3], float rgb[3], float *pdf);
 int rt_environment_sample(const rt_scene *s, float u1, float u2, float dir[3], float rgb[3], float *pdf);
+
+/* ---- homogeneous participating media (fog, smoke) ----------------
+ * Up to RT_MAX_MEDIA media per scene, a list of its own: media are not primitives (not in rt_scene_get_prims, not in the
+ * grid, they occlude nothing) and leave the primitive part of the packed tables alone.  A medium is a boundary -- a sphere
+ * or an axis-aligned box -- filled with a density sigma >= 0 per unit world length and an albedo in [0, 1]^3; scattering is
+ * isotropic.  After every closest-hit query (ray o + t d, surface winner t_s, +inf on a miss) the media are walked in list
+ * order: [a, b] = the ray's stay inside the boundary clipped to [0.001, t_s]; an empty interval, or sigma = 0, takes no random
+ * draw; otherwise ONE draw u and t = a + (-ln(1 - u) / sigma) / |d|, an event if t < b.  The smallest event t (the earlier
+ * medium at equal t) wins over the surface hit: a vertex that costs one unit of depth, multiplies the throughput by the albedo,
+ * emits nothing, and goes on from o + t d in the direction of a uniform point of the unit sphere (the lambertian's rejection
+ * loop, three draws per attempt, normalised).  Nothing is remembered between queries, so cameras and vertices inside media,
+ * overlapping media (the summed-density process) and media inside glass shells need nothing more.  Russian roulette keeps
+ * its draw before the query.
+ * A scene with media gets the wide tables and renders through kernels of its own (rt_opts.variant 0, 16, 36 or 44;
+ * rt_stats.kernel_variant reports layout | 2048) through every render entry point.  Refused with RT_ERR_ARG: media together
+ * with light sampling that has something to sample, with an environment map, or with nested cells; rt_render_hip_count; any
+ * other variant.  Feature passes (rt_render_hip_feature) ignore media: they record the first SURFACE hit, so the denoiser's
+ * guides do not see fog.
+ * Errors of the add calls: RT_ERR_ARG null pointers; RT_ERR_SCENE a negative or non-finite density, an albedo outside [0, 1],
+ * a radius <= 0 or non-finite bounds, a box with min >= max on an axis; RT_ERR_LIMIT the 17th medium.
+ * JSON: top-level "media": {"data": [{"type": "sphere", "center", "radius", "density", "albedo"},
+ * {"type": "box", "min", "max", "density", "albedo"}]}. */
+#define RT_MAX_MEDIA 16
+typedef enum rt_medium_shape { RT_MEDIUM_SPHERE = 0, RT_MEDIUM_BOX = 1 } rt_medium_shape;
+typedef struct rt_medium {
+    int32_t shape;   /* rt_medium_shape */
+    float f[6];      /* sphere {cx, cy, cz, r}; box {min.xyz, max.xyz} */
+    float density;
+    float albedo[3];
+} rt_medium;
+int rt_scene_add_medium_sphere(rt_scene *s, const float center[3], float radius, float density, const float albedo[3]); /* -> medium id, or -rt_status */
+int rt_scene_add_medium_box(rt_scene *s, const float bmin[3], const float bmax[3], float density, const float albedo[3]);
+int rt_scene_get_media(const rt_scene *s, rt_medium *out, int cap); /* -> count, or -rt_status */
+int rt_scene_clear_media(rt_scene *s);
+/* Host evaluation of the device's interval formula (no GPU needed): the part of the ray o + t d inside the boundary, clipped to
+ * [0.001, t_max].  1: non-empty (a < b), with *t_in = a and *t_out = b; 0: empty; -RT_ERR_ARG for null arguments or a shape
+ * that is neither a sphere nor a box. */
+int rt_medium_interval(const rt_medium *m, const float orig[3], const float dir[3], float t_max, float *t_in, float *t_out);
 /* camera(lookfrom, lookat, vup, vfov, aspect, aperture, focus_dist) camera.cuh:9-15;
  * aspect <= 0 -> width/height, focus_dist <= 0 -> |lookfrom-lookat| (parser.hpp:122-124) */
 int rt_scene_set_camera(rt_scene *s, const float lookfrom[3], const float lookat[3],
@@ -323,7 +361,7 @@ typedef struct rt_table_info {
     int32_t off_rect_hot, off_cyl_hot, off_tri_hot;
     int32_t hot_bytes_grid;    /* what a grid-walk kernel stages into LDS */
     int32_t kernel_variant;    /* what rt_opts.variant = 0 renders this scene with (2, 6, 16, 36, 44 or 52; | 256 light sampling,
-                                  | 1024 an environment map) */
+                                  | 1024 an environment map, | 2048 participating media) */
 } rt_table_info;
 int rt_scene_table_info(const rt_scene *s, rt_table_info *out);
 /* The nested cells of the scene's tables (rt_scene_set_nested_grid); all zero while the tables are flat.  A nested cell's header
@@ -530,7 +568,7 @@ const char *rt_status_string(int status);
 int rt_abi_version(void);
 /* sizeof of the ABI structs as this library was compiled (binding self-checks):
  * 0 rt_opts, 1 rt_stats, 2 rt_prim, 3 rt_material, 4 rt_texture, 5 rt_camera, 6 rt_scene_info, 7 rt_table_info,
- * 8 rt_adaptive, 9 rt_adaptive_stats, 10 rt_nested_info, 16 rt_denoise; else 0 */
+ * 8 rt_adaptive, 9 rt_adaptive_stats, 10 rt_nested_info, 16 rt_denoise, 17 rt_medium; else 0 */
 size_t rt_struct_size(int which);
 /* number of usable gfx950 devices, or -rt_status */
 int rt_device_count(void);

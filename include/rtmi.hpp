@@ -98,6 +98,26 @@ inline material_ptr diffuse_light(std::shared_ptr<mytexture> a) {  // material.c
 }
 inline material_ptr diffuse_light(color c) { return diffuse_light(solid_color(c)); }  // material.cuh:166-167
 
+// ---- participating media (include/rtmi.h: homogeneous media, isotropic scattering) ------------
+// constant_medium(boundary, density, albedo): the boundary is a sphere (centre, radius) or an axis-aligned box (min, max)
+struct constant_medium {
+    rt_medium rec{};
+    constant_medium(point3 cen, float radius, float density, color albedo) {
+        rec.shape = RT_MEDIUM_SPHERE, rec.f[0] = cen.x(), rec.f[1] = cen.y(), rec.f[2] = cen.z(), rec.f[3] = radius;
+        fill(density, albedo);
+    }
+    constant_medium(point3 bmin, point3 bmax, float density, color albedo) {
+        rec.shape = RT_MEDIUM_BOX, rec.f[0] = bmin.x(), rec.f[1] = bmin.y(), rec.f[2] = bmin.z();
+        rec.f[3] = bmax.x(), rec.f[4] = bmax.y(), rec.f[5] = bmax.z();
+        fill(density, albedo);
+    }
+
+private:
+    void fill(float density, color albedo) {
+        rec.density = density, rec.albedo[0] = albedo.x(), rec.albedo[1] = albedo.y(), rec.albedo[2] = albedo.z();
+    }
+};
+
 // ---- hittables (object.cuh) ------------------------------------------------------------------
 struct hittable {
     int type = RT_PRIM_SPHERE;
@@ -189,6 +209,22 @@ public:
                                   c.focus_dist),
               "camera");
     }
+    // a medium joins the scene's media list (not the hittable list) -> its id
+    int add(const constant_medium &m) {
+        const rt_medium &r = m.rec;
+        const int id = r.shape == RT_MEDIUM_SPHERE ? rt_scene_add_medium_sphere(s_, r.f, r.f[3], r.density, r.albedo)
+                                                   : rt_scene_add_medium_box(s_, r.f, r.f + 3, r.density, r.albedo);
+        if (id < 0) throw error(-id, "add(constant_medium)");
+        return id;
+    }
+    std::vector<rt_medium> media() const {
+        const int n = rt_scene_get_media(s_, nullptr, 0);
+        if (n < 0) throw error(-n, "media");
+        std::vector<rt_medium> out((size_t)n);
+        if (n > 0) rt_scene_get_media(s_, out.data(), n);
+        return out;
+    }
+    void clear_media() { check(rt_scene_clear_media(s_), "clear_media"); }
     // hittable_list::add
     int add(const hittable &h) {
         if (!h.mat) throw std::logic_error("hittable without a material");

@@ -51,6 +51,10 @@ MATERIAL_DTYPE = np.dtype(
 )
 TEXTURE_DTYPE = np.dtype([("type", "<i4"), ("c0", "<f4", (3,)), ("c1", "<f4", (3,))])
 LIGHT_ENVIRONMENT = 100  # rt_light.shape of the environment map (RT_LIGHT_ENVIRONMENT)
+MEDIUM_SPHERE, MEDIUM_BOX = 0, 1  # rt_medium.shape
+MEDIUM_DTYPE = np.dtype(  # rt_medium: sphere f = {cx, cy, cz, r}; box f = {min.xyz, max.xyz}
+    [("shape", "<i4"), ("f", "<f4", (6,)), ("density", "<f4"), ("albedo", "<f4", (3,))]
+)
 LIGHT_DTYPE = np.dtype(
     [("prim", "<i4"), ("shape", "<i4"), ("probability", "<f4"), ("area", "<f4"), ("emission", "<f4", (3,)),
      ("emission_odd", "<f4", (3,))]
@@ -240,6 +244,11 @@ _sig("rt_scene_get_environment", C.c_int, _p, C.POINTER(C.c_int), C.POINTER(C.c_
      C.c_size_t)
 _sig("rt_environment_eval", C.c_int, _p, _f3, _f3, C.POINTER(C.c_float))
 _sig("rt_environment_sample", C.c_int, _p, C.c_float, C.c_float, _f3, _f3, C.POINTER(C.c_float))
+_sig("rt_scene_add_medium_sphere", C.c_int, _p, _f3, C.c_float, C.c_float, _f3)
+_sig("rt_scene_add_medium_box", C.c_int, _p, _f3, _f3, C.c_float, _f3)
+_sig("rt_scene_get_media", C.c_int, _p, _p, C.c_int)
+_sig("rt_scene_clear_media", C.c_int, _p)
+_sig("rt_medium_interval", C.c_int, _p, _f3, _f3, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float))
 _sig("rt_scene_set_nested_grid", C.c_int, _p, C.c_int)
 _sig("rt_scene_get_nested_grid", C.c_int, _p)
 _sig("rt_scene_nested_info", C.c_int, _p, C.POINTER(NestedInfo))
@@ -285,6 +294,7 @@ C_SYMBOLS = [
     "rt_scene_set_nested_grid", "rt_scene_get_nested_grid", "rt_scene_nested_info",
     "rt_scene_set_environment", "rt_scene_set_environment_file", "rt_scene_get_environment", "rt_environment_eval",
     "rt_environment_sample",
+    "rt_scene_add_medium_sphere", "rt_scene_add_medium_box", "rt_scene_get_media", "rt_scene_clear_media", "rt_medium_interval",
     "rt_render_hip_feature", "rt_render_hip_feature_device", "rt_denoise_hip", "rt_denoise_hip_device",
 ]
 
@@ -378,6 +388,22 @@ class Scene:
             raise ValueError("environment: a rows x cols x 3 array")
         _check(_lib.rt_scene_set_environment(self._h, a.shape[0], a.shape[1], a.ctypes.data_as(C.c_void_p), float(scale), float(rotate)),
                "set_environment")
+
+    def add_medium_sphere(self, center, radius: float, density: float, albedo=(1.0, 1.0, 1.0)) -> int:
+        """A homogeneous medium inside a sphere (include/rtmi.h, participating media): density per unit length, isotropic
+        scattering with the given albedo.  Returns the medium's id."""
+        return _check_id(_lib.rt_scene_add_medium_sphere(self._h, _v3(center), float(radius), float(density), _v3(albedo)), "add_medium_sphere")
+
+    def add_medium_box(self, bmin, bmax, density: float, albedo=(1.0, 1.0, 1.0)) -> int:
+        """A homogeneous medium inside an axis-aligned box."""
+        return _check_id(_lib.rt_scene_add_medium_box(self._h, _v3(bmin), _v3(bmax), float(density), _v3(albedo)), "add_medium_box")
+
+    def media(self) -> np.ndarray:
+        """The scene's media in list order (MEDIUM_DTYPE records)."""
+        return self._table(_lib.rt_scene_get_media, MEDIUM_DTYPE)
+
+    def clear_media(self):
+        _check(_lib.rt_scene_clear_media(self._h), "clear_media")
 
     @property
     def environment(self):
@@ -789,6 +815,17 @@ def sample_stream(seed, pixel, sample, n):
     out = (C.c_uint32 * n)()
     _lib.rt_sample_stream(seed, pixel, sample, out, n)
     return list(out)
+
+
+def medium_interval(medium, orig, direction, t_max=float("inf")):
+    """Host evaluation of the device's interval formula: the stay of the ray orig + t direction inside the boundary of
+    ``medium`` (a MEDIUM_DTYPE record) clipped to [0.001, t_max] -> (non-empty, t_in, t_out)."""
+    rec = np.zeros(1, MEDIUM_DTYPE)
+    rec[0] = medium
+    a, b = C.c_float(), C.c_float()
+    rc = _check_id(_lib.rt_medium_interval(rec.ctypes.data_as(C.c_void_p), _v3(orig), _v3(direction), float(t_max), C.byref(a), C.byref(b)),
+                   "medium_interval")
+    return bool(rc), a.value, b.value
 
 
 def aabb_hit(bmin, bmax, orig, direction, t_min, t_max) -> bool:

@@ -10,6 +10,7 @@
 
 #include "philox.h"
 #include "rt_env.h"
+#include "rt_media.h"
 #include "scene.hpp"
 
 using namespace rtmi;
@@ -52,6 +53,7 @@ size_t rt_struct_size(int which) {
     case 9: return sizeof(rt_adaptive_stats);
     case 10: return sizeof(rt_nested_info);
     case 16: return sizeof(rt_denoise);  // (11 .. 15 stay 0: the next structs of the scene / render interface)
+    case 17: return sizeof(rt_medium);
     default: return 0;
     }
 }
@@ -734,6 +736,65 @@ int rt_aabb_hit(const float bmin[3], const float bmax[3], const float orig[3], c
         if (t_max <= t_min) return 0;
     }
     return 1;
+}
+
+// ---- homogeneous media: the scene interface and the host evaluation of the device's interval (rt_media.h)
+int rt_scene_add_medium_sphere(rt_scene *s, const float center[3], float radius, float density, const float albedo[3]) {
+    if (!s || !center || !albedo) {
+        set_error("rt_scene_add_medium_sphere: null argument");
+        return -RT_ERR_ARG;
+    }
+    rt_medium m;
+    memset(&m, 0, sizeof m);
+    m.shape = RT_MEDIUM_SPHERE;
+    for (int k = 0; k < 3; ++k) m.f[k] = center[k], m.albedo[k] = albedo[k];
+    m.f[3] = radius, m.density = density;
+    return add_medium(s->s, m);
+}
+
+int rt_scene_add_medium_box(rt_scene *s, const float bmin[3], const float bmax[3], float density, const float albedo[3]) {
+    if (!s || !bmin || !bmax || !albedo) {
+        set_error("rt_scene_add_medium_box: null argument");
+        return -RT_ERR_ARG;
+    }
+    rt_medium m;
+    memset(&m, 0, sizeof m);
+    m.shape = RT_MEDIUM_BOX;
+    for (int k = 0; k < 3; ++k) m.f[k] = bmin[k], m.f[3 + k] = bmax[k], m.albedo[k] = albedo[k];
+    m.density = density;
+    return add_medium(s->s, m);
+}
+
+int rt_scene_get_media(const rt_scene *s, rt_medium *out, int cap) {
+    if (bad_scene(s, "rt_scene_get_media")) return -RT_ERR_ARG;
+    for (int i = 0; out && i < cap && i < (int)s->s.media.size(); ++i) out[i] = s->s.media[(size_t)i];
+    return (int)s->s.media.size();
+}
+
+int rt_scene_clear_media(rt_scene *s) {
+    if (bad_scene(s, "rt_scene_clear_media")) return RT_ERR_ARG;
+    if (!s->s.media.empty()) {  // (a scene without media stays the scene it was: same version, same tables)
+        s->s.media.clear();
+        s->s.touch();
+    }
+    return RT_OK;
+}
+
+int rt_medium_interval(const rt_medium *m, const float orig[3], const float dir[3], float t_max, float *t_in, float *t_out) {
+    if (!m || !orig || !dir) {
+        set_error("rt_medium_interval: null argument");
+        return -RT_ERR_ARG;
+    }
+    if (m->shape != RT_MEDIUM_SPHERE && m->shape != RT_MEDIUM_BOX) {
+        set_error("rt_medium_interval: shape %d (0 sphere, 1 box)", m->shape);
+        return -RT_ERR_ARG;
+    }
+    float a, b;
+    const bool hit = medium_interval(m->shape, m->f[0], m->f[1], m->f[2], m->f[3], m->f[4], m->f[5], orig[0], orig[1], orig[2], dir[0],
+                                     dir[1], dir[2], t_max, a, b);
+    if (t_in) *t_in = a;
+    if (t_out) *t_out = b;
+    return hit ? 1 : 0;
 }
 
 // ---- environment map: the scene interface and the host evaluations of the device functions of rt_env.h (no GPU needed)

@@ -26,6 +26,8 @@
 //     slot    [ns + nr + nc + nt] one 32-bit word per grouped primitive id: its light, -1 = not a sampled light
 //     (an environment that is sampled is the last light: {3, -1, selection probability, 1 / 4 pi}, no geometry)
 //   ENVIRONMENT part (only with an environment map; global memory, read by the environment kernels): rt_env.h
+//   MEDIA part (only with at least one medium; global memory, read by the media kernels): rt_media.h.  Two words of the camera
+//     block say where it lies ({count, offset} in the .w of records off_cam + 1 and + 2; zero without media)
 //
 // Primitives are grouped by type (spheres, rects, cylinders), each group in list
 // order; the original list index is kept for the reference's tie rule (a later
@@ -74,7 +76,8 @@ enum MatKind : int32_t {
     MK_DIELECTRIC = 4,       // p0 = ir, p1 = 1/ir, p2 = r0(1/ir), p3 = r0(ir)
     MK_LIGHT_SOLID = 5,      // c0 = emission
     MK_LIGHT_CHECKER = 6,    // c0 = even, c1 = odd
-    MK_LIGHT_IMAGE = 7       // as MK_LAMBERT_IMAGE
+    MK_LIGHT_IMAGE = 7,      // as MK_LAMBERT_IMAGE
+    MK_MEDIUM = 8            // a medium event of the media kernels (rt_media.h): no material record, `mat` is the medium's index
 };
 
 // Per-launch values the kernel needs only when a wave fetches or flushes a work item.  They live in global

@@ -12,6 +12,7 @@
 #include <utility>
 
 #include "pack.h"
+#include "rt_media.h"
 
 namespace rtmi {
 namespace {
@@ -661,7 +662,8 @@ int lay_out_hot(RenderParams &L, const Grid &g) {
 
 // Every offset of the image, in image order: the one place that says what the image looks like.  Returns the record count;
 // image_word[k]: the first 32-bit word of image texture k's texels.
-int lay_out_image(RenderParams &L, const Grid &g, const Scene &s, std::vector<int> &image_word) {
+// off_media: the first record of the MEDIA part (rt_media.h; 0: the scene has no media).
+int lay_out_image(RenderParams &L, const Grid &g, const Scene &s, std::vector<int> &image_word, int &off_media) {
     int off = lay_out_hot(L, g);
     L.hot_vec4_grid = off;  // what the grid-walk kernels stage into LDS
     // the boxes of the cluster searches (ablation builds) lie behind the grid tables, so that the grid walk does not stage
@@ -713,6 +715,12 @@ int lay_out_image(RenderParams &L, const Grid &g, const Scene &s, std::vector<in
         if (end + 4 > (long long)INT32_MAX) return -1;
         L.off_env_tex = (int)tex, L.off_env_marg = (int)marg, L.off_env_cond = (int)cond, L.off_env_band = (int)band, L.off_env_ct = (int)ct;
         off = (int)((end + 3) / 4);
+    }
+    // the MEDIA part (rt_media.h): the media's records, behind everything else; global memory only, read by the media kernels
+    off_media = 0;
+    if (!s.media.empty()) {
+        off_media = off;
+        off += RT_MEDIUM_STRIDE * (int)s.media.size();
     }
     return off;
 }
@@ -1047,6 +1055,23 @@ void write_lights(float *I, const RenderParams &L, const Scene &s, const SphereS
     }
 }
 
+// the media's records, and in the camera block how many there are and where (rt_media.h)
+void write_media(float *I, const RenderParams &L, const Scene &s, int off_media) {
+    const int32_t n = (int32_t)s.media.size(), off = off_media;
+    memcpy(rec4(I, L.off_cam + 1) + 3, &n, 4);
+    memcpy(rec4(I, L.off_cam + 2) + 3, &off, 4);
+    for (int i = 0; i < n; ++i) {
+        const rt_medium &m = s.media[(size_t)i];
+        float *r0 = rec4(I, off_media + RT_MEDIUM_STRIDE * i), *r1 = r0 + 4, *r2 = r0 + 8;
+        for (int k = 0; k < 4; ++k) r0[k] = m.f[k];
+        for (int c = 0; c < 3; ++c) r1[c] = m.albedo[c];
+        r1[3] = m.density;
+        r2[0] = m.f[4], r2[1] = m.f[5];
+        memcpy(r2 + 2, &m.shape, 4);
+        r2[3] = 0.0f;
+    }
+}
+
 // the environment's texels and sampling tables, as the host evaluation reads them
 void write_environment(float *I, const RenderParams &L, const Scene &s) {
     const SceneEnvironment &e = *s.env;
@@ -1096,8 +1121,8 @@ bool pack_round(const Scene &s, std::vector<char> &forced, std::vector<float> &i
     L.nl = (int)lights.size();
 
     Grid g;
-    // (an environment, like light sampling, runs in general kernels of its own: wide tables)
-    const bool wide = !sphere_only || S.ns() >= 65536 || !lights.empty() || s.env || nest_over > 0 || knob_set("RTMI_FORCE_WIDE");  // (the knob: measurement)
+    // (an environment and media, like light sampling, run in general kernels of their own: wide tables)
+    const bool wide = !sphere_only || S.ns() >= 65536 || !lights.empty() || s.env || !s.media.empty() || nest_over > 0 || knob_set("RTMI_FORCE_WIDE");  // (the knob: measurement)
     const bool built = build_grid(s, S, O, L, wide, forced, g, nest_over, nest_cap);
     note.demoted = note.demoted || g.demoted;
     if (!built) return false;
@@ -1107,7 +1132,8 @@ bool pack_round(const Scene &s, std::vector<char> &forced, std::vector<float> &i
     L.grid_wide = g.wide ? (nested ? 2 : 1) : 0;
     L.grid_sheet = (!g.cells.empty() && g.n[1] == 1 && !g.wide) ? 1 : 0;
     std::vector<int> image_word;
-    const int records = lay_out_image(L, g, s, image_word);
+    int off_media = 0;
+    const int records = lay_out_image(L, g, s, image_word, off_media);
     if (records < 0) {
         note.too_large = true;
         return true;
@@ -1132,6 +1158,7 @@ bool pack_round(const Scene &s, std::vector<char> &forced, std::vector<float> &i
     write_materials(I, L, s, S, O, image_word);
     if (L.nl > 0) write_lights(I, L, s, S, O, lights);
     if (s.env) write_environment(I, L, s);
+    if (!s.media.empty()) write_media(I, L, s, off_media);
     note.nested = NestedInfo();
     if (nested) {
         note.nested.cells = (int)(g.subs.size() / 16);

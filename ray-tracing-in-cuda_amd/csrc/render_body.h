@@ -1,5 +1,5 @@
 // The body of the render kernels (render_kernel.hip): included INSIDE render_kernel, render_nee_kernel, render_nested_kernel,
-// render_feature_kernel and render_env_kernel (render_env.hip), after their template arguments and a constexpr NEE, AOV and ENV.  As text rather than a force-inlined device function, so that the render_kernel
+// render_feature_kernel and render_env_kernel (render_env.hip), after their template arguments and a constexpr NEE, AOV, ENV and MEDIA (render_media_kernel, render_media.hip, is the one with MEDIA on).  As text rather than a force-inlined device function, so that the render_kernel
 // instances compile to the very instructions they did before light sampling came (a device function that takes the
 // kernel's parameters by reference changes the order of the kernel-argument loads and with it the register allocation).
 // Not a header of its own: it needs the kernel's scope (P, image, acc, queue, counters and the template arguments).
@@ -945,6 +945,29 @@
             // ---- (2) the winner (ray_color body, main.cu:45-65 / main.cpp:22-38)
             // 1/|d| once per query (metal, dielectric and the sky all normalise the direction)
             inv_len = 1.0f / rt_sqrtf(ra);
+            // MEDIA: the media walk of a finished query.  The media -- records behind a count and an offset in the camera
+            // block, all wave-uniform reads from global memory -- in list order: the ray's stay [a, b] inside the boundary up to
+            // the surface winner; a non-empty stay in a medium of positive density takes ONE draw, the free-flight distance.
+            // The smallest event wins over the surface hit.  What outlives the walk: med_t and med_i.
+            float med_t = INFINITY;
+            int med_i = -1;
+            if constexpr (MEDIA) {
+                if (!unfinished) {
+                    const int n_med = __builtin_amdgcn_readfirstlane(__float_as_int(image[P.off_cam + 1].w));
+                    const float4 *med = image + __builtin_amdgcn_readfirstlane(__float_as_int(image[P.off_cam + 2].w));
+                    const float len = rt_sqrtf(ra);
+                    for (int m = 0; m < n_med; ++m) {
+                        const float4 g0 = med[RT_MEDIUM_STRIDE * m], g1 = med[RT_MEDIUM_STRIDE * m + 1], g2 = med[RT_MEDIUM_STRIDE * m + 2];
+                        float ta, tb;
+                        if (g1.w > 0.0f &&
+                            medium_interval(__float_as_int(g2.z), g0.x, g0.y, g0.z, g0.w, g2.x, g2.y, ox, oy, oz, dx, dy, dz, best_t, ta, tb)) {
+                            const float u = rng_next<COUNT>(rng);
+                            const float t = ta + (-logf(1.0f - u) / g1.w) / len;
+                            if (t < tb && t < med_t) med_t = t, med_i = m;
+                        }
+                    }
+                }
+            }
             if (unfinished) {
             } else if (NEE && shadow != 0) {
                 // the shadow query's verdict: the light sample counts when nothing lies between the vertex and its light
@@ -956,6 +979,13 @@
                 ra = dot3(dx, dy, dz, dx, dy, dz);
                 rinv_a = 1.0f / ra;
                 shadow = 0;
+            } else if (MEDIA && med_i >= 0) {
+                // a medium event: a vertex without a normal and without a material record (the scatter step takes the albedo
+                // from the medium's record), which emits nothing
+                px = fmaf(med_t, dx, ox), py = fmaf(med_t, dy, oy), pz = fmaf(med_t, dz, oz);
+                nx = ny = nz = 0.0f;
+                mat = med_i;
+                kind = MK_MEDIUM;
             } else if (best_id >= 0) {
                 // hit record of the winner only (the reference fills one per candidate)
                 if (SPH || best_id < ns) {
@@ -1309,7 +1339,7 @@
         // ---- (5) rejection sampling, one converged loop: random_in_unit_sphere (vec3.h:121-129: three draws, for the
         // lanes whose material scatters with one: lambertian, metal) and random_in_unit_disk (vec3.h:157-165: two
         // draws, for the lens sample of the paths that start)
-        const bool need_s = kind >= 0 && kind <= MK_METAL;
+        const bool need_s = (kind >= 0 && kind <= MK_METAL) || (MEDIA && kind == MK_MEDIUM);
         const bool need_d = started && (P.flags & RT_FLAG_DEFOCUS_BLUR) != 0u;
         float sx = 0, sy = 0, sz = 0, sl2 = 1;
         if (need_s || need_d) {
@@ -1345,11 +1375,14 @@
         float vb_r = 0, vb_g = 0, vb_b = 0, mrx = 0, mry = 0, mrz = 0, mfz = 0;
         if (kind >= 0) {
             const float4 *M = image + P.off_mat + 3 * mat;
+            if constexpr (MEDIA) {  // (a medium's record 1 is {albedo, density}: where a material keeps c0)
+                if (kind == MK_MEDIUM) M = image + __builtin_amdgcn_readfirstlane(__float_as_int(image[P.off_cam + 2].w)) + RT_MEDIUM_STRIDE * mat;
+            }
             const float4 q0 = M[0], q1 = M[1], q2 = M[2];
                 float ndx, ndy, ndz;           // scattered direction
                 float at_r, at_g, at_b;        // attenuation
                 bool scattered = true;
-                if (kind <= MK_LAMBERT_IMAGE) {  // lambertian::scatter, material.h:25-35
+                if (kind <= MK_LAMBERT_IMAGE || (MEDIA && kind == MK_MEDIUM)) {  // lambertian::scatter, material.h:25-35 (MEDIA: a medium vertex, n = 0)
                     const float inv = 1.0f / rt_sqrtf(sl2);
                     ndx = nx + inv * sx, ndy = ny + inv * sy, ndz = nz + inv * sz;
                     const float eps = 1e-8f;

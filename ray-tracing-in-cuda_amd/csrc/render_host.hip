@@ -38,6 +38,10 @@ bool launch_render_env(const RenderParams &P, const void *image, unsigned long l
                        unsigned grid, hipStream_t stream, unsigned layout, bool nee, bool feature);
 bool layout_has_env(unsigned layout);
 int blocks_per_cu_env(unsigned layout, size_t lds_bytes, bool nee, bool feature);
+bool launch_render_media(const RenderParams &P, const void *image, unsigned long long *acc, unsigned int *queue, size_t lds_bytes,
+                         unsigned grid, hipStream_t stream, unsigned layout);
+bool layout_has_media(unsigned layout);
+int blocks_per_cu_media(unsigned layout, size_t lds_bytes);
 bool variant_has_ext(unsigned variant);
 bool variant_has_count(unsigned variant);
 bool has_ablations();
@@ -320,6 +324,7 @@ static int read_tables(const rt_scene *sc, rt_table_info *out, float *dst, int c
     out->kernel_variant = (int32_t)pick_variant(L, false, (size_t)knob("RTMI_GLOBAL_TABLE_BYTES", (double)kLdsTableBytes));
     if (L.nl > 0) out->kernel_variant |= 256;  // light sampling: the layout's light-sampling kernel
     if (L.env_rows > 0) out->kernel_variant |= 1024;  // an environment map: the layout's environment kernel
+    if (!sc->s.media.empty()) out->kernel_variant |= 2048;  // media: the layout's media kernel
     if (dst && cap_floats > 0) memcpy(dst, cache.image.data(), sizeof(float) * std::min((size_t)cap_floats, cache.image.size()));
     return RT_OK;
 }
@@ -451,6 +456,7 @@ struct Launcher {
     bool ext, nee, count;
     bool env;     // an environment map: render_env_kernel of layout `variant` (plain, light sampling or feature pass)
     int feature;  // >= 0: a feature pass (render_feature_kernel of layout `variant`)
+    bool media;   // homogeneous media: render_media_kernel of layout `variant` (never with nee, env or a feature pass)
 
     int enqueue(unsigned long long *acc, unsigned int *d_queue, int first, int n, int n_list, const ChunkPlan &pl) const {
         RenderParams Q = P;
@@ -482,6 +488,13 @@ struct Launcher {
             if (feature >= 0) Q.feature = feature;
             if (!launch_render_env(Q, ent->d_image, acc, d_queue, lds_bytes, (unsigned)grid, stream, variant, nee, feature >= 0)) {
                 set_error("layout %u has no environment kernel", variant);
+                return RT_ERR_ARG;
+            }
+            return RT_OK;
+        }
+        if (media) {
+            if (!launch_render_media(Q, ent->d_image, acc, d_queue, lds_bytes, (unsigned)grid, stream, variant)) {
+                set_error("layout %u has no media kernel", variant);
                 return RT_ERR_ARG;
             }
             return RT_OK;
@@ -670,6 +683,12 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
         set_error("unknown kernel variant %u%s", variant, has_ablations() ? "" : " (this library was built without the measurement variants: make ABLATIONS=1)");
         return RT_ERR_ARG;
     }
+    // homogeneous media: kernels of their own; a feature pass ignores them (the first SURFACE hit)
+    const bool media = !s.media.empty() && feature < 0;
+    if (media && count) {
+        set_error("rt_render_hip_count: this scene has participating media, which the counting kernels do not carry");
+        return RT_ERR_ARG;
+    }
     if (count && !has_ablations()) {
         set_error("rt_render_hip_count: this library was built without the counting kernels (make ABLATIONS=1)");
         return RT_ERR_LIMIT;
@@ -767,6 +786,24 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     }
     // an environment map: kernels of their own, for the general layouts
     const bool env = P.env_rows > 0;
+    if (media) {
+        if (nee) {
+            set_error("this scene has participating media and light sampling with emitters to sample, which no kernel combines: switch one of them off");
+            return RT_ERR_ARG;
+        }
+        if (env) {
+            set_error("this scene has participating media and an environment map, which no kernel combines: remove one of them");
+            return RT_ERR_ARG;
+        }
+        if (P.grid_wide == 2) {
+            set_error("this scene has participating media and the nested grid, which no kernel combines: switch the nested grid off");
+            return RT_ERR_ARG;
+        }
+        if (!layout_has_media(variant)) {
+            set_error("kernel variant %u does not carry participating media (the media kernels are variants 0, 16, 36 and 44)", variant);
+            return RT_ERR_ARG;
+        }
+    }
     if (env && P.grid_wide == 2) {
         set_error("this scene has the nested grid and an environment map, which no kernel combines: switch one of them off");
         return RT_ERR_ARG;
@@ -826,7 +863,7 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
         return RT_ERR_LIMIT;
     }
     if (force_ext && variant_has_ext(variant) && P.grid_wide) ext = true;
-    if (nee || env) ext = true;
+    if (nee || env || media) ext = true;
     const size_t hot_bytes = hot_bytes_of(mode);
     const bool tables_global = (variant & 8u) != 0 || mode == 8;
     const size_t lds_bytes = (tables_global ? 0 : hot_bytes) + acc_lds;
@@ -869,7 +906,8 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
         ent->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     }
     const unsigned long long resident =
-        (unsigned long long)ent->num_cus * (env          ? blocks_per_cu_env(variant, lds_bytes, nee, feature >= 0)
+        (unsigned long long)ent->num_cus * (media        ? blocks_per_cu_media(variant, lds_bytes)
+                                            : env        ? blocks_per_cu_env(variant, lds_bytes, nee, feature >= 0)
                                             : feature >= 0 ? blocks_per_cu_feature(variant, lds_bytes)
                                             : nee  ? blocks_per_cu_nee(variant, lds_bytes)
                                                    : blocks_per_cu(variant, count, lds_bytes, ext));
@@ -893,7 +931,7 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     const size_t queue_off = (plane * sizeof(unsigned long long) + 255) & ~(size_t)255;
     const long long frame_tiles = (long long)P.tiles_x * P.bands;
     const size_t need = queue_off + (ad ? (((size_t)(RT_TILE_LIST_AT + frame_tiles) * 4 + 255) & ~(size_t)255) : 256);
-    const Launcher launch{P, sh, ent, d_cnt, stream, lds_bytes, resident, variant, ext, nee, count, env, feature};
+    const Launcher launch{P, sh, ent, d_cnt, stream, lds_bytes, resident, variant, ext, nee, count, env, feature, media};
 
     int launches = 0;
     if (ad) {
@@ -926,8 +964,8 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     HIP_TRY(hipGetLastError());
 
     if (stats) {
-        // what variant 0 (or a counting call) resolved to (| 256: light sampling, | 512: a feature pass, | 1024: an environment map)
-        stats->kernel_variant = (int32_t)(variant | (nee ? 256u : 0u) | (feature >= 0 ? 512u : 0u) | (env ? 1024u : 0u));
+        // what variant 0 (or a counting call) resolved to (| 256: light sampling, | 512: a feature pass, | 1024: an environment map, | 2048: media)
+        stats->kernel_variant = (int32_t)(variant | (nee ? 256u : 0u) | (feature >= 0 ? 512u : 0u) | (env ? 1024u : 0u) | (media ? 2048u : 0u));
         HIP_TRY(hipEventRecord(ev2, stream));
         lock.unlock();
         HIP_TRY(hipEventSynchronize(ev2));

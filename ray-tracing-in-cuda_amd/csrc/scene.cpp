@@ -585,6 +585,48 @@ int scene_from_json(const char *text, size_t len, Scene &s, const char *base_dir
         }
     }
     if (r.ok && env_rc != RT_OK) return env_rc == RT_ERR_ARG ? RT_ERR_SCENE : env_rc;
+    // "media": {"data": [{"type": "sphere", "center", "radius", "density", "albedo"}, {"type": "box", "min", "max", "density", "albedo"}]}
+    s.media.clear();
+    if (root.find("media")) {
+        if (const JsonValue *arr = r.data_array(root, "media")) {
+            for (size_t i = 0; i < arr->arr.size() && r.ok; ++i) {
+                const JsonValue &t = arr->arr[i];
+                snprintf(where, sizeof where, "medium %zu", i);
+                const JsonValue *ty = t.find("type");
+                if (!t.is_object() || !ty || !ty->is_string()) {
+                    r.fail("%s: missing string \"type\"", where);
+                    break;
+                }
+                rt_medium m;
+                memset(&m, 0, sizeof m);
+                double v[3], w[3];
+                if (ty->str == "sphere") {
+                    m.shape = RT_MEDIUM_SPHERE;
+                    r.vec3(t, "center", where, v);
+                    for (int k = 0; k < 3; ++k) m.f[k] = (float)v[k];
+                    m.f[3] = (float)r.num(t, "radius", where);
+                } else if (ty->str == "box") {
+                    m.shape = RT_MEDIUM_BOX;
+                    r.vec3(t, "min", where, v);
+                    r.vec3(t, "max", where, w);
+                    for (int k = 0; k < 3; ++k) m.f[k] = (float)v[k], m.f[3 + k] = (float)w[k];
+                } else {
+                    r.fail("%s: unknown type \"%s\" (sphere, box)", where, ty->str.c_str());
+                    break;
+                }
+                m.density = (float)r.num(t, "density", where);
+                r.vec3(t, "albedo", where, v);
+                for (int k = 0; k < 3; ++k) m.albedo[k] = (float)v[k];
+                if (!r.ok) break;
+                const int rc = add_medium(s, m);
+                if (rc < 0) {  // (the record's own message, with its place in the file)
+                    const std::string why = get_error();
+                    set_error("%s: %s", where, why.c_str());
+                    return -rc;
+                }
+            }
+        }
+    }
 
     // camera, parser.hpp:113-141
     const JsonValue *cam = root.find("camera");
@@ -850,6 +892,27 @@ std::string scene_to_json(const Scene &s) {
             o += "]";
         }
         o += ", \"scale\": " + json_float(s.env_scale) + ", \"rotate\": " + json_float(s.env_rotate) + "},\n";
+    }
+    if (!s.media.empty()) {
+        o += "  \"media\": {\"data\": [";
+        for (size_t i = 0; i < s.media.size(); ++i) {
+            const rt_medium &m = s.media[i];
+            o += i ? ",\n    " : "\n    ";
+            if (m.shape == RT_MEDIUM_SPHERE) {
+                o += "{\"type\": \"sphere\", \"center\": ";
+                put_vec3(o, m.f);
+                o += ", \"radius\": " + json_float(m.f[3]);
+            } else {
+                o += "{\"type\": \"box\", \"min\": ";
+                put_vec3(o, m.f);
+                o += ", \"max\": ";
+                put_vec3(o, m.f + 3);
+            }
+            o += ", \"density\": " + json_float(m.density) + ", \"albedo\": ";
+            put_vec3(o, m.albedo);
+            o += "}";
+        }
+        o += "\n  ]},\n";
     }
     o += "  \"camera\": {\"lookfrom\": ";
     put_vec3d(o, s.cam.lookfrom);
@@ -1338,6 +1401,50 @@ double scene_bound_radius(const Scene &s) {
     double d2 = 0.0;
     for (int a = 0; a < 3; ++a) d2 += (hi[a] - lo[a]) * (hi[a] - lo[a]);
     return 0.5 * std::sqrt(d2);
+}
+
+// ---------------------------------------------------------------- homogeneous media
+int add_medium(Scene &s, const rt_medium &m) {
+    if (m.shape != RT_MEDIUM_SPHERE && m.shape != RT_MEDIUM_BOX) {
+        set_error("medium: shape %d (0 sphere, 1 box)", m.shape);
+        return -RT_ERR_SCENE;
+    }
+    if (!(std::isfinite(m.density) && m.density >= 0.0f)) {
+        set_error("medium: density %g must be finite and >= 0", (double)m.density);
+        return -RT_ERR_SCENE;
+    }
+    for (int c = 0; c < 3; ++c)
+        if (!(m.albedo[c] >= 0.0f && m.albedo[c] <= 1.0f)) {
+            set_error("medium: albedo component %d (%g) outside [0, 1]", c, (double)m.albedo[c]);
+            return -RT_ERR_SCENE;
+        }
+    const int nf = m.shape == RT_MEDIUM_SPHERE ? 4 : 6;
+    for (int k = 0; k < nf; ++k)
+        if (!std::isfinite(m.f[k])) {
+            set_error("medium: a bound is not finite");
+            return -RT_ERR_SCENE;
+        }
+    if (m.shape == RT_MEDIUM_SPHERE) {
+        if (!(m.f[3] > 0.0f)) {
+            set_error("medium sphere: radius %g must be > 0", (double)m.f[3]);
+            return -RT_ERR_SCENE;
+        }
+    } else {
+        for (int k = 0; k < 3; ++k)
+            if (!(m.f[k] < m.f[3 + k])) {
+                set_error("medium box: min %g >= max %g on axis %d", (double)m.f[k], (double)m.f[3 + k], k);
+                return -RT_ERR_SCENE;
+            }
+    }
+    if (s.media.size() >= (size_t)RT_MAX_MEDIA) {
+        set_error("a scene holds at most %d media", RT_MAX_MEDIA);
+        return -RT_ERR_LIMIT;
+    }
+    rt_medium rec = m;
+    if (rec.shape == RT_MEDIUM_SPHERE) rec.f[4] = rec.f[5] = 0.0f;
+    s.media.push_back(rec);
+    s.touch();
+    return (int)s.media.size() - 1;
 }
 
 }  // namespace rtmi

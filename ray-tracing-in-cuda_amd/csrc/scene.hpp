@@ -64,6 +64,7 @@ struct Scene {
     std::vector<SceneImage> images;  // referenced by RT_TEX_IMAGE textures (c0[0] = index)
     std::shared_ptr<const SceneEnvironment> env;  // null: no environment (a miss gives the background / the sky)
     float env_scale = 1.0f, env_rotate = 0.0f;    // radiance = scale x texel; degrees about +y
+    std::vector<rt_medium> media;  // homogeneous participating media, a list of its own: at most RT_MAX_MEDIA
     uint64_t version = 1;  // bumped on every mutation; invalidates device caches
     std::shared_ptr<DeviceSceneCache> dev;
 
@@ -109,6 +110,9 @@ double scene_bound_radius(const Scene &s);  // radius of the bounding sphere of 
 int add_triangle(Scene &s, const float v1[3], const float v2[3], const float v3[3], const float uv1[2], const float uv2[2],
                  const float uv3[2], int material);
 int add_obj(Scene &s, const char *path, int material, float scale, const float matrix[9], const float translate[3]);
+
+// a medium (scene.cpp): checks the record and appends it -> medium id, or -rt_status
+int add_medium(Scene &s, const rt_medium &m);
 
 void set_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
 const char *get_error();
