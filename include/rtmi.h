@@ -275,6 +275,44 @@ int rt_scene_clear_media(rt_scene *s);
  * [0.001, t_max].  1: non-empty (a < b), with *t_in = a and *t_out = b; 0: empty; -RT_ERR_ARG for null arguments or a shape
  * that is neither a sphere nor a box. */
 int rt_medium_interval(const rt_medium *m, const float orig[3], const float dir[3], float t_max, float *t_in, float *t_out);
+
+/* ---- motion blur: linearly moving spheres over a per-sample shutter time ----------------
+ * Up to RT_MAX_MOVING_SPHERES moving spheres per scene, a list of its own: they are not in rt_scene_get_prims and not in the
+ * grid, and leave the primitive part of the packed tables alone.  They are surfaces: they occlude and carry any material of
+ * the scene, a diffuse_light included.  At shutter time s in [0, 1) the centre is c(s) = center0 + s (center1 - center0),
+ * per component fmaf(s, v, center0) with v = center1 - center0 computed once in fp32.
+ * A sample of a scene with at least one mover has ONE time s for its whole path.  s is not a draw of the sample's stream: it is
+ * the top 24 bits of word 0 of Philox4x32-10(counter = (pixel_id, sample_index, 1, 0), key = (seed_lo, seed_hi)) x 2^-24 -- the
+ * block beside the one that seeds the stream (whose counter word 2 is 0) --, so every other draw of the sample stays where
+ * it is (rt_shutter_time).
+ * Every closest-hit query first finds its winner among the static primitives as before, then tests the movers in list order
+ * against the sphere (c(s), radius) with sphere::hit's operation sequence (oc, a, half_b, c, discriminant, the near root, then
+ * the far one; t_min = 0.001) and t_max = the nearest t so far: a mover behaves as a sphere listed behind every primitive, so
+ * at equal t a mover wins over a static primitive and a later mover over an earlier one.  The hit record is p = o + t d, the
+ * outward normal (p - c(s)) / radius, face-turned, and (u, v) for image textures as for a static sphere.
+ * A scene with a mover gets the wide tables and renders through kernels of its own (rt_opts.variant 0, 16, 36 or 44;
+ * rt_stats.kernel_variant reports layout | 4096) through every render entry point.  Refused with RT_ERR_ARG: movers together
+ * with light sampling that has something to sample, with an environment map, with media or with nested cells;
+ * rt_render_hip_count; feature passes (the denoiser's guides would show the scene at no particular time); any other variant.
+ * Errors of the add call: RT_ERR_ARG null pointers; RT_ERR_SCENE a radius <= 0 or not finite, non-finite centres, an unknown
+ * material; RT_ERR_LIMIT the 65th mover.
+ * JSON: an object {"type": "moving_sphere", "center0", "center1", "radius", "material"} in "object". */
+#define RT_MAX_MOVING_SPHERES 64
+typedef struct rt_moving_sphere {
+    float center0[3]; /* the centre at s = 0 */
+    float center1[3]; /* ... and at s = 1 */
+    float radius;
+    int32_t material;
+} rt_moving_sphere;
+int rt_scene_add_moving_sphere(rt_scene *s, const float center0[3], const float center1[3], float radius, int material); /* -> mover id, or -rt_status */
+int rt_scene_moving_sphere_count(const rt_scene *s); /* -> count, or -rt_status */
+int rt_scene_get_moving_spheres(const rt_scene *s, rt_moving_sphere *out, int cap); /* -> count, or -rt_status */
+int rt_scene_clear_moving_spheres(rt_scene *s);
+/* Host evaluation of the device's intersection (no GPU needed): the mover at shutter time s against the ray orig + t dir over
+ * [0.001, t_max].  1: a hit, with *t its ray parameter; 0: a miss; -RT_ERR_ARG for null arguments (t may be null). */
+int rt_moving_sphere_hit(const rt_moving_sphere *m, float s, const float orig[3], const float dir[3], float t_max, float *t);
+/* the shutter time of sample `sample` of pixel `pixel` (y * width + x) under `seed`, as the kernels evaluate it */
+float rt_shutter_time(uint64_t seed, uint32_t pixel, uint32_t sample);
 /* camera(lookfrom, lookat, vup, vfov, aspect, aperture, focus_dist) camera.cuh:9-15;
  * aspect <= 0 -> width/height, focus_dist <= 0 -> |lookfrom-lookat| (parser.hpp:122-124) */
 int rt_scene_set_camera(rt_scene *s, const float lookfrom[3], const float lookat[3],
@@ -361,7 +399,7 @@ typedef struct rt_table_info {
     int32_t off_rect_hot, off_cyl_hot, off_tri_hot;
     int32_t hot_bytes_grid;    /* what a grid-walk kernel stages into LDS */
     int32_t kernel_variant;    /* what rt_opts.variant = 0 renders this scene with (2, 6, 16, 36, 44 or 52; | 256 light sampling,
-                                  | 1024 an environment map, | 2048 participating media) */
+                                  | 1024 an environment map, | 2048 participating media, | 4096 moving spheres) */
 } rt_table_info;
 int rt_scene_table_info(const rt_scene *s, rt_table_info *out);
 /* The nested cells of the scene's tables (rt_scene_set_nested_grid); all zero while the tables are flat.  A nested cell's header
@@ -568,7 +606,7 @@ const char *rt_status_string(int status);
 int rt_abi_version(void);
 /* sizeof of the ABI structs as this library was compiled (binding self-checks):
  * 0 rt_opts, 1 rt_stats, 2 rt_prim, 3 rt_material, 4 rt_texture, 5 rt_camera, 6 rt_scene_info, 7 rt_table_info,
- * 8 rt_adaptive, 9 rt_adaptive_stats, 10 rt_nested_info, 16 rt_denoise, 17 rt_medium; else 0 */
+ * 8 rt_adaptive, 9 rt_adaptive_stats, 10 rt_nested_info, 16 rt_denoise, 17 rt_medium, 18 rt_moving_sphere; else 0 */
 size_t rt_struct_size(int which);
 /* number of usable gfx950 devices, or -rt_status */
 int rt_device_count(void);

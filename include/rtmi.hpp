@@ -118,6 +118,15 @@ private:
     }
 };
 
+// ---- motion blur (include/rtmi.h: moving spheres) ---------------------------------------------
+// moving_sphere(center0, center1, radius, material): the centre goes from center0 to center1 over the shutter time of a sample
+struct moving_sphere {
+    point3 center0, center1;
+    float radius;
+    material_ptr mat;
+    moving_sphere(point3 c0, point3 c1, float r, material_ptr m) : center0(c0), center1(c1), radius(r), mat(std::move(m)) {}
+};
+
 // ---- hittables (object.cuh) ------------------------------------------------------------------
 struct hittable {
     int type = RT_PRIM_SPHERE;
@@ -225,6 +234,21 @@ public:
         return out;
     }
     void clear_media() { check(rt_scene_clear_media(s_), "clear_media"); }
+    // a moving sphere joins the scene's list of movers (not the hittable list) -> its id
+    int add(const moving_sphere &m) {
+        if (!m.mat) throw std::logic_error("moving_sphere without a material");
+        const int id = rt_scene_add_moving_sphere(s_, m.center0.e, m.center1.e, m.radius, material_id(m.mat));
+        if (id < 0) throw error(-id, "add(moving_sphere)");
+        return id;
+    }
+    std::vector<rt_moving_sphere> moving_spheres() const {
+        const int n = rt_scene_get_moving_spheres(s_, nullptr, 0);
+        if (n < 0) throw error(-n, "moving_spheres");
+        std::vector<rt_moving_sphere> out((size_t)n);
+        if (n > 0) rt_scene_get_moving_spheres(s_, out.data(), n);
+        return out;
+    }
+    void clear_moving_spheres() { check(rt_scene_clear_moving_spheres(s_), "clear_moving_spheres"); }
     // hittable_list::add
     int add(const hittable &h) {
         if (!h.mat) throw std::logic_error("hittable without a material");

@@ -55,6 +55,10 @@ MEDIUM_SPHERE, MEDIUM_BOX = 0, 1  # rt_medium.shape
 MEDIUM_DTYPE = np.dtype(  # rt_medium: sphere f = {cx, cy, cz, r}; box f = {min.xyz, max.xyz}
     [("shape", "<i4"), ("f", "<f4", (6,)), ("density", "<f4"), ("albedo", "<f4", (3,))]
 )
+MAX_MOVING_SPHERES = 64
+MOVING_SPHERE_DTYPE = np.dtype(  # rt_moving_sphere: the centre at shutter time 0 and at 1
+    [("center0", "<f4", (3,)), ("center1", "<f4", (3,)), ("radius", "<f4"), ("material", "<i4")]
+)
 LIGHT_DTYPE = np.dtype(
     [("prim", "<i4"), ("shape", "<i4"), ("probability", "<f4"), ("area", "<f4"), ("emission", "<f4", (3,)),
      ("emission_odd", "<f4", (3,))]
@@ -249,6 +253,12 @@ _sig("rt_scene_add_medium_box", C.c_int, _p, _f3, _f3, C.c_float, _f3)
 _sig("rt_scene_get_media", C.c_int, _p, _p, C.c_int)
 _sig("rt_scene_clear_media", C.c_int, _p)
 _sig("rt_medium_interval", C.c_int, _p, _f3, _f3, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float))
+_sig("rt_scene_add_moving_sphere", C.c_int, _p, _f3, _f3, C.c_float, C.c_int)
+_sig("rt_scene_moving_sphere_count", C.c_int, _p)
+_sig("rt_scene_get_moving_spheres", C.c_int, _p, _p, C.c_int)
+_sig("rt_scene_clear_moving_spheres", C.c_int, _p)
+_sig("rt_moving_sphere_hit", C.c_int, _p, C.c_float, _f3, _f3, C.c_float, C.POINTER(C.c_float))
+_sig("rt_shutter_time", C.c_float, C.c_uint64, C.c_uint32, C.c_uint32)
 _sig("rt_scene_set_nested_grid", C.c_int, _p, C.c_int)
 _sig("rt_scene_get_nested_grid", C.c_int, _p)
 _sig("rt_scene_nested_info", C.c_int, _p, C.POINTER(NestedInfo))
@@ -295,6 +305,8 @@ C_SYMBOLS = [
     "rt_scene_set_environment", "rt_scene_set_environment_file", "rt_scene_get_environment", "rt_environment_eval",
     "rt_environment_sample",
     "rt_scene_add_medium_sphere", "rt_scene_add_medium_box", "rt_scene_get_media", "rt_scene_clear_media", "rt_medium_interval",
+    "rt_scene_add_moving_sphere", "rt_scene_moving_sphere_count", "rt_scene_get_moving_spheres", "rt_scene_clear_moving_spheres",
+    "rt_moving_sphere_hit", "rt_shutter_time",
     "rt_render_hip_feature", "rt_render_hip_feature_device", "rt_denoise_hip", "rt_denoise_hip_device",
 ]
 
@@ -404,6 +416,19 @@ class Scene:
 
     def clear_media(self):
         _check(_lib.rt_scene_clear_media(self._h), "clear_media")
+
+    def add_moving_sphere(self, center0, center1, radius: float, material: int) -> int:
+        """A sphere whose centre moves from center0 (shutter time 0) to center1 (shutter time 1) within every sample
+        (include/rtmi.h, motion blur).  Returns the mover's id."""
+        return _check_id(_lib.rt_scene_add_moving_sphere(self._h, _v3(center0), _v3(center1), float(radius), int(material)),
+                         "add_moving_sphere")
+
+    def moving_spheres(self) -> np.ndarray:
+        """The scene's moving spheres in list order (MOVING_SPHERE_DTYPE records)."""
+        return self._table(_lib.rt_scene_get_moving_spheres, MOVING_SPHERE_DTYPE)
+
+    def clear_moving_spheres(self):
+        _check(_lib.rt_scene_clear_moving_spheres(self._h), "clear_moving_spheres")
 
     @property
     def environment(self):
@@ -826,6 +851,23 @@ def medium_interval(medium, orig, direction, t_max=float("inf")):
     rc = _check_id(_lib.rt_medium_interval(rec.ctypes.data_as(C.c_void_p), _v3(orig), _v3(direction), float(t_max), C.byref(a), C.byref(b)),
                    "medium_interval")
     return bool(rc), a.value, b.value
+
+
+def moving_sphere_hit(mover, s, orig, direction, t_max=float("inf")):
+    """Host evaluation of the device's intersection: ``mover`` (a MOVING_SPHERE_DTYPE record) at shutter time ``s`` against
+    the ray orig + t direction over [0.001, t_max] -> (hit, t)."""
+    rec = np.zeros(1, MOVING_SPHERE_DTYPE)
+    rec[0] = mover
+    t = C.c_float()
+    rc = _check_id(_lib.rt_moving_sphere_hit(rec.ctypes.data_as(C.c_void_p), float(s), _v3(orig), _v3(direction), float(t_max), C.byref(t)),
+                   "moving_sphere_hit")
+    return bool(rc), t.value
+
+
+def shutter_time(seed, pixel, sample) -> float:
+    """The shutter time in [0, 1) of sample ``sample`` of pixel ``pixel`` (y * width + x): the top 24 bits of word 0 of
+    Philox4x32-10(counter = (pixel, sample, 1, 0), key = seed) x 2^-24 -- not a draw of the sample's stream."""
+    return float(_lib.rt_shutter_time(int(seed), int(pixel), int(sample)))
 
 
 def aabb_hit(bmin, bmax, orig, direction, t_min, t_max) -> bool:

@@ -11,6 +11,7 @@
 #include "philox.h"
 #include "rt_env.h"
 #include "rt_media.h"
+#include "rt_motion.h"
 #include "scene.hpp"
 
 using namespace rtmi;
@@ -54,6 +55,7 @@ size_t rt_struct_size(int which) {
     case 10: return sizeof(rt_nested_info);
     case 16: return sizeof(rt_denoise);  // (11 .. 15 stay 0: the next structs of the scene / render interface)
     case 17: return sizeof(rt_medium);
+    case 18: return sizeof(rt_moving_sphere);
     default: return 0;
     }
 }
@@ -795,6 +797,58 @@ int rt_medium_interval(const rt_medium *m, const float orig[3], const float dir[
     if (t_in) *t_in = a;
     if (t_out) *t_out = b;
     return hit ? 1 : 0;
+}
+
+// ---- moving spheres: the scene interface and the host evaluations of the device's functions (rt_motion.h)
+int rt_scene_add_moving_sphere(rt_scene *s, const float center0[3], const float center1[3], float radius, int material) {
+    if (!s || !center0 || !center1) {
+        set_error("rt_scene_add_moving_sphere: null argument");
+        return -RT_ERR_ARG;
+    }
+    rt_moving_sphere m;
+    memset(&m, 0, sizeof m);
+    for (int k = 0; k < 3; ++k) m.center0[k] = center0[k], m.center1[k] = center1[k];
+    m.radius = radius, m.material = material;
+    return add_moving_sphere(s->s, m);
+}
+
+int rt_scene_moving_sphere_count(const rt_scene *s) {
+    if (bad_scene(s, "rt_scene_moving_sphere_count")) return -RT_ERR_ARG;
+    return (int)s->s.movers.size();
+}
+
+int rt_scene_get_moving_spheres(const rt_scene *s, rt_moving_sphere *out, int cap) {
+    if (bad_scene(s, "rt_scene_get_moving_spheres")) return -RT_ERR_ARG;
+    for (int i = 0; out && i < cap && i < (int)s->s.movers.size(); ++i) out[i] = s->s.movers[(size_t)i];
+    return (int)s->s.movers.size();
+}
+
+int rt_scene_clear_moving_spheres(rt_scene *s) {
+    if (bad_scene(s, "rt_scene_clear_moving_spheres")) return RT_ERR_ARG;
+    if (!s->s.movers.empty()) {  // (a scene without movers stays the scene it was: same version, same tables)
+        s->s.movers.clear();
+        s->s.touch();
+    }
+    return RT_OK;
+}
+
+int rt_moving_sphere_hit(const rt_moving_sphere *m, float s, const float orig[3], const float dir[3], float t_max, float *t) {
+    if (!m || !orig || !dir) {
+        set_error("rt_moving_sphere_hit: null argument");
+        return -RT_ERR_ARG;
+    }
+    // the ray's A = d.d and 1 / A as the kernel carries them (render_body.h: ra, rinv_a), v as the packer writes it
+    const float A = fmaf(dir[0], dir[0], fmaf(dir[1], dir[1], dir[2] * dir[2])), inv_a = 1.0f / A;
+    float root = 0.0f;
+    const bool hit = moving_sphere_hit(m->center0[0], m->center0[1], m->center0[2], m->radius, m->center1[0] - m->center0[0],
+                                       m->center1[1] - m->center0[1], m->center1[2] - m->center0[2], s, orig[0], orig[1], orig[2], dir[0],
+                                       dir[1], dir[2], A, inv_a, t_max, root);
+    if (hit && t) *t = root;
+    return hit ? 1 : 0;
+}
+
+float rt_shutter_time(uint64_t seed, uint32_t pixel, uint32_t sample) {
+    return shutter_time(pixel, sample, (uint32_t)seed, (uint32_t)(seed >> 32));
 }
 
 // ---- environment map: the scene interface and the host evaluations of the device functions of rt_env.h (no GPU needed)

@@ -12,6 +12,7 @@
 #include <utility>
 
 #include "pack.h"
+#include "rt_motion.h"  // (before rt_media.h: philox.h defines RTMI_HD, rt_trig.h takes it as it finds it)
 #include "rt_media.h"
 
 namespace rtmi {
@@ -662,8 +663,9 @@ int lay_out_hot(RenderParams &L, const Grid &g) {
 
 // Every offset of the image, in image order: the one place that says what the image looks like.  Returns the record count;
 // image_word[k]: the first 32-bit word of image texture k's texels.
-// off_media: the first record of the MEDIA part (rt_media.h; 0: the scene has no media).
-int lay_out_image(RenderParams &L, const Grid &g, const Scene &s, std::vector<int> &image_word, int &off_media) {
+// off_media: the first record of the MEDIA part (rt_media.h; 0: the scene has no media); off_motion: of the MOTION part
+// (rt_motion.h; 0: no moving spheres).
+int lay_out_image(RenderParams &L, const Grid &g, const Scene &s, std::vector<int> &image_word, int &off_media, int &off_motion) {
     int off = lay_out_hot(L, g);
     L.hot_vec4_grid = off;  // what the grid-walk kernels stage into LDS
     // the boxes of the cluster searches (ablation builds) lie behind the grid tables, so that the grid walk does not stage
@@ -721,6 +723,12 @@ int lay_out_image(RenderParams &L, const Grid &g, const Scene &s, std::vector<in
     if (!s.media.empty()) {
         off_media = off;
         off += RT_MEDIUM_STRIDE * (int)s.media.size();
+    }
+    // the MOTION part (rt_motion.h): the moving spheres' records, last of all; global memory only, read by the motion kernels
+    off_motion = 0;
+    if (!s.movers.empty()) {
+        off_motion = off;
+        off += RT_MOTION_STRIDE * (int)s.movers.size();
     }
     return off;
 }
@@ -1072,6 +1080,24 @@ void write_media(float *I, const RenderParams &L, const Scene &s, int off_media)
     }
 }
 
+// the moving spheres' records, and in the camera block how many there are and where (rt_motion.h).  After write_materials:
+// a record carries its material's kind, as the primitives' cold records do.
+void write_motion(float *I, const RenderParams &L, const Scene &s, int off_motion) {
+    const int32_t n = (int32_t)s.movers.size(), off = off_motion;
+    memcpy(rec4(I, L.off_cam + 3) + 3, &n, 4);
+    memcpy(rec4(I, L.off_cam + 4) + 3, &off, 4);
+    for (int i = 0; i < n; ++i) {
+        const rt_moving_sphere &m = s.movers[(size_t)i];
+        float *r0 = rec4(I, off_motion + RT_MOTION_STRIDE * i), *r1 = r0 + 4, *r2 = r0 + 8;
+        for (int k = 0; k < 3; ++k) r0[k] = m.center0[k], r1[k] = m.center1[k] - m.center0[k];  // v, once, in fp32
+        r0[3] = m.radius;
+        r1[3] = 1.0f / m.radius;  // (p - c) / r  ==  (1/r) * (p - c), as for the static spheres
+        r2[0] = bits(m.material);
+        r2[1] = I[(size_t)(L.off_mat + 3 * m.material) * 4];  // the material's kind (bits)
+        r2[2] = r2[3] = 0.0f;
+    }
+}
+
 // the environment's texels and sampling tables, as the host evaluation reads them
 void write_environment(float *I, const RenderParams &L, const Scene &s) {
     const SceneEnvironment &e = *s.env;
@@ -1121,8 +1147,8 @@ bool pack_round(const Scene &s, std::vector<char> &forced, std::vector<float> &i
     L.nl = (int)lights.size();
 
     Grid g;
-    // (an environment and media, like light sampling, run in general kernels of their own: wide tables)
-    const bool wide = !sphere_only || S.ns() >= 65536 || !lights.empty() || s.env || !s.media.empty() || nest_over > 0 || knob_set("RTMI_FORCE_WIDE");  // (the knob: measurement)
+    // (an environment, media and moving spheres, like light sampling, run in general kernels of their own: wide tables)
+    const bool wide = !sphere_only || S.ns() >= 65536 || !lights.empty() || s.env || !s.media.empty() || !s.movers.empty() || nest_over > 0 || knob_set("RTMI_FORCE_WIDE");  // (the knob: measurement)
     const bool built = build_grid(s, S, O, L, wide, forced, g, nest_over, nest_cap);
     note.demoted = note.demoted || g.demoted;
     if (!built) return false;
@@ -1132,8 +1158,8 @@ bool pack_round(const Scene &s, std::vector<char> &forced, std::vector<float> &i
     L.grid_wide = g.wide ? (nested ? 2 : 1) : 0;
     L.grid_sheet = (!g.cells.empty() && g.n[1] == 1 && !g.wide) ? 1 : 0;
     std::vector<int> image_word;
-    int off_media = 0;
-    const int records = lay_out_image(L, g, s, image_word, off_media);
+    int off_media = 0, off_motion = 0;
+    const int records = lay_out_image(L, g, s, image_word, off_media, off_motion);
     if (records < 0) {
         note.too_large = true;
         return true;
@@ -1159,6 +1185,7 @@ bool pack_round(const Scene &s, std::vector<char> &forced, std::vector<float> &i
     if (L.nl > 0) write_lights(I, L, s, S, O, lights);
     if (s.env) write_environment(I, L, s);
     if (!s.media.empty()) write_media(I, L, s, off_media);
+    if (!s.movers.empty()) write_motion(I, L, s, off_motion);
     note.nested = NestedInfo();
     if (nested) {
         note.nested.cells = (int)(g.subs.size() / 16);

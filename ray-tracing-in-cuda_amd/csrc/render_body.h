@@ -1,5 +1,5 @@
 // The body of the render kernels (render_kernel.hip): included INSIDE render_kernel, render_nee_kernel, render_nested_kernel,
-// render_feature_kernel and render_env_kernel (render_env.hip), after their template arguments and a constexpr NEE, AOV, ENV and MEDIA (render_media_kernel, render_media.hip, is the one with MEDIA on).  As text rather than a force-inlined device function, so that the render_kernel
+// render_feature_kernel and render_env_kernel (render_env.hip), after their template arguments and a constexpr NEE, AOV, ENV, MEDIA (render_media_kernel, render_media.hip, is the one with MEDIA on) and MOTION (render_motion_kernel, render_motion.hip).  As text rather than a force-inlined device function, so that the render_kernel
 // instances compile to the very instructions they did before light sampling came (a device function that takes the
 // kernel's parameters by reference changes the order of the kernel-argument loads and with it the register allocation).
 // Not a header of its own: it needs the kernel's scope (P, image, acc, queue, counters and the template arguments).
@@ -129,6 +129,8 @@
     float mis_pdf = -1.0f;
     int shadow = 0;
     float cdx = 0, cdy = 0, cdz = 0, pend_r = 0, pend_g = 0, pend_b = 0;
+    // MOTION: the shutter time of the lane's sample (rt_motion.h), set where the sample starts and kept for the life of its path
+    float mot_s = 0.0f;
     const int *lslot = reinterpret_cast<const int *>(image + P.off_lslot);
     // ENV: the environment's tables (rt_env.h), built where they are used from launch values (wave-uniform)
     auto env_view = [&]() -> EnvView {
@@ -968,6 +970,23 @@
                     }
                 }
             }
+            // MOTION: the moving spheres of a finished query.  The movers -- records behind a count and an offset in the
+            // camera block, all wave-uniform reads from global memory -- in list order, each at the lane's shutter time, against
+            // what the query has found so far: a mover behaves as a sphere listed behind every static primitive (a root equal
+            // to the winner's takes over, the later mover wins a tie among movers).  What outlives the loop: best_t and mot_i.
+            int mot_i = -1;
+            if constexpr (MOTION) {
+                if (!unfinished) {
+                    const int n_mot = __builtin_amdgcn_readfirstlane(__float_as_int(image[P.off_cam + 3].w));
+                    const float4 *mot = image + __builtin_amdgcn_readfirstlane(__float_as_int(image[P.off_cam + 4].w));
+                    for (int m = 0; m < n_mot; ++m) {
+                        const float4 g0 = mot[RT_MOTION_STRIDE * m], g1 = mot[RT_MOTION_STRIDE * m + 1];
+                        float t;
+                        if (moving_sphere_hit(g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, mot_s, ox, oy, oz, dx, dy, dz, ra, rinv_a, best_t, t))
+                            best_t = t, mot_i = m;
+                    }
+                }
+            }
             if (unfinished) {
             } else if (NEE && shadow != 0) {
                 // the shadow query's verdict: the light sample counts when nothing lies between the vertex and its light
@@ -986,9 +1005,19 @@
                 nx = ny = nz = 0.0f;
                 mat = med_i;
                 kind = MK_MEDIUM;
-            } else if (best_id >= 0) {
+            } else if (best_id >= 0 || (MOTION && mot_i >= 0)) {
                 // hit record of the winner only (the reference fills one per candidate)
-                if (SPH || best_id < ns) {
+                if (MOTION && mot_i >= 0) {  // a moving sphere: the static sphere's record about the centre at the shutter time
+                    const float4 *g = image + __builtin_amdgcn_readfirstlane(__float_as_int(image[P.off_cam + 4].w)) + RT_MOTION_STRIDE * mot_i;
+                    const float4 g0 = g[0], g1 = g[1], g2 = g[2];
+                    const float cx = fmaf(mot_s, g1.x, g0.x), cy = fmaf(mot_s, g1.y, g0.y), cz = fmaf(mot_s, g1.z, g0.z);
+                    px = fmaf(best_t, dx, ox), py = fmaf(best_t, dy, oy), pz = fmaf(best_t, dz, oz);
+                    const float onx = g1.w * (px - cx), ony = g1.w * (py - cy), onz = g1.w * (pz - cz);
+                    front = dot3(dx, dy, dz, onx, ony, onz) < 0.0f;
+                    nx = front ? onx : -onx, ny = front ? ony : -ony, nz = front ? onz : -onz;
+                    mat = __float_as_int(g2.x);
+                    kind = __float_as_int(g2.y);
+                } else if (SPH || best_id < ns) {
                     const float4 s = sph[best_id];
                     const float4 cold = image[P.off_sph_cold + best_id];
                     px = fmaf(best_t, dx, ox), py = fmaf(best_t, dy, oy), pz = fmaf(best_t, dz, oz);
@@ -1049,7 +1078,7 @@
                 // would be the most expensive part of sphere::hit
                 if (EXT && (kind == MK_LAMBERT_IMAGE || kind == MK_LIGHT_IMAGE)) {
                     float tu, tv;
-                    if (best_id < ns) {  // get_sphere_uv(outward_normal), object.cuh:87-93
+                    if ((MOTION && mot_i >= 0) || best_id < ns) {  // get_sphere_uv(outward_normal), object.cuh:87-93
                         const float onx = front ? nx : -nx, ony = front ? ny : -ny, onz = front ? nz : -nz;
                         const float theta = rt_acosf(-ony);
                         const float phi = rt_atan2f(-onz, onx) + 3.1415927410125732421875f;
@@ -1314,6 +1343,11 @@
             if (start) {
                 cur_p = sp;
                 rng_start(rng, (uint32_t)(spy * P.width + spx), (uint32_t)ss, k0, k1);
+                if constexpr (MOTION) {  // (the key behind the same barrier as in rng_start: its schedule stays scalar)
+                    uint32_t m0 = k0, m1 = k1;
+                    asm volatile("" : "+s"(m0), "+s"(m1));
+                    mot_s = shutter_time((uint32_t)(spy * P.width + spx), (uint32_t)ss, m0, m1);
+                }
                 u = ((float)spx + rng_next<COUNT>(rng)) * P.inv_wm1;
                 v = ((float)spy + rng_next<COUNT>(rng)) * P.inv_hm1;
                 if (COUNT) c_samples++;

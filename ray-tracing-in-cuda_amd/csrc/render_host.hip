@@ -42,6 +42,10 @@ bool launch_render_media(const RenderParams &P, const void *image, unsigned long
                          unsigned grid, hipStream_t stream, unsigned layout);
 bool layout_has_media(unsigned layout);
 int blocks_per_cu_media(unsigned layout, size_t lds_bytes);
+bool launch_render_motion(const RenderParams &P, const void *image, unsigned long long *acc, unsigned int *queue, size_t lds_bytes,
+                          unsigned grid, hipStream_t stream, unsigned layout);
+bool layout_has_motion(unsigned layout);
+int blocks_per_cu_motion(unsigned layout, size_t lds_bytes);
 bool variant_has_ext(unsigned variant);
 bool variant_has_count(unsigned variant);
 bool has_ablations();
@@ -325,6 +329,7 @@ static int read_tables(const rt_scene *sc, rt_table_info *out, float *dst, int c
     if (L.nl > 0) out->kernel_variant |= 256;  // light sampling: the layout's light-sampling kernel
     if (L.env_rows > 0) out->kernel_variant |= 1024;  // an environment map: the layout's environment kernel
     if (!sc->s.media.empty()) out->kernel_variant |= 2048;  // media: the layout's media kernel
+    if (!sc->s.movers.empty()) out->kernel_variant |= 4096;  // moving spheres: the layout's motion kernel
     if (dst && cap_floats > 0) memcpy(dst, cache.image.data(), sizeof(float) * std::min((size_t)cap_floats, cache.image.size()));
     return RT_OK;
 }
@@ -457,6 +462,7 @@ struct Launcher {
     bool env;     // an environment map: render_env_kernel of layout `variant` (plain, light sampling or feature pass)
     int feature;  // >= 0: a feature pass (render_feature_kernel of layout `variant`)
     bool media;   // homogeneous media: render_media_kernel of layout `variant` (never with nee, env or a feature pass)
+    bool motion;  // moving spheres: render_motion_kernel of layout `variant` (never with nee, env, media or a feature pass)
 
     int enqueue(unsigned long long *acc, unsigned int *d_queue, int first, int n, int n_list, const ChunkPlan &pl) const {
         RenderParams Q = P;
@@ -495,6 +501,13 @@ struct Launcher {
         if (media) {
             if (!launch_render_media(Q, ent->d_image, acc, d_queue, lds_bytes, (unsigned)grid, stream, variant)) {
                 set_error("layout %u has no media kernel", variant);
+                return RT_ERR_ARG;
+            }
+            return RT_OK;
+        }
+        if (motion) {
+            if (!launch_render_motion(Q, ent->d_image, acc, d_queue, lds_bytes, (unsigned)grid, stream, variant)) {
+                set_error("layout %u has no motion kernel", variant);
                 return RT_ERR_ARG;
             }
             return RT_OK;
@@ -689,6 +702,20 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
         set_error("rt_render_hip_count: this scene has participating media, which the counting kernels do not carry");
         return RT_ERR_ARG;
     }
+    // moving spheres: kernels of their own
+    const bool motion = !s.movers.empty();
+    if (motion && count) {
+        set_error("rt_render_hip_count: this scene has moving spheres, which the counting kernels do not carry");
+        return RT_ERR_ARG;
+    }
+    if (motion && feature >= 0) {
+        set_error("a feature pass of a scene with moving spheres: the guides would show the scene at no particular time (clear the moving spheres for the pass)");
+        return RT_ERR_ARG;
+    }
+    if (motion && media) {
+        set_error("this scene has moving spheres and participating media, which no kernel combines: remove one of them");
+        return RT_ERR_ARG;
+    }
     if (count && !has_ablations()) {
         set_error("rt_render_hip_count: this library was built without the counting kernels (make ABLATIONS=1)");
         return RT_ERR_LIMIT;
@@ -804,6 +831,24 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
             return RT_ERR_ARG;
         }
     }
+    if (motion) {
+        if (nee) {
+            set_error("this scene has moving spheres and light sampling with emitters to sample, which no kernel combines: switch light sampling off");
+            return RT_ERR_ARG;
+        }
+        if (env) {
+            set_error("this scene has moving spheres and an environment map, which no kernel combines: remove one of them");
+            return RT_ERR_ARG;
+        }
+        if (P.grid_wide == 2) {
+            set_error("this scene has moving spheres and the nested grid, which no kernel combines: switch the nested grid off");
+            return RT_ERR_ARG;
+        }
+        if (!layout_has_motion(variant)) {
+            set_error("kernel variant %u does not carry moving spheres (the motion kernels are variants 0, 16, 36 and 44)", variant);
+            return RT_ERR_ARG;
+        }
+    }
     if (env && P.grid_wide == 2) {
         set_error("this scene has the nested grid and an environment map, which no kernel combines: switch one of them off");
         return RT_ERR_ARG;
@@ -863,7 +908,7 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
         return RT_ERR_LIMIT;
     }
     if (force_ext && variant_has_ext(variant) && P.grid_wide) ext = true;
-    if (nee || env || media) ext = true;
+    if (nee || env || media || motion) ext = true;
     const size_t hot_bytes = hot_bytes_of(mode);
     const bool tables_global = (variant & 8u) != 0 || mode == 8;
     const size_t lds_bytes = (tables_global ? 0 : hot_bytes) + acc_lds;
@@ -906,7 +951,8 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
         ent->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     }
     const unsigned long long resident =
-        (unsigned long long)ent->num_cus * (media        ? blocks_per_cu_media(variant, lds_bytes)
+        (unsigned long long)ent->num_cus * (motion       ? blocks_per_cu_motion(variant, lds_bytes)
+                                            : media      ? blocks_per_cu_media(variant, lds_bytes)
                                             : env        ? blocks_per_cu_env(variant, lds_bytes, nee, feature >= 0)
                                             : feature >= 0 ? blocks_per_cu_feature(variant, lds_bytes)
                                             : nee  ? blocks_per_cu_nee(variant, lds_bytes)
@@ -931,7 +977,7 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     const size_t queue_off = (plane * sizeof(unsigned long long) + 255) & ~(size_t)255;
     const long long frame_tiles = (long long)P.tiles_x * P.bands;
     const size_t need = queue_off + (ad ? (((size_t)(RT_TILE_LIST_AT + frame_tiles) * 4 + 255) & ~(size_t)255) : 256);
-    const Launcher launch{P, sh, ent, d_cnt, stream, lds_bytes, resident, variant, ext, nee, count, env, feature, media};
+    const Launcher launch{P, sh, ent, d_cnt, stream, lds_bytes, resident, variant, ext, nee, count, env, feature, media, motion};
 
     int launches = 0;
     if (ad) {
@@ -964,8 +1010,9 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     HIP_TRY(hipGetLastError());
 
     if (stats) {
-        // what variant 0 (or a counting call) resolved to (| 256: light sampling, | 512: a feature pass, | 1024: an environment map, | 2048: media)
-        stats->kernel_variant = (int32_t)(variant | (nee ? 256u : 0u) | (feature >= 0 ? 512u : 0u) | (env ? 1024u : 0u) | (media ? 2048u : 0u));
+        // what variant 0 (or a counting call) resolved to (| 256: light sampling, | 512: a feature pass, | 1024: an environment map, | 2048: media, | 4096: moving spheres)
+        stats->kernel_variant = (int32_t)(variant | (nee ? 256u : 0u) | (feature >= 0 ? 512u : 0u) | (env ? 1024u : 0u) | (media ? 2048u : 0u) |
+                                          (motion ? 4096u : 0u));
         HIP_TRY(hipEventRecord(ev2, stream));
         lock.unlock();
         HIP_TRY(hipEventSynchronize(ev2));

@@ -47,6 +47,7 @@
 #include "philox.h"
 #include "rt_env.h"
 #include "rt_media.h"
+#include "rt_motion.h"
 #include "rt_trig.h"
 #include "shard.h"
 #include "../../include/rtmi.h"
@@ -267,7 +268,7 @@ __global__ __launch_bounds__(256, RT_WAVES_PER_SIMD) void render_kernel(const Re
                                                      unsigned long long *__restrict__ acc,
                                                      unsigned int *__restrict__ queue,
                                                      DevCounters *__restrict__ counters) {
-    constexpr bool NEE = false, AOV = false, ENV = false, MEDIA = false;
+    constexpr bool NEE = false, AOV = false, ENV = false, MEDIA = false, MOTION = false;
 #include "render_body.h"
 }
 
@@ -278,7 +279,7 @@ __global__ __launch_bounds__(256, RT_NEE_WAVES_PER_SIMD) void render_nee_kernel(
                                                          unsigned long long *__restrict__ acc,
                                                          unsigned int *__restrict__ queue,
                                                          DevCounters *__restrict__ counters) {
-    constexpr bool COUNT = false, POOL = true, EXT = true, SPH = false, NEE = true, AOV = false, ENV = false, MEDIA = false;
+    constexpr bool COUNT = false, POOL = true, EXT = true, SPH = false, NEE = true, AOV = false, ENV = false, MEDIA = false, MOTION = false;
 #include "render_body.h"
 }
 
@@ -290,7 +291,7 @@ __global__ __launch_bounds__(256, RT_WAVES_PER_SIMD) void render_nested_kernel(c
                                                             unsigned long long *__restrict__ acc,
                                                             unsigned int *__restrict__ queue,
                                                             DevCounters *__restrict__ counters) {
-    constexpr bool POOL = true, SCALAR = true, SPH = false, NEE = false, AOV = false, ENV = false, MEDIA = false;
+    constexpr bool POOL = true, SCALAR = true, SPH = false, NEE = false, AOV = false, ENV = false, MEDIA = false, MOTION = false;
     constexpr int CULL = 8;
 #include "render_body.h"
 }
@@ -304,11 +305,11 @@ __global__ __launch_bounds__(256, RT_WAVES_PER_SIMD) void render_feature_kernel(
                                                              unsigned long long *__restrict__ acc,
                                                              unsigned int *__restrict__ queue,
                                                              DevCounters *__restrict__ counters) {
-    constexpr bool COUNT = false, POOL = true, EXT = true, SPH = false, NEE = false, AOV = true, ENV = false, MEDIA = false;
+    constexpr bool COUNT = false, POOL = true, EXT = true, SPH = false, NEE = false, AOV = true, ENV = false, MEDIA = false, MOTION = false;
 #include "render_body.h"
 }
 
-#if !defined(RT_ENV_TU) && !defined(RT_MEDIA_TU)  // (render_env.hip and render_media.hip include this file for the helpers above and define their own kernels)
+#if !defined(RT_ENV_TU) && !defined(RT_MEDIA_TU) && !defined(RT_MOTION_TU)  // (render_env.hip, render_media.hip and render_motion.hip include this file for the helpers above and define their own kernels)
 // fixed-point pixel sums -> fp32 framebuffer (rgb_sum[(row*W + x)*3 + c]); every store
 // instruction writes 256 contiguous bytes
 __global__ __launch_bounds__(256) void finalize_kernel(const unsigned long long *__restrict__ acc,
@@ -317,9 +318,9 @@ __global__ __launch_bounds__(256) void finalize_kernel(const unsigned long long 
     if (i < n) out[i] = (float)((double)(long long)acc[i] * (1.0 / 16777216.0));
 }
 
-#endif  // RT_ENV_TU, RT_MEDIA_TU
+#endif  // RT_ENV_TU, RT_MEDIA_TU, RT_MOTION_TU
 
-#if defined(RT_ENV_TU) || defined(RT_MEDIA_TU)
+#if defined(RT_ENV_TU) || defined(RT_MEDIA_TU) || defined(RT_MOTION_TU)
 #elif defined(RT_ISA_ONLY)
 // tools/isa_stats.py: one instance alone (RT_ISA_ONLY = its template arguments), compiled to assembly in seconds
 template __global__ void render_kernel<RT_ISA_ONLY>(const RenderParams, const float4 *__restrict__, unsigned long long *__restrict__,
@@ -593,6 +594,7 @@ void launch_finalize(const unsigned long long *acc, float *out, size_t n, hipStr
 
 int set_max_dynamic_lds_env(size_t bytes);    // render_env.hip
 int set_max_dynamic_lds_media(size_t bytes);  // render_media.hip
+int set_max_dynamic_lds_motion(size_t bytes); // render_motion.hip
 
 int set_max_dynamic_lds(size_t bytes) {
 #define RT_ATTR1(K)                                                                                                  \
@@ -613,8 +615,8 @@ int set_max_dynamic_lds(size_t bytes) {
     RT_FEATURE_TABLE(RT_ATTR_AOV)
 #undef RT_ATTR_AOV
 #undef RT_ATTR1
-    return set_max_dynamic_lds_env(bytes) || set_max_dynamic_lds_media(bytes);
+    return set_max_dynamic_lds_env(bytes) || set_max_dynamic_lds_media(bytes) || set_max_dynamic_lds_motion(bytes);
 }
-#endif  // RT_ENV_TU, RT_MEDIA_TU, RT_ISA_ONLY, RT_ISA_ONLY_NEE, RT_ISA_ONLY_NESTED, RT_ISA_ONLY_AOV
+#endif  // RT_ENV_TU, RT_MEDIA_TU, RT_MOTION_TU, RT_ISA_ONLY, RT_ISA_ONLY_NEE, RT_ISA_ONLY_NESTED, RT_ISA_ONLY_AOV
 
 }  // namespace rtmi

@@ -194,6 +194,11 @@ int scene_validate(const Scene &s) {
             return RT_ERR_SCENE;
         }
     }
+    for (size_t i = 0; i < s.movers.size(); ++i)
+        if (s.movers[i].material < 0 || s.movers[i].material >= (int)s.mats.size()) {
+            set_error("moving sphere %zu references material %d (have %zu)", i, s.movers[i].material, s.mats.size());
+            return RT_ERR_SCENE;
+        }
     double d[3];
     v3sub(s.cam.lookfrom, s.cam.lookat, d);
     if (!(v3len(d) > 0)) {
@@ -741,7 +746,8 @@ int scene_from_json(const char *text, size_t len, Scene &s, const char *base_dir
     }
     if (!r.ok) return RT_ERR_SCENE;
 
-    // objects, parser.hpp:283-478
+    // objects, parser.hpp:283-478 (a "moving_sphere" -- a sphere with "center0" and "center1" -- joins the movers' list)
+    s.movers.clear();
     if (const JsonValue *arr = r.data_array(root, "object")) {
         for (size_t i = 0; i < arr->arr.size() && r.ok; ++i) {
             const JsonValue &o = arr->arr[i];
@@ -763,6 +769,22 @@ int scene_from_json(const char *text, size_t len, Scene &s, const char *base_dir
                 rec.material = r.integer(o, "material", where);
                 s.prims.push_back(rec);
                 s.xforms.emplace_back();
+            } else if (t == "moving_sphere") {
+                rt_moving_sphere m;
+                memset(&m, 0, sizeof m);
+                double c0[3], c1[3];
+                r.vec3(o, "center0", where, c0);
+                r.vec3(o, "center1", where, c1);
+                for (int k = 0; k < 3; ++k) m.center0[k] = (float)c0[k], m.center1[k] = (float)c1[k];
+                m.radius = (float)r.num(o, "radius", where);
+                m.material = r.integer(o, "material", where);
+                if (!r.ok) break;
+                const int rc = add_moving_sphere(s, m);
+                if (rc < 0) {  // (the record's own message, with its place in the file)
+                    const std::string why = get_error();
+                    set_error("%s: %s", where, why.c_str());
+                    return -rc;
+                }
             } else if (t == "xy_rect" || t == "xz_rect" || t == "yz_rect") {
                 const char *k0, *k1, *k2, *k3;
                 if (t == "xy_rect") rec.type = RT_PRIM_XY_RECT, k0 = "x0", k1 = "x1", k2 = "y0", k3 = "y1";
@@ -975,6 +997,15 @@ std::string scene_to_json(const Scene &s) {
         default: break;
         }
         o += ", \"material\": " + std::to_string(p.material) + "}";
+    }
+    for (size_t i = 0; i < s.movers.size(); ++i) {  // the moving spheres, behind the primitives
+        const rt_moving_sphere &m = s.movers[i];
+        o += (i || !s.prims.empty()) ? ",\n    " : "\n    ";
+        o += "{\"type\": \"moving_sphere\", \"center0\": ";
+        put_vec3(o, m.center0);
+        o += ", \"center1\": ";
+        put_vec3(o, m.center1);
+        o += ", \"radius\": " + json_float(m.radius) + ", \"material\": " + std::to_string(m.material) + "}";
     }
     o += "\n  ]},\n";
 
@@ -1445,6 +1476,30 @@ int add_medium(Scene &s, const rt_medium &m) {
     s.media.push_back(rec);
     s.touch();
     return (int)s.media.size() - 1;
+}
+
+// ---------------------------------------------------------------- moving spheres
+int add_moving_sphere(Scene &s, const rt_moving_sphere &m) {
+    if (!(std::isfinite(m.radius) && m.radius > 0.0f)) {
+        set_error("moving sphere: radius %g must be finite and > 0", (double)m.radius);
+        return -RT_ERR_SCENE;
+    }
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(m.center0[k]) || !std::isfinite(m.center1[k]) || !std::isfinite(m.center1[k] - m.center0[k])) {
+            set_error("moving sphere: a centre is not finite");
+            return -RT_ERR_SCENE;
+        }
+    if (m.material < 0 || m.material >= (int)s.mats.size()) {
+        set_error("moving sphere: unknown material %d (have %zu)", m.material, s.mats.size());
+        return -RT_ERR_SCENE;
+    }
+    if (s.movers.size() >= (size_t)RT_MAX_MOVING_SPHERES) {
+        set_error("a scene holds at most %d moving spheres", RT_MAX_MOVING_SPHERES);
+        return -RT_ERR_LIMIT;
+    }
+    s.movers.push_back(m);
+    s.touch();
+    return (int)s.movers.size() - 1;
 }
 
 }  // namespace rtmi

@@ -65,6 +65,7 @@ struct Scene {
     std::shared_ptr<const SceneEnvironment> env;  // null: no environment (a miss gives the background / the sky)
     float env_scale = 1.0f, env_rotate = 0.0f;    // radiance = scale x texel; degrees about +y
     std::vector<rt_medium> media;  // homogeneous participating media, a list of its own: at most RT_MAX_MEDIA
+    std::vector<rt_moving_sphere> movers;  // moving spheres, a list of its own: at most RT_MAX_MOVING_SPHERES
     uint64_t version = 1;  // bumped on every mutation; invalidates device caches
     std::shared_ptr<DeviceSceneCache> dev;
 
@@ -113,6 +114,8 @@ int add_obj(Scene &s, const char *path, int material, float scale, const float m
 
 // a medium (scene.cpp): checks the record and appends it -> medium id, or -rt_status
 int add_medium(Scene &s, const rt_medium &m);
+// a moving sphere (scene.cpp): checks the record and appends it -> mover id, or -rt_status
+int add_moving_sphere(Scene &s, const rt_moving_sphere &m);
 
 void set_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
 const char *get_error();

@@ -6,6 +6,7 @@ usage: tools/isa_stats.py [--inst "false,true,false,6,false,true"] [--waves 7] [
        tools/isa_stats.py --aov "false,7"                     (a feature kernel: render_feature_kernel<SCALAR, CULL>)
        tools/isa_stats.py --env "false,7,true,false"          (an environment kernel: render_env_kernel<SCALAR, CULL, NEE, AOV>)
        tools/isa_stats.py --media "false,7" [--media-waves 6] (a media kernel: render_media_kernel<SCALAR, CULL>)
+       tools/isa_stats.py --motion "false,7" [--motion-waves 6] (a motion kernel: render_motion_kernel<SCALAR, CULL>)
 The default instance is the headline kernel (sphere-only x-z grid walk, variant 0 -> 2 on RTIOW)."""
 import argparse, collections, os, re, subprocess, sys, tempfile
 
@@ -13,6 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "ray-tracing-in-cuda_amd", "csrc", "render_kernel.hip")
 SRC_ENV = os.path.join(ROOT, "ray-tracing-in-cuda_amd", "csrc", "render_env.hip")
 SRC_MEDIA = os.path.join(ROOT, "ray-tracing-in-cuda_amd", "csrc", "render_media.hip")
+SRC_MOTION = os.path.join(ROOT, "ray-tracing-in-cuda_amd", "csrc", "render_motion.hip")
 
 
 def main():
@@ -26,12 +28,15 @@ def main():
     ap.add_argument("--env", default=None, help="SCALAR,CULL,NEE,AOV of a render_env_kernel instance instead of --inst")
     ap.add_argument("--media", default=None, help="SCALAR,CULL of a render_media_kernel instance instead of --inst")
     ap.add_argument("--media-waves", type=int, default=None)
+    ap.add_argument("--motion", default=None, help="SCALAR,CULL of a render_motion_kernel instance instead of --inst")
+    ap.add_argument("--motion-waves", type=int, default=None)
     ap.add_argument("--keep", default=None)
     ap.add_argument("extra", nargs="*")
     a = ap.parse_args()
     out = a.keep or os.path.join(tempfile.gettempdir(), "rtmi_isa_%d.s" % os.getpid())
     cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
            "-fno-slp-vectorize", "-DRT_WAVES_PER_SIMD=%d" % a.waves, "-DRT_GROUP=4",
+           ("-DRT_ISA_ONLY_MOTION=" + a.motion) if a.motion else
            ("-DRT_ISA_ONLY_MEDIA=" + a.media) if a.media else
            ("-DRT_ISA_ONLY_ENV=" + a.env) if a.env else
            ("-DRT_ISA_ONLY_AOV=" + a.aov) if a.aov else
@@ -40,11 +45,13 @@ def main():
         cmd.append("-DRT_NEE_WAVES_PER_SIMD=%d" % a.nee_waves)
     if a.media and a.media_waves:
         cmd.append("-DRT_MEDIA_WAVES_PER_SIMD=%d" % a.media_waves)
+    if a.motion and a.motion_waves:
+        cmd.append("-DRT_MOTION_WAVES_PER_SIMD=%d" % a.motion_waves)
     cmd += [
-           "--offload-device-only", "-S", "-o", out, SRC_MEDIA if a.media else SRC_ENV if a.env else SRC] + a.extra
+           "--offload-device-only", "-S", "-o", out, SRC_MOTION if a.motion else SRC_MEDIA if a.media else SRC_ENV if a.env else SRC] + a.extra
     subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
     text = open(out).read()
-    body = text[text.index("render_media_kernel" if a.media else "render_env_kernel" if a.env else "render_feature_kernel" if a.aov else
+    body = text[text.index("render_motion_kernel" if a.motion else "render_media_kernel" if a.media else "render_env_kernel" if a.env else "render_feature_kernel" if a.aov else
                            "render_nee_kernel" if a.nee else ("render_nested_kernel" if a.nested else "render_kernel")):]
     meta = {}
     for key in ("next_free_vgpr", "next_free_sgpr", "private_segment_fixed_size", "group_segment_fixed_size", "accum_offset"):
@@ -77,7 +84,9 @@ def main():
         else:
             continue
         names[op] += 1
-    if a.media:
+    if a.motion:
+        print("render_motion_kernel <%s> at %s waves/SIMD" % (a.motion, a.motion_waves or a.waves))
+    elif a.media:
         print("render_media_kernel <%s> at %s waves/SIMD" % (a.media, a.media_waves or a.waves))
     elif a.env:
         print("render_env_kernel <%s> at %d waves/SIMD (light sampling: %s)" % (a.env, a.waves, a.nee_waves or "the default"))
