@@ -1,5 +1,7 @@
-// The body of the render kernels (render_kernel.hip): included INSIDE render_kernel, render_nee_kernel, render_nested_kernel,
-// render_feature_kernel and render_env_kernel (render_env.hip), after their template arguments and a constexpr NEE, AOV, ENV, MEDIA (render_media_kernel, render_media.hip, is the one with MEDIA on) and MOTION (render_motion_kernel, render_motion.hip).  As text rather than a force-inlined device function, so that the render_kernel
+// The body of the render kernels: included INSIDE render_kernel, render_nee_kernel, render_nested_kernel and render_feature_kernel
+// (render_kernel.hip), render_env_kernel (render_env.hip), render_media_kernel (render_media.hip) and render_motion_kernel
+// (render_motion.hip), after their template arguments and a constexpr NEE, AOV, ENV, MEDIA and MOTION.  The device functions it
+// calls are render_device.h's, which each of those files includes.  As text rather than a force-inlined device function, so that the render_kernel
 // instances compile to the very instructions they did before light sampling came (a device function that takes the
 // kernel's parameters by reference changes the order of the kernel-argument loads and with it the register allocation).
 // Not a header of its own: it needs the kernel's scope (P, image, acc, queue, counters and the template arguments).

@@ -18,47 +18,26 @@
 #include <vector>
 
 #include "device_scene.h"
+#include "kernels.h"
 #include "pack.h"
 #include "scene.hpp"
 #include "shard.h"
 
 namespace rtmi {
 
-bool launch_render(const RenderParams &P, const void *image, unsigned long long *acc, unsigned int *queue,
-                   DevCounters *counters, size_t lds_bytes, unsigned grid, hipStream_t stream, unsigned variant, bool ext);
-int blocks_per_cu(unsigned variant, bool count, size_t lds_bytes, bool ext);
-bool launch_render_nee(const RenderParams &P, const void *image, unsigned long long *acc, unsigned int *queue, size_t lds_bytes,
-                       unsigned grid, hipStream_t stream, unsigned variant);
-bool variant_has_nee(unsigned variant);
-bool launch_render_feature(const RenderParams &P, const void *image, unsigned long long *acc, unsigned int *queue, size_t lds_bytes,
-                           unsigned grid, hipStream_t stream, unsigned layout);
-int blocks_per_cu_feature(unsigned layout, size_t lds_bytes);
-int blocks_per_cu_nee(unsigned variant, size_t lds_bytes);
-bool launch_render_env(const RenderParams &P, const void *image, unsigned long long *acc, unsigned int *queue, size_t lds_bytes,
-                       unsigned grid, hipStream_t stream, unsigned layout, bool nee, bool feature);
-bool layout_has_env(unsigned layout);
-int blocks_per_cu_env(unsigned layout, size_t lds_bytes, bool nee, bool feature);
-bool launch_render_media(const RenderParams &P, const void *image, unsigned long long *acc, unsigned int *queue, size_t lds_bytes,
-                         unsigned grid, hipStream_t stream, unsigned layout);
-bool layout_has_media(unsigned layout);
-int blocks_per_cu_media(unsigned layout, size_t lds_bytes);
-bool launch_render_motion(const RenderParams &P, const void *image, unsigned long long *acc, unsigned int *queue, size_t lds_bytes,
-                          unsigned grid, hipStream_t stream, unsigned layout);
-bool layout_has_motion(unsigned layout);
-int blocks_per_cu_motion(unsigned layout, size_t lds_bytes);
-bool variant_has_ext(unsigned variant);
-bool variant_has_count(unsigned variant);
-bool has_ablations();
-void launch_finalize(const unsigned long long *acc, float *out, size_t n, hipStream_t stream);
-void launch_item_params(unsigned int *queue, const ItemParams &ip, hipStream_t stream);
 void launch_adaptive_estimate(const long long *A, const long long *B, const unsigned int *list, int n_list, unsigned int *next_list,
                               unsigned int *next_count, int *tile_n, int width, int height, int tiles_x, int nA, int nB, int n,
                               bool retire_all, bool use_metric, double t4, hipStream_t stream);
 void launch_adaptive_merge(const long long *A, const long long *B, const int *tile_n, float *out, int *spp_map, int width, int height,
                            int tiles_x, hipStream_t stream);
-int set_max_dynamic_lds(size_t bytes);
-bool variant_exists(unsigned variant);
-int variant_cull_mode(unsigned variant);
+// the row of a render variant (rt_opts.variant, never 0) -- render_kernel, or render_nested_kernel for 52; null: no such build.
+// Its cull is the variant's candidate search.  ext: the build with triangles and image textures; count: the counting build
+static const KernelRow *variant_row(unsigned variant, bool ext = false, bool count = false) {
+    const KernelRow *row = find_kernel({K_PLAIN, variant, ext, count});
+    return row ? row : find_kernel({K_NESTED, variant, ext, count});
+}
+
+static bool variant_exists(unsigned variant) { return variant == 0 || variant_row(variant); }
 
 #define HIP_TRY(expr)                                                                         \
     do {                                                                                      \
@@ -457,12 +436,8 @@ struct Launcher {
     hipStream_t stream;
     size_t lds_bytes;
     unsigned long long resident;  // workgroups that fill the chip
-    unsigned variant;
-    bool ext, nee, count;
-    bool env;     // an environment map: render_env_kernel of layout `variant` (plain, light sampling or feature pass)
-    int feature;  // >= 0: a feature pass (render_feature_kernel of layout `variant`)
-    bool media;   // homogeneous media: render_media_kernel of layout `variant` (never with nee, env or a feature pass)
-    bool motion;  // moving spheres: render_motion_kernel of layout `variant` (never with nee, env, media or a feature pass)
+    const KernelRow &kernel;      // the instance every launch of the call runs (kernels.h)
+    int feature;                  // >= 0: a feature pass
 
     int enqueue(unsigned long long *acc, unsigned int *d_queue, int first, int n, int n_list, const ChunkPlan &pl) const {
         RenderParams Q = P;
@@ -490,41 +465,8 @@ struct Launcher {
         // persistent launch: enough workgroups to fill the chip, never more than the work needs
         const unsigned long long need_blocks = (items + 3) / 4;
         const unsigned long long grid = need_blocks < resident ? (need_blocks ? need_blocks : 1) : resident;
-        if (env) {
-            if (feature >= 0) Q.feature = feature;
-            if (!launch_render_env(Q, ent->d_image, acc, d_queue, lds_bytes, (unsigned)grid, stream, variant, nee, feature >= 0)) {
-                set_error("layout %u has no environment kernel", variant);
-                return RT_ERR_ARG;
-            }
-            return RT_OK;
-        }
-        if (media) {
-            if (!launch_render_media(Q, ent->d_image, acc, d_queue, lds_bytes, (unsigned)grid, stream, variant)) {
-                set_error("layout %u has no media kernel", variant);
-                return RT_ERR_ARG;
-            }
-            return RT_OK;
-        }
-        if (motion) {
-            if (!launch_render_motion(Q, ent->d_image, acc, d_queue, lds_bytes, (unsigned)grid, stream, variant)) {
-                set_error("layout %u has no motion kernel", variant);
-                return RT_ERR_ARG;
-            }
-            return RT_OK;
-        }
-        if (feature >= 0) {
-            Q.feature = feature;
-            if (!launch_render_feature(Q, ent->d_image, acc, d_queue, lds_bytes, (unsigned)grid, stream, variant)) {
-                set_error("layout %u has no feature kernel", variant);
-                return RT_ERR_LIMIT;
-            }
-            return RT_OK;
-        }
-        if (nee ? !launch_render_nee(Q, ent->d_image, acc, d_queue, lds_bytes, (unsigned)grid, stream, variant)
-                : !launch_render(Q, ent->d_image, acc, d_queue, d_cnt, lds_bytes, (unsigned)grid, stream, variant, ext)) {
-            set_error("kernel variant %u has no %s build", variant, count ? "counting" : (ext ? "triangle / texture" : "such"));
-            return RT_ERR_LIMIT;
-        }
+        if (feature >= 0) Q.feature = feature;
+        launch_kernel(kernel, Q, ent->d_image, acc, d_queue, d_cnt, lds_bytes, (unsigned)grid, stream);
         return RT_OK;
     }
 };
@@ -601,7 +543,7 @@ static int run_adaptive(const Launcher &launch, const AdaptiveRun &ad, const Sce
 }
 
 // the counting kernels' counters -> stats (rt_render_hip_count)
-static int read_counters(const DevCounters *d_cnt, const RenderParams &P, unsigned variant, size_t n_prims, rt_stats *stats) {
+static int read_counters(const DevCounters *d_cnt, const RenderParams &P, int cull_mode, size_t n_prims, rt_stats *stats) {
     DevCounters h;
     HIP_TRY(hipMemcpy(&h, d_cnt, sizeof h, hipMemcpyDeviceToHost));
     stats->samples = h.samples;
@@ -645,7 +587,7 @@ static int read_counters(const DevCounters *d_cnt, const RenderParams &P, unsign
     stats->wave_queries = h.wave_queries;
     stats->cull_prefix = P.np, stats->cull_clusters = P.ncl, stats->cull_groups = P.ngr;
     stats->cull_cluster_size = P.cluster;
-    stats->cull_mode = variant_cull_mode(variant), stats->cull_windows = P.nwin;  // (of the kernel that ran)
+    stats->cull_mode = cull_mode, stats->cull_windows = P.nwin;  // (of the kernel that ran)
     stats->grid_sheet = P.grid_sheet;
     return RT_OK;
 }
@@ -826,7 +768,7 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
             set_error("this scene has participating media and the nested grid, which no kernel combines: switch the nested grid off");
             return RT_ERR_ARG;
         }
-        if (!layout_has_media(variant)) {
+        if (!find_kernel({K_MEDIA, variant, true})) {
             set_error("kernel variant %u does not carry participating media (the media kernels are variants 0, 16, 36 and 44)", variant);
             return RT_ERR_ARG;
         }
@@ -844,7 +786,7 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
             set_error("this scene has moving spheres and the nested grid, which no kernel combines: switch the nested grid off");
             return RT_ERR_ARG;
         }
-        if (!layout_has_motion(variant)) {
+        if (!find_kernel({K_MOTION, variant, true})) {
             set_error("kernel variant %u does not carry moving spheres (the motion kernels are variants 0, 16, 36 and 44)", variant);
             return RT_ERR_ARG;
         }
@@ -853,7 +795,7 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
         set_error("this scene has the nested grid and an environment map, which no kernel combines: switch one of them off");
         return RT_ERR_ARG;
     }
-    if (env && (count || !layout_has_env(variant))) {
+    if (env && (count || !find_kernel({K_ENV, variant, true}))) {
         set_error("%s: this scene has an environment map, which the %s (the environment kernels are variants 0, 16, 36 and 44)",
                   count ? "rt_render_hip_count" : "kernel variant", count ? "counting kernels do not carry" : "requested variant does not carry");
         return RT_ERR_ARG;
@@ -862,17 +804,18 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
         set_error("this scene has the nested grid and light sampling on, which no kernel combines: switch one of them off");
         return RT_ERR_ARG;
     }
-    if (nee && (count || !variant_has_nee(variant))) {
+    if (nee && (count || !find_kernel({K_NEE, variant, true}))) {
         set_error("%s: this scene has light sampling on, which the %s (the light-sampling kernels are variants 0, 16, 36 and 44)",
                   count ? "rt_render_hip_count" : "kernel variant", count ? "counting kernels do not carry" : "requested variant does not carry");
         return RT_ERR_ARG;
     }
     // the counting kernels exist for the grid walks (3-D) and two ablation searches: anything else is counted by the kernel
     // variant 0 would run (reported in stats->kernel_variant / cull_mode)
-    if (count && !variant_has_count(variant)) variant = (variant == 2) ? 6u : pick(true);
+    if (count && !variant_row(variant, false, true)) variant = (variant == 2) ? 6u : pick(true);
     if (count && variant == 2) variant = 6;
     // (the feature layouts exist in every build; variant 24 as a render variant only with RTMI_ABLATIONS)
-    const int mode = feature >= 0 ? (variant == 52 ? 8 : (variant == 36 || variant == 44) ? 7 : 0) : variant_cull_mode(variant);
+    const KernelRow *plain = variant_row(variant);
+    const int mode = feature >= 0 ? (variant == 52 ? 8 : (variant == 36 || variant == 44) ? 7 : 0) : plain ? plain->cull : -1;
     // nested cells are walked by variant 52 alone, and variant 52 walks nothing else; the linear scans read no grid
     if (mode == 8 && P.grid_wide != 2) {
         set_error("kernel variant %u walks tables with nested cells, which this scene does not have (rt_scene_set_nested_grid, and a "
@@ -899,7 +842,7 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
         return RT_ERR_LIMIT;
     }
     if (feature >= 0) ext = true;  // (the feature kernels are general builds)
-    if (feature < 0 && ext && !variant_has_ext(variant)) {
+    if (feature < 0 && ext && !variant_row(variant, true)) {
         set_error("kernel variant %u has no build with triangles / image textures (variants 0, 36, 44 and the linear scans 16 / 24 have)", variant);
         return RT_ERR_LIMIT;
     }
@@ -907,7 +850,7 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
         set_error("kernel variant %u is built for sphere-only scenes", variant);
         return RT_ERR_LIMIT;
     }
-    if (force_ext && variant_has_ext(variant) && P.grid_wide) ext = true;
+    if (force_ext && variant_row(variant, true) && P.grid_wide) ext = true;
     if (nee || env || media || motion) ext = true;
     const size_t hot_bytes = hot_bytes_of(mode);
     const bool tables_global = (variant & 8u) != 0 || mode == 8;
@@ -928,10 +871,6 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
                   variant, lds_bytes);
         return RT_ERR_LIMIT;
     }
-    if (lds_bytes > 64 * 1024 && set_max_dynamic_lds(lds_bytes)) {
-        set_error("cannot raise the dynamic LDS limit to %zu bytes", lds_bytes);
-        return RT_ERR_HIP;
-    }
     if (s.width > 65536 || P.bands > 32767) {  // the kernel packs (tile x0, band) of a wave's older item into one register
         set_error("frame of %d x %d rows per shard exceeds the tile index range (65536 columns, 262136 rows)", s.width,
                   sh.local_rows);
@@ -950,13 +889,24 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
         HIP_TRY(hipGetDeviceProperties(&prop, device));
         ent->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     }
-    const unsigned long long resident =
-        (unsigned long long)ent->num_cus * (motion       ? blocks_per_cu_motion(variant, lds_bytes)
-                                            : media      ? blocks_per_cu_media(variant, lds_bytes)
-                                            : env        ? blocks_per_cu_env(variant, lds_bytes, nee, feature >= 0)
-                                            : feature >= 0 ? blocks_per_cu_feature(variant, lds_bytes)
-                                            : nee  ? blocks_per_cu_nee(variant, lds_bytes)
-                                                   : blocks_per_cu(variant, count, lds_bytes, ext));
+    // ---- the instance: resolved once; the launches, the grid size and the LDS limit go through its row
+    const char *family = env ? "environment" : media ? "media" : motion ? "motion" : feature >= 0 ? "feature" : nullptr;
+    const KernelRow *kernel = env            ? find_kernel({K_ENV, variant, true, false, nee, feature >= 0})
+                              : media        ? find_kernel({K_MEDIA, variant, true})
+                              : motion       ? find_kernel({K_MOTION, variant, true})
+                              : feature >= 0 ? find_kernel({K_FEATURE, variant, true})
+                              : nee          ? find_kernel({K_NEE, variant, true})
+                                             : variant_row(variant, ext, count);
+    if (!kernel) {
+        if (family) set_error("layout %u has no %s kernel", variant, family);
+        else set_error("kernel variant %u has no %s build", variant, count ? "counting" : (ext ? "triangle / texture" : "such"));
+        return env || media || motion ? RT_ERR_ARG : RT_ERR_LIMIT;
+    }
+    if (lds_bytes > 64 * 1024 && set_max_dynamic_lds(*kernel, lds_bytes)) {
+        set_error("cannot raise the dynamic LDS limit to %zu bytes", lds_bytes);
+        return RT_ERR_HIP;
+    }
+    const unsigned long long resident = (unsigned long long)ent->num_cus * blocks_per_cu(*kernel, lds_bytes);
 
     float *d_out = (float *)d_rgb_sum;
     DevCounters *d_cnt = nullptr;
@@ -977,7 +927,7 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     const size_t queue_off = (plane * sizeof(unsigned long long) + 255) & ~(size_t)255;
     const long long frame_tiles = (long long)P.tiles_x * P.bands;
     const size_t need = queue_off + (ad ? (((size_t)(RT_TILE_LIST_AT + frame_tiles) * 4 + 255) & ~(size_t)255) : 256);
-    const Launcher launch{P, sh, ent, d_cnt, stream, lds_bytes, resident, variant, ext, nee, count, env, feature, media, motion};
+    const Launcher launch{P, sh, ent, d_cnt, stream, lds_bytes, resident, *kernel, feature};
 
     int launches = 0;
     if (ad) {
@@ -1022,7 +972,7 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
         stats->upload_ms = up;
         stats->kernel_ms = k;
         stats->launches = launches;
-        if (count) return read_counters(d_cnt, P, variant, s.prims.size(), stats);
+        if (count) return read_counters(d_cnt, P, kernel->cull, s.prims.size(), stats);
     }
     return RT_OK;
 }

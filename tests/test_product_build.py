@@ -1,6 +1,7 @@
 """The product build (make ABLATIONS=0 -> librtmi_product.so): the product kernels alone -- no measurement variants, no
 counting kernels, no RTMI_* environment knobs -- behind the same C ABI.  The default library (librtmi.so), which the rest
 of the tests and bench.py load, carries all of those."""
+import json
 import os
 import re
 import subprocess
@@ -35,6 +36,17 @@ def test_product_library_has_the_same_abi_and_only_the_product_kernels():
                            "false, true, false, 0, false, false", "false, true, false, 0, true, false"])
     assert set(prod) < set(full) and len(full) >= len(prod) + 10
     assert "getenv" not in subprocess.run(["nm", "-D", "--undefined-only", PRODUCT], capture_output=True, text=True).stdout
+
+
+def test_both_libraries_hold_exactly_the_recorded_kernel_instances():
+    """every render*_kernel instance of the two libraries, by its demangled host stub: the kernel tables (csrc/kernels.h) list
+    what tests/golden/kernel_instances.json records, no instance more and none less"""
+    with open(os.path.join(ROOT, "tests", "golden", "kernel_instances.json")) as f:
+        want = json.load(f)
+    assert sorted(want) == ["librtmi.so", "librtmi_product.so"]
+    for name, lib in (("librtmi.so", DEFAULT), ("librtmi_product.so", PRODUCT)):
+        got = sorted(set(re.findall(r"__device_stub__(render\w*_kernel<[^>]*>)", _nm(lib))))
+        assert got == want[name], (name, sorted(set(got) ^ set(want[name])))
 
 
 _SCRIPT = textwrap.dedent("""

@@ -1,58 +1,40 @@
 #!/usr/bin/env python3
-"""Static picture of ONE render_kernel instance (no GPU needed): registers, scratch, instruction mix.
+"""Static picture of ONE render kernel instance (no GPU needed): registers, scratch, instruction mix.
 usage: tools/isa_stats.py [--inst "false,true,false,6,false,true"] [--waves 7] [--keep out.s] [-- extra hipcc flags]
-       tools/isa_stats.py --nee "false,7" [--nee-waves 6]     (a light-sampling kernel: render_nee_kernel<SCALAR, CULL>)
-       tools/isa_stats.py --nested "false,true"               (a nested-grid kernel: render_nested_kernel<COUNT, EXT>)
-       tools/isa_stats.py --aov "false,7"                     (a feature kernel: render_feature_kernel<SCALAR, CULL>)
-       tools/isa_stats.py --env "false,7,true,false"          (an environment kernel: render_env_kernel<SCALAR, CULL, NEE, AOV>)
-       tools/isa_stats.py --media "false,7" [--media-waves 6] (a media kernel: render_media_kernel<SCALAR, CULL>)
-       tools/isa_stats.py --motion "false,7" [--motion-waves 6] (a motion kernel: render_motion_kernel<SCALAR, CULL>)
-The default instance is the headline kernel (sphere-only x-z grid walk, variant 0 -> 2 on RTIOW)."""
+       tools/isa_stats.py --kernel "render_nee_kernel<false,7>"               (light sampling: <SCALAR, CULL>)
+       tools/isa_stats.py --kernel "render_nested_kernel<false,true>"         (the nested grid: <COUNT, EXT>)
+       tools/isa_stats.py --kernel "render_feature_kernel<false,7>"           (a feature pass: <SCALAR, CULL>)
+       tools/isa_stats.py --kernel "render_env_kernel<false,7,true,false>"    (an environment map: <SCALAR, CULL, NEE, AOV>)
+       tools/isa_stats.py --kernel "render_media_kernel<false,7>" -- -DRT_MEDIA_WAVES_PER_SIMD=6    (media: <SCALAR, CULL>)
+       tools/isa_stats.py --kernel "render_motion_kernel<false,7>"            (moving spheres: <SCALAR, CULL>)
+--inst ARGS is short for --kernel "render_kernel<ARGS>"; the default instance is the headline kernel (sphere-only x-z grid walk,
+variant 0 -> 2 on RTIOW).  The families whose register budget is not --waves take theirs after "--":
+-DRT_NEE_WAVES_PER_SIMD=N (render_nee_kernel, render_env_kernel with NEE), -DRT_MEDIA_WAVES_PER_SIMD=N, -DRT_MOTION_WAVES_PER_SIMD=N."""
 import argparse, collections, os, re, subprocess, sys, tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "ray-tracing-in-cuda_amd", "csrc", "render_kernel.hip")
-SRC_ENV = os.path.join(ROOT, "ray-tracing-in-cuda_amd", "csrc", "render_env.hip")
-SRC_MEDIA = os.path.join(ROOT, "ray-tracing-in-cuda_amd", "csrc", "render_media.hip")
-SRC_MOTION = os.path.join(ROOT, "ray-tracing-in-cuda_amd", "csrc", "render_motion.hip")
+# the translation unit of a kernel template (render_nee_kernel, render_nested_kernel and render_feature_kernel live in render_kernel.hip too)
+SOURCES = {"render_kernel": "render_kernel.hip", "render_env_kernel": "render_env.hip", "render_media_kernel": "render_media.hip",
+           "render_motion_kernel": "render_motion.hip"}
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--inst", default="false,true,false,6,false,true")
+    ap.add_argument("--inst", default="false,true,false,6,false,true", help="template arguments of a render_kernel instance")
+    ap.add_argument("--kernel", default=None, help="a whole template-id instead of --inst, e.g. 'render_media_kernel<false,7>'")
     ap.add_argument("--waves", type=int, default=7)
-    ap.add_argument("--nee", default=None, help="SCALAR,CULL of a render_nee_kernel instance instead of --inst")
-    ap.add_argument("--nee-waves", type=int, default=None)
-    ap.add_argument("--nested", default=None, help="COUNT,EXT of a render_nested_kernel instance instead of --inst")
-    ap.add_argument("--aov", default=None, help="SCALAR,CULL of a render_feature_kernel instance instead of --inst")
-    ap.add_argument("--env", default=None, help="SCALAR,CULL,NEE,AOV of a render_env_kernel instance instead of --inst")
-    ap.add_argument("--media", default=None, help="SCALAR,CULL of a render_media_kernel instance instead of --inst")
-    ap.add_argument("--media-waves", type=int, default=None)
-    ap.add_argument("--motion", default=None, help="SCALAR,CULL of a render_motion_kernel instance instead of --inst")
-    ap.add_argument("--motion-waves", type=int, default=None)
     ap.add_argument("--keep", default=None)
     ap.add_argument("extra", nargs="*")
     a = ap.parse_args()
+    name, args = re.fullmatch(r"(\w+)<(.*)>", a.kernel or "render_kernel<%s>" % a.inst).groups()
+    src = os.path.join(ROOT, "ray-tracing-in-cuda_amd", "csrc", SOURCES.get(name, SOURCES["render_kernel"]))
     out = a.keep or os.path.join(tempfile.gettempdir(), "rtmi_isa_%d.s" % os.getpid())
     cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
-           "-fno-slp-vectorize", "-DRT_WAVES_PER_SIMD=%d" % a.waves, "-DRT_GROUP=4",
-           ("-DRT_ISA_ONLY_MOTION=" + a.motion) if a.motion else
-           ("-DRT_ISA_ONLY_MEDIA=" + a.media) if a.media else
-           ("-DRT_ISA_ONLY_ENV=" + a.env) if a.env else
-           ("-DRT_ISA_ONLY_AOV=" + a.aov) if a.aov else
-           ("-DRT_ISA_ONLY_NEE=" + a.nee) if a.nee else (("-DRT_ISA_ONLY_NESTED=" + a.nested) if a.nested else ("-DRT_ISA_ONLY=" + a.inst))]
-    if (a.nee or a.env) and a.nee_waves:
-        cmd.append("-DRT_NEE_WAVES_PER_SIMD=%d" % a.nee_waves)
-    if a.media and a.media_waves:
-        cmd.append("-DRT_MEDIA_WAVES_PER_SIMD=%d" % a.media_waves)
-    if a.motion and a.motion_waves:
-        cmd.append("-DRT_MOTION_WAVES_PER_SIMD=%d" % a.motion_waves)
-    cmd += [
-           "--offload-device-only", "-S", "-o", out, SRC_MOTION if a.motion else SRC_MEDIA if a.media else SRC_ENV if a.env else SRC] + a.extra
+           "-fno-slp-vectorize", "-DRT_WAVES_PER_SIMD=%d" % a.waves, "-DRT_GROUP=4", "-DRT_ISA_ONLY=%s<%s>" % (name, args),
+           "--offload-device-only", "-S", "-o", out, src] + a.extra
     subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
     text = open(out).read()
-    body = text[text.index("render_motion_kernel" if a.motion else "render_media_kernel" if a.media else "render_env_kernel" if a.env else "render_feature_kernel" if a.aov else
-                           "render_nee_kernel" if a.nee else ("render_nested_kernel" if a.nested else "render_kernel")):]
+    body = text[text.index(name):]
     meta = {}
     for key in ("next_free_vgpr", "next_free_sgpr", "private_segment_fixed_size", "group_segment_fixed_size", "accum_offset"):
         m = re.search(r"amdhsa_%s (\d+)" % key, text)
@@ -84,20 +66,17 @@ def main():
         else:
             continue
         names[op] += 1
-    if a.motion:
-        print("render_motion_kernel <%s> at %s waves/SIMD" % (a.motion, a.motion_waves or a.waves))
-    elif a.media:
-        print("render_media_kernel <%s> at %s waves/SIMD" % (a.media, a.media_waves or a.waves))
-    elif a.env:
-        print("render_env_kernel <%s> at %d waves/SIMD (light sampling: %s)" % (a.env, a.waves, a.nee_waves or "the default"))
-    elif a.aov:
-        print("render_feature_kernel <%s> at %d waves/SIMD" % (a.aov, a.waves))
-    elif a.nested:
-        print("render_nested_kernel <%s> at %d waves/SIMD" % (a.nested, a.waves))
-    elif a.nee:
-        print("render_nee_kernel <%s> at %s waves/SIMD" % (a.nee, a.nee_waves or "the default"))
+    own = dict(re.findall(r"-D(RT_\w+_WAVES_PER_SIMD)=(\d+)", " ".join(a.extra)))  # a family's own budget, where it was given
+    if name == "render_kernel":
+        print("instance <%s> at %d waves/SIMD" % (args, a.waves))
+    elif name == "render_nee_kernel":
+        print("render_nee_kernel <%s> at %s waves/SIMD" % (args, own.get("RT_NEE_WAVES_PER_SIMD", "the default")))
+    elif name == "render_env_kernel":
+        print("render_env_kernel <%s> at %d waves/SIMD (light sampling: %s)" % (args, a.waves, own.get("RT_NEE_WAVES_PER_SIMD", "the default")))
+    elif name in ("render_media_kernel", "render_motion_kernel"):
+        print("%s <%s> at %s waves/SIMD" % (name, args, own.get("RT_%s_WAVES_PER_SIMD" % name.split("_")[1].upper(), a.waves)))
     else:
-        print("instance <%s> at %d waves/SIMD" % (a.inst, a.waves))
+        print("%s <%s> at %d waves/SIMD" % (name, args, a.waves))
     print("  registers:", meta)
     print("  static instruction mix:", dict(mix), "total", sum(mix.values()))
     hot = ["v_readlane_b32", "v_writelane_b32", "v_mov_b32_e32", "v_cndmask_b32_e32", "v_cndmask_b32_e64", "scratch_load_dword",
