@@ -597,6 +597,10 @@ int rt_quantize_rgb8(const float *rgb_sum, int width, int height, int spp, int g
 /* write_image(), gpu-version/color.cuh:15-35 (called at main.cu:514 with json["output_file"]):
  * 8-bit RGB PNG, rows top to bottom; gamma = 0 is the reference's linear image. */
 int rt_write_png(const char *path, const float *rgb_sum, int width, int height, int spp, int gamma);
+/* the same two files from bytes that are already quantised (width*height*3, rows top to bottom: what rt_quantize_rgb8 and
+ * rt_display_hip's out_rgb8 hold); rt_write_ppm and rt_write_png quantise and then go through these */
+int rt_write_ppm_rgb8(const char *path, const uint8_t *rgb8, int width, int height);
+int rt_write_png_rgb8(const char *path, const uint8_t *rgb8, int width, int height);
 /* the scene's "output_file" (parser.hpp:566-567, default "main.png") */
 const char *rt_scene_output_file(const rt_scene *s);
 
@@ -606,7 +610,8 @@ const char *rt_status_string(int status);
 int rt_abi_version(void);
 /* sizeof of the ABI structs as this library was compiled (binding self-checks):
  * 0 rt_opts, 1 rt_stats, 2 rt_prim, 3 rt_material, 4 rt_texture, 5 rt_camera, 6 rt_scene_info, 7 rt_table_info,
- * 8 rt_adaptive, 9 rt_adaptive_stats, 10 rt_nested_info, 16 rt_denoise, 17 rt_medium, 18 rt_moving_sphere; else 0 */
+ * 8 rt_adaptive, 9 rt_adaptive_stats, 10 rt_nested_info, 16 rt_denoise, 17 rt_medium, 18 rt_moving_sphere, 19 rt_display,
+ * 20 rt_display_stats; else 0 */
 size_t rt_struct_size(int which);
 /* number of usable gfx950 devices, or -rt_status */
 int rt_device_count(void);
@@ -727,6 +732,59 @@ int rt_denoise_hip(int width, int height, const float *rgb_sum, int spp, const i
 int rt_denoise_hip_device(int width, int height, const void *d_rgb_sum, int spp, const void *d_spp_map,
                           const void *d_albedo_sum, const void *d_normal_sum, const void *d_depth_sum, int feature_spp,
                           const rt_denoise *p, int device, void *d_out_rgb_sum, void *stream, double *ms);
+
+/* ---- display stage: exposure, bloom, tone curve, 8-bit quantisation; HDR files ---------------------------------
+ * Runs after the render (and after rt_denoise_hip where that is used) on a whole frame of sums.  The definition -- mean,
+ * auto exposure from an exact integer log-luminance sum, scale, bloom as the mean of the smooth planes of a B3-spline a-trous
+ * transform, tone curve, quantisation -- is DESIGN.md section 7i; every device operation in it is a single fp32 + - x / min
+ * max sqrt in a fixed order (no exp / log / pow), so a numpy float32 restatement reproduces both outputs bit for bit. */
+typedef enum rt_tonemap { RT_TONEMAP_CLAMP = 0, RT_TONEMAP_REINHARD = 1, RT_TONEMAP_ACES = 2 } rt_tonemap;
+typedef struct rt_display {
+    int32_t tonemap;          /* rt_tonemap */
+    float   exposure;         /* linear multiplier > 0; 0 -> 1 */
+    float   auto_key;         /* > 0: exposure is chosen from the frame (the log-average luminance is mapped to auto_key)
+                                 and `exposure` multiplies it; 0: off */
+    float   white;            /* Reinhard's white point > 0; 0 -> 4 */
+    float   bloom_strength;   /* >= 0; 0: no bloom, no bloom kernels are launched */
+    float   bloom_threshold;  /* >= 0; 0 is a valid value here, not a stand-in for a default; all-defaults is a NULL rt_display */
+    int32_t bloom_levels;     /* 1 .. 8; 0 -> 5 */
+} rt_display;
+typedef struct rt_display_stats {
+    int64_t log_sum;          /* auto exposure: sum over pixels of (bits of the clamped luminance) - 0x3F800000; 0 when off */
+    float   exposure_used;    /* the multiplier E the pixels were scaled by */
+    double  ms;               /* hipEvent time of the kernels */
+} rt_display_stats;
+
+/* rgb_sum, spp, spp_map: as for rt_denoise_hip (H*W*3 floats, row 0 at the bottom; an spp_map entry < 1 counts as 1).
+ * out_rgb (H*W*3 floats, same layout): display-referred linear colour, a sum over ONE sample -- the writers take it with
+ * spp = 1.  out_rgb8 (H*W*3 bytes, rows top to bottom): int(256 clamp(sqrt(out_rgb), 0, 0.999)), what
+ * rt_quantize_rgb8(out_rgb, W, H, 1, 1, .) gives.  Either output may be NULL, not both.  p == NULL: all defaults (clamp,
+ * E = 1, no bloom): out_rgb is rgb_sum / n, and out_rgb8 is what rt_quantize_rgb8(rgb_sum, W, H, spp, 1, .) writes -- whenever
+ * the stage is ASKED to be this identity (p == NULL, or clamp with exposure 0 or 1, auto_key 0 and bloom_strength 0: a matter of
+ * the parameters, never of a computed exposure) the byte is taken from the sum in the writer's own form, sqrt(rgb_sum x (1 / n)),
+ * which can differ from sqrt(rgb_sum / n) -- the byte of out_rgb -- in the last bit.
+ * RT_ERR_ARG, checked before any device access, for: a null input, both outputs null, a size <= 0 (or > 65536), spp <= 0
+ * without an spp_map, a negative or non-finite field, tonemap outside 0 .. 2, bloom_levels outside 0 .. 8.  st may be NULL. */
+int rt_display_hip(int width, int height, const float *rgb_sum, int spp, const int32_t *spp_map, const rt_display *p, int device,
+                   float *out_rgb, uint8_t *out_rgb8, rt_display_stats *st);
+/* the same on DEVICE buffers of device `device`, enqueued on `stream` (hipStream_t as void*); asynchronous when st == NULL and
+ * auto_key == 0 (auto exposure reads its sum back once, which waits for the stream).  Scratch buffers (four planes of 16 bytes
+ * per pixel) are kept per device between calls: overlapping calls on one device must share a stream. */
+int rt_display_hip_device(int width, int height, const void *d_rgb_sum, int spp, const void *d_spp_map, const rt_display *p,
+                          int device, void *d_out_rgb, void *d_out_rgb8, void *stream, rt_display_stats *st);
+/* A measuring hook, not part of the stage's interface (tools/gpu_display.py reads it; nothing else needs it): the
+ * hipEvent times (ms) of the single kernels of this thread's last rt_display_hip* call that had st != NULL, in launch order:
+ * [reduction (auto exposure only),] prepare, [blur level 0 horizontal, vertical, level 1 ...,] finish.  Copies at most cap
+ * entries; returns the number of kernels. */
+int rt_display_timing(double *ms, int cap);
+
+/* The MEAN image rgb_sum / spp -- scene-referred: no exposure, no curve -- as a float image file.  Both are read back by
+ * rt_scene_set_environment_file with the image's top row as the zenith row.  RT_ERR_ARG / RT_ERR_IO as the other writers.
+ * rt_write_hdr: Radiance RGBE, "-Y H +X W", rows top to bottom, flat scanlines; the exponent comes from the largest channel
+ * and mantissas are truncated (negative and NaN channels are written as 0).
+ * rt_write_pfm: "PF", scale -1.0 (little-endian), rows bottom to top: the framebuffer's own order. */
+int rt_write_hdr(const char *path, const float *rgb_sum, int width, int height, int spp);
+int rt_write_pfm(const char *path, const float *rgb_sum, int width, int height, int spp);
 
 #ifdef __cplusplus
 }

@@ -366,6 +366,20 @@ public:
                              normal_sum.data(), depth_sum.data(), feature_spp, params, device, out.data(), ms), "denoise");
         return out;
     }
+    // the display stage on a whole frame of this scene (rt_display_hip): exposure, bloom, tone curve -> the quantised bytes, rows
+    // top to bottom, and -- if out_rgb != nullptr -- the display-referred linear colour (a sum over one sample)
+    std::vector<uint8_t> display(const std::vector<float> &rgb_sum, int spp, const rt_display *params = nullptr,
+                                 const std::vector<int32_t> *spp_map = nullptr, int device = 0, std::vector<float> *out_rgb = nullptr,
+                                 rt_display_stats *stats = nullptr) const {
+        const rt_scene_info i = info();
+        const size_t n = (size_t)i.width * i.height * 3;
+        if (rgb_sum.size() != n || (spp_map && spp_map->size() * 3 != n)) throw error(RT_ERR_ARG, "display: buffer sizes");
+        std::vector<uint8_t> out8(n);
+        if (out_rgb) out_rgb->resize(n);
+        check(rt_display_hip(i.width, i.height, rgb_sum.data(), spp, spp_map ? spp_map->data() : nullptr, params, device,
+                             out_rgb ? out_rgb->data() : nullptr, out8.data(), stats), "display");
+        return out8;
+    }
     rt_scene *handle() const { return s_; }
 
 private:

@@ -178,6 +178,19 @@ class Denoise(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float)]
 
 
+class Display(C.Structure):
+    """rt_display (include/rtmi.h): the display stage's parameters; exposure, white and bloom_levels 0 are their defaults."""
+    _fields_ = [("tonemap", C.c_int32), ("exposure", C.c_float), ("auto_key", C.c_float), ("white", C.c_float),
+                ("bloom_strength", C.c_float), ("bloom_threshold", C.c_float), ("bloom_levels", C.c_int32)]
+
+
+class DisplayStats(C.Structure):
+    """rt_display_stats (include/rtmi.h)."""
+    _fields_ = [("log_sum", C.c_int64), ("exposure_used", C.c_float), ("ms", C.c_double)]
+
+
+TONEMAP_CLAMP, TONEMAP_REINHARD, TONEMAP_ACES = 0, 1, 2
+TONEMAPS = {"clamp": TONEMAP_CLAMP, "reinhard": TONEMAP_REINHARD, "aces": TONEMAP_ACES}
 FEATURE_ALBEDO, FEATURE_NORMAL, FEATURE_DEPTH = 0, 1, 2
 DENOISE_DEFAULT_ITERATIONS = -1
 
@@ -283,6 +296,14 @@ _sig("rt_denoise_hip", C.c_int, C.c_int, C.c_int, _p, C.c_int, _p, _p, _p, _p, C
      C.POINTER(C.c_double))
 _sig("rt_denoise_hip_device", C.c_int, C.c_int, C.c_int, _p, C.c_int, _p, _p, _p, _p, C.c_int, C.POINTER(Denoise), C.c_int, _p, _p,
      C.POINTER(C.c_double))
+_sig("rt_display_hip", C.c_int, C.c_int, C.c_int, _p, C.c_int, _p, C.POINTER(Display), C.c_int, _p, _p, C.POINTER(DisplayStats))
+_sig("rt_display_hip_device", C.c_int, C.c_int, C.c_int, _p, C.c_int, _p, C.POINTER(Display), C.c_int, _p, _p, _p,
+     C.POINTER(DisplayStats))
+_sig("rt_display_timing", C.c_int, C.POINTER(C.c_double), C.c_int)
+_sig("rt_write_ppm_rgb8", C.c_int, C.c_char_p, _p, C.c_int, C.c_int)
+_sig("rt_write_png_rgb8", C.c_int, C.c_char_p, _p, C.c_int, C.c_int)
+_sig("rt_write_hdr", C.c_int, C.c_char_p, _p, C.c_int, C.c_int, C.c_int)
+_sig("rt_write_pfm", C.c_int, C.c_char_p, _p, C.c_int, C.c_int, C.c_int)
 
 C_SYMBOLS = [
     "rt_last_error", "rt_status_string", "rt_abi_version", "rt_struct_size", "rt_device_count", "rt_has_ablations", "rt_opts_default",
@@ -308,6 +329,8 @@ C_SYMBOLS = [
     "rt_scene_add_moving_sphere", "rt_scene_moving_sphere_count", "rt_scene_get_moving_spheres", "rt_scene_clear_moving_spheres",
     "rt_moving_sphere_hit", "rt_shutter_time",
     "rt_render_hip_feature", "rt_render_hip_feature_device", "rt_denoise_hip", "rt_denoise_hip_device",
+    "rt_display_hip", "rt_display_hip_device", "rt_display_timing", "rt_write_hdr", "rt_write_pfm",
+    "rt_write_ppm_rgb8", "rt_write_png_rgb8",
 ]
 
 
@@ -787,6 +810,67 @@ def denoise(rgb_sum, spp, albedo_sum, normal_sum, depth_sum, feature_spp, *, spp
     if timing is not None:
         timing.append(ms.value)
     return out
+
+
+def display(rgb_sum, spp, *, spp_map=None, tonemap=None, exposure=0.0, auto_key=0.0, white=0.0, bloom_strength=0.0,
+            bloom_threshold=0.0, bloom_levels=0, device=0, want_rgb=True, want_rgb8=True, stats=None):
+    """The display stage (rt_display_hip) on an (H, W, 3) frame of SUMS over `spp` samples per pixel -- or over
+    spp_map[y, x] samples.  tonemap: None (a NULL rt_display when every other parameter is at its default too), a name of
+    TONEMAPS or its number.  Returns (out_rgb, out_rgb8): display-referred linear colour, (H, W, 3) float32 with row 0 at the
+    bottom (the writers take it with spp = 1), and its quantised bytes, (H, W, 3) uint8 with row 0 at the TOP; None for an
+    output that was not wanted.  stats: a DisplayStats to fill."""
+    rgb = np.ascontiguousarray(rgb_sum, dtype=np.float32)
+    if rgb.ndim != 3 or rgb.shape[2] != 3:
+        raise ValueError("display: rgb_sum must have shape (height, width, 3)")
+    h, w = rgb.shape[:2]
+    m = None
+    if spp_map is not None:
+        m = np.ascontiguousarray(spp_map, dtype=np.int32)
+        if m.shape != (h, w):
+            raise ValueError("display: spp_map must have shape (height, width)")
+    p = None
+    if tonemap is not None or any((exposure, auto_key, white, bloom_strength, bloom_threshold, bloom_levels)):
+        t = TONEMAPS[tonemap] if isinstance(tonemap, str) else int(tonemap or 0)
+        p = Display(tonemap=t, exposure=float(exposure), auto_key=float(auto_key), white=float(white),
+                    bloom_strength=float(bloom_strength), bloom_threshold=float(bloom_threshold), bloom_levels=int(bloom_levels))
+    out = np.empty_like(rgb) if want_rgb else None
+    out8 = np.empty((h, w, 3), dtype=np.uint8) if want_rgb8 else None
+    _check(_lib.rt_display_hip(w, h, rgb.ctypes.data_as(C.c_void_p), int(spp), m.ctypes.data_as(C.c_void_p) if m is not None else None,
+                               C.byref(p) if p is not None else None, int(device),
+                               out.ctypes.data_as(C.c_void_p) if want_rgb else None,
+                               out8.ctypes.data_as(C.c_void_p) if want_rgb8 else None,
+                               C.byref(stats) if stats is not None else None), "rt_display_hip")
+    return out, out8
+
+
+def display_device(width, height, d_rgb_sum, spp, d_out_rgb, d_out_rgb8, stream=0, *, d_spp_map=None, params=None, device=0,
+                   stats=None):
+    """rt_display_hip_device: the display stage on DEVICE buffers (addresses as integers; an output may be None), enqueued on
+    `stream` (a hipStream_t as an integer); params: a Display or None (all defaults)."""
+    _check(_lib.rt_display_hip_device(int(width), int(height), d_rgb_sum, int(spp), d_spp_map,
+                                      C.byref(params) if params is not None else None, int(device), d_out_rgb, d_out_rgb8,
+                                      stream or None, C.byref(stats) if stats is not None else None), "rt_display_hip_device")
+
+
+def display_timing():
+    """hipEvent ms of the single kernels of this thread's last display call that had stats, in launch order (rt_display_timing)."""
+    buf = (C.c_double * 32)()
+    n = _lib.rt_display_timing(buf, 32)
+    return list(buf[:n])
+
+
+def write_hdr(image: np.ndarray, samples_per_pixel: int, filename: str):
+    """The mean image as a Radiance RGBE file (rt_write_hdr); rt_scene_set_environment_file reads it back."""
+    img = np.ascontiguousarray(image, dtype=np.float32)
+    _check(_lib.rt_write_hdr(os.fsencode(filename), img.ctypes.data_as(C.c_void_p), img.shape[1], img.shape[0], samples_per_pixel),
+           "rt_write_hdr")
+
+
+def write_pfm(image: np.ndarray, samples_per_pixel: int, filename: str):
+    """The mean image as a little-endian colour PFM file (rt_write_pfm)."""
+    img = np.ascontiguousarray(image, dtype=np.float32)
+    _check(_lib.rt_write_pfm(os.fsencode(filename), img.ctypes.data_as(C.c_void_p), img.shape[1], img.shape[0], samples_per_pixel),
+           "rt_write_pfm")
 
 
 def _guess_status() -> int:

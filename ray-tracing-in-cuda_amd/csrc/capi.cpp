@@ -1,5 +1,6 @@
 // C ABI glue (include/rtmi.h): scene I/O and building, table read-back, PPM output.
 // The render entry points live in render_host.hip.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -7,6 +8,7 @@
 #include <new>
 #include <sstream>
 #include <string>
+#include <vector>
 
 #include "philox.h"
 #include "rt_env.h"
@@ -56,6 +58,8 @@ size_t rt_struct_size(int which) {
     case 16: return sizeof(rt_denoise);  // (11 .. 15 stay 0: the next structs of the scene / render interface)
     case 17: return sizeof(rt_medium);
     case 18: return sizeof(rt_moving_sphere);
+    case 19: return sizeof(rt_display);
+    case 20: return sizeof(rt_display_stats);
     default: return 0;
     }
 }
@@ -595,9 +599,10 @@ int rt_quantize_rgb8(const float *rgb_sum, int width, int height, int spp, int g
     return RT_OK;
 }
 
-int rt_write_ppm(const char *path, const float *rgb_sum, int width, int height, int spp) {
-    if (!path || !rgb_sum || width <= 0 || height <= 0 || spp <= 0) {
-        set_error("rt_write_ppm: bad argument");
+// the P3 text of bytes that are already quantised, rows top to bottom
+int rt_write_ppm_rgb8(const char *path, const uint8_t *rgb8, int width, int height) {
+    if (!path || !rgb8 || width <= 0 || height <= 0) {
+        set_error("rt_write_ppm_rgb8: bad argument");
         return RT_ERR_ARG;
     }
     FILE *fp = fopen(path, "w");
@@ -609,12 +614,11 @@ int rt_write_ppm(const char *path, const float *rgb_sum, int width, int height, 
     buf.reserve((size_t)width * 12 + 64);
     fprintf(fp, "P3\n%d %d\n255\n", width, height);  // main.cu:363
     char line[48];
-    for (int j = height - 1; j >= 0; --j) {
+    for (int j = 0; j < height; ++j) {
         buf.clear();
         for (int i = 0; i < width; ++i) {
-            const float *p = rgb_sum + ((size_t)j * width + i) * 3;
-            int n = snprintf(line, sizeof line, "%d %d %d\n", quantize(p[0], spp, 1), quantize(p[1], spp, 1),
-                             quantize(p[2], spp, 1));
+            const uint8_t *p = rgb8 + ((size_t)j * width + i) * 3;
+            int n = snprintf(line, sizeof line, "%d %d %d\n", p[0], p[1], p[2]);
             buf.append(line, (size_t)n);
         }
         if (fwrite(buf.data(), 1, buf.size(), fp) != buf.size()) {
@@ -628,6 +632,16 @@ int rt_write_ppm(const char *path, const float *rgb_sum, int width, int height, 
         return RT_ERR_IO;
     }
     return RT_OK;
+}
+
+int rt_write_ppm(const char *path, const float *rgb_sum, int width, int height, int spp) {
+    if (!path || !rgb_sum || width <= 0 || height <= 0 || spp <= 0) {
+        set_error("rt_write_ppm: bad argument");
+        return RT_ERR_ARG;
+    }
+    std::vector<uint8_t> rgb8((size_t)width * height * 3);
+    rt_quantize_rgb8(rgb_sum, width, height, spp, 1, rgb8.data());
+    return rt_write_ppm_rgb8(path, rgb8.data(), width, height);
 }
 
 // write_image(), gpu-version/color.cuh:15-35: 8-bit RGB PNG of the LINEAR means (no gamma), rows top
@@ -665,13 +679,23 @@ int rt_write_png(const char *path, const float *rgb_sum, int width, int height, 
         set_error("rt_write_png: bad argument");
         return RT_ERR_ARG;
     }
+    std::vector<uint8_t> rgb8((size_t)width * height * 3);
+    rt_quantize_rgb8(rgb_sum, width, height, spp, gamma, rgb8.data());
+    return rt_write_png_rgb8(path, rgb8.data(), width, height);
+}
+
+// the encoder: bytes that are already quantised, rows top to bottom
+int rt_write_png_rgb8(const char *path, const uint8_t *rgb8, int width, int height) {
+    if (!path || !rgb8 || width <= 0 || height <= 0) {
+        set_error("rt_write_png_rgb8: bad argument");
+        return RT_ERR_ARG;
+    }
     // raw scanlines: filter byte 0 + RGB bytes, top row first
     std::string raw;
     raw.reserve((size_t)height * ((size_t)width * 3 + 1));
-    for (int j = height - 1; j >= 0; --j) {
+    for (int j = 0; j < height; ++j) {
         raw.push_back(0);
-        for (int i = 0; i < width; ++i)
-            for (int c = 0; c < 3; ++c) raw.push_back((char)quantize(rgb_sum[((size_t)j * width + i) * 3 + c], spp, gamma));
+        raw.append((const char *)rgb8 + (size_t)j * width * 3, (size_t)width * 3);
     }
     std::string z;
     z.push_back(0x78), z.push_back(0x01);  // zlib header, no preset dictionary
@@ -706,6 +730,85 @@ int rt_write_png(const char *path, const float *rgb_sum, int width, int height, 
         return RT_ERR_IO;
     }
     return RT_OK;
+}
+
+// ---- float image files of the mean image (scene-referred: what the environment readers of env_read.hpp take back) ----
+static int write_file(const char *path, const std::string &data) {
+    FILE *fp = fopen(path, "wb");
+    if (!fp) {
+        set_error("cannot open '%s' for writing", path);
+        return RT_ERR_IO;
+    }
+    bool ok = fwrite(data.data(), 1, data.size(), fp) == data.size();
+    ok = (fclose(fp) == 0) && ok;
+    if (!ok) {
+        set_error("short write to '%s'", path);
+        return RT_ERR_IO;
+    }
+    return RT_OK;
+}
+
+// Radiance RGBE (Ward, "Real Pixels", Graphics Gems II): the exponent of the largest channel, mantissas truncated
+int rt_write_hdr(const char *path, const float *rgb_sum, int width, int height, int spp) {
+    if (!path || !rgb_sum || width <= 0 || height <= 0 || spp <= 0) {
+        set_error("rt_write_hdr: bad argument");
+        return RT_ERR_ARG;
+    }
+    char head[96];
+    const int hn = snprintf(head, sizeof head, "#?RADIANCE\nFORMAT=32-bit_rle_rgbe\n\n-Y %d +X %d\n", height, width);
+    std::string out(head, (size_t)hn);
+    out.reserve(out.size() + (size_t)width * height * 4 + (size_t)height * 8);
+    std::string row;
+    const float n = (float)spp;
+    for (int j = height - 1; j >= 0; --j) {  // top row first
+        row.clear();
+        for (int i = 0; i < width; ++i) {
+            const float *p = rgb_sum + ((size_t)j * width + i) * 3;
+            double c[3];
+            for (int k = 0; k < 3; ++k) {
+                const float v = p[k] / n;
+                c[k] = v > 0.0f ? (double)v : 0.0;  // (negative and NaN: 0)
+            }
+            const double m = std::max(c[0], std::max(c[1], c[2]));
+            unsigned char q[4] = {0, 0, 0, 0};
+            if (m >= 1e-32) {
+                int e = 0;
+                if (std::isfinite(m)) (void)std::frexp(m, &e);  // m = f 2^e, f in [0.5, 1)
+                else e = 128;
+                if (e > 127) {  // beyond the format: its largest value
+                    q[0] = c[0] >= m ? 255 : 0, q[1] = c[1] >= m ? 255 : 0, q[2] = c[2] >= m ? 255 : 0, q[3] = 255;
+                } else {
+                    for (int k = 0; k < 3; ++k) q[k] = (unsigned char)(int)std::ldexp(c[k], 8 - e);  // exact, then truncated
+                    q[3] = (unsigned char)(e + 128);
+                }
+            }
+            row.append((const char *)q, 4);
+        }
+        // (the largest channel's mantissa is >= 128, so no scanline begins with the 2, 2 of a run-length coded one)
+        out += row;
+    }
+    return write_file(path, out);
+}
+
+int rt_write_pfm(const char *path, const float *rgb_sum, int width, int height, int spp) {
+    if (!path || !rgb_sum || width <= 0 || height <= 0 || spp <= 0) {
+        set_error("rt_write_pfm: bad argument");
+        return RT_ERR_ARG;
+    }
+    char head[64];
+    const int hn = snprintf(head, sizeof head, "PF\n%d %d\n-1.0\n", width, height);
+    std::string out(head, (size_t)hn);
+    const size_t count = (size_t)width * height * 3;
+    out.reserve(out.size() + count * 4);
+    const float n = (float)spp;
+    for (size_t i = 0; i < count; ++i) {  // rows bottom to top: the framebuffer's order
+        const float v = rgb_sum[i] / n;
+        uint32_t u;
+        memcpy(&u, &v, 4);
+        const char b[4] = {(char)(u & 255), (char)((u >> 8) & 255), (char)((u >> 16) & 255), (char)(u >> 24)};
+        out.append(b, 4);
+    }
+    return write_file(path, out);
 }
 
 // ---- misc ----------------------------------------------------------------------------

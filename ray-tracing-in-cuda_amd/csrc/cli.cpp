@@ -16,8 +16,13 @@
 // within T (rt_render_hip_adaptive); each pixel is written rescaled to the scene's spp (sum * spp / n).
 // Environment map: --env FILE [--env-scale S] [--env-rotate DEG] lights the scene with a lat-long .hdr / .pfm / .png / .ppm
 // panorama (rt_scene_set_environment_file); with --nee its bright texels are sampled.
+// Display stage (rt_display_hip): --tonemap clamp|reinhard|aces, --exposure EV (multiplier 2^EV), --auto-exposure
+// [KEY], --white W, --bloom STRENGTH [--bloom-threshold T] [--bloom-levels L].  With any of them the PPM and the PNG are
+// written from the stage's 8-bit output; without, the program writes what it always wrote.  --hdr-out FILE.hdr|FILE.pfm
+// writes the mean image before the display stage (and after --denoise) as a float image (rt_write_hdr / rt_write_pfm).
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -48,9 +53,25 @@ static int usage(const char *argv0) {
             "          [--acc-in sums.bin] [--acc-out sums.bin] [--spp-begin FIRST] [--rr SURVIVAL_PROBABILITY] [--nee]\n"
             "          [--nested-grid] [--env map.hdr [--env-scale S] [--env-rotate DEG]]\n"
             "          [--gpus N] [--tile-rows R] [--adaptive THRESHOLD [--min-spp N] [--max-spp N]]\n"
-            "          [--denoise] [--aov PREFIX] [--feature-spp N]\n",
+            "          [--denoise] [--aov PREFIX] [--feature-spp N]\n"
+            "          [--tonemap clamp|reinhard|aces] [--exposure EV] [--auto-exposure [KEY]] [--white W]\n"
+            "          [--bloom STRENGTH] [--bloom-threshold T] [--bloom-levels L] [--hdr-out frame.hdr|frame.pfm]\n",
             argv0);
     return 2;
+}
+
+// a whole-string number in [lo, hi]; false for anything else (NaN included)
+static bool number(const char *v, double lo, double hi, double *out) {
+    char *end = nullptr;
+    const double x = strtod(v, &end);
+    if (end == v || *end != '\0' || !(x >= lo && x <= hi)) return false;
+    *out = x;
+    return true;
+}
+
+static bool ends_with(const std::string &s, const char *tail) {
+    const size_t n = strlen(tail);
+    return s.size() > n && s.compare(s.size() - n, n, tail) == 0;
 }
 
 int main(int argc, char **argv) {
@@ -72,6 +93,10 @@ int main(int argc, char **argv) {
     std::string aov_prefix;   // write PREFIX_albedo.png, PREFIX_normal.png, PREFIX_depth.png
     int feature_spp = 0;      // samples of the feature passes, 0: min(spp, 16)
     bool have_min = false, have_max = false;
+    bool have_display = false;  // any display flag: the images are written from rt_display_hip's bytes
+    rt_display dp;
+    memset(&dp, 0, sizeof dp);
+    std::string hdr_out;        // the mean image before the display stage, .hdr or .pfm
     int w = 0, h = 0, depth = 0, spp = 0, device = 0, chunk = 0, gpus = 0, tile_rows = 0;
     unsigned long long seed = 2023;
     unsigned scene_seed = 7;  // srand(7), main.cpp:119
@@ -128,6 +153,68 @@ int main(int argc, char **argv) {
                 return 2;
             }
             feature_spp = (int)n;
+        }
+        else if (!strcmp(argv[i], "--tonemap")) {
+            const char *v = need("--tonemap");
+            if (!strcmp(v, "clamp")) dp.tonemap = RT_TONEMAP_CLAMP;
+            else if (!strcmp(v, "reinhard")) dp.tonemap = RT_TONEMAP_REINHARD;
+            else if (!strcmp(v, "aces")) dp.tonemap = RT_TONEMAP_ACES;
+            else {
+                fprintf(stderr, "rtmi: --tonemap needs clamp, reinhard or aces, got '%s'\n", v);
+                return 2;
+            }
+            have_display = true;
+        }
+        else if (!strcmp(argv[i], "--exposure")) {
+            const char *v = need("--exposure");
+            double ev;
+            if (!number(v, -100.0, 100.0, &ev)) {
+                fprintf(stderr, "rtmi: --exposure needs a number of stops in -100 .. 100, got '%s'\n", v);
+                return 2;
+            }
+            dp.exposure = (float)std::exp2(ev);  // fp64, rounded once
+            have_display = true;
+        }
+        else if (!strcmp(argv[i], "--auto-exposure")) {
+            double key = 0.18;  // the value is optional: the next argument is taken if it is a number
+            double x;
+            if (i + 1 < argc && number(argv[i + 1], -1e30, 1e30, &x)) {
+                if (!(x > 0.0)) {
+                    fprintf(stderr, "rtmi: --auto-exposure needs a key > 0, got '%s'\n", argv[i + 1]);
+                    return 2;
+                }
+                key = x, ++i;
+            }
+            dp.auto_key = (float)key;
+            have_display = true;
+        }
+        else if (!strcmp(argv[i], "--white") || !strcmp(argv[i], "--bloom") || !strcmp(argv[i], "--bloom-threshold")) {
+            const char *flag = argv[i], *v = need(flag);
+            const bool white = !strcmp(flag, "--white");
+            double x;
+            if (!number(v, 0.0, 1e30, &x) || (white && !(x > 0.0))) {
+                fprintf(stderr, "rtmi: %s needs a number %s 0, got '%s'\n", flag, white ? ">" : ">=", v);
+                return 2;
+            }
+            (white ? dp.white : !strcmp(flag, "--bloom") ? dp.bloom_strength : dp.bloom_threshold) = (float)x;
+            have_display = true;
+        }
+        else if (!strcmp(argv[i], "--bloom-levels")) {
+            const char *v = need("--bloom-levels");
+            double x;
+            if (!number(v, 1.0, 8.0, &x) || x != (double)(int)x) {
+                fprintf(stderr, "rtmi: --bloom-levels needs a whole number in 1 .. 8, got '%s'\n", v);
+                return 2;
+            }
+            dp.bloom_levels = (int)x;
+            have_display = true;
+        }
+        else if (!strcmp(argv[i], "--hdr-out")) {
+            hdr_out = need("--hdr-out");
+            if (!ends_with(hdr_out, ".hdr") && !ends_with(hdr_out, ".pfm")) {
+                fprintf(stderr, "rtmi: --hdr-out needs a file name ending in .hdr or .pfm, got '%s'\n", hdr_out.c_str());
+                return 2;
+            }
         }
         else if (!strcmp(argv[i], "--rtiow")) rtiow = true;
         else if (!strcmp(argv[i], "--count")) count = true;
@@ -365,16 +452,37 @@ int main(int argc, char **argv) {
                 }
         }
     }
-    if (rt_write_ppm(out_file.c_str(), img.data(), info.width, info.height, total_spp) != RT_OK) {
+    if (!hdr_out.empty()) {
+        const bool pfm = ends_with(hdr_out, ".pfm");
+        if ((pfm ? rt_write_pfm : rt_write_hdr)(hdr_out.c_str(), img.data(), info.width, info.height, total_spp) != RT_OK) {
+            fprintf(stderr, "rtmi: %s\n", rt_last_error());
+            return 1;
+        }
+    }
+    // what is written: with a display flag the stage's bytes, in both files; else the frame through the reference's writers
+    // (write_image(..., data["output_file"]), main.cu:514: a LINEAR PNG next to the PPM).  The PNG is skipped when the
+    // directory of output_file does not exist, which the reference would crash on.
+    std::vector<uint8_t> rgb8;
+    if (have_display) {
+        rgb8.resize(img.size());
+        rt_display_stats ds;
+        if (rt_display_hip(info.width, info.height, img.data(), total_spp, nullptr, &dp, device, nullptr, rgb8.data(), &ds) != RT_OK) {
+            fprintf(stderr, "rtmi: display stage failed: %s\n", rt_last_error());
+            return 1;
+        }
+        fprintf(stderr, "display: exposure x%g, %.3f ms\n", (double)ds.exposure_used, ds.ms);
+    }
+    const int ppm_rc = have_display ? rt_write_ppm_rgb8(out_file.c_str(), rgb8.data(), info.width, info.height)
+                                    : rt_write_ppm(out_file.c_str(), img.data(), info.width, info.height, total_spp);
+    if (ppm_rc != RT_OK) {
         fprintf(stderr, "rtmi: %s\n", rt_last_error());
         return 1;
     }
-    // write_image(..., data["output_file"]), main.cu:514: linear PNG next to the PPM (skipped when the
-    // directory of output_file does not exist, which the reference would crash on)
     if (!no_png) {
         const char *png = rt_scene_output_file(sc);
-        if (rt_write_png(png, img.data(), info.width, info.height, total_spp, 0) != RT_OK)
-            fprintf(stderr, "rtmi: PNG not written: %s\n", rt_last_error());
+        const int png_rc = have_display ? rt_write_png_rgb8(png, rgb8.data(), info.width, info.height)
+                                        : rt_write_png(png, img.data(), info.width, info.height, total_spp, 0);
+        if (png_rc != RT_OK) fprintf(stderr, "rtmi: PNG not written: %s\n", rt_last_error());
     }
     fprintf(stderr, "Program finish, cost: %f s\n", now_s() - t0);  // main.cu:519-520
     rt_scene_free(sc);
