@@ -3,12 +3,13 @@ import os
 
 import numpy as np
 
+from nee_scenes import REF_DRAWS, REF_H, REF_K, REF_W
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MEDIA = 2048  # rt_stats.kernel_variant / rt_table_info.kernel_variant: a media kernel
 
-# the per-sample comparison: frame, one-sample frames, seed, uniforms requested per sample
-REF_W, REF_H, REF_K, REF_SEED = 48, 27, 13, 91
-REF_DRAWS = 384
+# the per-sample comparison: nee_scenes' frame, one-sample frames and uniforms requested per sample, under a seed of its own
+REF_SEED = 91
 
 
 def room(rtmi, w=REF_W, h=REF_H, spp=16, depth=6, rr=0.0):

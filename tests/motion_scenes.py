@@ -7,7 +7,7 @@ MOTION = 4096  # rt_stats.kernel_variant / rt_table_info.kernel_variant: a motio
 
 
 def shutter_times(rtmi, seed, width, height, first, count):
-    """[count * height * width] shutter times, samples ordered (sample, y, x) as nee_ref64.uniforms orders its words"""
+    """[count * height * width] shutter times, samples ordered (sample, y, x) as ref64.uniforms orders its words"""
     return np.array([rtmi.shutter_time(seed, pix, first + k) for k in range(count) for pix in range(height * width)], np.float64)
 
 

@@ -196,7 +196,7 @@ def nee_cases():
     return cases
 
 
-# The special vertices a case is there for, by the names of nee_ref64.tally(): the reference must have met each at least
+# The special vertices a case is there for, by the names of ref64.tally(): the reference must have met each at least
 # REQUIRED_EVENTS times among the scene's 16 848 samples, or the case does not test what its name says.  1 % of the samples: an
 # estimator wrong by a factor of order one on that many vertices moves the paired mean by 1e-2 of a contribution, four
 # orders above the 1e-6 the bias assertion resolves where no branch flips.

@@ -1,19 +1,29 @@
-"""An independent statement of the path estimators of DESIGN 7a (light sampling + MIS) and 7e (environment maps), in NumPy,
-vectorised over a batch of samples, at a floating type of the caller's choice (float64: the reference; float32: the same
+"""An independent statement of the path estimators of DESIGN 7a (light sampling + MIS), 7e (environment maps), 7f (homogeneous
+participating media with isotropic scattering) and 7g (motion blur: linearly moving spheres over a per-sample shutter time), in
+NumPy, vectorised over a batch of samples, at a floating type of the caller's choice (float64: the reference; float32: the same
 formulas at the kernel's precision, used to measure how many samples sit on a branch).
 
 Test infrastructure only.  It is written from the definitions -- DESIGN 2 (the integrator, the order of the draws), 7a, 7e,
-and the reference's primitive and material definitions -- with libm's arccos / arctan2, plain closest-hit loops over the
-primitive list and no fused operations.  It shares no code with the kernels or with oracle/rt_oracle.c.
+7f (the media walk), 7g (the shutter time, the movers' query and its tie rule), and the reference's primitive and material
+definitions -- with libm's arccos / arctan2 / log, plain closest-hit loops over the primitive, mover and media lists and no fused
+operations.  It shares no code with the kernels or with oracle/.
 
-Inputs are the product's exported tables (Scene.prims / materials / textures / lights / get_camera / info / environment),
-the light alias table and the environment's CDF tables as the packed image stores them (table_image, found by content), and
-the uniforms of rtmi.sample_stream.  Out of scope: triangles, image textures, the nested grid.
+There is ONE integrator loop, trace().  An extension joins it with a record list on RefScene (lights, media, movers: empty
+unless the scene has them), a block in the loop, columns in the signature and keys in tally().  The reference evaluates the
+scene it is given: which combinations the product renders is the product's to refuse and test_refusals' to assert.  Where two
+extensions meet and DESIGN defines no order -- a light sample at a medium vertex, a shadow ray through a medium or past a
+mover -- trace() raises NotImplementedError.
 
-trace() returns, per sample, the radiance, an event signature (one row of integers: per vertex the primitive hit, what the
-material did, the checker parity, the roulette outcome, the light and texel picked and whether through the alias, the shadow
-ray's verdict, how an emitter hit was weighted; two samples took the same branches iff their rows are equal; tally() counts the
-special vertices of a batch from it) and the number of draws consumed.
+Inputs are the product's exported tables (Scene.prims / materials / textures / lights / media / moving_spheres / get_camera /
+info / environment), the light alias table and the environment's CDF tables as the packed image stores them (table_image,
+found by content), the uniforms of rtmi.sample_stream and, for movers, the shutter times of rtmi.shutter_time (one per sample:
+the time is no draw of the stream).  Out of scope: triangles, image textures, the nested grid.
+
+trace() returns, per sample, the radiance, an event signature (one row of integers: per vertex the primitive hit, the mover
+that took over, the set of media that took a free-flight draw and the medium whose event won, what the material did, the
+checker parity, the roulette outcome, the light and texel picked and whether through the alias, the shadow ray's verdict, how
+an emitter hit was weighted; columns a scene does not exercise stay NONE; two samples took the same branches iff their rows
+are equal; tally() counts the special vertices of a batch from it) and the number of draws consumed.
 """
 import numpy as np
 
@@ -21,17 +31,22 @@ SPHERE, XY_RECT, XZ_RECT, YZ_RECT, CYLINDER, TRIANGLE = range(6)
 LAMBERTIAN, METAL, DIELECTRIC, DIFFUSE_LIGHT = range(4)
 SOLID, CHECKER, IMAGE = range(3)
 ENVIRONMENT = 100
+MEDIUM_SPHERE, MEDIUM_BOX = 0, 1
 T_MIN = 0.001           # hittable_list::hit's t_min of every query
 SHADOW_T_MAX = 0.999    # a shadow ray ends just short of its light point
 METAL_MIN_FUZZ = 0.05   # metal vertices below this fuzz take no light sample
 
 # event codes of the signature
 EV_MISS, EV_EMIT, EV_LAMBERT, EV_METAL, EV_METAL_ABSORBED, EV_REFLECT, EV_REFRACT = range(7)
+EV_MEDIUM = 20
 NONE = -9
-# the signature's columns: two per sample (draws consumed, the first roulette), then one block per vertex
+# the signature's columns: two per sample (draws consumed, the first roulette), then one block per vertex.  C_PRIM is the static
+# winner; C_MOVER the mover that took over (-1: none) in a scene with movers; C_DREW the set of media that took a free-flight
+# draw and C_MEDIUM the medium whose event won (-1: none) in a scene with media
 SAMPLE_COLUMNS = 2
-C_PRIM, C_MISS_TEXEL, C_PARITY, C_EVENT, C_ROULETTE, C_LIGHT, C_TEXEL, C_SHADOW, C_HIT_WEIGHT, C_ALIAS = range(10)
-VERTEX_COLUMNS = 10
+(C_PRIM, C_MISS_TEXEL, C_PARITY, C_EVENT, C_ROULETTE, C_LIGHT, C_TEXEL, C_SHADOW, C_HIT_WEIGHT, C_ALIAS,
+ C_MOVER, C_DREW, C_MEDIUM) = range(13)
+VERTEX_COLUMNS = 13
 # C_SHADOW: the light sample reached its light / was occluded / had zero weight (no shadow ray) / was not made because the
 # vertex lies inside the sphere light it picked
 SHADOW_CLEAR, SHADOW_OCCLUDED, SHADOW_NONE, SHADOW_INSIDE = range(4)
@@ -94,9 +109,10 @@ def find_env_tables(image, texels):
 
 
 class RefScene:
-    """What trace() reads, taken from a product Scene."""
+    """What trace() reads, taken from a product Scene.  nee=False, movers=False, media=False take the plain twin's view: the
+    scene with that extension left out."""
 
-    def __init__(self, sc, nee=None):
+    def __init__(self, sc, nee=None, movers=True, media=True):
         info = sc.info
         self.width, self.height, self.max_depth = info.width, info.height, info.max_depth
         self.flags, self.background, self.rr = info.flags, np.array(info.background[:], np.float32), np.float32(info.russian_roulette)
@@ -128,6 +144,8 @@ class RefScene:
                 raise ValueError("the alias table only exists while the scene's light sampling is on")
             self.thr, self.alias = find_alias_table(image, self.lights)
         self.light_of_prim = {int(l["prim"]): i for i, l in enumerate(self.lights) if l["prim"] >= 0}
+        self.movers = sc.moving_spheres() if movers else sc.moving_spheres()[:0]
+        self.media = sc.media() if media else sc.media()[:0]
 
 
 def uniforms(rtmi, seed, width, height, first, count, n):
@@ -233,6 +251,51 @@ def hit_record(S, o, d, t, idx, T):
             n_out[m, _rect_axes(ty)[0]] = 1
     front = _dot(d, n_out) < 0
     return p, np.where(front[:, None], n_out, -n_out), front
+
+
+def mover_centre(m, s, T):
+    """c(s) = center0 + s v, with v = center1 - center0 as the scene keeps it: one fp32 subtraction per component"""
+    v = (m["center1"].astype(np.float32) - m["center0"].astype(np.float32)).astype(T)
+    return m["center0"].astype(T) + s.astype(T)[:, None] * v
+
+
+def mover_t(m, s, o, d, dd, t_min, best, T):
+    """sphere::hit against (c(s), radius): the near root where it lies in [t_min, best], else the far one; NaN without a real root"""
+    oc = o - mover_centre(m, s, T)
+    r = T(m["radius"])
+    with np.errstate(all="ignore"):
+        hb = _dot(oc, d)
+        disc = hb * hb - dd * (_dot(oc, oc) - r * r)
+        sq = np.sqrt(np.maximum(disc, 0))
+        r1, r2 = (-hb - sq) / dd, (-hb + sq) / dd
+        first = (r1 >= t_min) & (r1 <= best)
+        return np.where(disc < 0, T(np.nan), np.where(first, r1, r2))
+
+
+def medium_interval(m, o, d, t_s, T):
+    """[a, b]: the stay of the rays o + t d inside the boundary of medium m, clipped to [0.001, t_s]; non-empty where a < b"""
+    f = m["f"].astype(T)
+    a = np.full(len(o), T(T_MIN), T)
+    b = t_s.astype(T).copy()
+    with np.errstate(all="ignore"):
+        if int(m["shape"]) == MEDIUM_SPHERE:
+            oc = o - f[:3]
+            A = _dot(d, d)
+            hb = _dot(oc, d)
+            disc = hb * hb - A * (_dot(oc, oc) - f[3] * f[3])
+            sq = np.sqrt(np.maximum(disc, 0))
+            a = np.maximum(a, (-hb - sq) / A)
+            b = np.minimum(b, (-hb + sq) / A)
+            ok = (disc > 0) & (a < b)
+        else:
+            for k in range(3):
+                inv = T(1) / d[:, k]
+                t0, t1 = (f[k] - o[:, k]) * inv, (f[3 + k] - o[:, k]) * inv
+                lo, hi = np.where(inv < 0, t1, t0), np.where(inv < 0, t0, t1)
+                a = np.where(lo > a, lo, a)
+                b = np.where(hi < b, hi, b)
+            ok = a < b
+    return a, b, ok
 
 
 def checker_odd(p, T):
@@ -421,9 +484,13 @@ class _Draws:
         return out
 
 
-def trace(S, words, first_pixel=0, dtype=np.float64, perturb=()):
+def trace(S, words, first_pixel=0, dtype=np.float64, perturb=(), shutter=None):
     """One sample per row of `words` (the sample's stream as uint32 words), pixel ids first_pixel, first_pixel + 1, ... modulo the
-    frame.  Returns (rgb [N][3], signature [N][*] int64, draws consumed [N])."""
+    frame; `shutter`: the samples' shutter times, required where the scene has movers.  Returns (rgb [N][3], signature [N][*]
+    int64, draws consumed [N]).  perturb names deliberate mistakes, for the tests that show the comparison can fail: "skip_draw",
+    "no_cos", "mis_unsquared", "no_rr_light" at the light sample; "skip_flight" leaves the free-flight draw out (the distance is
+    taken from the NEXT position instead: a wrong order of draws); "half_time" puts every sample at s = 0.5 (a renderer that
+    ignores the shutter time)."""
     T = dtype
     N = len(words)
     D = _Draws(words, T)
@@ -431,6 +498,10 @@ def trace(S, words, first_pixel=0, dtype=np.float64, perturb=()):
     pix = (first_pixel + np.arange(N)) % (W * H)
     everyone = np.arange(N)
     rr, pi = T(S.rr), T(np.pi)
+    if len(S.movers):
+        if shutter is None:
+            raise ValueError("a scene with movers needs the samples' shutter times")
+        time = np.full(N, 0.5, T) if "half_time" in perturb else np.asarray(shutter, np.float64).astype(T)
     cam = {k: v.astype(T) for k, v in S.cam.items()}
     sig = [np.full((N, SAMPLE_COLUMNS), NONE, np.int64)]
 
@@ -463,8 +534,48 @@ def trace(S, words, first_pixel=0, dtype=np.float64, perturb=()):
         t_hit, idx = closest_hit(S, oo, dd, np.inf, T)
         sig.append(np.full((N, VERTEX_COLUMNS), NONE, np.int64))
         note(C_PRIM, who, idx)
+        # ---- the movers (7g), in list order, behind every static primitive: accepted while t_min <= t <= the closest so far
+        mov = np.full(len(who), -1, np.int64)
+        if len(S.movers):
+            a = _dot(dd, dd)
+            t_min = T(T_MIN)
+            for mi, m in enumerate(S.movers):
+                tt = mover_t(m, time[who], oo, dd, a, t_min, t_hit, T)
+                with np.errstate(invalid="ignore"):
+                    ok = (tt >= t_min) & (tt <= t_hit)
+                t_hit = np.where(ok, tt, t_hit)
+                mov = np.where(ok, mi, mov)
+            note(C_MOVER, who, mov)
+        # ---- the media walk (7f), in list order: a non-empty stay in a medium of positive density takes one draw
+        t_m = np.full(len(who), np.inf, T)
+        med = np.full(len(who), -1, np.int64)
+        if len(S.media):
+            drew = np.zeros(len(who), np.int64)
+            length = np.sqrt(_dot(dd, dd))
+            for mi, m in enumerate(S.media):
+                sigma = T(m["density"])
+                if not sigma > 0:
+                    continue
+                a, b, ok = medium_interval(m, oo, dd, t_hit, T)
+                k = np.flatnonzero(ok)
+                if len(k) == 0:
+                    continue
+                if "skip_flight" in perturb:
+                    D.at[who[k]] += 1
+                u = D.next(who[k])
+                if "skip_flight" in perturb:
+                    D.at[who[k]] -= 1
+                tt = a[k] + (-np.log(1 - u) / sigma) / length[k]
+                drew[k] |= 1 << mi
+                win = (tt < b[k]) & (tt < t_m[k])
+                t_m[k[win]] = tt[win]
+                med[k[win]] = mi
+            note(C_DREW, who, drew)
+            note(C_MEDIUM, who, med)
+        vol = med >= 0  # a medium event nearer than the surface: a vertex of the volume
+        t_hit = np.where(vol, t_m, t_hit)
         # ---- a miss ends the path with the background
-        miss = idx < 0
+        miss = (idx < 0) & (mov < 0) & ~vol
         if miss.any():
             m = who[miss]
             ud = _unit(dd[miss])
@@ -483,11 +594,26 @@ def trace(S, words, first_pixel=0, dtype=np.float64, perturb=()):
             alive[m] = False
         if miss.all():
             continue
-        who, oo, dd, t_hit, idx = who[~miss], oo[~miss], dd[~miss], t_hit[~miss], idx[~miss]
-        p, n, front = hit_record(S, oo, dd, t_hit, idx, T)
-        mat = S.prims["material"][idx]
-        kind = S.mats["type"][mat]
-        tex = S.mats["texture"][mat]
+        who, oo, dd, t_hit, idx, mov, med, vol = (x[~miss] for x in (who, oo, dd, t_hit, idx, mov, med, vol))
+        # ---- the hit record: a static winner's; a mover's is the sphere's about c(s); a medium event has a point and no normal
+        p = oo + t_hit[:, None] * dd
+        n = np.zeros_like(dd)
+        front = np.zeros(len(who), bool)
+        mat = np.full(len(who), -1, np.int64)
+        st = np.flatnonzero((mov < 0) & ~vol)
+        p[st], n[st], front[st] = hit_record(S, oo[st], dd[st], t_hit[st], idx[st], T)
+        mat[st] = S.prims["material"][idx[st]]
+        for mi, m in enumerate(S.movers):
+            q = np.flatnonzero((mov == mi) & ~vol)
+            if len(q):
+                n_out = (p[q] - mover_centre(m, time[who[q]], T)) / T(m["radius"])
+                f = _dot(dd[q], n_out) < 0
+                n[q], front[q], mat[q] = np.where(f[:, None], n_out, -n_out), f, int(m["material"])
+        surface = np.flatnonzero(~vol)
+        kind = np.full(len(who), NONE, np.int64)
+        tex = np.full(len(who), -1, np.int64)
+        kind[surface], tex[surface] = S.mats["type"][mat[surface]], S.mats["texture"][mat[surface]]
+        listed = np.where(mov < 0, idx, -1)  # the static winner where it is the vertex's surface: the key of a listed light
         checker = np.isin(kind, (LAMBERTIAN, DIFFUSE_LIGHT)) & (S.texs["type"][np.maximum(tex, 0)] == CHECKER)
         note(C_PARITY, who, np.where(checker, checker_odd(p, T), NONE))
         event = np.full(len(who), NONE, np.int64)
@@ -498,8 +624,8 @@ def trace(S, words, first_pixel=0, dtype=np.float64, perturb=()):
             Le = texture_value(S, tex[em], p[em], T)
             wgt = np.ones(em.sum(), T)
             how = np.full(em.sum(), HIT_UNSAMPLED, np.int64)
-            for li in {S.light_of_prim.get(int(i), -1) for i in np.unique(idx[em])} - {-1}:
-                sel = idx[em] == S.lights[li]["prim"]
+            for li in {S.light_of_prim.get(int(i), -1) for i in np.unique(listed[em])} - {-1}:
+                sel = listed[em] == S.lights[li]["prim"]
                 pl = light_pdf_of_hit(S, li, oo[em][sel], dd[em][sel], t_hit[em][sel], n[em][sel], T)
                 wgt[sel] = _mis_bsdf(mis[m][sel], pl, perturb)
                 inside = inside_sphere_light(S, li, oo[em][sel], T) if S.lights[li]["shape"] == SPHERE else np.zeros(sel.sum(), bool)
@@ -516,6 +642,13 @@ def trace(S, words, first_pixel=0, dtype=np.float64, perturb=()):
         refl_dir = np.zeros_like(dd)       # metal: the mirror direction of its lobe
         fuzz = np.zeros(len(who), T)       # metal: its fuzz (0: a lambertian vertex)
         takes_light = np.zeros(len(who), bool)
+        if vol.any():  # a medium event: a vertex without a normal that emits nothing -- albedo, then a uniform direction
+            if len(S.lights):
+                raise NotImplementedError("a light sample at a medium vertex: DESIGN defines none")
+            k = np.flatnonzero(vol)
+            new_d[k] = _unit(D.reject(who[k], 3, T))
+            att[k] = S.media["albedo"][med[k]].astype(T)
+            event[k] = EV_MEDIUM
         lam = kind == LAMBERTIAN
         if lam.any():
             sph = D.reject(who[lam], 3, T)
@@ -620,6 +753,8 @@ def trace(S, words, first_pixel=0, dtype=np.float64, perturb=()):
         usable = (pl > 0) & (pb > 0) & (d2 > 0) & np.isfinite(weight) & (weight > 0)
         verdict = np.where(inside, SHADOW_INSIDE, SHADOW_NONE)
         if usable.any():
+            if len(S.media) or len(S.movers):
+                raise NotImplementedError("a shadow ray through a medium or past a mover: DESIGN defines none")
             k = np.flatnonzero(usable)
             is_env = S.lights["shape"][pick[k]] == ENVIRONMENT
             far = np.where(is_env, T(np.inf), T(SHADOW_T_MAX))
@@ -648,15 +783,33 @@ def tally(sig):
     assert that the case was there: light samples not made because the vertex lies inside the sphere light it picked, and BSDF
     hits on that light from inside kept at weight 1; absorbed metal vertices that took a light sample all the same; dielectric
     vertices, the light samples they took (none, by definition) and the emitter hits of their rays at full weight; light picks
-    that went to the bucket's own light and to its alias."""
+    that went to the bucket's own light and to its alias.  Of 7f (MEDIA_KEYS): medium events, those on paths that met a surface
+    vertex later, those behind a refraction, and the media that had one.  Of 7g (MOTION_KEYS): vertices on movers, which movers
+    were hit, and the paths that went from a mover to a static surface and the other way."""
     v = sig[:, SAMPLE_COLUMNS:].reshape(len(sig), -1, VERTEX_COLUMNS)
-    event, light, shadow, how, alias = (v[:, :, c] for c in (C_EVENT, C_LIGHT, C_SHADOW, C_HIT_WEIGHT, C_ALIAS))
+    event, light, shadow, how, alias, mover = (v[:, :, c] for c in (C_EVENT, C_LIGHT, C_SHADOW, C_HIT_WEIGHT, C_ALIAS, C_MOVER))
     glass = np.isin(event, (EV_REFLECT, EV_REFRACT))
+    later = lambda x: np.flip(np.cumsum(np.flip(x, axis=1), axis=1), axis=1) - x > 0
+    med = event == EV_MEDIUM
+    surface = np.isin(event, (EV_LAMBERT, EV_METAL, EV_METAL_ABSORBED, EV_REFLECT, EV_REFRACT, EV_EMIT))
+    glass_before = np.cumsum(np.isin(event, (EV_REFRACT,)), axis=1) > 0
+    vertex = event != NONE
+    on_mover, on_static = vertex & (mover >= 0), vertex & (mover < 0)
     return dict(inside_no_sample=int((shadow == SHADOW_INSIDE).sum()), inside_full_weight_hits=int((how == HIT_FROM_INSIDE).sum()),
                 absorbed_metal_light_samples=int(((event == EV_METAL_ABSORBED) & (light != NONE)).sum()),
                 dielectric_vertices=int(glass.sum()), dielectric_light_samples=int((glass & (light != NONE)).sum()),
                 dielectric_full_weight_hits=int((glass[:, :-1] & (how[:, 1:] == HIT_UNSAMPLED)).sum()),
-                bucket_picks=int((alias == 0).sum()), alias_picks=int((alias == 1).sum()))
+                bucket_picks=int((alias == 0).sum()), alias_picks=int((alias == 1).sum()),
+                medium_events=int(med.sum()), medium_then_surface=int((med & later(surface)).any(axis=1).sum()),
+                medium_behind_glass=int((med & glass_before).sum()),
+                media_with_events=sorted(int(i) for i in np.unique(v[:, :, C_MEDIUM][med])),
+                mover_vertices=int(on_mover.sum()), movers_hit=sorted(int(i) for i in np.unique(mover[on_mover])),
+                mover_then_static=int((on_mover & later(on_static)).any(axis=1).sum()),
+                static_then_mover=int((on_static & later(on_mover)).any(axis=1).sum()))
+
+
+MEDIA_KEYS = ("medium_events", "medium_then_surface", "medium_behind_glass", "media_with_events")
+MOTION_KEYS = ("mover_vertices", "movers_hit", "mover_then_static", "static_then_mover")
 
 
 def _mis_bsdf(pdf_b, pl, perturb=()):
@@ -681,11 +834,11 @@ def implied_alias_probability(thr, alias):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the comparison
-def reference(S, words):
+def reference(S, words, shutter=None):
     """the fp64 radiance, which samples took the same branches at fp32 (the stable ones), the draws consumed, and the tally of the
     fp64 run's special vertices"""
-    rgb, sig64, draws = trace(S, words)
-    _, sig32, _ = trace(S, words, dtype=np.float32)
+    rgb, sig64, draws = trace(S, words, shutter=shutter)
+    _, sig32, _ = trace(S, words, dtype=np.float32, shutter=shutter)
     return rgb, same_signature(sig64, sig32), draws, tally(sig64)
 
 

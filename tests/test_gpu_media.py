@@ -6,19 +6,18 @@
   2. the exact composition of layouts, spp chunks, sample splits, row shards and adaptive tiles;
   3. exact powers of the albedo inside a closed emitter;
   4. Beer-Lambert transmittance within the binomial bound of the samples' own fp64 transmittances;
-  5. per-sample agreement with the fp64 statement (media_ref64.py), criteria (a)-(d) of test_gpu_nee_reference.py;
+  5. per-sample agreement with the fp64 statement (ref64.py), criteria (a)-(d) of test_gpu_nee_reference.py;
   6. the refusals.
 
 Rows of test 5 measured on the MI355X: DESIGN 2."""
 import os
-import sys
 
 import numpy as np
 import pytest
 
-import media_ref64 as M
 import media_scenes as MS
-import nee_ref64 as R
+import ref64 as R
+import per_sample as PS
 from test_nested_grid import clump
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -29,12 +28,7 @@ SEED = 31
 
 @pytest.fixture(scope="module")
 def rtmi():
-    sys.path.insert(0, ROOT)
-    from __graft_entry__ import load_package
-    mod = load_package()
-    if mod.device_count() < 1:
-        pytest.skip("no HIP device")
-    return mod
+    return PS.gpu_package()
 
 
 # ---- 1 ---------------------------------------------------------------------------------------------------------------
@@ -162,19 +156,14 @@ def words(rtmi):
 
 
 def kernel_samples(rtmi, sc, family):
-    out = []
-    for k in range(MS.REF_K):
-        st = rtmi.Stats()
-        out.append(sc.render(rtmi.Opts(seed=MS.REF_SEED, sample_first=k, sample_count=1), st))
-        assert st.kernel_variant & MEDIA == family, (st.kernel_variant, family)
-    return np.stack(out).reshape(-1, 3).astype(np.float64)
+    return PS.kernel_samples(rtmi, sc, MS.REF_SEED, MS.REF_K, MEDIA, family)
 
 
 @pytest.mark.parametrize("name", list(MS.ref_cases()))
 def test_media_kernel_against_fp64(rtmi, words, name):
     assert len(words) >= 16000
     sc = MS.ref_cases()[name](rtmi)
-    ref, stable, draws, tally = M.reference(M.RefScene(sc), words)
+    ref, stable, draws, tally = R.reference(R.RefScene(sc), words)
     assert draws.max() <= MS.REF_DRAWS, draws.max()                                         # (d)
     assert tally["medium_events"] > 0 and tally["medium_then_surface"] >= 1, tally
     assert tally["media_with_events"] == list(range(len(sc.media()))), tally
@@ -183,54 +172,43 @@ def test_media_kernel_against_fp64(rtmi, words, name):
     j = R.judge(kernel_samples(rtmi, sc, MEDIA), ref, stable)
     plain = MS.ref_cases()[name](rtmi)
     plain.clear_media()
-    bref, bstable, _, _ = M.reference(M.RefScene(plain), words)
+    bref, bstable, _, _ = R.reference(R.RefScene(plain), words)
     b = R.judge(kernel_samples(rtmi, plain, 0), bref, bstable)
-    print("\n" + R.row(name, j, b["share_stable"]))
-    print("    " + ", ".join(f"{k} {v}" for k, v in tally.items()))
-    assert j["flips"] <= 0.01, j["flips"]
-    assert j["share"] >= 0.97, j                                                            # (a)
-    assert j["share_stable"] >= b["share_stable"] - 0.005, (j["share_stable"], b["share_stable"])  # (b)
-    assert j["bias_ok"], (j["mean_diff"], j["z"])                                           # (c)
+    PS.assert_agreement(name, j, b)                                                         # (a), (b), (c)
+    print("    " + ", ".join(f"{k} {tally[k]}" for k in R.MEDIA_KEYS))
 
 
 def test_a_skipped_free_flight_draw_fails_the_agreement(rtmi, words):
     """(d): a reference that leaves the free-flight draw out of the order of draws is far from 97 %"""
     sc = MS.ref_cases()["camera inside thin fog"](rtmi)
-    S = M.RefScene(sc)
+    S = R.RefScene(sc)
     got = kernel_samples(rtmi, sc, MEDIA)
-    ref, stable, _, _ = M.reference(S, words)
-    wrong, _, _ = M.trace(S, words, perturb=("skip_flight",))
+    ref, stable, _, _ = R.reference(S, words)
+    wrong, _, _ = R.trace(S, words, perturb=("skip_flight",))
     good, bad = R.judge(got, ref, stable), R.judge(got, wrong, stable)
     print(f"\nskipped free-flight draw: within tolerance {100 * good['share']:.2f} % -> {100 * bad['share']:.2f} %")
-    assert good["share"] >= 0.97 and bad["share"] < 0.97, (good["share"], bad["share"])
+    PS.assert_perturbation_noticed(good, bad)
 
 
 # ---- 6 ---------------------------------------------------------------------------------------------------------------
-def _refused(rtmi, call):
-    with pytest.raises(rtmi.RtmiError) as e:
-        call()
-    assert e.value.status == 1, str(e.value)  # RT_ERR_ARG
-    return str(e.value)
-
-
 def test_refusals(rtmi):
     sc = fog_scene(rtmi, spp=2)
     sc.set_light_sampling(True)
     assert len(sc.lights()) >= 1
-    assert "light sampling" in _refused(rtmi, lambda: sc.render(rtmi.Opts(seed=SEED)))
+    assert "light sampling" in PS.refused(rtmi, lambda: sc.render(rtmi.Opts(seed=SEED)))
     sc.set_light_sampling(False)
     sc.set_environment(np.ones((4, 8, 3), np.float32))
-    assert "environment" in _refused(rtmi, lambda: sc.render(rtmi.Opts(seed=SEED)))
+    assert "environment" in PS.refused(rtmi, lambda: sc.render(rtmi.Opts(seed=SEED)))
     sc.set_environment(None)
-    assert "counting" in _refused(rtmi, lambda: sc.count(rtmi.Opts(seed=SEED)))
-    assert "variant 6" in _refused(rtmi, lambda: sc.render(rtmi.Opts(seed=SEED, variant=6)))
+    assert "counting" in PS.refused(rtmi, lambda: sc.count(rtmi.Opts(seed=SEED)))
+    assert "variant 6" in PS.refused(rtmi, lambda: sc.render(rtmi.Opts(seed=SEED, variant=6)))
     sc.render(rtmi.Opts(seed=SEED))  # (and on its own it renders)
     nested = clump(rtmi)
     nested.set_nested_grid(True)
     assert nested.nested_info().cells > 0
     nested.add_medium_sphere((0, 0, 0), 1.0, 0.5, (0.5, 0.5, 0.5))
     assert nested.nested_info().cells > 0
-    assert "nested" in _refused(rtmi, lambda: nested.render(rtmi.Opts(seed=SEED)))
+    assert "nested" in PS.refused(rtmi, lambda: nested.render(rtmi.Opts(seed=SEED)))
     # a light-sampling switch with nothing to sample is no obstacle
     dark = rtmi.Scene.new(32, 18, 2, 4)
     dark.sphere((0, 0, -3), 1.0, dark.lambertian((0.5, 0.5, 0.5)))

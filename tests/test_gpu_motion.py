@@ -5,22 +5,21 @@
      stream, so everything else in the motion kernel is the oracle-pinned computation;
   2. the exact composition of layouts, spp chunks, sample splits, row shards, tiles and adaptive tiles;
   3. coverage: a black mover before a white background, every sample decided in fp64 from its own jitter and shutter time;
-  4. per-sample agreement with the fp64 statement (motion_ref64.py), criteria (a)-(d) of test_gpu_media.py;
+  4. per-sample agreement with the fp64 statement (ref64.py), criteria (a)-(d) of test_gpu_media.py;
   5. the comparison can fail: a reference that puts every sample at s = 0.5;
   6. the refusals;
   7. the shipped scene.
 
 Rows of test 4 measured on the MI355X: DESIGN 2."""
 import os
-import sys
 
 import numpy as np
 import pytest
 
 import media_scenes as MS
-import motion_ref64 as M
 import motion_scenes as MO
-import nee_ref64 as R
+import ref64 as R
+import per_sample as PS
 from test_nested_grid import clump
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -31,12 +30,7 @@ SEED = 31
 
 @pytest.fixture(scope="module")
 def rtmi():
-    sys.path.insert(0, ROOT)
-    from __graft_entry__ import load_package
-    mod = load_package()
-    if mod.device_count() < 1:
-        pytest.skip("no HIP device")
-    return mod
+    return PS.gpu_package()
 
 
 # ---- 1 ---------------------------------------------------------------------------------------------------------------
@@ -122,19 +116,14 @@ def shutter(rtmi):
 
 
 def kernel_samples(rtmi, sc, family):
-    out = []
-    for k in range(MS.REF_K):
-        st = rtmi.Stats()
-        out.append(sc.render(rtmi.Opts(seed=MS.REF_SEED, sample_first=k, sample_count=1), st))
-        assert st.kernel_variant & MOTION == family, (st.kernel_variant, family)
-    return np.stack(out).reshape(-1, 3).astype(np.float64)
+    return PS.kernel_samples(rtmi, sc, MS.REF_SEED, MS.REF_K, MOTION, family)
 
 
 @pytest.mark.parametrize("name", list(MO.ref_cases()))
 def test_motion_kernel_against_fp64(rtmi, words, shutter, name):
     assert len(words) >= 16000 and len(shutter) == len(words)
     sc = MO.ref_cases()[name](rtmi)
-    ref, stable, draws, tally = M.reference(M.RefScene(sc), words, shutter)
+    ref, stable, draws, tally = R.reference(R.RefScene(sc), words, shutter)
     assert draws.max() <= MS.REF_DRAWS, draws.max()                                         # (d)
     assert tally["movers_hit"] == list(range(len(sc.moving_spheres()))), tally
     if name != "an emissive mover over the floor":  # (an emitter ends its path: nothing comes after it)
@@ -144,55 +133,44 @@ def test_motion_kernel_against_fp64(rtmi, words, shutter, name):
     j = R.judge(got, ref, stable)
     plain = MO.ref_cases()[name](rtmi)
     plain.clear_moving_spheres()
-    bref, bstable, _, _ = M.reference(M.RefScene(plain), words, shutter)
+    bref, bstable, _, _ = R.reference(R.RefScene(plain), words)
     b = R.judge(kernel_samples(rtmi, plain, 0), bref, bstable)
-    print("\n" + R.row(name, j, b["share_stable"]))
-    print("    " + ", ".join(f"{k} {v}" for k, v in tally.items()))
+    PS.assert_agreement(name, j, b)                                                         # (a), (b), (c)
+    print("    " + ", ".join(f"{k} {tally[k]}" for k in R.MOTION_KEYS))
     if name == "a zero-velocity mover":
         twin = kernel_samples(rtmi, MO.static_twin(rtmi), 0)
         print(f"    one-sample pixels bit-equal to the static twin's: {100 * (twin == got).all(axis=1).mean():.3f} %")
-    assert j["flips"] <= 0.01, j["flips"]
-    assert j["share"] >= 0.97, j                                                            # (a)
-    assert j["share_stable"] >= b["share_stable"] - 0.005, (j["share_stable"], b["share_stable"])  # (b)
-    assert j["bias_ok"], (j["mean_diff"], j["z"])                                           # (c)
 
 
 # ---- 5 ---------------------------------------------------------------------------------------------------------------
 def test_a_reference_without_the_shutter_time_fails_the_agreement(rtmi, words, shutter):
     """a reference that puts every sample at s = 0.5 is far from 97 %"""
     sc = MO.ref_cases()[MO.IN_FRONT](rtmi)
-    S = M.RefScene(sc)
+    S = R.RefScene(sc)
     got = kernel_samples(rtmi, sc, MOTION)
-    ref, stable, _, _ = M.reference(S, words, shutter)
-    wrong, _, _ = M.trace(S, words, shutter, perturb=("half_time",))
+    ref, stable, _, _ = R.reference(S, words, shutter)
+    wrong, _, _ = R.trace(S, words, shutter=shutter, perturb=("half_time",))
     good, bad = R.judge(got, ref, stable), R.judge(got, wrong, stable)
     print(f"\nevery sample at s = 0.5: within tolerance {100 * good['share']:.2f} % -> {100 * bad['share']:.2f} %")
-    assert good["share"] >= 0.97 and bad["share"] < 0.97, (good["share"], bad["share"])
+    PS.assert_perturbation_noticed(good, bad)
 
 
 # ---- 6 ---------------------------------------------------------------------------------------------------------------
-def _refused(rtmi, call):
-    with pytest.raises(rtmi.RtmiError) as e:
-        call()
-    assert e.value.status == 1, str(e.value)  # RT_ERR_ARG
-    return str(e.value)
-
-
 def test_refusals(rtmi):
     sc = MO.two_movers(rtmi, spp=2)
     sc.set_light_sampling(True)
     assert len(sc.lights()) >= 1
-    assert "light sampling" in _refused(rtmi, lambda: sc.render(rtmi.Opts(seed=SEED)))
+    assert "light sampling" in PS.refused(rtmi, lambda: sc.render(rtmi.Opts(seed=SEED)))
     sc.set_light_sampling(False)
     sc.set_environment(np.ones((4, 8, 3), np.float32))
-    assert "environment" in _refused(rtmi, lambda: sc.render(rtmi.Opts(seed=SEED)))
+    assert "environment" in PS.refused(rtmi, lambda: sc.render(rtmi.Opts(seed=SEED)))
     sc.set_environment(None)
     sc.add_medium_sphere((0, 1, 0), 1.0, 0.5, (0.5, 0.5, 0.5))
-    assert "media" in _refused(rtmi, lambda: sc.render(rtmi.Opts(seed=SEED)))
+    assert "media" in PS.refused(rtmi, lambda: sc.render(rtmi.Opts(seed=SEED)))
     sc.clear_media()
-    assert "counting" in _refused(rtmi, lambda: sc.count(rtmi.Opts(seed=SEED)))
-    assert "feature pass" in _refused(rtmi, lambda: sc.render_feature(0, rtmi.Opts(seed=SEED)))
-    assert "variant 6" in _refused(rtmi, lambda: sc.render(rtmi.Opts(seed=SEED, variant=6)))
+    assert "counting" in PS.refused(rtmi, lambda: sc.count(rtmi.Opts(seed=SEED)))
+    assert "feature pass" in PS.refused(rtmi, lambda: sc.render_feature(0, rtmi.Opts(seed=SEED)))
+    assert "variant 6" in PS.refused(rtmi, lambda: sc.render(rtmi.Opts(seed=SEED, variant=6)))
     st = rtmi.Stats()
     sc.render(rtmi.Opts(seed=SEED), st)  # (and on its own it renders)
     assert st.kernel_variant & MOTION
@@ -201,7 +179,7 @@ def test_refusals(rtmi):
     assert nested.nested_info().cells > 0
     nested.add_moving_sphere((0, 0, 0), (1, 0, 0), 1.0, 0)
     assert nested.nested_info().cells > 0
-    assert "nested" in _refused(rtmi, lambda: nested.render(rtmi.Opts(seed=SEED)))
+    assert "nested" in PS.refused(rtmi, lambda: nested.render(rtmi.Opts(seed=SEED)))
     # a light-sampling switch with nothing to sample is no obstacle
     dark = rtmi.Scene.new(32, 18, 2, 4)
     dark.sphere((0, 0, -3), 1.0, dark.lambertian((0.5, 0.5, 0.5)))

@@ -1,4 +1,4 @@
-"""render_nee_kernel and render_env_kernel (7e) against the fp64 statement of their estimators (nee_ref64.py),
+"""render_nee_kernel and render_env_kernel (7e) against the fp64 statement of their estimators (ref64.py),
 sample by sample on the same draws.  A one-sample frame is that sample's radiance in 2^-24 fixed point (each contribution
 rounded separately: at most (max_depth + 1) 2^-25, negligible against the tolerance).  Per scene:
 
@@ -14,16 +14,11 @@ A case named for a special vertex (inside the sphere light, a dielectric, an abs
 the reference's signatures that such vertices occurred (nee_scenes.SPECIAL_VERTICES).
 
 Every scene prints one row of figures (pytest -s); DESIGN 2 holds the rows measured on the MI355X."""
-import os
-import sys
-
-import numpy as np
 import pytest
 
-import nee_ref64 as R
+import ref64 as R
 import nee_scenes as NS
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import per_sample as PS
 
 pytestmark = pytest.mark.gpu
 NEE, ENV = 256, 1024
@@ -31,12 +26,7 @@ NEE, ENV = 256, 1024
 
 @pytest.fixture(scope="module")
 def rtmi():
-    sys.path.insert(0, ROOT)
-    from __graft_entry__ import load_package
-    mod = load_package()
-    if mod.device_count() < 1:
-        pytest.skip("no HIP device")
-    return mod
+    return PS.gpu_package()
 
 
 @pytest.fixture(scope="module")
@@ -45,13 +35,7 @@ def words(rtmi):
 
 
 def kernel_samples(rtmi, sc, family):
-    """[K x H x W][3]: the radiance of every sample, from one-sample frames; the kernel family is checked on each"""
-    out = []
-    for k in range(NS.REF_K):
-        st = rtmi.Stats()
-        out.append(sc.render(rtmi.Opts(seed=NS.REF_SEED, sample_first=k, sample_count=1), st))
-        assert st.kernel_variant & (NEE | ENV) == family, (st.kernel_variant, family)
-    return np.stack(out).reshape(-1, 3).astype(np.float64)
+    return PS.kernel_samples(rtmi, sc, NS.REF_SEED, NS.REF_K, NEE | ENV, family)
 
 
 def check(rtmi, words, name, sc, plain, family):
@@ -63,14 +47,9 @@ def check(rtmi, words, name, sc, plain, family):
     plain.set_light_sampling(False)
     bref, bstable, _, _ = R.reference(R.RefScene(plain), words)
     b = R.judge(kernel_samples(rtmi, plain, 0), bref, bstable)
-    print("\n" + R.row(name, j, b["share_stable"]))
+    PS.assert_agreement(name, j, b)                                                        # (a), (b), (c)
     if name in NS.SPECIAL_VERTICES:
         print("    " + ", ".join(f"{k} {tally[k]}" for k in NS.SPECIAL_VERTICES[name]))
-    assert j["flips"] <= 0.01, j["flips"]
-    assert j["share"] >= 0.97, j                                                           # (a)
-    assert j["share_stable"] >= b["share_stable"] - 0.005, (j["share_stable"], b["share_stable"])  # (b)
-    assert j["bias_ok"], (j["mean_diff"], j["z"])                                          # (c)
-    return j
 
 
 @pytest.mark.parametrize("name", list(NS.nee_cases()))
@@ -103,4 +82,4 @@ def test_a_skipped_draw_fails_the_agreement(rtmi, words):
     wrong, _, _ = R.trace(S, words, perturb=("skip_draw",))
     good, bad = R.judge(got, ref, stable), R.judge(got, wrong, stable)
     print(f"\nskipped draw: within tolerance {100 * good['share']:.2f} % -> {100 * bad['share']:.2f} %")
-    assert good["share"] >= 0.97 and bad["share"] < 0.97, (good["share"], bad["share"])
+    PS.assert_perturbation_noticed(good, bad)

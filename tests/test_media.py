@@ -8,9 +8,8 @@ import subprocess
 import numpy as np
 import pytest
 
-import media_ref64 as M
 import media_scenes as MS
-import nee_ref64 as R
+import ref64 as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ERR_ARG, ERR_SCENE, ERR_LIMIT = 1, 4, 6
@@ -161,34 +160,35 @@ def test_buried_media_are_unreachable(rtmi):
 
 
 def test_reference_branch_flip_rate_of_every_case(rtmi):
-    """media_ref64 alone, no kernel: on every case of the per-sample GPU comparison the share of samples whose event signature
+    """ref64 alone, no kernel: on every case of the per-sample GPU comparison the share of samples whose event signature
     differs between the reference's fp32 and fp64 runs is at most 1 %, the reference stays inside the draws it requested, medium
     events occur (some on paths with later surface vertices), and leaving the free-flight draw out is noticed"""
     words = R.uniforms(rtmi, MS.REF_SEED, MS.REF_W, MS.REF_H, 0, MS.REF_K, MS.REF_DRAWS)
     print()
     for name, build in MS.ref_cases().items():
         sc = build(rtmi)
-        S = M.RefScene(sc)
-        r64, sig64, draws = M.trace(S, words)
-        r32, sig32, _ = M.trace(S, words, dtype=np.float32)
+        S = R.RefScene(sc)
+        r64, sig64, draws = R.trace(S, words)
+        r32, sig32, _ = R.trace(S, words, dtype=np.float32)
         stable = R.same_signature(sig64, sig32)
-        flips, tally = 1 - stable.mean(), M.tally(sig64)
+        flips, tally = 1 - stable.mean(), {k: v for k, v in R.tally(sig64).items() if k in R.MEDIA_KEYS}
         j = R.judge(r32, r64, stable)
         print(f"{name:32s} flips {100 * flips:.3f} %   fp32 within {100 * j['share']:.3f} %   draws <= {draws.max()}   {tally}")
         assert flips <= 0.01 and j["share"] >= 0.97, (name, flips, j["share"])
         assert draws.max() <= MS.REF_DRAWS
         assert tally["medium_events"] > 0 and tally["medium_then_surface"] >= 1
         assert tally["media_with_events"] == list(range(len(sc.media())))
-    S = M.RefScene(MS.ref_cases()["camera inside thin fog"](rtmi))
-    r32, sig32, _ = M.trace(S, words, dtype=np.float32)
-    r64, sig64, _ = M.trace(S, words)
-    wrong, _, _ = M.trace(S, words, perturb=("skip_flight",))
+    S = R.RefScene(MS.ref_cases()["camera inside thin fog"](rtmi))
+    r32, sig32, _ = R.trace(S, words, dtype=np.float32)
+    r64, sig64, _ = R.trace(S, words)
+    wrong, _, _ = R.trace(S, words, perturb=("skip_flight",))
     assert R.judge(r32, wrong, R.same_signature(sig64, sig32))["share"] < 0.97
-    # without media the statement is the plain integrator's: nee_ref64's trace, light sampling off
-    plain = M.RefScene(MS.ref_cases()["dense sphere"](rtmi), media=False)
-    a, _, da = M.trace(plain, words[:4000])
-    b, _, db = R.trace(plain, words[:4000])
-    assert np.array_equal(a, b) and np.array_equal(da, db)
+    # without media the statement is the plain integrator's: the media=False view is the scene with its media cleared
+    sc = MS.ref_cases()["dense sphere"](rtmi)
+    a, _, da = R.trace(R.RefScene(sc, media=False), words[:4000])
+    sc.clear_media()
+    b, sig, db = R.trace(R.RefScene(sc), words[:4000])
+    assert np.array_equal(a, b) and np.array_equal(da, db) and R.tally(sig)["medium_events"] == 0
 
 
 # ---- rt_medium_interval against an fp64 derivation --------------------------------------------------------------------

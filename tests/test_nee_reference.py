@@ -1,4 +1,4 @@
-"""The fp64 statement of the light-sampling and environment estimators (nee_ref64.py) checked on its own, no GPU: against the
+"""The fp64 statement of the light-sampling and environment estimators (ref64.py) checked on its own, no GPU: against the
 fp32 checker on the plain path, against closed forms, for the consistency of its two MIS strategies, the stored alias table,
 how often the chosen scenes sit on a branch (fp32 against fp64 signatures), and that the per-sample comparison the GPU test
 makes notices a wrong estimator."""
@@ -9,7 +9,7 @@ import sys
 import numpy as np
 import pytest
 
-import nee_ref64 as R
+import ref64 as R
 import nee_scenes as NS
 import rtcheck
 
