@@ -17,6 +17,7 @@
 #include <mutex>
 #include <vector>
 
+#include "hip_host.h"
 #include "scene.hpp"
 
 namespace rtmi {
@@ -114,15 +115,6 @@ __global__ __launch_bounds__(256) void denoise_finish_kernel(const DenoiseParams
     out[3 * p + 2] = (c.z * fmaxf(albedo[3 * p + 2] / nf, kAlbedoEps)) * n;
 }
 
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) {                                                               \
-            set_error("HIP error %d (%s) at %s:%d: %s", (int)e_, hipGetErrorString(e_), __FILE__, __LINE__, #expr); \
-            return RT_ERR_HIP;                                                                \
-        }                                                                                     \
-    } while (0)
-
 namespace {
 
 constexpr int kDefaultIterations = 3, kMaxIterations = 10;  // defaults: the sweep of DESIGN.md section 7d
@@ -177,38 +169,13 @@ int check_args(int width, int height, const void *rgb, int spp, const void *spp_
 // scratch records of a device (C, C', G), kept between calls
 struct Scratch {
     int device = -1;
-    float4 *buf = nullptr;
-    size_t pixels = 0;
+    DeviceBuffer<float4> buf;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
 std::mutex g_mu;
-std::vector<std::unique_ptr<Scratch>> g_scratch;
-
-struct DeviceScope {
-    int prev = -1;
-    bool switched = false;
-    int enter(int device) {
-        int ndev = 0;
-        HIP_TRY(hipGetDeviceCount(&ndev));
-        if (ndev <= 0) {
-            set_error("no HIP device visible: the denoiser has no CPU fallback");
-            return RT_ERR_HIP;
-        }
-        if (device < 0 || device >= ndev) {
-            set_error("device %d out of range (%d visible)", device, ndev);
-            return RT_ERR_ARG;
-        }
-        HIP_TRY(hipGetDevice(&prev));
-        if (prev != device) {
-            HIP_TRY(hipSetDevice(device));
-            switched = true;
-        }
-        return RT_OK;
-    }
-    ~DeviceScope() {
-        if (switched) (void)hipSetDevice(prev);
-    }
-};
+// never destroyed at process exit, as tiles.hip's g_groups: the records own device memory, and the HIP runtime may already be
+// gone by then
+std::vector<std::unique_ptr<Scratch>> &g_scratch = *new std::vector<std::unique_ptr<Scratch>>();
 
 int denoise_device(int width, int height, const float *d_rgb, int spp, const int *d_spp_map, const float *d_albedo,
                    const float *d_normal, const float *d_depth, int feature_spp, const Resolved &r, int device, float *d_out,
@@ -223,25 +190,13 @@ int denoise_device(int width, int height, const float *d_rgb, int spp, const int
         return RT_OK;
     }
     std::lock_guard<std::mutex> lock(g_mu);
-    Scratch *sc = nullptr;
-    for (auto &s : g_scratch)
-        if (s->device == device) sc = s.get();
-    if (!sc) {
-        g_scratch.emplace_back(new Scratch());
-        sc = g_scratch.back().get();
-        sc->device = device;
-    }
-    if (sc->pixels < pixels) {
-        if (sc->buf) HIP_TRY(hipFree(sc->buf));
-        sc->buf = nullptr, sc->pixels = 0;
-        HIP_TRY(hipMalloc((void **)&sc->buf, pixels * 3 * sizeof(float4)));
-        sc->pixels = pixels;
-    }
+    Scratch *sc = device_record(g_scratch, device);
+    if (int rc = sc->buf.reserve(pixels * 3)) return rc;
     if (ms && !sc->ev0) {
         HIP_TRY(hipEventCreate(&sc->ev0));
         HIP_TRY(hipEventCreate(&sc->ev1));
     }
-    float4 *C0 = sc->buf, *C1 = sc->buf + pixels, *G = sc->buf + 2 * pixels;
+    float4 *C0 = sc->buf.get(), *C1 = C0 + pixels, *G = C0 + 2 * pixels;
     DenoiseParams D;
     D.width = width, D.height = height, D.spp = spp, D.feature_spp = feature_spp;
     D.inv_sn2 = 1.0f / (r.sigma_normal * r.sigma_normal);
@@ -283,7 +238,7 @@ int rt_denoise_hip_device(int width, int height, const void *d_rgb_sum, int spp,
                         d_out_rgb_sum, r);
     if (rc) return rc;
     DeviceScope scope;
-    rc = scope.enter(device);
+    rc = scope.enter(device, "the denoiser");
     if (rc) return rc;
     return denoise_device(width, height, (const float *)d_rgb_sum, spp, (const int *)d_spp_map, (const float *)d_albedo_sum,
                           (const float *)d_normal_sum, (const float *)d_depth_sum, feature_spp, r, device, (float *)d_out_rgb_sum,
@@ -297,16 +252,14 @@ int rt_denoise_hip(int width, int height, const float *rgb_sum, int spp, const i
     int rc = check_args(width, height, rgb_sum, spp, spp_map, albedo_sum, normal_sum, depth_sum, feature_spp, p, out_rgb_sum, r);
     if (rc) return rc;
     DeviceScope scope;
-    rc = scope.enter(device);
+    rc = scope.enter(device, "the denoiser");
     if (rc) return rc;
     const size_t pixels = (size_t)width * height, plane = pixels * 3 * sizeof(float);
     // one allocation: the four input planes, the output plane, the sample counts
-    char *d = nullptr;
-    HIP_TRY(hipMalloc((void **)&d, 5 * plane + pixels * sizeof(int32_t)));
-    struct Free {
-        char *p;
-        ~Free() { (void)hipFree(p); }
-    } guard{d};
+    DeviceBuffer<char> staging;
+    rc = staging.reserve(5 * plane + pixels * sizeof(int32_t));
+    if (rc) return rc;
+    char *const d = staging.get();
     float *d_rgb = (float *)d, *d_alb = (float *)(d + plane), *d_nrm = (float *)(d + 2 * plane), *d_dep = (float *)(d + 3 * plane);
     float *d_out = (float *)(d + 4 * plane);
     int *d_map = spp_map ? (int *)(d + 5 * plane) : nullptr;

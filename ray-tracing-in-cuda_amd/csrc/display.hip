@@ -20,6 +20,7 @@
 #include <mutex>
 #include <vector>
 
+#include "hip_host.h"
 #include "scene.hpp"
 
 namespace rtmi {
@@ -169,15 +170,6 @@ __global__ __launch_bounds__(256) void display_finish_kernel(const DisplayParams
     }
 }
 
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) {                                                               \
-            set_error("HIP error %d (%s) at %s:%d: %s", (int)e_, hipGetErrorString(e_), __FILE__, __LINE__, #expr); \
-            return RT_ERR_HIP;                                                                \
-        }                                                                                     \
-    } while (0)
-
 namespace {
 
 constexpr float kDefaultWhite = 4.0f;
@@ -237,79 +229,35 @@ int check_args(int width, int height, const void *rgb, int spp, const void *spp_
 // what a device keeps between calls: the four planes (X, B, T, S) and the sum's word, the events, the host entry's staging
 struct Scratch {
     int device = -1;
-    float4 *planes = nullptr;
-    size_t pixels = 0;
-    unsigned long long *d_sum = nullptr;
+    DeviceBuffer<float4> planes;
+    DeviceBuffer<unsigned long long> d_sum;
     long long *h_sum = nullptr;  // pinned
     hipEvent_t ev[kMaxKernels + 2] = {};
     bool have_events = false;
-    char *stage = nullptr;       // rt_display_hip: sums, sample counts, both outputs
-    size_t stage_bytes = 0;
+    DeviceBuffer<char> stage;    // rt_display_hip: sums, sample counts, both outputs
 };
 std::mutex g_mu;
-std::vector<std::unique_ptr<Scratch>> g_scratch;
+// never destroyed at process exit, as tiles.hip's g_groups: the records own device memory, and the HIP runtime may already be
+// gone by then
+std::vector<std::unique_ptr<Scratch>> &g_scratch = *new std::vector<std::unique_ptr<Scratch>>();
 thread_local double t_kernel_ms[kMaxKernels];
 thread_local int t_kernels = 0;
-
-struct DeviceScope {
-    int prev = -1;
-    bool switched = false;
-    int enter(int device) {
-        int ndev = 0;
-        HIP_TRY(hipGetDeviceCount(&ndev));
-        if (ndev <= 0) {
-            set_error("no HIP device visible: the display stage has no CPU fallback");
-            return RT_ERR_HIP;
-        }
-        if (device < 0 || device >= ndev) {
-            set_error("device %d out of range (%d visible)", device, ndev);
-            return RT_ERR_ARG;
-        }
-        HIP_TRY(hipGetDevice(&prev));
-        if (prev != device) {
-            HIP_TRY(hipSetDevice(device));
-            switched = true;
-        }
-        return RT_OK;
-    }
-    ~DeviceScope() {
-        if (switched) (void)hipSetDevice(prev);
-    }
-};
-
-// (g_mu held)
-int scratch_of(int device, Scratch *&sc) {
-    sc = nullptr;
-    for (auto &s : g_scratch)
-        if (s->device == device) sc = s.get();
-    if (!sc) {
-        g_scratch.emplace_back(new Scratch());
-        sc = g_scratch.back().get();
-        sc->device = device;
-    }
-    return RT_OK;
-}
 
 // (g_mu held)
 int display_device(int width, int height, const float *d_rgb, int spp, const int *d_spp_map, const Resolved &r, Scratch *sc,
                    float *d_out_rgb, uint8_t *d_out_rgb8, hipStream_t stream, rt_display_stats *st) {
     const size_t pixels = (size_t)width * height;
     const size_t planes = r.levels ? 4 : 1;
-    if (sc->pixels < pixels * planes) {
-        if (sc->planes) HIP_TRY(hipFree(sc->planes));
-        sc->planes = nullptr, sc->pixels = 0;
-        HIP_TRY(hipMalloc((void **)&sc->planes, pixels * planes * sizeof(float4)));
-        sc->pixels = pixels * planes;
-    }
-    if (r.auto_key > 0.0f && !sc->d_sum) {
-        HIP_TRY(hipMalloc((void **)&sc->d_sum, sizeof(unsigned long long)));
-        HIP_TRY(hipHostMalloc((void **)&sc->h_sum, sizeof(long long), hipHostMallocDefault));
+    if (int rc = sc->planes.reserve(pixels * planes)) return rc;
+    if (r.auto_key > 0.0f) {
+        if (int rc = sc->d_sum.reserve(1)) return rc;
+        if (!sc->h_sum) HIP_TRY(hipHostMalloc((void **)&sc->h_sum, sizeof(long long), hipHostMallocDefault));
     }
     if (st && !sc->have_events) {
         for (hipEvent_t &e : sc->ev) HIP_TRY(hipEventCreate(&e));
         sc->have_events = true;
     }
-    float4 *X = sc->planes, *B = X + pixels, *T = X + 2 * pixels, *S = X + 3 * pixels;
+    float4 *X = sc->planes.get(), *B = X + pixels, *T = X + 2 * pixels, *S = X + 3 * pixels;
     DisplayParams D;
     D.width = width, D.height = height, D.spp = spp;
     D.tonemap = r.tonemap, D.bloom = r.levels;
@@ -321,16 +269,17 @@ int display_device(int width, int height, const float *d_rgb, int spp, const int
     int gap = -1;
     auto mark = [&]() -> hipError_t { return st ? hipEventRecord(sc->ev[n_ev++], stream) : hipSuccess; };
 
+    unsigned long long *const d_sum = sc->d_sum.get();
     long long log_sum = 0;
     double E = r.exposure;
     if (r.auto_key > 0.0f) {
-        HIP_TRY(hipMemsetAsync(sc->d_sum, 0, sizeof(unsigned long long), stream));
+        HIP_TRY(hipMemsetAsync(d_sum, 0, sizeof(unsigned long long), stream));
         HIP_TRY(mark());
-        hipLaunchKernelGGL(display_reduce_kernel, grid, block, 0, stream, D, d_rgb, d_spp_map, sc->d_sum);
+        hipLaunchKernelGGL(display_reduce_kernel, grid, block, 0, stream, D, d_rgb, d_spp_map, d_sum);
         HIP_TRY(hipGetLastError());
         HIP_TRY(mark());
         gap = n_ev;
-        HIP_TRY(hipMemcpyAsync(sc->h_sum, sc->d_sum, sizeof(long long), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(sc->h_sum, d_sum, sizeof(long long), hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
         log_sum = *sc->h_sum;
         // the mean of the piecewise-linear log2 of the luminance, then key / 2^mean: fp64 on the host, rounded once
@@ -392,11 +341,10 @@ int rt_display_hip_device(int width, int height, const void *d_rgb_sum, int spp,
     int rc = check_args(width, height, d_rgb_sum, spp, d_spp_map, p, d_out_rgb, d_out_rgb8, r);
     if (rc) return rc;
     DeviceScope scope;
-    rc = scope.enter(device);
+    rc = scope.enter(device, "the display stage");
     if (rc) return rc;
     std::lock_guard<std::mutex> lock(g_mu);
-    Scratch *sc;
-    scratch_of(device, sc);
+    Scratch *sc = device_record(g_scratch, device);
     return display_device(width, height, (const float *)d_rgb_sum, spp, (const int *)d_spp_map, r, sc, (float *)d_out_rgb,
                           (uint8_t *)d_out_rgb8, (hipStream_t)stream, st);
 }
@@ -407,23 +355,19 @@ int rt_display_hip(int width, int height, const float *rgb_sum, int spp, const i
     int rc = check_args(width, height, rgb_sum, spp, spp_map, p, out_rgb, out_rgb8, r);
     if (rc) return rc;
     DeviceScope scope;
-    rc = scope.enter(device);
+    rc = scope.enter(device, "the display stage");
     if (rc) return rc;
     std::lock_guard<std::mutex> lock(g_mu);
-    Scratch *sc;
-    scratch_of(device, sc);
+    Scratch *sc = device_record(g_scratch, device);
     const size_t pixels = (size_t)width * height, plane = pixels * 3 * sizeof(float);
     // staging, kept between calls: the sums, the float output, the sample counts, the bytes
     const size_t need = 2 * plane + pixels * sizeof(int32_t) + pixels * 3;
-    if (sc->stage_bytes < need) {
-        if (sc->stage) HIP_TRY(hipFree(sc->stage));
-        sc->stage = nullptr, sc->stage_bytes = 0;
-        HIP_TRY(hipMalloc((void **)&sc->stage, need));
-        sc->stage_bytes = need;
-    }
-    float *d_rgb = (float *)sc->stage, *d_out = (float *)(sc->stage + plane);
-    int *d_map = (int *)(sc->stage + 2 * plane);
-    uint8_t *d_out8 = (uint8_t *)(sc->stage + 2 * plane + pixels * sizeof(int32_t));
+    rc = sc->stage.reserve(need);
+    if (rc) return rc;
+    char *const stage = sc->stage.get();
+    float *d_rgb = (float *)stage, *d_out = (float *)(stage + plane);
+    int *d_map = (int *)(stage + 2 * plane);
+    uint8_t *d_out8 = (uint8_t *)(stage + 2 * plane + pixels * sizeof(int32_t));
     HIP_TRY(hipMemcpy(d_rgb, rgb_sum, plane, hipMemcpyHostToDevice));
     if (spp_map) HIP_TRY(hipMemcpy(d_map, spp_map, pixels * sizeof(int32_t), hipMemcpyHostToDevice));
     rc = display_device(width, height, d_rgb, spp, spp_map ? d_map : nullptr, r, sc, out_rgb ? d_out : nullptr,

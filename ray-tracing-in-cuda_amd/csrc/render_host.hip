@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "device_scene.h"
+#include "hip_host.h"
 #include "kernels.h"
 #include "pack.h"
 #include "scene.hpp"
@@ -39,29 +40,15 @@ static const KernelRow *variant_row(unsigned variant, bool ext = false, bool cou
 
 static bool variant_exists(unsigned variant) { return variant == 0 || variant_row(variant); }
 
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) {                                                               \
-            set_error("HIP error %d (%s) at %s:%d: %s", (int)e_, hipGetErrorString(e_), __FILE__, __LINE__, #expr); \
-            return RT_ERR_HIP;                                                                \
-        }                                                                                     \
-    } while (0)
-
 struct DeviceEntry {
     int device = -1;
     uint64_t version = 0;
-    void *d_image = nullptr;
-    size_t image_bytes = 0;
-    unsigned long long *d_acc = nullptr;  // fixed-point pixel accumulators of the last launch
-    size_t acc_bytes = 0;
-    DevCounters *d_counters = nullptr;
-    float *d_out = nullptr;  // framebuffer of the host-buffer entry points (rt_render_hip), kept between calls
-    size_t out_bytes = 0;
-    char *d_adapt = nullptr;  // adaptive sampling: accumulator plane B, next tile list, tile counts, list counter
-    size_t adapt_bytes = 0;
-    int *d_spp = nullptr;     // spp_map of rt_render_hip_adaptive (host-buffer entry point)
-    size_t spp_bytes = 0;
+    DeviceBuffer<float> d_image;
+    DeviceBuffer<unsigned long long> d_acc;  // fixed-point pixel accumulators of the last launch
+    DeviceBuffer<DevCounters> d_counters;
+    DeviceBuffer<float> d_out;  // framebuffer of the host-buffer entry points (rt_render_hip), kept between calls
+    DeviceBuffer<char> d_adapt;  // adaptive sampling: accumulator plane B, next tile list, tile counts, list counter
+    DeviceBuffer<int> d_spp;     // spp_map of rt_render_hip_adaptive (host-buffer entry point)
     int num_cus = 0;
 };
 
@@ -73,22 +60,6 @@ struct DeviceSceneCache {
     std::vector<float> image;  // float4 records
     RenderParams layout;       // ns/nr/nc/nm + offsets filled by pack
     NestedInfo nested;         // the nested cells of that packing (all zero: flat tables)
-    ~DeviceSceneCache() {
-        int cur = 0;
-        bool have = hipGetDevice(&cur) == hipSuccess;
-        for (auto &ep : entries) {
-            DeviceEntry &e = *ep;
-            if (e.device < 0) continue;
-            if (hipSetDevice(e.device) != hipSuccess) continue;
-            if (e.d_image) (void)hipFree(e.d_image);
-            if (e.d_acc) (void)hipFree(e.d_acc);
-            if (e.d_counters) (void)hipFree(e.d_counters);
-            if (e.d_out) (void)hipFree(e.d_out);
-            if (e.d_adapt) (void)hipFree(e.d_adapt);
-            if (e.d_spp) (void)hipFree(e.d_spp);
-        }
-        if (have) (void)hipSetDevice(cur);
-    }
 };
 
 // the scene's packed tables and device entries (created by the first call that needs them)
@@ -96,15 +67,6 @@ static DeviceSceneCache &cache_of(const Scene &s) {
     Scene &ms = const_cast<Scene &>(s);
     if (!ms.dev) ms.dev = std::make_shared<DeviceSceneCache>();
     return *ms.dev;
-}
-
-// the entry of `device` (created at its first use); under cache.mu
-static DeviceEntry *entry_for(DeviceSceneCache &cache, int device) {
-    for (auto &e : cache.entries)
-        if (e->device == device) return e.get();
-    cache.entries.emplace_back(new DeviceEntry());
-    cache.entries.back()->device = device;
-    return cache.entries.back().get();
 }
 
 // packs the scene's tables unless the cache holds them for its version; under cache.mu.  The image, the layout and the
@@ -122,43 +84,6 @@ static int ensure_packed(const Scene &s, DeviceSceneCache &cache) {
     cache.packed_version = s.version;
     return RT_OK;
 }
-
-// a kept device buffer of at least `bytes`
-template <class T>
-static int grow(T *&buf, size_t &have, size_t bytes) {
-    if (have >= bytes) return RT_OK;
-    if (buf) HIP_TRY(hipFree(buf));
-    buf = nullptr, have = 0;
-    HIP_TRY(hipMalloc((void **)&buf, bytes));
-    have = bytes;
-    return RT_OK;
-}
-
-// select(device) makes `device` the calling thread's device; the caller's device comes back on every return path
-struct DeviceGuard {
-    int prev = 0, cur = 0;
-    int select(int device) {
-        int ndev = 0;
-        HIP_TRY(hipGetDeviceCount(&ndev));
-        if (ndev <= 0) {
-            set_error("no HIP device visible: the render path has no CPU fallback");
-            return RT_ERR_HIP;
-        }
-        if (device < 0 || device >= ndev) {
-            set_error("device %d out of range (%d visible)", device, ndev);
-            return RT_ERR_ARG;
-        }
-        HIP_TRY(hipGetDevice(&prev));
-        cur = prev;
-        if (prev != device) HIP_TRY(hipSetDevice(device));
-        cur = device;
-        return RT_OK;
-    }
-    ~DeviceGuard() {
-        if (prev != cur) (void)hipSetDevice(prev);
-    }
-};
-
 
 // ---- shard geometry ----------------------------------------------------------------
 struct Shard {
@@ -466,7 +391,7 @@ struct Launcher {
         const unsigned long long need_blocks = (items + 3) / 4;
         const unsigned long long grid = need_blocks < resident ? (need_blocks ? need_blocks : 1) : resident;
         if (feature >= 0) Q.feature = feature;
-        launch_kernel(kernel, Q, ent->d_image, acc, d_queue, d_cnt, lds_bytes, (unsigned)grid, stream);
+        launch_kernel(kernel, Q, ent->d_image.get(), acc, d_queue, d_cnt, lds_bytes, (unsigned)grid, stream);
         return RT_OK;
     }
 };
@@ -481,21 +406,23 @@ static int run_adaptive(const Launcher &launch, const AdaptiveRun &ad, const Sce
     DeviceEntry *ent = launch.ent;
     const hipStream_t stream = launch.stream;
     const long long frame_tiles = (long long)P.tiles_x * P.bands;
-    int rc = grow(ent->d_acc, ent->acc_bytes, need);
+    int rc = ent->d_acc.reserve(need / sizeof(unsigned long long));  // (need: a multiple of 256 bytes)
     if (rc) return rc;
+    unsigned long long *const d_acc = ent->d_acc.get();
     const size_t b_off = 0, list_off = queue_off, tn_off = list_off + (size_t)frame_tiles * 4;
     const size_t cnt_off = tn_off + (size_t)frame_tiles * 4;
-    rc = grow(ent->d_adapt, ent->adapt_bytes, cnt_off + 256);
+    rc = ent->d_adapt.reserve(cnt_off + 256);
     if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(ent->d_acc, 0, need, stream));
-    HIP_TRY(hipMemsetAsync(ent->d_adapt, 0, cnt_off + 256, stream));
-    long long *dA = reinterpret_cast<long long *>(ent->d_acc);
-    long long *dB = reinterpret_cast<long long *>(ent->d_adapt + b_off);
-    unsigned int *d_queue = reinterpret_cast<unsigned int *>(reinterpret_cast<char *>(ent->d_acc) + queue_off);
+    char *const d_adapt = ent->d_adapt.get();
+    HIP_TRY(hipMemsetAsync(d_acc, 0, need, stream));
+    HIP_TRY(hipMemsetAsync(d_adapt, 0, cnt_off + 256, stream));
+    long long *dA = reinterpret_cast<long long *>(d_acc);
+    long long *dB = reinterpret_cast<long long *>(d_adapt + b_off);
+    unsigned int *d_queue = reinterpret_cast<unsigned int *>(reinterpret_cast<char *>(d_acc) + queue_off);
     unsigned int *d_list = d_queue + RT_TILE_LIST_AT;
-    unsigned int *d_next = reinterpret_cast<unsigned int *>(ent->d_adapt + list_off);
-    int *d_tn = reinterpret_cast<int *>(ent->d_adapt + tn_off);
-    unsigned int *d_next_count = reinterpret_cast<unsigned int *>(ent->d_adapt + cnt_off);
+    unsigned int *d_next = reinterpret_cast<unsigned int *>(d_adapt + list_off);
+    int *d_tn = reinterpret_cast<int *>(d_adapt + tn_off);
+    unsigned int *d_next_count = reinterpret_cast<unsigned int *>(d_adapt + cnt_off);
     std::vector<unsigned int> all((size_t)frame_tiles);  // every tile: band << 16 | x0
     for (long long t = 0; t < frame_tiles; ++t) all[(size_t)t] = (unsigned)((t / P.tiles_x) << 16 | (t % P.tiles_x) * 8);
     HIP_TRY(hipMemcpyAsync(d_list, all.data(), all.size() * 4, hipMemcpyHostToDevice, stream));
@@ -667,8 +594,8 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     for (const rt_prim &p : s.prims) ext = ext || p.type == RT_PRIM_TRIANGLE;
     const bool force_ext = knob_set("RTMI_FORCE_EXT");  // measurement: the EXT builds on scenes that do not need them
     const int device = o ? o->device : 0;
-    DeviceGuard guard;
-    rc = guard.select(device);
+    DeviceScope scope;
+    rc = scope.enter(device, "the render path");
     if (rc) return rc;
 
     hipStream_t stream = (hipStream_t)stream_v;
@@ -680,7 +607,7 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     std::unique_lock<std::mutex> lock(cache.mu);
     rc = ensure_packed(s, cache);
     if (rc) return rc;
-    DeviceEntry *ent = entry_for(cache, device);
+    DeviceEntry *ent = device_record(cache.entries, device);
     // timing events: three per (host thread, device), created at the thread's first timed call there and kept
     struct Events {
         std::vector<std::array<hipEvent_t, 3>> per_device;
@@ -701,12 +628,12 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
         HIP_TRY(hipEventRecord(ev0, stream));
     }
     size_t image_bytes = cache.image.size() * sizeof(float);
-    if (ent->version != s.version || !ent->d_image) {
-        rc = grow(ent->d_image, ent->image_bytes, image_bytes);
+    if (ent->version != s.version || !ent->d_image.get()) {
+        rc = ent->d_image.reserve(cache.image.size());
         if (rc) return rc;
         // stream-ordered: the launches below follow on the same stream (renders of one scene object on one device share
         // a stream: include/rtmi.h).  The source is pageable, so the call returns once the bytes are staged.
-        HIP_TRY(hipMemcpyAsync(ent->d_image, cache.image.data(), image_bytes, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(ent->d_image.get(), cache.image.data(), image_bytes, hipMemcpyHostToDevice, stream));
         ent->version = s.version;
     }
 
@@ -911,8 +838,9 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     float *d_out = (float *)d_rgb_sum;
     DevCounters *d_cnt = nullptr;
     if (count) {
-        if (!ent->d_counters) HIP_TRY(hipMalloc((void **)&ent->d_counters, sizeof(DevCounters)));
-        d_cnt = ent->d_counters;
+        rc = ent->d_counters.reserve(1);
+        if (rc) return rc;
+        d_cnt = ent->d_counters.get();
         HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(DevCounters), stream));
         // the two minima start at all-ones
         HIP_TRY(hipMemsetAsync(&d_cnt->t_start_min, 0xff, sizeof(unsigned long long), stream));
@@ -937,23 +865,24 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
         // while (depth > 0) never runs: every sample is black (main.cpp:20,42)
         HIP_TRY(hipMemsetAsync(d_out, 0, plane * sizeof(float), stream));
     } else {
-        rc = grow(ent->d_acc, ent->acc_bytes, need);
+        rc = ent->d_acc.reserve(need / sizeof(unsigned long long));  // (need: a multiple of 256 bytes)
         if (rc) return rc;
-        HIP_TRY(hipMemsetAsync(ent->d_acc, 0, need, stream));
+        unsigned long long *const d_acc = ent->d_acc.get();
+        HIP_TRY(hipMemsetAsync(d_acc, 0, need, stream));
         // progressive rendering: continue from the caller's exact sums
-        if (h_acc) HIP_TRY(hipMemcpyAsync(ent->d_acc, h_acc, plane * sizeof(long long), hipMemcpyHostToDevice, stream));
-        unsigned int *d_queue = reinterpret_cast<unsigned int *>(reinterpret_cast<char *>(ent->d_acc) + queue_off);
+        if (h_acc) HIP_TRY(hipMemcpyAsync(d_acc, h_acc, plane * sizeof(long long), hipMemcpyHostToDevice, stream));
+        unsigned int *d_queue = reinterpret_cast<unsigned int *>(reinterpret_cast<char *>(d_acc) + queue_off);
         if (s.max_depth > 0 || feature >= 0) {
-            rc = launch.enqueue(ent->d_acc, d_queue, sample_first, sample_count, 0, plan);
+            rc = launch.enqueue(d_acc, d_queue, sample_first, sample_count, 0, plan);
             if (rc) return rc;
             ++launches;
         }
         if (d_out) {
-            launch_finalize(ent->d_acc, d_out, plane, stream);
+            launch_finalize(d_acc, d_out, plane, stream);
             ++launches;
         }
         if (h_acc) {
-            HIP_TRY(hipMemcpyAsync(h_acc, ent->d_acc, plane * sizeof(long long), hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipMemcpyAsync(h_acc, d_acc, plane * sizeof(long long), hipMemcpyDeviceToHost, stream));
             HIP_TRY(hipStreamSynchronize(stream));
         }
     }
@@ -999,8 +928,8 @@ static int render_host_buffer(const rt_scene *sc, const rt_opts *o, float *rgb_s
     int rc = shard_of(sc->s, o, sh);
     if (rc) return rc;
     const int device = o ? o->device : 0;
-    DeviceGuard guard;
-    rc = guard.select(device);
+    DeviceScope scope;
+    rc = scope.enter(device, "the render path");
     if (rc) return rc;
     const size_t bytes = (size_t)sh.local_rows * sc->s.width * 3 * sizeof(float);
     // the device framebuffer of this (scene, device) is kept between calls (no hipMalloc / hipFree per frame)
@@ -1009,14 +938,14 @@ static int render_host_buffer(const rt_scene *sc, const rt_opts *o, float *rgb_s
     if (bytes && (rgb_sum || !h_acc)) {
         DeviceSceneCache &cache = cache_of(sc->s);
         std::lock_guard<std::mutex> lock(cache.mu);
-        DeviceEntry *ent = entry_for(cache, device);
-        rc = grow(ent->d_out, ent->out_bytes, bytes);
+        DeviceEntry *ent = device_record(cache.entries, device);
+        rc = ent->d_out.reserve(bytes / sizeof(float));
         if (rc) return rc;
-        d_out = ent->d_out;
+        d_out = ent->d_out.get();
         if (ad) {  // ... and so is the sample-count map of the adaptive entry point
-            rc = grow(ent->d_spp, ent->spp_bytes, bytes / 3 / sizeof(float) * sizeof(int32_t));
+            rc = ent->d_spp.reserve(bytes / 3 / sizeof(float));
             if (rc) return rc;
-            ad->d_spp_map = ent->d_spp;
+            ad->d_spp_map = ent->d_spp.get();
         }
     }
     rc = bytes ? render_impl(sc, o, d_out, nullptr, stats ? stats : &local, h_acc, count, ad, feature) : RT_OK;

@@ -22,6 +22,7 @@
 #include <mutex>
 #include <vector>
 
+#include "hip_host.h"
 #include "scene.hpp"
 #include "shard.h"
 
@@ -64,14 +65,6 @@ static RcclApi *rccl_api() {
     return api.handle ? &api : nullptr;
 }
 
-#define HIP_TRY(expr)                                                                                                   \
-    do {                                                                                                                \
-        hipError_t e_ = (expr);                                                                                         \
-        if (e_ != hipSuccess) {                                                                                         \
-            set_error("HIP error %d (%s) at %s:%d: %s", (int)e_, hipGetErrorString(e_), __FILE__, __LINE__, #expr);     \
-            return RT_ERR_HIP;                                                                                          \
-        }                                                                                                               \
-    } while (0)
 #define NCCL_TRY(api, expr)                                                                                             \
     do {                                                                                                                \
         ncclResult_t r_ = (expr);                                                                                       \
@@ -104,13 +97,11 @@ struct TileGroup {
     std::vector<int> devices;
     std::vector<hipStream_t> streams;
     std::vector<ncclComm_t> comms;       // empty until the first gather
-    std::vector<float *> local;          // per device: pad_rows x W x 3
+    std::vector<DeviceBuffer<float>> local;  // per device: pad_rows x W x 3
     std::vector<hipEvent_t> ev0, ev1;    // render span per device
-    size_t local_floats = 0;
-    float *gathered = nullptr;           // root: N x local_floats
-    size_t gathered_floats = 0;
-    float *full = nullptr;               // root: H x W x 3
-    size_t full_floats = 0;
+    size_t local_floats = 0;             // the joint capacity of `local`
+    DeviceBuffer<float> gathered;        // root: N x local_floats
+    DeviceBuffer<float> full;            // root: H x W x 3
     hipEvent_t ev_gather0 = nullptr, ev_done = nullptr;  // root stream
     std::mutex mu;                       // one frame at a time per group
 
@@ -124,21 +115,18 @@ struct TileGroup {
         for (size_t i = 0; i < devices.size(); ++i) {
             if (hipSetDevice(devices[i]) != hipSuccess) continue;
             if (api && i < comms.size() && comms[i]) (void)api->CommDestroy(comms[i]);
-            if (i < local.size() && local[i]) (void)hipFree(local[i]);
             if (i < ev0.size() && ev0[i]) (void)hipEventDestroy(ev0[i]);
             if (i < ev1.size() && ev1[i]) (void)hipEventDestroy(ev1[i]);
             if (i == 0) {
-                if (gathered) (void)hipFree(gathered);
-                if (full) (void)hipFree(full);
                 if (ev_gather0) (void)hipEventDestroy(ev_gather0);
                 if (ev_done) (void)hipEventDestroy(ev_done);
             }
             if (i < streams.size() && streams[i]) (void)hipStreamDestroy(streams[i]);
         }
         if (have) (void)hipSetDevice(cur);
-        streams.clear(), comms.clear(), local.clear(), ev0.clear(), ev1.clear();
-        local_floats = gathered_floats = full_floats = 0;
-        gathered = full = nullptr;
+        streams.clear(), comms.clear(), ev0.clear(), ev1.clear();
+        local.clear(), gathered.release(), full.release();  // (each buffer is freed under its own device)
+        local_floats = 0;
         ev_gather0 = ev_done = nullptr;
     }
     // waits for whatever has been queued on the group's streams (error paths: nothing of a failed frame is left running)
@@ -160,15 +148,6 @@ static std::shared_ptr<TileGroup> group_for(const std::vector<int> &devices) {
     g_groups.emplace_back(new TileGroup());
     g_groups.back()->devices = devices;
     return g_groups.back();
-}
-
-static int ensure(float *&buf, size_t &have, size_t want) {
-    if (have >= want) return RT_OK;
-    if (buf) HIP_TRY(hipFree(buf));
-    buf = nullptr, have = 0;
-    HIP_TRY(hipMalloc((void **)&buf, want * sizeof(float)));
-    have = want;
-    return RT_OK;
 }
 
 // the frame cut into n_ranks shards with `deal` (rt_opts.tile_rotate; negative: an error of rt_shard_deal): shard[r] = base with
@@ -253,12 +232,8 @@ extern "C" int rt_render_hip_tiles(const rt_scene *sc, const rt_opts *o, const i
     const int W = sc->s.width, H = sc->s.height;
     const size_t row_floats = (size_t)W * 3;
 
-    int prev = 0;
-    HIP_TRY(hipGetDevice(&prev));
-    struct Restore {
-        int dev;
-        ~Restore() { (void)hipSetDevice(dev); }
-    } restore{prev};
+    DeviceScope scope;  // (the calls below select the group's devices in turn)
+    if (int rc = scope.save()) return rc;
 
     const std::shared_ptr<TileGroup> gp = group_for(devs);
     TileGroup *g = gp.get();
@@ -275,7 +250,7 @@ extern "C" int rt_render_hip_tiles(const rt_scene *sc, const rt_opts *o, const i
     RcclApi *api = nullptr;
     auto set_up = [&]() -> int {
     if (g->streams.empty()) {
-        g->streams.assign(N, nullptr), g->local.assign(N, nullptr), g->ev0.assign(N, nullptr), g->ev1.assign(N, nullptr);
+        g->streams.assign(N, nullptr), g->local.resize(N), g->ev0.assign(N, nullptr), g->ev1.assign(N, nullptr);
         for (int r = 0; r < N; ++r) {
             HIP_TRY(hipSetDevice(devs[r]));
             HIP_TRY(hipStreamCreateWithFlags(&g->streams[r], hipStreamNonBlocking));
@@ -289,16 +264,14 @@ extern "C" int rt_render_hip_tiles(const rt_scene *sc, const rt_opts *o, const i
     if (g->local_floats < local_floats) {
         for (int r = 0; r < N; ++r) {
             HIP_TRY(hipSetDevice(devs[r]));
-            if (g->local[r]) HIP_TRY(hipFree(g->local[r]));
-            g->local[r] = nullptr;
-            HIP_TRY(hipMalloc((void **)&g->local[r], std::max<size_t>(local_floats, 1) * sizeof(float)));
+            if (int rc = g->local[r].reserve(std::max<size_t>(local_floats, 1))) return rc;
         }
         g->local_floats = local_floats;
     }
     HIP_TRY(hipSetDevice(devs[0]));
-    int rc = ensure(g->gathered, g->gathered_floats, std::max<size_t>((size_t)N * local_floats, 1));
+    int rc = g->gathered.reserve(std::max<size_t>((size_t)N * local_floats, 1));
     if (rc) return rc;
-    rc = ensure(g->full, g->full_floats, std::max<size_t>((size_t)H * row_floats, 1));
+    rc = g->full.reserve(std::max<size_t>((size_t)H * row_floats, 1));
     if (rc) return rc;
     api = rccl_api();
     if (!api) {
@@ -325,7 +298,7 @@ extern "C" int rt_render_hip_tiles(const rt_scene *sc, const rt_opts *o, const i
     for (int r = 0; r < N; ++r) {
         HIP_TRY(hipSetDevice(devs[r]));
         HIP_TRY(hipEventRecord(g->ev0[r], g->streams[r]));
-        rc = rt_render_hip_device(sc, &shard[r], g->local[r], (void *)g->streams[r], nullptr);
+        rc = rt_render_hip_device(sc, &shard[r], g->local[r].get(), (void *)g->streams[r], nullptr);
         if (rc) return rc;
         HIP_TRY(hipEventRecord(g->ev1[r], g->streams[r]));
     }
@@ -334,8 +307,8 @@ extern "C" int rt_render_hip_tiles(const rt_scene *sc, const rt_opts *o, const i
     HIP_TRY(hipEventRecord(g->ev_gather0, g->streams[0]));
     NCCL_TRY(api, api->GroupStart());
     for (int r = 0; r < N; ++r) {
-        ncclResult_t nr = api->Gather(g->local[r], r == 0 ? g->gathered : nullptr, local_floats, ncclFloat, 0, g->comms[r],
-                                      g->streams[r]);
+        ncclResult_t nr = api->Gather(g->local[r].get(), r == 0 ? g->gathered.get() : nullptr, local_floats, ncclFloat, 0,
+                                      g->comms[r], g->streams[r]);
         if (nr != ncclSuccess) {
             (void)api->GroupEnd();
             set_error("RCCL error %d (%s) in ncclGather, rank %d", (int)nr, api->GetErrorString(nr), r);
@@ -345,11 +318,11 @@ extern "C" int rt_render_hip_tiles(const rt_scene *sc, const rt_opts *o, const i
     NCCL_TRY(api, api->GroupEnd());
     // ---- rows to their image positions, frame to the caller
     HIP_TRY(hipSetDevice(devs[0]));
-    rc = place_rows(sc, base.tile_rows, N, deal, pad_rows, g->gathered, g->full, g->streams[0]);
+    rc = place_rows(sc, base.tile_rows, N, deal, pad_rows, g->gathered.get(), g->full.get(), g->streams[0]);
     if (rc) return rc;
     const size_t total = (size_t)H * row_floats;
     HIP_TRY(hipEventRecord(g->ev_done, g->streams[0]));
-    HIP_TRY(hipMemcpyAsync(rgb_sum, g->full, total * sizeof(float), hipMemcpyDeviceToHost, g->streams[0]));
+    HIP_TRY(hipMemcpyAsync(rgb_sum, g->full.get(), total * sizeof(float), hipMemcpyDeviceToHost, g->streams[0]));
     for (int r = 0; r < N; ++r) {
         HIP_TRY(hipSetDevice(devs[r]));
         HIP_TRY(hipStreamSynchronize(g->streams[r]));

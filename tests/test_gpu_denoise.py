@@ -97,6 +97,21 @@ def test_kernel_equals_the_numpy_restatement(rtmi, which):
     assert np.array_equal(rtmi.denoise(ad_img, 16, a, n, d, 8, spp_map=ad_map, iterations=0).view(np.uint32), ad_img.view(np.uint32))
 
 
+def test_kept_buffers_regrow(rtmi):
+    """The records a device keeps between calls: a small frame, a larger one, the small one again.  A stale or mis-sized
+    buffer would show in the third output or in the second."""
+    frames = {}
+    for w, h in ((8, 8), (32, 16)):
+        sc = mixed(rtmi, w, h, 4)
+        frames[w, h] = (sc.render(rtmi.Opts(seed=SEED)), *features(rtmi, sc, 2))
+    outs = [rtmi.denoise(frames[size][0], 4, *frames[size][1:], 2) for size in ((8, 8), (32, 16), (8, 8))]
+    assert np.array_equal(outs[0].view(np.uint32), outs[2].view(np.uint32))
+    img, a, n, d = frames[32, 16]
+    want = restate(img, 4, a, n, d, 2, **DEFAULTS)
+    bad = (outs[1].view(np.uint32) != want.view(np.uint32)).any(axis=2).sum()
+    assert bad == 0, f"{bad} pixels differ in their bits"
+
+
 def _rmse(mean, ref):
     return float(np.sqrt(np.mean((mean.astype(np.float64) - ref) ** 2)))
 

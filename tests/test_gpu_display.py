@@ -242,6 +242,20 @@ def test_device_entry_equals_host_entry(rtmi):
 
 
 @gpu
+def test_kept_buffers_regrow(rtmi):
+    """The planes and the staging a device keeps between calls: a small frame, a larger one, the small one again (bloom on at
+    2 levels: the four-plane scratch).  A stale or mis-sized buffer would show in the third output or in the second."""
+    par = dict(tonemap=ACES, exposure=0.37, bloom_strength=0.6, bloom_threshold=1.5, bloom_levels=2)
+    small, large = frame(8, 8), frame(32, 16)
+    first, first8 = rtmi.display(small, SPP, **par)
+    rgb, rgb8 = rtmi.display(large, SPP, **par)
+    third, third8 = rtmi.display(small, SPP, **par)
+    assert same_bits(first, third) and np.array_equal(first8, third8)
+    want, want8 = restate(large, SPP, ACES, 0.37, bloom_strength=0.6, bloom_threshold=1.5, bloom_levels=2)
+    assert same_bits(rgb, want) and np.array_equal(rgb8, want8)
+
+
+@gpu
 @pytest.mark.parametrize("size", SIZES)
 def test_bloom_leaves_dark_frames_alone(rtmi, size):
     w, h = size

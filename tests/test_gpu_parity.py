@@ -96,6 +96,29 @@ def test_seed_changes_image_and_is_deterministic(rtmi, scenes_dir, golden_dir):
     assert not np.array_equal(a, hi)
 
 
+@pytest.mark.parametrize("entry", ["render", "accumulate", "render_adaptive"])
+def test_kept_buffers_regrow(rtmi, scenes_dir, golden_dir, entry):
+    """The device buffers a scene object keeps between calls (framebuffer, accumulators, adaptive planes, sample-count map):
+    4 tiles, then 24, then 4 again on ONE object, each result bit-identical to the same call on a fresh clone, whose device
+    residency is its own.  A stale or mis-sized kept buffer would show."""
+    def call(sc):
+        if entry == "render":
+            return (sc.render(rtmi.Opts(seed=SEED)),)
+        if entry == "accumulate":  # two calls of one sample each, continuing one accumulator
+            acc, _ = sc.accumulate(None, rtmi.Opts(seed=SEED, sample_first=0, sample_count=1))
+            acc, img = sc.accumulate(acc, rtmi.Opts(seed=SEED, sample_first=1, sample_count=1))
+            return acc, img
+        img, spp_map, _ = sc.render_adaptive(0.0, min_spp=2, max_spp=4, opts=rtmi.Opts(seed=SEED))
+        return img, spp_map
+
+    kept = _scene(rtmi, scenes_dir, golden_dir, "three_sphere")
+    for w, h in ((16, 16), (48, 32), (16, 16)):
+        kept.override(width=w, height=h, spp=2, max_depth=4)
+        got, want = call(kept), call(kept.clone())
+        for a, b in zip(got, want):
+            assert a.shape == b.shape and a.any() and np.array_equal(a, b), (entry, w, h)
+
+
 @pytest.mark.parametrize("world,tile_rows", [(2, 8), (3, 8), (8, 8), (2, 4), (5, 16)])
 def test_partition_invariance(rtmi, scenes_dir, golden_dir, world, tile_rows):
     """G4: the assembled row-tile shards are bit-identical to the unsharded frame."""

@@ -21,3 +21,19 @@ def test_host_code_is_sanitizer_clean(tmp_path, scenes_dir, golden_dir):
     r = subprocess.run([exe, str(tmp_path)] + files, capture_output=True, text=True, env=env)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "sanitize driver ok" in r.stdout and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr
+
+
+def test_hip_host_header_is_sanitizer_clean(tmp_path):
+    """csrc/hip_host.h (error check, device scope, kept device buffer, per-device record) against a fake HIP runtime with two
+    devices: tests/hip_host_driver.cpp.  No HIP runtime is linked; scene.cpp supplies set_error."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    csrc = os.path.join(root, "ray-tracing-in-cuda_amd", "csrc")
+    exe = str(tmp_path / "hip_host")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                    "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I", os.path.join(root, "include"),
+                    os.path.join(root, "tests", "hip_host_driver.cpp"), os.path.join(csrc, "scene.cpp"), "-o", exe], check=True)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([exe], capture_output=True, text=True, env=env)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "hip_host driver ok" in r.stdout and ", 0 live" in r.stdout
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr and "LeakSanitizer" not in r.stderr
