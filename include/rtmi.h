@@ -506,6 +506,8 @@ typedef struct rt_stats {
     int32_t grid_sheet;   /* rt_render_hip_count: 1 if the scene's grid is one cell high, i.e. the default kernel walks it along
                              x and z only (variant 2; the counting kernel itself walks in 3-D: same cells, same tests) */
     int32_t kernel_variant; /* the kernel that ran: what variant 0 (or a counting call) resolved to */
+    int32_t walk_resumed; /* rt_render_hip_count, grid: LANES that took up a walk which the wave had cut short an iteration earlier
+                             (its stragglers' hand-over; saturates at INT32_MAX).  In what was the struct's tail padding: same size */
 } rt_stats;
 
 void rt_opts_default(rt_opts *o);

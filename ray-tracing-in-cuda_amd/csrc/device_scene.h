@@ -43,6 +43,9 @@
 
 // spheres per cluster of the sphere table (a cluster occupies RT_CLUSTER + 1 slots, the last one never hit)
 #define RT_CLUSTER 8
+// sphere slots of a scene: fewer than this, so that 16 x a slot -- the byte offset of its cold record -- fits 32 bits
+// (the packer's lay_out_image refuses with RT_ERR_LIMIT; the kernels' rec_at relies on it)
+#define RT_MAX_SPHERE_SLOTS (1LL << 28)
 
 // records per light of the light table (light sampling)
 #define RT_LIGHT_STRIDE 7
@@ -182,6 +185,7 @@ struct DevCounters {
     unsigned long long group_maxpop, query_maxpop;  // culling: max over lanes of needed clusters, per visited group / per wave-query
     unsigned long long wave_queries;             // closest-hit queries executed per wave (loop iterations)
     unsigned long long lane_cands;               // range tables: candidate clusters per lane (before the box test)
+    unsigned long long walk_resumed;             // grid: lanes that took up a walk cut short in the previous iteration
 };
 
 }  // namespace rtmi

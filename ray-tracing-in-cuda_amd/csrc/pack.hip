@@ -281,6 +281,8 @@ Growth size_grid(const Scene &s, const SphereSlots &S, const OtherPrims &O, size
     const std::vector<int> &rest = S.rest;
     const double cell_factor = knob("RTMI_GRID_CELL", 1.0);
     const double ob_env = knob("RTMI_GRID_OB", 0.0);  // experiments
+    // (steps left per axis in 10 / 8 bits of one register; the walk's entry cell index is put together with 24-bit
+    //  multiplies, which these bounds keep far inside their range: (z n_y + y) n_x + x < 2^21)
     const double max_dim = g.wide ? 1023.0 : 255.0;
     const long long max_cells = g.wide ? (1LL << 21) : (1LL << 18);
     // centres (spheres) and box centres (others): the cloud the cells are sized for
@@ -664,8 +666,11 @@ int lay_out_hot(RenderParams &L, const Grid &g) {
 // Every offset of the image, in image order: the one place that says what the image looks like.  Returns the record count;
 // image_word[k]: the first 32-bit word of image texture k's texels.
 // off_media: the first record of the MEDIA part (rt_media.h; 0: the scene has no media); off_motion: of the MOTION part
-// (rt_motion.h; 0: no moving spheres).
+// (rt_motion.h; 0: no moving spheres).  -1: the environment's words would not fit an int32 offset; -2: 2^28 sphere slots or more.
 int lay_out_image(RenderParams &L, const Grid &g, const Scene &s, std::vector<int> &image_word, int &off_media, int &off_motion) {
+    // The kernels read the winner's cold record at a 32-bit BYTE offset from the cold table, 16 x its slot (rec_at,
+    // render_device.h): the slots end below 2^28.  This is the check that bound rests on; pack_scene refuses with RT_ERR_LIMIT.
+    if ((long long)L.ns >= RT_MAX_SPHERE_SLOTS) return -2;
     int off = lay_out_hot(L, g);
     L.hot_vec4_grid = off;  // what the grid-walk kernels stage into LDS
     // the boxes of the cluster searches (ablation builds) lie behind the grid tables, so that the grid walk does not stage
@@ -1111,6 +1116,7 @@ void write_environment(float *I, const RenderParams &L, const Scene &s) {
 // what a round tells pack_scene beside the image
 struct PackNote {
     bool too_large = false;  // the environment's tables end beyond an int32 word offset
+    bool too_many_slots = false;  // RT_MAX_SPHERE_SLOTS sphere slots or more (lay_out_image)
     bool demoted = false;  // (this or an earlier round) the members of an overflowing cell were forced
     size_t longest = 0;    // the longest list (near + far + others) of a cell a walk can meet
     NestedInfo nested;
@@ -1161,7 +1167,7 @@ bool pack_round(const Scene &s, std::vector<char> &forced, std::vector<float> &i
     int off_media = 0, off_motion = 0;
     const int records = lay_out_image(L, g, s, image_word, off_media, off_motion);
     if (records < 0) {
-        note.too_large = true;
+        (records == -2 ? note.too_many_slots : note.too_large) = true;
         return true;
     }
     if (s.env) {
@@ -1215,6 +1221,10 @@ int pack_scene(const Scene &s, std::vector<float> &image, RenderParams &layout, 
         set_error("the environment map's tables end beyond the int32 word offsets of the scene image");
         return RT_ERR_LIMIT;
     }
+    if (note.too_many_slots) {
+        set_error("the scene's spheres take %lld slots or more, beyond the 32-bit byte offsets of their cold records", RT_MAX_SPHERE_SLOTS);
+        return RT_ERR_LIMIT;
+    }
     // The nested grid (rt_scene_set_nested_grid): only a scene whose flat tables have a cell longer than the threshold, or lost
     // primitives to the always-tested set through an overflowing cell, is packed again -- wide, from a clean slate, with such
     // cells nested.  If that packing nests nothing (every clump was a clump in its sub-grid too), the flat tables stand.
@@ -1231,7 +1241,7 @@ int pack_scene(const Scene &s, std::vector<float> &image, RenderParams &layout, 
             bool packed2 = false;
             for (size_t round = 0; round <= s.prims.size() && !packed2; ++round)
                 packed2 = pack_round(s, forced2, image2, layout2, nest_over, nest_cap, note2);
-            if (packed2 && !note2.too_large && note2.nested.cells > 0) {
+            if (packed2 && !note2.too_large && !note2.too_many_slots && note2.nested.cells > 0) {
                 image = std::move(image2), layout = layout2;
                 if (nested_out) *nested_out = note2.nested;
             }

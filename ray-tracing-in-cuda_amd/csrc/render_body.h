@@ -39,7 +39,7 @@
 
     uint32_t c_samples = 0, c_queries = 0, c_hits = 0, c_misses = 0;
     uint32_t c_scatter0 = 0, c_scatter1 = 0, c_scatter2 = 0, c_scatter3 = 0;
-    uint32_t c_cand = 0, c_cand_wave = 0, c_clusters = 0, c_groups = 0, c_wave_queries = 0, c_lane_clusters = 0, c_lane_groups = 0, c_lane_cands = 0, c_group_maxpop = 0, c_query_maxpop = 0;
+    uint32_t c_cand = 0, c_cand_wave = 0, c_clusters = 0, c_groups = 0, c_wave_queries = 0, c_lane_clusters = 0, c_lane_groups = 0, c_lane_cands = 0, c_group_maxpop = 0, c_query_maxpop = 0, c_walk_resumed = 0;
     // COUNT: shader-clock time of the main loop's sections, per wave (refill, prefix spheres, culled spheres +
     // rects + cylinders, shading, pixel accumulation, loop control)
     unsigned long long cyc[6] = {0, 0, 0, 0, 0, 0}, tmark = 0, t_qe = 0;
@@ -519,7 +519,7 @@
                 // a walk that was cut short goes on a few ulps past the cell boundary it stopped at: inside the next cell (the
                 // lists' margin of 0.004 cell covers the sliver), so that every resumption ends at a later boundary
                 const float t_from = t_res * 1.000002f;
-                bool live = false;
+                bool enters = false;
                 int ci = 0, k = 0, kend = 0;
                 uint32_t rem = 0;  // steps left before the ray leaves the grid: x | y << 8 | z << 16
                 float tmx = INFINITY, tmy = INFINITY, tmz = INFINITY, t_exit = 0.0f;
@@ -533,8 +533,8 @@
                     const float lz = (bz0 - oz) * bp.idz, uz = (bz1 - oz) * bp.idz;
                     const float tn = fmaxf(fmaxf(fmaxf(fminf(lx, ux), fminf(ly, uy)), t_from), fminf(lz, uz));
                     t_exit = fminf(fminf(fmaxf(lx, ux), fmaxf(ly, uy)), fmaxf(lz, uz));
-                    live = !(tn > fminf(t_exit, blim));
-                    if (live) {
+                    enters = !(tn > fminf(t_exit, blim));
+                    if (enters) {
                         // the cell of the entry point
                         const float px = fmaf(tn, dx, ox), py = fmaf(tn, dy, oy), pz = fmaf(tn, dz, oz);
                         const int ix = min(max((int)floorf((px - g_min.x) * g_inv.x), 0), gnx - 1);
@@ -543,7 +543,8 @@
                         // neither a y cell index nor a y leave distance, and visits the cells the 3-D walk would visit)
                         const int iy = SHEET ? 0 : min(max((int)floorf((py - g_min.y) * g_inv.y), 0), gny - 1);
                         const int iz = min(max((int)floorf((pz - g_min.z) * g_inv.z), 0), gnz - 1);
-                        ci = SHEET ? iz * gnx + ix : (iz * gny + iy) * gnx + ix;
+                        // (24-bit multiplies, full rate: at most 1023 cells per axis and 2^21 in all, pack.hip size_grid)
+                        ci = SHEET ? __mul24(iz, gnx) + ix : __mul24(__mul24(iz, gny) + iy, gnx) + ix;
                         // ray parameter at which the ray leaves the cell along each axis (a component of exactly 0
                         // never leaves), and how many steps are left before it leaves the grid
                         tmx = dx == 0.0f ? INFINITY : (fmaf((float)(ix + (dx > 0.0f ? 1 : 0)), g_size.x, g_min.x) - ox) * bp.idx;
@@ -557,7 +558,14 @@
                     }
                 }
                 if (COUNT && far_scan) c_query_maxpop++;
+                if (COUNT && t_res != 0.0f) c_walk_resumed++;
                 t_res = 0.0f;
+                // The lanes that are still walking, as a lane mask in scalar registers (like c_hvmask): the loops below ask "any lane?"
+                // and "how many?" of it with scalar instructions, a lane that stops is cleared from it with one scalar and-not, and
+                // a lane-level `if` takes it as its exec mask.  (As a bool per lane, carried round the loops, it lived in a vector
+                // register as 0 / 1 and was compared back into a mask at the head of the walk, after every pass over the lists
+                // and before the tail's decision.)
+                unsigned long long live = __builtin_amdgcn_ballot_w64(enters);
                 // |size / d| per axis: what one step adds to the leave distance
                 float dtx = g_size.x * fabsf(bp.idx), dty = g_size.y * fabsf(bp.idy), dtz = g_size.z * fabsf(bp.idz);
                 int sx = dx > 0.0f ? 1 : -1, sy = dy > 0.0f ? gnx : -gnx, sz = SHEET ? (dz > 0.0f ? gnx : -gnx) : (dz > 0.0f ? gnx * gny : -(gnx * gny));
@@ -572,9 +580,9 @@
 #define RT_WALK_WAITING 32  /* ... and at least this many live lanes done: the stragglers go on next iteration */
 #endif
                 if (RT_PRIO_W != RT_PRIO_Q) __builtin_amdgcn_s_setprio(RT_PRIO_W);
-                while (__builtin_amdgcn_ballot_w64(live) != 0ull) {
+                while (live != 0ull) {
                     if constexpr (NEST) {
-                        if (live && sub >= 0) {
+                        if (__builtin_amdgcn_inverse_ballot_w64(live) && sub >= 0) {
                             // into the sub-grid of the nested cell this lane stands in: one 64-byte line per lane {min, first
                             // cell} {1 / size} {size} {n}.  The sub-grid spans what the cell's entries reach of the outer cell
                             // (grown, like the lists); the walk through it is the outer walk's code on this state, over the
@@ -589,13 +597,15 @@
                             const float ly = (s_min.y - oy) * bp.idy, uy = (fmaf((float)sny, s_size.y, s_min.y) - oy) * bp.idy;
                             const float lz = (s_min.z - oz) * bp.idz, uz = (fmaf((float)snz, s_size.z, s_min.z) - oz) * bp.idz;
                             const float t_in = fmaxf(fmaxf(fmaxf(fminf(lx, ux), fminf(ly, uy)), t_cur), fminf(lz, uz));
+                            // (fminf here, quieting and all: once per nested cell a lane enters, and not on the headline kernel's
+                            //  path -- min_arith is kept to the step pass, where the compiler has nothing to fold into it)
                             t_exit = fminf(fminf(fminf(t_exit, fminf(fminf(tmx, tmy), tmz)), fminf(fmaxf(lx, ux), fmaxf(ly, uy))), fmaxf(lz, uz));
                             const bool miss = t_in > fminf(t_exit, best_t * 1.0001f);
                             const float px = fmaf(t_in, dx, ox), py = fmaf(t_in, dy, oy), pz = fmaf(t_in, dz, oz);
                             const int ix = min(max((int)floorf((px - s_min.x) * s_inv.x), 0), snx - 1);
                             const int iy = min(max((int)floorf((py - s_min.y) * s_inv.y), 0), sny - 1);
                             const int iz = min(max((int)floorf((pz - s_min.z) * s_inv.z), 0), snz - 1);
-                            ci = __float_as_int(s_min.w) + (iz * sny + iy) * snx + ix;
+                            ci = __float_as_int(s_min.w) + __mul24(__mul24(iz, sny) + iy, snx) + ix;
                             tmx = dx == 0.0f ? INFINITY : (fmaf((float)(ix + (dx > 0.0f ? 1 : 0)), s_size.x, s_min.x) - ox) * bp.idx;
                             tmy = dy == 0.0f ? INFINITY : (fmaf((float)(iy + (dy > 0.0f ? 1 : 0)), s_size.y, s_min.y) - oy) * bp.idy;
                             tmz = dz == 0.0f ? INFINITY : (fmaf((float)(iz + (dz > 0.0f ? 1 : 0)), s_size.z, s_min.z) - oz) * bp.idz;
@@ -632,13 +642,13 @@
                         // (the masks of the two conditions are combined as scalars, and the count is declared wave-uniform:
                         //  ballot(a && b) of two lane masks goes through a VGPR, and its popcount is compared as a vector)
                         if (RT_STEP_AT < 65 &&
-                            mask_count(__builtin_amdgcn_ballot_w64(live) & ~__builtin_amdgcn_ballot_w64(k < kend)) >= RT_STEP_AT)
+                            mask_count(live & ~__builtin_amdgcn_ballot_w64(k < kend)) >= RT_STEP_AT)
                             break;
                     }
                     // the cell's other primitives, one per lane and pass, for the lanes that are through with its spheres
                     if (OTHERS) {
-                        while (__builtin_amdgcn_ballot_w64(live && !(k < kend) && ko < koend) != 0ull) {
-                            if (live && !(k < kend) && ko < koend) {
+                        while ((live & ~__builtin_amdgcn_ballot_w64(k < kend) & __builtin_amdgcn_ballot_w64(ko < koend)) != 0ull) {
+                            if (__builtin_amdgcn_inverse_ballot_w64(live) && !(k < kend) && ko < koend) {
                                 const int id = (int)g_items32[ko];
                                 ++ko;
                                 if (COUNT) c_lane_clusters++;
@@ -672,17 +682,20 @@
                     // its shading, the stragglers stop at their next cell boundary and go on from there in the next
                     // iteration, together with the new queries (the walk is front to back: nothing nearer than the
                     // boundary was found, and whatever was found beyond it is found again in its own cell).
-                    const unsigned long long walking = __builtin_amdgcn_ballot_w64(live);
-                    const bool cut = RT_WALK_TAIL > 0 && mask_count(walking) <= RT_WALK_TAIL &&
-                                     mask_count(__builtin_amdgcn_ballot_w64(active) & ~walking) >= RT_WALK_WAITING;
-                    if (live && !(k < kend) && !(OTHERS && ko < koend)) {
+                    const bool cut = RT_WALK_TAIL > 0 && mask_count(live) <= RT_WALK_TAIL &&
+                                     mask_count(__builtin_amdgcn_ballot_w64(active) & ~live) >= RT_WALK_WAITING;
+                    // the lanes that are through with their cell's lists: they step, or stop.  (Every lane evaluates the step's
+                    // conditions; they count for these lanes alone, as masks: who stops, who is cut short, who goes on.)
+                    unsigned long long stepping = live & ~__builtin_amdgcn_ballot_w64(k < kend);
+                    if (OTHERS) stepping &= ~__builtin_amdgcn_ballot_w64(ko < koend);
+                    {
                         if constexpr (NEST) {
-                            if (in_sub) {
+                            if (__builtin_amdgcn_inverse_ballot_w64(stepping) && in_sub) {
                                 // the sub-grid's walk is over where the outer walk's would be (past the ray's stay in the outer
                                 // cell, which is t_exit here, or past a hit, or at the sub-grid's last cell): back to the outer one
-                                const float tn_s = fminf(fminf(tmx, tmy), tmz);
+                                const float tn_s = min3_arith(tmx, tmy, tmz);
                                 const int sh_s = tmx == tn_s ? 0 : (tmy == tn_s ? REM_BITS : 2 * REM_BITS);
-                                if (tn_s > fminf(t_exit, best_t * 1.0001f) || ((rem >> sh_s) & REM_MASK) == 0u) {
+                                if (tn_s > min_arith(t_exit, best_t * 1.0001f) || ((rem >> sh_s) & REM_MASK) == 0u) {
                                     tmx = o_tmx, tmy = o_tmy, tmz = o_tmz, t_exit = o_texit, rem = o_rem, ci = o_ci;
                                     dtx = g_size.x * fabsf(bp.idx), dty = g_size.y * fabsf(bp.idy), dtz = g_size.z * fabsf(bp.idz);
                                     sx = dx > 0.0f ? 1 : -1, sy = dy > 0.0f ? gnx : -gnx, sz = dz > 0.0f ? gnx * gny : -(gnx * gny);
@@ -690,15 +703,19 @@
                                 }
                             }
                         }
-                        const float tnext = SHEET ? fminf(tmx, tmz) : fminf(fminf(tmx, tmy), tmz);
+                        // (the leave distances and t_exit are sums, products and minima of such, or +-inf, carried round the loop:
+                        //  min_arith, where fminf would first quiet all three, one v_max_f32 each)
+                        const float tnext = SHEET ? min_arith(tmx, tmz) : min3_arith(tmx, tmy, tmz);
                         const bool xle = tmx == tnext, yle = !SHEET && !xle && tmy == tnext;
                         const int sh = xle ? 0 : (yle ? REM_BITS : 2 * REM_BITS);
-                        if (tnext > fminf(t_exit, best_t * 1.0001f) || ((rem >> sh) & REM_MASK) == 0u) {
-                            live = false;
-                        } else if (cut && tnext > t_from && !(best_t < tnext)) {  // (a hit inside the cell being left stays: the walk ends at the next boundary test)
-                            live = false;
-                            t_res = tnext;
-                        } else {
+                        const unsigned long long ends = __builtin_amdgcn_ballot_w64(tnext > min_arith(t_exit, best_t * 1.0001f)) |
+                                                        __builtin_amdgcn_ballot_w64(((rem >> sh) & REM_MASK) == 0u);
+                        // (a hit inside the cell being left stays: the walk ends at the next boundary test)
+                        const unsigned long long cuts =
+                            cut ? __builtin_amdgcn_ballot_w64(tnext > t_from) & ~__builtin_amdgcn_ballot_w64(best_t < tnext) & ~ends : 0ull;
+                        live &= ~(stepping & (ends | cuts));
+                        if (__builtin_amdgcn_inverse_ballot_w64(stepping & cuts)) t_res = tnext;
+                        if (__builtin_amdgcn_inverse_ballot_w64(stepping & ~(ends | cuts))) {
                             ci += xle ? sx : (yle ? sy : sz);
                             tmx += xle ? dtx : 0.0f, tmz += (xle || yle) ? 0.0f : dtz;
                             if (!SHEET) tmy += yle ? dty : 0.0f;
@@ -1021,7 +1038,7 @@
                     kind = __float_as_int(g2.y);
                 } else if (SPH || best_id < ns) {
                     const float4 s = sph[best_id];
-                    const float4 cold = image[P.off_sph_cold + best_id];
+                    const float4 cold = *rec_at(image + P.off_sph_cold, (uint32_t)best_id << 4);  // (fewer than 2^28 slots: lay_out_image)
                     px = fmaf(best_t, dx, ox), py = fmaf(best_t, dy, oy), pz = fmaf(best_t, dz, oz);
                     const float onx = cold.x * (px - s.x), ony = cold.x * (py - s.y), onz = cold.x * (pz - s.z);
                     front = dot3(dx, dy, dz, onx, ony, onz) < 0.0f;
@@ -1344,11 +1361,13 @@
             }
             if (start) {
                 cur_p = sp;
-                rng_start(rng, (uint32_t)(spy * P.width + spx), (uint32_t)ss, k0, k1);
+                // (row and width are at most 65536, scene_validate: a 24-bit multiply, full rate; its low 32 bits are the id's)
+                const uint32_t pixel = __umul24((uint32_t)spy, (uint32_t)P.width) + (uint32_t)spx;
+                rng_start(rng, pixel, (uint32_t)ss, k0, k1);
                 if constexpr (MOTION) {  // (the key behind the same barrier as in rng_start: its schedule stays scalar)
                     uint32_t m0 = k0, m1 = k1;
                     asm volatile("" : "+s"(m0), "+s"(m1));
-                    mot_s = shutter_time((uint32_t)(spy * P.width + spx), (uint32_t)ss, m0, m1);
+                    mot_s = shutter_time(pixel, (uint32_t)ss, m0, m1);
                 }
                 u = ((float)spx + rng_next<COUNT>(rng)) * P.inv_wm1;
                 v = ((float)spy + rng_next<COUNT>(rng)) * P.inv_hm1;
@@ -1410,7 +1429,7 @@
         bool nee_v = false, nee_end = false;
         float vb_r = 0, vb_g = 0, vb_b = 0, mrx = 0, mry = 0, mrz = 0, mfz = 0;
         if (kind >= 0) {
-            const float4 *M = image + P.off_mat + 3 * mat;
+            const float4 *M = rec_at(image + P.off_mat, __umul24((uint32_t)mat, 48u));  // (below 2^24 materials: scene_validate)
             if constexpr (MEDIA) {  // (a medium's record 1 is {albedo, density}: where a material keeps c0)
                 if (kind == MK_MEDIUM) M = image + __builtin_amdgcn_readfirstlane(__float_as_int(image[P.off_cam + 2].w)) + RT_MEDIUM_STRIDE * mat;
             }
@@ -1672,6 +1691,7 @@
         wave_add(&counters->lane_cands, c_lane_cands);
         wave_add(&counters->group_maxpop, c_group_maxpop);
         wave_add(&counters->query_maxpop, c_query_maxpop);
+        wave_add(&counters->walk_resumed, c_walk_resumed);
         if (lane == 0) {
             for (int i = 0; i < 6; ++i) atomicAdd(&counters->cycles[i], cyc[i]);
             const unsigned long long t = __builtin_amdgcn_s_memrealtime();

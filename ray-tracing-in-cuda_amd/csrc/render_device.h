@@ -120,6 +120,33 @@ __device__ __forceinline__ int mask_count(unsigned long long m) {
     return __builtin_amdgcn_readfirstlane(__builtin_popcount((uint32_t)m) + __builtin_popcount((uint32_t)(m >> 32)));
 }
 
+// fminf for operands that are results of fp32 arithmetic or +-inf, never a signalling NaN: the bare v_min_f32 / v_min3_f32,
+// which in the kernel's IEEE mode return the other operand for a quiet NaN, as fminf does.  fminf() itself quiets every
+// operand whose origin the compiler cannot see (a value carried round a loop) with a v_max_f32 x, x, x of its own first.
+// As inline assembly they take vector registers only and are opaque to the compiler -- no constant, scalar operand or source
+// modifier folds in, no min3 / med3 forms across them -- so they are for the walk's step pass alone, whose operands are
+// lane values in registers anyway; everywhere else fminf stays.
+__device__ __forceinline__ float min_arith(float a, float b) {
+    float r;
+    asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ float min3_arith(float a, float b, float c) {
+    float r;
+    asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
+
+// The record `bytes` behind a wave-uniform table address, the offset a 32-bit lane value: the load takes its base from
+// scalar registers and its offset from one vector register, and no 64-bit address is put together on the vector ALU.
+// The callers' bounds, each refused with RT_ERR_LIMIT where the host would break it: a sphere's cold record, 16 x its slot
+// with fewer than RT_MAX_SPHERE_SLOTS = 2^28 slots (pack.hip, lay_out_image); a material's record, 48 x its index with fewer
+// than 2^24 materials (scene.cpp, scene_validate).
+static_assert(RT_MAX_SPHERE_SLOTS * 16 <= (1LL << 32), "a cold record's byte offset in 32 bits");
+__device__ __forceinline__ const float4 *rec_at(const float4 *table, uint32_t bytes) {
+    return reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(table) + bytes);
+}
+
 // checker_texture::value, texture.cuh:44-52: sign of sin(10x)sin(10y)sin(10z) as the
 // parity of floor(10x/pi) + floor(10y/pi) + floor(10z/pi); zero factor -> even
 __device__ __forceinline__ bool checker_odd(float px, float py, float pz) {

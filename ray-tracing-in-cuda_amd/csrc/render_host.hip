@@ -489,6 +489,7 @@ static int read_counters(const DevCounters *d_cnt, const RenderParams &P, int cu
     stats->lane_cands = h.lane_cands;
     stats->group_maxpop = h.group_maxpop;
     stats->query_maxpop = h.query_maxpop;
+    stats->walk_resumed = (int32_t)std::min<unsigned long long>(h.walk_resumed, (unsigned long long)INT32_MAX);
     for (int i = 0; i < 6; ++i) stats->cycles[i] = h.cycles[i];
     stats->wave_start_spread_us = (double)(h.t_start_max - h.t_start_min) * 0.01;
     stats->wave_end_spread_us = (double)(h.t_end_max - h.t_end_min) * 0.01;

@@ -148,9 +148,18 @@ int scene_validate(const Scene &s) {
         set_error("width and height must be >= 2 (got %dx%d)", s.width, s.height);
         return RT_ERR_SCENE;
     }
+    // (THIS is the check the kernels rely on for a sample's pixel id: row x width + column is one 24-bit multiply-add there,
+    //  which takes both factors below 2^24 -- render_body.h, the refill.  Every entry point validates the scene before it
+    //  packs or renders it; the launch path's own width check in render_host.hip guards the tile index it packs, nothing else.
+    //  An image this size is a malformed scene rather than a kernel limit, hence RT_ERR_SCENE as before.)
     if (s.width > 65536 || s.height > 65536) {
         set_error("image larger than 65536 on a side (%dx%d)", s.width, s.height);
         return RT_ERR_SCENE;
+    }
+    // (likewise: a material record's byte offset, 48 x its index, is a 24-bit multiply in the scatter step)
+    if (s.mats.size() >= ((size_t)1 << 24)) {
+        set_error("%zu materials exceed the kernels' 24-bit material index", s.mats.size());
+        return RT_ERR_LIMIT;
     }
     if (s.spp < 1 || s.max_depth < 0) {
         set_error("samples_per_pixel must be >= 1 and max_depth >= 0 (got %d, %d)", s.spp, s.max_depth);
