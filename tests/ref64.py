@@ -4,9 +4,10 @@ NumPy, vectorised over a batch of samples, at a floating type of the caller's ch
 formulas at the kernel's precision, used to measure how many samples sit on a branch).
 
 Test infrastructure only.  It is written from the definitions -- DESIGN 2 (the integrator, the order of the draws), 7a, 7e,
-7f (the media walk), 7g (the shutter time, the movers' query and its tie rule), and the reference's primitive and material
-definitions -- with libm's arccos / arctan2 / log, plain closest-hit loops over the primitive, mover and media lists and no fused
-operations.  It shares no code with the kernels or with oracle/.
+7f (the media walk), 7g (the shutter time, the movers' query and its tie rule), and the reference's primitive, material and
+texture definitions (triangles, the hit record's (u, v) and the image lookup among them) -- with libm's arccos / arctan2 / log,
+plain closest-hit loops over the primitive, mover and media lists and no fused operations.  It shares no code with the kernels
+or with oracle/.
 
 There is ONE integrator loop, trace().  An extension joins it with a record list on RefScene (lights, media, movers: empty
 unless the scene has them), a block in the loop, columns in the signature and keys in tally().  The reference evaluates the
@@ -17,13 +18,15 @@ mover -- trace() raises NotImplementedError.
 Inputs are the product's exported tables (Scene.prims / materials / textures / lights / media / moving_spheres / get_camera /
 info / environment), the light alias table and the environment's CDF tables as the packed image stores them (table_image,
 found by content), the uniforms of rtmi.sample_stream and, for movers, the shutter times of rtmi.shutter_time (one per sample:
-the time is no draw of the stream).  Out of scope: triangles, image textures, the nested grid.
+the time is no draw of the stream) and the pixels of the image textures (Scene.get_image).  Triangles and image textures are
+in scope.  Out of scope: the nested grid (a candidate search, which this reference has none of: it scans the lists).
 
 trace() returns, per sample, the radiance, an event signature (one row of integers: per vertex the primitive hit, the mover
 that took over, the set of media that took a free-flight draw and the medium whose event won, what the material did, the
-checker parity, the roulette outcome, the light and texel picked and whether through the alias, the shadow ray's verdict, how
-an emitter hit was weighted; columns a scene does not exercise stay NONE; two samples took the same branches iff their rows
-are equal; tally() counts the special vertices of a batch from it) and the number of draws consumed.
+checker parity, the image texel read, the roulette outcome, the light and texel picked and whether through the alias, the
+shadow ray's verdict and the primitive that stopped it, how an emitter hit was weighted; columns a scene does not exercise
+stay NONE; two samples took the same branches iff their rows are equal; tally() counts the special vertices of a batch from
+it) and the number of draws consumed.
 """
 import numpy as np
 
@@ -44,9 +47,11 @@ NONE = -9
 # winner; C_MOVER the mover that took over (-1: none) in a scene with movers; C_DREW the set of media that took a free-flight
 # draw and C_MEDIUM the medium whose event won (-1: none) in a scene with media
 SAMPLE_COLUMNS = 2
+# C_IMAGE_TEXEL the flat index (row x cols + col) of the image texel the vertex's material read; C_BLOCKER the primitive that
+# stopped the shadow ray
 (C_PRIM, C_MISS_TEXEL, C_PARITY, C_EVENT, C_ROULETTE, C_LIGHT, C_TEXEL, C_SHADOW, C_HIT_WEIGHT, C_ALIAS,
- C_MOVER, C_DREW, C_MEDIUM) = range(13)
-VERTEX_COLUMNS = 13
+ C_MOVER, C_DREW, C_MEDIUM, C_IMAGE_TEXEL, C_BLOCKER) = range(15)
+VERTEX_COLUMNS = 15
 # C_SHADOW: the light sample reached its light / was occluded / had zero weight (no shadow ray) / was not made because the
 # vertex lies inside the sphere light it picked
 SHADOW_CLEAR, SHADOW_OCCLUDED, SHADOW_NONE, SHADOW_INSIDE = range(4)
@@ -120,12 +125,7 @@ class RefScene:
         self.cam = {k: np.array(getattr(cam, k)[:], np.float32) for k in ("origin", "lower_left", "horizontal", "vertical", "u", "v")}
         self.lens_radius = np.float32(cam.lens_radius)
         self.prims, self.mats, self.texs = sc.prims(), sc.materials(), sc.textures()
-        for p in self.prims:
-            if p["type"] == TRIANGLE:
-                raise ValueError("triangles are out of this reference's scope")
-        for m in self.mats:
-            if m["type"] in (LAMBERTIAN, DIFFUSE_LIGHT) and self.texs[m["texture"]]["type"] == IMAGE:
-                raise ValueError("image textures are out of this reference's scope")
+        self.images = {ti: sc.get_image(ti) for ti, t in enumerate(self.texs) if t["type"] == IMAGE}  # (rows, cols, 3) uint8
         self.env = None
         environment = sc.environment
         self.nee = sc.light_sampling if nee is None else bool(nee)
@@ -176,6 +176,31 @@ def _affine(m, T):
     return m[:, :3], m[:, 3]
 
 
+def _cross(a, b):
+    return np.stack([a[..., 1] * b[..., 2] - a[..., 2] * b[..., 1], a[..., 2] * b[..., 0] - a[..., 0] * b[..., 2],
+                     a[..., 0] * b[..., 1] - a[..., 1] * b[..., 0]], axis=-1)
+
+
+def _triangle_plane(p, o, d, dd, T):
+    """hit_triangle up to its range test: (the plane point r, theta = d.n / |d| with the stored normal n turned to the origin's
+    side, (o - v1).n, the four same-side tests all > 0).  The ray is rejected unless theta < 0."""
+    m = p["m"].astype(T)
+    v1, v2, v3, n0 = m[0:3], m[3:6], m[6:9], m[9:12]
+    oc = o - v1
+    n = np.where((_dot(oc, n0) < 0)[:, None], -n0, n0)
+    a = np.sqrt(dd)
+    with np.errstate(all="ignore"):
+        theta = _dot(d, n) / a
+        ocn = _dot(oc, n)
+        r = o - d / a[:, None] * ocn[:, None] / theta[:, None]
+        n1 = _dot(_cross(r - v1, v2 - v1), _cross(v3 - v1, v2 - v1))
+        n2 = _dot(_cross(r - v2, v1 - v2), _cross(v3 - v2, v1 - v2))
+        n3 = _dot(_cross(r - v1, v3 - v1), _cross(v2 - v1, v3 - v1))
+        n4 = _dot(_cross(r - v2, v3 - v2), _cross(v1 - v2, v3 - v2))
+        inside = (n1 > 0) & (n2 > 0) & (n3 > 0) & (n4 > 0)
+    return r, theta, ocn, inside
+
+
 def _prim_t(p, o, d, dd, t_min, best, T):
     """ray parameter at which the primitive's own hit() accepts the ray within [t_min, best], NaN where it does not"""
     nan = T(np.nan)
@@ -196,6 +221,9 @@ def _prim_t(p, o, d, dd, t_min, best, T):
             a, b = o[:, aa] + t * d[:, aa], o[:, ba] + t * d[:, ba]
             inside = (a >= f[0]) & (a <= f[1]) & (b >= f[2]) & (b <= f[3])
             return np.where(inside, t, nan)
+        if ty == TRIANGLE:
+            _, theta, ocn, inside = _triangle_plane(p, o, d, dd, T)
+            return np.where((theta < 0) & inside, -ocn / theta / np.sqrt(dd), nan)
         # open tube about the object-space z axis
         R, tr = _affine(p["m_inv"], T)
         oo, od = o @ R.T + tr, d @ R.T
@@ -247,6 +275,8 @@ def hit_record(S, o, d, t, idx, T):
             radial = np.stack([op[:, 0], op[:, 1], np.zeros_like(op[:, 0])], axis=1)
             radial /= np.sqrt(_dot(radial, radial))[:, None]
             n_out[m] = radial @ R  # apply_normal: the transpose of the inverse
+        elif ty == TRIANGLE:
+            n_out[m] = pr["m"][9:12].astype(T)  # the stored unit normal
         else:
             n_out[m, _rect_axes(ty)[0]] = 1
     front = _dot(d, n_out) < 0
@@ -304,14 +334,87 @@ def checker_odd(p, T):
     return (k % 2 != 0) & ~(p == 0).any(axis=1)
 
 
-def texture_value(S, tex, p, T):
+def sphere_uv(n, T):
+    """get_sphere_uv of a unit outward normal: u from the azimuth atan2(-z, x) + pi, v from the polar angle acos(-y)"""
+    pi = T(np.pi)
+    return (np.arctan2(-n[:, 2], n[:, 0]) + pi) / (2 * pi), np.arccos(-n[:, 1]) / pi
+
+
+def hit_uv(S, o, d, t, idx, T, mov=None, time=None, perturb=()):
+    """the hit record's (u, v) of accepted hits: of the static primitive idx, or of mover mov >= 0 at the samples' shutter times"""
+    u, v = np.zeros(len(o), T), np.zeros(len(o), T)
+    static = np.ones(len(o), bool) if mov is None else mov < 0
+    with np.errstate(all="ignore"):
+        for mi in (() if mov is None else np.unique(mov[~static])):
+            k = mov == mi
+            mv = S.movers[mi]
+            n_out = (o[k] + t[k][:, None] * d[k] - mover_centre(mv, time[k], T)) / T(mv["radius"])
+            u[k], v[k] = sphere_uv(n_out, T)
+        for i in np.unique(idx[static]):
+            k = static & (idx == i)
+            pr = S.prims[i]
+            ty, f = int(pr["type"]), pr["f"].astype(T)
+            oo, dd, tt = o[k], d[k], t[k]
+            if ty == SPHERE:
+                u[k], v[k] = sphere_uv((oo + tt[:, None] * dd - f[:3]) / f[3], T)
+            elif ty in (XY_RECT, XZ_RECT, YZ_RECT):
+                _, aa, ba = _rect_axes(ty)
+                u[k] = (oo[:, aa] + tt * dd[:, aa] - f[0]) / (f[1] - f[0])
+                v[k] = (oo[:, ba] + tt * dd[:, ba] - f[2]) / (f[3] - f[2])
+            elif ty == CYLINDER:
+                R, tr = _affine(pr["m_inv"], T)
+                op = (oo @ R.T + tr) + tt[:, None] * (dd @ R.T)
+                u[k] = (np.arctan2(op[:, 1], op[:, 0]) + 2 * T(np.pi)) / (4 * T(np.pi))
+                v[k] = (op[:, 2] - f[1]) / (f[2] - f[1])
+            else:
+                # the area weights of the plane point, each with the corner the reference pairs it with: the sub-triangle
+                # (r, v1, v2) over the whole goes with u1, (r, v1, v3) with u2, (r, v3, v2) with u3
+                m = pr["m"].astype(T)
+                v1, v2, v3 = m[0:3], m[3:6], m[6:9]
+                c = pr["m_inv"].astype(T)
+                uv1, uv2, uv3 = c[0:2], c[2:4], c[4:6]
+                if "tri_natural_pairing" in perturb:  # each weight with the corner opposite its sub-triangle
+                    uv1, uv3 = uv3, uv1
+                r, _, _, _ = _triangle_plane(pr, oo, dd, _dot(dd, dd), T)
+                norm = lambda a: np.sqrt(_dot(a, a))
+                w1 = norm(_cross(r - v1, r - v2)) / norm(_cross(v3 - v1, v3 - v2))
+                w2 = norm(_cross(r - v1, r - v3)) / norm(_cross(v2 - v1, v2 - v3))
+                w3 = norm(_cross(r - v3, r - v2)) / norm(_cross(v1 - v3, v1 - v2))
+                u[k] = uv1[0] * w1 + uv2[0] * w2 + uv3[0] * w3
+                v[k] = uv1[1] * w1 + uv2[1] * w2 + uv3[1] * w3
+    return u, v
+
+
+def image_texel(img, u, v, T, perturb=()):
+    """(row, col) of texel[int(frac(u) rows)][int(frac(v) cols)]: u indexes ROWS; clamped to the last row and column"""
+    rows, cols = img.shape[:2]
+    if "uv_transposed" in perturb:
+        u, v = v, u
+    with np.errstate(invalid="ignore"):
+        row = np.nan_to_num((u - np.floor(u)) * T(rows)).astype(np.int64).clip(0, rows - 1)
+        col = np.nan_to_num((v - np.floor(v)) * T(cols)).astype(np.int64).clip(0, cols - 1)
+    return row, col
+
+
+def texture_value(S, tex, p, T, o=None, d=None, t=None, idx=None, mov=None, time=None, perturb=()):
+    """(colour, flat index of the image texel read or NONE) of the textures `tex` at the hits: a solid colour, the checker's
+    parity at the point p, or the image's texel at the hit record's (u, v), which needs the ray (o, d), its parameter t, the
+    static primitive idx, and the mover that took over with the samples' shutter times"""
     out = np.zeros_like(p)
+    texel = np.full(len(p), NONE, np.int64)
     for ti in np.unique(tex):
         m = tex == ti
-        t = S.texs[ti]
-        c0, c1 = t["c0"].astype(T), t["c1"].astype(T)
-        out[m] = np.where(checker_odd(p[m], T)[:, None], c1, c0) if t["type"] == CHECKER else c0
-    return out
+        tx = S.texs[ti]
+        c0, c1 = tx["c0"].astype(T), tx["c1"].astype(T)
+        if tx["type"] == IMAGE:
+            img = S.images[int(ti)]
+            u, v = hit_uv(S, o[m], d[m], t[m], idx[m], T, None if mov is None else mov[m], None if time is None else time[m], perturb)
+            row, col = image_texel(img, u, v, T, perturb)
+            out[m] = img[row, col].astype(T) / T(255)
+            texel[m] = row * img.shape[1] + col
+        else:
+            out[m] = np.where(checker_odd(p[m], T)[:, None], c1, c0) if tx["type"] == CHECKER else c0
+    return out, texel
 
 
 def metal_pdf(w, r, f, T):
@@ -490,7 +593,8 @@ def trace(S, words, first_pixel=0, dtype=np.float64, perturb=(), shutter=None):
     int64, draws consumed [N]).  perturb names deliberate mistakes, for the tests that show the comparison can fail: "skip_draw",
     "no_cos", "mis_unsquared", "no_rr_light" at the light sample; "skip_flight" leaves the free-flight draw out (the distance is
     taken from the NEXT position instead: a wrong order of draws); "half_time" puts every sample at s = 0.5 (a renderer that
-    ignores the shutter time)."""
+    ignores the shutter time); "uv_transposed": the image lookup with u indexing columns; "tri_natural_pairing": each area weight
+    of a triangle with the corner opposite its sub-triangle."""
     T = dtype
     N = len(words)
     D = _Draws(words, T)
@@ -617,11 +721,18 @@ def trace(S, words, first_pixel=0, dtype=np.float64, perturb=(), shutter=None):
         checker = np.isin(kind, (LAMBERTIAN, DIFFUSE_LIGHT)) & (S.texs["type"][np.maximum(tex, 0)] == CHECKER)
         note(C_PARITY, who, np.where(checker, checker_odd(p, T), NONE))
         event = np.full(len(who), NONE, np.int64)
+        shutter_of = time[who] if len(S.movers) else None
+
+        def textured(k):  # the texture's value at the vertices k, with the image texel it read noted
+            value, texel = texture_value(S, tex[k], p[k], T, oo[k], dd[k], t_hit[k], idx[k], mov[k],
+                                         None if shutter_of is None else shutter_of[k], perturb)
+            note(C_IMAGE_TEXEL, who[k], texel)
+            return value
         # ---- an emitter ends the path with what it emits
         em = kind == DIFFUSE_LIGHT
         if em.any():
             m = who[em]
-            Le = texture_value(S, tex[em], p[em], T)
+            Le = textured(em)
             wgt = np.ones(em.sum(), T)
             how = np.full(em.sum(), HIT_UNSAMPLED, np.int64)
             for li in {S.light_of_prim.get(int(i), -1) for i in np.unique(listed[em])} - {-1}:
@@ -655,7 +766,7 @@ def trace(S, words, first_pixel=0, dtype=np.float64, perturb=(), shutter=None):
             nd = n[lam] + _unit(sph)
             tiny = (np.abs(nd) < 1e-8).all(axis=1)
             nd[tiny] = n[lam][tiny]
-            new_d[lam], att[lam] = nd, texture_value(S, tex[lam], p[lam], T)
+            new_d[lam], att[lam] = nd, textured(lam)
             event[lam] = EV_LAMBERT
             takes_light[lam] = True
             pdf_b[lam] = np.maximum(0, _dot(_unit(nd), n[lam])) / pi
@@ -760,6 +871,7 @@ def trace(S, words, first_pixel=0, dtype=np.float64, perturb=(), shutter=None):
             far = np.where(is_env, T(np.inf), T(SHADOW_T_MAX))
             _, blocker = closest_hit(S, p[ls][k], ld[k], far, T)
             verdict[k] = np.where(blocker >= 0, SHADOW_OCCLUDED, SHADOW_CLEAR)
+            note(C_BLOCKER, m[k], np.where(blocker >= 0, blocker, NONE))
             clear = k[blocker < 0]
             through = carried[ls][clear]
             if "no_rr_light" in perturb and rr > 0:
@@ -778,16 +890,28 @@ def same_signature(a, b):
     return (pad(a) == pad(b)).all(axis=1)
 
 
-def tally(sig):
+def tally(sig, S=None):
     """How often the special vertices of DESIGN 7a occurred in a batch, read from its signatures, so that a test of such a case can
     assert that the case was there: light samples not made because the vertex lies inside the sphere light it picked, and BSDF
     hits on that light from inside kept at weight 1; absorbed metal vertices that took a light sample all the same; dielectric
     vertices, the light samples they took (none, by definition) and the emitter hits of their rays at full weight; light picks
     that went to the bucket's own light and to its alias.  Of 7f (MEDIA_KEYS): medium events, those on paths that met a surface
     vertex later, those behind a refraction, and the media that had one.  Of 7g (MOTION_KEYS): vertices on movers, which movers
-    were hit, and the paths that went from a mover to a static surface and the other way."""
+    were hit, and the paths that went from a mover to a static surface and the other way.  Of triangles and image textures
+    (EXT_KEYS): vertices that read an image texel, those that took a light sample, those on a mover, the samples with such a
+    vertex, and the samples that met one after a medium event; emitter hits at full weight behind a vertex that took a light
+    sample (the emitter is no listed light); and, where the RefScene S says which primitives are triangles and which carry
+    an image texture, vertices on triangles, those that took a light sample, and shadow rays stopped by either kind."""
     v = sig[:, SAMPLE_COLUMNS:].reshape(len(sig), -1, VERTEX_COLUMNS)
     event, light, shadow, how, alias, mover = (v[:, :, c] for c in (C_EVENT, C_LIGHT, C_SHADOW, C_HIT_WEIGHT, C_ALIAS, C_MOVER))
+    prim, blocker = v[:, :, C_PRIM], v[:, :, C_BLOCKER]
+    image = v[:, :, C_IMAGE_TEXEL] != NONE
+    is_tri, is_image = np.zeros(1, bool), np.zeros(1, bool)
+    if S is not None and len(S.prims):
+        is_tri = S.prims["type"] == TRIANGLE
+        mat = S.mats[S.prims["material"]]
+        is_image = np.isin(mat["type"], (LAMBERTIAN, DIFFUSE_LIGHT)) & (S.texs["type"][mat["texture"]] == IMAGE)
+    of = lambda flags, i: (i >= 0) & flags[np.clip(i, 0, len(flags) - 1)]
     glass = np.isin(event, (EV_REFLECT, EV_REFRACT))
     later = lambda x: np.flip(np.cumsum(np.flip(x, axis=1), axis=1), axis=1) - x > 0
     med = event == EV_MEDIUM
@@ -795,6 +919,7 @@ def tally(sig):
     glass_before = np.cumsum(np.isin(event, (EV_REFRACT,)), axis=1) > 0
     vertex = event != NONE
     on_mover, on_static = vertex & (mover >= 0), vertex & (mover < 0)
+    on_tri = on_static & ~med & of(is_tri, prim)
     return dict(inside_no_sample=int((shadow == SHADOW_INSIDE).sum()), inside_full_weight_hits=int((how == HIT_FROM_INSIDE).sum()),
                 absorbed_metal_light_samples=int(((event == EV_METAL_ABSORBED) & (light != NONE)).sum()),
                 dielectric_vertices=int(glass.sum()), dielectric_light_samples=int((glass & (light != NONE)).sum()),
@@ -805,11 +930,23 @@ def tally(sig):
                 media_with_events=sorted(int(i) for i in np.unique(v[:, :, C_MEDIUM][med])),
                 mover_vertices=int(on_mover.sum()), movers_hit=sorted(int(i) for i in np.unique(mover[on_mover])),
                 mover_then_static=int((on_mover & later(on_static)).any(axis=1).sum()),
-                static_then_mover=int((on_static & later(on_mover)).any(axis=1).sum()))
+                static_then_mover=int((on_static & later(on_mover)).any(axis=1).sum()),
+                image_vertices=int(image.sum()), image_vertices_with_light_sample=int((image & (light != NONE)).sum()),
+                image_samples=int(image.any(axis=1).sum()), image_mover_vertices=int((image & on_mover).sum()),
+                medium_then_image_surface=int((med & later(image)).any(axis=1).sum()),
+                unlisted_emitter_hits_after_light_sample=int(((light[:, :-1] != NONE) & (event[:, 1:] == EV_EMIT)
+                                                              & (how[:, 1:] == HIT_UNSAMPLED)).sum()),
+                triangle_vertices=int(on_tri.sum()),
+                triangle_vertices_with_light_sample=int((on_tri & (light != NONE)).sum()),
+                shadow_stopped_by_triangle=int(of(is_tri, blocker).sum()),
+                shadow_stopped_by_image_prim=int(of(is_image, blocker).sum()))
 
 
 MEDIA_KEYS = ("medium_events", "medium_then_surface", "medium_behind_glass", "media_with_events")
 MOTION_KEYS = ("mover_vertices", "movers_hit", "mover_then_static", "static_then_mover")
+EXT_KEYS = ("image_vertices", "image_vertices_with_light_sample", "image_samples", "triangle_vertices",
+            "triangle_vertices_with_light_sample", "shadow_stopped_by_triangle", "shadow_stopped_by_image_prim",
+            "unlisted_emitter_hits_after_light_sample", "medium_then_image_surface", "image_mover_vertices")
 
 
 def _mis_bsdf(pdf_b, pl, perturb=()):
@@ -839,7 +976,7 @@ def reference(S, words, shutter=None):
     fp64 run's special vertices"""
     rgb, sig64, draws = trace(S, words, shutter=shutter)
     _, sig32, _ = trace(S, words, dtype=np.float32, shutter=shutter)
-    return rgb, same_signature(sig64, sig32), draws, tally(sig64)
+    return rgb, same_signature(sig64, sig32), draws, tally(sig64, S)
 
 
 def judge(got, ref, stable):
