@@ -32,7 +32,15 @@
     const int ns = P.ns, nr = SPH ? 0 : P.nr, nc = SPH ? 0 : P.nc, nt = SPH ? 0 : P.nt;
     const float4 *tri = hot + P.off_tri_hot;
     // original list index of a grouped primitive id (the tie rule)
-    auto lidx = [&](int id) { return SPH ? __float_as_int(image[P.off_sph_cold + id].z) : list_index_of(P, image, id); };
+    // (the sphere's cold record at a 32-bit byte offset, as the winner's is read: fewer than 2^28 slots, lay_out_image)
+    auto lidx = [&](int id) { return SPH ? __float_as_int(rec_at(image + P.off_sph_cold, (uint32_t)id << 4)->z) : list_index_of(P, image, id); };
+    // The wave's votes on a lane flag that was merged across branches -- any(active), ballot(enters), ballot(far_scan),
+    // any(active || started) -- compile to v_cndmask 0 / 1 from the flag's lane mask and a v_cmp_ne back into one.  With
+    // VOTE_MASKS the questions are asked of lane masks in scalar registers instead: a ballot straight from the compare that
+    // decides the flag, combined with scalar and / and-not, and `inverse_ballot` where a lane-level `if` needs the flag.
+    // (Not in the moving-sphere kernels: their spilled vector registers rose from 109 to 114 with it.  The refill's start
+    // mask below is the same idea and holds for every family.)
+    constexpr bool VOTE_MASKS = !MOTION;
     // u = (x + xi) / (W - 1), main.cu:96-97, evaluated as a multiply by the fp32 reciprocal (as the checker does)
     // (the two reciprocals come with the launch parameters: computed here they were vector registers, spilled to scratch and
     //  fetched back with two dependent scratch loads in every refill)
@@ -69,8 +77,7 @@
     unsigned long long *c_acc = my_acc;  // accumulator of the current item (wave-uniform pointer)
     int c_x0 = 0, c_band = 0, c_sbegin = 0, c_pool = 0, cursor = 0;  // c_pool = 64 x samples of the item
     bool c_valid = false, queue_empty = false;
-    int c_hy = 0, c_hvalid = 0;  // this lane's home pixel in the current item (row, on-image)
-    unsigned long long c_hvmask = 0ull;  // ... and the on-image bits of all 64 home pixels (wave-uniform)
+    int c_hy = 0, c_hvalid = 0;  // this lane's home pixel in the current item (row, on-image; POOL: the row is -1 off-image)
     int mine = 0;                // !POOL: samples of the home pixel started so far (current item)
 
     // home pixel of this lane in the tile (x0, band): column, dense local row, image row, on-image
@@ -172,7 +179,9 @@
         asm volatile("" : "=v"(px), "=v"(py), "=v"(pz), "=v"(nx), "=v"(ny), "=v"(nz), "=v"(inv_len), "=v"(mat));
         bool front = false;
         float tex_r = 0, tex_g = 0, tex_b = 0;  // the texel of an image texture at the hit's (u, v)
-        if (__any(active)) {
+        // (VOTE_MASKS: no vote here.  Everything below sits behind `if (active)`, whose own branch on an empty exec mask skips
+        //  it when no lane is live; the vote in front of it was two vector instructions per iteration for the same answer.)
+        if (VOTE_MASKS || __any(active)) {
         {
             // ---- closest-hit query over the LDS-resident list (hittable_list::hit,
             // object.cuh:23-37).  Wave-uniform trip counts; `best_id` is the grouped id.
@@ -460,6 +469,7 @@
                 }
             };
             bool far_scan = false;  // GRID: this lane's origin lies beyond the reach of the cells' lists: it scans what they list
+            unsigned long long far_m = 0ull;  // VOTE_MASKS: ... and those lanes as a lane mask
             if (active) {
             if (GRID && P.grid_cells != 0) {  // (no cells: a scene small enough for every primitive to be tested per query)
                 // ---- uniform grid, 3-D DDA per lane (the default).  The clustered spheres -- and, in the wide tables, the
@@ -523,7 +533,21 @@
                 int ci = 0, k = 0, kend = 0;
                 uint32_t rem = 0;  // steps left before the ray leaves the grid: x | y << 8 | z << 16
                 float tmx = INFINITY, tmy = INFINITY, tmz = INFINITY, t_exit = 0.0f;
-                if (beyond) {
+                // (only the lanes in `live` read these, and entering the grid sets them: "undefined" values spare their v_mov
+                //  in both set-up paths.  k and kend stay 0: ballot(k < kend) below is asked of every lane.)
+                asm volatile("" : "=v"(tmx), "=v"(tmz), "=v"(t_exit), "=v"(ci), "=v"(rem));
+                // VOTE_MASKS: the lanes beyond the lists' reach as a mask, the scan's lanes inside a wave-uniform branch; every
+                // other lane evaluates the entry test (a lane beyond: for nothing), and the mask of who enters is the walk's `live`
+                unsigned long long m_beyond = 0ull, m_enters = 0ull;
+                if (VOTE_MASKS) {
+                    m_beyond = __builtin_amdgcn_ballot_w64(o2 > g_inv.w);
+                    if (m_beyond != 0ull) {
+                        const float4 fmn = {bx0, by0, bz0, 0.0f}, fmx = {bx1, by1, bz1, 0.0f};
+                        far_m = m_beyond & __builtin_amdgcn_ballot_w64(slab_live(bp, fmn, fmx));
+                        far_scan = __builtin_amdgcn_inverse_ballot_w64(far_m);
+                    }
+                }
+                if (!VOTE_MASKS && beyond) {
                     const float4 fmn = {bx0, by0, bz0, 0.0f}, fmx = {bx1, by1, bz1, 0.0f};
                     far_scan = slab_live(bp, fmn, fmx);
                 } else {
@@ -533,7 +557,12 @@
                     const float lz = (bz0 - oz) * bp.idz, uz = (bz1 - oz) * bp.idz;
                     const float tn = fmaxf(fmaxf(fmaxf(fminf(lx, ux), fminf(ly, uy)), t_from), fminf(lz, uz));
                     t_exit = fminf(fminf(fmaxf(lx, ux), fmaxf(ly, uy)), fmaxf(lz, uz));
-                    enters = !(tn > fminf(t_exit, blim));
+                    if (VOTE_MASKS) {
+                        m_enters = __builtin_amdgcn_ballot_w64(!(tn > fminf(t_exit, blim))) & ~m_beyond;
+                        enters = __builtin_amdgcn_inverse_ballot_w64(m_enters);
+                    } else {
+                        enters = !(tn > fminf(t_exit, blim));
+                    }
                     if (enters) {
                         // the cell of the entry point
                         const float px = fmaf(tn, dx, ox), py = fmaf(tn, dy, oy), pz = fmaf(tn, dz, oz);
@@ -560,12 +589,12 @@
                 if (COUNT && far_scan) c_query_maxpop++;
                 if (COUNT && t_res != 0.0f) c_walk_resumed++;
                 t_res = 0.0f;
-                // The lanes that are still walking, as a lane mask in scalar registers (like c_hvmask): the loops below ask "any lane?"
+                // The lanes that are still walking, as a lane mask in scalar registers: the loops below ask "any lane?"
                 // and "how many?" of it with scalar instructions, a lane that stops is cleared from it with one scalar and-not, and
                 // a lane-level `if` takes it as its exec mask.  (As a bool per lane, carried round the loops, it lived in a vector
                 // register as 0 / 1 and was compared back into a mask at the head of the walk, after every pass over the lists
                 // and before the tail's decision.)
-                unsigned long long live = __builtin_amdgcn_ballot_w64(enters);
+                unsigned long long live = VOTE_MASKS ? m_enters : __builtin_amdgcn_ballot_w64(enters);
                 // |size / d| per axis: what one step adds to the leave distance
                 float dtx = g_size.x * fabsf(bp.idx), dty = g_size.y * fabsf(bp.idy), dtz = g_size.z * fabsf(bp.idz);
                 int sx = dx > 0.0f ? 1 : -1, sy = dy > 0.0f ? gnx : -gnx, sz = SHEET ? (dz > 0.0f ? gnx : -gnx) : (dz > 0.0f ? gnx * gny : -(gnx * gny));
@@ -730,7 +759,7 @@
                 }
                 if (RT_PRIO_W != RT_PRIO_H) __builtin_amdgcn_s_setprio(RT_PRIO_H);
                 // far origins that can reach the grid at all: every clustered sphere (the flat scan)
-                if (__builtin_amdgcn_ballot_w64(far_scan) != 0ull) {
+                if (VOTE_MASKS ? far_m != 0ull : __builtin_amdgcn_ballot_w64(far_scan) != 0ull) {
                     const int end = P.np + (CSIZE + 1) * P.ncl;
                     for (int i = P.np; i < end; i += 4) {
                         const float4 s0 = sph[i], s1 = sph[i + 1], s2 = sph[i + 2], s3 = sph[i + 3];
@@ -923,7 +952,7 @@
             // (the reference's loop), the oversized ones in the grid kernels -- plus, for a lane whose origin lies beyond the reach
             // of the cells' lists (far_scan), the listed ones as well
             if (!SPH) {
-                const bool any_far = GRID && __builtin_amdgcn_ballot_w64(far_scan) != 0ull;
+                const bool any_far = GRID && (VOTE_MASKS ? far_m != 0ull : __builtin_amdgcn_ballot_w64(far_scan) != 0ull);
                 const int nr_loop = (GRID && !any_far) ? P.nr_a : nr, nc_loop = (GRID && !any_far) ? P.nc_a : nc;
                 const int nt_loop = EXT ? ((GRID && !any_far) ? P.nt_a : nt) : 0;
                 for (int j = 0; j < nr_loop; ++j)
@@ -1248,7 +1277,9 @@
                     if (fg) atomicAdd(g + 1, fg);
                     if (fb) atomicAdd(g + 2, fb);
                 } else {
-                    unsigned long long *a = c_acc + cur_p * 3;
+                    // (an LDS address and cur_p < 64: a 24-bit multiply-add on the low word, where `c_acc + cur_p * 3` was a
+                    //  quarter-rate v_mad_u64_u32)
+                    unsigned long long *a = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(c_acc) + __umul24((uint32_t)cur_p, 24u));
                     atomicAdd(a + 0, fr);
                     atomicAdd(a + 1, fg);
                     atomicAdd(a + 2, fb);
@@ -1262,6 +1293,9 @@
         // (render()'s sample loop, main.cu:95-101; camera::get_ray camera.h:32-39)
         float u = 0, v = 0;    // jitter of the sample a lane starts (main.cu:96-97)
         bool started = false;  // this lane starts a new path in this iteration
+        // ... and those lanes as a lane mask, from the compares that decide it (each a ballot of its own, combined as scalars),
+        // so that the vote below needs no round trip through a vector register
+        unsigned long long started_m = 0ull;
         const bool need = !active;
         const unsigned long long idle = __ballot(need);
         // is the current item handed out completely?
@@ -1334,7 +1368,8 @@
                     c_valid = true;
                     int hx_unused, hlr_unused;
                     home_pixel(c_x0, c_band, hx_unused, hlr_unused, c_hy, c_hvalid);
-                    c_hvmask = __builtin_amdgcn_ballot_w64(c_hvalid != 0);
+                    // (POOL: a pixel's row is read across lanes in the refill; an off-image pixel says so through it)
+                    if (POOL && c_hvalid == 0) c_hy = -1;
                 }
             }
             bool start = false;
@@ -1345,17 +1380,17 @@
                 const int k = cursor + rank;
                 if (c_valid) cursor = min(cursor + mask_count(idle), c_pool);
                 sp = k & 63;
-                // row and validity of pixel sp live in lane sp's registers (all lanes take part)
+                // row and validity of pixel sp live in lane sp's registers (all lanes take part): one cross-lane read, the row
+                // of an off-image pixel is -1.  (As a wave-uniform mask of on-image bits beside the row, the bit of pixel sp cost a
+                //  select between the mask's halves, a bit-field extract and a compare, and the mask two scalar registers.)
                 spy = __shfl(c_hy, sp, 64);
-                // (on-image bit of pixel sp from the item's lane mask: a select and a bit-field extract instead of a second
-                //  cross-lane read)
-                const uint32_t hv_word = (sp & 32) ? (uint32_t)(c_hvmask >> 32) : (uint32_t)c_hvmask;
-                const int pv = (int)((hv_word >> (sp & 31)) & 1u);
                 spx = c_x0 + (sp & 7);
                 ss = c_sbegin + (k >> 6);
-                start = need && c_valid && k < c_pool && pv != 0;
+                started_m = c_valid ? idle & __builtin_amdgcn_ballot_w64(k < c_pool) & __builtin_amdgcn_ballot_w64(spy >= 0) : 0ull;
+                start = __builtin_amdgcn_inverse_ballot_w64(started_m);
             } else {
-                start = need && c_valid && mine * 64 < c_pool && c_hvalid != 0;
+                started_m = c_valid ? idle & __builtin_amdgcn_ballot_w64(mine * 64 < c_pool) & __builtin_amdgcn_ballot_w64(c_hvalid != 0) : 0ull;
+                start = __builtin_amdgcn_inverse_ballot_w64(started_m);
                 sp = lane, spx = c_x0 + (lane & 7), spy = c_hy, ss = c_sbegin + mine;
                 if (start) mine++;
             }
@@ -1373,10 +1408,11 @@
                 v = ((float)spy + rng_next<COUNT>(rng)) * P.inv_hm1;
                 if (COUNT) c_samples++;
             }
-            started = start;
         }
+        started = __builtin_amdgcn_inverse_ballot_w64(started_m);
         tick(0);
-        if (!__any(active || started)) {
+        // (`active` has not changed since `idle` was taken: the live lanes are the others of this wave)
+        if (((__builtin_amdgcn_ballot_w64(true) & ~idle) | started_m) == 0ull) {
             // nothing in flight.  Out of work when the queue is dry, the current item is handed out and no sample
             // waits to be added; otherwise loop: the refill above makes progress every time (takes an item,
             // marks the queue empty, or skips off-image pool entries).
@@ -1397,6 +1433,7 @@
         const bool need_s = (kind >= 0 && kind <= MK_METAL) || (MEDIA && kind == MK_MEDIUM);
         const bool need_d = started && (P.flags & RT_FLAG_DEFOCUS_BLUR) != 0u;
         float sx = 0, sy = 0, sz = 0, sl2 = 1;
+        asm volatile("" : "=v"(sx), "=v"(sy), "=v"(sz), "=v"(sl2));  // (read by the lanes that ran the loop below, which sets all four)
         if (need_s || need_d) {
             if (RT_PRIO_R != RT_PRIO_F) __builtin_amdgcn_s_setprio(RT_PRIO_R);
             // The three draws of an attempt written out on the generator's four state words (xor128_next, philox.h): every
