@@ -613,7 +613,7 @@ int rt_abi_version(void);
 /* sizeof of the ABI structs as this library was compiled (binding self-checks):
  * 0 rt_opts, 1 rt_stats, 2 rt_prim, 3 rt_material, 4 rt_texture, 5 rt_camera, 6 rt_scene_info, 7 rt_table_info,
  * 8 rt_adaptive, 9 rt_adaptive_stats, 10 rt_nested_info, 16 rt_denoise, 17 rt_medium, 18 rt_moving_sphere, 19 rt_display,
- * 20 rt_display_stats; else 0 */
+ * 20 rt_display_stats, 21 rt_ray, 22 rt_hit; else 0 */
 size_t rt_struct_size(int which);
 /* number of usable gfx950 devices, or -rt_status */
 int rt_device_count(void);
@@ -699,6 +699,56 @@ int rt_render_hip_feature(const rt_scene *s, const rt_opts *o, int feature, floa
 /* the same into a DEVICE buffer on `stream` (hipStream_t as void*), asynchronous when stats == NULL (rt_render_hip_device) */
 int rt_render_hip_feature_device(const rt_scene *s, const rt_opts *o, int feature, void *d_sum, void *stream,
                                  rt_stats *stats);
+
+/* ---- ray queries: closest hit and occlusion for caller-supplied rays ---------------------------------
+ *
+ * A ray query is exactly the renderer's closest-hit query: hittable_list::hit over the scene's STATIC primitives in list
+ * order, over the range [0.001, t_max]; a hit with t <= the closest so far is accepted, so at equal t the later list entry
+ * wins.  dir is not normalised and t is in units of dir; t_max = +inf is allowed, a negative t_max is valid and misses.
+ * The walk is the render kernels' own (one 3-D DDA over the scene's tables, bit-identical to the linear scan in every
+ * layout), and the record carries what their winner section computes:
+ *   hit      t, point (p = o + t d as the kernels evaluate it, fp32; a cylinder's through its object space), the hit record's
+ *            normal turned against the ray, front (1: the ray met the outward side), the material index, prim (the index into
+ *            rt_scene_get_prims) and the hit record's (u, v), evaluated for EVERY hit here by the fixed atan2 / acos sequences
+ *            the image textures are read with (the render kernels evaluate them for image textures only)
+ *   miss     t = +inf, prim = -1, every other word 0
+ *   invalid  prim = RT_HIT_INVALID, t = +inf, every other word 0.  A ray is invalid if a component of origin or dir is not
+ *            finite, t_max is NaN, or dir.dir evaluated in fp32 (fma(dx, dx, fma(dy, dy, dz dz))) is zero, denormal or not
+ *            finite.  Such a ray never enters the walk.  rt_ray_valid is the host evaluation of the kernel's guard.
+ * RT_TRACE_OCCLUDED writes one uint8_t per ray instead: 1 iff RT_TRACE_CLOSEST would report a hit for the same ray, else 0
+ * (an invalid ray: 0).  out[i] belongs to ray i; its bytes do not depend on n, on the batch the ray arrives in, on the
+ * layout or on the schedule.  `reserved` is ignored.
+ * What a query sees: the static primitives.  Media and an environment map are not surfaces and are ignored (as feature
+ * passes ignore media); light sampling, Russian roulette, max_depth, the frame size and the camera play no part.  A scene
+ * with moving spheres is refused with RT_ERR_ARG (a query has no shutter time: clear the movers, rt_scene_clear_moving_spheres).
+ * rt_opts: `device` and `variant` are read, every other field is ignored.  variant names the LAYOUT as for
+ * rt_render_hip_feature: 0, 16, 24, 36, 44 or 52; a scene with compact tables runs the linear scan, in LDS while it fits and
+ * from global memory beyond; any other variant is RT_ERR_ARG.  rt_stats reports kernel_ms, upload_ms and launches, and
+ * kernel_variant the layout | 8192.
+ * Errors, all checked before any device access: null scene, a mode outside 0..1, a variant outside the list, moving
+ * spheres: RT_ERR_ARG; n >= 2^31: RT_ERR_LIMIT; n == 0 returns RT_OK without touching a device; null rays or null out with
+ * n > 0: RT_ERR_ARG. */
+typedef struct rt_ray { float origin[3]; float t_max; float dir[3]; float reserved; } rt_ray;   /* 32 bytes: two 16-byte records */
+typedef struct rt_hit {                     /* 48 bytes: three 16-byte records */
+    float t; int32_t prim; int32_t material; int32_t front;
+    float normal[3]; float u;
+    float point[3];  float v;
+} rt_hit;
+#define RT_HIT_INVALID (-2)
+typedef enum rt_trace_mode { RT_TRACE_CLOSEST = 0, RT_TRACE_OCCLUDED = 1 } rt_trace_mode;
+/* rays per work item of the query kernels: scheduling only, it bears on no record (exposed for the tests' batch sizes) */
+#define RT_TRACE_ITEM 64
+/* rays (host, n records) -> out (host: n rt_hit, or n bytes in occlusion mode); stats may be NULL */
+int rt_trace_hip(const rt_scene *s, const rt_opts *o, int mode, const rt_ray *rays, size_t n, void *out, rt_stats *stats);
+/* the same on DEVICE buffers (16-byte aligned) on `stream` (hipStream_t as void*), asynchronous when stats == NULL
+ * (rt_render_hip_device); the scene's tables are uploaded and cached per device as for a render.  Queries and renders of ONE
+ * scene object on one device must share a stream, or be serialised by the caller (they share its tables and work counter);
+ * different scene objects, or clones, are independent */
+int rt_trace_hip_device(const rt_scene *s, const rt_opts *o, int mode, const void *d_rays, size_t n, void *d_out, void *stream, rt_stats *stats);
+/* 1: the ray may enter the walk; 0: it is invalid (or r is NULL).  No GPU needed. */
+int rt_ray_valid(const rt_ray *r);
+
+/* ---- the denoiser (guided by the first-hit feature buffers above) ------------ */
 
 /* Edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) on the demodulated image (mean colour / first-hit albedo),
  * guided by the three feature sums.  The definition -- prepare, weights, order of the taps, pixels without coverage -- is

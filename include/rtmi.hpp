@@ -277,6 +277,19 @@ public:
     }
     void override_size(int w, int h, int spp, int depth) { check(rt_scene_override(s_, w, h, spp, depth), "override"); }
 
+    // ray queries (rt_trace_hip): the renderer's closest-hit query for caller-supplied rays, one record per ray (prim -1: a
+    // miss, RT_HIT_INVALID: the ray failed rt_ray_valid); occluded(): 1 where the closest-hit query would report a hit
+    std::vector<rt_hit> trace(const std::vector<rt_ray> &rays, const rt_opts *opts = nullptr) const {
+        std::vector<rt_hit> out(rays.size());
+        check(rt_trace_hip(s_, opts, RT_TRACE_CLOSEST, rays.data(), rays.size(), out.data(), nullptr), "trace");
+        return out;
+    }
+    std::vector<uint8_t> occluded(const std::vector<rt_ray> &rays, const rt_opts *opts = nullptr) const {
+        std::vector<uint8_t> out(rays.size());
+        check(rt_trace_hip(s_, opts, RT_TRACE_OCCLUDED, rays.data(), rays.size(), out.data(), nullptr), "occluded");
+        return out;
+    }
+
     rt_scene_info info() const {
         rt_scene_info i;
         check(rt_scene_get_info(s_, &i), "info");

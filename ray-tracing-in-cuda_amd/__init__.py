@@ -59,6 +59,14 @@ MAX_MOVING_SPHERES = 64
 MOVING_SPHERE_DTYPE = np.dtype(  # rt_moving_sphere: the centre at shutter time 0 and at 1
     [("center0", "<f4", (3,)), ("center1", "<f4", (3,)), ("radius", "<f4"), ("material", "<i4")]
 )
+# ray queries (rt_trace_hip): rt_ray is two 16-byte records, rt_hit three
+RAY_DTYPE = np.dtype([("origin", "<f4", (3,)), ("t_max", "<f4"), ("dir", "<f4", (3,)), ("reserved", "<f4")])
+HIT_DTYPE = np.dtype([("t", "<f4"), ("prim", "<i4"), ("material", "<i4"), ("front", "<i4"), ("normal", "<f4", (3,)), ("u", "<f4"),
+                      ("point", "<f4", (3,)), ("v", "<f4")])
+HIT_INVALID = -2     # rt_hit.prim of a ray that failed the guard (RT_HIT_INVALID)
+TRACE_CLOSEST, TRACE_OCCLUDED = 0, 1
+TRACE_ITEM = 64      # rays per work item of the query kernels (RT_TRACE_ITEM): scheduling only
+TRACE_LAYOUT = 8192  # Stats.kernel_variant of a ray query: the layout | 8192
 LIGHT_DTYPE = np.dtype(
     [("prim", "<i4"), ("shape", "<i4"), ("probability", "<f4"), ("area", "<f4"), ("emission", "<f4", (3,)),
      ("emission_odd", "<f4", (3,))]
@@ -292,6 +300,10 @@ _sig("rt_aabb_hit", C.c_int, _f3, _f3, _f3, _f3, C.c_float, C.c_float)
 _sig("rt_sample_stream", None, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_int)
 _sig("rt_render_hip_feature", C.c_int, _p, C.POINTER(Opts), C.c_int, _p, C.POINTER(Stats))
 _sig("rt_render_hip_feature_device", C.c_int, _p, C.POINTER(Opts), C.c_int, _p, _p, C.POINTER(Stats))
+_sig("rt_trace_hip", C.c_int, _p, C.POINTER(Opts), C.c_int, _p, C.c_size_t, _p, C.POINTER(Stats))
+_sig("rt_trace_hip_device", C.c_int, _p, C.POINTER(Opts), C.c_int, _p, C.c_size_t, _p, _p, C.POINTER(Stats))
+_sig("rt_ray_valid", C.c_int, _p)
+assert _lib.rt_struct_size(21) == RAY_DTYPE.itemsize == 32 and _lib.rt_struct_size(22) == HIT_DTYPE.itemsize == 48
 _sig("rt_denoise_hip", C.c_int, C.c_int, C.c_int, _p, C.c_int, _p, _p, _p, _p, C.c_int, C.POINTER(Denoise), C.c_int, _p,
      C.POINTER(C.c_double))
 _sig("rt_denoise_hip_device", C.c_int, C.c_int, C.c_int, _p, C.c_int, _p, _p, _p, _p, C.c_int, C.POINTER(Denoise), C.c_int, _p, _p,
@@ -328,6 +340,7 @@ C_SYMBOLS = [
     "rt_scene_add_medium_sphere", "rt_scene_add_medium_box", "rt_scene_get_media", "rt_scene_clear_media", "rt_medium_interval",
     "rt_scene_add_moving_sphere", "rt_scene_moving_sphere_count", "rt_scene_get_moving_spheres", "rt_scene_clear_moving_spheres",
     "rt_moving_sphere_hit", "rt_shutter_time",
+    "rt_trace_hip", "rt_trace_hip_device", "rt_ray_valid",
     "rt_render_hip_feature", "rt_render_hip_feature_device", "rt_denoise_hip", "rt_denoise_hip_device",
     "rt_display_hip", "rt_display_hip_device", "rt_display_timing", "rt_write_hdr", "rt_write_pfm",
     "rt_write_ppm_rgb8", "rt_write_png_rgb8",
@@ -691,6 +704,31 @@ class Scene:
                "rt_render_hip_feature")
         return out
 
+    # ---- ray queries (HIP only) ---------------------------------------------------
+    def trace(self, origins, directions, t_max=float("inf"), occluded: bool = False, opts: Opts | None = None,
+              stats: Stats | None = None) -> np.ndarray:
+        """Closest hit (rt_trace_hip) of n caller-supplied rays against the scene's static primitives: exactly the renderer's
+        closest-hit query over [0.001, t_max], directions not normalised, t in units of the direction.  origins, directions:
+        (n, 3); t_max: a scalar or (n,).  Returns n HIT_DTYPE records (prim -1: a miss, HIT_INVALID: the ray failed ray_valid),
+        or with occluded=True n bools: would the closest-hit query report a hit.  opts: device and variant (a layout) are read."""
+        rays = pack_rays(origins, directions, t_max)
+        n = len(rays)
+        out = np.zeros(n, dtype=np.uint8) if occluded else np.zeros(n, dtype=HIT_DTYPE)
+        opts = opts or Opts()
+        _check(_lib.rt_trace_hip(self._h, C.byref(opts), TRACE_OCCLUDED if occluded else TRACE_CLOSEST, rays.ctypes.data_as(C.c_void_p),
+                                 n, out.ctypes.data_as(C.c_void_p), C.byref(stats) if stats is not None else None), "rt_trace_hip")
+        return out.astype(bool) if occluded else out
+
+    def trace_device(self, d_rays: int, n: int, d_out: int, occluded: bool = False, stream: int = 0, opts: Opts | None = None,
+                     stats: Stats | None = None):
+        """The same on raw device pointers (rt_trace_hip_device): d_rays n x 32 bytes (RAY_DTYPE; a torch float32 tensor of shape
+        (n, 8) passes data_ptr()), d_out n x 48 bytes (HIT_DTYPE; (n, 12) float32) or n bytes with occluded=True, stream e.g.
+        torch.cuda.current_stream().cuda_stream.  Asynchronous when stats is None."""
+        opts = opts or Opts()
+        _check(_lib.rt_trace_hip_device(self._h, C.byref(opts), TRACE_OCCLUDED if occluded else TRACE_CLOSEST, C.c_void_p(d_rays), int(n),
+                                        C.c_void_p(d_out), C.c_void_p(stream), C.byref(stats) if stats is not None else None),
+               "rt_trace_hip_device")
+
     def render_tiles(self, devices=None, opts: Opts | None = None, stats: Stats | None = None, n: int | None = None,
                      out: np.ndarray | None = None):
         """One frame over several GPUs of this node: row tiles dealt out to `devices` (ordinals; None =
@@ -946,6 +984,27 @@ def moving_sphere_hit(mover, s, orig, direction, t_max=float("inf")):
     rc = _check_id(_lib.rt_moving_sphere_hit(rec.ctypes.data_as(C.c_void_p), float(s), _v3(orig), _v3(direction), float(t_max), C.byref(t)),
                    "moving_sphere_hit")
     return bool(rc), t.value
+
+
+def pack_rays(origins, directions, t_max=float("inf")) -> np.ndarray:
+    """(n, 3) origins and directions and a scalar or (n,) t_max as n RAY_DTYPE records"""
+    o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
+    d = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
+    if len(o) != len(d):
+        raise ValueError("trace: %d origins for %d directions" % (len(o), len(d)))
+    rays = np.zeros(len(o), dtype=RAY_DTYPE)
+    rays["origin"], rays["dir"] = o, d
+    rays["t_max"] = np.broadcast_to(np.asarray(t_max, dtype=np.float32), (len(o),))
+    return rays
+
+
+def ray_valid(ray) -> bool:
+    """May this ray enter the walk (rt_ray_valid, the host evaluation of the kernel's guard)?  ray: one RAY_DTYPE record, or
+    (origin, direction) or (origin, direction, t_max)."""
+    if not (isinstance(ray, (np.ndarray, np.void)) and ray.dtype == RAY_DTYPE):
+        ray = pack_rays([ray[0]], [ray[1]], ray[2] if len(ray) > 2 else float("inf"))
+    rec = np.ascontiguousarray(np.asarray(ray, dtype=RAY_DTYPE).reshape(-1)[:1])
+    return bool(_lib.rt_ray_valid(rec.ctypes.data_as(C.c_void_p)))
 
 
 def shutter_time(seed, pixel, sample) -> float:

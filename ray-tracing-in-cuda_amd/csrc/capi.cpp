@@ -14,6 +14,7 @@
 #include "rt_env.h"
 #include "rt_media.h"
 #include "rt_motion.h"
+#include "rt_trace.h"
 #include "scene.hpp"
 
 using namespace rtmi;
@@ -60,6 +61,8 @@ size_t rt_struct_size(int which) {
     case 18: return sizeof(rt_moving_sphere);
     case 19: return sizeof(rt_display);
     case 20: return sizeof(rt_display_stats);
+    case 21: return sizeof(rt_ray);
+    case 22: return sizeof(rt_hit);
     default: return 0;
     }
 }
@@ -948,6 +951,13 @@ int rt_moving_sphere_hit(const rt_moving_sphere *m, float s, const float orig[3]
                                        dir[1], dir[2], A, inv_a, t_max, root);
     if (hit && t) *t = root;
     return hit ? 1 : 0;
+}
+
+// ---- ray queries: the host evaluation of the kernel's guard (rt_trace.h)
+static_assert(sizeof(rt_ray) == 32 && sizeof(rt_hit) == 48, "two and three 16-byte records");
+int rt_ray_valid(const rt_ray *r) {
+    if (!r) return 0;
+    return ray_valid(r->origin[0], r->origin[1], r->origin[2], r->t_max, r->dir[0], r->dir[1], r->dir[2]) ? 1 : 0;
 }
 
 float rt_shutter_time(uint64_t seed, uint32_t pixel, uint32_t sample) {

@@ -20,6 +20,9 @@
 // [KEY], --white W, --bloom STRENGTH [--bloom-threshold T] [--bloom-levels L].  With any of them the PPM and the PNG are
 // written from the stage's 8-bit output; without, the program writes what it always wrote.  --hdr-out FILE.hdr|FILE.pfm
 // writes the mean image before the display stage (and after --denoise) as a float image (rt_write_hdr / rt_write_pfm).
+// Ray queries (rt_trace_hip): --pick X,Y (X from the left, Y from the top) traces the ray through that pixel's
+// centre and prints what it meets as one JSON line on stdout; no frame is rendered.  --focus-at X,Y traces the same ray and
+// focuses the camera on what it meets (focus_dist = t |dir|, rt_scene_set_camera) before the render.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -55,7 +58,8 @@ static int usage(const char *argv0) {
             "          [--gpus N] [--tile-rows R] [--adaptive THRESHOLD [--min-spp N] [--max-spp N]]\n"
             "          [--denoise] [--aov PREFIX] [--feature-spp N]\n"
             "          [--tonemap clamp|reinhard|aces] [--exposure EV] [--auto-exposure [KEY]] [--white W]\n"
-            "          [--bloom STRENGTH] [--bloom-threshold T] [--bloom-levels L] [--hdr-out frame.hdr|frame.pfm]\n",
+            "          [--bloom STRENGTH] [--bloom-threshold T] [--bloom-levels L] [--hdr-out frame.hdr|frame.pfm]\n"
+            "          [--pick X,Y] [--focus-at X,Y]\n",
             argv0);
     return 2;
 }
@@ -72,6 +76,45 @@ static bool number(const char *v, double lo, double hi, double *out) {
 static bool ends_with(const std::string &s, const char *tail) {
     const size_t n = strlen(tail);
     return s.size() > n && s.compare(s.size() - n, n, tail) == 0;
+}
+
+// "X,Y": two whole numbers >= 0
+static bool pixel_pair(const char *v, int *x, int *y) {
+    char *end = nullptr;
+    const long a = strtol(v, &end, 10);
+    if (end == v || *end != ',' || a < 0 || a > 1000000) return false;
+    const char *w = end + 1;
+    const long b = strtol(w, &end, 10);
+    if (end == w || *end != '\0' || b < 0 || b > 1000000) return false;
+    *x = (int)a, *y = (int)b;
+    return true;
+}
+
+// The ray through the centre of pixel (x from the left, y from the top) and what it meets: the camera's derived frame as the
+// kernels use it -- u = (x + 0.5) / (W - 1), v likewise from the bottom row, one fma per term -- and no lens offset.
+static int trace_pixel(const rt_scene *sc, int device, int x, int y, rt_ray *ray, rt_hit *hit) {
+    rt_scene_info info;
+    rt_camera cam;
+    if (rt_scene_get_info(sc, &info) != RT_OK || rt_scene_get_camera(sc, &cam) != RT_OK) return RT_ERR_ARG;
+    if (x >= info.width || y >= info.height) {
+        fprintf(stderr, "rtmi: pixel %d,%d lies outside the %d x %d frame\n", x, y, info.width, info.height);
+        return RT_ERR_ARG;
+    }
+    const float u = ((float)x + 0.5f) * (1.0f / (float)(info.width - 1));
+    const float v = ((float)(info.height - 1 - y) + 0.5f) * (1.0f / (float)(info.height - 1));
+    memset(ray, 0, sizeof *ray);
+    for (int a = 0; a < 3; ++a) {
+        ray->origin[a] = cam.origin[a];
+        ray->dir[a] = fmaf(v, cam.vertical[a], fmaf(u, cam.horizontal[a], cam.lower_left[a])) - cam.origin[a];
+    }
+    ray->t_max = INFINITY;
+    rt_opts o;
+    rt_opts_default(&o);
+    o.device = device;
+    const int rc = rt_trace_hip(sc, &o, RT_TRACE_CLOSEST, ray, 1, hit, nullptr);
+    if (rc != RT_OK) fprintf(stderr, "rtmi: %s\n", rt_last_error());
+    else if (hit->prim == RT_HIT_INVALID) fprintf(stderr, "rtmi: the camera's ray through pixel %d,%d is not a valid ray\n", x, y);
+    return rc != RT_OK ? rc : hit->prim == RT_HIT_INVALID ? RT_ERR_ARG : RT_OK;
 }
 
 int main(int argc, char **argv) {
@@ -98,6 +141,8 @@ int main(int argc, char **argv) {
     memset(&dp, 0, sizeof dp);
     std::string hdr_out;        // the mean image before the display stage, .hdr or .pfm
     int w = 0, h = 0, depth = 0, spp = 0, device = 0, chunk = 0, gpus = 0, tile_rows = 0;
+    bool pick = false, focus_at = false;  // ray queries through a pixel's centre
+    int pick_x = 0, pick_y = 0, focus_x = 0, focus_y = 0;
     unsigned long long seed = 2023;
     unsigned scene_seed = 7;  // srand(7), main.cpp:119
     for (int i = 1; i < argc; ++i) {
@@ -216,6 +261,15 @@ int main(int argc, char **argv) {
                 return 2;
             }
         }
+        else if (!strcmp(argv[i], "--pick") || !strcmp(argv[i], "--focus-at")) {
+            const char *flag = argv[i], *v = need(flag);
+            const bool p = !strcmp(flag, "--pick");
+            if (!pixel_pair(v, p ? &pick_x : &focus_x, p ? &pick_y : &focus_y)) {
+                fprintf(stderr, "rtmi: %s needs a pixel X,Y (X from the left, Y from the top), got '%s'\n", flag, v);
+                return 2;
+            }
+            (p ? pick : focus_at) = true;
+        }
         else if (!strcmp(argv[i], "--rtiow")) rtiow = true;
         else if (!strcmp(argv[i], "--count")) count = true;
         else if (!strcmp(argv[i], "--no-png")) no_png = true;
@@ -280,6 +334,24 @@ int main(int argc, char **argv) {
         fprintf(stderr, "rtmi: %s\n", rt_last_error());
         return 1;
     }
+    if (focus_at) {
+        rt_ray ray;
+        rt_hit hit;
+        if (trace_pixel(sc, device, focus_x, focus_y, &ray, &hit) != RT_OK) return 1;
+        if (hit.prim < 0) {
+            fprintf(stderr, "rtmi: --focus-at %d,%d: the ray through that pixel meets nothing to focus on\n", focus_x, focus_y);
+            return 1;
+        }
+        rt_camera cam;
+        rt_scene_get_camera(sc, &cam);
+        const float len = sqrtf(fmaf(ray.dir[0], ray.dir[0], fmaf(ray.dir[1], ray.dir[1], ray.dir[2] * ray.dir[2])));
+        const float focus = hit.t * len;
+        if (rt_scene_set_camera(sc, cam.lookfrom, cam.lookat, cam.vup, cam.vfov, cam.aspect, cam.aperture, focus) != RT_OK) {
+            fprintf(stderr, "rtmi: %s\n", rt_last_error());
+            return 1;
+        }
+        fprintf(stderr, "focus: pixel %d,%d meets primitive %d at distance %.9g\n", focus_x, focus_y, hit.prim, (double)focus);
+    }
     rt_scene_info info;
     rt_scene_get_info(sc, &info);
     fprintf(stderr, "scene: %dx%d, %d spp, depth %d, %d objects, %d materials, %d textures\n", info.width,
@@ -296,6 +368,29 @@ int main(int argc, char **argv) {
         }
         fwrite(buf.data(), 1, n - 1, fp);
         fclose(fp);
+    }
+    if (pick) {
+        rt_ray ray;
+        rt_hit hit;
+        if (trace_pixel(sc, device, pick_x, pick_y, &ray, &hit) != RT_OK) return 1;
+        if (hit.prim < 0) {
+            printf("{\"prim\": -1}\n");
+        } else {
+            std::vector<rt_prim> prims((size_t)info.num_prims);
+            rt_scene_get_prims(sc, prims.data(), info.num_prims);
+            static const char *const types[] = {"sphere", "xy_rect", "xz_rect", "yz_rect", "cylinder", "triangle"};
+            const int ty = prims[(size_t)hit.prim].type;
+            const float len = sqrtf(fmaf(ray.dir[0], ray.dir[0], fmaf(ray.dir[1], ray.dir[1], ray.dir[2] * ray.dir[2])));
+            // (%.9g: every fp32 value reads back as itself)
+            printf("{\"prim\": %d, \"type\": \"%s\", \"material\": %d, \"t\": %.9g, \"distance\": %.9g, \"point\": [%.9g, %.9g, %.9g], "
+                   "\"normal\": [%.9g, %.9g, %.9g], \"front\": %d, \"uv\": [%.9g, %.9g], \"origin\": [%.9g, %.9g, %.9g], \"dir\": [%.9g, %.9g, %.9g]}\n",
+                   hit.prim, ty >= 0 && ty < 6 ? types[ty] : "?", hit.material, (double)hit.t, (double)(hit.t * len), (double)hit.point[0],
+                   (double)hit.point[1], (double)hit.point[2], (double)hit.normal[0], (double)hit.normal[1], (double)hit.normal[2], hit.front,
+                   (double)hit.u, (double)hit.v, (double)ray.origin[0], (double)ray.origin[1], (double)ray.origin[2], (double)ray.dir[0],
+                   (double)ray.dir[1], (double)ray.dir[2]);
+        }
+        rt_scene_free(sc);
+        return 0;
     }
     rt_opts o;
     rt_opts_default(&o);

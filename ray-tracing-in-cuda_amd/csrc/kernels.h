@@ -1,6 +1,6 @@
 // The render kernels as the host sees them: one row per built instance, named by what render_host.hip knows when it has
-// to pick one.  Each of the four kernel translation units (render_kernel.hip, render_env.hip, render_media.hip,
-// render_motion.hip) lists its instances in a static array of rows -- taking a kernel's address in a row is what
+// to pick one.  Each of the kernel translation units (render_kernel.hip, render_env.hip, render_media.hip,
+// render_motion.hip, and trace.hip for the ray queries) lists its instances in a static array of rows -- taking a kernel's address in a row is what
 // instantiates it -- and the host resolves a launch ONCE, to a row, and launches, sizes the grid and raises the LDS limit
 // through the row's function pointer.  A new family is a kernel definition and its rows.
 #pragma once
@@ -19,6 +19,7 @@ enum KernelFamily {
     K_ENV,      // render_env_kernel: an environment map (plain, with light sampling, or a feature pass)
     K_MEDIA,    // render_media_kernel
     K_MOTION,   // render_motion_kernel
+    K_TRACE,    // trace_kernel: ray queries (rt_trace_hip); not a render kernel, launched through launch_trace
 };
 
 struct KernelKey {
@@ -42,6 +43,7 @@ const KernelRow *render_kernel_rows(size_t *n);  // render_kernel.hip: K_PLAIN, 
 const KernelRow *env_kernel_rows(size_t *n);     // render_env.hip
 const KernelRow *media_kernel_rows(size_t *n);   // render_media.hip
 const KernelRow *motion_kernel_rows(size_t *n);  // render_motion.hip
+const KernelRow *trace_kernel_rows(size_t *n);   // trace.hip
 
 // render_kernel.hip
 const KernelRow *find_kernel(const KernelKey &key);  // null: no such build
@@ -52,5 +54,9 @@ int set_max_dynamic_lds(const KernelRow &row, size_t bytes);
 bool has_ablations();
 void launch_finalize(const unsigned long long *acc, float *out, size_t n, hipStream_t stream);
 void launch_item_params(unsigned int *queue, const ItemParams &ip, hipStream_t stream);
+
+// trace.hip: n rays (two 16-byte records each) -> out (three 16-byte records per ray, or one byte per ray in occlusion mode)
+void launch_trace(const KernelRow &row, const RenderParams &P, const void *image, const void *rays, void *out, unsigned int *queue,
+                  unsigned int n, int mode, size_t lds_bytes, unsigned grid, hipStream_t stream);
 
 }  // namespace rtmi

@@ -1,6 +1,7 @@
 // The body of the render kernels: included INSIDE render_kernel, render_nee_kernel, render_nested_kernel and render_feature_kernel
 // (render_kernel.hip), render_env_kernel (render_env.hip), render_media_kernel (render_media.hip) and render_motion_kernel
-// (render_motion.hip), after their template arguments and a constexpr NEE, AOV, ENV, MEDIA and MOTION.  The device functions it
+// (render_motion.hip), after their template arguments and a constexpr NEE, AOV, ENV, MEDIA, MOTION and QUERY (with the TraceArgs
+// TQ of render_device.h: null there), and inside trace_kernel (trace.hip), where QUERY is set.  The device functions it
 // calls are render_device.h's, which each of those files includes.  As text rather than a force-inlined device function, so that the render_kernel
 // instances compile to the very instructions they did before light sampling came (a device function that takes the
 // kernel's parameters by reference changes the order of the kernel-argument loads and with it the register allocation).
@@ -12,6 +13,7 @@
     constexpr int CSIZE = RT_CLUSTER;
     static_assert(!(CULL == 5 || CULL == 6) || SPH, "the compact grid tables list spheres only");
     static_assert(!(SPH && EXT), "image textures and triangles come with the general builds");
+    static_assert(!QUERY || (EXT && POOL && !COUNT && !NEE && !AOV && !ENV && !MEDIA && !MOTION), "a ray query is the general build's walk and winner, nothing else");
     // stage the hot tables (hittable_list contents) into LDS: each candidate search stages the part it reads
     // (the cluster searches leave the grid tables, which lie in front of their boxes, out: `gap` records)
     const int gap = (SCALAR || GRID) ? 0 : P.off_box - P.off_grid;
@@ -19,7 +21,9 @@
     for (int i = threadIdx.x; i < staged; i += 256) lds[i] = image[i < P.off_grid ? i : i + gap];
     // per-wave tile accumulator of the current work item: 64 pixels x rgb, 64-bit fixed point
     unsigned long long *tile_acc = reinterpret_cast<unsigned long long *>(lds + staged);
-    for (int i = threadIdx.x; i < 4 * 64 * 3; i += 256) tile_acc[i] = 0ull;
+    // (QUERY: a ray's record goes straight to memory: no accumulators, and no LDS reserved for them)
+    if constexpr (!QUERY)
+        for (int i = threadIdx.x; i < 4 * 64 * 3; i += 256) tile_acc[i] = 0ull;
     __syncthreads();
 
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;  // (wave: in a scalar register)
@@ -165,6 +169,21 @@
     // CULL == 5: ray parameter at which this lane's grid walk was cut short in the previous iteration (0: it was not);
     // the walk goes on from there in this one
     float t_res = 0.0f;
+    // QUERY: the ray this lane traces, and its t_max: the best_t its query starts from -- and starts from again when its walk was
+    // cut short.  A record is three 16-byte stores (rt_hit), or one byte in occlusion mode.
+    uint32_t q_ray = 0u;
+    float q_tmax = INFINITY;
+    auto put_record = [&](uint32_t ray, float t, int prim, int material, int is_front, float rnx, float rny, float rnz, float ru,
+                          float rpx, float rpy, float rpz, float rv) {
+        if (TQ.mode != 0) {
+            reinterpret_cast<uint8_t *>(TQ.out)[ray] = prim >= 0 ? (uint8_t)1 : (uint8_t)0;
+        } else {
+            float4 *rec = TQ.out + (size_t)ray * 3;
+            rec[0] = make_float4(t, __int_as_float(prim), __int_as_float(material), __int_as_float(is_front));
+            rec[1] = make_float4(rnx, rny, rnz, ru);
+            rec[2] = make_float4(rpx, rpy, rpz, rv);
+        }
+    };
     for (;;) {
         tick(5);
         bool path_done = false;
@@ -187,7 +206,8 @@
             // object.cuh:23-37).  Wave-uniform trip counts; `best_id` is the grouped id.
             // (a shadow ray ends just short of its light point y = o + d: any hit before that occludes)
             // (ENV: the shadow ray towards the environment -- shadow bit 2 -- has no far end)
-            float best_t = (NEE && shadow != 0 && !(ENV && (shadow & 4) != 0)) ? 0.999f : INFINITY;
+            // (QUERY: the ray's own far end)
+            float best_t = QUERY ? q_tmax : (NEE && shadow != 0 && !(ENV && (shadow & 4) != 0)) ? 0.999f : INFINITY;
             int best_id = -1;
 
             // spheres: sphere::hit, object.cuh:47-75.  Early-outs that need no sqrt:
@@ -1124,7 +1144,8 @@
                 // the hit record's (u, v) -- only where the material's texture reads them (an image texture); every
                 // other texture of the reference ignores them, and acos / atan2 per candidate hit (object.cuh:87-93)
                 // would be the most expensive part of sphere::hit
-                if (EXT && (kind == MK_LAMBERT_IMAGE || kind == MK_LIGHT_IMAGE)) {
+                // (QUERY: for every hit, they are part of the record)
+                if (EXT && (QUERY || kind == MK_LAMBERT_IMAGE || kind == MK_LIGHT_IMAGE)) {
                     float tu, tv;
                     if ((MOTION && mot_i >= 0) || best_id < ns) {  // get_sphere_uv(outward_normal), object.cuh:87-93
                         const float onx = front ? nx : -nx, ony = front ? ny : -ny, onz = front ? nz : -nz;
@@ -1174,6 +1195,12 @@
                         tu = fmaf(c1.z, w3, fmaf(c1.x, w2, c0.z * w1));
                         tv = fmaf(c1.w, w3, fmaf(c1.y, w2, c0.w * w1));
                     }
+                    if constexpr (QUERY) {
+                        // the query's answer: the record as it stands here, the primitive by its index in the scene's list
+                        put_record(q_ray, best_t, list_index_of(P, image, best_id), mat, front ? 1 : 0, nx, ny, nz, tu, px, py, pz, tv);
+                        active = false;
+                        kind = -1;
+                    } else
                     image_texel(image, M[1], tu, tv, tex_r, tex_g, tex_b);
                 }
                 if (COUNT) {
@@ -1183,6 +1210,8 @@
                     else if (kind == MK_DIELECTRIC) c_scatter2++;
                     else c_scatter3++;
                 }
+                if constexpr (QUERY) {
+                } else
                 if constexpr (AOV) {
                     // first-hit feature (render_feature_kernel): the path ends here and adds one triple in place of radiance --
                     // the texture value under the hit (metal: its albedo, dielectric: white), the face-turned normal, or (t, 1, 0)
@@ -1231,6 +1260,9 @@
                     path_done = true;  // absorbed: main.cu:55-58
                     kind = -1;
                 }
+            } else if (QUERY) {
+                put_record(q_ray, INFINITY, -1, 0, 0, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f);
+                active = false;
             } else {
                 // miss: main.cpp:36-38 (sky) or main.cu:63 (constant background)
                 float bg_r, bg_g, bg_b;
@@ -1268,7 +1300,7 @@
         }
         tick(3);
         // ---- (3) res += ray_color(...), main.cu:100 -- exact fixed-point add into the tile
-        if (path_done || (NEE && nee_add)) {
+        if (!QUERY && (path_done || (NEE && nee_add))) {
             {
                 const unsigned long long fr = radiance_to_fixed(L_r), fg = radiance_to_fixed(L_g), fb = radiance_to_fixed(L_b);
                 if (cur_p < 0) {
@@ -1311,7 +1343,10 @@
         // 147.9 / 147.9 / 147.3 ms and 1.16 / - / 2.0 GB of HBM writes, a 1/8 row shard (short items) 20.36 / 20.11 /
         // 19.97 ms: the host sets 12 for launches with many tiles per wave and 63 for small ones.
         bool fetch = exhausted && !queue_empty;
-        if (c_valid && idle != 0ull && fetch) {
+        if (QUERY) {
+            // (the lanes still tracing carry their ray's index: an item that is handed out has nothing left to wait for)
+            if (idle != 0ull && fetch) c_valid = false;
+        } else if (c_valid && idle != 0ull && fetch) {
             if (mask_count(~idle) <= P.orphan_max) {
                 if (active && cur_p >= 0) cur_p = ~((c_band * 8 + (cur_p >> 3)) * P.width + c_x0 + (cur_p & 7));
                 flush_tile(c_acc, c_x0, c_band);
@@ -1325,6 +1360,19 @@
                 unsigned int item = 0;
                 if (lane == 0) item = atomicAdd(queue, 1u);
                 item = __builtin_amdgcn_readfirstlane(item);
+                if constexpr (QUERY) {
+                    // item i is the rays [i * RT_TRACE_ITEM, + RT_TRACE_ITEM) of the batch (n < 2^31, and the counter
+                    // passes the last item by at most one per wave: 32 bits hold it)
+                    const uint32_t base = item * (uint32_t)RT_TRACE_ITEM;
+                    if (base >= TQ.n) {
+                        queue_empty = true;
+                    } else {
+                        c_sbegin = (int)base;
+                        c_pool = (int)min((uint32_t)RT_TRACE_ITEM, TQ.n - base);
+                        cursor = 0;
+                        c_valid = true;
+                    }
+                } else {
                 const int4 ia = ipar4(0), ib = ipar4(1), ic = ipar4(2);
                 if (item >= (unsigned int)ia.z) {
                     queue_empty = true;  // the counter only grows: every wave gets here
@@ -1371,9 +1419,35 @@
                     // (POOL: a pixel's row is read across lanes in the refill; an off-image pixel says so through it)
                     if (POOL && c_hvalid == 0) c_hy = -1;
                 }
+                }
             }
             bool start = false;
             int sp = 0, spx = 0, spy = 0, ss = 0;
+            if constexpr (QUERY) {
+                // an idle lane takes ray c_sbegin + cursor + rank: two 16-byte loads, the guard (rt_trace.h), and what every new
+                // ray needs.  A ray that fails the guard gets its record here and never enters the walk; its lane stays idle.
+                const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32),
+                                                                __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
+                const int k = cursor + rank;
+                if (c_valid) cursor = min(cursor + mask_count(idle), c_pool);
+                const unsigned long long takes = c_valid ? idle & __builtin_amdgcn_ballot_w64(k < c_pool) : 0ull;
+                bool ok = false;
+                if (__builtin_amdgcn_inverse_ballot_w64(takes)) {
+                    const uint32_t ray = (uint32_t)(c_sbegin + k);
+                    const float4 r0 = TQ.rays[(size_t)ray * 2], r1 = TQ.rays[(size_t)ray * 2 + 1];
+                    ok = ray_valid(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z);
+                    if (ok) {
+                        q_ray = ray, q_tmax = r0.w;
+                        ox = r0.x, oy = r0.y, oz = r0.z, dx = r1.x, dy = r1.y, dz = r1.z;
+                        ra = dot3(dx, dy, dz, dx, dy, dz);
+                        rinv_a = 1.0f / ra;
+                        active = true;
+                    } else {
+                        put_record(ray, INFINITY, RT_HIT_INVALID, 0, 0, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f);
+                    }
+                }
+                started_m = takes & __builtin_amdgcn_ballot_w64(ok);
+            } else
             if (POOL) {
                 const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32),
                                                                 __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
@@ -1422,7 +1496,7 @@
                 else exhausted = __builtin_amdgcn_ballot_w64(c_hvalid != 0 && mine * 64 < c_pool) == 0ull;
             }
             if (queue_empty && exhausted) {
-                if (c_valid) flush_tile(c_acc, c_x0, c_band);
+                if (!QUERY && c_valid) flush_tile(c_acc, c_x0, c_band);
                 break;
             }
             continue;
@@ -1430,8 +1504,9 @@
         // ---- (5) rejection sampling, one converged loop: random_in_unit_sphere (vec3.h:121-129: three draws, for the
         // lanes whose material scatters with one: lambertian, metal) and random_in_unit_disk (vec3.h:157-165: two
         // draws, for the lens sample of the paths that start)
-        const bool need_s = (kind >= 0 && kind <= MK_METAL) || (MEDIA && kind == MK_MEDIUM);
-        const bool need_d = started && (P.flags & RT_FLAG_DEFOCUS_BLUR) != 0u;
+        // (QUERY: a ray is traced once and answered: no scatter step, no camera, no roulette -- nothing from here on)
+        const bool need_s = !QUERY && ((kind >= 0 && kind <= MK_METAL) || (MEDIA && kind == MK_MEDIUM));
+        const bool need_d = !QUERY && started && (P.flags & RT_FLAG_DEFOCUS_BLUR) != 0u;
         float sx = 0, sy = 0, sz = 0, sl2 = 1;
         asm volatile("" : "=v"(sx), "=v"(sy), "=v"(sz), "=v"(sl2));  // (read by the lanes that ran the loop below, which sets all four)
         if (need_s || need_d) {
@@ -1465,7 +1540,7 @@
         // absorbed metal vertex), the throughput the continuation carries, the metal's reflected direction and fuzz (0: lambertian)
         bool nee_v = false, nee_end = false;
         float vb_r = 0, vb_g = 0, vb_b = 0, mrx = 0, mry = 0, mrz = 0, mfz = 0;
-        if (kind >= 0) {
+        if (!QUERY && kind >= 0) {
             const float4 *M = rec_at(image + P.off_mat, __umul24((uint32_t)mat, 48u));  // (below 2^24 materials: scene_validate)
             if constexpr (MEDIA) {  // (a medium's record 1 is {albedo, density}: where a material keeps c0)
                 if (kind == MK_MEDIUM) M = image + __builtin_amdgcn_readfirstlane(__float_as_int(image[P.off_cam + 2].w)) + RT_MEDIUM_STRIDE * mat;
@@ -1546,7 +1621,7 @@
             }
         }
         // ---- (6b) the camera ray of the paths that start (camera::get_ray, camera.h:32-39)
-        if (started) {
+        if (!QUERY && started) {
                 float offx = 0.0f, offy = 0.0f, offz = 0.0f;
                 // the camera's derived vectors come from the hot table (wave-uniform reads, used here only),
                 // not from kernel arguments that would sit in SGPRs for the whole launch
@@ -1583,7 +1658,7 @@
         // Russian roulette before the next query (4_0_path_tracing.py:45-46; include/rtmi.h,
         // rt_scene_set_russian_roulette): a path that does not survive keeps what it has collected (a new one:
         // nothing, so there is nothing to add); a survivor's throughput is divided by p at once
-        if (!AOV && P.rr_p > 0.0f) {  // (a feature sample ends at its first query: no roulette draw)
+        if (!AOV && !QUERY && P.rr_p > 0.0f) {  // (a feature sample ends at its first query: no roulette draw)
             if (started) {
                 if (rng_next<COUNT>(rng) > P.rr_p) active = false;
                 beta_r = beta_g = beta_b = 1.0f / P.rr_p;

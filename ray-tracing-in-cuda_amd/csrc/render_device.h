@@ -13,6 +13,7 @@
 #include "rt_env.h"
 #include "rt_media.h"
 #include "rt_motion.h"
+#include "rt_trace.h"
 #include "rt_trig.h"
 #include "shard.h"
 #include "../../include/rtmi.h"
@@ -62,6 +63,17 @@ namespace rtmi {
 
 static constexpr float kTMin = 0.001f;  // main.cu:45 / main.cpp:22
 static_assert(RT_FIX_BITS == RT_ACC_FIX_BITS, "the kernel's pixel sums and the ABI's scale");
+
+// ---------------------------------------------------------------- ray queries (trace.hip)
+// what trace_kernel gets beside the scene: n rays of two 16-byte records each {origin, t_max} {dir, reserved}; out: three
+// 16-byte records per ray (mode 0, rt_hit) or one byte per ray (mode 1).  The render kernels carry a null one (render_body.h
+// names its members in text that is compiled, and discarded, there).
+struct TraceArgs {
+    const float4 *rays;
+    float4 *out;
+    uint32_t n;
+    int32_t mode;
+};
 
 // ---------------------------------------------------------------- RNG
 struct LaneRng {

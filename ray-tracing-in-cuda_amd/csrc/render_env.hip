@@ -15,7 +15,8 @@ __global__ __launch_bounds__(256, NEE_ ? RT_NEE_WAVES_PER_SIMD : RT_WAVES_PER_SI
     const RenderParams P, const float4 *__restrict__ image, unsigned long long *__restrict__ acc, unsigned int *__restrict__ queue,
     DevCounters *__restrict__ counters) {
     static_assert(!(NEE_ && AOV_), "a feature sample ends at its first query");
-    constexpr bool COUNT = false, POOL = true, EXT = true, SPH = false, NEE = NEE_, AOV = AOV_, ENV = true, MEDIA = false, MOTION = false;
+    constexpr bool COUNT = false, POOL = true, EXT = true, SPH = false, NEE = NEE_, AOV = AOV_, ENV = true, MEDIA = false, MOTION = false, QUERY = false;
+    constexpr TraceArgs TQ{nullptr, nullptr, 0u, 0};
 #include "render_body.h"
 }
 

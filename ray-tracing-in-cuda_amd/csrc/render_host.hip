@@ -49,6 +49,8 @@ struct DeviceEntry {
     DeviceBuffer<float> d_out;  // framebuffer of the host-buffer entry points (rt_render_hip), kept between calls
     DeviceBuffer<char> d_adapt;  // adaptive sampling: accumulator plane B, next tile list, tile counts, list counter
     DeviceBuffer<int> d_spp;     // spp_map of rt_render_hip_adaptive (host-buffer entry point)
+    DeviceBuffer<unsigned int> d_trace_queue;  // ray queries: the work counter of a launch (64 words)
+    DeviceBuffer<char> d_trace_io;             // rays and records of rt_trace_hip (host-buffer entry point), kept between calls
     int num_cus = 0;
 };
 
@@ -520,6 +522,25 @@ static int read_counters(const DevCounters *d_cnt, const RenderParams &P, int cu
     return RT_OK;
 }
 
+// timing events: three per (host thread, device), created at the thread's first timed call there and kept
+static int timing_events(int device, std::array<hipEvent_t, 3> *&out) {
+    struct Events {
+        std::vector<std::array<hipEvent_t, 3>> per_device;
+        ~Events() {
+            for (auto &t : per_device)
+                for (hipEvent_t ev : t)
+                    if (ev) (void)hipEventDestroy(ev);
+        }
+    };
+    static thread_local Events events;
+    if ((int)events.per_device.size() <= device) events.per_device.resize((size_t)device + 1, {nullptr, nullptr, nullptr});
+    auto &t = events.per_device[(size_t)device];
+    for (hipEvent_t &ev : t)
+        if (!ev) HIP_TRY(hipEventCreate(&ev));
+    out = &t;
+    return RT_OK;
+}
+
 static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, void *stream_v, rt_stats *stats,
                        long long *h_acc, bool count, const AdaptiveRun *ad = nullptr, int feature = -1) {
     if (!sc || (!d_rgb_sum && !h_acc)) {
@@ -609,23 +630,12 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     rc = ensure_packed(s, cache);
     if (rc) return rc;
     DeviceEntry *ent = device_record(cache.entries, device);
-    // timing events: three per (host thread, device), created at the thread's first timed call there and kept
-    struct Events {
-        std::vector<std::array<hipEvent_t, 3>> per_device;
-        ~Events() {
-            for (auto &t : per_device)
-                for (hipEvent_t ev : t)
-                    if (ev) (void)hipEventDestroy(ev);
-        }
-    };
-    static thread_local Events events;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
     if (stats) {
-        if ((int)events.per_device.size() <= device) events.per_device.resize((size_t)device + 1, {nullptr, nullptr, nullptr});
-        auto &t = events.per_device[(size_t)device];
-        for (hipEvent_t &ev : t)
-            if (!ev) HIP_TRY(hipEventCreate(&ev));
-        ev0 = t[0], ev1 = t[1], ev2 = t[2];
+        std::array<hipEvent_t, 3> *t = nullptr;
+        rc = timing_events(device, t);
+        if (rc) return rc;
+        ev0 = (*t)[0], ev1 = (*t)[1], ev2 = (*t)[2];
         HIP_TRY(hipEventRecord(ev0, stream));
     }
     size_t image_bytes = cache.image.size() * sizeof(float);
@@ -1067,6 +1077,178 @@ int rt_render_hip_feature_device(const rt_scene *s, const rt_opts *o, int featur
     int rc = feature_args(s, feature, d_sum);
     if (rc) return rc;
     return render_impl(s, o, d_sum, stream, stats, nullptr, false, nullptr, feature);
+}
+
+// ---- ray queries.  The arguments, checked before any device access; *layout: the variant as given
+static int trace_args(const rt_scene *sc, const rt_opts *o, int mode, const void *rays, size_t n, const void *out, unsigned *layout) {
+    if (!sc) {
+        set_error("rt_trace_hip: null scene");
+        return RT_ERR_ARG;
+    }
+    if (mode != RT_TRACE_CLOSEST && mode != RT_TRACE_OCCLUDED) {
+        set_error("rt_trace_hip: mode %d (0 closest hit, 1 occlusion)", mode);
+        return RT_ERR_ARG;
+    }
+    if (n >= ((size_t)1 << 31)) {
+        set_error("rt_trace_hip: %zu rays in one batch (fewer than 2^31: split the batch)", n);
+        return RT_ERR_LIMIT;
+    }
+    if (!sc->s.movers.empty()) {
+        set_error("rt_trace_hip: this scene has moving spheres and a ray query has no shutter time: clear the moving spheres for the query (rt_scene_clear_moving_spheres)");
+        return RT_ERR_ARG;
+    }
+    const unsigned variant = o ? o->variant : 0;
+    const unsigned ok[] = {0u, 16u, 24u, 36u, 44u, 52u};
+    if (std::find(std::begin(ok), std::end(ok), variant) == std::end(ok)) {
+        set_error("rt_trace_hip: layout %u (0, 16, 24, 36, 44 or 52)", variant);
+        return RT_ERR_ARG;
+    }
+    *layout = variant;
+    if (n > 0 && (!rays || !out)) {
+        set_error("rt_trace_hip: null rays or output pointer");
+        return RT_ERR_ARG;
+    }
+    return RT_OK;
+}
+
+// n > 0 rays at d_rays -> d_out, both on o->device (the arguments have been checked)
+static int trace_impl(const rt_scene *sc, const rt_opts *o, unsigned variant, int mode, const void *d_rays, size_t n, void *d_out,
+                      void *stream_v, rt_stats *stats) {
+    const Scene &s = sc->s;
+    int rc = scene_validate(s);
+    if (rc) return rc;
+    if (stats) memset(stats, 0, sizeof *stats);
+    const int device = o ? o->device : 0;
+    DeviceScope scope;
+    rc = scope.enter(device, "the ray-query path");
+    if (rc) return rc;
+    hipStream_t stream = (hipStream_t)stream_v;
+    DeviceSceneCache &cache = cache_of(s);
+    std::unique_lock<std::mutex> lock(cache.mu);  // (as render_impl: packing, the entry list and the enqueueing)
+    rc = ensure_packed(s, cache);
+    if (rc) return rc;
+    DeviceEntry *ent = device_record(cache.entries, device);
+    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
+    if (stats) {
+        std::array<hipEvent_t, 3> *t = nullptr;
+        rc = timing_events(device, t);
+        if (rc) return rc;
+        ev0 = (*t)[0], ev1 = (*t)[1], ev2 = (*t)[2];
+        HIP_TRY(hipEventRecord(ev0, stream));
+    }
+    if (ent->version != s.version || !ent->d_image.get()) {
+        rc = ent->d_image.reserve(cache.image.size());
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(ent->d_image.get(), cache.image.data(), cache.image.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+        ent->version = s.version;
+    }
+    // the layout: the scene's own, or the one named; compact tables list spheres for the sphere-only kernels, a query scans
+    // the list instead (as a feature pass does)
+    const RenderParams &P = cache.layout;
+    static const size_t global_threshold = (size_t)knob("RTMI_GLOBAL_TABLE_BYTES", (double)kLdsTableBytes);
+    if (variant == 0) variant = pick_variant(P, false, global_threshold);
+    const size_t scan_bytes = (size_t)(P.hot_vec4 - (P.off_box - P.off_grid)) * 16;
+    if (variant == 2 || variant == 6) variant = scan_bytes <= global_threshold ? 16u : 24u;
+    const int mode_cull = variant == 52 ? 8 : (variant == 36 || variant == 44) ? 7 : 0;
+    if (mode_cull == 8 && P.grid_wide != 2) {
+        set_error("layout 52 walks tables with nested cells, which this scene does not have (rt_scene_set_nested_grid, and a cell to nest): use 0");
+        return RT_ERR_ARG;
+    }
+    if (mode_cull == 7 && P.grid_wide == 2) {
+        set_error("layout %u does not walk the nested cells of this scene's tables: use 0, 52 or the linear scans 16 / 24", variant);
+        return RT_ERR_ARG;
+    }
+    if (mode_cull == 7 && !P.grid_wide) {
+        set_error("layout %u walks the wide grid tables; this scene (spheres only, small enough for LDS) has the compact ones: use 0, 16 or 24", variant);
+        return RT_ERR_LIMIT;
+    }
+    const KernelRow *kernel = find_kernel({K_TRACE, variant, true});
+    if (!kernel) {
+        set_error("layout %u has no ray-query kernel", variant);
+        return RT_ERR_ARG;
+    }
+    // LDS per workgroup: the hot tables the search reads, unless it reads them from global memory -- and nothing else
+    const bool tables_global = (variant & 8u) != 0 || mode_cull == 8;
+    const size_t lds_bytes = tables_global ? 0 : (mode_cull == 7 ? (size_t)P.hot_vec4_grid * 16 : scan_bytes);
+    if (lds_bytes > 160 * 1024) {
+        set_error("layout %u keeps the scene tables in LDS and this scene needs %zu bytes per workgroup (limit 163840); use layout 0", variant, lds_bytes);
+        return RT_ERR_LIMIT;
+    }
+    if (ent->num_cus == 0) {
+        hipDeviceProp_t prop;
+        HIP_TRY(hipGetDeviceProperties(&prop, device));
+        ent->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    }
+    if (lds_bytes > 64 * 1024 && set_max_dynamic_lds(*kernel, lds_bytes)) {
+        set_error("cannot raise the dynamic LDS limit to %zu bytes", lds_bytes);
+        return RT_ERR_HIP;
+    }
+    const unsigned long long resident = (unsigned long long)ent->num_cus * blocks_per_cu(*kernel, lds_bytes);
+    rc = ent->d_trace_queue.reserve(64);
+    if (rc) return rc;
+    if (stats) HIP_TRY(hipEventRecord(ev1, stream));
+    HIP_TRY(hipMemsetAsync(ent->d_trace_queue.get(), 0, 4, stream));
+    // persistent launch: enough workgroups to fill the chip, never more than the work needs (an item per wave)
+    const unsigned long long items = (n + RT_TRACE_ITEM - 1) / RT_TRACE_ITEM, need_blocks = (items + 3) / 4;
+    const unsigned long long grid = need_blocks < resident ? need_blocks : resident;
+    RenderParams Q = P;
+    Q.rr_p = 0.0f, Q.flags = 0u, Q.max_depth = 1;
+    launch_trace(*kernel, Q, ent->d_image.get(), d_rays, d_out, ent->d_trace_queue.get(), (unsigned int)n, mode, lds_bytes, (unsigned)grid, stream);
+    HIP_TRY(hipGetLastError());
+    if (stats) {
+        stats->kernel_variant = (int32_t)(variant | 8192u);
+        HIP_TRY(hipEventRecord(ev2, stream));
+        lock.unlock();
+        HIP_TRY(hipEventSynchronize(ev2));
+        float up = 0, k = 0;
+        HIP_TRY(hipEventElapsedTime(&up, ev0, ev1));
+        HIP_TRY(hipEventElapsedTime(&k, ev1, ev2));
+        stats->upload_ms = up, stats->kernel_ms = k, stats->launches = 1;
+    }
+    return RT_OK;
+}
+
+int rt_trace_hip_device(const rt_scene *s, const rt_opts *o, int mode, const void *d_rays, size_t n, void *d_out, void *stream, rt_stats *stats) {
+    unsigned layout = 0;
+    int rc = trace_args(s, o, mode, d_rays, n, d_out, &layout);
+    if (rc) return rc;
+    if (n == 0) {
+        if (stats) memset(stats, 0, sizeof *stats);
+        return RT_OK;
+    }
+    return trace_impl(s, o, layout, mode, d_rays, n, d_out, stream, stats);
+}
+
+int rt_trace_hip(const rt_scene *s, const rt_opts *o, int mode, const rt_ray *rays, size_t n, void *out, rt_stats *stats) {
+    unsigned layout = 0;
+    int rc = trace_args(s, o, mode, rays, n, out, &layout);
+    if (rc) return rc;
+    if (n == 0) {
+        if (stats) memset(stats, 0, sizeof *stats);
+        return RT_OK;
+    }
+    const int device = o ? o->device : 0;
+    DeviceScope scope;
+    rc = scope.enter(device, "the ray-query path");
+    if (rc) return rc;
+    // the device copies of this (scene, device) are kept between calls: rays, then (256-byte aligned) the records
+    const size_t ray_bytes = n * sizeof(rt_ray), out_bytes = mode == RT_TRACE_OCCLUDED ? n : n * sizeof(rt_hit);
+    const size_t out_off = (ray_bytes + 255) & ~(size_t)255;
+    char *d_io = nullptr;
+    {
+        DeviceSceneCache &cache = cache_of(s->s);
+        std::lock_guard<std::mutex> lock(cache.mu);
+        DeviceEntry *ent = device_record(cache.entries, device);
+        rc = ent->d_trace_io.reserve(out_off + out_bytes);
+        if (rc) return rc;
+        d_io = ent->d_trace_io.get();
+    }
+    HIP_TRY(hipMemcpy(d_io, rays, ray_bytes, hipMemcpyHostToDevice));
+    rt_stats local;
+    rc = trace_impl(s, o, layout, mode, d_io, n, d_io + out_off, nullptr, stats ? stats : &local);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(out, d_io + out_off, out_bytes, hipMemcpyDeviceToHost));
+    return RT_OK;
 }
 
 int rt_render_hip_accumulate(const rt_scene *s, const rt_opts *o, int64_t *acc, float *rgb_sum, rt_stats *stats) {

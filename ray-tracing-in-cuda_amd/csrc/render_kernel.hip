@@ -78,7 +78,8 @@ __global__ __launch_bounds__(256, RT_WAVES_PER_SIMD) void render_kernel(const Re
                                                      unsigned long long *__restrict__ acc,
                                                      unsigned int *__restrict__ queue,
                                                      DevCounters *__restrict__ counters) {
-    constexpr bool NEE = false, AOV = false, ENV = false, MEDIA = false, MOTION = false;
+    constexpr bool NEE = false, AOV = false, ENV = false, MEDIA = false, MOTION = false, QUERY = false;
+    constexpr TraceArgs TQ{nullptr, nullptr, 0u, 0};
 #include "render_body.h"
 }
 
@@ -89,7 +90,8 @@ __global__ __launch_bounds__(256, RT_NEE_WAVES_PER_SIMD) void render_nee_kernel(
                                                          unsigned long long *__restrict__ acc,
                                                          unsigned int *__restrict__ queue,
                                                          DevCounters *__restrict__ counters) {
-    constexpr bool COUNT = false, POOL = true, EXT = true, SPH = false, NEE = true, AOV = false, ENV = false, MEDIA = false, MOTION = false;
+    constexpr bool COUNT = false, POOL = true, EXT = true, SPH = false, NEE = true, AOV = false, ENV = false, MEDIA = false, MOTION = false, QUERY = false;
+    constexpr TraceArgs TQ{nullptr, nullptr, 0u, 0};
 #include "render_body.h"
 }
 
@@ -101,7 +103,8 @@ __global__ __launch_bounds__(256, RT_WAVES_PER_SIMD) void render_nested_kernel(c
                                                             unsigned long long *__restrict__ acc,
                                                             unsigned int *__restrict__ queue,
                                                             DevCounters *__restrict__ counters) {
-    constexpr bool POOL = true, SCALAR = true, SPH = false, NEE = false, AOV = false, ENV = false, MEDIA = false, MOTION = false;
+    constexpr bool POOL = true, SCALAR = true, SPH = false, NEE = false, AOV = false, ENV = false, MEDIA = false, MOTION = false, QUERY = false;
+    constexpr TraceArgs TQ{nullptr, nullptr, 0u, 0};
     constexpr int CULL = 8;
 #include "render_body.h"
 }
@@ -115,7 +118,8 @@ __global__ __launch_bounds__(256, RT_WAVES_PER_SIMD) void render_feature_kernel(
                                                              unsigned long long *__restrict__ acc,
                                                              unsigned int *__restrict__ queue,
                                                              DevCounters *__restrict__ counters) {
-    constexpr bool COUNT = false, POOL = true, EXT = true, SPH = false, NEE = false, AOV = true, ENV = false, MEDIA = false, MOTION = false;
+    constexpr bool COUNT = false, POOL = true, EXT = true, SPH = false, NEE = false, AOV = true, ENV = false, MEDIA = false, MOTION = false, QUERY = false;
+    constexpr TraceArgs TQ{nullptr, nullptr, 0u, 0};
 #include "render_body.h"
 }
 
@@ -201,7 +205,7 @@ const KernelRow *render_kernel_rows(size_t *n) {
 bool has_ablations() { return RTMI_ABLATIONS != 0; }
 
 const KernelRow *find_kernel(const KernelKey &key) {
-    const KernelRow *(*const tables[])(size_t *) = {render_kernel_rows, env_kernel_rows, media_kernel_rows, motion_kernel_rows};
+    const KernelRow *(*const tables[])(size_t *) = {render_kernel_rows, env_kernel_rows, media_kernel_rows, motion_kernel_rows, trace_kernel_rows};
     for (auto rows_of : tables) {
         size_t n = 0;
         const KernelRow *rows = rows_of(&n);

@@ -18,7 +18,8 @@ template <bool SCALAR, int CULL>
 __global__ __launch_bounds__(256, RT_MEDIA_WAVES_PER_SIMD) void render_media_kernel(
     const RenderParams P, const float4 *__restrict__ image, unsigned long long *__restrict__ acc, unsigned int *__restrict__ queue,
     DevCounters *__restrict__ counters) {
-    constexpr bool COUNT = false, POOL = true, EXT = true, SPH = false, NEE = false, AOV = false, ENV = false, MEDIA = true, MOTION = false;
+    constexpr bool COUNT = false, POOL = true, EXT = true, SPH = false, NEE = false, AOV = false, ENV = false, MEDIA = true, MOTION = false, QUERY = false;
+    constexpr TraceArgs TQ{nullptr, nullptr, 0u, 0};
 #include "render_body.h"
 }
 

@@ -17,7 +17,8 @@ template <bool SCALAR, int CULL>
 __global__ __launch_bounds__(256, RT_MOTION_WAVES_PER_SIMD) void render_motion_kernel(
     const RenderParams P, const float4 *__restrict__ image, unsigned long long *__restrict__ acc, unsigned int *__restrict__ queue,
     DevCounters *__restrict__ counters) {
-    constexpr bool COUNT = false, POOL = true, EXT = true, SPH = false, NEE = false, AOV = false, ENV = false, MEDIA = false, MOTION = true;
+    constexpr bool COUNT = false, POOL = true, EXT = true, SPH = false, NEE = false, AOV = false, ENV = false, MEDIA = false, MOTION = true, QUERY = false;
+    constexpr TraceArgs TQ{nullptr, nullptr, 0u, 0};
 #include "render_body.h"
 }
 
