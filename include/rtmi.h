@@ -54,7 +54,9 @@ typedef enum rt_prim_type {
     RT_PRIM_YZ_RECT = 3,  /* object.cuh:166-197 f = {y0,y1,z0,z1,k}          */
     RT_PRIM_CYLINDER = 4, /* object.cuh:216-297 f = {radius,zmin,zmax}, m/m_inv */
     RT_PRIM_TRIANGLE = 5  /* taichi-version/hittable.py:38-71, 95-110: m[0..8] = v1, v2, v3; m[9..11] = the unit
-                             normal (v2-v1)x(v3-v1) / |..|; m_inv[0..5] = texture coordinates u1, u2, u3 (2 each) */
+                             normal (v2-v1)x(v3-v1) / |..|; m_inv[0..5] = texture coordinates u1, u2, u3 (2 each);
+                             the unit vertex normals of smooth shading: f[0..2] = n1, f[3..5] = n2,
+                             m_inv[6..8] = n3 -- all nine words zero: a flat triangle; m_inv[9..11] = 0 */
 } rt_prim_type;
 
 typedef enum rt_mat_type {
@@ -355,6 +357,34 @@ int rt_scene_add_triangle(rt_scene *s, const float v1[3], const float v2[3], con
  * every vertex is mapped to scale * (M v) + translate (M = 3x3 row-major, NULL = identity).  -> triangles added */
 int rt_scene_add_obj(rt_scene *s, const char *path, int material, float scale, const float matrix[9],
                      const float translate[3]);
+
+/* Smooth shading: a triangle with three vertex normals.  Geometry, t, the point, (u, v), `front` and the
+ * tie rule are the flat triangle's; where a material scatters (and in the normal feature buffer and rt_hit.normal)
+ * the normal is s = a1 n1 + a2 n2 + a3 n3, a_i the area of the sub-triangle opposite corner i over the whole (the three
+ * area weights of (u, v), each with the corner at which it is 1), normalised and turned into the hemisphere of the
+ * face-turned geometric normal; s zero or not finite: the geometric normal.  An emitter hit keeps the
+ * geometric normal.  n1, n2, n3 are normalised in fp64 and rounded once; a NULL, non-finite or zero-length normal
+ * is RT_ERR_ARG.  -> prim id */
+int rt_scene_add_triangle_normals(rt_scene *s, const float v1[3], const float v2[3], const float v3[3],
+                                  const float n1[3], const float n2[3], const float n3[3],
+                                  const float uv1[2], const float uv2[2], const float uv3[2], int material);
+/* where the vertex normals of a mesh come from */
+typedef enum rt_mesh_normals {
+    RT_MESH_NORMALS_FLAT = 0,   /* none: rt_scene_add_obj                                                          */
+    RT_MESH_NORMALS_FILE = 1,   /* the file's "vn x y z" lines through the corners "a//n" and "a/t/n" (1-based; an n
+                                   out of range is an error), mapped by the inverse transpose of scale * M and
+                                   renormalised; a corner without n takes its face's normal                         */
+    RT_MESH_NORMALS_SMOOTH = 2  /* generated: per corner the normalised angle-weighted sum of the face normals of
+                                   the triangles that meet at the corner's (placed) vertex position and whose face
+                                   normal lies within crease_degrees of the corner's own face                        */
+} rt_mesh_normals;
+/* rt_scene_add_obj with vertex normals; crease_degrees (0..180) is read by RT_MESH_NORMALS_SMOOTH alone.
+ * -> triangles added */
+int rt_scene_add_obj_normals(rt_scene *s, const char *path, int material, float scale, const float matrix[9],
+                             const float translate[3], int mode, float crease_degrees);
+/* every "mesh" of the scene files loaded from here on (this thread) takes its normals this way instead of its own
+ * "normals" / "crease_angle" (the CLI's --mesh-normals); mode < 0: back to what the files say */
+void rt_set_mesh_normals_override(int mode, float crease_degrees);
 
 /* ---- animation (gpu-version/blue.py, blue2.py, dna.py: the frame harness) ----- */
 /* blue.py:16-19 / blue2.py:16-19: add `degrees` to rotate.angle of every cylinder that has a

@@ -134,6 +134,9 @@ struct hittable {
     material_ptr mat;
     // triangle only (taichi-version/hittable.py:95-110): corners and their texture coordinates
     float v[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, uv[6] = {0, 0, 0, 0, 0, 0};
+    // ... and, for smooth shading, its three vertex normals (rt_scene_add_triangle_normals)
+    bool has_normals = false;
+    float n[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     // cylinder only: rotate (axis, radians) then translate, as cylinder::rotate/translate compose
     bool has_rotate = false, has_translate = false;
     vec3 axis{0, 0, 1}, offset;
@@ -178,6 +181,15 @@ inline hittable triangle(point3 v1, point3 v2, point3 v3, material_ptr m, const 
         h.v[3 * k] = c[k]->x(), h.v[3 * k + 1] = c[k]->y(), h.v[3 * k + 2] = c[k]->z();
         if (u[k]) h.uv[2 * k] = u[k][0], h.uv[2 * k + 1] = u[k][1];
     }
+    return h;
+}
+// ... with the vertex normals n1, n2, n3 of smooth shading (rt_scene_add_triangle_normals)
+inline hittable smooth_triangle(point3 v1, point3 v2, point3 v3, vec3 n1, vec3 n2, vec3 n3, material_ptr m, const float *u1 = nullptr,
+                                const float *u2 = nullptr, const float *u3 = nullptr) {
+    hittable h = triangle(v1, v2, v3, std::move(m), u1, u2, u3);
+    const vec3 *n[3] = {&n1, &n2, &n3};
+    h.has_normals = true;
+    for (int k = 0; k < 3; ++k) h.n[3 * k] = n[k]->x(), h.n[3 * k + 1] = n[k]->y(), h.n[3 * k + 2] = n[k]->z();
     return h;
 }
 inline hittable cylinder(float radius, float zmin, float zmax, material_ptr m) {  // object.cuh:220-223
@@ -256,7 +268,10 @@ public:
         int id;
         switch (h.type) {
         case RT_PRIM_SPHERE: id = rt_scene_add_sphere(s_, h.f, h.f[3], m); break;
-        case RT_PRIM_TRIANGLE: id = rt_scene_add_triangle(s_, h.v, h.v + 3, h.v + 6, h.uv, h.uv + 2, h.uv + 4, m); break;
+        case RT_PRIM_TRIANGLE:
+            id = h.has_normals ? rt_scene_add_triangle_normals(s_, h.v, h.v + 3, h.v + 6, h.n, h.n + 3, h.n + 6, h.uv, h.uv + 2, h.uv + 4, m)
+                               : rt_scene_add_triangle(s_, h.v, h.v + 3, h.v + 6, h.uv, h.uv + 2, h.uv + 4, m);
+            break;
         case RT_PRIM_CYLINDER: {
             const float deg = h.radians * 180.0f / 3.14159265358979323846f;
             id = rt_scene_add_cylinder(s_, h.f[0], h.f[1], h.f[2], m, h.has_rotate ? h.axis.e : nullptr, deg,
@@ -272,6 +287,13 @@ public:
     int add_obj(const std::string &path, const material_ptr &m, float scale = 1.0f, const float *matrix9 = nullptr,
                 const float *translate3 = nullptr) {
         int n = rt_scene_add_obj(s_, path.c_str(), material_id(m), scale, matrix9, translate3);
+        if (n < 0) throw error(-n, "add_obj");
+        return n;
+    }
+    // ... with vertex normals (smooth shading): from the file's vn lines, or generated within a crease angle
+    int add_obj(const std::string &path, const material_ptr &m, rt_mesh_normals normals, float crease_degrees = 180.0f, float scale = 1.0f,
+                const float *matrix9 = nullptr, const float *translate3 = nullptr) {
+        int n = rt_scene_add_obj_normals(s_, path.c_str(), material_id(m), scale, matrix9, translate3, normals, crease_degrees);
         if (n < 0) throw error(-n, "add_obj");
         return n;
     }

@@ -43,6 +43,7 @@ MAT_LAMBERTIAN, MAT_METAL, MAT_DIELECTRIC, MAT_DIFFUSE_LIGHT = range(4)
 TEX_SOLID, TEX_CHECKER, TEX_IMAGE = range(3)
 
 # numpy views of the table records (layouts of include/rtmi.h)
+MESH_NORMALS = {"flat": 0, "file": 1, "smooth": 2}  # rt_mesh_normals
 PRIM_DTYPE = np.dtype(
     [("type", "<i4"), ("material", "<i4"), ("f", "<f4", (6,)), ("m", "<f4", (12,)), ("m_inv", "<f4", (12,))]
 )
@@ -241,6 +242,9 @@ _sig("rt_scene_add_image_texture_file", C.c_int, _p, C.c_char_p)
 _sig("rt_scene_get_image", C.c_int, _p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), _p, C.c_size_t)
 _sig("rt_scene_add_triangle", C.c_int, _p, _f3, _f3, _f3, _f3, _f3, _f3, C.c_int)
 _sig("rt_scene_add_obj", C.c_int, _p, C.c_char_p, C.c_int, C.c_float, _f3, _f3)
+_sig("rt_scene_add_triangle_normals", C.c_int, _p, _f3, _f3, _f3, _f3, _f3, _f3, _f3, _f3, _f3, C.c_int)
+_sig("rt_scene_add_obj_normals", C.c_int, _p, C.c_char_p, C.c_int, C.c_float, _f3, _f3, C.c_int, C.c_float)
+_sig("rt_set_mesh_normals_override", None, C.c_int, C.c_float)
 _sig("rt_scene_override", C.c_int, _p, C.c_int, C.c_int, C.c_int, C.c_int)
 _sig("rt_scene_rotate_cylinders", C.c_int, _p, C.c_double)
 _sig("rt_scene_set_output_file", C.c_int, _p, C.c_char_p)
@@ -325,7 +329,7 @@ C_SYMBOLS = [
     "rt_scene_add_checker", "rt_scene_add_lambertian", "rt_scene_add_metal", "rt_scene_add_dielectric",
     "rt_scene_add_diffuse_light", "rt_scene_add_sphere", "rt_scene_add_rect", "rt_scene_add_cylinder",
     "rt_scene_add_image_texture", "rt_scene_add_image_texture_file", "rt_scene_get_image", "rt_scene_add_triangle",
-    "rt_scene_add_obj",
+    "rt_scene_add_obj", "rt_scene_add_triangle_normals", "rt_scene_add_obj_normals", "rt_set_mesh_normals_override",
     "rt_scene_override", "rt_scene_get_info", "rt_scene_get_camera", "rt_scene_get_prims",
     "rt_scene_get_materials", "rt_scene_get_textures", "rt_shard_rows", "rt_shard_global_row", "rt_shard_deal",
     "rt_render_hip_device", "rt_render_hip", "rt_render_hip_tiles", "rt_tiles_shutdown", "rt_shard_place_rows_device", "rt_render_hip_count", "rt_render_hip_accumulate", "rt_scene_set_russian_roulette",
@@ -531,16 +535,30 @@ class Scene:
                   "rt_scene_get_image")
         return out
 
-    def triangle(self, v1, v2, v3, material, u1=(0, 0), u2=(0, 0), u3=(0, 0)) -> int:
-        """Triangle(v1, v2, v3, u1, u2, u3, material), taichi-version/hittable.py:95-110."""
+    def triangle(self, v1, v2, v3, material, u1=(0, 0), u2=(0, 0), u3=(0, 0), normals=None) -> int:
+        """Triangle(v1, v2, v3, u1, u2, u3, material), taichi-version/hittable.py:95-110.  normals: three vertex normals
+        (n1, n2, n3) for smooth shading (stored normalised, visible in prims()), None: a flat triangle."""
         uv = [(C.c_float * 3)(float(u[0]), float(u[1]), 0.0) for u in (u1, u2, u3)]
+        if normals is not None:
+            n = np.asarray(normals, dtype=np.float64)
+            if n.shape != (3, 3):
+                raise ValueError("triangle normals must be three vectors of 3 numbers")
+            return _check_id(_lib.rt_scene_add_triangle_normals(self._h, _v3(v1), _v3(v2), _v3(v3), _v3(n[0]), _v3(n[1]), _v3(n[2]),
+                                                                uv[0], uv[1], uv[2], material), "triangle")
         return _check_id(_lib.rt_scene_add_triangle(self._h, _v3(v1), _v3(v2), _v3(v3), uv[0], uv[1], uv[2], material),
                          "triangle")
 
-    def add_obj(self, path, material, scale=1.0, matrix=None, translate=None) -> int:
-        """readobj + placement, taichi-version/main.py:23-41, 110-118; returns the number of triangles added."""
+    def add_obj(self, path, material, scale=1.0, matrix=None, translate=None, normals="flat", crease_angle=180.0) -> int:
+        """readobj + placement, taichi-version/main.py:23-41, 110-118; returns the number of triangles added.
+        normals: "flat", "file" (the file's vn lines) or "smooth" (generated, angle-weighted, from the faces within
+        crease_angle degrees of each other)."""
         m = (C.c_float * 9)(*[float(x) for x in np.asarray(matrix, dtype=np.float64).reshape(9)]) if matrix is not None else None
         t = _v3(translate) if translate is not None else None
+        if normals not in MESH_NORMALS:
+            raise ValueError('add_obj normals must be "flat", "file" or "smooth"')
+        if normals != "flat":
+            return _check_id(_lib.rt_scene_add_obj_normals(self._h, os.fsencode(path), material, scale, m, t, MESH_NORMALS[normals],
+                                                           float(crease_angle)), "add_obj")
         return _check_id(_lib.rt_scene_add_obj(self._h, os.fsencode(path), material, scale, m, t), "add_obj")
 
     def lambertian(self, texture_or_color) -> int:

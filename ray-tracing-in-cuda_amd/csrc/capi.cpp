@@ -370,6 +370,35 @@ int rt_scene_add_obj(rt_scene *s, const char *path, int material, float scale, c
     return add_obj(s->s, path, material, scale, matrix, translate);
 }
 
+int rt_scene_add_triangle_normals(rt_scene *s, const float v1[3], const float v2[3], const float v3[3], const float n1[3],
+                                  const float n2[3], const float n3[3], const float uv1[2], const float uv2[2], const float uv3[2],
+                                  int material) {
+    if (bad_scene(s, "rt_scene_add_triangle_normals")) return -RT_ERR_ARG;
+    if (!v1 || !v2 || !v3) {
+        set_error("triangle vertex is null");
+        return -RT_ERR_ARG;
+    }
+    if (!n1 || !n2 || !n3) {
+        set_error("triangle vertex normal is null");
+        return -RT_ERR_ARG;
+    }
+    if (bad_material(s, material)) return -RT_ERR_SCENE;
+    return add_triangle_normals(s->s, v1, v2, v3, n1, n2, n3, uv1, uv2, uv3, material);
+}
+
+int rt_scene_add_obj_normals(rt_scene *s, const char *path, int material, float scale, const float matrix[9],
+                             const float translate[3], int mode, float crease_degrees) {
+    if (bad_scene(s, "rt_scene_add_obj_normals")) return -RT_ERR_ARG;
+    if (!path) {
+        set_error("rt_scene_add_obj_normals: null path");
+        return -RT_ERR_ARG;
+    }
+    if (bad_material(s, material)) return -RT_ERR_SCENE;
+    return add_obj_normals(s->s, path, material, scale, matrix, translate, mode, crease_degrees);
+}
+
+void rt_set_mesh_normals_override(int mode, float crease_degrees) { set_mesh_normals_override(mode, crease_degrees); }
+
 int rt_scene_add_rect(rt_scene *s, int axis, float a0, float a1, float b0, float b1, float k, int material) {
     if (bad_scene(s, "rt_scene_add_rect")) return -RT_ERR_ARG;
     if (axis < 0 || axis > 2) {

@@ -23,6 +23,8 @@
 // Ray queries (rt_trace_hip): --pick X,Y (X from the left, Y from the top) traces the ray through that pixel's
 // centre and prints what it meets as one JSON line on stdout; no frame is rendered.  --focus-at X,Y traces the same ray and
 // focuses the camera on what it meets (focus_dist = t |dir|, rt_scene_set_camera) before the render.
+// Smooth shading: --mesh-normals flat|file|smooth[:DEG] gives every "mesh" of the scene file its vertex normals
+// that way, whatever its own "normals" says (DEG: the crease angle of the generated normals, 180 without).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -59,7 +61,7 @@ static int usage(const char *argv0) {
             "          [--denoise] [--aov PREFIX] [--feature-spp N]\n"
             "          [--tonemap clamp|reinhard|aces] [--exposure EV] [--auto-exposure [KEY]] [--white W]\n"
             "          [--bloom STRENGTH] [--bloom-threshold T] [--bloom-levels L] [--hdr-out frame.hdr|frame.pfm]\n"
-            "          [--pick X,Y] [--focus-at X,Y]\n",
+            "          [--pick X,Y] [--focus-at X,Y] [--mesh-normals flat|file|smooth[:DEG]]\n",
             argv0);
     return 2;
 }
@@ -172,6 +174,20 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--rr")) rr = atof(need("--rr"));
         else if (!strcmp(argv[i], "--nee")) nee = true;
         else if (!strcmp(argv[i], "--nested-grid")) nested = true;
+        else if (!strcmp(argv[i], "--mesh-normals")) {
+            const std::string v = need("--mesh-normals");
+            double deg = 180.0;
+            int mode = -1;
+            if (v == "flat") mode = RT_MESH_NORMALS_FLAT;
+            else if (v == "file") mode = RT_MESH_NORMALS_FILE;
+            else if (v == "smooth") mode = RT_MESH_NORMALS_SMOOTH;
+            else if (v.rfind("smooth:", 0) == 0 && number(v.c_str() + 7, 0.0, 180.0, &deg)) mode = RT_MESH_NORMALS_SMOOTH;
+            if (mode < 0) {
+                fprintf(stderr, "rtmi: --mesh-normals takes flat, file, smooth or smooth:DEG (0..180), not %s\n", v.c_str());
+                return 2;
+            }
+            rt_set_mesh_normals_override(mode, (float)deg);
+        }
         else if (!strcmp(argv[i], "--env")) env_file = need("--env");
         else if (!strcmp(argv[i], "--env-scale")) env_scale = atof(need("--env-scale")), have_env_opts = true;
         else if (!strcmp(argv[i], "--env-rotate")) env_rotate = atof(need("--env-rotate")), have_env_opts = true;

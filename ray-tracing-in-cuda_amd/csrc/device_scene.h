@@ -28,6 +28,10 @@
 //   ENVIRONMENT part (only with an environment map; global memory, read by the environment kernels): rt_env.h
 //   MEDIA part (only with at least one medium; global memory, read by the media kernels): rt_media.h.  Two words of the camera
 //     block say where it lies ({count, offset} in the .w of records off_cam + 1 and + 2; zero without media)
+//   NORMALS part (smooth shading; only when at least one triangle has vertex normals; global memory, read by the
+//     winner section of the general kernels): per triangle of the triangle tables 3 x float4 {n1.xyz, has normals(bits)}
+//     {n2.xyz, 0} {n3.xyz, 0}; a flat triangle's records are zeros.  The .w of record off_cam + 5 is the part's first record
+//     (zero: the scene has no vertex normals and no such part)
 //
 // Primitives are grouped by type (spheres, rects, cylinders), each group in list
 // order; the original list index is kept for the reference's tie rule (a later

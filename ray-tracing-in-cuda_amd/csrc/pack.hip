@@ -666,8 +666,9 @@ int lay_out_hot(RenderParams &L, const Grid &g) {
 // Every offset of the image, in image order: the one place that says what the image looks like.  Returns the record count;
 // image_word[k]: the first 32-bit word of image texture k's texels.
 // off_media: the first record of the MEDIA part (rt_media.h; 0: the scene has no media); off_motion: of the MOTION part
-// (rt_motion.h; 0: no moving spheres).  -1: the environment's words would not fit an int32 offset; -2: 2^28 sphere slots or more.
-int lay_out_image(RenderParams &L, const Grid &g, const Scene &s, std::vector<int> &image_word, int &off_media, int &off_motion) {
+// (rt_motion.h; 0: no moving spheres); off_normals: of the NORMALS part (device_scene.h; 0: no triangle has vertex normals).  -1: the environment's words would not fit an int32 offset; -2: 2^28 sphere slots or more.
+int lay_out_image(RenderParams &L, const Grid &g, const Scene &s, std::vector<int> &image_word, int &off_media, int &off_motion,
+                  int &off_normals) {
     // The kernels read the winner's cold record at a 32-bit BYTE offset from the cold table, 16 x its slot (rec_at,
     // render_device.h): the slots end below 2^28.  This is the check that bound rests on; pack_scene refuses with RT_ERR_LIMIT.
     if ((long long)L.ns >= RT_MAX_SPHERE_SLOTS) return -2;
@@ -735,6 +736,15 @@ int lay_out_image(RenderParams &L, const Grid &g, const Scene &s, std::vector<in
         off_motion = off;
         off += RT_MOTION_STRIDE * (int)s.movers.size();
     }
+    // the NORMALS part (smooth shading): three records per triangle, only when a triangle has vertex normals; global
+    // memory only, read by the winner section of the general kernels
+    off_normals = 0;
+    for (const rt_prim &p : s.prims)
+        if (p.type == RT_PRIM_TRIANGLE && tri_has_normals(p)) {
+            off_normals = off;
+            off += 3 * L.nt;
+            break;
+        }
     return off;
 }
 
@@ -1103,6 +1113,19 @@ void write_motion(float *I, const RenderParams &L, const Scene &s, int off_motio
     }
 }
 
+// the triangles' vertex normals in the order of the triangle tables, and in the camera block where they lie (device_scene.h)
+void write_normals(float *I, const RenderParams &L, const Scene &s, const OtherPrims &O, int off_normals) {
+    const int32_t off = off_normals;
+    memcpy(rec4(I, L.off_cam + 5) + 3, &off, 4);
+    for (int k = 0; k < L.nt; ++k) {
+        const rt_prim &p = s.prims[O.tri[k]];
+        float *r = rec4(I, off_normals + 3 * k);
+        const float *n[3] = {p.f, p.f + 3, p.m_inv + 6};
+        for (int c = 0; c < 3; ++c) r[4 * c] = n[c][0], r[4 * c + 1] = n[c][1], r[4 * c + 2] = n[c][2];
+        r[3] = bits(tri_has_normals(p) ? 1 : 0);  // (a flat triangle's records are zeros)
+    }
+}
+
 // the environment's texels and sampling tables, as the host evaluation reads them
 void write_environment(float *I, const RenderParams &L, const Scene &s) {
     const SceneEnvironment &e = *s.env;
@@ -1164,8 +1187,8 @@ bool pack_round(const Scene &s, std::vector<char> &forced, std::vector<float> &i
     L.grid_wide = g.wide ? (nested ? 2 : 1) : 0;
     L.grid_sheet = (!g.cells.empty() && g.n[1] == 1 && !g.wide) ? 1 : 0;
     std::vector<int> image_word;
-    int off_media = 0, off_motion = 0;
-    const int records = lay_out_image(L, g, s, image_word, off_media, off_motion);
+    int off_media = 0, off_motion = 0, off_normals = 0;
+    const int records = lay_out_image(L, g, s, image_word, off_media, off_motion, off_normals);
     if (records < 0) {
         (records == -2 ? note.too_many_slots : note.too_large) = true;
         return true;
@@ -1192,6 +1215,7 @@ bool pack_round(const Scene &s, std::vector<char> &forced, std::vector<float> &i
     if (s.env) write_environment(I, L, s);
     if (!s.media.empty()) write_media(I, L, s, off_media);
     if (!s.movers.empty()) write_motion(I, L, s, off_motion);
+    if (off_normals) write_normals(I, L, s, O, off_normals);
     note.nested = NestedInfo();
     if (nested) {
         note.nested.cells = (int)(g.subs.size() / 16);

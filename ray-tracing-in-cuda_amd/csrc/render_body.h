@@ -1145,7 +1145,59 @@
                 // other texture of the reference ignores them, and acos / atan2 per candidate hit (object.cuh:87-93)
                 // would be the most expensive part of sphere::hit
                 // (QUERY: for every hit, they are part of the record)
-                if (EXT && (QUERY || kind == MK_LAMBERT_IMAGE || kind == MK_LIGHT_IMAGE)) {
+                const bool want_uv = EXT && (QUERY || kind == MK_LAMBERT_IMAGE || kind == MK_LIGHT_IMAGE);
+                // a triangle's area weights (hittable.py:54-58), stated once: of the plane point for (u, v), and -- smooth shading,
+                // DESIGN 7l -- of the vertex normals.  The NORMALS part (device_scene.h) is there only when the scene has a triangle
+                // with vertex normals: where it lies is a wave-uniform word of the camera block, as for the media and the movers.
+                // The shading normal replaces the face-turned geometric one where the material scatters, in a query's record and
+                // in a feature pass; an emitter keeps the geometric normal (its light pdf below reads nx, ny, nz).
+                float w1 = 0.0f, w2 = 0.0f, w3 = 0.0f;
+                if constexpr (EXT) {
+                    if (!(MOTION && mot_i >= 0) && best_id >= ns + nr + nc) {
+                        const int k = best_id - ns - nr - nc;
+                        const int off_nrm = __builtin_amdgcn_readfirstlane(__float_as_int(image[P.off_cam + 5].w));
+                        bool smooth = false;
+                        if (off_nrm != 0 && (QUERY || AOV || kind < MK_LIGHT_SOLID)) smooth = __float_as_int(image[off_nrm + 3 * k].w) != 0;
+                        if (want_uv || smooth) {
+                            const float4 r0 = tri[RT_TRI_STRIDE * k], r1 = tri[RT_TRI_STRIDE * k + 1], r2 = tri[RT_TRI_STRIDE * k + 2];
+                            float rix, riy, riz, root;
+                            tri_plane(r0, r1, r2, rix, riy, riz, root);
+                            const float a1x = rix - r0.x, a1y = riy - r0.y, a1z = riz - r0.z;
+                            const float a2x = rix - r1.x, a2y = riy - r1.y, a2z = riz - r1.z;
+                            const float a3x = rix - r2.x, a3y = riy - r2.y, a3z = riz - r2.z;
+                            float cx, cy, cz, ex, ey, ez;
+                            cross3(a1x, a1y, a1z, a2x, a2y, a2z, cx, cy, cz);
+                            cross3(r2.x - r0.x, r2.y - r0.y, r2.z - r0.z, r2.x - r1.x, r2.y - r1.y, r2.z - r1.z, ex, ey, ez);
+                            w1 = rt_sqrtf(dot3(cx, cy, cz, cx, cy, cz)) / rt_sqrtf(dot3(ex, ey, ez, ex, ey, ez));
+                            cross3(a1x, a1y, a1z, a3x, a3y, a3z, cx, cy, cz);
+                            cross3(r1.x - r0.x, r1.y - r0.y, r1.z - r0.z, r1.x - r2.x, r1.y - r2.y, r1.z - r2.z, ex, ey, ez);
+                            w2 = rt_sqrtf(dot3(cx, cy, cz, cx, cy, cz)) / rt_sqrtf(dot3(ex, ey, ez, ex, ey, ez));
+                            cross3(a3x, a3y, a3z, a2x, a2y, a2z, cx, cy, cz);
+                            cross3(r0.x - r2.x, r0.y - r2.y, r0.z - r2.z, r0.x - r1.x, r0.y - r1.y, r0.z - r1.z, ex, ey, ez);
+                            w3 = rt_sqrtf(dot3(cx, cy, cz, cx, cy, cz)) / rt_sqrtf(dot3(ex, ey, ez, ex, ey, ez));
+                        }
+                        if (smooth) {
+                            // each corner's normal by the area of the sub-triangle OPPOSITE that corner (the barycentric weight
+                            // that is 1 at the corner): w1 is (r, v1, v2) over the whole and goes with n3, w2 is (r, v1, v3) and
+                            // goes with n2, w3 is (r, v3, v2) and goes with n1.  (u, v) above keeps the reference's pairing, u1
+                            // with w1: under that pairing a normal would be n3 at v1 and jump across every edge.)  Normalised,
+                            // turned into the geometric normal's hemisphere; zero or not finite: the geometric normal stays
+                            const float4 *nr3 = image + off_nrm + 3 * k;
+                            const float4 n1 = nr3[0], n2 = nr3[1], n3 = nr3[2];
+                            const float sx = fmaf(n1.x, w3, fmaf(n2.x, w2, n3.x * w1));
+                            const float sy = fmaf(n1.y, w3, fmaf(n2.y, w2, n3.y * w1));
+                            const float sz = fmaf(n1.z, w3, fmaf(n2.z, w2, n3.z * w1));
+                            const float l2 = dot3(sx, sy, sz, sx, sy, sz);
+                            if (l2 > 0.0f && l2 < INFINITY) {
+                                const float inv = 1.0f / rt_sqrtf(l2);
+                                const float ux = inv * sx, uy = inv * sy, uz = inv * sz;
+                                const bool turn = dot3(ux, uy, uz, nx, ny, nz) < 0.0f;
+                                nx = turn ? -ux : ux, ny = turn ? -uy : uy, nz = turn ? -uz : uz;
+                            }
+                        }
+                    }
+                }
+                if (want_uv) {
                     float tu, tv;
                     if ((MOTION && mot_i >= 0) || best_id < ns) {  // get_sphere_uv(outward_normal), object.cuh:87-93
                         const float onx = front ? nx : -nx, ony = front ? ny : -ny, onz = front ? nz : -nz;
@@ -1173,24 +1225,8 @@
                         const float phi = rt_atan2f(opy, opx) + 6.283185482025146484375f;
                         tu = phi / 12.56637096405029296875f;
                         tv = (opz - pr.y) / (pr.z - pr.y);
-                    } else {  // hittable.py:54-58, 233: area weights of the plane point, uv = u1 w1 + u2 w2 + u3 w3
+                    } else {  // hittable.py:233: uv = u1 w1 + u2 w2 + u3 w3, with the area weights from above
                         const int k = best_id - ns - nr - nc;
-                        const float4 r0 = tri[RT_TRI_STRIDE * k], r1 = tri[RT_TRI_STRIDE * k + 1], r2 = tri[RT_TRI_STRIDE * k + 2];
-                        float rix, riy, riz, root;
-                        tri_plane(r0, r1, r2, rix, riy, riz, root);
-                        const float a1x = rix - r0.x, a1y = riy - r0.y, a1z = riz - r0.z;
-                        const float a2x = rix - r1.x, a2y = riy - r1.y, a2z = riz - r1.z;
-                        const float a3x = rix - r2.x, a3y = riy - r2.y, a3z = riz - r2.z;
-                        float cx, cy, cz, ex, ey, ez;
-                        cross3(a1x, a1y, a1z, a2x, a2y, a2z, cx, cy, cz);
-                        cross3(r2.x - r0.x, r2.y - r0.y, r2.z - r0.z, r2.x - r1.x, r2.y - r1.y, r2.z - r1.z, ex, ey, ez);
-                        const float w1 = rt_sqrtf(dot3(cx, cy, cz, cx, cy, cz)) / rt_sqrtf(dot3(ex, ey, ez, ex, ey, ez));
-                        cross3(a1x, a1y, a1z, a3x, a3y, a3z, cx, cy, cz);
-                        cross3(r1.x - r0.x, r1.y - r0.y, r1.z - r0.z, r1.x - r2.x, r1.y - r2.y, r1.z - r2.z, ex, ey, ez);
-                        const float w2 = rt_sqrtf(dot3(cx, cy, cz, cx, cy, cz)) / rt_sqrtf(dot3(ex, ey, ez, ex, ey, ez));
-                        cross3(a3x, a3y, a3z, a2x, a2y, a2z, cx, cy, cz);
-                        cross3(r0.x - r2.x, r0.y - r2.y, r0.z - r2.z, r0.x - r1.x, r0.y - r1.y, r0.z - r1.z, ex, ey, ez);
-                        const float w3 = rt_sqrtf(dot3(cx, cy, cz, cx, cy, cz)) / rt_sqrtf(dot3(ex, ey, ez, ex, ey, ez));
                         const float4 c0 = image[P.off_tri_cold + 2 * k], c1 = image[P.off_tri_cold + 2 * k + 1];
                         tu = fmaf(c1.z, w3, fmaf(c1.x, w2, c0.z * w1));
                         tv = fmaf(c1.w, w3, fmaf(c1.y, w2, c0.w * w1));

@@ -7,6 +7,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <map>
 
 #include "env_read.hpp"
 #include "json.hpp"
@@ -364,8 +365,59 @@ int add_triangle(Scene &s, const float v1[3], const float v2[3], const float v3[
     return (int)s.prims.size() - 1;
 }
 
-// readobj(), taichi-version/main.py:23-41, and the placement of main.py:110-118 (scale * Rot @ x + dis)
+// Smooth shading: the three vertex normals of triangle p, normalised in fp64 and rounded once, into the words
+// a triangle leaves unused (include/rtmi.h, RT_PRIM_TRIANGLE).  False: a normal is zero or not finite.
+static bool store_tri_normals(rt_prim &p, const double n[3][3]) {
+    float *dst[3] = {p.f, p.f + 3, p.m_inv + 6};
+    for (int c = 0; c < 3; ++c) {
+        const double len = v3len(n[c]);
+        if (!(len > 0) || !std::isfinite(len)) return false;
+        // (a vector within fp32 rounding of unit length -- sqrt(3) x 2^-24 -- is one that was stored before: kept bit for bit,
+        //  so that a scene written to JSON and read back has the same normals)
+        const double div = std::fabs(len - 1.0) <= 1.5e-7 ? 1.0 : len;
+        for (int k = 0; k < 3; ++k) dst[c][k] = (float)(n[c][k] / div);
+    }
+    return true;
+}
+
+int add_triangle_normals(Scene &s, const float v1[3], const float v2[3], const float v3[3], const float n1[3], const float n2[3],
+                         const float n3[3], const float uv1[2], const float uv2[2], const float uv3[2], int material) {
+    const float *nn[3] = {n1, n2, n3};
+    double n[3][3];
+    rt_prim probe;
+    memset(&probe, 0, sizeof probe);
+    for (int c = 0; c < 3; ++c)
+        for (int k = 0; k < 3; ++k) n[c][k] = (double)nn[c][k];
+    if (!store_tri_normals(probe, n)) {
+        set_error("triangle vertex normal is zero or not finite");
+        return -RT_ERR_ARG;
+    }
+    const int id = add_triangle(s, v1, v2, v3, uv1, uv2, uv3, material);
+    if (id < 0) return id;
+    store_tri_normals(s.prims[(size_t)id], n);
+    return id;
+}
+
+static thread_local int g_mesh_normals_mode = -1;
+static thread_local float g_mesh_normals_crease = 180.0f;
+void set_mesh_normals_override(int mode, float crease_degrees) { g_mesh_normals_mode = mode, g_mesh_normals_crease = crease_degrees; }
+
 int add_obj(Scene &s, const char *path, int material, float scale, const float matrix[9], const float translate[3]) {
+    return add_obj_normals(s, path, material, scale, matrix, translate, RT_MESH_NORMALS_FLAT, 0.0f);
+}
+
+// readobj(), taichi-version/main.py:23-41, and the placement of main.py:110-118 (scale * Rot @ x + dis); the vertex
+// normals of smooth shading by `mode` (rt_mesh_normals, include/rtmi.h)
+int add_obj_normals(Scene &s, const char *path, int material, float scale, const float matrix[9], const float translate[3], int mode,
+                    float crease_degrees) {
+    if (mode < RT_MESH_NORMALS_FLAT || mode > RT_MESH_NORMALS_SMOOTH) {
+        set_error("mesh normals mode %d (0 flat, 1 file, 2 smooth)", mode);
+        return -RT_ERR_ARG;
+    }
+    if (mode == RT_MESH_NORMALS_SMOOTH && !(crease_degrees >= 0.0f && crease_degrees <= 180.0f)) {
+        set_error("mesh crease angle %g outside [0, 180] degrees", (double)crease_degrees);
+        return -RT_ERR_ARG;
+    }
     FILE *fp = fopen(path, "r");
     if (!fp) {
         set_error("cannot open %s", path);
@@ -373,8 +425,9 @@ int add_obj(Scene &s, const char *path, int material, float scale, const float m
     }
     std::vector<std::array<float, 3>> pts;
     std::vector<std::array<float, 2>> vts;
+    std::vector<std::array<double, 3>> vns;
     struct Corner {
-        long v, t;
+        long v, t, n;
     };
     std::vector<std::array<Corner, 3>> faces;
     char line[1024];
@@ -392,6 +445,10 @@ int add_obj(Scene &s, const char *path, int material, float scale, const float m
             double u, v;
             if (sscanf(p + 2, "%lf %lf", &u, &v) != 2) bad = true;
             else vts.push_back({(float)u, (float)v});
+        } else if (mode == RT_MESH_NORMALS_FILE && p[0] == 'v' && p[1] == 'n' && (p[2] == ' ' || p[2] == '\t')) {
+            double x, y, z;
+            if (sscanf(p + 2, "%lf %lf %lf", &x, &y, &z) != 3) bad = true;
+            else vns.push_back({x, y, z});
         } else if (p[0] == 'f' && (p[1] == ' ' || p[1] == '\t')) {
             std::array<Corner, 3> f;
             char *q = p + 1;
@@ -399,7 +456,7 @@ int add_obj(Scene &s, const char *path, int material, float scale, const float m
             for (; got < 3; ++got) {
                 while (*q == ' ' || *q == '\t') ++q;
                 char *e;
-                long vi = strtol(q, &e, 10), ti = 0;
+                long vi = strtol(q, &e, 10), ti = 0, ni = 0;
                 if (e == q) break;
                 q = e;
                 if (*q == '/') {  // a/t or a/t/n or a//n
@@ -408,11 +465,12 @@ int add_obj(Scene &s, const char *path, int material, float scale, const float m
                     q = e;
                     if (*q == '/') {
                         ++q;
-                        (void)strtol(q, &e, 10);
+                        ni = strtol(q, &e, 10);
+                        if (e != q && ni == 0) ni = -1;  // "0" is written but names nothing: out of range below
                         q = e;
                     }
                 }
-                f[got] = {vi, ti ? ti : vi};  // without vt indices the reference takes texids[face corner]
+                f[got] = {vi, ti ? ti : vi, ni};  // without vt indices the reference takes texids[face corner]
             }
             if (got != 3) bad = true;
             else faces.push_back(f);
@@ -424,11 +482,16 @@ int add_obj(Scene &s, const char *path, int material, float scale, const float m
         set_error("%s:%d: cannot parse this line", path, lineno);
         return -RT_ERR_IO;
     }
-    int added = 0;
-    for (const auto &f : faces) {
+    // the placed corners of every face, then its unit normal and corner angles in fp64 (what add_triangle derives too)
+    struct Face {
         float v[3][3], uv[3][2];
+        double n[3], angle[3];
+    };
+    std::vector<Face> placed(faces.size());
+    for (size_t i = 0; i < faces.size(); ++i) {
+        Face &F = placed[i];
         for (int c = 0; c < 3; ++c) {
-            const long vi = f[c].v, ti = f[c].t;
+            const long vi = faces[i][c].v, ti = faces[i][c].t;
             if (vi < 1 || vi > (long)pts.size()) {
                 set_error("%s: face refers to vertex %ld (have %zu)", path, vi, pts.size());
                 return -RT_ERR_SCENE;
@@ -437,12 +500,87 @@ int add_obj(Scene &s, const char *path, int material, float scale, const float m
             for (int r = 0; r < 3; ++r) {
                 double m = matrix ? (double)matrix[3 * r] * x[0] + (double)matrix[3 * r + 1] * x[1] + (double)matrix[3 * r + 2] * x[2]
                                   : (double)x[r];
-                v[c][r] = (float)((double)scale * m + (translate ? (double)translate[r] : 0.0));
+                F.v[c][r] = (float)((double)scale * m + (translate ? (double)translate[r] : 0.0));
             }
-            uv[c][0] = uv[c][1] = 0.0f;
-            if (ti >= 1 && ti <= (long)vts.size()) uv[c][0] = vts[ti - 1][0], uv[c][1] = vts[ti - 1][1];
+            F.uv[c][0] = F.uv[c][1] = 0.0f;
+            if (ti >= 1 && ti <= (long)vts.size()) F.uv[c][0] = vts[ti - 1][0], F.uv[c][1] = vts[ti - 1][1];
         }
-        int rc = add_triangle(s, v[0], v[1], v[2], uv[0], uv[1], uv[2], material);
+        if (mode == RT_MESH_NORMALS_FLAT) continue;
+        double e[3][3];  // e[c]: from corner c to corner c + 1
+        for (int c = 0; c < 3; ++c)
+            for (int k = 0; k < 3; ++k) e[c][k] = (double)F.v[(c + 1) % 3][k] - (double)F.v[c][k];
+        const double back[3] = {-e[2][0], -e[2][1], -e[2][2]};  // v3 - v1
+        v3cross(e[0], back, F.n);
+        const double len = v3len(F.n);
+        if (!(len > 0) || !std::isfinite(len)) {
+            set_error("%s: face %zu has zero area (or non-finite vertices)", path, i + 1);
+            return -RT_ERR_SCENE;
+        }
+        for (int k = 0; k < 3; ++k) F.n[k] /= len;
+        for (int c = 0; c < 3; ++c) {  // the angle at corner c, between the edges that leave it
+            const double *a = e[c], *b = e[(c + 2) % 3];
+            double x[3];
+            v3cross(a, b, x);
+            F.angle[c] = std::atan2(v3len(x), -(a[0] * b[0] + a[1] * b[1] + a[2] * b[2]));
+        }
+    }
+    // FILE: n -> (scale M)^-T n, up to a positive factor cof(M) n x sign(scale det M)
+    double cof[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, flip = scale < 0.0f ? -1.0 : 1.0;
+    if (matrix) {
+        const float *m = matrix;
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) {
+                const int r1 = (r + 1) % 3, r2 = (r + 2) % 3, c1 = (c + 1) % 3, c2 = (c + 2) % 3;
+                cof[3 * r + c] = (double)m[3 * r1 + c1] * m[3 * r2 + c2] - (double)m[3 * r1 + c2] * m[3 * r2 + c1];
+            }
+        const double det = m[0] * cof[0] + m[1] * cof[1] + m[2] * cof[2];
+        if (det < 0) flip = -flip;
+    }
+    // SMOOTH: the corners that share a placed position
+    std::map<std::array<float, 3>, std::vector<std::pair<int, int>>> at;
+    if (mode == RT_MESH_NORMALS_SMOOTH)
+        for (size_t i = 0; i < placed.size(); ++i)
+            for (int c = 0; c < 3; ++c) at[{placed[i].v[c][0], placed[i].v[c][1], placed[i].v[c][2]}].push_back({(int)i, c});
+    const double cos_crease = std::cos((double)crease_degrees * std::acos(-1.0) / 180.0) - 1e-12;
+    int added = 0;
+    for (size_t i = 0; i < placed.size(); ++i) {
+        const Face &F = placed[i];
+        int rc;
+        if (mode == RT_MESH_NORMALS_FLAT) {
+            rc = add_triangle(s, F.v[0], F.v[1], F.v[2], F.uv[0], F.uv[1], F.uv[2], material);
+        } else {
+            double n[3][3];
+            for (int c = 0; c < 3; ++c) {
+                double *o = n[c];
+                o[0] = F.n[0], o[1] = F.n[1], o[2] = F.n[2];  // a corner without a normal of its own: the face's
+                if (mode == RT_MESH_NORMALS_FILE) {
+                    const long ni = faces[i][c].n;
+                    if (ni == 0) continue;
+                    if (ni < 1 || ni > (long)vns.size()) {
+                        set_error("%s: face refers to normal %ld (have %zu)", path, ni, vns.size());
+                        return -RT_ERR_SCENE;
+                    }
+                    const auto &x = vns[ni - 1];
+                    double t[3];
+                    for (int r = 0; r < 3; ++r) t[r] = flip * (cof[3 * r] * x[0] + cof[3 * r + 1] * x[1] + cof[3 * r + 2] * x[2]);
+                    const double len = v3len(t);
+                    if (len > 0 && std::isfinite(len)) o[0] = t[0] / len, o[1] = t[1] / len, o[2] = t[2] / len;
+                } else {
+                    double sum[3] = {0, 0, 0};
+                    for (const auto &fc : at[{F.v[c][0], F.v[c][1], F.v[c][2]}]) {
+                        const Face &G = placed[(size_t)fc.first];
+                        if (G.n[0] * F.n[0] + G.n[1] * F.n[1] + G.n[2] * F.n[2] < cos_crease) continue;
+                        for (int k = 0; k < 3; ++k) sum[k] += G.angle[fc.second] * G.n[k];
+                    }
+                    const double len = v3len(sum);
+                    if (len > 0 && std::isfinite(len)) o[0] = sum[0] / len, o[1] = sum[1] / len, o[2] = sum[2] / len;
+                }
+            }
+            const float nf[3][3] = {{(float)n[0][0], (float)n[0][1], (float)n[0][2]},
+                                    {(float)n[1][0], (float)n[1][1], (float)n[1][2]},
+                                    {(float)n[2][0], (float)n[2][1], (float)n[2][2]}};
+            rc = add_triangle_normals(s, F.v[0], F.v[1], F.v[2], nf[0], nf[1], nf[2], F.uv[0], F.uv[1], F.uv[2], material);
+        }
         if (rc < 0) return rc;
         ++added;
     }
@@ -840,14 +978,22 @@ int scene_from_json(const char *text, size_t len, Scene &s, const char *base_dir
                             r.fail("%s: \"%s\" must be an array of 2 numbers", where, uk[c]);
                         else u[c][0] = uv->arr[0].num, u[c][1] = uv->arr[1].num;
                     }
+                // vertex normals: all three or none
+                double n[3][3];
+                const char *nk[3] = {"n1", "n2", "n3"};
+                const int have_n = (o.find("n1") != nullptr) + (o.find("n2") != nullptr) + (o.find("n3") != nullptr);
+                if (have_n == 3) r.vec3(o, "n1", where, n[0]), r.vec3(o, "n2", where, n[1]), r.vec3(o, "n3", where, n[2]);
+                else if (have_n != 0) r.fail("%s: \"%s\", \"%s\" and \"%s\" come together", where, nk[0], nk[1], nk[2]);
                 const int mat = r.integer(o, "material", where);
                 if (r.ok) {
-                    float vf[3][3], uf[3][2];
+                    float vf[3][3], uf[3][2], nf[3][3];
                     for (int c = 0; c < 3; ++c) {
-                        for (int k = 0; k < 3; ++k) vf[c][k] = (float)v[c][k];
+                        for (int k = 0; k < 3; ++k) vf[c][k] = (float)v[c][k], nf[c][k] = have_n ? (float)n[c][k] : 0.0f;
                         uf[c][0] = (float)u[c][0], uf[c][1] = (float)u[c][1];
                     }
-                    if (add_triangle(s, vf[0], vf[1], vf[2], uf[0], uf[1], uf[2], mat) < 0) return RT_ERR_SCENE;
+                    const int rc = have_n ? add_triangle_normals(s, vf[0], vf[1], vf[2], nf[0], nf[1], nf[2], uf[0], uf[1], uf[2], mat)
+                                          : add_triangle(s, vf[0], vf[1], vf[2], uf[0], uf[1], uf[2], mat);
+                    if (rc < 0) return RT_ERR_SCENE;
                 }
             } else if (t == "mesh") {  // readobj + placement, taichi-version/main.py:23-41, 110-118
                 const JsonValue *f = o.find("file");
@@ -872,8 +1018,19 @@ int scene_from_json(const char *text, size_t len, Scene &s, const char *base_dir
                     T[0] = (float)d[0], T[1] = (float)d[1], T[2] = (float)d[2];
                     pt = T;
                 }
+                // "normals": "flat" (default) | "file" | "smooth", "crease_angle" in degrees
+                int mode = RT_MESH_NORMALS_FLAT;
+                float crease = 180.0f;
+                if (const JsonValue *nv = o.find("normals")) {
+                    if (nv->is_string() && nv->str == "flat") mode = RT_MESH_NORMALS_FLAT;
+                    else if (nv->is_string() && nv->str == "file") mode = RT_MESH_NORMALS_FILE;
+                    else if (nv->is_string() && nv->str == "smooth") mode = RT_MESH_NORMALS_SMOOTH;
+                    else r.fail("%s: \"normals\" must be \"flat\", \"file\" or \"smooth\"", where);
+                }
+                if (o.find("crease_angle")) crease = (float)r.num(o, "crease_angle", where);
+                if (g_mesh_normals_mode >= 0) mode = g_mesh_normals_mode, crease = g_mesh_normals_crease;
                 if (r.ok) {
-                    const int rc = add_obj(s, resolve(f->str).c_str(), mat, scale, pm, pt);
+                    const int rc = add_obj_normals(s, resolve(f->str).c_str(), mat, scale, pm, pt, mode, crease);
                     if (rc < 0) return -rc;
                 }
             } else {
@@ -1001,6 +1158,14 @@ std::string scene_to_json(const Scene &s) {
             }
             for (int c = 0; c < 3; ++c)
                 o += std::string(", \"") + uk[c] + "\": [" + json_float(p.m_inv[2 * c]) + ", " + json_float(p.m_inv[2 * c + 1]) + "]";
+            if (tri_has_normals(p)) {  // smooth shading
+                const char *nk[3] = {"n1", "n2", "n3"};
+                const float *nv[3] = {p.f, p.f + 3, p.m_inv + 6};
+                for (int c = 0; c < 3; ++c) {
+                    o += std::string(", \"") + nk[c] + "\": ";
+                    put_vec3(o, nv[c]);
+                }
+            }
             break;
         }
         default: break;

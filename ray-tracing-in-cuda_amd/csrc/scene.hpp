@@ -111,6 +111,18 @@ double scene_bound_radius(const Scene &s);  // radius of the bounding sphere of 
 int add_triangle(Scene &s, const float v1[3], const float v2[3], const float v3[3], const float uv1[2], const float uv2[2],
                  const float uv3[2], int material);
 int add_obj(Scene &s, const char *path, int material, float scale, const float matrix[9], const float translate[3]);
+// smooth shading: a triangle with vertex normals; a mesh whose normals come from `mode` (rt_mesh_normals)
+int add_triangle_normals(Scene &s, const float v1[3], const float v2[3], const float v3[3], const float n1[3], const float n2[3],
+                         const float n3[3], const float uv1[2], const float uv2[2], const float uv3[2], int material);
+int add_obj_normals(Scene &s, const char *path, int material, float scale, const float matrix[9], const float translate[3], int mode,
+                    float crease_degrees);
+void set_mesh_normals_override(int mode, float crease_degrees);
+// does triangle p carry vertex normals (any of the nine words non-zero)?
+inline bool tri_has_normals(const rt_prim &p) {
+    for (int k = 0; k < 6; ++k)
+        if (p.f[k] != 0.0f) return true;
+    return p.m_inv[6] != 0.0f || p.m_inv[7] != 0.0f || p.m_inv[8] != 0.0f;
+}
 
 // a medium (scene.cpp): checks the record and appends it -> medium id, or -rt_status
 int add_medium(Scene &s, const rt_medium &m);
