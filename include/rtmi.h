@@ -63,7 +63,10 @@ typedef enum rt_mat_type {
     RT_MAT_LAMBERTIAN = 0,    /* material.cuh:28-56   tex = albedo texture   */
     RT_MAT_METAL = 1,         /* material.cuh:58-75   albedo, fuzz (<=1)     */
     RT_MAT_DIELECTRIC = 2,    /* material.cuh:89-159  ir                     */
-    RT_MAT_DIFFUSE_LIGHT = 3  /* material.cuh:161-182 tex = emission texture */
+    RT_MAT_DIFFUSE_LIGHT = 3, /* material.cuh:161-182 tex = emission texture */
+    /* glossy materials: a GGX microfacet lobe.  They reuse the record's fields:                      */
+    RT_MAT_ROUGH_METAL = 4,   /* albedo = F0, fuzz = roughness in [0, 1]                                       */
+    RT_MAT_PLASTIC = 5        /* texture = body colour, fuzz = roughness in [0, 1], ir = the coat's index (> 1) */
 } rt_mat_type;
 
 typedef enum rt_tex_type {
@@ -83,10 +86,10 @@ typedef struct rt_prim {
 
 typedef struct rt_material {
     int32_t type;     /* rt_mat_type                                         */
-    int32_t texture;  /* lambertian / diffuse_light: texture index, else -1  */
-    float albedo[3];  /* metal                                               */
-    float fuzz;       /* metal, clamped to <= 1 (material.cuh:61)            */
-    float ir;         /* dielectric                                          */
+    int32_t texture;  /* lambertian / diffuse_light / plastic (body colour): texture index, else -1 */
+    float albedo[3];  /* metal; rough_metal: F0                              */
+    float fuzz;       /* metal, clamped to <= 1 (material.cuh:61); rough_metal / plastic: the roughness r in [0, 1] */
+    float ir;         /* dielectric; plastic: the coat's index of refraction */
 } rt_material;
 
 typedef struct rt_texture {
@@ -325,6 +328,13 @@ int rt_scene_add_checker(rt_scene *s, const float even[3], const float odd[3]); 
 int rt_scene_add_lambertian(rt_scene *s, int texture);                         /* -> material id */
 int rt_scene_add_metal(rt_scene *s, const float albedo[3], float fuzz);
 int rt_scene_add_dielectric(rt_scene *s, float ir);
+/* Glossy materials: a GGX lobe with height-correlated Smith masking, sampled through its visible normals.
+ * rough_metal: Schlick Fresnel about F0 = albedo (each component finite and in [0, 1]).  plastic: a diffuse body of the
+ * texture's colour (solid, checker or image) under a clear coat of index ior (finite, > 1).  roughness is finite and in [0, 1]
+ * (alpha = max(roughness^2, 1e-3)); with light sampling on, a vertex of either takes a light sample iff roughness >= 0.05.
+ * Anything else is RT_ERR_ARG.  A scene with either runs the general (triangle / texture) kernels.  -> material id or -rt_status */
+int rt_scene_add_rough_metal(rt_scene *s, const float albedo[3], float roughness);
+int rt_scene_add_plastic(rt_scene *s, int texture, float ior, float roughness);
 int rt_scene_add_diffuse_light(rt_scene *s, int texture);
 int rt_scene_add_sphere(rt_scene *s, const float center[3], float radius, int material); /* -> prim id */
 /* axis: 0 = xy_rect (a=x,b=y,k=z), 1 = xz_rect, 2 = yz_rect */

@@ -86,6 +86,18 @@ inline material_ptr metal(color a, float f) {                                   
     m->type = RT_MAT_METAL, m->albedo = a, m->fuzz = f;
     return m;
 }
+// glossy materials: fuzz holds the roughness, albedo F0, ir the coat's index
+inline material_ptr rough_metal(color f0, float roughness) {
+    auto m = std::make_shared<material>();
+    m->type = RT_MAT_ROUGH_METAL, m->albedo = f0, m->fuzz = roughness;
+    return m;
+}
+inline material_ptr plastic(std::shared_ptr<mytexture> body, float ior = 1.5f, float roughness = 0.3f) {
+    auto m = std::make_shared<material>();
+    m->type = RT_MAT_PLASTIC, m->tex = std::move(body), m->ir = ior, m->fuzz = roughness;
+    return m;
+}
+inline material_ptr plastic(color body, float ior = 1.5f, float roughness = 0.3f) { return plastic(solid_color(body), ior, roughness); }
 inline material_ptr dielectric(float index_of_refraction) {  // material.cuh:91-92
     auto m = std::make_shared<material>();
     m->type = RT_MAT_DIELECTRIC, m->ir = index_of_refraction;
@@ -443,6 +455,8 @@ private:
         case RT_MAT_LAMBERTIAN: id = rt_scene_add_lambertian(s_, texture_id(m->tex)); break;
         case RT_MAT_METAL: id = rt_scene_add_metal(s_, m->albedo.e, m->fuzz); break;
         case RT_MAT_DIELECTRIC: id = rt_scene_add_dielectric(s_, m->ir); break;
+        case RT_MAT_ROUGH_METAL: id = rt_scene_add_rough_metal(s_, m->albedo.e, m->fuzz); break;
+        case RT_MAT_PLASTIC: id = rt_scene_add_plastic(s_, texture_id(m->tex), m->ir, m->fuzz); break;
         default: id = rt_scene_add_diffuse_light(s_, texture_id(m->tex)); break;
         }
         if (id < 0) throw error(-id, "material");

@@ -233,6 +233,8 @@ _sig("rt_scene_add_checker", C.c_int, _p, _f3, _f3)
 _sig("rt_scene_add_lambertian", C.c_int, _p, C.c_int)
 _sig("rt_scene_add_metal", C.c_int, _p, _f3, C.c_float)
 _sig("rt_scene_add_dielectric", C.c_int, _p, C.c_float)
+_sig("rt_scene_add_rough_metal", C.c_int, _p, _f3, C.c_float)
+_sig("rt_scene_add_plastic", C.c_int, _p, C.c_int, C.c_float, C.c_float)
 _sig("rt_scene_add_diffuse_light", C.c_int, _p, C.c_int)
 _sig("rt_scene_add_sphere", C.c_int, _p, _f3, C.c_float, C.c_int)
 _sig("rt_scene_add_rect", C.c_int, _p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int)
@@ -327,6 +329,7 @@ C_SYMBOLS = [
     "rt_scene_load_json", "rt_scene_parse_json", "rt_scene_rtiow", "rt_scene_to_json", "rt_scene_free",
     "rt_scene_new", "rt_scene_set_background", "rt_scene_set_camera", "rt_scene_add_solid_color",
     "rt_scene_add_checker", "rt_scene_add_lambertian", "rt_scene_add_metal", "rt_scene_add_dielectric",
+    "rt_scene_add_rough_metal", "rt_scene_add_plastic",
     "rt_scene_add_diffuse_light", "rt_scene_add_sphere", "rt_scene_add_rect", "rt_scene_add_cylinder",
     "rt_scene_add_image_texture", "rt_scene_add_image_texture_file", "rt_scene_get_image", "rt_scene_add_triangle",
     "rt_scene_add_obj", "rt_scene_add_triangle_normals", "rt_scene_add_obj_normals", "rt_set_mesh_normals_override",
@@ -567,6 +570,16 @@ class Scene:
 
     def metal(self, albedo, fuzz) -> int:
         return _check_id(_lib.rt_scene_add_metal(self._h, _v3(albedo), fuzz), "metal")
+
+    def rough_metal(self, albedo, roughness) -> int:
+        """GGX rough metal: albedo is F0, roughness in [0, 1]; materials() shows it as type 4 with fuzz = roughness."""
+        return _check_id(_lib.rt_scene_add_rough_metal(self._h, _v3(albedo), roughness), "rough_metal")
+
+    def plastic(self, texture_or_color, ior=1.5, roughness=0.3) -> int:
+        """A diffuse body (a colour or a texture id, as lambertian takes) under a clear GGX coat of index ior > 1 (DESIGN 7m);
+        materials() shows it as type 5 with fuzz = roughness and ir = ior."""
+        tex = texture_or_color if isinstance(texture_or_color, int) else self.solid_color(texture_or_color)
+        return _check_id(_lib.rt_scene_add_plastic(self._h, tex, ior, roughness), "plastic")
 
     def dielectric(self, index_of_refraction) -> int:
         return _check_id(_lib.rt_scene_add_dielectric(self._h, index_of_refraction), "dielectric")

@@ -281,6 +281,31 @@ int rt_scene_add_metal(rt_scene *s, const float albedo[3], float fuzz) {
     }
     return add_material(s, RT_MAT_METAL, -1, albedo, fuzz, 0);
 }
+// glossy materials: the record's fuzz holds the roughness, albedo is F0, ir the coat's index
+static int add_glossy(rt_scene *s, const rt_material &m, const char *where) {
+    if (bad_scene(s, where)) return -RT_ERR_ARG;
+    if (!glossy_material_ok(m, s->s.texs.size(), where)) return -RT_ERR_ARG;
+    s->s.mats.push_back(m);
+    s->s.touch();
+    return (int)s->s.mats.size() - 1;
+}
+int rt_scene_add_rough_metal(rt_scene *s, const float albedo[3], float roughness) {
+    if (!albedo) {
+        set_error("rt_scene_add_rough_metal: albedo is null");
+        return -RT_ERR_ARG;
+    }
+    rt_material m;
+    memset(&m, 0, sizeof m);
+    m.type = RT_MAT_ROUGH_METAL, m.texture = -1, m.fuzz = roughness;
+    memcpy(m.albedo, albedo, sizeof m.albedo);
+    return add_glossy(s, m, "rt_scene_add_rough_metal");
+}
+int rt_scene_add_plastic(rt_scene *s, int texture, float ior, float roughness) {
+    rt_material m;
+    memset(&m, 0, sizeof m);
+    m.type = RT_MAT_PLASTIC, m.texture = texture, m.ir = ior, m.fuzz = roughness;
+    return add_glossy(s, m, "rt_scene_add_plastic");
+}
 int rt_scene_add_dielectric(rt_scene *s, float ir) { return add_material(s, RT_MAT_DIELECTRIC, -1, nullptr, 0, ir); }
 int rt_scene_add_diffuse_light(rt_scene *s, int texture) {
     return add_material(s, RT_MAT_DIFFUSE_LIGHT, texture, nullptr, 0, 0);

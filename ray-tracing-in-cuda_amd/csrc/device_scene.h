@@ -84,7 +84,13 @@ enum MatKind : int32_t {
     MK_LIGHT_SOLID = 5,      // c0 = emission
     MK_LIGHT_CHECKER = 6,    // c0 = even, c1 = odd
     MK_LIGHT_IMAGE = 7,      // as MK_LAMBERT_IMAGE
-    MK_MEDIUM = 8            // a medium event of the media kernels (rt_media.h): no material record, `mat` is the medium's index
+    MK_MEDIUM = 8,           // a medium event of the media kernels (rt_media.h): no material record, `mat` is the medium's index
+    // glossy materials (rt_glossy.h), in the general (EXT) builds alone.  p0 = alpha = max(r^2, 1e-3), p2 = the
+    // roughness r itself (what the light-sample threshold is asked of)
+    MK_ROUGH_METAL = 9,      // c0 = F0
+    MK_PLASTIC_SOLID = 10,   // p1 = r0 of the coat, c0 = body colour
+    MK_PLASTIC_CHECKER = 11, // p1 = r0, c0 = even, c1 = odd
+    MK_PLASTIC_IMAGE = 12    // p1 = r0, c0 as MK_LAMBERT_IMAGE
 };
 
 // Per-launch values the kernel needs only when a wave fetches or flushes a work item.  They live in global

@@ -1005,6 +1005,26 @@ void write_materials(float *I, const RenderParams &L, const Scene &s, const Sphe
             q[1] = ir, q[2] = inv_ir, q[3] = r0f, q[7] = r0b;
             break;
         }
+        case RT_MAT_ROUGH_METAL:  // alpha = max(r^2, 1e-3), and r itself for the light-sample threshold
+            kind = MK_ROUGH_METAL;
+            q[1] = std::max(m.fuzz * m.fuzz, 1e-3f), q[3] = m.fuzz;
+            q[4] = m.albedo[0], q[5] = m.albedo[1], q[6] = m.albedo[2];
+            break;
+        case RT_MAT_PLASTIC: {
+            float r0 = (m.ir - 1.0f) / (m.ir + 1.0f);
+            r0 = r0 * r0;
+            q[1] = std::max(m.fuzz * m.fuzz, 1e-3f), q[2] = r0, q[3] = m.fuzz;
+            kind = (t && t->type == RT_TEX_CHECKER) ? MK_PLASTIC_CHECKER : MK_PLASTIC_SOLID;
+            if (t && t->type == RT_TEX_IMAGE) {
+                kind = MK_PLASTIC_IMAGE;
+                const size_t im = (size_t)t->c0[0];
+                q[4] = bits(image_word[im]), q[5] = bits(s.images[im].rows), q[6] = bits(s.images[im].cols);
+            } else if (t) {
+                q[4] = t->c0[0], q[5] = t->c0[1], q[6] = t->c0[2];
+                q[8] = t->c1[0], q[9] = t->c1[1], q[10] = t->c1[2];
+            }
+            break;
+        }
         default: break;
         }
         q[0] = bits(kind);
@@ -1159,7 +1179,8 @@ bool pack_round(const Scene &s, std::vector<char> &forced, std::vector<float> &i
         default: rec.push_back((int)i); break;
         }
     }
-    const bool sphere_only = rec.empty() && cyl.empty() && tri.empty() && s.images.empty();
+    // (a glossy material, DESIGN 7m, runs in the general kernels alone, as an image texture does)
+    const bool sphere_only = rec.empty() && cyl.empty() && tri.empty() && s.images.empty() && !scene_has_glossy(s);
     const SphereSlots S = sphere_slots(s, std::move(sph), forced);
     const OtherPrims O = other_prims(s, S, std::move(rec), std::move(cyl), std::move(tri), forced);
     // light sampling runs in the general kernels alone (render_nee_kernel: the linear scan and the wide-table walks), so a

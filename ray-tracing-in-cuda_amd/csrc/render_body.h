@@ -1145,7 +1145,7 @@
                 // other texture of the reference ignores them, and acos / atan2 per candidate hit (object.cuh:87-93)
                 // would be the most expensive part of sphere::hit
                 // (QUERY: for every hit, they are part of the record)
-                const bool want_uv = EXT && (QUERY || kind == MK_LAMBERT_IMAGE || kind == MK_LIGHT_IMAGE);
+                const bool want_uv = EXT && (QUERY || kind == MK_LAMBERT_IMAGE || kind == MK_LIGHT_IMAGE || kind == MK_PLASTIC_IMAGE);
                 // a triangle's area weights (hittable.py:54-58), stated once: of the plane point for (u, v), and -- smooth shading,
                 // DESIGN 7l -- of the vertex normals.  The NORMALS part (device_scene.h) is there only when the scene has a triangle
                 // with vertex normals: where it lies is a wave-uniform word of the camera block, as for the media and the movers.
@@ -1157,7 +1157,7 @@
                         const int k = best_id - ns - nr - nc;
                         const int off_nrm = __builtin_amdgcn_readfirstlane(__float_as_int(image[P.off_cam + 5].w));
                         bool smooth = false;
-                        if (off_nrm != 0 && (QUERY || AOV || kind < MK_LIGHT_SOLID)) smooth = __float_as_int(image[off_nrm + 3 * k].w) != 0;
+                        if (off_nrm != 0 && (QUERY || AOV || kind < MK_LIGHT_SOLID || kind >= MK_ROUGH_METAL)) smooth = __float_as_int(image[off_nrm + 3 * k].w) != 0;
                         if (want_uv || smooth) {
                             const float4 r0 = tri[RT_TRI_STRIDE * k], r1 = tri[RT_TRI_STRIDE * k + 1], r2 = tri[RT_TRI_STRIDE * k + 2];
                             float rix, riy, riz, root;
@@ -1241,8 +1241,9 @@
                 }
                 if (COUNT) {
                     c_hits++;
-                    if (kind <= MK_LAMBERT_IMAGE) c_scatter0++;
-                    else if (kind == MK_METAL) c_scatter1++;
+                    // (the glossy materials, DESIGN 7m: plastic counts with the lambertians, rough metal with the metals)
+                    if (kind <= MK_LAMBERT_IMAGE || (EXT && kind >= MK_PLASTIC_SOLID)) c_scatter0++;
+                    else if (kind == MK_METAL || (EXT && kind == MK_ROUGH_METAL)) c_scatter1++;
                     else if (kind == MK_DIELECTRIC) c_scatter2++;
                     else c_scatter3++;
                 }
@@ -1253,9 +1254,10 @@
                     // the texture value under the hit (metal: its albedo, dielectric: white), the face-turned normal, or (t, 1, 0)
                     if (P.feature == RT_FEATURE_ALBEDO) {
                         const float4 q1 = M[1], q2 = M[2];
-                        const bool odd = (kind == MK_LAMBERT_CHECKER || kind == MK_LIGHT_CHECKER) && checker_odd(px, py, pz);
+                        // (rough metal: F0, where metal keeps its albedo; plastic: the body's texture)
+                        const bool odd = (kind == MK_LAMBERT_CHECKER || kind == MK_LIGHT_CHECKER || kind == MK_PLASTIC_CHECKER) && checker_odd(px, py, pz);
                         L_r = odd ? q2.x : q1.x, L_g = odd ? q2.y : q1.y, L_b = odd ? q2.z : q1.z;
-                        if (kind == MK_LAMBERT_IMAGE || kind == MK_LIGHT_IMAGE) L_r = tex_r, L_g = tex_g, L_b = tex_b;
+                        if (kind == MK_LAMBERT_IMAGE || kind == MK_LIGHT_IMAGE || kind == MK_PLASTIC_IMAGE) L_r = tex_r, L_g = tex_g, L_b = tex_b;
                         if (kind == MK_DIELECTRIC) L_r = L_g = L_b = 1.0f;
                     } else if (P.feature == RT_FEATURE_NORMAL) {
                         L_r = nx, L_g = ny, L_b = nz;
@@ -1265,7 +1267,7 @@
                     path_done = true;
                     kind = -1;
                 } else
-                if (kind >= MK_LIGHT_SOLID) {  // diffuse_light: emitted, never scatters (material.cuh:161-182, main.cu:48-58)
+                if (kind >= MK_LIGHT_SOLID && (!EXT || kind <= MK_LIGHT_IMAGE)) {  // diffuse_light: emitted, never scatters (material.cuh:161-182, main.cu:48-58)
                     const float4 q1 = M[1], q2 = M[2];
                     const bool odd = kind == MK_LIGHT_CHECKER && checker_odd(px, py, pz);
                     float er = odd ? q2.x : q1.x, eg = odd ? q2.y : q1.y, eb = odd ? q2.z : q1.z;
@@ -1576,6 +1578,8 @@
         // absorbed metal vertex), the throughput the continuation carries, the metal's reflected direction and fuzz (0: lambertian)
         bool nee_v = false, nee_end = false;
         float vb_r = 0, vb_g = 0, vb_b = 0, mrx = 0, mry = 0, mrz = 0, mfz = 0;
+        float glossy_pdf = 0;  // (EXT, NEE) pdf_b of the direction a glossy vertex drew
+        uint32_t gtex = 0u;    // (EXT, NEE) an image-textured plastic vertex: its texel, 8 bits a channel, for the light-sample step
         if (!QUERY && kind >= 0) {
             const float4 *M = rec_at(image + P.off_mat, __umul24((uint32_t)mat, 48u));  // (below 2^24 materials: scene_validate)
             if constexpr (MEDIA) {  // (a medium's record 1 is {albedo, density}: where a material keeps c0)
@@ -1601,6 +1605,45 @@
                     at_r = q1.x, at_g = q1.y, at_b = q1.z;
                     if (NEE) mrx = rx, mry = ry, mrz = rz, mfz = q0.y;
                     scattered = dot3(ndx, ndy, ndz, nx, ny, nz) > 0.0f;
+                } else if (EXT && kind >= MK_ROUGH_METAL) {
+                    // the glossy materials (rt_glossy.h): two draws for the lobe's visible normal, plastic one more
+                    // in front of them for the choice between coat and body.  A vertex seen from below its shading normal
+                    // (wo.z <= 0) is absorbed without a draw and takes no light sample; one whose direction comes out below
+                    // (wi.z <= 0) is absorbed as a metal vertex is.
+                    const float ux = inv_len * dx, uy = inv_len * dy, uz = inv_len * dz;
+                    float gpdf = 0.0f;
+                    bool below = false, lobe = false;
+                    at_r = at_g = at_b = 0.0f, ndx = ndy = ndz = 0.0f;
+                    if (-dot3(ux, uy, uz, nx, ny, nz) > 0.0f) {
+                        const bool plastic = kind != MK_ROUGH_METAL;
+                        // F0, or the coat's r0 in every channel with the body's colour beside it
+                        float f_r = q1.x, f_g = q1.y, f_b = q1.z, rh_r = 0.0f, rh_g = 0.0f, rh_b = 0.0f, ul = 0.0f;
+                        if (plastic) {
+                            const bool odd = kind == MK_PLASTIC_CHECKER && checker_odd(px, py, pz);
+                            rh_r = odd ? q2.x : q1.x, rh_g = odd ? q2.y : q1.y, rh_b = odd ? q2.z : q1.z;
+                            if (kind == MK_PLASTIC_IMAGE) rh_r = tex_r, rh_g = tex_g, rh_b = tex_b;
+                            f_r = f_g = f_b = q0.z;
+                            ul = rng_next<COUNT>(rng);
+                        }
+                        const float u1 = rng_next<COUNT>(rng), u2 = rng_next<COUNT>(rng);
+                        scattered = glossy_sample(plastic, nx, ny, nz, ux, uy, uz, q0.y, f_r, f_g, f_b, rh_r, rh_g, rh_b, ul, u1, u2, ndx, ndy,
+                                                  ndz, at_r, at_g, at_b, gpdf, below, lobe);
+                    } else {
+                        scattered = false, below = true;
+                    }
+                    if (NEE) {
+                        // the light sample's f cos is not albedo x pdf_b here: step (7) evaluates the material for the light's
+                        // direction, from -unit(d) (kept where metal keeps its mirror direction) and the throughput in FRONT
+                        // of this vertex.  Where metal keeps its fuzz, a NEGATIVE number says "glossy" and carries in its bits what
+                        // that step needs to find the material again -- sign | below << 30 | kind << 24 | material (below 2^24:
+                        // scene_validate; a small normal number, never a NaN) -- so that neither kind nor mat nor the texel's
+                        // three floats stay live across the roulette section and the light's sample
+                        mrx = ux, mry = uy, mrz = uz;
+                        mfz = __uint_as_float(0x80000000u | (below ? 0x40000000u : 0u) | ((uint32_t)kind << 24) | (uint32_t)mat);
+                        if (kind == MK_PLASTIC_IMAGE)
+                            gtex = (uint32_t)fmaf(tex_r, 255.0f, 0.5f) | (uint32_t)fmaf(tex_g, 255.0f, 0.5f) << 8 | (uint32_t)fmaf(tex_b, 255.0f, 0.5f) << 16;
+                        glossy_pdf = gpdf;
+                    }
                 } else {  // dielectric::scatter, material.h:66-95
                     const float ratio = front ? q0.z : q0.y;
                     const float ux = inv_len * dx, uy = inv_len * dy, uz = inv_len * dz;
@@ -1632,7 +1675,12 @@
                 // light-sampled vertices: lambertian, and metal fuzzy enough for its lobe to meet a light; the continuation's pdf
                 // is kept for the MIS weight of an emitter it hits
                 nee_v = kind <= MK_LAMBERT_IMAGE || (kind == MK_METAL && q0.y >= 0.05f);
+                const bool glossy = EXT && mfz < 0.0f;
+                if (glossy) nee_v = q0.w >= RT_GLOSSY_MIN_ROUGHNESS && (__float_as_uint(mfz) & 0x40000000u) == 0u;
                 float cpdf = -1.0f;
+                if (glossy) {
+                    if (nee_v && scattered) cpdf = glossy_pdf;
+                } else
                 if (nee_v && scattered) {
                     const float il = 1.0f / sqrtf(dot3(ndx, ndy, ndz, ndx, ndy, ndz));
                     const float wx = ndx * il, wy = ndy * il, wz = ndz * il;
@@ -1640,6 +1688,7 @@
                 }
                 mis_pdf = cpdf;
                 vb_r = beta_r * at_r, vb_g = beta_g * at_g, vb_b = beta_b * at_b;
+                if (glossy) vb_r = beta_r, vb_g = beta_g, vb_b = beta_b;
                 // an absorbed metal vertex still samples its light when its continuation would have been traced: the light
                 // sample may not depend on the direction the BSDF drew
                 nee_end = !scattered;
@@ -1714,6 +1763,9 @@
                 }
             } else {
                 nee_v = active;
+                if (EXT && mfz < 0.0f) {  // (a glossy vertex: the throughput in front of it, the roulette's division included)
+                    if (P.rr_p > 0.0f) vb_r = vb_r / P.rr_p, vb_g = vb_g / P.rr_p, vb_b = vb_b / P.rr_p;
+                } else
                 vb_r = beta_r, vb_g = beta_g, vb_b = beta_b;
             }
         }
@@ -1749,9 +1801,8 @@
                     const float c = sqrtf(c2), ic = 1.0f / c;
                     const float ax = wx * ic, ay = wy * ic, az = wz * ic;
                     // orthonormal frame around the axis (Duff et al. 2017)
-                    const float sg = copysignf(1.0f, az), fa = -1.0f / (sg + az), fb = ax * ay * fa;
-                    const float t1x = fmaf(sg * ax * ax, fa, 1.0f), t1y = sg * fb, t1z = -sg * ax;
-                    const float t2x = fb, t2y = fmaf(ay * ay, fa, sg), t2z = -ay;
+                    float t1x, t1y, t1z, t2x, t2y, t2z;
+                    duff_frame(ax, ay, az, t1x, t1y, t1z, t2x, t2y, t2z);
                     const float s1 = sth * cp, s2 = sth * sp;
                     const float ex = fmaf(s1, t1x, fmaf(s2, t2x, cth * ax));
                     const float ey = fmaf(s1, t1y, fmaf(s2, t2y, cth * ay));
@@ -1788,9 +1839,34 @@
             const float wx = ldx * il, wy = ldy * il, wz = ldz * il;
             const float wn = dot3(wx, wy, wz, nx, ny, nz);
             float pb = 0.0f;
+            float gf_r = 1.0f, gf_g = 1.0f, gf_b = 1.0f;  // a glossy vertex: f cos of the light's direction
+            const bool glossy = EXT && mfz < 0.0f;
+            if (glossy) {
+                // the material again, from its record and the hit (the frame is rebuilt from n: nothing of it is kept live
+                // across the roulette section); which record and which kind: the bits of mfz
+                const uint32_t gbits = __float_as_uint(mfz);
+                const int gkind = (int)((gbits >> 24) & 15u);
+                const float4 *M = rec_at(image + P.off_mat, __umul24(gbits & 0xffffffu, 48u));
+                const float4 q0 = M[0], q1 = M[1], q2 = M[2];
+                const bool plastic = gkind != MK_ROUGH_METAL;
+                float f_r = q1.x, f_g = q1.y, f_b = q1.z, rh_r = 0.0f, rh_g = 0.0f, rh_b = 0.0f;
+                if (plastic) {
+                    const bool odd = gkind == MK_PLASTIC_CHECKER && checker_odd(px, py, pz);
+                    rh_r = odd ? q2.x : q1.x, rh_g = odd ? q2.y : q1.y, rh_b = odd ? q2.z : q1.z;
+                    if (gkind == MK_PLASTIC_IMAGE)  // (the texel as image_texel made it: the same byte over 255)
+                        rh_r = (float)(gtex & 255u) / 255.0f, rh_g = (float)((gtex >> 8) & 255u) / 255.0f, rh_b = (float)((gtex >> 16) & 255u) / 255.0f;
+                    f_r = f_g = f_b = q0.z;
+                }
+                glossy_eval(plastic, nx, ny, nz, mrx, mry, mrz, q0.y, f_r, f_g, f_b, rh_r, rh_g, rh_b, wx, wy, wz, gf_r, gf_g, gf_b, pb);
+            } else
             if (wn > 0.0f) pb = mfz > 0.0f ? metal_pdf(wx, wy, wz, mrx, mry, mrz, mfz) : wn * kInvPi;
             // f cos / p_l x the power heuristic's p_l^2 / (p_l^2 + pdf_b^2) = albedo x pdf_b p_l / (p_l^2 + pdf_b^2)
-            const float wgt = (pl > 0.0f && pb > 0.0f && d2 > 0.0f) ? pb / (pl + pb * (pb / pl)) : 0.0f;
+            // (glossy: f cos x p_l / (p_l^2 + pdf_b^2), f cos per channel)
+            float wgt = (pl > 0.0f && pb > 0.0f && d2 > 0.0f) ? pb / (pl + pb * (pb / pl)) : 0.0f;
+            if (glossy) {
+                wgt = (pl > 0.0f && pb > 0.0f && d2 > 0.0f) ? 1.0f / (pl + pb * (pb / pl)) : 0.0f;
+                vb_r *= gf_r, vb_g *= gf_g, vb_b *= gf_b;
+            }
             if (wgt > 0.0f) {
                 const float lx = px + ldx, ly = py + ldy, lz = pz + ldz;
                 const float4 e0 = lr[1], e1 = lr[2];

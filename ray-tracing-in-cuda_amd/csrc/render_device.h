@@ -214,6 +214,11 @@ __device__ __forceinline__ unsigned long long radiance_to_fixed(float v) {
     return v < 0.0f ? 0ull - m : m;
 }
 
+// the glossy materials: behind rt_sqrtf, which they use
+}  // namespace rtmi
+#include "rt_glossy.h"
+namespace rtmi {
+
 // ---------------------------------------------------------------- light sampling (render_nee_kernel)
 static constexpr float kPi = 3.14159265358979323846f, kInvPi = 0.318309886183790671538f;
 

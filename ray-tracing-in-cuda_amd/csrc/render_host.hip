@@ -614,6 +614,7 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     // triangles and image textures live in separate builds of the kernels (template argument EXT)
     bool ext = !s.images.empty();
     for (const rt_prim &p : s.prims) ext = ext || p.type == RT_PRIM_TRIANGLE;
+    ext = ext || scene_has_glossy(s);  // (the glossy materials' code sits in those builds alone)
     const bool force_ext = knob_set("RTMI_FORCE_EXT");  // measurement: the EXT builds on scenes that do not need them
     const int device = o ? o->device : 0;
     DeviceScope scope;

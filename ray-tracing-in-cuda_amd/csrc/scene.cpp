@@ -143,6 +143,30 @@ int add_cylinder(Scene &s, float radius, float zmin, float zmax, int material, c
 }
 
 // ---------------------------------------------------------------- validation
+bool glossy_material_ok(const rt_material &m, size_t textures, const char *where) {
+    if (!(m.fuzz >= 0.0f && m.fuzz <= 1.0f)) {  // (a NaN fails the comparison)
+        set_error("%s: roughness must be finite and in [0, 1] (got %g)", where, (double)m.fuzz);
+        return false;
+    }
+    if (m.type == RT_MAT_ROUGH_METAL) {
+        for (int k = 0; k < 3; ++k)
+            if (!(m.albedo[k] >= 0.0f && m.albedo[k] <= 1.0f)) {
+                set_error("%s: rough_metal albedo (F0) components must be finite and in [0, 1] (got %g)", where, (double)m.albedo[k]);
+                return false;
+            }
+    } else {
+        if (!(m.ir > 1.0f && m.ir < INFINITY)) {
+            set_error("%s: plastic ior must be finite and > 1 (got %g)", where, (double)m.ir);
+            return false;
+        }
+        if (m.texture < 0 || (size_t)m.texture >= textures) {
+            set_error("%s references texture %d (have %zu)", where, m.texture, textures);
+            return false;
+        }
+    }
+    return true;
+}
+
 int scene_validate(const Scene &s) {
     if (s.width < 2 || s.height < 2) {
         // u = (x + xi) / (W - 1), main.cu:97-98: W = 1 divides by zero
@@ -173,6 +197,10 @@ int scene_validate(const Scene &s) {
                 set_error("material %zu references texture %d (have %zu)", i, m.texture, s.texs.size());
                 return RT_ERR_SCENE;
             }
+        } else if (is_glossy(m)) {
+            char where[32];
+            snprintf(where, sizeof where, "material %zu", i);
+            if (!glossy_material_ok(m, s.texs.size(), where)) return RT_ERR_SCENE;
         }
     }
     for (size_t i = 0; i < s.texs.size(); ++i) {
@@ -869,6 +897,13 @@ int scene_from_json(const char *text, size_t len, Scene &s, const char *base_dir
             rt_material rec;
             memset(&rec, 0, sizeof rec);
             rec.texture = -1;
+            auto only_keys = [&](const JsonValue &o, std::initializer_list<const char *> known) {  // (the glossy materials: a misspelt field is an error)
+                for (const auto &kv : o.obj) {
+                    bool found = false;
+                    for (const char *k : known) found = found || kv.first == k;
+                    if (!found) r.fail("%s: unknown field \"%s\"", where, kv.first.c_str());
+                }
+            };
             if (ty->str == "lambertian") {
                 rec.type = RT_MAT_LAMBERTIAN;
                 rec.texture = r.integer(m, "texture", where);
@@ -879,6 +914,21 @@ int scene_from_json(const char *text, size_t len, Scene &s, const char *base_dir
                 for (int k = 0; k < 3; ++k) rec.albedo[k] = (float)c[k];
                 float f = (float)r.num(m, "fuzz", where);
                 rec.fuzz = f < 1 ? f : 1;  // material.cuh:61
+            } else if (ty->str == "rough_metal") {  // albedo is F0, fuzz holds the roughness
+                rec.type = RT_MAT_ROUGH_METAL;
+                only_keys(m, {"type", "albedo", "roughness"});
+                double c[3];
+                r.vec3(m, "albedo", where, c);
+                for (int k = 0; k < 3; ++k) rec.albedo[k] = (float)c[k];
+                rec.fuzz = (float)r.num(m, "roughness", where);
+                if (r.ok && !glossy_material_ok(rec, s.texs.size(), where)) r.ok = false;
+            } else if (ty->str == "plastic") {  // texture is the body colour, fuzz the roughness, ir the coat's index
+                rec.type = RT_MAT_PLASTIC;
+                only_keys(m, {"type", "texture", "ior", "roughness"});
+                rec.texture = r.integer(m, "texture", where);
+                rec.ir = (float)r.num(m, "ior", where);
+                rec.fuzz = (float)r.num(m, "roughness", where);
+                if (r.ok && !glossy_material_ok(rec, s.texs.size(), where)) r.ok = false;
             } else if (ty->str == "dielectric") {
                 rec.type = RT_MAT_DIELECTRIC;
                 rec.ir = (float)r.num(m, "index_of_refraction", where);
@@ -1199,6 +1249,15 @@ std::string scene_to_json(const Scene &s) {
             break;
         case RT_MAT_DIFFUSE_LIGHT:
             o += "{\"type\": \"diffuse_light\", \"texture\": " + std::to_string(m.texture) + "}";
+            break;
+        case RT_MAT_ROUGH_METAL:
+            o += "{\"type\": \"rough_metal\", \"albedo\": ";
+            put_vec3(o, m.albedo);
+            o += ", \"roughness\": " + json_float(m.fuzz) + "}";
+            break;
+        case RT_MAT_PLASTIC:
+            o += "{\"type\": \"plastic\", \"texture\": " + std::to_string(m.texture) + ", \"ior\": " + json_float(m.ir) +
+                 ", \"roughness\": " + json_float(m.fuzz) + "}";
             break;
         default: break;
         }

@@ -124,6 +124,16 @@ inline bool tri_has_normals(const rt_prim &p) {
     return p.m_inv[6] != 0.0f || p.m_inv[7] != 0.0f || p.m_inv[8] != 0.0f;
 }
 
+// glossy materials: does the material table hold one (such a scene runs the general kernels over the wide tables);
+// is a rough_metal / plastic record within its argument rules (false: the message is set, prefixed with `where`)
+inline bool is_glossy(const rt_material &m) { return m.type == RT_MAT_ROUGH_METAL || m.type == RT_MAT_PLASTIC; }
+inline bool scene_has_glossy(const Scene &s) {
+    for (const rt_material &m : s.mats)
+        if (is_glossy(m)) return true;
+    return false;
+}
+bool glossy_material_ok(const rt_material &m, size_t textures, const char *where);
+
 // a medium (scene.cpp): checks the record and appends it -> medium id, or -rt_status
 int add_medium(Scene &s, const rt_medium &m);
 // a moving sphere (scene.cpp): checks the record and appends it -> mover id, or -rt_status
