@@ -5,7 +5,8 @@ Every case uses the frame, sample count, seed and draw budget of nee_scenes.REF_
 16 848 samples; the media and motion cases use their families' seed through ext_scenes.seed_of's rule).  Roughnesses are
 {0.15, 0.4, 0.8} and one material at 0.02, below the light-sample threshold.  A builder called with glossy=False builds the
 case's TWIN: every rough_metal replaced by lambertian(F0) and every plastic by lambertian of its texture -- the geometry the
-plain kernel is pinned on, the baseline of criterion (b).
+plain kernel is pinned on, the baseline of criterion (b).  The reference of a case or of its twin is ref64.reference /
+ref64.trace on its RefScene, called plainly: glossy_mesh's shading normals come with ref64's hit record.
 
 What was adjusted, and why (the fp64 and fp32 references were run on the CPU on every case before it was fixed; a case stays
 only if the fp32 reference alone meets criterion (a) with at most 1 % of the samples flipping a branch):
@@ -151,15 +152,15 @@ def motion(rtmi, glossy=True):
     return sc
 
 
-# name -> (family bits the kernel must report, builder, light sampling on, smooth normals, the glossy_tally keys it is there for)
+# name -> (family bits the kernel must report, builder, light sampling on, the glossy keys of ref64.tally() it is there for)
 CASES = {
-    "glossy_sky": (0, sky, False, False, ("rough_vertices", "coat_vertices", "body_vertices")),
-    "glossy_mesh": (0, mesh, False, True, ("coat_vertices", "body_vertices", "rough_vertices")),
-    "glossy_lights": (NEE, lights, True, False, ("glossy_light_samples", "smooth_glossy_vertices", "smooth_glossy_full_weight_hits",
-                                                   "absorbed_wi_light_samples", "roulette_losses")),
-    "glossy_env": (ENV | NEE, env, True, False, ("glossy_env_picks", "glossy_escapes_after_light_sample")),
-    "glossy_fog": (MEDIA, fog, False, False, ("medium_then_glossy", "glossy_then_medium")),
-    "glossy_motion": (MOTION, motion, False, False, ("glossy_mover_vertices", "glossy_static_vertices")),
+    "glossy_sky": (0, sky, False, ("rough_vertices", "coat_vertices", "body_vertices")),
+    "glossy_mesh": (0, mesh, False, ("coat_vertices", "body_vertices", "rough_vertices")),
+    "glossy_lights": (NEE, lights, True, ("glossy_light_samples", "smooth_glossy_vertices", "smooth_glossy_full_weight_hits",
+                                            "absorbed_wi_light_samples", "roulette_losses")),
+    "glossy_env": (ENV | NEE, env, True, ("glossy_env_picks", "glossy_escapes_after_light_sample")),
+    "glossy_fog": (MEDIA, fog, False, ("medium_then_glossy", "glossy_then_medium")),
+    "glossy_motion": (MOTION, motion, False, ("glossy_mover_vertices", "glossy_static_vertices")),
 }
 
 
@@ -194,26 +195,11 @@ def inputs(rtmi, name):
     return words, shutter
 
 
-def reference(name, S, words, shutter=None):
-    """ref64_glossy.reference, under the shading normal where the case has vertex normals"""
-    if CASES[name][3]:
-        with SM.smooth_reference():
-            return G.reference(S, words, shutter)
-    return G.reference(S, words, shutter)
-
-
-def traced(name, S, words, shutter=None, **kw):
-    if CASES[name][3]:
-        with SM.smooth_reference():
-            return G.trace(S, words, shutter=shutter, **kw)
-    return G.trace(S, words, shutter=shutter, **kw)
-
-
 def check_contents(name, tally):
     """the case met the vertices it is there for, each at least once per hundred samples (nee_scenes.REQUIRED_EVENTS) -- but the
     absorbed-by-wo vertices of glossy_mesh, which only a grazing ray on a smooth-shaded face makes: at least one, as the case's
     definition asks -- and every roughness it names"""
-    for what in CASES[name][4]:
+    for what in CASES[name][3]:
         assert tally[what] >= NS.REQUIRED_EVENTS, (name, what, tally[what])
     if name == "glossy_mesh":
         assert tally["below_vertices"] >= 1 and tally["below_light_samples"] == 0, tally

@@ -22,13 +22,16 @@ def gpu_package():
     return mod
 
 
-def kernel_samples(rtmi, sc, seed, k, mask, family):
-    """[k x H x W][3]: the radiance of every sample, from one-sample frames; the kernel family is checked on each"""
+def kernel_samples(rtmi, sc, seed, k, mask, family, variant=0):
+    """[k x H x W][3]: the radiance of every sample, from one-sample frames; the kernel family is checked on each, and the
+    layout where one is asked for (variant: 0 is the scene's own)"""
     out = []
     for i in range(k):
         st = rtmi.Stats()
-        out.append(sc.render(rtmi.Opts(seed=seed, sample_first=i, sample_count=1), st))
+        out.append(sc.render(rtmi.Opts(seed=seed, sample_first=i, sample_count=1, variant=variant), st))
         assert st.kernel_variant & mask == family, (st.kernel_variant, family)
+        if variant:
+            assert st.kernel_variant & ~mask == variant, (st.kernel_variant, variant)
     return np.stack(out).reshape(-1, 3).astype(np.float64)
 
 

@@ -1,7 +1,8 @@
 """An independent statement of the path estimators of DESIGN 7a (light sampling + MIS), 7e (environment maps), 7f (homogeneous
-participating media with isotropic scattering) and 7g (motion blur: linearly moving spheres over a per-sample shutter time), in
-NumPy, vectorised over a batch of samples, at a floating type of the caller's choice (float64: the reference; float32: the same
-formulas at the kernel's precision, used to measure how many samples sit on a branch).
+participating media with isotropic scattering), 7g (motion blur: linearly moving spheres over a per-sample shutter time), 7l
+(smooth shading: the shading normal of triangles with vertex normals) and 7m (the glossy materials), in NumPy, vectorised over
+a batch of samples, at a floating type of the caller's choice (float64: the reference; float32: the same formulas at the
+kernel's precision, used to measure how many samples sit on a branch).
 
 Test infrastructure only.  It is written from the definitions -- DESIGN 2 (the integrator, the order of the draws), 7a, 7e,
 7f (the media walk), 7g (the shutter time, the movers' query and its tie rule), and the reference's primitive, material and
@@ -9,11 +10,14 @@ texture definitions (triangles, the hit record's (u, v) and the image lookup amo
 plain closest-hit loops over the primitive, mover and media lists and no fused operations.  It shares no code with the kernels
 or with oracle/.
 
-There is ONE integrator loop, trace().  An extension joins it with a record list on RefScene (lights, media, movers: empty
-unless the scene has them), a block in the loop, columns in the signature and keys in tally().  The reference evaluates the
-scene it is given: which combinations the product renders is the product's to refuse and test_refusals' to assert.  Where two
-extensions meet and DESIGN defines no order -- a light sample at a medium vertex, a shadow ray through a medium or past a
-mover -- trace() raises NotImplementedError.
+There is ONE integrator loop, trace(), and one hit record, hit_record().  An extension joins them with a record list on
+RefScene (lights, media, movers: empty unless the scene has them) or records the scene's tables already hold (a triangle's
+vertex normals, a material's type), a block in the loop, columns or event codes in the signature and keys in tally(); its
+deliberate mistakes are names in trace()'s `perturb`.  A material model large enough for a file of its own (ref64_glossy.py:
+the GGX lobe, both glossy materials' sample and evaluation) is imported HERE and holds no loop: no module restates trace(),
+and none swaps a function of this one.  The reference evaluates the scene it is given: which combinations the product renders
+is the product's to refuse and test_refusals' to assert.  Where two extensions meet and DESIGN defines no order -- a light
+sample at a medium vertex, a shadow ray through a medium or past a mover -- trace() raises NotImplementedError.
 
 Inputs are the product's exported tables (Scene.prims / materials / textures / lights / media / moving_spheres / get_camera /
 info / environment), the light alias table and the environment's CDF tables as the packed image stores them (table_image,
@@ -30,8 +34,11 @@ it) and the number of draws consumed.
 """
 import numpy as np
 
+from ref64_glossy import (ROUGH_METAL, PLASTIC, GLOSSY_MIN_ROUGHNESS, EV_ROUGH, EV_COAT, EV_BODY, EV_BELOW, EV_ROUGH_ABSORBED,
+                          EV_COAT_ABSORBED, alpha_of, r0_of, glossy_sample, glossy_eval, glossy_tally)
+
 SPHERE, XY_RECT, XZ_RECT, YZ_RECT, CYLINDER, TRIANGLE = range(6)
-LAMBERTIAN, METAL, DIELECTRIC, DIFFUSE_LIGHT = range(4)
+LAMBERTIAN, METAL, DIELECTRIC, DIFFUSE_LIGHT = range(4)  # (ref64_glossy: ROUGH_METAL, PLASTIC = 4, 5)
 SOLID, CHECKER, IMAGE = range(3)
 ENVIRONMENT = 100
 MEDIUM_SPHERE, MEDIUM_BOX = 0, 1
@@ -259,8 +266,41 @@ def closest_hit(S, o, d, t_max, T):
     return best, idx
 
 
-def hit_record(S, o, d, t, idx, T):
-    """point and face-turned normal of accepted hits; front = the ray meets the outward side"""
+def prim_normals(p):
+    """(n1, n2, n3) [3][3] of an rt_prim record: f[0..5] and m_inv[6..8]; all zero on a triangle without vertex normals"""
+    return np.concatenate([p["f"][:6], p["m_inv"][6:9]]).reshape(3, 3)
+
+
+def has_normals(p):
+    return bool(np.any(prim_normals(p) != 0))
+
+
+def shading_normal(pr, o, d, g, T):
+    """s = a1 n1 + a2 n2 + a3 n3, each corner's normal by the area of the sub-triangle opposite it over the whole (the
+    weight that is 1 at the corner): the three area weights of hit_uv, where w1 = (r, v1, v2) is corner 3's, w2 = (r, v1, v3)
+    corner 2's and w3 = (r, v3, v2) corner 1's.  Normalised, turned into the hemisphere of the face-turned geometric normal g;
+    s zero or not finite: g.  In dtype T, the plane point as the triangle test derives it."""
+    m = pr["m"].astype(T)
+    v1, v2, v3 = m[0:3], m[3:6], m[6:9]
+    n1, n2, n3 = prim_normals(pr).astype(T)
+    r, _, _, _ = _triangle_plane(pr, o, d, _dot(d, d), T)
+    norm = lambda a: np.sqrt(_dot(a, a))
+    with np.errstate(all="ignore"):
+        w1 = norm(_cross(r - v1, r - v2)) / norm(_cross(v3 - v1, v3 - v2))
+        w2 = norm(_cross(r - v1, r - v3)) / norm(_cross(v2 - v1, v2 - v3))
+        w3 = norm(_cross(r - v3, r - v2)) / norm(_cross(v1 - v3, v1 - v2))
+        s = w3[:, None] * n1 + w2[:, None] * n2 + w1[:, None] * n3
+        l2 = _dot(s, s)
+        ok = np.isfinite(l2) & (l2 > 0)
+        s = s / np.sqrt(l2)[:, None]
+        s = np.where((_dot(s, g) < 0)[:, None], -s, s)
+    return np.where(ok[:, None], s, g).astype(T)
+
+
+def hit_record(S, o, d, t, idx, T, flat=False):
+    """point and face-turned normal of accepted hits; front = the ray meets the outward side.  On a triangle that carries vertex
+    normals and whose material is no emitter the normal is the shading normal (front stays the geometric side); flat=True
+    leaves the geometric normal there too."""
     p = o + t[:, None] * d
     n_out = np.zeros_like(o)
     for i in np.unique(idx):
@@ -280,7 +320,13 @@ def hit_record(S, o, d, t, idx, T):
         else:
             n_out[m, _rect_axes(ty)[0]] = 1
     front = _dot(d, n_out) < 0
-    return p, np.where(front[:, None], n_out, -n_out), front
+    n = np.where(front[:, None], n_out, -n_out)
+    for i in (() if flat else np.unique(idx)):
+        pr = S.prims[i]
+        if int(pr["type"]) == TRIANGLE and has_normals(pr) and int(S.mats["type"][pr["material"]]) != DIFFUSE_LIGHT:
+            m = idx == i
+            n[m] = shading_normal(pr, o[m], d[m], n[m], T)
+    return p, n, front
 
 
 def mover_centre(m, s, T):
@@ -587,14 +633,22 @@ class _Draws:
         return out
 
 
-def trace(S, words, first_pixel=0, dtype=np.float64, perturb=(), shutter=None):
+def trace(S, words, first_pixel=0, dtype=np.float64, perturb=(), shutter=None, probe=None):
     """One sample per row of `words` (the sample's stream as uint32 words), pixel ids first_pixel, first_pixel + 1, ... modulo the
     frame; `shutter`: the samples' shutter times, required where the scene has movers.  Returns (rgb [N][3], signature [N][*]
-    int64, draws consumed [N]).  perturb names deliberate mistakes, for the tests that show the comparison can fail: "skip_draw",
-    "no_cos", "mis_unsquared", "no_rr_light" at the light sample; "skip_flight" leaves the free-flight draw out (the distance is
-    taken from the NEXT position instead: a wrong order of draws); "half_time" puts every sample at s = 0.5 (a renderer that
-    ignores the shutter time); "uv_transposed": the image lookup with u indexing columns; "tri_natural_pairing": each area weight
-    of a triangle with the corner opposite its sub-triangle."""
+    int64, draws consumed [N]).  probe: a dict that receives the FIRST vertex of every sample (what a feature pass shows):
+    "glossy" (bool: it lies on a glossy material), "albedo" (F0 or rho there), "normal" (the shading normal).
+    perturb names deliberate mistakes, for the tests that show the comparison can fail.  Every name, in one place:
+      "skip_draw", "no_cos", "mis_unsquared", "no_rr_light": at the light sample;
+      "skip_flight": the free-flight draw left out (the distance is taken from the NEXT position instead: a wrong order of draws);
+      "half_time": every sample at s = 0.5 (a renderer that ignores the shutter time);
+      "uv_transposed": the image lookup with u indexing columns;
+      "tri_natural_pairing": each area weight of a triangle with the corner opposite its sub-triangle;
+      "flat_normals": the geometric normal where a triangle carries vertex normals (a renderer without smooth shading);
+      "g1_for_g2": a glossy vertex's attenuation with G1(wo) in place of G2 (without the factor G2 / G1);
+      "lobe_draw_last": plastic's lobe draw taken after u1, u2 instead of in front of them;
+      "nee_albedo_pdf": a glossy vertex's light sample with f cos taken as albedo x pdf_b, the shortcut that holds for
+      lambertian and metal."""
     T = dtype
     N = len(words)
     D = _Draws(words, T)
@@ -705,7 +759,7 @@ def trace(S, words, first_pixel=0, dtype=np.float64, perturb=(), shutter=None):
         front = np.zeros(len(who), bool)
         mat = np.full(len(who), -1, np.int64)
         st = np.flatnonzero((mov < 0) & ~vol)
-        p[st], n[st], front[st] = hit_record(S, oo[st], dd[st], t_hit[st], idx[st], T)
+        p[st], n[st], front[st] = hit_record(S, oo[st], dd[st], t_hit[st], idx[st], T, flat="flat_normals" in perturb)
         mat[st] = S.prims["material"][idx[st]]
         for mi, m in enumerate(S.movers):
             q = np.flatnonzero((mov == mi) & ~vol)
@@ -718,7 +772,7 @@ def trace(S, words, first_pixel=0, dtype=np.float64, perturb=(), shutter=None):
         tex = np.full(len(who), -1, np.int64)
         kind[surface], tex[surface] = S.mats["type"][mat[surface]], S.mats["texture"][mat[surface]]
         listed = np.where(mov < 0, idx, -1)  # the static winner where it is the vertex's surface: the key of a listed light
-        checker = np.isin(kind, (LAMBERTIAN, DIFFUSE_LIGHT)) & (S.texs["type"][np.maximum(tex, 0)] == CHECKER)
+        checker = np.isin(kind, (LAMBERTIAN, DIFFUSE_LIGHT, PLASTIC)) & (S.texs["type"][np.maximum(tex, 0)] == CHECKER)
         note(C_PARITY, who, np.where(checker, checker_odd(p, T), NONE))
         event = np.full(len(who), NONE, np.int64)
         shutter_of = time[who] if len(S.movers) else None
@@ -802,11 +856,50 @@ def trace(S, words, first_pixel=0, dtype=np.float64, perturb=(), shutter=None):
             refracted = perp - np.sqrt(np.abs(1 - _dot(perp, perp)))[:, None] * nn
             new_d[die] = np.where(reflect[:, None], ud - 2 * _dot(ud, nn)[:, None] * nn, refracted)
             event[die] = np.where(reflect, EV_REFLECT, EV_REFRACT)
+        # ---- the glossy materials: their draws where dielectric takes its Fresnel draw; none where wo.z <= 0
+        glo = np.isin(kind, (ROUGH_METAL, PLASTIC))
+        g_alpha, g_f0, g_rho = np.zeros(len(who), T), np.zeros((len(who), 3), T), np.zeros((len(who), 3), T)
+        g_plastic, g_ud = np.zeros(len(who), bool), np.zeros_like(dd)
+        if glo.any():
+            k = np.flatnonzero(glo)
+            rec = S.mats[mat[k]]
+            g_plastic[k] = rec["type"] == PLASTIC
+            g_alpha[k] = alpha_of(rec["fuzz"]).astype(T)
+            g_f0[k] = np.where(g_plastic[k][:, None], r0_of(rec["ir"]).astype(T)[:, None], rec["albedo"].astype(T))
+            kp = k[g_plastic[k]]
+            if len(kp):
+                g_rho[kp] = textured(kp)
+            g_ud[k] = _unit(dd[k])
+            wo_z = -_dot(g_ud[k], n[k])
+            dr = k[wo_z > 0]  # the vertices that draw
+            ul, u1, u2 = np.zeros(len(who), T), np.zeros(len(who), T), np.zeros(len(who), T)
+            pd = dr[g_plastic[dr]]
+            if "lobe_draw_last" not in perturb:
+                ul[pd] = D.next(who[pd])
+            u1[dr] = D.next(who[dr])
+            u2[dr] = D.next(who[dr])
+            if "lobe_draw_last" in perturb:
+                ul[pd] = D.next(who[pd])
+            wi, at, pdf, below, absorbed_wi, lobe = glossy_sample(n[k], g_ud[k], g_alpha[k], g_plastic[k], g_f0[k], g_rho[k], ul[k],
+                                                                  u1[k], u2[k], T, perturb)
+            new_d[k], att[k] = wi, at
+            scattered[k] = ~below & ~absorbed_wi
+            event[k] = np.where(below, EV_BELOW, np.where(g_plastic[k], np.where(lobe, np.where(absorbed_wi, EV_COAT_ABSORBED, EV_COAT), EV_BODY),
+                                                         np.where(absorbed_wi, EV_ROUGH_ABSORBED, EV_ROUGH)))
+            takes_light[k] = (rec["fuzz"] >= np.float32(GLOSSY_MIN_ROUGHNESS)) & ~below
+            pdf_b[k] = np.where(scattered[k], pdf, -1)
+        if probe is not None and len(sig) == 2:
+            probe["glossy"], probe["albedo"], probe["normal"] = np.zeros(N, bool), np.zeros((N, 3), T), np.zeros((N, 3), T)
+            probe["glossy"][who] = glo
+            probe["albedo"][who] = np.where(g_plastic[:, None], g_rho, g_f0)
+            probe["normal"][who] = n
         note(C_EVENT, who, event)
         if not S.nee or len(S.lights) == 0:
             takes_light[:] = False
         # ---- what goes on: depth, then the roulette of the next query
         go = ~em & scattered
+        if glo.any():
+            before = beta[who].copy()                  # the throughput in front of the vertex (a glossy vertex's light sample)
         carried = beta[who] * att                      # the throughput the continuation carries
         depth[who[go]] -= 1
         go_on = go & (depth[who] > 0)
@@ -820,6 +913,8 @@ def trace(S, words, first_pixel=0, dtype=np.float64, perturb=(), shutter=None):
             note(C_ROULETTE, who[k], lost)
             survived[k] = ~lost
             carried[k] = carried[k] / rr
+            if glo.any():
+                before[k] = before[k] / rr
         alive[who] = go_on & survived
         beta[who] = carried
         o[who], d[who] = p, new_d
@@ -851,6 +946,7 @@ def trace(S, words, first_pixel=0, dtype=np.float64, perturb=(), shutter=None):
                 inside[sel] = inside_sphere_light(S, li, p[ls][sel], T)
         note(C_TEXEL, m, texel)
         d2 = _dot(ld, ld)
+        gl = glo[ls]
         with np.errstate(all="ignore"):
             w = ld / np.sqrt(d2)[:, None]
             wn = _dot(w, n[ls])
@@ -859,8 +955,19 @@ def trace(S, words, first_pixel=0, dtype=np.float64, perturb=(), shutter=None):
                 sel = fuzz[ls] == f
                 pb[sel] = metal_pdf(w[sel], refl_dir[ls][sel], f, T)
             pb = np.where(wn > 0, pb, 0)
-            # f cos / p_l times the power heuristic's p_l^2 / (p_l^2 + pdf_b^2); f cos = albedo x pdf_b for both materials
+            if gl.any():
+                # f cos is not albedo x pdf_b at a glossy vertex: both are evaluated for the light's direction
+                q = ls[gl]
+                fc, pg = glossy_eval(n[q], g_ud[q], g_alpha[q], g_plastic[q], g_f0[q], g_rho[q], w[gl], T)
+                if "nee_albedo_pdf" in perturb:
+                    fc = np.where(g_plastic[q][:, None], g_rho[q], g_f0[q]) * pg[:, None]
+                pb[gl] = pg
+                fcos = np.zeros((len(ls), 3), T)
+                fcos[gl] = fc
+            # f cos / p_l times the power heuristic's p_l^2 / (p_l^2 + pdf_b^2); f cos = albedo x pdf_b for lambertian and metal
             weight = pb * pl / (pl + pb if "mis_unsquared" in perturb else pl * pl + pb * pb)
+            if gl.any():  # the glossy vertices' scalar part: p_l / (p_l^2 + pdf_b^2); f cos joins per channel below
+                weight = np.where(gl, pl / (pl + pb if "mis_unsquared" in perturb else pl * pl + pb * pb), weight)
         usable = (pl > 0) & (pb > 0) & (d2 > 0) & np.isfinite(weight) & (weight > 0)
         verdict = np.where(inside, SHADOW_INSIDE, SHADOW_NONE)
         if usable.any():
@@ -874,6 +981,8 @@ def trace(S, words, first_pixel=0, dtype=np.float64, perturb=(), shutter=None):
             note(C_BLOCKER, m[k], np.where(blocker >= 0, blocker, NONE))
             clear = k[blocker < 0]
             through = carried[ls][clear]
+            if gl.any():
+                through = np.where(gl[clear][:, None], before[ls][clear] * fcos[clear], through)
             if "no_rr_light" in perturb and rr > 0:
                 through = through * rr
             rgb[m[clear]] += through * Le[clear] * weight[clear][:, None]
@@ -901,7 +1010,8 @@ def tally(sig, S=None):
     (EXT_KEYS): vertices that read an image texel, those that took a light sample, those on a mover, the samples with such a
     vertex, and the samples that met one after a medium event; emitter hits at full weight behind a vertex that took a light
     sample (the emitter is no listed light); and, where the RefScene S says which primitives are triangles and which carry
-    an image texture, vertices on triangles, those that took a light sample, and shadow rays stopped by either kind."""
+    an image texture, vertices on triangles, those that took a light sample, and shadow rays stopped by either kind.  Of 7m
+    (ref64_glossy.GLOSSY_KEYS and more): what ref64_glossy.glossy_tally() counts."""
     v = sig[:, SAMPLE_COLUMNS:].reshape(len(sig), -1, VERTEX_COLUMNS)
     event, light, shadow, how, alias, mover = (v[:, :, c] for c in (C_EVENT, C_LIGHT, C_SHADOW, C_HIT_WEIGHT, C_ALIAS, C_MOVER))
     prim, blocker = v[:, :, C_PRIM], v[:, :, C_BLOCKER]
@@ -920,7 +1030,12 @@ def tally(sig, S=None):
     vertex = event != NONE
     on_mover, on_static = vertex & (mover >= 0), vertex & (mover < 0)
     on_tri = on_static & ~med & of(is_tri, prim)
-    return dict(inside_no_sample=int((shadow == SHADOW_INSIDE).sum()), inside_full_weight_hits=int((how == HIT_FROM_INSIDE).sum()),
+    env_light = len(S.lights) - 1 if S is not None and len(S.lights) and S.lights[-1]["shape"] == ENVIRONMENT else -1
+    glossy = glossy_tally(event, dict(prim=prim, light=light, env_light=env_light, took_light=light != NONE,
+                                      clear=shadow == SHADOW_CLEAR, medium=med, on_mover=mover >= 0,
+                                      full_weight_emitter=(event == EV_EMIT) & (how == HIT_UNSAMPLED),
+                                      missed_to_texel=v[:, :, C_MISS_TEXEL] != NONE, lost=v[:, :, C_ROULETTE] == 1), S)
+    return dict(glossy, inside_no_sample=int((shadow == SHADOW_INSIDE).sum()), inside_full_weight_hits=int((how == HIT_FROM_INSIDE).sum()),
                 absorbed_metal_light_samples=int(((event == EV_METAL_ABSORBED) & (light != NONE)).sum()),
                 dielectric_vertices=int(glass.sum()), dielectric_light_samples=int((glass & (light != NONE)).sum()),
                 dielectric_full_weight_hits=int((glass[:, :-1] & (how[:, 1:] == HIT_UNSAMPLED)).sum()),

@@ -1,11 +1,10 @@
-"""Smooth shading: meshes with vertex normals, the fp64 statement of the shading normal, and the scenes of
-test_smooth.py (CPU) and test_gpu_smooth.py, built once per process.
+"""Smooth shading: meshes with vertex normals, the scenes of test_smooth.py (CPU) and test_gpu_smooth.py, built
+once per process, and independent_normal(), a second statement of the shading normal.
 
-ref64.trace is reused unchanged: it takes every hit record from the module-level ref64.hit_record, and smooth_reference()
-swaps that one name for smooth_hit_record (the shading normal at scattering materials, the geometric one at emitters) for the
-duration of a trace.  per_sample.kernel_samples renders in the scene's own layout only, so kernel_samples() here is that loop
-with the layout as an argument."""
-import contextlib
+The first statement is ref64.shading_normal, which ref64.hit_record applies on every triangle that carries vertex normals
+(the geometric normal at emitters): ref64.trace and ref64.reference need nothing from this file, and the flat form is their
+"flat_normals" perturbation.  independent_normal() shares nothing with ref64: it is what the first statement is checked
+against."""
 import functools
 
 import numpy as np
@@ -63,81 +62,6 @@ def write_obj(path, v, n=None, corner="a//n"):
         for k in range(len(v)):
             ids = [3 * k + 1, 3 * k + 2, 3 * k + 3]
             f.write("f " + " ".join({"a": "%d" % i, "a//n": "%d//%d" % (i, i), "a/t/n": "%d/1/%d" % (i, i)}[corner] for i in ids) + "\n")
-
-
-def prim_normals(p):
-    """(n1, n2, n3) [3][3] of an rt_prim record: f[0..5] and m_inv[6..8]"""
-    return np.concatenate([p["f"][:6], p["m_inv"][6:9]]).reshape(3, 3)
-
-
-def has_normals(p):
-    return bool(np.any(prim_normals(p) != 0))
-
-
-# ------------------------------------------------------------------------------------------- the statement of DESIGN 7l
-def shading_normal(pr, o, d, g, T):
-    """s = a1 n1 + a2 n2 + a3 n3, each corner's normal by the area of the sub-triangle opposite it over the whole (the weight
-    that is 1 at the corner): the three area weights of ref64.hit_uv, where w1 = (r, v1, v2) is corner 3's, w2 = (r, v1, v3)
-    corner 2's and w3 = (r, v3, v2) corner 1's.  Normalised, turned into the hemisphere of the face-turned geometric normal g;
-    s zero or not finite: g.  In dtype T, the plane point as the triangle test derives it."""
-    m = pr["m"].astype(T)
-    v1, v2, v3 = m[0:3], m[3:6], m[6:9]
-    n1, n2, n3 = prim_normals(pr).astype(T)
-    r, _, _, _ = R._triangle_plane(pr, o, d, R._dot(d, d), T)
-    norm = lambda a: np.sqrt(R._dot(a, a))
-    with np.errstate(all="ignore"):
-        w1 = norm(R._cross(r - v1, r - v2)) / norm(R._cross(v3 - v1, v3 - v2))
-        w2 = norm(R._cross(r - v1, r - v3)) / norm(R._cross(v2 - v1, v2 - v3))
-        w3 = norm(R._cross(r - v3, r - v2)) / norm(R._cross(v1 - v3, v1 - v2))
-        s = w3[:, None] * n1 + w2[:, None] * n2 + w1[:, None] * n3
-        l2 = R._dot(s, s)
-        ok = np.isfinite(l2) & (l2 > 0)
-        s = s / np.sqrt(l2)[:, None]
-        s = np.where((R._dot(s, g) < 0)[:, None], -s, s)
-    return np.where(ok[:, None], s, g).astype(T)
-
-
-_flat_hit_record = R.hit_record
-
-
-def smooth_hit_record(S, o, d, t, idx, T):
-    """ref64.hit_record with the shading normal on triangles that carry vertex normals and whose material scatters"""
-    p, n, front = _flat_hit_record(S, o, d, t, idx, T)
-    n = np.array(n)
-    for i in np.unique(idx):
-        pr = S.prims[i]
-        if int(pr["type"]) != R.TRIANGLE or not has_normals(pr) or int(S.mats["type"][pr["material"]]) == R.DIFFUSE_LIGHT:
-            continue
-        m = idx == i
-        n[m] = shading_normal(pr, o[m], d[m], n[m], T)
-    return p, n, front
-
-
-@contextlib.contextmanager
-def smooth_reference():
-    R.hit_record = smooth_hit_record
-    try:
-        yield
-    finally:
-        R.hit_record = _flat_hit_record
-
-
-def reference(S, words, shutter=None):
-    """ref64.reference under the shading normal"""
-    with smooth_reference():
-        return R.reference(S, words, shutter)
-
-
-def kernel_samples(rtmi, sc, k, mask, family, variant=0):
-    """per_sample.kernel_samples with the layout as an argument"""
-    out = []
-    for i in range(k):
-        st = rtmi.Stats()
-        out.append(sc.render(rtmi.Opts(seed=SEED, sample_first=i, sample_count=1, variant=variant), st))
-        assert st.kernel_variant & mask == family, (st.kernel_variant, family)
-        if variant:
-            assert st.kernel_variant & ~mask == variant, (st.kernel_variant, variant)
-    return np.stack(out).reshape(-1, 3).astype(np.float64)
 
 
 # ---------------------------------------------------------------------------------------------------------------- scenes
@@ -288,7 +212,7 @@ def independent_normal(pr, o, d):
     -> (shading normal, face-turned geometric normal g, front: the ray meets the side the face normal (v2 - v1) x (v3 - v1) points to)"""
     m = pr["m"].astype(np.float64)
     v1, v2, v3 = m[0:3], m[3:6], m[6:9]
-    n1, n2, n3 = prim_normals(pr).astype(np.float64)
+    n1, n2, n3 = np.concatenate([pr["f"][:6], pr["m_inv"][6:9]]).reshape(3, 3).astype(np.float64)  # the record's vertex normals
     nf = np.cross(v2 - v1, v3 - v1)
     area = np.sqrt(nf @ nf)
     nf = nf / area

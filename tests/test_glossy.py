@@ -4,10 +4,12 @@
      C++ code's share within tolerance is at least the fp32 numpy statement's minus 0.5 points);
   3. the estimator against itself in fp64: pdf_b integrates to 1 with the absorbed share, the mean attenuation is the integral
      of f cos, reciprocity, and a white rough metal reflects no more than it receives;
-  4. ref64_glossy.trace returns exactly ref64.trace's results on scenes without glossy materials (what licenses the
-     restatement), and its perturbations change what they name.
+  4. ref64.trace, which holds the glossy vertices, still returns on scenes without glossy materials what it returned before
+     they joined it (a pinned fixture), never evaluates the glossy model there, and its glossy perturbations change what
+     they name.
 test_gpu_glossy.py holds the kernels to that reference."""
 import ctypes
+import hashlib
 import json
 import os
 import subprocess
@@ -327,14 +329,36 @@ def _existing_cases(rtmi):
 
 
 @pytest.mark.parametrize("name", ["light sampling", "environment", "medium"])
-def test_the_restated_tracer_is_ref64_without_glossy_materials(rtmi, name):
+def test_the_tracer_is_pinned_on_scenes_without_glossy_materials(rtmi, golden_dir, name):
+    """golden/ref64_trace_pin.npz holds what ref64.trace returned on these cases before the glossy materials joined its loop
+    (golden/make_ref64_trace_pin.py; the first sample of each pixel).  The draws and the signature are exact: a branch or an
+    order of draws that changed shows there.  rgb to rtol 1e-9: a libm whose log / sin / arccos differ in the last bit moves
+    a path of a few hundred fp64 operations by far less, and the kernels are held to 1e-4."""
+    pin = np.load(os.path.join(golden_dir, "ref64_trace_pin.npz"))
     sc, seed = _existing_cases(rtmi)[name]
-    words = R.uniforms(rtmi, seed, NS.REF_W, NS.REF_H, 0, 2, NS.REF_DRAWS)
+    words = R.uniforms(rtmi, seed, NS.REF_W, NS.REF_H, 0, 1, NS.REF_DRAWS)
     S = R.RefScene(sc)
-    for dtype in (np.float64, np.float32):
-        a, b = R.trace(S, words, dtype=dtype), G.trace(S, words, dtype=dtype)
-        assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2]), (name, dtype)
-    assert a[0].any()
+    for tag, dtype in (("64", np.float64), ("32", np.float32)):
+        rgb, sig, draws = R.trace(S, words, dtype=dtype)
+        assert np.array_equal(draws, pin[f"{name}/draws{tag}"]), (name, tag)
+        assert hashlib.sha256(np.ascontiguousarray(sig).tobytes()).hexdigest() == str(pin[f"{name}/sig{tag}"]), (name, tag)
+        assert rgb.dtype == dtype and np.allclose(rgb, pin[f"{name}/rgb{tag}"], rtol=1e-9, atol=1e-12), (name, tag)
+        assert rgb.any()
+
+
+def test_the_glossy_block_is_inert_without_glossy_materials(rtmi, monkeypatch):
+    """on the pinned cases neither the glossy sample nor the glossy evaluation is ever called"""
+    def never(*a, **k):
+        raise AssertionError("the glossy model was evaluated on a scene without glossy materials")
+    for module in (R, G):
+        monkeypatch.setattr(module, "glossy_sample", never)
+        monkeypatch.setattr(module, "glossy_eval", never)
+    for name, (sc, seed) in _existing_cases(rtmi).items():
+        words = R.uniforms(rtmi, seed, NS.REF_W, NS.REF_H, 0, 1, NS.REF_DRAWS)
+        rgb, _, _ = R.trace(R.RefScene(sc), words)
+        assert rgb.any(), name
+    with pytest.raises(AssertionError, match="glossy model"):  # ... and the swap does reach the tracer
+        R.trace(R.RefScene(GS.scene(rtmi, "glossy_sky")), words[:64])
 
 
 @pytest.fixture(scope="module")
@@ -346,7 +370,7 @@ def references(rtmi):
             sc = GS.scene(rtmi, name)
             words, shutter = GS.inputs(rtmi, name)
             S = R.RefScene(sc)
-            made[name] = (S, words, shutter, GS.reference(name, S, words, shutter))
+            made[name] = (S, words, shutter, R.reference(S, words, shutter))
         return made[name]
     return of
 
@@ -358,7 +382,7 @@ def test_the_cases_hold_what_they_are_there_for(rtmi, references, name):
     S, words, shutter, (ref, stable, draws, tally) = references(name)
     assert len(words) >= 16000 and draws.max() <= NS.REF_DRAWS
     GS.check_contents(name, tally)
-    rgb32, _, _ = GS.traced(name, S, words, shutter, dtype=np.float32)
+    rgb32, _, _ = R.trace(S, words, shutter=shutter, dtype=np.float32)
     j = R.judge(rgb32, ref, stable)
     print("\n" + R.row(name + " (fp32 reference)", j))
     assert j["flips"] <= 0.01 and j["share"] >= 0.97, j
@@ -371,7 +395,7 @@ def test_the_cases_hold_what_they_are_there_for(rtmi, references, name):
 @pytest.mark.parametrize("name,mistake", [("glossy_sky", "g1_for_g2"), ("glossy_sky", "lobe_draw_last"), ("glossy_lights", "nee_albedo_pdf")])
 def test_the_perturbations_change_the_reference(references, name, mistake):
     S, words, shutter, (ref, stable, _, _) = references(name)
-    wrong, _, _ = GS.traced(name, S, words[:4000], shutter, perturb=(mistake,))
+    wrong, _, _ = R.trace(S, words[:4000], shutter=shutter, perturb=(mistake,))
     j = R.judge(wrong, ref[:4000], stable[:4000])
     print(f"\n{name}, {mistake}: the perturbed reference agrees with the reference on {100 * j['share']:.1f} % of the samples")
     assert j["share"] < 0.9, j["share"]

@@ -1,5 +1,5 @@
 """The glossy materials (GGX rough metal, coated plastic) in every render family, against the fp64 statement of
-ref64_glossy.py, sample by sample on the same draws: criteria (a) - (d) of test_gpu_nee_reference.py with per_sample's
+ref64.py and ref64_glossy.py, sample by sample on the same draws: criteria (a) - (d) of test_gpu_nee_reference.py with per_sample's
 thresholds, on the six cases of glossy_scenes.py.  The (b) baseline is the plain kernel on the case's twin -- every glossy
 material replaced by lambertian of the same texture (or of F0), light sampling off, environment, media and movers cleared --
 against the twin's reference.  Each case asserts from the reference's signatures that it contains the vertices it is there for.
@@ -62,7 +62,7 @@ def cases(rtmi, inputs):
             sc.render(rtmi.Opts(seed=GS.seed_of(name), sample_count=1), st)
             assert st.kernel_variant & ~GS.FAMILIES in GENERAL_LAYOUTS and st.kernel_variant & GS.FAMILIES == GS.family(name), st.kernel_variant
             got = PS.kernel_samples(rtmi, sc, GS.seed_of(name), NS.REF_K, GS.FAMILIES, GS.family(name))
-            made[name] = (sc, S, got, GS.reference(name, S, words, shutter))
+            made[name] = (sc, S, got, R.reference(S, words, shutter))
         return made[name]
     return of
 
@@ -75,7 +75,7 @@ def test_kernel_against_fp64(rtmi, inputs, cases, name):
     assert draws.max() <= NS.REF_DRAWS, draws.max()                                        # (d)
     GS.check_contents(name, tally)
     plain = GS.plain_twin(rtmi, name)
-    bref, bstable, _, _ = GS.reference(name, R.RefScene(plain), words)
+    bref, bstable, _, _ = R.reference(R.RefScene(plain), words)
     b = R.judge(PS.kernel_samples(rtmi, plain, GS.seed_of(name), NS.REF_K, GS.FAMILIES, 0), bref, bstable)
     PS.assert_agreement(name, R.judge(got, ref, stable), b)                                # (a), (b), (c)
     print("    " + ", ".join(f"{k} {tally[k]}" for k in G.GLOSSY_KEYS if tally[k]))
@@ -86,7 +86,7 @@ def test_a_mistake_fails_the_agreement(inputs, cases, name, mistake):
     """(d): against the kernel, a reference with one deliberate mistake of the model is far from 97 %"""
     words, shutter = inputs(name)
     sc, S, got, (ref, stable, _, _) = cases(name)
-    wrong, _, _ = GS.traced(name, S, words, shutter, perturb=(mistake,))
+    wrong, _, _ = R.trace(S, words, shutter=shutter, perturb=(mistake,))
     good, bad = R.judge(got, ref, stable), R.judge(got, wrong, stable)
     print(f"\n{name}, {mistake}: within tolerance {100 * good['share']:.2f} % -> {100 * bad['share']:.2f} %")
     PS.assert_perturbation_noticed(good, bad)
@@ -141,8 +141,8 @@ def test_feature_buffers_show_the_first_vertex(rtmi, inputs):
     words, _ = inputs(name)
     n = NS.REF_W * NS.REF_H
     probe, probe32 = {}, {}
-    GS.traced(name, R.RefScene(sc), words[:n], probe=probe)
-    GS.traced(name, R.RefScene(sc), words[:n], dtype=np.float32, probe=probe32)
+    R.trace(R.RefScene(sc), words[:n], probe=probe)
+    R.trace(R.RefScene(sc), words[:n], dtype=np.float32, probe=probe32)
     o = rtmi.Opts(seed=GS.seed_of(name), sample_first=0, sample_count=1)
     albedo = sc.render_feature(rtmi.FEATURE_ALBEDO, o).reshape(-1, 3).astype(np.float64)
     normal = sc.render_feature(rtmi.FEATURE_NORMAL, o).reshape(-1, 3).astype(np.float64)

@@ -20,7 +20,7 @@ RTMI = os.path.join(ROOT, "ray-tracing-in-cuda_amd", "rtmi")
 SCENE_FILE = os.path.join(ROOT, "ray-tracing-in-cuda_amd", "scenes", "smooth_mesh.json")
 
 # |normal - fp64| per component.  Measured on the CPU, on this file's rays, no kernel involved: the statement of
-# smooth_scenes.shading_normal evaluated in fp32 and in fp64 part by at most 1.38e-6 (858 hits on 79 smooth triangles; the
+# ref64.shading_normal evaluated in fp32 and in fp64 part by at most 1.38e-6 (858 hits on 79 smooth triangles; the
 # independent fp64 statement below is within 9.2e-8 of it: it takes the face normal from the corners, not the stored one).
 # The bound is 8 x that, the margin test_gpu_trace.py gives its normals (2.4e-6 against 2e-5).
 NORMAL_TOL = 1.1e-5
@@ -50,7 +50,7 @@ def run(rtmi, smooth, variant=0):
 
 def smooth_mask(sc, h):
     prims = sc.prims()
-    is_smooth = np.array([int(p["type"]) == R.TRIANGLE and SS.has_normals(p) for p in prims])
+    is_smooth = np.array([int(p["type"]) == R.TRIANGLE and R.has_normals(p) for p in prims])
     return (h["prim"] >= 0) & is_smooth[np.maximum(h["prim"], 0)]
 
 
@@ -137,7 +137,7 @@ def test_the_degenerate_sum_falls_back_to_the_geometric_normal(gpu):
     n1 = (0.6, 0.0, 0.8)
     sc.triangle((0, 0, 0), (4, 0, 0), (0, 4, 0), sc.lambertian((0.5, 0.5, 0.5)), normals=(n1, (-0.6, 0.0, -0.8), n1))
     sc.xy_rect(-3, 7, -3, 7, -2.0, sc.lambertian((0.5, 0.5, 0.5)))
-    assert np.array_equal(SS.prim_normals(sc.prims()[0])[1], -SS.prim_normals(sc.prims()[0])[0])
+    assert np.array_equal(R.prim_normals(sc.prims()[0])[1], -R.prim_normals(sc.prims()[0])[0])
     degenerate_o = [(2, 1, 1), (2, 1, -1), (2, 1, 2), (2, 1, 0.5)]
     degenerate_d = [(0, 0, -1), (0, 0, 1), (0, 0, -2), (0, 0, -0.25)]
     rng = np.random.default_rng(5)
@@ -168,10 +168,10 @@ def references(rtmi, name):
         build, fam, _ = SS.RENDER_CASES[name]
         S = R.RefScene(build(rtmi))
         sh = SS.shutter(rtmi) if fam == SS.MOTION else None
-        ref, stable, draws, tally = SS.reference(S, SS.words(rtmi), sh)
+        ref, stable, draws, tally = R.reference(S, SS.words(rtmi), sh)
         assert draws.max() <= SS.DRAWS
         assert tally["triangle_vertices"] >= 0.2 * len(ref), tally["triangle_vertices"]
-        flat, _, _ = R.trace(S, SS.words(rtmi), shutter=sh)
+        flat, _, _ = R.trace(S, SS.words(rtmi), shutter=sh, perturb=("flat_normals",))
         _refs[name] = (ref, stable, flat)
     return _refs[name]
 
@@ -185,7 +185,7 @@ def baseline(rtmi, name):
     if key not in _baselines:
         twin = SS.plain_twin(rtmi, key)
         ref, stable, _ = references(rtmi, key)
-        _baselines[key] = R.judge(SS.kernel_samples(rtmi, twin, SS.K, SS.FAMILIES, 0), ref, stable)
+        _baselines[key] = R.judge(PS.kernel_samples(rtmi, twin, SS.SEED, SS.K, SS.FAMILIES, 0), ref, stable)
     return _baselines[key]
 
 
@@ -195,11 +195,11 @@ def test_render_families_against_fp64_under_the_shading_normal(gpu, name, varian
     is far from 97 % -- what fails without the feature even if the interface existed"""
     build, fam, _ = SS.RENDER_CASES[name]
     sc = build(gpu)
-    assert any(SS.has_normals(p) for p in sc.prims())
-    kinds = {int(sc.materials()[p["material"]]["type"]) for p in sc.prims() if int(p["type"]) == R.TRIANGLE and SS.has_normals(p)}
+    assert any(R.has_normals(p) for p in sc.prims())
+    kinds = {int(sc.materials()[p["material"]]["type"]) for p in sc.prims() if int(p["type"]) == R.TRIANGLE and R.has_normals(p)}
     assert kinds == {0, 1, 2}  # lambertian, metal and dielectric on smooth triangles
     ref, stable, flat = references(gpu, name)
-    got = SS.kernel_samples(gpu, sc, SS.K, SS.FAMILIES, fam, variant)
+    got = PS.kernel_samples(gpu, sc, SS.SEED, SS.K, SS.FAMILIES, fam, variant)
     good, bad = R.judge(got, ref, stable), R.judge(got, flat, stable)
     print(f"\n{name} @ {variant}: flat-normal reference within tolerance {100 * bad['share']:.2f} %")
     PS.assert_agreement(f"{name} @ {variant}", good, baseline(gpu, name))

@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+import ref64 as R
 import smooth_pack_cases as PC
 import smooth_scenes as SS
 
@@ -35,14 +36,14 @@ def test_round_trip_through_prims_and_json(rtmi, tmp_path):
     sc.triangle(*V, mat, (0.1, 0.2), (0.3, 0.4), (0.5, 0.6), normals=N)
     sc.triangle(*V, mat)
     smooth, flat = tris(sc)
-    got = SS.prim_normals(smooth)
+    got = R.prim_normals(smooth)
     # normalised in fp64, rounded once
     assert np.array_equal(got, unit(np.asarray(N, np.float32)).astype(np.float32))  # (the interface takes fp32)
     assert np.abs(np.sqrt((got.astype(np.float64) ** 2).sum(axis=1)) - 1.0).max() <= 1e-7
     assert np.array_equal(smooth["m_inv"][9:12], np.zeros(3, np.float32))
     assert np.array_equal(smooth["m_inv"][:6], np.array([0.1, 0.2, 0.3, 0.4, 0.5, 0.6], np.float32))
     # a flat triangle: nine zeros, and the geometry words are the same with and without normals
-    assert not SS.has_normals(flat) and np.array_equal(SS.prim_normals(flat), np.zeros((3, 3), np.float32))
+    assert not R.has_normals(flat) and np.array_equal(R.prim_normals(flat), np.zeros((3, 3), np.float32))
     assert np.array_equal(smooth["m"], flat["m"])
     # JSON: the normals are written and read back bit for bit; a flat triangle has no n1
     text = sc.to_json()
@@ -118,15 +119,15 @@ def test_obj_vn_lines_and_corner_forms(rtmi, tmp_path):
     sc, mat = new(rtmi)
     assert sc.add_obj(str(obj), mat, normals="file") == 3
     t = tris(sc)
-    assert np.array_equal(SS.prim_normals(t[0]), vn[[0, 1, 2]])          # a//n
-    assert np.array_equal(SS.prim_normals(t[1]), vn[[2, 1, 0]])          # a/t/n
+    assert np.array_equal(R.prim_normals(t[0]), vn[[0, 1, 2]])          # a//n
+    assert np.array_equal(R.prim_normals(t[1]), vn[[2, 1, 0]])          # a/t/n
     assert np.array_equal(t[1]["m_inv"][:6], np.array([0.25, 0.75] * 3, np.float32))
-    assert np.array_equal(SS.prim_normals(t[2]), np.array([face, vn[1], face]))  # corners without n: the face normal
+    assert np.array_equal(R.prim_normals(t[2]), np.array([face, vn[1], face]))  # corners without n: the face normal
     # rt_scene_add_obj and normals="flat": n ignored, as before
     for kw in ({}, {"normals": "flat"}):
         fl, m2 = new(rtmi)
         assert fl.add_obj(str(obj), m2, **kw) == 3
-        assert not any(SS.has_normals(p) for p in tris(fl))
+        assert not any(R.has_normals(p) for p in tris(fl))
         assert np.array_equal(tris(fl)["m"], t["m"])
     # an n out of range (0 and negative included) is an error
     for corner in ("1//4", "1//0", "1//-1"):
@@ -150,7 +151,7 @@ def test_obj_normals_go_through_the_inverse_transpose(rtmi, tmp_path):
         assert sc.add_obj(str(obj), mat, scale, M.reshape(9), (0.5, -1.0, 2.0), normals="file") == len(v)
         A = scale * M
         want = unit(n.reshape(-1, 3) @ np.linalg.inv(A)).reshape(-1, 3, 3)  # rows: (A^-T n)^T = n^T A^-1
-        got = np.array([SS.prim_normals(p) for p in tris(sc)], np.float64)
+        got = np.array([R.prim_normals(p) for p in tris(sc)], np.float64)
         # bound: the product and the normalisation in fp64, one rounding to fp32 (2^-24 per component)
         assert np.abs(got - want).max() <= 1e-7, np.abs(got - want).max()
         # and it is NOT the matrix itself applied to the normal
@@ -185,12 +186,12 @@ def test_cube_normals_do_not_depend_on_the_triangulation(rtmi, tmp_path, cut):
     for p in tris(sc):
         corners = (p["m"][:9].reshape(3, 3).astype(np.float64) - (3.0, 1.0, -2.0)) / 0.75
         want = (corners / np.sqrt(3.0)).astype(np.float32)
-        got = SS.prim_normals(p)
+        got = R.prim_normals(p)
         assert np.abs(got - want).max() <= 2.0 ** -24, (got, want)  # to fp32 rounding of 0.577...
     sharp, m2 = new(rtmi)
     assert sharp.add_obj(str(obj), m2, normals="smooth", crease_angle=30.0) == 12
     for p in tris(sharp):
-        assert np.array_equal(SS.prim_normals(p), np.tile(p["m"][9:12], (3, 1)))
+        assert np.array_equal(R.prim_normals(p), np.tile(p["m"][9:12], (3, 1)))
 
 
 def test_generated_normals_of_a_uv_sphere_are_radial(rtmi, tmp_path):
@@ -203,7 +204,7 @@ def test_generated_normals_of_a_uv_sphere_are_radial(rtmi, tmp_path):
     SS.write_obj(str(obj), v, None, "a")
     sc, mat = new(rtmi)
     assert sc.add_obj(str(obj), mat, normals="smooth") == len(v)
-    got = np.array([SS.prim_normals(p) for p in tris(sc)], np.float64)
+    got = np.array([R.prim_normals(p) for p in tris(sc)], np.float64)
     dev = np.abs(got - n).max()
     print("uv sphere generated normals: max deviation from radial", dev)
     assert dev <= 0.02
@@ -241,7 +242,7 @@ def test_the_normals_part(rtmi):
     n_smooth = 0
     for k in range(nt):
         p = prims[cold[k, 0].view(np.int32)[1]]  # the triangle's list index
-        assert np.array_equal(part[k, :, :3], SS.prim_normals(p))
-        assert part[k, 0].view(np.int32)[3] == (1 if SS.has_normals(p) else 0) and part[k, 1, 3] == 0 and part[k, 2, 3] == 0
-        n_smooth += SS.has_normals(p)
+        assert np.array_equal(part[k, :, :3], R.prim_normals(p))
+        assert part[k, 0].view(np.int32)[3] == (1 if R.has_normals(p) else 0) and part[k, 1, 3] == 0 and part[k, 2, 3] == 0
+        n_smooth += R.has_normals(p)
     assert n_smooth == 83
