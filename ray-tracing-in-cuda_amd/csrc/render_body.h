@@ -45,6 +45,9 @@
     // (Not in the moving-sphere kernels: their spilled vector registers rose from 109 to 114 with it.  The refill's start
     // mask below is the same idea and holds for every family.)
     constexpr bool VOTE_MASKS = !MOTION;
+    // rt_sqrtf's guard as a vote of the wave and its root from v_rsq_f32 (render_device.h).  (Not in the nested walk: with
+    // triangles and textures its spilled vector registers rose from 86 to 97 with the vote.)
+    constexpr bool ROOT_VOTE = !NEST;
     // u = (x + xi) / (W - 1), main.cu:96-97, evaluated as a multiply by the fp32 reciprocal (as the checker does)
     // (the two reciprocals come with the launch parameters: computed here they were vector registers, spilled to scratch and
     //  fetched back with two dependent scratch loads in every refill)
@@ -223,7 +226,7 @@
                     const unsigned long long em = __builtin_amdgcn_ballot_w64(true);
                     if ((int)__builtin_ctzll(em) == lane) c_cand_wave++;
                 }
-                const float sq = rt_sqrtf(disc);
+                const float sq = rt_sqrtf<ROOT_VOTE>(disc);
                 float root = (-hb - sq) * rinv_a;
                 if (root < kTMin || best_t < root) root = (-hb + sq) * rinv_a;
                 if (!(root < kTMin || best_t < root)) {
@@ -242,7 +245,7 @@
             //  test -- a triangle test is about 190 instructions, 41 of them these)
             float tq_a = 1.0f, tq_ux = 0.0f, tq_uy = 0.0f, tq_uz = 0.0f;
             if (EXT && nt > 0 && active) {
-                tq_a = rt_sqrtf(ra);
+                tq_a = rt_sqrtf<ROOT_VOTE>(ra);
                 tq_ux = dx / tq_a, tq_uy = dy / tq_a, tq_uz = dz / tq_a;
             }
             auto tri_plane = [&](const float4 r0, const float4 r1, const float4 r2, float &rix, float &riy, float &riz,
@@ -414,7 +417,7 @@
                 const float qc = fmaf(oox, oox, fmaf(ooy, ooy, -pr.x));
                 const float delta = fmaf(qb, qb, -((4.0f * qa) * qc));
                 if (!(delta < 0.0f)) {
-                    const float sq = rt_sqrtf(delta);
+                    const float sq = rt_sqrtf<ROOT_VOTE>(delta);
                     float t0 = (-0.5f * (qb - sq)) / qa;
                     float t1 = (-0.5f * (qb + sq)) / qa;
                     if (t0 > t1) {
@@ -1014,7 +1017,7 @@
             tick(2);
             // ---- (2) the winner (ray_color body, main.cu:45-65 / main.cpp:22-38)
             // 1/|d| once per query (metal, dielectric and the sky all normalise the direction)
-            inv_len = 1.0f / rt_sqrtf(ra);
+            inv_len = 1.0f / rt_sqrtf<ROOT_VOTE>(ra);
             // MEDIA: the media walk of a finished query.  The media -- records behind a count and an offset in the camera
             // block, all wave-uniform reads from global memory -- in list order: the ray's stay [a, b] inside the boundary up to
             // the surface winner; a non-empty stay in a medium of positive density takes ONE draw, the free-flight distance.
@@ -1025,7 +1028,7 @@
                 if (!unfinished) {
                     const int n_med = __builtin_amdgcn_readfirstlane(__float_as_int(image[P.off_cam + 1].w));
                     const float4 *med = image + __builtin_amdgcn_readfirstlane(__float_as_int(image[P.off_cam + 2].w));
-                    const float len = rt_sqrtf(ra);
+                    const float len = rt_sqrtf<ROOT_VOTE>(ra);
                     for (int m = 0; m < n_med; ++m) {
                         const float4 g0 = med[RT_MEDIUM_STRIDE * m], g1 = med[RT_MEDIUM_STRIDE * m + 1], g2 = med[RT_MEDIUM_STRIDE * m + 2];
                         float ta, tb;
@@ -1118,7 +1121,7 @@
                     const float ody = fmaf(r1.x, dx, fmaf(r1.y, dy, r1.z * dz));
                     const float odz = fmaf(r2.x, dx, fmaf(r2.y, dy, r2.z * dz));
                     const float opx = fmaf(best_t, odx, oox), opy = fmaf(best_t, ody, ooy), opz = fmaf(best_t, odz, ooz);
-                    const float len = rt_sqrtf(fmaf(opx, opx, opy * opy));
+                    const float len = rt_sqrtf<ROOT_VOTE>(fmaf(opx, opx, opy * opy));
                     const float onx = opx / len, ony = opy / len;
                     px = fmaf(m0.x, opx, fmaf(m0.y, opy, fmaf(m0.z, opz, m0.w)));
                     py = fmaf(m1.x, opx, fmaf(m1.y, opy, fmaf(m1.z, opz, m1.w)));
@@ -1168,13 +1171,13 @@
                             float cx, cy, cz, ex, ey, ez;
                             cross3(a1x, a1y, a1z, a2x, a2y, a2z, cx, cy, cz);
                             cross3(r2.x - r0.x, r2.y - r0.y, r2.z - r0.z, r2.x - r1.x, r2.y - r1.y, r2.z - r1.z, ex, ey, ez);
-                            w1 = rt_sqrtf(dot3(cx, cy, cz, cx, cy, cz)) / rt_sqrtf(dot3(ex, ey, ez, ex, ey, ez));
+                            w1 = rt_sqrtf<ROOT_VOTE>(dot3(cx, cy, cz, cx, cy, cz)) / rt_sqrtf<ROOT_VOTE>(dot3(ex, ey, ez, ex, ey, ez));
                             cross3(a1x, a1y, a1z, a3x, a3y, a3z, cx, cy, cz);
                             cross3(r1.x - r0.x, r1.y - r0.y, r1.z - r0.z, r1.x - r2.x, r1.y - r2.y, r1.z - r2.z, ex, ey, ez);
-                            w2 = rt_sqrtf(dot3(cx, cy, cz, cx, cy, cz)) / rt_sqrtf(dot3(ex, ey, ez, ex, ey, ez));
+                            w2 = rt_sqrtf<ROOT_VOTE>(dot3(cx, cy, cz, cx, cy, cz)) / rt_sqrtf<ROOT_VOTE>(dot3(ex, ey, ez, ex, ey, ez));
                             cross3(a3x, a3y, a3z, a2x, a2y, a2z, cx, cy, cz);
                             cross3(r0.x - r2.x, r0.y - r2.y, r0.z - r2.z, r0.x - r1.x, r0.y - r1.y, r0.z - r1.z, ex, ey, ez);
-                            w3 = rt_sqrtf(dot3(cx, cy, cz, cx, cy, cz)) / rt_sqrtf(dot3(ex, ey, ez, ex, ey, ez));
+                            w3 = rt_sqrtf<ROOT_VOTE>(dot3(cx, cy, cz, cx, cy, cz)) / rt_sqrtf<ROOT_VOTE>(dot3(ex, ey, ez, ex, ey, ez));
                         }
                         if (smooth) {
                             // each corner's normal by the area of the sub-triangle OPPOSITE that corner (the barycentric weight
@@ -1189,7 +1192,7 @@
                             const float sz = fmaf(n1.z, w3, fmaf(n2.z, w2, n3.z * w1));
                             const float l2 = dot3(sx, sy, sz, sx, sy, sz);
                             if (l2 > 0.0f && l2 < INFINITY) {
-                                const float inv = 1.0f / rt_sqrtf(l2);
+                                const float inv = 1.0f / rt_sqrtf<ROOT_VOTE>(l2);
                                 const float ux = inv * sx, uy = inv * sy, uz = inv * sz;
                                 const bool turn = dot3(ux, uy, uz, nx, ny, nz) < 0.0f;
                                 nx = turn ? -ux : ux, ny = turn ? -uy : uy, nz = turn ? -uz : uz;
@@ -1590,7 +1593,7 @@
                 float at_r, at_g, at_b;        // attenuation
                 bool scattered = true;
                 if (kind <= MK_LAMBERT_IMAGE || (MEDIA && kind == MK_MEDIUM)) {  // lambertian::scatter, material.h:25-35 (MEDIA: a medium vertex, n = 0)
-                    const float inv = 1.0f / rt_sqrtf(sl2);
+                    const float inv = 1.0f / rt_sqrtf<ROOT_VOTE>(sl2);
                     ndx = nx + inv * sx, ndy = ny + inv * sy, ndz = nz + inv * sz;
                     const float eps = 1e-8f;
                     if (fabsf(ndx) < eps && fabsf(ndy) < eps && fabsf(ndz) < eps) ndx = nx, ndy = ny, ndz = nz;
@@ -1649,7 +1652,7 @@
                     const float ux = inv_len * dx, uy = inv_len * dy, uz = inv_len * dz;
                     const float udn = dot3(ux, uy, uz, nx, ny, nz);
                     const float cos_t = fminf(-udn, 1.0f);
-                    const float sin_t = rt_sqrtf(fmaf(-cos_t, cos_t, 1.0f));
+                    const float sin_t = rt_sqrtf<ROOT_VOTE>(fmaf(-cos_t, cos_t, 1.0f));
                     bool refl = ratio * sin_t > 1.0f;
                     if (!refl) {
                         const float r0 = front ? q0.w : q1.w;
@@ -1665,7 +1668,7 @@
                         const float ppx = ratio * fmaf(cos_t, nx, ux);
                         const float ppy = ratio * fmaf(cos_t, ny, uy);
                         const float ppz = ratio * fmaf(cos_t, nz, uz);
-                        const float kk = -rt_sqrtf(fabsf(1.0f - dot3(ppx, ppy, ppz, ppx, ppy, ppz)));
+                        const float kk = -rt_sqrtf<ROOT_VOTE>(fabsf(1.0f - dot3(ppx, ppy, ppz, ppx, ppy, ppz)));
                         ndx = fmaf(kk, nx, ppx), ndy = fmaf(kk, ny, ppy), ndz = fmaf(kk, nz, ppz);
                     }
                     at_r = at_g = at_b = 1.0f;

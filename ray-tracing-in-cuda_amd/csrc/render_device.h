@@ -110,14 +110,30 @@ __device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, fl
     return fmaf(ax, bx, fmaf(ay, by, az * bz));
 }
 
-// IEEE-correct fp32 square root, bit for bit what sqrtf() returns.  hipcc expands sqrtf() to v_sqrt_f32 (1 ulp) plus the
-// one-step correction below, wrapped in a scaling for arguments below 2^-96 (v_sqrt_f32 flushes denormals) and a fix-up for
-// 0 and inf: 17 instructions.  The arguments of this kernel (discriminants, squared lengths) are ordinary numbers, so the
-// wrapping only runs -- through sqrtf() itself -- when some lane of the wave really holds such an argument: 11 instructions
-// otherwise.  The kernel takes ~10 square roots per iteration of its main loop.
+// IEEE-correct fp32 square root, bit for bit what sqrtf() returns, for arguments that are ordinary numbers -- the kernel's
+// discriminants and squared lengths: ~10 per iteration of its main loop.  hipcc expands sqrtf() to v_sqrt_f32 (1 ulp) plus a
+// one-step correction, wrapped in a scaling for arguments below 2^-96 (v_sqrt_f32 flushes denormals) and a fix-up for 0 and
+// inf: 17 instructions.  Here that wrapping only runs -- through sqrtf() itself -- when an argument really needs it.
+// VOTE (the grid walks' kernels, render_body.h's ROOT_VOTE): the guard is a vote of the wave -- sqrtf() is exact everywhere, so
+// ordinary lanes that go through it with an odd one lose nothing -- i.e. one compare and a scalar branch, no exec-mask
+// bookkeeping around the root; and the root is the compiler's own correctly rounded sequence for flushed-denormal mode, one
+// v_rsq_f32 and seven plain instructions without a compare or a select (inside the guarded range every intermediate value is a
+// normal number).  Held to sqrtf() on all 2^32 bit patterns on the device (csrc/sqrt_sweep.hip).
+// !VOTE (the nested walk, whose spilled registers rise with the vote, and the glossy materials): the guard per lane, then
+// v_sqrt_f32 and the +-1 ulp correction.
+template <bool VOTE = false>
 __device__ __forceinline__ float rt_sqrtf(float x) {
     // [2^-96, inf): one unsigned compare on the bit pattern (negative numbers and NaN fall outside as well)
-    if (__builtin_expect((uint32_t)(__float_as_uint(x) - 0x0f800000u) >= (0x7f800000u - 0x0f800000u), 0)) return sqrtf(x);
+    const bool odd = (uint32_t)(__float_as_uint(x) - 0x0f800000u) >= (0x7f800000u - 0x0f800000u);
+    if (__builtin_expect(VOTE ? __builtin_amdgcn_ballot_w64(odd) != 0ull : odd, 0)) return sqrtf(x);
+    if (VOTE) {
+        const float r = __builtin_amdgcn_rsqf(x);
+        float s = x * r, h = 0.5f * r;
+        const float e = fmaf(-h, s, 0.5f);
+        h = fmaf(h, e, h), s = fmaf(s, e, s);
+        const float d = fmaf(-s, s, x);
+        return fmaf(d, h, s);
+    }
     const float s = __builtin_amdgcn_sqrtf(x);
     const float s_dn = __uint_as_float(__float_as_uint(s) - 1u), s_up = __uint_as_float(__float_as_uint(s) + 1u);
     const float r_dn = fmaf(-s_dn, s, x), r_up = fmaf(-s_up, s, x);
