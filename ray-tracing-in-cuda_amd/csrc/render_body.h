@@ -229,15 +229,16 @@
                 const float sq = rt_sqrtf<ROOT_VOTE>(disc);
                 float root = (-hb - sq) * rinv_a;
                 if (root < kTMin || best_t < root) root = (-hb + sq) * rinv_a;
-                if (!(root < kTMin || best_t < root)) {
-                    bool take = true;
-                    if (root == best_t && best_id >= 0)
-                        take = lidx(idx) > lidx(best_id);
-                    if (take) {
-                        best_t = root;
-                        best_id = idx;
-                    }
+                // straight-line: the winner by two selects, and the tie rule -- which reads global memory and practically
+                // never runs -- behind one vote of the wave.  (As three nested lane-level `if`s -- range, tie, take -- every
+                // entry paid three exec-mask save / branch / restore groups.)
+                bool take = !(root < kTMin || best_t < root);
+                const bool tie = take && root == best_t && best_id >= 0;
+                if (__builtin_expect(__builtin_amdgcn_ballot_w64(tie) != 0ull, 0)) {
+                    if (tie) take = lidx(idx) > lidx(best_id);
                 }
+                best_t = take ? root : best_t;
+                best_id = take ? idx : best_id;
             };
             // the point where the ray meets a triangle's plane and its ray parameter (hittable.py:44-52, 61):
             // n = the unit normal turned towards the origin, theta = d.n / |d| < 0, r = o - d/|d| (oc.n) / theta
@@ -680,7 +681,12 @@
                         if (k < kend) {
                             const int idx = WIDE ? (int)g_items32[k] : (int)g_items[k];
                             const int j_raw = WIDE ? (int)g_items32[k + 1] : (int)g_items[k + 1];  // (one entry past the list at worst: the next list, or the padding entry behind the last one)
-                            const int jdx = k + 1 < kend ? j_raw : P.np + CSIZE;
+                            // (the compact tables of the product instances take the entry as it is: a sphere of the next list,
+                            //  whose test finds a true hit or none -- the closest hit is a minimum over true hits, so a
+                            //  candidate nobody needs changes nothing, and the select and its compare are gone from every
+                            //  pair pass.  The wide tables list other primitives behind a cell's spheres, and the counting
+                            //  builds count tests: both keep the never-hit slot.)
+                            const int jdx = ((!COUNT && !WIDE) || k + 1 < kend) ? j_raw : P.np + CSIZE;
                             if (COUNT) c_lane_clusters += k + 1 < kend ? 2u : 1u;
                             k += 2;
                             const float4 S = sph[idx], T = sph[jdx];

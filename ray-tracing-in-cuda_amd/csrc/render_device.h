@@ -115,8 +115,8 @@ __device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, fl
 // one-step correction, wrapped in a scaling for arguments below 2^-96 (v_sqrt_f32 flushes denormals) and a fix-up for 0 and
 // inf: 17 instructions.  Here that wrapping only runs -- through sqrtf() itself -- when an argument really needs it.
 // VOTE (the grid walks' kernels, render_body.h's ROOT_VOTE): the guard is a vote of the wave -- sqrtf() is exact everywhere, so
-// ordinary lanes that go through it with an odd one lose nothing -- i.e. one compare and a scalar branch, no exec-mask
-// bookkeeping around the root; and the root is the compiler's own correctly rounded sequence for flushed-denormal mode, one
+// ordinary lanes that go through it with an odd one lose nothing -- i.e. one compare and one scalar branch (not taken) behind
+// the root, no exec-mask bookkeeping around it; and the root is the compiler's own correctly rounded sequence for flushed-denormal mode, one
 // v_rsq_f32 and seven plain instructions without a compare or a select (inside the guarded range every intermediate value is a
 // normal number).  Held to sqrtf() on all 2^32 bit patterns on the device (csrc/sqrt_sweep.hip).
 // !VOTE (the nested walk, whose spilled registers rise with the vote, and the glossy materials): the guard per lane, then
@@ -125,15 +125,20 @@ template <bool VOTE = false>
 __device__ __forceinline__ float rt_sqrtf(float x) {
     // [2^-96, inf): one unsigned compare on the bit pattern (negative numbers and NaN fall outside as well)
     const bool odd = (uint32_t)(__float_as_uint(x) - 0x0f800000u) >= (0x7f800000u - 0x0f800000u);
-    if (__builtin_expect(VOTE ? __builtin_amdgcn_ballot_w64(odd) != 0ull : odd, 0)) return sqrtf(x);
     if (VOTE) {
+        // the root first, the vote after it: returning sqrtf(x) from inside the voted branch made the compiler rejoin the two
+        // paths through a mask and a second branch in front of every fast root.  A wave with an odd lane has run the
+        // sequence on arguments outside its range; it has no side effects, and sqrtf() replaces the result in every lane.
         const float r = __builtin_amdgcn_rsqf(x);
         float s = x * r, h = 0.5f * r;
         const float e = fmaf(-h, s, 0.5f);
         h = fmaf(h, e, h), s = fmaf(s, e, s);
         const float d = fmaf(-s, s, x);
-        return fmaf(d, h, s);
+        float res = fmaf(d, h, s);
+        if (__builtin_expect(__builtin_amdgcn_ballot_w64(odd) != 0ull, 0)) res = sqrtf(x);
+        return res;
     }
+    if (__builtin_expect(odd, 0)) return sqrtf(x);
     const float s = __builtin_amdgcn_sqrtf(x);
     const float s_dn = __uint_as_float(__float_as_uint(s) - 1u), s_up = __uint_as_float(__float_as_uint(s) + 1u);
     const float r_dn = fmaf(-s_dn, s, x), r_up = fmaf(-s_up, s, x);
@@ -143,9 +148,14 @@ __device__ __forceinline__ float rt_sqrtf(float x) {
 }
 
 // number of set bits of a lane mask as a 32-bit SCALAR (popcll's result is compared as a 64-bit value, for which the
-// scalar unit has no ordered compare: the comparison then runs on the vector ALU, once per pass of the walk's loops)
+// scalar unit has no ordered compare: the comparison then runs on the vector ALU, once per pass of the walk's loops).
+// One 64-bit scalar popcount: the builtin on two halves compiled to two 32-bit counts and an add, and the compare behind
+// it to a mask (s_cselect, s_and with exec, a branch on vcc) where four of the six sites now branch on scc.  Plain asm, not
+// volatile: a pure function of its operand.
 __device__ __forceinline__ int mask_count(unsigned long long m) {
-    return __builtin_amdgcn_readfirstlane(__builtin_popcount((uint32_t)m) + __builtin_popcount((uint32_t)(m >> 32)));
+    int r;
+    asm("s_bcnt1_i32_b64 %0, %1" : "=s"(r) : "s"(m) : "scc");
+    return r;
 }
 
 // fminf for operands that are results of fp32 arithmetic or +-inf, never a signalling NaN: the bare v_min_f32 / v_min3_f32,
