@@ -184,6 +184,14 @@ int rt_scene_set_russian_roulette(rt_scene *s, float p);
  * "light_sampling": true. */
 int rt_scene_set_light_sampling(rt_scene *s, int on);
 int rt_scene_get_light_sampling(const rt_scene *s); /* 1, 0, or -rt_status */
+/* Mesh lights: with on = 1 the list of sampled emitters (rt_scene_get_lights) also holds every triangle -- the triangles of
+ * an OBJ mesh among them, one light each -- whose material is a diffuse_light with a solid or checker texture and whose area
+ * and power are positive and finite (a degenerate triangle is skipped); a point on it is drawn uniformly by area, the
+ * density is stated with its geometric normal, vertex normals or not.  The switch only widens that list: without light
+ * sampling on it changes nothing that is rendered, and with on = 0 (default) the list, the tables and every frame are what
+ * they were, an emissive triangle being reached by the BSDF sample alone.  JSON: top-level "mesh_lights": true. */
+int rt_scene_set_mesh_lights(rt_scene *s, int on);
+int rt_scene_get_mesh_lights(const rt_scene *s); /* 1, 0, or -rt_status */
 /* Nested grid: a second grid level for scenes whose geometry is clustered (a detailed mesh standing in a room).  The candidate
  * search is one uniform grid whose cell comes from the extent of all primitives; a cell that a dense mesh overfills can only
  * hand its members to the set that is tested for every query.  With on = 1 such a scene -- one whose flat tables have a cell
@@ -198,9 +206,9 @@ int rt_scene_set_nested_grid(rt_scene *s, int on);
 int rt_scene_get_nested_grid(const rt_scene *s); /* 1, 0, or -rt_status */
 typedef struct rt_light {
     int32_t prim;        /* index into the primitive list                      */
-    int32_t shape;       /* rt_prim_type: sphere, xy / xz / yz rect or cylinder */
+    int32_t shape;       /* rt_prim_type: sphere, xy / xz / yz rect, cylinder or -- with mesh lights on -- triangle */
     float probability;   /* selection probability (the list sums to 1)         */
-    float area;          /* surface area (the cylinder's tube)                 */
+    float area;          /* surface area (the cylinder's tube; a triangle's |e1 x e2| / 2) */
     float emission[3];   /* emission (a checker texture: its even colour)      */
     float emission_odd[3]; /* a checker texture's odd colour (else = emission) */
 } rt_light;

@@ -349,6 +349,9 @@ public:
     void set_russian_roulette(float p) { check(rt_scene_set_russian_roulette(s_, p), "set_russian_roulette"); }
     // light sampling: next-event estimation + MIS at lambertian and fuzzy-metal vertices (rt_scene_set_light_sampling)
     void set_light_sampling(bool on) { check(rt_scene_set_light_sampling(s_, on ? 1 : 0), "set_light_sampling"); }
+    // mesh lights: emissive triangles join the emitters that light sampling samples (rt_scene_set_mesh_lights)
+    void set_mesh_lights(bool on) { check(rt_scene_set_mesh_lights(s_, on ? 1 : 0), "set_mesh_lights"); }
+    bool mesh_lights() const { return rt_scene_get_mesh_lights(s_) > 0; }
     // nested grid: overfull cells of the candidate grid get a sub-grid of their own (rt_scene_set_nested_grid)
     void set_nested_grid(bool on) { check(rt_scene_set_nested_grid(s_, on ? 1 : 0), "set_nested_grid"); }
     bool nested_grid() const { return rt_scene_get_nested_grid(s_) > 0; }

@@ -269,6 +269,8 @@ _sig("rt_scene_set_russian_roulette", C.c_int, _p, C.c_float)
 _sig("rt_scene_set_light_sampling", C.c_int, _p, C.c_int)
 _sig("rt_scene_get_light_sampling", C.c_int, _p)
 _sig("rt_scene_get_lights", C.c_int, _p, _p, C.c_int)
+_sig("rt_scene_set_mesh_lights", C.c_int, _p, C.c_int)
+_sig("rt_scene_get_mesh_lights", C.c_int, _p)
 _sig("rt_scene_set_environment", C.c_int, _p, C.c_int, C.c_int, _p, C.c_float, C.c_float)
 _sig("rt_scene_set_environment_file", C.c_int, _p, C.c_char_p, C.c_float, C.c_float)
 _sig("rt_scene_get_environment", C.c_int, _p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float), _p,
@@ -340,6 +342,7 @@ C_SYMBOLS = [
     "rt_quantize_rgb8", "rt_philox4x32_10", "rt_aabb_hit", "rt_sample_stream", "rt_write_png",
     "rt_scene_output_file", "rt_scene_rotate_cylinders", "rt_scene_set_output_file", "rt_scene_dna", "rt_scene_clone",
     "rt_scene_set_light_sampling", "rt_scene_get_light_sampling", "rt_scene_get_lights",
+    "rt_scene_set_mesh_lights", "rt_scene_get_mesh_lights",
     "rt_render_hip_adaptive", "rt_render_hip_adaptive_device",
     "rt_scene_set_nested_grid", "rt_scene_get_nested_grid", "rt_scene_nested_info",
     "rt_scene_set_environment", "rt_scene_set_environment_file", "rt_scene_get_environment", "rt_environment_eval",
@@ -428,6 +431,15 @@ class Scene:
     @property
     def light_sampling(self) -> bool:
         return _check_id(_lib.rt_scene_get_light_sampling(self._h), "get_light_sampling") != 0
+
+    def set_mesh_lights(self, on: bool = True):
+        """Emissive triangles (OBJ meshes: one light per triangle) join the emitters light sampling samples (include/rtmi.h,
+        rt_scene_set_mesh_lights); False, the default, leaves them to the BSDF sample."""
+        _check(_lib.rt_scene_set_mesh_lights(self._h, 1 if on else 0), "set_mesh_lights")
+
+    @property
+    def mesh_lights(self) -> bool:
+        return _check_id(_lib.rt_scene_get_mesh_lights(self._h), "get_mesh_lights") != 0
 
     def set_environment(self, rgb=None, scale: float = 1.0, rotate: float = 0.0, file: str = None):
         """Environment map (include/rtmi.h, rt_scene_set_environment): ``rgb`` is a rows x cols x 3 float array in lat-long

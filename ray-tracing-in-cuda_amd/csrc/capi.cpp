@@ -176,6 +176,18 @@ int rt_scene_get_light_sampling(const rt_scene *s) {
     return s->s.light_sampling ? 1 : 0;
 }
 
+int rt_scene_set_mesh_lights(rt_scene *s, int on) {
+    if (bad_scene(s, "rt_scene_set_mesh_lights")) return RT_ERR_ARG;
+    s->s.mesh_lights = on != 0;
+    s->s.touch();
+    return RT_OK;
+}
+
+int rt_scene_get_mesh_lights(const rt_scene *s) {
+    if (bad_scene(s, "rt_scene_get_mesh_lights")) return -RT_ERR_ARG;
+    return s->s.mesh_lights ? 1 : 0;
+}
+
 int rt_scene_set_nested_grid(rt_scene *s, int on) {
     if (bad_scene(s, "rt_scene_set_nested_grid")) return RT_ERR_ARG;
     s->s.nested_grid = on != 0;

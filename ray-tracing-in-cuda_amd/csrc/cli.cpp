@@ -25,6 +25,7 @@
 // focuses the camera on what it meets (focus_dist = t |dir|, rt_scene_set_camera) before the render.
 // Smooth shading: --mesh-normals flat|file|smooth[:DEG] gives every "mesh" of the scene file its vertex normals
 // that way, whatever its own "normals" says (DEG: the crease angle of the generated normals, 180 without).
+// Mesh lights: --mesh-lights lists emissive triangles among the emitters --nee samples (rt_scene_set_mesh_lights).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -56,7 +57,7 @@ static int usage(const char *argv0) {
             "usage: %s [-f scene.json | --rtiow] [-w W] [-h H] [-d DEPTH] [-spp N] [-o out.ppm]\n"
             "          [--seed S] [--scene-seed S] [--device N] [--chunk N] [--dump-json file] [--count] [--no-png]\n"
             "          [--acc-in sums.bin] [--acc-out sums.bin] [--spp-begin FIRST] [--rr SURVIVAL_PROBABILITY] [--nee]\n"
-            "          [--nested-grid] [--env map.hdr [--env-scale S] [--env-rotate DEG]]\n"
+            "          [--mesh-lights] [--nested-grid] [--env map.hdr [--env-scale S] [--env-rotate DEG]]\n"
             "          [--gpus N] [--tile-rows R] [--adaptive THRESHOLD [--min-spp N] [--max-spp N]]\n"
             "          [--denoise] [--aov PREFIX] [--feature-spp N]\n"
             "          [--tonemap clamp|reinhard|aces] [--exposure EV] [--auto-exposure [KEY]] [--white W]\n"
@@ -126,6 +127,7 @@ int main(int argc, char **argv) {
     long long spp_begin = -1;
     double rr = -1.0;  // Russian roulette: keep the scene file's setting
     bool nee = false;  // light sampling: on if the scene file or --nee says so
+    bool mesh_lights = false;  // emissive triangles are sampled too: on if the scene file or --mesh-lights says so
     bool nested = false;  // nested grid: on if the scene file or --nested-grid says so
     std::string env_file;  // environment map: replaces the scene file's
     double env_scale = 1.0, env_rotate = 0.0;
@@ -173,6 +175,7 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--spp-begin")) spp_begin = atoll(need("--spp-begin"));
         else if (!strcmp(argv[i], "--rr")) rr = atof(need("--rr"));
         else if (!strcmp(argv[i], "--nee")) nee = true;
+        else if (!strcmp(argv[i], "--mesh-lights")) mesh_lights = true;
         else if (!strcmp(argv[i], "--nested-grid")) nested = true;
         else if (!strcmp(argv[i], "--mesh-normals")) {
             const std::string v = need("--mesh-normals");
@@ -335,6 +338,10 @@ int main(int argc, char **argv) {
         return 1;
     }
     if (nee && rt_scene_set_light_sampling(sc, 1) != RT_OK) {
+        fprintf(stderr, "rtmi: %s\n", rt_last_error());
+        return 1;
+    }
+    if (mesh_lights && rt_scene_set_mesh_lights(sc, 1) != RT_OK) {
         fprintf(stderr, "rtmi: %s\n", rt_last_error());
         return 1;
     }

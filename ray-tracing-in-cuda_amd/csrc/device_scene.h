@@ -18,10 +18,11 @@
 //     mat     [nm]  3 x float4   {kind(bits), p0, p1, p2} {c0.xyz, p3} {c1.xyz, 0}
 //     image   texels of the image textures, one 32-bit word each (r | g << 8 | b << 16), row-major
 //   LIGHT part (only with light sampling on and at least one sampled emitter; global memory, read by the light-sampling kernels)
-//     light   [nl]  7 x float4   {shape(bits): 0 sphere, 1 rect, 2 cylinder, grouped id(bits), selection probability, 1/area}
+//     light   [nl]  7 x float4   {shape(bits): 0 sphere, 1 rect, 2 cylinder, 4 triangle, grouped id(bits), selection probability, 1/area}
 //                                {emission even.rgb, checker(bits)} {emission odd.rgb, 0}, then the geometry:
 //                                sphere {c.xyz, |r|}; rect {a0, a1, b0, b1} {k, axis(bits), 0, 0}; cylinder o2w rows 0..2,
-//                                {|radius|, zmin, zmax, 0}
+//                                {|radius|, zmin, zmax, 0}; triangle (mesh lights) {v1, 0} {e1 = v2 - v1, 0}
+//                                {e2 = v3 - v1, 0} {the geometric unit normal, 0}
 //     alias   [nl]  1 x float4   {threshold, alias light(bits), 0, 0}: one draw u picks i = floor(u nl), then i or its alias
 //     slot    [ns + nr + nc + nt] one 32-bit word per grouped primitive id: its light, -1 = not a sampled light
 //     (an environment that is sampled is the last light: {3, -1, selection probability, 1 / 4 pi}, no geometry)

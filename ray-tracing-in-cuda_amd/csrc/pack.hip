@@ -1047,6 +1047,7 @@ void write_lights(float *I, const RenderParams &L, const Scene &s, const SphereS
         if (S.slots[k] >= 0) group_id[(size_t)S.slots[k]] = k;
     for (int k = 0; k < L.nr; ++k) group_id[(size_t)O.rec[k]] = L.ns + k;
     for (int k = 0; k < L.nc; ++k) group_id[(size_t)O.cyl[k]] = L.ns + L.nr + k;
+    for (int k = 0; k < L.nt; ++k) group_id[(size_t)O.tri[k]] = L.ns + L.nr + L.nc + k;
     int32_t *slot = reinterpret_cast<int32_t *>(rec4(I, L.off_lslot));
     for (int k = 0; k < L.ns + L.nr + L.nc + L.nt; ++k) slot[k] = -1;
     for (int i = 0; i < L.nl; ++i) {
@@ -1060,7 +1061,7 @@ void write_lights(float *I, const RenderParams &L, const Scene &s, const SphereS
         const int gid = group_id[(size_t)l.prim];
         slot[gid] = i;
         float *r = rec4(I, L.off_light + RT_LIGHT_STRIDE * i);
-        const int shape = p.type == RT_PRIM_SPHERE ? 0 : (p.type == RT_PRIM_CYLINDER ? 2 : 1);
+        const int shape = p.type == RT_PRIM_SPHERE ? 0 : (p.type == RT_PRIM_CYLINDER ? 2 : (p.type == RT_PRIM_TRIANGLE ? 4 : 1));
         r[0] = bits(shape), r[1] = bits(gid), r[2] = (float)l.prob, r[3] = (float)(1.0 / l.area);
         for (int c3 = 0; c3 < 3; ++c3) r[4 + c3] = l.even[c3], r[8 + c3] = l.odd[c3];
         r[7] = bits(l.checker ? 1 : 0);
@@ -1070,9 +1071,14 @@ void write_lights(float *I, const RenderParams &L, const Scene &s, const SphereS
         } else if (shape == 1) {
             g[0] = p.f[0], g[1] = p.f[1], g[2] = p.f[2], g[3] = p.f[3];
             g[4] = p.f[4], g[5] = bits(p.type - RT_PRIM_XY_RECT);
-        } else {
+        } else if (shape == 2) {
             memcpy(g, p.m, 12 * sizeof(float));
             g[12] = std::fabs(p.f[0]), g[13] = p.f[1], g[14] = p.f[2];
+        } else {  // triangle (mesh lights): v1, the edges from it (fp32 differences) and the GEOMETRIC unit normal
+            for (int c3 = 0; c3 < 3; ++c3) {
+                g[c3] = p.m[c3], g[4 + c3] = p.m[3 + c3] - p.m[c3], g[8 + c3] = p.m[6 + c3] - p.m[c3];
+                g[12 + c3] = p.m[9 + c3];
+            }
         }
     }
     // alias table (Vose): one uniform draw picks bucket i = floor(u n), then i itself below the threshold, else its alias

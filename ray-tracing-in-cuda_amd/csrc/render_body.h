@@ -1829,15 +1829,27 @@
                     const float yx = axis == 2 ? g2.x : a, yy = axis == 0 ? b : (axis == 1 ? g2.x : a), yz = axis == 0 ? g2.x : b;
                     ldx = yx - px, ldy = yy - py, ldz = yz - pz;
                     lnx = axis == 2 ? 1.0f : 0.0f, lny = axis == 1 ? 1.0f : 0.0f, lnz = axis == 0 ? 1.0f : 0.0f;
-                } else {  // cylinder tube: uniform by area in object space, through the (rigid) object-to-world transform
+                } else {
+                    // the four geometry records of a tube or a triangle, loaded once for both: nothing of the triangle's is
+                    // live outside its branch
                     const float4 m0 = lr[3], m1 = lr[4], m2 = lr[5], g = lr[6];
-                    float sp, cp;
-                    sincosf((2.0f * kPi) * u1, &sp, &cp);
-                    const float qx = g.x * cp, qy = g.x * sp, qz = fmaf(u2, g.z - g.y, g.y);
-                    ldx = fmaf(m0.x, qx, fmaf(m0.y, qy, fmaf(m0.z, qz, m0.w))) - px;
-                    ldy = fmaf(m1.x, qx, fmaf(m1.y, qy, fmaf(m1.z, qz, m1.w))) - py;
-                    ldz = fmaf(m2.x, qx, fmaf(m2.y, qy, fmaf(m2.z, qz, m2.w))) - pz;
-                    lnx = fmaf(m0.x, cp, m0.y * sp), lny = fmaf(m1.x, cp, m1.y * sp), lnz = fmaf(m2.x, cp, m2.y * sp);
+                    if (shape == 4) {  // triangle (mesh lights): uniform by area, y = v1 + b1 e1 + b2 e2 with
+                        // {v1, e1, e2, n} = {m0, m1, m2, g}
+                        const float s = sqrtf(u1);
+                        const float b1 = 1.0f - s, b2 = u2 * s;
+                        ldx = fmaf(b2, m2.x, fmaf(b1, m1.x, m0.x)) - px;
+                        ldy = fmaf(b2, m2.y, fmaf(b1, m1.y, m0.y)) - py;
+                        ldz = fmaf(b2, m2.z, fmaf(b1, m1.z, m0.z)) - pz;
+                        lnx = g.x, lny = g.y, lnz = g.z;  // the geometric normal, whatever the vertex normals (the hit side's too)
+                    } else {  // cylinder tube: uniform by area in object space, through the (rigid) object-to-world transform
+                        float sp, cp;
+                        sincosf((2.0f * kPi) * u1, &sp, &cp);
+                        const float qx = g.x * cp, qy = g.x * sp, qz = fmaf(u2, g.z - g.y, g.y);
+                        ldx = fmaf(m0.x, qx, fmaf(m0.y, qy, fmaf(m0.z, qz, m0.w))) - px;
+                        ldy = fmaf(m1.x, qx, fmaf(m1.y, qy, fmaf(m1.z, qz, m1.w))) - py;
+                        ldz = fmaf(m2.x, qx, fmaf(m2.y, qy, fmaf(m2.z, qz, m2.w))) - pz;
+                        lnx = fmaf(m0.x, cp, m0.y * sp), lny = fmaf(m1.x, cp, m1.y * sp), lnz = fmaf(m2.x, cp, m2.y * sp);
+                    }
                 }
                 const float d2 = dot3(ldx, ldy, ldz, ldx, ldy, ldz);
                 pl = ((h.z * h.w) * (d2 * sqrtf(d2))) / fabsf(dot3(lnx, lny, lnz, ldx, ldy, ldz));

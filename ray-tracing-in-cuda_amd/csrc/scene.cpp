@@ -723,6 +723,10 @@ int scene_from_json(const char *text, size_t len, Scene &s, const char *base_dir
         if (f->kind != JsonValue::Bool) r.fail("top level: \"light_sampling\" must be a boolean");
         else s.light_sampling = f->b;
     }
+    if (const JsonValue *f = root.find("mesh_lights")) {
+        if (f->kind != JsonValue::Bool) r.fail("top level: \"mesh_lights\" must be a boolean");
+        else s.mesh_lights = f->b;
+    }
     if (const JsonValue *f = root.find("nested_grid")) {
         if (f->kind != JsonValue::Bool) r.fail("top level: \"nested_grid\" must be a boolean");
         else s.nested_grid = f->b;
@@ -1120,6 +1124,7 @@ std::string scene_to_json(const Scene &s) {
     o += std::string("  \"defocus_blur\": ") + ((s.flags & RT_FLAG_DEFOCUS_BLUR) ? "true" : "false") + ",\n";
     if (s.rr_p > 0.0f) o += "  \"russian_roulette\": " + json_double((double)s.rr_p) + ",\n";
     if (s.light_sampling) o += "  \"light_sampling\": true,\n";
+    if (s.mesh_lights) o += "  \"mesh_lights\": true,\n";
     if (s.nested_grid) o += "  \"nested_grid\": true,\n";
     if (s.env) {
         o += "  \"environment\": {";
@@ -1438,7 +1443,19 @@ std::vector<SceneLight> scene_lights(const Scene &s) {
             l.area = 2.0 * pi * std::fabs((double)p.f[0]) * ((double)p.f[2] - p.f[1]);
             break;
         }
-        default: continue;  // triangles stay BSDF-only
+        case RT_PRIM_TRIANGLE: {
+            // mesh lights, opt-in: one light per triangle, |e1 x e2| / 2 in fp64 from the stored vertices.  A
+            // degenerate triangle -- no area, or a sliver whose area or 1 / area the light record's fp32 words cannot hold --
+            // is skipped: it stays a BSDF-only emitter
+            if (!s.mesh_lights) continue;
+            double a[3], b[3], n[3];
+            for (int k = 0; k < 3; ++k) a[k] = (double)p.m[3 + k] - (double)p.m[k], b[k] = (double)p.m[6 + k] - (double)p.m[k];
+            v3cross(a, b, n);
+            l.area = 0.5 * v3len(n);
+            if (!((float)l.area > 0.0f) || !std::isfinite((float)(1.0 / l.area))) continue;
+            break;
+        }
+        default: continue;
         }
         const double power = l.area * 0.5 * (luminance(l.even) + luminance(l.odd));
         if (!(l.area > 0.0) || !(power > 0.0) || !std::isfinite(power)) continue;

@@ -54,6 +54,7 @@ struct Scene {
     uint32_t flags = 0;
     float rr_p = 0.0f;  // Russian-roulette survival probability per bounce, 0 = off
     bool light_sampling = false;  // next-event estimation + MIS (rt_scene_set_light_sampling)
+    bool mesh_lights = false;     // scene_lights() also lists emissive triangles (rt_scene_set_mesh_lights)
     bool nested_grid = false;     // overfull grid cells get a sub-grid (rt_scene_set_nested_grid)
     std::string output_file = "main.png";  // parser.hpp:566-567 default
     CameraParams cam;
@@ -72,9 +73,9 @@ struct Scene {
     void touch() { ++version; }
 };
 
-// the emitters that light sampling samples (spheres, axis-aligned rects and rigid cylinder tubes whose material is a
-// diffuse_light with a solid or checker texture and nonzero power), in list order, with their selection probabilities
-// (proportional to area x mean emission luminance)
+// the emitters that light sampling samples (spheres, axis-aligned rects and rigid cylinder tubes -- with Scene::mesh_lights,
+// triangles too, one light each -- whose material is a diffuse_light with a solid or checker texture and nonzero power), in
+// list order, with their selection probabilities (proportional to area x mean emission luminance)
 struct SceneLight {
     int prim = 0, type = 0;  // list index, rt_prim_type; the environment (always last): -1, RT_LIGHT_ENVIRONMENT
     double area = 0.0, prob = 0.0;
