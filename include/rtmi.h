@@ -72,9 +72,29 @@ typedef enum rt_mat_type {
 typedef enum rt_tex_type {
     RT_TEX_SOLID = 0,   /* texture.cuh:14-31  c0                             */
     RT_TEX_CHECKER = 1, /* texture.cuh:33-57  c0 = even, c1 = odd            */
-    RT_TEX_IMAGE = 2    /* taichi-version/material.py:137-144: texel lookup by the hit record's (u, v);
+    RT_TEX_IMAGE = 2,   /* taichi-version/material.py:137-144: texel lookup by the hit record's (u, v);
                            c0 = {image index, rows, columns} as floats (exact: small integers) */
+    RT_TEX_NOISE = 3    /* a procedural solid texture: c0 + s (c1 - c0), s in [0, 1] from lattice noise at the
+                           hit point; the parameters (rt_noise) live beside the texture table: rt_scene_get_noise */
 } rt_tex_type;
+
+/* Noise textures (the model: csrc/rt_noise.h).  Gradient noise n(q, seed) on the hashed integer lattice, summed over
+ * `octaves` octaves of doubling frequency and halving amplitude from `scale` x the world-space hit point p:
+ *   S = sum 2^-o n(2^o scale p, seed + o),  A = the same sum over |n|
+ *   fbm: s = clamp(0.5 + 0.5 S, 0, 1)    turbulence: s = min(1, A)    marble: s = 0.5 + 0.5 sin(scale p[axis] + distortion A) */
+typedef enum rt_noise_style {
+    RT_NOISE_STYLE_FBM = 0,
+    RT_NOISE_STYLE_TURBULENCE = 1,
+    RT_NOISE_STYLE_MARBLE = 2
+} rt_noise_style;
+
+typedef struct rt_noise {
+    int32_t style, octaves; /* rt_noise_style; 1..8                                                      */
+    uint32_t seed;
+    int32_t axis;           /* marble alone: 0 = x, 1 = y, 2 = z (the other styles store 0)               */
+    float scale;            /* finite, > 0                                                               */
+    float distortion;       /* marble alone: finite (the other styles store 0)                           */
+} rt_noise;
 
 typedef struct rt_prim {
     int32_t type;      /* rt_prim_type                                       */
@@ -367,6 +387,16 @@ int rt_scene_add_image_texture(rt_scene *s, int rows, int cols, const uint8_t *r
 int rt_scene_add_image_texture_file(rt_scene *s, const char *path);
 /* rows / cols of image texture `texture` and, if out != NULL, its rows*cols*3 bytes; -rt_status on error */
 int rt_scene_get_image(const rt_scene *s, int texture, int *rows, int *cols, uint8_t *out, size_t cap);
+/* Noise texture: value(p) = c0 + s (c1 - c0) per channel with s from `noise` at the world-space hit point (on
+ * a moving sphere too: the texture swims, as the checker does).  Usable wherever a texture id is: lambertian, plastic (body
+ * colour) and diffuse_light; such an emitter emits what the texture says at the hit and, like an image-textured one, is not
+ * among the sampled lights.  Colours are finite and >= 0 (they may exceed 1), scale finite and > 0, octaves in 1..8, style
+ * in 0..2; for marble, axis in 0..2 and distortion finite (the other styles have neither: what the caller's record holds
+ * there is not read, and zeros are stored).  Anything else is RT_ERR_ARG.  A scene with one runs the general (triangle /
+ * texture) kernels.  -> texture id or -rt_status */
+int rt_scene_add_noise_texture(rt_scene *s, const float c0[3], const float c1[3], const rt_noise *noise);
+/* the parameters of noise texture `texture`; RT_ERR_ARG if it is none */
+int rt_scene_get_noise(const rt_scene *s, int texture, rt_noise *out);
 /* Triangle(v1, v2, v3, u1, u2, u3, material), taichi-version/hittable.py:95-110; uv pointers may be NULL (zeros) */
 int rt_scene_add_triangle(rt_scene *s, const float v1[3], const float v2[3], const float v3[3],
                           const float uv1[2], const float uv2[2], const float uv3[2], int material);
@@ -429,7 +459,10 @@ int rt_scene_get_textures(const rt_scene *s, rt_texture *out, int cap);   /* -> 
 /* The device tables the host builds for a scene (no GPU needed: host logic tests, tools).  The reference rebuilds its object
  * graph on the device (move_to_device<<<1,1>>>, main.cu:374-446); here the host flattens the scene into ONE image of 16-byte
  * records -- sphere slots, the other primitives' records and boxes, the uniform grid over every primitive type (cells + lists),
- * cold records, materials -- which one memcpy uploads (csrc/device_scene.h, csrc/pack.hip pack_scene). */
+ * cold records, materials -- which one memcpy uploads (csrc/device_scene.h, csrc/pack.hip pack_scene).  (The parameters of
+ * the noise textures, DESIGN 7o, are one record each behind the image textures' texels: {scale, distortion, seed, style |
+ * axis << 2 | octaves << 4}; a material with such a texture holds the record's offset in the fourth word of its second
+ * record.  No field here says where they begin: a scene without a noise texture has none and packs to the bytes it did.) */
 typedef struct rt_table_info {
     int32_t image_floats;      /* size of the image (rt_scene_table_image) */
     int32_t grid_wide;         /* 1: wide tables (32-bit entries, two words per cell: every primitive type listed); 0: compact
@@ -661,7 +694,7 @@ int rt_abi_version(void);
 /* sizeof of the ABI structs as this library was compiled (binding self-checks):
  * 0 rt_opts, 1 rt_stats, 2 rt_prim, 3 rt_material, 4 rt_texture, 5 rt_camera, 6 rt_scene_info, 7 rt_table_info,
  * 8 rt_adaptive, 9 rt_adaptive_stats, 10 rt_nested_info, 16 rt_denoise, 17 rt_medium, 18 rt_moving_sphere, 19 rt_display,
- * 20 rt_display_stats, 21 rt_ray, 22 rt_hit; else 0 */
+ * 20 rt_display_stats, 21 rt_ray, 22 rt_hit, 24 rt_noise; else 0 */
 size_t rt_struct_size(int which);
 /* number of usable gfx950 devices, or -rt_status */
 int rt_device_count(void);

@@ -49,6 +49,7 @@ struct mytexture {
     // image texture (taichi-version/material.py:96-110, 137-144): rows x cols texels, R G B bytes
     int rows = 0, cols = 0;
     std::vector<uint8_t> rgb;
+    rt_noise noise{};  // noise texture: c0, c1 are its two colours
 };
 inline std::shared_ptr<mytexture> solid_color(color c) {  // texture.cuh:18-19
     auto t = std::make_shared<mytexture>();
@@ -64,6 +65,16 @@ inline std::shared_ptr<mytexture> checker_texture(color even, color odd) {  // t
 inline std::shared_ptr<mytexture> image_texture(int rows, int cols, std::vector<uint8_t> rgb) {
     auto t = std::make_shared<mytexture>();
     t->type = RT_TEX_IMAGE, t->rows = rows, t->cols = cols, t->rgb = std::move(rgb);
+    return t;
+}
+
+// a procedural solid texture: c0 + s (c1 - c0) with s from fBm, turbulence or marble noise at the hit point
+inline std::shared_ptr<mytexture> noise_texture(color c0, color c1, int style = RT_NOISE_STYLE_FBM, float scale = 1.0f, int octaves = 1,
+                                                uint32_t seed = 0, int axis = 1, float distortion = 5.0f) {
+    auto t = std::make_shared<mytexture>();
+    t->type = RT_TEX_NOISE, t->c0 = c0, t->c1 = c1;
+    t->noise.style = style, t->noise.octaves = octaves, t->noise.seed = seed, t->noise.axis = axis;
+    t->noise.scale = scale, t->noise.distortion = distortion;
     return t;
 }
 
@@ -445,6 +456,7 @@ private:
             if (kv.first == t) return kv.second;
         int id = t->type == RT_TEX_CHECKER ? rt_scene_add_checker(s_, t->c0.e, t->c1.e)
                  : t->type == RT_TEX_IMAGE ? rt_scene_add_image_texture(s_, t->rows, t->cols, t->rgb.data())
+                 : t->type == RT_TEX_NOISE ? rt_scene_add_noise_texture(s_, t->c0.e, t->c1.e, &t->noise)
                                            : rt_scene_add_solid_color(s_, t->c0.e);
         if (id < 0) throw error(-id, "texture");
         texs_.emplace_back(t, id);

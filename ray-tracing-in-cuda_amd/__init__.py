@@ -242,6 +242,18 @@ _sig("rt_scene_add_cylinder", C.c_int, _p, C.c_float, C.c_float, C.c_float, C.c_
 _sig("rt_scene_add_image_texture", C.c_int, _p, C.c_int, C.c_int, _p)
 _sig("rt_scene_add_image_texture_file", C.c_int, _p, C.c_char_p)
 _sig("rt_scene_get_image", C.c_int, _p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), _p, C.c_size_t)
+
+
+class Noise(C.Structure):  # rt_noise
+    _fields_ = [("style", C.c_int32), ("octaves", C.c_int32), ("seed", C.c_uint32), ("axis", C.c_int32), ("scale", C.c_float),
+                ("distortion", C.c_float)]
+
+
+NOISE_STYLES = {"fbm": 0, "turbulence": 1, "marble": 2}
+NOISE_AXES = {"x": 0, "y": 1, "z": 2}
+_sig("rt_scene_add_noise_texture", C.c_int, _p, _f3, _f3, C.POINTER(Noise))
+_sig("rt_scene_get_noise", C.c_int, _p, C.c_int, C.POINTER(Noise))
+assert _lib.rt_struct_size(24) == C.sizeof(Noise) == 24
 _sig("rt_scene_add_triangle", C.c_int, _p, _f3, _f3, _f3, _f3, _f3, _f3, C.c_int)
 _sig("rt_scene_add_obj", C.c_int, _p, C.c_char_p, C.c_int, C.c_float, _f3, _f3)
 _sig("rt_scene_add_triangle_normals", C.c_int, _p, _f3, _f3, _f3, _f3, _f3, _f3, _f3, _f3, _f3, C.c_int)
@@ -331,7 +343,7 @@ C_SYMBOLS = [
     "rt_scene_load_json", "rt_scene_parse_json", "rt_scene_rtiow", "rt_scene_to_json", "rt_scene_free",
     "rt_scene_new", "rt_scene_set_background", "rt_scene_set_camera", "rt_scene_add_solid_color",
     "rt_scene_add_checker", "rt_scene_add_lambertian", "rt_scene_add_metal", "rt_scene_add_dielectric",
-    "rt_scene_add_rough_metal", "rt_scene_add_plastic",
+    "rt_scene_add_rough_metal", "rt_scene_add_plastic", "rt_scene_add_noise_texture", "rt_scene_get_noise",
     "rt_scene_add_diffuse_light", "rt_scene_add_sphere", "rt_scene_add_rect", "rt_scene_add_cylinder",
     "rt_scene_add_image_texture", "rt_scene_add_image_texture_file", "rt_scene_get_image", "rt_scene_add_triangle",
     "rt_scene_add_obj", "rt_scene_add_triangle_normals", "rt_scene_add_obj_normals", "rt_set_mesh_normals_override",
@@ -541,6 +553,24 @@ class Scene:
             raise ValueError("image texture pixels must have shape (rows, cols, 3)")
         return _check_id(_lib.rt_scene_add_image_texture(self._h, px.shape[0], px.shape[1], px.ctypes.data_as(C.c_void_p)),
                          "image_texture")
+
+    def noise_texture(self, color0, color1, style="fbm", scale=1.0, octaves=1, seed=0, axis="y", distortion=5.0) -> int:
+        """A procedural solid texture: color0 + s (color1 - color0) with s in [0, 1] from lattice noise at the hit
+        point.  style: "fbm", "turbulence" or "marble"; axis ("x", "y", "z") and distortion are marble's alone."""
+        if style not in NOISE_STYLES:
+            raise ValueError('noise_texture style must be "fbm", "turbulence" or "marble"')
+        if axis not in NOISE_AXES:
+            raise ValueError('noise_texture axis must be "x", "y" or "z"')
+        n = Noise(NOISE_STYLES[style], int(octaves), int(seed) & 0xFFFFFFFF, NOISE_AXES[axis], float(scale), float(distortion))
+        return _check_id(_lib.rt_scene_add_noise_texture(self._h, _v3(color0), _v3(color1), C.byref(n)), "noise_texture")
+
+    def noise(self, texture: int) -> dict:
+        """The parameters of noise texture `texture` as noise_texture() takes them (a style other than marble: axis "x",
+        distortion 0 -- it has neither)."""
+        n = Noise()
+        _check(_lib.rt_scene_get_noise(self._h, texture, C.byref(n)), "rt_scene_get_noise")
+        return {"style": [k for k, v in NOISE_STYLES.items() if v == n.style][0], "scale": float(n.scale), "octaves": int(n.octaves),
+                "seed": int(n.seed), "axis": "xyz"[n.axis], "distortion": float(n.distortion)}
 
     def get_image(self, texture: int) -> np.ndarray:
         rows, cols = C.c_int(), C.c_int()

@@ -63,6 +63,7 @@ size_t rt_struct_size(int which) {
     case 20: return sizeof(rt_display_stats);
     case 21: return sizeof(rt_ray);
     case 22: return sizeof(rt_hit);
+    case 24: return sizeof(rt_noise);  // (23 stays 0)
     default: return 0;
     }
 }
@@ -266,6 +267,30 @@ static int add_texture(rt_scene *s, int type, const float a[3], const float b[3]
 int rt_scene_add_solid_color(rt_scene *s, const float rgb[3]) { return add_texture(s, RT_TEX_SOLID, rgb, rgb); }
 int rt_scene_add_checker(rt_scene *s, const float even[3], const float odd[3]) {
     return add_texture(s, RT_TEX_CHECKER, even, odd);
+}
+
+// a noise texture: the two colours in the texture record, the parameters beside the table
+int rt_scene_add_noise_texture(rt_scene *s, const float c0[3], const float c1[3], const rt_noise *noise) {
+    if (bad_scene(s, "rt_scene_add_noise_texture")) return -RT_ERR_ARG;
+    if (!noise) {
+        set_error("rt_scene_add_noise_texture: null parameters");
+        return -RT_ERR_ARG;
+    }
+    return add_noise_texture(s->s, c0, c1, *noise, "rt_scene_add_noise_texture");
+}
+
+int rt_scene_get_noise(const rt_scene *s, int texture, rt_noise *out) {
+    if (bad_scene(s, "rt_scene_get_noise")) return RT_ERR_ARG;
+    if (!out) {
+        set_error("rt_scene_get_noise: null output");
+        return RT_ERR_ARG;
+    }
+    if (texture < 0 || texture >= (int)s->s.texs.size() || s->s.texs[texture].type != RT_TEX_NOISE || (size_t)texture >= s->s.noise.size()) {
+        set_error("texture %d is not a noise texture", texture);
+        return RT_ERR_ARG;
+    }
+    *out = s->s.noise[texture];
+    return RT_OK;
 }
 
 static int add_material(rt_scene *s, int type, int tex, const float *albedo, float fuzz, float ir) {
@@ -518,7 +543,7 @@ rt_scene *rt_scene_dna(const rt_scene *base, double angle) {
     if (base) {
         sc = base->s;
         sc.dev.reset();
-        sc.prims.clear(), sc.xforms.clear(), sc.mats.clear(), sc.texs.clear();
+        sc.prims.clear(), sc.xforms.clear(), sc.mats.clear(), sc.texs.clear(), sc.noise.clear();
     } else {  // gpu-version/basic_scene.json
         sc.width = 1600, sc.height = 900, sc.spp = 100, sc.max_depth = 50;
         sc.background[0] = 0.0005f, sc.background[1] = 0.0007f, sc.background[2] = 0.00099f;

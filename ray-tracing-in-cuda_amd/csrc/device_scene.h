@@ -17,6 +17,10 @@
 //     tri     [nt]  2 x float4   {material(bits), list index(bits), u1.x, u1.y} {u2.x, u2.y, u3.x, u3.y}
 //     mat     [nm]  3 x float4   {kind(bits), p0, p1, p2} {c0.xyz, p3} {c1.xyz, 0}
 //     image   texels of the image textures, one 32-bit word each (r | g << 8 | b << 16), row-major
+//     noise   [nn]  1 x float4   (only with noise textures; behind the texels) per noise texture, in texture order:
+//                                {scale, distortion, seed(bits), style | axis << 2 | octaves << 4 (bits)}.  A material with such a
+//                                texture keeps the two colours in c0.xyz / c1.xyz and the record's offset (in float4 records
+//                                from the image's start, bits) in c0.w -- the one word plastic's p0..p2 leave free
 //   LIGHT part (only with light sampling on and at least one sampled emitter; global memory, read by the light-sampling kernels)
 //     light   [nl]  7 x float4   {shape(bits): 0 sphere, 1 rect, 2 cylinder, 4 triangle, grouped id(bits), selection probability, 1/area}
 //                                {emission even.rgb, checker(bits)} {emission odd.rgb, 0}, then the geometry:
@@ -91,7 +95,13 @@ enum MatKind : int32_t {
     MK_ROUGH_METAL = 9,      // c0 = F0
     MK_PLASTIC_SOLID = 10,   // p1 = r0 of the coat, c0 = body colour
     MK_PLASTIC_CHECKER = 11, // p1 = r0, c0 = even, c1 = odd
-    MK_PLASTIC_IMAGE = 12    // p1 = r0, c0 as MK_LAMBERT_IMAGE
+    MK_PLASTIC_IMAGE = 12,   // p1 = r0, c0 as MK_LAMBERT_IMAGE
+    // noise textures (rt_noise.h), in the general (EXT) builds alone: c0 = colour at s = 0, c1 = colour at s = 1,
+    // p3 (c0.w) = the offset of the texture's noise record (bits).  The winner section evaluates the texture and hands the
+    // vertex on as the matching *_IMAGE kind, except plastic (whose light sample needs the colour again at full precision)
+    MK_LAMBERT_NOISE = 13,
+    MK_LIGHT_NOISE = 14,
+    MK_PLASTIC_NOISE = 15    // p1 = r0 (the kind rides in 6 bits of a glossy vertex's packed word: kinds stay below 64)
 };
 
 // Per-launch values the kernel needs only when a wave fetches or flushes a work item.  They live in global

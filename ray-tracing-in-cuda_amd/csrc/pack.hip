@@ -14,6 +14,7 @@
 #include "pack.h"
 #include "rt_motion.h"  // (before rt_media.h: philox.h defines RTMI_HD, rt_trig.h takes it as it finds it)
 #include "rt_media.h"
+#include "rt_noise.h"
 
 namespace rtmi {
 namespace {
@@ -667,8 +668,9 @@ int lay_out_hot(RenderParams &L, const Grid &g) {
 // image_word[k]: the first 32-bit word of image texture k's texels.
 // off_media: the first record of the MEDIA part (rt_media.h; 0: the scene has no media); off_motion: of the MOTION part
 // (rt_motion.h; 0: no moving spheres); off_normals: of the NORMALS part (device_scene.h; 0: no triangle has vertex normals).  -1: the environment's words would not fit an int32 offset; -2: 2^28 sphere slots or more.
+// off_noise: the first record of the noise textures' parameters (device_scene.h; 0: the scene has no noise texture).
 int lay_out_image(RenderParams &L, const Grid &g, const Scene &s, std::vector<int> &image_word, int &off_media, int &off_motion,
-                  int &off_normals) {
+                  int &off_normals, int &off_noise) {
     // The kernels read the winner's cold record at a 32-bit BYTE offset from the cold table, 16 x its slot (rec_at,
     // render_device.h): the slots end below 2^28.  This is the check that bound rests on; pack_scene refuses with RT_ERR_LIMIT.
     if ((long long)L.ns >= RT_MAX_SPHERE_SLOTS) return -2;
@@ -704,6 +706,13 @@ int lay_out_image(RenderParams &L, const Grid &g, const Scene &s, std::vector<in
         image_word[k] = off * 4;
         off += (int)(((size_t)s.images[k].rows * s.images[k].cols + 3) / 4);
     }
+    // the noise textures' parameters: one record each, in texture order; none: not a byte
+    off_noise = 0;
+    for (const rt_texture &t : s.texs)
+        if (t.type == RT_TEX_NOISE) {
+            if (!off_noise) off_noise = off;
+            ++off;
+        }
     // the LIGHT part (device_scene.h): light records, alias table, light slot of every grouped primitive id
     if (L.nl > 0) {
         L.off_light = off;
@@ -966,8 +975,27 @@ void write_texels(float *I, const Scene &s, const std::vector<int> &image_word) 
     }
 }
 
+// the noise textures' records {scale, distortion, seed, style | axis << 2 | octaves << 4}; noise_rec[i]: texture i's record
+void write_noise(float *I, const Scene &s, int off_noise, std::vector<int> &noise_rec) {
+    noise_rec.assign(s.texs.size(), 0);
+    int at = off_noise;
+    for (size_t i = 0; i < s.texs.size(); ++i) {
+        if (s.texs[i].type != RT_TEX_NOISE) continue;
+        const rt_noise &n = s.noise[i];
+        float *q = rec4(I, at);
+        q[0] = n.scale, q[1] = n.distortion, q[3] = bits((int32_t)noise_pack(n.style, n.axis, n.octaves));
+        memcpy(q + 2, &n.seed, 4);  // (any 32 bits: never through a float register)
+        noise_rec[i] = at++;
+    }
+}
+
 void write_materials(float *I, const RenderParams &L, const Scene &s, const SphereSlots &S, const OtherPrims &O,
-                     const std::vector<int> &image_word) {
+                     const std::vector<int> &image_word, const std::vector<int> &noise_rec) {
+    // a noise texture under a material: the two colours where a checker keeps them, the record's offset in c0.w
+    auto noise_words = [&](float *q, const rt_material &m, const rt_texture &t) {
+        q[4] = t.c0[0], q[5] = t.c0[1], q[6] = t.c0[2], q[7] = bits(noise_rec[(size_t)m.texture]);
+        q[8] = t.c1[0], q[9] = t.c1[1], q[10] = t.c1[2];
+    };
     for (int k = 0; k < L.nm; ++k) {
         const rt_material &m = s.mats[k];
         float *q = rec4(I, L.off_mat + 3 * k);
@@ -983,6 +1011,9 @@ void write_materials(float *I, const RenderParams &L, const Scene &s, const Sphe
                 kind = light ? MK_LIGHT_IMAGE : MK_LAMBERT_IMAGE;
                 const size_t im = (size_t)t->c0[0];
                 q[4] = bits(image_word[im]), q[5] = bits(s.images[im].rows), q[6] = bits(s.images[im].cols);
+            } else if (t && t->type == RT_TEX_NOISE) {
+                kind = light ? MK_LIGHT_NOISE : MK_LAMBERT_NOISE;
+                noise_words(q, m, *t);
             } else if (t) {
                 q[4] = t->c0[0], q[5] = t->c0[1], q[6] = t->c0[2];
                 q[8] = t->c1[0], q[9] = t->c1[1], q[10] = t->c1[2];
@@ -1019,6 +1050,9 @@ void write_materials(float *I, const RenderParams &L, const Scene &s, const Sphe
                 kind = MK_PLASTIC_IMAGE;
                 const size_t im = (size_t)t->c0[0];
                 q[4] = bits(image_word[im]), q[5] = bits(s.images[im].rows), q[6] = bits(s.images[im].cols);
+            } else if (t && t->type == RT_TEX_NOISE) {
+                kind = MK_PLASTIC_NOISE;
+                noise_words(q, m, *t);
             } else if (t) {
                 q[4] = t->c0[0], q[5] = t->c0[1], q[6] = t->c0[2];
                 q[8] = t->c1[0], q[9] = t->c1[1], q[10] = t->c1[2];
@@ -1185,8 +1219,8 @@ bool pack_round(const Scene &s, std::vector<char> &forced, std::vector<float> &i
         default: rec.push_back((int)i); break;
         }
     }
-    // (a glossy material, DESIGN 7m, runs in the general kernels alone, as an image texture does)
-    const bool sphere_only = rec.empty() && cyl.empty() && tri.empty() && s.images.empty() && !scene_has_glossy(s);
+    // (a glossy material, DESIGN 7m, and a noise texture, 7o, run in the general kernels alone, as an image texture does)
+    const bool sphere_only = rec.empty() && cyl.empty() && tri.empty() && s.images.empty() && !scene_has_glossy(s) && !scene_has_noise(s);
     const SphereSlots S = sphere_slots(s, std::move(sph), forced);
     const OtherPrims O = other_prims(s, S, std::move(rec), std::move(cyl), std::move(tri), forced);
     // light sampling runs in the general kernels alone (render_nee_kernel: the linear scan and the wide-table walks), so a
@@ -1214,8 +1248,9 @@ bool pack_round(const Scene &s, std::vector<char> &forced, std::vector<float> &i
     L.grid_wide = g.wide ? (nested ? 2 : 1) : 0;
     L.grid_sheet = (!g.cells.empty() && g.n[1] == 1 && !g.wide) ? 1 : 0;
     std::vector<int> image_word;
-    int off_media = 0, off_motion = 0, off_normals = 0;
-    const int records = lay_out_image(L, g, s, image_word, off_media, off_motion, off_normals);
+    std::vector<int> noise_rec;
+    int off_media = 0, off_motion = 0, off_normals = 0, off_noise = 0;
+    const int records = lay_out_image(L, g, s, image_word, off_media, off_motion, off_normals, off_noise);
     if (records < 0) {
         (records == -2 ? note.too_many_slots : note.too_large) = true;
         return true;
@@ -1237,7 +1272,8 @@ bool pack_round(const Scene &s, std::vector<char> &forced, std::vector<float> &i
     write_grid(I, L, g);
     write_others(I, L, s, O, g, inflate);
     write_texels(I, s, image_word);
-    write_materials(I, L, s, S, O, image_word);
+    write_noise(I, s, off_noise, noise_rec);
+    write_materials(I, L, s, S, O, image_word, noise_rec);
     if (L.nl > 0) write_lights(I, L, s, S, O, lights);
     if (s.env) write_environment(I, L, s);
     if (!s.media.empty()) write_media(I, L, s, off_media);

@@ -1150,11 +1150,24 @@
                 }
                 // (the material kind rides in the primitive's cold record: one dependent load, not two)
                 const float4 *M = image + P.off_mat + 3 * mat;
+                // a noise texture (rt_noise.h): a solid texture, evaluated here at the hit point the checker reads and
+                // left where an image's texel is left.  From here on the vertex IS the image-textured one of its material --
+                // scatter, emitter, albedo feature, the counters and every ordered comparison of kinds see the kind they know --
+                // except plastic, whose light sample needs the colour again (step (7) evaluates it again from the same point).
+                bool noise_tex = false;
+                if constexpr (EXT && !QUERY) {
+                    if (kind >= MK_LAMBERT_NOISE) {
+                        const float4 c = noise_texel(image, M[1], M[2], px, py, pz);
+                        tex_r = c.x, tex_g = c.y, tex_b = c.z;
+                        noise_tex = true;
+                        if (kind != MK_PLASTIC_NOISE) kind = kind == MK_LAMBERT_NOISE ? MK_LAMBERT_IMAGE : MK_LIGHT_IMAGE;
+                    }
+                }
                 // the hit record's (u, v) -- only where the material's texture reads them (an image texture); every
                 // other texture of the reference ignores them, and acos / atan2 per candidate hit (object.cuh:87-93)
                 // would be the most expensive part of sphere::hit
                 // (QUERY: for every hit, they are part of the record)
-                const bool want_uv = EXT && (QUERY || kind == MK_LAMBERT_IMAGE || kind == MK_LIGHT_IMAGE || kind == MK_PLASTIC_IMAGE);
+                const bool want_uv = EXT && (QUERY || (!noise_tex && (kind == MK_LAMBERT_IMAGE || kind == MK_LIGHT_IMAGE || kind == MK_PLASTIC_IMAGE)));
                 // a triangle's area weights (hittable.py:54-58), stated once: of the plane point for (u, v), and -- smooth shading,
                 // DESIGN 7l -- of the vertex normals.  The NORMALS part (device_scene.h) is there only when the scene has a triangle
                 // with vertex normals: where it lies is a wave-uniform word of the camera block, as for the media and the movers.
@@ -1266,7 +1279,7 @@
                         // (rough metal: F0, where metal keeps its albedo; plastic: the body's texture)
                         const bool odd = (kind == MK_LAMBERT_CHECKER || kind == MK_LIGHT_CHECKER || kind == MK_PLASTIC_CHECKER) && checker_odd(px, py, pz);
                         L_r = odd ? q2.x : q1.x, L_g = odd ? q2.y : q1.y, L_b = odd ? q2.z : q1.z;
-                        if (kind == MK_LAMBERT_IMAGE || kind == MK_LIGHT_IMAGE || kind == MK_PLASTIC_IMAGE) L_r = tex_r, L_g = tex_g, L_b = tex_b;
+                        if (kind == MK_LAMBERT_IMAGE || kind == MK_LIGHT_IMAGE || kind == MK_PLASTIC_IMAGE || kind == MK_PLASTIC_NOISE) L_r = tex_r, L_g = tex_g, L_b = tex_b;
                         if (kind == MK_DIELECTRIC) L_r = L_g = L_b = 1.0f;
                     } else if (P.feature == RT_FEATURE_NORMAL) {
                         L_r = nx, L_g = ny, L_b = nz;
@@ -1630,7 +1643,7 @@
                         if (plastic) {
                             const bool odd = kind == MK_PLASTIC_CHECKER && checker_odd(px, py, pz);
                             rh_r = odd ? q2.x : q1.x, rh_g = odd ? q2.y : q1.y, rh_b = odd ? q2.z : q1.z;
-                            if (kind == MK_PLASTIC_IMAGE) rh_r = tex_r, rh_g = tex_g, rh_b = tex_b;
+                            if (kind == MK_PLASTIC_IMAGE || kind == MK_PLASTIC_NOISE) rh_r = tex_r, rh_g = tex_g, rh_b = tex_b;
                             f_r = f_g = f_b = q0.z;
                             ul = rng_next<COUNT>(rng);
                         }
@@ -1866,7 +1879,7 @@
                 // the material again, from its record and the hit (the frame is rebuilt from n: nothing of it is kept live
                 // across the roulette section); which record and which kind: the bits of mfz
                 const uint32_t gbits = __float_as_uint(mfz);
-                const int gkind = (int)((gbits >> 24) & 15u);
+                const int gkind = (int)((gbits >> 24) & 63u);
                 const float4 *M = rec_at(image + P.off_mat, __umul24(gbits & 0xffffffu, 48u));
                 const float4 q0 = M[0], q1 = M[1], q2 = M[2];
                 const bool plastic = gkind != MK_ROUGH_METAL;
@@ -1876,6 +1889,12 @@
                     rh_r = odd ? q2.x : q1.x, rh_g = odd ? q2.y : q1.y, rh_b = odd ? q2.z : q1.z;
                     if (gkind == MK_PLASTIC_IMAGE)  // (the texel as image_texel made it: the same byte over 255)
                         rh_r = (float)(gtex & 255u) / 255.0f, rh_g = (float)((gtex >> 8) & 255u) / 255.0f, rh_b = (float)((gtex >> 16) & 255u) / 255.0f;
+                    // (a noise texture: 8 bits a channel would lose it.  Evaluated again at the hit point, which is still in
+                    //  px, py, pz: the same operations on the same floats, so the rho the vertex scattered with, bit for bit)
+                    if (gkind == MK_PLASTIC_NOISE) {
+                        const float4 c = noise_texel(image, q1, q2, px, py, pz);
+                        rh_r = c.x, rh_g = c.y, rh_b = c.z;
+                    }
                     f_r = f_g = f_b = q0.z;
                 }
                 glossy_eval(plastic, nx, ny, nz, mrx, mry, mrz, q0.y, f_r, f_g, f_b, rh_r, rh_g, rh_b, wx, wy, wz, gf_r, gf_g, gf_b, pb);

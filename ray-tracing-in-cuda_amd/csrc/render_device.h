@@ -243,7 +243,27 @@ __device__ __forceinline__ unsigned long long radiance_to_fixed(float v) {
 // the glossy materials: behind rt_sqrtf, which they use
 }  // namespace rtmi
 #include "rt_glossy.h"
+#include "rt_noise.h"
 namespace rtmi {
+
+// a noise texture's colour at the point p: q1 = {c0, offset of the noise record (bits)}, q2 = {c1, _} of the
+// material, the record {scale, distortion, seed, style | axis << 2 | octaves << 4} behind the texels (device_scene.h).
+// Called from two places (the winner section; a plastic vertex's light sample) and inlined into both; RT_NOISE_INLINE=0 builds
+// it as one __noinline__ function returning by value instead.  DESIGN 7o has both forms' rows: the call form is the slower one.
+#ifndef RT_NOISE_INLINE
+#define RT_NOISE_INLINE 1
+#endif
+#if RT_NOISE_INLINE
+__device__ __forceinline__
+#else
+__device__ __noinline__
+#endif
+float4 noise_texel(const float4 *__restrict__ image, const float4 q1, const float4 q2, float px, float py, float pz) {
+    const float4 nr = image[__float_as_int(q1.w)];
+    float4 c = {0.0f, 0.0f, 0.0f, 0.0f};  // (by value: in registers, where three references would go through scratch)
+    noise_color(__float_as_uint(nr.w), nr.x, nr.y, __float_as_uint(nr.z), q1.x, q1.y, q1.z, q2.x, q2.y, q2.z, px, py, pz, c.x, c.y, c.z);
+    return c;
+}
 
 // ---------------------------------------------------------------- light sampling (render_nee_kernel)
 static constexpr float kPi = 3.14159265358979323846f, kInvPi = 0.318309886183790671538f;

@@ -167,6 +167,59 @@ bool glossy_material_ok(const rt_material &m, size_t textures, const char *where
     return true;
 }
 
+bool noise_texture_ok(const float c0[3], const float c1[3], const rt_noise &n, const char *where) {
+    for (int k = 0; k < 3; ++k)
+        if (!(c0[k] >= 0.0f && c0[k] < INFINITY && c1[k] >= 0.0f && c1[k] < INFINITY)) {  // (a NaN fails the comparison)
+            set_error("%s: noise texture colours must be finite and >= 0 (got %g, %g)", where, (double)c0[k], (double)c1[k]);
+            return false;
+        }
+    if (n.style < RT_NOISE_STYLE_FBM || n.style > RT_NOISE_STYLE_MARBLE) {
+        set_error("%s: noise style must be 0 (fbm), 1 (turbulence) or 2 (marble) (got %d)", where, n.style);
+        return false;
+    }
+    if (!(n.scale > 0.0f && n.scale < INFINITY)) {
+        set_error("%s: noise scale must be finite and > 0 (got %g)", where, (double)n.scale);
+        return false;
+    }
+    if (n.octaves < 1 || n.octaves > 8) {
+        set_error("%s: noise octaves must be in 1..8 (got %d)", where, n.octaves);
+        return false;
+    }
+    if (n.style == RT_NOISE_STYLE_MARBLE) {
+        if (n.axis < 0 || n.axis > 2) {
+            set_error("%s: marble axis must be 0 (x), 1 (y) or 2 (z) (got %d)", where, n.axis);
+            return false;
+        }
+        if (!(std::fabs(n.distortion) < INFINITY)) {
+            set_error("%s: marble distortion must be finite (got %g)", where, (double)n.distortion);
+            return false;
+        }
+    }
+    return true;
+}
+
+int add_noise_texture(Scene &s, const float c0[3], const float c1[3], const rt_noise &n, const char *where) {
+    if (!c0 || !c1) {
+        set_error("%s: noise texture colour is null", where);
+        return -RT_ERR_ARG;
+    }
+    if (!noise_texture_ok(c0, c1, n, where)) return -RT_ERR_ARG;
+    rt_texture t;
+    memset(&t, 0, sizeof t);
+    t.type = RT_TEX_NOISE;
+    memcpy(t.c0, c0, sizeof t.c0);
+    memcpy(t.c1, c1, sizeof t.c1);
+    rt_noise rec = n;
+    if (rec.style != RT_NOISE_STYLE_MARBLE) rec.axis = 0, rec.distortion = 0.0f;  // (fields of marble alone)
+    s.texs.push_back(t);
+    rt_noise none;
+    memset(&none, 0, sizeof none);
+    s.noise.resize(s.texs.size(), none);
+    s.noise.back() = rec;
+    s.touch();
+    return (int)s.texs.size() - 1;
+}
+
 int scene_validate(const Scene &s) {
     if (s.width < 2 || s.height < 2) {
         // u = (x + xi) / (W - 1), main.cu:97-98: W = 1 divides by zero
@@ -212,6 +265,14 @@ int scene_validate(const Scene &s) {
                 set_error("texture %zu references image %d, which is missing or has another size", i, im);
                 return RT_ERR_SCENE;
             }
+        } else if (t.type == RT_TEX_NOISE) {
+            char where[32];
+            snprintf(where, sizeof where, "texture %zu", i);
+            if (i >= s.noise.size()) {
+                set_error("texture %zu is a noise texture without parameters", i);
+                return RT_ERR_SCENE;
+            }
+            if (!noise_texture_ok(t.c0, t.c1, s.noise[i], where)) return RT_ERR_SCENE;
         } else if (t.type != RT_TEX_SOLID && t.type != RT_TEX_CHECKER) {
             set_error("texture %zu has unknown type %d", i, t.type);
             return RT_ERR_SCENE;
@@ -880,6 +941,41 @@ int scene_from_json(const char *text, size_t len, Scene &s, const char *base_dir
                 }
                 if (r.ok && id < 0) return -id;
                 continue;  // add_image_texture appended the texture record
+            } else if (ty->str == "noise") {  // DESIGN 7o; a field the style does not have is an error, as for the glossy materials
+                rt_noise n;
+                memset(&n, 0, sizeof n);
+                const JsonValue *st = t.find("style");
+                if (!st || !st->is_string()) r.fail("%s: missing string \"style\"", where);
+                else if (st->str == "fbm") n.style = RT_NOISE_STYLE_FBM;
+                else if (st->str == "turbulence") n.style = RT_NOISE_STYLE_TURBULENCE;
+                else if (st->str == "marble") n.style = RT_NOISE_STYLE_MARBLE;
+                else r.fail("%s: unknown style \"%s\" (fbm, turbulence, marble)", where, st->str.c_str());
+                const bool marble = n.style == RT_NOISE_STYLE_MARBLE;
+                for (const auto &kv : t.obj) {
+                    bool found = false;
+                    for (const char *k : {"type", "style", "color0", "color1", "scale", "octaves", "seed"}) found = found || kv.first == k;
+                    if (marble) found = found || kv.first == "axis" || kv.first == "distortion";
+                    if (!found) r.fail("%s: unknown field \"%s\"", where, kv.first.c_str());
+                }
+                double c1[3];
+                r.vec3(t, "color0", where, c);
+                r.vec3(t, "color1", where, c1);
+                n.scale = (float)r.num(t, "scale", where);
+                n.octaves = r.integer(t, "octaves", where);
+                const double seed = r.num(t, "seed", where);
+                if (!(seed >= 0 && seed <= 4294967295.0 && seed == std::floor(seed))) r.fail("%s: \"seed\" must be an integer in 0..2^32 - 1", where);
+                else n.seed = (uint32_t)seed;
+                if (marble) {
+                    const JsonValue *ax = t.find("axis");
+                    if (!ax || !ax->is_string() || ax->str.size() != 1 || ax->str[0] < 'x' || ax->str[0] > 'z')
+                        r.fail("%s: \"axis\" must be \"x\", \"y\" or \"z\"", where);
+                    else n.axis = ax->str[0] - 'x';
+                    n.distortion = (float)r.num(t, "distortion", where);
+                }
+                if (!r.ok) break;
+                const float f0[3] = {(float)c[0], (float)c[1], (float)c[2]}, f1[3] = {(float)c1[0], (float)c1[1], (float)c1[2]};
+                if (add_noise_texture(s, f0, f1, n, where) < 0) return RT_ERR_SCENE;
+                continue;  // add_noise_texture appended the texture record
             } else {
                 r.fail("%s: unknown type \"%s\"", where, ty->str.c_str());
             }
@@ -1287,6 +1383,17 @@ std::string scene_to_json(const Scene &s) {
                 for (size_t k = 0; k < im.rgb.size(); ++k) o += (k ? "," : "") + std::to_string((int)im.rgb[k]);
                 o += "]}";
             }
+        } else if (t.type == RT_TEX_NOISE) {
+            const rt_noise &n = s.noise[i];
+            static const char *const styles[3] = {"fbm", "turbulence", "marble"};
+            o += std::string("{\"type\": \"noise\", \"style\": \"") + styles[n.style] + "\", \"color0\": ";
+            put_vec3(o, t.c0);
+            o += ", \"color1\": ";
+            put_vec3(o, t.c1);
+            o += ", \"scale\": " + json_float(n.scale) + ", \"octaves\": " + std::to_string(n.octaves) + ", \"seed\": " + std::to_string(n.seed);
+            if (n.style == RT_NOISE_STYLE_MARBLE)
+                o += std::string(", \"axis\": \"") + (char)('x' + n.axis) + "\", \"distortion\": " + json_float(n.distortion);
+            o += "}";
         } else {
             o += "{\"type\": \"checker\", \"even\": ";
             put_vec3(o, t.c0);

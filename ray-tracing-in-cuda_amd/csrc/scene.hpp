@@ -63,6 +63,8 @@ struct Scene {
     std::vector<rt_material> mats;
     std::vector<rt_texture> texs;
     std::vector<SceneImage> images;  // referenced by RT_TEX_IMAGE textures (c0[0] = index)
+    std::vector<rt_noise> noise;     // noise[i]: the parameters of texture i where it is an RT_TEX_NOISE; beside the
+                                     // texture table as the images are, as long as the last noise texture's id + 1
     std::shared_ptr<const SceneEnvironment> env;  // null: no environment (a miss gives the background / the sky)
     float env_scale = 1.0f, env_rotate = 0.0f;    // radiance = scale x texel; degrees about +y
     std::vector<rt_medium> media;  // homogeneous participating media, a list of its own: at most RT_MAX_MEDIA
@@ -134,6 +136,18 @@ inline bool scene_has_glossy(const Scene &s) {
     return false;
 }
 bool glossy_material_ok(const rt_material &m, size_t textures, const char *where);
+
+// noise textures: does the texture table hold one (such a scene runs the general kernels over the wide tables, as
+// one with an image texture does); are two colours and a parameter record within the argument rules (false: the message is
+// set, prefixed with `where`); checks and appends -> texture id, or -RT_ERR_ARG.  A style other than marble has neither axis
+// nor distortion: the stored record keeps zeros there, whatever the caller's held.
+inline bool scene_has_noise(const Scene &s) {
+    for (const rt_texture &t : s.texs)
+        if (t.type == RT_TEX_NOISE) return true;
+    return false;
+}
+bool noise_texture_ok(const float c0[3], const float c1[3], const rt_noise &n, const char *where);
+int add_noise_texture(Scene &s, const float c0[3], const float c1[3], const rt_noise &n, const char *where);
 
 // a medium (scene.cpp): checks the record and appends it -> medium id, or -rt_status
 int add_medium(Scene &s, const rt_medium &m);
