@@ -397,6 +397,18 @@ int rt_scene_get_image(const rt_scene *s, int texture, int *rows, int *cols, uin
 int rt_scene_add_noise_texture(rt_scene *s, const float c0[3], const float c1[3], const rt_noise *noise);
 /* the parameters of noise texture `texture`; RT_ERR_ARG if it is none */
 int rt_scene_get_noise(const rt_scene *s, int texture, rt_noise *out);
+/* Bump mapping: the scalar s(p) of noise texture `texture` as a height field on material `material`.  At a
+ * surface vertex with face-turned shading normal n, face-turned geometric normal g, ray direction d and sigma = +1 on a front
+ * hit, -1 on a back hit (height is measured along the OUTWARD normal): G = grad s(p) (analytic), Gt = G - (G . n) n,
+ * b = n - sigma strength Gt, n' = b / |b|; n' replaces n where it is finite, n' . g > 0 and n' . d < 0.  Only the height is
+ * used, not the texture's colours.  The hit point, front, t, (u, v), emitter hits and the ray queries stay geometric.  On
+ * lambertian, metal, dielectric, rough_metal and plastic; RT_ERR_ARG for an unknown material, a diffuse_light, a texture that
+ * is not an RT_TEX_NOISE or a strength that is not finite.  texture = -1 or strength = 0 removes the bump.  A scene with one
+ * runs the general (triangle / texture) kernels; a moving sphere whose material carries one is refused when rendered.
+ * The bumps live beside the material table: rt_material is unchanged. */
+int rt_scene_set_bump(rt_scene *s, int material, int texture, float strength);
+/* the bump of `material` (either pointer may be NULL): texture -1 and strength 0 where it has none; RT_ERR_ARG: no such material */
+int rt_scene_get_bump(const rt_scene *s, int material, int *texture, float *strength);
 /* Triangle(v1, v2, v3, u1, u2, u3, material), taichi-version/hittable.py:95-110; uv pointers may be NULL (zeros) */
 int rt_scene_add_triangle(rt_scene *s, const float v1[3], const float v2[3], const float v3[3],
                           const float uv1[2], const float uv2[2], const float uv3[2], int material);
@@ -462,7 +474,9 @@ int rt_scene_get_textures(const rt_scene *s, rt_texture *out, int cap);   /* -> 
  * cold records, materials -- which one memcpy uploads (csrc/device_scene.h, csrc/pack.hip pack_scene).  (The parameters of
  * the noise textures, DESIGN 7o, are one record each behind the image textures' texels: {scale, distortion, seed, style |
  * axis << 2 | octaves << 4}; a material with such a texture holds the record's offset in the fourth word of its second
- * record.  No field here says where they begin: a scene without a noise texture has none and packs to the bytes it did.) */
+ * record.  No field here says where they begin: a scene without a noise texture has none and packs to the bytes it did.
+ * The bumps, DESIGN 7p, follow them the same way: one record per bumped material, {offset of the height texture's noise
+ * record, strength, 0, 0}, whose offset the material holds in the fourth word of its third record; none without a bump.) */
 typedef struct rt_table_info {
     int32_t image_floats;      /* size of the image (rt_scene_table_image) */
     int32_t grid_wide;         /* 1: wide tables (32-bit entries, two words per cell: every primitive type listed); 0: compact

@@ -84,6 +84,8 @@ struct material {
     std::shared_ptr<mytexture> tex;  // lambertian albedo / diffuse_light emit
     color albedo;
     float fuzz = 0, ir = 1;
+    std::shared_ptr<mytexture> bump;  // bump mapping: a noise texture as the height field, null: none
+    float bump_strength = 0;
 };
 using material_ptr = std::shared_ptr<material>;
 inline material_ptr lambertian(std::shared_ptr<mytexture> a) {  // material.cuh:34-35
@@ -120,6 +122,14 @@ inline material_ptr diffuse_light(std::shared_ptr<mytexture> a) {  // material.c
     return m;
 }
 inline material_ptr diffuse_light(color c) { return diffuse_light(solid_color(c)); }  // material.cuh:166-167
+
+// bump mapping: a copy of `m` whose shading normal is perturbed by the gradient of `height`'s scalar (a noise
+// texture; only its height is used, not its colours) x `strength`.  Any material but diffuse_light.
+inline material_ptr bumped(const material_ptr &m, std::shared_ptr<mytexture> height, float strength) {
+    auto b = std::make_shared<material>(*m);
+    b->bump = std::move(height), b->bump_strength = strength;
+    return b;
+}
 
 // ---- participating media (include/rtmi.h: homogeneous media, isotropic scattering) ------------
 // constant_medium(boundary, density, albedo): the boundary is a sphere (centre, radius) or an axis-aligned box (min, max)
@@ -475,6 +485,7 @@ private:
         default: id = rt_scene_add_diffuse_light(s_, texture_id(m->tex)); break;
         }
         if (id < 0) throw error(-id, "material");
+        if (m->bump) check(rt_scene_set_bump(s_, id, texture_id(m->bump), m->bump_strength), "bump");
         mats_.emplace_back(m, id);
         return id;
     }

@@ -253,6 +253,8 @@ NOISE_STYLES = {"fbm": 0, "turbulence": 1, "marble": 2}
 NOISE_AXES = {"x": 0, "y": 1, "z": 2}
 _sig("rt_scene_add_noise_texture", C.c_int, _p, _f3, _f3, C.POINTER(Noise))
 _sig("rt_scene_get_noise", C.c_int, _p, C.c_int, C.POINTER(Noise))
+_sig("rt_scene_set_bump", C.c_int, _p, C.c_int, C.c_int, C.c_float)
+_sig("rt_scene_get_bump", C.c_int, _p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float))
 assert _lib.rt_struct_size(24) == C.sizeof(Noise) == 24
 _sig("rt_scene_add_triangle", C.c_int, _p, _f3, _f3, _f3, _f3, _f3, _f3, C.c_int)
 _sig("rt_scene_add_obj", C.c_int, _p, C.c_char_p, C.c_int, C.c_float, _f3, _f3)
@@ -344,6 +346,7 @@ C_SYMBOLS = [
     "rt_scene_new", "rt_scene_set_background", "rt_scene_set_camera", "rt_scene_add_solid_color",
     "rt_scene_add_checker", "rt_scene_add_lambertian", "rt_scene_add_metal", "rt_scene_add_dielectric",
     "rt_scene_add_rough_metal", "rt_scene_add_plastic", "rt_scene_add_noise_texture", "rt_scene_get_noise",
+    "rt_scene_set_bump", "rt_scene_get_bump",
     "rt_scene_add_diffuse_light", "rt_scene_add_sphere", "rt_scene_add_rect", "rt_scene_add_cylinder",
     "rt_scene_add_image_texture", "rt_scene_add_image_texture_file", "rt_scene_get_image", "rt_scene_add_triangle",
     "rt_scene_add_obj", "rt_scene_add_triangle_normals", "rt_scene_add_obj_normals", "rt_set_mesh_normals_override",
@@ -571,6 +574,17 @@ class Scene:
         _check(_lib.rt_scene_get_noise(self._h, texture, C.byref(n)), "rt_scene_get_noise")
         return {"style": [k for k, v in NOISE_STYLES.items() if v == n.style][0], "scale": float(n.scale), "octaves": int(n.octaves),
                 "seed": int(n.seed), "axis": "xyz"[n.axis], "distortion": float(n.distortion)}
+
+    def set_bump(self, material: int, texture: int, strength: float) -> None:
+        """Bump mapping: the scalar of noise texture `texture` as a height field on `material`; the shading normal
+        tilts against its gradient x `strength`.  Any material but a diffuse_light; texture -1 or strength 0 removes it."""
+        _check(_lib.rt_scene_set_bump(self._h, int(material), int(texture), float(strength)), "rt_scene_set_bump")
+
+    def bump(self, material: int):
+        """(texture, strength) of the material's bump, or None."""
+        t, k = C.c_int(), C.c_float()
+        _check(_lib.rt_scene_get_bump(self._h, int(material), C.byref(t), C.byref(k)), "rt_scene_get_bump")
+        return None if t.value < 0 else (int(t.value), float(k.value))
 
     def get_image(self, texture: int) -> np.ndarray:
         rows, cols = C.c_int(), C.c_int()

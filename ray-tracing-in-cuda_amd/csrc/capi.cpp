@@ -348,6 +348,24 @@ int rt_scene_add_diffuse_light(rt_scene *s, int texture) {
     return add_material(s, RT_MAT_DIFFUSE_LIGHT, texture, nullptr, 0, 0);
 }
 
+// bump mapping: a side table beside the materials, as rt_noise is beside the textures
+int rt_scene_set_bump(rt_scene *s, int material, int texture, float strength) {
+    if (bad_scene(s, "rt_scene_set_bump")) return RT_ERR_ARG;
+    return set_bump(s->s, material, texture, strength, "rt_scene_set_bump") ? RT_OK : RT_ERR_ARG;
+}
+
+int rt_scene_get_bump(const rt_scene *s, int material, int *texture, float *strength) {
+    if (bad_scene(s, "rt_scene_get_bump")) return RT_ERR_ARG;
+    if (material < 0 || material >= (int)s->s.mats.size()) {
+        set_error("rt_scene_get_bump: unknown material %d (have %zu)", material, s->s.mats.size());
+        return RT_ERR_ARG;
+    }
+    const SceneBump *b = scene_bump(s->s, material);
+    if (texture) *texture = b ? b->texture : -1;
+    if (strength) *strength = b ? b->strength : 0.0f;
+    return RT_OK;
+}
+
 static bool bad_material(rt_scene *s, int material) {
     if (material < 0 || material >= (int)s->s.mats.size()) {
         set_error("object references material %d (have %zu)", material, s->s.mats.size());
@@ -543,7 +561,7 @@ rt_scene *rt_scene_dna(const rt_scene *base, double angle) {
     if (base) {
         sc = base->s;
         sc.dev.reset();
-        sc.prims.clear(), sc.xforms.clear(), sc.mats.clear(), sc.texs.clear(), sc.noise.clear();
+        sc.prims.clear(), sc.xforms.clear(), sc.mats.clear(), sc.texs.clear(), sc.noise.clear(), sc.bumps.clear();
     } else {  // gpu-version/basic_scene.json
         sc.width = 1600, sc.height = 900, sc.spp = 100, sc.max_depth = 50;
         sc.background[0] = 0.0005f, sc.background[1] = 0.0007f, sc.background[2] = 0.00099f;

@@ -21,6 +21,9 @@
 //                                {scale, distortion, seed(bits), style | axis << 2 | octaves << 4 (bits)}.  A material with such a
 //                                texture keeps the two colours in c0.xyz / c1.xyz and the record's offset (in float4 records
 //                                from the image's start, bits) in c0.w -- the one word plastic's p0..p2 leave free
+//     bump    [nb]  1 x float4   (only with bumped materials; behind the noise records) per bumped material, in
+//                                material order: {offset of the height texture's noise record (bits), strength, 0, 0}.  Such a
+//                                material holds its bump record's offset (bits) in c1.w, the word no kind uses; 0: no bump
 //   LIGHT part (only with light sampling on and at least one sampled emitter; global memory, read by the light-sampling kernels)
 //     light   [nl]  7 x float4   {shape(bits): 0 sphere, 1 rect, 2 cylinder, 4 triangle, grouped id(bits), selection probability, 1/area}
 //                                {emission even.rgb, checker(bits)} {emission odd.rgb, 0}, then the geometry:

@@ -669,8 +669,9 @@ int lay_out_hot(RenderParams &L, const Grid &g) {
 // off_media: the first record of the MEDIA part (rt_media.h; 0: the scene has no media); off_motion: of the MOTION part
 // (rt_motion.h; 0: no moving spheres); off_normals: of the NORMALS part (device_scene.h; 0: no triangle has vertex normals).  -1: the environment's words would not fit an int32 offset; -2: 2^28 sphere slots or more.
 // off_noise: the first record of the noise textures' parameters (device_scene.h; 0: the scene has no noise texture).
+// off_bump: the first bump record (device_scene.h; 0: no material carries a bump).
 int lay_out_image(RenderParams &L, const Grid &g, const Scene &s, std::vector<int> &image_word, int &off_media, int &off_motion,
-                  int &off_normals, int &off_noise) {
+                  int &off_normals, int &off_noise, int &off_bump) {
     // The kernels read the winner's cold record at a 32-bit BYTE offset from the cold table, 16 x its slot (rec_at,
     // render_device.h): the slots end below 2^28.  This is the check that bound rests on; pack_scene refuses with RT_ERR_LIMIT.
     if ((long long)L.ns >= RT_MAX_SPHERE_SLOTS) return -2;
@@ -711,6 +712,13 @@ int lay_out_image(RenderParams &L, const Grid &g, const Scene &s, std::vector<in
     for (const rt_texture &t : s.texs)
         if (t.type == RT_TEX_NOISE) {
             if (!off_noise) off_noise = off;
+            ++off;
+        }
+    // the bump records: one per bumped material, in material order, behind the noise records; none: not a byte
+    off_bump = 0;
+    for (const SceneBump &b : s.bumps)
+        if (b.texture >= 0) {
+            if (!off_bump) off_bump = off;
             ++off;
         }
     // the LIGHT part (device_scene.h): light records, alias table, light slot of every grouped primitive id
@@ -989,8 +997,20 @@ void write_noise(float *I, const Scene &s, int off_noise, std::vector<int> &nois
     }
 }
 
+// the bump records {offset of the texture's noise record (bits), strength, 0, 0}; bump_rec[m]: material m's record, 0: none
+void write_bumps(float *I, const Scene &s, int off_bump, const std::vector<int> &noise_rec, std::vector<int> &bump_rec) {
+    bump_rec.assign(s.mats.size(), 0);
+    int at = off_bump;
+    for (size_t m = 0; m < s.bumps.size() && m < s.mats.size(); ++m) {
+        if (s.bumps[m].texture < 0) continue;
+        float *q = rec4(I, at);
+        q[0] = bits(noise_rec[(size_t)s.bumps[m].texture]), q[1] = s.bumps[m].strength;
+        bump_rec[m] = at++;
+    }
+}
+
 void write_materials(float *I, const RenderParams &L, const Scene &s, const SphereSlots &S, const OtherPrims &O,
-                     const std::vector<int> &image_word, const std::vector<int> &noise_rec) {
+                     const std::vector<int> &image_word, const std::vector<int> &noise_rec, const std::vector<int> &bump_rec) {
     // a noise texture under a material: the two colours where a checker keeps them, the record's offset in c0.w
     auto noise_words = [&](float *q, const rt_material &m, const rt_texture &t) {
         q[4] = t.c0[0], q[5] = t.c0[1], q[6] = t.c0[2], q[7] = bits(noise_rec[(size_t)m.texture]);
@@ -1062,6 +1082,8 @@ void write_materials(float *I, const RenderParams &L, const Scene &s, const Sphe
         default: break;
         }
         q[0] = bits(kind);
+        // a bump: its record's offset in c1.w, the one word no kind above uses; 0: none
+        if (bump_rec[(size_t)k]) q[11] = bits(bump_rec[(size_t)k]);
     }
     // The material kind of every sphere, rect and cylinder sits in its cold record too: the shading then knows after ONE
     // dependent load (the primitive's cold record) whether the path ends, scatters or needs a rejection sample, instead
@@ -1219,8 +1241,8 @@ bool pack_round(const Scene &s, std::vector<char> &forced, std::vector<float> &i
         default: rec.push_back((int)i); break;
         }
     }
-    // (a glossy material, DESIGN 7m, and a noise texture, 7o, run in the general kernels alone, as an image texture does)
-    const bool sphere_only = rec.empty() && cyl.empty() && tri.empty() && s.images.empty() && !scene_has_glossy(s) && !scene_has_noise(s);
+    // (a glossy material, DESIGN 7m, a noise texture, 7o, and a bump, 7p, run in the general kernels alone, as an image texture does)
+    const bool sphere_only = rec.empty() && cyl.empty() && tri.empty() && s.images.empty() && !scene_has_glossy(s) && !scene_has_noise(s) && !scene_has_bump(s);
     const SphereSlots S = sphere_slots(s, std::move(sph), forced);
     const OtherPrims O = other_prims(s, S, std::move(rec), std::move(cyl), std::move(tri), forced);
     // light sampling runs in the general kernels alone (render_nee_kernel: the linear scan and the wide-table walks), so a
@@ -1248,9 +1270,9 @@ bool pack_round(const Scene &s, std::vector<char> &forced, std::vector<float> &i
     L.grid_wide = g.wide ? (nested ? 2 : 1) : 0;
     L.grid_sheet = (!g.cells.empty() && g.n[1] == 1 && !g.wide) ? 1 : 0;
     std::vector<int> image_word;
-    std::vector<int> noise_rec;
-    int off_media = 0, off_motion = 0, off_normals = 0, off_noise = 0;
-    const int records = lay_out_image(L, g, s, image_word, off_media, off_motion, off_normals, off_noise);
+    std::vector<int> noise_rec, bump_rec;
+    int off_media = 0, off_motion = 0, off_normals = 0, off_noise = 0, off_bump = 0;
+    const int records = lay_out_image(L, g, s, image_word, off_media, off_motion, off_normals, off_noise, off_bump);
     if (records < 0) {
         (records == -2 ? note.too_many_slots : note.too_large) = true;
         return true;
@@ -1273,7 +1295,8 @@ bool pack_round(const Scene &s, std::vector<char> &forced, std::vector<float> &i
     write_others(I, L, s, O, g, inflate);
     write_texels(I, s, image_word);
     write_noise(I, s, off_noise, noise_rec);
-    write_materials(I, L, s, S, O, image_word, noise_rec);
+    write_bumps(I, s, off_bump, noise_rec, bump_rec);
+    write_materials(I, L, s, S, O, image_word, noise_rec, bump_rec);
     if (L.nl > 0) write_lights(I, L, s, S, O, lights);
     if (s.env) write_environment(I, L, s);
     if (!s.media.empty()) write_media(I, L, s, off_media);

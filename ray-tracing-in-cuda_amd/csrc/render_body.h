@@ -1261,6 +1261,23 @@
                     } else
                     image_texel(image, M[1], tu, tv, tex_r, tex_g, tex_b);
                 }
+                // a bump: the material's noise height field tilts the shading normal, behind the smooth-shading normal
+                // and the (u, v) above (a sphere's read its normal) and before everything that shades: the feature pass, the
+                // scatter step, the light sample's cosine and frame.  The hit point, front, t and an emitter's normal (a
+                // diffuse_light takes no bump) stay geometric; a query never comes here.
+                if constexpr (EXT && !QUERY) {
+                    const int boff = __float_as_int(M[2].w);
+                    if (boff != 0 && !(MOTION && mot_i >= 0)) {
+                        float gnx = nx, gny = ny, gnz = nz;  // the face-turned geometric normal: a triangle's may have been replaced
+                        if (best_id >= ns + nr + nc) {
+                            const int k = best_id - ns - nr - nc;
+                            const float tnx = tri[RT_TRI_STRIDE * k].w, tny = tri[RT_TRI_STRIDE * k + 1].w, tnz = tri[RT_TRI_STRIDE * k + 2].w;
+                            gnx = front ? tnx : -tnx, gny = front ? tny : -tny, gnz = front ? tnz : -tnz;
+                        }
+                        const float4 nb = bump_normal(image, boff, front, nx, ny, nz, gnx, gny, gnz, dx, dy, dz, px, py, pz);
+                        nx = nb.x, ny = nb.y, nz = nb.z;
+                    }
+                }
                 if (COUNT) {
                     c_hits++;
                     // (the glossy materials, DESIGN 7m: plastic counts with the lambertians, rough metal with the metals)

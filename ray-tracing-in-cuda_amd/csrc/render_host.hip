@@ -616,6 +616,7 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     for (const rt_prim &p : s.prims) ext = ext || p.type == RT_PRIM_TRIANGLE;
     ext = ext || scene_has_glossy(s);  // (the glossy materials' code sits in those builds alone)
     ext = ext || scene_has_noise(s);   // (and the noise textures')
+    ext = ext || scene_has_bump(s);    // (and the bumps')
     const bool force_ext = knob_set("RTMI_FORCE_EXT");  // measurement: the EXT builds on scenes that do not need them
     const int device = o ? o->device : 0;
     DeviceScope scope;
@@ -726,6 +727,12 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
             set_error("this scene has moving spheres and the nested grid, which no kernel combines: switch the nested grid off");
             return RT_ERR_ARG;
         }
+        for (const rt_moving_sphere &m : s.movers)
+            if (scene_bump(s, m.material)) {
+                set_error("this scene has a moving sphere whose material carries a bump, which no kernel renders (the relief would swim "
+                          "through the ball): remove the bump or give the mover another material");
+                return RT_ERR_ARG;
+            }
         if (!find_kernel({K_MOTION, variant, true})) {
             set_error("kernel variant %u does not carry moving spheres (the motion kernels are variants 0, 16, 36 and 44)", variant);
             return RT_ERR_ARG;

@@ -134,4 +134,133 @@ RTMI_HD void noise_color(uint32_t packed, float scale, float distortion, uint32_
     r = fmaf(s, c1r - c0r, c0r), g = fmaf(s, c1g - c0g, c0g), b = fmaf(s, c1b - c0b, c0b);
 }
 
+// ---------------------------------------------------------------- the gradient, for bump mapping
+// The lattice noise is a quintic-faded trilinear interpolation of LINEAR corner functions g_abc(t) = G_abc . (t - (a, b, c)),
+// so its gradient is analytic and comes from the same eight hashes in the same pass:
+//   dn/dx = sum_abc Wa(tx) Wb(ty) Wc(tz) G_abc.x + w'(tx) sum_bc Wb(ty) Wc(tz) (g_1bc - g_0bc),  w'(t) = 30 t^2 (t - 1)^2
+// and likewise for y and z, with W0 = 1 - w, W1 = w.  A coordinate outside (-2^30, 2^30), or a NaN, has a zero component.
+//   grad S = f sum_o grad_q n(2^o f p, seed + o)  (the chain rule's 2^o cancels the amplitude 2^-o),
+//   grad A = f sum_o sgn(n_o) grad_q n_o, sgn(0) = 0
+//   fbm: grad s = 0.5 grad S where 0 < 0.5 + 0.5 S < 1, else 0;  turbulence: grad s = grad A where A < 1, else 0
+//   marble: grad s = 0.5 cos(f p[a] + D A) (f e_a + D grad A)
+
+// noise_grad's value and the constant corner gradient G it selects: (+-1, +-1, 0) and its kin, components in {-1, 0, 1}
+RTMI_HD float noise_grad_vec(uint32_t h, float x, float y, float z, float &Gx, float &Gy, float &Gz) {
+    const uint32_t g = h >> 28;
+    const bool vx = g == 12u || g == 14u;
+    const float su = (g & 1u) ? -1.0f : 1.0f, sv = (g & 2u) ? -1.0f : 1.0f;
+    Gx = g < 8u ? su : (vx ? sv : 0.0f);
+    Gy = g < 4u ? sv : (g < 8u ? 0.0f : su);
+    Gz = (g < 4u || vx) ? 0.0f : sv;
+    const float u = g < 8u ? x : y;
+    const float v = g < 4u ? y : (vx ? x : z);
+    return ((g & 1u) ? -u : u) + ((g & 2u) ? -v : v);
+}
+
+RTMI_HD float noise_fade_deriv(float t) {
+    const float a = t * (t - 1.0f);
+    return 30.0f * (a * a);
+}
+
+// is the coordinate one that noise_cell leaves alone (inside the clamp, not a NaN)?
+RTMI_HD bool noise_free(float q) { return q > -1073741824.0f && q < 1073741824.0f; }
+
+// one x edge of the cell: its two corners' values (d = g1 - g0) and the components of G, interpolated along x
+struct NoiseEdge {
+    float a, d, Gx, Gy, Gz;
+};
+RTMI_HD void noise_edge(uint32_t x0, uint32_t x1, uint32_t yz, float tx, float ux, float vy, float vz, float wx, NoiseEdge &e) {
+    float G0x, G0y, G0z, G1x, G1y, G1z;
+    const float g0 = noise_grad_vec(noise_mix(x0 ^ yz), tx, vy, vz, G0x, G0y, G0z);
+    const float g1 = noise_grad_vec(noise_mix(x1 ^ yz), ux, vy, vz, G1x, G1y, G1z);
+    e.d = g1 - g0;
+    e.a = fmaf(wx, e.d, g0);
+    e.Gx = fmaf(wx, G1x - G0x, G0x), e.Gy = fmaf(wx, G1y - G0y, G0y), e.Gz = fmaf(wx, G1z - G0z, G0z);
+}
+
+// n(q, s) as noise3 gives it, and its gradient with respect to q
+RTMI_HD float noise3_grad(float qx, float qy, float qz, uint32_t s, float &dnx, float &dny, float &dnz) {
+    int32_t ci, cj, ck;
+    const float tx = noise_cell(qx, ci), ty = noise_cell(qy, cj), tz = noise_cell(qz, ck);
+    const uint32_t x0 = s ^ ((uint32_t)ci * RT_NOISE_KX), x1 = s ^ ((uint32_t)ci * RT_NOISE_KX + RT_NOISE_KX);
+    const uint32_t y0 = (uint32_t)cj * RT_NOISE_KY, y1 = y0 + RT_NOISE_KY;
+    const uint32_t z0 = (uint32_t)ck * RT_NOISE_KZ, z1 = z0 + RT_NOISE_KZ;
+    const float ux = tx - 1.0f, uy = ty - 1.0f, uz = tz - 1.0f;
+    const float wx = noise_fade(tx), wy = noise_fade(ty), wz = noise_fade(tz);
+    // the four x edges (y0 z0, y1 z0, y0 z1, y1 z1), then along y, then z
+    NoiseEdge e0, e1, e2, e3;
+    noise_edge(x0, x1, y0 ^ z0, tx, ux, ty, tz, wx, e0);
+    noise_edge(x0, x1, y1 ^ z0, tx, ux, uy, tz, wx, e1);
+    noise_edge(x0, x1, y0 ^ z1, tx, ux, ty, uz, wx, e2);
+    noise_edge(x0, x1, y1 ^ z1, tx, ux, uy, uz, wx, e3);
+    const float dY0 = e1.a - e0.a, dY1 = e3.a - e2.a;
+    const float b0 = fmaf(wy, dY0, e0.a), b1 = fmaf(wy, dY1, e2.a);
+    const float dZ = b1 - b0;
+    const float n = fmaf(wz, dZ, b0);
+    const float bx0 = fmaf(wy, e1.Gx - e0.Gx, e0.Gx), bx1 = fmaf(wy, e3.Gx - e2.Gx, e2.Gx);
+    const float by0 = fmaf(wy, e1.Gy - e0.Gy, e0.Gy), by1 = fmaf(wy, e3.Gy - e2.Gy, e2.Gy);
+    const float bz0 = fmaf(wy, e1.Gz - e0.Gz, e0.Gz), bz1 = fmaf(wy, e3.Gz - e2.Gz, e2.Gz);
+    const float ex0 = fmaf(wy, e1.d - e0.d, e0.d), ex1 = fmaf(wy, e3.d - e2.d, e2.d);
+    dnx = fmaf(noise_fade_deriv(tx), fmaf(wz, ex1 - ex0, ex0), fmaf(wz, bx1 - bx0, bx0));
+    dny = fmaf(noise_fade_deriv(ty), fmaf(wz, dY1 - dY0, dY0), fmaf(wz, by1 - by0, by0));
+    dnz = fmaf(noise_fade_deriv(tz), dZ, fmaf(wz, bz1 - bz0, bz0));
+    if (!noise_free(qx)) dnx = 0.0f;
+    if (!noise_free(qy)) dny = 0.0f;
+    if (!noise_free(qz)) dnz = 0.0f;
+    return n;
+}
+
+RTMI_HD float noise_cosf(float x) { return cosf(x); }  // (as noise_sinf: the same cosine on host and device)
+
+// grad s of the texture's scalar with respect to the world point p
+RTMI_HD void noise_gradient(int style, float scale, int octaves, uint32_t seed, int axis, float distortion, float px, float py, float pz,
+                            float &gx, float &gy, float &gz) {
+    float qx = scale * px, qy = scale * py, qz = scale * pz;
+    float sum = 0.0f, amp = 1.0f, sx = 0.0f, sy = 0.0f, sz = 0.0f;
+    for (int o = 0; o < octaves; ++o) {
+        float dx, dy, dz;
+        const float n = noise3_grad(qx, qy, qz, seed + (uint32_t)o, dx, dy, dz);
+        sum = fmaf(amp, style == RT_NOISE_FBM ? n : fabsf(n), sum);
+        const float sg = style == RT_NOISE_FBM ? 1.0f : (n > 0.0f ? 1.0f : (n < 0.0f ? -1.0f : 0.0f));
+        sx = fmaf(sg, dx, sx), sy = fmaf(sg, dy, sy), sz = fmaf(sg, dz, sz);
+        amp *= 0.5f;
+        qx *= 2.0f, qy *= 2.0f, qz *= 2.0f;
+    }
+    sx *= scale, sy *= scale, sz *= scale;
+    if (style == RT_NOISE_FBM) {
+        const float v = fmaf(0.5f, sum, 0.5f);
+        const float m = (v > 0.0f && v < 1.0f) ? 0.5f : 0.0f;
+        gx = m * sx, gy = m * sy, gz = m * sz;
+    } else if (style == RT_NOISE_TURBULENCE) {
+        const float m = sum < 1.0f ? 1.0f : 0.0f;
+        gx = m * sx, gy = m * sy, gz = m * sz;
+    } else {
+        const float pa = axis == 0 ? px : (axis == 1 ? py : pz);
+        const float c = 0.5f * noise_cosf(fmaf(distortion, sum, scale * pa));
+        gx = c * fmaf(distortion, sx, axis == 0 ? scale : 0.0f);
+        gy = c * fmaf(distortion, sy, axis == 1 ? scale : 0.0f);
+        gz = c * fmaf(distortion, sz, axis == 2 ? scale : 0.0f);
+    }
+}
+
+// The bump.  n: the face-turned shading normal, g: the face-turned geometric one, d: the ray's direction (any
+// length), sk = sigma k (sigma = +1 on a front hit, -1 on a back hit: height is measured along the OUTWARD normal), G = grad s:
+//   Gt = G - (G . n) n,  b = n - sigma k Gt,  n' = b / |b|
+// n' replaces n iff it is finite, n' . g > 0 and n' . d < 0; else n stays.  root: the caller's square root (the kernels':
+// rt_sqrtf).  -> was n replaced
+template <class Root>
+RTMI_HD bool noise_bump(float &nx, float &ny, float &nz, float gnx, float gny, float gnz, float dx, float dy, float dz, float sk, float Gx,
+                        float Gy, float Gz, Root root) {
+    const float gn = fmaf(Gx, nx, fmaf(Gy, ny, Gz * nz));
+    const float tx = fmaf(-gn, nx, Gx), ty = fmaf(-gn, ny, Gy), tz = fmaf(-gn, nz, Gz);
+    const float bx = fmaf(-sk, tx, nx), by = fmaf(-sk, ty, ny), bz = fmaf(-sk, tz, nz);
+    const float l2 = fmaf(bx, bx, fmaf(by, by, bz * bz));
+    if (!(l2 > 0.0f && l2 < INFINITY)) return false;  // (a NaN fails the comparison)
+    const float inv = 1.0f / root(l2);
+    const float ux = inv * bx, uy = inv * by, uz = inv * bz;
+    if (!(fmaf(ux, gnx, fmaf(uy, gny, uz * gnz)) > 0.0f && fmaf(ux, dx, fmaf(uy, dy, uz * dz)) < 0.0f)) return false;
+    nx = ux, ny = uy, nz = uz;
+    return true;
+}
+
 }  // namespace rtmi

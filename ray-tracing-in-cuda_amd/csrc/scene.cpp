@@ -220,6 +220,42 @@ int add_noise_texture(Scene &s, const float c0[3], const float c1[3], const rt_n
     return (int)s.texs.size() - 1;
 }
 
+// bump mapping: the argument rules of a bump, shared by the C call, the JSON reader and scene_validate.
+// none_ok: texture -1 (no bump) passes
+static bool bump_ok(const Scene &s, int material, int texture, float strength, bool none_ok, const char *where) {
+    if (material < 0 || material >= (int)s.mats.size()) {
+        set_error("%s: unknown material %d (have %zu)", where, material, s.mats.size());
+        return false;
+    }
+    if (s.mats[(size_t)material].type == RT_MAT_DIFFUSE_LIGHT) {
+        set_error("%s: material %d is a diffuse_light, which takes no bump", where, material);
+        return false;
+    }
+    if (!(std::fabs(strength) < INFINITY)) {  // (a NaN fails the comparison)
+        set_error("%s: bump strength must be finite (got %g)", where, (double)strength);
+        return false;
+    }
+    if (none_ok && texture == -1) return true;
+    if (texture < 0 || texture >= (int)s.texs.size() || s.texs[(size_t)texture].type != RT_TEX_NOISE) {
+        set_error("%s: bump texture %d is not a noise texture", where, texture);
+        return false;
+    }
+    return true;
+}
+
+bool set_bump(Scene &s, int material, int texture, float strength, const char *where) {
+    if (!bump_ok(s, material, texture, strength, true, where)) return false;
+    if (texture == -1 || strength == 0.0f) {  // removes; the table ends at the last bumped material
+        if ((size_t)material < s.bumps.size()) s.bumps[(size_t)material] = SceneBump();
+        while (!s.bumps.empty() && s.bumps.back().texture < 0) s.bumps.pop_back();
+    } else {
+        if (s.bumps.size() <= (size_t)material) s.bumps.resize((size_t)material + 1);
+        s.bumps[(size_t)material].texture = texture, s.bumps[(size_t)material].strength = strength;
+    }
+    s.touch();
+    return true;
+}
+
 int scene_validate(const Scene &s) {
     if (s.width < 2 || s.height < 2) {
         // u = (x + xi) / (W - 1), main.cu:97-98: W = 1 divides by zero
@@ -255,6 +291,12 @@ int scene_validate(const Scene &s) {
             snprintf(where, sizeof where, "material %zu", i);
             if (!glossy_material_ok(m, s.texs.size(), where)) return RT_ERR_SCENE;
         }
+    }
+    for (size_t i = 0; i < s.bumps.size(); ++i) {
+        if (s.bumps[i].texture < 0) continue;
+        char where[32];
+        snprintf(where, sizeof where, "material %zu", i);
+        if (!bump_ok(s, (int)i, s.bumps[i].texture, s.bumps[i].strength, false, where)) return RT_ERR_SCENE;
     }
     for (size_t i = 0; i < s.texs.size(); ++i) {
         const rt_texture &t = s.texs[i];
@@ -1004,6 +1046,21 @@ int scene_from_json(const char *text, size_t len, Scene &s, const char *base_dir
                     if (!found) r.fail("%s: unknown field \"%s\"", where, kv.first.c_str());
                 }
             };
+            // a bump on any material but an emitter: {"texture": <noise texture>, "strength": <number>}
+            const JsonValue *bump = m.find("bump");
+            int bump_tex = -1;
+            float bump_k = 0.0f;
+            if (bump) {
+                if (!bump->is_object()) r.fail("%s: \"bump\" must be an object", where);
+                else {
+                    char bw[128];
+                    snprintf(bw, sizeof bw, "%s: bump", where);
+                    for (const auto &kv : bump->obj)
+                        if (kv.first != "texture" && kv.first != "strength") r.fail("%s: unknown field \"%s\"", bw, kv.first.c_str());
+                    bump_tex = r.integer(*bump, "texture", bw);
+                    bump_k = (float)r.num(*bump, "strength", bw);
+                }
+            }
             if (ty->str == "lambertian") {
                 rec.type = RT_MAT_LAMBERTIAN;
                 rec.texture = r.integer(m, "texture", where);
@@ -1016,7 +1073,7 @@ int scene_from_json(const char *text, size_t len, Scene &s, const char *base_dir
                 rec.fuzz = f < 1 ? f : 1;  // material.cuh:61
             } else if (ty->str == "rough_metal") {  // albedo is F0, fuzz holds the roughness
                 rec.type = RT_MAT_ROUGH_METAL;
-                only_keys(m, {"type", "albedo", "roughness"});
+                only_keys(m, {"type", "albedo", "roughness", "bump"});
                 double c[3];
                 r.vec3(m, "albedo", where, c);
                 for (int k = 0; k < 3; ++k) rec.albedo[k] = (float)c[k];
@@ -1024,7 +1081,7 @@ int scene_from_json(const char *text, size_t len, Scene &s, const char *base_dir
                 if (r.ok && !glossy_material_ok(rec, s.texs.size(), where)) r.ok = false;
             } else if (ty->str == "plastic") {  // texture is the body colour, fuzz the roughness, ir the coat's index
                 rec.type = RT_MAT_PLASTIC;
-                only_keys(m, {"type", "texture", "ior", "roughness"});
+                only_keys(m, {"type", "texture", "ior", "roughness", "bump"});
                 rec.texture = r.integer(m, "texture", where);
                 rec.ir = (float)r.num(m, "ior", where);
                 rec.fuzz = (float)r.num(m, "roughness", where);
@@ -1039,6 +1096,7 @@ int scene_from_json(const char *text, size_t len, Scene &s, const char *base_dir
                 r.fail("%s: unknown type \"%s\"", where, ty->str.c_str());
             }
             s.mats.push_back(rec);
+            if (r.ok && bump && !set_bump(s, (int)s.mats.size() - 1, bump_tex, bump_k, where)) r.ok = false;
         }
     }
     if (!r.ok) return RT_ERR_SCENE;
@@ -1361,6 +1419,10 @@ std::string scene_to_json(const Scene &s) {
                  ", \"roughness\": " + json_float(m.fuzz) + "}";
             break;
         default: break;
+        }
+        if (const SceneBump *b = scene_bump(s, (int)i)) {  // (inside the material's object: before its closing brace)
+            o.pop_back();
+            o += ", \"bump\": {\"texture\": " + std::to_string(b->texture) + ", \"strength\": " + json_float(b->strength) + "}}";
         }
     }
     o += "\n  ]},\n";

@@ -48,6 +48,12 @@ struct SceneEnvironment {
 
 struct DeviceSceneCache;  // owned by the render module
 
+// a material's bump: the height field is the scalar s of noise texture `texture`, scaled by `strength`
+struct SceneBump {
+    int texture = -1;
+    float strength = 0.0f;
+};
+
 struct Scene {
     int width = 400, height = 225, spp = 100, max_depth = 50;
     float background[3] = {0, 0, 0};
@@ -65,6 +71,8 @@ struct Scene {
     std::vector<SceneImage> images;  // referenced by RT_TEX_IMAGE textures (c0[0] = index)
     std::vector<rt_noise> noise;     // noise[i]: the parameters of texture i where it is an RT_TEX_NOISE; beside the
                                      // texture table as the images are, as long as the last noise texture's id + 1
+    std::vector<SceneBump> bumps;    // bumps[m]: the bump of material m, texture < 0: none; beside the material table
+                                     // as `noise` is beside the textures, at most as long as the last bumped material's id + 1
     std::shared_ptr<const SceneEnvironment> env;  // null: no environment (a miss gives the background / the sky)
     float env_scale = 1.0f, env_rotate = 0.0f;    // radiance = scale x texel; degrees about +y
     std::vector<rt_medium> media;  // homogeneous participating media, a list of its own: at most RT_MAX_MEDIA
@@ -148,6 +156,19 @@ inline bool scene_has_noise(const Scene &s) {
 }
 bool noise_texture_ok(const float c0[3], const float c1[3], const rt_noise &n, const char *where);
 int add_noise_texture(Scene &s, const float c0[3], const float c1[3], const rt_noise &n, const char *where);
+
+// bump mapping: the bump of material m, or null; does any material carry one (such a scene runs the general
+// kernels over the wide tables); set_bump checks (false: the message is set, prefixed with `where`) and stores -- texture -1
+// or strength 0 removes
+inline const SceneBump *scene_bump(const Scene &s, int m) {
+    return (m >= 0 && (size_t)m < s.bumps.size() && s.bumps[(size_t)m].texture >= 0) ? &s.bumps[(size_t)m] : nullptr;
+}
+inline bool scene_has_bump(const Scene &s) {
+    for (const SceneBump &b : s.bumps)
+        if (b.texture >= 0) return true;
+    return false;
+}
+bool set_bump(Scene &s, int material, int texture, float strength, const char *where);
 
 // a medium (scene.cpp): checks the record and appends it -> medium id, or -rt_status
 int add_medium(Scene &s, const rt_medium &m);
