@@ -53,10 +53,16 @@ typedef enum rt_prim_type {
     RT_PRIM_XZ_RECT = 2,  /* object.cuh:134-164 f = {x0,x1,z0,z1,k}          */
     RT_PRIM_YZ_RECT = 3,  /* object.cuh:166-197 f = {y0,y1,z0,z1,k}          */
     RT_PRIM_CYLINDER = 4, /* object.cuh:216-297 f = {radius,zmin,zmax}, m/m_inv */
-    RT_PRIM_TRIANGLE = 5  /* taichi-version/hittable.py:38-71, 95-110: m[0..8] = v1, v2, v3; m[9..11] = the unit
+    RT_PRIM_TRIANGLE = 5, /* taichi-version/hittable.py:38-71, 95-110: m[0..8] = v1, v2, v3; m[9..11] = the unit
                              normal (v2-v1)x(v3-v1) / |..|; m_inv[0..5] = texture coordinates u1, u2, u3 (2 each);
                              the unit vertex normals of smooth shading: f[0..2] = n1, f[3..5] = n2,
                              m_inv[6..8] = n3 -- all nine words zero: a flat triangle; m_inv[9..11] = 0 */
+    RT_PRIM_QUAD = 6      /* a parallelogram (the model: csrc/rt_quad.h) with corner Q and edges u, v -- the corners
+                             Q, Q + u, Q + u + v, Q + v: m[0..8] = Q, u, v; and, derived in fp64 from those fp32 values and
+                             rounded once, with c = u x v and w = c / (c.c): m[9..11] = the outward unit normal n = c / |c|,
+                             m_inv[0..2] = A = v x w, m_inv[3..5] = B = w x u; f and m_inv[6..11] = 0.  The hit: den = n.d
+                             (zero or not finite: a miss), t = n.(Q - o) / den, p = o + t d, a = A.(p - Q), b = B.(p - Q),
+                             a hit iff both lie in [0, 1]; the hit record's (u, v) = (a, b), front = den < 0 */
 } rt_prim_type;
 
 typedef enum rt_mat_type {
@@ -158,7 +164,9 @@ typedef struct rt_scene rt_scene; /* opaque; gpu-version/parser.hpp:16-32 `struc
  * texture.data[] [output_file].  Extensions: texture type "checker"
  * {even[3], odd[3]} (texture.cuh:33-57 has the class, the parser lacks it), texture type "image" {"file": ppm} or
  * {"rows", "cols", "data": [r, g, b, ...]}, object types "triangle" {v1, v2, v3, [u1, u2, u3]} and "mesh" {"file":
- * obj, ["scale", "matrix"[9], "translate"]} (expanded into triangles when parsed),
+ * obj, ["scale", "matrix"[9], "translate"]} (expanded into triangles when parsed), "quad" {q, u, v, ["rotate": {axis,
+ * angle}], ["translate"]} and "box" {min, max, ["rotate"], ["translate"]} (expanded into six quads; both written back as the
+ * quads they became, and a field neither has is an error: rt_scene_add_quad),
  * optional top-level "sky_gradient": bool, "defocus_blur": bool (both default false: gpu-version renders a
  * constant background, main.cu:63, and has the lens sample disabled, camera.cuh:33-34) and
  * "russian_roulette": number in [0, 1].
@@ -226,9 +234,9 @@ int rt_scene_set_nested_grid(rt_scene *s, int on);
 int rt_scene_get_nested_grid(const rt_scene *s); /* 1, 0, or -rt_status */
 typedef struct rt_light {
     int32_t prim;        /* index into the primitive list                      */
-    int32_t shape;       /* rt_prim_type: sphere, xy / xz / yz rect, cylinder or -- with mesh lights on -- triangle */
+    int32_t shape;       /* rt_prim_type: sphere, xy / xz / yz rect, cylinder, quad or -- with mesh lights on -- triangle */
     float probability;   /* selection probability (the list sums to 1)         */
-    float area;          /* surface area (the cylinder's tube; a triangle's |e1 x e2| / 2) */
+    float area;          /* surface area (the cylinder's tube; a triangle's |e1 x e2| / 2; a quad's |u x v|) */
     float emission[3];   /* emission (a checker texture: its even colour)      */
     float emission_odd[3]; /* a checker texture's odd colour (else = emission) */
 } rt_light;
@@ -409,6 +417,19 @@ int rt_scene_get_noise(const rt_scene *s, int texture, rt_noise *out);
 int rt_scene_set_bump(rt_scene *s, int material, int texture, float strength);
 /* the bump of `material` (either pointer may be NULL): texture -1 and strength 0 where it has none; RT_ERR_ARG: no such material */
 int rt_scene_get_bump(const rt_scene *s, int material, int *texture, float *strength);
+/* Quads and boxes.  quad(Q, u, v, material): the parallelogram Q, Q + u, Q + u + v, Q + v, whose normal is along
+ * u x v; then rotate(axis, degrees) then translate(offset), the cylinder's pair and order (pass NULL to skip either).  The
+ * transform is applied to Q, u, v here, in fp64, and rounded once: what is stored, rendered and written to JSON is the quad it
+ * became.  A quad whose material is a diffuse_light with a solid or checker texture is one of the sampled emitters
+ * (rt_scene_get_lights), uniform by area.  RT_ERR_SCENE: |u x v|^2 not positive or not finite, a value not finite, a rotation
+ * axis of zero length.  A scene with a quad runs the general (triangle / texture) kernels.  -> prim id or -rt_status */
+int rt_scene_add_quad(rt_scene *s, const float q[3], const float u[3], const float v[3], int material,
+                      const float rot_axis[3], float rot_degrees, const float translate[3]);
+/* box(min, max, material): six quads over [min, max] (min < max on every axis) in the order +z, -z, +x, -x, +y, -y, every
+ * u x v pointing outward -- so `front` is the outside and a dielectric box is a solid block of glass -- with the same optional
+ * transform about the origin.  All six are added or none.  -> the prim id of the first of the six, or -rt_status */
+int rt_scene_add_box(rt_scene *s, const float min[3], const float max[3], int material, const float rot_axis[3],
+                     float rot_degrees, const float translate[3]);
 /* Triangle(v1, v2, v3, u1, u2, u3, material), taichi-version/hittable.py:95-110; uv pointers may be NULL (zeros) */
 int rt_scene_add_triangle(rt_scene *s, const float v1[3], const float v2[3], const float v3[3],
                           const float uv1[2], const float uv2[2], const float uv3[2], int material);
@@ -487,7 +508,9 @@ typedef struct rt_table_info {
     float grid_min[3], grid_size[3];
     float ob_near2, ob_far2;   /* squared reach of the lists' near / far tier (|ray origin|^2) */
     int32_t ns, np, ncl;       /* sphere slots, leading always-tested slots, clusters of 8 (+ 1 never-hit slot each) behind them */
-    int32_t nr, nc, nt;        /* rectangles, cylinders, triangles ... */
+    int32_t nr, nc, nt;        /* rectangles, cylinders, triangles ... (quads, DESIGN 7q, are not counted here: their hot and
+                                  cold records follow the triangles' with the triangles' strides, grouped ids from
+                                  ns + nr + nc + nt on, in list order behind the always-tested ones) */
     int32_t nr_a, nc_a, nt_a;  /* ... of which the leading ones are tested for every query instead of being listed */
     int32_t off_grid_cells, off_grid_items;                         /* record (float4) offsets into the image */
     int32_t off_sph_cold, off_rect_cold, off_cyl_cold, off_tri_cold; /* cold records: {.., material, list index, kind} */

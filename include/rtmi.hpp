@@ -174,13 +174,16 @@ struct hittable {
     bool has_rotate = false, has_translate = false;
     vec3 axis{0, 0, 1}, offset;
     float radians = 0;
+    // (quad, box: is_box, and the same pair)
+    bool is_box = false;
     void rotate(vec3 a, float rad) {  // object.cuh:225-227
-        if (type != RT_PRIM_CYLINDER || has_rotate || has_translate)
-            throw std::logic_error("rotate: only once, on a cylinder, before translate");
+        if ((type != RT_PRIM_CYLINDER && type != RT_PRIM_QUAD) || has_rotate || has_translate)
+            throw std::logic_error("rotate: only once, on a cylinder, quad or box, before translate");
         has_rotate = true, axis = a, radians = rad;
     }
     void translate(vec3 o) {  // object.cuh:229-231
-        if (type != RT_PRIM_CYLINDER || has_translate) throw std::logic_error("translate: only once, on a cylinder");
+        if ((type != RT_PRIM_CYLINDER && type != RT_PRIM_QUAD) || has_translate)
+            throw std::logic_error("translate: only once, on a cylinder, quad or box");
         has_translate = true, offset = o;
     }
 };
@@ -223,6 +226,20 @@ inline hittable smooth_triangle(point3 v1, point3 v2, point3 v3, vec3 n1, vec3 n
     const vec3 *n[3] = {&n1, &n2, &n3};
     h.has_normals = true;
     for (int k = 0; k < 3; ++k) h.n[3 * k] = n[k]->x(), h.n[3 * k + 1] = n[k]->y(), h.n[3 * k + 2] = n[k]->z();
+    return h;
+}
+// quad(Q, u, v, material): the parallelogram Q, Q + u, Q + u + v, Q + v; rotate() / translate() as a cylinder's
+inline hittable quad(point3 Q, vec3 u, vec3 v, material_ptr m) {
+    hittable h;
+    h.type = RT_PRIM_QUAD, h.mat = std::move(m);
+    const vec3 *c[3] = {&Q, &u, &v};
+    for (int k = 0; k < 3; ++k) h.v[3 * k] = c[k]->x(), h.v[3 * k + 1] = c[k]->y(), h.v[3 * k + 2] = c[k]->z();
+    return h;
+}
+// box(min, max, material): six quads, normals outward; scene::add returns the id of the first
+inline hittable box(point3 mn, point3 mx, material_ptr m) {
+    hittable h = quad(mn, mx, vec3(), std::move(m));
+    h.is_box = true;
     return h;
 }
 inline hittable cylinder(float radius, float zmin, float zmax, material_ptr m) {  // object.cuh:220-223
@@ -305,6 +322,12 @@ public:
             id = h.has_normals ? rt_scene_add_triangle_normals(s_, h.v, h.v + 3, h.v + 6, h.n, h.n + 3, h.n + 6, h.uv, h.uv + 2, h.uv + 4, m)
                                : rt_scene_add_triangle(s_, h.v, h.v + 3, h.v + 6, h.uv, h.uv + 2, h.uv + 4, m);
             break;
+        case RT_PRIM_QUAD: {
+            const float deg = h.radians * 180.0f / 3.14159265358979323846f;
+            const float *ax = h.has_rotate ? h.axis.e : nullptr, *off = h.has_translate ? h.offset.e : nullptr;
+            id = h.is_box ? rt_scene_add_box(s_, h.v, h.v + 3, m, ax, deg, off) : rt_scene_add_quad(s_, h.v, h.v + 3, h.v + 6, m, ax, deg, off);
+            break;
+        }
         case RT_PRIM_CYLINDER: {
             const float deg = h.radians * 180.0f / 3.14159265358979323846f;
             id = rt_scene_add_cylinder(s_, h.f[0], h.f[1], h.f[2], m, h.has_rotate ? h.axis.e : nullptr, deg,

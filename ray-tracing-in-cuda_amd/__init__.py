@@ -38,7 +38,7 @@ _lib = C.CDLL(_LIB_PATH)
 RT_OK = 0
 FLAG_SKY_GRADIENT = 1
 FLAG_DEFOCUS_BLUR = 2
-PRIM_SPHERE, PRIM_XY_RECT, PRIM_XZ_RECT, PRIM_YZ_RECT, PRIM_CYLINDER, PRIM_TRIANGLE = range(6)
+PRIM_SPHERE, PRIM_XY_RECT, PRIM_XZ_RECT, PRIM_YZ_RECT, PRIM_CYLINDER, PRIM_TRIANGLE, PRIM_QUAD = range(7)
 MAT_LAMBERTIAN, MAT_METAL, MAT_DIELECTRIC, MAT_DIFFUSE_LIGHT = range(4)
 TEX_SOLID, TEX_CHECKER, TEX_IMAGE = range(3)
 
@@ -257,6 +257,8 @@ _sig("rt_scene_set_bump", C.c_int, _p, C.c_int, C.c_int, C.c_float)
 _sig("rt_scene_get_bump", C.c_int, _p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float))
 assert _lib.rt_struct_size(24) == C.sizeof(Noise) == 24
 _sig("rt_scene_add_triangle", C.c_int, _p, _f3, _f3, _f3, _f3, _f3, _f3, C.c_int)
+_sig("rt_scene_add_quad", C.c_int, _p, _f3, _f3, _f3, C.c_int, _f3, C.c_float, _f3)
+_sig("rt_scene_add_box", C.c_int, _p, _f3, _f3, C.c_int, _f3, C.c_float, _f3)
 _sig("rt_scene_add_obj", C.c_int, _p, C.c_char_p, C.c_int, C.c_float, _f3, _f3)
 _sig("rt_scene_add_triangle_normals", C.c_int, _p, _f3, _f3, _f3, _f3, _f3, _f3, _f3, _f3, _f3, C.c_int)
 _sig("rt_scene_add_obj_normals", C.c_int, _p, C.c_char_p, C.c_int, C.c_float, _f3, _f3, C.c_int, C.c_float)
@@ -349,7 +351,7 @@ C_SYMBOLS = [
     "rt_scene_set_bump", "rt_scene_get_bump",
     "rt_scene_add_diffuse_light", "rt_scene_add_sphere", "rt_scene_add_rect", "rt_scene_add_cylinder",
     "rt_scene_add_image_texture", "rt_scene_add_image_texture_file", "rt_scene_get_image", "rt_scene_add_triangle",
-    "rt_scene_add_obj", "rt_scene_add_triangle_normals", "rt_scene_add_obj_normals", "rt_set_mesh_normals_override",
+    "rt_scene_add_quad", "rt_scene_add_box", "rt_scene_add_obj", "rt_scene_add_triangle_normals", "rt_scene_add_obj_normals", "rt_set_mesh_normals_override",
     "rt_scene_override", "rt_scene_get_info", "rt_scene_get_camera", "rt_scene_get_prims",
     "rt_scene_get_materials", "rt_scene_get_textures", "rt_shard_rows", "rt_shard_global_row", "rt_shard_deal",
     "rt_render_hip_device", "rt_render_hip", "rt_render_hip_tiles", "rt_tiles_shutdown", "rt_shard_place_rows_device", "rt_render_hip_count", "rt_render_hip_accumulate", "rt_scene_set_russian_roulette",
@@ -606,6 +608,20 @@ class Scene:
                                                                 uv[0], uv[1], uv[2], material), "triangle")
         return _check_id(_lib.rt_scene_add_triangle(self._h, _v3(v1), _v3(v2), _v3(v3), uv[0], uv[1], uv[2], material),
                          "triangle")
+
+    def quad(self, q, u, v, material, rotate=None, translate=None) -> int:
+        """The parallelogram q, q + u, q + u + v, q + v, its normal along u x v.  rotate: (axis, degrees), then
+        translate: an offset -- applied to q, u, v when it is added; prims() shows the quad it became."""
+        ax, deg = (_v3(rotate[0]), float(rotate[1])) if rotate is not None else (None, 0.0)
+        t = _v3(translate) if translate is not None else None
+        return _check_id(_lib.rt_scene_add_quad(self._h, _v3(q), _v3(u), _v3(v), material, ax, deg, t), "quad")
+
+    def box(self, min, max, material, rotate=None, translate=None) -> int:
+        """Six quads over [min, max], normals outward, with the same optional rotate (axis, degrees) then translate; returns
+        the index of the first of the six (+z, -z, +x, -x, +y, -y)."""
+        ax, deg = (_v3(rotate[0]), float(rotate[1])) if rotate is not None else (None, 0.0)
+        t = _v3(translate) if translate is not None else None
+        return _check_id(_lib.rt_scene_add_box(self._h, _v3(min), _v3(max), material, ax, deg, t), "box")
 
     def add_obj(self, path, material, scale=1.0, matrix=None, translate=None, normals="flat", crease_angle=180.0) -> int:
         """readobj + placement, taichi-version/main.py:23-41, 110-118; returns the number of triangles added.

@@ -509,6 +509,38 @@ int rt_scene_add_cylinder(rt_scene *s, float radius, float zmin, float zmax, int
                         translate ? off : nullptr);
 }
 
+int rt_scene_add_quad(rt_scene *s, const float q[3], const float u[3], const float v[3], int material, const float rot_axis[3],
+                      float rot_degrees, const float translate[3]) {
+    if (bad_scene(s, "rt_scene_add_quad")) return -RT_ERR_ARG;
+    if (!q || !u || !v) {
+        set_error("quad corner or edge is null");
+        return -RT_ERR_ARG;
+    }
+    if (bad_material(s, material)) return -RT_ERR_SCENE;
+    double ax[3], off[3];
+    if (rot_axis)
+        for (int i = 0; i < 3; ++i) ax[i] = rot_axis[i];
+    if (translate)
+        for (int i = 0; i < 3; ++i) off[i] = translate[i];
+    return add_quad(s->s, q, u, v, material, rot_axis ? ax : nullptr, rot_degrees, translate ? off : nullptr);
+}
+
+int rt_scene_add_box(rt_scene *s, const float min[3], const float max[3], int material, const float rot_axis[3], float rot_degrees,
+                     const float translate[3]) {
+    if (bad_scene(s, "rt_scene_add_box")) return -RT_ERR_ARG;
+    if (!min || !max) {
+        set_error("box min or max is null");
+        return -RT_ERR_ARG;
+    }
+    if (bad_material(s, material)) return -RT_ERR_SCENE;
+    double ax[3], off[3];
+    if (rot_axis)
+        for (int i = 0; i < 3; ++i) ax[i] = rot_axis[i];
+    if (translate)
+        for (int i = 0; i < 3; ++i) off[i] = translate[i];
+    return add_box(s->s, min, max, material, rot_axis ? ax : nullptr, rot_degrees, translate ? off : nullptr);
+}
+
 // ---- animation ---------------------------------------------------------------------------
 rt_scene *rt_scene_clone(const rt_scene *src) {
     if (bad_scene(src, "rt_scene_clone")) return nullptr;

@@ -10,11 +10,16 @@
 //                                {min.xyz, _} {max.xyz, _}: one run of records, so that a lane that finds the cylinder in a cell's
 //                                list has its box and its matrix in flight together
 //     tri     [nt]  5 x float4   {v1.xyz, n.x} {v2.xyz, n.y} {v3.xyz, n.z}   (n = unit normal, hittable.py:104), then its box
+//     quad    [nq]  5 x float4   {Q.xyz, n.x} {A.xyz, n.y} {B.xyz, n.z}   (rt_quad.h: the corner, the unit normal, and the
+//                                two vectors that turn p - Q into the parallelogram's coordinates), then its box.  Straight behind
+//                                the triangles, with their stride: a cell's entry finds its box at one address for both
 //   COLD part (stays in global memory / L2; read once per bounce by the winning lane)
 //     sphere  [ns]  1 x float4   {1/r, material(bits), list index(bits), material kind(bits)}
 //     rect    [nr]  1 x float4   {material(bits), list index(bits), material kind(bits), 0}
 //     cyl     [nc]  4 x float4   m rows 0..2, {material(bits), list index(bits), material kind(bits), 0}
 //     tri     [nt]  2 x float4   {material(bits), list index(bits), u1.x, u1.y} {u2.x, u2.y, u3.x, u3.y}
+//     quad    [nq]  2 x float4   {material(bits), list index(bits), 0, 0} {0, 0, 0, 0}: straight behind the triangles' and as wide
+//                                as theirs, so that the tie rule's list_index_of reads both through one address
 //     mat     [nm]  3 x float4   {kind(bits), p0, p1, p2} {c0.xyz, p3} {c1.xyz, 0}
 //     image   texels of the image textures, one 32-bit word each (r | g << 8 | b << 16), row-major
 //     noise   [nn]  1 x float4   (only with noise textures; behind the texels) per noise texture, in texture order:
@@ -25,13 +30,13 @@
 //                                material order: {offset of the height texture's noise record (bits), strength, 0, 0}.  Such a
 //                                material holds its bump record's offset (bits) in c1.w, the word no kind uses; 0: no bump
 //   LIGHT part (only with light sampling on and at least one sampled emitter; global memory, read by the light-sampling kernels)
-//     light   [nl]  7 x float4   {shape(bits): 0 sphere, 1 rect, 2 cylinder, 4 triangle, grouped id(bits), selection probability, 1/area}
+//     light   [nl]  7 x float4   {shape(bits): 0 sphere, 1 rect, 2 cylinder, 4 triangle, 5 quad, grouped id(bits), selection probability, 1/area}
 //                                {emission even.rgb, checker(bits)} {emission odd.rgb, 0}, then the geometry:
 //                                sphere {c.xyz, |r|}; rect {a0, a1, b0, b1} {k, axis(bits), 0, 0}; cylinder o2w rows 0..2,
 //                                {|radius|, zmin, zmax, 0}; triangle (mesh lights) {v1, 0} {e1 = v2 - v1, 0}
-//                                {e2 = v3 - v1, 0} {the geometric unit normal, 0}
+//                                {e2 = v3 - v1, 0} {the geometric unit normal, 0}; quad {Q, 0} {u, 0} {v, 0} {n, 0}
 //     alias   [nl]  1 x float4   {threshold, alias light(bits), 0, 0}: one draw u picks i = floor(u nl), then i or its alias
-//     slot    [ns + nr + nc + nt] one 32-bit word per grouped primitive id: its light, -1 = not a sampled light
+//     slot    [ns + nr + nc + nt + nq] one 32-bit word per grouped primitive id: its light, -1 = not a sampled light
 //     (an environment that is sampled is the last light: {3, -1, selection probability, 1 / 4 pi}, no geometry)
 //   ENVIRONMENT part (only with an environment map; global memory, read by the environment kernels): rt_env.h
 //   MEDIA part (only with at least one medium; global memory, read by the media kernels): rt_media.h.  Two words of the camera
@@ -65,6 +70,10 @@
 // records per cylinder / triangle of the hot tables: the primitive, then its bounding box (2 records)
 #define RT_CYL_STRIDE 6
 #define RT_TRI_STRIDE 5
+// ... and per quad.  The quads' hot records follow the triangles' as one table (the cells' lists and the box tests
+// address both by RT_TRI_STRIDE x (id - ns - nr - nc)), so the two strides are one number
+#define RT_QUAD_STRIDE 5
+static_assert(RT_QUAD_STRIDE == RT_TRI_STRIDE, "quads and triangles share one hot table");
 
 // consecutive clusters under one outer box
 #ifndef RT_GROUP
@@ -188,6 +197,10 @@ struct RenderParams {
     float env_scale, env_uoff;
     int32_t off_env_tex, off_env_marg, off_env_cond, off_env_band, off_env_ct;
     float env_sel;           // selection probability of the environment's entry in the light table (the last one); 0: not sampled
+    // quads (grouped ids ns + nr + nc + nt ...) and the leading ones that are tested for every query.  Their hot and
+    // cold records follow the triangles' (off_tri_hot + RT_TRI_STRIDE nt, off_tri_cold + 2 nt).  Last in the block: the
+    // sphere-only kernels never read them, and every word in front of them stays where it was
+    int32_t nq, nq_a;
 };
 
 struct DevCounters {

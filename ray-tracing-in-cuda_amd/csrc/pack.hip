@@ -166,34 +166,46 @@ OBox tri_box(const rt_prim &p) {
     return b;
 }
 
+// a quad's box: the bounds of its four corners Q, Q + u, Q + u + v, Q + v
+OBox quad_box(const rt_prim &p) {
+    OBox b;
+    for (int a = 0; a < 3; ++a) {
+        const double q = p.m[a], u = p.m[3 + a], v = p.m[6 + a];
+        b.lo[a] = q + std::min(0.0, u) + std::min(0.0, v);
+        b.hi[a] = q + std::max(0.0, u) + std::max(0.0, v);
+    }
+    return b;
+}
+
 struct OtherPrims {
-    std::vector<int> rec, cyl, tri;  // prim indices per table, the always-tested ones first
-    int nr_a = 0, nc_a = 0, nt_a = 0;
+    std::vector<int> rec, cyl, tri, quad;  // prim indices per table, the always-tested ones first
+    int nr_a = 0, nc_a = 0, nt_a = 0, nq_a = 0;
     std::vector<int> others;         // rects, cylinders, triangles in list order: the index k of the per-k vectors below
     std::vector<int> oidx;           // per prim: its k, -1 for spheres
     std::vector<OBox> obox;          // world box
     std::vector<char> listed;        // listed in the grid's cells (else tested for every query)
     std::vector<int> gid;            // per prim: grouped id (its position in the tables behind the sphere slots)
-    int prim_of_gid(int g, int ns) const {  // (a grouped id of a rect, cylinder or triangle)
-        const int k = g - ns, nr = (int)rec.size(), nc = (int)cyl.size();
-        return k < nr ? rec[k] : (k < nr + nc ? cyl[k - nr] : tri[k - nr - nc]);
+    int prim_of_gid(int g, int ns) const {  // (a grouped id of a rect, cylinder, triangle or quad)
+        const int k = g - ns, nr = (int)rec.size(), nc = (int)cyl.size(), nt = (int)tri.size();
+        return k < nr ? rec[k] : (k < nr + nc ? cyl[k - nr] : (k < nr + nc + nt ? tri[k - nr - nc] : quad[k - nr - nc - nt]));
     }
 };
 
 OtherPrims other_prims(const Scene &s, const SphereSlots &S, std::vector<int> rec, std::vector<int> cyl, std::vector<int> tri,
-                       const std::vector<char> &forced) {
+                       std::vector<int> quad, const std::vector<char> &forced) {
     OtherPrims O;
     std::vector<int> &others = O.others;
     others.insert(others.end(), rec.begin(), rec.end());
     others.insert(others.end(), cyl.begin(), cyl.end());
     others.insert(others.end(), tri.begin(), tri.end());
+    others.insert(others.end(), quad.begin(), quad.end());
     O.oidx.assign(s.prims.size(), -1);
     for (size_t k = 0; k < others.size(); ++k) O.oidx[others[k]] = (int)k;
     std::vector<OBox> &obox = O.obox;
     obox.resize(others.size());
     for (size_t k = 0; k < others.size(); ++k) {
         const rt_prim &p = s.prims[others[k]];
-        obox[k] = p.type == RT_PRIM_CYLINDER ? cyl_box(p, std::fabs((double)p.f[0]), 0.0) : (p.type == RT_PRIM_TRIANGLE ? tri_box(p) : rect_box(p));
+        obox[k] = p.type == RT_PRIM_CYLINDER ? cyl_box(p, std::fabs((double)p.f[0]), 0.0) : (p.type == RT_PRIM_TRIANGLE ? tri_box(p) : (p.type == RT_PRIM_QUAD ? quad_box(p) : rect_box(p)));
     }
     // Which of them go into the grid's cells?  Like the spheres: none while the scene is small (16 primitives outside the
     // sphere prefix or fewer: the per-query loops are the cheaper search), and not the oversized ones (largest box edge > 8 x
@@ -219,13 +231,14 @@ OtherPrims other_prims(const Scene &s, const SphereSlots &S, std::vector<int> re
         v = a;
         v.insert(v.end(), b.begin(), b.end());
     };
-    order_table(rec, O.nr_a), order_table(cyl, O.nc_a), order_table(tri, O.nt_a);
-    const int ns = S.ns(), nr = (int)rec.size(), nc = (int)cyl.size();
+    order_table(rec, O.nr_a), order_table(cyl, O.nc_a), order_table(tri, O.nt_a), order_table(quad, O.nq_a);
+    const int ns = S.ns(), nr = (int)rec.size(), nc = (int)cyl.size(), nt = (int)tri.size();
     O.gid.assign(s.prims.size(), -1);
     for (size_t k = 0; k < rec.size(); ++k) O.gid[rec[k]] = ns + (int)k;
     for (size_t k = 0; k < cyl.size(); ++k) O.gid[cyl[k]] = ns + nr + (int)k;
     for (size_t k = 0; k < tri.size(); ++k) O.gid[tri[k]] = ns + nr + nc + (int)k;
-    O.rec = std::move(rec), O.cyl = std::move(cyl), O.tri = std::move(tri);
+    for (size_t k = 0; k < quad.size(); ++k) O.gid[quad[k]] = ns + nr + nc + nt + (int)k;
+    O.rec = std::move(rec), O.cyl = std::move(cyl), O.tri = std::move(tri), O.quad = std::move(quad);
     return O;
 }
 
@@ -649,6 +662,7 @@ int lay_out_hot(RenderParams &L, const Grid &g) {
     off += RT_CYL_STRIDE * L.nc;  // (each followed by its box)
     L.off_tri_hot = off;
     off += RT_TRI_STRIDE * L.nt;
+    off += RT_QUAD_STRIDE * L.nq;  // (the quads' records, DESIGN 7q: one table with the triangles')
     L.off_cam = off;  // camera::camera's derived vectors (camera.h:9-31): read once per new sample
     off += 6;
     L.off_grid = off;  // 4 records {min.xyz, ob_near^2} {1/size.xyz, ob_far^2} {size.xyz, shrink} {nx, ny, nz, -}, then cells, then items
@@ -699,6 +713,7 @@ int lay_out_image(RenderParams &L, const Grid &g, const Scene &s, std::vector<in
     off += 4 * L.nc;
     L.off_tri_cold = off;
     off += 2 * L.nt;
+    off += 2 * L.nq;  // (the quads' cold records: behind the triangles', and as wide)
     L.off_mat = off;
     off += 3 * L.nm;
     // texels of the image textures: one 32-bit word each, every image starts on a float4 record
@@ -728,7 +743,7 @@ int lay_out_image(RenderParams &L, const Grid &g, const Scene &s, std::vector<in
         L.off_alias = off;
         off += L.nl;
         L.off_lslot = off;
-        off += (L.ns + L.nr + L.nc + L.nt + 3) / 4;
+        off += (L.ns + L.nr + L.nc + L.nt + L.nq + 3) / 4;
     }
     // the ENVIRONMENT part (rt_env.h): texels, then the sampler's tables -- fp32 WORD offsets; global memory only, read by the
     // environment kernels.  -1: the words would not fit an int32 offset
@@ -820,6 +835,10 @@ float box_extent(const Scene &s, const SphereSlots &S, const OtherPrims &O) {
     for (int prim : O.tri) {
         const rt_prim &p = s.prims[prim];
         for (int cc = 0; cc < 9; ++cc) extent = std::max(extent, std::fabs(p.m[cc]));
+    }
+    for (int prim : O.quad) {
+        const OBox &b = O.obox[(size_t)O.oidx[prim]];
+        for (int a = 0; a < 3; ++a) extent = std::max(extent, (float)std::max(std::fabs(b.lo[a]), std::fabs(b.hi[a])));
     }
     return extent;
 }
@@ -972,6 +991,18 @@ void write_others(float *I, const RenderParams &L, const Scene &s, const OtherPr
         cd[2] = p.m_inv[0], cd[3] = p.m_inv[1];
         cd[4] = p.m_inv[2], cd[5] = p.m_inv[3], cd[6] = p.m_inv[4], cd[7] = p.m_inv[5];
     }
+    // quads: {Q, n.x} {A, n.y} {B, n.z}, the box; cold {material, list index, 0, 0} {0, 0, 0, 0}
+    for (int k = 0; k < L.nq; ++k) {
+        const rt_prim &p = s.prims[O.quad[k]];
+        float *h = rec4(I, L.off_tri_hot + RT_TRI_STRIDE * L.nt + RT_QUAD_STRIDE * k);
+        for (int cc = 0; cc < 3; ++cc) {
+            h[cc] = p.m[cc], h[4 + cc] = p.m_inv[cc], h[8 + cc] = p.m_inv[3 + cc];
+            h[4 * cc + 3] = p.m[9 + cc];
+        }
+        store_box(h + 12, O.quad[k]);  // (records 3 and 4)
+        float *cd = rec4(I, L.off_tri_cold + 2 * (L.nt + k));
+        cd[0] = bits(p.material), cd[1] = bits(O.quad[k]);
+    }
 }
 
 void write_texels(float *I, const Scene &s, const std::vector<int> &image_word) {
@@ -1104,8 +1135,9 @@ void write_lights(float *I, const RenderParams &L, const Scene &s, const SphereS
     for (int k = 0; k < L.nr; ++k) group_id[(size_t)O.rec[k]] = L.ns + k;
     for (int k = 0; k < L.nc; ++k) group_id[(size_t)O.cyl[k]] = L.ns + L.nr + k;
     for (int k = 0; k < L.nt; ++k) group_id[(size_t)O.tri[k]] = L.ns + L.nr + L.nc + k;
+    for (int k = 0; k < L.nq; ++k) group_id[(size_t)O.quad[k]] = L.ns + L.nr + L.nc + L.nt + k;
     int32_t *slot = reinterpret_cast<int32_t *>(rec4(I, L.off_lslot));
-    for (int k = 0; k < L.ns + L.nr + L.nc + L.nt; ++k) slot[k] = -1;
+    for (int k = 0; k < L.ns + L.nr + L.nc + L.nt + L.nq; ++k) slot[k] = -1;
     for (int i = 0; i < L.nl; ++i) {
         const SceneLight &l = lights[(size_t)i];
         if (l.prim < 0) {  // the environment: shape 3, no primitive, no geometry (rt_env.h samples it)
@@ -1117,7 +1149,7 @@ void write_lights(float *I, const RenderParams &L, const Scene &s, const SphereS
         const int gid = group_id[(size_t)l.prim];
         slot[gid] = i;
         float *r = rec4(I, L.off_light + RT_LIGHT_STRIDE * i);
-        const int shape = p.type == RT_PRIM_SPHERE ? 0 : (p.type == RT_PRIM_CYLINDER ? 2 : (p.type == RT_PRIM_TRIANGLE ? 4 : 1));
+        const int shape = p.type == RT_PRIM_SPHERE ? 0 : (p.type == RT_PRIM_CYLINDER ? 2 : (p.type == RT_PRIM_TRIANGLE ? 4 : (p.type == RT_PRIM_QUAD ? 5 : 1)));
         r[0] = bits(shape), r[1] = bits(gid), r[2] = (float)l.prob, r[3] = (float)(1.0 / l.area);
         for (int c3 = 0; c3 < 3; ++c3) r[4 + c3] = l.even[c3], r[8 + c3] = l.odd[c3];
         r[7] = bits(l.checker ? 1 : 0);
@@ -1130,6 +1162,8 @@ void write_lights(float *I, const RenderParams &L, const Scene &s, const SphereS
         } else if (shape == 2) {
             memcpy(g, p.m, 12 * sizeof(float));
             g[12] = std::fabs(p.f[0]), g[13] = p.f[1], g[14] = p.f[2];
+        } else if (shape == 5) {  // quad: Q, u, v and the unit normal
+            for (int c3 = 0; c3 < 3; ++c3) g[c3] = p.m[c3], g[4 + c3] = p.m[3 + c3], g[8 + c3] = p.m[6 + c3], g[12 + c3] = p.m[9 + c3];
         } else {  // triangle (mesh lights): v1, the edges from it (fp32 differences) and the GEOMETRIC unit normal
             for (int c3 = 0; c3 < 3; ++c3) {
                 g[c3] = p.m[c3], g[4 + c3] = p.m[3 + c3] - p.m[c3], g[8 + c3] = p.m[6 + c3] - p.m[c3];
@@ -1232,19 +1266,20 @@ struct PackNote {
 // earlier round).  False, with more primitives added to `forced`, when the grid could not list them.
 bool pack_round(const Scene &s, std::vector<char> &forced, std::vector<float> &image, RenderParams &L, size_t nest_over, int nest_cap,
                 PackNote &note) {
-    std::vector<int> sph, rec, cyl, tri;
+    std::vector<int> sph, rec, cyl, tri, quad;
     for (size_t i = 0; i < s.prims.size(); ++i) {
         switch (s.prims[i].type) {
         case RT_PRIM_SPHERE: sph.push_back((int)i); break;
         case RT_PRIM_CYLINDER: cyl.push_back((int)i); break;
         case RT_PRIM_TRIANGLE: tri.push_back((int)i); break;
+        case RT_PRIM_QUAD: quad.push_back((int)i); break;
         default: rec.push_back((int)i); break;
         }
     }
     // (a glossy material, DESIGN 7m, a noise texture, 7o, and a bump, 7p, run in the general kernels alone, as an image texture does)
-    const bool sphere_only = rec.empty() && cyl.empty() && tri.empty() && s.images.empty() && !scene_has_glossy(s) && !scene_has_noise(s) && !scene_has_bump(s);
+    const bool sphere_only = rec.empty() && cyl.empty() && tri.empty() && quad.empty() && s.images.empty() && !scene_has_glossy(s) && !scene_has_noise(s) && !scene_has_bump(s);
     const SphereSlots S = sphere_slots(s, std::move(sph), forced);
-    const OtherPrims O = other_prims(s, S, std::move(rec), std::move(cyl), std::move(tri), forced);
+    const OtherPrims O = other_prims(s, S, std::move(rec), std::move(cyl), std::move(tri), std::move(quad), forced);
     // light sampling runs in the general kernels alone (render_nee_kernel: the linear scan and the wide-table walks), so a
     // sphere-only scene that has lights to sample gets the wide tables; with nothing to sample the image stays as it was
     const std::vector<SceneLight> lights = s.light_sampling ? scene_lights(s) : std::vector<SceneLight>();
@@ -1253,6 +1288,7 @@ bool pack_round(const Scene &s, std::vector<char> &forced, std::vector<float> &i
     L.ns = S.ns(), L.feature = 0, L.np = S.np, L.ncl = S.n_clusters, L.cluster = RT_CLUSTER;
     L.nr = (int)O.rec.size(), L.nc = (int)O.cyl.size(), L.nt = (int)O.tri.size(), L.nm = (int)s.mats.size();
     L.nr_a = O.nr_a, L.nc_a = O.nc_a, L.nt_a = O.nt_a;
+    L.nq = (int)O.quad.size(), L.nq_a = O.nq_a;
     L.ngr = (S.n_clusters + RT_GROUP - 1) / RT_GROUP;        // RT_GROUP consecutive clusters share an outer box
     L.nwin = (L.ngr + 64 / RT_GROUP - 1) / (64 / RT_GROUP);  // 64 clusters per window
     L.rt_axes = S.axes;

@@ -613,7 +613,7 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     }
     // triangles and image textures live in separate builds of the kernels (template argument EXT)
     bool ext = !s.images.empty();
-    for (const rt_prim &p : s.prims) ext = ext || p.type == RT_PRIM_TRIANGLE;
+    for (const rt_prim &p : s.prims) ext = ext || p.type == RT_PRIM_TRIANGLE || p.type == RT_PRIM_QUAD;  // (quads: DESIGN 7q)
     ext = ext || scene_has_glossy(s);  // (the glossy materials' code sits in those builds alone)
     ext = ext || scene_has_noise(s);   // (and the noise textures')
     ext = ext || scene_has_bump(s);    // (and the bumps')

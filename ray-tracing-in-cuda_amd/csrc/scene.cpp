@@ -142,6 +142,133 @@ int add_cylinder(Scene &s, float radius, float zmin, float zmax, int material, c
     return (int)s.prims.size() - 1;
 }
 
+// ---------------------------------------------------------------- quads and boxes
+// The cylinder's pair and order: rotate about `axis` by `degrees` (the Rodrigues form above), then translate by `offset`; either
+// may be null.  False: the axis has zero length or something is not finite.
+static bool rigid_transform(const double *axis, double degrees, const double *offset, double R[3][3], double t[3]) {
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) R[i][j] = i == j ? 1.0 : 0.0;
+    t[0] = t[1] = t[2] = 0.0;
+    if (axis) {
+        double a[3] = {axis[0], axis[1], axis[2]};
+        const double len = v3len(a);
+        if (!(len > 0) || !std::isfinite(len) || !std::isfinite(degrees)) return false;
+        v3unit(a);
+        const double pi = std::acos(-1.0);
+        const double th = degrees / 180.0 * pi;
+        const double sn = std::sin(th), cs = std::cos(th);
+        R[0][0] = a[0] * a[0] + (1 - a[0] * a[0]) * cs;
+        R[0][1] = a[0] * a[1] * (1 - cs) - a[2] * sn;
+        R[0][2] = a[0] * a[2] * (1 - cs) + a[1] * sn;
+        R[1][0] = a[0] * a[1] * (1 - cs) + a[2] * sn;
+        R[1][1] = a[1] * a[1] + (1 - a[1] * a[1]) * cs;
+        R[1][2] = a[1] * a[2] * (1 - cs) - a[0] * sn;
+        R[2][0] = a[0] * a[2] * (1 - cs) - a[1] * sn;
+        R[2][1] = a[1] * a[2] * (1 - cs) + a[0] * sn;
+        R[2][2] = a[2] * a[2] + (1 - a[2] * a[2]) * cs;
+    }
+    if (offset) {
+        for (int i = 0; i < 3; ++i) t[i] = offset[i];
+        if (!std::isfinite(t[0]) || !std::isfinite(t[1]) || !std::isfinite(t[2])) return false;
+    }
+    return true;
+}
+
+// The record of the quad with corner Q and edges u, v (fp64 in, rounded once to the fp32 the record holds), and what the hit
+// test reads, derived in fp64 from THOSE fp32 values and rounded once: c = u x v, n = c / |c|, w = c / (c.c), A = v x w,
+// B = w x u (include/rtmi.h, RT_PRIM_QUAD).  False: |c|^2 is not finite or not positive, or a word is not finite.
+static bool quad_record(const double Q[3], const double u[3], const double v[3], int material, rt_prim &p) {
+    memset(&p, 0, sizeof p);
+    p.type = RT_PRIM_QUAD;
+    p.material = material;
+    double q[3], a[3], b[3], c[3], w[3], A[3], B[3];
+    for (int k = 0; k < 3; ++k) {
+        p.m[k] = (float)Q[k], p.m[3 + k] = (float)u[k], p.m[6 + k] = (float)v[k];
+        q[k] = p.m[k], a[k] = p.m[3 + k], b[k] = p.m[6 + k];
+        if (!std::isfinite(p.m[k]) || !std::isfinite(p.m[3 + k]) || !std::isfinite(p.m[6 + k])) return false;
+    }
+    v3cross(a, b, c);
+    const double cc = c[0] * c[0] + c[1] * c[1] + c[2] * c[2];
+    if (!std::isfinite(cc) || !(cc > 0)) return false;
+    const double len = std::sqrt(cc);
+    for (int k = 0; k < 3; ++k) w[k] = c[k] / cc;
+    v3cross(b, w, A);
+    v3cross(w, a, B);
+    for (int k = 0; k < 3; ++k) {
+        p.m[9 + k] = (float)(c[k] / len);
+        p.m_inv[k] = (float)A[k], p.m_inv[3 + k] = (float)B[k];
+        if (!std::isfinite(p.m[9 + k]) || !std::isfinite(p.m_inv[k]) || !std::isfinite(p.m_inv[3 + k])) return false;
+    }
+    // (the fp32 record must still name a plane and an area: the light record holds 1 / |c| in fp32)
+    if (!((float)len > 0.0f) || !std::isfinite((float)(1.0 / len)) || !std::isfinite((float)len)) return false;
+    return true;
+}
+
+static void apply_rigid(const double R[3][3], const double *t, const double x[3], double out[3]) {
+    for (int i = 0; i < 3; ++i) out[i] = R[i][0] * x[0] + R[i][1] * x[1] + R[i][2] * x[2] + (t ? t[i] : 0.0);
+}
+
+int add_quad(Scene &s, const float q[3], const float u[3], const float v[3], int material, const double *axis, double degrees,
+             const double *offset) {
+    double R[3][3], t[3];
+    if (!rigid_transform(axis, degrees, offset, R, t)) {
+        set_error("quad: rotate.axis has zero length, or the transform is not finite");
+        return -RT_ERR_SCENE;
+    }
+    double Q[3] = {q[0], q[1], q[2]}, U[3] = {u[0], u[1], u[2]}, V[3] = {v[0], v[1], v[2]};
+    if (axis || offset) {  // (no transform: the values as given, not through a multiplication by one)
+        double Q2[3], U2[3], V2[3];
+        apply_rigid(R, t, Q, Q2), apply_rigid(R, nullptr, U, U2), apply_rigid(R, nullptr, V, V2);
+        for (int k = 0; k < 3; ++k) Q[k] = Q2[k], U[k] = U2[k], V[k] = V2[k];
+    }
+    rt_prim p;
+    if (!quad_record(Q, U, V, material, p)) {
+        set_error("quad with zero area (|u x v|^2 not positive or not finite), or non-finite corner or edges");
+        return -RT_ERR_SCENE;
+    }
+    s.prims.push_back(p);
+    s.xforms.emplace_back();
+    s.touch();
+    return (int)s.prims.size() - 1;
+}
+
+// box(min, max): six quads, every u x v pointing outward (so that `front` is the outside: a dielectric box refracts as a solid),
+// in the order +z, -z, +x, -x, +y, -y; all six or none
+int add_box(Scene &s, const float mn[3], const float mx[3], int material, const double *axis, double degrees, const double *offset) {
+    double R[3][3], t[3];
+    if (!rigid_transform(axis, degrees, offset, R, t)) {
+        set_error("box: rotate.axis has zero length, or the transform is not finite");
+        return -RT_ERR_SCENE;
+    }
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(mn[k]) || !std::isfinite(mx[k]) || !(mn[k] < mx[k])) {
+            set_error("box: min %g must be finite and below max %g on axis %d", (double)mn[k], (double)mx[k], k);
+            return -RT_ERR_SCENE;
+        }
+    const double x0 = mn[0], y0 = mn[1], z0 = mn[2], x1 = mx[0], y1 = mx[1], z1 = mx[2];
+    const double dx = x1 - x0, dy = y1 - y0, dz = z1 - z0;
+    const double face[6][9] = {{x0, y0, z1, dx, 0, 0, 0, dy, 0},   // +z
+                               {x0, y0, z0, 0, dy, 0, dx, 0, 0},   // -z
+                               {x1, y0, z0, 0, dy, 0, 0, 0, dz},   // +x
+                               {x0, y0, z0, 0, 0, dz, 0, dy, 0},   // -x
+                               {x0, y1, z0, 0, 0, dz, dx, 0, 0},   // +y
+                               {x0, y0, z0, dx, 0, 0, 0, 0, dz}};  // -y
+    rt_prim rec[6];
+    for (int f = 0; f < 6; ++f) {
+        double Q[3], U[3], V[3];
+        if (axis || offset) apply_rigid(R, t, face[f], Q), apply_rigid(R, nullptr, face[f] + 3, U), apply_rigid(R, nullptr, face[f] + 6, V);
+        else
+            for (int k = 0; k < 3; ++k) Q[k] = face[f][k], U[k] = face[f][3 + k], V[k] = face[f][6 + k];
+        if (!quad_record(Q, U, V, material, rec[f])) {
+            set_error("box: a face has no area in fp32, or is not finite");
+            return -RT_ERR_SCENE;
+        }
+    }
+    for (int f = 0; f < 6; ++f) s.prims.push_back(rec[f]), s.xforms.emplace_back();
+    s.touch();
+    return (int)s.prims.size() - 6;
+}
+
 // ---------------------------------------------------------------- validation
 bool glossy_material_ok(const rt_material &m, size_t textures, const char *where) {
     if (!(m.fuzz >= 0.0f && m.fuzz <= 1.0f)) {  // (a NaN fails the comparison)
@@ -322,7 +449,7 @@ int scene_validate(const Scene &s) {
     }
     for (size_t i = 0; i < s.prims.size(); ++i) {
         const rt_prim &p = s.prims[i];
-        if (p.type < RT_PRIM_SPHERE || p.type > RT_PRIM_TRIANGLE) {
+        if (p.type < RT_PRIM_SPHERE || p.type > RT_PRIM_QUAD) {
             set_error("object %zu has unknown type %d", i, p.type);
             return RT_ERR_SCENE;
         }
@@ -1203,6 +1330,45 @@ int scene_from_json(const char *text, size_t len, Scene &s, const char *base_dir
                                           : add_triangle(s, vf[0], vf[1], vf[2], uf[0], uf[1], uf[2], mat);
                     if (rc < 0) return RT_ERR_SCENE;
                 }
+            } else if (t == "quad" || t == "box") {  // a parallelogram; six of them over [min, max]
+                const bool is_box = t == "box";
+                for (const auto &kv : o.obj) {  // (a field the type does not have is an error, as for the glossy materials)
+                    const std::string &k = kv.first;
+                    const bool known = k == "type" || k == "material" || k == "rotate" || k == "translate" ||
+                                       (is_box ? (k == "min" || k == "max") : (k == "q" || k == "u" || k == "v"));
+                    if (!known) r.fail("%s: unknown field \"%s\"", where, k.c_str());
+                }
+                double a3[3][3];
+                if (is_box) r.vec3(o, "min", where, a3[0]), r.vec3(o, "max", where, a3[1]);
+                else r.vec3(o, "q", where, a3[0]), r.vec3(o, "u", where, a3[1]), r.vec3(o, "v", where, a3[2]);
+                const int mat = r.integer(o, "material", where);
+                double axis[3], off[3], deg = 0;
+                const double *pa = nullptr, *po = nullptr;
+                if (const JsonValue *rot = o.find("rotate")) {
+                    if (!rot->is_object()) r.fail("%s: \"rotate\" must be an object", where);
+                    else {
+                        for (const auto &kv : rot->obj)
+                            if (kv.first != "axis" && kv.first != "angle") r.fail("%s: rotate: unknown field \"%s\"", where, kv.first.c_str());
+                        r.vec3(*rot, "axis", where, axis);
+                        deg = r.num(*rot, "angle", where);
+                        pa = axis;
+                    }
+                }
+                if (o.find("translate")) {
+                    r.vec3(o, "translate", where, off);
+                    po = off;
+                }
+                if (r.ok) {
+                    float f3[3][3];
+                    for (int c = 0; c < 3; ++c)
+                        for (int k = 0; k < 3; ++k) f3[c][k] = (float)a3[c][k];
+                    const int rc = is_box ? add_box(s, f3[0], f3[1], mat, pa, deg, po) : add_quad(s, f3[0], f3[1], f3[2], mat, pa, deg, po);
+                    if (rc < 0) {
+                        const std::string why = get_error();
+                        set_error("%s: %s", where, why.c_str());
+                        return RT_ERR_SCENE;
+                    }
+                }
             } else if (t == "mesh") {  // readobj + placement, taichi-version/main.py:23-41, 110-118
                 const JsonValue *f = o.find("file");
                 if (!f || !f->is_string()) r.fail("%s: missing string \"file\"", where);
@@ -1374,6 +1540,15 @@ std::string scene_to_json(const Scene &s) {
                     o += std::string(", \"") + nk[c] + "\": ";
                     put_vec3(o, nv[c]);
                 }
+            }
+            break;
+        }
+        case RT_PRIM_QUAD: {  // (as stored: a rotated quad, or a box's face, comes out as the quad it became)
+            o += "{\"type\": \"quad\"";
+            const char *qk[3] = {"q", "u", "v"};
+            for (int c = 0; c < 3; ++c) {
+                o += std::string(", \"") + qk[c] + "\": ";
+                put_vec3(o, p.m + 3 * c);
             }
             break;
         }
@@ -1624,6 +1799,14 @@ std::vector<SceneLight> scene_lights(const Scene &s) {
             if (!((float)l.area > 0.0f) || !std::isfinite((float)(1.0 / l.area))) continue;
             break;
         }
+        case RT_PRIM_QUAD: {
+            // quads always join, as rects do: |u x v| in fp64 from the stored edges
+            double a[3] = {p.m[3], p.m[4], p.m[5]}, b[3] = {p.m[6], p.m[7], p.m[8]}, n[3];
+            v3cross(a, b, n);
+            l.area = v3len(n);
+            if (!((float)l.area > 0.0f) || !std::isfinite((float)(1.0 / l.area))) continue;
+            break;
+        }
         default: continue;
         }
         const double power = l.area * 0.5 * (luminance(l.even) + luminance(l.odd));
@@ -1843,6 +2026,12 @@ double scene_bound_radius(const Scene &s) {
         }
         case RT_PRIM_TRIANGLE:
             for (int k = 0; k < 3; ++k) add(p.m[3 * k], p.m[3 * k + 1], p.m[3 * k + 2]);
+            break;
+        case RT_PRIM_QUAD:
+            for (int k = 0; k < 4; ++k) {
+                const double fu = (k == 1 || k == 2) ? 1.0 : 0.0, fv = k >= 2 ? 1.0 : 0.0;
+                add(p.m[0] + fu * p.m[3] + fv * p.m[6], p.m[1] + fu * p.m[4] + fv * p.m[7], p.m[2] + fu * p.m[5] + fv * p.m[8]);
+            }
             break;
         default: break;
         }

@@ -119,6 +119,11 @@ int set_environment(Scene &s, int rows, int cols, const float *rgb, float scale,
 int set_environment_file(Scene &s, const char *path, float scale, float rotate_deg);
 float env_uoff(float rotate_deg);           // the rotation as the lookup's offset of u, in [0, 1)
 double scene_bound_radius(const Scene &s);  // radius of the bounding sphere of the primitives (of their boxes' union)
+// quads and boxes: rotate (axis, degrees) then translate, either may be null -- applied on the host, in fp64.
+// add_box -> the index of the first of its six quads
+int add_quad(Scene &s, const float q[3], const float u[3], const float v[3], int material, const double *axis, double degrees,
+             const double *offset);
+int add_box(Scene &s, const float mn[3], const float mx[3], int material, const double *axis, double degrees, const double *offset);
 int add_triangle(Scene &s, const float v1[3], const float v2[3], const float v3[3], const float uv1[2], const float uv2[2],
                  const float uv3[2], int material);
 int add_obj(Scene &s, const char *path, int material, float scale, const float matrix[9], const float translate[3]);
