@@ -72,7 +72,9 @@ typedef enum rt_mat_type {
     RT_MAT_DIFFUSE_LIGHT = 3, /* material.cuh:161-182 tex = emission texture */
     /* glossy materials: a GGX microfacet lobe.  They reuse the record's fields:                      */
     RT_MAT_ROUGH_METAL = 4,   /* albedo = F0, fuzz = roughness in [0, 1]                                       */
-    RT_MAT_PLASTIC = 5        /* texture = body colour, fuzz = roughness in [0, 1], ir = the coat's index (> 1) */
+    RT_MAT_PLASTIC = 5,       /* texture = body colour, fuzz = roughness in [0, 1], ir = the coat's index (> 1) */
+    RT_MAT_ROUGH_GLASS = 6    /*  ir = the index (> 1), fuzz = roughness in [0, 1], albedo = the absorption
+                                 coefficient sigma per unit world length (each >= 0), texture = -1              */
 } rt_mat_type;
 
 typedef enum rt_tex_type {
@@ -113,9 +115,9 @@ typedef struct rt_prim {
 typedef struct rt_material {
     int32_t type;     /* rt_mat_type                                         */
     int32_t texture;  /* lambertian / diffuse_light / plastic (body colour): texture index, else -1 */
-    float albedo[3];  /* metal; rough_metal: F0                              */
+    float albedo[3];  /* metal; rough_metal: F0; rough_glass: the absorption coefficient sigma */
     float fuzz;       /* metal, clamped to <= 1 (material.cuh:61); rough_metal / plastic: the roughness r in [0, 1] */
-    float ir;         /* dielectric; plastic: the coat's index of refraction */
+    float ir;         /* dielectric; plastic: the coat's index of refraction; rough_glass: the index */
 } rt_material;
 
 typedef struct rt_texture {
@@ -371,6 +373,26 @@ int rt_scene_add_dielectric(rt_scene *s, float ir);
  * Anything else is RT_ERR_ARG.  A scene with either runs the general (triangle / texture) kernels.  -> material id or -rt_status */
 int rt_scene_add_rough_metal(rt_scene *s, const float albedo[3], float roughness);
 int rt_scene_add_plastic(rt_scene *s, int texture, float ior, float roughness);
+/* Rough glass (the model: csrc/rt_glass.h): reflection or refraction about a microfacet normal of the same GGX
+ * lobe, tinted by the distance travelled inside the object.  ir finite and > 1, roughness finite and in [0, 1], absorption
+ * (NULL: clear) three finite coefficients >= 0 per unit world length; anything else is RT_ERR_ARG.
+ * At a vertex with face-turned shading normal n, in the frame of Duff et al. about n, wo = -unit(d), alpha =
+ * max(roughness^2, 1e-3), eta = front ? 1 / ir : ir:
+ *   wo.z <= 0: absorbed, no draws, no light sample.  Otherwise three draws uf, u1, u2; h = the visible normal of the lobe from
+ *   (u1, u2), c = wo.h; s2 = eta^2 (1 - c^2); F = 1 if s2 >= 1, else with ct = sqrt(1 - s2), rs = (eta c - ct) / (eta c + ct),
+ *   rp = (c - eta ct) / (c + eta ct): F = (rs^2 + rp^2) / 2 (the exact unpolarised Fresnel term).
+ *   uf < F: wi = 2 c h - wo, absorbed if wi.z <= 0, pdf_b = F G1(wo) D(h) / (4 wo.z).
+ *   else:   wi = (eta c - ct) h - eta wo, absorbed if wi.z >= 0; an emitter the continuation reaches counts at full weight.
+ *   Attenuation, both: Tr G2(wo, wi) / G1(wo), Lambda(wi) of wi as it stands.  No eta^2 radiance scaling (as dielectric).
+ *   Tr = 1 on a front hit, exp(-sigma t |d|) per channel on a back hit (t |d|: the length of the segment that arrived).
+ *   The rule is stateless: right for solid closed objects, for a camera inside one and for objects embedded in the glass seen
+ *   from the embedded object; a segment that ENDS on another material inside the glass is not tinted, and air bubbles are not
+ *   handled (both out of scope, with nested or overlapping glass).
+ * With light sampling on, a vertex takes a light sample iff roughness >= 0.05 and wo.z > 0; the light strategy covers the
+ * reflection hemisphere alone: for wl.z > 0, h_l = unit(wo + wl): f cos = Tr F(wo.h_l) D(h_l) G2 / (4 wo.z), pdf_b =
+ * F(wo.h_l) G1(wo) D(h_l) / (4 wo.z); zero for wl.z <= 0 (no light sample through the surface).  The feature passes report
+ * albedo 1 and the shading normal.  A scene with one runs the general (triangle / texture) kernels.  -> material id or -rt_status */
+int rt_scene_add_rough_glass(rt_scene *s, float ir, float roughness, const float absorption[3]);
 int rt_scene_add_diffuse_light(rt_scene *s, int texture);
 int rt_scene_add_sphere(rt_scene *s, const float center[3], float radius, int material); /* -> prim id */
 /* axis: 0 = xy_rect (a=x,b=y,k=z), 1 = xz_rect, 2 = yz_rect */
@@ -410,7 +432,7 @@ int rt_scene_get_noise(const rt_scene *s, int texture, rt_noise *out);
  * hit, -1 on a back hit (height is measured along the OUTWARD normal): G = grad s(p) (analytic), Gt = G - (G . n) n,
  * b = n - sigma strength Gt, n' = b / |b|; n' replaces n where it is finite, n' . g > 0 and n' . d < 0.  Only the height is
  * used, not the texture's colours.  The hit point, front, t, (u, v), emitter hits and the ray queries stay geometric.  On
- * lambertian, metal, dielectric, rough_metal and plastic; RT_ERR_ARG for an unknown material, a diffuse_light, a texture that
+ * lambertian, metal, dielectric, rough_metal, plastic and rough_glass; RT_ERR_ARG for an unknown material, a diffuse_light, a texture that
  * is not an RT_TEX_NOISE or a strength that is not finite.  texture = -1 or strength = 0 removes the bump.  A scene with one
  * runs the general (triangle / texture) kernels; a moving sphere whose material carries one is refused when rendered.
  * The bumps live beside the material table: rt_material is unchanged. */

@@ -111,6 +111,12 @@ inline material_ptr plastic(std::shared_ptr<mytexture> body, float ior = 1.5f, f
     return m;
 }
 inline material_ptr plastic(color body, float ior = 1.5f, float roughness = 0.3f) { return plastic(solid_color(body), ior, roughness); }
+// rough glass: ir the index, fuzz the roughness, albedo the absorption coefficient per unit length (0: clear)
+inline material_ptr rough_glass(float ir = 1.5f, float roughness = 0.3f, color absorption = color(0, 0, 0)) {
+    auto m = std::make_shared<material>();
+    m->type = RT_MAT_ROUGH_GLASS, m->ir = ir, m->fuzz = roughness, m->albedo = absorption;
+    return m;
+}
 inline material_ptr dielectric(float index_of_refraction) {  // material.cuh:91-92
     auto m = std::make_shared<material>();
     m->type = RT_MAT_DIELECTRIC, m->ir = index_of_refraction;
@@ -505,6 +511,7 @@ private:
         case RT_MAT_DIELECTRIC: id = rt_scene_add_dielectric(s_, m->ir); break;
         case RT_MAT_ROUGH_METAL: id = rt_scene_add_rough_metal(s_, m->albedo.e, m->fuzz); break;
         case RT_MAT_PLASTIC: id = rt_scene_add_plastic(s_, texture_id(m->tex), m->ir, m->fuzz); break;
+        case RT_MAT_ROUGH_GLASS: id = rt_scene_add_rough_glass(s_, m->ir, m->fuzz, m->albedo.e); break;
         default: id = rt_scene_add_diffuse_light(s_, texture_id(m->tex)); break;
         }
         if (id < 0) throw error(-id, "material");

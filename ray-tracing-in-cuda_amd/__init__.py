@@ -235,6 +235,7 @@ _sig("rt_scene_add_metal", C.c_int, _p, _f3, C.c_float)
 _sig("rt_scene_add_dielectric", C.c_int, _p, C.c_float)
 _sig("rt_scene_add_rough_metal", C.c_int, _p, _f3, C.c_float)
 _sig("rt_scene_add_plastic", C.c_int, _p, C.c_int, C.c_float, C.c_float)
+_sig("rt_scene_add_rough_glass", C.c_int, _p, C.c_float, C.c_float, _f3)
 _sig("rt_scene_add_diffuse_light", C.c_int, _p, C.c_int)
 _sig("rt_scene_add_sphere", C.c_int, _p, _f3, C.c_float, C.c_int)
 _sig("rt_scene_add_rect", C.c_int, _p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int)
@@ -347,7 +348,7 @@ C_SYMBOLS = [
     "rt_scene_load_json", "rt_scene_parse_json", "rt_scene_rtiow", "rt_scene_to_json", "rt_scene_free",
     "rt_scene_new", "rt_scene_set_background", "rt_scene_set_camera", "rt_scene_add_solid_color",
     "rt_scene_add_checker", "rt_scene_add_lambertian", "rt_scene_add_metal", "rt_scene_add_dielectric",
-    "rt_scene_add_rough_metal", "rt_scene_add_plastic", "rt_scene_add_noise_texture", "rt_scene_get_noise",
+    "rt_scene_add_rough_metal", "rt_scene_add_plastic", "rt_scene_add_rough_glass", "rt_scene_add_noise_texture", "rt_scene_get_noise",
     "rt_scene_set_bump", "rt_scene_get_bump",
     "rt_scene_add_diffuse_light", "rt_scene_add_sphere", "rt_scene_add_rect", "rt_scene_add_cylinder",
     "rt_scene_add_image_texture", "rt_scene_add_image_texture_file", "rt_scene_get_image", "rt_scene_add_triangle",
@@ -652,6 +653,13 @@ class Scene:
         materials() shows it as type 5 with fuzz = roughness and ir = ior."""
         tex = texture_or_color if isinstance(texture_or_color, int) else self.solid_color(texture_or_color)
         return _check_id(_lib.rt_scene_add_plastic(self._h, tex, ior, roughness), "plastic")
+
+    def rough_glass(self, ir=1.5, roughness=0.3, absorption=None) -> int:
+        """Rough glass (DESIGN 7r): GGX reflection or refraction about a microfacet normal, index ir > 1, roughness in [0, 1];
+        absorption: three coefficients >= 0 per unit world length (None: clear) that tint light by the distance travelled inside.
+        materials() shows it as type 6 with fuzz = roughness and albedo = absorption."""
+        sigma = None if absorption is None else _v3(absorption)
+        return _check_id(_lib.rt_scene_add_rough_glass(self._h, ir, roughness, sigma), "rough_glass")
 
     def dielectric(self, index_of_refraction) -> int:
         return _check_id(_lib.rt_scene_add_dielectric(self._h, index_of_refraction), "dielectric")

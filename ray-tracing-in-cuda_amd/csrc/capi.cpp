@@ -343,6 +343,14 @@ int rt_scene_add_plastic(rt_scene *s, int texture, float ior, float roughness) {
     m.type = RT_MAT_PLASTIC, m.texture = texture, m.ir = ior, m.fuzz = roughness;
     return add_glossy(s, m, "rt_scene_add_plastic");
 }
+// rough glass: ir the index, fuzz the roughness, albedo the absorption coefficient (NULL: clear)
+int rt_scene_add_rough_glass(rt_scene *s, float ir, float roughness, const float absorption[3]) {
+    rt_material m;
+    memset(&m, 0, sizeof m);
+    m.type = RT_MAT_ROUGH_GLASS, m.texture = -1, m.ir = ir, m.fuzz = roughness;
+    if (absorption) memcpy(m.albedo, absorption, sizeof m.albedo);
+    return add_glossy(s, m, "rt_scene_add_rough_glass");
+}
 int rt_scene_add_dielectric(rt_scene *s, float ir) { return add_material(s, RT_MAT_DIELECTRIC, -1, nullptr, 0, ir); }
 int rt_scene_add_diffuse_light(rt_scene *s, int texture) {
     return add_material(s, RT_MAT_DIFFUSE_LIGHT, texture, nullptr, 0, 0);

@@ -113,7 +113,11 @@ enum MatKind : int32_t {
     // vertex on as the matching *_IMAGE kind, except plastic (whose light sample needs the colour again at full precision)
     MK_LAMBERT_NOISE = 13,
     MK_LIGHT_NOISE = 14,
-    MK_PLASTIC_NOISE = 15    // p1 = r0 (the kind rides in 6 bits of a glossy vertex's packed word: kinds stay below 64)
+    MK_PLASTIC_NOISE = 15,   // p1 = r0 (the kind rides in 6 bits of a glossy vertex's packed word: kinds stay below 64)
+    // rough glass (rt_glass.h), the third glossy material: {kind, alpha, 1/ir, r}{sigma.rgb, ir}{., ., ., bump} --
+    // p0 and p2 as the other two, p1 = 1/ir (eta of a front hit), c0 = the absorption coefficient per unit length,
+    // p3 (c0.w) = ir (eta of a back hit).  In a glossy vertex's packed word a back hit rides as kind 17 (bit 0 set)
+    MK_ROUGH_GLASS = 16
 };
 
 // Per-launch values the kernel needs only when a wave fetches or flushes a work item.  They live in global

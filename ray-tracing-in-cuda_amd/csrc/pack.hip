@@ -1110,6 +1110,11 @@ void write_materials(float *I, const RenderParams &L, const Scene &s, const Sphe
             }
             break;
         }
+        case RT_MAT_ROUGH_GLASS:  // eta of a front hit in p1, of a back hit in c0.w; albedo holds sigma
+            kind = MK_ROUGH_GLASS;
+            q[1] = std::max(m.fuzz * m.fuzz, 1e-3f), q[2] = 1.0f / m.ir, q[3] = m.fuzz;
+            q[4] = m.albedo[0], q[5] = m.albedo[1], q[6] = m.albedo[2], q[7] = m.ir;
+            break;
         default: break;
         }
         q[0] = bits(kind);

@@ -1193,7 +1193,7 @@
                 // except plastic, whose light sample needs the colour again (step (7) evaluates it again from the same point).
                 bool noise_tex = false;
                 if constexpr (EXT && !QUERY) {
-                    if (kind >= MK_LAMBERT_NOISE) {
+                    if (kind >= MK_LAMBERT_NOISE && kind <= MK_PLASTIC_NOISE) {  // (rough glass, above them, has no texture)
                         const float4 c = noise_texel(image, M[1], M[2], px, py, pz);
                         tex_r = c.x, tex_g = c.y, tex_b = c.z;
                         noise_tex = true;
@@ -1328,9 +1328,10 @@
                 if (COUNT) {
                     c_hits++;
                     // (the glossy materials, DESIGN 7m: plastic counts with the lambertians, rough metal with the metals)
-                    if (kind <= MK_LAMBERT_IMAGE || (EXT && kind >= MK_PLASTIC_SOLID)) c_scatter0++;
+                    // (rough glass, DESIGN 7r, with the dielectrics)
+                    if (kind <= MK_LAMBERT_IMAGE || (EXT && kind >= MK_PLASTIC_SOLID && kind != MK_ROUGH_GLASS)) c_scatter0++;
                     else if (kind == MK_METAL || (EXT && kind == MK_ROUGH_METAL)) c_scatter1++;
-                    else if (kind == MK_DIELECTRIC) c_scatter2++;
+                    else if (kind == MK_DIELECTRIC || (EXT && kind == MK_ROUGH_GLASS)) c_scatter2++;
                     else c_scatter3++;
                 }
                 if constexpr (QUERY) {
@@ -1344,7 +1345,7 @@
                         const bool odd = (kind == MK_LAMBERT_CHECKER || kind == MK_LIGHT_CHECKER || kind == MK_PLASTIC_CHECKER) && checker_odd(px, py, pz);
                         L_r = odd ? q2.x : q1.x, L_g = odd ? q2.y : q1.y, L_b = odd ? q2.z : q1.z;
                         if (kind == MK_LAMBERT_IMAGE || kind == MK_LIGHT_IMAGE || kind == MK_PLASTIC_IMAGE || kind == MK_PLASTIC_NOISE) L_r = tex_r, L_g = tex_g, L_b = tex_b;
-                        if (kind == MK_DIELECTRIC) L_r = L_g = L_b = 1.0f;
+                        if (kind == MK_DIELECTRIC || (EXT && kind == MK_ROUGH_GLASS)) L_r = L_g = L_b = 1.0f;  // (c0 of rough glass is its sigma)
                     } else if (P.feature == RT_FEATURE_NORMAL) {
                         L_r = nx, L_g = ny, L_b = nz;
                     } else {
@@ -1666,6 +1667,7 @@
         float vb_r = 0, vb_g = 0, vb_b = 0, mrx = 0, mry = 0, mrz = 0, mfz = 0;
         float glossy_pdf = 0;  // (EXT, NEE) pdf_b of the direction a glossy vertex drew
         uint32_t gtex = 0u;    // (EXT, NEE) an image-textured plastic vertex: its texel, 8 bits a channel, for the light-sample step
+        float gv_r = 1.0f, gv_g = 1.0f, gv_b = 1.0f;  // (EXT) a rough-glass back hit: its tint, until it is folded into vb below
         if (!QUERY && kind >= 0) {
             const float4 *M = rec_at(image + P.off_mat, __umul24((uint32_t)mat, 48u));  // (below 2^24 materials: scene_validate)
             if constexpr (MEDIA) {  // (a medium's record 1 is {albedo, density}: where a material keeps c0)
@@ -1700,8 +1702,18 @@
                     float gpdf = 0.0f;
                     bool below = false, lobe = false;
                     at_r = at_g = at_b = 0.0f, ndx = ndy = ndz = 0.0f;
+                    // Rough glass (rt_glass.h) goes through the same body as a rough metal with F0 = 1: uf where plastic
+                    // draws ul, then the same two.  The tint of a back hit is formed here, from the hit point and the origin of
+                    // the ray that arrived (both still live: t |d| = |p - o|), so that nothing of it is carried through the walk;
+                    // it goes into the attenuation and into the throughput the light sample starts from (gv), nowhere else.
+                    const bool glass = kind == MK_ROUGH_GLASS;
+                    if (glass && !front) {
+                        const float ex = px - ox, ey = py - oy, ez = pz - oz;
+                        const float dist = rt_sqrtf(dot3(ex, ey, ez, ex, ey, ez));
+                        gv_r = glass_tint(q1.x, dist), gv_g = glass_tint(q1.y, dist), gv_b = glass_tint(q1.z, dist);
+                    }
                     if (-dot3(ux, uy, uz, nx, ny, nz) > 0.0f) {
-                        const bool plastic = kind != MK_ROUGH_METAL;
+                        const bool plastic = kind != MK_ROUGH_METAL && !glass;
                         // F0, or the coat's r0 in every channel with the body's colour beside it
                         float f_r = q1.x, f_g = q1.y, f_b = q1.z, rh_r = 0.0f, rh_g = 0.0f, rh_b = 0.0f, ul = 0.0f;
                         if (plastic) {
@@ -1709,14 +1721,18 @@
                             rh_r = odd ? q2.x : q1.x, rh_g = odd ? q2.y : q1.y, rh_b = odd ? q2.z : q1.z;
                             if (kind == MK_PLASTIC_IMAGE || kind == MK_PLASTIC_NOISE) rh_r = tex_r, rh_g = tex_g, rh_b = tex_b;
                             f_r = f_g = f_b = q0.z;
-                            ul = rng_next<COUNT>(rng);
                         }
+                        if (glass) f_r = f_g = f_b = 1.0f;  // (its c0 is sigma)
+                        if (plastic || glass) ul = rng_next<COUNT>(rng);
                         const float u1 = rng_next<COUNT>(rng), u2 = rng_next<COUNT>(rng);
-                        scattered = glossy_sample(plastic, nx, ny, nz, ux, uy, uz, q0.y, f_r, f_g, f_b, rh_r, rh_g, rh_b, ul, u1, u2, ndx, ndy,
-                                                  ndz, at_r, at_g, at_b, gpdf, below, lobe);
+                        scattered = glossy_sample_body(glass ? GLOSSY_GLASS : (plastic ? GLOSSY_PLASTIC : GLOSSY_METAL), nx, ny, nz, ux, uy, uz, q0.y,
+                                                       f_r, f_g, f_b, rh_r, rh_g, rh_b, front ? q0.z : q1.w, ul, u1, u2, ndx, ndy, ndz, at_r, at_g,
+                                                       at_b, gpdf, below, lobe, NEE && !ENV);  // (the Fresnel term behind a call there: DESIGN 7r)
+                        if (glass) at_r *= gv_r, at_g *= gv_g, at_b *= gv_b;
                     } else {
                         scattered = false, below = true;
                     }
+                    if (glass && !front) kind = MK_ROUGH_GLASS + 1;  // (what the packed word below tells the light sample: eta = ir)
                     if (NEE) {
                         // the light sample's f cos is not albedo x pdf_b here: step (7) evaluates the material for the light's
                         // direction, from -unit(d) (kept where metal keeps its mirror direction) and the throughput in FRONT
@@ -1774,7 +1790,8 @@
                 }
                 mis_pdf = cpdf;
                 vb_r = beta_r * at_r, vb_g = beta_g * at_g, vb_b = beta_b * at_b;
-                if (glossy) vb_r = beta_r, vb_g = beta_g, vb_b = beta_b;
+                // (the throughput in front of a glossy vertex; rough glass: times its tint, which is not part of glass_eval)
+                if (glossy) vb_r = beta_r * gv_r, vb_g = beta_g * gv_g, vb_b = beta_b * gv_b;
                 // an absorbed metal vertex still samples its light when its continuation would have been traced: the light
                 // sample may not depend on the direction the BSDF drew
                 nee_end = !scattered;
@@ -1947,8 +1964,10 @@
                 const int gkind = (int)((gbits >> 24) & 63u);
                 const float4 *M = rec_at(image + P.off_mat, __umul24(gbits & 0xffffffu, 48u));
                 const float4 q0 = M[0], q1 = M[1], q2 = M[2];
-                const bool plastic = gkind != MK_ROUGH_METAL;
+                const bool glass = gkind >= MK_ROUGH_GLASS;  // (bit 0 of the kind: a back hit)
+                const bool plastic = gkind != MK_ROUGH_METAL && !glass;
                 float f_r = q1.x, f_g = q1.y, f_b = q1.z, rh_r = 0.0f, rh_g = 0.0f, rh_b = 0.0f;
+                if (glass) f_r = f_g = f_b = 1.0f;  // (its c0 is sigma; its tint is in vb already)
                 if (plastic) {
                     const bool odd = gkind == MK_PLASTIC_CHECKER && checker_odd(px, py, pz);
                     rh_r = odd ? q2.x : q1.x, rh_g = odd ? q2.y : q1.y, rh_b = odd ? q2.z : q1.z;
@@ -1962,7 +1981,8 @@
                     }
                     f_r = f_g = f_b = q0.z;
                 }
-                glossy_eval(plastic, nx, ny, nz, mrx, mry, mrz, q0.y, f_r, f_g, f_b, rh_r, rh_g, rh_b, wx, wy, wz, gf_r, gf_g, gf_b, pb);
+                glossy_eval_body(glass ? GLOSSY_GLASS : (plastic ? GLOSSY_PLASTIC : GLOSSY_METAL), nx, ny, nz, mrx, mry, mrz, q0.y, f_r, f_g, f_b, rh_r,
+                                 rh_g, rh_b, (gkind & 1) ? q1.w : q0.z, wx, wy, wz, gf_r, gf_g, gf_b, pb, !ENV);
             } else
             if (wn > 0.0f) pb = mfz > 0.0f ? metal_pdf(wx, wy, wz, mrx, mry, mrz, mfz) : wn * kInvPi;
             // f cos / p_l x the power heuristic's p_l^2 / (p_l^2 + pdf_b^2) = albedo x pdf_b p_l / (p_l^2 + pdf_b^2)

@@ -243,6 +243,7 @@ __device__ __forceinline__ unsigned long long radiance_to_fixed(float v) {
 // the glossy materials: behind rt_sqrtf, which they use
 }  // namespace rtmi
 #include "rt_glossy.h"
+#include "rt_glass.h"
 #include "rt_noise.h"
 #include "rt_quad.h"
 namespace rtmi {

@@ -159,11 +159,55 @@ RTMI_HD void glossy_terms(bool plastic, float alpha, float f0r, float f0g, float
         pdf = fmaf(ps, pdf_s, (1.0f - ps) * cpi);
     }
 }
-// The scatter step.  Draws: u1, u2, and for plastic ul in front of them.  false: an absorbed vertex (absorbed_wo: wo.z <= 0,
-// else wi.z <= 0); true: the unit scattered direction (world), the attenuation and pdf_b of that direction.
-RTMI_HD bool glossy_sample(bool plastic, float nx, float ny, float nz, float ux, float uy, float uz, float alpha, float f0r, float f0g,
-                           float f0b, float rho_r, float rho_g, float rho_b, float ul, float u1, float u2, float &wx, float &wy,
-                           float &wz, float &at_r, float &at_g, float &at_b, float &pdf, bool &absorbed_wo, bool &lobe) {
+// ---- rough glass (rt_glass.h has its entry points and the tint), the third material of the same body: a rough metal
+// with F0 = 1 whose microfacet reflects with the exact unpolarised Fresnel term F(c; eta) of c = wo.h and refracts otherwise.
+// s2 = eta^2 (1 - c^2); F = 1 (and ct = 0) where s2 >= 1, else ct = sqrt(1 - s2), rs = (eta c - ct) / (eta c + ct),
+// rp = (c - eta ct) / (c + eta ct), F = (rs^2 + rp^2) / 2
+RTMI_HD float glass_fresnel(float eta, float c, float &ct) {
+    const float s2 = (eta * eta) * fmaf(-c, c, 1.0f);
+    ct = 0.0f;
+    if (s2 >= 1.0f) return 1.0f;
+    ct = glossy_sqrtf(1.0f - s2);
+    const float ec = eta * c, et = eta * ct;
+    const float rs = (ec - ct) / (ec + ct), rp = (c - et) / (c + et);
+    return 0.5f * fmaf(rs, rs, rp * rp);
+}
+// The same term behind a call, for the kernels in which the inlined text costs the scenes WITHOUT the material more than a call's
+// save area does (DESIGN 7r has both forms' rows: the light-sampling kernels without an environment).  A body called with
+// fresnel_call takes this one on the device; the values are the same bits either way.
+struct GlassFresnel {
+    float F, ct;  // (by value: in registers, where two references would go through scratch)
+};
+#if defined(__HIP_DEVICE_COMPILE__) && __HIP_DEVICE_COMPILE__
+__device__ inline __attribute__((noinline)) GlassFresnel glass_fresnel_call(float eta, float c) {
+    GlassFresnel r;
+    r.F = glass_fresnel(eta, c, r.ct);
+    return r;
+}
+#endif
+RTMI_HD float glass_fresnel_of(bool call, float eta, float c, float &ct) {
+#if defined(__HIP_DEVICE_COMPILE__) && __HIP_DEVICE_COMPILE__
+    if (call) {
+        const GlassFresnel r = glass_fresnel_call(eta, c);
+        ct = r.ct;
+        return r.F;
+    }
+#endif
+    return glass_fresnel(eta, c, ct);
+}
+enum GlossyMode : int { GLOSSY_METAL = 0, GLOSSY_PLASTIC = 1, GLOSSY_GLASS = 2 };
+
+// The scatter step.  Draws: u1, u2, and in front of them ul for plastic (the choice between coat and body) and for glass (reflect
+// iff ul < F).  false: an absorbed vertex (absorbed_wo: wo.z <= 0, else the direction came out on the wrong side: wi.z <= 0, for a
+// refracted one wi.z >= 0); true: the unit scattered direction (world), the attenuation and pdf_b of that direction.
+// Glass (f0 = 1, eta = front ? 1 / ir : ir): reflected, wi = 2 c h - wo and pdf_b = F pdf_s; refracted (lobe comes back false),
+// wi = (eta c - ct) h - eta wo and pdf_b = -1 (the light strategy never produces it); the attenuation is G2 / G1(wo) either way,
+// Lambda of wi as it stands (it is even in z), and the caller multiplies it by the tint.
+RTMI_HD bool glossy_sample_body(int mode, float nx, float ny, float nz, float ux, float uy, float uz, float alpha, float f0r, float f0g,
+                                float f0b, float rho_r, float rho_g, float rho_b, float eta, float ul, float u1, float u2, float &wx,
+                                float &wy, float &wz, float &at_r, float &at_g, float &at_b, float &pdf, bool &absorbed_wo, bool &lobe,
+                                bool fresnel_call = false) {
+    const bool plastic = mode == GLOSSY_PLASTIC, glass = mode == GLOSSY_GLASS;
     const GlossyLocal g = glossy_local(nx, ny, nz, ux, uy, uz);
     absorbed_wo = !(g.woz > 0.0f);
     lobe = false;
@@ -180,7 +224,17 @@ RTMI_HD bool glossy_sample(bool plastic, float nx, float ny, float nz, float ux,
         wix = rr * cp, wiy = rr * sp, wiz = glossy_sqrtf(1.0f - u1);
         glossy_half(g, wix, wiy, wiz, hx, hy, hz, woh);
     }
-    if (!(wiz > 0.0f)) return false;
+    float F = 1.0f;
+    if (glass) {
+        float ct;
+        F = glass_fresnel_of(fresnel_call, eta, woh, ct);
+        lobe = ul < F;
+        if (!lobe) {
+            const float k = fmaf(eta, woh, -ct);
+            wix = fmaf(k, hx, -(eta * g.wox)), wiy = fmaf(k, hy, -(eta * g.woy)), wiz = fmaf(k, hz, -(eta * g.woz));
+        }
+    }
+    if ((glass && !lobe) ? !(wiz < 0.0f) : !(wiz > 0.0f)) return false;
     float fr, fg, fb, ratio;
     glossy_terms(plastic, alpha, f0r, f0g, f0b, rho_r, rho_g, rho_b, g, wix, wiy, wiz, hx, hy, hz, woh, fr, fg, fb, pdf, ratio);
     if (plastic) {
@@ -188,13 +242,22 @@ RTMI_HD bool glossy_sample(bool plastic, float nx, float ny, float nz, float ux,
     } else {
         at_r = glossy_schlick(f0r, woh) * ratio, at_g = glossy_schlick(f0g, woh) * ratio, at_b = glossy_schlick(f0b, woh) * ratio;
     }
+    if (glass) pdf = lobe ? F * pdf : -1.0f;
     glossy_to_world(g, nx, ny, nz, wix, wiy, wiz, wx, wy, wz);
     return true;
 }
+RTMI_HD bool glossy_sample(bool plastic, float nx, float ny, float nz, float ux, float uy, float uz, float alpha, float f0r, float f0g,
+                           float f0b, float rho_r, float rho_g, float rho_b, float ul, float u1, float u2, float &wx, float &wy,
+                           float &wz, float &at_r, float &at_g, float &at_b, float &pdf, bool &absorbed_wo, bool &lobe) {
+    return glossy_sample_body(plastic ? GLOSSY_PLASTIC : GLOSSY_METAL, nx, ny, nz, ux, uy, uz, alpha, f0r, f0g, f0b, rho_r, rho_g, rho_b, 1.0f,
+                              ul, u1, u2, wx, wy, wz, at_r, at_g, at_b, pdf, absorbed_wo, lobe);
+}
 // f cos and pdf_b of the unit world direction (lx, ly, lz); zeros where the vertex or the direction is below the surface
-RTMI_HD void glossy_eval(bool plastic, float nx, float ny, float nz, float ux, float uy, float uz, float alpha, float f0r, float f0g,
-                         float f0b, float rho_r, float rho_g, float rho_b, float lx, float ly, float lz, float &fc_r, float &fc_g,
-                         float &fc_b, float &pdf) {
+// (glass, f0 = 1: the reflection hemisphere alone -- f cos = F(wo.h) D G2 / (4 wo.z) without the tint, pdf_b = F(wo.h) pdf_s)
+RTMI_HD void glossy_eval_body(int mode, float nx, float ny, float nz, float ux, float uy, float uz, float alpha, float f0r, float f0g,
+                              float f0b, float rho_r, float rho_g, float rho_b, float eta, float lx, float ly, float lz, float &fc_r,
+                              float &fc_g, float &fc_b, float &pdf, bool fresnel_call = false) {
+    const bool plastic = mode == GLOSSY_PLASTIC;
     const GlossyLocal g = glossy_local(nx, ny, nz, ux, uy, uz);
     const float wix = glossy_dot(lx, ly, lz, g.t1x, g.t1y, g.t1z), wiy = glossy_dot(lx, ly, lz, g.t2x, g.t2y, g.t2z),
                 wiz = glossy_dot(lx, ly, lz, nx, ny, nz);
@@ -203,6 +266,17 @@ RTMI_HD void glossy_eval(bool plastic, float nx, float ny, float nz, float ux, f
     float hx, hy, hz, woh, ratio;
     glossy_half(g, wix, wiy, wiz, hx, hy, hz, woh);
     glossy_terms(plastic, alpha, f0r, f0g, f0b, rho_r, rho_g, rho_b, g, wix, wiy, wiz, hx, hy, hz, woh, fc_r, fc_g, fc_b, pdf, ratio);
+    if (mode == GLOSSY_GLASS) {
+        float ct;
+        const float F = glass_fresnel_of(fresnel_call, eta, woh, ct);
+        fc_r *= F, fc_g *= F, fc_b *= F, pdf *= F;
+    }
+}
+RTMI_HD void glossy_eval(bool plastic, float nx, float ny, float nz, float ux, float uy, float uz, float alpha, float f0r, float f0g,
+                         float f0b, float rho_r, float rho_g, float rho_b, float lx, float ly, float lz, float &fc_r, float &fc_g,
+                         float &fc_b, float &pdf) {
+    glossy_eval_body(plastic ? GLOSSY_PLASTIC : GLOSSY_METAL, nx, ny, nz, ux, uy, uz, alpha, f0r, f0g, f0b, rho_r, rho_g, rho_b, 1.0f, lx, ly,
+                     lz, fc_r, fc_g, fc_b, pdf);
 }
 
 }  // namespace rtmi

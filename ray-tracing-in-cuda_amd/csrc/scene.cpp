@@ -281,6 +281,20 @@ bool glossy_material_ok(const rt_material &m, size_t textures, const char *where
                 set_error("%s: rough_metal albedo (F0) components must be finite and in [0, 1] (got %g)", where, (double)m.albedo[k]);
                 return false;
             }
+    } else if (m.type == RT_MAT_ROUGH_GLASS) {  // albedo holds the absorption coefficient
+        if (!(m.ir > 1.0f && m.ir < INFINITY)) {
+            set_error("%s: rough_glass ir must be finite and > 1 (got %g)", where, (double)m.ir);
+            return false;
+        }
+        for (int k = 0; k < 3; ++k)
+            if (!(m.albedo[k] >= 0.0f && m.albedo[k] < INFINITY)) {
+                set_error("%s: rough_glass absorption components must be finite and >= 0 (got %g)", where, (double)m.albedo[k]);
+                return false;
+            }
+        if (m.texture != -1) {
+            set_error("%s: rough_glass takes no texture (got %d)", where, m.texture);
+            return false;
+        }
     } else {
         if (!(m.ir > 1.0f && m.ir < INFINITY)) {
             set_error("%s: plastic ior must be finite and > 1 (got %g)", where, (double)m.ir);
@@ -1213,6 +1227,28 @@ int scene_from_json(const char *text, size_t len, Scene &s, const char *base_dir
                 rec.ir = (float)r.num(m, "ior", where);
                 rec.fuzz = (float)r.num(m, "roughness", where);
                 if (r.ok && !glossy_material_ok(rec, s.texs.size(), where)) r.ok = false;
+            } else if (ty->str == "rough_glass") {  // fuzz holds the roughness, albedo the absorption coefficient
+                rec.type = RT_MAT_ROUGH_GLASS;
+                only_keys(m, {"type", "ir", "roughness", "absorption", "tint", "tint_distance", "bump"});
+                rec.ir = (float)r.num(m, "ir", where);
+                rec.fuzz = (float)r.num(m, "roughness", where);
+                const bool has_tint = m.find("tint") || m.find("tint_distance");
+                if (m.find("absorption") && has_tint) r.fail("%s: \"absorption\" and \"tint\" / \"tint_distance\" exclude each other", where);
+                else if (m.find("absorption")) {
+                    double c[3];
+                    r.vec3(m, "absorption", where, c);
+                    for (int k = 0; k < 3; ++k) rec.albedo[k] = (float)c[k];
+                } else if (has_tint) {  // sigma = -ln(tint) / tint_distance, in fp64, rounded once
+                    double c[3] = {1, 1, 1};
+                    r.vec3(m, "tint", where, c);
+                    const double d = r.num(m, "tint_distance", where);
+                    if (r.ok && !(d > 0.0 && d < (double)INFINITY)) r.fail("%s: tint_distance must be finite and > 0 (got %g)", where, d);
+                    for (int k = 0; k < 3 && r.ok; ++k) {
+                        if (!(c[k] > 0.0 && c[k] <= 1.0)) r.fail("%s: tint components must be in (0, 1] (got %g)", where, c[k]);
+                        else rec.albedo[k] = (float)(-std::log(c[k]) / d + 0.0);
+                    }
+                }
+                if (r.ok && !glossy_material_ok(rec, s.texs.size(), where)) r.ok = false;
             } else if (ty->str == "dielectric") {
                 rec.type = RT_MAT_DIELECTRIC;
                 rec.ir = (float)r.num(m, "index_of_refraction", where);
@@ -1592,6 +1628,11 @@ std::string scene_to_json(const Scene &s) {
         case RT_MAT_PLASTIC:
             o += "{\"type\": \"plastic\", \"texture\": " + std::to_string(m.texture) + ", \"ior\": " + json_float(m.ir) +
                  ", \"roughness\": " + json_float(m.fuzz) + "}";
+            break;
+        case RT_MAT_ROUGH_GLASS:  // (a tint comes back as the absorption it was converted to)
+            o += "{\"type\": \"rough_glass\", \"ir\": " + json_float(m.ir) + ", \"roughness\": " + json_float(m.fuzz) + ", \"absorption\": ";
+            put_vec3(o, m.albedo);
+            o += "}";
             break;
         default: break;
         }

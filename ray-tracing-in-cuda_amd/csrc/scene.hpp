@@ -142,7 +142,8 @@ inline bool tri_has_normals(const rt_prim &p) {
 
 // glossy materials: does the material table hold one (such a scene runs the general kernels over the wide tables);
 // is a rough_metal / plastic record within its argument rules (false: the message is set, prefixed with `where`)
-inline bool is_glossy(const rt_material &m) { return m.type == RT_MAT_ROUGH_METAL || m.type == RT_MAT_PLASTIC; }
+// (rough_glass, DESIGN 7r, is the third of them)
+inline bool is_glossy(const rt_material &m) { return m.type == RT_MAT_ROUGH_METAL || m.type == RT_MAT_PLASTIC || m.type == RT_MAT_ROUGH_GLASS; }
 inline bool scene_has_glossy(const Scene &s) {
     for (const rt_material &m : s.mats)
         if (is_glossy(m)) return true;
