@@ -235,8 +235,8 @@ int rt_scene_get_mesh_lights(const rt_scene *s); /* 1, 0, or -rt_status */
 int rt_scene_set_nested_grid(rt_scene *s, int on);
 int rt_scene_get_nested_grid(const rt_scene *s); /* 1, 0, or -rt_status */
 typedef struct rt_light {
-    int32_t prim;        /* index into the primitive list                      */
-    int32_t shape;       /* rt_prim_type: sphere, xy / xz / yz rect, cylinder, quad or -- with mesh lights on -- triangle */
+    int32_t prim;        /* index into the primitive list (-1: an analytic light or the environment) */
+    int32_t shape;       /* rt_prim_type: sphere, xy / xz / yz rect, cylinder, quad or -- with mesh lights on -- triangle; or RT_LIGHT_* */
     float probability;   /* selection probability (the list sums to 1)         */
     float area;          /* surface area (the cylinder's tube; a triangle's |e1 x e2| / 2; a quad's |u x v|) */
     float emission[3];   /* emission (a checker texture: its even colour)      */
@@ -246,6 +246,49 @@ typedef struct rt_light {
  * with something to sample comes last: prim = -1, shape = RT_LIGHT_ENVIRONMENT, area = 4 pi, emission = its mean radiance. */
 int rt_scene_get_lights(const rt_scene *s, rt_light *out, int cap);
 #define RT_LIGHT_ENVIRONMENT 100 /* rt_light.shape of the environment (outside rt_prim_type's values) */
+
+/* ---- analytic lights: point, spot and distant -------------------
+ * An analytic light has no geometry: the camera does not see it, no BSDF ray hits it, feature passes and ray queries ignore
+ * it.  It acts through the light sample of a vertex alone, so only with light sampling on (rt_scene_set_light_sampling); with
+ * it off the lights are not in the tables and the scene renders the bytes of the scene without them.  Its sample carries MIS
+ * weight 1 (the BSDF strategy can never produce it).  Vertices that take no light sample -- dielectric, metal below fuzz
+ * 0.05, glossy below the minimum roughness -- see nothing of these lights (no highlight of a delta light on a near-mirror).
+ * With psel the light's selection probability, vb the throughput and fcos(w) the material's f cos towards w, at a vertex p:
+ *   point    position x, intensity I (RGB per steradian): ld = x - p, d2 = ld.ld, contribution vb fcos(ld/|ld|) I / (psel d2);
+ *            d2 = 0: no sample.
+ *   spot     the point light times a falloff: with the unit axis a (the direction it points), c = a.(-ld/|ld|),
+ *            s = clamp((c - cos(outer)) / (cos(inner) - cos(outer)), 0, 1), falloff = s^2 (3 - 2 s).
+ *   distant  unit direction t TOWARDS the light, normal irradiance E (RGB), angular radius alpha in [0, 45] degrees: the
+ *            sample direction w is uniform in the cone of half-angle alpha about t (alpha = 0: w = t exactly); the cone's
+ *            radiance is E / (pi sin^2 alpha), so that E is the irradiance on a surface facing the light, and the
+ *            contribution is vb fcos(w) E 2 / (1 + cos alpha) / psel.  The shadow ray is 4 x the scene's bounding radius long.
+ * Selection weights, beside area x mean luminance of the area emitters: 4 lum(I); 2 (1 - (cos_i + cos_o) / 2) lum(I);
+ * r^2 lum(E) with r the bounding radius of the primitives.  A light whose weight is not positive and finite is left out.
+ * Rules (RT_ERR_SCENE from the JSON reader, RT_ERR_ARG from the calls below): colours finite, >= 0, not all zero; directions
+ * finite and non-zero (normalised in fp64); 0 <= inner <= outer, 0 < outer <= 179; 0 <= angular radius <= 45.
+ * Not combined with media, moving spheres or the nested grid, which refuse as light sampling refuses them.
+ * JSON: top-level "lights": [{"type": "point", "position", "intensity"}, {"type": "spot", "position", "direction" | "target",
+ * "intensity", "inner_angle", "outer_angle"}, {"type": "distant", "direction", "irradiance", ["angular_radius"]}]; "lights"
+ * without a "light_sampling" key switches light sampling on. */
+#define RT_LIGHT_POINT 101
+#define RT_LIGHT_SPOT 102
+#define RT_LIGHT_DISTANT 103
+typedef struct rt_analytic_light {
+    int32_t type;       /* RT_LIGHT_POINT / RT_LIGHT_SPOT / RT_LIGHT_DISTANT */
+    float position[3];  /* point, spot */
+    float direction[3]; /* spot: where it points; distant: the direction the light TRAVELS (as given, not normalised) */
+    float color[3];     /* point, spot: intensity per steradian; distant: normal irradiance */
+    float angle[2];     /* degrees.  spot: inner, outer; distant: angular radius, 0 */
+} rt_analytic_light;
+int rt_scene_add_point_light(rt_scene *s, const float position[3], const float intensity[3]); /* -> index, or -rt_status */
+int rt_scene_add_spot_light(rt_scene *s, const float position[3], const float direction[3], const float intensity[3],
+                            float inner_deg, float outer_deg);
+int rt_scene_add_distant_light(rt_scene *s, const float direction_of_travel[3], const float irradiance[3], float angular_radius_deg);
+int rt_scene_get_analytic_lights(const rt_scene *s, rt_analytic_light *out, int cap); /* -> count, or -rt_status */
+int rt_scene_clear_analytic_lights(rt_scene *s);
+/* rt_scene_get_lights lists them after the area emitters and before the environment: prim = -1, shape = the type, emission =
+ * emission_odd = the colour as the light record holds it (a distant light's times 2 / (1 + cos alpha)), area = the measure of
+ * the selection weight: 4 pi, 2 pi (1 - (cos_i + cos_o) / 2), pi r^2. */
 
 /* ---- environment map (image-based lighting) -------------------------------
  * rows x cols fp32 RGB texels (finite, >= 0) in lat-long layout: row 0 is the zenith (+y), rows go down to -y, columns go
@@ -753,7 +796,7 @@ int rt_abi_version(void);
 /* sizeof of the ABI structs as this library was compiled (binding self-checks):
  * 0 rt_opts, 1 rt_stats, 2 rt_prim, 3 rt_material, 4 rt_texture, 5 rt_camera, 6 rt_scene_info, 7 rt_table_info,
  * 8 rt_adaptive, 9 rt_adaptive_stats, 10 rt_nested_info, 16 rt_denoise, 17 rt_medium, 18 rt_moving_sphere, 19 rt_display,
- * 20 rt_display_stats, 21 rt_ray, 22 rt_hit, 24 rt_noise; else 0 */
+ * 20 rt_display_stats, 21 rt_ray, 22 rt_hit, 24 rt_noise, 25 rt_analytic_light; else 0 */
 size_t rt_struct_size(int which);
 /* number of usable gfx950 devices, or -rt_status */
 int rt_device_count(void);

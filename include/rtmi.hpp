@@ -317,6 +317,30 @@ public:
         return out;
     }
     void clear_moving_spheres() { check(rt_scene_clear_moving_spheres(s_), "clear_moving_spheres"); }
+    // analytic lights (rt_scene_add_point_light ...): lights without geometry, sampled by light sampling alone -> index
+    int point_light(point3 position, color intensity) {
+        const int id = rt_scene_add_point_light(s_, position.e, intensity.e);
+        if (id < 0) throw error(-id, "point_light");
+        return id;
+    }
+    int spot_light(point3 position, vec3 direction, color intensity, float inner_deg, float outer_deg) {
+        const int id = rt_scene_add_spot_light(s_, position.e, direction.e, intensity.e, inner_deg, outer_deg);
+        if (id < 0) throw error(-id, "spot_light");
+        return id;
+    }
+    int distant_light(vec3 direction_of_travel, color irradiance, float angular_radius_deg = 0.0f) {
+        const int id = rt_scene_add_distant_light(s_, direction_of_travel.e, irradiance.e, angular_radius_deg);
+        if (id < 0) throw error(-id, "distant_light");
+        return id;
+    }
+    std::vector<rt_analytic_light> analytic_lights() const {
+        const int n = rt_scene_get_analytic_lights(s_, nullptr, 0);
+        if (n < 0) throw error(-n, "analytic_lights");
+        std::vector<rt_analytic_light> out((size_t)n);
+        if (n > 0) rt_scene_get_analytic_lights(s_, out.data(), n);
+        return out;
+    }
+    void clear_analytic_lights() { check(rt_scene_clear_analytic_lights(s_), "clear_analytic_lights"); }
     // hittable_list::add
     int add(const hittable &h) {
         if (!h.mat) throw std::logic_error("hittable without a material");

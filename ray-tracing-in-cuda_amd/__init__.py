@@ -68,6 +68,10 @@ HIT_INVALID = -2     # rt_hit.prim of a ray that failed the guard (RT_HIT_INVALI
 TRACE_CLOSEST, TRACE_OCCLUDED = 0, 1
 TRACE_ITEM = 64      # rays per work item of the query kernels (RT_TRACE_ITEM): scheduling only
 TRACE_LAYOUT = 8192  # Stats.kernel_variant of a ray query: the layout | 8192
+LIGHT_POINT, LIGHT_SPOT, LIGHT_DISTANT = 101, 102, 103  # rt_analytic_light.type, and rt_light.shape of such a light
+ANALYTIC_LIGHT_DTYPE = np.dtype(  # rt_analytic_light; angle: degrees -- spot: inner, outer; distant: angular radius, 0
+    [("type", "<i4"), ("position", "<f4", (3,)), ("direction", "<f4", (3,)), ("color", "<f4", (3,)), ("angle", "<f4", (2,))]
+)
 LIGHT_DTYPE = np.dtype(
     [("prim", "<i4"), ("shape", "<i4"), ("probability", "<f4"), ("area", "<f4"), ("emission", "<f4", (3,)),
      ("emission_odd", "<f4", (3,))]
@@ -305,6 +309,12 @@ _sig("rt_scene_get_moving_spheres", C.c_int, _p, _p, C.c_int)
 _sig("rt_scene_clear_moving_spheres", C.c_int, _p)
 _sig("rt_moving_sphere_hit", C.c_int, _p, C.c_float, _f3, _f3, C.c_float, C.POINTER(C.c_float))
 _sig("rt_shutter_time", C.c_float, C.c_uint64, C.c_uint32, C.c_uint32)
+_sig("rt_scene_add_point_light", C.c_int, _p, _f3, _f3)
+_sig("rt_scene_add_spot_light", C.c_int, _p, _f3, _f3, _f3, C.c_float, C.c_float)
+_sig("rt_scene_add_distant_light", C.c_int, _p, _f3, _f3, C.c_float)
+_sig("rt_scene_get_analytic_lights", C.c_int, _p, _p, C.c_int)
+_sig("rt_scene_clear_analytic_lights", C.c_int, _p)
+assert _lib.rt_struct_size(25) == ANALYTIC_LIGHT_DTYPE.itemsize == 48
 _sig("rt_scene_set_nested_grid", C.c_int, _p, C.c_int)
 _sig("rt_scene_get_nested_grid", C.c_int, _p)
 _sig("rt_scene_nested_info", C.c_int, _p, C.POINTER(NestedInfo))
@@ -368,6 +378,8 @@ C_SYMBOLS = [
     "rt_scene_add_medium_sphere", "rt_scene_add_medium_box", "rt_scene_get_media", "rt_scene_clear_media", "rt_medium_interval",
     "rt_scene_add_moving_sphere", "rt_scene_moving_sphere_count", "rt_scene_get_moving_spheres", "rt_scene_clear_moving_spheres",
     "rt_moving_sphere_hit", "rt_shutter_time",
+    "rt_scene_add_point_light", "rt_scene_add_spot_light", "rt_scene_add_distant_light", "rt_scene_get_analytic_lights",
+    "rt_scene_clear_analytic_lights",
     "rt_trace_hip", "rt_trace_hip_device", "rt_ray_valid",
     "rt_render_hip_feature", "rt_render_hip_feature_device", "rt_denoise_hip", "rt_denoise_hip_device",
     "rt_display_hip", "rt_display_hip_device", "rt_display_timing", "rt_write_hdr", "rt_write_pfm",
@@ -502,6 +514,29 @@ class Scene:
 
     def clear_moving_spheres(self):
         _check(_lib.rt_scene_clear_moving_spheres(self._h), "clear_moving_spheres")
+
+    def point_light(self, position, intensity) -> int:
+        """A point light (include/rtmi.h, rt_scene_add_point_light): ``intensity`` is RGB per steradian.  Analytic
+        lights act through light sampling alone (set_light_sampling)."""
+        return _check_id(_lib.rt_scene_add_point_light(self._h, _v3(position), _v3(intensity)), "point_light")
+
+    def spot_light(self, position, direction, intensity, inner_angle: float, outer_angle: float) -> int:
+        """A spot light pointing along ``direction``: full intensity inside ``inner_angle``, a smoothstep of the cosine down
+        to nothing at ``outer_angle`` (degrees from the axis)."""
+        return _check_id(_lib.rt_scene_add_spot_light(self._h, _v3(position), _v3(direction), _v3(intensity), float(inner_angle),
+                                                      float(outer_angle)), "spot_light")
+
+    def distant_light(self, direction, irradiance, angular_radius: float = 0.0) -> int:
+        """A distant light (a sun) whose light travels along ``direction``: ``irradiance`` is what a surface facing it
+        receives, ``angular_radius`` (degrees, at most 45) the half-angle of its disc."""
+        return _check_id(_lib.rt_scene_add_distant_light(self._h, _v3(direction), _v3(irradiance), float(angular_radius)), "distant_light")
+
+    def analytic_lights(self) -> np.ndarray:
+        """The scene's point, spot and distant lights in list order, as given (ANALYTIC_LIGHT_DTYPE records)."""
+        return self._table(_lib.rt_scene_get_analytic_lights, ANALYTIC_LIGHT_DTYPE)
+
+    def clear_analytic_lights(self):
+        _check(_lib.rt_scene_clear_analytic_lights(self._h), "clear_analytic_lights")
 
     @property
     def environment(self):

@@ -64,6 +64,7 @@ size_t rt_struct_size(int which) {
     case 21: return sizeof(rt_ray);
     case 22: return sizeof(rt_hit);
     case 24: return sizeof(rt_noise);  // (23 stays 0)
+    case 25: return sizeof(rt_analytic_light);
     default: return 0;
     }
 }
@@ -1082,6 +1083,57 @@ int rt_scene_clear_moving_spheres(rt_scene *s) {
     if (bad_scene(s, "rt_scene_clear_moving_spheres")) return RT_ERR_ARG;
     if (!s->s.movers.empty()) {  // (a scene without movers stays the scene it was: same version, same tables)
         s->s.movers.clear();
+        s->s.touch();
+    }
+    return RT_OK;
+}
+
+// ---- analytic lights: a list of its own, as given; scene_lights() derives what the tables hold
+static int add_analytic_light(rt_scene *s, const char *fn, int type, const float *position, const float *direction, const float *color,
+                              float a0, float a1) {
+    if (!s || !color || (type != RT_LIGHT_DISTANT && !position) || (type != RT_LIGHT_POINT && !direction)) {
+        set_error("%s: null argument", fn);
+        return -RT_ERR_ARG;
+    }
+    rt_analytic_light l;
+    memset(&l, 0, sizeof l);
+    l.type = type;
+    for (int k = 0; k < 3; ++k) {
+        if (position) l.position[k] = position[k];
+        if (direction) l.direction[k] = direction[k];
+        l.color[k] = color[k];
+    }
+    l.angle[0] = a0, l.angle[1] = a1;
+    if (!analytic_light_ok(l, fn)) return -RT_ERR_ARG;
+    s->s.alights.push_back(l);
+    s->s.touch();
+    return (int)s->s.alights.size() - 1;
+}
+
+int rt_scene_add_point_light(rt_scene *s, const float position[3], const float intensity[3]) {
+    return add_analytic_light(s, "rt_scene_add_point_light", RT_LIGHT_POINT, position, nullptr, intensity, 0.0f, 0.0f);
+}
+
+int rt_scene_add_spot_light(rt_scene *s, const float position[3], const float direction[3], const float intensity[3], float inner_deg,
+                            float outer_deg) {
+    return add_analytic_light(s, "rt_scene_add_spot_light", RT_LIGHT_SPOT, position, direction, intensity, inner_deg, outer_deg);
+}
+
+int rt_scene_add_distant_light(rt_scene *s, const float direction_of_travel[3], const float irradiance[3], float angular_radius_deg) {
+    return add_analytic_light(s, "rt_scene_add_distant_light", RT_LIGHT_DISTANT, nullptr, direction_of_travel, irradiance,
+                              angular_radius_deg, 0.0f);
+}
+
+int rt_scene_get_analytic_lights(const rt_scene *s, rt_analytic_light *out, int cap) {
+    if (bad_scene(s, "rt_scene_get_analytic_lights")) return -RT_ERR_ARG;
+    for (int i = 0; out && i < cap && i < (int)s->s.alights.size(); ++i) out[i] = s->s.alights[(size_t)i];
+    return (int)s->s.alights.size();
+}
+
+int rt_scene_clear_analytic_lights(rt_scene *s) {
+    if (bad_scene(s, "rt_scene_clear_analytic_lights")) return RT_ERR_ARG;
+    if (!s->s.alights.empty()) {  // (a scene without them stays the scene it was: same version, same tables)
+        s->s.alights.clear();
         s->s.touch();
     }
     return RT_OK;

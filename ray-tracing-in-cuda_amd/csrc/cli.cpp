@@ -341,6 +341,9 @@ int main(int argc, char **argv) {
         fprintf(stderr, "rtmi: %s\n", rt_last_error());
         return 1;
     }
+    if (rt_scene_get_light_sampling(sc) == 0 && rt_scene_get_analytic_lights(sc, nullptr, 0) > 0)
+        fprintf(stderr, "rtmi: light sampling is off: the scene's %d point / spot / distant lights light nothing (--nee switches it on)\n",
+                rt_scene_get_analytic_lights(sc, nullptr, 0));
     if (mesh_lights && rt_scene_set_mesh_lights(sc, 1) != RT_OK) {
         fprintf(stderr, "rtmi: %s\n", rt_last_error());
         return 1;

@@ -38,6 +38,9 @@
 //     alias   [nl]  1 x float4   {threshold, alias light(bits), 0, 0}: one draw u picks i = floor(u nl), then i or its alias
 //     slot    [ns + nr + nc + nt + nq] one 32-bit word per grouped primitive id: its light, -1 = not a sampled light
 //     (an environment that is sampled is the last light: {3, -1, selection probability, 1 / 4 pi}, no geometry)
+//     (analytic lights, DESIGN 7s, behind the area emitters: {shape(bits) 6 point / 7 spot / 8 distant, -1, selection
+//      probability, 1 / measure} {colour, 0} {colour, 0}, then point {x, 0}; spot {x, 0} {unit axis a, 0} {cos_o, inv, 0, 0};
+//      distant {unit direction t towards it, 1 - cos alpha} {D = 4 x bounding radius, 0, 0, 0}.  No slot points at them.)
 //   ENVIRONMENT part (only with an environment map; global memory, read by the environment kernels): rt_env.h
 //   MEDIA part (only with at least one medium; global memory, read by the media kernels): rt_media.h.  Two words of the camera
 //     block say where it lies ({count, offset} in the .w of records off_cam + 1 and + 2; zero without media)

@@ -1145,6 +1145,26 @@ void write_lights(float *I, const RenderParams &L, const Scene &s, const SphereS
     for (int k = 0; k < L.ns + L.nr + L.nc + L.nt + L.nq; ++k) slot[k] = -1;
     for (int i = 0; i < L.nl; ++i) {
         const SceneLight &l = lights[(size_t)i];
+        if (l.analytic >= 0) {  // point / spot / distant (rt_lights.h): shapes 6 / 7 / 8, no primitive, no slot
+            const rt_analytic_light &al = s.alights[(size_t)l.analytic];
+            const AnalyticRecord a = analytic_record(al, scene_bound_radius(s));
+            float *r = rec4(I, L.off_light + RT_LIGHT_STRIDE * i);
+            r[0] = bits(al.type == RT_LIGHT_POINT ? 6 : (al.type == RT_LIGHT_SPOT ? 7 : 8)), r[1] = bits(-1);
+            r[2] = (float)l.prob, r[3] = (float)(1.0 / l.area);
+            for (int c3 = 0; c3 < 3; ++c3) r[4 + c3] = r[8 + c3] = a.color[c3];
+            float *g = r + 12;
+            if (al.type == RT_LIGHT_DISTANT) {
+                for (int c3 = 0; c3 < 3; ++c3) g[c3] = (float)a.dir[c3];
+                g[3] = a.omc, g[4] = a.dist;
+            } else {
+                for (int c3 = 0; c3 < 3; ++c3) g[c3] = al.position[c3];
+                if (al.type == RT_LIGHT_SPOT) {
+                    for (int c3 = 0; c3 < 3; ++c3) g[4 + c3] = (float)a.dir[c3];
+                    g[8] = a.cos_o, g[9] = a.inv;
+                }
+            }
+            continue;
+        }
         if (l.prim < 0) {  // the environment: shape 3, no primitive, no geometry (rt_env.h samples it)
             float *r = rec4(I, L.off_light + RT_LIGHT_STRIDE * i);
             r[0] = bits(3), r[1] = bits(-1), r[2] = (float)l.prob, r[3] = (float)(1.0 / l.area);
@@ -1320,7 +1340,7 @@ bool pack_round(const Scene &s, std::vector<char> &forced, std::vector<float> &i
     }
     if (s.env) {
         L.env_scale = s.env_scale, L.env_uoff = env_uoff(s.env_rotate);
-        if (!lights.empty() && lights.back().prim < 0) L.env_sel = (float)lights.back().prob;
+        if (!lights.empty() && lights.back().type == RT_LIGHT_ENVIRONMENT) L.env_sel = (float)lights.back().prob;
     }
 
     image.assign((size_t)(records > 0 ? records : 1) * 4, 0.0f);

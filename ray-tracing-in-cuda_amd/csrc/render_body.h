@@ -1891,28 +1891,39 @@
                 env_sample(EV, u1, u2, ldx, ldy, ldz);
                 env_eval(EV, ldx, ldy, ldz, ev_r, ev_g, ev_b, pe);
                 pl = h.z * pe;
-            } else if (shape == 0) {  // sphere: a direction uniform in the cone it subtends, then the nearer intersection
+            } else if (shape == 0 || shape == 8) {
+                // sphere: a direction uniform in the cone it subtends, then the nearer intersection.  A distant light
+                // goes through the same cone code (light_cone_direction, rt_lights.h: one copy of the sincosf and the frame)
+                // with the record's axis t and 1 - cos(alpha); its ld is D e and its density the selection probability alone
                 const float4 g = lr[3];
-                const float wx = g.x - px, wy = g.y - py, wz = g.z - pz;
-                const float c2 = dot3(wx, wy, wz, wx, wy, wz), r2 = g.w * g.w;
-                if (c2 > r2) {
-                    const float omc = cone_one_minus_cos(r2, c2);
-                    const float om = u1 * omc, cth = 1.0f - om;
-                    const float sth = sqrtf(fmaxf(0.0f, om * (2.0f - om)));
-                    float sp, cp;
-                    sincosf((2.0f * kPi) * u2, &sp, &cp);
-                    const float c = sqrtf(c2), ic = 1.0f / c;
-                    const float ax = wx * ic, ay = wy * ic, az = wz * ic;
-                    // orthonormal frame around the axis (Duff et al. 2017)
-                    float t1x, t1y, t1z, t2x, t2y, t2z;
-                    duff_frame(ax, ay, az, t1x, t1y, t1z, t2x, t2y, t2z);
-                    const float s1 = sth * cp, s2 = sth * sp;
-                    const float ex = fmaf(s1, t1x, fmaf(s2, t2x, cth * ax));
-                    const float ey = fmaf(s1, t1y, fmaf(s2, t2y, cth * ay));
-                    const float ez = fmaf(s1, t1z, fmaf(s2, t2z, cth * az));
-                    const float tt = c * cth - sqrtf(fmaxf(0.0f, r2 - c2 * (sth * sth)));
-                    ldx = tt * ex, ldy = tt * ey, ldz = tt * ez;
+                const bool far = shape == 8;
+                float ax = g.x, ay = g.y, az = g.z, omc = g.w, c = 0.0f, c2 = 0.0f, r2 = 0.0f;
+                bool cone = true;
+                if (!far) {
+                    const float wx = g.x - px, wy = g.y - py, wz = g.z - pz;
+                    c2 = dot3(wx, wy, wz, wx, wy, wz), r2 = g.w * g.w;
+                    cone = c2 > r2;
+                    omc = cone_one_minus_cos(r2, c2);
+                    c = sqrtf(c2);
+                    const float ic = 1.0f / c;
+                    ax = wx * ic, ay = wy * ic, az = wz * ic;
+                }
+                if (cone) {
+                    float ex, ey, ez, cth, sth;
+                    light_cone_direction(ax, ay, az, omc, u1, u2, ex, ey, ez, cth, sth);
+                    float tt = c * cth - sqrtf(fmaxf(0.0f, r2 - c2 * (sth * sth)));
                     pl = h.z / ((2.0f * kPi) * omc);
+                    if (far) tt = lr[4].x, pl = h.z;
+                    ldx = tt * ex, ldy = tt * ey, ldz = tt * ez;
+                }
+            } else if (shape >= 6) {  // point and spot lights (rt_lights.h): ld = x - p, density psel d^2 (/ falloff)
+                const float4 g = lr[3];
+                ldx = g.x - px, ldy = g.y - py, ldz = g.z - pz;
+                const float d2 = dot3(ldx, ldy, ldz, ldx, ldy, ldz);
+                pl = point_light_density(h.z, d2);
+                if (shape == 7) {
+                    const float4 a = lr[4], k = lr[5];
+                    pl = spot_light_density(h.z, d2, spot_falloff(a.x, a.y, a.z, ldx, ldy, ldz, d2, k.x, k.y));
                 }
             } else {
                 float lnx, lny, lnz;  // the light's normal at y
@@ -1987,9 +1998,11 @@
             if (wn > 0.0f) pb = mfz > 0.0f ? metal_pdf(wx, wy, wz, mrx, mry, mrz, mfz) : wn * kInvPi;
             // f cos / p_l x the power heuristic's p_l^2 / (p_l^2 + pdf_b^2) = albedo x pdf_b p_l / (p_l^2 + pdf_b^2)
             // (glossy: f cos x p_l / (p_l^2 + pdf_b^2), f cos per channel)
-            float wgt = (pl > 0.0f && pb > 0.0f && d2 > 0.0f) ? pb / (pl + pb * (pb / pl)) : 0.0f;
+            // An analytic light (shapes 6, 7, 8) is sampled by this strategy alone: weight 1, f cos / p_l
+            const bool delta = shape >= 6;
+            float wgt = (pl > 0.0f && pb > 0.0f && d2 > 0.0f) ? pb / (delta ? pl : pl + pb * (pb / pl)) : 0.0f;
             if (glossy) {
-                wgt = (pl > 0.0f && pb > 0.0f && d2 > 0.0f) ? 1.0f / (pl + pb * (pb / pl)) : 0.0f;
+                wgt = (pl > 0.0f && pb > 0.0f && d2 > 0.0f) ? 1.0f / (delta ? pl : pl + pb * (pb / pl)) : 0.0f;
                 vb_r *= gf_r, vb_g *= gf_g, vb_b *= gf_b;
             }
             if (wgt > 0.0f) {

@@ -3,6 +3,7 @@
 
 #include <array>
 #include <cctype>
+#include <cfloat>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -1055,6 +1056,66 @@ int scene_from_json(const char *text, size_t len, Scene &s, const char *base_dir
             }
         }
     }
+    // "lights": [{"type": "point" | "spot" | "distant", ...}]; without a "light_sampling" key they switch it on
+    s.alights.clear();
+    if (const JsonValue *arr = root.find("lights")) {
+        if (!arr->is_array()) r.fail("top level: \"lights\" must be an array");
+        for (size_t i = 0; r.ok && i < arr->arr.size(); ++i) {
+            const JsonValue &t = arr->arr[i];
+            snprintf(where, sizeof where, "light %zu", i);
+            const JsonValue *ty = t.find("type");
+            if (!t.is_object() || !ty || !ty->is_string()) {
+                r.fail("%s: missing string \"type\"", where);
+                break;
+            }
+            auto only_keys = [&](std::initializer_list<const char *> known) {  // (a field the type does not have is an error)
+                for (const auto &kv : t.obj) {
+                    bool found = false;
+                    for (const char *k : known) found = found || kv.first == k;
+                    if (!found && r.ok) r.fail("%s: a %s light has no field \"%s\"", where, ty->str.c_str(), kv.first.c_str());
+                }
+            };
+            rt_analytic_light l;
+            memset(&l, 0, sizeof l);
+            double v[3] = {0, 0, 0}, w[3] = {0, 0, 0};
+            if (ty->str == "point") {
+                only_keys({"type", "position", "intensity"});
+                l.type = RT_LIGHT_POINT;
+                r.vec3(t, "position", where, v);
+                for (int k = 0; k < 3; ++k) l.position[k] = (float)v[k];
+                r.vec3(t, "intensity", where, v);
+            } else if (ty->str == "spot") {
+                only_keys({"type", "position", "direction", "target", "intensity", "inner_angle", "outer_angle"});
+                l.type = RT_LIGHT_SPOT;
+                r.vec3(t, "position", where, v);
+                for (int k = 0; k < 3; ++k) l.position[k] = (float)v[k];
+                const bool has_dir = t.find("direction") != nullptr, has_target = t.find("target") != nullptr;
+                if (r.ok && has_dir == has_target) r.fail("%s: a spot light takes one of \"direction\" and \"target\"", where);
+                if (r.ok) {
+                    r.vec3(t, has_dir ? "direction" : "target", where, w);
+                    for (int k = 0; k < 3; ++k) l.direction[k] = (float)(has_dir ? w[k] : w[k] - v[k]);
+                }
+                l.angle[0] = (float)r.num(t, "inner_angle", where);
+                l.angle[1] = (float)r.num(t, "outer_angle", where);
+                r.vec3(t, "intensity", where, v);
+            } else if (ty->str == "distant") {
+                only_keys({"type", "direction", "irradiance", "angular_radius"});
+                l.type = RT_LIGHT_DISTANT;
+                r.vec3(t, "direction", where, w);
+                for (int k = 0; k < 3; ++k) l.direction[k] = (float)w[k];
+                if (t.find("angular_radius")) l.angle[0] = (float)r.num(t, "angular_radius", where);
+                r.vec3(t, "irradiance", where, v);
+            } else {
+                r.fail("%s: unknown type \"%s\" (point, spot, distant)", where, ty->str.c_str());
+                break;
+            }
+            for (int k = 0; k < 3; ++k) l.color[k] = (float)v[k];
+            if (!r.ok) break;
+            if (!analytic_light_ok(l, where)) return RT_ERR_SCENE;
+            s.alights.push_back(l);
+        }
+        if (r.ok && !root.find("light_sampling")) s.light_sampling = true;
+    }
 
     // camera, parser.hpp:113-141
     const JsonValue *cam = root.find("camera");
@@ -1480,6 +1541,33 @@ std::string scene_to_json(const Scene &s) {
     o += std::string("  \"defocus_blur\": ") + ((s.flags & RT_FLAG_DEFOCUS_BLUR) ? "true" : "false") + ",\n";
     if (s.rr_p > 0.0f) o += "  \"russian_roulette\": " + json_double((double)s.rr_p) + ",\n";
     if (s.light_sampling) o += "  \"light_sampling\": true,\n";
+    else if (!s.alights.empty()) o += "  \"light_sampling\": false,\n";  // ("lights" alone would switch it on)
+    if (!s.alights.empty()) {  // analytic lights, as given
+        o += "  \"lights\": [";
+        for (size_t i = 0; i < s.alights.size(); ++i) {
+            const rt_analytic_light &l = s.alights[i];
+            o += i ? ",\n    " : "\n    ";
+            if (l.type == RT_LIGHT_DISTANT) {
+                o += "{\"type\": \"distant\", \"direction\": ";
+                put_vec3(o, l.direction);
+                o += ", \"irradiance\": ";
+                put_vec3(o, l.color);
+                o += ", \"angular_radius\": " + json_float(l.angle[0]) + "}";
+                continue;
+            }
+            o += l.type == RT_LIGHT_SPOT ? "{\"type\": \"spot\", \"position\": " : "{\"type\": \"point\", \"position\": ";
+            put_vec3(o, l.position);
+            if (l.type == RT_LIGHT_SPOT) {
+                o += ", \"direction\": ";
+                put_vec3(o, l.direction);
+                o += ", \"inner_angle\": " + json_float(l.angle[0]) + ", \"outer_angle\": " + json_float(l.angle[1]);
+            }
+            o += ", \"intensity\": ";
+            put_vec3(o, l.color);
+            o += "}";
+        }
+        o += "\n  ],\n";
+    }
     if (s.mesh_lights) o += "  \"mesh_lights\": true,\n";
     if (s.nested_grid) o += "  \"nested_grid\": true,\n";
     if (s.env) {
@@ -1855,6 +1943,20 @@ std::vector<SceneLight> scene_lights(const Scene &s) {
         l.prob = power;
         out.push_back(l);
     }
+    // analytic lights, behind the area emitters: measure x luminance / pi in the same units -- 4 lum(I), 2 (1 - (cos_i
+    // + cos_o) / 2) lum(I), r^2 lum(E)
+    if (!s.alights.empty()) {
+        const double r = scene_bound_radius(s);
+        for (size_t i = 0; i < s.alights.size(); ++i) {
+            const AnalyticRecord a = analytic_record(s.alights[i], r);
+            if (!(a.weight > 0.0) || !std::isfinite(a.weight)) continue;
+            SceneLight l;
+            l.prim = -1, l.type = s.alights[i].type, l.analytic = (int)i;
+            l.area = a.measure, l.prob = a.weight;
+            for (int c = 0; c < 3; ++c) l.even[c] = l.odd[c] = a.color[c];
+            out.push_back(l);
+        }
+    }
     // the environment, last: r^2 x scale x sum of luminance x solid angle, r the radius of the primitives' bounding sphere --
     // the flux through that sphere's cross-section up to pi, as area x luminance is an area emitter's up to pi
     if (s.env && s.env->flux > 0.0 && s.env_scale > 0.0f) {
@@ -2149,6 +2251,85 @@ int add_moving_sphere(Scene &s, const rt_moving_sphere &m) {
     s.movers.push_back(m);
     s.touch();
     return (int)s.movers.size() - 1;
+}
+
+// ---------------------------------------------------------------- analytic lights
+bool analytic_light_ok(const rt_analytic_light &l, const char *where) {
+    if (l.type != RT_LIGHT_POINT && l.type != RT_LIGHT_SPOT && l.type != RT_LIGHT_DISTANT) {
+        set_error("%s: unknown light type %d", where, l.type);
+        return false;
+    }
+    const char *colour = l.type == RT_LIGHT_DISTANT ? "irradiance" : "intensity";
+    bool any = false;
+    for (int c = 0; c < 3; ++c) {
+        if (!(std::isfinite(l.color[c]) && l.color[c] >= 0.0f)) {
+            set_error("%s: %s component %d (%g) must be finite and >= 0", where, colour, c, (double)l.color[c]);
+            return false;
+        }
+        any = any || l.color[c] > 0.0f;
+    }
+    if (!any) {
+        set_error("%s: the %s is all zero", where, colour);
+        return false;
+    }
+    if (l.type != RT_LIGHT_DISTANT)
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(l.position[k])) {
+                set_error("%s: the position is not finite", where);
+                return false;
+            }
+    if (l.type != RT_LIGHT_POINT) {
+        double n2 = 0.0;
+        for (int k = 0; k < 3; ++k) n2 += (double)l.direction[k] * (double)l.direction[k];
+        if (!(std::isfinite(n2) && n2 > 0.0)) {
+            set_error("%s: the direction must be finite and non-zero", where);
+            return false;
+        }
+    }
+    if (l.type == RT_LIGHT_SPOT && !(l.angle[0] >= 0.0f && l.angle[0] <= l.angle[1] && l.angle[1] > 0.0f && l.angle[1] <= 179.0f)) {
+        set_error("%s: the angles (inner %g, outer %g) must satisfy 0 <= inner <= outer, 0 < outer <= 179 degrees", where,
+                  (double)l.angle[0], (double)l.angle[1]);
+        return false;
+    }
+    if (l.type == RT_LIGHT_DISTANT && !(l.angle[0] >= 0.0f && l.angle[0] <= 45.0f)) {
+        set_error("%s: the angular radius (%g) must lie in [0, 45] degrees", where, (double)l.angle[0]);
+        return false;
+    }
+    return true;
+}
+
+AnalyticRecord analytic_record(const rt_analytic_light &l, double bound_radius) {
+    AnalyticRecord a;
+    const double pi = std::acos(-1.0), rad = pi / 180.0;
+    const double lum = 0.2126 * (double)l.color[0] + 0.7152 * (double)l.color[1] + 0.0722 * (double)l.color[2];
+    double fold = 1.0;
+    if (l.type != RT_LIGHT_POINT) {
+        double n2 = 0.0;
+        for (int k = 0; k < 3; ++k) n2 += (double)l.direction[k] * (double)l.direction[k];
+        const double inv_len = (l.type == RT_LIGHT_DISTANT ? -1.0 : 1.0) / std::sqrt(n2);  // (the record: TOWARDS a distant light)
+        for (int k = 0; k < 3; ++k) a.dir[k] = (double)l.direction[k] * inv_len + 0.0;  // (+ 0.0: no negative zero in the record)
+    }
+    if (l.type == RT_LIGHT_POINT) {
+        a.measure = 4.0 * pi;
+    } else if (l.type == RT_LIGHT_SPOT) {
+        const double ci = std::cos((double)l.angle[0] * rad), co = std::cos((double)l.angle[1] * rad);
+        a.cos_o = (float)co;
+        a.inv = (float)std::min(1.0 / (ci - co), (double)FLT_MAX);
+        a.measure = 2.0 * pi * (1.0 - 0.5 * (ci + co));
+    } else {
+        const double ca = std::cos((double)l.angle[0] * rad);
+        a.omc = (float)(1.0 - ca);
+        a.dist = (float)(4.0 * bound_radius);
+        fold = 2.0 / (1.0 + ca);
+        a.measure = pi * bound_radius * bound_radius;
+    }
+    for (int c = 0; c < 3; ++c) a.color[c] = (float)((double)l.color[c] * fold);
+    a.weight = a.measure * lum / pi;
+    // (what the record's fp32 words cannot hold is left out, as a sliver triangle is)
+    if (!std::isfinite(a.color[0]) || !std::isfinite(a.color[1]) || !std::isfinite(a.color[2]) || !((float)a.measure > 0.0f) ||
+        !std::isfinite((float)(1.0 / a.measure)) || !std::isfinite(a.dist))
+        a.weight = 0.0;
+    return a;
 }
 
 }  // namespace rtmi

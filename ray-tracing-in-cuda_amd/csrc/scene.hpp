@@ -77,6 +77,7 @@ struct Scene {
     float env_scale = 1.0f, env_rotate = 0.0f;    // radiance = scale x texel; degrees about +y
     std::vector<rt_medium> media;  // homogeneous participating media, a list of its own: at most RT_MAX_MEDIA
     std::vector<rt_moving_sphere> movers;  // moving spheres, a list of its own: at most RT_MAX_MOVING_SPHERES
+    std::vector<rt_analytic_light> alights;  // point, spot and distant lights, a list of its own, as given
     uint64_t version = 1;  // bumped on every mutation; invalidates device caches
     std::shared_ptr<DeviceSceneCache> dev;
 
@@ -91,8 +92,23 @@ struct SceneLight {
     double area = 0.0, prob = 0.0;
     float even[3] = {0, 0, 0}, odd[3] = {0, 0, 0};
     bool checker = false;
+    int analytic = -1;  // an analytic light: its index in Scene::alights; prim = -1, type = RT_LIGHT_POINT / SPOT / DISTANT
 };
 std::vector<SceneLight> scene_lights(const Scene &s);
+
+// analytic lights.  What the light record and the selection weight hold, derived in fp64 from the fp32 record:
+// `dir` the unit axis of a spot / the unit direction TOWARDS a distant light; `color` rounded once (a distant light's with the
+// fold 2 / (1 + cos alpha)); `measure` x lum(color as given) / pi is the selection weight
+struct AnalyticRecord {
+    double dir[3] = {0, 0, 0};
+    float color[3] = {0, 0, 0};
+    float cos_o = 0.0f, inv = 0.0f;  // spot: cos(outer), min(1 / (cos_i - cos_o), FLT_MAX)
+    float omc = 0.0f, dist = 0.0f;   // distant: 1 - cos alpha, D = 4 r
+    double measure = 0.0, weight = 0.0;
+};
+AnalyticRecord analytic_record(const rt_analytic_light &l, double bound_radius);
+// is the record within the argument rules (false: the message is set, prefixed with `where`)
+bool analytic_light_ok(const rt_analytic_light &l, const char *where);
 
 // derive the camera frame (camera.cuh:9-29) in fp64, round once to fp32
 void derive_camera(const Scene &s, rt_camera *out);
