@@ -839,6 +839,18 @@ class Scene:
                                            spp.ctypes.data_as(C.c_void_p), C.byref(st)), "rt_render_hip_adaptive")
         return out, spp, st
 
+    def render_adaptive_device(self, threshold: float, d_rgb_sum: int, d_spp_map: int, min_spp: int = 16, max_spp: int = 0,
+                               stream: int = 0, opts: Opts | None = None) -> AdaptiveStats:
+        """The same into DEVICE buffers (rt_render_hip_adaptive_device): d_rgb_sum H x W x 3 float32, d_spp_map H x W int32
+        (e.g. torch tensors' data_ptr()), on `stream` (a hipStream_t as an integer).  Returns when the frame is done: the
+        schedule reads the active tile count back once per pass."""
+        opts = opts or Opts()
+        a = Adaptive(min_spp=int(min_spp), max_spp=int(max_spp), threshold=float(threshold))
+        st = AdaptiveStats()
+        _check(_lib.rt_render_hip_adaptive_device(self._h, C.byref(opts), C.byref(a), C.c_void_p(d_rgb_sum), C.c_void_p(d_spp_map),
+                                                  C.c_void_p(stream), C.byref(st)), "rt_render_hip_adaptive_device")
+        return st
+
     def render_feature(self, feature: int, opts: Opts | None = None, stats: Stats | None = None) -> np.ndarray:
         """One first-hit feature pass (rt_render_hip_feature): FEATURE_ALBEDO, FEATURE_NORMAL or FEATURE_DEPTH (t, coverage,
         0).  (local_rows, W, 3) fp32 SUMS over the samples of `opts` (sample_count 0: the scene's spp), rows as render()."""
@@ -849,6 +861,13 @@ class Scene:
         _check(_lib.rt_render_hip_feature(self._h, C.byref(opts), int(feature), out.ctypes.data_as(C.c_void_p), C.byref(st)),
                "rt_render_hip_feature")
         return out
+
+    def render_feature_device(self, feature: int, d_sum: int, stream: int = 0, opts: Opts | None = None, stats: Stats | None = None):
+        """The same into a DEVICE buffer (rt_render_hip_feature_device): d_sum shard_rows(opts) x W x 3 float32, on `stream`
+        (a hipStream_t as an integer).  Asynchronous when stats is None."""
+        opts = opts or Opts()
+        _check(_lib.rt_render_hip_feature_device(self._h, C.byref(opts), int(feature), C.c_void_p(d_sum), C.c_void_p(stream),
+                                                 C.byref(stats) if stats is not None else None), "rt_render_hip_feature_device")
 
     # ---- ray queries (HIP only) ---------------------------------------------------
     def trace(self, origins, directions, t_max=float("inf"), occluded: bool = False, opts: Opts | None = None,
@@ -994,6 +1013,19 @@ def denoise(rgb_sum, spp, albedo_sum, normal_sum, depth_sum, feature_spp, *, spp
     if timing is not None:
         timing.append(ms.value)
     return out
+
+
+def denoise_device(width, height, d_rgb_sum, spp, d_albedo_sum, d_normal_sum, d_depth_sum, feature_spp, d_out_rgb_sum, stream=0, *,
+                   d_spp_map=None, params=None, device=0, timing=None):
+    """rt_denoise_hip_device: the filter on DEVICE buffers (addresses as integers; H x W x 3 float32 each, d_spp_map H x W int32
+    or None), enqueued on `stream` (a hipStream_t as an integer); params: a Denoise or None (all defaults).  timing: a list that
+    receives the kernels' ms -- the call then waits for them; None: asynchronous."""
+    ms = C.c_double(0.0) if timing is not None else None
+    _check(_lib.rt_denoise_hip_device(int(width), int(height), d_rgb_sum, int(spp), d_spp_map, d_albedo_sum, d_normal_sum, d_depth_sum,
+                                      int(feature_spp), C.byref(params) if params is not None else None, int(device), d_out_rgb_sum,
+                                      stream or None, C.byref(ms) if ms is not None else None), "rt_denoise_hip_device")
+    if timing is not None:
+        timing.append(ms.value)
 
 
 def display(rgb_sum, spp, *, spp_map=None, tonemap=None, exposure=0.0, auto_key=0.0, white=0.0, bloom_strength=0.0,

@@ -107,6 +107,21 @@ def test_python_wrapper_raises(rtmi, scene):
     assert e.value.status == RT_ERR_ARG
 
 
+def test_device_wrapper_refuses_null_pointers(rtmi, scene):
+    """Scene.render_adaptive_device: RT_ERR_ARG for a null pointer or a bad schedule, before any device is touched (the other
+    pointer dangles)."""
+    for rgb, spp in ((0, 16), (16, 0), (None, 16), (16, None), (0, 0)):
+        with pytest.raises(rtmi.RtmiError) as e:
+            scene.render_adaptive_device(0.1, rgb, spp, min_spp=4, max_spp=16)
+        assert e.value.status == RT_ERR_ARG, (rgb, spp)
+    with pytest.raises(rtmi.RtmiError) as e:
+        scene.render_adaptive_device(-1.0, 16, 16, stream=0)
+    assert e.value.status == RT_ERR_ARG
+    with pytest.raises(rtmi.RtmiError) as e:
+        scene.render_adaptive_device(0.1, 16, 16, min_spp=4, opts=rtmi.Opts(tile_stride=2))
+    assert e.value.status == RT_ERR_ARG
+
+
 @pytest.mark.parametrize("extra", [
     ["--gpus", "2"],
     ["--acc-out", "sums.bin"],
