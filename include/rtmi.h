@@ -73,8 +73,11 @@ typedef enum rt_mat_type {
     /* glossy materials: a GGX microfacet lobe.  They reuse the record's fields:                      */
     RT_MAT_ROUGH_METAL = 4,   /* albedo = F0, fuzz = roughness in [0, 1]                                       */
     RT_MAT_PLASTIC = 5,       /* texture = body colour, fuzz = roughness in [0, 1], ir = the coat's index (> 1) */
-    RT_MAT_ROUGH_GLASS = 6    /*  ir = the index (> 1), fuzz = roughness in [0, 1], albedo = the absorption
+    RT_MAT_ROUGH_GLASS = 6,   /*  ir = the index (> 1), fuzz = roughness in [0, 1], albedo = the absorption
                                  coefficient sigma per unit world length (each >= 0), texture = -1              */
+    RT_MAT_PBR = 7            /*  metallic-roughness: texture = base colour, albedo[0] = the metallic factor,
+                                 fuzz = the roughness factor (both in [0, 1]), ir = the coat's index (> 1), albedo[1..2] = 0;
+                                 its map: rt_scene_set_pbr_map                                                   */
 } rt_mat_type;
 
 typedef enum rt_tex_type {
@@ -436,6 +439,27 @@ int rt_scene_add_plastic(rt_scene *s, int texture, float ior, float roughness);
  * F(wo.h_l) G1(wo) D(h_l) / (4 wo.z); zero for wl.z <= 0 (no light sample through the surface).  The feature passes report
  * albedo 1 and the shading normal.  A scene with one runs the general (triangle / texture) kernels.  -> material id or -rt_status */
 int rt_scene_add_rough_glass(rt_scene *s, float ir, float roughness, const float absorption[3]);
+/* The metallic-roughness material (the model: csrc/rt_pbr.h), glTF 2.0's: a base colour texture of any type, a
+ * metallic factor mf and a roughness factor rf, finite and in [0, 1], a coat index ior, finite and > 1, and optionally one
+ * metallic-roughness map, a texture of any type whose G channel scales the roughness and whose B channel scales the metalness
+ * (an ORM image drops in unchanged).  The base texture must exist; the map must be an existing texture or -1 (none), on a pbr
+ * material only; anything else is RT_ERR_ARG.
+ * Per-hit parameters are 8-bit by definition: with the base colour c, the map's channels G, B at the hit (1 without a map),
+ *   byte(x) = (uint)fma(clamp(x, 0, 1), 255, 0.5) in fp32:  c8 = byte(c) per channel, r8 = byte(rf G), m8 = byte(mf B),
+ *   and the values are c8 / 255, r = r8 / 255, m = m8 / 255 (one fp32 division each): an image's texel is used exactly, solid,
+ *   checker and noise sources are rounded to that grid.
+ * A vertex seen from above its shading normal takes three draws ul, u1, u2, in plastic's order, whatever its metalness:
+ *   ul < m:  the vertex is a rough_metal with F0 = c8 / 255 and roughness r (ul is otherwise unused);
+ *   else:    a plastic with body c8 / 255, the coat's r0 from ior, roughness r, and lobe draw ul' = (ul - m) / (1 - m);
+ *   alpha = max(r r, 1e-3) in fp32.  Everything after that is the chosen material's rule, for the scatter step and -- iff
+ *   r >= 0.05 and the vertex is not below the surface -- for the light sample: both see the same, already chosen, BSDF.  The
+ *   expectation over the choice is m metal(c) + (1 - m) dielectric(c).
+ * The albedo feature pass reports c8 / 255; a bump applies as on the other glossy materials.  A scene with one runs the general
+ * (triangle / texture) kernels.  The map lives beside the material table, as the bumps do: rt_material is unchanged.
+ * rt_scene_add_pbr -> material id or -rt_status; the other two -> rt_status (get: *texture = the map's texture id, -1: none) */
+int rt_scene_add_pbr(rt_scene *s, int base_texture, float metallic, float roughness, float ior);
+int rt_scene_set_pbr_map(rt_scene *s, int material, int texture);
+int rt_scene_get_pbr_map(const rt_scene *s, int material, int *texture);
 int rt_scene_add_diffuse_light(rt_scene *s, int texture);
 int rt_scene_add_sphere(rt_scene *s, const float center[3], float radius, int material); /* -> prim id */
 /* axis: 0 = xy_rect (a=x,b=y,k=z), 1 = xz_rect, 2 = yz_rect */
@@ -475,7 +499,7 @@ int rt_scene_get_noise(const rt_scene *s, int texture, rt_noise *out);
  * hit, -1 on a back hit (height is measured along the OUTWARD normal): G = grad s(p) (analytic), Gt = G - (G . n) n,
  * b = n - sigma strength Gt, n' = b / |b|; n' replaces n where it is finite, n' . g > 0 and n' . d < 0.  Only the height is
  * used, not the texture's colours.  The hit point, front, t, (u, v), emitter hits and the ray queries stay geometric.  On
- * lambertian, metal, dielectric, rough_metal, plastic and rough_glass; RT_ERR_ARG for an unknown material, a diffuse_light, a texture that
+ * lambertian, metal, dielectric, rough_metal, plastic, rough_glass and pbr; RT_ERR_ARG for an unknown material, a diffuse_light, a texture that
  * is not an RT_TEX_NOISE or a strength that is not finite.  texture = -1 or strength = 0 removes the bump.  A scene with one
  * runs the general (triangle / texture) kernels; a moving sphere whose material carries one is refused when rendered.
  * The bumps live beside the material table: rt_material is unchanged. */
@@ -562,7 +586,10 @@ int rt_scene_get_textures(const rt_scene *s, rt_texture *out, int cap);   /* -> 
  * axis << 2 | octaves << 4}; a material with such a texture holds the record's offset in the fourth word of its second
  * record.  No field here says where they begin: a scene without a noise texture has none and packs to the bytes it did.
  * The bumps, DESIGN 7p, follow them the same way: one record per bumped material, {offset of the height texture's noise
- * record, strength, 0, 0}, whose offset the material holds in the fourth word of its third record; none without a bump.) */
+ * record, strength, 0, 0}, whose offset the material holds in the fourth word of its third record; none without a bump.
+ * The pbr materials' side records, DESIGN 7t, follow those: three records per pbr material, in material order -- {metallic
+ * factor, roughness factor, 0, 0}, then the map's texture as a material's second and third record hold theirs (no map: solid
+ * white) -- whose offset the material holds in the second word of its first record; none without a pbr material.) */
 typedef struct rt_table_info {
     int32_t image_floats;      /* size of the image (rt_scene_table_image) */
     int32_t grid_wide;         /* 1: wide tables (32-bit entries, two words per cell: every primitive type listed); 0: compact

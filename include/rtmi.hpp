@@ -86,6 +86,7 @@ struct material {
     float fuzz = 0, ir = 1;
     std::shared_ptr<mytexture> bump;  // bump mapping: a noise texture as the height field, null: none
     float bump_strength = 0;
+    std::shared_ptr<mytexture> map;  // pbr: the metallic-roughness map (G scales the roughness, B the metalness), null: none
 };
 using material_ptr = std::shared_ptr<material>;
 inline material_ptr lambertian(std::shared_ptr<mytexture> a) {  // material.cuh:34-35
@@ -116,6 +117,19 @@ inline material_ptr rough_glass(float ir = 1.5f, float roughness = 0.3f, color a
     auto m = std::make_shared<material>();
     m->type = RT_MAT_ROUGH_GLASS, m->ir = ir, m->fuzz = roughness, m->albedo = absorption;
     return m;
+}
+// the metallic-roughness material: tex the base colour, albedo[0] the metallic factor, fuzz the roughness factor,
+// ir the coat's index, map (optional) the metallic-roughness map
+inline material_ptr pbr(std::shared_ptr<mytexture> base, float metallic = 0.0f, float roughness = 0.5f, float ior = 1.5f,
+                        std::shared_ptr<mytexture> metallic_roughness = nullptr) {
+    auto m = std::make_shared<material>();
+    m->type = RT_MAT_PBR, m->tex = std::move(base), m->albedo = color(metallic, 0, 0), m->fuzz = roughness, m->ir = ior;
+    m->map = std::move(metallic_roughness);
+    return m;
+}
+inline material_ptr pbr(color base, float metallic = 0.0f, float roughness = 0.5f, float ior = 1.5f,
+                        std::shared_ptr<mytexture> metallic_roughness = nullptr) {
+    return pbr(solid_color(base), metallic, roughness, ior, std::move(metallic_roughness));
 }
 inline material_ptr dielectric(float index_of_refraction) {  // material.cuh:91-92
     auto m = std::make_shared<material>();
@@ -504,6 +518,24 @@ public:
                              out_rgb ? out_rgb->data() : nullptr, out8.data(), stats), "display");
         return out8;
     }
+    // the metallic-roughness material: pbr() registers one and returns its descriptor; set_pbr_map() gives a
+    // registered one another map (null: none); pbr_map() is the texture id of its map, or -1
+    material_ptr pbr(std::shared_ptr<mytexture> base, float metallic = 0.0f, float roughness = 0.5f, float ior = 1.5f,
+                     std::shared_ptr<mytexture> metallic_roughness = nullptr) {
+        material_ptr m = rtmi::pbr(std::move(base), metallic, roughness, ior, std::move(metallic_roughness));
+        material_id(m);
+        return m;
+    }
+    void set_pbr_map(const material_ptr &m, std::shared_ptr<mytexture> metallic_roughness) {
+        const int id = material_id(m);
+        check(rt_scene_set_pbr_map(s_, id, metallic_roughness ? texture_id(metallic_roughness) : -1), "set_pbr_map");
+        m->map = std::move(metallic_roughness);
+    }
+    int pbr_map(const material_ptr &m) {
+        int t = -1;
+        check(rt_scene_get_pbr_map(s_, material_id(m), &t), "pbr_map");
+        return t;
+    }
     rt_scene *handle() const { return s_; }
 
 private:
@@ -536,10 +568,12 @@ private:
         case RT_MAT_ROUGH_METAL: id = rt_scene_add_rough_metal(s_, m->albedo.e, m->fuzz); break;
         case RT_MAT_PLASTIC: id = rt_scene_add_plastic(s_, texture_id(m->tex), m->ir, m->fuzz); break;
         case RT_MAT_ROUGH_GLASS: id = rt_scene_add_rough_glass(s_, m->ir, m->fuzz, m->albedo.e); break;
+        case RT_MAT_PBR: id = rt_scene_add_pbr(s_, texture_id(m->tex), m->albedo.e[0], m->fuzz, m->ir); break;
         default: id = rt_scene_add_diffuse_light(s_, texture_id(m->tex)); break;
         }
         if (id < 0) throw error(-id, "material");
         if (m->bump) check(rt_scene_set_bump(s_, id, texture_id(m->bump), m->bump_strength), "bump");
+        if (m->type == RT_MAT_PBR && m->map) check(rt_scene_set_pbr_map(s_, id, texture_id(m->map)), "pbr map");
         mats_.emplace_back(m, id);
         return id;
     }

@@ -240,6 +240,9 @@ _sig("rt_scene_add_dielectric", C.c_int, _p, C.c_float)
 _sig("rt_scene_add_rough_metal", C.c_int, _p, _f3, C.c_float)
 _sig("rt_scene_add_plastic", C.c_int, _p, C.c_int, C.c_float, C.c_float)
 _sig("rt_scene_add_rough_glass", C.c_int, _p, C.c_float, C.c_float, _f3)
+_sig("rt_scene_add_pbr", C.c_int, _p, C.c_int, C.c_float, C.c_float, C.c_float)
+_sig("rt_scene_set_pbr_map", C.c_int, _p, C.c_int, C.c_int)
+_sig("rt_scene_get_pbr_map", C.c_int, _p, C.c_int, C.POINTER(C.c_int))
 _sig("rt_scene_add_diffuse_light", C.c_int, _p, C.c_int)
 _sig("rt_scene_add_sphere", C.c_int, _p, _f3, C.c_float, C.c_int)
 _sig("rt_scene_add_rect", C.c_int, _p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int)
@@ -359,7 +362,7 @@ C_SYMBOLS = [
     "rt_scene_new", "rt_scene_set_background", "rt_scene_set_camera", "rt_scene_add_solid_color",
     "rt_scene_add_checker", "rt_scene_add_lambertian", "rt_scene_add_metal", "rt_scene_add_dielectric",
     "rt_scene_add_rough_metal", "rt_scene_add_plastic", "rt_scene_add_rough_glass", "rt_scene_add_noise_texture", "rt_scene_get_noise",
-    "rt_scene_set_bump", "rt_scene_get_bump",
+    "rt_scene_set_bump", "rt_scene_get_bump", "rt_scene_add_pbr", "rt_scene_set_pbr_map", "rt_scene_get_pbr_map",
     "rt_scene_add_diffuse_light", "rt_scene_add_sphere", "rt_scene_add_rect", "rt_scene_add_cylinder",
     "rt_scene_add_image_texture", "rt_scene_add_image_texture_file", "rt_scene_get_image", "rt_scene_add_triangle",
     "rt_scene_add_quad", "rt_scene_add_box", "rt_scene_add_obj", "rt_scene_add_triangle_normals", "rt_scene_add_obj_normals", "rt_set_mesh_normals_override",
@@ -695,6 +698,28 @@ class Scene:
         materials() shows it as type 6 with fuzz = roughness and albedo = absorption."""
         sigma = None if absorption is None else _v3(absorption)
         return _check_id(_lib.rt_scene_add_rough_glass(self._h, ir, roughness, sigma), "rough_glass")
+
+    def pbr(self, texture_or_color, metallic=0.0, roughness=0.5, ior=1.5, metallic_roughness=None) -> int:
+        """The metallic-roughness material: a base colour (a texture id of any type, or a colour), a metallic and a
+        roughness factor in [0, 1], the coat's index ior > 1, and optionally a metallic-roughness map -- a texture id of any type
+        whose G channel scales the roughness and whose B channel scales the metalness (glTF 2.0's convention).  Every vertex is a
+        rough_metal (F0 = base colour) with probability metalness, else a plastic.  materials() shows it as type 7 with
+        fuzz = roughness factor and albedo[0] = metallic factor."""
+        tex = texture_or_color if isinstance(texture_or_color, int) else self.solid_color(texture_or_color)
+        m = _check_id(_lib.rt_scene_add_pbr(self._h, tex, metallic, roughness, ior), "pbr")
+        if metallic_roughness is not None:
+            self.set_pbr_map(m, metallic_roughness)
+        return m
+
+    def set_pbr_map(self, material: int, texture: int) -> None:
+        """The metallic-roughness map of a pbr material: any texture id; -1 removes it."""
+        _check(_lib.rt_scene_set_pbr_map(self._h, int(material), int(texture)), "rt_scene_set_pbr_map")
+
+    def pbr_map(self, material: int):
+        """The texture id of a pbr material's metallic-roughness map, or None."""
+        t = C.c_int()
+        _check(_lib.rt_scene_get_pbr_map(self._h, int(material), C.byref(t)), "rt_scene_get_pbr_map")
+        return None if t.value < 0 else int(t.value)
 
     def dielectric(self, index_of_refraction) -> int:
         return _check_id(_lib.rt_scene_add_dielectric(self._h, index_of_refraction), "dielectric")

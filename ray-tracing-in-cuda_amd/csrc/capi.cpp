@@ -352,6 +352,27 @@ int rt_scene_add_rough_glass(rt_scene *s, float ir, float roughness, const float
     if (absorption) memcpy(m.albedo, absorption, sizeof m.albedo);
     return add_glossy(s, m, "rt_scene_add_rough_glass");
 }
+// the metallic-roughness material: texture the base colour, albedo[0] the metallic factor, fuzz the roughness
+// factor, ir the coat's index; its map lives beside the material table, as the bumps do
+int rt_scene_add_pbr(rt_scene *s, int base_texture, float metallic, float roughness, float ior) {
+    rt_material m;
+    memset(&m, 0, sizeof m);
+    m.type = RT_MAT_PBR, m.texture = base_texture, m.albedo[0] = metallic, m.fuzz = roughness, m.ir = ior;
+    return add_glossy(s, m, "rt_scene_add_pbr");
+}
+int rt_scene_set_pbr_map(rt_scene *s, int material, int texture) {
+    if (bad_scene(s, "rt_scene_set_pbr_map")) return RT_ERR_ARG;
+    return set_pbr_map(s->s, material, texture, "rt_scene_set_pbr_map") ? RT_OK : RT_ERR_ARG;
+}
+int rt_scene_get_pbr_map(const rt_scene *s, int material, int *texture) {
+    if (bad_scene(s, "rt_scene_get_pbr_map")) return RT_ERR_ARG;
+    if (material < 0 || material >= (int)s->s.mats.size() || s->s.mats[(size_t)material].type != RT_MAT_PBR) {
+        set_error("rt_scene_get_pbr_map: material %d is not a pbr material (have %zu materials)", material, s->s.mats.size());
+        return RT_ERR_ARG;
+    }
+    if (texture) *texture = scene_pbr_map(s->s, material);
+    return RT_OK;
+}
 int rt_scene_add_dielectric(rt_scene *s, float ir) { return add_material(s, RT_MAT_DIELECTRIC, -1, nullptr, 0, ir); }
 int rt_scene_add_diffuse_light(rt_scene *s, int texture) {
     return add_material(s, RT_MAT_DIFFUSE_LIGHT, texture, nullptr, 0, 0);
@@ -602,7 +623,7 @@ rt_scene *rt_scene_dna(const rt_scene *base, double angle) {
     if (base) {
         sc = base->s;
         sc.dev.reset();
-        sc.prims.clear(), sc.xforms.clear(), sc.mats.clear(), sc.texs.clear(), sc.noise.clear(), sc.bumps.clear();
+        sc.prims.clear(), sc.xforms.clear(), sc.mats.clear(), sc.texs.clear(), sc.noise.clear(), sc.bumps.clear(), sc.pbr_maps.clear();
     } else {  // gpu-version/basic_scene.json
         sc.width = 1600, sc.height = 900, sc.spp = 100, sc.max_depth = 50;
         sc.background[0] = 0.0005f, sc.background[1] = 0.0007f, sc.background[2] = 0.00099f;

@@ -120,7 +120,13 @@ enum MatKind : int32_t {
     // rough glass (rt_glass.h), the third glossy material: {kind, alpha, 1/ir, r}{sigma.rgb, ir}{., ., ., bump} --
     // p0 and p2 as the other two, p1 = 1/ir (eta of a front hit), c0 = the absorption coefficient per unit length,
     // p3 (c0.w) = ir (eta of a back hit).  In a glossy vertex's packed word a back hit rides as kind 17 (bit 0 set)
-    MK_ROUGH_GLASS = 16
+    MK_ROUGH_GLASS = 16,
+    // the metallic-roughness material (rt_pbr.h): {kind, offset of its side record (bits), r0 of the coat,
+    // base type | map type << 4 (bits; 0 solid, 1 checker, 2 image, 3 noise)}, then c0 / c1 of the BASE texture as the
+    // textured kinds above keep them (c0.w: a noise base's record), c1.w the bump.  The side record is three rows shaped as a
+    // material's: {metallic factor, roughness factor, 0, 0}, then c0 / c1 of the MAP (none: solid white).  The winner section
+    // resolves both textures to bytes; in a glossy vertex's packed word the vertex rides as the lobe it chose: 18 plastic, 19 metal
+    MK_PBR = 18
 };
 
 // Per-launch values the kernel needs only when a wave fetches or flushes a work item.  They live in global

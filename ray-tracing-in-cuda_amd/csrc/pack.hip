@@ -684,8 +684,9 @@ int lay_out_hot(RenderParams &L, const Grid &g) {
 // (rt_motion.h; 0: no moving spheres); off_normals: of the NORMALS part (device_scene.h; 0: no triangle has vertex normals).  -1: the environment's words would not fit an int32 offset; -2: 2^28 sphere slots or more.
 // off_noise: the first record of the noise textures' parameters (device_scene.h; 0: the scene has no noise texture).
 // off_bump: the first bump record (device_scene.h; 0: no material carries a bump).
+// off_pbr: the first side record of the pbr materials (device_scene.h, MK_PBR; 0: the scene has none).
 int lay_out_image(RenderParams &L, const Grid &g, const Scene &s, std::vector<int> &image_word, int &off_media, int &off_motion,
-                  int &off_normals, int &off_noise, int &off_bump) {
+                  int &off_normals, int &off_noise, int &off_bump, int &off_pbr) {
     // The kernels read the winner's cold record at a 32-bit BYTE offset from the cold table, 16 x its slot (rec_at,
     // render_device.h): the slots end below 2^28.  This is the check that bound rests on; pack_scene refuses with RT_ERR_LIMIT.
     if ((long long)L.ns >= RT_MAX_SPHERE_SLOTS) return -2;
@@ -735,6 +736,13 @@ int lay_out_image(RenderParams &L, const Grid &g, const Scene &s, std::vector<in
         if (b.texture >= 0) {
             if (!off_bump) off_bump = off;
             ++off;
+        }
+    // the pbr materials' side records: three rows each, in material order, behind the bump records; none: not a byte
+    off_pbr = 0;
+    for (const rt_material &m : s.mats)
+        if (m.type == RT_MAT_PBR) {
+            if (!off_pbr) off_pbr = off;
+            off += 3;
         }
     // the LIGHT part (device_scene.h): light records, alias table, light slot of every grouped primitive id
     if (L.nl > 0) {
@@ -1041,12 +1049,31 @@ void write_bumps(float *I, const Scene &s, int off_bump, const std::vector<int> 
 }
 
 void write_materials(float *I, const RenderParams &L, const Scene &s, const SphereSlots &S, const OtherPrims &O,
-                     const std::vector<int> &image_word, const std::vector<int> &noise_rec, const std::vector<int> &bump_rec) {
+                     const std::vector<int> &image_word, const std::vector<int> &noise_rec, const std::vector<int> &bump_rec, int off_pbr) {
     // a noise texture under a material: the two colours where a checker keeps them, the record's offset in c0.w
     auto noise_words = [&](float *q, const rt_material &m, const rt_texture &t) {
         q[4] = t.c0[0], q[5] = t.c0[1], q[6] = t.c0[2], q[7] = bits(noise_rec[(size_t)m.texture]);
         q[8] = t.c1[0], q[9] = t.c1[1], q[10] = t.c1[2];
     };
+    // a pbr material's texture of any type into rows 1 and 2 of q, as the textured kinds keep theirs -> its type code
+    // (0 solid, 1 checker, 2 image, 3 noise); texture -1 (no map): solid white
+    auto pbr_texture = [&](float *q, int texture) {
+        if (texture < 0) {
+            q[4] = q[5] = q[6] = 1.0f;
+            return 0;
+        }
+        const rt_texture &t = s.texs[(size_t)texture];
+        if (t.type == RT_TEX_IMAGE) {
+            const size_t im = (size_t)t.c0[0];
+            q[4] = bits(image_word[im]), q[5] = bits(s.images[im].rows), q[6] = bits(s.images[im].cols);
+            return 2;
+        }
+        q[4] = t.c0[0], q[5] = t.c0[1], q[6] = t.c0[2];
+        q[8] = t.c1[0], q[9] = t.c1[1], q[10] = t.c1[2];
+        if (t.type == RT_TEX_NOISE) q[7] = bits(noise_rec[(size_t)texture]);
+        return t.type == RT_TEX_NOISE ? 3 : (t.type == RT_TEX_CHECKER ? 1 : 0);
+    };
+    int pbr_at = off_pbr;
     for (int k = 0; k < L.nm; ++k) {
         const rt_material &m = s.mats[k];
         float *q = rec4(I, L.off_mat + 3 * k);
@@ -1115,6 +1142,17 @@ void write_materials(float *I, const RenderParams &L, const Scene &s, const Sphe
             q[1] = std::max(m.fuzz * m.fuzz, 1e-3f), q[2] = 1.0f / m.ir, q[3] = m.fuzz;
             q[4] = m.albedo[0], q[5] = m.albedo[1], q[6] = m.albedo[2], q[7] = m.ir;
             break;
+        case RT_MAT_PBR: {  // the base texture here, the factors and the map in the side record
+            kind = MK_PBR;
+            float r0 = (m.ir - 1.0f) / (m.ir + 1.0f);
+            r0 = r0 * r0;
+            float *sd = rec4(I, pbr_at);
+            sd[0] = m.albedo[0], sd[1] = m.fuzz;
+            const int base = pbr_texture(q, m.texture), map = pbr_texture(sd, scene_pbr_map(s, k));
+            q[1] = bits(pbr_at), q[2] = r0, q[3] = bits(base | map << 4);
+            pbr_at += 3;
+            break;
+        }
         default: break;
         }
         q[0] = bits(kind);
@@ -1332,8 +1370,8 @@ bool pack_round(const Scene &s, std::vector<char> &forced, std::vector<float> &i
     L.grid_sheet = (!g.cells.empty() && g.n[1] == 1 && !g.wide) ? 1 : 0;
     std::vector<int> image_word;
     std::vector<int> noise_rec, bump_rec;
-    int off_media = 0, off_motion = 0, off_normals = 0, off_noise = 0, off_bump = 0;
-    const int records = lay_out_image(L, g, s, image_word, off_media, off_motion, off_normals, off_noise, off_bump);
+    int off_media = 0, off_motion = 0, off_normals = 0, off_noise = 0, off_bump = 0, off_pbr = 0;
+    const int records = lay_out_image(L, g, s, image_word, off_media, off_motion, off_normals, off_noise, off_bump, off_pbr);
     if (records < 0) {
         (records == -2 ? note.too_many_slots : note.too_large) = true;
         return true;
@@ -1357,7 +1395,7 @@ bool pack_round(const Scene &s, std::vector<char> &forced, std::vector<float> &i
     write_texels(I, s, image_word);
     write_noise(I, s, off_noise, noise_rec);
     write_bumps(I, s, off_bump, noise_rec, bump_rec);
-    write_materials(I, L, s, S, O, image_word, noise_rec, bump_rec);
+    write_materials(I, L, s, S, O, image_word, noise_rec, bump_rec, off_pbr);
     if (L.nl > 0) write_lights(I, L, s, S, O, lights);
     if (s.env) write_environment(I, L, s);
     if (!s.media.empty()) write_media(I, L, s, off_media);

@@ -1191,20 +1191,24 @@
                 // left where an image's texel is left.  From here on the vertex IS the image-textured one of its material --
                 // scatter, emitter, albedo feature, the counters and every ordered comparison of kinds see the kind they know --
                 // except plastic, whose light sample needs the colour again (step (7) evaluates it again from the same point).
+                // (Its value is formed further down, behind the (u, v): here the vertex only learns what it is.)
+                // The metallic-roughness material (rt_pbr.h) has two textures of any type: its base colour in the
+                // material's own rows and its map in the rows of a side record.  pbr_t: base type | map type << 4 (-1: not pbr)
                 bool noise_tex = false;
+                int pbr_t = -1;
                 if constexpr (EXT && !QUERY) {
+                    if (kind == MK_PBR) pbr_t = __float_as_int(M[0].w);
                     if (kind >= MK_LAMBERT_NOISE && kind <= MK_PLASTIC_NOISE) {  // (rough glass, above them, has no texture)
-                        const float4 c = noise_texel(image, M[1], M[2], px, py, pz);
-                        tex_r = c.x, tex_g = c.y, tex_b = c.z;
                         noise_tex = true;
                         if (kind != MK_PLASTIC_NOISE) kind = kind == MK_LAMBERT_NOISE ? MK_LAMBERT_IMAGE : MK_LIGHT_IMAGE;
                     }
                 }
+                const bool pbr_uv = EXT && !QUERY && pbr_t >= 0 && ((pbr_t & 15) == 2 || (pbr_t >> 4) == 2);
                 // the hit record's (u, v) -- only where the material's texture reads them (an image texture); every
                 // other texture of the reference ignores them, and acos / atan2 per candidate hit (object.cuh:87-93)
                 // would be the most expensive part of sphere::hit
                 // (QUERY: for every hit, they are part of the record)
-                const bool want_uv = EXT && (QUERY || (!noise_tex && (kind == MK_LAMBERT_IMAGE || kind == MK_LIGHT_IMAGE || kind == MK_PLASTIC_IMAGE)));
+                const bool want_uv = EXT && (QUERY || pbr_uv || (!noise_tex && (kind == MK_LAMBERT_IMAGE || kind == MK_LIGHT_IMAGE || kind == MK_PLASTIC_IMAGE)));
                 // a triangle's area weights (hittable.py:54-58), stated once: of the plane point for (u, v), and -- smooth shading,
                 // DESIGN 7l -- of the vertex normals.  The NORMALS part (device_scene.h) is there only when the scene has a triangle
                 // with vertex normals: where it lies is a wave-uniform word of the camera block, as for the media and the movers.
@@ -1265,8 +1269,8 @@
                         }
                     }
                 }
+                float tu = 0.0f, tv = 0.0f;
                 if (want_uv) {
-                    float tu, tv;
                     if ((MOTION && mot_i >= 0) || best_id < ns) {  // get_sphere_uv(outward_normal), object.cuh:87-93
                         const float onx = front ? nx : -nx, ony = front ? ny : -ny, onz = front ? nz : -nz;
                         const float theta = rt_acosf(-ony);
@@ -1306,7 +1310,50 @@
                         active = false;
                         kind = -1;
                     } else
-                    image_texel(image, M[1], tu, tv, tex_r, tex_g, tex_b);
+                    if (!pbr_uv) image_texel(image, M[1], tu, tv, tex_r, tex_g, tex_b);
+                }
+                // The solid textures' values: a noise texture under a lambertian, an emitter or a plastic, and both textures of a
+                // pbr material -- ONE copy of the noise code: a second pass of the same call site evaluates a pbr material's
+                // noise map.  Then a pbr hit's parameters (rt_pbr.h): its image, solid and checker sources, and everything to
+                // bytes.  From here on tex holds the base colour c8 / 255, and r8 and m8 ride in the kind's upper bits (kind =
+                // MK_PBR | r8 << 8 | m8 << 16) until the scatter step (6) has made the vertex a plastic or a rough-metal one: every
+                // ordered comparison of kinds in between sees a glossy kind, and nothing more stays live than for an
+                // image-textured plastic
+                if constexpr (EXT && !QUERY) {
+                    const bool pbr = pbr_t >= 0;
+                    if (noise_tex || pbr) {
+                        const float4 *PS = pbr ? image + __float_as_int(M[0].y) : M;
+                        float pm_g = 1.0f, pm_b = 1.0f;  // the map's G and B channels
+                        const bool n_base = !pbr || (pbr_t & 15) == 3, n_map = pbr && (pbr_t >> 4) == 3;
+#pragma clang loop unroll(disable)
+                        for (int pass = 0; pass < 2; ++pass) {
+                            if (pass == 0 ? n_base : n_map) {
+                                const float4 *R = pass == 0 ? M : PS;
+                                const float4 c = noise_texel(image, R[1], R[2], px, py, pz);
+                                if (pass == 0) tex_r = c.x, tex_g = c.y, tex_b = c.z;
+                                else pm_g = c.y, pm_b = c.z;
+                            }
+                        }
+                        if (pbr) {
+                            float mr;
+                            if ((pbr_t & 15) == 2) image_texel(image, M[1], tu, tv, tex_r, tex_g, tex_b);
+                            if ((pbr_t >> 4) == 2) image_texel(image, PS[1], tu, tv, mr, pm_g, pm_b);
+                            const float4 q1 = M[1], q2 = M[2], s0 = PS[0], s1 = PS[1], s2 = PS[2];
+                            const bool odd = checker_odd(px, py, pz);
+                            if ((pbr_t & 15) < 2) {
+                                const bool o = odd && (pbr_t & 15) == 1;
+                                tex_r = o ? q2.x : q1.x, tex_g = o ? q2.y : q1.y, tex_b = o ? q2.z : q1.z;
+                            }
+                            if ((pbr_t >> 4) < 2) {
+                                const bool o = odd && (pbr_t >> 4) == 1;
+                                pm_g = o ? s2.y : s1.y, pm_b = o ? s2.z : s1.z;
+                            }
+                            uint32_t m8;
+                            const uint32_t c8 = pbr_params(tex_r, tex_g, tex_b, pm_g, pm_b, s0.y, s0.x, m8);
+                            tex_r = pbr_unit(c8 & 255u), tex_g = pbr_unit((c8 >> 8) & 255u), tex_b = pbr_unit((c8 >> 16) & 255u);
+                            kind = MK_PBR | (int)((c8 >> 24) << 8) | (int)(m8 << 16);
+                        }
+                    }
                 }
                 // a bump: the material's noise height field tilts the shading normal, behind the smooth-shading normal
                 // and the (u, v) above (a sphere's read its normal) and before everything that shades: the feature pass, the
@@ -1344,7 +1391,7 @@
                         // (rough metal: F0, where metal keeps its albedo; plastic: the body's texture)
                         const bool odd = (kind == MK_LAMBERT_CHECKER || kind == MK_LIGHT_CHECKER || kind == MK_PLASTIC_CHECKER) && checker_odd(px, py, pz);
                         L_r = odd ? q2.x : q1.x, L_g = odd ? q2.y : q1.y, L_b = odd ? q2.z : q1.z;
-                        if (kind == MK_LAMBERT_IMAGE || kind == MK_LIGHT_IMAGE || kind == MK_PLASTIC_IMAGE || kind == MK_PLASTIC_NOISE) L_r = tex_r, L_g = tex_g, L_b = tex_b;
+                        if (kind == MK_LAMBERT_IMAGE || kind == MK_LIGHT_IMAGE || kind == MK_PLASTIC_IMAGE || kind == MK_PLASTIC_NOISE || (EXT && pbr_t >= 0)) L_r = tex_r, L_g = tex_g, L_b = tex_b;  // (pbr: the base colour, c8 / 255)
                         if (kind == MK_DIELECTRIC || (EXT && kind == MK_ROUGH_GLASS)) L_r = L_g = L_b = 1.0f;  // (c0 of rough glass is its sigma)
                     } else if (P.feature == RT_FEATURE_NORMAL) {
                         L_r = nx, L_g = ny, L_b = nz;
@@ -1674,6 +1721,7 @@
                 if (kind == MK_MEDIUM) M = image + __builtin_amdgcn_readfirstlane(__float_as_int(image[P.off_cam + 2].w)) + RT_MEDIUM_STRIDE * mat;
             }
             const float4 q0 = M[0], q1 = M[1], q2 = M[2];
+                float g_rough = q0.w;          // (EXT) a glossy vertex's roughness: the record's, or a pbr hit's own
                 float ndx, ndy, ndz;           // scattered direction
                 float at_r, at_g, at_b;        // attenuation
                 bool scattered = true;
@@ -1712,8 +1760,21 @@
                         const float dist = rt_sqrtf(dot3(ex, ey, ez, ex, ey, ez));
                         gv_r = glass_tint(q1.x, dist), gv_g = glass_tint(q1.y, dist), gv_b = glass_tint(q1.z, dist);
                     }
+                    // The metallic-roughness material (rt_pbr.h): its bytes come out of the kind's upper bits, and
+                    // from its first draw on the vertex is a plastic or a rough-metal one of roughness r8 / 255 -- in `kind` too
+                    // (MK_PBR: plastic, MK_PBR + 1: metal), which the packed word below hands to the light sample
+                    const bool pbr = (kind & 255) == MK_PBR;
+                    float g_alpha = q0.y;
+                    uint32_t pbr_m8 = 0u;
+                    if (pbr) {
+                        pbr_m8 = ((uint32_t)kind >> 16) & 255u;
+                        gtex = ((uint32_t)kind >> 8) << 24;  // (r8; m8 falls off the top)
+                        g_rough = pbr_unit(gtex >> 24);
+                        g_alpha = pbr_alpha(g_rough);
+                        kind = MK_PBR;
+                    }
                     if (-dot3(ux, uy, uz, nx, ny, nz) > 0.0f) {
-                        const bool plastic = kind != MK_ROUGH_METAL && !glass;
+                        bool plastic = kind != MK_ROUGH_METAL && !glass;
                         // F0, or the coat's r0 in every channel with the body's colour beside it
                         float f_r = q1.x, f_g = q1.y, f_b = q1.z, rh_r = 0.0f, rh_g = 0.0f, rh_b = 0.0f, ul = 0.0f;
                         if (plastic) {
@@ -1723,9 +1784,16 @@
                             f_r = f_g = f_b = q0.z;
                         }
                         if (glass) f_r = f_g = f_b = 1.0f;  // (its c0 is sigma)
-                        if (plastic || glass) ul = rng_next<COUNT>(rng);
+                        if (plastic || glass) ul = rng_next<COUNT>(rng);  // (pbr is a plastic so far: three draws, whatever it chooses)
+                        if (pbr) {
+                            rh_r = tex_r, rh_g = tex_g, rh_b = tex_b;
+                            if (pbr_choose(pbr_m8, ul, ul)) {
+                                plastic = false, kind = MK_PBR + 1;
+                                f_r = tex_r, f_g = tex_g, f_b = tex_b;
+                            }
+                        }
                         const float u1 = rng_next<COUNT>(rng), u2 = rng_next<COUNT>(rng);
-                        scattered = glossy_sample_body(glass ? GLOSSY_GLASS : (plastic ? GLOSSY_PLASTIC : GLOSSY_METAL), nx, ny, nz, ux, uy, uz, q0.y,
+                        scattered = glossy_sample_body(glass ? GLOSSY_GLASS : (plastic ? GLOSSY_PLASTIC : GLOSSY_METAL), nx, ny, nz, ux, uy, uz, g_alpha,
                                                        f_r, f_g, f_b, rh_r, rh_g, rh_b, front ? q0.z : q1.w, ul, u1, u2, ndx, ndy, ndz, at_r, at_g,
                                                        at_b, gpdf, below, lobe, NEE && !ENV);  // (the Fresnel term behind a call there: DESIGN 7r)
                         if (glass) at_r *= gv_r, at_g *= gv_g, at_b *= gv_b;
@@ -1742,8 +1810,9 @@
                         // three floats stay live across the roulette section and the light's sample
                         mrx = ux, mry = uy, mrz = uz;
                         mfz = __uint_as_float(0x80000000u | (below ? 0x40000000u : 0u) | ((uint32_t)kind << 24) | (uint32_t)mat);
-                        if (kind == MK_PLASTIC_IMAGE)
-                            gtex = (uint32_t)fmaf(tex_r, 255.0f, 0.5f) | (uint32_t)fmaf(tex_g, 255.0f, 0.5f) << 8 | (uint32_t)fmaf(tex_b, 255.0f, 0.5f) << 16;
+                        // (a pbr vertex: its colour bytes beside r8, which is there already -- all the light sample takes of it)
+                        if (kind == MK_PLASTIC_IMAGE || pbr)
+                            gtex |= (uint32_t)fmaf(tex_r, 255.0f, 0.5f) | (uint32_t)fmaf(tex_g, 255.0f, 0.5f) << 8 | (uint32_t)fmaf(tex_b, 255.0f, 0.5f) << 16;
                         glossy_pdf = gpdf;
                     }
                 } else {  // dielectric::scatter, material.h:66-95
@@ -1778,7 +1847,7 @@
                 // is kept for the MIS weight of an emitter it hits
                 nee_v = kind <= MK_LAMBERT_IMAGE || (kind == MK_METAL && q0.y >= 0.05f);
                 const bool glossy = EXT && mfz < 0.0f;
-                if (glossy) nee_v = q0.w >= RT_GLOSSY_MIN_ROUGHNESS && (__float_as_uint(mfz) & 0x40000000u) == 0u;
+                if (glossy) nee_v = g_rough >= RT_GLOSSY_MIN_ROUGHNESS && (__float_as_uint(mfz) & 0x40000000u) == 0u;  // (pbr: the per-hit r)
                 float cpdf = -1.0f;
                 if (glossy) {
                     if (nee_v && scattered) cpdf = glossy_pdf;
@@ -1975,14 +2044,19 @@
                 const int gkind = (int)((gbits >> 24) & 63u);
                 const float4 *M = rec_at(image + P.off_mat, __umul24(gbits & 0xffffffu, 48u));
                 const float4 q0 = M[0], q1 = M[1], q2 = M[2];
-                const bool glass = gkind >= MK_ROUGH_GLASS;  // (bit 0 of the kind: a back hit)
-                const bool plastic = gkind != MK_ROUGH_METAL && !glass;
+                const bool glass = (gkind & ~1) == MK_ROUGH_GLASS;  // (bit 0 of the kind: a back hit)
+                // a vertex of pbr origin (bit 0: it chose the metal lobe): alpha, r and the colour are the hit's own,
+                // from gtex, not the record's
+                const bool pbr = gkind >= MK_PBR;
+                const bool plastic = gkind != MK_ROUGH_METAL && !glass && gkind != MK_PBR + 1;
+                const float g_alpha = pbr ? pbr_alpha(pbr_unit(gtex >> 24)) : q0.y;
                 float f_r = q1.x, f_g = q1.y, f_b = q1.z, rh_r = 0.0f, rh_g = 0.0f, rh_b = 0.0f;
+                if (gkind == MK_PBR + 1) f_r = pbr_unit(gtex & 255u), f_g = pbr_unit((gtex >> 8) & 255u), f_b = pbr_unit((gtex >> 16) & 255u);
                 if (glass) f_r = f_g = f_b = 1.0f;  // (its c0 is sigma; its tint is in vb already)
                 if (plastic) {
                     const bool odd = gkind == MK_PLASTIC_CHECKER && checker_odd(px, py, pz);
                     rh_r = odd ? q2.x : q1.x, rh_g = odd ? q2.y : q1.y, rh_b = odd ? q2.z : q1.z;
-                    if (gkind == MK_PLASTIC_IMAGE)  // (the texel as image_texel made it: the same byte over 255)
+                    if (gkind == MK_PLASTIC_IMAGE || pbr)  // (the texel as image_texel made it: the same byte over 255)
                         rh_r = (float)(gtex & 255u) / 255.0f, rh_g = (float)((gtex >> 8) & 255u) / 255.0f, rh_b = (float)((gtex >> 16) & 255u) / 255.0f;
                     // (a noise texture: 8 bits a channel would lose it.  Evaluated again at the hit point, which is still in
                     //  px, py, pz: the same operations on the same floats, so the rho the vertex scattered with, bit for bit)
@@ -1992,7 +2066,7 @@
                     }
                     f_r = f_g = f_b = q0.z;
                 }
-                glossy_eval_body(glass ? GLOSSY_GLASS : (plastic ? GLOSSY_PLASTIC : GLOSSY_METAL), nx, ny, nz, mrx, mry, mrz, q0.y, f_r, f_g, f_b, rh_r,
+                glossy_eval_body(glass ? GLOSSY_GLASS : (plastic ? GLOSSY_PLASTIC : GLOSSY_METAL), nx, ny, nz, mrx, mry, mrz, g_alpha, f_r, f_g, f_b, rh_r,
                                  rh_g, rh_b, (gkind & 1) ? q1.w : q0.z, wx, wy, wz, gf_r, gf_g, gf_b, pb, !ENV);
             } else
             if (wn > 0.0f) pb = mfz > 0.0f ? metal_pdf(wx, wy, wz, mrx, mry, mrz, mfz) : wn * kInvPi;

@@ -297,8 +297,18 @@ bool glossy_material_ok(const rt_material &m, size_t textures, const char *where
             return false;
         }
     } else {
+        if (m.type == RT_MAT_PBR) {  // albedo[0] holds the metallic factor, the rest of albedo nothing
+            if (!(m.albedo[0] >= 0.0f && m.albedo[0] <= 1.0f)) {
+                set_error("%s: pbr metallic factor must be finite and in [0, 1] (got %g)", where, (double)m.albedo[0]);
+                return false;
+            }
+            if (m.albedo[1] != 0.0f || m.albedo[2] != 0.0f) {
+                set_error("%s: pbr albedo[1..2] must be 0 (got %g, %g)", where, (double)m.albedo[1], (double)m.albedo[2]);
+                return false;
+            }
+        }
         if (!(m.ir > 1.0f && m.ir < INFINITY)) {
-            set_error("%s: plastic ior must be finite and > 1 (got %g)", where, (double)m.ir);
+            set_error("%s: %s ior must be finite and > 1 (got %g)", where, m.type == RT_MAT_PBR ? "pbr" : "plastic", (double)m.ir);
             return false;
         }
         if (m.texture < 0 || (size_t)m.texture >= textures) {
@@ -398,6 +408,38 @@ bool set_bump(Scene &s, int material, int texture, float strength, const char *w
     return true;
 }
 
+// the metallic-roughness map of a pbr material: the argument rules, shared by the C call, the JSON reader and
+// scene_validate.  none_ok: texture -1 (no map) passes
+static bool pbr_map_ok(const Scene &s, int material, int texture, bool none_ok, const char *where) {
+    if (material < 0 || material >= (int)s.mats.size()) {
+        set_error("%s: unknown material %d (have %zu)", where, material, s.mats.size());
+        return false;
+    }
+    if (s.mats[(size_t)material].type != RT_MAT_PBR) {
+        set_error("%s: material %d is not a pbr material, which alone takes a metallic-roughness map", where, material);
+        return false;
+    }
+    if (none_ok && texture == -1) return true;
+    if (texture < 0 || texture >= (int)s.texs.size()) {
+        set_error("%s: metallic-roughness map references texture %d (have %zu)", where, texture, s.texs.size());
+        return false;
+    }
+    return true;
+}
+
+bool set_pbr_map(Scene &s, int material, int texture, const char *where) {
+    if (!pbr_map_ok(s, material, texture, true, where)) return false;
+    if (texture == -1) {  // removes; the table ends at the last mapped material
+        if ((size_t)material < s.pbr_maps.size()) s.pbr_maps[(size_t)material] = -1;
+        while (!s.pbr_maps.empty() && s.pbr_maps.back() < 0) s.pbr_maps.pop_back();
+    } else {
+        if (s.pbr_maps.size() <= (size_t)material) s.pbr_maps.resize((size_t)material + 1, -1);
+        s.pbr_maps[(size_t)material] = texture;
+    }
+    s.touch();
+    return true;
+}
+
 int scene_validate(const Scene &s) {
     if (s.width < 2 || s.height < 2) {
         // u = (x + xi) / (W - 1), main.cu:97-98: W = 1 divides by zero
@@ -439,6 +481,12 @@ int scene_validate(const Scene &s) {
         char where[32];
         snprintf(where, sizeof where, "material %zu", i);
         if (!bump_ok(s, (int)i, s.bumps[i].texture, s.bumps[i].strength, false, where)) return RT_ERR_SCENE;
+    }
+    for (size_t i = 0; i < s.pbr_maps.size(); ++i) {
+        if (s.pbr_maps[i] < 0) continue;
+        char where[32];
+        snprintf(where, sizeof where, "material %zu", i);
+        if (!pbr_map_ok(s, (int)i, s.pbr_maps[i], false, where)) return RT_ERR_SCENE;
     }
     for (size_t i = 0; i < s.texs.size(); ++i) {
         const rt_texture &t = s.texs[i];
@@ -1250,6 +1298,8 @@ int scene_from_json(const char *text, size_t len, Scene &s, const char *base_dir
             };
             // a bump on any material but an emitter: {"texture": <noise texture>, "strength": <number>}
             const JsonValue *bump = m.find("bump");
+            int pbr_map = -1;  // (a pbr material's "metallic_roughness")
+            bool has_pbr_map = false;
             int bump_tex = -1;
             float bump_k = 0.0f;
             if (bump) {
@@ -1288,6 +1338,15 @@ int scene_from_json(const char *text, size_t len, Scene &s, const char *base_dir
                 rec.ir = (float)r.num(m, "ior", where);
                 rec.fuzz = (float)r.num(m, "roughness", where);
                 if (r.ok && !glossy_material_ok(rec, s.texs.size(), where)) r.ok = false;
+            } else if (ty->str == "pbr") {  // fuzz holds the roughness factor, albedo[0] the metallic factor
+                rec.type = RT_MAT_PBR;
+                only_keys(m, {"type", "texture", "metallic", "roughness", "ior", "metallic_roughness", "bump"});
+                rec.texture = r.integer(m, "texture", where);
+                rec.albedo[0] = (float)r.num(m, "metallic", where);
+                rec.fuzz = (float)r.num(m, "roughness", where);
+                rec.ir = m.find("ior") ? (float)r.num(m, "ior", where) : 1.5f;
+                if (m.find("metallic_roughness")) pbr_map = r.integer(m, "metallic_roughness", where), has_pbr_map = true;
+                if (r.ok && !glossy_material_ok(rec, s.texs.size(), where)) r.ok = false;
             } else if (ty->str == "rough_glass") {  // fuzz holds the roughness, albedo the absorption coefficient
                 rec.type = RT_MAT_ROUGH_GLASS;
                 only_keys(m, {"type", "ir", "roughness", "absorption", "tint", "tint_distance", "bump"});
@@ -1321,6 +1380,7 @@ int scene_from_json(const char *text, size_t len, Scene &s, const char *base_dir
             }
             s.mats.push_back(rec);
             if (r.ok && bump && !set_bump(s, (int)s.mats.size() - 1, bump_tex, bump_k, where)) r.ok = false;
+            if (r.ok && has_pbr_map && !set_pbr_map(s, (int)s.mats.size() - 1, pbr_map, where)) r.ok = false;  // (-1: no map)
         }
     }
     if (!r.ok) return RT_ERR_SCENE;
@@ -1716,6 +1776,12 @@ std::string scene_to_json(const Scene &s) {
         case RT_MAT_PLASTIC:
             o += "{\"type\": \"plastic\", \"texture\": " + std::to_string(m.texture) + ", \"ior\": " + json_float(m.ir) +
                  ", \"roughness\": " + json_float(m.fuzz) + "}";
+            break;
+        case RT_MAT_PBR:
+            o += "{\"type\": \"pbr\", \"texture\": " + std::to_string(m.texture) + ", \"metallic\": " + json_float(m.albedo[0]) +
+                 ", \"roughness\": " + json_float(m.fuzz) + ", \"ior\": " + json_float(m.ir);
+            if (scene_pbr_map(s, (int)i) >= 0) o += ", \"metallic_roughness\": " + std::to_string(scene_pbr_map(s, (int)i));
+            o += "}";
             break;
         case RT_MAT_ROUGH_GLASS:  // (a tint comes back as the absorption it was converted to)
             o += "{\"type\": \"rough_glass\", \"ir\": " + json_float(m.ir) + ", \"roughness\": " + json_float(m.fuzz) + ", \"absorption\": ";

@@ -73,6 +73,8 @@ struct Scene {
                                      // texture table as the images are, as long as the last noise texture's id + 1
     std::vector<SceneBump> bumps;    // bumps[m]: the bump of material m, texture < 0: none; beside the material table
                                      // as `noise` is beside the textures, at most as long as the last bumped material's id + 1
+    std::vector<int> pbr_maps;       // pbr_maps[m]: the metallic-roughness map of pbr material m, -1: none; beside the
+                                     // material table as the bumps are, at most as long as the last mapped material's id + 1
     std::shared_ptr<const SceneEnvironment> env;  // null: no environment (a miss gives the background / the sky)
     float env_scale = 1.0f, env_rotate = 0.0f;    // radiance = scale x texel; degrees about +y
     std::vector<rt_medium> media;  // homogeneous participating media, a list of its own: at most RT_MAX_MEDIA
@@ -159,7 +161,10 @@ inline bool tri_has_normals(const rt_prim &p) {
 // glossy materials: does the material table hold one (such a scene runs the general kernels over the wide tables);
 // is a rough_metal / plastic record within its argument rules (false: the message is set, prefixed with `where`)
 // (rough_glass, DESIGN 7r, is the third of them)
-inline bool is_glossy(const rt_material &m) { return m.type == RT_MAT_ROUGH_METAL || m.type == RT_MAT_PLASTIC || m.type == RT_MAT_ROUGH_GLASS; }
+// (pbr, DESIGN 7t, becomes a rough_metal or a plastic at every vertex: fuzz = the roughness factor, albedo[0] = the metallic factor)
+inline bool is_glossy(const rt_material &m) {
+    return m.type == RT_MAT_ROUGH_METAL || m.type == RT_MAT_PLASTIC || m.type == RT_MAT_ROUGH_GLASS || m.type == RT_MAT_PBR;
+}
 inline bool scene_has_glossy(const Scene &s) {
     for (const rt_material &m : s.mats)
         if (is_glossy(m)) return true;
@@ -191,6 +196,11 @@ inline bool scene_has_bump(const Scene &s) {
     return false;
 }
 bool set_bump(Scene &s, int material, int texture, float strength, const char *where);
+
+// the metallic-roughness map of pbr material m, or -1; set_pbr_map checks (false: the message is set, prefixed
+// with `where`) and stores -- texture -1 removes
+inline int scene_pbr_map(const Scene &s, int m) { return (m >= 0 && (size_t)m < s.pbr_maps.size()) ? s.pbr_maps[(size_t)m] : -1; }
+bool set_pbr_map(Scene &s, int material, int texture, const char *where);
 
 // a medium (scene.cpp): checks the record and appends it -> medium id, or -rt_status
 int add_medium(Scene &s, const rt_medium &m);
