@@ -831,6 +831,13 @@ int rt_device_count(void);
  * (the default build; `make ABLATIONS=0` builds the six product kernels alone: same ABI, rt_render_hip_count then
  * fails with RT_ERR_LIMIT and rt_opts.variant accepts 0, 2, 6, 16, 36, 44, 52) */
 int rt_has_ablations(void);
+/* The workgroup that render variant `variant` (never 0) launches, as the host sizes it; no device is touched.
+ * out[0] threads per workgroup, out[1] bytes of LDS per wave behind the staged tables (tile accumulator; variants 2 and 6:
+ * and the slab of prepared camera rays), out[2] the largest table size in bytes that the packer keeps LDS-resident,
+ * out[3] dynamic LDS in bytes of a workgroup that stages tables of that size, out[4] workgroups per CU that the kernel's
+ * registers and the wave slots admit (what the LDS of a CU, 160 KB, has to hold).  RT_ERR_ARG for a null pointer or a variant
+ * this library does not carry. */
+int rt_variant_workgroup(unsigned variant, int32_t out[5]);
 /* Philox4x32-10 block (seeds every (pixel, sample) stream), for known-answer tests */
 void rt_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 /* first n raw 32-bit words of the xorshift128 stream of one (pixel, sample); the kernel's

@@ -221,6 +221,7 @@ _sig("rt_last_error", C.c_char_p)
 _sig("rt_status_string", C.c_char_p, C.c_int)
 _sig("rt_abi_version", C.c_int)
 _sig("rt_has_ablations", C.c_int)
+_sig("rt_variant_workgroup", C.c_int, C.c_uint, C.POINTER(C.c_int32))
 _sig("rt_device_count", C.c_int)
 _sig("rt_struct_size", C.c_size_t, C.c_int)
 _sig("rt_opts_default", None, C.POINTER(Opts))
@@ -357,7 +358,7 @@ _sig("rt_write_pfm", C.c_int, C.c_char_p, _p, C.c_int, C.c_int, C.c_int)
 
 C_SYMBOLS = [
     "rt_last_error", "rt_status_string", "rt_abi_version", "rt_struct_size", "rt_device_count", "rt_has_ablations", "rt_opts_default",
-    "rt_scene_table_info", "rt_scene_table_image",
+    "rt_scene_table_info", "rt_scene_table_image", "rt_variant_workgroup",
     "rt_scene_load_json", "rt_scene_parse_json", "rt_scene_rtiow", "rt_scene_to_json", "rt_scene_free",
     "rt_scene_new", "rt_scene_set_background", "rt_scene_set_camera", "rt_scene_add_solid_color",
     "rt_scene_add_checker", "rt_scene_add_lambertian", "rt_scene_add_metal", "rt_scene_add_dielectric",
@@ -1238,3 +1239,10 @@ def has_ablations() -> bool:
 
 
 LIB_PATH = _LIB_PATH
+
+
+def variant_workgroup(variant: int) -> dict:
+    """The workgroup render variant `variant` launches, as the host sizes it (rt_variant_workgroup; no device needed)."""
+    out = (C.c_int32 * 5)()
+    _check(_lib.rt_variant_workgroup(int(variant), out), "rt_variant_workgroup")
+    return dict(zip(("threads", "wave_lds", "max_table_bytes", "max_lds_bytes", "groups_per_cu"), (int(x) for x in out)))

@@ -32,11 +32,54 @@ struct KernelKey {
     bool feature = false;  // K_ENV: a feature pass
 };
 
+// The workgroup of an instance.  Every family runs 4 waves with one 1.5 KB tile accumulator each; the sphere-only
+// compact-table instances (variants 2 and 6) run kBigGroupWaves, which share ONE staged copy of the scene tables, and each
+// wave of theirs has a slab of 64 prepared camera rays behind its accumulator (render_body.h, the burst).  Two such
+// workgroups are resident on a CU; with the largest LDS-resident tables (pack.h, kLdsTableBytes) they take
+// 2 x (17.3 + 15 x (1.5 + 2.5)) = 154.6 of its 160 KB.
+// The shape is the measured one (profiles/headline_bursts_mi355x.txt).  A workgroup's waves are dealt to the four
+// SIMDs from the first one on, so two groups of n waves put 2 ceil(n / 4) waves on SIMD 0: at the 72-register budget of
+// 7 waves per SIMD two groups of 14 never share a CU (one ran alone: 148 ms against 105).  What fits is 24 waves at 80
+// registers (3 x 8 or 2 x 12) or up to 32 at 64 registers; 2 x 15 at 64 is the fastest shape that also holds the largest tables.
+// (measurement knobs of render_kernel.hip, tools/build_ab.sh: -DRT_BIG_GROUPS=0 builds variants 2 and 6 in the 4-wave shape,
+//  -DRT_BURSTS=0 the big groups without the slabs, -DRT_BIG_WAVES=n -DRT_BIG_WAVES_PER_SIMD=m other shapes)
+#ifndef RT_BIG_GROUPS
+#define RT_BIG_GROUPS 1
+#endif
+#ifndef RT_BURSTS
+#define RT_BURSTS 1
+#endif
+#ifndef RT_BIG_WAVES
+#define RT_BIG_WAVES 15
+#endif
+#ifndef RT_BIG_WAVES_PER_SIMD
+#define RT_BIG_WAVES_PER_SIMD 8
+#endif
+constexpr int kGroupWaves = 4, kBigGroupWaves = RT_BIG_WAVES;
+// workgroups of kBigGroupWaves that a CU holds: waves dealt from SIMD 0 on, RT_BIG_WAVES_PER_SIMD on each
+constexpr int kBigGroupsPerCu = RT_BIG_WAVES_PER_SIMD / ((RT_BIG_WAVES + 3) / 4);
+// is render_kernel<COUNT, POOL, SCALAR, CULL, EXT, SPH> built in the big shape / with bursts?
+constexpr bool big_group(bool count, bool pool, bool scalar, int cull, bool sph) {
+    return RT_BIG_GROUPS != 0 && sph && pool && !scalar && !count && (cull == 5 || cull == 6);
+}
+constexpr bool burst_starts(bool count, bool pool, bool scalar, int cull, bool sph) {
+    return RT_BURSTS != 0 && big_group(count, pool, scalar, cull, sph);
+}
+constexpr int kWaveAccBytes = 192 * 8;          // 64 pixels x rgb, 64-bit fixed point
+constexpr int kWaveSlabBytes = 64 * 10 * 4;     // 64 x {origin, direction, generator state}
+
 struct KernelRow {
     KernelKey key;
     int cull;        // the instance's CULL template argument: decides how much of the hot tables is staged
     const void *fn;  // the kernel instance
+    int waves = kGroupWaves;         // waves per workgroup
+    int wave_lds = kWaveAccBytes;    // LDS per wave behind the staged tables
+    int groups_per_cu = 0;           // workgroups a CU holds by registers and wave slots (0: one per wave of a SIMD's budget)
 };
+
+// block size and dynamic LDS of a launch of `row` with `table_bytes` of staged tables
+inline unsigned group_threads(const KernelRow &row) { return 64u * (unsigned)row.waves; }
+inline size_t group_lds(const KernelRow &row, size_t table_bytes) { return table_bytes + (size_t)row.waves * (size_t)row.wave_lds; }
 
 // the rows of a translation unit; *n: how many
 const KernelRow *render_kernel_rows(size_t *n);  // render_kernel.hip: K_PLAIN, K_NEE, K_NESTED, K_FEATURE

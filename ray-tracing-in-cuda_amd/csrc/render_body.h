@@ -18,16 +18,26 @@
     // (the cluster searches leave the grid tables, which lie in front of their boxes, out: `gap` records)
     const int gap = (SCALAR || GRID) ? 0 : P.off_box - P.off_grid;
     const int staged = SCALAR ? 0 : (GRID ? P.hot_vec4_grid : (CULL == 3 ? P.hot_vec4_tables : P.hot_vec4) - gap);
-    for (int i = threadIdx.x; i < staged; i += 256) lds[i] = image[i < P.off_grid ? i : i + gap];
+    // (BIG, kernels.h: the sphere-only compact-table instances run kBigGroupWaves waves on one staged copy, two workgroups per
+    //  CU; BURST: their paths start from a per-wave slab of 64 prepared camera rays -- the refill, below)
+    constexpr bool BIG = big_group(COUNT, POOL, SCALAR, CULL, SPH) && !QUERY && !NEE && !AOV && !ENV && !MEDIA && !MOTION;
+    constexpr bool BURST = BIG && burst_starts(COUNT, POOL, SCALAR, CULL, SPH);
+    constexpr int GW = BIG ? kBigGroupWaves : kGroupWaves;
+    for (int i = threadIdx.x; i < staged; i += 64 * GW) lds[i] = image[i < P.off_grid ? i : i + gap];
     // per-wave tile accumulator of the current work item: 64 pixels x rgb, 64-bit fixed point
     unsigned long long *tile_acc = reinterpret_cast<unsigned long long *>(lds + staged);
     // (QUERY: a ray's record goes straight to memory: no accumulators, and no LDS reserved for them)
     if constexpr (!QUERY)
-        for (int i = threadIdx.x; i < 4 * 64 * 3; i += 256) tile_acc[i] = 0ull;
+        for (int i = threadIdx.x; i < GW * 64 * 3; i += 64 * GW) tile_acc[i] = 0ull;
     __syncthreads();
 
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;  // (wave: in a scalar register)
     unsigned long long *my_acc = tile_acc + wave * 192;
+    // BURST: the wave's slab behind the accumulators, three arrays of 64 so that every read and write is one aligned
+    // instruction over consecutive addresses: {o.xyz, d.x} {d.yz, g.xy} {g.zw}.  An off-image pixel's d.x is a NaN.
+    float4 *slab_a = lds + staged + GW * (kWaveAccBytes / 16) + (BURST ? wave * (kWaveSlabBytes / 16) : 0);
+    float4 *slab_b = slab_a + 64;
+    float2 *slab_c = reinterpret_cast<float2 *>(slab_a + 128);
     const uint32_t k0 = P.seed_lo, k1 = P.seed_hi;
     const float4 *hot = SCALAR ? image : lds;
     const float4 *sph = hot;
@@ -1620,6 +1630,78 @@
                 }
                 started_m = takes & __builtin_amdgcn_ballot_w64(ok);
             } else
+            if constexpr (BURST) {
+                // Paths start from the wave's slab.  The pool's order is the other builds': entry k is pixel k & 63, sample
+                // c_sbegin + (k >> 6), so entries [64 b, 64 b + 64) are ONE sample of every pixel of the tile: batch b.  When the
+                // cursor stands on a multiple of 64 the slab is used up (or the item is new), and all 64 lanes prepare batch
+                // cursor >> 6 -- lane l its home pixel's sample: seed, the two jitter draws, the lens disk's rejection loop and the
+                // camera ray, each what a starting lane of the other builds computes, from the same counter in the same
+                // order -- at full occupancy instead of for the dozen lanes that happen to be idle.  An idle lane of rank r then
+                // takes slot (cursor + r) & 63: three reads.  Its stored generator state goes on with the roulette draw.
+                // A hand-out that reaches the end of a batch serves the rest of the idle lanes from the next one in the same
+                // iteration (at most two passes: a batch has a slot for every lane).
+                unsigned long long want = c_valid ? idle : 0ull;  // idle lanes not served yet
+                while (want != 0ull && cursor < c_pool) {
+                    if ((cursor & 63) == 0) {
+                        __builtin_amdgcn_wave_barrier();
+                        if (c_hy >= 0) {
+                            const int bx = c_x0 + (lane & 7);
+                            const uint32_t pixel = __umul24((uint32_t)c_hy, (uint32_t)P.width) + (uint32_t)bx;
+                            LaneRng br;
+                            br.draws = 0;
+                            rng_start(br, pixel, (uint32_t)(c_sbegin + (cursor >> 6)), k0, k1);
+                            const float bu = ((float)bx + rng_next<false>(br)) * P.inv_wm1;
+                            const float bv = ((float)c_hy + rng_next<false>(br)) * P.inv_hm1;
+                            float offx = 0.0f, offy = 0.0f, offz = 0.0f;
+                            const float4 *cv = hot + P.off_cam;
+                            const float4 c_org = cv[0];  // origin, lens_radius
+                            if (P.flags & RT_FLAG_DEFOCUS_BLUR) {
+                                // random_in_unit_disk (vec3.h:157-165): two draws per attempt; x^2 + y^2 as the merged loop forms it
+                                float bsx, bsy;
+                                do {
+                                    bsx = rng_pm1<false>(br);
+                                    bsy = rng_pm1<false>(br);
+                                } while (fmaf(bsx, bsx, bsy * bsy) >= 1.0f);
+                                const float4 c_u = cv[4], c_v = cv[5];
+                                const float rdx = c_org.w * bsx, rdy = c_org.w * bsy;
+                                offx = fmaf(c_u.x, rdx, c_v.x * rdy);
+                                offy = fmaf(c_u.y, rdx, c_v.y * rdy);
+                                offz = fmaf(c_u.z, rdx, c_v.z * rdy);
+                            }
+                            const float4 c_ll = cv[1], c_hor = cv[2], c_ver = cv[3];
+                            float bdx = fmaf(bv, c_ver.x, fmaf(bu, c_hor.x, c_ll.x));
+                            float bdy = fmaf(bv, c_ver.y, fmaf(bu, c_hor.y, c_ll.y));
+                            float bdz = fmaf(bv, c_ver.z, fmaf(bu, c_hor.z, c_ll.z));
+                            bdx = (bdx - c_org.x) - offx;
+                            bdy = (bdy - c_org.y) - offy;
+                            bdz = (bdz - c_org.z) - offz;
+                            slab_a[lane] = make_float4(c_org.x + offx, c_org.y + offy, c_org.z + offz, bdx);
+                            slab_b[lane] = make_float4(bdy, bdz, __uint_as_float(br.g.x), __uint_as_float(br.g.y));
+                            slab_c[lane] = make_float2(__uint_as_float(br.g.z), __uint_as_float(br.g.w));
+                        } else {
+                            slab_a[lane] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0x7fc00000u));
+                        }
+                        __builtin_amdgcn_wave_barrier();
+                    }
+                    const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(want >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)want, 0u));
+                    const int room = 64 - (cursor & 63);
+                    const unsigned long long takes = want & __builtin_amdgcn_ballot_w64(rank < room);
+                    bool on_image = false;
+                    if (__builtin_amdgcn_inverse_ballot_w64(takes)) {
+                        const int slot = (cursor + rank) & 63;
+                        const float4 a = slab_a[slot], b = slab_b[slot];
+                        const float2 c = slab_c[slot];
+                        on_image = a.w == a.w;
+                        ox = a.x, oy = a.y, oz = a.z, dx = a.w, dy = b.x, dz = b.y;
+                        rng.g.x = __float_as_uint(b.z), rng.g.y = __float_as_uint(b.w);
+                        rng.g.z = __float_as_uint(c.x), rng.g.w = __float_as_uint(c.y);
+                        cur_p = slot;
+                    }
+                    started_m |= takes & __builtin_amdgcn_ballot_w64(on_image);
+                    cursor += min(mask_count(want), room);
+                    want &= ~takes;
+                }
+            } else
             if (POOL) {
                 const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32),
                                                                 __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
@@ -1678,7 +1760,7 @@
         // draws, for the lens sample of the paths that start)
         // (QUERY: a ray is traced once and answered: no scatter step, no camera, no roulette -- nothing from here on)
         const bool need_s = !QUERY && ((kind >= 0 && kind <= MK_METAL) || (MEDIA && kind == MK_MEDIUM));
-        const bool need_d = !QUERY && started && (P.flags & RT_FLAG_DEFOCUS_BLUR) != 0u;
+        const bool need_d = !QUERY && !BURST && started && (P.flags & RT_FLAG_DEFOCUS_BLUR) != 0u;  // (BURST: the burst's own loop)
         float sx = 0, sy = 0, sz = 0, sl2 = 1;
         asm volatile("" : "=v"(sx), "=v"(sy), "=v"(sz), "=v"(sl2));  // (read by the lanes that ran the loop below, which sets all four)
         if (need_s || need_d) {
@@ -1878,6 +1960,15 @@
             }
         }
         // ---- (6b) the camera ray of the paths that start (camera::get_ray, camera.h:32-39)
+        if constexpr (BURST) {
+            // (the ray and the generator came out of the slab in the refill; the lane joins `fresh` for what every new ray needs)
+            if (started) {
+                beta_r = beta_g = beta_b = 1.0f;
+                depth = P.max_depth;
+                active = true;
+                fresh = true;
+            }
+        } else
         if (!QUERY && started) {
                 float offx = 0.0f, offy = 0.0f, offz = 0.0f;
                 // the camera's derived vectors come from the hot table (wave-uniform reads, used here only),

@@ -242,6 +242,18 @@ static int read_tables(const rt_scene *sc, rt_table_info *out, float *dst, int c
 
 int rt_scene_table_info(const rt_scene *sc, rt_table_info *out) { return read_tables(sc, out, nullptr, 0); }
 
+int rt_variant_workgroup(unsigned variant, int32_t out[5]) {
+    const KernelRow *row = out && variant != 0 ? variant_row(variant) : nullptr;
+    if (!row) {
+        set_error("rt_variant_workgroup: %s", out ? "no such render variant in this library" : "null argument");
+        return RT_ERR_ARG;
+    }
+    out[0] = (int32_t)group_threads(*row), out[1] = row->wave_lds, out[2] = (int32_t)kLdsTableBytes;
+    out[3] = (int32_t)group_lds(*row, kLdsTableBytes);
+    out[4] = row->groups_per_cu > 0 ? row->groups_per_cu : 4 * RT_WAVES_PER_SIMD / row->waves;
+    return RT_OK;
+}
+
 int rt_scene_nested_info(const rt_scene *sc, rt_nested_info *out) {
     if (!sc || !out) {
         set_error("rt_scene_nested_info: null argument");
@@ -390,7 +402,7 @@ struct Launcher {
             launch_item_params(d_queue, ip, stream);
         }
         // persistent launch: enough workgroups to fill the chip, never more than the work needs
-        const unsigned long long need_blocks = (items + 3) / 4;
+        const unsigned long long need_blocks = (items + kernel.waves - 1) / kernel.waves;
         const unsigned long long grid = need_blocks < resident ? (need_blocks ? need_blocks : 1) : resident;
         if (feature >= 0) Q.feature = feature;
         launch_kernel(kernel, Q, ent->d_image.get(), acc, d_queue, d_cnt, lds_bytes, (unsigned)grid, stream);
@@ -674,7 +686,7 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     // (RT_WAVES_PER_SIMD workgroups per CU); larger scenes run the same walk over global memory (4000 spheres 6.7 vs 19 ms),
     // which has no size limit.  The packer has chosen the table format (device_scene.h): COMPACT for sphere-only scenes whose
     // tables fit that LDS budget, WIDE for every other scene.
-    const size_t acc_lds = kAccLds;
+    // (variants 2 and 6: workgroups of 14 waves, each with a slab of prepared rays behind its accumulator -- kernels.h)
     auto hot_bytes_of = [&](int mode) {  // (each candidate search stages the part of the hot tables it reads)
         if (mode == 5 || mode == 6 || mode == 7 || mode == 8) return (size_t)P.hot_vec4_grid * 16;
         return (size_t)((mode == 3 ? P.hot_vec4_tables : P.hot_vec4) - (P.off_box - P.off_grid)) * 16;  // (without the grid tables)
@@ -801,7 +813,21 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     if (nee || env || media || motion) ext = true;
     const size_t hot_bytes = hot_bytes_of(mode);
     const bool tables_global = (variant & 8u) != 0 || mode == 8;
-    const size_t lds_bytes = (tables_global ? 0 : hot_bytes) + acc_lds;
+    // ---- the instance: resolved once; the block size, the per-wave LDS, the launches, the grid size and the LDS limit go
+    // through its row
+    const char *family = env ? "environment" : media ? "media" : motion ? "motion" : feature >= 0 ? "feature" : nullptr;
+    const KernelRow *kernel = env            ? find_kernel({K_ENV, variant, true, false, nee, feature >= 0})
+                              : media        ? find_kernel({K_MEDIA, variant, true})
+                              : motion       ? find_kernel({K_MOTION, variant, true})
+                              : feature >= 0 ? find_kernel({K_FEATURE, variant, true})
+                              : nee          ? find_kernel({K_NEE, variant, true})
+                                             : variant_row(variant, ext, count);
+    if (!kernel) {
+        if (family) set_error("layout %u has no %s kernel", variant, family);
+        else set_error("kernel variant %u has no %s build", variant, count ? "counting" : (ext ? "triangle / texture" : "such"));
+        return env || media || motion ? RT_ERR_ARG : RT_ERR_LIMIT;
+    }
+    const size_t lds_bytes = group_lds(*kernel, tables_global ? 0 : hot_bytes);
     if (knob_set("RTMI_DEBUG_LAYOUT")) {
         const float *g = cache.image.data() + (size_t)P.off_grid * 4;
         int gn[3];
@@ -836,24 +862,13 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
         HIP_TRY(hipGetDeviceProperties(&prop, device));
         ent->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     }
-    // ---- the instance: resolved once; the launches, the grid size and the LDS limit go through its row
-    const char *family = env ? "environment" : media ? "media" : motion ? "motion" : feature >= 0 ? "feature" : nullptr;
-    const KernelRow *kernel = env            ? find_kernel({K_ENV, variant, true, false, nee, feature >= 0})
-                              : media        ? find_kernel({K_MEDIA, variant, true})
-                              : motion       ? find_kernel({K_MOTION, variant, true})
-                              : feature >= 0 ? find_kernel({K_FEATURE, variant, true})
-                              : nee          ? find_kernel({K_NEE, variant, true})
-                                             : variant_row(variant, ext, count);
-    if (!kernel) {
-        if (family) set_error("layout %u has no %s kernel", variant, family);
-        else set_error("kernel variant %u has no %s build", variant, count ? "counting" : (ext ? "triangle / texture" : "such"));
-        return env || media || motion ? RT_ERR_ARG : RT_ERR_LIMIT;
-    }
     if (lds_bytes > 64 * 1024 && set_max_dynamic_lds(*kernel, lds_bytes)) {
         set_error("cannot raise the dynamic LDS limit to %zu bytes", lds_bytes);
         return RT_ERR_HIP;
     }
     const unsigned long long resident = (unsigned long long)ent->num_cus * blocks_per_cu(*kernel, lds_bytes);
+    if (knob_set("RTMI_DEBUG_LAYOUT"))
+        fprintf(stderr, "variant %u: workgroups of %u threads, %llu resident on %d CUs\n", variant, group_threads(*kernel), resident, ent->num_cus);
 
     float *d_out = (float *)d_rgb_sum;
     DevCounters *d_cnt = nullptr;

@@ -9,7 +9,7 @@
 //            curand XORWOW per-pixel state     -> Philox-seeded xorshift128 per (pixel, sample) (philox.h)
 //
 // Shape of the kernel
-//   * 256-thread workgroup = 4 wave64; the grid only fills the chip (persistent waves) and
+//   * 256-thread workgroup = 4 wave64 (variants 2 and 6: 15 wave64, kernels.h); the grid only fills the chip (persistent waves) and
 //     every wave pulls work items -- an 8x8 pixel tile x 64 sample indices -- from one
 //     global counter.  A work-item (lane) owns ONE PATH at a time and runs its whole
 //     bounce loop (get_color), exactly as the reference's thread does for its pixel.
@@ -73,8 +73,11 @@ namespace rtmi {
 //           by multiple importance sampling (power heuristic).  The sample's visibility is a SHADOW PHASE of the lane: the
 //           lane's next query is the shadow ray (same origin, best_t starting below 1, any hit occludes); then the lane
 //           adds the sample's contribution and restores its continuation.  Only render_nee_kernel carries it.
+// The sphere-only compact-table instances (variants 2 and 6) run workgroups of kBigGroupWaves waves that share one staged
+// copy of the tables, two per CU at a register budget of their own (kernels.h); every other instance runs four waves.
 template <bool COUNT, bool POOL, bool SCALAR, int CULL, bool EXT, bool SPH>
-__global__ __launch_bounds__(256, RT_WAVES_PER_SIMD) void render_kernel(const RenderParams P, const float4 *__restrict__ image,
+__global__ __launch_bounds__(64 * (big_group(COUNT, POOL, SCALAR, CULL, SPH) ? kBigGroupWaves : kGroupWaves),
+                             big_group(COUNT, POOL, SCALAR, CULL, SPH) ? RT_BIG_WAVES_PER_SIMD : RT_WAVES_PER_SIMD) void render_kernel(const RenderParams P, const float4 *__restrict__ image,
                                                      unsigned long long *__restrict__ acc,
                                                      unsigned int *__restrict__ queue,
                                                      DevCounters *__restrict__ counters) {
@@ -154,10 +157,14 @@ template __global__ void RT_ISA_ONLY(const RenderParams, const float4 *__restric
 //   17  variant 16 with strict ownership                         24  variant 16 with its tables in global memory
 //   32  wave-level cluster votes      64  per-lane cluster lists through the two-level box hierarchy (round 1's default)
 //  128  per-lane cluster lists through the range tables (first half of round 2)
+// (the workgroup of variants 2 and 6: kernels.h)
+constexpr int headline_waves(int cull) { return big_group(false, true, false, cull, true) ? kBigGroupWaves : kGroupWaves; }
+constexpr int headline_wave_lds(int cull) { return kWaveAccBytes + (burst_starts(false, true, false, cull, true) ? kWaveSlabBytes : 0); }
+constexpr int headline_groups(int cull) { return big_group(false, true, false, cull, true) ? kBigGroupsPerCu : 0; }
 static const KernelRow kRows[] = {
     // {{family, variant, ext, count}, CULL, instance}
-    {{K_PLAIN, 2, false}, 6, (const void *)&render_kernel<false, true, false, 6, false, true>},
-    {{K_PLAIN, 6, false}, 5, (const void *)&render_kernel<false, true, false, 5, false, true>},
+    {{K_PLAIN, 2, false}, 6, (const void *)&render_kernel<false, true, false, 6, false, true>, headline_waves(6), headline_wave_lds(6), headline_groups(6)},
+    {{K_PLAIN, 6, false}, 5, (const void *)&render_kernel<false, true, false, 5, false, true>, headline_waves(5), headline_wave_lds(5), headline_groups(5)},
     {{K_PLAIN, 36, false}, 7, (const void *)&render_kernel<false, true, false, 7, false, false>},
     {{K_PLAIN, 44, false}, 7, (const void *)&render_kernel<false, true, true, 7, false, false>},
     {{K_PLAIN, 16, false}, 0, (const void *)&render_kernel<false, true, false, 0, false, false>},
@@ -219,19 +226,19 @@ const KernelRow *find_kernel(const KernelKey &key) {
     return nullptr;
 }
 
-// one persistent launch of `grid` workgroups of 256 (an error surfaces in the caller's hipGetLastError)
+// one persistent launch of `grid` workgroups of the row's size (an error surfaces in the caller's hipGetLastError)
 void launch_kernel(const KernelRow &row, const RenderParams &P, const void *image, unsigned long long *acc, unsigned int *queue,
                    DevCounters *counters, size_t lds_bytes, unsigned grid, hipStream_t stream) {
     void *args[] = {const_cast<RenderParams *>(&P), &image, &acc, &queue, &counters};
-    (void)hipLaunchKernel(row.fn, dim3(grid), dim3(256), args, lds_bytes, stream);
+    (void)hipLaunchKernel(row.fn, dim3(grid), dim3(group_threads(row)), args, lds_bytes, stream);
 }
 
 // resident workgroups per CU of an instance at this dynamic-LDS size (advisory; an over-estimate only
 // leaves late workgroups that find the queue empty)
 int blocks_per_cu(const KernelRow &row, size_t lds_bytes) {
     int n = 0;
-    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, row.fn, 256, lds_bytes);
-    return (e == hipSuccess && n > 0) ? n : 4;
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, row.fn, (int)group_threads(row), lds_bytes);
+    return (e == hipSuccess && n > 0) ? n : (row.groups_per_cu > 0 ? row.groups_per_cu : 4);
 }
 
 // lets the instance be launched with more than 64 KB of dynamic LDS; nonzero: refused

@@ -10,7 +10,9 @@ usage: tools/isa_stats.py [--inst "false,true,false,6,false,true"] [--waves 7] [
        tools/isa_stats.py --kernel "trace_kernel<false,7>"                    (ray queries: <SCALAR, CULL>)
 --inst ARGS is short for --kernel "render_kernel<ARGS>"; the default instance is the headline kernel (sphere-only x-z grid walk,
 variant 0 -> 2 on RTIOW).  The families whose register budget is not --waves take theirs after "--":
--DRT_NEE_WAVES_PER_SIMD=N (render_nee_kernel, render_env_kernel with NEE), -DRT_MEDIA_WAVES_PER_SIMD=N, -DRT_MOTION_WAVES_PER_SIMD=N."""
+-DRT_NEE_WAVES_PER_SIMD=N (render_nee_kernel, render_env_kernel with NEE), -DRT_MEDIA_WAVES_PER_SIMD=N, -DRT_MOTION_WAVES_PER_SIMD=N,
+and the two big-workgroup instances of render_kernel (<false,true,false,6,false,true> and <false,true,false,5,false,true>, csrc/kernels.h)
+-DRT_BIG_WAVES_PER_SIMD=N (default 8) with -DRT_BIG_WAVES=n waves per workgroup; -DRT_BIG_GROUPS=0 gives them the 4-wave shape and --waves."""
 import argparse, collections, os, re, subprocess, sys, tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
