@@ -502,10 +502,27 @@ int rt_scene_get_noise(const rt_scene *s, int texture, rt_noise *out);
  * lambertian, metal, dielectric, rough_metal, plastic, rough_glass and pbr; RT_ERR_ARG for an unknown material, a diffuse_light, a texture that
  * is not an RT_TEX_NOISE or a strength that is not finite.  texture = -1 or strength = 0 removes the bump.  A scene with one
  * runs the general (triangle / texture) kernels; a moving sphere whose material carries one is refused when rendered.
- * The bumps live beside the material table: rt_material is unchanged. */
+ * The bumps live beside the material table: rt_material is unchanged.  (RT_ERR_ARG too for a material that carries a normal
+ * map, below: a material takes one of the two.) */
 int rt_scene_set_bump(rt_scene *s, int material, int texture, float strength);
 /* the bump of `material` (either pointer may be NULL): texture -1 and strength 0 where it has none; RT_ERR_ARG: no such material */
 int rt_scene_get_bump(const rt_scene *s, int material, int *texture, float *strength);
+/* Tangent-space normal maps: the texel of image texture `texture` at the hit record's (u, v) (the nearest texel, as
+ * an image-textured material reads its colour) as a direction in the surface's tangent frame, on material `material`.
+ * Decoding: x = max((r8 - 128) / 127, -1), y from g8, z from b8 (byte 128 is 0, byte 255 is 1); a texel with r8 == g8 == 128 or
+ * z <= 0 leaves the normal alone.  R runs along +dp/du, G along +dp/dv of the primitive's own (u, v), B along the outward
+ * normal.  With n the face-turned shading normal, g the face-turned geometric one, d the ray's direction, sigma = +1 on a front
+ * hit, -1 on a back hit, T and B the primitive's dp/du and dp/dv:  T' = unit(T - (T.n) n),  B' = unit(B - (B.n) n - (B.T') T')
+ * (zero or not finite: cross(sigma n, T')),  b = sigma scale (x T' + y B') + z n,  n' = b / |b|;  n' replaces n where it is
+ * finite, n'.g > 0 and n'.d < 0; T' zero or not finite (a sphere's pole, a triangle without usable uv): n stays.  The hit
+ * point, front, t, (u, v), emitter hits and the ray queries stay geometric.  On every material but diffuse_light; RT_ERR_ARG for
+ * an unknown material, a diffuse_light, a texture that is not an RT_TEX_IMAGE, a scale that is not finite, or a material that
+ * carries a bump (and rt_scene_set_bump refuses a material that carries a map).  texture = -1 or scale = 0 removes the map.
+ * A moving sphere whose material carries one is refused when rendered.  The maps live beside the material table:
+ * rt_material is unchanged. */
+int rt_scene_set_normal_map(rt_scene *s, int material, int texture, float scale);
+/* the normal map of `material` (either pointer may be NULL): texture -1 and scale 0 where it has none; RT_ERR_ARG: no such material */
+int rt_scene_get_normal_map(const rt_scene *s, int material, int *texture, float *scale);
 /* Quads and boxes.  quad(Q, u, v, material): the parallelogram Q, Q + u, Q + u + v, Q + v, whose normal is along
  * u x v; then rotate(axis, degrees) then translate(offset), the cylinder's pair and order (pass NULL to skip either).  The
  * transform is applied to Q, u, v here, in fp64, and rounded once: what is stored, rendered and written to JSON is the quad it
@@ -587,6 +604,8 @@ int rt_scene_get_textures(const rt_scene *s, rt_texture *out, int cap);   /* -> 
  * record.  No field here says where they begin: a scene without a noise texture has none and packs to the bytes it did.
  * The bumps, DESIGN 7p, follow them the same way: one record per bumped material, {offset of the height texture's noise
  * record, strength, 0, 0}, whose offset the material holds in the fourth word of its third record; none without a bump.
+ * The normal maps, DESIGN 7u, follow the bumps: one record per mapped material, {word offset of the map's texels, rows, cols,
+ * scale}; the material holds MINUS its offset in that same word; none without a map.
  * The pbr materials' side records, DESIGN 7t, follow those: three records per pbr material, in material order -- {metallic
  * factor, roughness factor, 0, 0}, then the map's texture as a material's second and third record hold theirs (no map: solid
  * white) -- whose offset the material holds in the second word of its first record; none without a pbr material.) */

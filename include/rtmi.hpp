@@ -86,6 +86,8 @@ struct material {
     float fuzz = 0, ir = 1;
     std::shared_ptr<mytexture> bump;  // bump mapping: a noise texture as the height field, null: none
     float bump_strength = 0;
+    std::shared_ptr<mytexture> normal_map;  // a tangent-space normal map: an image texture, null: none
+    float normal_scale = 0;
     std::shared_ptr<mytexture> map;  // pbr: the metallic-roughness map (G scales the roughness, B the metalness), null: none
 };
 using material_ptr = std::shared_ptr<material>;
@@ -148,6 +150,14 @@ inline material_ptr diffuse_light(color c) { return diffuse_light(solid_color(c)
 inline material_ptr bumped(const material_ptr &m, std::shared_ptr<mytexture> height, float strength) {
     auto b = std::make_shared<material>(*m);
     b->bump = std::move(height), b->bump_strength = strength;
+    return b;
+}
+
+// normal mapping: a copy of `m` whose shading normal is the texel of `map` (an image texture) read in the surface's
+// tangent frame, its tangential part x `scale`.  Any material but diffuse_light, and not one that is bumped.
+inline material_ptr normal_mapped(const material_ptr &m, std::shared_ptr<mytexture> map, float scale = 1.0f) {
+    auto b = std::make_shared<material>(*m);
+    b->normal_map = std::move(map), b->normal_scale = scale;
     return b;
 }
 
@@ -573,6 +583,7 @@ private:
         }
         if (id < 0) throw error(-id, "material");
         if (m->bump) check(rt_scene_set_bump(s_, id, texture_id(m->bump), m->bump_strength), "bump");
+        if (m->normal_map) check(rt_scene_set_normal_map(s_, id, texture_id(m->normal_map), m->normal_scale), "normal map");
         if (m->type == RT_MAT_PBR && m->map) check(rt_scene_set_pbr_map(s_, id, texture_id(m->map)), "pbr map");
         mats_.emplace_back(m, id);
         return id;

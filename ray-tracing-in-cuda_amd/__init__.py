@@ -264,6 +264,8 @@ _sig("rt_scene_add_noise_texture", C.c_int, _p, _f3, _f3, C.POINTER(Noise))
 _sig("rt_scene_get_noise", C.c_int, _p, C.c_int, C.POINTER(Noise))
 _sig("rt_scene_set_bump", C.c_int, _p, C.c_int, C.c_int, C.c_float)
 _sig("rt_scene_get_bump", C.c_int, _p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float))
+_sig("rt_scene_set_normal_map", C.c_int, _p, C.c_int, C.c_int, C.c_float)
+_sig("rt_scene_get_normal_map", C.c_int, _p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float))
 assert _lib.rt_struct_size(24) == C.sizeof(Noise) == 24
 _sig("rt_scene_add_triangle", C.c_int, _p, _f3, _f3, _f3, _f3, _f3, _f3, C.c_int)
 _sig("rt_scene_add_quad", C.c_int, _p, _f3, _f3, _f3, C.c_int, _f3, C.c_float, _f3)
@@ -363,7 +365,7 @@ C_SYMBOLS = [
     "rt_scene_new", "rt_scene_set_background", "rt_scene_set_camera", "rt_scene_add_solid_color",
     "rt_scene_add_checker", "rt_scene_add_lambertian", "rt_scene_add_metal", "rt_scene_add_dielectric",
     "rt_scene_add_rough_metal", "rt_scene_add_plastic", "rt_scene_add_rough_glass", "rt_scene_add_noise_texture", "rt_scene_get_noise",
-    "rt_scene_set_bump", "rt_scene_get_bump", "rt_scene_add_pbr", "rt_scene_set_pbr_map", "rt_scene_get_pbr_map",
+    "rt_scene_set_bump", "rt_scene_get_bump", "rt_scene_set_normal_map", "rt_scene_get_normal_map", "rt_scene_add_pbr", "rt_scene_set_pbr_map", "rt_scene_get_pbr_map",
     "rt_scene_add_diffuse_light", "rt_scene_add_sphere", "rt_scene_add_rect", "rt_scene_add_cylinder",
     "rt_scene_add_image_texture", "rt_scene_add_image_texture_file", "rt_scene_get_image", "rt_scene_add_triangle",
     "rt_scene_add_quad", "rt_scene_add_box", "rt_scene_add_obj", "rt_scene_add_triangle_normals", "rt_scene_add_obj_normals", "rt_set_mesh_normals_override",
@@ -626,6 +628,18 @@ class Scene:
         """(texture, strength) of the material's bump, or None."""
         t, k = C.c_int(), C.c_float()
         _check(_lib.rt_scene_get_bump(self._h, int(material), C.byref(t), C.byref(k)), "rt_scene_get_bump")
+        return None if t.value < 0 else (int(t.value), float(k.value))
+
+    def set_normal_map(self, material: int, texture: int, scale: float = 1.0) -> None:
+        """Normal mapping: image texture `texture` read at the hit's (u, v) as a direction in the surface's tangent
+        frame (R along +dp/du, G along +dp/dv, B along the outward normal) on `material`; the tangential part x `scale`.  Any
+        material but a diffuse_light, and not a bumped one; texture -1 or scale 0 removes it."""
+        _check(_lib.rt_scene_set_normal_map(self._h, int(material), int(texture), float(scale)), "rt_scene_set_normal_map")
+
+    def normal_map(self, material: int):
+        """(texture, scale) of the material's normal map, or None."""
+        t, k = C.c_int(), C.c_float()
+        _check(_lib.rt_scene_get_normal_map(self._h, int(material), C.byref(t), C.byref(k)), "rt_scene_get_normal_map")
         return None if t.value < 0 else (int(t.value), float(k.value))
 
     def get_image(self, texture: int) -> np.ndarray:

@@ -396,6 +396,24 @@ int rt_scene_get_bump(const rt_scene *s, int material, int *texture, float *stre
     return RT_OK;
 }
 
+// normal maps: a side table beside the materials, as the bumps are
+int rt_scene_set_normal_map(rt_scene *s, int material, int texture, float scale) {
+    if (bad_scene(s, "rt_scene_set_normal_map")) return RT_ERR_ARG;
+    return set_normal_map(s->s, material, texture, scale, "rt_scene_set_normal_map") ? RT_OK : RT_ERR_ARG;
+}
+
+int rt_scene_get_normal_map(const rt_scene *s, int material, int *texture, float *scale) {
+    if (bad_scene(s, "rt_scene_get_normal_map")) return RT_ERR_ARG;
+    if (material < 0 || material >= (int)s->s.mats.size()) {
+        set_error("rt_scene_get_normal_map: unknown material %d (have %zu)", material, s->s.mats.size());
+        return RT_ERR_ARG;
+    }
+    const SceneNormalMap *b = scene_normal_map(s->s, material);
+    if (texture) *texture = b ? b->texture : -1;
+    if (scale) *scale = b ? b->scale : 0.0f;
+    return RT_OK;
+}
+
 static bool bad_material(rt_scene *s, int material) {
     if (material < 0 || material >= (int)s->s.mats.size()) {
         set_error("object references material %d (have %zu)", material, s->s.mats.size());
@@ -623,7 +641,7 @@ rt_scene *rt_scene_dna(const rt_scene *base, double angle) {
     if (base) {
         sc = base->s;
         sc.dev.reset();
-        sc.prims.clear(), sc.xforms.clear(), sc.mats.clear(), sc.texs.clear(), sc.noise.clear(), sc.bumps.clear(), sc.pbr_maps.clear();
+        sc.prims.clear(), sc.xforms.clear(), sc.mats.clear(), sc.texs.clear(), sc.noise.clear(), sc.bumps.clear(), sc.pbr_maps.clear(), sc.normal_maps.clear();
     } else {  // gpu-version/basic_scene.json
         sc.width = 1600, sc.height = 900, sc.spp = 100, sc.max_depth = 50;
         sc.background[0] = 0.0005f, sc.background[1] = 0.0007f, sc.background[2] = 0.00099f;

@@ -29,6 +29,9 @@
 //     bump    [nb]  1 x float4   (only with bumped materials; behind the noise records) per bumped material, in
 //                                material order: {offset of the height texture's noise record (bits), strength, 0, 0}.  Such a
 //                                material holds its bump record's offset (bits) in c1.w, the word no kind uses; 0: no bump
+//     nmap    [nn]  1 x float4   (only with normal-mapped materials; behind the bump records) per mapped material, in
+//                                material order: {word offset of the map's texels (bits), rows (bits), cols (bits), scale}.  Such a
+//                                material holds MINUS its record's offset (bits) in c1.w: a bump or a map, never both
 //   LIGHT part (only with light sampling on and at least one sampled emitter; global memory, read by the light-sampling kernels)
 //     light   [nl]  7 x float4   {shape(bits): 0 sphere, 1 rect, 2 cylinder, 4 triangle, 5 quad, grouped id(bits), selection probability, 1/area}
 //                                {emission even.rgb, checker(bits)} {emission odd.rgb, 0}, then the geometry:
@@ -143,6 +146,10 @@ struct ItemParams {
     int32_t tile_rotate;  // how the tiles are dealt out to the shards (rt_opts.tile_rotate; shard.h)
     int32_t n_list = 0;   // 0: every tile of the shard; else the length of the tile list
 };
+
+// RenderParams::flags carries the scene's RT_FLAG_* bits (include/rtmi.h) and, above them, what the launch path adds:
+// "this scene has a normal map" (DESIGN 7u).  A kernel argument, so the test is a scalar branch around the whole step
+#define RT_PFLAG_NORMAL_MAPS (1u << 16)
 
 // kernel parameter block (passed by value: lands in SGPRs / the kernarg segment)
 struct RenderParams {

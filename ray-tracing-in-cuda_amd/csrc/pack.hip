@@ -684,9 +684,10 @@ int lay_out_hot(RenderParams &L, const Grid &g) {
 // (rt_motion.h; 0: no moving spheres); off_normals: of the NORMALS part (device_scene.h; 0: no triangle has vertex normals).  -1: the environment's words would not fit an int32 offset; -2: 2^28 sphere slots or more.
 // off_noise: the first record of the noise textures' parameters (device_scene.h; 0: the scene has no noise texture).
 // off_bump: the first bump record (device_scene.h; 0: no material carries a bump).
+// off_nmap: the first normal-map record (device_scene.h; 0: no material carries a normal map).
 // off_pbr: the first side record of the pbr materials (device_scene.h, MK_PBR; 0: the scene has none).
 int lay_out_image(RenderParams &L, const Grid &g, const Scene &s, std::vector<int> &image_word, int &off_media, int &off_motion,
-                  int &off_normals, int &off_noise, int &off_bump, int &off_pbr) {
+                  int &off_normals, int &off_noise, int &off_bump, int &off_nmap, int &off_pbr) {
     // The kernels read the winner's cold record at a 32-bit BYTE offset from the cold table, 16 x its slot (rec_at,
     // render_device.h): the slots end below 2^28.  This is the check that bound rests on; pack_scene refuses with RT_ERR_LIMIT.
     if ((long long)L.ns >= RT_MAX_SPHERE_SLOTS) return -2;
@@ -737,7 +738,14 @@ int lay_out_image(RenderParams &L, const Grid &g, const Scene &s, std::vector<in
             if (!off_bump) off_bump = off;
             ++off;
         }
-    // the pbr materials' side records: three rows each, in material order, behind the bump records; none: not a byte
+    // the normal-map records: one per mapped material, in material order, behind the bump records; none: not a byte
+    off_nmap = 0;
+    for (const SceneNormalMap &b : s.normal_maps)
+        if (b.texture >= 0) {
+            if (!off_nmap) off_nmap = off;
+            ++off;
+        }
+    // the pbr materials' side records: three rows each, in material order, behind those; none: not a byte
     off_pbr = 0;
     for (const rt_material &m : s.mats)
         if (m.type == RT_MAT_PBR) {
@@ -1048,6 +1056,19 @@ void write_bumps(float *I, const Scene &s, int off_bump, const std::vector<int> 
     }
 }
 
+// the normal-map records {word offset of the image's texels (bits), rows (bits), cols (bits), scale} -- the first three as an
+// image-textured material's second row holds them; bump_rec[m] = MINUS material m's record (a material carries a bump or a map)
+void write_normal_maps(float *I, const Scene &s, int off_nmap, const std::vector<int> &image_word, std::vector<int> &bump_rec) {
+    int at = off_nmap;
+    for (size_t m = 0; m < s.normal_maps.size() && m < s.mats.size(); ++m) {
+        if (s.normal_maps[m].texture < 0) continue;
+        const size_t im = (size_t)s.texs[(size_t)s.normal_maps[m].texture].c0[0];
+        float *q = rec4(I, at);
+        q[0] = bits(image_word[im]), q[1] = bits(s.images[im].rows), q[2] = bits(s.images[im].cols), q[3] = s.normal_maps[m].scale;
+        bump_rec[m] = -(at++);
+    }
+}
+
 void write_materials(float *I, const RenderParams &L, const Scene &s, const SphereSlots &S, const OtherPrims &O,
                      const std::vector<int> &image_word, const std::vector<int> &noise_rec, const std::vector<int> &bump_rec, int off_pbr) {
     // a noise texture under a material: the two colours where a checker keeps them, the record's offset in c0.w
@@ -1156,7 +1177,8 @@ void write_materials(float *I, const RenderParams &L, const Scene &s, const Sphe
         default: break;
         }
         q[0] = bits(kind);
-        // a bump: its record's offset in c1.w, the one word no kind above uses; 0: none
+        // a bump: its record's offset in c1.w, the one word no kind above uses; 0: none.  (A normal map, DESIGN 7u:
+        // minus its record's offset)
         if (bump_rec[(size_t)k]) q[11] = bits(bump_rec[(size_t)k]);
     }
     // The material kind of every sphere, rect and cylinder sits in its cold record too: the shading then knows after ONE
@@ -1339,7 +1361,8 @@ bool pack_round(const Scene &s, std::vector<char> &forced, std::vector<float> &i
         default: rec.push_back((int)i); break;
         }
     }
-    // (a glossy material, DESIGN 7m, a noise texture, 7o, and a bump, 7p, run in the general kernels alone, as an image texture does)
+    // (a glossy material, DESIGN 7m, a noise texture, 7o, and a bump, 7p, run in the general kernels alone, as an image texture does;
+    // a normal map, 7u, is an image texture)
     const bool sphere_only = rec.empty() && cyl.empty() && tri.empty() && quad.empty() && s.images.empty() && !scene_has_glossy(s) && !scene_has_noise(s) && !scene_has_bump(s);
     const SphereSlots S = sphere_slots(s, std::move(sph), forced);
     const OtherPrims O = other_prims(s, S, std::move(rec), std::move(cyl), std::move(tri), std::move(quad), forced);
@@ -1370,8 +1393,8 @@ bool pack_round(const Scene &s, std::vector<char> &forced, std::vector<float> &i
     L.grid_sheet = (!g.cells.empty() && g.n[1] == 1 && !g.wide) ? 1 : 0;
     std::vector<int> image_word;
     std::vector<int> noise_rec, bump_rec;
-    int off_media = 0, off_motion = 0, off_normals = 0, off_noise = 0, off_bump = 0, off_pbr = 0;
-    const int records = lay_out_image(L, g, s, image_word, off_media, off_motion, off_normals, off_noise, off_bump, off_pbr);
+    int off_media = 0, off_motion = 0, off_normals = 0, off_noise = 0, off_bump = 0, off_nmap = 0, off_pbr = 0;
+    const int records = lay_out_image(L, g, s, image_word, off_media, off_motion, off_normals, off_noise, off_bump, off_nmap, off_pbr);
     if (records < 0) {
         (records == -2 ? note.too_many_slots : note.too_large) = true;
         return true;
@@ -1395,6 +1418,7 @@ bool pack_round(const Scene &s, std::vector<char> &forced, std::vector<float> &i
     write_texels(I, s, image_word);
     write_noise(I, s, off_noise, noise_rec);
     write_bumps(I, s, off_bump, noise_rec, bump_rec);
+    write_normal_maps(I, s, off_nmap, image_word, bump_rec);
     write_materials(I, L, s, S, O, image_word, noise_rec, bump_rec, off_pbr);
     if (L.nl > 0) write_lights(I, L, s, S, O, lights);
     if (s.env) write_environment(I, L, s);

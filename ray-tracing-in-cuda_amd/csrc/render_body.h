@@ -1218,7 +1218,14 @@
                 // other texture of the reference ignores them, and acos / atan2 per candidate hit (object.cuh:87-93)
                 // would be the most expensive part of sphere::hit
                 // (QUERY: for every hit, they are part of the record)
-                const bool want_uv = EXT && (QUERY || pbr_uv || (!noise_tex && (kind == MK_LAMBERT_IMAGE || kind == MK_LIGHT_IMAGE || kind == MK_PLASTIC_IMAGE)));
+                // (and where the material carries a normal map, DESIGN 7u: a negative word where a bump's record offset sits)
+                // (has_maps: a bit of the parameter block, so a scene without maps takes one scalar branch around all of it)
+                bool nmap_uv = false;
+                const bool has_maps = EXT && !QUERY && (P.flags & RT_PFLAG_NORMAL_MAPS) != 0u;
+                if constexpr (EXT && !QUERY) {
+                    if (has_maps) nmap_uv = __float_as_int(M[2].w) < 0 && !(MOTION && mot_i >= 0);
+                }
+                const bool want_uv = EXT && (QUERY || pbr_uv || nmap_uv || (!noise_tex && (kind == MK_LAMBERT_IMAGE || kind == MK_LIGHT_IMAGE || kind == MK_PLASTIC_IMAGE)));
                 // a triangle's area weights (hittable.py:54-58), stated once: of the plane point for (u, v), and -- smooth shading,
                 // DESIGN 7l -- of the vertex normals.  The NORMALS part (device_scene.h) is there only when the scene has a triangle
                 // with vertex normals: where it lies is a wave-uniform word of the camera block, as for the media and the movers.
@@ -1320,7 +1327,7 @@
                         active = false;
                         kind = -1;
                     } else
-                    if (!pbr_uv) image_texel(image, M[1], tu, tv, tex_r, tex_g, tex_b);
+                    if (!pbr_uv && (kind == MK_LAMBERT_IMAGE || kind == MK_LIGHT_IMAGE || kind == MK_PLASTIC_IMAGE) && !noise_tex) image_texel(image, M[1], tu, tv, tex_r, tex_g, tex_b);
                 }
                 // The solid textures' values: a noise texture under a lambertian, an emitter or a plastic, and both textures of a
                 // pbr material -- ONE copy of the noise code: a second pass of the same call site evaluates a pbr material's
@@ -1365,7 +1372,8 @@
                         }
                     }
                 }
-                // a bump: the material's noise height field tilts the shading normal, behind the smooth-shading normal
+                // a bump or a normal map (7u; a material carries one of them): the material's noise height field, or its
+                // map's texel in the tangent frame, tilts the shading normal, behind the smooth-shading normal
                 // and the (u, v) above (a sphere's read its normal) and before everything that shades: the feature pass, the
                 // scatter step, the light sample's cosine and frame.  The hit point, front, t and an emitter's normal (a
                 // diffuse_light takes no bump) stay geometric; a query never comes here.
@@ -1378,8 +1386,42 @@
                             const float tnx = tri[RT_TRI_STRIDE * k].w, tny = tri[RT_TRI_STRIDE * k + 1].w, tnz = tri[RT_TRI_STRIDE * k + 2].w;
                             gnx = front ? tnx : -tnx, gny = front ? tny : -tny, gnz = front ? tnz : -tnz;
                         }
-                        const float4 nb = bump_normal(image, boff, front, nx, ny, nz, gnx, gny, gnz, dx, dy, dz, px, py, pz);
-                        nx = nb.x, ny = nb.y, nz = nb.z;
+                        if (boff > 0) {
+                            const float4 nb = bump_normal(image, boff, front, nx, ny, nz, gnx, gny, gnz, dx, dy, dz, px, py, pz);
+                            nx = nb.x, ny = nb.y, nz = nb.z;
+                        } else if (has_maps) {
+                            // a normal map (rt_tangent.h): the word is minus the offset of the record {texel word
+                            // offset, rows, cols, scale}.  The texel at the (u, v) above, then -- only where it tilts anything --
+                            // the raw tangents dp/du, dp/dv of the winner's primitive type from the records the blocks above read
+                            const float4 mr = image[-boff];
+                            float mx, my, mz;
+                            if (tangent_decode(image_texel_word(image, mr, tu, tv), mx, my, mz)) {
+                                float Tx, Ty, Tz, Bx, By, Bz;
+                                if (best_id < ns) {
+                                    tangent_sphere(front ? nx : -nx, front ? ny : -ny, front ? nz : -nz, Tx, Ty, Tz, Bx, By, Bz);
+                                } else if (best_id < ns + nr) {
+                                    const int j = best_id - ns;
+                                    const float4 q0r = rect[2 * j];
+                                    tangent_rect(__float_as_int(rect[2 * j + 1].y), q0r.x, q0r.y, q0r.z, q0r.w, Tx, Ty, Tz, Bx, By, Bz);
+                                } else if (best_id < ns + nr + nc) {
+                                    const int k = best_id - ns - nr;
+                                    const float4 r2 = cyl[RT_CYL_STRIDE * k + 2], pr = cyl[RT_CYL_STRIDE * k + 3];
+                                    tangent_cylinder(r2.x, r2.y, r2.z, front ? nx : -nx, front ? ny : -ny, front ? nz : -nz, pr.y, pr.z, Tx, Ty, Tz, Bx, By, Bz);
+                                } else {
+                                    const int k = best_id - ns - nr - nc;
+                                    const float4 r0 = tri[RT_TRI_STRIDE * k], r1 = tri[RT_TRI_STRIDE * k + 1], r2 = tri[RT_TRI_STRIDE * k + 2];
+                                    if (k >= nt) {  // a quad's record: {Q, n.x} {A, n.y} {B, n.z}
+                                        tangent_quad(r0.w, r1.w, r2.w, r1.x, r1.y, r1.z, r2.x, r2.y, r2.z, Tx, Ty, Tz, Bx, By, Bz);
+                                    } else {
+                                        const float4 c0 = image[P.off_tri_cold + 2 * k], c1 = image[P.off_tri_cold + 2 * k + 1];
+                                        tangent_triangle(r0.x, r0.y, r0.z, r1.x, r1.y, r1.z, r2.x, r2.y, r2.z, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w, Tx, Ty,
+                                                         Tz, Bx, By, Bz);
+                                    }
+                                }
+                                const float4 nb = mapped_normal(front, mr.w, nx, ny, nz, gnx, gny, gnz, dx, dy, dz, Tx, Ty, Tz, Bx, By, Bz, mx, my, mz);
+                                nx = nb.x, ny = nb.y, nz = nb.z;
+                            }
+                        }
                     }
                 }
                 if (COUNT) {

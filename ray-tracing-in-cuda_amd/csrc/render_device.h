@@ -248,6 +248,7 @@ __device__ __forceinline__ unsigned long long radiance_to_fixed(float v) {
 #include "rt_noise.h"
 #include "rt_quad.h"
 #include "rt_lights.h"
+#include "rt_tangent.h"
 namespace rtmi {
 
 // a noise texture's colour at the point p: q1 = {c0, offset of the noise record (bits)}, q2 = {c1, _} of the
@@ -291,6 +292,26 @@ float4 bump_normal(const float4 *__restrict__ image, int boff, bool front, float
     noise_gradient((int)(packed & 3u), nr.x, (int)(packed >> 4) & 15, __float_as_uint(nr.z), (int)(packed >> 2) & 3, nr.y, px, py, pz, Gx, Gy, Gz);
     noise_bump(nx, ny, nz, gnx, gny, gnz, dx, dy, dz, front ? br.y : -br.y, Gx, Gy, Gz, [](float x) { return rt_sqrtf(x); });  // (the per-lane root, as the glossy materials')
     const float4 n = {nx, ny, nz, 0.0f};  // (by value: in registers, where three references would go through scratch)
+    return n;
+}
+
+// a normal map's texel word: image_texel's nearest-texel lookup, with its row and column convention, of the record
+// mr = {texel word offset (bits), rows (bits), cols (bits), scale} -> r8 | g8 << 8 | b8 << 16
+__device__ __forceinline__ uint32_t image_texel_word(const float4 *__restrict__ image, const float4 mr, float u, float v) {
+    const int rows = __float_as_int(mr.y), cols = __float_as_int(mr.z);
+    const int x = min((int)((u - floorf(u)) * (float)rows), rows - 1);
+    const int y = min((int)((v - floorf(v)) * (float)cols), cols - 1);
+    return reinterpret_cast<const uint32_t *>(image)[__float_as_int(mr.x) + x * cols + y];
+}
+
+// the mapped shading normal (the rule: rt_tangent.h, tangent_normal) from the raw tangents (T, B) and the decoded
+// texel (x, y, z); arguments as bump_normal's.  -> n' where the rule accepts it, else n.  Inlined into the winner section, its
+// one caller, as bump_normal is
+__device__ __forceinline__ float4 mapped_normal(bool front, float s, float nx, float ny, float nz, float gnx, float gny, float gnz, float dx,
+                                                float dy, float dz, float tx, float ty, float tz, float bx, float by, float bz, float x, float y,
+                                                float z) {
+    tangent_normal(nx, ny, nz, gnx, gny, gnz, dx, dy, dz, front, s, tx, ty, tz, bx, by, bz, x, y, z, [](float v) { return rt_sqrtf(v); });
+    const float4 n = {nx, ny, nz, 0.0f};
     return n;
 }
 

@@ -629,6 +629,7 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     ext = ext || scene_has_glossy(s);  // (the glossy materials' code sits in those builds alone)
     ext = ext || scene_has_noise(s);   // (and the noise textures')
     ext = ext || scene_has_bump(s);    // (and the bumps')
+    ext = ext || scene_has_normal_map(s);  // (and the normal maps', DESIGN 7u -- an image texture, so it is set already)
     const bool force_ext = knob_set("RTMI_FORCE_EXT");  // measurement: the EXT builds on scenes that do not need them
     const int device = o ? o->device : 0;
     DeviceScope scope;
@@ -666,7 +667,7 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     // ---- kernel parameters
     RenderParams P = cache.layout;
     for (int i = 0; i < 3; ++i) P.background[i] = s.background[i];
-    P.flags = s.flags;
+    P.flags = s.flags | (scene_has_normal_map(s) ? RT_PFLAG_NORMAL_MAPS : 0u);
     P.rr_p = feature >= 0 ? 0.0f : s.rr_p;  // (a feature sample ends at its first query: no roulette, any max_depth)
     P.width = s.width, P.height = s.height, P.max_depth = feature >= 0 ? 1 : s.max_depth;
     P.inv_wm1 = 1.0f / (float)(s.width - 1), P.inv_hm1 = 1.0f / (float)(s.height - 1);  // IEEE fp32 divisions, as the checker's
@@ -743,6 +744,12 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
             if (scene_bump(s, m.material)) {
                 set_error("this scene has a moving sphere whose material carries a bump, which no kernel renders (the relief would swim "
                           "through the ball): remove the bump or give the mover another material");
+                return RT_ERR_ARG;
+            }
+        for (const rt_moving_sphere &m : s.movers)
+            if (scene_normal_map(s, m.material)) {
+                set_error("this scene has a moving sphere whose material carries a normal map, which no kernel renders (as a bump's, "
+                          "the relief would swim through the ball): remove the map or give the mover another material");
                 return RT_ERR_ARG;
             }
         if (!find_kernel({K_MOTION, variant, true})) {

@@ -397,12 +397,56 @@ static bool bump_ok(const Scene &s, int material, int texture, float strength, b
 
 bool set_bump(Scene &s, int material, int texture, float strength, const char *where) {
     if (!bump_ok(s, material, texture, strength, true, where)) return false;
+    if (texture != -1 && strength != 0.0f && scene_normal_map(s, material)) {  // (one of the two)
+        set_error("%s: material %d carries a normal map; a material takes a bump or a normal map, not both", where, material);
+        return false;
+    }
     if (texture == -1 || strength == 0.0f) {  // removes; the table ends at the last bumped material
         if ((size_t)material < s.bumps.size()) s.bumps[(size_t)material] = SceneBump();
         while (!s.bumps.empty() && s.bumps.back().texture < 0) s.bumps.pop_back();
     } else {
         if (s.bumps.size() <= (size_t)material) s.bumps.resize((size_t)material + 1);
         s.bumps[(size_t)material].texture = texture, s.bumps[(size_t)material].strength = strength;
+    }
+    s.touch();
+    return true;
+}
+
+// normal maps: the argument rules of a map, shared by the C call, the JSON reader and scene_validate.
+// none_ok: texture -1 (no map) passes
+static bool normal_map_ok(const Scene &s, int material, int texture, float scale, bool none_ok, const char *where) {
+    if (material < 0 || material >= (int)s.mats.size()) {
+        set_error("%s: unknown material %d (have %zu)", where, material, s.mats.size());
+        return false;
+    }
+    if (s.mats[(size_t)material].type == RT_MAT_DIFFUSE_LIGHT) {
+        set_error("%s: material %d is a diffuse_light, which takes no normal map", where, material);
+        return false;
+    }
+    if (!(std::fabs(scale) < INFINITY)) {  // (a NaN fails the comparison)
+        set_error("%s: normal map scale must be finite (got %g)", where, (double)scale);
+        return false;
+    }
+    if (none_ok && texture == -1) return true;
+    if (texture < 0 || texture >= (int)s.texs.size() || s.texs[(size_t)texture].type != RT_TEX_IMAGE) {
+        set_error("%s: normal map texture %d is not an image texture", where, texture);
+        return false;
+    }
+    if (scale != 0.0f && scene_bump(s, material)) {  // (scale 0 removes, as set_bump's strength 0: removing is always allowed)
+        set_error("%s: material %d carries a bump; a material takes a bump or a normal map, not both", where, material);
+        return false;
+    }
+    return true;
+}
+
+bool set_normal_map(Scene &s, int material, int texture, float scale, const char *where) {
+    if (!normal_map_ok(s, material, texture, scale, true, where)) return false;
+    if (texture == -1 || scale == 0.0f) {  // removes; the table ends at the last mapped material
+        if ((size_t)material < s.normal_maps.size()) s.normal_maps[(size_t)material] = SceneNormalMap();
+        while (!s.normal_maps.empty() && s.normal_maps.back().texture < 0) s.normal_maps.pop_back();
+    } else {
+        if (s.normal_maps.size() <= (size_t)material) s.normal_maps.resize((size_t)material + 1);
+        s.normal_maps[(size_t)material].texture = texture, s.normal_maps[(size_t)material].scale = scale;
     }
     s.touch();
     return true;
@@ -481,6 +525,12 @@ int scene_validate(const Scene &s) {
         char where[32];
         snprintf(where, sizeof where, "material %zu", i);
         if (!bump_ok(s, (int)i, s.bumps[i].texture, s.bumps[i].strength, false, where)) return RT_ERR_SCENE;
+    }
+    for (size_t i = 0; i < s.normal_maps.size(); ++i) {
+        if (s.normal_maps[i].texture < 0) continue;
+        char where[32];
+        snprintf(where, sizeof where, "material %zu", i);
+        if (!normal_map_ok(s, (int)i, s.normal_maps[i].texture, s.normal_maps[i].scale, false, where)) return RT_ERR_SCENE;
     }
     for (size_t i = 0; i < s.pbr_maps.size(); ++i) {
         if (s.pbr_maps[i] < 0) continue;
@@ -1313,6 +1363,21 @@ int scene_from_json(const char *text, size_t len, Scene &s, const char *base_dir
                     bump_k = (float)r.num(*bump, "strength", bw);
                 }
             }
+            // a normal map on any material but an emitter: {"texture": <image texture>, "scale": <number, default 1>}
+            const JsonValue *nmap = m.find("normal_map");
+            int nmap_tex = -1;
+            float nmap_s = 1.0f;
+            if (nmap) {
+                if (!nmap->is_object()) r.fail("%s: \"normal_map\" must be an object", where);
+                else {
+                    char bw[128];
+                    snprintf(bw, sizeof bw, "%s: normal_map", where);
+                    for (const auto &kv : nmap->obj)
+                        if (kv.first != "texture" && kv.first != "scale") r.fail("%s: unknown field \"%s\"", bw, kv.first.c_str());
+                    nmap_tex = r.integer(*nmap, "texture", bw);
+                    if (nmap->find("scale")) nmap_s = (float)r.num(*nmap, "scale", bw);
+                }
+            }
             if (ty->str == "lambertian") {
                 rec.type = RT_MAT_LAMBERTIAN;
                 rec.texture = r.integer(m, "texture", where);
@@ -1325,7 +1390,7 @@ int scene_from_json(const char *text, size_t len, Scene &s, const char *base_dir
                 rec.fuzz = f < 1 ? f : 1;  // material.cuh:61
             } else if (ty->str == "rough_metal") {  // albedo is F0, fuzz holds the roughness
                 rec.type = RT_MAT_ROUGH_METAL;
-                only_keys(m, {"type", "albedo", "roughness", "bump"});
+                only_keys(m, {"type", "albedo", "roughness", "bump", "normal_map"});
                 double c[3];
                 r.vec3(m, "albedo", where, c);
                 for (int k = 0; k < 3; ++k) rec.albedo[k] = (float)c[k];
@@ -1333,14 +1398,14 @@ int scene_from_json(const char *text, size_t len, Scene &s, const char *base_dir
                 if (r.ok && !glossy_material_ok(rec, s.texs.size(), where)) r.ok = false;
             } else if (ty->str == "plastic") {  // texture is the body colour, fuzz the roughness, ir the coat's index
                 rec.type = RT_MAT_PLASTIC;
-                only_keys(m, {"type", "texture", "ior", "roughness", "bump"});
+                only_keys(m, {"type", "texture", "ior", "roughness", "bump", "normal_map"});
                 rec.texture = r.integer(m, "texture", where);
                 rec.ir = (float)r.num(m, "ior", where);
                 rec.fuzz = (float)r.num(m, "roughness", where);
                 if (r.ok && !glossy_material_ok(rec, s.texs.size(), where)) r.ok = false;
             } else if (ty->str == "pbr") {  // fuzz holds the roughness factor, albedo[0] the metallic factor
                 rec.type = RT_MAT_PBR;
-                only_keys(m, {"type", "texture", "metallic", "roughness", "ior", "metallic_roughness", "bump"});
+                only_keys(m, {"type", "texture", "metallic", "roughness", "ior", "metallic_roughness", "bump", "normal_map"});
                 rec.texture = r.integer(m, "texture", where);
                 rec.albedo[0] = (float)r.num(m, "metallic", where);
                 rec.fuzz = (float)r.num(m, "roughness", where);
@@ -1349,7 +1414,7 @@ int scene_from_json(const char *text, size_t len, Scene &s, const char *base_dir
                 if (r.ok && !glossy_material_ok(rec, s.texs.size(), where)) r.ok = false;
             } else if (ty->str == "rough_glass") {  // fuzz holds the roughness, albedo the absorption coefficient
                 rec.type = RT_MAT_ROUGH_GLASS;
-                only_keys(m, {"type", "ir", "roughness", "absorption", "tint", "tint_distance", "bump"});
+                only_keys(m, {"type", "ir", "roughness", "absorption", "tint", "tint_distance", "bump", "normal_map"});
                 rec.ir = (float)r.num(m, "ir", where);
                 rec.fuzz = (float)r.num(m, "roughness", where);
                 const bool has_tint = m.find("tint") || m.find("tint_distance");
@@ -1380,6 +1445,7 @@ int scene_from_json(const char *text, size_t len, Scene &s, const char *base_dir
             }
             s.mats.push_back(rec);
             if (r.ok && bump && !set_bump(s, (int)s.mats.size() - 1, bump_tex, bump_k, where)) r.ok = false;
+            if (r.ok && nmap && !set_normal_map(s, (int)s.mats.size() - 1, nmap_tex, nmap_s, where)) r.ok = false;
             if (r.ok && has_pbr_map && !set_pbr_map(s, (int)s.mats.size() - 1, pbr_map, where)) r.ok = false;  // (-1: no map)
         }
     }
@@ -1793,6 +1859,10 @@ std::string scene_to_json(const Scene &s) {
         if (const SceneBump *b = scene_bump(s, (int)i)) {  // (inside the material's object: before its closing brace)
             o.pop_back();
             o += ", \"bump\": {\"texture\": " + std::to_string(b->texture) + ", \"strength\": " + json_float(b->strength) + "}}";
+        }
+        if (const SceneNormalMap *b = scene_normal_map(s, (int)i)) {
+            o.pop_back();
+            o += ", \"normal_map\": {\"texture\": " + std::to_string(b->texture) + ", \"scale\": " + json_float(b->scale) + "}}";
         }
     }
     o += "\n  ]},\n";

@@ -54,6 +54,12 @@ struct SceneBump {
     float strength = 0.0f;
 };
 
+// a material's normal map: image texture `texture` read in the surface's tangent frame, its tangential part x `scale`
+struct SceneNormalMap {
+    int texture = -1;
+    float scale = 0.0f;
+};
+
 struct Scene {
     int width = 400, height = 225, spp = 100, max_depth = 50;
     float background[3] = {0, 0, 0};
@@ -75,6 +81,8 @@ struct Scene {
                                      // as `noise` is beside the textures, at most as long as the last bumped material's id + 1
     std::vector<int> pbr_maps;       // pbr_maps[m]: the metallic-roughness map of pbr material m, -1: none; beside the
                                      // material table as the bumps are, at most as long as the last mapped material's id + 1
+    std::vector<SceneNormalMap> normal_maps;  // normal_maps[m]: the normal map of material m, texture < 0: none; beside
+                                     // the material table as the bumps are, at most as long as the last mapped material's id + 1
     std::shared_ptr<const SceneEnvironment> env;  // null: no environment (a miss gives the background / the sky)
     float env_scale = 1.0f, env_rotate = 0.0f;    // radiance = scale x texel; degrees about +y
     std::vector<rt_medium> media;  // homogeneous participating media, a list of its own: at most RT_MAX_MEDIA
@@ -201,6 +209,19 @@ bool set_bump(Scene &s, int material, int texture, float strength, const char *w
 // with `where`) and stores -- texture -1 removes
 inline int scene_pbr_map(const Scene &s, int m) { return (m >= 0 && (size_t)m < s.pbr_maps.size()) ? s.pbr_maps[(size_t)m] : -1; }
 bool set_pbr_map(Scene &s, int material, int texture, const char *where);
+
+// normal maps: the map of material m, or null; does any material carry one (such a scene runs the general kernels
+// over the wide tables, as one with a bump); set_normal_map checks (false: the message is set, prefixed with `where`) and
+// stores -- texture -1 or scale 0 removes.  A material carries a bump or a map, not both: either setter refuses the second
+inline const SceneNormalMap *scene_normal_map(const Scene &s, int m) {
+    return (m >= 0 && (size_t)m < s.normal_maps.size() && s.normal_maps[(size_t)m].texture >= 0) ? &s.normal_maps[(size_t)m] : nullptr;
+}
+inline bool scene_has_normal_map(const Scene &s) {
+    for (const SceneNormalMap &b : s.normal_maps)
+        if (b.texture >= 0) return true;
+    return false;
+}
+bool set_normal_map(Scene &s, int material, int texture, float scale, const char *where);
 
 // a medium (scene.cpp): checks the record and appends it -> medium id, or -rt_status
 int add_medium(Scene &s, const rt_medium &m);
