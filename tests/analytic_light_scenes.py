@@ -5,7 +5,7 @@ Every per-sample case uses the frame, sample count, seed and draw budget of nee_
 frames = 16 848 samples).  A builder called with full=False builds the case's twin geometry (glossy materials as lambertian,
 rough glass as a dielectric); the plain twin is that with light sampling off and the environment cleared -- the analytic lights
 are then in no table: what the plain kernel renders, the baseline of criterion (b).  The reference of a case is
-ref64_analytic_lights.reference on its attach()ed RefScene.
+ref64.reference on its RefScene.
 
 What was fixed, and why: checker floors are lifted off y = 0 (nee_scenes.LIFT); the intensities are chosen so that the alias table
 gives every light of a mixed case a share of the picks (the weights are 4 lum(I), 2 (1 - (cos_i + cos_o) / 2) lum(I), r^2 lum(E)
@@ -167,10 +167,6 @@ def plain_twin(rtmi, name):
     sc.set_light_sampling(False)
     sc.set_environment(None)
     return sc
-
-
-def ref_scene(sc):
-    return RA.attach(R.RefScene(sc), sc)
 
 
 def inputs(rtmi):

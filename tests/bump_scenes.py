@@ -6,7 +6,7 @@ Every case uses the frame, sample count, seed and draw budget of nee_scenes.REF_
 16 848 samples; the media and motion cases use their families' seed, as glossy_scenes.py and noise_scenes.py do).  A builder
 called with bump=False builds the case's TWIN: the same primitives and materials, in the same order, with no bump and without
 the height textures -- the baseline of criterion (b), and the scene whose feature buffers and query records a bump must leave
-alone.  The reference of a case is ref64_bump.reference(scene, ...); of its twin, ref64.reference called plainly.
+alone.  The reference of a case and of its twin is ref64.reference.
 
 Where fp32 can hold the per-sample tolerance (measured on the CPU with fp32 numpy against fp64): bumped
 surfaces lie within 4 units of the origin, every height texture has a scale <= 3 that is no power of two (with one, q = f p is
@@ -178,7 +178,7 @@ def nested(rtmi, bump=True, w=NS.REF_W, h=NS.REF_H):
     return sc
 
 
-# name -> (family bits the kernel must report, builder, light sampling on, the keys of ref64_bump.tally() it is there for)
+# name -> (family bits the kernel must report, builder, light sampling on, the bump_* keys of ref64.tally() it is there for)
 CASES = {
     "bump_sky": (0, sky, False, ("bump_lambertian", "bump_metal", "bump_dielectric", "bump_rough_metal", "bump_plastic")),
     "bump_prims": (0, prims, False, ("bump_lambertian", "bump_metal", "bump_plastic", "bump_dielectric", "bump_back", "bump_kept")),
@@ -187,7 +187,7 @@ CASES = {
     "bump_fog": (MEDIA, fog, False, ("bump_lambertian", "bump_rough_metal", "bump_plastic")),
     "bump_motion": (MOTION, motion, False, ("bump_lambertian", "bump_rough_metal", "bump_plastic")),
 }
-# the deliberate mistakes of ref64_bump, each on the case that exercises it
+# the deliberate mistakes of the bump (ref64_bump.PERTURBATIONS), each on the case that exercises it
 MISTAKES = (("bump_sky", "bump_off"), ("bump_sky", "bump_full_gradient"), ("bump_prims", "bump_back_unsigned"),
             ("bump_sky", "bump_cubic_fade_derivative"))
 

@@ -4,8 +4,7 @@ seeded records of the fp32-against-fp64 check of csrc/rt_glass.h.
 Every case uses the frame, sample count, seed and draw budget of nee_scenes.REF_* (48 x 27 pixels x 13 one-sample frames =
 16 848 samples; the media and motion cases use their families' seed, as glossy_scenes does).  A builder called with glass=False
 builds the case's TWIN: every rough_glass replaced by dielectric of the same ir -- the precision baseline for refractive paths,
-criterion (b).  The reference of a case is ref64_glass.reference on its RefScene; of a twin, ref64.reference under
-ref64_glass.installed() (for its quads and bumps; it has no glass row).
+criterion (b).  The reference of a case and of a twin is ref64.reference on its RefScene.
 
 No checker lies on y = 0 (nee_scenes.LIFT).  glass_mesh's torus is a small one made here (12 x 8 quads of two triangles, exact
 vertex normals), so that the list-scanning reference stays quick and grazing rays meet faces from below their shading normal.
@@ -183,11 +182,6 @@ def plain_twin(rtmi, name):
     sc.clear_media()
     sc.clear_moving_spheres()
     return sc
-
-
-def twin_reference(sc, words):
-    with GL.installed(sc=sc):
-        return R.reference(R.RefScene(sc), words)
 
 
 def inputs(rtmi, name):

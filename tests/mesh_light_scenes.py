@@ -5,7 +5,7 @@ alone.
 Every per-sample case uses the frame, sample count, seed and draw budget of nee_scenes.REF_* (48 x 27 pixels x 13 one-sample
 frames = 16 848 samples).  A builder called with glossy=False builds the case's glossy-free geometry (glossy_scenes._Mats); the
 plain twin is that with light sampling off and the environment cleared: what the plain kernel renders, the baseline of
-criterion (b).  The reference of a case is ref64_mesh_lights.reference on its RefScene.
+criterion (b).  The reference of a case is ref64.reference on its RefScene.
 
 What was fixed, and why (the fp64 and the fp32 reference were run on the CPU on every case before it was fixed; a case stays
 only if the fp32 reference alone meets criterion (a) with at most 1 % of the samples flipping a branch):
@@ -127,8 +127,10 @@ CASES = {
     "glossy under a triangle": (NEE, glossy),
 }
 MIXED = "smooth mesh + rect + sphere"
+# the keys of ref64.tally() a mesh-light case is read by
+TALLY_KEYS = ("triangle_picks", "other_picks", "triangle_shadow_stopped", "triangle_shadow_clear", "triangle_mis_hits", "triangle_full_weight_hits")
 
-# What each case holds, read off the fp64 reference (ref64_mesh_lights.tally on the 16 848 samples) and pinned: light samples
+# What each case holds, read off the fp64 reference (ref64.tally on the 16 848 samples) and pinned: light samples
 # that picked a triangle, those whose shadow ray was stopped, BSDF hits on a triangle light with an MIS weight below 1
 PINNED = {
     "lone triangle": dict(triangle_picks=13862, triangle_shadow_stopped=1017, triangle_mis_hits=174),

@@ -4,8 +4,7 @@ and the seeded records of the fp32-against-fp64 check of csrc/rt_noise.h.
 Every case uses the frame, sample count, seed and draw budget of nee_scenes.REF_* (48 x 27 pixels x 13 one-sample frames =
 16 848 samples; the media and motion cases use their families' seed, as glossy_scenes.py does).  A builder called with
 noise=False builds the case's TWIN: every noise texture replaced by the solid colour (c0 + c1) / 2 under the same material --
-the geometry the plain kernel is pinned on, the baseline of criterion (b).  The reference of a case is ref64.reference inside
-ref64_noise.installed(scene); of its twin, ref64.reference called plainly.
+the geometry the plain kernel is pinned on, the baseline of criterion (b).  The reference of a case and of its twin is ref64.reference.
 
 Together the cases carry fbm, turbulence and marble on lambertian, plastic (r = 0.3 and 0.5: both take light samples; one at
 r = 0.02, which takes none) and diffuse_light, one case per render family and one in a nested cell.
@@ -154,7 +153,7 @@ def nested(rtmi, noise=True, w=NS.REF_W, h=NS.REF_H):
     return sc
 
 
-# name -> (family bits the kernel must report, builder, light sampling on, the keys of ref64_noise.tally() it is there for)
+# name -> (family bits the kernel must report, builder, light sampling on, the noise_* keys of ref64.tally() it is there for)
 CASES = {
     "noise_sky": (0, sky, False, ("noise_lambertian", "noise_plastic")),
     "noise_lights": (NEE, lights, True, ("noise_lambertian", "noise_plastic", "noise_emitter", "noise_plastic_light_samples")),

@@ -211,7 +211,7 @@ def nested(rtmi, maps=True, w=NS.REF_W, h=NS.REF_H):
     return sc
 
 
-# name -> (family bits the kernel must report, builder, light sampling on, the keys of ref64_normal_map.tally() it is there for)
+# name -> (family bits the kernel must report, builder, light sampling on, the nm_* keys of ref64.tally() it is there for)
 CASES = {
     "nm_sky": (0, sky, False, ("nm_lambertian", "nm_metal", "nm_dielectric", "nm_rough_metal", "nm_plastic", "nm_rough_glass", "nm_pbr",
                                "nm_on_sphere", "nm_on_rect", "nm_on_cylinder", "nm_on_triangle", "nm_on_quad")),
@@ -221,7 +221,7 @@ CASES = {
     "nm_fog": (MEDIA, fog, False, ("nm_lambertian", "nm_rough_metal", "nm_plastic")),
     "nm_motion": (MOTION, motion, False, ("nm_lambertian", "nm_rough_metal", "nm_plastic")),
 }
-# the deliberate mistakes of ref64_normal_map, each on the case that exercises it
+# the deliberate mistakes of the normal map (ref64_normal_map.PERTURBATIONS), each on the case that exercises it
 MISTAKES = (("nm_sky", "nm_off"), ("nm_sky", "nm_swap_tb"), ("nm_prims", "nm_back_unsigned"), ("nm_prims", "nm_not_about_n"),
             ("nm_sky", "nm_2c_minus_1"))
 

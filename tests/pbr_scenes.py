@@ -4,12 +4,13 @@ twins, the known-answer scenes and the records of the fp32-against-fp64 check.
 Every per-sample case uses the frame, sample count, seed and draw budget of nee_scenes.REF_* (48 x 27 pixels x 13 one-sample
 frames = 16 848 samples).  A builder called with full=False builds the case's twin: every pbr material replaced by a lambertian
 of its base texture; the plain twin is that with light sampling off, the environment cleared and the analytic lights out of
-every table -- what the plain kernel renders, the baseline of criterion (b).  The reference of a case is ref64_pbr.reference.
+every table -- what the plain kernel renders, the baseline of criterion (b).  The reference of a case is ref64.reference.
 
 What was fixed, and why: solid colours and factors stay away from the values x with 255 x within 1e-3 of k + 1/2 (0.1, 0.3, 0.7,
-0.9 ...), where the byte of an fp32 evaluation and of the fp64 one may differ (0.5 is exact: 128 in both); every material keeps
-its r8 on one side of the light-sample threshold (ref64.trace takes that decision per material: ref64_pbr's docstring), so the
-image ORM map's G bytes start at 40 and the noise map's G at 0.3; colours, roughnesses and metalnesses of the maps otherwise run over their whole range."""
+0.9 ...), where the byte of an fp32 evaluation and of the fp64 one may differ (0.5 is exact: 128 in both); the image ORM map's G
+bytes start at 40 and the noise map's G at 0.3, which keeps those materials' r8 above the light-sample threshold (the reference
+once took that decision per material); colours, roughnesses and metalnesses of the maps otherwise run over their whole range.  The
+decision is each hit's: the last case holds one material whose checker map carries r8 across the threshold."""
 import numpy as np
 
 import ext_scenes as X
@@ -131,6 +132,22 @@ def plain_bump(rtmi, full=True, **kw):
     return sc
 
 
+ACROSS = ((0.0, 0.02, 1.0), (0.0, 0.6, 0.0))  # the checker map's two colours: (G, B) = (0.02, 1) and (0.6, 0), r8 = 5 and 153
+
+
+def across(rtmi, full=True, **kw):
+    """(5) one pbr material (m factor 0.5, r factor 1) whose checker map carries r8 from 5 to 153, across the light-sample
+    threshold of 13, on a floor tile and two balls under a quad light: its smooth tiles take no light sample, its rough ones do"""
+    sc = _frame(rtmi, **kw)
+    sc.xz_rect(-20, 20, -20, 20, 0.0, sc.lambertian((0.6, 0.5, 0.4)))
+    mat = _Mats(sc, full).pbr((0.5, 0.5, 0.5), 0.5, 1.0, 1.5, sc.checker_texture(*ACROSS))
+    sc.quad((-2.6, LIFT, -1.2), (0.0, 0.0, 3.0), (5.2, 0.0, 0.0), mat)
+    sc.sphere((-1.1, 0.75, 0.2), 0.7, mat)
+    sc.sphere((1.2, 0.65, 0.6), 0.6, mat)
+    sc.quad((-0.8, 3.4, -0.5), (1.6, 0.0, 0.0), (0.0, 0.0, 1.6), sc.diffuse_light((14.0, 13.0, 12.0)))
+    return sc
+
+
 _CHOICES = (("pbr_metal_choices", 500), ("pbr_plastic_choices", 500))
 # name -> (family bits the kernel must report, builder, light sampling, (key of the tally, at least))
 CASES = {
@@ -138,6 +155,7 @@ CASES = {
     "maps": (NEE, maps, True, _CHOICES + (("pbr_lit", 100), ("pbr_image_map_hits", 100), ("pbr_noise_map_hits", 100), ("pbr_image_base_hits", 100))),
     "maps under an environment": (ENV | NEE, maps_env, True, _CHOICES + (("pbr_lit", 100), ("pbr_image_map_hits", 100), ("pbr_noise_map_hits", 100))),
     "plain, bumped": (0, plain_bump, False, _CHOICES + (("pbr_image_map_hits", 100), ("pbr_noise_map_hits", 100))),
+    "a map across the threshold": (NEE, across, True, _CHOICES + (("pbr_lit", 100), ("pbr_smooth_vertices", 500), ("pbr_checker_map_hits", 1000))),
 }
 # the case each deliberate mistake is shown on
 MISTAKES = (("half-metal floor", "lobe_draw_not_rescaled"), ("room", "metal_f0_004"), ("maps", "roughness_from_r"), ("maps", "light_step_from_factors"))

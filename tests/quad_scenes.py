@@ -24,9 +24,6 @@ import media_scenes as MS
 import motion_scenes as MO
 import nee_scenes as NS
 import ref64 as R
-import ref64_bump as RB
-import ref64_noise as RN
-import ref64_quads as RQ
 
 NEE, ENV, MEDIA, MOTION = X.NEE, X.ENV, X.MEDIA, X.MOTION
 FAMILIES = NEE | ENV | MEDIA | MOTION
@@ -37,7 +34,7 @@ BOX_GAP = 0.013
 # reference itself is biased against fp64 (z = -7.4) and criterion (c) cannot be asked of any fp32 code.  At 100 the error is a
 # hundredth of that; the ground falls 0.03 under the boxes furthest out, which stand on BOX_GAP anyway.
 GROUND_R = 100.0
-QUAD = RQ.QUAD
+QUAD = R.QUAD
 
 
 class Geo:
@@ -245,53 +242,6 @@ def inputs(rtmi, name):
     words = R.uniforms(rtmi, seed_of(name), NS.REF_W, NS.REF_H, 0, NS.REF_K, NS.REF_DRAWS)
     shutter = MO.shutter_times(rtmi, seed_of(name), NS.REF_W, NS.REF_H, 0, NS.REF_K) if family(name) == MOTION else None
     return words, shutter
-
-
-def _stack(sc, perturb=()):
-    """the wrappers a case's reference runs under: quads, and the noise textures and bumps of the textured case"""
-    import contextlib
-    stack = contextlib.ExitStack()
-    stack.enter_context(RQ.installed(perturb))
-    if any(int(t["type"]) == RN.NOISE for t in sc.textures()):
-        stack.enter_context(RN.installed(sc))
-        stack.enter_context(RB.installed(sc))
-    return stack
-
-
-def trace(sc, S, words, shutter=None, perturb=(), **kw):
-    with _stack(sc, perturb):
-        return R.trace(S, words, perturb=tuple(perturb), shutter=shutter, **kw)
-
-
-def reference(sc, S, words, shutter=None):
-    with _stack(sc):
-        return R.reference(S, words, shutter)
-
-
-def back_hits(sc, S, words, shutter=None):
-    """quad vertices met from behind (front false), counted by a hit_record that looks on: the signature has no column for it"""
-    count = [0]
-    with _stack(sc):
-        inner = R.hit_record
-
-        def hit_record(S_, o, d, t, idx, T, flat=False):
-            p, n, front = inner(S_, o, d, t, idx, T, flat)
-            kinds = np.array([RQ.is_quad(q) for q in S_.prims], bool)
-            count[0] += int((kinds[idx] & ~front).sum())
-            return p, n, front
-        R.hit_record = hit_record
-        try:
-            R.trace(S, words, shutter=shutter)
-        finally:
-            R.hit_record = inner
-    return count[0]
-
-
-def tally(sc, S, sig, words, shutter=None):
-    out = dict(R.tally(sig, S))
-    out.update(RQ.tally(sig, S))
-    out["quad_back_hits"] = back_hits(sc, S, words, shutter)
-    return out
 
 
 def check_contents(name, tally_):

@@ -1,29 +1,39 @@
 """An independent statement of the path estimators of DESIGN 7a (light sampling + MIS), 7e (environment maps), 7f (homogeneous
 participating media with isotropic scattering), 7g (motion blur: linearly moving spheres over a per-sample shutter time), 7l
-(smooth shading: the shading normal of triangles with vertex normals) and 7m (the glossy materials), in NumPy, vectorised over
-a batch of samples, at a floating type of the caller's choice (float64: the reference; float32: the same formulas at the
-kernel's precision, used to measure how many samples sit on a branch).
+(smooth shading), 7m (the glossy materials) and 7n-7u (triangle lights, noise textures, bumps, quads, rough glass, point / spot /
+distant lights, the metallic-roughness material, normal maps), in NumPy, vectorised over a batch of samples, at a floating type
+of the caller's choice (float64: the reference; float32: the same formulas at the kernel's precision, used to measure how many
+samples sit on a branch).
 
-Test infrastructure only.  It is written from the definitions -- DESIGN 2 (the integrator, the order of the draws), 7a, 7e,
-7f (the media walk), 7g (the shutter time, the movers' query and its tie rule), and the reference's primitive, material and
-texture definitions (triangles, the hit record's (u, v) and the image lookup among them) -- with libm's arccos / arctan2 / log,
-plain closest-hit loops over the primitive, mover and media lists and no fused operations.  It shares no code with the kernels
-or with oracle/.
+Test infrastructure only.  It is written from the definitions -- DESIGN 2 (the integrator, the order of the draws), the
+sections above, include/rtmi.h's text of the records, and the reference's primitive, material and texture definitions -- with
+libm's arccos / arctan2 / log, plain closest-hit loops over the primitive, mover and media lists and no fused operations.  It
+shares no code with the kernels or with oracle/.
 
-There is ONE integrator loop, trace(), and one hit record, hit_record().  An extension joins them with a record list on
-RefScene (lights, media, movers: empty unless the scene has them) or records the scene's tables already hold (a triangle's
-vertex normals, a material's type), a block in the loop, columns or event codes in the signature and keys in tally(); its
-deliberate mistakes are names in trace()'s `perturb`.  A material model large enough for a file of its own (ref64_glossy.py:
-the GGX lobe, both glossy materials' sample and evaluation) is imported HERE and holds no loop: no module restates trace(),
-and none swaps a function of this one.  The reference evaluates the scene it is given: which combinations the product renders
-is the product's to refuse and test_refusals' to assert.  Where two extensions meet and DESIGN defines no order -- a light
-sample at a medium vertex, a shadow ray through a medium or past a mover -- trace() raises NotImplementedError.
+There is ONE integrator loop, trace(), one hit record, hit_record(), one texture lookup, texture_value(), and one light sample,
+sample_light().  An extension joins them with records on RefScene, read ONCE from the product scene (lights, media, movers,
+noise parameters, bumps, normal maps, pbr maps, analytic lights: each empty unless the scene has them) or records the scene's
+tables already hold (a triangle's vertex normals, a primitive's or a material's type), a branch in those functions or a block
+in the loop, columns or event codes in the signature, counters in trace()'s `log` for what the signature has no column for,
+and keys in tally(); its deliberate mistakes are names in trace()'s one `perturb`.  A model large enough for a file of its own
+is imported HERE, holds no loop and imports nothing of this file (ref64_base.py holds what they share):
+    ref64_glossy            7m  the GGX lobe, rough metal's and plastic's sample and evaluation
+    ref64_noise             7o  the lattice noise and the three styles' scalar and colour
+    ref64_bump              7p  the analytic gradient of that scalar and the rule that tilts the normal
+    ref64_glass             7r  the exact Fresnel term, rough glass's sample and evaluation, the tint
+    ref64_analytic_lights   7s  the light records, the three lights' samples
+    ref64_pbr               7t  the bytes of a hit, the choice between metal and plastic
+    ref64_normal_map        7u  the texel's decoding, every primitive's tangents, the frame and the rule
+(triangle lights, 7n, and quads, 7q, are short enough to stand here).  No module restates trace(), and none swaps a function of
+this one.  The reference evaluates the scene it is given: which combinations the product renders is the product's to refuse and
+test_refusals' to assert.  Where two extensions meet and DESIGN defines no order -- a light sample at a medium vertex, a shadow
+ray through a medium or past a mover -- trace() raises NotImplementedError.
 
 Inputs are the product's exported tables (Scene.prims / materials / textures / lights / media / moving_spheres / get_camera /
-info / environment), the light alias table and the environment's CDF tables as the packed image stores them (table_image,
-found by content), the uniforms of rtmi.sample_stream and, for movers, the shutter times of rtmi.shutter_time (one per sample:
-the time is no draw of the stream) and the pixels of the image textures (Scene.get_image).  Triangles and image textures are
-in scope.  Out of scope: the nested grid (a candidate search, which this reference has none of: it scans the lists).
+info / environment / noise / bump / normal_map / pbr_map / analytic_lights), the light alias table and the environment's CDF
+tables as the packed image stores them (table_image, found by content), the uniforms of rtmi.sample_stream and, for movers, the
+shutter times of rtmi.shutter_time (one per sample: the time is no draw of the stream) and the pixels of the image textures
+(Scene.get_image).  Out of scope: the nested grid (a candidate search, which this reference has none of: it scans the lists).
 
 trace() returns, per sample, the radiance, an event signature (one row of integers: per vertex the primitive hit, the mover
 that took over, the set of media that took a free-flight draw and the medium whose event won, what the material did, the
@@ -34,13 +44,30 @@ it) and the number of draws consumed.
 """
 import numpy as np
 
-from ref64_glossy import (ROUGH_METAL, PLASTIC, GLOSSY_MIN_ROUGHNESS, EV_ROUGH, EV_COAT, EV_BODY, EV_BELOW, EV_ROUGH_ABSORBED,
-                          EV_COAT_ABSORBED, alpha_of, r0_of, glossy_sample, glossy_eval, glossy_tally)
+import ref64_analytic_lights as AL
+import ref64_bump as BU
+import ref64_glass as GL
+import ref64_noise as NO
+import ref64_normal_map as NM
+import ref64_pbr as PB
+from ref64_base import SPHERE, XY_RECT, XZ_RECT, YZ_RECT, CYLINDER, TRIANGLE, QUAD, _affine, _cross, _dot, _rect_axes, _unit
+from ref64_glossy import (ROUGH_METAL, PLASTIC, GLOSSY_MIN_ROUGHNESS, GLOSSY_EVENTS, EV_ROUGH, EV_COAT, EV_BODY, EV_BELOW,
+                          EV_ROUGH_ABSORBED, EV_COAT_ABSORBED, alpha_of, r0_of, glossy_sample, glossy_eval, glossy_tally)
 
-SPHERE, XY_RECT, XZ_RECT, YZ_RECT, CYLINDER, TRIANGLE = range(6)
 LAMBERTIAN, METAL, DIELECTRIC, DIFFUSE_LIGHT = range(4)  # (ref64_glossy: ROUGH_METAL, PLASTIC = 4, 5)
-SOLID, CHECKER, IMAGE = range(3)
+ROUGH_GLASS, PBR = 6, 7
+SOLID, CHECKER, IMAGE, NOISE = range(4)
 ENVIRONMENT = 100
+POINT, SPOT, DISTANT = AL.POINT, AL.SPOT, AL.DISTANT
+DELTA_LIGHTS = (POINT, SPOT, DISTANT)
+# the counters of trace()'s `log`: what the signature has no column for.  bump_* / nm_*: perturbed vertices in all, on back faces,
+# (nm) whose texel tilts, and where a guard kept n (nm: the texel tilts and the frame was built)
+LOG_KEYS = (("bump_bumped", "bump_back", "bump_kept", "nm_mapped", "nm_back", "nm_tilting", "nm_kept", "quad_back_hits")
+            + GL.LOG_KEYS + AL.LOG_KEYS + PB.LOG_KEYS)
+
+
+def new_log():
+    return dict.fromkeys(LOG_KEYS, 0)
 MEDIUM_SPHERE, MEDIUM_BOX = 0, 1
 T_MIN = 0.001           # hittable_list::hit's t_min of every query
 SHADOW_T_MAX = 0.999    # a shadow ray ends just short of its light point
@@ -153,6 +180,21 @@ class RefScene:
         self.light_of_prim = {int(l["prim"]): i for i, l in enumerate(self.lights) if l["prim"] >= 0}
         self.movers = sc.moving_spheres() if movers else sc.moving_spheres()[:0]
         self.media = sc.media() if media else sc.media()[:0]
+        # the extensions' records, each empty unless the scene has them.  noise: texture -> the dict of Scene.noise; bumps:
+        # material -> (the height field's noise parameters, strength); normal_maps: material -> (image texture, scale); pbr_maps:
+        # pbr material -> its metallic-roughness map's texture or -1; analytic: index into lights -> ref64_analytic_lights.record
+        materials = range(len(self.mats))
+        self.noise = {ti: sc.noise(ti) for ti, t in enumerate(self.texs) if t["type"] == NOISE}
+        self.bumps = {m: (self.noise[int(b[0])], np.float32(b[1])) for m in materials for b in [sc.bump(m)] if b is not None}
+        self.normal_maps = {m: (int(b[0]), np.float32(b[1])) for m in materials for b in [sc.normal_map(m)] if b is not None}
+        self.pbr_maps = {m: -1 if mp is None else int(mp) for m in materials if self.mats["type"][m] == PBR for mp in [sc.pbr_map(m)]}
+        self.analytic = {}
+        at = [i for i, l in enumerate(self.lights) if l["shape"] in DELTA_LIGHTS]
+        if at:  # (a light whose weight is not positive and finite is in neither list)
+            radius = AL.bound_radius(self.prims)
+            recs = [r for r in (AL.record(al, radius) for al in sc.analytic_lights()) if r["weight"] > 0 and np.isfinite(r["weight"])]
+            assert [self.lights[i]["shape"] for i in at] == [r["type"] for r in recs], (at, [r["type"] for r in recs])
+            self.analytic = dict(zip(at, recs))
 
 
 def uniforms(rtmi, seed, width, height, first, count, n):
@@ -165,27 +207,30 @@ def uniforms(rtmi, seed, width, height, first, count, n):
 
 
 # ---------------------------------------------------------------------------------------------------------------- geometry
-def _dot(a, b):
-    return (a * b).sum(axis=-1)
+def quad_record(pr, T):
+    """(Q, u, v, n, A, B) of a quad's rt_prim record: the corner, the edges and, derived by the host in fp64 and rounded
+    once, the unit normal n = c / |c| (c = u x v) and A = v x w, B = w x u with w = c / (c.c)"""
+    m, mi = pr["m"].astype(T), pr["m_inv"].astype(T)
+    return m[0:3], m[3:6], m[6:9], m[9:12], mi[0:3], mi[3:6]
 
 
-def _unit(a):
-    return a / np.sqrt(_dot(a, a))[:, None]
+def quad_ab(pr, o, d, t, T):
+    """a = A.(p - Q), b = B.(p - Q) of the point p = o + t d: the quad holds p iff both lie in [0, 1]; its record's (u, v)"""
+    Q, _, _, _, A, B = quad_record(pr, T)
+    r = o + t[:, None] * d - Q
+    return _dot(A[None, :], r), _dot(B[None, :], r)
 
 
-def _rect_axes(ptype):
-    # (plane axis, first in-plane axis, second in-plane axis): xy_rect z = k, xz_rect y = k, yz_rect x = k
-    return {XY_RECT: (2, 0, 1), XZ_RECT: (1, 0, 2), YZ_RECT: (0, 1, 2)}[int(ptype)]
-
-
-def _affine(m, T):
-    m = np.asarray(m, T).reshape(3, 4)
-    return m[:, :3], m[:, 3]
-
-
-def _cross(a, b):
-    return np.stack([a[..., 1] * b[..., 2] - a[..., 2] * b[..., 1], a[..., 2] * b[..., 0] - a[..., 0] * b[..., 2],
-                     a[..., 0] * b[..., 1] - a[..., 1] * b[..., 0]], axis=-1)
+def quad_t(pr, o, d, T):
+    """t = n.(Q - o) / n.d where den = n.d is finite and not zero and the quad holds the point (any t: the caller applies the
+    range), NaN elsewhere"""
+    Q, _, _, n, _, _ = quad_record(pr, T)
+    with np.errstate(all="ignore"):
+        den = _dot(d, n[None, :])
+        t = _dot(n[None, :], Q - o) / den
+        a, b = quad_ab(pr, o, d, t, T)
+        ok = (den != 0) & np.isfinite(den) & (a >= 0) & (a <= 1) & (b >= 0) & (b <= 1)
+    return np.where(ok, t, T(np.nan)).astype(T)
 
 
 def _triangle_plane(p, o, d, dd, T):
@@ -231,6 +276,8 @@ def _prim_t(p, o, d, dd, t_min, best, T):
         if ty == TRIANGLE:
             _, theta, ocn, inside = _triangle_plane(p, o, d, dd, T)
             return np.where((theta < 0) & inside, -ocn / theta / np.sqrt(dd), nan)
+        if ty == QUAD:
+            return quad_t(p, o, d, T)
         # open tube about the object-space z axis
         R, tr = _affine(p["m_inv"], T)
         oo, od = o @ R.T + tr, d @ R.T
@@ -297,17 +344,22 @@ def shading_normal(pr, o, d, g, T):
     return np.where(ok[:, None], s, g).astype(T)
 
 
-def hit_record(S, o, d, t, idx, T, flat=False):
+def hit_record(S, o, d, t, idx, T, perturb=(), log=None):
     """point and face-turned normal of accepted hits; front = the ray meets the outward side.  On a triangle that carries vertex
-    normals and whose material is no emitter the normal is the shading normal (front stays the geometric side); flat=True
-    leaves the geometric normal there too."""
+    normals and whose material is no emitter the normal is the shading normal (front stays the geometric side); "flat_normals"
+    leaves the geometric normal there too.  Then the material's bump or its normal map (7u) tilts that normal about
+    the geometric one: the product refuses both on one material, so the order in which they stand here is no statement.  Movers
+    do not come here: the product refuses a bumped or mapped mover."""
     p = o + t[:, None] * d
     n_out = np.zeros_like(o)
+    quad = np.zeros(len(o), bool)
     for i in np.unique(idx):
         m = idx == i
         pr = S.prims[i]
         ty, f = int(pr["type"]), pr["f"].astype(T)
-        if ty == SPHERE:
+        if ty == QUAD:
+            n_out[m], quad[m] = quad_record(pr, T)[3], True
+        elif ty == SPHERE:
             n_out[m] = (p[m] - f[:3]) / f[3]
         elif ty == CYLINDER:
             R, tr = _affine(pr["m_inv"], T)
@@ -320,12 +372,43 @@ def hit_record(S, o, d, t, idx, T, flat=False):
         else:
             n_out[m, _rect_axes(ty)[0]] = 1
     front = _dot(d, n_out) < 0
-    n = np.where(front[:, None], n_out, -n_out)
-    for i in (() if flat else np.unique(idx)):
+    g = np.where(front[:, None], n_out, -n_out)
+    if "quad_front_flipped" in perturb:
+        front = front ^ quad
+    if log is not None:
+        log["quad_back_hits"] += int((quad & ~front).sum())
+    n = g.copy()
+    for i in (() if "flat_normals" in perturb else np.unique(idx)):
         pr = S.prims[i]
         if int(pr["type"]) == TRIANGLE and has_normals(pr) and int(S.mats["type"][pr["material"]]) != DIFFUSE_LIGHT:
             m = idx == i
             n[m] = shading_normal(pr, o[m], d[m], n[m], T)
+    mat = S.prims["material"][idx]
+    for m in (() if "bump_off" in perturb else np.unique(mat[np.isin(mat, list(S.bumps))])):
+        sel = mat == m
+        par, k = S.bumps[int(m)]
+        n[sel], ok = BU.bump(n[sel], g[sel], d[sel], front[sel], k, BU.gradient_of(p[sel], par, T, perturb), T, perturb)
+        if log is not None:
+            log["bump_bumped"] += int(sel.sum())
+            log["bump_back"] += int((~front[sel]).sum())
+            log["bump_kept"] += int((~ok).sum())
+    mapped = np.isin(mat, list(S.normal_maps))
+    if mapped.any() and "nm_off" not in perturb:
+        u, v = hit_uv(S, o, d, t, idx, T, perturb=perturb)
+        for i in np.unique(idx[mapped]):
+            sel = idx == i
+            tex, s = S.normal_maps[int(S.prims["material"][i])]
+            img = S.images[tex]
+            row, col = image_texel(img, u[sel], v[sel], T, perturb)
+            xyz, active = NM.decode(img[row, col], T, perturb)
+            Tr, Br = NM.raw_tangents(S.prims[i], p[sel], T)
+            parts = {}
+            n[sel], ok = NM.normal(n[sel], g[sel], d[sel], front[sel], s, Tr, Br, xyz, active, T, perturb, parts)
+            if log is not None:
+                log["nm_mapped"] += int(sel.sum())
+                log["nm_back"] += int((~front[sel]).sum())
+                log["nm_tilting"] += int(active.sum())
+                log["nm_kept"] += int((active & parts["usable"] & ~ok).sum())
     return p, n, front
 
 
@@ -412,6 +495,9 @@ def hit_uv(S, o, d, t, idx, T, mov=None, time=None, perturb=()):
                 op = (oo @ R.T + tr) + tt[:, None] * (dd @ R.T)
                 u[k] = (np.arctan2(op[:, 1], op[:, 0]) + 2 * T(np.pi)) / (4 * T(np.pi))
                 v[k] = (op[:, 2] - f[1]) / (f[2] - f[1])
+            elif ty == QUAD:
+                a, b = quad_ab(pr, oo, dd, tt, T)
+                u[k], v[k] = (b, a) if "quad_uv_swapped" in perturb else (a, b)
             else:
                 # the area weights of the plane point, each with the corner the reference pairs it with: the sub-triangle
                 # (r, v1, v2) over the whole goes with u1, (r, v1, v3) with u2, (r, v3, v2) with u3
@@ -444,7 +530,7 @@ def image_texel(img, u, v, T, perturb=()):
 
 def texture_value(S, tex, p, T, o=None, d=None, t=None, idx=None, mov=None, time=None, perturb=()):
     """(colour, flat index of the image texel read or NONE) of the textures `tex` at the hits: a solid colour, the checker's
-    parity at the point p, or the image's texel at the hit record's (u, v), which needs the ray (o, d), its parameter t, the
+    parity at the point p, the noise texture's colour at p, or the image's texel at the hit record's (u, v), which needs the ray (o, d), its parameter t, the
     static primitive idx, and the mover that took over with the samples' shutter times"""
     out = np.zeros_like(p)
     texel = np.full(len(p), NONE, np.int64)
@@ -458,6 +544,8 @@ def texture_value(S, tex, p, T, o=None, d=None, t=None, idx=None, mov=None, time
             row, col = image_texel(img, u, v, T, perturb)
             out[m] = img[row, col].astype(T) / T(255)
             texel[m] = row * img.shape[1] + col
+        elif tx["type"] == NOISE:
+            out[m] = NO.colour(p[m], tx["c0"], tx["c1"], S.noise[int(ti)], T, perturb)
         else:
             out[m] = np.where(checker_odd(p[m], T)[:, None], c1, c0) if tx["type"] == CHECKER else c0
     return out, texel
@@ -525,7 +613,9 @@ def inside_sphere_light(S, li, p, T):
 
 
 def light_pdf_of_hit(S, li, o, d, t, n, T):
-    """the light strategy's solid-angle density of the direction of a ray from o that hit light li at parameter t (normal n)"""
+    """the light strategy's solid-angle density of the direction of a ray from o that hit light li at parameter t (normal n): a
+    sphere's by the cone it subtends; every other shape's -- rectangle, cylinder, triangle, quad -- by area with the hit's normal,
+    which on an emitter is the geometric one"""
     L = S.lights[li]
     sel = T(L["probability"])
     if L["shape"] == SPHERE:
@@ -541,9 +631,42 @@ def light_pdf_of_hit(S, li, o, d, t, n, T):
         return sel / T(L["area"]) * dist2 / cos_l
 
 
-def sample_light(S, li, p, u1, u2, T, perturb=()):
+def triangle_light_record(pr):
+    """(v1, e1, e2, n) as the light record of a triangle holds them: fp32, the edges fp32 differences of the fp32
+    vertices, n the GEOMETRIC unit normal whatever vertex normals the triangle carries (an emitter hit keeps it)"""
+    m = pr["m"].astype(np.float32)
+    return m[0:3], m[3:6] - m[0:3], m[6:9] - m[0:3], m[9:12]
+
+
+def triangle_area(pr):
+    """|e1 x e2| / 2 in fp64 from the stored vertices"""
+    m = pr["m"].astype(np.float64)
+    return 0.5 * float(np.linalg.norm(np.cross(m[3:6] - m[0:3], m[6:9] - m[0:3])))
+
+
+def sample_triangle(pr, u1, u2, T, perturb=()):
+    """(the point uniform by area y = v1 + (1 - s) e1 + u2 s e2 with s = sqrt(u1), the normal the density is stated with)"""
+    v1, e1, e2, n = (a.astype(T) for a in triangle_light_record(pr))
+    if "tri_vertex_normal" in perturb:  # (a triangle without vertex normals: n tilted by 0.5 about e1, so the name never does nothing)
+        n1 = prim_normals(pr)[0].astype(T)
+        if not np.any(n1 != 0):
+            t = e1 / np.sqrt((e1 * e1).sum())
+            n1 = (np.cos(T(0.5)) * n + np.sin(T(0.5)) * np.cross(t, n)).astype(T)
+        n = n1
+    s = u1 if "tri_no_sqrt" in perturb else np.sqrt(u1)
+    return v1 + (1 - s)[:, None] * e1 + (u2 * s)[:, None] * e2, n
+
+
+def sample_quad(pr, u1, u2, T):
+    """(the point uniform by area y = Q + u1 u + u2 v, the quad's unit normal)"""
+    Q, u, v, n, _, _ = quad_record(pr, T)
+    return Q + u1[:, None] * u + u2[:, None] * v, n
+
+
+def sample_light(S, li, p, u1, u2, T, perturb=(), log=None):
     """for the vertices p that picked light li: (vector from p to the light point (a unit direction for the environment),
-    the light strategy's solid-angle density there, the emitted radiance towards p, the texel picked or NONE)"""
+    the light strategy's solid-angle density there, the emitted radiance towards p, the texel picked or NONE, delta: the light is
+    a point, spot or distant light, whose sample no BSDF ray can find: it counts at weight 1)"""
     L = S.lights[li]
     sel, pi = T(L["probability"]), T(np.pi)
     n = len(p)
@@ -551,7 +674,9 @@ def sample_light(S, li, p, u1, u2, T, perturb=()):
     if L["shape"] == ENVIRONMENT:
         ld = env_sample(S.env, u1, u2, T)
         rad, pe, texel = env_eval(S.env, ld, T)
-        return ld, sel * pe, rad, texel
+        return ld, sel * pe, rad, texel, False
+    if L["shape"] in DELTA_LIGHTS:
+        return AL.sample(L, S.analytic[li], p, u1, u2, T, perturb, log) + (texel, True)
     pr = S.prims[L["prim"]]
     f = pr["f"].astype(T)
     if L["shape"] == SPHERE:
@@ -579,29 +704,36 @@ def sample_light(S, li, p, u1, u2, T, perturb=()):
             pl = sel / (2 * pi * omc)
         outside = ~inside_sphere_light(S, li, p, T)  # a vertex inside the sphere takes no sample of it
         ld, pl = np.where(outside[:, None], ld, 0), np.where(outside, pl, 0)
-    else:
+    else:  # a point y uniform by area, with the normal ln there: p_l = selection / area x |ld|^2 / |ln . ld / |ld||
+        area = T(L["area"])
         if L["shape"] == CYLINDER:
             R, tr = _affine(pr["m"], T)
             phi = 2 * pi * u1
             q = np.stack([np.abs(f[0]) * np.cos(phi), np.abs(f[0]) * np.sin(phi), f[1] + u2 * (f[2] - f[1])], axis=1)
             y = q @ R.T + tr
             ln = np.stack([np.cos(phi), np.sin(phi), np.zeros_like(phi)], axis=1) @ R.T
+        elif L["shape"] == TRIANGLE:
+            y, ln = sample_triangle(pr, u1, u2, T, perturb)
+        elif L["shape"] == QUAD:
+            y, ln = sample_quad(pr, u1, u2, T)
+            if "quad_light_half_area" in perturb:
+                area = area * T(0.5)
         else:
             ka, aa, ba = _rect_axes(L["shape"])
             y = np.zeros((n, 3), T)
             y[:, aa], y[:, ba], y[:, ka] = f[0] + u1 * (f[1] - f[0]), f[2] + u2 * (f[3] - f[2]), f[4]
             ln = np.zeros((n, 3), T)
             ln[:, ka] = 1
-        ld = y - p
+        ld = (y - p).astype(T)
         d2 = _dot(ld, ld)
         with np.errstate(all="ignore"):
             cos_l = np.abs(_dot(ln, ld)) / np.sqrt(d2)
             if "no_cos" in perturb:
                 cos_l = np.ones_like(cos_l)
-            pl = sel / T(L["area"]) * d2 / cos_l
+            pl = sel / area * d2 / cos_l
     odd = checker_odd(p + ld, T)
     rad = np.where(odd[:, None], L["emission_odd"].astype(T), L["emission"].astype(T))
-    return ld.astype(T), pl.astype(T), rad, texel
+    return ld.astype(T), pl.astype(T), rad, texel, False
 
 
 # ---------------------------------------------------------------------------------------------------------------- the integrator
@@ -633,12 +765,22 @@ class _Draws:
         return out
 
 
-def trace(S, words, first_pixel=0, dtype=np.float64, perturb=(), shutter=None, probe=None):
+def trace(S, words, first_pixel=0, dtype=np.float64, perturb=(), shutter=None, probe=None, log=None):
     """One sample per row of `words` (the sample's stream as uint32 words), pixel ids first_pixel, first_pixel + 1, ... modulo the
     frame; `shutter`: the samples' shutter times, required where the scene has movers.  Returns (rgb [N][3], signature [N][*]
     int64, draws consumed [N]).  probe: a dict that receives the FIRST vertex of every sample (what a feature pass shows):
-    "glossy" (bool: it lies on a glossy material), "albedo" (F0 or rho there), "normal" (the shading normal).
-    perturb names deliberate mistakes, for the tests that show the comparison can fail.  Every name, in one place:
+    "glossy" (bool: it lies on a glossy material, rough glass and pbr among them), "albedo" (F0 or rho there; pbr: the base colour
+    c8 / 255), "normal" (the shading normal), "texture_value" (the colour an emitter, a lambertian or a plastic read from its
+    texture: zeros elsewhere).  log: a dict of new_log() that counts what the signature has no column for
+    (LOG_KEYS).
+    perturb names deliberate mistakes, for the tests that show the comparison can fail.  Every name, in one place (the model
+    files' docstrings say what each of theirs does):
+      ref64_noise.PERTURBATIONS, ref64_bump.PERTURBATIONS, ref64_normal_map.PERTURBATIONS, ref64_glass.PERTURBATIONS
+      ("fresnel_draw_last" is glass's name for "lobe_draw_last"), ref64_pbr.PERTURBATIONS, ref64_analytic_lights.PERTURBATIONS;
+      "tri_no_sqrt": a triangle light's barycentrics taken without the square root (s = u1): points crowd towards v2;
+      "tri_vertex_normal": a triangle light's density stated with its first vertex normal in place of the geometric one;
+      "quad_uv_swapped": a quad's (u, v) = (b, a);  "quad_light_half_area": a quad light's density stated with half the area;
+      "quad_front_flipped": a quad's front = den > 0 (the normal stays turned against the ray);
       "skip_draw", "no_cos", "mis_unsquared", "no_rr_light": at the light sample;
       "skip_flight": the free-flight draw left out (the distance is taken from the NEXT position instead: a wrong order of draws);
       "half_time": every sample at s = 0.5 (a renderer that ignores the shutter time);
@@ -648,9 +790,12 @@ def trace(S, words, first_pixel=0, dtype=np.float64, perturb=(), shutter=None, p
       "g1_for_g2": a glossy vertex's attenuation with G1(wo) in place of G2 (without the factor G2 / G1);
       "lobe_draw_last": plastic's lobe draw taken after u1, u2 instead of in front of them;
       "nee_albedo_pdf": a glossy vertex's light sample with f cos taken as albedo x pdf_b, the shortcut that holds for
-      lambertian and metal."""
+      lambertian and metal;
+      "delta_power_heuristic": the power heuristic applied to the sample of a point, spot or distant light."""
     T = dtype
     N = len(words)
+    log = new_log() if log is None else log
+    ul_last = "lobe_draw_last" in perturb or "fresnel_draw_last" in perturb
     D = _Draws(words, T)
     W, H = S.width, S.height
     pix = (first_pixel + np.arange(N)) % (W * H)
@@ -759,7 +904,7 @@ def trace(S, words, first_pixel=0, dtype=np.float64, perturb=(), shutter=None, p
         front = np.zeros(len(who), bool)
         mat = np.full(len(who), -1, np.int64)
         st = np.flatnonzero((mov < 0) & ~vol)
-        p[st], n[st], front[st] = hit_record(S, oo[st], dd[st], t_hit[st], idx[st], T, flat="flat_normals" in perturb)
+        p[st], n[st], front[st] = hit_record(S, oo[st], dd[st], t_hit[st], idx[st], T, perturb, log)
         mat[st] = S.prims["material"][idx[st]]
         for mi, m in enumerate(S.movers):
             q = np.flatnonzero((mov == mi) & ~vol)
@@ -777,10 +922,14 @@ def trace(S, words, first_pixel=0, dtype=np.float64, perturb=(), shutter=None, p
         event = np.full(len(who), NONE, np.int64)
         shutter_of = time[who] if len(S.movers) else None
 
-        def textured(k):  # the texture's value at the vertices k, with the image texel it read noted
-            value, texel = texture_value(S, tex[k], p[k], T, oo[k], dd[k], t_hit[k], idx[k], mov[k],
+        tex_read = np.zeros_like(dd)
+
+        def textured(k, of=None):  # the value at the vertices k of their material's texture (or of texture `of`), the image texel noted
+            value, texel = texture_value(S, tex[k] if of is None else np.full(len(k), of), p[k], T, oo[k], dd[k], t_hit[k], idx[k], mov[k],
                                          None if shutter_of is None else shutter_of[k], perturb)
-            note(C_IMAGE_TEXEL, who[k], texel)
+            if of is None:
+                note(C_IMAGE_TEXEL, who[k], texel)
+                tex_read[k] = value
             return value
         # ---- an emitter ends the path with what it emits
         em = kind == DIFFUSE_LIGHT
@@ -857,42 +1006,89 @@ def trace(S, words, first_pixel=0, dtype=np.float64, perturb=(), shutter=None, p
             new_d[die] = np.where(reflect[:, None], ud - 2 * _dot(ud, nn)[:, None] * nn, refracted)
             event[die] = np.where(reflect, EV_REFLECT, EV_REFRACT)
         # ---- the glossy materials: their draws where dielectric takes its Fresnel draw; none where wo.z <= 0
-        glo = np.isin(kind, (ROUGH_METAL, PLASTIC))
+        # Beside them rough glass (7r) and pbr (7t).  What the light sample needs again stands in the g_* arrays, per vertex: the
+        # lobe's alpha, whether the row is a plastic's (pbr: what ul chose), F0 (plastic: r0), rho (plastic and pbr: the body or base
+        # colour; rough glass: its tint Tr over the segment, 1 on a front hit) and, for rough glass, eta
+        glo = np.isin(kind, (ROUGH_METAL, PLASTIC, ROUGH_GLASS, PBR))
         g_alpha, g_f0, g_rho = np.zeros(len(who), T), np.zeros((len(who), 3), T), np.zeros((len(who), 3), T)
         g_plastic, g_ud = np.zeros(len(who), bool), np.zeros_like(dd)
+        g_eta = np.zeros(len(who), T)
         if glo.any():
             k = np.flatnonzero(glo)
+            kn, kg, kq = k[kind[k] != ROUGH_GLASS], k[kind[k] == ROUGH_GLASS], k[kind[k] == PBR]
             rec = S.mats[mat[k]]
             g_plastic[k] = rec["type"] == PLASTIC
             g_alpha[k] = alpha_of(rec["fuzz"]).astype(T)
-            g_f0[k] = np.where(g_plastic[k][:, None], r0_of(rec["ir"]).astype(T)[:, None], rec["albedo"].astype(T))
+            g_f0[k] = np.where(np.isin(rec["type"], (PLASTIC, PBR))[:, None], r0_of(rec["ir"]).astype(T)[:, None], rec["albedo"].astype(T))
+            rough = np.zeros(len(who), np.float32)  # the roughness that decides on the light sample: the material's; pbr: the hit's
+            rough[k] = rec["fuzz"]
             kp = k[g_plastic[k]]
             if len(kp):
                 g_rho[kp] = textured(kp)
+            if len(kg):  # the side from the hit record, the tint over t |d| with the material's sigma (its albedo words)
+                g_eta[kg] = GL.eta_of(S.mats["ir"][mat[kg]], front[kg], T, perturb)
+                sigma = S.mats["albedo"][mat[kg]]
+                tr = GL.tint(sigma, t_hit[kg] * np.sqrt(_dot(dd[kg], dd[kg])), T)
+                g_rho[kg] = np.where(front[kg][:, None] | ("no_absorption" in perturb), T(1), tr)
+                log["glass_tinted_back_hits"] += int((~front[kg] & (sigma > 0).any(axis=1)).sum())
+            m8 = np.zeros(len(who), T)
+            for pm in np.unique(mat[kq]):  # the bytes of the hit: from the base texture and the map under the factors rf, mf
+                q = kq[mat[kq] == pm]
+                base, mp = textured(q), np.ones((len(q), 3), T)
+                if S.pbr_maps[int(pm)] >= 0:
+                    mp = textured(q, S.pbr_maps[int(pm)])
+                c8, r8, m8[q] = PB.params(base, mp[:, 0] if "roughness_from_r" in perturb else mp[:, 1], mp[:, 2], S.mats["fuzz"][pm],
+                                          S.mats["albedo"][pm][0], T)
+                g_rho[q], rough[q], g_alpha[q] = PB.unit(c8, T), PB.unit(r8, np.float32), PB.alpha_of(PB.unit(r8, T), T)
+                for key, which in (("map", S.pbr_maps[int(pm)]), ("base", int(S.mats["texture"][pm]))):
+                    name = {IMAGE: "image", NOISE: "noise", CHECKER: "checker"}.get(int(S.texs["type"][which]) if which >= 0 else -1)
+                    if f"pbr_{name}_{key}_hits" in log:
+                        log[f"pbr_{name}_{key}_hits"] += len(q)
             g_ud[k] = _unit(dd[k])
             wo_z = -_dot(g_ud[k], n[k])
             dr = k[wo_z > 0]  # the vertices that draw
             ul, u1, u2 = np.zeros(len(who), T), np.zeros(len(who), T), np.zeros(len(who), T)
-            pd = dr[g_plastic[dr]]
-            if "lobe_draw_last" not in perturb:
+            pd = dr[kind[dr] != ROUGH_METAL]  # ul: plastic's lobe draw, rough glass's Fresnel draw, pbr's choice
+            if not ul_last:
                 ul[pd] = D.next(who[pd])
             u1[dr] = D.next(who[dr])
             u2[dr] = D.next(who[dr])
-            if "lobe_draw_last" in perturb:
+            if ul_last:
                 ul[pd] = D.next(who[pd])
-            wi, at, pdf, below, absorbed_wi, lobe = glossy_sample(n[k], g_ud[k], g_alpha[k], g_plastic[k], g_f0[k], g_rho[k], ul[k],
-                                                                  u1[k], u2[k], T, perturb)
-            new_d[k], att[k] = wi, at
-            scattered[k] = ~below & ~absorbed_wi
-            event[k] = np.where(below, EV_BELOW, np.where(g_plastic[k], np.where(lobe, np.where(absorbed_wi, EV_COAT_ABSORBED, EV_COAT), EV_BODY),
-                                                         np.where(absorbed_wi, EV_ROUGH_ABSORBED, EV_ROUGH)))
-            takes_light[k] = (rec["fuzz"] >= np.float32(GLOSSY_MIN_ROUGHNESS)) & ~below
-            pdf_b[k] = np.where(scattered[k], pdf, -1)
+            # pbr: ul < m is a rough metal of F0 = c, else a plastic of body c under the coat's r0, with ul rescaled
+            if len(kq):
+                metal, ul[kq] = PB.choose(m8[kq], ul[kq], T, perturb)
+                g_plastic[kq] = ~metal
+                g_f0[kq] = np.where(metal[:, None], T(0.04) if "metal_f0_004" in perturb else g_rho[kq], g_f0[kq])
+            wi, at, pdf = np.zeros_like(dd), np.zeros_like(dd), np.zeros(len(who), T)
+            below, absorbed_wi, lobe = np.zeros(len(who), bool), np.zeros(len(who), bool), np.zeros(len(who), bool)
+            if len(kn):
+                wi[kn], at[kn], pdf[kn], below[kn], absorbed_wi[kn], lobe[kn] = glossy_sample(
+                    n[kn], g_ud[kn], g_alpha[kn], g_plastic[kn], g_f0[kn], g_rho[kn], ul[kn], u1[kn], u2[kn], T, perturb)
+            if len(kg):  # (lobe: the ray was reflected)
+                wi[kg], at[kg], pdf[kg], below[kg], absorbed_wi[kg], lobe[kg] = GL.glass_sample(
+                    n[kg], g_ud[kg], g_alpha[kg], g_eta[kg], g_rho[kg], ul[kg], u1[kg], u2[kg], T, perturb, log)
+            if len(kq):
+                lobe[kq] |= metal  # (a pbr metal choice is signed EV_COAT)
+            new_d[k], att[k] = wi[k], at[k]
+            scattered[k] = ~below[k] & ~absorbed_wi[k]
+            event[k] = np.where(below[k], EV_BELOW, np.where(kind[k] != ROUGH_METAL,
+                                                             np.where(lobe[k], np.where(absorbed_wi[k], EV_COAT_ABSORBED, EV_COAT), EV_BODY),
+                                                             np.where(absorbed_wi[k], EV_ROUGH_ABSORBED, EV_ROUGH)))
+            takes_light[k] = (rough[k] >= np.float32(GLOSSY_MIN_ROUGHNESS)) & ~below[k]
+            pdf_b[k] = np.where(scattered[k], pdf[k], -1)
+            if len(kq):
+                log["pbr_vertices"] += len(kq)
+                log["pbr_below"] += int(below[kq].sum())
+                log["pbr_metal_choices"] += int((metal & ~below[kq]).sum())
+                log["pbr_plastic_choices"] += int((~metal & ~below[kq]).sum())
+                log["pbr_smooth_vertices"] += int((~takes_light[kq] & ~below[kq]).sum())
         if probe is not None and len(sig) == 2:
-            probe["glossy"], probe["albedo"], probe["normal"] = np.zeros(N, bool), np.zeros((N, 3), T), np.zeros((N, 3), T)
+            probe.update(glossy=np.zeros(N, bool), albedo=np.zeros((N, 3), T), normal=np.zeros((N, 3), T), texture_value=np.zeros((N, 3), T))
             probe["glossy"][who] = glo
             probe["albedo"][who] = np.where(g_plastic[:, None], g_rho, g_f0)
             probe["normal"][who] = n
+            probe["texture_value"][who] = tex_read
         note(C_EVENT, who, event)
         if not S.nee or len(S.lights) == 0:
             takes_light[:] = False
@@ -939,9 +1135,10 @@ def trace(S, words, first_pixel=0, dtype=np.float64, perturb=(), shutter=None, p
         Le = np.zeros((len(m), 3), T)
         texel = np.full(len(m), NONE, np.int64)
         inside = np.zeros(len(m), bool)
+        delta = np.zeros(len(m), bool)
         for li in np.unique(pick):
             sel = pick == li
-            ld[sel], pl[sel], Le[sel], texel[sel] = sample_light(S, li, p[ls][sel], u1[sel], u2[sel], T, perturb)
+            ld[sel], pl[sel], Le[sel], texel[sel], delta[sel] = sample_light(S, li, p[ls][sel], u1[sel], u2[sel], T, perturb, log)
             if S.lights[li]["shape"] == SPHERE:
                 inside[sel] = inside_sphere_light(S, li, p[ls][sel], T)
         note(C_TEXEL, m, texel)
@@ -957,8 +1154,19 @@ def trace(S, words, first_pixel=0, dtype=np.float64, perturb=(), shutter=None, p
             pb = np.where(wn > 0, pb, 0)
             if gl.any():
                 # f cos is not albedo x pdf_b at a glossy vertex: both are evaluated for the light's direction
-                q = ls[gl]
-                fc, pg = glossy_eval(n[q], g_ud[q], g_alpha[q], g_plastic[q], g_f0[q], g_rho[q], w[gl], T)
+                q, wl = ls[gl], w[gl]
+                fc, pg = np.zeros((len(q), 3), T), np.zeros(len(q), T)
+                a = g_alpha[q]
+                if "light_step_from_factors" in perturb:
+                    a = np.where(kind[q] == PBR, alpha_of(S.mats["fuzz"][mat[q]]).astype(T), a)
+                r, e = kind[q] != ROUGH_GLASS, kind[q] == ROUGH_GLASS
+                if r.any():  # (a pbr row as the material its vertex chose)
+                    fc[r], pg[r] = glossy_eval(n[q[r]], g_ud[q[r]], a[r], g_plastic[q[r]], g_f0[q[r]], g_rho[q[r]], wl[r], T)
+                if e.any():
+                    fc[e], pg[e] = GL.glass_eval(n[q[e]], g_ud[q[e]], a[e], g_eta[q[e]], g_rho[q[e]], wl[e], T)
+                log["glass_light_evaluations"] += int(e.sum())
+                log["pbr_light_evaluations"] += int((kind[q] == PBR).sum())
+                log["pbr_lit"] += int((fc[kind[q] == PBR] > 0).any(axis=1).sum())
                 if "nee_albedo_pdf" in perturb:
                     fc = np.where(g_plastic[q][:, None], g_rho[q], g_f0[q]) * pg[:, None]
                 pb[gl] = pg
@@ -968,6 +1176,8 @@ def trace(S, words, first_pixel=0, dtype=np.float64, perturb=(), shutter=None, p
             weight = pb * pl / (pl + pb if "mis_unsquared" in perturb else pl * pl + pb * pb)
             if gl.any():  # the glossy vertices' scalar part: p_l / (p_l^2 + pdf_b^2); f cos joins per channel below
                 weight = np.where(gl, pl / (pl + pb if "mis_unsquared" in perturb else pl * pl + pb * pb), weight)
+            if "delta_power_heuristic" not in perturb:  # a delta sample counts at weight 1: f cos x colour / p_l
+                weight = np.where(delta, np.where(gl, 1 / pl, pb / pl), weight)
         usable = (pl > 0) & (pb > 0) & (d2 > 0) & np.isfinite(weight) & (weight > 0)
         verdict = np.where(inside, SHADOW_INSIDE, SHADOW_NONE)
         if usable.any():
@@ -999,7 +1209,7 @@ def same_signature(a, b):
     return (pad(a) == pad(b)).all(axis=1)
 
 
-def tally(sig, S=None):
+def tally(sig, S=None, log=None):
     """How often the special vertices of DESIGN 7a occurred in a batch, read from its signatures, so that a test of such a case can
     assert that the case was there: light samples not made because the vertex lies inside the sphere light it picked, and BSDF
     hits on that light from inside kept at weight 1; absorbed metal vertices that took a light sample all the same; dielectric
@@ -1011,7 +1221,9 @@ def tally(sig, S=None):
     vertex, and the samples that met one after a medium event; emitter hits at full weight behind a vertex that took a light
     sample (the emitter is no listed light); and, where the RefScene S says which primitives are triangles and which carry
     an image texture, vertices on triangles, those that took a light sample, and shadow rays stopped by either kind.  Of 7m
-    (ref64_glossy.GLOSSY_KEYS and more): what ref64_glossy.glossy_tally() counts."""
+    (ref64_glossy.GLOSSY_KEYS and more): what ref64_glossy.glossy_tally() counts (by the material's roughness: a pbr vertex's is
+    its hit's, which the log counts as pbr_smooth_vertices).  Of 7n-7u, with S: _extension_tally()'s counts.  With the `log` that
+    trace() filled: its counters (LOG_KEYS), which hold what the signature has no column for."""
     v = sig[:, SAMPLE_COLUMNS:].reshape(len(sig), -1, VERTEX_COLUMNS)
     event, light, shadow, how, alias, mover = (v[:, :, c] for c in (C_EVENT, C_LIGHT, C_SHADOW, C_HIT_WEIGHT, C_ALIAS, C_MOVER))
     prim, blocker = v[:, :, C_PRIM], v[:, :, C_BLOCKER]
@@ -1031,11 +1243,18 @@ def tally(sig, S=None):
     on_mover, on_static = vertex & (mover >= 0), vertex & (mover < 0)
     on_tri = on_static & ~med & of(is_tri, prim)
     env_light = len(S.lights) - 1 if S is not None and len(S.lights) and S.lights[-1]["shape"] == ENVIRONMENT else -1
-    glossy = glossy_tally(event, dict(prim=prim, light=light, env_light=env_light, took_light=light != NONE,
+    roughness = None
+    if S is not None:  # a material's roughness; pbr: the byte of its factor, as every hit has it, where no map scales it
+        roughness = S.mats["fuzz"].astype(np.float64)
+        for m, mp in S.pbr_maps.items():
+            roughness[m] = PB.unit(PB.byte(roughness[m], np.float64), np.float32) if mp < 0 else np.nan
+    glossy = glossy_tally(event, dict(prim=prim, light=light, env_light=env_light, took_light=light != NONE, roughness=roughness,
                                       clear=shadow == SHADOW_CLEAR, medium=med, on_mover=mover >= 0,
                                       full_weight_emitter=(event == EV_EMIT) & (how == HIT_UNSAMPLED),
                                       missed_to_texel=v[:, :, C_MISS_TEXEL] != NONE, lost=v[:, :, C_ROULETTE] == 1), S)
-    return dict(glossy, inside_no_sample=int((shadow == SHADOW_INSIDE).sum()), inside_full_weight_hits=int((how == HIT_FROM_INSIDE).sum()),
+    ext = _extension_tally(v, S) if S is not None else {}
+    return dict(glossy, **ext, **(log or {}),
+                inside_no_sample=int((shadow == SHADOW_INSIDE).sum()), inside_full_weight_hits=int((how == HIT_FROM_INSIDE).sum()),
                 absorbed_metal_light_samples=int(((event == EV_METAL_ABSORBED) & (light != NONE)).sum()),
                 dielectric_vertices=int(glass.sum()), dielectric_light_samples=int((glass & (light != NONE)).sum()),
                 dielectric_full_weight_hits=int((glass[:, :-1] & (how[:, 1:] == HIT_UNSAMPLED)).sum()),
@@ -1055,6 +1274,77 @@ def tally(sig, S=None):
                 triangle_vertices_with_light_sample=int((on_tri & (light != NONE)).sum()),
                 shadow_stopped_by_triangle=int(of(is_tri, blocker).sum()),
                 shadow_stopped_by_image_prim=int(of(is_image, blocker).sum()))
+
+
+def _extension_tally(v, S):
+    """tally()'s counts of DESIGN 7n-7u from the signature's vertex blocks v [N][vertices][columns], by the RefScene's records: what
+    the cases of each extension are there for.  Triangle lights (triangle_*) and quads (quad_*): light samples that picked one,
+    their shadow rays' verdicts, BSDF hits on one by weight (C_FRONT is no column: the two sides of a cube are told apart by the
+    event that follows); other_picks: light samples of a light that is neither.  Noise (noise_*): surface vertices whose material's
+    texture is a noise texture, by material type, and the share of samples with one.  Bumps (bump_*) and normal maps (nm_*): the
+    static surface vertices whose material carries one, by material and (nm) primitive type.  Rough glass (glass_*): its vertices
+    by event, with a light sample, the emitter hits behind them by weight, the roughnesses met.  Point, spot and distant lights:
+    picks per type, their shadow rays, glossy vertices one of them lit, emitter hits weighted by MIS."""
+    N = len(v)
+    event, light, shadow, how, prim, blocker, mover = (v[:, :, c] for c in (C_EVENT, C_LIGHT, C_SHADOW, C_HIT_WEIGHT, C_PRIM, C_BLOCKER, C_MOVER))
+    pick = lambda flags, i: (i >= 0) & np.asarray(flags, bool)[np.clip(i, 0, max(len(flags) - 1, 0))] if len(flags) else np.zeros(i.shape, bool)
+    count = lambda x: int(x.sum())
+    nxt = lambda x: np.concatenate([x[:, 1:], np.zeros((N, 1), bool)], axis=1)
+    took, emit = light != NONE, event == EV_EMIT
+    # ---- the lights by shape
+    shape = S.lights["shape"]
+    of = lambda kind: pick(shape == kind, light)
+    tri_pick, quad_pick = of(TRIANGLE), of(QUAD)
+    delta = of(POINT) | of(SPOT) | of(DISTANT)
+    light_prim = lambda kind: np.isin(np.arange(len(S.prims)), S.lights["prim"][shape == kind])
+    on_tri_light, on_quad = emit & pick(light_prim(TRIANGLE), prim), pick(S.prims["type"] == QUAD, prim)
+    glossy = np.isin(event, GLOSSY_EVENTS)
+    out = dict(triangle_picks=count(tri_pick), quad_picks=count(quad_pick), other_picks=count((light >= 0) & ~tri_pick & ~quad_pick),
+               triangle_shadow_stopped=count(tri_pick & (shadow == SHADOW_OCCLUDED)), triangle_shadow_clear=count(tri_pick & (shadow == SHADOW_CLEAR)),
+               triangle_mis_hits=count(on_tri_light & (how == HIT_MIS)), triangle_full_weight_hits=count(on_tri_light & (how == HIT_UNSAMPLED)),
+               quad_vertices=count(on_quad), quad_shadow_stops=count((shadow == SHADOW_OCCLUDED) & pick(S.prims["type"] == QUAD, blocker)),
+               quad_refractions=count(on_quad & (event == EV_REFRACT)), quad_reflections=count(on_quad & (event == EV_REFLECT)),
+               quad_emitter_hits=count(on_quad & emit), quad_mis_hits=count(on_quad & emit & (how == HIT_MIS)),
+               point_picks=count(of(POINT)), spot_picks=count(of(SPOT)), distant_picks=count(of(DISTANT)), area_picks=count((light >= 0) & ~delta),
+               analytic_shadow_occluded=count(delta & (shadow == SHADOW_OCCLUDED)), analytic_shadow_clear=count(delta & (shadow == SHADOW_CLEAR)),
+               analytic_no_shadow_ray=count(delta & (shadow == SHADOW_NONE)), glossy_lit_by_analytic=count(glossy & delta & (shadow == SHADOW_CLEAR)),
+               emitter_mis_hits=count(emit & (how == HIT_MIS)))
+    # ---- the material under every surface vertex: a mover's is its own; a medium event is no surface
+    surface = (event != NONE) & (event != EV_MISS) & (event != EV_MEDIUM)
+    on_mover = mover >= 0 if len(S.movers) else np.zeros(event.shape, bool)
+    static = surface & (prim >= 0) & ~on_mover
+    mat = np.where(prim >= 0, S.prims["material"][np.clip(prim, 0, max(len(S.prims) - 1, 0))], -1) if len(S.prims) else np.full(event.shape, -1)
+    if len(S.movers):
+        mat = np.where(on_mover, S.movers["material"][np.clip(mover, 0, len(S.movers) - 1)], mat)
+    mat = np.where(surface, mat, -1)
+    mtype = np.where(mat >= 0, S.mats["type"][np.clip(mat, 0, len(S.mats) - 1)], -1)
+    tex = np.where(mat >= 0, S.mats["texture"][np.clip(mat, 0, len(S.mats) - 1)], -1)
+    noisy = np.isin(mtype, (LAMBERTIAN, DIFFUSE_LIGHT, PLASTIC)) & (tex >= 0) & (S.texs["type"][np.clip(tex, 0, len(S.texs) - 1)] == NOISE)
+    out.update(noise_vertices=count(noisy), noise_share=float(noisy.any(axis=1).mean()), noise_lambertian=count(noisy & (mtype == LAMBERTIAN)),
+               noise_plastic=count(noisy & (mtype == PLASTIC)), noise_emitter=count(noisy & (mtype == DIFFUSE_LIGHT)),
+               noise_plastic_light_samples=count(noisy & (mtype == PLASTIC) & took), noise_mover=count(noisy & on_mover),
+               noise_textures=sorted(int(t) for t in np.unique(tex[noisy])))
+    kinds = (("lambertian", LAMBERTIAN), ("metal", METAL), ("dielectric", DIELECTRIC), ("rough_metal", ROUGH_METAL), ("plastic", PLASTIC))
+    for prefix, carriers, more in (("bump_", S.bumps, ()), ("nm_", S.normal_maps, (("rough_glass", ROUGH_GLASS), ("pbr", PBR)))):
+        on = static & np.isin(mat, list(carriers))
+        out.update({prefix + "vertices": count(on), prefix + "share": float(on.any(axis=1).mean()), prefix + "light_samples": count(on & took)})
+        out.update({prefix + name: count(on & (mtype == kind)) for name, kind in kinds + more})
+    on = static & np.isin(mat, list(S.normal_maps))
+    ptype = np.where(on, S.prims["type"][np.clip(prim, 0, max(len(S.prims) - 1, 0))], -1) if len(S.prims) else np.full(event.shape, -1)
+    for name, shapes in (("sphere", (SPHERE,)), ("rect", (XY_RECT, XZ_RECT, YZ_RECT)), ("cylinder", (CYLINDER,)), ("triangle", (TRIANGLE,)), ("quad", (QUAD,))):
+        out["nm_on_" + name] = count(np.isin(ptype, shapes))
+    # ---- rough glass
+    on = glossy & (mtype == ROUGH_GLASS)
+    emit_full, emit_mis = emit & (how == HIT_UNSAMPLED), emit & (how == HIT_MIS)
+    rough = S.mats["fuzz"][np.clip(mat, 0, len(S.mats) - 1)][on & ~on_mover]
+    out.update(glass_vertices=count(on), glass_mover_vertices=count(on & on_mover), glass_reflect_events=count(on & (event == EV_COAT)),
+               glass_refract_events=count(on & (event == EV_BODY)), glass_below_events=count(on & (event == EV_BELOW)),
+               glass_light_samples=count(on & took), glass_below_light_samples=count(on & (event == EV_BELOW) & took),
+               glass_full_weight_hits_behind_refraction=count(on & (event == EV_BODY) & took & nxt(emit_full)),
+               glass_mis_hits_behind_reflection=count(on & (event == EV_COAT) & nxt(emit_mis)),
+               glass_then_medium=count((np.cumsum(on & (event == EV_BODY), axis=1) > 0) & (event == EV_MEDIUM)),
+               glass_roughnesses=sorted(float(np.float32(x)) for x in np.unique(rough)))
+    return out
 
 
 MEDIA_KEYS = ("medium_events", "medium_then_surface", "medium_behind_glass", "media_with_events")
@@ -1088,10 +1378,11 @@ def implied_alias_probability(thr, alias):
 # ---------------------------------------------------------------------------------------------------------------- the comparison
 def reference(S, words, shutter=None):
     """the fp64 radiance, which samples took the same branches at fp32 (the stable ones), the draws consumed, and the tally of the
-    fp64 run's special vertices"""
-    rgb, sig64, draws = trace(S, words, shutter=shutter)
+    fp64 run's special vertices, its log among them"""
+    log = new_log()
+    rgb, sig64, draws = trace(S, words, shutter=shutter, log=log)
     _, sig32, _ = trace(S, words, dtype=np.float32, shutter=shutter)
-    return rgb, same_signature(sig64, sig32), draws, tally(sig64, S)
+    return rgb, same_signature(sig64, sig32), draws, tally(sig64, S, log)
 
 
 def judge(got, ref, stable):

@@ -13,37 +13,26 @@ What the host derives in fp64 and rounds once is derived here the same way from 
 distant light's negated: towards the light), cos_o, inv = min(1 / (cos_i - cos_o), FLT_MAX), omc, the folded colour, and D = 4 x
 the half diagonal of the primitives' bounding box (bound_radius, restated here).
 
-ref64.py is not edited and its loop is not restated.  ref64.trace applies the power heuristic pb pl / (pl^2 + pb^2) to every
-light sample; installed() states weight 1 through it by returning (ld, K pl, K colour) with a power of two K: the product
-pb (K pl) (K colour) / ((K pl)^2 + pb^2) is pb colour / pl up to the relative term pb^2 / (K pl)^2.  K = 2^100 at float64 and
-2^40 at float32; both conditions -- (K pl)^2 finite, and pb_max^2 / (K pl)^2 below a quarter of the type's epsilon, with pb_max
-a bound of the scene's BSDF densities (pb_bound) -- are checked on every call, and a violation raises ArithmeticError (with a
-`report` dict, a term that does not vanish is counted there instead: a run whose radiance is discarded, the fp32 signatures).
-The shadow ray's far end of 0.999 is what ref64 gives every light that is not the environment.
+This file holds the model alone and imports nothing of ref64.  RefScene keeps record() of every analytic light;
+ref64.sample_light calls sample() and tells trace() that the sample is a delta sample, and trace() adds f cos x colour / pl
+without the power heuristic.  The shadow ray's far end of 0.999 is what ref64 gives every light that is not the environment.
+sample() counts the spot samples by falloff into trace()'s log, under LOG_KEYS.
 
 Deliberate mistakes (names in `perturb`):
   point_no_inverse_square   pl = psel for point and spot lights
   spot_linear_falloff       falloff = s
   distant_unfolded          the colour E without 2 / (1 + cos alpha)
-  delta_power_heuristic     K = 1: the power heuristic applied to the sample
+  delta_power_heuristic     the power heuristic applied to the sample (trace()'s own)
 """
-import contextlib
-
 import numpy as np
 
-import ref64 as R
-import ref64_glass as RG
+from ref64_base import SPHERE, XY_RECT, XZ_RECT, YZ_RECT, CYLINDER, TRIANGLE, _dot, _rect_axes
 
 POINT, SPOT, DISTANT = 101, 102, 103
 PERTURBATIONS = ("point_no_inverse_square", "spot_linear_falloff", "distant_unfolded", "delta_power_heuristic")
 FLT_MAX = float(np.finfo(np.float32).max)
-K_OF = {np.dtype(np.float64): 2.0 ** 100, np.dtype(np.float32): 2.0 ** 40}
-LOG_KEYS = ("point_samples", "spot_samples", "distant_samples", "spot_falloff_zero", "spot_falloff_partial", "spot_falloff_one",
-            "distant_alpha_zero_samples")
-
-
-def new_log():
-    return dict.fromkeys(LOG_KEYS, 0)
+LOG_KEYS = tuple("analytic_" + k for k in ("point_samples", "spot_samples", "distant_samples", "spot_falloff_zero", "spot_falloff_partial",
+                                           "spot_falloff_one", "distant_alpha_zero_samples"))
 
 
 def luminance(c):
@@ -61,20 +50,20 @@ def bound_radius(prims):
             lo, hi = np.minimum(lo, p), np.maximum(hi, p)
     for p in prims:
         f, m, t = p["f"].astype(np.float64), p["m"].astype(np.float64), int(p["type"])
-        if t == R.SPHERE:
+        if t == SPHERE:
             add(f[:3] - abs(f[3]), f[:3] + abs(f[3]))
-        elif t in (R.XY_RECT, R.XZ_RECT, R.YZ_RECT):
-            ka, aa, ba = R._rect_axes(t)
+        elif t in (XY_RECT, XZ_RECT, YZ_RECT):
+            ka, aa, ba = _rect_axes(t)
             for a, b in ((f[0], f[2]), (f[1], f[3])):
                 q = np.zeros(3)
                 q[aa], q[ba], q[ka] = a, b, f[4]
                 add(q)
-        elif t == R.CYLINDER:
+        elif t == CYLINDER:
             r = abs(f[0])
             for k in range(8):
                 q = np.array([r if k & 1 else -r, r if k & 2 else -r, f[2] if k & 4 else f[1], 1.0])
                 add(m.reshape(3, 4) @ q)
-        elif t == R.TRIANGLE:
+        elif t == TRIANGLE:
             add(m[0:3], m[3:6], m[6:9])
         else:  # a quad: Q, Q + u, Q + u + v, Q + v
             add(m[0:3], m[0:3] + m[3:6], m[0:3] + m[3:6] + m[6:9], m[0:3] + m[6:9])
@@ -110,36 +99,11 @@ def record(al, radius):
     return out
 
 
-def attach(S, sc):
-    """give the RefScene the records of the scene's analytic lights, by index into S.lights (a light whose weight is not
-    positive and finite is in neither list)"""
-    radius = bound_radius(sc.prims())
-    recs = [record(al, radius) for al in sc.analytic_lights()]
-    recs = [r for r in recs if r["weight"] > 0 and np.isfinite(r["weight"])]
-    at = [i for i, l in enumerate(S.lights) if l["shape"] in (POINT, SPOT, DISTANT)]
-    assert len(at) == len(recs) and all(S.lights[i]["shape"] == r["type"] for i, r in zip(at, recs)), (at, [r["type"] for r in recs])
-    S.analytic = dict(zip(at, recs))
-    return S
-
-
-def pb_bound(S):
-    """a bound of the BSDF densities a light sample can meet: lambertian 1 / pi; metal of fuzz f: 3 (1 + f)^2 / (2 pi f^2); a
-    GGX lobe of alpha = max(r^2, 1e-3): G1 D / (4 wo.z) <= 1 / (2 pi alpha^3)"""
-    b = 1 / np.pi
-    for m in S.mats:
-        f = float(m["fuzz"])
-        if m["type"] == R.METAL and f >= R.METAL_MIN_FUZZ:
-            b = max(b, 3 * (1 + f) ** 2 / (2 * np.pi * f * f))
-        elif m["type"] in (R.ROUGH_METAL, R.PLASTIC, RG.ROUGH_GLASS) and f >= R.GLOSSY_MIN_ROUGHNESS:
-            b = max(b, 1 / (2 * np.pi * max(f * f, 1e-3) ** 3) + 1 / np.pi)
-    return b
-
-
 def falloff_of(rec, ld, T, perturb=()):
     """the spot's falloff towards the vertex at -ld from it"""
     a = np.atleast_2d(np.asarray(rec["axis"]).astype(T))  # (one axis, or one per vertex)
     with np.errstate(all="ignore"):
-        c = -R._dot(a, ld) / np.sqrt(R._dot(ld, ld))
+        c = -_dot(a, ld) / np.sqrt(_dot(ld, ld))
         s = np.clip((c - np.asarray(rec["cos_o"]).astype(T)) * np.asarray(rec["inv"]).astype(T), 0, 1)
     s = np.where(np.isnan(s), 0, s).astype(T)
     return s if "spot_linear_falloff" in perturb else s * s * (3 - 2 * s)
@@ -160,9 +124,8 @@ def cone_direction(t, omc, u1, u2, T):
     return ((sth * np.cos(phi))[:, None] * t1 + (sth * np.sin(phi))[:, None] * t2 + cth[:, None] * a).astype(T)
 
 
-def sample(S, li, p, u1, u2, T, perturb=(), log=None):
-    """(ld, pl, colour) of the analytic light li at the vertices p, at its true scale (no K)"""
-    L, rec = S.lights[li], S.analytic[li]
+def sample(L, rec, p, u1, u2, T, perturb=(), log=None):
+    """(ld, pl, colour) at the vertices p of the analytic light with the light record L and the record() rec"""
     sel = T(L["probability"])
     n = len(p)
     colour = np.broadcast_to(L["emission"].astype(T), (n, 3)).copy()
@@ -172,90 +135,22 @@ def sample(S, li, p, u1, u2, T, perturb=(), log=None):
         if "distant_unfolded" in perturb:
             colour = (colour / T(rec["fold"])).astype(T)
         if log is not None:
-            log["distant_samples"] += n
-            log["distant_alpha_zero_samples"] += n if rec["omc"] == 0 else 0
+            log["analytic_distant_samples"] += n
+            log["analytic_distant_alpha_zero_samples"] += n if rec["omc"] == 0 else 0
         return ld, pl, colour
     ld = (rec["x"].astype(T) - p).astype(T)
-    d2 = R._dot(ld, ld)
+    d2 = _dot(ld, ld)
     pl = np.full(n, sel, T) if "point_no_inverse_square" in perturb else (sel * d2).astype(T)
     if rec["type"] == SPOT:
         fall = falloff_of(rec, ld, T, perturb)
-        # (the falloff on the colour, not under pl: the same product, and K pl stays in range at a falloff of 1e-30)
+        # (the falloff on the colour, not under pl: the same product, and pl stays in range at a falloff of 1e-30)
         pl = np.where(fall > 0, pl, 0).astype(T)
         colour = (colour * fall[:, None]).astype(T)
         if log is not None:
-            log["spot_samples"] += n
-            log["spot_falloff_zero"] += int((fall == 0).sum())
-            log["spot_falloff_one"] += int((fall == 1).sum())
-            log["spot_falloff_partial"] += int(((fall > 0) & (fall < 1)).sum())
+            log["analytic_spot_samples"] += n
+            log["analytic_spot_falloff_zero"] += int((fall == 0).sum())
+            log["analytic_spot_falloff_one"] += int((fall == 1).sum())
+            log["analytic_spot_falloff_partial"] += int(((fall > 0) & (fall < 1)).sum())
     elif log is not None:
-        log["point_samples"] += n
+        log["analytic_point_samples"] += n
     return ld, np.where(d2 > 0, pl, 0).astype(T), colour
-
-
-@contextlib.contextmanager
-def installed(perturb=(), log=None, report=None):
-    """ref64.sample_light with the analytic lights of an attach()ed RefScene, for the length of the block"""
-    original = R.sample_light
-
-    def sample_light(S, li, p, u1, u2, T, perturb_=()):
-        if S.lights[li]["shape"] not in (POINT, SPOT, DISTANT):
-            return original(S, li, p, u1, u2, T, perturb_)
-        ld, pl, colour = sample(S, li, p, u1, u2, T, tuple(perturb) + tuple(perturb_), log)
-        K = 1.0 if "delta_power_heuristic" in perturb else K_OF[np.dtype(T)]
-        with np.errstate(all="ignore"):
-            kpl = (T(K) * pl).astype(T)
-            made = kpl[pl > 0]
-            if K != 1.0 and len(made):
-                if not np.isfinite(made * made).all():
-                    raise ArithmeticError(f"(K pl)^2 overflows {np.dtype(T)} at K = 2^{int(np.log2(K))}")
-                late = int((pb_bound(S) ** 2 / (made.astype(np.float64) ** 2) > np.finfo(T).eps / 4).sum())
-                if late and report is None:
-                    raise ArithmeticError(f"pb^2 / (K pl)^2 does not vanish at {np.dtype(T)} for {late} samples (K = 2^{int(np.log2(K))})")
-                if late:
-                    report["not_vanishing"] = report.get("not_vanishing", 0) + late
-        return ld, kpl, (T(K) * colour).astype(T), np.full(len(p), R.NONE, np.int64)
-    R.sample_light = sample_light
-    try:
-        yield
-    finally:
-        R.sample_light = original
-
-
-def trace(S, words, perturb=(), log=None, report=None, sc=None, **kw):
-    """ref64.trace through ref64_glass (rough glass, quads and, with sc, bumps) with the analytic lights installed"""
-    rest = tuple(x for x in perturb if x not in PERTURBATIONS)
-    with installed(perturb, log, report):
-        return RG.trace(S, words, perturb=rest, sc=sc, **kw)
-
-
-def reference(S, words, sc=None):
-    """ref64.reference's four results, the tally extended by tally() and the log of the fp64 run"""
-    log, glass_log = new_log(), RG.new_log()
-    with installed((), log):
-        rgb, sig64, draws = RG.trace(S, words, log=glass_log, sc=sc)
-    with installed((), None, {}):  # (the fp32 run's radiance is discarded: its signatures say which samples are stable)
-        _, sig32, _ = RG.trace(S, words, dtype=np.float32, sc=sc)
-    P = RG.present(S)
-    return rgb, R.same_signature(sig64, sig32), draws, dict(R.tally(sig64, P), **RG.tally(sig64, P, glass_log), **tally(sig64, S, log))
-
-
-def tally(sig, S, log):
-    """What an analytic-light case is there for.  From the signatures: light samples per type, their shadow rays occluded and
-    clear, glossy vertices (rough metal, plastic, rough glass events) that took a sample of an analytic light and had it arrive,
-    emitter hits weighted by MIS.  From the wrapper's log: the spot samples by falloff (LOG_KEYS)."""
-    v = sig[:, R.SAMPLE_COLUMNS:].reshape(len(sig), -1, R.VERTEX_COLUMNS)
-    event, light, shadow, how = (v[:, :, c] for c in (R.C_EVENT, R.C_LIGHT, R.C_SHADOW, R.C_HIT_WEIGHT))
-    shape = S.lights["shape"] if len(S.lights) else np.zeros(1, np.int32)
-    of = lambda kind: (light >= 0) & (shape[np.clip(light, 0, len(shape) - 1)] == kind)
-    delta = of(POINT) | of(SPOT) | of(DISTANT)
-    glossy = np.isin(event, RG.G.GLOSSY_EVENTS)
-    out = {"analytic_" + k: v for k, v in log.items()}
-    out.update(point_picks=int(of(POINT).sum()), spot_picks=int(of(SPOT).sum()), distant_picks=int(of(DISTANT).sum()),
-               area_picks=int(((light >= 0) & ~delta).sum()),
-               analytic_shadow_occluded=int((delta & (shadow == R.SHADOW_OCCLUDED)).sum()),
-               analytic_shadow_clear=int((delta & (shadow == R.SHADOW_CLEAR)).sum()),
-               analytic_no_shadow_ray=int((delta & (shadow == R.SHADOW_NONE)).sum()),
-               glossy_lit_by_analytic=int((glossy & delta & (shadow == R.SHADOW_CLEAR)).sum()),
-               emitter_mis_hits=int(((event == R.EV_EMIT) & (how == R.HIT_MIS)).sum()))
-    return out

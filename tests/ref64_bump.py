@@ -13,22 +13,19 @@ ref64_noise's lattice_hash, grad and fade:
     the bump: n the face-turned shading normal, g the face-turned geometric one, sigma = +1 front / -1 back, G = grad s(p):
               Gt = G - (G . n) n,  b = n - sigma k Gt,  n' = b / |b|;  n' replaces n iff finite, n' . g > 0, n' . (-unit(d)) > 0
 
-ref64.py is not edited.  installed(sc) replaces ref64.hit_record for the length of a block: the wrapper calls the original, once
-more with flat=True for g, finds each hit's material (S.prims["material"][idx]) and its bump (sc.bump(material)), applies the rule
-and hands every other hit through.  Movers do not go through hit_record in ref64.trace: a bumped mover is refused by the product.
+This file holds the model alone and imports nothing of ref64: ref64.hit_record finds each hit's material and its bump (RefScene
+read them from Scene.bump), calls gradient_of() and bump() and counts what the signature does not keep into trace()'s log.
 
-Deliberate mistakes (names in `perturb`, handled by the wrapper):
+Deliberate mistakes (names in `perturb`, as ref64.trace takes them; bump_off is hit_record's own):
   bump_off                     no perturbation
   bump_full_gradient           G in place of Gt
   bump_back_unsigned           sigma = 1 on back hits
   bump_cubic_fade_derivative   w' = 6 t (1 - t)
 """
-import contextlib
-
 import numpy as np
 
-import ref64 as R
 import ref64_noise as N
+from ref64_base import _dot, _unit
 
 PERTURBATIONS = ("bump_off", "bump_full_gradient", "bump_back_unsigned", "bump_cubic_fade_derivative")
 LIMIT = 2.0 ** 30
@@ -111,98 +108,9 @@ def bump(n, g, d, front, k, G, T, perturb=()):
     """(n' where the rule accepts it, else n; accepted [n] bool).  k: the strength, one or one per vertex"""
     k = np.asarray(k, np.float32).astype(T)
     sigma = np.ones(len(n), T) if "bump_back_unsigned" in perturb else np.where(front, T(1), T(-1))
-    Gt = G if "bump_full_gradient" in perturb else G - R._dot(G, n)[:, None] * n
+    Gt = G if "bump_full_gradient" in perturb else G - _dot(G, n)[:, None] * n
     with np.errstate(all="ignore"):
         b = n - (sigma * k)[:, None] * Gt
-        nb = b / np.sqrt(R._dot(b, b))[:, None]
-        ok = np.isfinite(nb).all(axis=1) & (R._dot(nb, g) > 0) & (R._dot(nb, -R._unit(d)) > 0)
+        nb = b / np.sqrt(_dot(b, b))[:, None]
+        ok = np.isfinite(nb).all(axis=1) & (_dot(nb, g) > 0) & (_dot(nb, -_unit(d)) > 0)
     return np.where(ok[:, None], nb, n).astype(T), ok
-
-
-def new_log():
-    """what installed() counts: bumped vertices in all, on back faces, and where a guard kept n"""
-    return dict(bumped=0, back=0, kept=0)
-
-
-@contextlib.contextmanager
-def installed(sc, perturb=(), log=None):
-    """ref64.hit_record with the bumps of the product scene sc, for the length of the block.  log: a dict of new_log() that
-    counts the bumped vertices of every call"""
-    original = R.hit_record
-    bumps = {}
-    for m in range(len(sc.materials())):
-        b = sc.bump(m)
-        if b is not None:
-            bumps[m] = (sc.noise(b[0]), np.float32(b[1]))
-
-    def hit_record(S, o, d, t, idx, T, flat=False):
-        p, n, front = original(S, o, d, t, idx, T, flat)
-        mat = S.prims["material"][idx]
-        which = np.isin(mat, list(bumps))
-        if not which.any() or "bump_off" in perturb:
-            return p, n, front
-        _, g, _ = original(S, o, d, t, idx, T, True)
-        n = n.copy()
-        for m in np.unique(mat[which]):
-            sel = mat == m
-            par, k = bumps[int(m)]
-            G = gradient_of(p[sel], par, T, perturb)
-            n[sel], ok = bump(n[sel], g[sel], d[sel], front[sel], k, G, T, perturb)
-            if log is not None:
-                log["bumped"] += int(sel.sum())
-                log["back"] += int((~front[sel]).sum())
-                log["kept"] += int((~ok).sum())
-        return p, n, front
-    R.hit_record = hit_record
-    try:
-        yield
-    finally:
-        R.hit_record = original
-
-
-def _rest(perturb):
-    return tuple(x for x in perturb if x not in PERTURBATIONS)
-
-
-def _noise(sc):
-    mats, texs = sc.materials(), sc.textures()
-    used = [int(m["texture"]) for m in mats if int(m["texture"]) >= 0]
-    return any(int(texs[t]["type"]) == N.NOISE for t in used)
-
-
-def trace(sc, S, words, perturb=(), log=None, **kw):
-    with contextlib.ExitStack() as stack:
-        stack.enter_context(installed(sc, perturb, log))
-        if _noise(sc):
-            stack.enter_context(N.installed(sc))
-        return R.trace(S, words, perturb=_rest(perturb), **kw)
-
-
-def reference(sc, S, words, shutter=None):
-    with contextlib.ExitStack() as stack:
-        stack.enter_context(installed(sc))
-        if _noise(sc):
-            stack.enter_context(N.installed(sc))
-        return R.reference(S, words, shutter)
-
-
-def tally(sig, S, sc, log=None):
-    """What a bump case is there for.  From the reference's signatures: the surface vertices whose material carries a bump, by
-    material type, and the share of samples with at least one.  From the wrapper's log (the signatures keep neither the side nor
-    the guards): the bumped vertices on back faces and those where a guard kept n."""
-    v = sig[:, R.SAMPLE_COLUMNS:].reshape(len(sig), -1, R.VERTEX_COLUMNS)
-    event, prim = v[:, :, R.C_EVENT], v[:, :, R.C_PRIM]
-    surface = (event != R.NONE) & (event != R.EV_MISS) & (event != R.EV_MEDIUM) & (prim >= 0)
-    if len(S.movers):
-        surface &= ~(v[:, :, R.C_MOVER] >= 0)
-    mat = np.where(surface, S.prims["material"][np.clip(prim, 0, len(S.prims) - 1)], -1)
-    bumped = np.isin(mat, [m for m in range(len(S.mats)) if sc.bump(m) is not None])
-    mtype = np.where(bumped, S.mats["type"][np.clip(mat, 0, len(S.mats) - 1)], -1)
-    out = dict(bump_vertices=int(bumped.sum()), bump_share=float(bumped.any(axis=1).mean()))
-    for name, kind in (("lambertian", R.LAMBERTIAN), ("metal", R.METAL), ("dielectric", R.DIELECTRIC), ("rough_metal", R.ROUGH_METAL),
-                       ("plastic", R.PLASTIC)):
-        out["bump_" + name] = int((mtype == kind).sum())
-    out["bump_light_samples"] = int((bumped & (v[:, :, R.C_LIGHT] != R.NONE)).sum())
-    if log is not None:
-        out["bump_back"], out["bump_kept"] = log["back"], log["kept"]
-    return out

@@ -14,6 +14,8 @@ EV_BELOW (absorbed because wo.z <= 0), EV_ROUGH_ABSORBED / EV_COAT_ABSORBED (abs
 took a light sample is one of those with C_LIGHT set: glossy_tally() counts them, as a part of ref64.tally()."""
 import numpy as np
 
+from ref64_base import _cross, _dot, _unit
+
 ROUGH_METAL, PLASTIC = 4, 5
 GLOSSY_MIN_ROUGHNESS = 0.05  # vertices of a glossy material below this roughness take no light sample
 EV_ROUGH, EV_COAT, EV_BODY, EV_BELOW, EV_ROUGH_ABSORBED, EV_COAT_ABSORBED = range(30, 36)
@@ -26,19 +28,6 @@ GLOSSY_KEYS = ("rough_vertices", "coat_vertices", "body_vertices", "below_vertic
 
 
 # ------------------------------------------------------------------------------------------------- the model (local frame)
-def _dot(a, b):
-    return (a * b).sum(axis=-1)
-
-
-def _unit(a):
-    return a / np.sqrt(_dot(a, a))[:, None]
-
-
-def _cross(a, b):
-    return np.stack([a[..., 1] * b[..., 2] - a[..., 2] * b[..., 1], a[..., 2] * b[..., 0] - a[..., 0] * b[..., 2],
-                     a[..., 0] * b[..., 1] - a[..., 1] * b[..., 0]], axis=-1)
-
-
 def alpha_of(r):
     """alpha = max(r^2, 1e-3) as the packer stores it (fp32)"""
     r = np.asarray(r, np.float32)
@@ -184,7 +173,8 @@ def glossy_tally(event, at, S):
     sequence with emitters, media and the environment.  event [N][vertices]: the signature's C_EVENT; `at`: what ref64.tally()
     read from the other columns, per vertex -- prim, light (the light picked), env_light (the environment's index among the
     lights, -1: none) and the flags took_light, clear (the shadow ray's verdict), medium, on_mover, full_weight_emitter (an
-    emitter hit at full weight), missed_to_texel (an escape that read an environment texel), lost (the roulette) -- so that
+    emitter hit at full weight), missed_to_texel (an escape that read an environment texel), lost (the roulette) -- and, per
+    MATERIAL, roughness (NaN where the material has no single one: a pbr material under a map), so that
     this file knows the glossy event codes and no others.  S: the RefScene, or None (no count by roughness then)."""
     prim, light, took_light, med, on_mover = at["prim"], at["light"], at["took_light"], at["medium"], at["on_mover"]
     glossy = np.isin(event, GLOSSY_EVENTS)
@@ -193,7 +183,7 @@ def glossy_tally(event, at, S):
     # the roughness of the material under each static glossy vertex (movers: by their own material, counted separately)
     rough = np.full(event.shape, np.nan)
     if S is not None and len(S.prims):
-        r_of_prim = S.mats["fuzz"][S.prims["material"]].astype(np.float64)
+        r_of_prim = at["roughness"][S.prims["material"]]
         on_static = glossy & (prim >= 0) & ~on_mover
         rough[on_static] = r_of_prim[prim[on_static]]
     with np.errstate(invalid="ignore"):

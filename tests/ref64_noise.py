@@ -11,10 +11,8 @@ Test infrastructure only, written from the model's text (include/rtmi.h, DESIGN 
     fbm: clamp(0.5 + 0.5 S, 0, 1)   turbulence: min(1, A)   marble: 0.5 + 0.5 sin(f p[axis] + D A)   colour: c0 + s (c1 - c0)
 Everything runs at dtype T with plain (unfused) operations; the lattice coordinates and the hash are integers at any T.
 
-ref64.py is not edited: its texture_value knows solid, checker and image.  installed(sc) puts a wrapper in its place while a
-trace runs -- the wrapper handles textures of type NOISE itself, with the parameters of sc.noise(texture), and passes every other
-texture to the function it replaced -- and takes it out again.  trace(), reference() and judge() are ref64's, called inside
-installed().
+This file holds the model alone and imports nothing of ref64: ref64.texture_value calls colour() for a texture of type NOISE, with
+the parameters RefScene read from Scene.noise(texture), and ref64.tally() counts the noise vertices.
 
 Deliberate mistakes (names in `perturb`, as ref64.trace takes them):
   noise_cubic_fade   the fade 3 t^2 - 2 t^3 in place of the quintic
@@ -22,11 +20,7 @@ Deliberate mistakes (names in `perturb`, as ref64.trace takes them):
   noise_wrong_axis   marble's phase along the next axis (x -> y -> z -> x); fbm and turbulence: the octaves' amplitudes not
                      halved, so that the name never does nothing
 """
-import contextlib
-
 import numpy as np
-
-import ref64 as R
 
 NOISE = 3
 FBM, TURBULENCE, MARBLE = range(3)
@@ -110,66 +104,3 @@ def colour(p, c0, c1, par, T, perturb=()):
               T, perturb)
     c0, c1 = np.asarray(c0, np.float32).astype(T), np.asarray(c1, np.float32).astype(T)
     return (c0[None, :] + s[:, None] * (c1 - c0)[None, :]).astype(T)
-
-
-@contextlib.contextmanager
-def installed(sc, log=None):
-    """ref64.texture_value with the noise textures of the product scene sc, for the length of the block.  log: a list that
-    receives (texture ids, colours) of every call, in call order (the feature-buffer test reads the first vertex from it)"""
-    original = R.texture_value
-    params = {ti: sc.noise(ti) for ti, t in enumerate(sc.textures()) if int(t["type"]) == NOISE}
-
-    def texture_value(S, tex, p, T, o=None, d=None, t=None, idx=None, mov=None, time=None, perturb=()):
-        tex = np.asarray(tex)
-        is_noise = np.isin(tex, list(params))
-        out = np.zeros_like(p)
-        texel = np.full(len(p), R.NONE, np.int64)
-        rest = ~is_noise
-        if rest.any():
-            pick = lambda a: None if a is None else a[rest]
-            out[rest], texel[rest] = original(S, tex[rest], p[rest], T, pick(o), pick(d), pick(t), pick(idx), pick(mov), pick(time), perturb)
-        for ti in np.unique(tex[is_noise]):
-            m = tex == ti
-            out[m] = colour(p[m], S.texs[ti]["c0"], S.texs[ti]["c1"], params[int(ti)], T, perturb)
-        if log is not None:
-            log.append((tex.copy(), out.copy()))
-        return out, texel
-    R.texture_value = texture_value
-    try:
-        yield
-    finally:
-        R.texture_value = original
-
-
-def trace(sc, S, words, **kw):
-    with installed(sc):
-        return R.trace(S, words, **kw)
-
-
-def reference(sc, S, words, shutter=None):
-    with installed(sc):
-        return R.reference(S, words, shutter)
-
-
-def tally(sig, S):
-    """What a noise case is there for, from the reference's signatures: the vertices on a surface whose material's texture is a
-    noise texture, by material type and by style (styles: texture id -> style, from Scene.noise), and the share of samples with
-    at least one such vertex.  A mover's material is its own; a medium event is no surface."""
-    v = sig[:, R.SAMPLE_COLUMNS:].reshape(len(sig), -1, R.VERTEX_COLUMNS)
-    event, prim, mover, light = (v[:, :, c] for c in (R.C_EVENT, R.C_PRIM, R.C_MOVER, R.C_LIGHT))
-    surface = (event != R.NONE) & (event != R.EV_MISS) & (event != R.EV_MEDIUM)
-    mat = np.where(prim >= 0, S.prims["material"][np.clip(prim, 0, len(S.prims) - 1)], -1)
-    if len(S.movers):
-        on_mover = mover >= 0
-        mat = np.where(on_mover, S.movers["material"][np.clip(mover, 0, len(S.movers) - 1)], mat)
-    mat = np.where(surface, mat, -1)
-    mtype = np.where(mat >= 0, S.mats["type"][np.clip(mat, 0, len(S.mats) - 1)], -1)
-    tex = np.where(mat >= 0, S.mats["texture"][np.clip(mat, 0, len(S.mats) - 1)], -1)
-    textured = np.isin(mtype, (R.LAMBERTIAN, R.DIFFUSE_LIGHT, R.PLASTIC)) & (tex >= 0)
-    noisy = textured & (S.texs["type"][np.clip(tex, 0, len(S.texs) - 1)] == NOISE)
-    return dict(noise_vertices=int(noisy.sum()), noise_share=float(noisy.any(axis=1).mean()),
-                noise_lambertian=int((noisy & (mtype == R.LAMBERTIAN)).sum()), noise_plastic=int((noisy & (mtype == R.PLASTIC)).sum()),
-                noise_emitter=int((noisy & (mtype == R.DIFFUSE_LIGHT)).sum()),
-                noise_plastic_light_samples=int((noisy & (mtype == R.PLASTIC) & (light != R.NONE)).sum()),
-                noise_mover=int((noisy & (mover >= 0)).sum()) if len(S.movers) else 0,
-                noise_textures=sorted(int(t) for t in np.unique(tex[noisy])))

@@ -243,7 +243,7 @@ def test_the_list_of_lights_its_order_and_probabilities(rtmi):
     assert np.array_equal(L["emission"][4], (np.array((0.2, 0.2, 0.15), np.float32).astype(np.float64) * fold).astype(np.float32))
     # with exactly these words ref64 finds the light records and the alias table in the packed image, once
     sc.set_light_sampling(True)
-    S = AL.ref_scene(sc)
+    S = R.RefScene(sc)
     assert len(S.thr) == 6 and sorted(S.analytic) == [2, 3, 4]
     assert np.allclose(R.implied_alias_probability(S.thr, S.alias), p, atol=1e-6)
     # a light whose weight is not positive and finite is left out: a distant light in a scene without primitives

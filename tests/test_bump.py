@@ -358,19 +358,6 @@ def test_sanity_of_the_model():
 
 
 # ------------------------------------------------------------------------------------------------------ 4. the cases on the CPU
-def test_without_bumps_the_wrapper_is_ref64(rtmi):
-    """on a case's unbumped twin ref64_bump.trace returns ref64.trace's radiance, signatures and draw counts exactly"""
-    name = "bump_lights"
-    words, shutter = BS.inputs(rtmi, name)
-    words = words[:2 * NS.REF_W * NS.REF_H]
-    twin = BS.scene(rtmi, name, bump=False)
-    S = R.RefScene(twin)
-    a, b = B.trace(twin, S, words), R.trace(S, words)
-    for x, y in zip(a, b):
-        assert np.array_equal(x, y)
-    assert R.hit_record.__module__ == "ref64"  # (taken out again)
-
-
 def test_a_case_holds_its_vertices_and_the_mistakes_change_it(rtmi):
     """bump_prims at fp64 on the CPU (the other cases: test_gpu_bump.py): the vertices it is there for, the twin's first hits,
     and every deliberate mistake moves a tenth of the samples and more"""
@@ -379,20 +366,20 @@ def test_a_case_holds_its_vertices_and_the_mistakes_change_it(rtmi):
     words = words[:4 * NS.REF_W * NS.REF_H]
     sc = BS.scene(rtmi, name)
     S = R.RefScene(sc)
-    log = B.new_log()
-    rgb, sig, draws = B.trace(sc, S, words, log=log)
-    tally = B.tally(sig, S, sc, log)
+    log = R.new_log()
+    rgb, sig, draws = R.trace(S, words, log=log)
+    tally = R.tally(sig, S, log)
     assert tally["bump_share"] >= BS.MIN_BUMP_SHARE and min(tally[k] for k in BS.CASES[name][3]) >= 50, tally
-    assert log["bumped"] >= tally["bump_vertices"]
+    assert log["bump_bumped"] >= tally["bump_vertices"]
     twin = BS.scene(rtmi, name, bump=False)
     rgb_t, sig_t, _ = R.trace(R.RefScene(twin), words)
     assert np.array_equal(sig[:, R.SAMPLE_COLUMNS + R.C_PRIM], sig_t[:, R.SAMPLE_COLUMNS + R.C_PRIM])  # (the geometry is the twin's)
     far = lambda a, b: (np.abs(a - b).max(axis=1) > 1e-4 * np.maximum(1, np.abs(b).max(axis=1))).mean()
     assert far(rgb_t, rgb) > 0.15
-    off, _, _ = B.trace(sc, S, words, perturb=("bump_off",))
+    off, _, _ = R.trace(S, words, perturb=("bump_off",))
     assert np.array_equal(off, rgb_t)  # (bump_off IS the twin)
     for mistake in B.PERTURBATIONS:
-        wrong, _, _ = B.trace(sc, S, words, perturb=(mistake,))
+        wrong, _, _ = R.trace(S, words, perturb=(mistake,))
         moved = far(wrong, rgb)
         print(f"{name}, {mistake}: {100 * moved:.1f} % of the samples move")
         assert moved > 0.10, (mistake, moved)

@@ -6,7 +6,7 @@
      within tolerance is at least the fp32 numpy statement's minus 0.5 points; branch flips counted apart, at most 0.5 %);
   3. closed forms of the model in fp64;
   4. the estimator against a quadrature of itself in fp64;
-  5. ref64_glass.installed() leaves ref64.trace on scenes without the material as it was (the pinned fixture), the cases hold
+  5. no extension's model is reached on scenes without it, which trace as pinned (the pinned fixture), the cases hold
      what they are there for, and each deliberate mistake changes the reference.
 test_gpu_glass.py holds the kernels to that reference."""
 import ctypes
@@ -330,21 +330,59 @@ def test_the_estimator_is_consistent_with_itself():
 
 # -------------------------------------------------------------------------------------------------- 5. the fp64 path tracer
 @pytest.mark.parametrize("name", ["light sampling", "environment", "medium"])
-def test_installed_leaves_the_pinned_cases_alone(rtmi, golden_dir, name):
-    """test_glossy.py's three pinned cases under ref64_glass.installed(), through present(): the draws and the signature are
-    exact, the radiance within 1e-9"""
+def test_installed_leaves_the_pinned_cases_alone(rtmi, golden_dir, name, monkeypatch):
+    """test_glossy.py's three pinned cases with every entry point of the extensions' models replaced by one that
+    raises: none of them is reached without its records in the scene, the draws and the signature are exact, the radiance within
+    1e-9.  (Named for the wrappers these models once were installed by.)"""
     from test_glossy import _existing_cases
+
+    def never(*a, **k):
+        raise AssertionError("an extension's model was reached in a scene without it")
+    for module, names in ((R.GL, ("glass_sample", "glass_eval")), (R.PB, ("choose",)), (R.NO, ("colour",)), (R.BU, ("gradient_of",)),
+                          (R.NM, ("normal",)), (R.AL, ("sample",)), (R, ("sample_quad", "sample_triangle", "quad_t"))):
+        for f in names:
+            monkeypatch.setattr(module, f, never)
     pin = np.load(os.path.join(golden_dir, "ref64_trace_pin.npz"))
     sc, seed = _existing_cases(rtmi)[name]
     words = R.uniforms(rtmi, seed, NS.REF_W, NS.REF_H, 0, 1, NS.REF_DRAWS)
     S = R.RefScene(sc)
-    assert GL.present(S) is S
     for tag, dtype in (("64", np.float64), ("32", np.float32)):
-        rgb, sig, draws = GL.trace(S, words, dtype=dtype, sc=sc)
+        rgb, sig, draws = R.trace(S, words, dtype=dtype)
         assert np.array_equal(draws, pin[f"{name}/draws{tag}"]), (name, tag)
         assert hashlib.sha256(np.ascontiguousarray(sig).tobytes()).hexdigest() == str(pin[f"{name}/sig{tag}"]), (name, tag)
         assert np.allclose(rgb, pin[f"{name}/rgb{tag}"], rtol=1e-9, atol=1e-12), (name, tag)
-    assert R.glossy_sample is G.glossy_sample and R.texture_value.__module__ == "ref64"  # (taken out again)
+
+
+@pytest.mark.parametrize("family", ["mesh_lights", "noise", "bump", "quads", "glass", "analytic_lights", "pbr", "normal_map"])
+def test_the_extensions_trace_as_pinned(rtmi, golden_dir, family):
+    """golden/ref64_ext_pin.npz holds what the reference returned on one case of each extension of DESIGN 7n-7u while each was a
+    module of its own around ref64's functions (golden/make_ref64_ext_pin.py; the first sample of each pixel).  As the first pin
+    is compared: the draws and the signature exact, the radiance at rtol 1e-9 -- the fp64 run's after rounding to float32, as
+    it is stored; the fp32 run's by its bytes.  One exception, which the fold made on purpose: a point, spot or distant light's
+    sample is stated at weight 1 directly, no longer through the power heuristic at a scaled density, and lands a few roundings
+    from the pinned value; the analytic-light case's fp32 radiance is therefore held to 32 float32 epsilons."""
+    import importlib
+    import json
+    pin = np.load(os.path.join(golden_dir, "ref64_ext_pin.npz"))
+    cases = json.loads(str(pin["cases"]))
+    at, rec = list(cases).index(family), cases[family]
+    SC = importlib.import_module({"mesh_lights": "mesh_light_scenes", "quads": "quad_scenes", "analytic_lights": "analytic_light_scenes"}.get(family, family + "_scenes"))
+    sc = SC.scene(rtmi, rec["case"])
+    try:
+        words = SC.inputs(rtmi, rec["case"])[0]
+    except TypeError:
+        words = SC.inputs(rtmi)
+    S, sha = R.RefScene(sc), lambda a: hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+    for k, (tag, dtype) in enumerate((("64", np.float64), ("32", np.float32))):
+        rgb, sig, draws = R.trace(S, words[:NS.REF_W * NS.REF_H], dtype=dtype)
+        assert np.array_equal(draws, pin["draws"][k][at]) and sha(sig) == rec["sig" + tag], (family, tag)
+        if tag == "64":
+            assert np.allclose(rgb.astype(np.float32), pin["rgb64"][at], rtol=1e-9, atol=1e-12), (family, tag)
+        elif family != "analytic_lights":
+            assert sha(rgb) == rec["rgb32"], (family, tag)
+        else:
+            pinned = (pin["rgb64"][at].view(np.int32) + pin["analytic_rgb32_steps"]).view(np.float32)
+            assert sha(pinned) == rec["rgb32"] and np.allclose(rgb, pinned, rtol=32 * np.finfo(np.float32).eps, atol=0), (family, tag)
 
 
 @pytest.fixture(scope="module")
@@ -356,7 +394,7 @@ def references(rtmi):
             sc = GS.scene(rtmi, name)
             words, shutter = GS.inputs(rtmi, name)
             S = R.RefScene(sc)
-            made[name] = (sc, S, words, shutter, GL.reference(S, words, shutter, sc=sc))
+            made[name] = (sc, S, words, shutter, R.reference(S, words, shutter))
         return made[name]
     return of
 
@@ -368,7 +406,7 @@ def test_the_cases_hold_what_they_are_there_for(rtmi, references, name):
     sc, S, words, shutter, (ref, stable, draws, tally) = references(name)
     assert len(words) >= 16000 and draws.max() <= NS.REF_DRAWS
     GS.check_contents(name, tally)
-    rgb32, _, _ = GL.trace(S, words, shutter=shutter, dtype=np.float32, sc=sc)
+    rgb32, _, _ = R.trace(S, words, shutter=shutter, dtype=np.float32)
     j = R.judge(rgb32, ref, stable)
     print("\n" + R.row(name + " (fp32 reference)", j))
     print("    " + ", ".join(f"{k[6:]} {v}" for k, v in tally.items() if k.startswith("glass_") and not isinstance(v, list)))
@@ -383,7 +421,7 @@ def test_the_cases_hold_what_they_are_there_for(rtmi, references, name):
 @pytest.mark.parametrize("name,mistake", GS.MISTAKES)
 def test_the_perturbations_change_the_reference(references, name, mistake):
     sc, S, words, shutter, (ref, stable, _, _) = references(name)
-    wrong, _, _ = GL.trace(S, words, shutter=shutter, perturb=(mistake,), sc=sc)
+    wrong, _, _ = R.trace(S, words, shutter=shutter, perturb=(mistake,))
     j = R.judge(wrong, ref, stable)
     print(f"\n{name}, {mistake}: the perturbed reference agrees with the reference on {100 * j['share']:.1f} % of the samples")
     assert j["share"] < 0.97, j

@@ -20,11 +20,9 @@ import numpy as np
 import pytest
 
 import analytic_light_scenes as AL
-import glass_scenes as GLS
 import nee_scenes as NS
 import per_sample as PS
 import ref64 as R
-import ref64_analytic_lights as RA
 import smooth_scenes as SM
 
 pytestmark = pytest.mark.gpu
@@ -52,12 +50,12 @@ def cases(rtmi, words):
     def of(name):
         if name not in made:
             sc = AL.scene(rtmi, name)
-            S = AL.ref_scene(sc)
+            S = R.RefScene(sc)
             st = rtmi.Stats()
             sc.render(rtmi.Opts(seed=NS.REF_SEED, sample_count=1), st)
             assert st.kernel_variant & ~AL.FAMILIES in GENERAL_LAYOUTS and st.kernel_variant & AL.FAMILIES == AL.family(name), st.kernel_variant
             got = PS.kernel_samples(rtmi, sc, NS.REF_SEED, NS.REF_K, AL.FAMILIES, AL.family(name))
-            made[name] = (sc, S, got, RA.reference(S, words, sc=sc))
+            made[name] = (sc, S, got, R.reference(S, words))
         return made[name]
     return of
 
@@ -70,13 +68,10 @@ def test_kernel_against_fp64(rtmi, words, cases, name):
     AL.check_contents(name, tally)
     plain = AL.plain_twin(rtmi, name)
     assert len(plain.analytic_lights()) == len(sc.analytic_lights())
-    bref, bstable, _, _ = GLS.twin_reference(plain, words)
+    bref, bstable, _, _ = R.reference(R.RefScene(plain), words)
     b = R.judge(PS.kernel_samples(rtmi, plain, NS.REF_SEED, NS.REF_K, AL.FAMILIES, 0), bref, bstable)
-    try:
-        r32, _, _ = RA.trace(S, words, dtype=np.float32, sc=sc)
-        fp32 = f"fp32 NumPy within {100 * R.judge(r32, ref, stable)['share']:.3f} %"
-    except ArithmeticError as e:  # (weight 1 cannot be stated through the power heuristic at float32 here: the row is left out)
-        fp32 = f"fp32 NumPy row left out ({e})"
+    r32, _, _ = R.trace(S, words, dtype=np.float32)
+    fp32 = f"fp32 NumPy within {100 * R.judge(r32, ref, stable)['share']:.3f} %"
     shown = [k for k in tally if k in AL.CASES[name][2] or k.endswith("_picks")]
     print(f"\n    {fp32}; " + ", ".join(f"{k} {tally[k]}" for k in shown))
     PS.assert_agreement(name, R.judge(got, ref, stable), b)                                # (a), (b), (c)
@@ -86,7 +81,7 @@ def test_kernel_against_fp64(rtmi, words, cases, name):
 def test_a_wrong_reference_is_noticed(words, cases, name, mistake):
     """against the kernel, a reference with one deliberate mistake of the analytic lights is far from 97 %"""
     sc, S, got, (ref, stable, _, _) = cases(name)
-    wrong, _, _ = RA.trace(S, words, perturb=(mistake,), sc=sc)
+    wrong, _, _ = R.trace(S, words, perturb=(mistake,))
     good, bad = R.judge(got, ref, stable), R.judge(got, wrong, stable)
     print(f"\n{name}, {mistake}: within tolerance {100 * good['share']:.2f} % -> {100 * bad['share']:.2f} %")
     PS.assert_perturbation_noticed(good, bad)

@@ -25,7 +25,6 @@ import bump_scenes as BS
 import nee_scenes as NS
 import per_sample as PS
 import ref64 as R
-import ref64_bump as B
 
 pytestmark = pytest.mark.gpu
 ROOT = PS.ROOT
@@ -65,10 +64,8 @@ def cases(rtmi, inputs):
             sc.render(rtmi.Opts(seed=BS.seed_of(name), sample_count=1), st)
             assert st.kernel_variant & ~BS.FAMILIES in GENERAL_LAYOUTS and st.kernel_variant & BS.FAMILIES == BS.family(name), st.kernel_variant
             got = PS.kernel_samples(rtmi, sc, BS.seed_of(name), NS.REF_K, BS.FAMILIES, BS.family(name))
-            ref = B.reference(sc, S, words, shutter)
-            log = B.new_log()
-            _, sig, _ = B.trace(sc, S, words, log=log, shutter=shutter)
-            made[name] = (sc, S, got, ref, B.tally(sig, S, sc, log))
+            ref = R.reference(S, words, shutter)
+            made[name] = (sc, S, got, ref, {k: v for k, v in ref[3].items() if k.startswith("bump_")})
         return made[name]
     return of
 
@@ -92,7 +89,7 @@ def test_a_mistake_fails_the_agreement(inputs, cases, name, mistake):
     """(d): against the kernel, a reference with one deliberate mistake of the model is far from 97 %"""
     words, shutter = inputs(name)
     sc, S, got, (ref, stable, _, _), _ = cases(name)
-    wrong, _, _ = B.trace(sc, S, words, shutter=shutter, perturb=(mistake,))
+    wrong, _, _ = R.trace(S, words, shutter=shutter, perturb=(mistake,))
     good, bad = R.judge(got, ref, stable), R.judge(got, wrong, stable)
     print(f"\n{name}, {mistake}: within tolerance {100 * good['share']:.2f} % -> {100 * bad['share']:.2f} %")
     PS.assert_perturbation_noticed(good, bad)
@@ -180,7 +177,7 @@ def test_feature_buffers_show_the_bumped_normal(rtmi, inputs):
     words, _ = inputs(name)
     n = NS.REF_W * NS.REF_H
     S, probe = R.RefScene(sc), {}
-    _, sig, _ = B.trace(sc, S, words[:n], probe=probe)
+    _, sig, _ = R.trace(S, words[:n], probe=probe)
     prim = sig[:, R.SAMPLE_COLUMNS + R.C_PRIM]
     mat = np.where(prim >= 0, S.prims["material"][np.clip(prim, 0, None)], -1)
     bumped = np.isin(mat, [m for m in range(len(S.mats)) if sc.bump(m) is not None])

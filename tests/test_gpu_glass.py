@@ -64,7 +64,7 @@ def cases(rtmi, inputs):
             sc.render(rtmi.Opts(seed=GS.seed_of(name), sample_count=1), st)
             assert st.kernel_variant & ~GS.FAMILIES in GENERAL_LAYOUTS and st.kernel_variant & GS.FAMILIES == GS.family(name), st.kernel_variant
             got = PS.kernel_samples(rtmi, sc, GS.seed_of(name), NS.REF_K, GS.FAMILIES, GS.family(name))
-            made[name] = (sc, S, got, GL.reference(S, words, shutter, sc=sc))
+            made[name] = (sc, S, got, R.reference(S, words, shutter))
         return made[name]
     return of
 
@@ -77,7 +77,7 @@ def test_kernel_against_fp64(rtmi, inputs, cases, name):
     assert draws.max() <= NS.REF_DRAWS, draws.max()                                        # (d)
     GS.check_contents(name, tally)
     plain = GS.plain_twin(rtmi, name)
-    bref, bstable, _, _ = GS.twin_reference(plain, words)
+    bref, bstable, _, _ = R.reference(R.RefScene(plain), words)
     b = R.judge(PS.kernel_samples(rtmi, plain, GS.seed_of(name), NS.REF_K, GS.FAMILIES, 0), bref, bstable)
     PS.assert_agreement(name, R.judge(got, ref, stable), b)                                # (a), (b), (c)
     print("    " + ", ".join(f"{k[6:]} {v}" for k, v in tally.items() if k.startswith("glass_") and not isinstance(v, list) and v))
@@ -88,7 +88,7 @@ def test_a_mistake_fails_the_agreement(inputs, cases, name, mistake):
     """(d): against the kernel, a reference with one deliberate mistake of the model is far from 97 %"""
     words, shutter = inputs(name)
     sc, S, got, (ref, stable, _, _) = cases(name)
-    wrong, _, _ = GL.trace(S, words, shutter=shutter, perturb=(mistake,), sc=sc)
+    wrong, _, _ = R.trace(S, words, shutter=shutter, perturb=(mistake,))
     good, bad = R.judge(got, ref, stable), R.judge(got, wrong, stable)
     print(f"\n{name}, {mistake}: within tolerance {100 * good['share']:.2f} % -> {100 * bad['share']:.2f} %")
     PS.assert_perturbation_noticed(good, bad)
@@ -168,12 +168,12 @@ def test_feature_buffers_show_the_first_vertex(rtmi, inputs):
     words, _ = inputs(name)
     n = NS.REF_W * NS.REF_H
     probe, probe32 = {}, {}
-    GL.trace(R.RefScene(sc), words[:n], probe=probe, sc=sc)
-    GL.trace(R.RefScene(sc), words[:n], dtype=np.float32, probe=probe32, sc=sc)
+    R.trace(R.RefScene(sc), words[:n], probe=probe)
+    R.trace(R.RefScene(sc), words[:n], dtype=np.float32, probe=probe32)
     o = rtmi.Opts(seed=GS.seed_of(name), sample_first=0, sample_count=1)
     albedo = sc.render_feature(rtmi.FEATURE_ALBEDO, o).reshape(-1, 3).astype(np.float64)
     normal = sc.render_feature(rtmi.FEATURE_NORMAL, o).reshape(-1, 3).astype(np.float64)
-    on = probe["glossy"] & probe32["glossy"]  # (the torus: the only surface ref64 sees as glossy)
+    on = probe["glossy"] & probe32["glossy"]  # (the torus: the only glossy surface)
     assert on.sum() >= 100, on.sum()
     assert (albedo[on] == 1.0).all()
     err = np.abs(normal[on] - probe["normal"][on]).max(axis=1)

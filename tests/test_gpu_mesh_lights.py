@@ -1,5 +1,5 @@
 """Mesh lights (emissive triangles among the sampled emitters) on the GPU, against the fp64 statement of ref64.py
-with ref64_mesh_lights' triangle sample, sample by sample on the same draws: criteria (a) - (c) of test_gpu_nee_reference.py
+with ref64's triangle sample, sample by sample on the same draws: criteria (a) - (c) of test_gpu_nee_reference.py
 with per_sample's thresholds on the five cases of mesh_light_scenes.py.  The (b) baseline is the plain kernel on the case's
 plain twin (light sampling off, environment cleared, glossy materials replaced by lambertian) against the twin's reference.
 Each case asserts from the reference's signatures that it holds the pinned counts of what it is there for, and prints the share
@@ -25,7 +25,6 @@ import mesh_light_scenes as ML
 import nee_scenes as NS
 import per_sample as PS
 import ref64 as R
-import ref64_mesh_lights as RM
 
 pytestmark = pytest.mark.gpu
 ROOT = PS.ROOT
@@ -45,7 +44,7 @@ def words(rtmi):
 
 @pytest.fixture(scope="module")
 def cases(rtmi, words):
-    """name -> (scene, RefScene, kernel samples, (ref, stable, draws, tally of ref64), signatures): rendered and traced once"""
+    """name -> (scene, RefScene, kernel samples, (ref, stable, draws, tally of ref64)): rendered and traced once"""
     made = {}
 
     def of(name):
@@ -56,7 +55,7 @@ def cases(rtmi, words):
             sc.render(rtmi.Opts(seed=NS.REF_SEED, sample_count=1), st)
             assert st.kernel_variant & ~ML.FAMILIES in GENERAL_LAYOUTS and st.kernel_variant & ML.FAMILIES == ML.family(name), st.kernel_variant
             got = PS.kernel_samples(rtmi, sc, NS.REF_SEED, NS.REF_K, ML.FAMILIES, ML.family(name))
-            made[name] = (sc, S, got, RM.reference(S, words), RM.trace(S, words)[1])
+            made[name] = (sc, S, got, R.reference(S, words))
         return made[name]
     return of
 
@@ -64,16 +63,15 @@ def cases(rtmi, words):
 @pytest.mark.parametrize("name", list(ML.CASES))
 def test_kernel_against_fp64(rtmi, words, cases, name):
     assert len(words) >= 16000
-    sc, S, got, (ref, stable, draws, _), sig = cases(name)
+    sc, S, got, (ref, stable, draws, tally) = cases(name)
     assert draws.max() <= NS.REF_DRAWS, draws.max()
-    tally = RM.tally(sig, S)
     ML.check_contents(name, tally)
     plain = ML.plain_twin(rtmi, name)
     bref, bstable, _, _ = R.reference(R.RefScene(plain), words)
     b = R.judge(PS.kernel_samples(rtmi, plain, NS.REF_SEED, NS.REF_K, ML.FAMILIES, 0), bref, bstable)
-    r32, _, _ = RM.trace(S, words, dtype=np.float32)
+    r32, _, _ = R.trace(S, words, dtype=np.float32)
     j32 = R.judge(r32, ref, stable)
-    print(f"\n    fp32 NumPy within {100 * j32['share']:.3f} %; " + ", ".join(f"{k} {v}" for k, v in tally.items()))
+    print(f"\n    fp32 NumPy within {100 * j32['share']:.3f} %; " + ", ".join(f"{k} {v}" for k, v in tally.items() if k in ML.TALLY_KEYS))
     PS.assert_agreement(name, R.judge(got, ref, stable), b)                                # (a), (b), (c)
 
 
@@ -82,8 +80,8 @@ def test_kernel_against_fp64(rtmi, words, cases, name):
 def test_a_wrong_reference_is_noticed(words, cases, name, mistake):
     """against the kernel, a reference with one deliberate mistake of the triangle sample is far from 97 % (on the smooth mesh
     the vertex normal is the triangle's own first vertex normal: the density must be stated with the geometric one)"""
-    sc, S, got, (ref, stable, _, _), _ = cases(name)
-    wrong, _, _ = RM.trace(S, words, perturb=(mistake,))
+    sc, S, got, (ref, stable, _, _) = cases(name)
+    wrong, _, _ = R.trace(S, words, perturb=(mistake,))
     good, bad = R.judge(got, ref, stable), R.judge(got, wrong, stable)
     print(f"\n{name}, {mistake}: within tolerance {100 * good['share']:.2f} % -> {100 * bad['share']:.2f} %")
     PS.assert_perturbation_noticed(good, bad)

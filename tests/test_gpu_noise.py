@@ -65,10 +65,8 @@ def cases(rtmi, inputs):
             layouts = (NSC.NESTED_LAYOUT,) if name == "noise_nested" else GENERAL_LAYOUTS
             assert st.kernel_variant & ~NSC.FAMILIES in layouts and st.kernel_variant & NSC.FAMILIES == NSC.family(name), st.kernel_variant
             got = PS.kernel_samples(rtmi, sc, NSC.seed_of(name), NS.REF_K, NSC.FAMILIES, NSC.family(name))
-            with N.installed(sc):
-                ref = R.reference(S, words, shutter)
-                _, sig, _ = R.trace(S, words, shutter=shutter)
-            made[name] = (sc, S, got, ref, N.tally(sig, S))
+            ref = R.reference(S, words, shutter)
+            made[name] = (sc, S, got, ref, {k: v for k, v in ref[3].items() if k.startswith("noise_")})
         return made[name]
     return of
 
@@ -92,7 +90,7 @@ def test_a_mistake_fails_the_agreement(inputs, cases, name, mistake):
     """(d): against the kernel, a reference with one deliberate mistake of the model is far from 97 %"""
     words, shutter = inputs(name)
     sc, S, got, (ref, stable, _, _), _ = cases(name)
-    wrong, _, _ = N.trace(sc, S, words, shutter=shutter, perturb=(mistake,))
+    wrong, _, _ = R.trace(S, words, shutter=shutter, perturb=(mistake,))
     good, bad = R.judge(got, ref, stable), R.judge(got, wrong, stable)
     print(f"\n{name}, {mistake}: within tolerance {100 * good['share']:.2f} % -> {100 * bad['share']:.2f} %")
     PS.assert_perturbation_noticed(good, bad)
@@ -147,27 +145,18 @@ def test_layouts_a_sample_split_and_the_product_library_give_the_same_bytes(rtmi
 
 def test_feature_buffers_show_the_first_vertex(rtmi, inputs):
     """one-sample feature passes of noise_sky: the albedo against the texture values the reference read at its FIRST vertex of
-    sample 0 of every pixel (the wrapper's log: ref64.trace asks for the emitters' textures, then the lambertians', then the
-    plastics', each in sample order), within 1e-4 per channel -- the per-sample tolerance -- on at least 99 % of the noise pixels;
+    sample 0 of every pixel (trace()'s probe["texture_value"]), within 1e-4 per channel -- the per-sample tolerance -- on at least 99 % of the noise pixels;
     normal and depth are the twin's, byte for byte"""
     name = "noise_sky"
     sc, twin = NSC.scene(rtmi, name), NSC.scene(rtmi, name, noise=False)
     words, _ = inputs(name)
     n = NS.REF_W * NS.REF_H
-    S, log = R.RefScene(sc), []
-    with N.installed(sc, log):
-        _, sig, _ = R.trace(S, words[:n])
+    S, probe = R.RefScene(sc), {}
+    _, sig, _ = R.trace(S, words[:n], probe=probe)
     prim = sig[:, R.SAMPLE_COLUMNS + R.C_PRIM]
     mtype = np.where(prim >= 0, S.mats["type"][S.prims["material"][np.clip(prim, 0, None)]], -1)
     tex_of = np.where(prim >= 0, S.mats["texture"][S.prims["material"][np.clip(prim, 0, None)]], -1)
-    want = np.full((n, 3), np.nan)
-    calls = iter(log)
-    for kind in (R.DIFFUSE_LIGHT, R.LAMBERTIAN, R.PLASTIC):
-        m = mtype == kind
-        if m.any():
-            tex, value = next(calls)
-            assert np.array_equal(tex, tex_of[m]), kind  # (the call IS the first vertices of this kind, in sample order)
-            want[m] = value
+    want = np.where(np.isin(mtype, (R.DIFFUSE_LIGHT, R.LAMBERTIAN, R.PLASTIC))[:, None], probe["texture_value"], np.nan)
     noisy = (tex_of >= 0) & (S.texs["type"][np.clip(tex_of, 0, None)] == N.NOISE) & np.isin(mtype, (R.LAMBERTIAN, R.PLASTIC, R.DIFFUSE_LIGHT))
     assert noisy.sum() >= 300 and set(np.unique(mtype[noisy])) == {R.LAMBERTIAN, R.PLASTIC}, noisy.sum()
     o = rtmi.Opts(seed=NSC.seed_of(name), sample_first=0, sample_count=1)

@@ -69,10 +69,8 @@ def cases(rtmi, inputs):
             sc.render(rtmi.Opts(seed=NMS.seed_of(name), sample_count=1), st)
             assert st.kernel_variant & ~NMS.FAMILIES in GENERAL_LAYOUTS and st.kernel_variant & NMS.FAMILIES == NMS.family(name), st.kernel_variant
             got = PS.kernel_samples(rtmi, sc, NMS.seed_of(name), NS.REF_K, NMS.FAMILIES, NMS.family(name))
-            ref = NM.reference(sc, S, words, shutter)
-            log = NM.new_log()
-            _, sig, _ = NM.trace(sc, S, words, log=log, shutter=shutter)
-            made[name] = (sc, S, got, ref, NM.tally(sig, S, sc, log))
+            ref = R.reference(S, words, shutter)
+            made[name] = (sc, S, got, ref, {k: v for k, v in ref[3].items() if k.startswith("nm_")})
         return made[name]
     return of
 
@@ -86,7 +84,7 @@ def test_kernel_against_fp64(rtmi, inputs, cases, name):
     print("\n    " + ", ".join(f"{k} {v if isinstance(v, int) else round(v, 3)}" for k, v in map_tally.items() if v))
     NMS.check_contents(name, map_tally)
     plain = NMS.plain_twin(rtmi, name)
-    bref, bstable, _, _ = NM.reference(plain, R.RefScene(plain), words)
+    bref, bstable, _, _ = R.reference(R.RefScene(plain), words)
     b = R.judge(PS.kernel_samples(rtmi, plain, NMS.seed_of(name), NS.REF_K, NMS.FAMILIES, 0), bref, bstable)
     PS.assert_agreement(name, R.judge(got, ref, stable), b)                                # (a), (b), (c)
 
@@ -96,7 +94,7 @@ def test_a_mistake_fails_the_agreement(inputs, cases, name, mistake):
     """(d): against the kernel, a reference with one deliberate mistake of the model is far from 97 %"""
     words, shutter = inputs(name)
     sc, S, got, (ref, stable, _, _), _ = cases(name)
-    wrong, _, _ = NM.trace(sc, S, words, shutter=shutter, perturb=(mistake,))
+    wrong, _, _ = R.trace(S, words, shutter=shutter, perturb=(mistake,))
     good, bad = R.judge(got, ref, stable), R.judge(got, wrong, stable)
     print(f"\n{name}, {mistake}: within tolerance {100 * good['share']:.2f} % -> {100 * bad['share']:.2f} %")
     PS.assert_perturbation_noticed(good, bad)
@@ -196,7 +194,7 @@ def test_feature_buffers_show_the_mapped_normal(rtmi, inputs):
     words, _ = inputs(name)
     n = NS.REF_W * NS.REF_H
     S, probe = R.RefScene(sc), {}
-    _, sig, _ = NM.trace(sc, S, words[:n], probe=probe)
+    _, sig, _ = R.trace(S, words[:n], probe=probe)
     prim = sig[:, R.SAMPLE_COLUMNS + R.C_PRIM]
     mat = np.where(prim >= 0, S.prims["material"][np.clip(prim, 0, None)], -1)
     mapped = np.isin(mat, [m for m in range(len(S.mats)) if sc.normal_map(m) is not None])

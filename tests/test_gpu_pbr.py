@@ -55,7 +55,7 @@ def cases(rtmi, words):
             sc.render(rtmi.Opts(seed=NS.REF_SEED, sample_count=1), st)
             assert st.kernel_variant & ~PBS.FAMILIES in GENERAL_LAYOUTS and st.kernel_variant & PBS.FAMILIES == PBS.family(name), st.kernel_variant
             got = PS.kernel_samples(rtmi, sc, NS.REF_SEED, NS.REF_K, PBS.FAMILIES, PBS.family(name))
-            made[name] = (sc, S, got, RP.reference(S, words, sc))
+            made[name] = (sc, S, got, R.reference(S, words))
         return made[name]
     return of
 
@@ -67,7 +67,7 @@ def test_kernel_against_fp64(rtmi, words, cases, name):
     assert draws.max() <= NS.REF_DRAWS, draws.max()                                        # (d)
     PBS.check_contents(name, tally)
     plain = PBS.plain_twin(rtmi, name)
-    bref, bstable, _, _ = RP.reference(R.RefScene(plain), words, plain)
+    bref, bstable, _, _ = R.reference(R.RefScene(plain), words)
     b = R.judge(PS.kernel_samples(rtmi, plain, NS.REF_SEED, NS.REF_K, PBS.FAMILIES, 0), bref, bstable)
     PS.assert_agreement(name, R.judge(got, ref, stable), b)                                # (a), (b), (c)
     print("    " + ", ".join(f"{k[4:]} {v}" for k, v in tally.items() if k.startswith("pbr_") and v))
@@ -77,7 +77,7 @@ def test_kernel_against_fp64(rtmi, words, cases, name):
 def test_a_mistake_fails_the_agreement(words, cases, name, mistake):
     """(d): against the kernel, a reference with one deliberate mistake of the model is far from 97 %"""
     sc, S, got, (ref, stable, _, _) = cases(name)
-    wrong, _, _ = RP.trace(S, words, sc, perturb=(mistake,))
+    wrong, _, _ = R.trace(S, words, perturb=(mistake,))
     good, bad = R.judge(got, ref, stable), R.judge(got, wrong, stable)
     print(f"\n{name}, {mistake}: within tolerance {100 * good['share']:.2f} % -> {100 * bad['share']:.2f} %")
     PS.assert_perturbation_noticed(good, bad)
@@ -199,14 +199,14 @@ def test_the_albedo_feature_shows_the_bytes(rtmi, words):
     sc = PBS.scene(rtmi, name)
     n = NS.REF_W * NS.REF_H
     probe, probe32 = {}, {}
-    RP.trace(R.RefScene(sc), words[:n], sc, probe=probe)
-    RP.trace(R.RefScene(sc), words[:n], sc, dtype=np.float32, probe=probe32)
+    R.trace(R.RefScene(sc), words[:n], probe=probe)
+    R.trace(R.RefScene(sc), words[:n], dtype=np.float32, probe=probe32)
     albedo = sc.render_feature(rtmi.FEATURE_ALBEDO, rtmi.Opts(seed=NS.REF_SEED, sample_first=0, sample_count=1)).reshape(-1, 3)
-    rho = probe["albedo"]  # (a presented pbr row: the sentinel's value, bytes in the low 8 bits)
     on = probe["glossy"] & probe32["glossy"] & (probe["albedo"] == probe32["albedo"]).all(axis=1)
     assert on.sum() >= 100, on.sum()
-    c8 = rho[on] - 256 * np.floor(rho[on] / 256)
-    want = c8.astype(np.float32) / np.float32(255)
+    want = probe["albedo"][on].astype(np.float32)  # (a pbr row: c8 / 255 in fp32)
+    c8 = np.rint(want.astype(np.float64) * 255)
+    assert np.array_equal((c8.astype(np.float32) / np.float32(255)), want)
     assert np.abs(albedo[on].astype(np.float64) - want).max() <= 2.0 ** -24, float(np.abs(albedo[on] - want).max())
     assert len(np.unique(c8, axis=0)) >= 20  # (many texels and the solid colour)
 

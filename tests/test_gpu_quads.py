@@ -1,4 +1,4 @@
-"""Quads and boxes on the GPU, against the fp64 statement of ref64.py with ref64_quads' wrappers, sample by sample on
+"""Quads and boxes on the GPU, against the fp64 statement of ref64.py, sample by sample on
 the same draws: criteria (a) - (c) of test_gpu_nee_reference.py with per_sample's thresholds on the six cases of
 quad_scenes.py.  The (b) baseline is the plain kernel on the case's triangle twin (every quad as its two triangles; light
 sampling off, environment, media and movers cleared) against that twin's reference.  Each case asserts from the reference's
@@ -22,7 +22,6 @@ import nee_scenes as NS
 import per_sample as PS
 import quad_scenes as Q
 import ref64 as R
-import ref64_quads as RQ
 
 pytestmark = pytest.mark.gpu
 ROOT = PS.ROOT
@@ -49,7 +48,7 @@ def inputs(rtmi):
 
 @pytest.fixture(scope="module")
 def cases(rtmi, inputs):
-    """name -> (scene, RefScene, kernel samples, (ref, stable, draws, tally of ref64), signatures): rendered and traced once"""
+    """name -> (scene, RefScene, kernel samples, (ref, stable, draws, tally of ref64)): rendered and traced once"""
     made = {}
 
     def of(name):
@@ -58,21 +57,20 @@ def cases(rtmi, inputs):
             S = R.RefScene(sc)
             words, shutter = inputs(name)
             got = PS.kernel_samples(rtmi, sc, Q.seed_of(name), NS.REF_K, Q.FAMILIES, Q.family(name))
-            made[name] = (sc, S, got, Q.reference(sc, S, words, shutter), Q.trace(sc, S, words, shutter)[1])
+            made[name] = (sc, S, got, R.reference(S, words, shutter))
         return made[name]
     return of
 
 
 @pytest.mark.parametrize("name", list(Q.CASES))
 def test_kernel_against_fp64(rtmi, inputs, cases, name):
-    sc, S, got, (ref, stable, draws, _), sig = cases(name)
+    sc, S, got, (ref, stable, draws, tally) = cases(name)
     words, shutter = inputs(name)
     assert len(words) >= 16000 and draws.max() <= NS.REF_DRAWS, draws.max()
-    tally = Q.tally(sc, S, sig, words, shutter)
     Q.check_contents(name, tally)
     plain = Q.plain_twin(rtmi, name)
     assert not (plain.prims()["type"] == Q.QUAD).any()
-    bref, bstable, _, _ = Q.reference(plain, R.RefScene(plain), words)
+    bref, bstable, _, _ = R.reference(R.RefScene(plain), words)
     b = R.judge(PS.kernel_samples(rtmi, plain, Q.seed_of(name), NS.REF_K, Q.FAMILIES, 0), bref, bstable)
     print("\n    " + ", ".join(f"{k} {tally[k]}" for k in Q.CASES[name][3]))
     PS.assert_agreement(name, R.judge(got, ref, stable), b)                                # (a), (b), (c)
@@ -81,9 +79,9 @@ def test_kernel_against_fp64(rtmi, inputs, cases, name):
 @pytest.mark.parametrize("name,mistake", Q.MISTAKES)
 def test_a_wrong_reference_is_noticed(inputs, cases, name, mistake):
     """(d): against the kernel, a reference with one deliberate mistake is far from 97 %"""
-    sc, S, got, (ref, stable, _, _), _ = cases(name)
+    sc, S, got, (ref, stable, _, _) = cases(name)
     words, shutter = inputs(name)
-    wrong, _, _ = Q.trace(sc, S, words, shutter, perturb=(mistake,))
+    wrong, _, _ = R.trace(S, words, shutter=shutter, perturb=(mistake,))
     good, bad = R.judge(got, ref, stable), R.judge(got, wrong, stable)
     print(f"\n{name}, {mistake}: within tolerance {100 * good['share']:.2f} % -> {100 * bad['share']:.2f} %")
     PS.assert_perturbation_noticed(good, bad)
@@ -175,24 +173,23 @@ def test_ray_queries_against_fp64(rtmi):
     d = ((target - o) * rng.uniform(0.2, 3.0, (n, 1))).astype(np.float32)
     h = sc.trace(o, d)
     o64, d64 = o.astype(np.float64), d.astype(np.float64)
-    with RQ.installed():
-        t64, p64 = R.closest_hit(S, o64, d64, np.inf, np.float64)
-        same = h["prim"] == p64
-        both = same & (p64 >= 0)
-        rel = np.abs(h["t"][both] - t64[both]) / np.maximum(1.0, np.abs(t64[both]))
-        isq = both & (S.prims["type"][np.clip(p64, 0, None)] == Q.QUAD)
-        print("same primitive", same.mean(), "hits", int(both.sum()), "on quads", int(isq.sum()), "max rel t", rel.max())
-        assert same.mean() >= 0.99 and rel.max() <= 2e-5 and isq.sum() > 500
-        hit = h["prim"] >= 0
-        p, nn, front = R.hit_record(S, o64[hit], d64[hit], h["t"][hit].astype(np.float64), h["prim"][hit].astype(np.int64), np.float64)
-        dp = np.sqrt(((h["point"][hit] - p) ** 2).sum(axis=1)) / np.maximum(1.0, np.sqrt((p * p).sum(axis=1)))
-        dn = np.abs(h["normal"][hit] - nn).max(axis=1)
-        assert dp.max() <= 1e-5 and dn.max() <= 2e-5, (dp.max(), dn.max())
-        clear = np.abs((d64[hit] * nn).sum(axis=1)) / np.sqrt((d64[hit] * d64[hit]).sum(axis=1)) > 1e-4
-        assert clear.mean() > 0.99 and np.array_equal(h["front"][hit][clear] != 0, front[clear])
-        fq = h["front"][isq] != 0
-        assert 0.05 < fq.mean() < 1.0  # (rays that start inside a box meet its faces from behind)
-        u, v = R.hit_uv(S, o64[isq], d64[isq], h["t"][isq].astype(np.float64), p64[isq], np.float64)
+    t64, p64 = R.closest_hit(S, o64, d64, np.inf, np.float64)
+    same = h["prim"] == p64
+    both = same & (p64 >= 0)
+    rel = np.abs(h["t"][both] - t64[both]) / np.maximum(1.0, np.abs(t64[both]))
+    isq = both & (S.prims["type"][np.clip(p64, 0, None)] == Q.QUAD)
+    print("same primitive", same.mean(), "hits", int(both.sum()), "on quads", int(isq.sum()), "max rel t", rel.max())
+    assert same.mean() >= 0.99 and rel.max() <= 2e-5 and isq.sum() > 500
+    hit = h["prim"] >= 0
+    p, nn, front = R.hit_record(S, o64[hit], d64[hit], h["t"][hit].astype(np.float64), h["prim"][hit].astype(np.int64), np.float64)
+    dp = np.sqrt(((h["point"][hit] - p) ** 2).sum(axis=1)) / np.maximum(1.0, np.sqrt((p * p).sum(axis=1)))
+    dn = np.abs(h["normal"][hit] - nn).max(axis=1)
+    assert dp.max() <= 1e-5 and dn.max() <= 2e-5, (dp.max(), dn.max())
+    clear = np.abs((d64[hit] * nn).sum(axis=1)) / np.sqrt((d64[hit] * d64[hit]).sum(axis=1)) > 1e-4
+    assert clear.mean() > 0.99 and np.array_equal(h["front"][hit][clear] != 0, front[clear])
+    fq = h["front"][isq] != 0
+    assert 0.05 < fq.mean() < 1.0  # (rays that start inside a box meet its faces from behind)
+    u, v = R.hit_uv(S, o64[isq], d64[isq], h["t"][isq].astype(np.float64), p64[isq], np.float64)
     assert np.abs(h["u"][isq] - u).max() <= 1e-5 and np.abs(h["v"][isq] - v).max() <= 1e-5
     assert sc.trace(o, d, occluded=True).tolist() == (h["prim"] >= 0).tolist()
 

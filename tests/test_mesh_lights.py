@@ -12,7 +12,6 @@ import ext_scenes as X
 import mesh_light_scenes as ML
 import nee_scenes as NS
 import ref64 as R
-import ref64_mesh_lights as RM
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "ray-tracing-in-cuda_amd")
@@ -156,7 +155,7 @@ def test_unlisted_emitters_with_the_switch_on(rtmi):
     img = [i for i in range(len(P)) if M["type"][P["material"][i]] == R.DIFFUSE_LIGHT and T["type"][M["texture"][P["material"][i]]] == R.IMAGE]
     assert len(img) == 1 and img[0] not in L["prim"]
     # area and probability against fp64
-    area = np.array([1.0] + [RM.triangle_area(P[i]) for i in tris])
+    area = np.array([1.0] + [R.triangle_area(P[i]) for i in tris])
     power = area * np.array([lum((6.0, 5.0, 4.0))] + [lum((2.0, 1.5, 1.0))] * 2)
     np.testing.assert_allclose(L["area"], area, rtol=1e-6)
     np.testing.assert_allclose(L["probability"], power / power.sum(), rtol=1e-6)
@@ -199,7 +198,7 @@ def test_an_emissive_mesh_is_one_light_per_triangle(rtmi):
     L = sc.lights()
     assert len(L) == 1 + n and (L["shape"][1:] == R.TRIANGLE).all() and list(L["prim"][1:]) == list(range(2, 2 + n))
     P = sc.prims()
-    area = np.array([4.0] + [RM.triangle_area(P[i]) for i in L["prim"][1:]])
+    area = np.array([4.0] + [R.triangle_area(P[i]) for i in L["prim"][1:]])
     np.testing.assert_allclose(L["area"], area, rtol=1e-6)
     power = area * 0.5 * (lum(L["emission"]) + lum(L["emission_odd"]))
     np.testing.assert_allclose(L["probability"], power / power.sum(), rtol=1e-6)
@@ -236,9 +235,9 @@ def test_packed_record_of_a_triangle_light(rtmi):
     for i in range(2):
         rec, ib = w[at + 28 * i:at + 28 * (i + 1)], bits[at + 28 * i:at + 28 * (i + 1)]
         pr = P[L["prim"][i]]
-        v1, e1, e2, n = RM.triangle_record(pr)
+        v1, e1, e2, n = R.triangle_light_record(pr)
         want = np.zeros(28, np.float32)
-        want[2], want[3] = L["probability"][i], np.float32(1.0 / RM.triangle_area(pr))
+        want[2], want[3] = L["probability"][i], np.float32(1.0 / R.triangle_area(pr))
         want[4:7], want[8:11] = (6.0, 1.0, 0.5), (0.5, 2.0, 6.0)
         want[12:15], want[16:19], want[20:23], want[24:27] = v1, e1, e2, n
         wb = want.view(np.int32).copy()
@@ -257,18 +256,15 @@ def words(rtmi):
 
 
 def test_refscene_builds_and_the_wrapper_is_removed(rtmi, words):
+    """(the wrapper that once held the triangle lights is gone for good: ref64.sample_light samples them itself)"""
     sc = ML.scene(rtmi, ML.MIXED)
     S = R.RefScene(sc)
     assert len(S.lights) == 18 and (S.lights["shape"] == R.TRIANGLE).sum() == 16 and len(S.light_of_prim) == 18
-    original = R.sample_light
-    with RM.installed():
-        assert R.sample_light is not original
-    assert R.sample_light is original
     # the density of a sampled point equals the density ref64 states from the hit's side (geometric normal on both)
     rng = np.random.default_rng(1)
     li = int(np.flatnonzero(S.lights["shape"] == R.TRIANGLE)[3])
     p = rng.uniform(-1, 1, (50, 3)) + (0.0, 0.2, 2.5)
-    ld, pl, _, _ = RM.sample_triangle(S, li, p, rng.random(50), rng.random(50), np.float64)
+    ld, pl, _, _, _ = R.sample_light(S, li, p, rng.random(50), rng.random(50), np.float64)
     n = np.repeat(S.prims[S.lights[li]["prim"]]["m"][9:12].astype(np.float64)[None, :], 50, axis=0)
     np.testing.assert_allclose(R.light_pdf_of_hit(S, li, p, ld, np.ones(50), n, np.float64), pl, rtol=1e-12)
 
@@ -279,10 +275,10 @@ def test_fp32_statement_clears_the_share_and_the_case_holds_its_vertices(rtmi, w
     flipping a branch, and the reference's signatures hold the pinned counts"""
     sc = ML.scene(rtmi, name)
     S = R.RefScene(sc)
-    ref, stable, draws, _ = RM.reference(S, words)
+    ref, stable, draws, tally = R.reference(S, words)
     assert draws.max() <= NS.REF_DRAWS
-    r32, _, _ = RM.trace(S, words, dtype=np.float32)
+    r32, _, _ = R.trace(S, words, dtype=np.float32)
     j = R.judge(r32, ref, stable)
     print("\n" + R.row(name + " (fp32 NumPy)", j))
     assert j["share"] >= 0.97 and j["flips"] <= 0.01 and j["bias_ok"], j
-    ML.check_contents(name, RM.tally(RM.trace(S, words)[1], S))
+    ML.check_contents(name, tally)

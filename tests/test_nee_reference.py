@@ -139,7 +139,7 @@ def test_p_l_of_a_hit_is_p_l_of_the_sample(rtmi, light):
     for v in VERTICES:
         n = 4000
         p = np.tile(v, (n, 1))
-        ld, pl, _, _ = R.sample_light(S, 0, p, rng.random(n), rng.random(n), np.float64)
+        ld, pl, _, _, _ = R.sample_light(S, 0, p, rng.random(n), rng.random(n), np.float64)
         t, idx = R.closest_hit(S, p, ld, np.inf, np.float64)
         seen = (idx == 0) & (np.abs(t - 1) < tol)  # (a point on the far wall of the tube is hidden by the near wall)
         assert seen.mean() > (0.3 if light == "cylinder" else 0.999)

@@ -24,7 +24,6 @@ import nee_scenes as NS
 import normal_map_scenes as NMS
 import ref64 as R
 import ref64_normal_map as NM
-import ref64_quads as Q
 import smooth_pack_cases as PC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -278,7 +277,7 @@ def _surface_points(S, rng, n):
             v = pr["m"].astype(T)[:9].reshape(3, 3)
             p[m] = w @ v
         else:
-            q, u, v, _, _, _ = Q.record(pr, T)
+            q, u, v, _, _, _ = R.quad_record(pr, T)
             p[m] = q + rng.uniform(0.01, 0.99, (k, 1)) * u + rng.uniform(0.01, 0.99, (k, 1)) * v
     return idx, p
 
@@ -295,21 +294,20 @@ def test_the_frame_against_central_differences_of_the_parametrisation(rtmi, shap
     rng = np.random.default_rng(23 + NMS.SHAPES.index(shape))
     n = 20000
     idx, p = _surface_points(S, rng, n)
-    with Q.installed():
-        _, g, _ = R.hit_record(S, p - 1.0, np.ones_like(p), np.ones(n), idx, T, True)  # (any ray: the geometric normal's line)
-        g = np.where((rng.integers(0, 2, n) != 0)[:, None], g, -g)
-        a1 = R._unit(np.cross(g, rng.normal(size=(n, 3))))
-        a2 = np.cross(g, a1)
-        d = R._unit(-g + 0.3 * a1 * rng.uniform(-1, 1, (n, 1)) + 0.3 * a2 * rng.uniform(-1, 1, (n, 1)))  # from the side g faces
+    _, g, _ = R.hit_record(S, p - 1.0, np.ones_like(p), np.ones(n), idx, T, ("flat_normals", "nm_off"))  # (any ray: the geometric normal's line)
+    g = np.where((rng.integers(0, 2, n) != 0)[:, None], g, -g)
+    a1 = R._unit(np.cross(g, rng.normal(size=(n, 3))))
+    a2 = np.cross(g, a1)
+    d = R._unit(-g + 0.3 * a1 * rng.uniform(-1, 1, (n, 1)) + 0.3 * a2 * rng.uniform(-1, 1, (n, 1)))  # from the side g faces
 
-        def uv(q):
-            return R.hit_uv(S, q - d, d, np.ones(n), idx, T)
-        h = 1e-6
-        gu, gv = np.zeros((n, 3)), np.zeros((n, 3))
-        for a in (a1, a2):
-            (u1, v1), (u0, v0) = uv(p + h * a), uv(p - h * a)
-            gu += ((u1 - u0) / (2 * h))[:, None] * a
-            gv += ((v1 - v0) / (2 * h))[:, None] * a
+    def uv(q):
+        return R.hit_uv(S, q - d, d, np.ones(n), idx, T)
+    h = 1e-6
+    gu, gv = np.zeros((n, 3)), np.zeros((n, 3))
+    for a in (a1, a2):
+        (u1, v1), (u0, v0) = uv(p + h * a), uv(p - h * a)
+        gu += ((u1 - u0) / (2 * h))[:, None] * a
+        gv += ((v1 - v0) / (2 * h))[:, None] * a
     Tr, Br = np.zeros((n, 3)), np.zeros((n, 3))
     for i in np.unique(idx):
         m = idx == i
@@ -429,7 +427,7 @@ def test_the_raw_tangents_on_the_host(rtmi, driver, shape):
         elif ty == R.TRIANGLE:
             code[m], rec[m, 1:10], rec[m, 10:16] = 3, pr["m"][:9], pr["m_inv"][:6]
         else:
-            _, _, _, qn, A, B = Q.record(pr, T)
+            _, _, _, qn, A, B = R.quad_record(pr, T)
             code[m], rec[m, 1:4], rec[m, 4:7], rec[m, 7:10] = 4, qn, A, B
     words = rec.view(np.uint32).copy()
     words[:, 0] = code
@@ -549,19 +547,6 @@ def test_sanity_of_the_model():
 
 
 # ------------------------------------------------------------------------------------------------------ 5. the cases on the CPU
-def test_without_maps_the_wrapper_is_ref64(rtmi):
-    """on a case's twin without maps ref64_normal_map.trace returns ref64.trace's radiance, signatures and draw counts exactly"""
-    name = "nm_motion"
-    words, shutter = NMS.inputs(rtmi, name)
-    words, shutter = words[:2 * NS.REF_W * NS.REF_H], shutter[:2 * NS.REF_W * NS.REF_H]
-    twin = NMS.scene(rtmi, name, maps=False)
-    S = R.RefScene(twin)
-    a, b = NM.trace(twin, S, words, shutter=shutter), R.trace(S, words, shutter=shutter)
-    for x, y in zip(a, b):
-        assert np.array_equal(x, y)
-    assert R.hit_record.__module__ == "ref64"  # (taken out again)
-
-
 def test_a_case_holds_its_vertices_and_the_mistakes_change_it(rtmi):
     """nm_prims at fp64 on the CPU (the other cases: test_gpu_normal_map.py): the vertices it is there for, the twin's first
     hits, a constant (128, 128, 255) map IS the twin, and every deliberate mistake moves a clear share of the samples"""
@@ -570,22 +555,22 @@ def test_a_case_holds_its_vertices_and_the_mistakes_change_it(rtmi):
     words = words[:4 * NS.REF_W * NS.REF_H]
     sc = NMS.scene(rtmi, name)
     S = R.RefScene(sc)
-    log = NM.new_log()
-    rgb, sig, draws = NM.trace(sc, S, words, log=log)
-    tally = NM.tally(sig, S, sc, log)
+    log = R.new_log()
+    rgb, sig, draws = R.trace(S, words, log=log)
+    tally = R.tally(sig, S, log)
     assert tally["nm_share"] >= NMS.MIN_MAP_SHARE and min(tally[k] for k in NMS.CASES[name][3]) >= 50, tally
-    assert log["mapped"] >= tally["nm_vertices"]
+    assert log["nm_mapped"] >= tally["nm_vertices"]
     twin = NMS.scene(rtmi, name, maps=False)
-    rgb_t, sig_t, _ = NM.trace(twin, R.RefScene(twin), words)
+    rgb_t, sig_t, _ = R.trace(R.RefScene(twin), words)
     assert np.array_equal(sig[:, R.SAMPLE_COLUMNS + R.C_PRIM], sig_t[:, R.SAMPLE_COLUMNS + R.C_PRIM])  # (the geometry is the twin's)
     far = lambda a, b: (np.abs(a - b).max(axis=1) > 1e-4 * np.maximum(1, np.abs(b).max(axis=1))).mean()
     assert far(rgb_t, rgb) > 0.15
-    off, _, _ = NM.trace(sc, S, words, perturb=("nm_off",))
+    off, _, _ = R.trace(S, words, perturb=("nm_off",))
     assert np.array_equal(off, rgb_t)  # (nm_off IS the twin)
     still = NMS.scene(rtmi, name, maps="flat")
-    assert np.array_equal(NM.trace(still, R.RefScene(still), words)[0], rgb_t)  # (and so is a map of texels that leave n)
+    assert np.array_equal(R.trace(R.RefScene(still), words)[0], rgb_t)  # (and so is a map of texels that leave n)
     for mistake in NM.PERTURBATIONS:
-        wrong, _, _ = NM.trace(sc, S, words, perturb=(mistake,))
+        wrong, _, _ = R.trace(S, words, perturb=(mistake,))
         moved = far(wrong, rgb)
         print(f"{name}, {mistake}: {100 * moved:.1f} % of the samples move")
         assert moved > 0.05, (mistake, moved)

@@ -1,6 +1,6 @@
 """Quads and boxes without a GPU: the constructors through C / Python, C++ and JSON with their argument rules, the
 record words, a box's outward normals, rotate-then-translate against the fp64 matrix, the JSON round trip, the light list and
-its records; ref64_quads' wrappers pinned to the unedited ref64 on axis-aligned scenes; csrc/rt_quad.h on the host against the
+its records; ref64's quads pinned to its rectangles on axis-aligned scenes; csrc/rt_quad.h on the host against the
 fp64 statement on random rays (test_primitives_fuzz.py's tolerances and its rule for rays near an edge or near grazing); the
 light's density integrated over the quad's solid angle; the per-sample cases' fp32 NumPy reference; the shipped scene."""
 import json
@@ -14,7 +14,6 @@ import pytest
 import nee_scenes as NS
 import quad_scenes as Q
 import ref64 as R
-import ref64_quads as RQ
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "ray-tracing-in-cuda_amd")
@@ -343,18 +342,17 @@ def _pair(rtmi, quads, nee, checker):
 
 @pytest.mark.parametrize("nee,checker", [(False, False), (True, False), (False, True), (True, True)])
 def test_wrappers_give_the_rects_answers(rtmi, nee, checker):
+    """(named for the wrappers ref64's quads once were: now ref64's own quad code, held to its rectangles on axis-aligned scenes)"""
     words = R.uniforms(rtmi, NS.REF_SEED, 24, 14, 0, 4, NS.REF_DRAWS)
     rects, quads = _pair(rtmi, False, nee, checker), _pair(rtmi, True, nee, checker)
     ra, sa, da = R.trace(R.RefScene(rects), words)
-    rb, sb, db = RQ.trace(R.RefScene(quads), words)
+    rb, sb, db = R.trace(R.RefScene(quads), words)
     assert R.same_signature(sa, sb).all() and np.array_equal(da, db)
     assert np.abs(ra - rb).max() <= 1e-9, np.abs(ra - rb).max()
     t = R.tally(sb, R.RefScene(quads))
     assert t["image_vertices"] > 20
     if nee:
-        assert RQ.tally(sb, R.RefScene(quads))["quad_picks"] > 500
-    # the wrappers are gone again
-    assert R._prim_t.__module__ == "ref64" and R.hit_record.__module__ == "ref64" and R.sample_light.__module__ == "ref64"
+        assert t["quad_picks"] > 500
 
 
 # ---------------------------------------------------------------------------------------- rt_quad.h on the host, random rays
@@ -471,8 +469,9 @@ def test_the_density_integrates_to_one_over_the_solid_angle(rtmi, vertex):
     g = (np.arange(k) + 0.5) / k
     u1, u2 = (x.reshape(-1) for x in np.meshgrid(g, g, indexing="ij"))
     p = np.tile(np.array(vertex, np.float64), (len(u1), 1))
-    ld, pl, rad, _ = RQ.sample_quad(S, 0, p, u1, u2, np.float64)
-    Q3, U, V, nrm, _, _ = RQ.record(S.prims[0], np.float64)
+    ld, pl, rad, _, delta = R.sample_light(S, 0, p, u1, u2, np.float64)
+    assert not delta
+    Q3, U, V, nrm, _, _ = R.quad_record(S.prims[0], np.float64)
     area = np.linalg.norm(np.cross(U, V))
     d2 = (ld * ld).sum(axis=1)
     cosl = np.abs(ld @ nrm) / np.sqrt(d2)
@@ -481,11 +480,9 @@ def test_the_density_integrates_to_one_over_the_solid_angle(rtmi, vertex):
     assert abs(total - 1.0) < 1e-6, total
     assert np.allclose(p + ld, Q3 + u1[:, None] * U + u2[:, None] * V) and np.array_equal(rad, np.tile((4.0, 3.0, 2.0), (len(p), 1)))
     # from the hit's side: a ray from the vertex that hits the quad at the sampled point has the same density
-    pdf = RQ.installed
-    with RQ.installed():
-        back = R.light_pdf_of_hit(S, 0, p, ld, np.ones(len(p)), np.tile(nrm, (len(p), 1)), np.float64)
+    back = R.light_pdf_of_hit(S, 0, p, ld, np.ones(len(p)), np.tile(nrm, (len(p), 1)), np.float64)
     assert np.allclose(back, pl, rtol=1e-12)
-    half = RQ.sample_quad(S, 0, p, u1, u2, np.float64, ("quad_light_half_area",))[1]
+    half = R.sample_light(S, 0, p, u1, u2, np.float64, ("quad_light_half_area",))[1]
     assert np.allclose(half, 2 * pl)
 
 
@@ -509,12 +506,10 @@ def test_fp32_reference_meets_criterion_a(rtmi, inputs, name):
     sc = Q.scene(rtmi, name)
     S = R.RefScene(sc)
     words, shutter = inputs(name)
-    ref, stable, draws, _ = Q.reference(sc, S, words, shutter)
+    ref, stable, draws, tally = R.reference(S, words, shutter)
     assert draws.max() <= NS.REF_DRAWS
-    _, sig, _ = Q.trace(sc, S, words, shutter)
-    r32, _, _ = Q.trace(sc, S, words, shutter, dtype=np.float32)
+    r32, _, _ = R.trace(S, words, shutter=shutter, dtype=np.float32)
     j = R.judge(r32, ref, stable)
-    tally = Q.tally(sc, S, sig, words, shutter)
     print("\n" + R.row(name + " (fp32 NumPy)", j) + "\n    " + ", ".join(f"{k} {tally[k]}" for k in Q.CASES[name][3]))
     assert j["share"] >= 0.97 and j["flips"] <= 0.01, j
     Q.check_contents(name, tally)
@@ -526,8 +521,8 @@ def test_a_mistake_changes_the_reference(rtmi, inputs):
         sc = Q.scene(rtmi, name)
         S = R.RefScene(sc)
         words, shutter = inputs(name)
-        ref, stable, _, _ = Q.reference(sc, S, words, shutter)
-        wrong, _, _ = Q.trace(sc, S, words, shutter, perturb=(mistake,))
+        ref, stable, _, _ = R.reference(S, words, shutter)
+        wrong, _, _ = R.trace(S, words, shutter=shutter, perturb=(mistake,))
         assert R.judge(wrong, ref, stable)["share"] < 0.97, (name, mistake)
 
 
