@@ -478,12 +478,38 @@ int rt_scene_add_cylinder(rt_scene *s, float radius, float zmin, float zmax, int
  * are only evaluated for hits on materials with an image texture. */
 int rt_scene_add_image_texture(rt_scene *s, int rows, int cols, const uint8_t *rgb);
 /* the same from a file: PNG (8 bits per channel, non-interlaced; grey, grey + alpha, RGB, RGBA or palette; alpha is
- * dropped) or binary / text PPM (P6 / P3, maxval 255).  The reference reads its assets through OpenCV, and two of its
+ * kept as a plane of its own for grey + alpha, RGBA and a palette with a tRNS chunk -- DESIGN 7v, below) or binary / text PPM (P6 / P3, maxval 255).  The reference reads its assets through OpenCV, and two of its
  * three "*.png" textures are JPEG files: convert those once
  * (`python -c "from PIL import Image; Image.open('bricks2.png').convert('RGB').save('bricks2.ppm')"`). */
 int rt_scene_add_image_texture_file(rt_scene *s, const char *path);
 /* rows / cols of image texture `texture` and, if out != NULL, its rows*cols*3 bytes; -rt_status on error */
 int rt_scene_get_image(const rt_scene *s, int texture, int *rows, int *cols, uint8_t *out, size_t cap);
+/* Alpha cutouts.  An image texture may carry an alpha plane: rows*cols*4 bytes R G B A here, or a file with alpha.
+ * Colour lookups ignore the plane; it only serves as a material's alpha mask (rt_scene_set_alpha). -> texture id */
+int rt_scene_add_image_texture_rgba(rt_scene *s, int rows, int cols, const uint8_t *rgba);
+/* rows / cols of image texture `texture` and, if out != NULL and the image has an alpha plane, its rows*cols alpha bytes.
+ * -> 1: the image has a plane, 0: it has none (every texel counts as 255; out is left alone); -rt_status on error */
+int rt_scene_get_image_alpha(const rt_scene *s, int texture, int *rows, int *cols, uint8_t *out, size_t cap);
+/* The alpha mask of `material`: the alpha byte a8 of image texture `texture` at the hit record's (u, v) -- the nearest texel,
+ * as an image-textured material reads its colour: the row from u, the column from v, clamped to the last row and column --
+ * against the cutoff byte c8 = clamp(ceil(255 x cutoff), 1, 255), computed once in fp64 (0.5 -> 128).  The hit is TRANSPARENT
+ * iff a8 < c8, a comparison of integers.  A transparent hit is no vertex: nothing of its material is evaluated (no texture,
+ * bump or normal map, no Beer-Lambert segment, no emission), it takes no random draw, counts no bounce and plays no Russian
+ * roulette; the ray goes on from the hit point p = o + t d in the same direction with the usual t_min, so a surface closer
+ * than t_min behind a hole is skipped as behind any vertex (two coincident cards do not show through each other's holes).
+ * A shadow ray's far end stays where it was.  This happens inside one closest-hit query: for camera and BSDF rays, for the
+ * shadow rays of light sampling (area, mesh, analytic and environment lights) and for the first-hit feature passes, whose
+ * albedo, normal and depth are those of the first OPAQUE hit, the depth measured from the camera.  One query passes through
+ * at most 64 transparent hits; the 65th masked hit of the query counts as opaque whatever its texel says.  The texture may
+ * be the material's own base-colour image (the usual RGBA leaf).  On every material but diffuse_light and on every primitive
+ * type.  RT_ERR_ARG for an unknown material, a diffuse_light, a texture that is not an image or has no alpha plane, a cutoff
+ * outside (0, 1] or not finite.  texture = -1 removes the mask.  Refused with RT_ERR_ARG when rendered: a moving sphere whose
+ * material carries a mask; a scene with both a medium and a masked material; the compact sphere-only kernel layouts
+ * (variants 2 and 6); rt_render_hip_count (the counting kernels carry no masks).  The ray queries (rt_trace_hip) stay geometric: they return the closest hit whatever its mask says;
+ * the record carries the material and (u, v), so a caller can look the mask up.  rt_material is unchanged. */
+int rt_scene_set_alpha(rt_scene *s, int material, int texture, float cutoff);
+/* the alpha mask of `material` (either pointer may be NULL): texture -1 and cutoff 0 where it has none; RT_ERR_ARG: no such material */
+int rt_scene_get_alpha(const rt_scene *s, int material, int *texture, float *cutoff);
 /* Noise texture: value(p) = c0 + s (c1 - c0) per channel with s from `noise` at the world-space hit point (on
  * a moving sphere too: the texture swims, as the checker does).  Usable wherever a texture id is: lambertian, plastic (body
  * colour) and diffuse_light; such an emitter emits what the texture says at the hit and, like an image-textured one, is not
@@ -606,6 +632,9 @@ int rt_scene_get_textures(const rt_scene *s, rt_texture *out, int cap);   /* -> 
  * record, strength, 0, 0}, whose offset the material holds in the fourth word of its third record; none without a bump.
  * The normal maps, DESIGN 7u, follow the bumps: one record per mapped material, {word offset of the map's texels, rows, cols,
  * scale}; the material holds MINUS its offset in that same word; none without a map.
+ * The alpha masks, DESIGN 7v: when any material carries a mask, one record per material straight behind the material table,
+ * {word offset of the mask's texels, rows, cols, c8}, rows 0 where the material has none; a texel word's top byte then holds
+ * 255 - a8.
  * The pbr materials' side records, DESIGN 7t, follow those: three records per pbr material, in material order -- {metallic
  * factor, roughness factor, 0, 0}, then the map's texture as a material's second and third record hold theirs (no map: solid
  * white) -- whose offset the material holds in the second word of its first record; none without a pbr material.) */

@@ -49,6 +49,7 @@ struct mytexture {
     // image texture (taichi-version/material.py:96-110, 137-144): rows x cols texels, R G B bytes
     int rows = 0, cols = 0;
     std::vector<uint8_t> rgb;
+    std::vector<uint8_t> alpha;  // an alpha plane: rows x cols bytes, empty: none
     rt_noise noise{};  // noise texture: c0, c1 are its two colours
 };
 inline std::shared_ptr<mytexture> solid_color(color c) {  // texture.cuh:18-19
@@ -65,6 +66,19 @@ inline std::shared_ptr<mytexture> checker_texture(color even, color odd) {  // t
 inline std::shared_ptr<mytexture> image_texture(int rows, int cols, std::vector<uint8_t> rgb) {
     auto t = std::make_shared<mytexture>();
     t->type = RT_TEX_IMAGE, t->rows = rows, t->cols = cols, t->rgb = std::move(rgb);
+    return t;
+}
+
+// an image with an alpha plane: rows x cols x 4 bytes R G B A; the plane serves as an alpha mask (alpha_masked)
+inline std::shared_ptr<mytexture> image_texture_rgba(int rows, int cols, const std::vector<uint8_t> &rgba) {
+    auto t = std::make_shared<mytexture>();
+    t->type = RT_TEX_IMAGE, t->rows = rows, t->cols = cols;
+    const size_t n = rgba.size() / 4;
+    t->rgb.resize(3 * n), t->alpha.resize(n);
+    for (size_t i = 0; i < n; ++i) {
+        t->rgb[3 * i] = rgba[4 * i], t->rgb[3 * i + 1] = rgba[4 * i + 1], t->rgb[3 * i + 2] = rgba[4 * i + 2];
+        t->alpha[i] = rgba[4 * i + 3];
+    }
     return t;
 }
 
@@ -88,6 +102,8 @@ struct material {
     float bump_strength = 0;
     std::shared_ptr<mytexture> normal_map;  // a tangent-space normal map: an image texture, null: none
     float normal_scale = 0;
+    std::shared_ptr<mytexture> alpha;  // an alpha mask: an image texture with an alpha plane, null: none
+    float alpha_cutoff = 0.5f;
     std::shared_ptr<mytexture> map;  // pbr: the metallic-roughness map (G scales the roughness, B the metalness), null: none
 };
 using material_ptr = std::shared_ptr<material>;
@@ -158,6 +174,14 @@ inline material_ptr bumped(const material_ptr &m, std::shared_ptr<mytexture> hei
 inline material_ptr normal_mapped(const material_ptr &m, std::shared_ptr<mytexture> map, float scale = 1.0f) {
     auto b = std::make_shared<material>(*m);
     b->normal_map = std::move(map), b->normal_scale = scale;
+    return b;
+}
+
+// alpha cutouts: a copy of `m` with holes where the alpha byte of `mask` (an image texture with an alpha plane, which
+// may be the material's own colour image) at the hit's (u, v) lies below ceil(255 x cutoff).  Any material but diffuse_light.
+inline material_ptr alpha_masked(const material_ptr &m, std::shared_ptr<mytexture> mask, float cutoff = 0.5f) {
+    auto b = std::make_shared<material>(*m);
+    b->alpha = std::move(mask), b->alpha_cutoff = cutoff;
     return b;
 }
 
@@ -556,11 +580,20 @@ private:
     static void check(int st, const char *where) {
         if (st != RT_OK) throw error(st, where);
     }
+    int add_image(const mytexture &t) {  // (an alpha plane, DESIGN 7v: through the RGBA call)
+        if (t.alpha.empty()) return rt_scene_add_image_texture(s_, t.rows, t.cols, t.rgb.data());
+        std::vector<uint8_t> rgba(t.alpha.size() * 4);
+        for (size_t i = 0; i < t.alpha.size() && 3 * i + 2 < t.rgb.size(); ++i) {
+            rgba[4 * i] = t.rgb[3 * i], rgba[4 * i + 1] = t.rgb[3 * i + 1], rgba[4 * i + 2] = t.rgb[3 * i + 2];
+            rgba[4 * i + 3] = t.alpha[i];
+        }
+        return (size_t)t.rows * t.cols == t.alpha.size() ? rt_scene_add_image_texture_rgba(s_, t.rows, t.cols, rgba.data()) : -RT_ERR_ARG;
+    }
     int texture_id(const std::shared_ptr<mytexture> &t) {
         for (auto &kv : texs_)
             if (kv.first == t) return kv.second;
         int id = t->type == RT_TEX_CHECKER ? rt_scene_add_checker(s_, t->c0.e, t->c1.e)
-                 : t->type == RT_TEX_IMAGE ? rt_scene_add_image_texture(s_, t->rows, t->cols, t->rgb.data())
+                 : t->type == RT_TEX_IMAGE ? add_image(*t)
                  : t->type == RT_TEX_NOISE ? rt_scene_add_noise_texture(s_, t->c0.e, t->c1.e, &t->noise)
                                            : rt_scene_add_solid_color(s_, t->c0.e);
         if (id < 0) throw error(-id, "texture");
@@ -584,6 +617,7 @@ private:
         if (id < 0) throw error(-id, "material");
         if (m->bump) check(rt_scene_set_bump(s_, id, texture_id(m->bump), m->bump_strength), "bump");
         if (m->normal_map) check(rt_scene_set_normal_map(s_, id, texture_id(m->normal_map), m->normal_scale), "normal map");
+        if (m->alpha) check(rt_scene_set_alpha(s_, id, texture_id(m->alpha), m->alpha_cutoff), "alpha mask");
         if (m->type == RT_MAT_PBR && m->map) check(rt_scene_set_pbr_map(s_, id, texture_id(m->map)), "pbr map");
         mats_.emplace_back(m, id);
         return id;

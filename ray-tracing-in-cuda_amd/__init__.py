@@ -266,6 +266,10 @@ _sig("rt_scene_set_bump", C.c_int, _p, C.c_int, C.c_int, C.c_float)
 _sig("rt_scene_get_bump", C.c_int, _p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float))
 _sig("rt_scene_set_normal_map", C.c_int, _p, C.c_int, C.c_int, C.c_float)
 _sig("rt_scene_get_normal_map", C.c_int, _p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float))
+_sig("rt_scene_add_image_texture_rgba", C.c_int, _p, C.c_int, C.c_int, _p)
+_sig("rt_scene_get_image_alpha", C.c_int, _p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), _p, C.c_size_t)
+_sig("rt_scene_set_alpha", C.c_int, _p, C.c_int, C.c_int, C.c_float)
+_sig("rt_scene_get_alpha", C.c_int, _p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float))
 assert _lib.rt_struct_size(24) == C.sizeof(Noise) == 24
 _sig("rt_scene_add_triangle", C.c_int, _p, _f3, _f3, _f3, _f3, _f3, _f3, C.c_int)
 _sig("rt_scene_add_quad", C.c_int, _p, _f3, _f3, _f3, C.c_int, _f3, C.c_float, _f3)
@@ -365,7 +369,8 @@ C_SYMBOLS = [
     "rt_scene_new", "rt_scene_set_background", "rt_scene_set_camera", "rt_scene_add_solid_color",
     "rt_scene_add_checker", "rt_scene_add_lambertian", "rt_scene_add_metal", "rt_scene_add_dielectric",
     "rt_scene_add_rough_metal", "rt_scene_add_plastic", "rt_scene_add_rough_glass", "rt_scene_add_noise_texture", "rt_scene_get_noise",
-    "rt_scene_set_bump", "rt_scene_get_bump", "rt_scene_set_normal_map", "rt_scene_get_normal_map", "rt_scene_add_pbr", "rt_scene_set_pbr_map", "rt_scene_get_pbr_map",
+    "rt_scene_set_bump", "rt_scene_get_bump", "rt_scene_set_normal_map", "rt_scene_get_normal_map",
+    "rt_scene_add_image_texture_rgba", "rt_scene_get_image_alpha", "rt_scene_set_alpha", "rt_scene_get_alpha", "rt_scene_add_pbr", "rt_scene_set_pbr_map", "rt_scene_get_pbr_map",
     "rt_scene_add_diffuse_light", "rt_scene_add_sphere", "rt_scene_add_rect", "rt_scene_add_cylinder",
     "rt_scene_add_image_texture", "rt_scene_add_image_texture_file", "rt_scene_get_image", "rt_scene_add_triangle",
     "rt_scene_add_quad", "rt_scene_add_box", "rt_scene_add_obj", "rt_scene_add_triangle_normals", "rt_scene_add_obj_normals", "rt_set_mesh_normals_override",
@@ -591,11 +596,24 @@ class Scene:
     def checker_texture(self, even, odd) -> int:
         return _check_id(_lib.rt_scene_add_checker(self._h, _v3(even), _v3(odd)), "checker_texture")
 
-    def image_texture(self, pixels) -> int:
-        """Image texture (taichi-version/material.py:137-144) from a (rows, cols, 3) uint8 array or a PPM file."""
+    def image_texture(self, pixels, alpha=None) -> int:
+        """Image texture (taichi-version/material.py:137-144) from a (rows, cols, 3) uint8 array or a PPM / PNG file.
+        alpha: a (rows, cols) uint8 alpha plane (a (rows, cols, 4) array brings its own, as a PNG file with alpha does):
+        colour lookups ignore it, set_alpha() makes it a material's mask."""
         if isinstance(pixels, (str, bytes, os.PathLike)):
+            if alpha is not None:
+                raise ValueError("an image file brings its own alpha")
             return _check_id(_lib.rt_scene_add_image_texture_file(self._h, os.fsencode(pixels)), "image_texture")
         px = np.ascontiguousarray(pixels, dtype=np.uint8)
+        if px.ndim == 3 and px.shape[2] == 4 and alpha is None:
+            px, alpha = np.ascontiguousarray(px[:, :, :3]), px[:, :, 3]
+        if alpha is not None:
+            al = np.ascontiguousarray(alpha, dtype=np.uint8)
+            if px.ndim != 3 or px.shape[2] != 3 or al.shape != px.shape[:2]:
+                raise ValueError("image texture pixels must have shape (rows, cols, 3) and alpha (rows, cols)")
+            rgba = np.ascontiguousarray(np.concatenate([px, al[:, :, None]], axis=2))
+            return _check_id(_lib.rt_scene_add_image_texture_rgba(self._h, px.shape[0], px.shape[1], rgba.ctypes.data_as(C.c_void_p)),
+                             "image_texture")
         if px.ndim != 3 or px.shape[2] != 3:
             raise ValueError("image texture pixels must have shape (rows, cols, 3)")
         return _check_id(_lib.rt_scene_add_image_texture(self._h, px.shape[0], px.shape[1], px.ctypes.data_as(C.c_void_p)),
@@ -641,6 +659,28 @@ class Scene:
         t, k = C.c_int(), C.c_float()
         _check(_lib.rt_scene_get_normal_map(self._h, int(material), C.byref(t), C.byref(k)), "rt_scene_get_normal_map")
         return None if t.value < 0 else (int(t.value), float(k.value))
+
+    def set_alpha(self, material: int, texture: int, cutoff: float = 0.5) -> None:
+        """Alpha cutout: the alpha byte of image texture `texture` at the hit's (u, v) opens a hole in `material`
+        where it lies below ceil(255 x cutoff); cutoff in (0, 1].  Any material but a diffuse_light; texture -1 removes it."""
+        _check(_lib.rt_scene_set_alpha(self._h, int(material), int(texture), float(cutoff)), "rt_scene_set_alpha")
+
+    def alpha(self, material: int):
+        """(texture, cutoff) of the material's alpha mask, or None."""
+        t, k = C.c_int(), C.c_float()
+        _check(_lib.rt_scene_get_alpha(self._h, int(material), C.byref(t), C.byref(k)), "rt_scene_get_alpha")
+        return None if t.value < 0 else (int(t.value), float(k.value))
+
+    def get_image_alpha(self, texture: int):
+        """The (rows, cols) uint8 alpha plane of image texture `texture`, or None where it has none."""
+        rows, cols = C.c_int(), C.c_int()
+        has = _check_id(_lib.rt_scene_get_image_alpha(self._h, texture, C.byref(rows), C.byref(cols), None, 0), "rt_scene_get_image_alpha")
+        if not has:
+            return None
+        out = np.empty((rows.value, cols.value), dtype=np.uint8)
+        _check_id(_lib.rt_scene_get_image_alpha(self._h, texture, None, None, out.ctypes.data_as(C.c_void_p), out.nbytes),
+                  "rt_scene_get_image_alpha")
+        return out
 
     def get_image(self, texture: int) -> np.ndarray:
         rows, cols = C.c_int(), C.c_int()

@@ -414,6 +414,24 @@ int rt_scene_get_normal_map(const rt_scene *s, int material, int *texture, float
     return RT_OK;
 }
 
+// alpha masks: a side table beside the materials, as the bumps are
+int rt_scene_set_alpha(rt_scene *s, int material, int texture, float cutoff) {
+    if (bad_scene(s, "rt_scene_set_alpha")) return RT_ERR_ARG;
+    return set_alpha(s->s, material, texture, cutoff, "rt_scene_set_alpha") ? RT_OK : RT_ERR_ARG;
+}
+
+int rt_scene_get_alpha(const rt_scene *s, int material, int *texture, float *cutoff) {
+    if (bad_scene(s, "rt_scene_get_alpha")) return RT_ERR_ARG;
+    if (material < 0 || material >= (int)s->s.mats.size()) {
+        set_error("rt_scene_get_alpha: unknown material %d (have %zu)", material, s->s.mats.size());
+        return RT_ERR_ARG;
+    }
+    const SceneAlpha *b = scene_alpha(s->s, material);
+    if (texture) *texture = b ? b->texture : -1;
+    if (cutoff) *cutoff = b ? b->cutoff : 0.0f;
+    return RT_OK;
+}
+
 static bool bad_material(rt_scene *s, int material) {
     if (material < 0 || material >= (int)s->s.mats.size()) {
         set_error("object references material %d (have %zu)", material, s->s.mats.size());
@@ -448,6 +466,22 @@ int rt_scene_add_image_texture(rt_scene *s, int rows, int cols, const uint8_t *r
     return add_image_texture(s->s, rows, cols, rgb, "");
 }
 
+// an image with an alpha plane: rows x cols x 4 bytes R G B A
+int rt_scene_add_image_texture_rgba(rt_scene *s, int rows, int cols, const uint8_t *rgba) {
+    if (bad_scene(s, "rt_scene_add_image_texture_rgba")) return -RT_ERR_ARG;
+    if (rows < 1 || cols < 1 || rows > 16384 || cols > 16384 || !rgba) {
+        set_error("image texture: rows and cols must be in 1..16384 and the pixels not null (got %d x %d)", rows, cols);
+        return -RT_ERR_ARG;
+    }
+    const size_t n = (size_t)rows * cols;
+    std::vector<uint8_t> rgb(n * 3), alpha(n);
+    for (size_t i = 0; i < n; ++i) {
+        rgb[3 * i] = rgba[4 * i], rgb[3 * i + 1] = rgba[4 * i + 1], rgb[3 * i + 2] = rgba[4 * i + 2];
+        alpha[i] = rgba[4 * i + 3];
+    }
+    return add_image_texture(s->s, rows, cols, rgb.data(), "", alpha.data());
+}
+
 int rt_scene_add_image_texture_file(rt_scene *s, const char *path) {
     if (bad_scene(s, "rt_scene_add_image_texture_file")) return -RT_ERR_ARG;
     if (!path) {
@@ -474,6 +508,25 @@ int rt_scene_get_image(const rt_scene *s, int texture, int *rows, int *cols, uin
         memcpy(out, im.rgb.data(), im.rgb.size());
     }
     return RT_OK;
+}
+
+int rt_scene_get_image_alpha(const rt_scene *s, int texture, int *rows, int *cols, uint8_t *out, size_t cap) {
+    if (bad_scene(s, "rt_scene_get_image_alpha")) return -RT_ERR_ARG;
+    if (texture < 0 || texture >= (int)s->s.texs.size() || s->s.texs[texture].type != RT_TEX_IMAGE) {
+        set_error("texture %d is not an image texture", texture);
+        return -RT_ERR_ARG;
+    }
+    const SceneImage &im = s->s.images[(size_t)s->s.texs[texture].c0[0]];
+    if (rows) *rows = im.rows;
+    if (cols) *cols = im.cols;
+    if (out && !im.alpha.empty()) {
+        if (cap < im.alpha.size()) {
+            set_error("rt_scene_get_image_alpha: buffer of %zu bytes, the plane needs %zu", cap, im.alpha.size());
+            return -RT_ERR_ARG;
+        }
+        memcpy(out, im.alpha.data(), im.alpha.size());
+    }
+    return im.alpha.empty() ? 0 : 1;
 }
 
 int rt_scene_add_triangle(rt_scene *s, const float v1[3], const float v2[3], const float v3[3], const float uv1[2],
@@ -641,7 +694,7 @@ rt_scene *rt_scene_dna(const rt_scene *base, double angle) {
     if (base) {
         sc = base->s;
         sc.dev.reset();
-        sc.prims.clear(), sc.xforms.clear(), sc.mats.clear(), sc.texs.clear(), sc.noise.clear(), sc.bumps.clear(), sc.pbr_maps.clear(), sc.normal_maps.clear();
+        sc.prims.clear(), sc.xforms.clear(), sc.mats.clear(), sc.texs.clear(), sc.noise.clear(), sc.bumps.clear(), sc.pbr_maps.clear(), sc.normal_maps.clear(), sc.alphas.clear();
     } else {  // gpu-version/basic_scene.json
         sc.width = 1600, sc.height = 900, sc.spp = 100, sc.max_depth = 50;
         sc.background[0] = 0.0005f, sc.background[1] = 0.0007f, sc.background[2] = 0.00099f;

@@ -21,6 +21,12 @@
 //     quad    [nq]  2 x float4   {material(bits), list index(bits), 0, 0} {0, 0, 0, 0}: straight behind the triangles' and as wide
 //                                as theirs, so that the tie rule's list_index_of reads both through one address
 //     mat     [nm]  3 x float4   {kind(bits), p0, p1, p2} {c0.xyz, p3} {c1.xyz, 0}
+//     alpha   [nm]  1 x float4   (only when a material carries an alpha mask; straight behind the material table, at
+//                                off_mat + 3 nm: found without a word of its own in the parameter block, which stays as it was
+//                                for every kernel) one per material: {word offset of the mask's texels (bits), rows (bits), cols
+//                                (bits), c8 (bits)}; rows = 0: the material has no mask.  Read by the instances of alpha_kernel.h
+//                                alone.  (With alpha, a texel word's top byte holds 255 - a8: zero for an opaque texel and for
+//                                every image without alpha)
 //     image   texels of the image textures, one 32-bit word each (r | g << 8 | b << 16), row-major
 //     noise   [nn]  1 x float4   (only with noise textures; behind the texels) per noise texture, in texture order:
 //                                {scale, distortion, seed(bits), style | axis << 2 | octaves << 4 (bits)}.  A material with such a
@@ -150,6 +156,8 @@ struct ItemParams {
 // RenderParams::flags carries the scene's RT_FLAG_* bits (include/rtmi.h) and, above them, what the launch path adds:
 // "this scene has a normal map" (DESIGN 7u).  A kernel argument, so the test is a scalar branch around the whole step
 #define RT_PFLAG_NORMAL_MAPS (1u << 16)
+// alpha cutouts: the holes one query passes through at most; the next masked hit counts as opaque whatever its texel says
+#define RT_ALPHA_MAX_PASSES 64
 
 // kernel parameter block (passed by value: lands in SGPRs / the kernarg segment)
 struct RenderParams {

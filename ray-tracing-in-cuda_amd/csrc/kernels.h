@@ -30,6 +30,8 @@ struct KernelKey {
                            // find_kernel() does not compare `ext` for it
     bool nee = false;      // K_ENV: with light sampling
     bool feature = false;  // K_ENV: a feature pass
+    bool alpha = false;    // an instance of alpha_kernel.h: the family's kernel with the alpha cutouts' code, for a scene
+                           // with masks; every other scene runs the rows without it, whose code knows nothing of masks
 };
 
 // The workgroup of an instance.  Every family runs 4 waves with one 1.5 KB tile accumulator each; the sphere-only
@@ -66,6 +68,9 @@ constexpr bool burst_starts(bool count, bool pool, bool scalar, int cull, bool s
     return RT_BURSTS != 0 && big_group(count, pool, scalar, cull, sph);
 }
 constexpr int kWaveAccBytes = 192 * 8;          // 64 pixels x rgb, 64-bit fixed point
+// alpha cutouts: five words per lane of a 4-wave workgroup behind the accumulators -- what a query keeps while it
+// passes through holes (render_body.h).  Added to the LDS of a launch of an alpha_kernel.h instance
+constexpr int kAlphaLdsBytes = 5 * 4 * 64 * 4;
 constexpr int kWaveSlabBytes = 64 * 10 * 4;     // 64 x {origin, direction, generator state}
 
 struct KernelRow {
@@ -84,6 +89,8 @@ inline size_t group_lds(const KernelRow &row, size_t table_bytes) { return table
 // the rows of a translation unit; *n: how many
 const KernelRow *render_kernel_rows(size_t *n);  // render_kernel.hip: K_PLAIN, K_NEE, K_NESTED, K_FEATURE
 const KernelRow *env_kernel_rows(size_t *n);     // render_env.hip
+const KernelRow *alpha_kernel_rows(size_t *n);      // alpha_kernel.hip: K_PLAIN, K_NESTED, K_FEATURE, K_MOTION with alpha
+const KernelRow *alpha_nee_kernel_rows(size_t *n);  // alpha_nee_kernel.hip: K_NEE, K_ENV with alpha
 const KernelRow *media_kernel_rows(size_t *n);   // render_media.hip
 const KernelRow *motion_kernel_rows(size_t *n);  // render_motion.hip
 const KernelRow *trace_kernel_rows(size_t *n);   // trace.hip

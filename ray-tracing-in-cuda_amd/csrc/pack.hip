@@ -15,6 +15,7 @@
 #include "rt_motion.h"  // (before rt_media.h: philox.h defines RTMI_HD, rt_trig.h takes it as it finds it)
 #include "rt_media.h"
 #include "rt_noise.h"
+#include "rt_alpha.h"
 
 namespace rtmi {
 namespace {
@@ -718,6 +719,8 @@ int lay_out_image(RenderParams &L, const Grid &g, const Scene &s, std::vector<in
     off += 2 * L.nq;  // (the quads' cold records: behind the triangles', and as wide)
     L.off_mat = off;
     off += 3 * L.nm;
+    // the alpha masks' records: one per material, straight behind the material table; no mask in the scene: not a byte
+    if (scene_has_alpha(s)) off += L.nm;
     // texels of the image textures: one 32-bit word each, every image starts on a float4 record
     image_word.assign(s.images.size(), 0);
     for (size_t k = 0; k < s.images.size(); ++k) {
@@ -1027,6 +1030,21 @@ void write_texels(float *I, const Scene &s, const std::vector<int> &image_word) 
         uint32_t *w = reinterpret_cast<uint32_t *>(I) + image_word[k];
         for (size_t t = 0; t < (size_t)im.rows * im.cols; ++t)
             w[t] = (uint32_t)im.rgb[3 * t] | ((uint32_t)im.rgb[3 * t + 1] << 8) | ((uint32_t)im.rgb[3 * t + 2] << 16);
+        // an alpha plane (rt_alpha.h): 255 - a8 in the top byte, so that an opaque texel keeps the word it had
+        if (!im.alpha.empty())
+            for (size_t t = 0; t < (size_t)im.rows * im.cols; ++t) w[t] |= alpha_word_bits(im.alpha[t]);
+    }
+}
+
+// the alpha masks' records: material m's at off_alpha + m (off_alpha = off_mat + 3 nm), {word offset of the mask's texels (bits), rows (bits),
+// cols (bits), c8 (bits)}; a material without a mask keeps zeros (rows = 0)
+void write_alphas(float *I, const Scene &s, int off_alpha, const std::vector<int> &image_word) {
+    for (size_t m = 0; m < s.alphas.size() && m < s.mats.size(); ++m) {
+        if (s.alphas[m].texture < 0) continue;
+        const size_t im = (size_t)s.texs[(size_t)s.alphas[m].texture].c0[0];
+        float *q = rec4(I, off_alpha + (int)m);
+        q[0] = bits(image_word[im]), q[1] = bits(s.images[im].rows), q[2] = bits(s.images[im].cols);
+        q[3] = bits((int)alpha_cutoff_byte((double)s.alphas[m].cutoff));
     }
 }
 
@@ -1419,6 +1437,7 @@ bool pack_round(const Scene &s, std::vector<char> &forced, std::vector<float> &i
     write_noise(I, s, off_noise, noise_rec);
     write_bumps(I, s, off_bump, noise_rec, bump_rec);
     write_normal_maps(I, s, off_nmap, image_word, bump_rec);
+    if (scene_has_alpha(s)) write_alphas(I, s, L.off_mat + 3 * L.nm, image_word);
     write_materials(I, L, s, S, O, image_word, noise_rec, bump_rec, off_pbr);
     if (L.nl > 0) write_lights(I, L, s, S, O, lights);
     if (s.env) write_environment(I, L, s);

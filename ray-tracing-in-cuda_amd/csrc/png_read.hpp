@@ -1,7 +1,8 @@
 // Minimal PNG reader for image textures (8-bit, non-interlaced; grey, grey + alpha, RGB, RGBA, palette).
 // The reference reads its textures through OpenCV (taichi-version/hittable.py:165: cv2.imread); there is no
 // image library on the target, so this is a from-scratch inflate (RFC 1951) + PNG unfilter (RFC 2083).
-// Alpha is dropped (cv2.imread(..., 1) returns three channels too).
+// Alpha is kept as a plane of its own for colour types 4 and 6 and for a palette with a tRNS chunk; every other
+// image has none (cv2.imread(..., 1) returns three channels).
 #pragma once
 #include <cstdint>
 #include <cstring>
@@ -189,8 +190,9 @@ inline bool inflate(const uint8_t *src, size_t n, std::vector<uint8_t> &out, std
     return false;
 }
 
-// -> rows x cols x 3 bytes (R, G, B)
-inline bool read(const std::vector<uint8_t> &file, int &rows, int &cols, std::vector<uint8_t> &rgb, std::string &err) {
+// -> rows x cols x 3 bytes (R, G, B); alpha (may be null): rows x cols alpha bytes where the file carries alpha, else left empty
+inline bool read(const std::vector<uint8_t> &file, int &rows, int &cols, std::vector<uint8_t> &rgb, std::string &err,
+                 std::vector<uint8_t> *alpha = nullptr) {
     static const uint8_t sig[8] = {137, 80, 78, 71, 13, 10, 26, 10};
     if (file.size() < 8 || memcmp(file.data(), sig, 8) != 0) {
         err = "not a PNG file";
@@ -200,7 +202,8 @@ inline bool read(const std::vector<uint8_t> &file, int &rows, int &cols, std::ve
     size_t pos = 8;
     uint32_t w = 0, h = 0;
     int depth = 0, ctype = -1, interlace = 0;
-    std::vector<uint8_t> idat, plte;
+    std::vector<uint8_t> idat, plte, trns;
+    bool has_trns = false;
     while (pos + 12 <= file.size()) {
         const uint32_t len = be32(pos);
         const char *type = (const char *)&file[pos + 4];
@@ -210,6 +213,7 @@ inline bool read(const std::vector<uint8_t> &file, int &rows, int &cols, std::ve
             w = be32(pos + 8), h = be32(pos + 12);
             depth = data[8], ctype = data[9], interlace = data[12];
         } else if (!memcmp(type, "PLTE", 4)) plte.assign(data, data + len);
+        else if (!memcmp(type, "tRNS", 4)) trns.assign(data, data + len), has_trns = true;
         else if (!memcmp(type, "IDAT", 4)) idat.insert(idat.end(), data, data + len);
         else if (!memcmp(type, "IEND", 4)) break;
         pos += 12 + (size_t)len;
@@ -258,9 +262,14 @@ inline bool read(const std::vector<uint8_t> &file, int &rows, int &cols, std::ve
     }
     rows = (int)h, cols = (int)w;
     rgb.resize((size_t)w * h * 3);
+    const bool keep_alpha = alpha && (ctype == 4 || ctype == 6 || (ctype == 3 && has_trns));
+    if (alpha) alpha->clear();
+    if (keep_alpha) alpha->resize((size_t)w * h);
     for (size_t i = 0; i < (size_t)w * h; ++i) {
         const uint8_t *px = &img[i * ch];
         uint8_t *o = &rgb[i * 3];
+        // (a palette entry beyond the tRNS chunk's length is opaque, RFC 2083 section 4.2.1.1)
+        if (keep_alpha) (*alpha)[i] = ctype == 3 ? (px[0] < trns.size() ? trns[px[0]] : (uint8_t)255) : px[ch - 1];
         if (ctype == 3) {
             const size_t k = (size_t)px[0] * 3;
             if (k + 2 >= plte.size()) {

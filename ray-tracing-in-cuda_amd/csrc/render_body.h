@@ -159,6 +159,21 @@
     float cdx = 0, cdy = 0, cdz = 0, pend_r = 0, pend_g = 0, pend_b = 0;
     // MOTION: the shutter time of the lane's sample (rt_motion.h), set where the sample starts and kept for the life of its path
     float mot_s = 0.0f;
+    // ALPHA (alpha cutouts, DESIGN 7v, rt_alpha.h; a constant of the including kernel, true in the instances of alpha_kernel.h
+    // alone, which the host picks for a scene with masks): a winner whose material carries a mask and whose texel is transparent
+    // is no vertex -- the lane's query starts again from the hit point.  What a query keeps while it passes through holes: how
+    // many (at most RT_ALPHA_MAX_PASSES), the ray parameter covered so far, and the origin it set out from, which comes back
+    // with the query's verdict (a shadow ray's continuation, an emitter's pdf, a glass segment and the depth feature all
+    // measure from there).  All zero between queries.  The five words live in LDS, behind the accumulators, in five arrays of
+    // one word per lane (kAlphaLdsBytes, kernels.h: the launch of such an instance adds them).
+    static_assert(!ALPHA || (EXT && !QUERY && !MEDIA), "masks come with the general builds, and not with media");
+    constexpr bool has_alpha = ALPHA;
+    static_assert(!ALPHA || 5 * 4 * 64 * GW == kAlphaLdsBytes, "the alpha state is five words per lane of the workgroup");
+    constexpr int AL_T = 64 * GW, AL_OX = 2 * AL_T, AL_OY = 3 * AL_T, AL_OZ = 4 * AL_T;  // (the pass count: word 0)
+    float *al_state = reinterpret_cast<float *>(lds + staged + GW * (kWaveAccBytes / 16)) + threadIdx.x;
+    if constexpr (ALPHA) {
+        if (has_alpha) al_state[0] = __int_as_float(0), al_state[AL_T] = 0.0f;
+    }
     const int *lslot = reinterpret_cast<const int *>(image + P.off_lslot);
     // ENV: the environment's tables (rt_env.h), built where they are used from launch values (wave-uniform)
     auto env_view = [&]() -> EnvView {
@@ -222,7 +237,11 @@
             // (a shadow ray ends just short of its light point y = o + d: any hit before that occludes)
             // (ENV: the shadow ray towards the environment -- shadow bit 2 -- has no far end)
             // (QUERY: the ray's own far end)
+            // (ALPHA: ... less what the query has covered on its way through holes; al_t is 0 otherwise)
             float best_t = QUERY ? q_tmax : (NEE && shadow != 0 && !(ENV && (shadow & 4) != 0)) ? 0.999f : INFINITY;
+            if constexpr (ALPHA && NEE) {
+                if (shadow != 0 && !(ENV && (shadow & 4) != 0)) best_t = 0.999f - al_state[AL_T];
+            }
             int best_id = -1;
 
             // spheres: sphere::hit, object.cuh:47-75.  Early-outs that need no sqrt:
@@ -1111,17 +1130,34 @@
                     }
                 }
             }
+            // the shadow query's verdict (CLEAR: nothing lies between the vertex and its light point): the light sample counts or is
+            // lost, then the continuation comes back (or, behind an absorbed metal vertex, the path ends).  One text for its two
+            // places -- here, and in the winner's branch of the alpha kernels, where an occluder may be a hole; as text
+            // and not as a lambda, which changed the register allocation of every instance
+#define RT_SHADOW_VERDICT(CLEAR)                                        \
+    {                                                                   \
+        nee_add = (CLEAR);                                              \
+        L_r = pend_r, L_g = pend_g, L_b = pend_b;                       \
+        if ((ENV ? (shadow & 3) : shadow) == 2) active = false;         \
+        dx = cdx, dy = cdy, dz = cdz;                                   \
+        ra = dot3(dx, dy, dz, dx, dy, dz);                              \
+        rinv_a = 1.0f / ra;                                             \
+        shadow = 0;                                                     \
+    }
             if (unfinished) {
-            } else if (NEE && shadow != 0) {
+            } else if (NEE && shadow != 0 && !(ALPHA && has_alpha && best_id >= 0)) {
                 // the shadow query's verdict: the light sample counts when nothing lies between the vertex and its light
                 // point; then the continuation comes back (or, behind an absorbed metal vertex, the path ends)
-                nee_add = best_id < 0;
-                L_r = pend_r, L_g = pend_g, L_b = pend_b;
-                if ((ENV ? (shadow & 3) : shadow) == 2) active = false;
-                dx = cdx, dy = cdy, dz = cdz;
-                ra = dot3(dx, dy, dz, dx, dy, dz);
-                rinv_a = 1.0f / ra;
-                shadow = 0;
+                // (ALPHA: in a scene with masks an occluder may be a hole: such a lane takes the winner's branch below, which
+                //  needs the hit's material and (u, v), and its verdict there.  A ray that got here through holes starts its
+                //  continuation from the vertex it left)
+                if constexpr (ALPHA) {
+                    if (has_alpha) {
+                        if (__float_as_int(al_state[0]) != 0) ox = al_state[AL_OX], oy = al_state[AL_OY], oz = al_state[AL_OZ];
+                        al_state[0] = __int_as_float(0), al_state[AL_T] = 0.0f;
+                    }
+                }
+                RT_SHADOW_VERDICT(best_id < 0)
             } else if (MEDIA && med_i >= 0) {
                 // a medium event: a vertex without a normal and without a material record (the scatter step takes the albedo
                 // from the medium's record), which emits nothing
@@ -1225,7 +1261,19 @@
                 if constexpr (EXT && !QUERY) {
                     if (has_maps) nmap_uv = __float_as_int(M[2].w) < 0 && !(MOTION && mot_i >= 0);
                 }
-                const bool want_uv = EXT && (QUERY || pbr_uv || nmap_uv || (!noise_tex && (kind == MK_LAMBERT_IMAGE || kind == MK_LIGHT_IMAGE || kind == MK_PLASTIC_IMAGE)));
+                // (and where the material carries an alpha mask, DESIGN 7v: its record {texel word offset, rows, cols, c8} stands
+                //  behind the material table, at off_mat + 3 nm + material, rows = 0: none.  A query that has used up its passes reads no mask: the hit is opaque.
+                //  al_shadow: a shadow ray came here only to learn whether its occluder is a hole -- nothing else of the hit is formed)
+                bool al_mask = false, al_pass = false;
+                float4 al_rec = {0.0f, 0.0f, 0.0f, 0.0f};
+                const bool al_shadow = ALPHA && NEE && shadow != 0;
+                if constexpr (ALPHA) {
+                    if (has_alpha && !(MOTION && mot_i >= 0)) {
+                        al_rec = image[P.off_mat + 3 * P.nm + mat];
+                        al_mask = __float_as_int(al_rec.y) != 0 && __float_as_int(al_state[0]) < RT_ALPHA_MAX_PASSES;
+                    }
+                }
+                const bool want_uv = EXT && (al_shadow ? al_mask : (QUERY || pbr_uv || nmap_uv || al_mask || (!noise_tex && (kind == MK_LAMBERT_IMAGE || kind == MK_LIGHT_IMAGE || kind == MK_PLASTIC_IMAGE))));
                 // a triangle's area weights (hittable.py:54-58), stated once: of the plane point for (u, v), and -- smooth shading,
                 // DESIGN 7l -- of the vertex normals.  The NORMALS part (device_scene.h) is there only when the scene has a triangle
                 // with vertex normals: where it lies is a wave-uniform word of the camera block, as for the media and the movers.
@@ -1321,14 +1369,44 @@
                         tv = fmaf(c1.w, w3, fmaf(c1.y, w2, c0.w * w1));
                         if (k >= nt) tu = w1, tv = w2;  // a quad's (a, b)
                     }
+                    // the mask's verdict (rt_alpha.h): the texel of the mask's image at this (u, v), its alpha byte against c8
+                    if constexpr (ALPHA) {
+                        if (al_mask) al_pass = alpha_transparent(image_texel_word(image, al_rec, tu, tv), (uint32_t)__float_as_int(al_rec.w));
+                    }
                     if constexpr (QUERY) {
                         // the query's answer: the record as it stands here, the primitive by its index in the scene's list
                         put_record(q_ray, best_t, list_index_of(P, image, best_id), mat, front ? 1 : 0, nx, ny, nz, tu, px, py, pz, tv);
                         active = false;
                         kind = -1;
                     } else
-                    if (!pbr_uv && (kind == MK_LAMBERT_IMAGE || kind == MK_LIGHT_IMAGE || kind == MK_PLASTIC_IMAGE) && !noise_tex) image_texel(image, M[1], tu, tv, tex_r, tex_g, tex_b);
+                    if (!pbr_uv && (kind == MK_LAMBERT_IMAGE || kind == MK_LIGHT_IMAGE || kind == MK_PLASTIC_IMAGE) && !noise_tex && !al_pass && !al_shadow) image_texel(image, M[1], tu, tv, tex_r, tex_g, tex_b);
                 }
+                // ALPHA: the transition.  A hole: the query starts again from p = o + t d with everything else of the lane as it
+                // is -- no vertex, no draw, no bounce.  A surface: the query ends; if it came through holes, the origin it set
+                // out from comes back and t counts from there.  A shadow ray takes its verdict here (occluded) and is done.
+                if constexpr (ALPHA) {
+                    if (has_alpha) {
+                        const int al_n = __float_as_int(al_state[0]);
+                        if (al_pass) {
+                            if (al_n == 0) al_state[AL_OX] = ox, al_state[AL_OY] = oy, al_state[AL_OZ] = oz;
+                            ox = fmaf(best_t, dx, ox), oy = fmaf(best_t, dy, oy), oz = fmaf(best_t, dz, oz);
+                            al_state[AL_T] += best_t;
+                            al_state[0] = __int_as_float(al_n + 1);
+                            kind = -1;
+                        } else {
+                            if (al_n != 0) {
+                                ox = al_state[AL_OX], oy = al_state[AL_OY], oz = al_state[AL_OZ];
+                                best_t += al_state[AL_T];
+                            }
+                            al_state[0] = __int_as_float(0), al_state[AL_T] = 0.0f;
+                            if (al_shadow) {  // (an opaque occluder: the light sample is lost)
+                                RT_SHADOW_VERDICT(false)
+                                kind = -1;
+                            }
+                        }
+                    }
+                }
+                if (!(ALPHA && kind < 0)) {  // (a hole and a shadow ray's occluder: nothing of the material is evaluated)
                 // The solid textures' values: a noise texture under a lambertian, an emitter or a plastic, and both textures of a
                 // pbr material -- ONE copy of the noise code: a second pass of the same call site evaluates a pbr material's
                 // noise map.  Then a pbr hit's parameters (rt_pbr.h): its image, solid and checker sources, and everything to
@@ -1484,11 +1562,15 @@
                     path_done = true;  // absorbed: main.cu:55-58
                     kind = -1;
                 }
+                }  // if (!(ALPHA && kind < 0))
             } else if (QUERY) {
                 put_record(q_ray, INFINITY, -1, 0, 0, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f);
                 active = false;
             } else {
                 // miss: main.cpp:36-38 (sky) or main.cu:63 (constant background)
+                if constexpr (ALPHA) {
+                    if (has_alpha) al_state[0] = __int_as_float(0), al_state[AL_T] = 0.0f;  // (the path ends here: the origin is of no use any more)
+                }
                 float bg_r, bg_g, bg_b;
                 float env_w = 1.0f;  // ENV + NEE: the MIS weight of a BSDF ray that escapes
                 if constexpr (ENV) {
@@ -1519,6 +1601,7 @@
                 path_done = true;
                 if (COUNT) c_misses++;
             }
+#undef RT_SHADOW_VERDICT
             }  // if (active): rects, cylinders, triangles, shading part 1
           }
         }

@@ -17,6 +17,7 @@ __global__ __launch_bounds__(256, NEE_ ? RT_NEE_WAVES_PER_SIMD : RT_WAVES_PER_SI
     static_assert(!(NEE_ && AOV_), "a feature sample ends at its first query");
     constexpr bool COUNT = false, POOL = true, EXT = true, SPH = false, NEE = NEE_, AOV = AOV_, ENV = true, MEDIA = false, MOTION = false, QUERY = false;
     constexpr TraceArgs TQ{nullptr, nullptr, 0u, 0};
+    constexpr bool ALPHA = false;  // (alpha cutouts, DESIGN 7v: the instances of alpha_kernel.h alone)
 #include "render_body.h"
 }
 

@@ -33,9 +33,9 @@ void launch_adaptive_merge(const long long *A, const long long *B, const int *ti
                            int tiles_x, hipStream_t stream);
 // the row of a render variant (rt_opts.variant, never 0) -- render_kernel, or render_nested_kernel for 52; null: no such build.
 // Its cull is the variant's candidate search.  ext: the build with triangles and image textures; count: the counting build
-static const KernelRow *variant_row(unsigned variant, bool ext = false, bool count = false) {
-    const KernelRow *row = find_kernel({K_PLAIN, variant, ext, count});
-    return row ? row : find_kernel({K_NESTED, variant, ext, count});
+static const KernelRow *variant_row(unsigned variant, bool ext = false, bool count = false, bool alpha = false) {
+    const KernelRow *row = find_kernel({K_PLAIN, variant, ext, count, false, false, alpha});
+    return row ? row : find_kernel({K_NESTED, variant, ext, count, false, false, alpha});
 }
 
 static bool variant_exists(unsigned variant) { return variant == 0 || variant_row(variant); }
@@ -630,6 +630,8 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     ext = ext || scene_has_noise(s);   // (and the noise textures')
     ext = ext || scene_has_bump(s);    // (and the bumps')
     ext = ext || scene_has_normal_map(s);  // (and the normal maps', DESIGN 7u -- an image texture, so it is set already)
+    const bool alpha = scene_has_alpha(s);  // (alpha masks, DESIGN 7v: an image texture's plane, so ext is set already)
+    ext = ext || alpha;
     const bool force_ext = knob_set("RTMI_FORCE_EXT");  // measurement: the EXT builds on scenes that do not need them
     const int device = o ? o->device : 0;
     DeviceScope scope;
@@ -709,6 +711,28 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     }
     // an environment map: kernels of their own, for the general layouts
     const bool env = P.env_rows > 0;
+    // alpha masks: what no kernel renders
+    if (alpha) {
+        if (count) {
+            set_error("rt_render_hip_count: this scene has a material with an alpha mask, which the counting kernels do not carry");
+            return RT_ERR_ARG;
+        }
+        if (variant == 2 || variant == 6) {
+            set_error("kernel variant %u is a compact sphere-only layout, which knows no alpha mask: use variant 0, 16, 36 or 44", variant);
+            return RT_ERR_ARG;
+        }
+        if (media) {
+            set_error("this scene has participating media and a material with an alpha mask, which no kernel combines (the media "
+                      "kernels draw one free-flight distance per query): remove the media or the masks");
+            return RT_ERR_ARG;
+        }
+        for (const rt_moving_sphere &m : s.movers)
+            if (scene_alpha(s, m.material)) {
+                set_error("this scene has a moving sphere whose material carries an alpha mask, which no kernel renders (the holes "
+                          "would swim through the ball): remove the mask or give the mover another material");
+                return RT_ERR_ARG;
+            }
+    }
     if (media) {
         if (nee) {
             set_error("this scene has participating media and light sampling with emitters to sample, which no kernel combines: switch one of them off");
@@ -823,18 +847,20 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     // ---- the instance: resolved once; the block size, the per-wave LDS, the launches, the grid size and the LDS limit go
     // through its row
     const char *family = env ? "environment" : media ? "media" : motion ? "motion" : feature >= 0 ? "feature" : nullptr;
-    const KernelRow *kernel = env            ? find_kernel({K_ENV, variant, true, false, nee, feature >= 0})
+    // (a scene with alpha masks, DESIGN 7v: the family's instance of alpha_kernel.h; every other scene: the rows it always ran)
+    const KernelRow *kernel = env            ? find_kernel({K_ENV, variant, true, false, nee, feature >= 0, alpha})
                               : media        ? find_kernel({K_MEDIA, variant, true})
-                              : motion       ? find_kernel({K_MOTION, variant, true})
-                              : feature >= 0 ? find_kernel({K_FEATURE, variant, true})
-                              : nee          ? find_kernel({K_NEE, variant, true})
-                                             : variant_row(variant, ext, count);
+                              : motion       ? find_kernel({K_MOTION, variant, true, false, false, false, alpha})
+                              : feature >= 0 ? find_kernel({K_FEATURE, variant, true, false, false, false, alpha})
+                              : nee          ? find_kernel({K_NEE, variant, true, false, false, false, alpha})
+                                             : variant_row(variant, ext, count, alpha);
     if (!kernel) {
         if (family) set_error("layout %u has no %s kernel", variant, family);
         else set_error("kernel variant %u has no %s build", variant, count ? "counting" : (ext ? "triangle / texture" : "such"));
         return env || media || motion ? RT_ERR_ARG : RT_ERR_LIMIT;
     }
-    const size_t lds_bytes = group_lds(*kernel, tables_global ? 0 : hot_bytes);
+    // (alpha masks, DESIGN 7v: the passing queries' state, behind the accumulators of the 4-wave workgroups that render such a scene)
+    const size_t lds_bytes = group_lds(*kernel, tables_global ? 0 : hot_bytes) + (kernel->key.alpha ? (size_t)kAlphaLdsBytes : 0);
     if (knob_set("RTMI_DEBUG_LAYOUT")) {
         const float *g = cache.image.data() + (size_t)P.off_grid * 4;
         int gn[3];

@@ -83,6 +83,7 @@ __global__ __launch_bounds__(64 * (big_group(COUNT, POOL, SCALAR, CULL, SPH) ? k
                                                      DevCounters *__restrict__ counters) {
     constexpr bool NEE = false, AOV = false, ENV = false, MEDIA = false, MOTION = false, QUERY = false;
     constexpr TraceArgs TQ{nullptr, nullptr, 0u, 0};
+    constexpr bool ALPHA = false;  // (alpha cutouts, DESIGN 7v: the instances of alpha_kernel.h alone)
 #include "render_body.h"
 }
 
@@ -95,6 +96,7 @@ __global__ __launch_bounds__(256, RT_NEE_WAVES_PER_SIMD) void render_nee_kernel(
                                                          DevCounters *__restrict__ counters) {
     constexpr bool COUNT = false, POOL = true, EXT = true, SPH = false, NEE = true, AOV = false, ENV = false, MEDIA = false, MOTION = false, QUERY = false;
     constexpr TraceArgs TQ{nullptr, nullptr, 0u, 0};
+    constexpr bool ALPHA = false;  // (alpha cutouts, DESIGN 7v: the instances of alpha_kernel.h alone)
 #include "render_body.h"
 }
 
@@ -109,6 +111,7 @@ __global__ __launch_bounds__(256, RT_WAVES_PER_SIMD) void render_nested_kernel(c
     constexpr bool POOL = true, SCALAR = true, SPH = false, NEE = false, AOV = false, ENV = false, MEDIA = false, MOTION = false, QUERY = false;
     constexpr TraceArgs TQ{nullptr, nullptr, 0u, 0};
     constexpr int CULL = 8;
+    constexpr bool ALPHA = false;  // (alpha cutouts, DESIGN 7v: the instances of alpha_kernel.h alone)
 #include "render_body.h"
 }
 
@@ -123,6 +126,7 @@ __global__ __launch_bounds__(256, RT_WAVES_PER_SIMD) void render_feature_kernel(
                                                              DevCounters *__restrict__ counters) {
     constexpr bool COUNT = false, POOL = true, EXT = true, SPH = false, NEE = false, AOV = true, ENV = false, MEDIA = false, MOTION = false, QUERY = false;
     constexpr TraceArgs TQ{nullptr, nullptr, 0u, 0};
+    constexpr bool ALPHA = false;  // (alpha cutouts, DESIGN 7v: the instances of alpha_kernel.h alone)
 #include "render_body.h"
 }
 
@@ -212,14 +216,15 @@ const KernelRow *render_kernel_rows(size_t *n) {
 bool has_ablations() { return RTMI_ABLATIONS != 0; }
 
 const KernelRow *find_kernel(const KernelKey &key) {
-    const KernelRow *(*const tables[])(size_t *) = {render_kernel_rows, env_kernel_rows, media_kernel_rows, motion_kernel_rows, trace_kernel_rows};
+    const KernelRow *(*const tables[])(size_t *) = {render_kernel_rows, env_kernel_rows, media_kernel_rows, motion_kernel_rows, trace_kernel_rows,
+                                                       alpha_kernel_rows, alpha_nee_kernel_rows};
     for (auto rows_of : tables) {
         size_t n = 0;
         const KernelRow *rows = rows_of(&n);
         for (size_t i = 0; i < n; ++i) {
             const KernelKey &r = rows[i].key;
             if (r.family == key.family && r.variant == key.variant && r.count == key.count && (key.count || r.ext == key.ext) &&
-                r.nee == key.nee && r.feature == key.feature)
+                r.nee == key.nee && r.feature == key.feature && r.alpha == key.alpha)
                 return &rows[i];
         }
     }

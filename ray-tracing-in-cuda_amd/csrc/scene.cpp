@@ -452,6 +452,47 @@ bool set_normal_map(Scene &s, int material, int texture, float scale, const char
     return true;
 }
 
+// alpha masks: the argument rules of a mask, shared by the C call, the JSON reader and scene_validate.
+// none_ok: texture -1 (no mask) passes
+static bool alpha_ok(const Scene &s, int material, int texture, float cutoff, bool none_ok, const char *where) {
+    if (material < 0 || material >= (int)s.mats.size()) {
+        set_error("%s: unknown material %d (have %zu)", where, material, s.mats.size());
+        return false;
+    }
+    if (none_ok && texture == -1) return true;
+    if (s.mats[(size_t)material].type == RT_MAT_DIFFUSE_LIGHT) {
+        set_error("%s: material %d is a diffuse_light, which takes no alpha mask (the light sampler would not know its holes)", where, material);
+        return false;
+    }
+    if (texture < 0 || texture >= (int)s.texs.size() || s.texs[(size_t)texture].type != RT_TEX_IMAGE) {
+        set_error("%s: alpha texture %d is not an image texture", where, texture);
+        return false;
+    }
+    const int im = (int)s.texs[(size_t)texture].c0[0];
+    if (im < 0 || im >= (int)s.images.size() || s.images[(size_t)im].alpha.empty()) {
+        set_error("%s: alpha texture %d has no alpha plane", where, texture);
+        return false;
+    }
+    if (!(cutoff > 0.0f && cutoff <= 1.0f)) {  // (a NaN fails the comparison)
+        set_error("%s: alpha cutoff must lie in (0, 1] (got %g)", where, (double)cutoff);
+        return false;
+    }
+    return true;
+}
+
+bool set_alpha(Scene &s, int material, int texture, float cutoff, const char *where) {
+    if (!alpha_ok(s, material, texture, cutoff, true, where)) return false;
+    if (texture == -1) {  // removes; the table ends at the last masked material
+        if ((size_t)material < s.alphas.size()) s.alphas[(size_t)material] = SceneAlpha();
+        while (!s.alphas.empty() && s.alphas.back().texture < 0) s.alphas.pop_back();
+    } else {
+        if (s.alphas.size() <= (size_t)material) s.alphas.resize((size_t)material + 1);
+        s.alphas[(size_t)material].texture = texture, s.alphas[(size_t)material].cutoff = cutoff;
+    }
+    s.touch();
+    return true;
+}
+
 // the metallic-roughness map of a pbr material: the argument rules, shared by the C call, the JSON reader and
 // scene_validate.  none_ok: texture -1 (no map) passes
 static bool pbr_map_ok(const Scene &s, int material, int texture, bool none_ok, const char *where) {
@@ -532,6 +573,12 @@ int scene_validate(const Scene &s) {
         snprintf(where, sizeof where, "material %zu", i);
         if (!normal_map_ok(s, (int)i, s.normal_maps[i].texture, s.normal_maps[i].scale, false, where)) return RT_ERR_SCENE;
     }
+    for (size_t i = 0; i < s.alphas.size(); ++i) {
+        if (s.alphas[i].texture < 0) continue;
+        char where[32];
+        snprintf(where, sizeof where, "material %zu", i);
+        if (!alpha_ok(s, (int)i, s.alphas[i].texture, s.alphas[i].cutoff, false, where)) return RT_ERR_SCENE;
+    }
     for (size_t i = 0; i < s.pbr_maps.size(); ++i) {
         if (s.pbr_maps[i] < 0) continue;
         char where[32];
@@ -543,7 +590,8 @@ int scene_validate(const Scene &s) {
         if (t.type == RT_TEX_IMAGE) {
             const int im = (int)t.c0[0];
             if (im < 0 || im >= (int)s.images.size() || s.images[im].rows != (int)t.c0[1] || s.images[im].cols != (int)t.c0[2] ||
-                s.images[im].rgb.size() != (size_t)s.images[im].rows * s.images[im].cols * 3) {
+                s.images[im].rgb.size() != (size_t)s.images[im].rows * s.images[im].cols * 3 ||
+                (!s.images[im].alpha.empty() && s.images[im].alpha.size() != (size_t)s.images[im].rows * s.images[im].cols)) {
                 set_error("texture %zu references image %d, which is missing or has another size", i, im);
                 return RT_ERR_SCENE;
             }
@@ -590,7 +638,7 @@ int scene_validate(const Scene &s) {
 }
 
 // ---------------------------------------------------------------- image textures, triangles, meshes
-int add_image_texture(Scene &s, int rows, int cols, const uint8_t *rgb, const std::string &file) {
+int add_image_texture(Scene &s, int rows, int cols, const uint8_t *rgb, const std::string &file, const uint8_t *alpha) {
     if (rows < 1 || cols < 1 || rows > 16384 || cols > 16384 || !rgb) {
         set_error("image texture: rows and cols must be in 1..16384 and the pixels not null (got %d x %d)", rows, cols);
         return -RT_ERR_ARG;
@@ -598,6 +646,7 @@ int add_image_texture(Scene &s, int rows, int cols, const uint8_t *rgb, const st
     SceneImage im;
     im.rows = rows, im.cols = cols, im.file = file;
     im.rgb.assign(rgb, rgb + (size_t)rows * cols * 3);
+    if (alpha) im.alpha.assign(alpha, alpha + (size_t)rows * cols);
     s.images.push_back(std::move(im));
     rt_texture t;
     memset(&t, 0, sizeof t);
@@ -673,7 +722,8 @@ static int read_ppm(const char *path, int &rows, int &cols, std::vector<uint8_t>
     return RT_OK;
 }
 
-int read_image_file(const char *path, int &rows, int &cols, std::vector<uint8_t> &rgb) {
+int read_image_file(const char *path, int &rows, int &cols, std::vector<uint8_t> &rgb, std::vector<uint8_t> *alpha) {
+    if (alpha) alpha->clear();
     // PNG by signature (8-bit, non-interlaced), else PPM
     bool is_png = false;
     if (FILE *fp = fopen(path, "rb")) {
@@ -689,7 +739,7 @@ int read_image_file(const char *path, int &rows, int &cols, std::vector<uint8_t>
         fclose(fp);
         if (is_png) {
             std::string err;
-            if (!png::read(file, rows, cols, rgb, err)) {
+            if (!png::read(file, rows, cols, rgb, err, alpha)) {
                 set_error("%s: %s", path, err.c_str());
                 return RT_ERR_IO;
             }
@@ -701,10 +751,10 @@ int read_image_file(const char *path, int &rows, int &cols, std::vector<uint8_t>
 
 int add_image_texture_file(Scene &s, const char *path) {
     int rows = 0, cols = 0;
-    std::vector<uint8_t> rgb;
-    int rc = read_image_file(path, rows, cols, rgb);
+    std::vector<uint8_t> rgb, alpha;
+    int rc = read_image_file(path, rows, cols, rgb, &alpha);
     if (rc) return -rc;
-    return add_image_texture(s, rows, cols, rgb.data(), path);
+    return add_image_texture(s, rows, cols, rgb.data(), path, alpha.empty() ? nullptr : alpha.data());
 }
 
 // Triangle.__init__, taichi-version/hittable.py:95-110: the unit normal (v2 - v1) x (v3 - v1) / |..| is a
@@ -1264,6 +1314,7 @@ int scene_from_json(const char *text, size_t len, Scene &s, const char *base_dir
                     else {
                         id = add_image_texture_file(s, resolve(f->str).c_str());
                         if (id >= 0) s.images.back().file = f->str;  // serialised as given
+                        if (t.find("alpha")) r.fail("%s: \"alpha\" goes with inline \"data\" (a file brings its own)", where);
                     }
                 } else {
                     const int rows = r.integer(t, "rows", where), cols = r.integer(t, "cols", where);
@@ -1278,7 +1329,21 @@ int scene_from_json(const char *text, size_t len, Scene &s, const char *base_dir
                                 r.fail("%s: \"data\"[%zu] is not a byte", where, k);
                             else px[k] = (uint8_t)v.num;
                         }
-                        if (r.ok) id = add_image_texture(s, rows, cols, px.data(), "");
+                        // an alpha plane: rows * cols bytes beside the pixels
+                        std::vector<uint8_t> al;
+                        if (const JsonValue *a = t.find("alpha")) {
+                            if (!a->is_array() || a->arr.size() != (size_t)rows * cols) r.fail("%s: \"alpha\" must be an array of rows * cols bytes", where);
+                            else {
+                                al.resize(a->arr.size());
+                                for (size_t k = 0; k < al.size() && r.ok; ++k) {
+                                    const JsonValue &v = a->arr[k];
+                                    if (!v.is_number() || v.num < 0 || v.num > 255 || v.num != std::floor(v.num))
+                                        r.fail("%s: \"alpha\"[%zu] is not a byte", where, k);
+                                    else al[k] = (uint8_t)v.num;
+                                }
+                            }
+                        }
+                        if (r.ok) id = add_image_texture(s, rows, cols, px.data(), "", al.empty() ? nullptr : al.data());
                     }
                 }
                 if (r.ok && id < 0) return -id;
@@ -1378,6 +1443,22 @@ int scene_from_json(const char *text, size_t len, Scene &s, const char *base_dir
                     if (nmap->find("scale")) nmap_s = (float)r.num(*nmap, "scale", bw);
                 }
             }
+            // an alpha mask on any material but an emitter: {"texture": <image texture with alpha>, "cutoff": <number, default 0.5>}
+            const JsonValue *amask = m.find("alpha");
+            int amask_tex = -1;
+            float amask_c = 0.5f;
+            if (amask) {
+                if (!amask->is_object()) r.fail("%s: \"alpha\" must be an object", where);
+                else {
+                    char bw[128];
+                    snprintf(bw, sizeof bw, "%s: alpha", where);
+                    for (const auto &kv : amask->obj)
+                        if (kv.first != "texture" && kv.first != "cutoff") r.fail("%s: unknown field \"%s\"", bw, kv.first.c_str());
+                    amask_tex = r.integer(*amask, "texture", bw);
+                    if (amask->find("cutoff")) amask_c = (float)r.num(*amask, "cutoff", bw);
+                    if (r.ok && amask_tex < 0) r.fail("%s: \"texture\" must be an image texture", bw);
+                }
+            }
             if (ty->str == "lambertian") {
                 rec.type = RT_MAT_LAMBERTIAN;
                 rec.texture = r.integer(m, "texture", where);
@@ -1390,7 +1471,7 @@ int scene_from_json(const char *text, size_t len, Scene &s, const char *base_dir
                 rec.fuzz = f < 1 ? f : 1;  // material.cuh:61
             } else if (ty->str == "rough_metal") {  // albedo is F0, fuzz holds the roughness
                 rec.type = RT_MAT_ROUGH_METAL;
-                only_keys(m, {"type", "albedo", "roughness", "bump", "normal_map"});
+                only_keys(m, {"type", "albedo", "roughness", "bump", "normal_map", "alpha"});
                 double c[3];
                 r.vec3(m, "albedo", where, c);
                 for (int k = 0; k < 3; ++k) rec.albedo[k] = (float)c[k];
@@ -1398,14 +1479,14 @@ int scene_from_json(const char *text, size_t len, Scene &s, const char *base_dir
                 if (r.ok && !glossy_material_ok(rec, s.texs.size(), where)) r.ok = false;
             } else if (ty->str == "plastic") {  // texture is the body colour, fuzz the roughness, ir the coat's index
                 rec.type = RT_MAT_PLASTIC;
-                only_keys(m, {"type", "texture", "ior", "roughness", "bump", "normal_map"});
+                only_keys(m, {"type", "texture", "ior", "roughness", "bump", "normal_map", "alpha"});
                 rec.texture = r.integer(m, "texture", where);
                 rec.ir = (float)r.num(m, "ior", where);
                 rec.fuzz = (float)r.num(m, "roughness", where);
                 if (r.ok && !glossy_material_ok(rec, s.texs.size(), where)) r.ok = false;
             } else if (ty->str == "pbr") {  // fuzz holds the roughness factor, albedo[0] the metallic factor
                 rec.type = RT_MAT_PBR;
-                only_keys(m, {"type", "texture", "metallic", "roughness", "ior", "metallic_roughness", "bump", "normal_map"});
+                only_keys(m, {"type", "texture", "metallic", "roughness", "ior", "metallic_roughness", "bump", "normal_map", "alpha"});
                 rec.texture = r.integer(m, "texture", where);
                 rec.albedo[0] = (float)r.num(m, "metallic", where);
                 rec.fuzz = (float)r.num(m, "roughness", where);
@@ -1414,7 +1495,7 @@ int scene_from_json(const char *text, size_t len, Scene &s, const char *base_dir
                 if (r.ok && !glossy_material_ok(rec, s.texs.size(), where)) r.ok = false;
             } else if (ty->str == "rough_glass") {  // fuzz holds the roughness, albedo the absorption coefficient
                 rec.type = RT_MAT_ROUGH_GLASS;
-                only_keys(m, {"type", "ir", "roughness", "absorption", "tint", "tint_distance", "bump", "normal_map"});
+                only_keys(m, {"type", "ir", "roughness", "absorption", "tint", "tint_distance", "bump", "normal_map", "alpha"});
                 rec.ir = (float)r.num(m, "ir", where);
                 rec.fuzz = (float)r.num(m, "roughness", where);
                 const bool has_tint = m.find("tint") || m.find("tint_distance");
@@ -1446,6 +1527,7 @@ int scene_from_json(const char *text, size_t len, Scene &s, const char *base_dir
             s.mats.push_back(rec);
             if (r.ok && bump && !set_bump(s, (int)s.mats.size() - 1, bump_tex, bump_k, where)) r.ok = false;
             if (r.ok && nmap && !set_normal_map(s, (int)s.mats.size() - 1, nmap_tex, nmap_s, where)) r.ok = false;
+            if (r.ok && amask && !set_alpha(s, (int)s.mats.size() - 1, amask_tex, amask_c, where)) r.ok = false;
             if (r.ok && has_pbr_map && !set_pbr_map(s, (int)s.mats.size() - 1, pbr_map, where)) r.ok = false;  // (-1: no map)
         }
     }
@@ -1864,6 +1946,10 @@ std::string scene_to_json(const Scene &s) {
             o.pop_back();
             o += ", \"normal_map\": {\"texture\": " + std::to_string(b->texture) + ", \"scale\": " + json_float(b->scale) + "}}";
         }
+        if (const SceneAlpha *b = scene_alpha(s, (int)i)) {
+            o.pop_back();
+            o += ", \"alpha\": {\"texture\": " + std::to_string(b->texture) + ", \"cutoff\": " + json_float(b->cutoff) + "}}";
+        }
     }
     o += "\n  ]},\n";
 
@@ -1883,7 +1969,13 @@ std::string scene_to_json(const Scene &s) {
                 o += "{\"type\": \"image\", \"rows\": " + std::to_string(im.rows) + ", \"cols\": " + std::to_string(im.cols) +
                      ", \"data\": [";
                 for (size_t k = 0; k < im.rgb.size(); ++k) o += (k ? "," : "") + std::to_string((int)im.rgb[k]);
-                o += "]}";
+                o += "]";
+                if (!im.alpha.empty()) {
+                    o += ", \"alpha\": [";
+                    for (size_t k = 0; k < im.alpha.size(); ++k) o += (k ? "," : "") + std::to_string((int)im.alpha[k]);
+                    o += "]";
+                }
+                o += "}";
             }
         } else if (t.type == RT_TEX_NOISE) {
             const rt_noise &n = s.noise[i];

@@ -33,6 +33,7 @@ struct CylinderXform {
 struct SceneImage {
     int rows = 0, cols = 0;
     std::vector<uint8_t> rgb;
+    std::vector<uint8_t> alpha;  // rows x cols alpha bytes; empty: no plane, every texel is 255
     std::string file;  // where it was read from ("" = given inline), for serialisation
 };
 
@@ -60,6 +61,13 @@ struct SceneNormalMap {
     float scale = 0.0f;
 };
 
+// a material's alpha mask: the alpha byte of image texture `texture` at the hit's (u, v) against c8 =
+// alpha_cutoff_byte(cutoff) (rt_alpha.h); a8 < c8: the hit is transparent
+struct SceneAlpha {
+    int texture = -1;
+    float cutoff = 0.0f;
+};
+
 struct Scene {
     int width = 400, height = 225, spp = 100, max_depth = 50;
     float background[3] = {0, 0, 0};
@@ -83,6 +91,8 @@ struct Scene {
                                      // material table as the bumps are, at most as long as the last mapped material's id + 1
     std::vector<SceneNormalMap> normal_maps;  // normal_maps[m]: the normal map of material m, texture < 0: none; beside
                                      // the material table as the bumps are, at most as long as the last mapped material's id + 1
+    std::vector<SceneAlpha> alphas;  // alphas[m]: the alpha mask of material m, texture < 0: none; beside the material
+                                     // table as the bumps are, at most as long as the last masked material's id + 1
     std::shared_ptr<const SceneEnvironment> env;  // null: no environment (a miss gives the background / the sky)
     float env_scale = 1.0f, env_rotate = 0.0f;    // radiance = scale x texel; degrees about +y
     std::vector<rt_medium> media;  // homogeneous participating media, a list of its own: at most RT_MAX_MEDIA
@@ -134,10 +144,11 @@ int add_cylinder(Scene &s, float radius, float zmin, float zmax, int material, c
                  double degrees, const double *offset);
 
 // -> texture id / triangles added / prim id, or -rt_status
-int add_image_texture(Scene &s, int rows, int cols, const uint8_t *rgb, const std::string &file);
+// alpha: rows x cols alpha bytes, or null: the image has no alpha plane
+int add_image_texture(Scene &s, int rows, int cols, const uint8_t *rgb, const std::string &file, const uint8_t *alpha = nullptr);
 int add_image_texture_file(Scene &s, const char *path);
 // an 8-bit image file (PNG by signature, else PPM) -> RT_OK or an rt_status
-int read_image_file(const char *path, int &rows, int &cols, std::vector<uint8_t> &rgb);
+int read_image_file(const char *path, int &rows, int &cols, std::vector<uint8_t> &rgb, std::vector<uint8_t> *alpha = nullptr);
 
 // the environment map (scene.cpp).  set_environment: rows = 0 clears; file: what to_json writes in place of the texels ("" = inline)
 constexpr long long kEnvMaxTexels = 1LL << 25;
@@ -222,6 +233,19 @@ inline bool scene_has_normal_map(const Scene &s) {
     return false;
 }
 bool set_normal_map(Scene &s, int material, int texture, float scale, const char *where);
+
+// alpha masks: the mask of material m, or null; does any material carry one (such a scene runs the general kernels
+// over the wide tables: its texture is an image); set_alpha checks (false: the message is set, prefixed with `where`) and
+// stores -- texture -1 removes
+inline const SceneAlpha *scene_alpha(const Scene &s, int m) {
+    return (m >= 0 && (size_t)m < s.alphas.size() && s.alphas[(size_t)m].texture >= 0) ? &s.alphas[(size_t)m] : nullptr;
+}
+inline bool scene_has_alpha(const Scene &s) {
+    for (const SceneAlpha &b : s.alphas)
+        if (b.texture >= 0) return true;
+    return false;
+}
+bool set_alpha(Scene &s, int material, int texture, float cutoff, const char *where);
 
 // a medium (scene.cpp): checks the record and appends it -> medium id, or -rt_status
 int add_medium(Scene &s, const rt_medium &m);
