@@ -15,14 +15,11 @@ of their surface.  Each case's conditions (check_contents) are asserted from the
 """
 import numpy as np
 
-import ext_scenes as X
-import media_scenes as MS
-import motion_scenes as MO
+import feature_scenes as FS
 import nee_scenes as NS
 import ref64 as R
 
-NEE, ENV, MEDIA, MOTION = X.NEE, X.ENV, X.MEDIA, X.MOTION
-FAMILIES = NEE | ENV | MEDIA | MOTION
+NEE, ENV, MEDIA, MOTION, FAMILIES = FS.NEE, FS.ENV, FS.MEDIA, FS.MOTION, FS.FAMILIES
 MIN_MASKED_SHARE = 0.15   # of a case's samples meet a masked hit
 MIN_VERDICT_SHARE = 0.05  # of the masked hits are passes, and as many are opaque
 MIN_SHADOW_THROUGH = 500  # shadow queries through a hole, in the cases with light sampling
@@ -223,17 +220,12 @@ CASES = {
     "al_env": (ENV | NEE, env, True),
     "al_motion": (MOTION, motion, False),
 }
-# the deliberate mistakes (ref64_alpha.PERTURBATIONS), each on the case that exercises it
+# the deliberate mistakes (ref64.trace's al_* names), each on the case that exercises it
 MISTAKES = (("al_sky", "al_off"), ("al_sky", "al_inverted"), ("al_sky", "al_uv_swapped"), ("al_lights", "al_shadow_opaque"),
             ("al_layers", "al_counts_bounce"))
 
 
-def family(name):
-    return CASES[name][0]
-
-
-def seed_of(name):
-    return NS.REF_SEED if not family(name) & (MEDIA | MOTION) else MS.REF_SEED
+family, seed_of, inputs = FS.bindings(CASES.__getitem__)
 
 
 def scene(rtmi, name, masks=True):
@@ -243,38 +235,24 @@ def scene(rtmi, name, masks=True):
 
 
 def plain_twin(rtmi, name):
-    """the twin without masks, light sampling off and its environment, movers and analytic lights cleared: what the plain
+    """the twin without masks, made plain (feature_scenes.cleared): what the plain
     kernel renders"""
-    sc = CASES[name][1](rtmi, False)
-    sc.set_light_sampling(False)
-    sc.set_environment(None)
-    sc.clear_media()
-    sc.clear_moving_spheres()
-    sc.clear_analytic_lights()
-    return sc
-
-
-def inputs(rtmi, name):
-    """(uniforms, shutter times or None) of the case's 48 x 27 x 13 samples"""
-    words = R.uniforms(rtmi, seed_of(name), NS.REF_W, NS.REF_H, 0, NS.REF_K, NS.REF_DRAWS)
-    shutter = MO.shutter_times(rtmi, seed_of(name), NS.REF_W, NS.REF_H, 0, NS.REF_K) if family(name) == MOTION else None
-    return words, shutter
+    return FS.cleared(CASES[name][1](rtmi, False))
 
 
 def nested_tally(rtmi):
     """the reference's alpha tally of the nested clump (the reference scans the lists: the grid, nested or flat, is the
     kernels' business), on the case's 48 x 27 x 13 samples"""
-    import ref64_alpha as RA
     words = R.uniforms(rtmi, NS.REF_SEED, NS.REF_W, NS.REF_H, 0, NS.REF_K, NS.REF_DRAWS)
-    return RA.reference(RA.ref_scene(nested(rtmi)), words)[4]
+    return R.reference(R.RefScene(nested(rtmi)), words)[3]
 
 
 def check_contents(name, tally):
-    """the case's conditions, from the reference's tally (ref64_alpha.summary) alone"""
-    assert tally["masked_share"] >= MIN_MASKED_SHARE, (name, tally["masked_share"])
-    assert tally["pass_share"] >= MIN_VERDICT_SHARE, (name, tally["pass_share"])
-    assert tally["opaque_share"] >= MIN_VERDICT_SHARE, (name, tally["opaque_share"])
+    """the case's conditions, from the reference's tally (ref64.tally's alpha_* keys) alone"""
+    assert tally["alpha_masked_share"] >= MIN_MASKED_SHARE, (name, tally["alpha_masked_share"])
+    assert tally["alpha_pass_share"] >= MIN_VERDICT_SHARE, (name, tally["alpha_pass_share"])
+    assert tally["alpha_opaque_share"] >= MIN_VERDICT_SHARE, (name, tally["alpha_opaque_share"])
     if name == "al_layers":
-        assert tally["max_passes"] >= 2, (name, tally["max_passes"])
+        assert tally["alpha_max_passes"] >= 2, (name, tally["alpha_max_passes"])
     if name in ("al_lights", "al_env"):
-        assert tally["shadow_through"] >= MIN_SHADOW_THROUGH, (name, tally["shadow_through"])
+        assert tally["alpha_shadow_through"] >= MIN_SHADOW_THROUGH, (name, tally["alpha_shadow_through"])

@@ -13,15 +13,14 @@ beside area x luminance); the spots' cones cover part of the floor only, so that
 all occur; under the environment the map keeps scenes/env_sun.json's scale and the distant light's irradiance is set beside it."""
 import numpy as np
 
-import ext_scenes as X
+import feature_scenes as FS
 import glass_scenes as GLS
 import glossy_scenes as GS
 import nee_scenes as NS
 import ref64 as R
 import ref64_analytic_lights as RA
 
-NEE, ENV = X.NEE, X.ENV
-FAMILIES = GS.FAMILIES
+NEE, ENV, FAMILIES = FS.NEE, FS.ENV, FS.FAMILIES
 LIFT = NS.LIFT
 
 
@@ -152,8 +151,7 @@ def _entry(name):
     return CASES[name] if name in CASES else EXTRA[name]
 
 
-def family(name):
-    return _entry(name)[0]
+family, seed_of, inputs = FS.bindings(_entry)
 
 
 def scene(rtmi, name, **kw):
@@ -163,15 +161,8 @@ def scene(rtmi, name, **kw):
 
 
 def plain_twin(rtmi, name):
-    sc = _entry(name)[1](rtmi, False)
-    sc.set_light_sampling(False)
-    sc.set_environment(None)
-    return sc
-
-
-def inputs(rtmi):
-    """the uniforms of the cases' 48 x 27 x 13 samples"""
-    return R.uniforms(rtmi, NS.REF_SEED, NS.REF_W, NS.REF_H, 0, NS.REF_K, NS.REF_DRAWS)
+    """made plain, the point, spot and distant lights kept: without light sampling they light nothing"""
+    return FS.cleared(_entry(name)[1](rtmi, False), analytic_lights=False)
 
 
 def check_contents(name, tally):

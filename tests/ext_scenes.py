@@ -11,8 +11,8 @@ import media_scenes as MS
 import motion_scenes as MO
 import nee_scenes as NS
 import ref64 as R
+from feature_scenes import NEE, ENV, MEDIA, MOTION  # (the family bits of rt_stats.kernel_variant)
 
-NEE, ENV, MEDIA, MOTION = 256, 1024, MS.MEDIA, MO.MOTION
 MIN_IMAGE_SHARE = 0.20  # of a case's samples read an image texel at some vertex
 
 

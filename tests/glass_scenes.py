@@ -13,16 +13,14 @@ import functools
 
 import numpy as np
 
-import ext_scenes as X
+import feature_scenes as FS
 import media_scenes as MS
-import motion_scenes as MO
 import nee_scenes as NS
 import ref64 as R
 import ref64_glass as GL
 import ref64_glossy as G
 
-NEE, ENV, MEDIA, MOTION = X.NEE, X.ENV, X.MEDIA, X.MOTION
-FAMILIES = NEE | ENV | MEDIA | MOTION
+NEE, ENV, MEDIA, MOTION, FAMILIES = FS.NEE, FS.ENV, FS.MEDIA, FS.MOTION, FS.FAMILIES
 LIFT = NS.LIFT
 SMOOTH_R = 0.02
 TINT = (0.9, 0.35, 0.15)  # an absorption coefficient per unit length
@@ -160,12 +158,7 @@ MISTAKES = (("glass_sky", "fresnel_draw_last"), ("glass_sky", "g1_for_g2"), ("gl
             ("glass_sky", "no_absorption"), ("glass_lights", "refraction_mis_weighted"))
 
 
-def family(name):
-    return CASES[name][0]
-
-
-def seed_of(name):
-    return NS.REF_SEED if not family(name) & (MEDIA | MOTION) else MS.REF_SEED
+family, seed_of, inputs = FS.bindings(CASES.__getitem__)
 
 
 def scene(rtmi, name, glass=True):
@@ -175,20 +168,8 @@ def scene(rtmi, name, glass=True):
 
 
 def plain_twin(rtmi, name):
-    """the dielectric twin with light sampling off and its environment, media and movers cleared: what the plain kernel renders"""
-    sc = CASES[name][1](rtmi, False)
-    sc.set_light_sampling(False)
-    sc.set_environment(None)
-    sc.clear_media()
-    sc.clear_moving_spheres()
-    return sc
-
-
-def inputs(rtmi, name):
-    """(uniforms, shutter times or None) of the case's 48 x 27 x 13 samples"""
-    words = R.uniforms(rtmi, seed_of(name), NS.REF_W, NS.REF_H, 0, NS.REF_K, NS.REF_DRAWS)
-    shutter = MO.shutter_times(rtmi, seed_of(name), NS.REF_W, NS.REF_H, 0, NS.REF_K) if family(name) == MOTION else None
-    return words, shutter
+    """the dielectric twin made plain (feature_scenes.cleared): what the plain kernel renders"""
+    return FS.cleared(CASES[name][1](rtmi, False))
 
 
 def check_contents(name, tally):

@@ -28,13 +28,12 @@ import os
 import numpy as np
 
 import ext_scenes as X
+import feature_scenes as FS
 import glossy_scenes as GS
 import nee_scenes as NS
-import ref64 as R
 import smooth_scenes as SM
 
-NEE, ENV = X.NEE, X.ENV
-FAMILIES = GS.FAMILIES
+NEE, ENV, FAMILIES = FS.NEE, FS.ENV, FS.FAMILIES
 LIFT = NS.LIFT
 SHIPPED_BEFORE = ("env_sun.json", "fog_room.json", "glossy_balls.json", "mixed_emissive.json", "motion_balls.json", "smooth_mesh.json",
                   "three_sphere.json")
@@ -141,8 +140,7 @@ PINNED = {
 }
 
 
-def family(name):
-    return CASES[name][0]
+family, seed_of, inputs = FS.bindings(CASES.__getitem__)
 
 
 def scene(rtmi, name, mesh_lights=True, **kw):
@@ -153,15 +151,7 @@ def scene(rtmi, name, mesh_lights=True, **kw):
 
 
 def plain_twin(rtmi, name):
-    sc = CASES[name][1](rtmi, False)
-    sc.set_light_sampling(False)
-    sc.set_environment(None)
-    return sc
-
-
-def inputs(rtmi):
-    """the uniforms of the cases' 48 x 27 x 13 samples (one seed: every case is a light-sampling case)"""
-    return R.uniforms(rtmi, NS.REF_SEED, NS.REF_W, NS.REF_H, 0, NS.REF_K, NS.REF_DRAWS)
+    return FS.cleared(CASES[name][1](rtmi, False))
 
 
 def check_contents(name, tally):

@@ -27,16 +27,13 @@ import functools
 
 import numpy as np
 
-import ext_scenes as X
+import feature_scenes as FS
 import media_scenes as MS
-import motion_scenes as MO
 import nee_scenes as NS
-import ref64 as R
 import ref64_noise as N
 import smooth_scenes as SM
 
-NEE, ENV, MEDIA, MOTION = X.NEE, X.ENV, X.MEDIA, X.MOTION
-FAMILIES = NEE | ENV | MEDIA | MOTION
+NEE, ENV, MEDIA, MOTION, FAMILIES = FS.NEE, FS.ENV, FS.MEDIA, FS.MOTION, FS.FAMILIES
 MIN_NOISE_SHARE = 0.15  # of a case's samples touch a noise texture: a mistake can then pull the agreement below 97 %
 
 
@@ -165,12 +162,7 @@ CASES = {
 NESTED_LAYOUT = 52
 
 
-def family(name):
-    return CASES[name][0]
-
-
-def seed_of(name):
-    return NS.REF_SEED if not family(name) & (MEDIA | MOTION) else MS.REF_SEED
+family, seed_of, inputs = FS.bindings(CASES.__getitem__)
 
 
 def scene(rtmi, name, noise=True):
@@ -180,20 +172,8 @@ def scene(rtmi, name, noise=True):
 
 
 def plain_twin(rtmi, name):
-    """the solid-colour twin with light sampling off and its environment, media and movers cleared: what the plain kernel renders"""
-    sc = CASES[name][1](rtmi, False)
-    sc.set_light_sampling(False)
-    sc.set_environment(None)
-    sc.clear_media()
-    sc.clear_moving_spheres()
-    return sc
-
-
-def inputs(rtmi, name):
-    """(uniforms, shutter times or None) of the case's 48 x 27 x 13 samples"""
-    words = R.uniforms(rtmi, seed_of(name), NS.REF_W, NS.REF_H, 0, NS.REF_K, NS.REF_DRAWS)
-    shutter = MO.shutter_times(rtmi, seed_of(name), NS.REF_W, NS.REF_H, 0, NS.REF_K) if family(name) == MOTION else None
-    return words, shutter
+    """the solid-colour twin made plain (feature_scenes.cleared): what the plain kernel renders"""
+    return FS.cleared(CASES[name][1](rtmi, False))
 
 
 def check_contents(name, tally):

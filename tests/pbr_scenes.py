@@ -13,14 +13,12 @@ once took that decision per material); colours, roughnesses and metalnesses of t
 decision is each hit's: the last case holds one material whose checker map carries r8 across the threshold."""
 import numpy as np
 
-import ext_scenes as X
+import feature_scenes as FS
 import glass_scenes as GLS
 import nee_scenes as NS
-import ref64 as R
 import ref64_pbr as RP
 
-NEE, ENV, MEDIA, MOTION = X.NEE, X.ENV, X.MEDIA, X.MOTION
-FAMILIES = NEE | ENV | MEDIA | MOTION
+NEE, ENV, MEDIA, MOTION, FAMILIES = FS.NEE, FS.ENV, FS.MEDIA, FS.MOTION, FS.FAMILIES
 LIFT = NS.LIFT
 SMOOTH = (0.02, 0.03)  # roughness factors below the threshold (r8 = 5, 8)
 
@@ -180,8 +178,7 @@ def _entry(name):
     return CASES[name] if name in CASES else EXTRA[name]
 
 
-def family(name):
-    return _entry(name)[0]
+family, seed_of, inputs = FS.bindings(_entry)
 
 
 def scene(rtmi, name, **kw):
@@ -191,15 +188,7 @@ def scene(rtmi, name, **kw):
 
 
 def plain_twin(rtmi, name):
-    sc = _entry(name)[1](rtmi, False)
-    sc.set_light_sampling(False)
-    sc.set_environment(None)
-    return sc
-
-
-def inputs(rtmi):
-    """the uniforms of the cases' 48 x 27 x 13 samples"""
-    return R.uniforms(rtmi, NS.REF_SEED, NS.REF_W, NS.REF_H, 0, NS.REF_K, NS.REF_DRAWS)
+    return FS.cleared(_entry(name)[1](rtmi, False))
 
 
 def check_contents(name, tally):

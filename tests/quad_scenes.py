@@ -20,13 +20,12 @@ reference alone meets criterion (a) with at most 1 % of the samples flipping a b
 import numpy as np
 
 import ext_scenes as X
+import feature_scenes as FS
 import media_scenes as MS
-import motion_scenes as MO
 import nee_scenes as NS
 import ref64 as R
 
-NEE, ENV, MEDIA, MOTION = X.NEE, X.ENV, X.MEDIA, X.MOTION
-FAMILIES = NEE | ENV | MEDIA | MOTION
+NEE, ENV, MEDIA, MOTION, FAMILIES = FS.NEE, FS.ENV, FS.MEDIA, FS.MOTION, FS.FAMILIES
 LIFT = NS.LIFT
 BOX_GAP = 0.013
 # The ground sphere of the sky case.  The fp32 sphere test's error grows with |o - c|^2: under the series' radius of 1000 a
@@ -214,12 +213,7 @@ CORNELL = "quad_cornell"
 MISTAKES = (("quad_textured", "quad_uv_swapped"), (CORNELL, "quad_light_half_area"), ("quad_sky", "quad_front_flipped"))
 
 
-def family(name):
-    return CASES[name][0]
-
-
-def seed_of(name):
-    return NS.REF_SEED if not family(name) & (MEDIA | MOTION) else MS.REF_SEED
+family, seed_of, inputs = FS.bindings(CASES.__getitem__)
 
 
 def scene(rtmi, name, tri=False):
@@ -229,19 +223,8 @@ def scene(rtmi, name, tri=False):
 
 
 def plain_twin(rtmi, name):
-    sc = CASES[name][1](rtmi, True)
-    sc.set_light_sampling(False)
-    sc.set_environment(None)
-    sc.clear_media()
-    sc.clear_moving_spheres()
-    return sc
-
-
-def inputs(rtmi, name):
-    """(uniforms, shutter times or None) of the case's 48 x 27 x 13 samples"""
-    words = R.uniforms(rtmi, seed_of(name), NS.REF_W, NS.REF_H, 0, NS.REF_K, NS.REF_DRAWS)
-    shutter = MO.shutter_times(rtmi, seed_of(name), NS.REF_W, NS.REF_H, 0, NS.REF_K) if family(name) == MOTION else None
-    return words, shutter
+    """the two-triangle twin, made plain (feature_scenes.cleared): what the plain kernel renders"""
+    return FS.cleared(CASES[name][1](rtmi, True))
 
 
 def check_contents(name, tally_):

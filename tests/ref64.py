@@ -1,7 +1,7 @@
 """An independent statement of the path estimators of DESIGN 7a (light sampling + MIS), 7e (environment maps), 7f (homogeneous
 participating media with isotropic scattering), 7g (motion blur: linearly moving spheres over a per-sample shutter time), 7l
 (smooth shading), 7m (the glossy materials) and 7n-7u (triangle lights, noise textures, bumps, quads, rough glass, point / spot /
-distant lights, the metallic-roughness material, normal maps), in NumPy, vectorised over a batch of samples, at a floating type
+distant lights, the metallic-roughness material, normal maps) and 7v (alpha cutouts), in NumPy, vectorised over a batch of samples, at a floating type
 of the caller's choice (float64: the reference; float32: the same formulas at the kernel's precision, used to measure how many
 samples sit on a branch).
 
@@ -12,7 +12,7 @@ shares no code with the kernels or with oracle/.
 
 There is ONE integrator loop, trace(), one hit record, hit_record(), one texture lookup, texture_value(), and one light sample,
 sample_light().  An extension joins them with records on RefScene, read ONCE from the product scene (lights, media, movers,
-noise parameters, bumps, normal maps, pbr maps, analytic lights: each empty unless the scene has them) or records the scene's
+noise parameters, bumps, normal maps, pbr maps, analytic lights, alpha masks: each empty unless the scene has them) or records the scene's
 tables already hold (a triangle's vertex normals, a primitive's or a material's type), a branch in those functions or a block
 in the loop, columns or event codes in the signature, counters in trace()'s `log` for what the signature has no column for,
 and keys in tally(); its deliberate mistakes are names in trace()'s one `perturb`.  A model large enough for a file of its own
@@ -24,13 +24,14 @@ is imported HERE, holds no loop and imports nothing of this file (ref64_base.py 
     ref64_analytic_lights   7s  the light records, the three lights' samples
     ref64_pbr               7t  the bytes of a hit, the choice between metal and plastic
     ref64_normal_map        7u  the texel's decoding, every primitive's tangents, the frame and the rule
-(triangle lights, 7n, and quads, 7q, are short enough to stand here).  No module restates trace(), and none swaps a function of
+(triangle lights, 7n, quads, 7q, and alpha cutouts, 7v -- opaque_hit(), the query trace() makes -- are short enough to stand
+here).  No module restates trace(), and none swaps a function of
 this one.  The reference evaluates the scene it is given: which combinations the product renders is the product's to refuse and
 test_refusals' to assert.  Where two extensions meet and DESIGN defines no order -- a light sample at a medium vertex, a shadow
 ray through a medium or past a mover -- trace() raises NotImplementedError.
 
 Inputs are the product's exported tables (Scene.prims / materials / textures / lights / media / moving_spheres / get_camera /
-info / environment / noise / bump / normal_map / pbr_map / analytic_lights), the light alias table and the environment's CDF
+info / environment / noise / bump / normal_map / pbr_map / analytic_lights / alpha / get_image_alpha), the light alias table and the environment's CDF
 tables as the packed image stores them (table_image, found by content), the uniforms of rtmi.sample_stream and, for movers, the
 shutter times of rtmi.shutter_time (one per sample: the time is no draw of the stream) and the pixels of the image textures
 (Scene.get_image).  Out of scope: the nested grid (a candidate search, which this reference has none of: it scans the lists).
@@ -61,13 +62,15 @@ ENVIRONMENT = 100
 POINT, SPOT, DISTANT = AL.POINT, AL.SPOT, AL.DISTANT
 DELTA_LIGHTS = (POINT, SPOT, DISTANT)
 # the counters of trace()'s `log`: what the signature has no column for.  bump_* / nm_*: perturbed vertices in all, on back faces,
-# (nm) whose texel tilts, and where a guard kept n (nm: the texel tilts and the frame was built)
+# (nm) whose texel tilts, and where a guard kept n (nm: the texel tilts and the frame was built).  alpha_*: opaque_hit()'s counters
+ALPHA_COUNTERS = ("masked_hits", "passes", "opaque", "max_passes", "shadow_through", "shadow_queries", "path_queries")
 LOG_KEYS = (("bump_bumped", "bump_back", "bump_kept", "nm_mapped", "nm_back", "nm_tilting", "nm_kept", "quad_back_hits")
-            + GL.LOG_KEYS + AL.LOG_KEYS + PB.LOG_KEYS)
+            + GL.LOG_KEYS + AL.LOG_KEYS + PB.LOG_KEYS + tuple("alpha_" + k for k in ALPHA_COUNTERS))
 
 
 def new_log():
-    return dict.fromkeys(LOG_KEYS, 0)
+    """the counters at 0 and alpha_masked_samples, the set of the samples that met a masked hit"""
+    return dict(dict.fromkeys(LOG_KEYS, 0), alpha_masked_samples=set())
 MEDIUM_SPHERE, MEDIUM_BOX = 0, 1
 T_MIN = 0.001           # hittable_list::hit's t_min of every query
 SHADOW_T_MAX = 0.999    # a shadow ray ends just short of its light point (DESIGN 7a)
@@ -182,12 +185,14 @@ class RefScene:
         self.media = sc.media() if media else sc.media()[:0]
         # the extensions' records, each empty unless the scene has them.  noise: texture -> the dict of Scene.noise; bumps:
         # material -> (the height field's noise parameters, strength); normal_maps: material -> (image texture, scale); pbr_maps:
-        # pbr material -> its metallic-roughness map's texture or -1; analytic: index into lights -> ref64_analytic_lights.record
+        # pbr material -> its metallic-roughness map's texture or -1; analytic: index into lights -> ref64_analytic_lights.record;
+        # alpha_masks: material -> (the mask's alpha plane [rows][cols] uint8, c8)
         materials = range(len(self.mats))
         self.noise = {ti: sc.noise(ti) for ti, t in enumerate(self.texs) if t["type"] == NOISE}
         self.bumps = {m: (self.noise[int(b[0])], np.float32(b[1])) for m in materials for b in [sc.bump(m)] if b is not None}
         self.normal_maps = {m: (int(b[0]), np.float32(b[1])) for m in materials for b in [sc.normal_map(m)] if b is not None}
         self.pbr_maps = {m: -1 if mp is None else int(mp) for m in materials if self.mats["type"][m] == PBR for mp in [sc.pbr_map(m)]}
+        self.alpha_masks = {m: (sc.get_image_alpha(int(a[0])), cutoff_byte(a[1])) for m in materials for a in [sc.alpha(m)] if a is not None}
         self.analytic = {}
         at = [i for i, l in enumerate(self.lights) if l["shape"] in DELTA_LIGHTS]
         if at:  # (a light whose weight is not positive and finite is in neither list)
@@ -562,6 +567,81 @@ def metal_pdf(w, r, f, T):
     return np.where((disc >= 0) & (t1 > 0), pdf, 0).astype(T)
 
 
+# ---------------------------------------------------------------------------------------------------------------- alpha cutouts
+CAP = 64  # one query passes through at most this many transparent hits
+
+
+def cutoff_byte(cutoff):
+    """c8 = clamp(ceil(255 cutoff), 1, 255), in fp64"""
+    return int(min(max(np.ceil(255.0 * np.float64(cutoff)), 1.0), 255.0))
+
+
+def opaque_hit(S, o, d, t_max, T, perturb=(), log=None, samples=None, depth=None, on_pass=None):
+    """DESIGN 7v, from the model's text in include/rtmi.h: the closest hit that is no hole, as (total t from o, the opaque winner
+    or -1); a scalar t_max is a path query, an array of far ends a shadow query.  A material's mask is read at the hit record's
+    (u, v) with image_texel's nearest texel; with a8 the alpha byte there the hit is transparent iff a8 < c8.  A transparent hit is
+    no vertex: the query goes on from o + t d in the same direction with the usual t_min and t_max - t left of its range, and
+    nothing else happens.  One query passes through at most CAP transparent hits: the next masked hit counts as opaque whatever
+    its texel says.  Without masks this is closest_hit()'s result as it stands.
+    log: counts into its alpha_* keys; samples: the rays' sample indices (for the log); depth: trace()'s counters, for
+    "al_counts_bounce"; on_pass(samples or None, points, directions): called with the hole points of every round of passes"""
+    shadow = not np.isscalar(t_max)
+    masks = {} if "al_off" in perturb or (shadow and "al_shadow_opaque" in perturb) else S.alpha_masks
+    n = len(o)
+    if log is not None:
+        log["alpha_shadow_queries" if shadow else "alpha_path_queries"] += n
+    if not masks:
+        return closest_hit(S, o, d, t_max, T)
+    left = np.asarray(t_max).astype(T).copy() if shadow else np.full(n, t_max, T)
+    at = np.array(o, T, copy=True)
+    total = np.zeros(n, T)
+    passes = np.zeros(n, np.int64)
+    out_t = left.copy()
+    out_idx = np.full(n, -1, np.int64)
+    todo = np.arange(n)
+    material = S.prims["material"]
+    while len(todo):
+        t, idx = closest_hit(S, at[todo], d[todo], left[todo], T)
+        through = np.zeros(len(todo), bool)
+        mat = np.where(idx >= 0, material[np.clip(idx, 0, None)], -1)
+        for m, (plane, c8) in masks.items():
+            k = np.flatnonzero(mat == m)
+            if len(k) == 0:
+                continue
+            u, v = hit_uv(S, at[todo[k]], d[todo[k]], t[k], idx[k], T)
+            if "al_uv_swapped" in perturb:
+                u, v = v, u
+            row, col = image_texel(plane, u, v, T)
+            a8 = plane[row, col].astype(np.int64)
+            clear = (a8 >= c8) if "al_inverted" in perturb else (a8 < c8)
+            clear &= passes[todo[k]] < CAP  # the 65th masked hit of a query is opaque whatever its texel says
+            through[k] = clear
+            if log is not None:
+                log["alpha_masked_hits"] += len(k)
+                log["alpha_passes"] += int(clear.sum())
+                log["alpha_opaque"] += int((~clear).sum())
+                if samples is not None:
+                    log["alpha_masked_samples"].update(samples[todo[k]].tolist())
+        done = todo[~through]
+        out_t[done] = total[done] + t[~through]
+        out_idx[done] = idx[~through]
+        go = todo[through]
+        at[go] = at[go] + t[through][:, None] * d[go]
+        total[go] += t[through]
+        left[go] -= t[through]
+        passes[go] += 1
+        if on_pass is not None and len(go):
+            on_pass(None if samples is None else samples[go], at[go], d[go])
+        todo = go
+    if log is not None:
+        log["alpha_max_passes"] = max(log["alpha_max_passes"], int(passes.max()) if n else 0)
+        if shadow:
+            log["alpha_shadow_through"] += int((passes > 0).sum())
+    if depth is not None and "al_counts_bounce" in perturb and not shadow and samples is not None:
+        depth[samples] -= passes
+    return out_t, out_idx
+
+
 # ---------------------------------------------------------------------------------------------------------------- environment
 def env_texel(E, d, T):
     rows, cols = E["tex"].shape[:2]
@@ -765,14 +845,15 @@ class _Draws:
         return out
 
 
-def trace(S, words, first_pixel=0, dtype=np.float64, perturb=(), shutter=None, probe=None, log=None):
+def trace(S, words, first_pixel=0, dtype=np.float64, perturb=(), shutter=None, probe=None, log=None, on_pass=None):
     """One sample per row of `words` (the sample's stream as uint32 words), pixel ids first_pixel, first_pixel + 1, ... modulo the
     frame; `shutter`: the samples' shutter times, required where the scene has movers.  Returns (rgb [N][3], signature [N][*]
     int64, draws consumed [N]).  probe: a dict that receives the FIRST vertex of every sample (what a feature pass shows):
     "glossy" (bool: it lies on a glossy material, rough glass and pbr among them), "albedo" (F0 or rho there; pbr: the base colour
     c8 / 255), "normal" (the shading normal), "texture_value" (the colour an emitter, a lambertian or a plastic read from its
-    texture: zeros elsewhere).  log: a dict of new_log() that counts what the signature has no column for
-    (LOG_KEYS).
+    texture: zeros elsewhere), "first_t" / "first_idx" (the first path query's total t and its opaque winner; NaN / -1 where the
+    sample made no query).  log: a dict of new_log() that counts what the signature has no column for (LOG_KEYS).  on_pass:
+    handed to opaque_hit(), in an fp64 run alone.
     perturb names deliberate mistakes, for the tests that show the comparison can fail.  Every name, in one place (the model
     files' docstrings say what each of theirs does):
       ref64_noise.PERTURBATIONS, ref64_bump.PERTURBATIONS, ref64_normal_map.PERTURBATIONS, ref64_glass.PERTURBATIONS
@@ -791,7 +872,10 @@ def trace(S, words, first_pixel=0, dtype=np.float64, perturb=(), shutter=None, p
       "lobe_draw_last": plastic's lobe draw taken after u1, u2 instead of in front of them;
       "nee_albedo_pdf": a glossy vertex's light sample with f cos taken as albedo x pdf_b, the shortcut that holds for
       lambertian and metal;
-      "delta_power_heuristic": the power heuristic applied to the sample of a point, spot or distant light."""
+      "delta_power_heuristic": the power heuristic applied to the sample of a point, spot or distant light;
+      "al_off": masks ignored;  "al_inverted": a masked hit is transparent iff a8 >= c8;  "al_uv_swapped": the mask read with
+      the row from v and the column from u;  "al_shadow_opaque": shadow rays do not pass;  "al_counts_bounce": a pass uses up
+      a bounce."""
     T = dtype
     N = len(words)
     log = new_log() if log is None else log
@@ -834,7 +918,10 @@ def trace(S, words, first_pixel=0, dtype=np.float64, perturb=(), shutter=None, p
     while alive.any():
         who = np.flatnonzero(alive)
         oo, dd = o[who], d[who]
-        t_hit, idx = closest_hit(S, oo, dd, np.inf, T)
+        t_hit, idx = opaque_hit(S, oo, dd, np.inf, T, perturb, log, who, depth, on_pass if T is np.float64 else None)
+        if probe is not None and len(sig) == 1:
+            probe.update(first_t=np.full(N, np.nan), first_idx=np.full(N, -1, np.int64))
+            probe["first_t"][who], probe["first_idx"][who] = t_hit, idx
         sig.append(np.full((N, VERTEX_COLUMNS), NONE, np.int64))
         note(C_PRIM, who, idx)
         # ---- the movers (7g), in list order, behind every static primitive: accepted while t_min <= t <= the closest so far
@@ -1186,7 +1273,7 @@ def trace(S, words, first_pixel=0, dtype=np.float64, perturb=(), shutter=None, p
             k = np.flatnonzero(usable)
             is_env = S.lights["shape"][pick[k]] == ENVIRONMENT
             far = np.where(is_env, T(np.inf), T(SHADOW_T_MAX))
-            _, blocker = closest_hit(S, p[ls][k], ld[k], far, T)
+            _, blocker = opaque_hit(S, p[ls][k], ld[k], far, T, perturb, log, m[k])
             verdict[k] = np.where(blocker >= 0, SHADOW_OCCLUDED, SHADOW_CLEAR)
             note(C_BLOCKER, m[k], np.where(blocker >= 0, blocker, NONE))
             clear = k[blocker < 0]
@@ -1223,7 +1310,8 @@ def tally(sig, S=None, log=None):
     an image texture, vertices on triangles, those that took a light sample, and shadow rays stopped by either kind.  Of 7m
     (ref64_glossy.GLOSSY_KEYS and more): what ref64_glossy.glossy_tally() counts (by the material's roughness: a pbr vertex's is
     its hit's, which the log counts as pbr_smooth_vertices).  Of 7n-7u, with S: _extension_tally()'s counts.  With the `log` that
-    trace() filled: its counters (LOG_KEYS), which hold what the signature has no column for."""
+    trace() filled: its counters (LOG_KEYS), which hold what the signature has no column for, and of 7v the shares the alpha cases
+    assert (alpha_masked_share, alpha_pass_share, alpha_opaque_share)."""
     v = sig[:, SAMPLE_COLUMNS:].reshape(len(sig), -1, VERTEX_COLUMNS)
     event, light, shadow, how, alias, mover = (v[:, :, c] for c in (C_EVENT, C_LIGHT, C_SHADOW, C_HIT_WEIGHT, C_ALIAS, C_MOVER))
     prim, blocker = v[:, :, C_PRIM], v[:, :, C_BLOCKER]
@@ -1253,6 +1341,10 @@ def tally(sig, S=None, log=None):
                                       full_weight_emitter=(event == EV_EMIT) & (how == HIT_UNSAMPLED),
                                       missed_to_texel=v[:, :, C_MISS_TEXEL] != NONE, lost=v[:, :, C_ROULETTE] == 1), S)
     ext = _extension_tally(v, S) if S is not None else {}
+    if log:  # alpha cutouts: the shares of samples that met a masked hit, and of masked hits that passed / were opaque
+        hits = max(log["alpha_masked_hits"], 1)
+        log = dict(log, alpha_masked_samples=len(log["alpha_masked_samples"]), alpha_masked_share=len(log["alpha_masked_samples"]) / max(len(sig), 1),
+                   alpha_pass_share=log["alpha_passes"] / hits, alpha_opaque_share=log["alpha_opaque"] / hits)
     return dict(glossy, **ext, **(log or {}),
                 inside_no_sample=int((shadow == SHADOW_INSIDE).sum()), inside_full_weight_hits=int((how == HIT_FROM_INSIDE).sum()),
                 absorbed_metal_light_samples=int(((event == EV_METAL_ABSORBED) & (light != NONE)).sum()),

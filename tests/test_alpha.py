@@ -4,12 +4,13 @@
      set and removed pack to the same bytes; a plane lands in the texel words' top byte as 255 - a8; the mask records;
   3. the cutoff byte: 0.5 -> 128, 1 -> 255, 1e-9 -> 1; a texel of 127 is a hole against 128 and one of 128 is not;
   4. the interface -- Python, C, C++ (tests/alpha_host_driver.cpp), JSON -- with every refusal and the round trip;
-  5. the fp64 statement (ref64_alpha.py): all-opaque masks give ref64's own samples, all-transparent masks the samples of the
+  5. the fp64 statement (ref64.opaque_hit): all-opaque masks give ref64's own samples, all-transparent masks the samples of the
      scene without those primitives, the tally counts as stated, the 65th masked hit of a query is opaque, and every case of
-     alpha_scenes.py holds the contents it is there for;
+     alpha_scenes.py holds the contents it is there for; two cases trace as pinned before the statement moved into ref64.py;
   6. a stand-alone program over the PNG reader and the packer with masked scenes under -fsanitize=address,undefined.
 test_gpu_alpha.py holds the kernels to that reference."""
 import ctypes
+import hashlib
 import json
 import os
 import struct
@@ -22,7 +23,6 @@ import pytest
 import alpha_scenes as AS
 import nee_scenes as NS
 import ref64 as R
-import ref64_alpha as RA
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "ray-tracing-in-cuda_amd")
@@ -170,8 +170,8 @@ def test_the_packed_mask_records(rtmi):
 
 # ------------------------------------------------------------------------------------------------------------ 3. the cutoff byte
 def test_the_cutoff_byte(rtmi):
-    assert RA.cutoff_byte(0.5) == 128 and RA.cutoff_byte(1.0) == 255 and RA.cutoff_byte(1e-9) == 1
-    assert RA.cutoff_byte(np.float32(0.5)) == 128 and RA.cutoff_byte(128 / 255) in (128, 129) and RA.cutoff_byte(0.999) == 255
+    assert R.cutoff_byte(0.5) == 128 and R.cutoff_byte(1.0) == 255 and R.cutoff_byte(1e-9) == 1
+    assert R.cutoff_byte(np.float32(0.5)) == 128 and R.cutoff_byte(128 / 255) in (128, 129) and R.cutoff_byte(0.999) == 255
     # the packer's byte (csrc/rt_alpha.h) through the packed record, and the verdict through the reference's closest hit
     for cutoff, c8 in ((0.5, 128), (1.0, 255), (1e-9, 1), (0.25, 64), (0.7, 179)):
         sc = rtmi.Scene.new(8, 8, 1, 2)
@@ -181,11 +181,11 @@ def test_the_cutoff_byte(rtmi):
         sc.xy_rect(-1, 1, -1, 1, 0.0, m)  # (u from x, v from y: the column from y)
         bits = sc.table_image().reshape(-1).view(np.int32)
         assert any(tuple(bits[k:k + 4][1:]) == (1, 2, c8) for k in range(0, bits.size, 4)), (cutoff, c8)
-        S = RA.ref_scene(sc)
+        S = R.RefScene(sc)
         assert S.alpha_masks[m][1] == c8
         o = np.array([[0.0, -0.5, 3.0], [0.0, 0.5, 3.0]])
         d = np.array([[0.0, 0.0, -1.0], [0.0, 0.0, -1.0]])
-        _, idx = RA.closest_hit(S, o, d, np.inf, np.float64)
+        _, idx = R.opaque_hit(S, o, d, np.inf, np.float64)
         assert idx.tolist() == [-1, 0], (cutoff, idx)  # (a8 = c8 - 1 is a hole, a8 = c8 is not)
 
 
@@ -352,11 +352,11 @@ def words(rtmi):
 @pytest.mark.parametrize("name", ["al_sky", "al_lights"])
 def test_opaque_masks_give_the_plain_references_samples(rtmi, words, name):
     sc = AS.scene(rtmi, name, masks="opaque")
-    tally = RA.new_tally(len(words))
-    a, sa, da = RA.trace(RA.ref_scene(sc), words, tally=tally)
+    log = R.new_log()
+    a, sa, da = R.trace(R.RefScene(sc), words, log=log)
     b, sb, db = R.trace(R.RefScene(AS.scene(rtmi, name, masks=False)), words)
     assert np.array_equal(a, b) and np.array_equal(sa, sb) and np.array_equal(da, db)
-    assert tally["masked_hits"] > 1000 and tally["passes"] == 0 and tally["opaque"] == tally["masked_hits"] and tally["max_passes"] == 0
+    assert log["alpha_masked_hits"] > 1000 and log["alpha_passes"] == 0 and log["alpha_opaque"] == log["alpha_masked_hits"] and log["alpha_max_passes"] == 0
 
 
 @pytest.mark.parametrize("name", ["al_sky", "al_layers", "al_lights"])
@@ -368,18 +368,17 @@ def test_clear_masks_give_the_samples_of_the_scene_without_those_primitives(rtmi
     types = {int(p["type"]) for p in clear.prims() if clear.alpha(int(p["material"])) is not None}
     if name == "al_sky":
         assert len(types) >= 4, types  # sphere, rectangle, cylinder, quad (al_layers adds the triangles)
-    tally = RA.new_tally(len(words))
+    log = R.new_log()
     G = R.RefScene(gone)
-    plain = R.closest_hit  # (ref64's own: while RA.trace runs, the name holds the alpha-aware one)
     near = np.zeros(len(words), bool)  # samples one of whose holes has a surface of the remaining scene within t_min behind it
 
     def on_pass(samples, at, d):
         # a ray from t_min in FRONT of the hole, over 2 t_min: what it meets lies within t_min behind the hole (with a margin
         # of a thousandth of t_min for the two roundings)
         tm = R.T_MIN
-        _, idx = plain(G, at - tm * d, d, 2.001 * tm, np.float64)
+        _, idx = R.closest_hit(G, at - tm * d, d, 2.001 * tm, np.float64)
         near[samples[idx >= 0]] = True
-    a, _, da = RA.trace(RA.ref_scene(clear), words, tally=tally, on_pass=on_pass)
+    a, _, da = R.trace(R.RefScene(clear), words, log=log, on_pass=on_pass)
     b, _, db = R.trace(G, words)
     same = np.abs(a - b).max(axis=1) <= 1e-9 * np.maximum(1.0, np.abs(b).max(axis=1))
     print(f"\n{name}: {(~same).sum()} of {len(same)} samples differ, {near.sum()} have a surface within t_min behind a hole")
@@ -387,70 +386,91 @@ def test_clear_masks_give_the_samples_of_the_scene_without_those_primitives(rtmi
     # sphere, met at a grazing angle).  Every sample that differs is such a sample; every other one agrees, draws included
     assert not (~same & ~near).any(), np.flatnonzero(~same & ~near)
     assert np.array_equal(da[same], db[same]) and (~same).sum() <= 3
-    assert tally["passes"] == tally["masked_hits"] > 1000 and tally["opaque"] == 0
+    assert log["alpha_passes"] == log["alpha_masked_hits"] > 1000 and log["alpha_opaque"] == 0
 
 
 def test_the_tally_and_the_cap(rtmi):
     """70 stacked all-transparent quads in front of a wall: the head-on query passes 64 and the 65th hit is opaque"""
     sc = AS.stack(rtmi)
-    S = RA.ref_scene(sc)
+    S = R.RefScene(sc)
     o, d = np.array([[0.0, 0.0, 10.0], [0.0, 0.0, 10.0], [30.0, 0.0, 10.0]]), np.array([[0.0, 0.0, -1.0], [0.0, 0.0, -20.0], [0.0, 0.0, -1.0]])
-    tally = RA.new_tally(3)
-    t, idx = RA.closest_hit(S, o, d, np.inf, np.float64, tally=tally, samples=np.arange(3))
-    quad65 = 1 + RA.CAP  # (the wall is primitive 0, the quads follow)
+    log = R.new_log()
+    t, idx = R.opaque_hit(S, o, d, np.inf, np.float64, log=log, samples=np.arange(3))
+    quad65 = 1 + R.CAP  # (the wall is primitive 0, the quads follow)
     assert idx.tolist() == [quad65, quad65, -1]
-    assert abs(t[0] - (10.0 - (4.0 - 0.1 * RA.CAP))) < 1e-6 and abs(t[1] - t[0] / 20) < 1e-9  # (the total t, from the first origin; the quad's z is an fp32)
-    assert tally["masked_hits"] == 130 and tally["passes"] == 128 and tally["opaque"] == 2 and tally["max_passes"] == RA.CAP
-    assert tally["sample_masked"].tolist() == [True, True, False] and tally["path_queries"] == 3 and tally["shadow_queries"] == 0
+    assert abs(t[0] - (10.0 - (4.0 - 0.1 * R.CAP))) < 1e-6 and abs(t[1] - t[0] / 20) < 1e-9  # (the total t, from the first origin; the quad's z is an fp32)
+    assert log["alpha_masked_hits"] == 130 and log["alpha_passes"] == 128 and log["alpha_opaque"] == 2 and log["alpha_max_passes"] == R.CAP
+    assert sorted(log["alpha_masked_samples"]) == [0, 1] and log["alpha_path_queries"] == 3 and log["alpha_shadow_queries"] == 0
     # a shadow query (an array of far ends) whose far end lies behind 3 quads passes them and is clear; one that ends on the
     # 66th hit is occluded by the 65th
     far = np.array([6.25, 20.0])
-    t, idx = RA.closest_hit(S, o[:2], np.array([[0.0, 0.0, -1.0]] * 2), far, np.float64, tally=tally)
-    assert idx.tolist() == [-1, quad65] and tally["shadow_through"] == 2 and tally["shadow_queries"] == 2
+    t, idx = R.opaque_hit(S, o[:2], np.array([[0.0, 0.0, -1.0]] * 2), far, np.float64, log=log)
+    assert idx.tolist() == [-1, quad65] and log["alpha_shadow_through"] == 2 and log["alpha_shadow_queries"] == 2
     # 64 quads: all passed, the wall is the winner; without masks: the first quad
-    few = AS.stack(rtmi, n=RA.CAP)
-    assert RA.closest_hit(RA.ref_scene(few), o[:1], d[:1], np.inf, np.float64)[1].tolist() == [0]
-    assert RA.closest_hit(RA.ref_scene(AS.stack(rtmi, masks=False)), o[:1], d[:1], np.inf, np.float64)[1].tolist() == [1]
+    few = AS.stack(rtmi, n=R.CAP)
+    assert R.opaque_hit(R.RefScene(few), o[:1], d[:1], np.inf, np.float64)[1].tolist() == [0]
+    assert R.opaque_hit(R.RefScene(AS.stack(rtmi, masks=False)), o[:1], d[:1], np.inf, np.float64)[1].tolist() == [1]
     # the mistakes change the verdicts
-    assert RA.closest_hit(S, o[:1], d[:1], np.inf, np.float64, perturb=("al_off",))[1].tolist() == [1]
-    assert RA.closest_hit(S, o[:1], d[:1], np.inf, np.float64, perturb=("al_inverted",))[1].tolist() == [1]
-    assert RA.closest_hit(S, o[:1], d[:1], far[1:], np.float64, perturb=("al_shadow_opaque",))[1].tolist() == [1]
+    assert R.opaque_hit(S, o[:1], d[:1], np.inf, np.float64, perturb=("al_off",))[1].tolist() == [1]
+    assert R.opaque_hit(S, o[:1], d[:1], np.inf, np.float64, perturb=("al_inverted",))[1].tolist() == [1]
+    assert R.opaque_hit(S, o[:1], d[:1], far[1:], np.float64, perturb=("al_shadow_opaque",))[1].tolist() == [1]
     # the frame's centre pixel is the 65th quad's colour under the white background
     w = R.uniforms(rtmi, 5, 9, 9, 0, 1, 64)
-    rgb, _, _ = RA.trace(S, w)
-    assert np.abs(rgb.reshape(9, 9, 3)[4, 4] - np.array(AS.stack_colour(RA.CAP))).max() < 1e-6
+    rgb, _, _ = R.trace(S, w)
+    assert np.abs(rgb.reshape(9, 9, 3)[4, 4] - np.array(AS.stack_colour(R.CAP))).max() < 1e-6
 
 
 def test_the_nested_clump_holds_its_contents(rtmi):
     """the nested case's conditions, from the reference's tally (its grid is the kernels' business: layout 52 against the flat
     walk is test_gpu_alpha.py's)"""
     tally = AS.nested_tally(rtmi)
-    print("\n    " + ", ".join(f"{k} {v if isinstance(v, int) else round(v, 3)}" for k, v in tally.items() if not k.startswith("first")))
+    print("\n    " + ", ".join(f"{k} {v if isinstance(v, int) else round(v, 3)}" for k, v in tally.items() if k.startswith("alpha_")))
     AS.check_contents("al_nested", tally)
 
 
 @pytest.mark.parametrize("name", list(AS.CASES))
 def test_every_case_holds_its_contents(rtmi, name):
-    """the conditions test_gpu_alpha.py asserts before it compares, checked here without a device; the installed function is
-    gone afterwards"""
+    """the conditions test_gpu_alpha.py asserts before it compares, checked here without a device"""
     words, shutter = AS.inputs(rtmi, name)
-    plain = R.closest_hit
-    rgb, stable, draws, _, tally = RA.reference(RA.ref_scene(AS.scene(rtmi, name)), words, shutter)
-    assert R.closest_hit is plain
-    print("\n    " + ", ".join(f"{k} {v if isinstance(v, int) else round(v, 3)}" for k, v in tally.items() if not k.startswith("first")))
+    rgb, stable, draws, tally = R.reference(R.RefScene(AS.scene(rtmi, name)), words, shutter)
+    print("\n    " + ", ".join(f"{k} {v if isinstance(v, int) else round(v, 3)}" for k, v in tally.items() if k.startswith("alpha_")))
     AS.check_contents(name, tally)
     assert draws.max() <= NS.REF_DRAWS and np.isfinite(rgb).all() and 1 - stable.mean() <= 0.01
 
 
 @pytest.mark.parametrize("name,mistake", AS.MISTAKES)
 def test_a_mistake_changes_the_reference(rtmi, words, name, mistake):
-    S = RA.ref_scene(AS.scene(rtmi, name))
+    S = R.RefScene(AS.scene(rtmi, name))
     w = words[:NS.REF_W * NS.REF_H]
-    good, _, _ = RA.trace(S, w)
-    wrong, _, _ = RA.trace(S, w, perturb=(mistake,))
+    good, _, _ = R.trace(S, w)
+    wrong, _, _ = R.trace(S, w, perturb=(mistake,))
     moved = (np.abs(good - wrong).max(axis=1) > 1e-4).mean()
     print(f"\n{name}, {mistake}: {100 * moved:.1f} % of the samples move")
     assert moved > 0.03, (mistake, moved)
+
+
+@pytest.mark.parametrize("name", ["al_layers", "al_lights"])
+def test_the_alpha_cases_trace_as_pinned(rtmi, golden_dir, name):
+    """golden/ref64_alpha_pin.npz holds what the reference returned on al_layers (several passes in one query) and al_lights
+    (shadow rays through holes) while the alpha-aware query was a module of its own that stood in ref64.closest_hit's place for
+    the length of a trace (golden/make_ref64_alpha_pin.py; the first sample of each pixel).  Compared as
+    test_glass.py::test_the_extensions_trace_as_pinned compares: the draws, the signature, the seven counters and first_idx
+    exact; the radiance at rtol 1e-9 -- the fp64 run's after rounding to float32, as it is stored; the fp32 run's by its bytes"""
+    pin = np.load(os.path.join(golden_dir, "ref64_alpha_pin.npz"))
+    cases = json.loads(str(pin["cases"]))
+    at, rec = list(cases).index(name), cases[name]
+    S, sha = R.RefScene(AS.scene(rtmi, name)), lambda a: hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+    words = AS.inputs(rtmi, name)[0][:NS.REF_W * NS.REF_H]
+    for k, (tag, dtype) in enumerate((("64", np.float64), ("32", np.float32))):
+        log, probe = R.new_log(), {}
+        rgb, sig, draws = R.trace(S, words, dtype=dtype, log=log, probe=probe)
+        assert np.array_equal(draws, pin["draws"][k][at]) and sha(sig) == rec["sig" + tag], (name, tag)
+        assert {c: log["alpha_" + c] for c in R.ALPHA_COUNTERS} == rec["counters" + tag], (name, tag)
+        assert sha(probe["first_idx"]) == rec["first_idx" + tag], (name, tag)
+        if tag == "64":
+            assert np.allclose(rgb.astype(np.float32), pin["rgb64"][at], rtol=1e-9, atol=1e-12), (name, tag)
+        else:
+            assert sha(rgb) == rec["rgb32"], (name, tag)
 
 
 def test_the_tool_writes_the_shipped_scene(rtmi, scenes_dir):
@@ -468,7 +488,7 @@ def test_the_tool_writes_the_shipped_scene(rtmi, scenes_dir):
     assert len(text) < 96 * 1024
     sc = rtmi.Scene.parse(text)
     masked = [m for m in range(len(sc.materials())) if sc.alpha(m) is not None]
-    assert len(masked) == 4 and all(0.2 < (sc.get_image_alpha(sc.alpha(m)[0]) >= RA.cutoff_byte(sc.alpha(m)[1])).mean() < 0.8 for m in masked)
+    assert len(masked) == 4 and all(0.2 < (sc.get_image_alpha(sc.alpha(m)[0]) >= R.cutoff_byte(sc.alpha(m)[1])).mean() < 0.8 for m in masked)
 
 
 # ------------------------------------------------------------------------------------------------------------ 6. sanitizers

@@ -368,10 +368,7 @@ def test_the_extensions_trace_as_pinned(rtmi, golden_dir, family):
     at, rec = list(cases).index(family), cases[family]
     SC = importlib.import_module({"mesh_lights": "mesh_light_scenes", "quads": "quad_scenes", "analytic_lights": "analytic_light_scenes"}.get(family, family + "_scenes"))
     sc = SC.scene(rtmi, rec["case"])
-    try:
-        words = SC.inputs(rtmi, rec["case"])[0]
-    except TypeError:
-        words = SC.inputs(rtmi)
+    words = SC.inputs(rtmi, rec["case"])[0]
     S, sha = R.RefScene(sc), lambda a: hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
     for k, (tag, dtype) in enumerate((("64", np.float64), ("32", np.float32))):
         rgb, sig, draws = R.trace(S, words[:NS.REF_W * NS.REF_H], dtype=dtype)

@@ -1,5 +1,5 @@
-"""Alpha cutouts in every general render family, against the fp64 statement of ref64.py with ref64_alpha's
-closest hit installed, sample by sample on the same draws: criteria (a) - (d) of test_gpu_nee_reference.py with per_sample's
+"""Alpha cutouts in every general render family, against the fp64 statement of ref64.py (its opaque_hit is the query
+trace() makes), sample by sample on the same draws: criteria (a) - (d) of test_gpu_nee_reference.py with per_sample's
 thresholds, on the five cases of alpha_scenes.py.  The (b) baseline is the plain kernel on the case's twin -- every mask
 removed, light sampling off, environment, movers and analytic lights cleared -- against the twin's reference.  Each case
 asserts its contents from the reference's tally alone (alpha_scenes.check_contents).
@@ -19,10 +19,6 @@ grid; the feature buffers; ray queries; the refusals; the command line on the sh
 estimator.
 
 Every case prints one row of figures (pytest -s)."""
-import os
-import subprocess
-import sys
-import textwrap
 
 import numpy as np
 import pytest
@@ -31,13 +27,8 @@ import alpha_scenes as AS
 import nee_scenes as NS
 import per_sample as PS
 import ref64 as R
-import ref64_alpha as RA
 
 pytestmark = pytest.mark.gpu
-ROOT = PS.ROOT
-PKG = os.path.join(ROOT, "ray-tracing-in-cuda_amd")
-GENERAL_LAYOUTS = (16, 36, 44)  # a scene with a mask runs the general (EXT) builds: never the compact layouts 2 / 6
-NESTED_LAYOUT = 52
 
 
 @pytest.fixture(scope="module")
@@ -47,58 +38,24 @@ def rtmi():
 
 @pytest.fixture(scope="module")
 def inputs(rtmi):
-    made = {}
-
-    def of(name):
-        key = (AS.seed_of(name), AS.family(name) == AS.MOTION)
-        if key not in made:
-            made[key] = AS.inputs(rtmi, name)
-        return made[key]
-    return of
+    return PS.input_cache(rtmi, AS)
 
 
 @pytest.fixture(scope="module")
 def cases(rtmi, inputs):
-    """name -> (scene, RefScene, kernel samples, (ref, stable, draws, tally, alpha tally)): rendered and traced once, shared"""
-    made = {}
-
-    def of(name):
-        if name not in made:
-            words, shutter = inputs(name)
-            sc = AS.scene(rtmi, name)
-            S = RA.ref_scene(sc)
-            st = rtmi.Stats()
-            sc.render(rtmi.Opts(seed=AS.seed_of(name), sample_count=1), st)
-            assert st.kernel_variant & ~AS.FAMILIES in GENERAL_LAYOUTS and st.kernel_variant & AS.FAMILIES == AS.family(name), st.kernel_variant
-            got = PS.kernel_samples(rtmi, sc, AS.seed_of(name), NS.REF_K, AS.FAMILIES, AS.family(name))
-            made[name] = (sc, S, got, RA.reference(S, words, shutter))
-        return made[name]
-    return of
+    """name -> (scene, RefScene, kernel samples, (ref, stable, draws, tally)): rendered and traced once, shared by the tests"""
+    return PS.case_cache(rtmi, AS, inputs)
 
 
 @pytest.mark.parametrize("name", list(AS.CASES))
 def test_kernel_against_fp64(rtmi, inputs, cases, name):
-    words, shutter = inputs(name)
-    assert len(words) >= 16000
-    sc, S, got, (ref, stable, draws, _, tally) = cases(name)
-    assert draws.max() <= NS.REF_DRAWS, draws.max()                                        # (d)
-    print("\n    " + ", ".join(f"{k} {v if isinstance(v, int) else round(v, 3)}" for k, v in tally.items() if not k.startswith("first")))
-    AS.check_contents(name, tally)
-    plain = AS.plain_twin(rtmi, name)
-    bref, bstable, _, _ = R.reference(R.RefScene(plain), words)
-    b = R.judge(PS.kernel_samples(rtmi, plain, AS.seed_of(name), NS.REF_K, AS.FAMILIES, 0), bref, bstable)
-    PS.assert_agreement(name, R.judge(got, ref, stable), b)                                # (a), (b), (c)
+    print("\n    " + ", ".join(f"{k} {v if isinstance(v, int) else round(v, 3)}" for k, v in cases(name)[3][3].items() if k.startswith("alpha_")))
+    PS.check_kernel_against_fp64(rtmi, AS, inputs, cases, name)
 
 
 @pytest.mark.parametrize("name,mistake", AS.MISTAKES)
 def test_a_mistake_fails_the_agreement(inputs, cases, name, mistake):
-    """(d): against the kernel, a reference with one deliberate mistake of the model is far from 97 %"""
-    words, shutter = inputs(name)
-    sc, S, got, (ref, stable, _, _, _) = cases(name)
-    wrong, _, _ = RA.trace(S, words, shutter=shutter, perturb=(mistake,))
-    good, bad = R.judge(got, ref, stable), R.judge(got, wrong, stable)
-    print(f"\n{name}, {mistake}: within tolerance {100 * good['share']:.2f} % -> {100 * bad['share']:.2f} %")
-    PS.assert_perturbation_noticed(good, bad)
+    PS.check_a_mistake_fails_the_agreement(inputs, cases, name, mistake)
 
 
 @pytest.mark.parametrize("name", ["al_sky", "al_lights", "al_motion"])
@@ -109,7 +66,7 @@ def test_opaque_masks_render_the_twins_bytes(rtmi, name):
     assert sum(still.alpha(m) is not None for m in range(len(still.materials()))) >= 2
     assert still.table_image().tobytes() != twin.table_image().tobytes()
     st = rtmi.Stats()
-    for variant in GENERAL_LAYOUTS:
+    for variant in PS.GENERAL_LAYOUTS:
         o = rtmi.Opts(seed=AS.seed_of(name), sample_count=NS.REF_K, variant=variant)
         a = still.render(o, st)
         assert st.kernel_variant == variant | AS.family(name), (variant, st.kernel_variant)
@@ -129,7 +86,7 @@ def test_clear_masks_render_the_scene_without_those_primitives(rtmi, name):
     assert len(gone.prims()) < len(clear.prims())
     fam, seed = AS.family(name), AS.seed_of(name)
     want = PS.kernel_samples(rtmi, gone, seed, 4, AS.FAMILIES, fam)
-    for variant in GENERAL_LAYOUTS:
+    for variant in PS.GENERAL_LAYOUTS:
         got = PS.kernel_samples(rtmi, clear, seed, 4, AS.FAMILIES, fam, variant=variant)
         j = R.judge(got, want, np.ones(len(want), bool))
         print(f"\n{name}, layout {variant}: within {100 * j['share']:.3f} %, max |mean diff| {np.abs(j['mean_diff']).max():.1e}")
@@ -142,51 +99,19 @@ def test_the_cap_shows_the_65th_quad(rtmi):
     front, which a new query may pass).  Without the cap it would show the wall"""
     sc = AS.stack(rtmi)
     st = rtmi.Stats()
-    for variant in GENERAL_LAYOUTS:
+    for variant in PS.GENERAL_LAYOUTS:
         img = sc.render(rtmi.Opts(seed=5, sample_count=1, variant=variant), st)
         assert st.kernel_variant == variant
         px = img[4, 4].astype(np.float64)
         print(f"\nlayout {variant}: centre pixel {px}")
-        assert np.abs(px - np.array(AS.stack_colour(RA.CAP))).max() < 1e-4, (variant, px)
+        assert np.abs(px - np.array(AS.stack_colour(R.CAP))).max() < 1e-4, (variant, px)
         assert np.abs(px - np.array(AS.STACK_WALL)).max() > 0.1
-    few = AS.stack(rtmi, n=RA.CAP).render(rtmi.Opts(seed=5, sample_count=1), st)[4, 4]
+    few = AS.stack(rtmi, n=R.CAP).render(rtmi.Opts(seed=5, sample_count=1), st)[4, 4]
     assert np.abs(few - np.array(AS.STACK_WALL)).max() < 1e-4, few  # (64 quads: all passed, the wall shows)
 
 
-_PRODUCT = textwrap.dedent("""
-    import os, sys
-    import numpy as np
-    sys.path.insert(0, %r)
-    sys.path.insert(0, os.path.join(%r, "tests"))
-    from __graft_entry__ import load_package
-    rtmi = load_package()
-    assert not rtmi.has_ablations()
-    import alpha_scenes as AS, nee_scenes as NS
-    for name in ("al_sky", "al_lights"):
-        st = rtmi.Stats()
-        img = AS.scene(rtmi, name).render(rtmi.Opts(seed=AS.seed_of(name), sample_count=NS.REF_K), st)
-        assert st.kernel_variant & AS.FAMILIES == AS.family(name), st.kernel_variant
-        np.save(os.path.join(sys.argv[1], name + ".npy"), img)
-""") % (ROOT, ROOT)
-
-
 def test_layouts_a_sample_split_and_the_product_library_give_the_same_bytes(rtmi, tmp_path):
-    env = dict(os.environ, RTMI_LIB=os.path.join(PKG, "librtmi_product.so"))
-    p = subprocess.run([sys.executable, "-c", _PRODUCT, str(tmp_path)], capture_output=True, text=True, env=env, timeout=600)
-    assert p.returncode == 0, p.stderr[-2000:]
-    for name in ("al_sky", "al_lights"):
-        sc, fam, seed, st = AS.scene(rtmi, name), AS.family(name), AS.seed_of(name), rtmi.Stats()
-        ref = sc.render(rtmi.Opts(seed=seed, sample_count=NS.REF_K), st)
-        assert st.kernel_variant & AS.FAMILIES == fam and st.kernel_variant & ~AS.FAMILIES in GENERAL_LAYOUTS
-        for variant in GENERAL_LAYOUTS:
-            got = sc.render(rtmi.Opts(seed=seed, sample_count=NS.REF_K, variant=variant), st)
-            assert st.kernel_variant == variant | fam, (variant, st.kernel_variant)
-            assert np.array_equal(got, ref), (name, variant, float(np.abs(got - ref).max()))
-        acc, _ = sc.accumulate(None, rtmi.Opts(seed=seed, sample_first=0, sample_count=5), st)
-        assert st.kernel_variant & AS.FAMILIES == fam
-        acc, img = sc.accumulate(acc, rtmi.Opts(seed=seed, sample_first=5, sample_count=NS.REF_K - 5), st)
-        assert np.array_equal(img, ref), (name, float(np.abs(img - ref).max()))
-        assert np.array_equal(np.load(str(tmp_path / (name + ".npy"))), ref), name
+    PS.check_same_bytes(rtmi, AS, ("al_sky", "al_lights"), tmp_path)
 
 
 def test_refusals(rtmi):
@@ -218,15 +143,15 @@ def test_the_nested_grid_renders_the_same_bytes(rtmi):
     sc = AS.nested(rtmi)
     assert sc.nested_info().cells > 0
     tally = AS.nested_tally(rtmi)
-    print("\n    " + ", ".join(f"{k} {v if isinstance(v, int) else round(v, 3)}" for k, v in tally.items() if not k.startswith("first")))
+    print("\n    " + ", ".join(f"{k} {v if isinstance(v, int) else round(v, 3)}" for k, v in tally.items() if k.startswith("alpha_")))
     AS.check_contents("al_nested", tally)  # (the clump's queries meet masked hits, with both verdicts)
     nested = sc.render(rtmi.Opts(seed=NS.REF_SEED, sample_count=NS.REF_K), st)
-    assert st.kernel_variant == NESTED_LAYOUT
+    assert st.kernel_variant == PS.NESTED_LAYOUT
     twin = AS.nested(rtmi, masks=False).render(rtmi.Opts(seed=NS.REF_SEED, sample_count=NS.REF_K), st)
     assert not np.array_equal(nested, twin)  # (the holes show)
     sc.set_nested_grid(False)
     flat = sc.render(rtmi.Opts(seed=NS.REF_SEED, sample_count=NS.REF_K), st)
-    assert st.kernel_variant in GENERAL_LAYOUTS and np.array_equal(nested, flat)
+    assert st.kernel_variant in PS.GENERAL_LAYOUTS and np.array_equal(nested, flat)
 
 
 def test_feature_buffers_show_the_first_opaque_hit(rtmi, inputs):
@@ -238,18 +163,17 @@ def test_feature_buffers_show_the_first_opaque_hit(rtmi, inputs):
     sc, twin = AS.scene(rtmi, name), AS.scene(rtmi, name, masks=False)
     words, _ = inputs(name)
     n = NS.REF_W * NS.REF_H
-    S, probe, tally, t32 = RA.ref_scene(sc), {}, RA.new_tally(n), RA.new_tally(n)
-    t32["dtype"] = np.float32
-    RA.trace(S, words[:n], probe=probe, tally=tally)
-    RA.trace(S, words[:n], dtype=np.float32, tally=t32)
-    hit = tally["first_idx"] >= 0
-    same = hit & (tally["first_idx"] == t32["first_idx"])  # (the pixels whose first opaque winner does not depend on the precision)
+    S, probe, p32 = R.RefScene(sc), {}, {}
+    R.trace(S, words[:n], probe=probe)
+    R.trace(S, words[:n], dtype=np.float32, probe=p32)
+    hit = probe["first_idx"] >= 0
+    same = hit & (probe["first_idx"] == p32["first_idx"])  # (the pixels whose first opaque winner does not depend on the precision)
     o = rtmi.Opts(seed=AS.seed_of(name), sample_first=0, sample_count=1)
     depth = sc.render_feature(rtmi.FEATURE_DEPTH, o).reshape(-1, 3).astype(np.float64)
     normal = sc.render_feature(rtmi.FEATURE_NORMAL, o).reshape(-1, 3).astype(np.float64)
     flat_d = twin.render_feature(rtmi.FEATURE_DEPTH, o).reshape(-1, 3).astype(np.float64)
     assert (depth[same, 1] == 1).all()  # (coverage: 1 on a hit)
-    err_t = np.abs(depth[same, 0] - tally["first_t"][same]) / np.maximum(1.0, tally["first_t"][same])
+    err_t = np.abs(depth[same, 0] - probe["first_t"][same]) / np.maximum(1.0, probe["first_t"][same])
     err_n = np.abs(normal[same] - probe["normal"][same]).max(axis=1)
     through = hit & (np.abs(depth[:, 0] - flat_d[:, 0]) > 1e-3)
     print(f"\nfeature passes of {name}: {hit.sum()} hit pixels, {same.sum()} with one winner at both precisions: max depth error "
@@ -262,35 +186,15 @@ def test_feature_buffers_show_the_first_opaque_hit(rtmi, inputs):
 
 def test_ray_queries_report_the_twins_records(rtmi):
     """Scene.trace on al_layers returns the records of its twin without masks: queries are for geometry"""
-    import trace_cases as TC
     sc, twin = AS.scene(rtmi, "al_layers"), AS.scene(rtmi, "al_layers", masks=False)
-    boxes = [TC.prim_box(p) for p in sc.prims()[2:]]  # (every primitive but the floor and the wall)
-    lo, hi = np.min([b[0] for b in boxes], axis=0), np.max([b[1] for b in boxes], axis=0)
-    o, d = TC.make_rays(lo, hi)
-    a, b = sc.trace(o, d), twin.trace(o, d)
-    hit = a["prim"] >= 0
-    assert hit.sum() >= 500
-    assert a.tobytes() == b.tobytes()
+    a, hit = PS.check_ray_queries_of_twins(sc, twin, lambda prims: prims[2:])  # (every primitive but the floor and the wall)
     assert sum(sc.alpha(int(m)) is not None for m in a["material"][hit]) >= 300
 
 
 @pytest.mark.parametrize("nee", [False, True], ids=["plain", "nee"])
 def test_the_cli_renders_the_shipped_scene(rtmi, tmp_path, nee):
-    out = str(tmp_path / "garden.ppm")
-    p = subprocess.run([os.path.join(PKG, "rtmi"), "-f", os.path.join(PKG, "scenes", "cutout_garden.json"), "-w", "64", "-h", "36", "-spp", "4",
-                        "-o", out, "--no-png"] + (["--nee"] if nee else []), capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0, p.stderr[-2000:]
-    sc = rtmi.Scene.load(os.path.join(PKG, "scenes", "cutout_garden.json"))
-    assert sum(sc.alpha(m) is not None for m in range(len(sc.materials()))) >= 4
-    sc.override(64, 36, 4)
-    sc.set_light_sampling(nee)
-    st = rtmi.Stats()
-    img = sc.render(rtmi.Opts(), st)
-    assert bool(st.kernel_variant & AS.NEE) == nee and np.isfinite(img).all() and img.mean() > 0
-    tokens = open(out).read().split()  # the reference's text PPM: P3, width, height, 255, then the 8-bit values
-    assert tokens[:4] == ["P3", "64", "36", "255"] and len(tokens) == 4 + 64 * 36 * 3
-    values = np.array(tokens[4:], np.int64)
-    assert values.min() >= 0 and values.max() <= 255 and values.max() > 0
+    PS.check_cli(rtmi, tmp_path, "cutout_garden.json", nee, AS.NEE,
+                 loaded=lambda sc: sum(sc.alpha(m) is not None for m in range(len(sc.materials()))) >= 4)
 
 
 def test_light_sampling_is_unbiased_against_the_plain_estimator(rtmi):

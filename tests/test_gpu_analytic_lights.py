@@ -13,8 +13,6 @@ the lights, ray queries and feature passes unchanged, and the command line rende
 Every case prints one row of figures (pytest -s); DESIGN 7s holds the rows measured on the MI355X."""
 import os
 import subprocess
-import sys
-import textwrap
 
 import numpy as np
 import pytest
@@ -26,9 +24,6 @@ import ref64 as R
 import smooth_scenes as SM
 
 pytestmark = pytest.mark.gpu
-ROOT = PS.ROOT
-PKG = os.path.join(ROOT, "ray-tracing-in-cuda_amd")
-GENERAL_LAYOUTS = (16, 36, 44)
 NEE = AL.NEE
 
 
@@ -38,53 +33,29 @@ def rtmi():
 
 
 @pytest.fixture(scope="module")
-def words(rtmi):
-    return AL.inputs(rtmi)
+def inputs(rtmi):
+    return PS.input_cache(rtmi, AL)
 
 
 @pytest.fixture(scope="module")
-def cases(rtmi, words):
-    """name -> (scene, RefScene, kernel samples, (ref, stable, draws, tally)): rendered and traced once"""
-    made = {}
-
-    def of(name):
-        if name not in made:
-            sc = AL.scene(rtmi, name)
-            S = R.RefScene(sc)
-            st = rtmi.Stats()
-            sc.render(rtmi.Opts(seed=NS.REF_SEED, sample_count=1), st)
-            assert st.kernel_variant & ~AL.FAMILIES in GENERAL_LAYOUTS and st.kernel_variant & AL.FAMILIES == AL.family(name), st.kernel_variant
-            got = PS.kernel_samples(rtmi, sc, NS.REF_SEED, NS.REF_K, AL.FAMILIES, AL.family(name))
-            made[name] = (sc, S, got, R.reference(S, words))
-        return made[name]
-    return of
+def cases(rtmi, inputs):
+    """name -> (scene, RefScene, kernel samples, (ref, stable, draws, tally)): rendered and traced once, shared by the tests"""
+    return PS.case_cache(rtmi, AL, inputs)
 
 
 @pytest.mark.parametrize("name", list(AL.CASES))
-def test_kernel_against_fp64(rtmi, words, cases, name):
-    assert len(words) >= 16000
+def test_kernel_against_fp64(rtmi, inputs, cases, name):
     sc, S, got, (ref, stable, draws, tally) = cases(name)
-    assert draws.max() <= NS.REF_DRAWS, draws.max()
-    AL.check_contents(name, tally)
-    plain = AL.plain_twin(rtmi, name)
-    assert len(plain.analytic_lights()) == len(sc.analytic_lights())
-    bref, bstable, _, _ = R.reference(R.RefScene(plain), words)
-    b = R.judge(PS.kernel_samples(rtmi, plain, NS.REF_SEED, NS.REF_K, AL.FAMILIES, 0), bref, bstable)
-    r32, _, _ = R.trace(S, words, dtype=np.float32)
-    fp32 = f"fp32 NumPy within {100 * R.judge(r32, ref, stable)['share']:.3f} %"
+    r32, _, _ = R.trace(S, inputs(name)[0], dtype=np.float32)
+    assert len(AL.plain_twin(rtmi, name).analytic_lights()) == len(sc.analytic_lights())
     shown = [k for k in tally if k in AL.CASES[name][2] or k.endswith("_picks")]
-    print(f"\n    {fp32}; " + ", ".join(f"{k} {tally[k]}" for k in shown))
-    PS.assert_agreement(name, R.judge(got, ref, stable), b)                                # (a), (b), (c)
+    print(f"\n    fp32 NumPy within {100 * R.judge(r32, ref, stable)['share']:.3f} %; " + ", ".join(f"{k} {tally[k]}" for k in shown))
+    PS.check_kernel_against_fp64(rtmi, AL, inputs, cases, name)
 
 
 @pytest.mark.parametrize("name,mistake", AL.MISTAKES)
-def test_a_wrong_reference_is_noticed(words, cases, name, mistake):
-    """against the kernel, a reference with one deliberate mistake of the analytic lights is far from 97 %"""
-    sc, S, got, (ref, stable, _, _) = cases(name)
-    wrong, _, _ = R.trace(S, words, perturb=(mistake,))
-    good, bad = R.judge(got, ref, stable), R.judge(got, wrong, stable)
-    print(f"\n{name}, {mistake}: within tolerance {100 * good['share']:.2f} % -> {100 * bad['share']:.2f} %")
-    PS.assert_perturbation_noticed(good, bad)
+def test_a_wrong_reference_is_noticed(inputs, cases, name, mistake):
+    PS.check_a_mistake_fails_the_agreement(inputs, cases, name, mistake)
 
 
 # ---------------------------------------------------------------------------------------------------------- known answers
@@ -208,41 +179,8 @@ def test_refusals_are_light_samplings(rtmi):
 
 
 # ---------------------------------------------------------------------------------------------------------- what stays
-_BYTES_CASES = ("two spots + quad + sphere", "sun + environment")
-_PRODUCT = textwrap.dedent("""
-    import os, sys
-    import numpy as np
-    sys.path.insert(0, %r)
-    sys.path.insert(0, os.path.join(%r, "tests"))
-    from __graft_entry__ import load_package
-    rtmi = load_package()
-    assert not rtmi.has_ablations()
-    import analytic_light_scenes as AL, nee_scenes as NS
-    for name in %r:
-        st = rtmi.Stats()
-        img = AL.scene(rtmi, name).render(rtmi.Opts(seed=NS.REF_SEED, sample_count=NS.REF_K), st)
-        assert st.kernel_variant & AL.FAMILIES == AL.family(name), st.kernel_variant
-        np.save(os.path.join(sys.argv[1], name.replace(" ", "_") + ".npy"), img)
-""") % (ROOT, ROOT, _BYTES_CASES)
-
-
 def test_layouts_a_sample_split_and_the_product_library_give_the_same_bytes(rtmi, tmp_path):
-    env = dict(os.environ, RTMI_LIB=os.path.join(PKG, "librtmi_product.so"))
-    p = subprocess.run([sys.executable, "-c", _PRODUCT, str(tmp_path)], capture_output=True, text=True, env=env, timeout=600)
-    assert p.returncode == 0, p.stderr[-2000:]
-    for name in _BYTES_CASES:
-        sc, fam, seed, st = AL.scene(rtmi, name), AL.family(name), NS.REF_SEED, rtmi.Stats()
-        ref = sc.render(rtmi.Opts(seed=seed, sample_count=NS.REF_K), st)
-        assert st.kernel_variant & AL.FAMILIES == fam and st.kernel_variant & ~AL.FAMILIES in GENERAL_LAYOUTS
-        for variant in GENERAL_LAYOUTS:
-            got = sc.render(rtmi.Opts(seed=seed, sample_count=NS.REF_K, variant=variant), st)
-            assert st.kernel_variant == variant | fam, (variant, st.kernel_variant)
-            assert np.array_equal(got, ref), (name, variant, float(np.abs(got - ref).max()))
-        acc, _ = sc.accumulate(None, rtmi.Opts(seed=seed, sample_first=0, sample_count=5), st)
-        assert st.kernel_variant & AL.FAMILIES == fam
-        acc, img = sc.accumulate(acc, rtmi.Opts(seed=seed, sample_first=5, sample_count=NS.REF_K - 5), st)
-        assert np.array_equal(img, ref), (name, float(np.abs(img - ref).max()))
-        assert np.array_equal(np.load(str(tmp_path / (name.replace(" ", "_") + ".npy"))), ref), name
+    PS.check_same_bytes(rtmi, AL, ("two spots + quad + sphere", "sun + environment"), tmp_path)
 
 
 def test_light_sampling_off_renders_the_scene_without_the_lights(rtmi):
@@ -279,14 +217,14 @@ def test_ray_queries_and_feature_passes_ignore_the_lights(rtmi):
 
 def test_the_command_line_renders_the_shipped_scene(rtmi, tmp_path):
     out = str(tmp_path / "spot_stage.png")
-    scene = os.path.join(PKG, "scenes", "spot_stage.json")
+    scene = os.path.join(PS.PKG, "scenes", "spot_stage.json")
     size = ["-w", "96", "-h", "54", "-spp", "8"]
-    p = subprocess.run([os.path.join(PKG, "rtmi"), "-f", scene, "-o", out, "--nee"] + size, capture_output=True, text=True, timeout=300)
+    p = subprocess.run([os.path.join(PS.PKG, "rtmi"), "-f", scene, "-o", out, "--nee"] + size, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
     assert os.path.getsize(out) > 1000 and "light sampling is off" not in p.stderr
     # the file leaves light sampling to --nee, as every shipped scene does: without it the lights light nothing, and rtmi says
     # so in one line on stderr
     assert '"light_sampling": false' in open(scene).read()
-    p = subprocess.run([os.path.join(PKG, "rtmi"), "-f", scene, "-o", out] + size, capture_output=True, text=True, timeout=300)
+    p = subprocess.run([os.path.join(PS.PKG, "rtmi"), "-f", scene, "-o", out] + size, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
     assert p.stderr.count("light sampling is off") == 1

@@ -13,11 +13,6 @@ refusals; the nested grid; the feature buffers; ray queries; the command line on
 the plain estimator.
 
 Every case prints one row of figures (pytest -s); DESIGN 7p holds the rows measured on the MI355X."""
-import os
-import subprocess
-import sys
-import textwrap
-
 import numpy as np
 import pytest
 
@@ -27,10 +22,6 @@ import per_sample as PS
 import ref64 as R
 
 pytestmark = pytest.mark.gpu
-ROOT = PS.ROOT
-PKG = os.path.join(ROOT, "ray-tracing-in-cuda_amd")
-GENERAL_LAYOUTS = (16, 36, 44)  # a scene with a bump runs the general (EXT) builds: never the compact layouts 2 / 6
-NESTED_LAYOUT = 52
 
 
 @pytest.fixture(scope="module")
@@ -40,97 +31,29 @@ def rtmi():
 
 @pytest.fixture(scope="module")
 def inputs(rtmi):
-    made = {}
-
-    def of(name):
-        key = (BS.seed_of(name), BS.family(name) == BS.MOTION)
-        if key not in made:
-            made[key] = BS.inputs(rtmi, name)
-        return made[key]
-    return of
+    return PS.input_cache(rtmi, BS)
 
 
 @pytest.fixture(scope="module")
 def cases(rtmi, inputs):
-    """name -> (scene, RefScene, kernel samples, (ref, stable, draws, tally), bump tally): rendered and traced once, shared"""
-    made = {}
-
-    def of(name):
-        if name not in made:
-            words, shutter = inputs(name)
-            sc = BS.scene(rtmi, name)
-            S = R.RefScene(sc)
-            st = rtmi.Stats()
-            sc.render(rtmi.Opts(seed=BS.seed_of(name), sample_count=1), st)
-            assert st.kernel_variant & ~BS.FAMILIES in GENERAL_LAYOUTS and st.kernel_variant & BS.FAMILIES == BS.family(name), st.kernel_variant
-            got = PS.kernel_samples(rtmi, sc, BS.seed_of(name), NS.REF_K, BS.FAMILIES, BS.family(name))
-            ref = R.reference(S, words, shutter)
-            made[name] = (sc, S, got, ref, {k: v for k, v in ref[3].items() if k.startswith("bump_")})
-        return made[name]
-    return of
+    """name -> (scene, RefScene, kernel samples, (ref, stable, draws, tally)): rendered and traced once, shared by the tests"""
+    return PS.case_cache(rtmi, BS, inputs)
 
 
 @pytest.mark.parametrize("name", list(BS.CASES))
 def test_kernel_against_fp64(rtmi, inputs, cases, name):
-    words, shutter = inputs(name)
-    assert len(words) >= 16000
-    sc, S, got, (ref, stable, draws, tally), bump_tally = cases(name)
-    assert draws.max() <= NS.REF_DRAWS, draws.max()                                        # (d)
-    BS.check_contents(name, bump_tally)
-    plain = BS.plain_twin(rtmi, name)
-    bref, bstable, _, _ = R.reference(R.RefScene(plain), words)
-    b = R.judge(PS.kernel_samples(rtmi, plain, BS.seed_of(name), NS.REF_K, BS.FAMILIES, 0), bref, bstable)
-    PS.assert_agreement(name, R.judge(got, ref, stable), b)                                # (a), (b), (c)
+    PS.check_kernel_against_fp64(rtmi, BS, inputs, cases, name)
+    bump_tally = {k: v for k, v in cases(name)[3][3].items() if k.startswith("bump_")}
     print("    " + ", ".join(f"{k} {v if isinstance(v, int) else round(v, 3)}" for k, v in bump_tally.items() if v))
 
 
 @pytest.mark.parametrize("name,mistake", BS.MISTAKES)
 def test_a_mistake_fails_the_agreement(inputs, cases, name, mistake):
-    """(d): against the kernel, a reference with one deliberate mistake of the model is far from 97 %"""
-    words, shutter = inputs(name)
-    sc, S, got, (ref, stable, _, _), _ = cases(name)
-    wrong, _, _ = R.trace(S, words, shutter=shutter, perturb=(mistake,))
-    good, bad = R.judge(got, ref, stable), R.judge(got, wrong, stable)
-    print(f"\n{name}, {mistake}: within tolerance {100 * good['share']:.2f} % -> {100 * bad['share']:.2f} %")
-    PS.assert_perturbation_noticed(good, bad)
-
-
-_PRODUCT = textwrap.dedent("""
-    import os, sys
-    import numpy as np
-    sys.path.insert(0, %r)
-    sys.path.insert(0, os.path.join(%r, "tests"))
-    from __graft_entry__ import load_package
-    rtmi = load_package()
-    assert not rtmi.has_ablations()
-    import bump_scenes as BS, nee_scenes as NS
-    for name in ("bump_sky", "bump_lights"):
-        st = rtmi.Stats()
-        img = BS.scene(rtmi, name).render(rtmi.Opts(seed=BS.seed_of(name), sample_count=NS.REF_K), st)
-        assert st.kernel_variant & BS.FAMILIES == BS.family(name), st.kernel_variant
-        np.save(os.path.join(sys.argv[1], name + ".npy"), img)
-""") % (ROOT, ROOT)
+    PS.check_a_mistake_fails_the_agreement(inputs, cases, name, mistake)
 
 
 def test_layouts_a_sample_split_and_the_product_library_give_the_same_bytes(rtmi, tmp_path):
-    env = dict(os.environ, RTMI_LIB=os.path.join(PKG, "librtmi_product.so"))
-    p = subprocess.run([sys.executable, "-c", _PRODUCT, str(tmp_path)], capture_output=True, text=True, env=env, timeout=600)
-    assert p.returncode == 0, p.stderr[-2000:]
-    for name in ("bump_sky", "bump_lights"):
-        sc, fam, seed, st = BS.scene(rtmi, name), BS.family(name), BS.seed_of(name), rtmi.Stats()
-        ref = sc.render(rtmi.Opts(seed=seed, sample_count=NS.REF_K), st)
-        assert st.kernel_variant & BS.FAMILIES == fam and st.kernel_variant & ~BS.FAMILIES in GENERAL_LAYOUTS
-        twin = BS.scene(rtmi, name, bump=False).render(rtmi.Opts(seed=seed, sample_count=NS.REF_K), st)
-        assert not np.array_equal(ref, twin)  # (the bumps show)
-        for variant in GENERAL_LAYOUTS:
-            got = sc.render(rtmi.Opts(seed=seed, sample_count=NS.REF_K, variant=variant), st)
-            assert st.kernel_variant == variant | fam, (variant, st.kernel_variant)
-            assert np.array_equal(got, ref), (name, variant, float(np.abs(got - ref).max()))
-        acc, _ = sc.accumulate(None, rtmi.Opts(seed=seed, sample_first=0, sample_count=5), st)
-        assert st.kernel_variant & BS.FAMILIES == fam
-        acc, img = sc.accumulate(acc, rtmi.Opts(seed=seed, sample_first=5, sample_count=NS.REF_K - 5), st)
-        assert np.array_equal(img, ref), (name, float(np.abs(img - ref).max()))
-        assert np.array_equal(np.load(str(tmp_path / (name + ".npy"))), ref), name
+    PS.check_same_bytes(rtmi, BS, ("bump_sky", "bump_lights"), tmp_path, twin=lambda name: BS.scene(rtmi, name, bump=False))
 
 
 def test_refusals(rtmi):
@@ -156,16 +79,16 @@ def test_the_nested_grid_renders_the_same_bytes(rtmi):
     flat = sc.render(rtmi.Opts(seed=NS.REF_SEED, sample_count=NS.REF_K), st)
     sc.set_nested_grid(True)
     assert sc.nested_info().cells == 0
-    assert np.array_equal(sc.render(rtmi.Opts(seed=NS.REF_SEED, sample_count=NS.REF_K), st), flat) and st.kernel_variant in GENERAL_LAYOUTS
+    assert np.array_equal(sc.render(rtmi.Opts(seed=NS.REF_SEED, sample_count=NS.REF_K), st), flat) and st.kernel_variant in PS.GENERAL_LAYOUTS
     sc = BS.nested(rtmi)
     assert sc.nested_info().cells > 0
     nested = sc.render(rtmi.Opts(seed=NS.REF_SEED, sample_count=NS.REF_K), st)
-    assert st.kernel_variant == NESTED_LAYOUT
+    assert st.kernel_variant == PS.NESTED_LAYOUT
     twin = BS.nested(rtmi, bump=False).render(rtmi.Opts(seed=NS.REF_SEED, sample_count=NS.REF_K), st)
     assert not np.array_equal(nested, twin)  # (the bumps show)
     sc.set_nested_grid(False)
     flat = sc.render(rtmi.Opts(seed=NS.REF_SEED, sample_count=NS.REF_K), st)
-    assert st.kernel_variant in GENERAL_LAYOUTS and np.array_equal(nested, flat)
+    assert st.kernel_variant in PS.GENERAL_LAYOUTS and np.array_equal(nested, flat)
 
 
 def test_feature_buffers_show_the_bumped_normal(rtmi, inputs):
@@ -198,34 +121,14 @@ def test_feature_buffers_show_the_bumped_normal(rtmi, inputs):
 
 def test_ray_queries_report_the_twins_records(rtmi):
     """Scene.trace on bump_prims returns the records of its unbumped twin: queries are for geometry"""
-    import trace_cases as TC
     sc, twin = BS.scene(rtmi, "bump_prims"), BS.scene(rtmi, "bump_prims", bump=False)
-    boxes = [TC.prim_box(p) for p in sc.prims()[1:]]  # (every primitive but the far floor)
-    lo, hi = np.min([b[0] for b in boxes], axis=0), np.max([b[1] for b in boxes], axis=0)
-    o, d = TC.make_rays(lo, hi)
-    a, b = sc.trace(o, d), twin.trace(o, d)
-    hit = a["prim"] >= 0
-    assert hit.sum() >= 500
-    assert a.tobytes() == b.tobytes()
+    a, hit = PS.check_ray_queries_of_twins(sc, twin, lambda prims: prims[1:])  # (every primitive but the far floor)
     assert sum(sc.bump(int(m)) is not None for m in a["material"][hit]) >= 300
 
 
 @pytest.mark.parametrize("nee", [False, True], ids=["plain", "nee"])
 def test_the_cli_renders_the_shipped_scene(rtmi, tmp_path, nee):
-    out = str(tmp_path / "pond.ppm")
-    p = subprocess.run([os.path.join(PKG, "rtmi"), "-f", os.path.join(PKG, "scenes", "bumpy_pond.json"), "-w", "64", "-h", "36", "-spp", "4",
-                        "-o", out, "--no-png"] + (["--nee"] if nee else []), capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0, p.stderr[-2000:]
-    sc = rtmi.Scene.load(os.path.join(PKG, "scenes", "bumpy_pond.json"))
-    sc.override(64, 36, 4)
-    sc.set_light_sampling(nee)
-    st = rtmi.Stats()
-    img = sc.render(rtmi.Opts(), st)
-    assert bool(st.kernel_variant & BS.NEE) == nee and np.isfinite(img).all() and img.mean() > 0
-    tokens = open(out).read().split()  # the reference's text PPM: P3, width, height, 255, then the 8-bit values
-    assert tokens[:4] == ["P3", "64", "36", "255"] and len(tokens) == 4 + 64 * 36 * 3
-    values = np.array(tokens[4:], np.int64)
-    assert values.min() >= 0 and values.max() <= 255 and values.max() > 0
+    PS.check_cli(rtmi, tmp_path, "bumpy_pond.json", nee, BS.NEE)
 
 
 def test_light_sampling_is_unbiased_against_the_plain_estimator(rtmi):

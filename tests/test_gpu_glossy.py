@@ -11,11 +11,6 @@ Then what every feature keeps: the same bytes in every layout, through a sample 
 buffers; ray queries; the command line on the shipped scene; and light sampling against the plain estimator.
 
 Every case prints one row of figures (pytest -s); DESIGN 7m holds the rows measured on the MI355X."""
-import os
-import subprocess
-import sys
-import textwrap
-
 import numpy as np
 import pytest
 
@@ -26,9 +21,6 @@ import ref64 as R
 import ref64_glossy as G
 
 pytestmark = pytest.mark.gpu
-ROOT = PS.ROOT
-PKG = os.path.join(ROOT, "ray-tracing-in-cuda_amd")
-GENERAL_LAYOUTS = (16, 36, 44)  # a scene with a glossy material runs the general (EXT) builds: never the compact layouts 2 / 6
 
 
 @pytest.fixture(scope="module")
@@ -38,98 +30,30 @@ def rtmi():
 
 @pytest.fixture(scope="module")
 def inputs(rtmi):
-    made = {}
-
-    def of(name):
-        key = (GS.seed_of(name), GS.family(name) == GS.MOTION)
-        if key not in made:
-            made[key] = GS.inputs(rtmi, name)
-        return made[key]
-    return of
+    return PS.input_cache(rtmi, GS)
 
 
 @pytest.fixture(scope="module")
 def cases(rtmi, inputs):
     """name -> (scene, RefScene, kernel samples, (ref, stable, draws, tally)): rendered and traced once, shared by the tests"""
-    made = {}
-
-    def of(name):
-        if name not in made:
-            words, shutter = inputs(name)
-            sc = GS.scene(rtmi, name)
-            S = R.RefScene(sc)
-            st = rtmi.Stats()
-            sc.render(rtmi.Opts(seed=GS.seed_of(name), sample_count=1), st)
-            assert st.kernel_variant & ~GS.FAMILIES in GENERAL_LAYOUTS and st.kernel_variant & GS.FAMILIES == GS.family(name), st.kernel_variant
-            got = PS.kernel_samples(rtmi, sc, GS.seed_of(name), NS.REF_K, GS.FAMILIES, GS.family(name))
-            made[name] = (sc, S, got, R.reference(S, words, shutter))
-        return made[name]
-    return of
+    return PS.case_cache(rtmi, GS, inputs)
 
 
 @pytest.mark.parametrize("name", list(GS.CASES))
 def test_kernel_against_fp64(rtmi, inputs, cases, name):
-    words, shutter = inputs(name)
-    assert len(words) >= 16000
-    sc, S, got, (ref, stable, draws, tally) = cases(name)
-    assert draws.max() <= NS.REF_DRAWS, draws.max()                                        # (d)
-    GS.check_contents(name, tally)
-    plain = GS.plain_twin(rtmi, name)
-    bref, bstable, _, _ = R.reference(R.RefScene(plain), words)
-    b = R.judge(PS.kernel_samples(rtmi, plain, GS.seed_of(name), NS.REF_K, GS.FAMILIES, 0), bref, bstable)
-    PS.assert_agreement(name, R.judge(got, ref, stable), b)                                # (a), (b), (c)
+    PS.check_kernel_against_fp64(rtmi, GS, inputs, cases, name)
+    tally = cases(name)[3][3]
     print("    " + ", ".join(f"{k} {tally[k]}" for k in G.GLOSSY_KEYS if tally[k]))
 
 
 @pytest.mark.parametrize("name,mistake", [("glossy_sky", "g1_for_g2"), ("glossy_sky", "lobe_draw_last"), ("glossy_lights", "nee_albedo_pdf")])
 def test_a_mistake_fails_the_agreement(inputs, cases, name, mistake):
-    """(d): against the kernel, a reference with one deliberate mistake of the model is far from 97 %"""
-    words, shutter = inputs(name)
-    sc, S, got, (ref, stable, _, _) = cases(name)
-    wrong, _, _ = R.trace(S, words, shutter=shutter, perturb=(mistake,))
-    good, bad = R.judge(got, ref, stable), R.judge(got, wrong, stable)
-    print(f"\n{name}, {mistake}: within tolerance {100 * good['share']:.2f} % -> {100 * bad['share']:.2f} %")
-    PS.assert_perturbation_noticed(good, bad)
-
-
-_PRODUCT = textwrap.dedent("""
-    import os, sys
-    import numpy as np
-    sys.path.insert(0, %r)
-    sys.path.insert(0, os.path.join(%r, "tests"))
-    from __graft_entry__ import load_package
-    rtmi = load_package()
-    assert not rtmi.has_ablations()
-    import glossy_scenes as GS, nee_scenes as NS
-    for name in ("glossy_sky", "glossy_lights"):
-        st = rtmi.Stats()
-        img = GS.scene(rtmi, name).render(rtmi.Opts(seed=GS.seed_of(name), sample_count=NS.REF_K), st)
-        assert st.kernel_variant & GS.FAMILIES == GS.family(name), st.kernel_variant
-        np.save(os.path.join(sys.argv[1], name + ".npy"), img)
-""") % (ROOT, ROOT)
+    PS.check_a_mistake_fails_the_agreement(inputs, cases, name, mistake)
 
 
 def test_layouts_a_sample_split_and_the_product_library_give_the_same_bytes(rtmi, tmp_path):
-    env = dict(os.environ, RTMI_LIB=os.path.join(PKG, "librtmi_product.so"))
-    p = subprocess.run([sys.executable, "-c", _PRODUCT, str(tmp_path)], capture_output=True, text=True, env=env, timeout=600)
-    assert p.returncode == 0, p.stderr[-2000:]
-    for name in ("glossy_sky", "glossy_lights"):
-        sc, fam, seed, st = GS.scene(rtmi, name), GS.family(name), GS.seed_of(name), rtmi.Stats()
-        ref = sc.render(rtmi.Opts(seed=seed, sample_count=NS.REF_K), st)
-        assert st.kernel_variant & GS.FAMILIES == fam and st.kernel_variant & ~GS.FAMILIES in GENERAL_LAYOUTS
-        for variant in GENERAL_LAYOUTS:
-            got = sc.render(rtmi.Opts(seed=seed, sample_count=NS.REF_K, variant=variant), st)
-            assert st.kernel_variant == variant | fam, (variant, st.kernel_variant)
-            assert np.array_equal(got, ref), (name, variant, float(np.abs(got - ref).max()))
-        acc, _ = sc.accumulate(None, rtmi.Opts(seed=seed, sample_first=0, sample_count=5), st)
-        assert st.kernel_variant & GS.FAMILIES == fam
-        acc, img = sc.accumulate(acc, rtmi.Opts(seed=seed, sample_first=5, sample_count=NS.REF_K - 5), st)
-        assert np.array_equal(img, ref), (name, float(np.abs(img - ref).max()))
-        assert np.array_equal(np.load(str(tmp_path / (name + ".npy"))), ref), name
-    # the compact layouts list spheres for the sphere-only kernels, which carry no glossy material: refused
-    for variant in (2, 6):
-        with pytest.raises(rtmi.RtmiError):
-            GS.scene(rtmi, "glossy_sky").render(rtmi.Opts(variant=variant))
+    PS.check_same_bytes(rtmi, GS, ("glossy_sky", "glossy_lights"), tmp_path)
+    PS.check_compact_layouts_refuse(rtmi, lambda: GS.scene(rtmi, "glossy_sky"))
 
 
 def test_feature_buffers_show_the_first_vertex(rtmi, inputs):
@@ -160,34 +84,15 @@ def test_feature_buffers_show_the_first_vertex(rtmi, inputs):
 
 def test_ray_queries_report_the_twins_records(rtmi):
     """Scene.trace on glossy_mesh returns the records of its lambertian twin: a query never looks at what a material does"""
-    import trace_cases as TC
     sc, twin = GS.scene(rtmi, "glossy_mesh"), GS.scene(rtmi, "glossy_mesh", glossy=False)
-    boxes = [TC.prim_box(p) for p in sc.prims() if int(p["type"]) != R.XZ_RECT]
-    lo, hi = np.min([b[0] for b in boxes], axis=0), np.max([b[1] for b in boxes], axis=0)
-    o, d = TC.make_rays(lo, hi)
-    a, b = sc.trace(o, d), twin.trace(o, d)
-    assert (a["prim"] >= 0).sum() >= 500
-    assert a.tobytes() == b.tobytes()
-    kinds = sc.materials()["type"][a["material"][a["prim"] >= 0]]
+    a, hit = PS.check_ray_queries_of_twins(sc, twin, lambda prims: [p for p in prims if int(p["type"]) != R.XZ_RECT])
+    kinds = sc.materials()["type"][a["material"][hit]]
     assert set(np.unique(kinds)) >= {G.ROUGH_METAL, G.PLASTIC}, np.unique(kinds)
     assert not np.isin(twin.materials()["type"], (G.ROUGH_METAL, G.PLASTIC)).any()
 
 
 def test_the_cli_renders_the_shipped_scene(rtmi, tmp_path):
-    out = str(tmp_path / "glossy.ppm")
-    p = subprocess.run([os.path.join(PKG, "rtmi"), "-f", os.path.join(PKG, "scenes", "glossy_balls.json"), "-w", "64", "-h", "36", "-spp", "4",
-                        "-o", out, "--no-png", "--nee"], capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0, p.stderr[-2000:]
-    sc = rtmi.Scene.load(os.path.join(PKG, "scenes", "glossy_balls.json"))
-    sc.override(64, 36, 4)
-    sc.set_light_sampling(True)
-    st = rtmi.Stats()
-    img = sc.render(rtmi.Opts(), st)
-    assert st.kernel_variant & GS.NEE and np.isfinite(img).all() and img.mean() > 0
-    tokens = open(out).read().split()  # the reference's text PPM: P3, width, height, 255, then the 8-bit values
-    assert tokens[:4] == ["P3", "64", "36", "255"] and len(tokens) == 4 + 64 * 36 * 3
-    values = np.array(tokens[4:], np.int64)
-    assert values.min() >= 0 and values.max() <= 255 and values.max() > 0
+    PS.check_cli(rtmi, tmp_path, "glossy_balls.json", True, GS.NEE)
 
 
 def test_light_sampling_is_unbiased_against_the_plain_estimator(rtmi):

@@ -11,10 +11,6 @@ sample split and from the product library, the compact layouts refuse, and with 
 switch was never touched.
 
 Every case prints one row of figures (pytest -s); DESIGN 7n holds the rows measured on the MI355X."""
-import os
-import subprocess
-import sys
-import textwrap
 import zlib
 
 import numpy as np
@@ -27,9 +23,6 @@ import per_sample as PS
 import ref64 as R
 
 pytestmark = pytest.mark.gpu
-ROOT = PS.ROOT
-PKG = os.path.join(ROOT, "ray-tracing-in-cuda_amd")
-GENERAL_LAYOUTS = (16, 36, 44)
 
 
 @pytest.fixture(scope="module")
@@ -38,53 +31,28 @@ def rtmi():
 
 
 @pytest.fixture(scope="module")
-def words(rtmi):
-    return ML.inputs(rtmi)
+def inputs(rtmi):
+    return PS.input_cache(rtmi, ML)
 
 
 @pytest.fixture(scope="module")
-def cases(rtmi, words):
-    """name -> (scene, RefScene, kernel samples, (ref, stable, draws, tally of ref64)): rendered and traced once"""
-    made = {}
-
-    def of(name):
-        if name not in made:
-            sc = ML.scene(rtmi, name)
-            S = R.RefScene(sc)
-            st = rtmi.Stats()
-            sc.render(rtmi.Opts(seed=NS.REF_SEED, sample_count=1), st)
-            assert st.kernel_variant & ~ML.FAMILIES in GENERAL_LAYOUTS and st.kernel_variant & ML.FAMILIES == ML.family(name), st.kernel_variant
-            got = PS.kernel_samples(rtmi, sc, NS.REF_SEED, NS.REF_K, ML.FAMILIES, ML.family(name))
-            made[name] = (sc, S, got, R.reference(S, words))
-        return made[name]
-    return of
+def cases(rtmi, inputs):
+    """name -> (scene, RefScene, kernel samples, (ref, stable, draws, tally)): rendered and traced once, shared by the tests"""
+    return PS.case_cache(rtmi, ML, inputs)
 
 
 @pytest.mark.parametrize("name", list(ML.CASES))
-def test_kernel_against_fp64(rtmi, words, cases, name):
-    assert len(words) >= 16000
+def test_kernel_against_fp64(rtmi, inputs, cases, name):
     sc, S, got, (ref, stable, draws, tally) = cases(name)
-    assert draws.max() <= NS.REF_DRAWS, draws.max()
-    ML.check_contents(name, tally)
-    plain = ML.plain_twin(rtmi, name)
-    bref, bstable, _, _ = R.reference(R.RefScene(plain), words)
-    b = R.judge(PS.kernel_samples(rtmi, plain, NS.REF_SEED, NS.REF_K, ML.FAMILIES, 0), bref, bstable)
-    r32, _, _ = R.trace(S, words, dtype=np.float32)
-    j32 = R.judge(r32, ref, stable)
-    print(f"\n    fp32 NumPy within {100 * j32['share']:.3f} %; " + ", ".join(f"{k} {v}" for k, v in tally.items() if k in ML.TALLY_KEYS))
-    PS.assert_agreement(name, R.judge(got, ref, stable), b)                                # (a), (b), (c)
+    r32, _, _ = R.trace(S, inputs(name)[0], dtype=np.float32)
+    print(f"\n    fp32 NumPy within {100 * R.judge(r32, ref, stable)['share']:.3f} %; " + ", ".join(f"{k} {v}" for k, v in tally.items() if k in ML.TALLY_KEYS))
+    PS.check_kernel_against_fp64(rtmi, ML, inputs, cases, name)
 
 
 @pytest.mark.parametrize("name,mistake", [("lone triangle", "tri_no_sqrt"), ("lone triangle", "tri_vertex_normal"),
                                           (ML.MIXED, "tri_vertex_normal")])
-def test_a_wrong_reference_is_noticed(words, cases, name, mistake):
-    """against the kernel, a reference with one deliberate mistake of the triangle sample is far from 97 % (on the smooth mesh
-    the vertex normal is the triangle's own first vertex normal: the density must be stated with the geometric one)"""
-    sc, S, got, (ref, stable, _, _) = cases(name)
-    wrong, _, _ = R.trace(S, words, perturb=(mistake,))
-    good, bad = R.judge(got, ref, stable), R.judge(got, wrong, stable)
-    print(f"\n{name}, {mistake}: within tolerance {100 * good['share']:.2f} % -> {100 * bad['share']:.2f} %")
-    PS.assert_perturbation_noticed(good, bad)
+def test_a_wrong_reference_is_noticed(inputs, cases, name, mistake):
+    PS.check_a_mistake_fails_the_agreement(inputs, cases, name, mistake)
 
 
 def _mean(sc, img):
@@ -144,44 +112,9 @@ def test_unbiased_against_the_plain_estimator(rtmi):
     compare(seeds_of(rtmi, sc), b, "smooth mesh + rect + sphere, plain / mesh lights", c_max=7.0)
 
 
-_PRODUCT = textwrap.dedent("""
-    import os, sys
-    import numpy as np
-    sys.path.insert(0, %r)
-    sys.path.insert(0, os.path.join(%r, "tests"))
-    from __graft_entry__ import load_package
-    rtmi = load_package()
-    assert not rtmi.has_ablations()
-    import mesh_light_scenes as ML, nee_scenes as NS
-    for name in ("checker quad", ML.MIXED + ", env"):
-        st = rtmi.Stats()
-        img = ML.scene(rtmi, name).render(rtmi.Opts(seed=NS.REF_SEED, sample_count=NS.REF_K), st)
-        assert st.kernel_variant & ML.FAMILIES == ML.family(name), st.kernel_variant
-        np.save(os.path.join(sys.argv[1], name.replace(" ", "_") + ".npy"), img)
-""") % (ROOT, ROOT)
-
-
 def test_layouts_a_sample_split_and_the_product_library_give_the_same_bytes(rtmi, tmp_path):
-    env = dict(os.environ, RTMI_LIB=os.path.join(PKG, "librtmi_product.so"))
-    p = subprocess.run([sys.executable, "-c", _PRODUCT, str(tmp_path)], capture_output=True, text=True, env=env, timeout=600)
-    assert p.returncode == 0, p.stderr[-2000:]
-    for name in ("checker quad", ML.MIXED + ", env"):
-        sc, fam, seed, st = ML.scene(rtmi, name), ML.family(name), NS.REF_SEED, rtmi.Stats()
-        ref = sc.render(rtmi.Opts(seed=seed, sample_count=NS.REF_K), st)
-        assert st.kernel_variant & ML.FAMILIES == fam and st.kernel_variant & ~ML.FAMILIES in GENERAL_LAYOUTS
-        for variant in GENERAL_LAYOUTS:
-            got = sc.render(rtmi.Opts(seed=seed, sample_count=NS.REF_K, variant=variant), st)
-            assert st.kernel_variant == variant | fam, (variant, st.kernel_variant)
-            assert np.array_equal(got, ref), (name, variant, float(np.abs(got - ref).max()))
-        acc, _ = sc.accumulate(None, rtmi.Opts(seed=seed, sample_first=0, sample_count=5), st)
-        assert st.kernel_variant & ML.FAMILIES == fam
-        acc, img = sc.accumulate(acc, rtmi.Opts(seed=seed, sample_first=5, sample_count=NS.REF_K - 5), st)
-        assert np.array_equal(img, ref), (name, float(np.abs(img - ref).max()))
-        assert np.array_equal(np.load(str(tmp_path / (name.replace(" ", "_") + ".npy"))), ref), name
-    # the compact layouts list spheres for the sphere-only kernels: a scene with a light to sample is refused there
-    for variant in (2, 6):
-        with pytest.raises(rtmi.RtmiError):
-            ML.scene(rtmi, "lone triangle").render(rtmi.Opts(variant=variant))
+    PS.check_same_bytes(rtmi, ML, ("checker quad", ML.MIXED + ", env"), tmp_path)
+    PS.check_compact_layouts_refuse(rtmi, lambda: ML.scene(rtmi, "lone triangle"))  # (a scene with a light to sample)
 
 
 def test_switch_off_renders_the_bytes_of_a_scene_never_switched(rtmi):

@@ -13,11 +13,6 @@ Then what every feature keeps: the same bytes in every layout, through a sample 
 buffers; ray queries; the command line on the shipped scene; and light sampling against the plain estimator.
 
 Every case prints one row of figures (pytest -s); DESIGN 7o holds the rows measured on the MI355X."""
-import os
-import subprocess
-import sys
-import textwrap
-
 import numpy as np
 import pytest
 
@@ -28,9 +23,6 @@ import ref64 as R
 import ref64_noise as N
 
 pytestmark = pytest.mark.gpu
-ROOT = PS.ROOT
-PKG = os.path.join(ROOT, "ray-tracing-in-cuda_amd")
-GENERAL_LAYOUTS = (16, 36, 44)  # a scene with a noise texture runs the general (EXT) builds: never the compact layouts 2 / 6
 
 
 @pytest.fixture(scope="module")
@@ -40,107 +32,36 @@ def rtmi():
 
 @pytest.fixture(scope="module")
 def inputs(rtmi):
-    made = {}
-
-    def of(name):
-        key = (NSC.seed_of(name), NSC.family(name) == NSC.MOTION)
-        if key not in made:
-            made[key] = NSC.inputs(rtmi, name)
-        return made[key]
-    return of
+    return PS.input_cache(rtmi, NSC)
 
 
 @pytest.fixture(scope="module")
 def cases(rtmi, inputs):
-    """name -> (scene, RefScene, kernel samples, (ref, stable, draws, tally), noise tally): rendered and traced once, shared"""
-    made = {}
-
-    def of(name):
-        if name not in made:
-            words, shutter = inputs(name)
-            sc = NSC.scene(rtmi, name)
-            S = R.RefScene(sc)
-            st = rtmi.Stats()
-            sc.render(rtmi.Opts(seed=NSC.seed_of(name), sample_count=1), st)
-            layouts = (NSC.NESTED_LAYOUT,) if name == "noise_nested" else GENERAL_LAYOUTS
-            assert st.kernel_variant & ~NSC.FAMILIES in layouts and st.kernel_variant & NSC.FAMILIES == NSC.family(name), st.kernel_variant
-            got = PS.kernel_samples(rtmi, sc, NSC.seed_of(name), NS.REF_K, NSC.FAMILIES, NSC.family(name))
-            ref = R.reference(S, words, shutter)
-            made[name] = (sc, S, got, ref, {k: v for k, v in ref[3].items() if k.startswith("noise_")})
-        return made[name]
-    return of
+    """name -> (scene, RefScene, kernel samples, (ref, stable, draws, tally)): rendered and traced once, shared by the tests"""
+    return PS.case_cache(rtmi, NSC, inputs, nested=("noise_nested",))
 
 
 @pytest.mark.parametrize("name", list(NSC.CASES))
 def test_kernel_against_fp64(rtmi, inputs, cases, name):
-    words, shutter = inputs(name)
-    assert len(words) >= 16000
-    sc, S, got, (ref, stable, draws, tally), noise_tally = cases(name)
-    assert draws.max() <= NS.REF_DRAWS, draws.max()                                        # (d)
-    NSC.check_contents(name, noise_tally)
-    plain = NSC.plain_twin(rtmi, name)
-    bref, bstable, _, _ = R.reference(R.RefScene(plain), words)
-    b = R.judge(PS.kernel_samples(rtmi, plain, NSC.seed_of(name), NS.REF_K, NSC.FAMILIES, 0), bref, bstable)
-    PS.assert_agreement(name, R.judge(got, ref, stable), b)                                # (a), (b), (c)
-    print("    " + ", ".join(f"{k} {v}" for k, v in noise_tally.items() if v))
+    PS.check_kernel_against_fp64(rtmi, NSC, inputs, cases, name)
+    print("    " + ", ".join(f"{k} {v}" for k, v in cases(name)[3][3].items() if k.startswith("noise_") and v))
 
 
 @pytest.mark.parametrize("name,mistake", [("noise_sky", "noise_cubic_fade"), ("noise_sky", "noise_same_seed"), ("noise_lights", "noise_wrong_axis")])
 def test_a_mistake_fails_the_agreement(inputs, cases, name, mistake):
-    """(d): against the kernel, a reference with one deliberate mistake of the model is far from 97 %"""
-    words, shutter = inputs(name)
-    sc, S, got, (ref, stable, _, _), _ = cases(name)
-    wrong, _, _ = R.trace(S, words, shutter=shutter, perturb=(mistake,))
-    good, bad = R.judge(got, ref, stable), R.judge(got, wrong, stable)
-    print(f"\n{name}, {mistake}: within tolerance {100 * good['share']:.2f} % -> {100 * bad['share']:.2f} %")
-    PS.assert_perturbation_noticed(good, bad)
-
-
-_PRODUCT = textwrap.dedent("""
-    import os, sys
-    import numpy as np
-    sys.path.insert(0, %r)
-    sys.path.insert(0, os.path.join(%r, "tests"))
-    from __graft_entry__ import load_package
-    rtmi = load_package()
-    assert not rtmi.has_ablations()
-    import noise_scenes as NSC, nee_scenes as NS
-    for name in ("noise_sky", "noise_lights"):
-        st = rtmi.Stats()
-        img = NSC.scene(rtmi, name).render(rtmi.Opts(seed=NSC.seed_of(name), sample_count=NS.REF_K), st)
-        assert st.kernel_variant & NSC.FAMILIES == NSC.family(name), st.kernel_variant
-        np.save(os.path.join(sys.argv[1], name + ".npy"), img)
-""") % (ROOT, ROOT)
+    PS.check_a_mistake_fails_the_agreement(inputs, cases, name, mistake)
 
 
 def test_layouts_a_sample_split_and_the_product_library_give_the_same_bytes(rtmi, tmp_path):
-    env = dict(os.environ, RTMI_LIB=os.path.join(PKG, "librtmi_product.so"))
-    p = subprocess.run([sys.executable, "-c", _PRODUCT, str(tmp_path)], capture_output=True, text=True, env=env, timeout=600)
-    assert p.returncode == 0, p.stderr[-2000:]
-    for name in ("noise_sky", "noise_lights"):
-        sc, fam, seed, st = NSC.scene(rtmi, name), NSC.family(name), NSC.seed_of(name), rtmi.Stats()
-        ref = sc.render(rtmi.Opts(seed=seed, sample_count=NS.REF_K), st)
-        assert st.kernel_variant & NSC.FAMILIES == fam and st.kernel_variant & ~NSC.FAMILIES in GENERAL_LAYOUTS
-        for variant in GENERAL_LAYOUTS:
-            got = sc.render(rtmi.Opts(seed=seed, sample_count=NS.REF_K, variant=variant), st)
-            assert st.kernel_variant == variant | fam, (variant, st.kernel_variant)
-            assert np.array_equal(got, ref), (name, variant, float(np.abs(got - ref).max()))
-        acc, _ = sc.accumulate(None, rtmi.Opts(seed=seed, sample_first=0, sample_count=5), st)
-        assert st.kernel_variant & NSC.FAMILIES == fam
-        acc, img = sc.accumulate(acc, rtmi.Opts(seed=seed, sample_first=5, sample_count=NS.REF_K - 5), st)
-        assert np.array_equal(img, ref), (name, float(np.abs(img - ref).max()))
-        assert np.array_equal(np.load(str(tmp_path / (name + ".npy"))), ref), name
+    PS.check_same_bytes(rtmi, NSC, ("noise_sky", "noise_lights"), tmp_path)
     # the nested clump: its own layout against the flat wide-table walk of the same scene
     sc, st = NSC.scene(rtmi, "noise_nested"), rtmi.Stats()
     nested = sc.render(rtmi.Opts(seed=NS.REF_SEED, sample_count=NS.REF_K), st)
     assert st.kernel_variant == NSC.NESTED_LAYOUT
     sc.set_nested_grid(False)
     flat = sc.render(rtmi.Opts(seed=NS.REF_SEED, sample_count=NS.REF_K), st)
-    assert st.kernel_variant in GENERAL_LAYOUTS and np.array_equal(nested, flat)
-    # the compact layouts list spheres for the sphere-only kernels, which know no noise texture: refused
-    for variant in (2, 6):
-        with pytest.raises(rtmi.RtmiError):
-            NSC.scene(rtmi, "noise_sky").render(rtmi.Opts(variant=variant))
+    assert st.kernel_variant in PS.GENERAL_LAYOUTS and np.array_equal(nested, flat)
+    PS.check_compact_layouts_refuse(rtmi, lambda: NSC.scene(rtmi, "noise_sky"))
 
 
 def test_feature_buffers_show_the_first_vertex(rtmi, inputs):
@@ -171,34 +92,15 @@ def test_feature_buffers_show_the_first_vertex(rtmi, inputs):
 
 def test_ray_queries_report_the_twins_records(rtmi):
     """Scene.trace on noise_sky returns the records of its solid-colour twin: a query never looks at a texture"""
-    import trace_cases as TC
     sc, twin = NSC.scene(rtmi, "noise_sky"), NSC.scene(rtmi, "noise_sky", noise=False)
-    boxes = [TC.prim_box(p) for p in sc.prims()[1:]]  # (every primitive but the far floor)
-    lo, hi = np.min([b[0] for b in boxes], axis=0), np.max([b[1] for b in boxes], axis=0)
-    o, d = TC.make_rays(lo, hi)
-    a, b = sc.trace(o, d), twin.trace(o, d)
-    assert (a["prim"] >= 0).sum() >= 500
-    assert a.tobytes() == b.tobytes()
-    tex = sc.textures()["type"][sc.materials()["texture"][a["material"][a["prim"] >= 0]]]
+    a, hit = PS.check_ray_queries_of_twins(sc, twin, lambda prims: prims[1:])  # (every primitive but the far floor)
+    tex = sc.textures()["type"][sc.materials()["texture"][a["material"][hit]]]
     assert (tex == N.NOISE).sum() >= 300 and not (twin.textures()["type"] == N.NOISE).any()
 
 
 @pytest.mark.parametrize("nee", [False, True], ids=["plain", "nee"])
 def test_the_cli_renders_the_shipped_scene(rtmi, tmp_path, nee):
-    out = str(tmp_path / "marble.ppm")
-    p = subprocess.run([os.path.join(PKG, "rtmi"), "-f", os.path.join(PKG, "scenes", "marble_hall.json"), "-w", "64", "-h", "36", "-spp", "4",
-                        "-o", out, "--no-png"] + (["--nee"] if nee else []), capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0, p.stderr[-2000:]
-    sc = rtmi.Scene.load(os.path.join(PKG, "scenes", "marble_hall.json"))
-    sc.override(64, 36, 4)
-    sc.set_light_sampling(nee)
-    st = rtmi.Stats()
-    img = sc.render(rtmi.Opts(), st)
-    assert bool(st.kernel_variant & NSC.NEE) == nee and np.isfinite(img).all() and img.mean() > 0
-    tokens = open(out).read().split()  # the reference's text PPM: P3, width, height, 255, then the 8-bit values
-    assert tokens[:4] == ["P3", "64", "36", "255"] and len(tokens) == 4 + 64 * 36 * 3
-    values = np.array(tokens[4:], np.int64)
-    assert values.min() >= 0 and values.max() <= 255 and values.max() > 0
+    PS.check_cli(rtmi, tmp_path, "marble_hall.json", nee, NSC.NEE)
 
 
 def test_light_sampling_is_unbiased_against_the_plain_estimator(rtmi):

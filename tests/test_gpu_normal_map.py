@@ -17,11 +17,6 @@ refusals; the nested grid; the feature buffers; ray queries; the command line on
 the plain estimator.
 
 Every case prints one row of figures (pytest -s); DESIGN 7u holds the rows measured on the MI355X."""
-import os
-import subprocess
-import sys
-import textwrap
-
 import numpy as np
 import pytest
 
@@ -29,13 +24,8 @@ import nee_scenes as NS
 import normal_map_scenes as NMS
 import per_sample as PS
 import ref64 as R
-import ref64_normal_map as NM
 
 pytestmark = pytest.mark.gpu
-ROOT = PS.ROOT
-PKG = os.path.join(ROOT, "ray-tracing-in-cuda_amd")
-GENERAL_LAYOUTS = (16, 36, 44)  # a scene with a map runs the general (EXT) builds: never the compact layouts 2 / 6
-NESTED_LAYOUT = 52
 
 
 @pytest.fixture(scope="module")
@@ -45,59 +35,25 @@ def rtmi():
 
 @pytest.fixture(scope="module")
 def inputs(rtmi):
-    made = {}
-
-    def of(name):
-        key = (NMS.seed_of(name), NMS.family(name) == NMS.MOTION)
-        if key not in made:
-            made[key] = NMS.inputs(rtmi, name)
-        return made[key]
-    return of
+    return PS.input_cache(rtmi, NMS)
 
 
 @pytest.fixture(scope="module")
 def cases(rtmi, inputs):
-    """name -> (scene, RefScene, kernel samples, (ref, stable, draws, tally), map tally): rendered and traced once, shared"""
-    made = {}
-
-    def of(name):
-        if name not in made:
-            words, shutter = inputs(name)
-            sc = NMS.scene(rtmi, name)
-            S = R.RefScene(sc)
-            st = rtmi.Stats()
-            sc.render(rtmi.Opts(seed=NMS.seed_of(name), sample_count=1), st)
-            assert st.kernel_variant & ~NMS.FAMILIES in GENERAL_LAYOUTS and st.kernel_variant & NMS.FAMILIES == NMS.family(name), st.kernel_variant
-            got = PS.kernel_samples(rtmi, sc, NMS.seed_of(name), NS.REF_K, NMS.FAMILIES, NMS.family(name))
-            ref = R.reference(S, words, shutter)
-            made[name] = (sc, S, got, ref, {k: v for k, v in ref[3].items() if k.startswith("nm_")})
-        return made[name]
-    return of
+    """name -> (scene, RefScene, kernel samples, (ref, stable, draws, tally)): rendered and traced once, shared by the tests"""
+    return PS.case_cache(rtmi, NMS, inputs)
 
 
 @pytest.mark.parametrize("name", list(NMS.CASES))
 def test_kernel_against_fp64(rtmi, inputs, cases, name):
-    words, shutter = inputs(name)
-    assert len(words) >= 16000
-    sc, S, got, (ref, stable, draws, tally), map_tally = cases(name)
-    assert draws.max() <= NS.REF_DRAWS, draws.max()                                        # (d)
+    map_tally = {k: v for k, v in cases(name)[3][3].items() if k.startswith("nm_")}
     print("\n    " + ", ".join(f"{k} {v if isinstance(v, int) else round(v, 3)}" for k, v in map_tally.items() if v))
-    NMS.check_contents(name, map_tally)
-    plain = NMS.plain_twin(rtmi, name)
-    bref, bstable, _, _ = R.reference(R.RefScene(plain), words)
-    b = R.judge(PS.kernel_samples(rtmi, plain, NMS.seed_of(name), NS.REF_K, NMS.FAMILIES, 0), bref, bstable)
-    PS.assert_agreement(name, R.judge(got, ref, stable), b)                                # (a), (b), (c)
+    PS.check_kernel_against_fp64(rtmi, NMS, inputs, cases, name)
 
 
 @pytest.mark.parametrize("name,mistake", NMS.MISTAKES)
 def test_a_mistake_fails_the_agreement(inputs, cases, name, mistake):
-    """(d): against the kernel, a reference with one deliberate mistake of the model is far from 97 %"""
-    words, shutter = inputs(name)
-    sc, S, got, (ref, stable, _, _), _ = cases(name)
-    wrong, _, _ = R.trace(S, words, shutter=shutter, perturb=(mistake,))
-    good, bad = R.judge(got, ref, stable), R.judge(got, wrong, stable)
-    print(f"\n{name}, {mistake}: within tolerance {100 * good['share']:.2f} % -> {100 * bad['share']:.2f} %")
-    PS.assert_perturbation_noticed(good, bad)
+    PS.check_a_mistake_fails_the_agreement(inputs, cases, name, mistake)
 
 
 @pytest.mark.parametrize("name", ["nm_sky", "nm_lights"])
@@ -108,7 +64,7 @@ def test_a_constant_map_renders_the_twins_bytes(rtmi, name):
     assert sum(still.normal_map(m) is not None for m in range(len(still.materials()))) >= 4
     assert still.table_image().tobytes() != twin.table_image().tobytes()
     st = rtmi.Stats()
-    for variant in GENERAL_LAYOUTS:
+    for variant in PS.GENERAL_LAYOUTS:
         o = rtmi.Opts(seed=NMS.seed_of(name), sample_count=NS.REF_K, variant=variant)
         a = still.render(o, st)
         assert st.kernel_variant == variant | NMS.family(name), (variant, st.kernel_variant)
@@ -118,40 +74,8 @@ def test_a_constant_map_renders_the_twins_bytes(rtmi, name):
     assert not np.array_equal(NMS.scene(rtmi, name).render(rtmi.Opts(seed=NMS.seed_of(name), sample_count=NS.REF_K), st), b)  # (a relief shows)
 
 
-_PRODUCT = textwrap.dedent("""
-    import os, sys
-    import numpy as np
-    sys.path.insert(0, %r)
-    sys.path.insert(0, os.path.join(%r, "tests"))
-    from __graft_entry__ import load_package
-    rtmi = load_package()
-    assert not rtmi.has_ablations()
-    import normal_map_scenes as NMS, nee_scenes as NS
-    for name in ("nm_sky", "nm_lights"):
-        st = rtmi.Stats()
-        img = NMS.scene(rtmi, name).render(rtmi.Opts(seed=NMS.seed_of(name), sample_count=NS.REF_K), st)
-        assert st.kernel_variant & NMS.FAMILIES == NMS.family(name), st.kernel_variant
-        np.save(os.path.join(sys.argv[1], name + ".npy"), img)
-""") % (ROOT, ROOT)
-
-
 def test_layouts_a_sample_split_and_the_product_library_give_the_same_bytes(rtmi, tmp_path):
-    env = dict(os.environ, RTMI_LIB=os.path.join(PKG, "librtmi_product.so"))
-    p = subprocess.run([sys.executable, "-c", _PRODUCT, str(tmp_path)], capture_output=True, text=True, env=env, timeout=600)
-    assert p.returncode == 0, p.stderr[-2000:]
-    for name in ("nm_sky", "nm_lights"):
-        sc, fam, seed, st = NMS.scene(rtmi, name), NMS.family(name), NMS.seed_of(name), rtmi.Stats()
-        ref = sc.render(rtmi.Opts(seed=seed, sample_count=NS.REF_K), st)
-        assert st.kernel_variant & NMS.FAMILIES == fam and st.kernel_variant & ~NMS.FAMILIES in GENERAL_LAYOUTS
-        for variant in GENERAL_LAYOUTS:
-            got = sc.render(rtmi.Opts(seed=seed, sample_count=NS.REF_K, variant=variant), st)
-            assert st.kernel_variant == variant | fam, (variant, st.kernel_variant)
-            assert np.array_equal(got, ref), (name, variant, float(np.abs(got - ref).max()))
-        acc, _ = sc.accumulate(None, rtmi.Opts(seed=seed, sample_first=0, sample_count=5), st)
-        assert st.kernel_variant & NMS.FAMILIES == fam
-        acc, img = sc.accumulate(acc, rtmi.Opts(seed=seed, sample_first=5, sample_count=NS.REF_K - 5), st)
-        assert np.array_equal(img, ref), (name, float(np.abs(img - ref).max()))
-        assert np.array_equal(np.load(str(tmp_path / (name + ".npy"))), ref), name
+    PS.check_same_bytes(rtmi, NMS, ("nm_sky", "nm_lights"), tmp_path)
 
 
 def test_refusals(rtmi):
@@ -175,12 +99,12 @@ def test_the_nested_grid_renders_the_same_bytes(rtmi):
     sc = NMS.nested(rtmi)
     assert sc.nested_info().cells > 0
     nested = sc.render(rtmi.Opts(seed=NS.REF_SEED, sample_count=NS.REF_K), st)
-    assert st.kernel_variant == NESTED_LAYOUT
+    assert st.kernel_variant == PS.NESTED_LAYOUT
     twin = NMS.nested(rtmi, maps=False).render(rtmi.Opts(seed=NS.REF_SEED, sample_count=NS.REF_K), st)
     assert not np.array_equal(nested, twin)  # (the maps show)
     sc.set_nested_grid(False)
     flat = sc.render(rtmi.Opts(seed=NS.REF_SEED, sample_count=NS.REF_K), st)
-    assert st.kernel_variant in GENERAL_LAYOUTS and np.array_equal(nested, flat)
+    assert st.kernel_variant in PS.GENERAL_LAYOUTS and np.array_equal(nested, flat)
 
 
 def test_feature_buffers_show_the_mapped_normal(rtmi, inputs):
@@ -218,35 +142,16 @@ def test_feature_buffers_show_the_mapped_normal(rtmi, inputs):
 
 def test_ray_queries_report_the_twins_records(rtmi):
     """Scene.trace on nm_prims returns the records of its twin without maps: queries are for geometry"""
-    import trace_cases as TC
     sc, twin = NMS.scene(rtmi, "nm_prims"), NMS.scene(rtmi, "nm_prims", maps=False)
-    boxes = [TC.prim_box(p) for p in sc.prims()[1:] if int(p["type"]) != 6]  # (every primitive but the far floor; the box's faces lie among them)
-    lo, hi = np.min([b[0] for b in boxes], axis=0), np.max([b[1] for b in boxes], axis=0)
-    o, d = TC.make_rays(lo, hi)
-    a, b = sc.trace(o, d), twin.trace(o, d)
-    hit = a["prim"] >= 0
-    assert hit.sum() >= 500
-    assert a.tobytes() == b.tobytes()
+    # (every primitive but the far floor; the box's faces lie among them)
+    a, hit = PS.check_ray_queries_of_twins(sc, twin, lambda prims: [p for p in prims[1:] if int(p["type"]) != 6])
     assert sum(sc.normal_map(int(m)) is not None for m in a["material"][hit]) >= 300
 
 
 @pytest.mark.parametrize("nee", [False, True], ids=["plain", "nee"])
 def test_the_cli_renders_the_shipped_scene(rtmi, tmp_path, nee):
-    out = str(tmp_path / "wall.ppm")
-    p = subprocess.run([os.path.join(PKG, "rtmi"), "-f", os.path.join(PKG, "scenes", "normal_map_wall.json"), "-w", "64", "-h", "36", "-spp", "4",
-                        "-o", out, "--no-png"] + (["--nee"] if nee else []), capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0, p.stderr[-2000:]
-    sc = rtmi.Scene.load(os.path.join(PKG, "scenes", "normal_map_wall.json"))
-    assert sum(sc.normal_map(m) is not None for m in range(len(sc.materials()))) >= 5
-    sc.override(64, 36, 4)
-    sc.set_light_sampling(nee)
-    st = rtmi.Stats()
-    img = sc.render(rtmi.Opts(), st)
-    assert bool(st.kernel_variant & NMS.NEE) == nee and np.isfinite(img).all() and img.mean() > 0
-    tokens = open(out).read().split()  # the reference's text PPM: P3, width, height, 255, then the 8-bit values
-    assert tokens[:4] == ["P3", "64", "36", "255"] and len(tokens) == 4 + 64 * 36 * 3
-    values = np.array(tokens[4:], np.int64)
-    assert values.min() >= 0 and values.max() <= 255 and values.max() > 0
+    PS.check_cli(rtmi, tmp_path, "normal_map_wall.json", nee, NMS.NEE,
+                 loaded=lambda sc: sum(sc.normal_map(m) is not None for m in range(len(sc.materials()))) >= 5)
 
 
 def test_light_sampling_is_unbiased_against_the_plain_estimator(rtmi):

@@ -12,11 +12,6 @@ every layout, through a sample split and from the product library; the albedo fe
 families; the command line on the shipped scene.
 
 Every case prints one row of figures (pytest -s); DESIGN 7t holds the rows measured on the MI355X."""
-import os
-import subprocess
-import sys
-import textwrap
-
 import numpy as np
 import pytest
 
@@ -27,9 +22,6 @@ import ref64 as R
 import ref64_pbr as RP
 
 pytestmark = pytest.mark.gpu
-ROOT = PS.ROOT
-PKG = os.path.join(ROOT, "ray-tracing-in-cuda_amd")
-GENERAL_LAYOUTS = (16, 36, 44)  # a scene with a pbr material runs the general (EXT) builds: never the compact layouts 2 / 6
 
 
 @pytest.fixture(scope="module")
@@ -38,49 +30,30 @@ def rtmi():
 
 
 @pytest.fixture(scope="module")
-def words(rtmi):
-    return PBS.inputs(rtmi)
+def inputs(rtmi):
+    return PS.input_cache(rtmi, PBS)
 
 
 @pytest.fixture(scope="module")
-def cases(rtmi, words):
-    """name -> (scene, RefScene, kernel samples, (ref, stable, draws, tally)): rendered and traced once, shared by the tests"""
-    made = {}
+def words(inputs):
+    return inputs("room")[0]
 
-    def of(name):
-        if name not in made:
-            sc = PBS.scene(rtmi, name)
-            S = R.RefScene(sc)
-            st = rtmi.Stats()
-            sc.render(rtmi.Opts(seed=NS.REF_SEED, sample_count=1), st)
-            assert st.kernel_variant & ~PBS.FAMILIES in GENERAL_LAYOUTS and st.kernel_variant & PBS.FAMILIES == PBS.family(name), st.kernel_variant
-            got = PS.kernel_samples(rtmi, sc, NS.REF_SEED, NS.REF_K, PBS.FAMILIES, PBS.family(name))
-            made[name] = (sc, S, got, R.reference(S, words))
-        return made[name]
-    return of
+
+@pytest.fixture(scope="module")
+def cases(rtmi, inputs):
+    """name -> (scene, RefScene, kernel samples, (ref, stable, draws, tally)): rendered and traced once, shared by the tests"""
+    return PS.case_cache(rtmi, PBS, inputs)
 
 
 @pytest.mark.parametrize("name", list(PBS.CASES))
-def test_kernel_against_fp64(rtmi, words, cases, name):
-    assert len(words) >= 16000
-    sc, S, got, (ref, stable, draws, tally) = cases(name)
-    assert draws.max() <= NS.REF_DRAWS, draws.max()                                        # (d)
-    PBS.check_contents(name, tally)
-    plain = PBS.plain_twin(rtmi, name)
-    bref, bstable, _, _ = R.reference(R.RefScene(plain), words)
-    b = R.judge(PS.kernel_samples(rtmi, plain, NS.REF_SEED, NS.REF_K, PBS.FAMILIES, 0), bref, bstable)
-    PS.assert_agreement(name, R.judge(got, ref, stable), b)                                # (a), (b), (c)
-    print("    " + ", ".join(f"{k[4:]} {v}" for k, v in tally.items() if k.startswith("pbr_") and v))
+def test_kernel_against_fp64(rtmi, inputs, cases, name):
+    PS.check_kernel_against_fp64(rtmi, PBS, inputs, cases, name)
+    print("    " + ", ".join(f"{k[4:]} {v}" for k, v in cases(name)[3][3].items() if k.startswith("pbr_") and v))
 
 
 @pytest.mark.parametrize("name,mistake", PBS.MISTAKES)
-def test_a_mistake_fails_the_agreement(words, cases, name, mistake):
-    """(d): against the kernel, a reference with one deliberate mistake of the model is far from 97 %"""
-    sc, S, got, (ref, stable, _, _) = cases(name)
-    wrong, _, _ = R.trace(S, words, perturb=(mistake,))
-    good, bad = R.judge(got, ref, stable), R.judge(got, wrong, stable)
-    print(f"\n{name}, {mistake}: within tolerance {100 * good['share']:.2f} % -> {100 * bad['share']:.2f} %")
-    PS.assert_perturbation_noticed(good, bad)
+def test_a_mistake_fails_the_agreement(inputs, cases, name, mistake):
+    PS.check_a_mistake_fails_the_agreement(inputs, cases, name, mistake)
 
 
 def test_m0_against_unmodified_ref64_on_the_plastic_twin(rtmi, words):
@@ -152,44 +125,9 @@ def test_known_answer_a_checker_map_is_its_two_constant_materials(rtmi):
     assert abs(frames["even"][:, one_tile].mean() - frames["odd"][:, one_tile].mean()) > 0.01
 
 
-_PRODUCT = textwrap.dedent("""
-    import os, sys
-    import numpy as np
-    sys.path.insert(0, %r)
-    sys.path.insert(0, os.path.join(%r, "tests"))
-    from __graft_entry__ import load_package
-    rtmi = load_package()
-    assert not rtmi.has_ablations()
-    import pbr_scenes as PBS, nee_scenes as NS
-    for name in ("room", "maps under an environment"):
-        st = rtmi.Stats()
-        img = PBS.scene(rtmi, name).render(rtmi.Opts(seed=NS.REF_SEED, sample_count=NS.REF_K), st)
-        assert st.kernel_variant & PBS.FAMILIES == PBS.family(name), st.kernel_variant
-        np.save(os.path.join(sys.argv[1], name.replace(" ", "_") + ".npy"), img)
-""") % (ROOT, ROOT)
-
-
 def test_layouts_a_sample_split_and_the_product_library_give_the_same_bytes(rtmi, tmp_path):
-    env = dict(os.environ, RTMI_LIB=os.path.join(PKG, "librtmi_product.so"))
-    p = subprocess.run([sys.executable, "-c", _PRODUCT, str(tmp_path)], capture_output=True, text=True, env=env, timeout=600)
-    assert p.returncode == 0, p.stderr[-2000:]
-    for name in ("room", "maps under an environment"):
-        sc, fam, seed, st = PBS.scene(rtmi, name), PBS.family(name), NS.REF_SEED, rtmi.Stats()
-        ref = sc.render(rtmi.Opts(seed=seed, sample_count=NS.REF_K), st)
-        assert st.kernel_variant & PBS.FAMILIES == fam and st.kernel_variant & ~PBS.FAMILIES in GENERAL_LAYOUTS
-        for variant in GENERAL_LAYOUTS:
-            got = sc.render(rtmi.Opts(seed=seed, sample_count=NS.REF_K, variant=variant), st)
-            assert st.kernel_variant == variant | fam, (variant, st.kernel_variant)
-            assert np.array_equal(got, ref), (name, variant, float(np.abs(got - ref).max()))
-        acc, _ = sc.accumulate(None, rtmi.Opts(seed=seed, sample_first=0, sample_count=5), st)
-        assert st.kernel_variant & PBS.FAMILIES == fam
-        acc, img = sc.accumulate(acc, rtmi.Opts(seed=seed, sample_first=5, sample_count=NS.REF_K - 5), st)
-        assert np.array_equal(img, ref), (name, float(np.abs(img - ref).max()))
-        assert np.array_equal(np.load(str(tmp_path / (name.replace(" ", "_") + ".npy"))), ref), name
-    # the compact layouts list spheres for the sphere-only kernels, which carry no pbr material: refused
-    for variant in (2, 6):
-        with pytest.raises(rtmi.RtmiError):
-            PBS.scene(rtmi, "room").render(rtmi.Opts(variant=variant))
+    PS.check_same_bytes(rtmi, PBS, ("room", "maps under an environment"), tmp_path)
+    PS.check_compact_layouts_refuse(rtmi, lambda: PBS.scene(rtmi, "room"))
 
 
 def test_the_albedo_feature_shows_the_bytes(rtmi, words):
@@ -212,14 +150,9 @@ def test_the_albedo_feature_shows_the_bytes(rtmi, words):
 
 
 def test_ray_queries_are_unchanged_by_swapping_plastic_for_pbr(rtmi):
-    import trace_cases as TC
     sc, twin = PBS.grid_scene(rtmi, "pbr0"), PBS.grid_scene(rtmi, "plastic")
-    boxes = [TC.prim_box(p) for p in sc.prims() if int(p["type"]) != R.XZ_RECT]
-    lo, hi = np.min([b[0] for b in boxes], axis=0), np.max([b[1] for b in boxes], axis=0)
-    o, d = TC.make_rays(lo, hi)
-    a, b = sc.trace(o, d), twin.trace(o, d)
-    assert (a["prim"] >= 0).sum() >= 500 and a.tobytes() == b.tobytes()
-    assert RP.PBR in set(np.unique(sc.materials()["type"][a["material"][a["prim"] >= 0]]))
+    a, hit = PS.check_ray_queries_of_twins(sc, twin, lambda prims: [p for p in prims if int(p["type"]) != R.XZ_RECT])
+    assert RP.PBR in set(np.unique(sc.materials()["type"][a["material"][hit]]))
 
 
 @pytest.mark.parametrize("family", ["media", "motion"])
@@ -239,17 +172,4 @@ def test_a_pbr_scene_renders_in_the_media_and_motion_families(rtmi, family):
 
 @pytest.mark.parametrize("nee", [False, True], ids=["plain", "nee"])
 def test_the_cli_renders_the_shipped_scene(rtmi, tmp_path, nee):
-    out = str(tmp_path / "wear.ppm")
-    p = subprocess.run([os.path.join(PKG, "rtmi"), "-f", os.path.join(PKG, "scenes", "pbr_wear.json"), "-w", "64", "-h", "36", "-spp", "4",
-                        "-o", out, "--no-png"] + (["--nee"] if nee else []), capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0, p.stderr[-2000:]
-    sc = rtmi.Scene.load(os.path.join(PKG, "scenes", "pbr_wear.json"))
-    sc.override(64, 36, 4)
-    sc.set_light_sampling(nee)
-    st = rtmi.Stats()
-    img = sc.render(rtmi.Opts(), st)
-    assert bool(st.kernel_variant & PBS.NEE) == nee and np.isfinite(img).all() and img.mean() > 0
-    tokens = open(out).read().split()  # the reference's text PPM: P3, width, height, 255, then the 8-bit values
-    assert tokens[:4] == ["P3", "64", "36", "255"] and len(tokens) == 4 + 64 * 36 * 3
-    values = np.array(tokens[4:], np.int64)
-    assert values.min() >= 0 and values.max() <= 255 and values.max() > 0
+    PS.check_cli(rtmi, tmp_path, "pbr_wear.json", nee, PBS.NEE)

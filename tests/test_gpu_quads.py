@@ -10,11 +10,6 @@ quad pixels; ray queries on arbitrary rays against fp64; light sampling against 
 shipped scene.
 
 Every case prints one row of figures (pytest -s); DESIGN 7q holds the rows measured on the MI355X."""
-import os
-import subprocess
-import sys
-import textwrap
-
 import numpy as np
 import pytest
 
@@ -24,9 +19,6 @@ import quad_scenes as Q
 import ref64 as R
 
 pytestmark = pytest.mark.gpu
-ROOT = PS.ROOT
-PKG = os.path.join(ROOT, "ray-tracing-in-cuda_amd")
-GENERAL_LAYOUTS = (16, 36, 44)
 
 
 @pytest.fixture(scope="module")
@@ -36,91 +28,29 @@ def rtmi():
 
 @pytest.fixture(scope="module")
 def inputs(rtmi):
-    made = {}
-
-    def of(name):
-        key = Q.seed_of(name), Q.family(name) == Q.MOTION
-        if key not in made:
-            made[key] = Q.inputs(rtmi, name)
-        return made[key]
-    return of
+    return PS.input_cache(rtmi, Q)
 
 
 @pytest.fixture(scope="module")
 def cases(rtmi, inputs):
-    """name -> (scene, RefScene, kernel samples, (ref, stable, draws, tally of ref64)): rendered and traced once"""
-    made = {}
-
-    def of(name):
-        if name not in made:
-            sc = Q.scene(rtmi, name)
-            S = R.RefScene(sc)
-            words, shutter = inputs(name)
-            got = PS.kernel_samples(rtmi, sc, Q.seed_of(name), NS.REF_K, Q.FAMILIES, Q.family(name))
-            made[name] = (sc, S, got, R.reference(S, words, shutter))
-        return made[name]
-    return of
+    """name -> (scene, RefScene, kernel samples, (ref, stable, draws, tally)): rendered and traced once, shared by the tests"""
+    return PS.case_cache(rtmi, Q, inputs)
 
 
 @pytest.mark.parametrize("name", list(Q.CASES))
 def test_kernel_against_fp64(rtmi, inputs, cases, name):
-    sc, S, got, (ref, stable, draws, tally) = cases(name)
-    words, shutter = inputs(name)
-    assert len(words) >= 16000 and draws.max() <= NS.REF_DRAWS, draws.max()
-    Q.check_contents(name, tally)
-    plain = Q.plain_twin(rtmi, name)
-    assert not (plain.prims()["type"] == Q.QUAD).any()
-    bref, bstable, _, _ = R.reference(R.RefScene(plain), words)
-    b = R.judge(PS.kernel_samples(rtmi, plain, Q.seed_of(name), NS.REF_K, Q.FAMILIES, 0), bref, bstable)
-    print("\n    " + ", ".join(f"{k} {tally[k]}" for k in Q.CASES[name][3]))
-    PS.assert_agreement(name, R.judge(got, ref, stable), b)                                # (a), (b), (c)
+    assert not (Q.plain_twin(rtmi, name).prims()["type"] == Q.QUAD).any()
+    print("\n    " + ", ".join(f"{k} {cases(name)[3][3][k]}" for k in Q.CASES[name][3]))
+    PS.check_kernel_against_fp64(rtmi, Q, inputs, cases, name)
 
 
 @pytest.mark.parametrize("name,mistake", Q.MISTAKES)
 def test_a_wrong_reference_is_noticed(inputs, cases, name, mistake):
-    """(d): against the kernel, a reference with one deliberate mistake is far from 97 %"""
-    sc, S, got, (ref, stable, _, _) = cases(name)
-    words, shutter = inputs(name)
-    wrong, _, _ = R.trace(S, words, shutter=shutter, perturb=(mistake,))
-    good, bad = R.judge(got, ref, stable), R.judge(got, wrong, stable)
-    print(f"\n{name}, {mistake}: within tolerance {100 * good['share']:.2f} % -> {100 * bad['share']:.2f} %")
-    PS.assert_perturbation_noticed(good, bad)
-
-
-_PRODUCT = textwrap.dedent("""
-    import os, sys
-    import numpy as np
-    sys.path.insert(0, %r)
-    sys.path.insert(0, os.path.join(%r, "tests"))
-    from __graft_entry__ import load_package
-    rtmi = load_package()
-    assert not rtmi.has_ablations()
-    import quad_scenes as Q, nee_scenes as NS
-    for name in ("quad_sky", Q.CORNELL):
-        st = rtmi.Stats()
-        img = Q.scene(rtmi, name).render(rtmi.Opts(seed=NS.REF_SEED, sample_count=NS.REF_K), st)
-        assert st.kernel_variant & Q.FAMILIES == Q.family(name), st.kernel_variant
-        np.save(os.path.join(sys.argv[1], name + ".npy"), img)
-""") % (ROOT, ROOT)
+    PS.check_a_mistake_fails_the_agreement(inputs, cases, name, mistake)
 
 
 def test_layouts_a_sample_split_and_the_product_library_give_the_same_bytes(rtmi, tmp_path):
-    env = dict(os.environ, RTMI_LIB=os.path.join(PKG, "librtmi_product.so"))
-    p = subprocess.run([sys.executable, "-c", _PRODUCT, str(tmp_path)], capture_output=True, text=True, env=env, timeout=600)
-    assert p.returncode == 0, p.stderr[-2000:]
-    for name in ("quad_sky", Q.CORNELL):
-        sc, fam, seed, st = Q.scene(rtmi, name), Q.family(name), NS.REF_SEED, rtmi.Stats()
-        ref = sc.render(rtmi.Opts(seed=seed, sample_count=NS.REF_K), st)
-        assert st.kernel_variant & Q.FAMILIES == fam and st.kernel_variant & ~Q.FAMILIES in GENERAL_LAYOUTS
-        for variant in GENERAL_LAYOUTS:
-            got = sc.render(rtmi.Opts(seed=seed, sample_count=NS.REF_K, variant=variant), st)
-            assert st.kernel_variant == variant | fam, (variant, st.kernel_variant)
-            assert np.array_equal(got, ref), (name, variant, float(np.abs(got - ref).max()))
-        acc, _ = sc.accumulate(None, rtmi.Opts(seed=seed, sample_first=0, sample_count=5), st)
-        assert st.kernel_variant & Q.FAMILIES == fam
-        acc, img = sc.accumulate(acc, rtmi.Opts(seed=seed, sample_first=5, sample_count=NS.REF_K - 5), st)
-        assert np.array_equal(img, ref), (name, float(np.abs(img - ref).max()))
-        assert np.array_equal(np.load(str(tmp_path / (name + ".npy"))), ref), name
+    PS.check_same_bytes(rtmi, Q, ("quad_sky", Q.CORNELL), tmp_path)
     # the nested clump of boxes: its own layout against the flat wide-table walk and the linear scan of the same scene
     sc, st = Q.nested(rtmi), rtmi.Stats()
     nested = sc.render(rtmi.Opts(seed=NS.REF_SEED, sample_count=NS.REF_K), st)
@@ -129,11 +59,8 @@ def test_layouts_a_sample_split_and_the_product_library_give_the_same_bytes(rtmi
     assert st.kernel_variant == 16 and np.array_equal(nested, scan)
     sc.set_nested_grid(False)
     flat = sc.render(rtmi.Opts(seed=NS.REF_SEED, sample_count=NS.REF_K), st)
-    assert st.kernel_variant in GENERAL_LAYOUTS and np.array_equal(nested, flat)
-    # the compact layouts list spheres for the sphere-only kernels, which know no quad: refused
-    for variant in (2, 6):
-        with pytest.raises(rtmi.RtmiError):
-            Q.scene(rtmi, "quad_sky").render(rtmi.Opts(variant=variant))
+    assert st.kernel_variant in PS.GENERAL_LAYOUTS and np.array_equal(nested, flat)
+    PS.check_compact_layouts_refuse(rtmi, lambda: Q.scene(rtmi, "quad_sky"))
 
 
 def test_feature_buffers_on_quad_pixels(rtmi):
@@ -205,18 +132,4 @@ def test_light_sampling_is_unbiased_against_the_plain_estimator(rtmi):
 
 @pytest.mark.parametrize("nee", [False, True], ids=["plain", "nee"])
 def test_the_cli_renders_the_shipped_scene(rtmi, tmp_path, nee):
-    out = str(tmp_path / "cornell.ppm")
-    scene = os.path.join(PKG, "scenes", "cornell_box.json")
-    p = subprocess.run([os.path.join(PKG, "rtmi"), "-f", scene, "-w", "64", "-h", "64", "-spp", "4", "-o", out, "--no-png"] + (["--nee"] if nee else []),
-                       capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0, p.stderr[-2000:]
-    sc = rtmi.Scene.load(scene)
-    sc.override(64, 64, 4)
-    sc.set_light_sampling(nee)
-    st = rtmi.Stats()
-    img = sc.render(rtmi.Opts(), st)
-    assert bool(st.kernel_variant & Q.NEE) == nee and np.isfinite(img).all() and img.mean() > 0
-    tokens = open(out).read().split()
-    assert tokens[:4] == ["P3", "64", "64", "255"] and len(tokens) == 4 + 64 * 64 * 3
-    values = np.array(tokens[4:], np.int64)
-    assert values.min() >= 0 and values.max() <= 255 and values.max() > 0
+    PS.check_cli(rtmi, tmp_path, "cornell_box.json", nee, Q.NEE, height=64)

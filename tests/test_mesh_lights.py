@@ -252,7 +252,7 @@ def test_packed_record_of_a_triangle_light(rtmi):
 # ---- the references of the per-sample cases ---------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def words(rtmi):
-    return ML.inputs(rtmi)
+    return ML.inputs(rtmi, ML.MIXED)[0]
 
 
 def test_refscene_builds_and_the_wrapper_is_removed(rtmi, words):

@@ -349,7 +349,7 @@ def test_installed_leaves_the_pinned_cases_alone(rtmi, golden_dir, name):
 
 @pytest.fixture(scope="module")
 def references(rtmi):
-    made, words = {}, PS.inputs(rtmi)
+    made, words = {}, PS.inputs(rtmi, "room")[0]
 
     def of(name):
         if name not in made:
@@ -397,7 +397,7 @@ def test_a_map_across_the_threshold_is_traced_per_hit(rtmi):
     sc = PS.scene(rtmi, name)
     S = R.RefScene(sc)
     assert (S.mats["type"] == RP.PBR).sum() == 1 and not np.isin(S.mats["type"], (R.ROUGH_METAL, R.PLASTIC, R.ROUGH_GLASS)).any()
-    words = PS.inputs(rtmi)[:NS.REF_W * NS.REF_H * 3]
+    words = PS.inputs(rtmi, "room")[0][:NS.REF_W * NS.REF_H * 3]
     log = R.new_log()
     rgb, sig, draws = R.trace(S, words, log=log)
     tally = R.tally(sig, S, log)
@@ -413,7 +413,7 @@ def test_m0_is_the_plastic_of_ref64(rtmi):
     """with m = 0, no map, colour and roughness on the 8-bit grid: ref64_pbr gives unmodified ref64's radiance on the plastic
     twin, sample by sample (the draws and the model coincide; a rough_metal twin takes two draws where pbr takes three, so m = 1
     is a statistical statement: test_gpu_pbr.py)"""
-    words = PS.inputs(rtmi)[:NS.REF_W * NS.REF_H * 3]
+    words = PS.inputs(rtmi, "room")[0][:NS.REF_W * NS.REF_H * 3]
     sc, tw = PS.grid_scene(rtmi, "pbr0"), PS.grid_scene(rtmi, "plastic")
     a, _, da = R.trace(R.RefScene(sc), words)
     b, _, db = R.trace(R.RefScene(tw), words)
