@@ -407,6 +407,31 @@ float rt_shutter_time(uint64_t seed, uint32_t pixel, uint32_t sample);
 int rt_scene_set_camera(rt_scene *s, const float lookfrom[3], const float lookat[3],
                         const float vup[3], float vfov, float aspect, float aperture,
                         float focus_dist);
+/* Camera projections: how (s, t) in [0, 1]^2 -- s to the right, t upwards -- becomes a ray.  u, v, w are the frame
+ * of rt_camera, f = -w the forward direction, a the aspect ratio, fd the focus distance.  Every projection defines a pinhole
+ * ray (o, D) with |D| = fd; with RT_FLAG_DEFOCUS_BLUR the ray of the lens sample (lx, ly) is (o + off, D - off), off =
+ * lens_radius (lx u + ly v), so every lens ray of a sample passes through o + D, as the perspective camera's do.
+ *   RT_PROJ_PERSPECTIVE   the default: rt_scene_set_camera's pinhole / thin lens.  No parameters.
+ *   RT_PROJ_ORTHOGRAPHIC  params[0] = height h > 0 in world units: o = lookfrom + (s - 1/2) h a u + (t - 1/2) h v, D = fd f.  The
+ *                         camera's vfov is ignored.
+ *   RT_PROJ_PANORAMIC     params = {hfov in (0, 360], vfov in (0, 180]} degrees (null: 360, 180), a lat-long frame: phi = (s - 1/2)
+ *                         hfov, psi = (t - 1/2) vfov, D = fd (cos psi (cos phi f + sin phi u) + sin psi v), o = lookfrom.  Increasing
+ *                         s turns right, so the frame reads correctly from inside -- mirrored against the column order of an
+ *                         environment map (rt_scene_set_environment).
+ *   RT_PROJ_FISHEYE       params[0] = fov in (0, 360] degrees (null: 180), equidistant: (px, py) = ((2s - 1) max(a, 1), (2t - 1)
+ *                         max(1 / a, 1)), r = |(px, py)|, theta = r fov / 2, D = fd (cos theta f + (sin theta / r)(px u + py v)),
+ *                         o = lookfrom: the image circle is inscribed in the frame's shorter side.  A sample with r > 1 has no
+ *                         path: it takes its draws, adds zero radiance (zeros in a feature pass) and counts as a sample.
+ * The projection survives rt_scene_set_camera and rt_scene_override; a non-finite or out-of-range parameter or an unknown type
+ * is RT_ERR_ARG and changes nothing.  A scene with a projection other than the perspective one renders through kernel
+ * instances of its own (csrc/camera_kernel.h) over the general layouts.  Refused at render time (RT_ERR_ARG): the compact
+ * sphere-only layouts (variants 2 and 6: use 0, 16, 36 or 44); rt_render_hip_count; a scene that also has a material with an
+ * alpha mask (those kernels are not built: remove the masks or render in perspective). */
+typedef enum rt_projection_type {
+    RT_PROJ_PERSPECTIVE = 0, RT_PROJ_ORTHOGRAPHIC = 1, RT_PROJ_PANORAMIC = 2, RT_PROJ_FISHEYE = 3
+} rt_projection_type;
+int rt_scene_set_projection(rt_scene *s, int type, const float params[2]);
+int rt_scene_get_projection(const rt_scene *s, int *type, float params[2]); /* unused parameters read 0 */
 int rt_scene_add_solid_color(rt_scene *s, const float rgb[3]);                 /* -> texture id */
 int rt_scene_add_checker(rt_scene *s, const float even[3], const float odd[3]); /* -> texture id */
 int rt_scene_add_lambertian(rt_scene *s, int texture);                         /* -> material id */
@@ -1012,6 +1037,12 @@ int rt_trace_hip(const rt_scene *s, const rt_opts *o, int mode, const rt_ray *ra
 int rt_trace_hip_device(const rt_scene *s, const rt_opts *o, int mode, const void *d_rays, size_t n, void *d_out, void *stream, rt_stats *stats);
 /* 1: the ray may enter the walk; 0: it is invalid (or r is NULL).  No GPU needed. */
 int rt_ray_valid(const rt_ray *r);
+/* Host evaluation of the scene's camera, any projection (rt_scene_set_projection; no GPU needed): the ray the kernels start at
+ * (s, t) for the lens sample (lx, ly) of the unit disk, from the fp32 camera records the device reads, operation for
+ * operation (csrc/rt_camera.h; the sines and cosines come from the host's math library).  The lens sample acts iff the scene
+ * has RT_FLAG_DEFOCUS_BLUR, as in a render.  out->t_max = +inf.  *valid (may be NULL) = 1, or 0 where the projection has no ray
+ * -- a fisheye sample outside the image circle: *out is then zeros with t_max = +inf, which rt_ray_valid refuses too. */
+int rt_camera_ray(const rt_scene *s, float sx, float t, float lx, float ly, rt_ray *out, int *valid);
 
 /* ---- the denoiser (guided by the first-hit feature buffers above) ------------ */
 

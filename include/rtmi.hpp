@@ -433,6 +433,25 @@ public:
     }
     void override_size(int w, int h, int spp, int depth) { check(rt_scene_override(s_, w, h, spp, depth), "override"); }
 
+    // camera projections (rt_scene_set_projection): orthographic (p0 = height), panoramic (p0 = hfov, p1 = vfov,
+    // degrees), fisheye (p0 = fov); kept by every other camera setter.  projection(): the type, and the parameters if asked for
+    void set_projection(rt_projection_type type, float p0 = 0.0f, float p1 = 0.0f) {
+        const float p[2] = {p0, p1};
+        check(rt_scene_set_projection(s_, type, type == RT_PROJ_PERSPECTIVE ? nullptr : p), "set_projection");
+    }
+    rt_projection_type projection(float params[2] = nullptr) const {
+        int type = 0;
+        check(rt_scene_get_projection(s_, &type, params), "projection");
+        return (rt_projection_type)type;
+    }
+    // the ray the kernels start at (s, t) for the lens sample (lx, ly), any projection (rt_camera_ray; no GPU needed); false:
+    // no ray there (outside a fisheye's image circle)
+    bool camera_ray(float s, float t, rt_ray &out, float lx = 0.0f, float ly = 0.0f) const {
+        int valid = 0;
+        check(rt_camera_ray(s_, s, t, lx, ly, &out, &valid), "camera_ray");
+        return valid != 0;
+    }
+
     // ray queries (rt_trace_hip): the renderer's closest-hit query for caller-supplied rays, one record per ray (prim -1: a
     // miss, RT_HIT_INVALID: the ray failed rt_ray_valid); occluded(): 1 where the closest-hit query would report a hit
     std::vector<rt_hit> trace(const std::vector<rt_ray> &rays, const rt_opts *opts = nullptr) const {

@@ -66,6 +66,7 @@ HIT_DTYPE = np.dtype([("t", "<f4"), ("prim", "<i4"), ("material", "<i4"), ("fron
                       ("point", "<f4", (3,)), ("v", "<f4")])
 HIT_INVALID = -2     # rt_hit.prim of a ray that failed the guard (RT_HIT_INVALID)
 TRACE_CLOSEST, TRACE_OCCLUDED = 0, 1
+PROJECTIONS = ("perspective", "orthographic", "panoramic", "fisheye")  # rt_projection_type, by number
 TRACE_ITEM = 64      # rays per work item of the query kernels (RT_TRACE_ITEM): scheduling only
 TRACE_LAYOUT = 8192  # Stats.kernel_variant of a ray query: the layout | 8192
 LIGHT_POINT, LIGHT_SPOT, LIGHT_DISTANT = 101, 102, 103  # rt_analytic_light.type, and rt_light.shape of such a light
@@ -348,6 +349,9 @@ _sig("rt_render_hip_feature_device", C.c_int, _p, C.POINTER(Opts), C.c_int, _p, 
 _sig("rt_trace_hip", C.c_int, _p, C.POINTER(Opts), C.c_int, _p, C.c_size_t, _p, C.POINTER(Stats))
 _sig("rt_trace_hip_device", C.c_int, _p, C.POINTER(Opts), C.c_int, _p, C.c_size_t, _p, _p, C.POINTER(Stats))
 _sig("rt_ray_valid", C.c_int, _p)
+_sig("rt_scene_set_projection", C.c_int, _p, C.c_int, C.POINTER(C.c_float))
+_sig("rt_scene_get_projection", C.c_int, _p, C.POINTER(C.c_int), C.POINTER(C.c_float))
+_sig("rt_camera_ray", C.c_int, _p, C.c_float, C.c_float, C.c_float, C.c_float, _p, C.POINTER(C.c_int))
 assert _lib.rt_struct_size(21) == RAY_DTYPE.itemsize == 32 and _lib.rt_struct_size(22) == HIT_DTYPE.itemsize == 48
 _sig("rt_denoise_hip", C.c_int, C.c_int, C.c_int, _p, C.c_int, _p, _p, _p, _p, C.c_int, C.POINTER(Denoise), C.c_int, _p,
      C.POINTER(C.c_double))
@@ -392,6 +396,7 @@ C_SYMBOLS = [
     "rt_scene_add_point_light", "rt_scene_add_spot_light", "rt_scene_add_distant_light", "rt_scene_get_analytic_lights",
     "rt_scene_clear_analytic_lights",
     "rt_trace_hip", "rt_trace_hip_device", "rt_ray_valid",
+    "rt_scene_set_projection", "rt_scene_get_projection", "rt_camera_ray",
     "rt_render_hip_feature", "rt_render_hip_feature_device", "rt_denoise_hip", "rt_denoise_hip_device",
     "rt_display_hip", "rt_display_hip_device", "rt_display_timing", "rt_write_hdr", "rt_write_pfm",
     "rt_write_ppm_rgb8", "rt_write_png_rgb8",
@@ -589,6 +594,34 @@ class Scene:
     def camera(self, lookfrom, lookat, vup, vfov, aspect_ratio=0.0, aperture=0.0, focus_dist=0.0):
         _check(_lib.rt_scene_set_camera(self._h, _v3(lookfrom), _v3(lookat), _v3(vup), vfov, aspect_ratio,
                                         aperture, focus_dist), "camera")
+
+    def set_projection(self, type, *params) -> None:
+        """The camera's projection (rt_scene_set_projection): "perspective" (the default), "orthographic" (height),
+        "panoramic" (hfov = 360, vfov = 180) or "fisheye" (fov = 180), by name or number; angles in degrees.  Kept by camera()
+        and override()."""
+        t = PROJECTIONS.index(type) if isinstance(type, str) and type in PROJECTIONS else type
+        if isinstance(t, str) or len(params) > 2:
+            raise ValueError(f"set_projection: no projection {type!r} with {len(params)} parameters ({', '.join(PROJECTIONS)})")
+        p = (C.c_float * 2)(*[float(x) for x in params]) if params else None
+        if p is not None and int(t) == 2 and len(params) == 1:
+            p[1] = 180.0
+        _check(_lib.rt_scene_set_projection(self._h, int(t), p), "rt_scene_set_projection")
+
+    @property
+    def projection(self):
+        """(name, parameters): ("perspective", ()), ("orthographic", (height,)), ("panoramic", (hfov, vfov)), ("fisheye", (fov,))"""
+        t = C.c_int(0)
+        p = (C.c_float * 2)()
+        _check(_lib.rt_scene_get_projection(self._h, C.byref(t), p), "rt_scene_get_projection")
+        return PROJECTIONS[t.value], tuple(float(x) for x in p[: (0, 1, 2, 1)[t.value]])
+
+    def camera_ray(self, s, t, lx=0.0, ly=0.0):
+        """The ray the kernels start at (s, t) for the lens sample (lx, ly), any projection (rt_camera_ray; no GPU needed):
+        -> (origin[3], direction[3], valid) as float32 arrays; valid is False outside a fisheye's image circle (zeros)."""
+        ray = np.zeros(1, dtype=RAY_DTYPE)
+        ok = C.c_int(0)
+        _check(_lib.rt_camera_ray(self._h, float(s), float(t), float(lx), float(ly), ray.ctypes.data_as(C.c_void_p), C.byref(ok)), "rt_camera_ray")
+        return ray["origin"][0].copy(), ray["dir"][0].copy(), bool(ok.value)
 
     def solid_color(self, rgb) -> int:
         return _check_id(_lib.rt_scene_add_solid_color(self._h, _v3(rgb)), "solid_color")

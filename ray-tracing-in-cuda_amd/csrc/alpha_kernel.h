@@ -27,7 +27,7 @@ __global__ __launch_bounds__(256, alpha_waves(FAMILY)) void alpha_kernel(const R
                                                                          DevCounters *__restrict__ counters) {
     static_assert(!((FAMILY & AF_NEE) && (FAMILY & AF_AOV)) && (!(FAMILY & AF_MOTION) || FAMILY == AF_MOTION), "no such family");
     constexpr bool COUNT = false, POOL = true, EXT = true, SPH = false, NEE = (FAMILY & AF_NEE) != 0, AOV = (FAMILY & AF_AOV) != 0,
-                   ENV = (FAMILY & AF_ENV) != 0, MEDIA = false, MOTION = (FAMILY & AF_MOTION) != 0, QUERY = false, ALPHA = true;
+                   ENV = (FAMILY & AF_ENV) != 0, MEDIA = false, MOTION = (FAMILY & AF_MOTION) != 0, QUERY = false, ALPHA = true, CAMERA = false;
     constexpr TraceArgs TQ{nullptr, nullptr, 0u, 0};
 #include "render_body.h"
 }

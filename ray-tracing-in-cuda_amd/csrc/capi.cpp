@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "philox.h"
+#include "rt_camera.h"
 #include "rt_env.h"
 #include "rt_media.h"
 #include "rt_motion.h"
@@ -247,6 +248,62 @@ int rt_scene_set_camera(rt_scene *s, const float lookfrom[3], const float lookat
     c.aperture = aperture;
     c.focus_dist = focus_dist > 0 ? (double)focus_dist : 0.0;
     s->s.touch();
+    return RT_OK;
+}
+
+// the projection: checked as a whole, stored beside the camera's parameters, which no other setter of them touches
+int rt_scene_set_projection(rt_scene *s, int type, const float params[2]) {
+    if (bad_scene(s, "rt_scene_set_projection")) return RT_ERR_ARG;
+    double p[2] = {0.0, 0.0};
+    if (params) p[0] = params[0], p[1] = params[1];
+    else if (type == RT_PROJ_PANORAMIC) p[0] = 360.0, p[1] = 180.0;
+    else if (type == RT_PROJ_FISHEYE) p[0] = 180.0;
+    else if (type == RT_PROJ_ORTHOGRAPHIC) {
+        set_error("rt_scene_set_projection: an orthographic projection needs params[0], its height");
+        return RT_ERR_ARG;
+    }
+    if (!projection_ok(type, p, "rt_scene_set_projection")) return RT_ERR_ARG;
+    CameraParams &c = s->s.cam;
+    c.projection = type;
+    c.proj[0] = type == RT_PROJ_PERSPECTIVE ? 0.0 : p[0];
+    c.proj[1] = type == RT_PROJ_PANORAMIC ? p[1] : 0.0;
+    s->s.touch();
+    return RT_OK;
+}
+
+int rt_scene_get_projection(const rt_scene *s, int *type, float params[2]) {
+    if (bad_scene(s, "rt_scene_get_projection")) return RT_ERR_ARG;
+    if (type) *type = s->s.cam.projection;
+    if (params) params[0] = (float)s->s.cam.proj[0], params[1] = (float)s->s.cam.proj[1];
+    return RT_OK;
+}
+
+// the camera's ray on the host: the records the packer writes, through the text the kernels compile
+int rt_camera_ray(const rt_scene *s, float sx, float t, float lx, float ly, rt_ray *out, int *valid) {
+    if (bad_scene(s, "rt_camera_ray")) return RT_ERR_ARG;
+    if (!out) {
+        set_error("rt_camera_ray: null ray");
+        return RT_ERR_ARG;
+    }
+    int rc = scene_validate(s->s);
+    if (rc) return rc;
+    struct V4 { float x, y, z, w; };
+    float rec[6][3], lens_radius;
+    camera_records(s->s, rec, &lens_radius);
+    V4 c[6];
+    for (int k = 0; k < 6; ++k) c[k] = V4{rec[k][0], rec[k][1], rec[k][2], 0.0f};
+    float offx = 0.0f, offy = 0.0f, offz = 0.0f;
+    if (s->s.flags & RT_FLAG_DEFOCUS_BLUR) camera_lens_offset(lens_radius, c[4], c[5], lx, ly, offx, offy, offz);
+    bool seen = true;
+    const int model = s->s.cam.projection;
+    if (model == RT_PROJ_PERSPECTIVE)
+        camera_ray_perspective(c[0], c[1], c[2], c[3], sx, t, offx, offy, offz, out->origin[0], out->origin[1], out->origin[2], out->dir[0],
+                               out->dir[1], out->dir[2]);
+    else
+        seen = camera_ray(model, c[0], c[1], c[2], c[3], c[4], c[5], sx, t, offx, offy, offz, out->origin[0], out->origin[1], out->origin[2],
+                          out->dir[0], out->dir[1], out->dir[2]);
+    out->t_max = INFINITY, out->reserved = 0.0f;
+    if (valid) *valid = seen ? 1 : 0;
     return RT_OK;
 }
 

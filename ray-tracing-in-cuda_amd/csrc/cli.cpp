@@ -25,6 +25,8 @@
 // focuses the camera on what it meets (focus_dist = t |dir|, rt_scene_set_camera) before the render.
 // Smooth shading: --mesh-normals flat|file|smooth[:DEG] gives every "mesh" of the scene file its vertex normals
 // that way, whatever its own "normals" says (DEG: the crease angle of the generated normals, 180 without).
+// Camera projections: --projection TYPE[:P1[,P2]] replaces the scene file's -- perspective, orthographic:HEIGHT,
+// panoramic[:HFOV[,VFOV]], fisheye[:FOV] (degrees; rt_scene_set_projection).  --pick and --focus-at follow the scene's camera.
 // Mesh lights: --mesh-lights lists emissive triangles among the emitters --nee samples (rt_scene_set_mesh_lights).
 #include <algorithm>
 #include <chrono>
@@ -62,7 +64,8 @@ static int usage(const char *argv0) {
             "          [--denoise] [--aov PREFIX] [--feature-spp N]\n"
             "          [--tonemap clamp|reinhard|aces] [--exposure EV] [--auto-exposure [KEY]] [--white W]\n"
             "          [--bloom STRENGTH] [--bloom-threshold T] [--bloom-levels L] [--hdr-out frame.hdr|frame.pfm]\n"
-            "          [--pick X,Y] [--focus-at X,Y] [--mesh-normals flat|file|smooth[:DEG]]\n",
+            "          [--pick X,Y] [--focus-at X,Y] [--mesh-normals flat|file|smooth[:DEG]]\n"
+            "          [--projection perspective|orthographic:HEIGHT|panoramic[:HFOV[,VFOV]]|fisheye[:FOV]]\n",
             argv0);
     return 2;
 }
@@ -93,12 +96,12 @@ static bool pixel_pair(const char *v, int *x, int *y) {
     return true;
 }
 
-// The ray through the centre of pixel (x from the left, y from the top) and what it meets: the camera's derived frame as the
-// kernels use it -- u = (x + 0.5) / (W - 1), v likewise from the bottom row, one fma per term -- and no lens offset.
+// The ray through the centre of pixel (x from the left, y from the top) and what it meets: the scene's camera as the kernels
+// evaluate it, whatever its projection (rt_camera_ray) -- u = (x + 0.5) / (W - 1), v likewise from the bottom row -- and no
+// lens offset.  A pixel outside a fisheye's image circle has no ray: reported as an invalid ray is.
 static int trace_pixel(const rt_scene *sc, int device, int x, int y, rt_ray *ray, rt_hit *hit) {
     rt_scene_info info;
-    rt_camera cam;
-    if (rt_scene_get_info(sc, &info) != RT_OK || rt_scene_get_camera(sc, &cam) != RT_OK) return RT_ERR_ARG;
+    if (rt_scene_get_info(sc, &info) != RT_OK) return RT_ERR_ARG;
     if (x >= info.width || y >= info.height) {
         fprintf(stderr, "rtmi: pixel %d,%d lies outside the %d x %d frame\n", x, y, info.width, info.height);
         return RT_ERR_ARG;
@@ -106,11 +109,10 @@ static int trace_pixel(const rt_scene *sc, int device, int x, int y, rt_ray *ray
     const float u = ((float)x + 0.5f) * (1.0f / (float)(info.width - 1));
     const float v = ((float)(info.height - 1 - y) + 0.5f) * (1.0f / (float)(info.height - 1));
     memset(ray, 0, sizeof *ray);
-    for (int a = 0; a < 3; ++a) {
-        ray->origin[a] = cam.origin[a];
-        ray->dir[a] = fmaf(v, cam.vertical[a], fmaf(u, cam.horizontal[a], cam.lower_left[a])) - cam.origin[a];
+    if (rt_camera_ray(sc, u, v, 0.0f, 0.0f, ray, nullptr) != RT_OK) {
+        fprintf(stderr, "rtmi: %s\n", rt_last_error());
+        return RT_ERR_ARG;
     }
-    ray->t_max = INFINITY;
     rt_opts o;
     rt_opts_default(&o);
     o.device = device;
@@ -146,6 +148,9 @@ int main(int argc, char **argv) {
     std::string hdr_out;        // the mean image before the display stage, .hdr or .pfm
     int w = 0, h = 0, depth = 0, spp = 0, device = 0, chunk = 0, gpus = 0, tile_rows = 0;
     bool pick = false, focus_at = false;  // ray queries through a pixel's centre
+    int projection = -1;                  // --projection: replaces the scene file's; -1: keep it
+    float projection_params[2] = {0.0f, 0.0f};
+    int projection_given = 0;             // how many parameters the flag carried
     int pick_x = 0, pick_y = 0, focus_x = 0, focus_y = 0;
     unsigned long long seed = 2023;
     unsigned scene_seed = 7;  // srand(7), main.cpp:119
@@ -177,6 +182,30 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--nee")) nee = true;
         else if (!strcmp(argv[i], "--mesh-lights")) mesh_lights = true;
         else if (!strcmp(argv[i], "--nested-grid")) nested = true;
+        else if (!strcmp(argv[i], "--projection")) {
+            const std::string v = need("--projection");
+            const size_t colon = v.find(':');
+            const std::string name = v.substr(0, colon);
+            static const char *const names[] = {"perspective", "orthographic", "panoramic", "fisheye"};
+            for (int k = 0; k < 4; ++k)
+                if (name == names[k]) projection = k;
+            bool ok = projection >= 0;
+            if (ok && colon != std::string::npos) {
+                const std::string rest = v.substr(colon + 1);
+                const size_t comma = rest.find(',');
+                double a = 0, b = 0;
+                ok = number(rest.substr(0, comma).c_str(), -1e30, 1e30, &a);
+                projection_params[0] = (float)a, projection_given = 1;
+                if (ok && comma != std::string::npos) {
+                    ok = number(rest.substr(comma + 1).c_str(), -1e30, 1e30, &b);
+                    projection_params[1] = (float)b, projection_given = 2;
+                }
+            }
+            if (!ok) {
+                fprintf(stderr, "rtmi: --projection takes perspective, orthographic:HEIGHT, panoramic[:HFOV[,VFOV]] or fisheye[:FOV], not %s\n", v.c_str());
+                return 2;
+            }
+        }
         else if (!strcmp(argv[i], "--mesh-normals")) {
             const std::string v = need("--mesh-normals");
             double deg = 180.0;
@@ -351,6 +380,13 @@ int main(int argc, char **argv) {
     if (!env_file.empty() && rt_scene_set_environment_file(sc, env_file.c_str(), (float)env_scale, (float)env_rotate) != RT_OK) {
         fprintf(stderr, "rtmi: %s\n", rt_last_error());
         return 1;
+    }
+    if (projection >= 0) {
+        if (projection == RT_PROJ_PANORAMIC && projection_given == 1) projection_params[1] = 180.0f;
+        if (rt_scene_set_projection(sc, projection, projection_given ? projection_params : nullptr) != RT_OK) {
+            fprintf(stderr, "rtmi: %s\n", rt_last_error());
+            return 1;
+        }
     }
     if (nested && rt_scene_set_nested_grid(sc, 1) != RT_OK) {
         fprintf(stderr, "rtmi: %s\n", rt_last_error());

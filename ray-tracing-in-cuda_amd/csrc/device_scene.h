@@ -156,12 +156,16 @@ struct ItemParams {
 // RenderParams::flags carries the scene's RT_FLAG_* bits (include/rtmi.h) and, above them, what the launch path adds:
 // "this scene has a normal map" (DESIGN 7u).  A kernel argument, so the test is a scalar branch around the whole step
 #define RT_PFLAG_NORMAL_MAPS (1u << 16)
+// ... and the camera's projection (rt_camera.h): the model number in two bits, 0 = perspective.  Read by the
+// instances of camera_kernel.h alone, which a non-perspective scene runs
+#define RT_PFLAG_PROJ_SHIFT 17
 // alpha cutouts: the holes one query passes through at most; the next masked hit counts as opaque whatever its texel says
 #define RT_ALPHA_MAX_PASSES 64
 
 // kernel parameter block (passed by value: lands in SGPRs / the kernarg segment)
 struct RenderParams {
-    int32_t off_cam;         // 6 records of the hot table: {origin, lens_radius}, lower_left, horizontal, vertical, u, v
+    int32_t off_cam;         // 6 records of the hot table: {origin, lens_radius}, lower_left, horizontal, vertical, u, v (a projection
+                             // other than the perspective one: what rt_camera.h says)
     float background[3];
     uint32_t flags;
     float rr_p;              // Russian-roulette survival probability per bounce, 0 = off

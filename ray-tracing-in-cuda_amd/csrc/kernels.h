@@ -32,6 +32,8 @@ struct KernelKey {
     bool feature = false;  // K_ENV: a feature pass
     bool alpha = false;    // an instance of alpha_kernel.h: the family's kernel with the alpha cutouts' code, for a scene
                            // with masks; every other scene runs the rows without it, whose code knows nothing of masks
+    bool camera = false;   // an instance of camera_kernel.h: the family's kernel with the projections' path start, for a
+                           // scene whose camera is orthographic, panoramic or fisheye; a perspective scene runs the rows without it
 };
 
 // The workgroup of an instance.  Every family runs 4 waves with one 1.5 KB tile accumulator each; the sphere-only
@@ -91,6 +93,9 @@ const KernelRow *render_kernel_rows(size_t *n);  // render_kernel.hip: K_PLAIN, 
 const KernelRow *env_kernel_rows(size_t *n);     // render_env.hip
 const KernelRow *alpha_kernel_rows(size_t *n);      // alpha_kernel.hip: K_PLAIN, K_NESTED, K_FEATURE, K_MOTION with alpha
 const KernelRow *alpha_nee_kernel_rows(size_t *n);  // alpha_nee_kernel.hip: K_NEE, K_ENV with alpha
+const KernelRow *camera_kernel_rows(size_t *n);        // camera_kernel.hip: K_PLAIN, K_NESTED, K_FEATURE, K_MOTION with a projection
+const KernelRow *camera_nee_kernel_rows(size_t *n);    // camera_nee_kernel.hip: K_NEE, K_ENV with a projection
+const KernelRow *camera_media_kernel_rows(size_t *n);  // camera_media_kernel.hip: K_MEDIA with a projection
 const KernelRow *media_kernel_rows(size_t *n);   // render_media.hip
 const KernelRow *motion_kernel_rows(size_t *n);  // render_motion.hip
 const KernelRow *trace_kernel_rows(size_t *n);   // trace.hip

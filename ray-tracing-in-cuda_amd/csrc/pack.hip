@@ -801,6 +801,16 @@ int lay_out_image(RenderParams &L, const Grid &g, const Scene &s, std::vector<in
 
 // ---- stage 5: the writers -------------------------------------------------------------------
 void write_camera(float *I, const RenderParams &L, const Scene &s) {
+    if (s.cam.projection != RT_PROJ_PERSPECTIVE) {  // (the same six records, holding what rt_camera.h says for the model)
+        float rec[6][3], lens_radius;
+        camera_records(s, rec, &lens_radius);
+        for (int k = 0; k < 6; ++k) {
+            float *h = rec4(I, L.off_cam + k);
+            h[0] = rec[k][0], h[1] = rec[k][1], h[2] = rec[k][2];
+        }
+        rec4(I, L.off_cam)[3] = lens_radius;
+        return;
+    }
     rt_camera cam;
     derive_camera(s, &cam);
     const float *src[6] = {cam.origin, cam.lower_left, cam.horizontal, cam.vertical, cam.u, cam.v};
@@ -1400,7 +1410,8 @@ bool pack_round(const Scene &s, std::vector<char> &forced, std::vector<float> &i
 
     Grid g;
     // (an environment, media and moving spheres, like light sampling, run in general kernels of their own: wide tables)
-    const bool wide = !sphere_only || S.ns() >= 65536 || !lights.empty() || s.env || !s.media.empty() || !s.movers.empty() || nest_over > 0 || knob_set("RTMI_FORCE_WIDE");  // (the knob: measurement)
+    const bool wide = !sphere_only || S.ns() >= 65536 || !lights.empty() || s.env || !s.media.empty() || !s.movers.empty() || nest_over > 0 || knob_set("RTMI_FORCE_WIDE")  // (the knob: measurement)
+                      || s.cam.projection != RT_PROJ_PERSPECTIVE;  // (a projection, DESIGN 7w: the instances of camera_kernel.h are general builds)
     const bool built = build_grid(s, S, O, L, wide, forced, g, nest_over, nest_cap);
     note.demoted = note.demoted || g.demoted;
     if (!built) return false;

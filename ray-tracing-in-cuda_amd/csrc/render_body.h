@@ -174,6 +174,8 @@
     if constexpr (ALPHA) {
         if (has_alpha) al_state[0] = __int_as_float(0), al_state[AL_T] = 0.0f;
     }
+    // CAMERA (camera projections): the path start of section 6b alone; such an instance starts paths lane by lane
+    static_assert(!CAMERA || (EXT && POOL && !QUERY && !COUNT && !BURST && !ALPHA), "projections come with the general builds, and not with masks");
     const int *lslot = reinterpret_cast<const int *>(image + P.off_lslot);
     // ENV: the environment's tables (rt_env.h), built where they are used from launch values (wave-uniform)
     auto env_view = [&]() -> EnvView {
@@ -2092,6 +2094,26 @@
                 depth = P.max_depth;
                 active = true;
                 fresh = true;
+            }
+        } else
+        if constexpr (CAMERA) {
+            // CAMERA (camera projections, DESIGN 7w, rt_camera.h; a constant of the including kernel, true in the instances of
+            // camera_kernel.h alone, which the host picks for a scene whose projection is not the perspective one): the six
+            // camera records mean what rt_camera.h says for the model, which is a kernel argument -- the switch is scalar.  The
+            // draws before this point are the perspective camera's.  A fisheye sample outside the image circle has no path: the
+            // lane took its draws, adds nothing and is idle again at the next refill.
+            if (started) {
+                float offx = 0.0f, offy = 0.0f, offz = 0.0f;
+                const float4 *cv = hot + P.off_cam;
+                const float4 c_org = cv[0], c_u = cv[4], c_v = cv[5];
+                if (P.flags & RT_FLAG_DEFOCUS_BLUR) camera_lens_offset(c_org.w, c_u, c_v, sx, sy, offx, offy, offz);
+                const int model = (int)((P.flags >> RT_PFLAG_PROJ_SHIFT) & 3u);
+                const bool seen = camera_ray(model, c_org, cv[1], cv[2], cv[3], c_u, c_v, u, v, offx, offy, offz, ox, oy, oz, dx, dy, dz);
+                beta_r = beta_g = beta_b = 1.0f;
+                depth = P.max_depth;
+                active = seen;
+                fresh = seen;
+                if (NEE) mis_pdf = -1.0f;
             }
         } else
         if (!QUERY && started) {

@@ -250,6 +250,7 @@ __device__ __forceinline__ unsigned long long radiance_to_fixed(float v) {
 #include "rt_lights.h"
 #include "rt_tangent.h"
 #include "rt_alpha.h"
+#include "rt_camera.h"
 namespace rtmi {
 
 // a noise texture's colour at the point p: q1 = {c0, offset of the noise record (bits)}, q2 = {c1, _} of the

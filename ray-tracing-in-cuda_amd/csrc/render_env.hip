@@ -18,6 +18,7 @@ __global__ __launch_bounds__(256, NEE_ ? RT_NEE_WAVES_PER_SIMD : RT_WAVES_PER_SI
     constexpr bool COUNT = false, POOL = true, EXT = true, SPH = false, NEE = NEE_, AOV = AOV_, ENV = true, MEDIA = false, MOTION = false, QUERY = false;
     constexpr TraceArgs TQ{nullptr, nullptr, 0u, 0};
     constexpr bool ALPHA = false;  // (alpha cutouts, DESIGN 7v: the instances of alpha_kernel.h alone)
+    constexpr bool CAMERA = false;  // (camera projections, DESIGN 7w: the instances of camera_kernel.h alone)
 #include "render_body.h"
 }
 

@@ -33,9 +33,9 @@ void launch_adaptive_merge(const long long *A, const long long *B, const int *ti
                            int tiles_x, hipStream_t stream);
 // the row of a render variant (rt_opts.variant, never 0) -- render_kernel, or render_nested_kernel for 52; null: no such build.
 // Its cull is the variant's candidate search.  ext: the build with triangles and image textures; count: the counting build
-static const KernelRow *variant_row(unsigned variant, bool ext = false, bool count = false, bool alpha = false) {
-    const KernelRow *row = find_kernel({K_PLAIN, variant, ext, count, false, false, alpha});
-    return row ? row : find_kernel({K_NESTED, variant, ext, count, false, false, alpha});
+static const KernelRow *variant_row(unsigned variant, bool ext = false, bool count = false, bool alpha = false, bool camera = false) {
+    const KernelRow *row = find_kernel({K_PLAIN, variant, ext, count, false, false, alpha, camera});
+    return row ? row : find_kernel({K_NESTED, variant, ext, count, false, false, alpha, camera});
 }
 
 static bool variant_exists(unsigned variant) { return variant == 0 || variant_row(variant); }
@@ -632,6 +632,10 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     ext = ext || scene_has_normal_map(s);  // (and the normal maps', DESIGN 7u -- an image texture, so it is set already)
     const bool alpha = scene_has_alpha(s);  // (alpha masks, DESIGN 7v: an image texture's plane, so ext is set already)
     ext = ext || alpha;
+    // a projection other than the perspective one: the instances of camera_kernel.h, which are general builds
+    const int projection = s.cam.projection;
+    const bool camera = projection != RT_PROJ_PERSPECTIVE;
+    ext = ext || camera;
     const bool force_ext = knob_set("RTMI_FORCE_EXT");  // measurement: the EXT builds on scenes that do not need them
     const int device = o ? o->device : 0;
     DeviceScope scope;
@@ -670,6 +674,7 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     RenderParams P = cache.layout;
     for (int i = 0; i < 3; ++i) P.background[i] = s.background[i];
     P.flags = s.flags | (scene_has_normal_map(s) ? RT_PFLAG_NORMAL_MAPS : 0u);
+    if (camera) P.flags |= (uint32_t)projection << RT_PFLAG_PROJ_SHIFT;  // (the model number, DESIGN 7w: read by the camera instances alone)
     P.rr_p = feature >= 0 ? 0.0f : s.rr_p;  // (a feature sample ends at its first query: no roulette, any max_depth)
     P.width = s.width, P.height = s.height, P.max_depth = feature >= 0 ? 1 : s.max_depth;
     P.inv_wm1 = 1.0f / (float)(s.width - 1), P.inv_hm1 = 1.0f / (float)(s.height - 1);  // IEEE fp32 divisions, as the checker's
@@ -732,6 +737,23 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
                           "would swim through the ball): remove the mask or give the mover another material");
                 return RT_ERR_ARG;
             }
+    }
+    // camera projections: what no kernel renders
+    if (camera) {
+        if (count) {
+            set_error("rt_render_hip_count: this scene's camera is not the perspective one, which the counting kernels do not carry: "
+                      "count with rt_scene_set_projection(RT_PROJ_PERSPECTIVE)");
+            return RT_ERR_ARG;
+        }
+        if (variant == 2 || variant == 6) {
+            set_error("kernel variant %u is a compact sphere-only layout, whose path start is the perspective camera's: use variant 0, 16, 36 or 44", variant);
+            return RT_ERR_ARG;
+        }
+        if (alpha) {
+            set_error("this scene has a material with an alpha mask and a camera projection other than the perspective one, which no "
+                      "kernel combines: remove the masks or render with the perspective projection");
+            return RT_ERR_ARG;
+        }
     }
     if (media) {
         if (nee) {
@@ -848,12 +870,13 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     // through its row
     const char *family = env ? "environment" : media ? "media" : motion ? "motion" : feature >= 0 ? "feature" : nullptr;
     // (a scene with alpha masks, DESIGN 7v: the family's instance of alpha_kernel.h; every other scene: the rows it always ran)
-    const KernelRow *kernel = env            ? find_kernel({K_ENV, variant, true, false, nee, feature >= 0, alpha})
-                              : media        ? find_kernel({K_MEDIA, variant, true})
-                              : motion       ? find_kernel({K_MOTION, variant, true, false, false, false, alpha})
-                              : feature >= 0 ? find_kernel({K_FEATURE, variant, true, false, false, false, alpha})
-                              : nee          ? find_kernel({K_NEE, variant, true, false, false, false, alpha})
-                                             : variant_row(variant, ext, count, alpha);
+    // (a projection, DESIGN 7w: the family's instance of camera_kernel.h, likewise)
+    const KernelRow *kernel = env            ? find_kernel({K_ENV, variant, true, false, nee, feature >= 0, alpha, camera})
+                              : media        ? find_kernel({K_MEDIA, variant, true, false, false, false, false, camera})
+                              : motion       ? find_kernel({K_MOTION, variant, true, false, false, false, alpha, camera})
+                              : feature >= 0 ? find_kernel({K_FEATURE, variant, true, false, false, false, alpha, camera})
+                              : nee          ? find_kernel({K_NEE, variant, true, false, false, false, alpha, camera})
+                                             : variant_row(variant, ext, count, alpha, camera);
     if (!kernel) {
         if (family) set_error("layout %u has no %s kernel", variant, family);
         else set_error("kernel variant %u has no %s build", variant, count ? "counting" : (ext ? "triangle / texture" : "such"));

@@ -84,6 +84,7 @@ __global__ __launch_bounds__(64 * (big_group(COUNT, POOL, SCALAR, CULL, SPH) ? k
     constexpr bool NEE = false, AOV = false, ENV = false, MEDIA = false, MOTION = false, QUERY = false;
     constexpr TraceArgs TQ{nullptr, nullptr, 0u, 0};
     constexpr bool ALPHA = false;  // (alpha cutouts, DESIGN 7v: the instances of alpha_kernel.h alone)
+    constexpr bool CAMERA = false;  // (camera projections, DESIGN 7w: the instances of camera_kernel.h alone)
 #include "render_body.h"
 }
 
@@ -97,6 +98,7 @@ __global__ __launch_bounds__(256, RT_NEE_WAVES_PER_SIMD) void render_nee_kernel(
     constexpr bool COUNT = false, POOL = true, EXT = true, SPH = false, NEE = true, AOV = false, ENV = false, MEDIA = false, MOTION = false, QUERY = false;
     constexpr TraceArgs TQ{nullptr, nullptr, 0u, 0};
     constexpr bool ALPHA = false;  // (alpha cutouts, DESIGN 7v: the instances of alpha_kernel.h alone)
+    constexpr bool CAMERA = false;  // (camera projections, DESIGN 7w: the instances of camera_kernel.h alone)
 #include "render_body.h"
 }
 
@@ -112,6 +114,7 @@ __global__ __launch_bounds__(256, RT_WAVES_PER_SIMD) void render_nested_kernel(c
     constexpr TraceArgs TQ{nullptr, nullptr, 0u, 0};
     constexpr int CULL = 8;
     constexpr bool ALPHA = false;  // (alpha cutouts, DESIGN 7v: the instances of alpha_kernel.h alone)
+    constexpr bool CAMERA = false;  // (camera projections, DESIGN 7w: the instances of camera_kernel.h alone)
 #include "render_body.h"
 }
 
@@ -127,6 +130,7 @@ __global__ __launch_bounds__(256, RT_WAVES_PER_SIMD) void render_feature_kernel(
     constexpr bool COUNT = false, POOL = true, EXT = true, SPH = false, NEE = false, AOV = true, ENV = false, MEDIA = false, MOTION = false, QUERY = false;
     constexpr TraceArgs TQ{nullptr, nullptr, 0u, 0};
     constexpr bool ALPHA = false;  // (alpha cutouts, DESIGN 7v: the instances of alpha_kernel.h alone)
+    constexpr bool CAMERA = false;  // (camera projections, DESIGN 7w: the instances of camera_kernel.h alone)
 #include "render_body.h"
 }
 
@@ -217,14 +221,15 @@ bool has_ablations() { return RTMI_ABLATIONS != 0; }
 
 const KernelRow *find_kernel(const KernelKey &key) {
     const KernelRow *(*const tables[])(size_t *) = {render_kernel_rows, env_kernel_rows, media_kernel_rows, motion_kernel_rows, trace_kernel_rows,
-                                                       alpha_kernel_rows, alpha_nee_kernel_rows};
+                                                       alpha_kernel_rows, alpha_nee_kernel_rows,
+                                                       camera_kernel_rows, camera_nee_kernel_rows, camera_media_kernel_rows};
     for (auto rows_of : tables) {
         size_t n = 0;
         const KernelRow *rows = rows_of(&n);
         for (size_t i = 0; i < n; ++i) {
             const KernelKey &r = rows[i].key;
             if (r.family == key.family && r.variant == key.variant && r.count == key.count && (key.count || r.ext == key.ext) &&
-                r.nee == key.nee && r.feature == key.feature && r.alpha == key.alpha)
+                r.nee == key.nee && r.feature == key.feature && r.alpha == key.alpha && r.camera == key.camera)
                 return &rows[i];
         }
     }

@@ -1,6 +1,7 @@
 // Scene construction: JSON -> tables, RTIOW generator, camera derivation, JSON out.
 #include "scene.hpp"
 
+#include <algorithm>
 #include <array>
 #include <cctype>
 #include <cfloat>
@@ -83,6 +84,81 @@ void derive_camera(const Scene &s, rt_camera *out) {
     out->aperture = (float)c.aperture;
     out->focus_dist = (float)focus;
     out->lens_radius = (float)(c.aperture / 2);
+}
+
+// the camera records of any projection (rt_camera.h has the table)
+void camera_records(const Scene &s, float rec[6][3], float *lens_radius) {
+    rt_camera cam;
+    derive_camera(s, &cam);
+    const float *src[6] = {cam.origin, cam.lower_left, cam.horizontal, cam.vertical, cam.u, cam.v};
+    for (int k = 0; k < 6; ++k)
+        for (int i = 0; i < 3; ++i) rec[k][i] = src[k][i];
+    *lens_radius = cam.lens_radius;
+    const CameraParams &c = s.cam;
+    if (c.projection == RT_PROJ_PERSPECTIVE) return;
+    // the frame again in fp64, as derive_camera forms it
+    const double pi = std::acos(-1.0);
+    const double aspect = c.aspect > 0 ? c.aspect : (double)s.width / (double)s.height;
+    double d[3];
+    v3sub(c.lookfrom, c.lookat, d);
+    const double focus = c.focus_dist > 0 ? c.focus_dist : v3len(d);
+    double w[3] = {d[0], d[1], d[2]}, u[3], v[3];
+    v3unit(w);
+    v3cross(c.vup, w, u);
+    v3unit(u);
+    v3cross(w, u, v);
+    if (c.projection == RT_PROJ_ORTHOGRAPHIC) {
+        const double h = c.proj[0];
+        for (int i = 0; i < 3; ++i) {
+            const double hor = h * aspect * u[i], ver = h * v[i];
+            rec[0][i] = (float)(-focus * w[i]);  // D = fd f
+            rec[1][i] = (float)(c.lookfrom[i] - hor / 2 - ver / 2);
+            rec[2][i] = (float)hor;
+            rec[3][i] = (float)ver;
+        }
+        return;
+    }
+    for (int i = 0; i < 3; ++i) rec[2][i] = 0.0f, rec[3][i] = (float)(-w[i]);
+    rec[2][0] = (float)focus;
+    if (c.projection == RT_PROJ_PANORAMIC) {
+        rec[1][0] = (float)(c.proj[0] * pi / 180.0), rec[1][1] = (float)(c.proj[1] * pi / 180.0), rec[1][2] = 0.0f;
+    } else {  // fisheye: the half angle, and the image circle inscribed in the shorter side
+        rec[1][0] = (float)(c.proj[0] * pi / 360.0);
+        rec[1][1] = (float)std::max(aspect, 1.0), rec[1][2] = (float)std::max(1.0 / aspect, 1.0);
+    }
+}
+
+const char *projection_name(int type) {
+    static const char *const names[] = {"perspective", "orthographic", "panoramic", "fisheye"};
+    return type >= 0 && type < 4 ? names[type] : nullptr;
+}
+
+bool projection_ok(int type, const double p[2], const char *where) {
+    auto in = [](double x, double hi) { return std::isfinite(x) && x > 0 && x <= hi; };
+    switch (type) {
+    case RT_PROJ_PERSPECTIVE: return true;
+    case RT_PROJ_ORTHOGRAPHIC:
+        // (the records are fp32: a height whose fp32 value is 0 or inf is out of range too)
+        if (!(std::isfinite(p[0]) && (float)p[0] > 0.0f && std::isfinite((float)p[0]))) {
+            set_error("%s: an orthographic projection's \"height\" must be a positive finite number", where);
+            return false;
+        }
+        return true;
+    case RT_PROJ_PANORAMIC:
+        if (!in(p[0], 360.0) || !in(p[1], 180.0)) {
+            set_error("%s: a panoramic projection's \"hfov\" must be in (0, 360] and its \"vfov\" in (0, 180] degrees", where);
+            return false;
+        }
+        return true;
+    case RT_PROJ_FISHEYE:
+        if (!in(p[0], 360.0)) {
+            set_error("%s: a fisheye projection's \"fov\" must be in (0, 360] degrees", where);
+            return false;
+        }
+        return true;
+    }
+    set_error("%s: unknown projection type %d (0 perspective, 1 orthographic, 2 panoramic, 3 fisheye)", where, type);
+    return false;
 }
 
 // ---------------------------------------------------------------- cylinders
@@ -1280,6 +1356,41 @@ int scene_from_json(const char *text, size_t len, Scene &s, const char *base_dir
             if (fd->is_number() && fd->num > 0) s.cam.focus_dist = fd->num;
             else r.fail("camera: \"focus_dist\" must be a positive number");
         }
+        // "projection": {"type": ..., parameters}; absent: perspective
+        s.cam.projection = RT_PROJ_PERSPECTIVE, s.cam.proj[0] = s.cam.proj[1] = 0.0;
+        if (const JsonValue *pj = cam->find("projection")) {
+            const JsonValue *ty = pj->is_object() ? pj->find("type") : nullptr;
+            if (!ty || !ty->is_string()) r.fail("camera: \"projection\" must be an object with a string \"type\"");
+            else {
+                int type = -1;
+                for (int k = 0; k < 4; ++k)
+                    if (ty->str == projection_name(k)) type = k;
+                // the fields of each type, the first two in the order of CameraParams::proj; {default, or 0: required}
+                static const char *const fields[4][2] = {{nullptr, nullptr}, {"height", nullptr}, {"hfov", "vfov"}, {"fov", nullptr}};
+                static const double defaults[4][2] = {{0, 0}, {0, 0}, {360, 180}, {180, 0}};
+                if (type < 0) r.fail("camera: projection: unknown type \"%s\" (perspective, orthographic, panoramic, fisheye)", ty->str.c_str());
+                else {
+                    for (const auto &kv : pj->obj) {
+                        bool known = kv.first == "type";
+                        for (int k = 0; k < 2; ++k) known = known || (fields[type][k] && kv.first == fields[type][k]);
+                        if (!known) r.fail("camera: projection: unknown field \"%s\" of type \"%s\"", kv.first.c_str(), ty->str.c_str());
+                    }
+                    double p[2] = {0, 0};
+                    for (int k = 0; k < 2 && r.ok; ++k) {
+                        if (!fields[type][k]) continue;
+                        const JsonValue *f = pj->find(fields[type][k]);
+                        if (f && !f->is_number()) r.fail("camera: projection: \"%s\" must be a number", fields[type][k]);
+                        else if (f) p[k] = f->num;
+                        else if (defaults[type][k] > 0) p[k] = defaults[type][k];
+                        else r.fail("camera: projection: missing number \"%s\"", fields[type][k]);
+                    }
+                    if (r.ok) {
+                        if (!projection_ok(type, p, "camera: projection")) return RT_ERR_SCENE;
+                        s.cam.projection = type, s.cam.proj[0] = p[0], s.cam.proj[1] = p[1];
+                    }
+                }
+            }
+        }
     }
     if (!r.ok) return RT_ERR_SCENE;
 
@@ -1817,6 +1928,13 @@ std::string scene_to_json(const Scene &s) {
     put_vec3d(o, s.cam.vup);
     o += ", \"vfov\": " + json_double(s.cam.vfov) + ", \"aperture\": " + json_double(s.cam.aperture);
     if (s.cam.focus_dist > 0) o += ", \"focus_dist\": " + json_double(s.cam.focus_dist);
+    if (s.cam.projection != RT_PROJ_PERSPECTIVE) {  // (a perspective scene is written as it always was)
+        o += std::string(", \"projection\": {\"type\": \"") + projection_name(s.cam.projection) + "\"";
+        if (s.cam.projection == RT_PROJ_ORTHOGRAPHIC) o += ", \"height\": " + json_double(s.cam.proj[0]);
+        if (s.cam.projection == RT_PROJ_PANORAMIC) o += ", \"hfov\": " + json_double(s.cam.proj[0]) + ", \"vfov\": " + json_double(s.cam.proj[1]);
+        if (s.cam.projection == RT_PROJ_FISHEYE) o += ", \"fov\": " + json_double(s.cam.proj[0]);
+        o += "}";
+    }
     o += "},\n";
 
     o += "  \"object\": {\"data\": [";

@@ -19,6 +19,10 @@ struct CameraParams {
     double aspect = 0.0;      // <= 0: width / height
     double aperture = 0.0;
     double focus_dist = 0.0;  // <= 0: |lookfrom - lookat|
+    // the projection (rt_projection_type) and its parameters: orthographic {height}, panoramic {hfov, vfov} in
+    // degrees, fisheye {fov} in degrees; unused ones are 0.  Kept by every setter of the fields above
+    int projection = RT_PROJ_PERSPECTIVE;
+    double proj[2] = {0.0, 0.0};
 };
 
 // how a cylinder's transform was specified (kept for JSON serialisation)
@@ -132,6 +136,13 @@ bool analytic_light_ok(const rt_analytic_light &l, const char *where);
 
 // derive the camera frame (camera.cuh:9-29) in fp64, round once to fp32
 void derive_camera(const Scene &s, rt_camera *out);
+// the six camera records of the hot table (xyz each) and the lens radius, for any projection (csrc/rt_camera.h says what they
+// hold): derived in fp64, rounded once.  The perspective ones are derive_camera's {origin, lower_left, horizontal, vertical, u, v}
+void camera_records(const Scene &s, float rec[6][3], float *lens_radius);
+// are a projection's parameters within the argument rules (false: the message is set, prefixed with `where`); p: two values,
+// of which the type's unused ones are ignored
+bool projection_ok(int type, const double p[2], const char *where);
+const char *projection_name(int type);  // "perspective", ... ; null: no such type
 
 // all return RT_OK or an rt_status, message via set_error()
 // base_dir: directory that relative "file" entries (image textures, meshes) are resolved against (NULL: the cwd)

@@ -27,6 +27,7 @@ __global__ __launch_bounds__(256, RT_TRACE_WAVES_PER_SIMD) void trace_kernel(con
     unsigned long long *const acc = nullptr;
     DevCounters *const counters = nullptr;
     constexpr bool ALPHA = false;  // (alpha cutouts, DESIGN 7v: the instances of alpha_kernel.h alone)
+    constexpr bool CAMERA = false;  // (camera projections, DESIGN 7w: the instances of camera_kernel.h alone)
 #include "render_body.h"
 }
 

@@ -274,9 +274,30 @@ def quads(rtmi, scenes):
         print("QUADS " + json.dumps(out), flush=True)
 
 
+def camera_views(rtmi, own):
+    """rows of both trees: this tree's scenes/camera_views.json at 1280 x 720 x 16 through the perspective camera (the file's
+    "projection" taken out), without and with light sampling; of this tree alone: the same through each projection"""
+    doc = json.load(open(os.path.join(ROOT, "ray-tracing-in-cuda_amd", "scenes", "camera_views.json")))
+    doc["camera"].pop("projection")
+    views = (("views perspective", None),)
+    if own:
+        views += (("views orthographic", ("orthographic", 5.0)), ("views panoramic", ("panoramic",)), ("views fisheye", ("fisheye", 180.0)))
+    rows = {}
+    for label, projection in views:
+        for nee in (False, True):
+            sc = rtmi.Scene.parse(json.dumps(doc))
+            sc.override(W, H, SPP)
+            sc.set_light_sampling(nee)
+            if projection:
+                sc.set_projection(*projection)
+            rows[label + (" nee" if nee else "")] = timed(rtmi, sc)
+    return rows
+
+
 # feature -> shared: the scenes that must render the same bytes in both trees (behind the height field, unless height_field is
 # False); scene: the feature's own shipped scene; twin: (its label, how it is made) where scene and twin are rows of the table;
-# libraries: NAME=LIBRARY contestants are accepted; extra: the feature's own line of figures, printed by this tree's first child
+# libraries: NAME=LIBRARY contestants are accepted; extra: the feature's own line of figures, printed by this tree's first child;
+# views: rows(rtmi, is this tree) that every child adds to the table
 FEATURES = {
     "glossy": dict(shared=SHIPPED[:5], scene="glossy_balls", extra=noise_beside_the_twin("GLOSSY", "glossy_balls", metal_and_lambertian)),
     "mesh_lights": dict(shared=SHIPPED[:2], height_field=False, scene="mesh_light", extra=benefit),
@@ -290,6 +311,7 @@ FEATURES = {
     "normal_map": dict(shared=SHIPPED[:8], scene="normal_map_wall",
                        twin=("wall_twin", without("normal_map", lambda sc, m: sc.set_normal_map(m, -1, 0.0))), libraries=True),
     "alpha": dict(shared=SHIPPED[:9], scene="cutout_garden", twin=("garden_twin", without("alpha", lambda sc, m: sc.set_alpha(m, -1)))),
+    "camera": dict(shared=SHIPPED[:9] + (("cutout_garden", True),), scene="camera_views", views=camera_views),
 }
 
 
@@ -320,6 +342,8 @@ def child(feature, tree, label, first):
                 sc.override(W, H, SPP)
                 sc.set_light_sampling(nee)
                 rows[name + (" nee" if nee else "")] = timed(rtmi, sc)
+    if "views" in f:
+        rows.update(f["views"](rtmi, tree == ROOT))
     for name, (lo, med, crc, kv) in rows.items():
         print("ROW " + json.dumps({"tree": label, "scene": name, "min": lo, "median": med, "crc": "%08x" % crc, "variant": kv}), flush=True)
     if "extra" in f and first:
@@ -337,6 +361,8 @@ def show():
         print("  contestants: this, other" + (", NAME=LIBRARY" if f.get("libraries") else ""))
         if "extra" in f:
             print("  extra:", " ".join((f["extra"].__doc__ or "").split()))
+        if "views" in f:
+            print("  views:", " ".join((f["views"].__doc__ or "").split()))
 
 
 def main():

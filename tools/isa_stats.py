@@ -9,6 +9,7 @@ usage: tools/isa_stats.py [--inst "false,true,false,6,false,true"] [--waves 7] [
        tools/isa_stats.py --kernel "render_motion_kernel<false,7>"            (moving spheres: <SCALAR, CULL>)
        tools/isa_stats.py --kernel "trace_kernel<false,7>"                    (ray queries: <SCALAR, CULL>)
        tools/isa_stats.py --kernel "alpha_kernel<1,false,0>"                  (a scene with alpha masks: <FAMILY, SCALAR, CULL>, csrc/alpha_kernel.h)
+       tools/isa_stats.py --kernel "camera_kernel<16,false,7>"                (a non-perspective camera: <FAMILY, SCALAR, CULL>, csrc/camera_kernel.h)
 --inst ARGS is short for --kernel "render_kernel<ARGS>"; the default instance is the headline kernel (sphere-only x-z grid walk,
 variant 0 -> 2 on RTIOW).  The families whose register budget is not --waves take theirs after "--":
 -DRT_NEE_WAVES_PER_SIMD=N (render_nee_kernel, render_env_kernel with NEE), -DRT_MEDIA_WAVES_PER_SIMD=N, -DRT_MOTION_WAVES_PER_SIMD=N,
@@ -19,7 +20,8 @@ import argparse, collections, os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # the translation unit of a kernel template (render_nee_kernel, render_nested_kernel and render_feature_kernel live in render_kernel.hip too)
 SOURCES = {"render_kernel": "render_kernel.hip", "render_env_kernel": "render_env.hip", "render_media_kernel": "render_media.hip",
-           "render_motion_kernel": "render_motion.hip", "trace_kernel": "trace.hip", "alpha_kernel": "alpha_kernel.hip"}
+           "render_motion_kernel": "render_motion.hip", "trace_kernel": "trace.hip", "alpha_kernel": "alpha_kernel.hip",
+           "camera_kernel": "camera_kernel.hip"}
 
 
 def main():
