@@ -53,6 +53,23 @@ struct KernelKey {
 #ifndef RT_BURSTS
 #define RT_BURSTS 1
 #endif
+// The burst also TRACES its 64 camera rays (render_body.h): the first closest-hit query of every path runs there, dense and
+// coherent, a ray that leaves the scene or ends on an emitter is settled there, and the slot of a scattering hit holds
+// {hit point, direction, generator state} -- the winner's id rides in the upper half of the lane's home-row register.
+// -DRT_BURST_TRACE=0: the burst hands out camera rays and the main loop runs every query (the control of the A/B);
+// -DRT_BURST_REPOP=0: a lane that pops a settled slot waits for the next iteration instead of taking a following slot.
+#ifndef RT_BURST_TRACE
+#define RT_BURST_TRACE 1
+#endif
+#ifndef RT_BURST_REPOP
+#define RT_BURST_REPOP 1
+#endif
+// (The traced burst sits at the top of the main loop's iteration.  Inside the refill, where the untraced one sits, it was
+//  measured 5 ms slower than the parent: DESIGN 5, profiles/headline_first_hit_mi355x.txt.)
+// The id's bits above the row (bits 16 .. 16 + kBurstIdBits - 1 of c_hy): enough for every record index of a table that is
+// staged in LDS at all, whatever bound the packer sets for it (pack.h, kLdsTableBytes; render_host.hip asserts that one too)
+constexpr size_t kCuLdsBytes = 160 * 1024;  // LDS of a CU
+constexpr int kBurstIdBits = 15;
 #ifndef RT_BIG_WAVES
 #define RT_BIG_WAVES 15
 #endif
@@ -73,7 +90,7 @@ constexpr int kWaveAccBytes = 192 * 8;          // 64 pixels x rgb, 64-bit fixed
 // alpha cutouts: five words per lane of a 4-wave workgroup behind the accumulators -- what a query keeps while it
 // passes through holes (render_body.h).  Added to the LDS of a launch of an alpha_kernel.h instance
 constexpr int kAlphaLdsBytes = 5 * 4 * 64 * 4;
-constexpr int kWaveSlabBytes = 64 * 10 * 4;     // 64 x {origin, direction, generator state}
+constexpr int kWaveSlabBytes = 64 * 10 * 4;     // 64 x {hit point (RT_BURST_TRACE=0: origin), direction, generator state}
 
 struct KernelRow {
     KernelKey key;

@@ -242,6 +242,10 @@ static int read_tables(const rt_scene *sc, rt_table_info *out, float *dst, int c
 
 int rt_scene_table_info(const rt_scene *sc, rt_table_info *out) { return read_tables(sc, out, nullptr, 0); }
 
+// a traced burst (render_burst.h) carries the id of a staged sphere in kBurstIdBits bits of a lane's home-row register: the
+// packer's bound for LDS-resident tables, and the CU's LDS that bounds any raised one (RTMI_GLOBAL_TABLE_BYTES), fit them
+static_assert(kLdsTableBytes <= kCuLdsBytes && kLdsTableBytes / 16 <= (size_t(1) << kBurstIdBits), "a staged record's index fits the burst's id bits");
+
 int rt_variant_workgroup(unsigned variant, int32_t out[5]) {
     const KernelRow *row = out && variant != 0 ? variant_row(variant) : nullptr;
     if (!row) {
