@@ -749,6 +749,18 @@ typedef struct rt_opts {
                               cluster votes, 64 = per-lane cluster lists through a two-level box hierarchy, 128 = per-lane
                               cluster lists through range tables */
 } rt_opts;
+/* The beam table of the frame: one record of 16 uint16 words per 8x8 tile of the WHOLE frame, row-major
+ * (tile (tx, ty) at ty * ceil(width / 8) + tx), whatever shard a launch renders: {count, id, id, ...}, the slots of the
+ * image's sphere table that a camera ray of the tile -- any pixel of it, any jitter, any lens point -- can be flagged for by
+ * the kernels' sphere test, ascending; count 0xffff: more than rt_scene_tile_beams_capacity() of them (the overflow mark: the
+ * kernels run the full query there).  Variants 2 and 6 start their paths from these lists.  rt_scene_tile_beams computes the
+ * table on the host (no device is touched); rt_scene_tile_beams_device builds it on device o->device (0 for a null o) as a
+ * launch does and reads it back; the two agree word for word.  Both copy min(cap_tiles, tiles) records and return the number
+ * of tiles, or -rt_status: RT_ERR_LIMIT for a scene without such lists (wide tables, a projection other than the perspective
+ * one, a frame under 2 x 2 pixels). */
+int rt_scene_tile_beams(const rt_scene *s, uint16_t *out, int cap_tiles);
+int rt_scene_tile_beams_device(const rt_scene *s, const rt_opts *o, uint16_t *out, int cap_tiles);
+int rt_scene_tile_beams_capacity(void);
 
 typedef struct rt_stats {
     double kernel_ms;     /* hipEvent time of the render launches of this call */

@@ -452,6 +452,18 @@ public:
         return valid != 0;
     }
 
+    // the beam table of the frame (rt_scene_tile_beams): 16 words per 8x8 tile of the whole frame, row-major,
+    // {count, ids ...}, count 0xffff = the overflow mark; as the host computes it (no GPU needed), or -- on_device -- as device
+    // opts->device builds it for its launches (rt_scene_tile_beams_device).  The two agree word for word
+    std::vector<uint16_t> tile_beams(bool on_device = false, const rt_opts *opts = nullptr) const {
+        const int n = on_device ? rt_scene_tile_beams_device(s_, opts, nullptr, 0) : rt_scene_tile_beams(s_, nullptr, 0);
+        check(n < 0 ? -n : 0, "tile_beams");
+        std::vector<uint16_t> out((size_t)n * 16);
+        const int m = on_device ? rt_scene_tile_beams_device(s_, opts, out.data(), n) : rt_scene_tile_beams(s_, out.data(), n);
+        check(m < 0 ? -m : 0, "tile_beams");
+        return out;
+    }
+
     // ray queries (rt_trace_hip): the renderer's closest-hit query for caller-supplied rays, one record per ray (prim -1: a
     // miss, RT_HIT_INVALID: the ray failed rt_ray_valid); occluded(): 1 where the closest-hit query would report a hit
     std::vector<rt_hit> trace(const std::vector<rt_ray> &rays, const rt_opts *opts = nullptr) const {

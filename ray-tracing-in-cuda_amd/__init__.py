@@ -332,6 +332,9 @@ _sig("rt_scene_nested_info", C.c_int, _p, C.POINTER(NestedInfo))
 _sig("rt_render_hip_count", C.c_int, _p, C.POINTER(Opts), _p, C.POINTER(Stats))
 _sig("rt_scene_table_info", C.c_int, _p, C.POINTER(TableInfo))
 _sig("rt_scene_table_image", C.c_int, _p, _p, C.c_int)
+_sig("rt_scene_tile_beams", C.c_int, _p, _p, C.c_int)
+_sig("rt_scene_tile_beams_device", C.c_int, _p, C.POINTER(Opts), _p, C.c_int)
+_sig("rt_scene_tile_beams_capacity", C.c_int)
 _sig("rt_render_hip_accumulate", C.c_int, _p, C.POINTER(Opts), _p, _p, C.POINTER(Stats))
 _sig("rt_acc_to_rgb", None, _p, _p, C.c_size_t)
 _sig("rt_render_hip_adaptive", C.c_int, _p, C.POINTER(Opts), C.POINTER(Adaptive), _p, _p, C.POINTER(AdaptiveStats))
@@ -369,6 +372,7 @@ _sig("rt_write_pfm", C.c_int, C.c_char_p, _p, C.c_int, C.c_int, C.c_int)
 C_SYMBOLS = [
     "rt_last_error", "rt_status_string", "rt_abi_version", "rt_struct_size", "rt_device_count", "rt_has_ablations", "rt_opts_default",
     "rt_scene_table_info", "rt_scene_table_image", "rt_variant_workgroup",
+    "rt_scene_tile_beams", "rt_scene_tile_beams_device", "rt_scene_tile_beams_capacity",
     "rt_scene_load_json", "rt_scene_parse_json", "rt_scene_rtiow", "rt_scene_to_json", "rt_scene_free",
     "rt_scene_new", "rt_scene_set_background", "rt_scene_set_camera", "rt_scene_add_solid_color",
     "rt_scene_add_checker", "rt_scene_add_lambertian", "rt_scene_add_metal", "rt_scene_add_dielectric",
@@ -1051,6 +1055,30 @@ class Scene:
         out = np.empty(n, dtype=np.float32)
         _lib.rt_scene_table_image(self._h, out.ctypes.data_as(C.c_void_p), n)
         return out.reshape(-1, 4)
+
+    def tile_beams(self, opts: Opts | None = None, device=False) -> np.ndarray:
+        """The beam table of the frame as uint16 records [tiles_y][tiles_x][16]: {count, ids ...} per 8x8 tile of the whole frame,
+        the staged spheres a camera ray of the tile can be flagged for; count 0xffff: the overflow mark.  As the host computes
+        it (rt_scene_tile_beams; no GPU needed), or with device=True as the device builds it (rt_scene_tile_beams_device)."""
+        name = "rt_scene_tile_beams_device" if device else "rt_scene_tile_beams"
+        call = (lambda p, n: _lib.rt_scene_tile_beams_device(self._h, C.byref(opts) if opts is not None else None, p, n)) if device else \
+               (lambda p, n: _lib.rt_scene_tile_beams(self._h, p, n))
+        n = call(None, 0)
+        if n < 0:
+            raise RtmiError(-n, name)
+        out = np.empty((n, 16), dtype=np.uint16)
+        n = call(out.ctypes.data_as(C.c_void_p), n)
+        if n < 0:
+            raise RtmiError(-n, name)
+        info = self.info
+        return out.reshape((int(info.height) + 7) // 8, (int(info.width) + 7) // 8, 16)
+
+    def tile_beam_list(self, tx: int, ty: int):
+        """(ids, overflow) of tile (tx, ty) of the frame's 8x8 tile grid, as the host computes them (no GPU needed)."""
+        rec = self.tile_beams()[ty, tx]
+        if rec[0] == 0xffff:
+            return [], True
+        return [int(i) for i in rec[1:1 + int(rec[0])]], False
 
     def count(self, opts: Opts | None = None, want_image=False):
         """Diagnostic launch with exact event counters (roofline flops accounting)."""

@@ -146,6 +146,9 @@ enum MatKind : int32_t {
 // + n_list), one word per tile: band << 16 | x0 (x0 = 8 x tile column); item i is chunk i / n_list of tile list[i % n_list].
 // Such a launch carries tiles_x = n_list and bands = 1, which makes the plain decode compute i % n_list and i / n_list.
 #define RT_TILE_LIST_AT 64
+// The beam table's address (rt_beam.h; variants 2 and 6): 64 bits at queue[RT_BEAMS_AT], between the item parameters and the
+// tile list; zero: the launch has no table and every burst runs the full query.  Read by the bursts with a uniform load.
+#define RT_BEAMS_AT 32
 struct ItemParams {
     int32_t tiles_x, bands, num_items, sample_first, sample_count, spp_chunk, n_big, n_med, q_med, q_small;
     int32_t tile_rows, tile_first, tile_stride, local_rows;

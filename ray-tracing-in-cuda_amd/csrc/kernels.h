@@ -8,6 +8,7 @@
 #include <stddef.h>
 
 #include "device_scene.h"
+#include "rt_beam.h"
 
 namespace rtmi {
 
@@ -63,6 +64,14 @@ struct KernelKey {
 #endif
 #ifndef RT_BURST_REPOP
 #define RT_BURST_REPOP 1
+#endif
+// The traced burst tests its tile's LIST (rt_beam.h, render_burst.h): the 64 rays of a burst are one sample of every pixel of
+// one 8x8 tile, a thin beam that the camera, the frame size and the tile fix; which staged spheres it can touch is a table
+// the host builds once per camera (tile_beams.hip, render_host.hip) and the burst reads with uniform loads.  Behind a record
+// the first query of a path is a wave-uniform loop over its ids: no prefix, no grid clip, no walk.
+// -DRT_BURST_LISTS=0: the burst runs the full query for every tile (the control of the A/B); no table is built.
+#ifndef RT_BURST_LISTS
+#define RT_BURST_LISTS 1
 #endif
 // (The traced burst sits at the top of the main loop's iteration.  Inside the refill, where the untraced one sits, it was
 //  measured 5 ms slower than the parent: DESIGN 5, profiles/headline_first_hit_mi355x.txt.)
@@ -126,6 +135,11 @@ int set_max_dynamic_lds(const KernelRow &row, size_t bytes);
 bool has_ablations();
 void launch_finalize(const unsigned long long *acc, float *out, size_t n, hipStream_t stream);
 void launch_item_params(unsigned int *queue, const ItemParams &ip, hipStream_t stream);
+
+// tile_beams.hip: the beam table of a frame (rt_beam.h) -- one record per 8x8 tile of the whole frame, row-major -- built from
+// the device's packed image, and the table's address written behind the item parameters (queue[RT_BEAMS_AT], 64 bits)
+void launch_tile_beams(const float *image, const BeamFrame &f, int tiles_x, int tiles_y, uint16_t *table, hipStream_t stream);
+void launch_beam_address(unsigned int *queue, const uint16_t *table, hipStream_t stream);
 
 // trace.hip: n rays (two 16-byte records each) -> out (three 16-byte records per ray, or one byte per ray in occlusion mode)
 void launch_trace(const KernelRow &row, const RenderParams &P, const void *image, const void *rays, void *out, unsigned int *queue,

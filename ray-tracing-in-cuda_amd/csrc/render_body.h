@@ -25,6 +25,9 @@
     // (TRACE: the burst also runs the first closest-hit query of its 64 camera rays and settles the paths that end there;
     //  REPOP: a lane that pops a settled slot takes a following one in the same refill)
     constexpr bool TRACE = BURST && RT_BURST_TRACE != 0, REPOP = TRACE && RT_BURST_REPOP != 0;
+    // (LISTS: the traced burst tests its tile's list of the beam table instead of running the prefix and the walk -- rt_beam.h,
+    //  render_burst.h; the host hands the table's address over behind the item parameters, RT_BEAMS_AT)
+    constexpr bool LISTS = TRACE && RT_BURST_LISTS != 0;
     // (the winner's id of a traced slot rides in the upper half of the home-row register, above a row of at most 65 535 and
     //  below the sign, in kBurstIdBits bits: a record of an LDS-resident table has an index below the CU's LDS / 16 --
     //  kernels.h; render_host.hip asserts the same of the packer's table bound)
@@ -256,7 +259,9 @@
         if (VOTE_MASKS || __any(active)) {
         {
 #define RT_QUERY_CUT true
+#define RT_QUERY_SKIP false
 #include "render_query.h"
+#undef RT_QUERY_SKIP
 #undef RT_QUERY_CUT
             if (active) {
 #undef RT_SPHERE_TEST

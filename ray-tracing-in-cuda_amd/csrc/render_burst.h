@@ -9,6 +9,23 @@
                         // TRACE: the lane's camera ray stays in registers for the query below; b_live: a path continues from it
                         float b_ox = 0.0f, b_oy = 0.0f, b_oz = 0.0f, b_dx = 0.0f, b_dy = 0.0f, b_dz = 1.0f;
                         bool b_live = false;
+                        // LISTS (kernels.h, RT_BURST_LISTS; rt_beam.h): the tile's record of the beam table -- the staged spheres a camera
+                        // ray of this tile can be flagged for at all -- by two wave-uniform loads, the table's address from behind the
+                        // item parameters and the record at whole-frame tile (x0 / 8, home row of lane 0 / 8).  Issued here, so that
+                        // they travel while the lanes seed their streams; read and dead inside the burst.  (Lane 0's pixel is on the
+                        // image whenever the item is: its c_hy is a row.)
+                        [[maybe_unused]] unsigned long long b_w0 = kBeamOverflow, b_w1 = 0ull, b_w2 = 0ull, b_w3 = 0ull;  // (no table: as the mark)
+                        if constexpr (LISTS) {
+                            typedef const __attribute__((address_space(4))) unsigned long long *BeamWords;
+                            asm volatile("" ::: "memory");
+                            const unsigned long long b_table = *(BeamWords)(uintptr_t)(queue + RT_BEAMS_AT);
+                            if (b_table != 0ull) {
+                                const int b_ty = (__builtin_amdgcn_readfirstlane(c_hy) & 0xffff) >> 3;
+                                const uint32_t b_tile = __umul24((uint32_t)b_ty, (uint32_t)P.tiles_x) + (uint32_t)(c_x0 >> 3);
+                                BeamWords b_rec = (BeamWords)(uintptr_t)(b_table + (unsigned long long)b_tile * (kBeamRecordWords * 2));
+                                b_w0 = b_rec[0], b_w1 = b_rec[1], b_w2 = b_rec[2], b_w3 = b_rec[3];
+                            }
+                        }
                         if (c_hy >= 0) {
                             const int bx = c_x0 + (lane & 7);
                             const int by = TRACE ? (c_hy & 0xffff) : c_hy;  // (TRACE: a winner's id above the row, below)
@@ -67,12 +84,29 @@
                             const float ox = b_ox, oy = b_oy, oz = b_oz, dx = b_dx, dy = b_dy, dz = b_dz;
                             const float ra = dot3(dx, dy, dz, dx, dy, dz), rinv_a = 1.0f / ra;  // (stage (6c)'s expressions)
                             const bool active = b_live;
+                            [[maybe_unused]] const bool b_listed = LISTS && (uint32_t)(b_w0 & 0xffffull) != (uint32_t)kBeamOverflow;
                             float t_res = 0.0f;
                             float4 rec = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0x7fc00000u));  // (nobody continues from here)
                             {
 #define RT_QUERY_CUT false
+#define RT_QUERY_SKIP (LISTS && b_listed)
 #include "render_query.h"
+#undef RT_QUERY_SKIP
 #undef RT_QUERY_CUT
+                                // LISTS: behind a record without the overflow mark the query is one wave-uniform loop over its ids --
+                                // the test, the resolve, the tie rule and kTMin of the text above; no prefix, no grid clip, no walk
+                                // (RT_QUERY_SKIP took them out).  An empty record: every live lane misses
+                                if constexpr (LISTS) {
+                                    if (b_listed) {
+                                        for (int b_n = (int)(b_w0 & 0xffffull); b_n > 0; --b_n) {
+                                            b_w0 = (b_w0 >> 16) | (b_w1 << 48), b_w1 = (b_w1 >> 16) | (b_w2 << 48);
+                                            b_w2 = (b_w2 >> 16) | (b_w3 << 48), b_w3 >>= 16;
+                                            const int b_id = (int)(b_w0 & 0xffffull);
+                                            const float4 b_s = sph[b_id];
+                                            if (active) RT_SPHERE_TEST(b_s, b_id)
+                                        }
+                                    }
+                                }
 #undef RT_SPHERE_TEST
                                 // ---- the outcome, stage (2)'s expressions.  A path that ends here -- the sky or the background on
                                 // a miss, an emitter -- adds its sample to the lane's OWN pixel of the tile (lane = home pixel: no

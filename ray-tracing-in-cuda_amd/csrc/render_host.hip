@@ -40,6 +40,21 @@ static const KernelRow *variant_row(unsigned variant, bool ext = false, bool cou
 
 static bool variant_exists(unsigned variant) { return variant == 0 || variant_row(variant); }
 
+// Everything a beam table depends on (rt_beam.h): the camera records as packed, the frame size and the defocus flag (`frame`),
+// and the identity of the sphere tables -- the scene version that was packed and the device image it was uploaded to.  The
+// growth of the bound is a function of these (the camera's distance and the sphere's), so it needs no word of its own.
+struct BeamKey {
+    bool valid = false;
+    uint64_t version = 0;
+    const void *image = nullptr;
+    BeamFrame frame{};
+    float camera[16] = {};
+    bool same(const BeamKey &o) const {
+        return valid && o.valid && version == o.version && image == o.image && !memcmp(&frame, &o.frame, sizeof frame) &&
+               !memcmp(camera, o.camera, sizeof camera);
+    }
+};
+
 struct DeviceEntry {
     int device = -1;
     uint64_t version = 0;
@@ -51,6 +66,9 @@ struct DeviceEntry {
     DeviceBuffer<int> d_spp;     // spp_map of rt_render_hip_adaptive (host-buffer entry point)
     DeviceBuffer<unsigned int> d_trace_queue;  // ray queries: the work counter of a launch (64 words)
     DeviceBuffer<char> d_trace_io;             // rays and records of rt_trace_hip (host-buffer entry point), kept between calls
+    // the beam table of variants 2 and 6 (rt_beam.h): one record per 8x8 tile of the whole frame, and what it was built from
+    DeviceBuffer<uint16_t> d_beams;
+    BeamKey beams_key;
     int num_cus = 0;
 };
 
@@ -84,6 +102,42 @@ static int ensure_packed(const Scene &s, DeviceSceneCache &cache) {
     cache.layout = layout;
     cache.nested = nested;
     cache.packed_version = s.version;
+    return RT_OK;
+}
+
+// ---- the beam table (rt_beam.h) -------------------------------------------------------
+// what the lists of scene s's frame are computed from, with the packed layout L
+static BeamFrame beam_frame_of(const Scene &s, const RenderParams &L) {
+    BeamFrame f;
+    memset(&f, 0, sizeof f);  // (the key compares bytes)
+    f.off_cam = L.off_cam, f.nslots = L.np + (RT_CLUSTER + 1) * L.ncl;
+    f.width = s.width, f.height = s.height;
+    f.inv_wm1 = 1.0f / (float)(s.width - 1), f.inv_hm1 = 1.0f / (float)(s.height - 1);  // (as the launch parameters)
+    f.defocus = (s.flags & RT_FLAG_DEFOCUS_BLUR) ? 1u : 0u;
+    return f;
+}
+
+// do a scene's bursts read lists at all?  Compact sphere tables (what variants 2 and 6 walk), the perspective camera, and a
+// frame whose jitter scale is finite
+static bool beams_apply(const Scene &s, const RenderParams &L) {
+    return !L.grid_wide && s.cam.projection == RT_PROJ_PERSPECTIVE && s.width > 1 && s.height > 1 &&
+           L.np + (RT_CLUSTER + 1) * L.ncl <= 65535;
+}
+
+// the device's table for the packed scene, built on `stream` unless the entry holds it for this key; under cache.mu
+static int ensure_beams(const Scene &s, const DeviceSceneCache &cache, DeviceEntry *ent, hipStream_t stream) {
+    BeamKey key;
+    key.valid = true, key.version = ent->version, key.image = ent->d_image.get();
+    key.frame = beam_frame_of(s, cache.layout);
+    memcpy(key.camera, cache.image.data() + 4 * (size_t)cache.layout.off_cam, sizeof key.camera);
+    const int tiles_x = (s.width + 7) / 8, tiles_y = (s.height + 7) / 8;
+    if (ent->beams_key.same(key) && ent->d_beams.get()) return RT_OK;
+    ent->beams_key.valid = false;
+    int rc = ent->d_beams.reserve((size_t)tiles_x * tiles_y * kBeamRecordWords);
+    if (rc) return rc;
+    launch_tile_beams(ent->d_image.get(), key.frame, tiles_x, tiles_y, ent->d_beams.get(), stream);
+    HIP_TRY(hipGetLastError());
+    ent->beams_key = key;
     return RT_OK;
 }
 
@@ -277,6 +331,73 @@ int rt_scene_nested_info(const rt_scene *sc, rt_nested_info *out) {
     return RT_OK;
 }
 
+int rt_scene_tile_beams(const rt_scene *sc, uint16_t *out, int cap_tiles) {
+    if (!sc) {
+        set_error("rt_scene_tile_beams: null scene");
+        return -RT_ERR_ARG;
+    }
+    int rc = scene_validate(sc->s);
+    if (rc) return -rc;
+    const Scene &s = sc->s;
+    DeviceSceneCache &cache = cache_of(s);
+    std::lock_guard<std::mutex> lock(cache.mu);
+    rc = ensure_packed(s, cache);
+    if (rc) return -rc;
+    if (!beams_apply(s, cache.layout)) {
+        set_error("rt_scene_tile_beams: the bursts of this scene read no lists (compact sphere tables, the perspective camera and a frame of at least 2 x 2 pixels have them)");
+        return -RT_ERR_LIMIT;
+    }
+    const int tiles_x = (s.width + 7) / 8, tiles_y = (s.height + 7) / 8;
+    const BeamFrame f = beam_frame_of(s, cache.layout);
+    for (int t = 0; out && t < tiles_x * tiles_y && t < cap_tiles; ++t)
+        beam_tile_record(cache.image.data(), f, t % tiles_x, t / tiles_x, out + (size_t)t * kBeamRecordWords);
+    return tiles_x * tiles_y;
+}
+
+int rt_scene_tile_beams_device(const rt_scene *sc, const rt_opts *o, uint16_t *out, int cap_tiles) {
+    if (!sc) {
+        set_error("rt_scene_tile_beams_device: null scene");
+        return -RT_ERR_ARG;
+    }
+    int rc = scene_validate(sc->s);
+    if (rc) return -rc;
+    const Scene &s = sc->s;
+    const int device = o ? o->device : 0;
+    DeviceScope scope;
+    rc = scope.enter(device, "the beam table");
+    if (rc) return -rc;
+    DeviceSceneCache &cache = cache_of(s);
+    std::lock_guard<std::mutex> lock(cache.mu);
+    rc = ensure_packed(s, cache);
+    if (rc) return -rc;
+    if (!beams_apply(s, cache.layout)) {
+        set_error("rt_scene_tile_beams_device: the bursts of this scene read no lists (compact sphere tables, the perspective camera and a frame of at least 2 x 2 pixels have them)");
+        return -RT_ERR_LIMIT;
+    }
+    DeviceEntry *ent = device_record(cache.entries, device);
+    if (ent->version != s.version || !ent->d_image.get()) {
+        rc = ent->d_image.reserve(cache.image.size());
+        if (rc) return -rc;
+        if (hipMemcpy(ent->d_image.get(), cache.image.data(), cache.image.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+            set_error("rt_scene_tile_beams_device: the upload of the scene image failed");
+            return -RT_ERR_HIP;
+        }
+        ent->version = s.version;
+    }
+    rc = ensure_beams(s, cache, ent, nullptr);
+    if (rc) return -rc;
+    const int tiles = ((s.width + 7) / 8) * ((s.height + 7) / 8);
+    const int n = std::min(tiles, cap_tiles);
+    if (hipStreamSynchronize(nullptr) != hipSuccess ||
+        (out && n > 0 && hipMemcpy(out, ent->d_beams.get(), (size_t)n * kBeamRecordWords * sizeof(uint16_t), hipMemcpyDeviceToHost) != hipSuccess)) {
+        set_error("rt_scene_tile_beams_device: reading the table back failed");
+        return -RT_ERR_HIP;
+    }
+    return tiles;
+}
+
+int rt_scene_tile_beams_capacity(void) { return kBeamCapacity; }
+
 int rt_scene_table_image(const rt_scene *sc, float *dst, int cap_floats) {
     rt_table_info info;
     int rc = read_tables(sc, &info, dst, cap_floats);
@@ -381,6 +502,7 @@ struct Launcher {
     unsigned long long resident;  // workgroups that fill the chip
     const KernelRow &kernel;      // the instance every launch of the call runs (kernels.h)
     int feature;                  // >= 0: a feature pass
+    const uint16_t *beams;        // the beam table the launches' bursts read (variants 2 and 6), or null
 
     int enqueue(unsigned long long *acc, unsigned int *d_queue, int first, int n, int n_list, const ChunkPlan &pl) const {
         RenderParams Q = P;
@@ -404,6 +526,7 @@ struct Launcher {
             ip.local_rows = Q.local_rows;
             ip.n_list = n_list;
             launch_item_params(d_queue, ip, stream);
+            if (beams) launch_beam_address(d_queue, beams, stream);
         }
         // persistent launch: enough workgroups to fill the chip, never more than the work needs
         const unsigned long long need_blocks = (items + kernel.waves - 1) / kernel.waves;
@@ -950,7 +1073,16 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     const size_t queue_off = (plane * sizeof(unsigned long long) + 255) & ~(size_t)255;
     const long long frame_tiles = (long long)P.tiles_x * P.bands;
     const size_t need = queue_off + (ad ? (((size_t)(RT_TILE_LIST_AT + frame_tiles) * 4 + 255) & ~(size_t)255) : 256);
-    const Launcher launch{P, sh, ent, d_cnt, stream, lds_bytes, resident, *kernel, feature};
+    // the beam table (rt_beam.h): for the instances whose bursts read it, when a band of the shard is a band of the frame (a
+    // record is indexed by whole-frame tile coordinates, whatever the shard and its deal)
+    const uint16_t *beams = nullptr;
+    if (RT_BURST_LISTS != 0 && kernel->key.family == K_PLAIN && !kernel->key.count && (kernel->cull == 5 || kernel->cull == 6) &&
+        sh.tile_rows % 8 == 0 && beams_apply(s, cache.layout)) {
+        rc = ensure_beams(s, cache, ent, stream);
+        if (rc) return rc;
+        beams = ent->d_beams.get();
+    }
+    const Launcher launch{P, sh, ent, d_cnt, stream, lds_bytes, resident, *kernel, feature, beams};
 
     int launches = 0;
     if (ad) {

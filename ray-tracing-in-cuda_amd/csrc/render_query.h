@@ -6,6 +6,9 @@
 // from t_res (the burst declares its own behind those names); it leaves best_t, best_id, far_scan, far_m and blim in that
 // scope.  RT_QUERY_CUT, defined by the including site: may a walk's stragglers be cut short and go on in the next iteration
 // (RT_WALK_TAIL)?  The main loop: true.  A burst has no next iteration: false, its walk runs to completion.
+// RT_QUERY_SKIP, likewise: a wave-uniform condition under which the prefix and the candidate search are left out and the
+// site tests its own candidates with the text's RT_SPHERE_TEST and resolve.  The main loop: false.  A burst whose tile has a
+// list (render_burst.h, RT_BURST_LISTS): true.
             // ---- closest-hit query over the LDS-resident list (hittable_list::hit,
             // object.cuh:23-37).  Wave-uniform trip counts; `best_id` is the grouped id.
             // (a shadow ray ends just short of its light point y = o + d: any hit before that occludes)
@@ -94,7 +97,7 @@
         }                                                                                      \
     }
             if (RT_PRIO_Q != RT_PRIO_S) __builtin_amdgcn_s_setprio(RT_PRIO_Q);
-            if (active) {
+            if (active && !RT_QUERY_SKIP) {
             // the always-tested prefix (big spheres, largest first), four records at a time: the first one -- in RTIOW the
             // ground, a candidate for half of the lanes -- is resolved at once, the other three share one resolve
             for (int i = 0; i < P.np; i += 4) {
@@ -317,7 +320,7 @@
             };
             bool far_scan = false;  // GRID: this lane's origin lies beyond the reach of the cells' lists: it scans what they list
             unsigned long long far_m = 0ull;  // VOTE_MASKS: ... and those lanes as a lane mask
-            if (active) {
+            if (active && !RT_QUERY_SKIP) {
             if (GRID && P.grid_cells != 0) {  // (no cells: a scene small enough for every primitive to be tested per query)
                 // ---- uniform grid, 3-D DDA per lane (the default).  The clustered spheres -- and, in the wide tables, the
                 // rectangles, cylinders and triangles that are not oversized -- are listed in the cells their (error-grown, see
