@@ -702,6 +702,10 @@ typedef struct rt_nested_info {
     int32_t longest;         /* longest list of a cell a walk can meet (plain cells and sub-cells) */
 } rt_nested_info;
 int rt_scene_nested_info(const rt_scene *s, rt_nested_info *out);
+/* The quads of the scene's tables, which rt_table_info does not count: *nq of them, of which the leading *nq_a are
+ * tested for every query instead of being listed.  Quad k has the grouped id ns + nr + nc + nt + k, its hot records at
+ * off_tri_hot + 5 (nt + k) and its cold records at off_tri_cold + 2 (nt + k), word 1 of the first: its list index. */
+int rt_scene_quad_counts(const rt_scene *s, int32_t *nq, int32_t *nq_a);
 /* copies min(cap_floats, image_floats) floats of the image; returns image_floats, or -rt_status */
 int rt_scene_table_image(const rt_scene *s, float *out, int cap_floats);
 

@@ -329,6 +329,7 @@ assert _lib.rt_struct_size(25) == ANALYTIC_LIGHT_DTYPE.itemsize == 48
 _sig("rt_scene_set_nested_grid", C.c_int, _p, C.c_int)
 _sig("rt_scene_get_nested_grid", C.c_int, _p)
 _sig("rt_scene_nested_info", C.c_int, _p, C.POINTER(NestedInfo))
+_sig("rt_scene_quad_counts", C.c_int, _p, C.POINTER(C.c_int32), C.POINTER(C.c_int32))
 _sig("rt_render_hip_count", C.c_int, _p, C.POINTER(Opts), _p, C.POINTER(Stats))
 _sig("rt_scene_table_info", C.c_int, _p, C.POINTER(TableInfo))
 _sig("rt_scene_table_image", C.c_int, _p, _p, C.c_int)
@@ -391,7 +392,7 @@ C_SYMBOLS = [
     "rt_scene_set_light_sampling", "rt_scene_get_light_sampling", "rt_scene_get_lights",
     "rt_scene_set_mesh_lights", "rt_scene_get_mesh_lights",
     "rt_render_hip_adaptive", "rt_render_hip_adaptive_device",
-    "rt_scene_set_nested_grid", "rt_scene_get_nested_grid", "rt_scene_nested_info",
+    "rt_scene_set_nested_grid", "rt_scene_get_nested_grid", "rt_scene_nested_info", "rt_scene_quad_counts",
     "rt_scene_set_environment", "rt_scene_set_environment_file", "rt_scene_get_environment", "rt_environment_eval",
     "rt_environment_sample",
     "rt_scene_add_medium_sphere", "rt_scene_add_medium_box", "rt_scene_get_media", "rt_scene_clear_media", "rt_medium_interval",
@@ -1046,6 +1047,13 @@ class Scene:
         t = TableInfo()
         _check(_lib.rt_scene_table_info(self._h, C.byref(t)), "rt_scene_table_info")
         return t
+
+    def quad_counts(self):
+        """(nq, nq_a): the quads of this scene's tables, and how many of them (the leading ones) are tested for every query
+        instead of being listed (rt_scene_quad_counts; TableInfo does not count quads; no GPU needed)."""
+        nq, nq_a = C.c_int32(), C.c_int32()
+        _check(_lib.rt_scene_quad_counts(self._h, C.byref(nq), C.byref(nq_a)), "rt_scene_quad_counts")
+        return int(nq.value), int(nq_a.value)
 
     def table_image(self) -> np.ndarray:
         """The packed device image as float32 records [n][4] (view it as uint32 / uint16 for the index tables)."""

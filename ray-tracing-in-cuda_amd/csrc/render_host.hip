@@ -331,6 +331,21 @@ int rt_scene_nested_info(const rt_scene *sc, rt_nested_info *out) {
     return RT_OK;
 }
 
+int rt_scene_quad_counts(const rt_scene *sc, int32_t *nq, int32_t *nq_a) {
+    if (!sc || !nq || !nq_a) {
+        set_error("rt_scene_quad_counts: null argument");
+        return RT_ERR_ARG;
+    }
+    int rc = scene_validate(sc->s);
+    if (rc) return rc;
+    DeviceSceneCache &cache = cache_of(sc->s);
+    std::lock_guard<std::mutex> lock(cache.mu);
+    rc = ensure_packed(sc->s, cache);
+    if (rc) return rc;
+    *nq = cache.layout.nq, *nq_a = cache.layout.nq_a;
+    return RT_OK;
+}
+
 int rt_scene_tile_beams(const rt_scene *sc, uint16_t *out, int cap_tiles) {
     if (!sc) {
         set_error("rt_scene_tile_beams: null scene");

@@ -18,6 +18,9 @@ Then what every feature keeps: the same bytes in every layout, through a sample 
 grid; the feature buffers; ray queries; the refusals; the command line on the shipped scene; light sampling against the plain
 estimator.
 
+None of the five cases of alpha_scenes.CASES has a grid in its tables: the alpha instances' grid walk, resumed behind a hole,
+is held to their linear scan in tests/test_gpu_walk_families.py.
+
 Every case prints one row of figures (pytest -s)."""
 
 import numpy as np

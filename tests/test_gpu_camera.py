@@ -17,6 +17,10 @@ distance at every pixel; a fisheye's pixels outside the image circle are zero in
 Then what every feature keeps: the same bytes in every layout, through a sample split, from the product library and through
 the tiles entry point; the refusals; the command line on the shipped scene, --pick included.
 
+Of these cases only cam_ortho_nested has a grid: the camera instances' grid walk -- from orthographic origins spread over a
+plane, along panoramic directions through the poles -- is held to their linear scan in tests/test_gpu_walk_families.py
+(DESIGN 7x).
+
 Every case prints one row of figures (pytest -s)."""
 import json
 import os

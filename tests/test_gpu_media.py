@@ -9,7 +9,10 @@
   5. per-sample agreement with the fp64 statement (ref64.py), criteria (a)-(d) of test_gpu_nee_reference.py;
   6. the refusals.
 
-Rows of test 5 measured on the MI355X: DESIGN 2."""
+Rows of test 5 measured on the MI355X: DESIGN 2.
+
+These cases pack to tables without a grid (layouts 36 and 44 run the scan's loops on them): the media kernels' grid walk is
+held to their linear scan in tests/test_gpu_walk_families.py."""
 import os
 
 import numpy as np

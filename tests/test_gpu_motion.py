@@ -10,7 +10,10 @@
   6. the refusals;
   7. the shipped scene.
 
-Rows of test 4 measured on the MI355X: DESIGN 2."""
+Rows of test 4 measured on the MI355X: DESIGN 2.
+
+These cases pack to tables without a grid (layouts 36 and 44 run the scan's loops on them): the motion kernels' grid walk is
+held to their linear scan in tests/test_gpu_walk_families.py."""
 import os
 
 import numpy as np

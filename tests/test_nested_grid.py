@@ -183,6 +183,10 @@ def check_nested_coverage(sc):
         gid_of[int(img[t.off_cyl_cold + 4 * k + 3].view(np.uint32)[1])] = ns + t.nr + k
     for k in range(t.nt_a, t.nt):
         gid_of[int(img[t.off_tri_cold + 2 * k].view(np.uint32)[1])] = ns + t.nr + t.nc + k
+    nq, nq_a = sc.quad_counts()  # (their records follow the triangles')
+    for k in range(nq_a, nq):
+        gid_of[int(img[t.off_tri_cold + 2 * (t.nt + k)].view(np.uint32)[1])] = ns + t.nr + t.nc + t.nt + k
+    assert all((int(P["type"][prim]) == 6) == (g >= ns + t.nr + t.nc + t.nt) for prim, g in gid_of.items())
     cache = {}
 
     def entries(c):

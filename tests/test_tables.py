@@ -58,7 +58,7 @@ class Tables:
 
 
 def other_box(p):
-    """exact world box of a rectangle / triangle; a cylinder's from points on its surface (a lower bound: coverage test)"""
+    """exact world box of a rectangle / triangle / quad; a cylinder's from points on its surface (a lower bound: coverage test)"""
     typ = int(p["type"])
     f, m = p["f"].astype(np.float64), p["m"].astype(np.float64)
     if typ in (1, 2, 3):
@@ -71,6 +71,10 @@ def other_box(p):
     if typ == 5:
         v = m[:9].reshape(3, 3)
         return v.min(axis=0), v.max(axis=0)
+    if typ == 6:  # the corners Q, Q + u, Q + u + v, Q + v
+        q, u, v = m[0:3], m[3:6], m[6:9]
+        c = np.array([q, q + u, q + u + v, q + v])
+        return c.min(axis=0), c.max(axis=0)
     ang = np.linspace(0, 2 * np.pi, 64, endpoint=False)
     pts = np.array([[abs(f[0]) * np.cos(a), abs(f[0]) * np.sin(a), z, 1.0] for a in ang for z in (f[1], f[2])])
     w = pts @ m.reshape(3, 4).T
@@ -101,10 +105,17 @@ def check_coverage(sc, expect_variant=None):
         gid_prim[ns + t.nr + k] = int(img[t.off_cyl_cold + 4 * k + 3].view(np.uint32)[1])
     for k in range(t.nt):
         gid_prim[ns + t.nr + t.nc + k] = int(img[t.off_tri_cold + 2 * k].view(np.uint32)[1])
+    # (quads: rt_table_info does not count them; their records follow the triangles', with the triangles' strides)
+    nq, nq_a = sc.quad_counts()
+    assert 0 <= nq_a <= nq == sum(1 for i in range(len(P)) if int(P["type"][i]) == 6)
+    for k in range(nq):
+        gid_prim[ns + t.nr + t.nc + t.nt + k] = int(img[t.off_tri_cold + 2 * (t.nt + k)].view(np.uint32)[1])
+        assert int(P["type"][gid_prim[ns + t.nr + t.nc + t.nt + k]]) == 6
     assert sorted(gid_prim.values()) == [i for i in range(len(P)) if int(P["type"][i]) != 0]
     always = set(range(ns, ns + t.nr_a)) | set(range(ns + t.nr, ns + t.nr + t.nc_a)) | set(range(ns + t.nr + t.nc, ns + t.nr + t.nc + t.nt_a))
+    always |= set(range(ns + t.nr + t.nc + t.nt, ns + t.nr + t.nc + t.nt + nq_a))
     if not t.grid_wide:
-        assert t.nr + t.nc + t.nt == 0
+        assert t.nr + t.nc + t.nt + nq == 0
     # ---- the lists only name what can be listed
     for c in range(t.grid_cells):
         sp = T.all_spheres(c)
@@ -127,7 +138,7 @@ def check_coverage(sc, expect_variant=None):
         lo, hi = other_box(P[prim])
         for c in T.cells_of_box(lo, hi):
             assert g in T.others(c), f"primitive {prim} (id {g}) missing from cell {c}"
-        # its stored box (behind its records) holds it
+        # its stored box (behind its records) holds it (a quad's: in the triangles' table, behind the triangles)
         if g >= ns + t.nr:
             k = g - ns - t.nr
             base = t.off_cyl_hot + 6 * k + 4 if k < t.nc else t.off_tri_hot + 5 * (k - t.nc) + 3
