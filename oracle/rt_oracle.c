@@ -27,9 +27,12 @@
  * Philox stream (oracle/ref_harness.cpp, oracle/Makefile).  tests/test_oracle_pin.py
  * compares per-sample radiance and images, and tests/golden/ holds vectors the
  * hooked reference produced (generator: tests/golden/make_golden.py).  The
- * CUDA-only features (rects, cylinders, emission, constant background) have no
- * runnable reference here: for those this file is "parity unpinned" and is
- * checked by analytic known-answer tests instead (tests/test_primitives.py).
+ * CUDA-only features (rects, cylinders, emission, constant background, checker,
+ * the hit record's u, v) are pinned against the host-compilable part of
+ * gpu-version (oracle/ref_gpu_harness.cpp -> oracle/_ref/libref_gpu.so;
+ * tests/test_reference_gpu_pin.py on vectors made by
+ * tests/golden/make_ref_gpu_pin.py) and by analytic known-answer tests
+ * (tests/test_primitives.py).
  */
 #include "rt_oracle.h"
 
@@ -472,6 +475,14 @@ static int world_hit(const rto_scene *s, const ray_t *r, float t_min, float t_ma
  * solid_color::value cpu/texture.hpp:11-26; checker_texture::value :28-49.
  * sin(t) < 0  <=>  floor(t/pi) odd (t != 0), so the sign of the triple product is
  * the parity of the three floors; a zero factor makes the product 0 -> "even". */
+static int checker_odd(vec3 p) {
+    const float inv_pi = 0.318309886183790671538f;
+    float tx = 10.0f * p.x, ty = 10.0f * p.y, tz = 10.0f * p.z;
+    int kx = (int)floorf(tx * inv_pi), ky = (int)floorf(ty * inv_pi), kz = (int)floorf(tz * inv_pi);
+    int zero = (tx == 0.0f) || (ty == 0.0f) || (tz == 0.0f);
+    return !zero && (((kx + ky + kz) & 1) != 0);
+}
+
 static vec3 texture_value(const rto_scene *s, int tex, const hit_record *rec, const ray_t *r) {
     const rto_texture *t = &s->texs[tex];
     const vec3 p = rec->p;
@@ -487,13 +498,11 @@ static vec3 texture_value(const rto_scene *s, int tex, const hit_record *rec, co
         const uint8_t *px = im->rgb + ((size_t)x * im->cols + y) * 3;
         return v3((float)px[0] / 255.0f, (float)px[1] / 255.0f, (float)px[2] / 255.0f);
     }
-    const float inv_pi = 0.318309886183790671538f;
-    float tx = 10.0f * p.x, ty = 10.0f * p.y, tz = 10.0f * p.z;
-    int kx = (int)floorf(tx * inv_pi), ky = (int)floorf(ty * inv_pi), kz = (int)floorf(tz * inv_pi);
-    int zero = (tx == 0.0f) || (ty == 0.0f) || (tz == 0.0f);
-    int odd = !zero && (((kx + ky + kz) & 1) != 0);
-    return odd ? v3(t->c1[0], t->c1[1], t->c1[2]) : c0;
+    return checker_odd(p) ? v3(t->c1[0], t->c1[1], t->c1[2]) : c0;
 }
+
+/* the checker's choice at a point, for the pin against the compiled gpu-version (tests/test_reference_gpu_pin.py) */
+int rto_checker_odd(const float p[3]) { return checker_odd(v3(p[0], p[1], p[2])); }
 
 /* ------------------------------------------------------------------ materials */
 
@@ -721,6 +730,21 @@ int rto_hit_uv(const rto_scene *s, const float o[3], const float d[3], float uv[
     if (!world_hit(s, &r, 0.001f, INFINITY, &rec, 0)) return 0;
     hit_uv(&rec, &r, &uv[0], &uv[1]);
     if (t) *t = rec.t;
+    if (prim) *prim = (int)(rec.prim - s->prims);
+    return 1;
+}
+
+/* the whole hit record of the closest hit: rec9 = {t, p.xyz, normal.xyz (face-turned), u, v}; returns 0 on a miss */
+int rto_hit_record(const rto_scene *s, const float o[3], const float d[3], float rec9[9], int *front, int *prim) {
+    ray_t r = make_ray(v3(o[0], o[1], o[2]), v3(d[0], d[1], d[2]));
+    hit_record rec;
+    memset(&rec, 0, sizeof rec);
+    if (!world_hit(s, &r, 0.001f, INFINITY, &rec, 0)) return 0;
+    rec9[0] = rec.t;
+    rec9[1] = rec.p.x, rec9[2] = rec.p.y, rec9[3] = rec.p.z;
+    rec9[4] = rec.normal.x, rec9[5] = rec.normal.y, rec9[6] = rec.normal.z;
+    hit_uv(&rec, &r, &rec9[7], &rec9[8]);
+    if (front) *front = rec.front_face;
     if (prim) *prim = (int)(rec.prim - s->prims);
     return 1;
 }

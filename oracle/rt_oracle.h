@@ -110,6 +110,11 @@ float rto_acosf(float c);
 /* (u, v) of the hit record and the image-texture value there for the closest hit of the ray (o, d); returns 0 on a miss
  * (known-answer tests of the texture coordinates: gpu/object.cuh:87-93, 113-114, 283-288, taichi hittable.py:54-58, 233) */
 int rto_hit_uv(const rto_scene *s, const float o[3], const float d[3], float uv[2], float *t, int *prim);
+/* the whole record of that hit: rec9 = {t, p.xyz, face-turned normal.xyz, u, v}, front_face, list index (the pin against the
+ * compiled gpu-version, tests/test_reference_gpu_pin.py) */
+int rto_hit_record(const rto_scene *s, const float o[3], const float d[3], float rec9[9], int *front, int *prim);
+/* checker_texture::value's choice at a point: 1 = the odd colour */
+int rto_checker_odd(const float p[3]);
 
 void rto_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 void rto_sample_stream(uint64_t seed, uint32_t pixel, uint32_t sample, uint32_t *out, int n);

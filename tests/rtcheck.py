@@ -3,6 +3,8 @@
 * ``oracle/librt_oracle.so``   -- fp32 CPU restatement (rt_oracle.c)
 * ``oracle/_ref/libref_cpu.so`` -- the reference's own cmake-cpu-version sources compiled
   with a hooked rand() (ref_harness.cpp); spheres + lambertian/metal/dielectric only.
+* ``oracle/_ref/libref_gpu.so`` -- the host-compilable part of the reference's gpu-version (ref_gpu_harness.cpp): rects,
+  cylinders, emitters, the constant background, the checker, the whole hit record.
 
 and tile_owner(), the tests' one restatement of how a frame's row tiles are dealt out to shards.
 
@@ -20,6 +22,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ORACLE_SO = os.path.join(ROOT, "oracle", "librt_oracle.so")
 REF_SO = os.path.join(ROOT, "oracle", "_ref", "libref_cpu.so")
+REF_GPU_SO = os.path.join(ROOT, "oracle", "_ref", "libref_gpu.so")
 
 
 class _RtoCamera(C.Structure):
@@ -304,6 +307,189 @@ def ref_write_color(rgb_sum, spp):
     out = (C.c_int * 3)()
     ref_lib().ref_write_color(_d3(rgb_sum), spp, out)
     return list(out)
+
+
+# ------------------------------------------------------------------ reference build, gpu-version (fp32, host C++)
+class _RefgMaterial(C.Structure):
+    _fields_ = [("type", C.c_int), ("tex_type", C.c_int), ("c0", C.c_double * 3), ("c1", C.c_double * 3),
+                ("fuzz", C.c_double), ("ir", C.c_double)]
+
+
+_ref_gpu = None
+RECORD_FIELDS = ("index", "front", "t", "p", "normal", "u", "v")
+
+
+def have_ref_gpu() -> bool:
+    return os.path.exists(REF_GPU_SO)
+
+
+def ref_gpu_lib():
+    global _ref_gpu
+    if _ref_gpu is None:
+        if not have_ref_gpu():
+            raise FileNotFoundError(f"{REF_GPU_SO} missing: run `make -C oracle` where the reference checkout exists")
+        lib = C.CDLL(REF_GPU_SO)
+        d3, mat = C.POINTER(C.c_double), C.POINTER(_RefgMaterial)
+        lib.refg_scene_new.restype = C.c_void_p
+        lib.refg_scene_free.argtypes = [C.c_void_p]
+        lib.refg_scene_set_camera.argtypes = [C.c_void_p, d3, d3, d3, C.c_double, C.c_double, C.c_double, C.c_double]
+        lib.refg_scene_set_background.argtypes = [C.c_void_p, d3]
+        lib.refg_scene_add_sphere.argtypes = [C.c_void_p, d3, C.c_double, mat]
+        lib.refg_scene_add_rect.argtypes = [C.c_void_p, C.c_int] + [C.c_double] * 5 + [mat]
+        lib.refg_scene_add_cylinder.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int, d3, C.c_double, C.c_int,
+                                                d3, mat]
+        lib.refg_scene_num_objects.argtypes = [C.c_void_p]
+        lib.refg_hit.restype = None
+        lib.refg_hit.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
+        lib.refg_sample.restype = C.c_int
+        lib.refg_sample.argtypes = [C.c_void_p, C.c_uint64] + [C.c_int] * 6 + [C.POINTER(C.c_float), C.POINTER(C.c_int)]
+        lib.refg_checker.restype = None
+        lib.refg_checker.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
+        _ref_gpu = lib
+    return _ref_gpu
+
+
+def _records(n):
+    return dict(index=np.full(n, -1, np.int32), front=np.zeros(n, np.int32), t=np.full(n, np.inf, np.float32),
+                p=np.zeros((n, 3), np.float32), normal=np.zeros((n, 3), np.float32), u=np.zeros(n, np.float32),
+                v=np.zeros(n, np.float32))
+
+
+def _fill_records(rec9, front, index):
+    out = _records(len(index))
+    hit = index >= 0
+    out["index"], out["front"] = index, np.where(hit, front, 0).astype(np.int32)
+    out["t"][hit], out["p"][hit], out["normal"][hit] = rec9[hit, 0], rec9[hit, 1:4], rec9[hit, 4:7]
+    out["u"][hit], out["v"][hit] = rec9[hit, 7], rec9[hit, 8]
+    return out
+
+
+def oracle_hit_records(scene, origins, directions):
+    """The restatement's whole hit record (rto_hit_record) of n rays, as RefGpuScene.hit returns the reference's: a dict of
+    index (-1: a miss), front, t (+inf on a miss), p, normal, u, v."""
+    lib = oracle_lib()
+    osc = scene if isinstance(scene, OracleScene) else OracleScene(scene)
+    lib.rto_hit_record.restype = C.c_int
+    lib.rto_hit_record.argtypes = [C.c_void_p] + [C.POINTER(C.c_float)] * 3 + [C.POINTER(C.c_int)] * 2
+    o, d = np.ascontiguousarray(origins, np.float32), np.ascontiguousarray(directions, np.float32)
+    n = len(o)
+    rec9, front, index = np.zeros((n, 9), np.float32), np.zeros(n, np.int32), np.full(n, -1, np.int32)
+    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int)
+    for i in range(n):
+        fr, pr = C.c_int(), C.c_int()
+        if lib.rto_hit_record(C.cast(C.byref(osc.c), C.c_void_p), o[i].ctypes.data_as(fp), d[i].ctypes.data_as(fp),
+                              rec9[i].ctypes.data_as(fp), C.byref(fr), C.byref(pr)):
+            front[i], index[i] = fr.value, pr.value
+    return _fill_records(rec9, front, index)
+
+
+def oracle_checker_odd(points):
+    """The restatement's checker at n points (rto_checker_odd): True where it takes the odd colour"""
+    lib = oracle_lib()
+    lib.rto_checker_odd.restype = C.c_int
+    lib.rto_checker_odd.argtypes = [C.POINTER(C.c_float)]
+    p = np.ascontiguousarray(points, np.float32)
+    return np.array([lib.rto_checker_odd(q.ctypes.data_as(C.POINTER(C.c_float))) for q in p], bool)
+
+
+def oracle_sample_draws(scene, seed, x, y, sample):
+    """oracle_sample with the number of uniforms the sample drew: (rgb fp32, draws)"""
+    lib = oracle_lib()
+    osc = scene if isinstance(scene, OracleScene) else OracleScene(scene)
+    rgb, cnt = (C.c_float * 3)(), _RtoCounts()
+    lib.rto_sample(C.byref(osc.c), seed, x, y, sample, rgb, C.byref(cnt))
+    return np.array(rgb[:], dtype=np.float32), int(cnt.rng_draws)
+
+
+class RefGpuScene:
+    """The scene rebuilt with the constructors of the reference's gpu-version (oracle/_ref/libref_gpu.so, ref_gpu_harness.cpp):
+    spheres, the three rects, cylinders (rotate, then translate), lambertian / metal / dielectric / diffuse_light over solid or
+    checker textures, the perspective camera with the lens off, a constant background.  ValueError for anything else.  hit()
+    takes any such scene; sample() only one of dielectric and diffuse_light (the harness header says why)."""
+
+    def __init__(self, scene):
+        lib = ref_gpu_lib()
+        info = scene.info
+        j = json.loads(scene.to_json())
+        if info.flags & 1:
+            raise ValueError("gpu-version's render() takes a constant background: no sky gradient")
+        if info.flags & 2:
+            raise ValueError("gpu-version's camera has the lens off: no defocus blur")
+        if info.russian_roulette > 0 or scene.light_sampling or scene.environment is not None or len(scene.media()) \
+                or len(scene.moving_spheres()) or len(scene.analytic_lights()) or "projection" in j["camera"]:
+            raise ValueError("gpu-version has no roulette, light sampling, environment, media, movers, analytic lights, projections")
+        prims, mats, texs = scene.prims(), scene.materials(), scene.textures()
+        self.lib, self.h = lib, lib.refg_scene_new()
+        self.paths_ok = True
+        for i, p in enumerate(prims):
+            m = mats[p["material"]]
+            mt = int(m["type"])
+            if mt > 3:
+                raise ValueError("gpu-version knows lambertian, metal, dielectric and diffuse_light")
+            if scene.bump(int(p["material"])) or scene.normal_map(int(p["material"])) or scene.alpha(int(p["material"])):
+                raise ValueError("gpu-version has no bump, normal map or alpha mask")
+            rm = _RefgMaterial(type=mt, tex_type=0, fuzz=float(m["fuzz"]), ir=float(m["ir"]))
+            if mt in (0, 3):
+                t = texs[m["texture"]]
+                if int(t["type"]) > 1:
+                    raise ValueError("gpu-version's textures are solid_color and checker_texture")
+                rm.tex_type = int(t["type"])
+                rm.c0[:], rm.c1[:] = [float(x) for x in t["c0"]], [float(x) for x in t["c1"]]
+            elif mt == 1:
+                rm.c0[:] = [float(x) for x in m["albedo"]]
+            self.paths_ok &= mt in (2, 3)
+            ty, f = int(p["type"]), [float(x) for x in p["f"]]
+            if ty == 0:
+                rc = lib.refg_scene_add_sphere(self.h, _d3(f[:3]), f[3], C.byref(rm))
+            elif ty in (1, 2, 3):
+                rc = lib.refg_scene_add_rect(self.h, ty - 1, f[0], f[1], f[2], f[3], f[4], C.byref(rm))
+            elif ty == 4:
+                o = j["object"]["data"][i]  # the pair the scene was given: axis and DEGREES, offset (parser.hpp:423-440)
+                assert o["type"] == "cylinder"
+                rot, off = o.get("rotate"), o.get("translate")
+                rc = lib.refg_scene_add_cylinder(self.h, f[0], f[1], f[2], rot is not None, _d3(rot["axis"] if rot else (0, 0, 1)),
+                                                 (rot["angle"] / 180.0 * math.pi) if rot else 0.0, off is not None,
+                                                 _d3(off if off is not None else (0, 0, 0)), C.byref(rm))
+            else:
+                raise ValueError("gpu-version has no triangles or quads")
+            assert rc == i, (rc, i)
+        cp = camera_params_of(scene)
+        lib.refg_scene_set_camera(self.h, _d3(cp["lookfrom"]), _d3(cp["lookat"]), _d3(cp["vup"]), cp["vfov"], cp["aspect"],
+                                  cp["aperture"], cp["focus_dist"])
+        lib.refg_scene_set_background(self.h, _d3(info.background[:]))
+        self.width, self.height, self.max_depth = info.width, info.height, info.max_depth
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            self.lib.refg_scene_free(self.h)
+            self.h = None
+
+    def hit(self, origins, directions):
+        """hittable_list::hit(r, 0.001, FLT_MAX, rec) of n rays: a dict of index (the winning list entry, -1: a miss), front, t
+        (+inf on a miss), p, normal, u, v, all as the reference holds them (fp32)"""
+        o, d = np.ascontiguousarray(origins, np.float32), np.ascontiguousarray(directions, np.float32)
+        n = len(o)
+        rec9, front, index = np.zeros((n, 9), np.float32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        self.lib.refg_hit(self.h, n, o.ctypes.data, d.ctypes.data, rec9.ctypes.data, front.ctypes.data, index.ctypes.data)
+        return _fill_records(rec9, front, index)
+
+    def sample(self, seed, x, y, s):
+        """(rgb fp32, uniforms drawn, (dielectric events, the list index of the light that ended the path or -1, cut at depth))"""
+        if not self.paths_ok:
+            raise ValueError("whole paths are compared on dielectric and diffuse_light only: gpu-version's lambertian and metal "
+                             "scatter from the positive octant")
+        rgb, cnt = (C.c_float * 3)(), (C.c_int * 3)()
+        draws = self.lib.refg_sample(self.h, seed, x, y, s, self.width, self.height, self.max_depth, rgb, cnt)
+        assert draws >= 0
+        return np.array(rgb[:], np.float32), draws, tuple(cnt[:])
+
+
+def ref_gpu_checker(points):
+    """checker_texture::value of the reference at n points: True where it returns the odd colour"""
+    p = np.ascontiguousarray(points, np.float32)
+    out = np.zeros(len(p), np.int32)
+    ref_gpu_lib().refg_checker(len(p), p.ctypes.data, out.ctypes.data)
+    return out != 0
 
 
 def tile_owner(t, world, deal):

@@ -453,7 +453,8 @@ def test_bright_emitter_saturates_instead_of_wrapping(rtmi, rtcheck):
 def test_unpinned_edge_cases_on_device(rtmi, rtcheck):
     """The closed-form edge cases of the CUDA-only primitives (tests/test_primitives.py: cylinder far-root / end-cap
     clipping / inside-wall normal flip, inclusive rect bounds, edge-on rects) rendered by the kernel: equal to the
-    checker bit for bit, and the expected values hold on the device too."""
+    checker bit for bit, and the expected values hold on the device too.  (The name is from when no reference run pinned
+    these primitives; tests/test_gpu_reference_gpu_pin.py now holds the kernel to the compiled gpu-version's records.)"""
     import test_primitives as tp
     for name, sc, want in tp.edge_case_scenes(rtmi):
         img = _assert_same(rtmi, rtcheck, sc)

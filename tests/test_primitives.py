@@ -1,6 +1,8 @@
 """Analytic known-answer tests of the checker for the features that exist only in the
-reference's CUDA code (no runnable reference here: "parity unpinned"): rects, cylinders +
-transforms, emission, constant background, checker texture; plus generic integrator laws.
+reference's CUDA code: rects, cylinders + transforms, emission, constant background, checker
+texture; plus generic integrator laws.  (These features are also pinned to an execution of the
+reference's own classes, compiled as host C++: tests/test_reference_gpu_pin.py.  The closed
+forms here stay as the statement of what the answers ARE.)
 Each scene is built through the product's builder API and evaluated by the CPU checker
 (the same scenes run on the HIP path in test_gpu_parity.py)."""
 import math
@@ -157,7 +159,8 @@ def test_tie_rule_later_object_wins(rtmi, rtcheck):
         assert np.all(_center_px(rtcheck, sc, 4) == np.float32(want))
 
 
-# ---- edge cases of the CUDA-only primitives (PARITY UNPINNED: no runnable reference; closed-form expectations) ----
+# ---- edge cases of the CUDA-only primitives (closed-form expectations; the compiled reference pins the same code paths on
+# random rays: tests/test_reference_gpu_pin.py) ----
 def edge_case_scenes(rtmi):
     """(name, scene, expected centre-pixel radiance or None) -- also rendered on the device by
     tests/test_gpu_parity.py::test_unpinned_edge_cases_on_device."""

@@ -1,6 +1,7 @@
 """The restatement's ray-primitive intersections against an independent fp64 derivation, on random rays.
 
-The rows of SURVEY 8 that no runnable reference pins (rectangles, cylinders + transforms, triangles: a6, a7, f3) are held by
+The rows of SURVEY 8 that only the CUDA and Taichi code has (rectangles, cylinders + transforms, triangles: a6, a7, f3; the first two
+are by now also pinned to the compiled gpu-version, tests/test_reference_gpu_pin.py) are held by
 closed-form known answers on chosen rays in test_primitives.py / test_textures_triangles.py.  This file adds volume: thousands
 of random rays per primitive through the checker's own closest-hit probe (oracle/rt_oracle.c, rto_hit_uv), compared with the
 geometry written down a second time in numpy fp64 from the reference's definitions:
