@@ -347,7 +347,21 @@ int rt_environment_sample(const rt_scene *s, float u1, float u2, float dir[3], f
  * Errors of the add calls: RT_ERR_ARG null pointers; RT_ERR_SCENE a negative or non-finite density, an albedo outside [0, 1],
  * a radius <= 0 or non-finite bounds, a box with min >= max on an axis; RT_ERR_LIMIT the 17th medium.
  * JSON: top-level "media": {"data": [{"type": "sphere", "center", "radius", "density", "albedo"},
- * {"type": "box", "min", "max", "density", "albedo"}]}. */
+ * {"type": "box", "min", "max", "density", "albedo"}]}, either with an optional "g".
+ *
+ * Anisotropic media: a medium has an asymmetry g in [-0.99, 0.99], 0 when it is added.  g > 0 scatters forward,
+ * along the direction of travel, g < 0 backward, by the Henyey-Greenstein phase function of the angle t between the arriving
+ * and the leaving direction of travel: p(cos t) = (1 - g^2) / (4 pi (1 + g^2 - 2 g cos t)^(3/2)) per steradian.  |g| < 1e-3 is
+ * stored as exactly 0, and such a medium is the isotropic one above, draw for draw and bit for bit; a non-finite g or
+ * |g| > 0.99 is RT_ERR_SCENE, a medium id the scene does not have RT_ERR_ARG.  A vertex in a medium with stored g != 0 takes no
+ * attempt of the rejection loop but TWO draws, u1 then u2, where the attempts would have been (behind the query's free-flight
+ * draws; the roulette draw keeps its place): with w = d / |d|, s = (1 - g^2) / (1 - g + 2 g u1),
+ * cos t = (1 + g^2 - s^2) / (2 g) clamped to [-1, 1], sin t = sqrt(max(0, 1 - cos^2 t)), p = 2 pi u2 and (t1, t2) the frame of
+ * Duff et al. about w, it goes on in the direction sin t cos p t1 + sin t sin p t2 + cos t w.  The direction is drawn with the
+ * phase function's own density, so the throughput is multiplied by the albedo and nothing else; the vertex costs one unit of
+ * depth and emits nothing, as the isotropic one.  The refusals are those above, whatever g is.  Setting a different stored
+ * value makes the scene a new version; setting the value it holds does not.  rt_scene_clear_media clears the asymmetries too.
+ * JSON writes "g" only where the stored value is not 0. */
 #define RT_MAX_MEDIA 16
 typedef enum rt_medium_shape { RT_MEDIUM_SPHERE = 0, RT_MEDIUM_BOX = 1 } rt_medium_shape;
 typedef struct rt_medium {
@@ -364,6 +378,13 @@ int rt_scene_clear_media(rt_scene *s);
  * [0.001, t_max].  1: non-empty (a < b), with *t_in = a and *t_out = b; 0: empty; -RT_ERR_ARG for null arguments or a shape
  * that is neither a sphere nor a box. */
 int rt_medium_interval(const rt_medium *m, const float orig[3], const float dir[3], float t_max, float *t_in, float *t_out);
+int rt_scene_set_medium_phase(rt_scene *s, int medium, float g);
+int rt_scene_get_medium_phase(const rt_scene *s, int medium, float *g); /* the STORED value: 0 after a set of 5e-4 */
+/* Host evaluations of the device's phase function (no GPU needed).  sample: the direction a vertex with asymmetry g (non-zero,
+ * |g| <= 0.99: else RT_ERR_ARG) leaves in, from the direction of travel `dir` (any length > 0) and its two draws; unit length
+ * up to rounding.  eval: p(cos t) per steradian, for any g in (-1, 1). */
+int rt_phase_hg_sample(float g, const float dir[3], float u1, float u2, float out[3]);
+float rt_phase_hg_eval(float g, float cos_theta);
 
 /* ---- motion blur: linearly moving spheres over a per-sample shutter time ----------------
  * Up to RT_MAX_MOVING_SPHERES moving spheres per scene, a list of its own: they are not in rt_scene_get_prims and not in the

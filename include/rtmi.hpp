@@ -185,15 +185,17 @@ inline material_ptr alpha_masked(const material_ptr &m, std::shared_ptr<mytextur
     return b;
 }
 
-// ---- participating media (include/rtmi.h: homogeneous media, isotropic scattering) ------------
-// constant_medium(boundary, density, albedo): the boundary is a sphere (centre, radius) or an axis-aligned box (min, max)
+// ---- participating media (include/rtmi.h: homogeneous media, isotropic or Henyey-Greenstein scattering) ------------
+// constant_medium(boundary, density, albedo[, g]): the boundary is a sphere (centre, radius) or an axis-aligned box (min, max);
+// g is the asymmetry of the phase function (0: isotropic)
 struct constant_medium {
     rt_medium rec{};
-    constant_medium(point3 cen, float radius, float density, color albedo) {
+    float g = 0.0f;
+    constant_medium(point3 cen, float radius, float density, color albedo, float g_ = 0.0f) : g(g_) {
         rec.shape = RT_MEDIUM_SPHERE, rec.f[0] = cen.x(), rec.f[1] = cen.y(), rec.f[2] = cen.z(), rec.f[3] = radius;
         fill(density, albedo);
     }
-    constant_medium(point3 bmin, point3 bmax, float density, color albedo) {
+    constant_medium(point3 bmin, point3 bmax, float density, color albedo, float g_ = 0.0f) : g(g_) {
         rec.shape = RT_MEDIUM_BOX, rec.f[0] = bmin.x(), rec.f[1] = bmin.y(), rec.f[2] = bmin.z();
         rec.f[3] = bmax.x(), rec.f[4] = bmax.y(), rec.f[5] = bmax.z();
         fill(density, albedo);
@@ -204,6 +206,15 @@ private:
         rec.density = density, rec.albedo[0] = albedo.x(), rec.albedo[1] = albedo.y(), rec.albedo[2] = albedo.z();
     }
 };
+
+// host evaluations of the device's phase function (include/rtmi.h: rt_phase_hg_sample, rt_phase_hg_eval)
+inline vec3 phase_hg_sample(float g, vec3 dir, float u1, float u2) {
+    vec3 out;
+    const int rc = rt_phase_hg_sample(g, dir.e, u1, u2, out.e);
+    if (rc != RT_OK) throw error(rc, "phase_hg_sample");
+    return out;
+}
+inline float phase_hg_eval(float g, float cos_theta) { return rt_phase_hg_eval(g, cos_theta); }
 
 // ---- motion blur (include/rtmi.h: moving spheres) ---------------------------------------------
 // moving_sphere(center0, center1, radius, material): the centre goes from center0 to center1 over the shutter time of a sample
@@ -340,7 +351,15 @@ public:
         const int id = r.shape == RT_MEDIUM_SPHERE ? rt_scene_add_medium_sphere(s_, r.f, r.f[3], r.density, r.albedo)
                                                    : rt_scene_add_medium_box(s_, r.f, r.f + 3, r.density, r.albedo);
         if (id < 0) throw error(-id, "add(constant_medium)");
+        if (m.g != 0.0f) set_medium_phase(id, m.g);
         return id;
+    }
+    void set_medium_phase(int medium, float g) { check(rt_scene_set_medium_phase(s_, medium, g), "set_medium_phase"); }
+    float medium_phase(int medium) const {
+        float g = 0.0f;
+        const int rc = rt_scene_get_medium_phase(s_, medium, &g);
+        if (rc != RT_OK) throw error(rc, "medium_phase");
+        return g;
     }
     std::vector<rt_medium> media() const {
         const int n = rt_scene_get_media(s_, nullptr, 0);

@@ -314,6 +314,10 @@ _sig("rt_scene_add_medium_box", C.c_int, _p, _f3, _f3, C.c_float, _f3)
 _sig("rt_scene_get_media", C.c_int, _p, _p, C.c_int)
 _sig("rt_scene_clear_media", C.c_int, _p)
 _sig("rt_medium_interval", C.c_int, _p, _f3, _f3, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float))
+_sig("rt_scene_set_medium_phase", C.c_int, _p, C.c_int, C.c_float)
+_sig("rt_scene_get_medium_phase", C.c_int, _p, C.c_int, C.POINTER(C.c_float))
+_sig("rt_phase_hg_sample", C.c_int, C.c_float, _f3, C.c_float, C.c_float, _f3)
+_sig("rt_phase_hg_eval", C.c_float, C.c_float, C.c_float)
 _sig("rt_scene_add_moving_sphere", C.c_int, _p, _f3, _f3, C.c_float, C.c_int)
 _sig("rt_scene_moving_sphere_count", C.c_int, _p)
 _sig("rt_scene_get_moving_spheres", C.c_int, _p, _p, C.c_int)
@@ -396,6 +400,7 @@ C_SYMBOLS = [
     "rt_scene_set_environment", "rt_scene_set_environment_file", "rt_scene_get_environment", "rt_environment_eval",
     "rt_environment_sample",
     "rt_scene_add_medium_sphere", "rt_scene_add_medium_box", "rt_scene_get_media", "rt_scene_clear_media", "rt_medium_interval",
+    "rt_scene_set_medium_phase", "rt_scene_get_medium_phase", "rt_phase_hg_sample", "rt_phase_hg_eval",
     "rt_scene_add_moving_sphere", "rt_scene_moving_sphere_count", "rt_scene_get_moving_spheres", "rt_scene_clear_moving_spheres",
     "rt_moving_sphere_hit", "rt_shutter_time",
     "rt_scene_add_point_light", "rt_scene_add_spot_light", "rt_scene_add_distant_light", "rt_scene_get_analytic_lights",
@@ -507,14 +512,32 @@ class Scene:
         _check(_lib.rt_scene_set_environment(self._h, a.shape[0], a.shape[1], a.ctypes.data_as(C.c_void_p), float(scale), float(rotate)),
                "set_environment")
 
-    def add_medium_sphere(self, center, radius: float, density: float, albedo=(1.0, 1.0, 1.0)) -> int:
-        """A homogeneous medium inside a sphere (include/rtmi.h, participating media): density per unit length, isotropic
-        scattering with the given albedo.  Returns the medium's id."""
-        return _check_id(_lib.rt_scene_add_medium_sphere(self._h, _v3(center), float(radius), float(density), _v3(albedo)), "add_medium_sphere")
+    def add_medium_sphere(self, center, radius: float, density: float, albedo=(1.0, 1.0, 1.0), g: float = 0.0) -> int:
+        """A homogeneous medium inside a sphere (include/rtmi.h, participating media): density per unit length, scattering
+        with the given albedo and Henyey-Greenstein asymmetry ``g`` (0: isotropic).  Returns the medium's id.  The medium is
+        added, then its phase set: a refused ``g`` raises and leaves the medium in the scene, isotropic."""
+        mid = _check_id(_lib.rt_scene_add_medium_sphere(self._h, _v3(center), float(radius), float(density), _v3(albedo)), "add_medium_sphere")
+        if g != 0.0:
+            self.set_medium_phase(mid, g)
+        return mid
 
-    def add_medium_box(self, bmin, bmax, density: float, albedo=(1.0, 1.0, 1.0)) -> int:
+    def add_medium_box(self, bmin, bmax, density: float, albedo=(1.0, 1.0, 1.0), g: float = 0.0) -> int:
         """A homogeneous medium inside an axis-aligned box."""
-        return _check_id(_lib.rt_scene_add_medium_box(self._h, _v3(bmin), _v3(bmax), float(density), _v3(albedo)), "add_medium_box")
+        mid = _check_id(_lib.rt_scene_add_medium_box(self._h, _v3(bmin), _v3(bmax), float(density), _v3(albedo)), "add_medium_box")
+        if g != 0.0:
+            self.set_medium_phase(mid, g)
+        return mid
+
+    def set_medium_phase(self, medium: int, g: float):
+        """The asymmetry g in [-0.99, 0.99] of a medium's Henyey-Greenstein phase function: > 0 scatters forward, < 0
+        backward; |g| < 1e-3 is stored as 0, the isotropic medium."""
+        _check(_lib.rt_scene_set_medium_phase(self._h, int(medium), float(g)), "set_medium_phase")
+
+    def medium_phase(self, medium: int) -> float:
+        """The asymmetry a medium holds (the stored value)."""
+        g = C.c_float()
+        _check(_lib.rt_scene_get_medium_phase(self._h, int(medium), C.byref(g)), "medium_phase")
+        return g.value
 
     def media(self) -> np.ndarray:
         """The scene's media in list order (MEDIUM_DTYPE records)."""
@@ -1300,6 +1323,19 @@ def medium_interval(medium, orig, direction, t_max=float("inf")):
     rc = _check_id(_lib.rt_medium_interval(rec.ctypes.data_as(C.c_void_p), _v3(orig), _v3(direction), float(t_max), C.byref(a), C.byref(b)),
                    "medium_interval")
     return bool(rc), a.value, b.value
+
+
+def phase_hg_sample(g, direction, u1, u2):
+    """Host evaluation of the device's phase-function sample: the direction a vertex of a medium with asymmetry ``g`` (not 0)
+    leaves in, from the direction of travel (any length) and its two draws -> (x, y, z)."""
+    out = (C.c_float * 3)()
+    _check(_lib.rt_phase_hg_sample(float(g), _v3(direction), float(u1), float(u2), out), "phase_hg_sample")
+    return out[0], out[1], out[2]
+
+
+def phase_hg_eval(g, cos_theta):
+    """The Henyey-Greenstein density per steradian as the device text evaluates it."""
+    return _lib.rt_phase_hg_eval(float(g), float(cos_theta))
 
 
 def moving_sphere_hit(mover, s, orig, direction, t_max=float("inf")):

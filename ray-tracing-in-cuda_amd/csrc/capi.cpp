@@ -14,6 +14,12 @@
 #include "rt_camera.h"
 #include "rt_env.h"
 #include "rt_media.h"
+// (rt_phase.h stands on rt_glossy.h, whose square root in a device pass is the kernels' own (render_device.h): the device pass of
+//  this file, which holds no kernel, leaves the header and the two bodies that evaluate it out)
+#if !(defined(__HIP_DEVICE_COMPILE__) && __HIP_DEVICE_COMPILE__)
+#define RT_CAPI_HOST_PASS 1
+#include "rt_phase.h"
+#endif
 #include "rt_motion.h"
 #include "rt_trace.h"
 #include "scene.hpp"
@@ -1182,6 +1188,7 @@ int rt_scene_clear_media(rt_scene *s) {
     if (bad_scene(s, "rt_scene_clear_media")) return RT_ERR_ARG;
     if (!s->s.media.empty()) {  // (a scene without media stays the scene it was: same version, same tables)
         s->s.media.clear();
+        s->s.media_g.clear();
         s->s.touch();
     }
     return RT_OK;
@@ -1202,6 +1209,53 @@ int rt_medium_interval(const rt_medium *m, const float orig[3], const float dir[
     if (t_in) *t_in = a;
     if (t_out) *t_out = b;
     return hit ? 1 : 0;
+}
+
+// ---- anisotropic media: a medium's asymmetry and the host evaluations of the device's phase function (rt_phase.h)
+int rt_scene_set_medium_phase(rt_scene *s, int medium, float g) {
+    if (bad_scene(s, "rt_scene_set_medium_phase")) return RT_ERR_ARG;
+    return set_medium_phase(s->s, medium, g);
+}
+
+int rt_scene_get_medium_phase(const rt_scene *s, int medium, float *g) {
+    if (bad_scene(s, "rt_scene_get_medium_phase")) return RT_ERR_ARG;
+    if (!g) {
+        set_error("rt_scene_get_medium_phase: null argument");
+        return RT_ERR_ARG;
+    }
+    if (medium < 0 || (size_t)medium >= s->s.media.size()) {
+        set_error("rt_scene_get_medium_phase: medium %d out of range (the scene has %zu)", medium, s->s.media.size());
+        return RT_ERR_ARG;
+    }
+    *g = s->s.media_g[(size_t)medium];
+    return RT_OK;
+}
+
+int rt_phase_hg_sample(float g, const float dir[3], float u1, float u2, float out[3]) {
+    if (!dir || !out) {
+        set_error("rt_phase_hg_sample: null argument");
+        return RT_ERR_ARG;
+    }
+    if (!(std::isfinite(g) && std::fabs(g) <= RT_PHASE_G_MAX && g != 0.0f)) {
+        set_error("rt_phase_hg_sample: g %g must be non-zero and within [-%g, %g] (g = 0 is the rejection loop's vertex)", (double)g,
+                  (double)RT_PHASE_G_MAX, (double)RT_PHASE_G_MAX);
+        return RT_ERR_ARG;
+    }
+#ifdef RT_CAPI_HOST_PASS
+    // the kernels' 1 / |d| of a query: ra = d.d, inv_len = 1 / sqrt(ra)
+    const float ra = fmaf(dir[0], dir[0], fmaf(dir[1], dir[1], dir[2] * dir[2]));
+    const float inv_len = 1.0f / sqrtf(ra);
+    phase_hg_sample(g, inv_len * dir[0], inv_len * dir[1], inv_len * dir[2], u1, u2, out[0], out[1], out[2]);
+#endif
+    return RT_OK;
+}
+
+float rt_phase_hg_eval(float g, float cos_theta) {
+#ifdef RT_CAPI_HOST_PASS
+    return phase_hg_eval(g, cos_theta);
+#else
+    return 0.0f;
+#endif
 }
 
 // ---- moving spheres: the scene interface and the host evaluations of the device's functions (rt_motion.h)

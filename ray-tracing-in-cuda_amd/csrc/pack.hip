@@ -1320,7 +1320,7 @@ void write_media(float *I, const RenderParams &L, const Scene &s, int off_media)
         r1[3] = m.density;
         r2[0] = m.f[4], r2[1] = m.f[5];
         memcpy(r2 + 2, &m.shape, 4);
-        r2[3] = 0.0f;
+        r2[3] = s.media_g[(size_t)i];  // (0: the isotropic medium, the word this place always held)
     }
 }
 

@@ -328,9 +328,11 @@
             // MEDIA: the media walk of a finished query.  The media -- records behind a count and an offset in the camera
             // block, all wave-uniform reads from global memory -- in list order: the ray's stay [a, b] inside the boundary up to
             // the surface winner; a non-empty stay in a medium of positive density takes ONE draw, the free-flight distance.
-            // The smallest event wins over the surface hit.  What outlives the walk: med_t and med_i.
+            // The smallest event wins over the surface hit.  What outlives the walk: med_t, med_i and the winner's asymmetry med_g
+            // (.w of its record 2, which the walk reads anyway; 0: the isotropic medium).
             float med_t = INFINITY;
             int med_i = -1;
+            float med_g = 0.0f;
             if constexpr (MEDIA) {
                 if (!unfinished) {
                     const int n_med = __builtin_amdgcn_readfirstlane(__float_as_int(image[P.off_cam + 1].w));
@@ -343,7 +345,7 @@
                             medium_interval(__float_as_int(g2.z), g0.x, g0.y, g0.z, g0.w, g2.x, g2.y, ox, oy, oz, dx, dy, dz, best_t, ta, tb)) {
                             const float u = rng_next<COUNT>(rng);
                             const float t = ta + (-logf(1.0f - u) / g1.w) / len;
-                            if (t < tb && t < med_t) med_t = t, med_i = m;
+                            if (t < tb && t < med_t) med_t = t, med_i = m, med_g = g2.w;
                         }
                     }
                 }
@@ -395,9 +397,11 @@
                 RT_SHADOW_VERDICT(best_id < 0)
             } else if (MEDIA && med_i >= 0) {
                 // a medium event: a vertex without a normal and without a material record (the scatter step takes the albedo
-                // from the medium's record), which emits nothing
+                // from the medium's record), which emits nothing.  Where a surface vertex keeps its normal's x, a medium vertex
+                // keeps its medium's asymmetry: 0 -- the normal n = 0 of the isotropic medium -- or g != 0, which the
+                // rejection loop (5) and the scatter step (6a) ask, and nothing else reads
                 px = fmaf(med_t, dx, ox), py = fmaf(med_t, dy, oy), pz = fmaf(med_t, dz, oz);
-                nx = ny = nz = 0.0f;
+                nx = med_g, ny = nz = 0.0f;
                 mat = med_i;
                 kind = MK_MEDIUM;
             } else if (best_id >= 0 || (MOTION && mot_i >= 0)) {
@@ -1137,7 +1141,8 @@
         // lanes whose material scatters with one: lambertian, metal) and random_in_unit_disk (vec3.h:157-165: two
         // draws, for the lens sample of the paths that start)
         // (QUERY: a ray is traced once and answered: no scatter step, no camera, no roulette -- nothing from here on)
-        const bool need_s = !QUERY && ((kind >= 0 && kind <= MK_METAL) || (MEDIA && kind == MK_MEDIUM));
+        // (MEDIA: an anisotropic medium vertex -- nx = g != 0 -- takes no attempt: its two draws come in (6a))
+        const bool need_s = !QUERY && ((kind >= 0 && kind <= MK_METAL) || (MEDIA && kind == MK_MEDIUM && nx == 0.0f));
         const bool need_d = !QUERY && !BURST && started && (P.flags & RT_FLAG_DEFOCUS_BLUR) != 0u;  // (BURST: the burst's own loop)
         float sx = 0, sy = 0, sz = 0, sl2 = 1;
         asm volatile("" : "=v"(sx), "=v"(sy), "=v"(sz), "=v"(sl2));  // (read by the lanes that ran the loop below, which sets all four)
@@ -1185,7 +1190,13 @@
                 float ndx, ndy, ndz;           // scattered direction
                 float at_r, at_g, at_b;        // attenuation
                 bool scattered = true;
-                if (kind <= MK_LAMBERT_IMAGE || (MEDIA && kind == MK_MEDIUM)) {  // lambertian::scatter, material.h:25-35 (MEDIA: a medium vertex, n = 0)
+                if (MEDIA && kind == MK_MEDIUM && nx != 0.0f) {
+                    // an anisotropic medium vertex (rt_phase.h): two draws, u1 for the polar angle about the direction of
+                    // travel and u2 for the azimuth; the sample's density is the phase function, so the weight is the albedo
+                    const float u1 = rng_next<COUNT>(rng), u2 = rng_next<COUNT>(rng);
+                    phase_hg_sample(nx, inv_len * dx, inv_len * dy, inv_len * dz, u1, u2, ndx, ndy, ndz);
+                    at_r = q1.x, at_g = q1.y, at_b = q1.z;
+                } else if (kind <= MK_LAMBERT_IMAGE || (MEDIA && kind == MK_MEDIUM)) {  // lambertian::scatter, material.h:25-35 (MEDIA: a medium vertex, n = 0)
                     const float inv = 1.0f / rt_sqrtf<ROOT_VOTE>(sl2);
                     ndx = nx + inv * sx, ndy = ny + inv * sy, ndz = nz + inv * sz;
                     const float eps = 1e-8f;

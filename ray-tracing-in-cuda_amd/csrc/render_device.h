@@ -244,6 +244,7 @@ __device__ __forceinline__ unsigned long long radiance_to_fixed(float v) {
 }  // namespace rtmi
 #include "rt_glossy.h"
 #include "rt_glass.h"
+#include "rt_phase.h"
 #include "rt_pbr.h"
 #include "rt_noise.h"
 #include "rt_quad.h"

@@ -1,6 +1,6 @@
 // The media kernels: the render loop of render_body.h with MEDIA on -- after every closest-hit query the scene's
-// homogeneous media (rt_media.h) are walked, and a free-flight event nearer than the surface hit becomes an isotropic
-// scattering vertex.  A kernel family and a translation unit of its own, like render_env.hip: the instances of
+// homogeneous media (rt_media.h) are walked, and a free-flight event nearer than the surface hit becomes a scattering
+// vertex: isotropic, or by the medium's Henyey-Greenstein phase function (rt_phase.h).  A kernel family and a translation unit of its own, like render_env.hip: the instances of
 // render_kernel.hip keep their code.  The helpers are render_device.h's; the host finds the instances through this file's
 // rows (kernels.h).
 #include "kernels.h"

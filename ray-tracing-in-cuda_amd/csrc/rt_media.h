@@ -3,7 +3,7 @@
 // (rt_medium_interval), like rt_env.h.  Every step is one fp32 operation in a fixed order.
 //
 // MEDIA part of the scene image (only with at least one medium; global memory, behind everything else): per medium
-//   3 x float4   {f0, f1, f2, f3} {albedo.rgb, density} {f4, f5, shape(bits), 0}      sphere f = {c.xyz, r}; box f = {min.xyz, max.xyz}
+//   3 x float4   {f0, f1, f2, f3} {albedo.rgb, density} {f4, f5, shape(bits), g}      sphere f = {c.xyz, r}; box f = {min.xyz, max.xyz}
 // (record 1 has the place of a material's {c0.xyz, p3}: the scatter step reads the albedo as it reads a lambertian's.)
 // Where the part lies is said by two words of the camera block, which are zero in a scene without media:
 //   record off_cam + 1, .w   number of media (bits)          record off_cam + 2, .w   float4 offset of the MEDIA part (bits)
@@ -14,6 +14,9 @@
 #include "rt_trig.h"  // RTMI_HD
 
 #define RT_MEDIUM_STRIDE 3
+// the asymmetry g of a medium's phase function (rt_phase.h), .w of record 2: |g| <= MAX, and |g| < SNAP is stored as 0
+#define RT_PHASE_G_MAX 0.99f
+#define RT_PHASE_G_SNAP 1e-3f
 
 namespace rtmi {
 

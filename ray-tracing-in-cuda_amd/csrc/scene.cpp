@@ -15,6 +15,7 @@
 #include "json.hpp"
 #include "png_read.hpp"
 #include "philox.h"
+#include "rt_media.h"
 
 namespace rtmi {
 
@@ -1239,7 +1240,9 @@ int scene_from_json(const char *text, size_t len, Scene &s, const char *base_dir
     }
     if (r.ok && env_rc != RT_OK) return env_rc == RT_ERR_ARG ? RT_ERR_SCENE : env_rc;
     // "media": {"data": [{"type": "sphere", "center", "radius", "density", "albedo"}, {"type": "box", "min", "max", "density", "albedo"}]}
+    // and on either, optionally, "g": the asymmetry of the phase function
     s.media.clear();
+    s.media_g.clear();
     if (root.find("media")) {
         if (const JsonValue *arr = r.data_array(root, "media")) {
             for (size_t i = 0; i < arr->arr.size() && r.ok; ++i) {
@@ -1270,8 +1273,10 @@ int scene_from_json(const char *text, size_t len, Scene &s, const char *base_dir
                 m.density = (float)r.num(t, "density", where);
                 r.vec3(t, "albedo", where, v);
                 for (int k = 0; k < 3; ++k) m.albedo[k] = (float)v[k];
+                const float g = t.find("g") ? (float)r.num(t, "g", where) : 0.0f;
                 if (!r.ok) break;
-                const int rc = add_medium(s, m);
+                int rc = add_medium(s, m);
+                if (rc >= 0) rc = -set_medium_phase(s, rc, g);
                 if (rc < 0) {  // (the record's own message, with its place in the file)
                     const std::string why = get_error();
                     set_error("%s: %s", where, why.c_str());
@@ -1916,6 +1921,7 @@ std::string scene_to_json(const Scene &s) {
             }
             o += ", \"density\": " + json_float(m.density) + ", \"albedo\": ";
             put_vec3(o, m.albedo);
+            if (s.media_g[i] != 0.0f) o += ", \"g\": " + json_float(s.media_g[i]);
             o += "}";
         }
         o += "\n  ]},\n";
@@ -2571,8 +2577,27 @@ int add_medium(Scene &s, const rt_medium &m) {
     rt_medium rec = m;
     if (rec.shape == RT_MEDIUM_SPHERE) rec.f[4] = rec.f[5] = 0.0f;
     s.media.push_back(rec);
+    s.media_g.push_back(0.0f);
     s.touch();
     return (int)s.media.size() - 1;
+}
+
+// ---------------------------------------------------------------- anisotropic media
+int set_medium_phase(Scene &s, int medium, float g) {
+    if (medium < 0 || (size_t)medium >= s.media.size()) {
+        set_error("medium phase: medium %d out of range (the scene has %zu)", medium, s.media.size());
+        return RT_ERR_ARG;
+    }
+    if (!(std::isfinite(g) && std::fabs(g) <= RT_PHASE_G_MAX)) {
+        set_error("medium phase: g %g must be finite and within [-%g, %g]", (double)g, (double)RT_PHASE_G_MAX, (double)RT_PHASE_G_MAX);
+        return RT_ERR_SCENE;
+    }
+    const float stored = std::fabs(g) < RT_PHASE_G_SNAP ? 0.0f : g;  // (the isotropic medium, instruction for instruction)
+    if (s.media_g[(size_t)medium] != stored) {  // (a scene set to what it holds stays the scene it was: same version, same tables)
+        s.media_g[(size_t)medium] = stored;
+        s.touch();
+    }
+    return RT_OK;
 }
 
 // ---------------------------------------------------------------- moving spheres

@@ -100,6 +100,8 @@ struct Scene {
     std::shared_ptr<const SceneEnvironment> env;  // null: no environment (a miss gives the background / the sky)
     float env_scale = 1.0f, env_rotate = 0.0f;    // radiance = scale x texel; degrees about +y
     std::vector<rt_medium> media;  // homogeneous participating media, a list of its own: at most RT_MAX_MEDIA
+    std::vector<float> media_g;    // media_g[i]: the Henyey-Greenstein asymmetry of medium i as stored (0: isotropic),
+                                   // beside `media` and always as long
     std::vector<rt_moving_sphere> movers;  // moving spheres, a list of its own: at most RT_MAX_MOVING_SPHERES
     std::vector<rt_analytic_light> alights;  // point, spot and distant lights, a list of its own, as given
     uint64_t version = 1;  // bumped on every mutation; invalidates device caches
@@ -260,6 +262,8 @@ bool set_alpha(Scene &s, int material, int texture, float cutoff, const char *wh
 
 // a medium (scene.cpp): checks the record and appends it -> medium id, or -rt_status
 int add_medium(Scene &s, const rt_medium &m);
+// the asymmetry g of a medium's phase function: checks it and stores it (|g| < 1e-3 as 0) -> RT_OK or an rt_status
+int set_medium_phase(Scene &s, int medium, float g);
 // a moving sphere (scene.cpp): checks the record and appends it -> mover id, or -rt_status
 int add_moving_sphere(Scene &s, const rt_moving_sphere &m);
 
