@@ -225,6 +225,21 @@ int rt_scene_get_light_sampling(const rt_scene *s); /* 1, 0, or -rt_status */
  * they were, an emissive triangle being reached by the BSDF sample alone.  JSON: top-level "mesh_lights": true. */
 int rt_scene_set_mesh_lights(rt_scene *s, int on);
 int rt_scene_get_mesh_lights(const rt_scene *s); /* 1, 0, or -rt_status */
+/* Light sampling in participating media: with on = 1 a scene that has media AND light sampling with something to
+ * sample renders through kernels that combine them (rt_opts.variant 0, 16, 36 or 44; rt_stats.kernel_variant reports
+ * layout | 2048 | 256) instead of being refused.  A medium vertex takes a light sample where a surface vertex does -- after
+ * the depth count and a survived roulette draw, the three light draws behind the roulette draw -- with the phase function as
+ * its density: pdf_b = 1 / (4 pi) for the stored g = 0, rt_phase_hg_eval(g, w . w_l) otherwise (w the unit direction of
+ * travel), f = albedo x pdf_b without a cosine, the power heuristic against the light's density, a point, spot or distant
+ * light at weight 1.  Its continuation carries pdf_b of the direction it drew, so an emitter it reaches is weighed as behind
+ * a surface vertex.  A shadow ray takes NO draw: every medium, in list order, adds sigma (b - a) |d| of its stay [a, b]
+ * (rt_medium_interval over the shadow ray's own range) to an optical depth tau, and an unoccluded sample is multiplied by
+ * exp(-tau) (rt_media_transmittance).  Any surface occludes, glass included.  The switch acts only together with media and
+ * light sampling that has something to sample: alone it changes no table and no frame.  Refused with RT_ERR_ARG beside
+ * everything media refuse: the switch (acting) with a projection other than the perspective one.  Off by default; JSON:
+ * top-level "media_light_sampling": true, written only when on. */
+int rt_scene_set_media_light_sampling(rt_scene *s, int on);
+int rt_scene_get_media_light_sampling(const rt_scene *s); /* 1, 0, or -rt_status */
 /* Nested grid: a second grid level for scenes whose geometry is clustered (a detailed mesh standing in a room).  The candidate
  * search is one uniform grid whose cell comes from the extent of all primitives; a cell that a dense mesh overfills can only
  * hand its members to the set that is tested for every query.  With on = 1 such a scene -- one whose flat tables have a cell
@@ -341,7 +356,7 @@ int rt_environment_sample(const rt_scene *s, float u1, float u2, float dir[3], f
  * its draw before the query.
  * A scene with media gets the wide tables and renders through kernels of its own (rt_opts.variant 0, 16, 36 or 44;
  * rt_stats.kernel_variant reports layout | 2048) through every render entry point.  Refused with RT_ERR_ARG: media together
- * with light sampling that has something to sample, with an environment map, or with nested cells; rt_render_hip_count; any
+ * with light sampling that has something to sample (unless rt_scene_set_media_light_sampling is on), with an environment map, or with nested cells; rt_render_hip_count; any
  * other variant.  Feature passes (rt_render_hip_feature) ignore media: they record the first SURFACE hit, so the denoiser's
  * guides do not see fog.
  * Errors of the add calls: RT_ERR_ARG null pointers; RT_ERR_SCENE a negative or non-finite density, an albedo outside [0, 1],
@@ -378,6 +393,11 @@ int rt_scene_clear_media(rt_scene *s);
  * [0.001, t_max].  1: non-empty (a < b), with *t_in = a and *t_out = b; 0: empty; -RT_ERR_ARG for null arguments or a shape
  * that is neither a sphere nor a box. */
 int rt_medium_interval(const rt_medium *m, const float orig[3], const float dir[3], float t_max, float *t_in, float *t_out);
+/* Host evaluation of a shadow ray's transmittance through the scene's media (no GPU needed): over the segment
+ * o + t d, t in [0.001, t_max], every medium of positive density in list order adds x = sigma * (b - a), tau = fma(x, |d|, tau)
+ * with [a, b] its rt_medium_interval and |d| = sqrt(d.d); *T = exp(-tau) in fp32, exactly 1 when no stay is non-empty.
+ * A shadow ray to a light point y has d = y - o and t_max = 0.999. */
+int rt_media_transmittance(const rt_scene *s, const float orig[3], const float dir[3], float t_max, float *T);
 int rt_scene_set_medium_phase(rt_scene *s, int medium, float g);
 int rt_scene_get_medium_phase(const rt_scene *s, int medium, float *g); /* the STORED value: 0 after a set of 5e-4 */
 /* Host evaluations of the device's phase function (no GPU needed).  sample: the direction a vertex with asymmetry g (non-zero,

@@ -524,6 +524,9 @@ public:
     // mesh lights: emissive triangles join the emitters that light sampling samples (rt_scene_set_mesh_lights)
     void set_mesh_lights(bool on) { check(rt_scene_set_mesh_lights(s_, on ? 1 : 0), "set_mesh_lights"); }
     bool mesh_lights() const { return rt_scene_get_mesh_lights(s_) > 0; }
+    // light sampling in participating media: medium vertices take light samples, shadow rays see the media (rt_scene_set_media_light_sampling)
+    void set_media_light_sampling(bool on) { check(rt_scene_set_media_light_sampling(s_, on ? 1 : 0), "set_media_light_sampling"); }
+    bool media_light_sampling() const { return rt_scene_get_media_light_sampling(s_) > 0; }
     // nested grid: overfull cells of the candidate grid get a sub-grid of their own (rt_scene_set_nested_grid)
     void set_nested_grid(bool on) { check(rt_scene_set_nested_grid(s_, on ? 1 : 0), "set_nested_grid"); }
     bool nested_grid() const { return rt_scene_get_nested_grid(s_) > 0; }

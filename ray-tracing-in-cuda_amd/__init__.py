@@ -303,6 +303,8 @@ _sig("rt_scene_get_light_sampling", C.c_int, _p)
 _sig("rt_scene_get_lights", C.c_int, _p, _p, C.c_int)
 _sig("rt_scene_set_mesh_lights", C.c_int, _p, C.c_int)
 _sig("rt_scene_get_mesh_lights", C.c_int, _p)
+_sig("rt_scene_set_media_light_sampling", C.c_int, _p, C.c_int)
+_sig("rt_scene_get_media_light_sampling", C.c_int, _p)
 _sig("rt_scene_set_environment", C.c_int, _p, C.c_int, C.c_int, _p, C.c_float, C.c_float)
 _sig("rt_scene_set_environment_file", C.c_int, _p, C.c_char_p, C.c_float, C.c_float)
 _sig("rt_scene_get_environment", C.c_int, _p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float), _p,
@@ -318,6 +320,7 @@ _sig("rt_scene_set_medium_phase", C.c_int, _p, C.c_int, C.c_float)
 _sig("rt_scene_get_medium_phase", C.c_int, _p, C.c_int, C.POINTER(C.c_float))
 _sig("rt_phase_hg_sample", C.c_int, C.c_float, _f3, C.c_float, C.c_float, _f3)
 _sig("rt_phase_hg_eval", C.c_float, C.c_float, C.c_float)
+_sig("rt_media_transmittance", C.c_int, _p, _f3, _f3, C.c_float, C.POINTER(C.c_float))
 _sig("rt_scene_add_moving_sphere", C.c_int, _p, _f3, _f3, C.c_float, C.c_int)
 _sig("rt_scene_moving_sphere_count", C.c_int, _p)
 _sig("rt_scene_get_moving_spheres", C.c_int, _p, _p, C.c_int)
@@ -395,6 +398,7 @@ C_SYMBOLS = [
     "rt_scene_output_file", "rt_scene_rotate_cylinders", "rt_scene_set_output_file", "rt_scene_dna", "rt_scene_clone",
     "rt_scene_set_light_sampling", "rt_scene_get_light_sampling", "rt_scene_get_lights",
     "rt_scene_set_mesh_lights", "rt_scene_get_mesh_lights",
+    "rt_scene_set_media_light_sampling", "rt_scene_get_media_light_sampling", "rt_media_transmittance",
     "rt_render_hip_adaptive", "rt_render_hip_adaptive_device",
     "rt_scene_set_nested_grid", "rt_scene_get_nested_grid", "rt_scene_nested_info", "rt_scene_quad_counts",
     "rt_scene_set_environment", "rt_scene_set_environment_file", "rt_scene_get_environment", "rt_environment_eval",
@@ -496,6 +500,23 @@ class Scene:
     @property
     def mesh_lights(self) -> bool:
         return _check_id(_lib.rt_scene_get_mesh_lights(self._h), "get_mesh_lights") != 0
+
+    def set_media_light_sampling(self, on: bool = True):
+        """Light sampling in participating media (include/rtmi.h, rt_scene_set_media_light_sampling): with media and light
+        sampling that has something to sample, medium vertices take light samples and shadow rays are attenuated by the
+        media they cross; False, the default, leaves that combination refused."""
+        _check(_lib.rt_scene_set_media_light_sampling(self._h, 1 if on else 0), "set_media_light_sampling")
+
+    @property
+    def media_light_sampling(self) -> bool:
+        return _check_id(_lib.rt_scene_get_media_light_sampling(self._h), "get_media_light_sampling") != 0
+
+    def media_transmittance(self, orig, direction, t_max=0.999):
+        """Host evaluation of a shadow ray's transmittance through the scene's media (rt_media_transmittance): exp(-tau) over
+        orig + t direction, t in [0.001, t_max], as the device text sums tau; exactly 1.0 when the ray stays in no medium."""
+        T = C.c_float()
+        _check(_lib.rt_media_transmittance(self._h, _v3(orig), _v3(direction), float(t_max), C.byref(T)), "media_transmittance")
+        return T.value
 
     def set_environment(self, rgb=None, scale: float = 1.0, rotate: float = 0.0, file: str = None):
         """Environment map (include/rtmi.h, rt_scene_set_environment): ``rgb`` is a rows x cols x 3 float array in lat-long

@@ -197,6 +197,18 @@ int rt_scene_get_mesh_lights(const rt_scene *s) {
     return s->s.mesh_lights ? 1 : 0;
 }
 
+int rt_scene_set_media_light_sampling(rt_scene *s, int on) {
+    if (bad_scene(s, "rt_scene_set_media_light_sampling")) return RT_ERR_ARG;
+    s->s.media_light_sampling = on != 0;
+    s->s.touch();
+    return RT_OK;
+}
+
+int rt_scene_get_media_light_sampling(const rt_scene *s) {
+    if (bad_scene(s, "rt_scene_get_media_light_sampling")) return -RT_ERR_ARG;
+    return s->s.media_light_sampling ? 1 : 0;
+}
+
 int rt_scene_set_nested_grid(rt_scene *s, int on) {
     if (bad_scene(s, "rt_scene_set_nested_grid")) return RT_ERR_ARG;
     s->s.nested_grid = on != 0;
@@ -1209,6 +1221,27 @@ int rt_medium_interval(const rt_medium *m, const float orig[3], const float dir[
     if (t_in) *t_in = a;
     if (t_out) *t_out = b;
     return hit ? 1 : 0;
+}
+
+// a shadow ray's transmittance through the scene's media: the media walk of a lane in its shadow phase, from the
+// device's own functions (rt_media.h) -- len = sqrt(d.d) as the kernels form it, the media in list order
+int rt_media_transmittance(const rt_scene *s, const float orig[3], const float dir[3], float t_max, float *T) {
+    if (bad_scene(s, "rt_media_transmittance")) return RT_ERR_ARG;
+    if (!orig || !dir || !T) {
+        set_error("rt_media_transmittance: null argument");
+        return RT_ERR_ARG;
+    }
+    const float ra = fmaf(dir[0], dir[0], fmaf(dir[1], dir[1], dir[2] * dir[2]));
+    const float len = sqrtf(ra);
+    float tau = 0.0f;
+    for (const rt_medium &m : s->s.media) {
+        float a, b;
+        if (m.density > 0.0f && medium_interval(m.shape, m.f[0], m.f[1], m.f[2], m.f[3], m.f[4], m.f[5], orig[0], orig[1], orig[2], dir[0],
+                                                dir[1], dir[2], t_max, a, b))
+            tau = medium_tau_add(m.density, a, b, len, tau);
+    }
+    *T = media_transmittance(tau);
+    return RT_OK;
 }
 
 // ---- anisotropic media: a medium's asymmetry and the host evaluations of the device's phase function (rt_phase.h)

@@ -28,6 +28,7 @@
 // Camera projections: --projection TYPE[:P1[,P2]] replaces the scene file's -- perspective, orthographic:HEIGHT,
 // panoramic[:HFOV[,VFOV]], fisheye[:FOV] (degrees; rt_scene_set_projection).  --pick and --focus-at follow the scene's camera.
 // Mesh lights: --mesh-lights lists emissive triangles among the emitters --nee samples (rt_scene_set_mesh_lights).
+// Light sampling in media: --nee-media is --nee plus rt_scene_set_media_light_sampling.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -58,7 +59,7 @@ static int usage(const char *argv0) {
     fprintf(stderr,
             "usage: %s [-f scene.json | --rtiow] [-w W] [-h H] [-d DEPTH] [-spp N] [-o out.ppm]\n"
             "          [--seed S] [--scene-seed S] [--device N] [--chunk N] [--dump-json file] [--count] [--no-png]\n"
-            "          [--acc-in sums.bin] [--acc-out sums.bin] [--spp-begin FIRST] [--rr SURVIVAL_PROBABILITY] [--nee]\n"
+            "          [--acc-in sums.bin] [--acc-out sums.bin] [--spp-begin FIRST] [--rr SURVIVAL_PROBABILITY] [--nee | --nee-media]\n"
             "          [--mesh-lights] [--nested-grid] [--env map.hdr [--env-scale S] [--env-rotate DEG]]\n"
             "          [--gpus N] [--tile-rows R] [--adaptive THRESHOLD [--min-spp N] [--max-spp N]]\n"
             "          [--denoise] [--aov PREFIX] [--feature-spp N]\n"
@@ -129,6 +130,7 @@ int main(int argc, char **argv) {
     long long spp_begin = -1;
     double rr = -1.0;  // Russian roulette: keep the scene file's setting
     bool nee = false;  // light sampling: on if the scene file or --nee says so
+    bool nee_media = false;    // light samples in participating media too: on if the scene file or --nee-media says so
     bool mesh_lights = false;  // emissive triangles are sampled too: on if the scene file or --mesh-lights says so
     bool nested = false;  // nested grid: on if the scene file or --nested-grid says so
     std::string env_file;  // environment map: replaces the scene file's
@@ -181,6 +183,7 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--rr")) rr = atof(need("--rr"));
         else if (!strcmp(argv[i], "--nee")) nee = true;
         else if (!strcmp(argv[i], "--mesh-lights")) mesh_lights = true;
+        else if (!strcmp(argv[i], "--nee-media")) nee = nee_media = true;
         else if (!strcmp(argv[i], "--nested-grid")) nested = true;
         else if (!strcmp(argv[i], "--projection")) {
             const std::string v = need("--projection");
@@ -373,6 +376,10 @@ int main(int argc, char **argv) {
     if (rt_scene_get_light_sampling(sc) == 0 && rt_scene_get_analytic_lights(sc, nullptr, 0) > 0)
         fprintf(stderr, "rtmi: light sampling is off: the scene's %d point / spot / distant lights light nothing (--nee switches it on)\n",
                 rt_scene_get_analytic_lights(sc, nullptr, 0));
+    if (nee_media && rt_scene_set_media_light_sampling(sc, 1) != RT_OK) {
+        fprintf(stderr, "rtmi: %s\n", rt_last_error());
+        return 1;
+    }
     if (mesh_lights && rt_scene_set_mesh_lights(sc, 1) != RT_OK) {
         fprintf(stderr, "rtmi: %s\n", rt_last_error());
         return 1;

@@ -18,7 +18,7 @@ enum KernelFamily {
     K_NESTED,   // render_nested_kernel: the nested-grid walk (variant 52)
     K_FEATURE,  // render_feature_kernel: first-hit feature passes
     K_ENV,      // render_env_kernel: an environment map (plain, with light sampling, or a feature pass)
-    K_MEDIA,    // render_media_kernel
+    K_MEDIA,    // render_media_kernel; with light sampling (key.nee): media_nee_kernel
     K_MOTION,   // render_motion_kernel
     K_TRACE,    // trace_kernel: ray queries (rt_trace_hip); not a render kernel, launched through launch_trace
 };
@@ -29,7 +29,7 @@ struct KernelKey {
     bool ext;              // built with triangles and image textures (every family but K_PLAIN and K_NESTED: always)
     bool count = false;    // a counting build (rt_render_hip_count).  It serves scenes with and without triangles / textures:
                            // find_kernel() does not compare `ext` for it
-    bool nee = false;      // K_ENV: with light sampling
+    bool nee = false;      // K_ENV, K_MEDIA: with light sampling
     bool feature = false;  // K_ENV: a feature pass
     bool alpha = false;    // an instance of alpha_kernel.h: the family's kernel with the alpha cutouts' code, for a scene
                            // with masks; every other scene runs the rows without it, whose code knows nothing of masks
@@ -123,6 +123,7 @@ const KernelRow *camera_kernel_rows(size_t *n);        // camera_kernel.hip: K_P
 const KernelRow *camera_nee_kernel_rows(size_t *n);    // camera_nee_kernel.hip: K_NEE, K_ENV with a projection
 const KernelRow *camera_media_kernel_rows(size_t *n);  // camera_media_kernel.hip: K_MEDIA with a projection
 const KernelRow *media_kernel_rows(size_t *n);   // render_media.hip
+const KernelRow *media_nee_kernel_rows(size_t *n);  // media_nee_kernel.hip: K_MEDIA with light sampling
 const KernelRow *motion_kernel_rows(size_t *n);  // render_motion.hip
 const KernelRow *trace_kernel_rows(size_t *n);   // trace.hip
 

@@ -1,6 +1,6 @@
 // The body of the render kernels: included INSIDE render_kernel, render_nee_kernel, render_nested_kernel and render_feature_kernel
-// (render_kernel.hip), render_env_kernel (render_env.hip), render_media_kernel (render_media.hip) and render_motion_kernel
-// (render_motion.hip), after their template arguments and a constexpr NEE, AOV, ENV, MEDIA, MOTION and QUERY (with the TraceArgs
+// (render_kernel.hip), render_env_kernel (render_env.hip), render_media_kernel (render_media.hip), media_nee_kernel
+// (media_nee_kernel.hip: MEDIA and NEE together) and render_motion_kernel (render_motion.hip), after their template arguments and a constexpr NEE, AOV, ENV, MEDIA, MOTION and QUERY (with the TraceArgs
 // TQ of render_device.h: null there), and inside trace_kernel (trace.hip), where QUERY is set.  The device functions it
 // calls are render_device.h's, which each of those files includes.  As text rather than a force-inlined device function, so that the render_kernel
 // instances compile to the very instructions they did before light sampling came (a device function that takes the
@@ -330,9 +330,17 @@
             // the surface winner; a non-empty stay in a medium of positive density takes ONE draw, the free-flight distance.
             // The smallest event wins over the surface hit.  What outlives the walk: med_t, med_i and the winner's asymmetry med_g
             // (.w of its record 2, which the walk reads anyway; 0: the isotropic medium).
+            // MEDIA && NEE: a lane in its shadow phase draws nothing and proposes no event -- each non-empty stay adds its
+            // optical depth sigma (b - a) |d| to tau, which lives where med_t lives (0 before the walk); lanes of both kinds share
+            // the trip through the loop and its wave-uniform record loads
             float med_t = INFINITY;
             int med_i = -1;
             float med_g = 0.0f;
+            bool med_sh = false;
+            if constexpr (MEDIA && NEE) {
+                med_sh = shadow != 0;
+                if (med_sh) med_t = 0.0f;
+            }
             if constexpr (MEDIA) {
                 if (!unfinished) {
                     const int n_med = __builtin_amdgcn_readfirstlane(__float_as_int(image[P.off_cam + 1].w));
@@ -343,6 +351,10 @@
                         float ta, tb;
                         if (g1.w > 0.0f &&
                             medium_interval(__float_as_int(g2.z), g0.x, g0.y, g0.z, g0.w, g2.x, g2.y, ox, oy, oz, dx, dy, dz, best_t, ta, tb)) {
+                            if (MEDIA && NEE && med_sh) {
+                                med_t = medium_tau_add(g1.w, ta, tb, len, med_t);
+                                continue;
+                            }
                             const float u = rng_next<COUNT>(rng);
                             const float t = ta + (-logf(1.0f - u) / g1.w) / len;
                             if (t < tb && t < med_t) med_t = t, med_i = m, med_g = g2.w;
@@ -395,6 +407,11 @@
                     }
                 }
                 RT_SHADOW_VERDICT(best_id < 0)
+                // MEDIA: what the media between the vertex and its light point let through; tau = 0: exactly 1
+                if constexpr (MEDIA && NEE) {
+                    const float T = media_transmittance(med_t);
+                    L_r *= T, L_g *= T, L_b *= T;
+                }
             } else if (MEDIA && med_i >= 0) {
                 // a medium event: a vertex without a normal and without a material record (the scatter step takes the albedo
                 // from the medium's record), which emits nothing.  Where a surface vertex keeps its normal's x, a medium vertex
@@ -1328,6 +1345,18 @@
                     const float wx = ndx * il, wy = ndy * il, wz = ndz * il;
                     cpdf = kind == MK_METAL ? metal_pdf(wx, wy, wz, mrx, mry, mrz, mfz) : fmaxf(0.0f, dot3(wx, wy, wz, nx, ny, nz)) * kInvPi;
                 }
+                // MEDIA: a medium vertex takes a light sample.  Its pdf_b is the phase function's -- 1 / (4 pi) for the
+                // stored g = 0 (the rejection loop's normalize(s) is uniform), phase_hg_eval(g, cos) otherwise, cos between the unit
+                // direction of travel w = inv_len d and the unit direction drawn -- and w waits where metal keeps its mirror
+                // direction, for the light's direction in step (7)
+                if constexpr (MEDIA && NEE) {
+                    if (kind == MK_MEDIUM) {
+                        nee_v = true;
+                        mrx = inv_len * dx, mry = inv_len * dy, mrz = inv_len * dz;
+                        const float il = 1.0f / sqrtf(dot3(ndx, ndy, ndz, ndx, ndy, ndz));
+                        cpdf = nx == 0.0f ? RT_PHASE_ISOTROPIC : phase_hg_eval(nx, dot3(ndx * il, ndy * il, ndz * il, mrx, mry, mrz));
+                    }
+                }
                 mis_pdf = cpdf;
                 vb_r = beta_r * at_r, vb_g = beta_g * at_g, vb_b = beta_b * at_b;
                 // (the throughput in front of a glossy vertex; rough glass: times its tint, which is not part of glass_eval)
@@ -1570,6 +1599,11 @@
                 }
                 glossy_eval_body(glass ? GLOSSY_GLASS : (plastic ? GLOSSY_PLASTIC : GLOSSY_METAL), nx, ny, nz, mrx, mry, mrz, g_alpha, f_r, f_g, f_b, rh_r,
                                  rh_g, rh_b, (gkind & 1) ? q1.w : q0.z, wx, wy, wz, gf_r, gf_g, gf_b, pb, !ENV);
+            } else
+            if (MEDIA && NEE && kind == MK_MEDIUM) {
+                // a medium vertex: the phase function's density of the light's direction about the direction of travel
+                // (kept in mr); no cosine, so f = albedo x pdf_b and the lambertian form below holds
+                pb = nx == 0.0f ? RT_PHASE_ISOTROPIC : phase_hg_eval(nx, dot3(mrx, mry, mrz, wx, wy, wz));
             } else
             if (wn > 0.0f) pb = mfz > 0.0f ? metal_pdf(wx, wy, wz, mrx, mry, mrz, mfz) : wn * kInvPi;
             // f cos / p_l x the power heuristic's p_l^2 / (p_l^2 + pdf_b^2) = albedo x pdf_b p_l / (p_l^2 + pdf_b^2)

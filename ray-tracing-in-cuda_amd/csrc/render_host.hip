@@ -897,9 +897,17 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
             return RT_ERR_ARG;
         }
     }
+    // light sampling in media (rt_scene_set_media_light_sampling): acts only with media and something to sample
+    const bool media_nee = media && nee && s.media_light_sampling;
     if (media) {
-        if (nee) {
-            set_error("this scene has participating media and light sampling with emitters to sample, which no kernel combines: switch one of them off");
+        if (nee && !media_nee) {
+            set_error("this scene has participating media and light sampling with emitters to sample, which no kernel combines: switch one of them off "
+                      "(or switch light sampling in media on: rt_scene_set_media_light_sampling, \"media_light_sampling\": true, --nee-media)");
+            return RT_ERR_ARG;
+        }
+        if (media_nee && camera) {
+            set_error("this scene has light sampling in participating media and a camera projection other than the perspective one, which no "
+                      "kernel combines: render with the perspective projection or switch rt_scene_set_media_light_sampling off");
             return RT_ERR_ARG;
         }
         if (env) {
@@ -910,7 +918,7 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
             set_error("this scene has participating media and the nested grid, which no kernel combines: switch the nested grid off");
             return RT_ERR_ARG;
         }
-        if (!find_kernel({K_MEDIA, variant, true})) {
+        if (!find_kernel({K_MEDIA, variant, true, false, media_nee})) {
             set_error("kernel variant %u does not carry participating media (the media kernels are variants 0, 16, 36 and 44)", variant);
             return RT_ERR_ARG;
         }
@@ -1014,7 +1022,7 @@ static int render_impl(const rt_scene *sc, const rt_opts *o, void *d_rgb_sum, vo
     // (a scene with alpha masks, DESIGN 7v: the family's instance of alpha_kernel.h; every other scene: the rows it always ran)
     // (a projection, DESIGN 7w: the family's instance of camera_kernel.h, likewise)
     const KernelRow *kernel = env            ? find_kernel({K_ENV, variant, true, false, nee, feature >= 0, alpha, camera})
-                              : media        ? find_kernel({K_MEDIA, variant, true, false, false, false, false, camera})
+                              : media        ? find_kernel({K_MEDIA, variant, true, false, media_nee, false, false, camera})
                               : motion       ? find_kernel({K_MOTION, variant, true, false, false, false, alpha, camera})
                               : feature >= 0 ? find_kernel({K_FEATURE, variant, true, false, false, false, alpha, camera})
                               : nee          ? find_kernel({K_NEE, variant, true, false, false, false, alpha, camera})

@@ -222,7 +222,7 @@ bool has_ablations() { return RTMI_ABLATIONS != 0; }
 const KernelRow *find_kernel(const KernelKey &key) {
     const KernelRow *(*const tables[])(size_t *) = {render_kernel_rows, env_kernel_rows, media_kernel_rows, motion_kernel_rows, trace_kernel_rows,
                                                        alpha_kernel_rows, alpha_nee_kernel_rows,
-                                                       camera_kernel_rows, camera_nee_kernel_rows, camera_media_kernel_rows};
+                                                       camera_kernel_rows, camera_nee_kernel_rows, camera_media_kernel_rows, media_nee_kernel_rows};
     for (auto rows_of : tables) {
         size_t n = 0;
         const KernelRow *rows = rows_of(&n);

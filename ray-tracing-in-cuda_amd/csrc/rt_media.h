@@ -17,6 +17,8 @@
 // the asymmetry g of a medium's phase function (rt_phase.h), .w of record 2: |g| <= MAX, and |g| < SNAP is stored as 0
 #define RT_PHASE_G_MAX 0.99f
 #define RT_PHASE_G_SNAP 1e-3f
+// the isotropic phase function's density per steradian, 1 / (4 pi): pdf_b of a medium vertex with the stored g = 0
+#define RT_PHASE_ISOTROPIC 0.0795774715459476678844f
 
 namespace rtmi {
 
@@ -55,5 +57,18 @@ RTMI_HD bool medium_interval(int shape, float f0, float f1, float f2, float f3, 
     }
     return a < b;
 }
+
+// A shadow ray through the media: the optical depth tau of the segment o + t d, t in [0.001, t_max], is summed
+// over the media in list order -- a non-empty stay [a, b] in a medium of density sigma adds sigma (b - a) |d| as
+//   s = b - a;  x = sigma * s;  tau = fma(x, len, tau)       (len = |d|: the caller's root of d.d)
+// and an unoccluded light sample is multiplied by T = exp(-tau): expf of either side's math library, as the azimuth's
+// sincosf is.  tau = 0 (no stay) gives exactly 1 without a call.
+RTMI_HD float medium_tau_add(float sigma, float a, float b, float len, float tau) {
+    const float s = b - a;
+    const float x = sigma * s;
+    return fmaf(x, len, tau);
+}
+
+RTMI_HD float media_transmittance(float tau) { return tau > 0.0f ? expf(-tau) : 1.0f; }
 
 }  // namespace rtmi

@@ -1193,6 +1193,10 @@ int scene_from_json(const char *text, size_t len, Scene &s, const char *base_dir
         if (f->kind != JsonValue::Bool) r.fail("top level: \"light_sampling\" must be a boolean");
         else s.light_sampling = f->b;
     }
+    if (const JsonValue *f = root.find("media_light_sampling")) {
+        if (f->kind != JsonValue::Bool) r.fail("top level: \"media_light_sampling\" must be a boolean");
+        else s.media_light_sampling = f->b;
+    }
     if (const JsonValue *f = root.find("mesh_lights")) {
         if (f->kind != JsonValue::Bool) r.fail("top level: \"mesh_lights\" must be a boolean");
         else s.mesh_lights = f->b;
@@ -1893,6 +1897,7 @@ std::string scene_to_json(const Scene &s) {
         o += "\n  ],\n";
     }
     if (s.mesh_lights) o += "  \"mesh_lights\": true,\n";
+    if (s.media_light_sampling) o += "  \"media_light_sampling\": true,\n";
     if (s.nested_grid) o += "  \"nested_grid\": true,\n";
     if (s.env) {
         o += "  \"environment\": {";

@@ -79,6 +79,7 @@ struct Scene {
     float rr_p = 0.0f;  // Russian-roulette survival probability per bounce, 0 = off
     bool light_sampling = false;  // next-event estimation + MIS (rt_scene_set_light_sampling)
     bool mesh_lights = false;     // scene_lights() also lists emissive triangles (rt_scene_set_mesh_lights)
+    bool media_light_sampling = false;  // light samples at medium vertices and through media (rt_scene_set_media_light_sampling)
     bool nested_grid = false;     // overfull grid cells get a sub-grid (rt_scene_set_nested_grid)
     std::string output_file = "main.png";  // parser.hpp:566-567 default
     CameraParams cam;
