@@ -116,7 +116,7 @@ def ref_cases():
     return cases
 
 
-# which case shows which deliberate mistake of ref64_media_nee (the others may too)
+# which case shows which of the four deliberate mistakes of DESIGN 7z that ref64.trace()'s `perturb` knows (the others may too)
 MISTAKES = {"no_transmittance": "camera inside thin fog", "isotropic_pdf": "thin fog, g = 0.7",
             "shadow_flight_draw": "camera inside thin fog", "medium_full_weight": "white furnace, g = 0.7"}
 

@@ -3,7 +3,10 @@ with a device behind it, the one-sample frames of a kernel family, the verdict o
 the bodies of the fixtures and tests that every feature suite (test_gpu_{quads,glossy,glass,noise,bump,normal_map,pbr,alpha,
 mesh_lights,analytic_lights}.py) holds: the case cache, the fp64 check, the mistake check, the same-bytes check, the command-line
 check and the ray-query check.  Each takes the feature's scenes module M (feature_scenes.py says what one provides).  Plain
-functions: the fixtures stay in the test files, which skip each on its own."""
+functions: the fixtures stay in the test files, which skip each on its own.  Last, what test_phase.py and test_media_nee.py
+share on the host: the check against golden/ref64_media_pin.npz."""
+import hashlib
+import json
 import os
 import subprocess
 import sys
@@ -207,3 +210,28 @@ def check_ray_queries_of_twins(sc, twin, bound):
     assert hit.sum() >= 500
     assert a.tobytes() == b.tobytes()
     return a, hit
+
+
+def check_media_pin(rtmi, golden_dir, key, sc):
+    """golden/ref64_media_pin.npz holds what the reference returned on `key`'s case while anisotropic media and light sampling
+    in media were path tracers of their own beside ref64.trace (golden/make_ref64_media_pin.py).  Exact: the draws of the fp64 and
+    the fp32 run, which samples took the same branches at fp32, every count of that commit's tally; the fp64 radiance after
+    rounding to float32, as it is stored; the fp32 run's by its bytes.  sc: the case's scene, brought to the pinned frame here.
+    Returns (RefScene, the uniforms, the fp64 radiance, the tally)"""
+    pin = np.load(os.path.join(golden_dir, "ref64_media_pin.npz"))
+    cases = json.loads(str(pin["cases"]))
+    size = lambda c: c["width"] * c["height"] * c["samples"]
+    rec, at = cases[key], sum(size(c) for c in list(cases.values())[:list(cases).index(key)])
+    n = size(rec)
+    sc.override(width=rec["width"], height=rec["height"])
+    words = R.uniforms(rtmi, rec["seed"], rec["width"], rec["height"], 0, rec["samples"], rec["draws"])
+    S, log = R.RefScene(sc), R.new_log()
+    rgb, sig, draws = R.trace(S, words, log=log)
+    rgb32, sig32, draws32 = R.trace(S, words, dtype=np.float32)
+    tally = R.tally(sig, S, log)
+    assert np.array_equal(draws, pin["draws64"][at:at + n]) and np.array_equal(draws32 - draws, pin["draws32_minus_64"][at:at + n]), key
+    assert np.array_equal(np.packbits(R.same_signature(sig, sig32)), pin["stable"][at // 8:(at + n) // 8]), key
+    assert {k: tally[k] for k in rec["tally"]} == rec["tally"], (key, tally)
+    assert np.allclose(rgb.astype(np.float32), pin["rgb64"][at:at + n], rtol=1e-9, atol=1e-12), key
+    assert hashlib.sha256(np.ascontiguousarray(rgb32).tobytes()).hexdigest() == rec["rgb32"], key
+    return S, words, rgb, tally

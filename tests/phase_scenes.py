@@ -1,9 +1,11 @@
-"""Scenes shared by the anisotropic-media tests, CPU and GPU: the scene class of ref64_phase.py -- spheres with solid
-lambertian and diffuse_light materials, a constant or sky-gradient background, a pinhole camera, media with an asymmetry g."""
+"""Scenes shared by the anisotropic-media tests, CPU and GPU: spheres with solid lambertian and diffuse_light
+materials, a constant or sky-gradient background, a pinhole camera, media with an asymmetry g."""
 from nee_scenes import REF_DRAWS, REF_H, REF_K, REF_W  # noqa: F401 (the per-sample comparison's frame, as media_scenes takes it)
 
 MEDIA = 2048  # rt_stats.kernel_variant: a media kernel
 REF_SEED = 113  # the per-sample comparison's seed, of its own
+# what the comparison's premises read of ref64.tally()
+TALLY_KEYS = ("anisotropic_events", "isotropic_events", "surface_after_anisotropic", "both_on_one_path", "media_with_events")
 
 
 def room(rtmi, w=REF_W, h=REF_H, spp=16, depth=6, rr=0.0, sky=False):

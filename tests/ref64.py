@@ -1,9 +1,9 @@
 """An independent statement of the path estimators of DESIGN 7a (light sampling + MIS), 7e (environment maps), 7f (homogeneous
 participating media with isotropic scattering), 7g (motion blur: linearly moving spheres over a per-sample shutter time), 7l
-(smooth shading), 7m (the glossy materials) and 7n-7u (triangle lights, noise textures, bumps, quads, rough glass, point / spot /
-distant lights, the metallic-roughness material, normal maps) and 7v (alpha cutouts), in NumPy, vectorised over a batch of samples, at a floating type
-of the caller's choice (float64: the reference; float32: the same formulas at the kernel's precision, used to measure how many
-samples sit on a branch).
+(smooth shading), 7m (the glossy materials), 7n-7u (triangle lights, noise textures, bumps, quads, rough glass, point / spot /
+distant lights, the metallic-roughness material, normal maps), 7v (alpha cutouts), 7y (anisotropic media) and 7z (light sampling
+in participating media), in NumPy, vectorised over a batch of samples, at a floating type of the caller's choice (float64: the
+reference; float32: the same formulas at the kernel's precision, used to measure how many samples sit on a branch).
 
 Test infrastructure only.  It is written from the definitions -- DESIGN 2 (the integrator, the order of the draws), the
 sections above, include/rtmi.h's text of the records, and the reference's primitive, material and texture definitions -- with
@@ -12,8 +12,9 @@ shares no code with the kernels or with oracle/.
 
 There is ONE integrator loop, trace(), one hit record, hit_record(), one texture lookup, texture_value(), and one light sample,
 sample_light().  An extension joins them with records on RefScene, read ONCE from the product scene (lights, media, movers,
-noise parameters, bumps, normal maps, pbr maps, analytic lights, alpha masks: each empty unless the scene has them) or records the scene's
-tables already hold (a triangle's vertex normals, a primitive's or a material's type), a branch in those functions or a block
+the media's asymmetries, noise parameters, bumps, normal maps, pbr maps, analytic lights, alpha masks: each empty unless the scene
+has them) or records the scene's tables already hold (a triangle's vertex normals, a primitive's or a material's type), a branch
+in those functions or a block
 in the loop, columns or event codes in the signature, counters in trace()'s `log` for what the signature has no column for,
 and keys in tally(); its deliberate mistakes are names in trace()'s one `perturb`.  A model large enough for a file of its own
 is imported HERE, holds no loop and imports nothing of this file (ref64_base.py holds what they share):
@@ -24,23 +25,24 @@ is imported HERE, holds no loop and imports nothing of this file (ref64_base.py 
     ref64_analytic_lights   7s  the light records, the three lights' samples
     ref64_pbr               7t  the bytes of a hit, the choice between metal and plastic
     ref64_normal_map        7u  the texel's decoding, every primitive's tangents, the frame and the rule
-(triangle lights, 7n, quads, 7q, and alpha cutouts, 7v -- opaque_hit(), the query trace() makes -- are short enough to stand
-here).  No module restates trace(), and none swaps a function of
-this one.  The reference evaluates the scene it is given: which combinations the product renders is the product's to refuse and
-test_refusals' to assert.  Where two extensions meet and DESIGN defines no order -- a light sample at a medium vertex, a shadow
-ray through a medium or past a mover -- trace() raises NotImplementedError.
+    ref64_phase             7y  the Henyey-Greenstein distribution, its inverse and density, the frame, a vertex's direction
+(triangle lights, 7n, quads, 7q, alpha cutouts, 7v -- opaque_hit(), the query trace() makes -- and a shadow ray's optical depth,
+7z -- optical_depth() -- are short enough to stand here).  No module restates trace(), and none swaps a function of this one.  The
+reference evaluates the scene it is given: which combinations the product renders is the product's to refuse and test_refusals'
+to assert.  Where two extensions meet and DESIGN defines no order -- a shadow ray past a mover, a shadow ray towards the
+environment light in a scene with media -- trace() raises NotImplementedError.
 
 Inputs are the product's exported tables (Scene.prims / materials / textures / lights / media / moving_spheres / get_camera /
-info / environment / noise / bump / normal_map / pbr_map / analytic_lights / alpha / get_image_alpha), the light alias table and the environment's CDF
-tables as the packed image stores them (table_image, found by content), the uniforms of rtmi.sample_stream and, for movers, the
+info / environment / noise / bump / normal_map / pbr_map / analytic_lights / alpha / get_image_alpha / medium_phase), the light
+alias table and the environment's CDF tables as the packed image stores them (table_image, found by content), the uniforms of rtmi.sample_stream and, for movers, the
 shutter times of rtmi.shutter_time (one per sample: the time is no draw of the stream) and the pixels of the image textures
 (Scene.get_image).  Out of scope: the nested grid (a candidate search, which this reference has none of: it scans the lists).
 
 trace() returns, per sample, the radiance, an event signature (one row of integers: per vertex the primitive hit, the mover
 that took over, the set of media that took a free-flight draw and the medium whose event won, what the material did, the
 checker parity, the image texel read, the roulette outcome, the light and texel picked and whether through the alias, the
-shadow ray's verdict and the primitive that stopped it, how an emitter hit was weighted; columns a scene does not exercise
-stay NONE; two samples took the same branches iff their rows are equal; tally() counts the special vertices of a batch from
+shadow ray's verdict, the primitive that stopped it and the media it stayed in, how an emitter hit was weighted; columns a scene
+does not exercise stay NONE; two samples took the same branches iff their rows are equal; tally() counts the special vertices of a batch from
 it) and the number of draws consumed.
 """
 import numpy as np
@@ -51,6 +53,7 @@ import ref64_glass as GL
 import ref64_noise as NO
 import ref64_normal_map as NM
 import ref64_pbr as PB
+import ref64_phase as PH
 from ref64_base import SPHERE, XY_RECT, XZ_RECT, YZ_RECT, CYLINDER, TRIANGLE, QUAD, _affine, _cross, _dot, _rect_axes, _unit
 from ref64_glossy import (ROUGH_METAL, PLASTIC, GLOSSY_MIN_ROUGHNESS, GLOSSY_EVENTS, EV_ROUGH, EV_COAT, EV_BODY, EV_BELOW,
                           EV_ROUGH_ABSORBED, EV_COAT_ABSORBED, alpha_of, r0_of, glossy_sample, glossy_eval, glossy_tally)
@@ -62,9 +65,10 @@ ENVIRONMENT = 100
 POINT, SPOT, DISTANT = AL.POINT, AL.SPOT, AL.DISTANT
 DELTA_LIGHTS = (POINT, SPOT, DISTANT)
 # the counters of trace()'s `log`: what the signature has no column for.  bump_* / nm_*: perturbed vertices in all, on back faces,
-# (nm) whose texel tilts, and where a guard kept n (nm: the texel tilts and the frame was built).  alpha_*: opaque_hit()'s counters
+# (nm) whose texel tilts, and where a guard kept n (nm: the texel tilts and the frame was built).  alpha_*: opaque_hit()'s counters.
+# ended_by_depth: the paths that scattered with no depth left
 ALPHA_COUNTERS = ("masked_hits", "passes", "opaque", "max_passes", "shadow_through", "shadow_queries", "path_queries")
-LOG_KEYS = (("bump_bumped", "bump_back", "bump_kept", "nm_mapped", "nm_back", "nm_tilting", "nm_kept", "quad_back_hits")
+LOG_KEYS = (("bump_bumped", "bump_back", "bump_kept", "nm_mapped", "nm_back", "nm_tilting", "nm_kept", "quad_back_hits", "ended_by_depth")
             + GL.LOG_KEYS + AL.LOG_KEYS + PB.LOG_KEYS + tuple("alpha_" + k for k in ALPHA_COUNTERS))
 
 
@@ -78,17 +82,21 @@ METAL_MIN_FUZZ = 0.05   # metal vertices below this fuzz take no light sample (D
 
 # event codes of the signature
 EV_MISS, EV_EMIT, EV_LAMBERT, EV_METAL, EV_METAL_ABSORBED, EV_REFLECT, EV_REFRACT = range(7)
-EV_MEDIUM = 20
+EV_MEDIUM, EV_MEDIUM_HG = 20, 21  # a medium vertex whose stored g is 0 (the rejection loop) / is not (two draws)
+MEDIUM_EVENTS = (EV_MEDIUM, EV_MEDIUM_HG)
 NONE = -9
 # the signature's columns: two per sample (draws consumed, the first roulette), then one block per vertex.  C_PRIM is the static
 # winner; C_MOVER the mover that took over (-1: none) in a scene with movers; C_DREW the set of media that took a free-flight
 # draw and C_MEDIUM the medium whose event won (-1: none) in a scene with media
 SAMPLE_COLUMNS = 2
 # C_IMAGE_TEXEL the flat index (row x cols + col) of the image texel the vertex's material read; C_BLOCKER the primitive that
-# stopped the shadow ray
+# stopped the shadow ray.  C_TEXEL is the texel the environment light's sample picked and, in a scene with media, the set of
+# media the shadow ray stayed in (C_STAYS): a shadow ray towards the environment in a scene with media raises, so the column is
+# NONE at every vertex of such a scene until the stays are written
 (C_PRIM, C_MISS_TEXEL, C_PARITY, C_EVENT, C_ROULETTE, C_LIGHT, C_TEXEL, C_SHADOW, C_HIT_WEIGHT, C_ALIAS,
  C_MOVER, C_DREW, C_MEDIUM, C_IMAGE_TEXEL, C_BLOCKER) = range(15)
 VERTEX_COLUMNS = 15
+C_STAYS = C_TEXEL
 # C_SHADOW: the light sample reached its light / was occluded / had zero weight (no shadow ray) / was not made because the
 # vertex lies inside the sphere light it picked
 SHADOW_CLEAR, SHADOW_OCCLUDED, SHADOW_NONE, SHADOW_INSIDE = range(4)
@@ -183,6 +191,7 @@ class RefScene:
         self.light_of_prim = {int(l["prim"]): i for i, l in enumerate(self.lights) if l["prim"] >= 0}
         self.movers = sc.moving_spheres() if movers else sc.moving_spheres()[:0]
         self.media = sc.media() if media else sc.media()[:0]
+        self.media_g = np.array([sc.medium_phase(i) for i in range(len(self.media))], np.float32)  # the stored asymmetries (7y)
         # the extensions' records, each empty unless the scene has them.  noise: texture -> the dict of Scene.noise; bumps:
         # material -> (the height field's noise parameters, strength); normal_maps: material -> (image texture, scale); pbr_maps:
         # pbr material -> its metallic-roughness map's texture or -1; analytic: index into lights -> ref64_analytic_lights.record;
@@ -460,6 +469,32 @@ def medium_interval(m, o, d, t_s, T):
                 b = np.where(hi < b, hi, b)
             ok = a < b
     return a, b, ok
+
+
+def optical_depth(S, o, d, t_max, T):
+    """(tau, the set of media with a non-empty stay) of the segments o + t d, t in [0.001, t_max]: every medium of
+    positive density, in list order, adds sigma (b - a) |d| of its stay [a, b].  No draw is taken"""
+    tau = np.zeros(len(o), T)
+    stays = np.zeros(len(o), np.int64)
+    length = np.sqrt(_dot(d, d))
+    far = np.full(len(o), t_max, T)
+    for mi, m in enumerate(S.media):
+        sigma = T(m["density"])
+        if not sigma > 0:
+            continue
+        a, b, ok = medium_interval(m, o, d, far, T)
+        tau = np.where(ok, tau + sigma * (b - a) * length, tau)
+        stays |= np.where(ok, 1 << mi, 0)
+    return tau, stays
+
+
+def phase_density(g, c, T):
+    """the phase function's density per steradian at cos t = c, per vertex: 1 / (4 pi) where the asymmetry g (fp64) is 0"""
+    out = np.full(len(g), T(1.0 / (4.0 * np.pi)), T)
+    k = g != 0
+    if k.any():
+        out[k] = PH.hg_density(g[k], c[k])
+    return out
 
 
 def checker_odd(p, T):
@@ -857,7 +892,13 @@ def trace(S, words, first_pixel=0, dtype=np.float64, perturb=(), shutter=None, p
     perturb names deliberate mistakes, for the tests that show the comparison can fail.  Every name, in one place (the model
     files' docstrings say what each of theirs does):
       ref64_noise.PERTURBATIONS, ref64_bump.PERTURBATIONS, ref64_normal_map.PERTURBATIONS, ref64_glass.PERTURBATIONS
-      ("fresnel_draw_last" is glass's name for "lobe_draw_last"), ref64_pbr.PERTURBATIONS, ref64_analytic_lights.PERTURBATIONS;
+      ("fresnel_draw_last" is glass's name for "lobe_draw_last"), ref64_pbr.PERTURBATIONS, ref64_analytic_lights.PERTURBATIONS,
+      ref64_phase.PERTURBATIONS ("phase_isotropic": g ignored altogether, every medium vertex runs the rejection loop);
+      of 7z (media_nee_scenes.MISTAKES says which case shows which): "no_transmittance": the shadow ray ignores the media
+      (T = 1);  "isotropic_pdf": pdf_b = 1 / (4 pi) at a vertex with g != 0, for the light's direction and the continuation's (the
+      direction is still drawn with g);
+      "shadow_flight_draw": a free-flight draw taken for every non-empty stay of a shadow ray (and thrown away);
+      "medium_full_weight": a medium vertex's continuation arrives at an emitter at full weight (as if it took no light sample);
       "tri_no_sqrt": a triangle light's barycentrics taken without the square root (s = u1): points crowd towards v2;
       "tri_vertex_normal": a triangle light's density stated with its first vertex normal in place of the geometric one;
       "quad_uv_swapped": a quad's (u, v) = (b, a);  "quad_light_half_area": a quad light's density stated with half the area;
@@ -891,6 +932,7 @@ def trace(S, words, first_pixel=0, dtype=np.float64, perturb=(), shutter=None, p
         time = np.full(N, 0.5, T) if "half_time" in perturb else np.asarray(shutter, np.float64).astype(T)
     cam = {k: v.astype(T) for k, v in S.cam.items()}
     sig = [np.full((N, SAMPLE_COLUMNS), NONE, np.int64)]
+    media_g = S.media_g.astype(np.float64) * (0 if "phase_isotropic" in perturb else -1 if "phase_backward" in perturb else 1)
 
     def note(column, who, values):
         sig[-1][who, column] = values
@@ -1043,13 +1085,27 @@ def trace(S, words, first_pixel=0, dtype=np.float64, perturb=(), shutter=None, p
         refl_dir = np.zeros_like(dd)       # metal: the mirror direction of its lobe
         fuzz = np.zeros(len(who), T)       # metal: its fuzz (0: a lambertian vertex)
         takes_light = np.zeros(len(who), bool)
-        if vol.any():  # a medium event: a vertex without a normal that emits nothing -- albedo, then a uniform direction
-            if len(S.lights):
-                raise NotImplementedError("a light sample at a medium vertex: DESIGN defines none")
+        travel = np.zeros_like(dd)             # a medium vertex: the unit direction of travel that arrived
+        g_v = np.zeros(len(who), np.float64)   # ... and its medium's asymmetry as the light sample and the continuation see it
+        if vol.any():  # a medium event: a vertex without a normal that emits nothing -- albedo, then a direction by its medium's g
             k = np.flatnonzero(vol)
-            new_d[k] = _unit(D.reject(who[k], 3, T))
+            travel[k] = _unit(dd[k])
+            iso, hg = k[media_g[med[k]] == 0], k[media_g[med[k]] != 0]
+            new_d[iso] = _unit(D.reject(who[iso], 3, T))  # g = 0 (7f): uniform, by the rejection loop
+            event[iso] = EV_MEDIUM
+            if len(hg):  # g != 0 (7y): two draws, the polar angle about the direction of travel from u1, the azimuth from u2
+                u1, u2 = D.next(who[hg]), D.next(who[hg])
+                if "phase_swapped_draws" in perturb:
+                    u1, u2 = u2, u1
+                for mi in np.unique(med[hg]):
+                    sel = med[hg] == mi
+                    new_d[hg[sel]] = PH.hg_direction(media_g[mi], travel[hg[sel]], u1[sel], u2[sel], T)
+                event[hg] = EV_MEDIUM_HG
             att[k] = S.media["albedo"][med[k]].astype(T)
-            event[k] = EV_MEDIUM
+            if S.nee and len(S.lights):  # (7z) it takes a light sample: f = albedo x pdf_b, no cosine and no hemisphere
+                g_v[k] = 0.0 if "isotropic_pdf" in perturb else media_g[med[k]]
+                takes_light[k] = True
+                pdf_b[k] = phase_density(g_v[k], _dot(_unit(new_d[k]), travel[k]), T)
         lam = kind == LAMBERTIAN
         if lam.any():
             sph = D.reject(who[lam], 3, T)
@@ -1186,6 +1242,7 @@ def trace(S, words, first_pixel=0, dtype=np.float64, perturb=(), shutter=None, p
         carried = beta[who] * att                      # the throughput the continuation carries
         depth[who[go]] -= 1
         go_on = go & (depth[who] > 0)
+        log["ended_by_depth"] += int((go & ~go_on).sum())
         absorbed = ~em & ~scattered                    # (a metal direction below the surface)
         # an absorbed metal vertex samples its light where its continuation would have been traced, with a roulette draw of its own
         draws_rr = go_on | (absorbed & takes_light & (depth[who] > 1))
@@ -1202,6 +1259,8 @@ def trace(S, words, first_pixel=0, dtype=np.float64, perturb=(), shutter=None, p
         beta[who] = carried
         o[who], d[who] = p, new_d
         mis[who] = np.where(takes_light, pdf_b, -1)
+        if "medium_full_weight" in perturb:
+            mis[who[vol]] = -1
         # ---- the light sample
         ls = np.flatnonzero(takes_light & survived & draws_rr & (len(S.lights) > 0))
         if len(ls) == 0:
@@ -1239,6 +1298,8 @@ def trace(S, words, first_pixel=0, dtype=np.float64, perturb=(), shutter=None, p
                 sel = fuzz[ls] == f
                 pb[sel] = metal_pdf(w[sel], refl_dir[ls][sel], f, T)
             pb = np.where(wn > 0, pb, 0)
+            mv = vol[ls]  # a medium vertex: the phase function's density of the light's direction, no cosine and no hemisphere
+            pb[mv] = phase_density(g_v[ls][mv], _dot(w[mv], travel[ls][mv]), T)
             if gl.any():
                 # f cos is not albedo x pdf_b at a glossy vertex: both are evaluated for the light's direction
                 q, wl = ls[gl], w[gl]
@@ -1268,21 +1329,30 @@ def trace(S, words, first_pixel=0, dtype=np.float64, perturb=(), shutter=None, p
         usable = (pl > 0) & (pb > 0) & (d2 > 0) & np.isfinite(weight) & (weight > 0)
         verdict = np.where(inside, SHADOW_INSIDE, SHADOW_NONE)
         if usable.any():
-            if len(S.media) or len(S.movers):
-                raise NotImplementedError("a shadow ray through a medium or past a mover: DESIGN defines none")
             k = np.flatnonzero(usable)
             is_env = S.lights["shape"][pick[k]] == ENVIRONMENT
+            if len(S.movers) or (len(S.media) and is_env.any()):
+                raise NotImplementedError("a shadow ray past a mover, or towards the environment in a scene with media: DESIGN defines none")
             far = np.where(is_env, T(np.inf), T(SHADOW_T_MAX))
             _, blocker = opaque_hit(S, p[ls][k], ld[k], far, T, perturb, log, m[k])
             verdict[k] = np.where(blocker >= 0, SHADOW_OCCLUDED, SHADOW_CLEAR)
             note(C_BLOCKER, m[k], np.where(blocker >= 0, blocker, NONE))
             clear = k[blocker < 0]
+            reach = weight[clear]  # the sample's weight as it reaches the vertex
+            if len(S.media):  # (7z) the shadow ray takes no draw; any opaque hit occludes; a clear sample is dimmed by exp(-tau)
+                tau, stays = optical_depth(S, p[ls][k], ld[k], T(SHADOW_T_MAX), T)
+                if "shadow_flight_draw" in perturb:
+                    for mi in range(len(S.media)):
+                        D.next(m[k][(stays >> mi) & 1 == 1])
+                note(C_STAYS, m[k], stays)
+                if "no_transmittance" not in perturb:
+                    reach = reach * np.exp(-tau[blocker < 0])
             through = carried[ls][clear]
             if gl.any():
                 through = np.where(gl[clear][:, None], before[ls][clear] * fcos[clear], through)
             if "no_rr_light" in perturb and rr > 0:
                 through = through * rr
-            rgb[m[clear]] += through * Le[clear] * weight[clear][:, None]
+            rgb[m[clear]] += through * Le[clear] * reach[:, None]
         note(C_SHADOW, m, verdict)
 
     sig[0][:, 0] = D.at
@@ -1302,7 +1372,10 @@ def tally(sig, S=None, log=None):
     hits on that light from inside kept at weight 1; absorbed metal vertices that took a light sample all the same; dielectric
     vertices, the light samples they took (none, by definition) and the emitter hits of their rays at full weight; light picks
     that went to the bucket's own light and to its alias.  Of 7f (MEDIA_KEYS): medium events, those on paths that met a surface
-    vertex later, those behind a refraction, and the media that had one.  Of 7g (MOTION_KEYS): vertices on movers, which movers
+    vertex later, those behind a refraction, and the media that had one.  Of 7y: medium events by whether the medium's g is 0,
+    paths that met a surface after an anisotropic one, paths with both kinds.  Of 7z: light samples at medium and at surface
+    vertices, the medium ones that were clear, shadow rays that stayed in a medium by verdict, emitter hits straight behind a
+    medium vertex and those of them weighted by MIS.  Of 7g (MOTION_KEYS): vertices on movers, which movers
     were hit, and the paths that went from a mover to a static surface and the other way.  Of triangles and image textures
     (EXT_KEYS): vertices that read an image texel, those that took a light sample, those on a mover, the samples with such a
     vertex, and the samples that met one after a medium event; emitter hits at full weight behind a vertex that took a light
@@ -1324,7 +1397,11 @@ def tally(sig, S=None, log=None):
     of = lambda flags, i: (i >= 0) & flags[np.clip(i, 0, len(flags) - 1)]
     glass = np.isin(event, (EV_REFLECT, EV_REFRACT))
     later = lambda x: np.flip(np.cumsum(np.flip(x, axis=1), axis=1), axis=1) - x > 0
-    med = event == EV_MEDIUM
+    med, hg = np.isin(event, MEDIUM_EVENTS), event == EV_MEDIUM_HG
+    took, emit = light != NONE, event == EV_EMIT
+    nxt = lambda x: np.concatenate([x[:, 1:], np.zeros((len(x), 1), bool)], axis=1)
+    # C_STAYS shares its column with the environment light's texel: it is a set of media where the scene has media (C_DREW is set)
+    through = (v[:, :, C_DREW] != NONE) & (v[:, :, C_STAYS] != NONE) & (v[:, :, C_STAYS] > 0)
     surface = np.isin(event, (EV_LAMBERT, EV_METAL, EV_METAL_ABSORBED, EV_REFLECT, EV_REFRACT, EV_EMIT))
     glass_before = np.cumsum(np.isin(event, (EV_REFRACT,)), axis=1) > 0
     vertex = event != NONE
@@ -1354,6 +1431,15 @@ def tally(sig, S=None, log=None):
                 medium_events=int(med.sum()), medium_then_surface=int((med & later(surface)).any(axis=1).sum()),
                 medium_behind_glass=int((med & glass_before).sum()),
                 media_with_events=sorted(int(i) for i in np.unique(v[:, :, C_MEDIUM][med])),
+                anisotropic_events=int(hg.sum()), isotropic_events=int((med & ~hg).sum()),
+                surface_after_anisotropic=int((hg & later(surface)).any(axis=1).sum()),
+                both_on_one_path=int((hg.any(axis=1) & (med & ~hg).any(axis=1)).sum()),
+                medium_light_samples=int((med & took).sum()), surface_light_samples=int((~med & took).sum()),
+                medium_samples_clear=int((med & (shadow == SHADOW_CLEAR)).sum()),
+                clear_through_media=int(((shadow == SHADOW_CLEAR) & through).sum()),
+                occluded_through_media=int(((shadow == SHADOW_OCCLUDED) & through).sum()),
+                medium_then_emitter=int((med & nxt(emit)).sum()),
+                medium_then_emitter_mis=int((med & took & nxt(emit & (how == HIT_MIS))).sum()),
                 mover_vertices=int(on_mover.sum()), movers_hit=sorted(int(i) for i in np.unique(mover[on_mover])),
                 mover_then_static=int((on_mover & later(on_static)).any(axis=1).sum()),
                 static_then_mover=int((on_static & later(on_mover)).any(axis=1).sum()),
@@ -1402,7 +1488,7 @@ def _extension_tally(v, S):
                analytic_no_shadow_ray=count(delta & (shadow == SHADOW_NONE)), glossy_lit_by_analytic=count(glossy & delta & (shadow == SHADOW_CLEAR)),
                emitter_mis_hits=count(emit & (how == HIT_MIS)))
     # ---- the material under every surface vertex: a mover's is its own; a medium event is no surface
-    surface = (event != NONE) & (event != EV_MISS) & (event != EV_MEDIUM)
+    surface = (event != NONE) & (event != EV_MISS) & ~np.isin(event, MEDIUM_EVENTS)
     on_mover = mover >= 0 if len(S.movers) else np.zeros(event.shape, bool)
     static = surface & (prim >= 0) & ~on_mover
     mat = np.where(prim >= 0, S.prims["material"][np.clip(prim, 0, max(len(S.prims) - 1, 0))], -1) if len(S.prims) else np.full(event.shape, -1)
@@ -1434,7 +1520,7 @@ def _extension_tally(v, S):
                glass_light_samples=count(on & took), glass_below_light_samples=count(on & (event == EV_BELOW) & took),
                glass_full_weight_hits_behind_refraction=count(on & (event == EV_BODY) & took & nxt(emit_full)),
                glass_mis_hits_behind_reflection=count(on & (event == EV_COAT) & nxt(emit_mis)),
-               glass_then_medium=count((np.cumsum(on & (event == EV_BODY), axis=1) > 0) & (event == EV_MEDIUM)),
+               glass_then_medium=count((np.cumsum(on & (event == EV_BODY), axis=1) > 0) & np.isin(event, MEDIUM_EVENTS)),
                glass_roughnesses=sorted(float(np.float32(x)) for x in np.unique(rough)))
     return out
 

@@ -6,7 +6,7 @@
      light-sampling kernel on the scene without it -- no interval, no draw, tau = 0, T = 1;
   3. inside a closed sphere emitter every one-sample pixel is exactly 2^-k or 0, though the light draws are consumed;
   4. the white furnace: every pixel's expectation is exactly 1;
-  5. per-sample agreement with the fp64 statement (ref64_media_nee.py), criteria (a)-(d) of test_gpu_nee_reference.py, and
+  5. per-sample agreement with the fp64 statement (ref64.trace), criteria (a)-(d) of test_gpu_nee_reference.py, and
      each of the statement's four deliberate mistakes noticed;
   6. the same estimator as the plain media kernel, by frame means;
   7. it pays on the showcase's lamp: the median per-pixel variance ratio plain / sampled is above 1;
@@ -23,7 +23,6 @@ import media_nee_scenes as MN
 import media_scenes as MS
 import per_sample as PS
 import ref64 as R
-import ref64_media_nee as RM
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
@@ -117,15 +116,14 @@ def words(rtmi):
 
 @pytest.fixture(scope="module")
 def cases(rtmi, words):
-    """of(name) -> (scene, RefScene, the media's stored g, kernel samples, (ref, stable, draws, tally)), rendered and traced once"""
+    """of(name) -> (scene, RefScene, kernel samples, (ref, stable, draws, tally)), rendered and traced once"""
     made = {}
 
     def of(name):
         if name not in made:
             sc = MN.scene(rtmi, name)
-            S, g = R.RefScene(sc), [sc.medium_phase(i) for i in range(len(sc.media()))]
             got = PS.kernel_samples(rtmi, sc, MN.REF_SEED, MN.REF_K, MN.FAMILIES, MN.FAMILIES)
-            made[name] = (sc, S, g, got, RM.reference(S, g, words))
+            made[name] = (sc, R.RefScene(sc), got, R.reference(R.RefScene(sc), words))
         return made[name]
     return of
 
@@ -136,7 +134,7 @@ TALLY_KEYS = ("medium_events", "medium_light_samples", "clear_through_media", "o
 @pytest.mark.parametrize("name", list(MN.ref_cases()))
 def test_kernel_against_fp64(rtmi, words, cases, name):
     assert len(words) >= 16000
-    sc, S, g, got, (ref, stable, draws, tally) = cases(name)
+    sc, S, got, (ref, stable, draws, tally) = cases(name)
     assert draws.max() <= MN.REF_DRAWS, draws.max()                                         # (d)
     assert tally["medium_events"] > 0 and tally["medium_light_samples"] > 0, tally
     if name == "medium inside a glass shell":
@@ -158,7 +156,7 @@ def test_kernel_against_fp64(rtmi, words, cases, name):
 def test_the_cases_together_cover_the_new_vertices(rtmi, words, cases):
     total = {k: 0 for k in TALLY_KEYS + ("anisotropic_events",)}
     for name in MN.ref_cases():
-        tally = cases(name)[4][3]
+        tally = cases(name)[3][3]
         for k in total:
             total[k] += tally[k]
     print("\n" + ", ".join(f"{k} {v}" for k, v in total.items()))
@@ -168,12 +166,7 @@ def test_the_cases_together_cover_the_new_vertices(rtmi, words, cases):
 @pytest.mark.parametrize("mistake", list(MN.MISTAKES))
 def test_a_mistake_fails_the_agreement(rtmi, words, cases, mistake):
     """(d): against the kernel, the statement with one deliberate mistake is far from 97 %"""
-    name = MN.MISTAKES[mistake]
-    sc, S, g, got, (ref, stable, _, _) = cases(name)
-    wrong, _, _ = RM.trace(S, g, words, perturb=(mistake,))
-    good, bad = R.judge(got, ref, stable), R.judge(got, wrong, stable)
-    print(f"\n{name}, {mistake}: within tolerance {100 * good['share']:.2f} % -> {100 * bad['share']:.2f} %")
-    PS.assert_perturbation_noticed(good, bad)
+    PS.check_a_mistake_fails_the_agreement(lambda name: (words, None), cases, MN.MISTAKES[mistake], mistake)
 
 
 # ---- 6 ---------------------------------------------------------------------------------------------------------------------------

@@ -4,7 +4,7 @@
   2. an anisotropic medium no ray can reach gives the plain kernel's bytes (media_scenes.bury_medium_*): no interval, no draw, so
      everything else in the media kernel is still the oracle-pinned computation;
   3. the sample weight is exactly the albedo: exact powers of 1/2 inside a closed emitter;
-  4. per-sample agreement with the fp64 statement (ref64_phase.py), criteria (a)-(c) of test_gpu_nee_reference.py with the
+  4. per-sample agreement with the fp64 statement (ref64.trace), criteria (a)-(c) of test_gpu_nee_reference.py with the
      plain kernel on the plain twin as the baseline (per_sample.assert_agreement);
   5. (d): each of the statement's three deliberate mistakes is noticed by the kernel's samples;
   6. the exact composition of layouts, a sample split, row shards and the product library; the shipped fog_halo scene;
@@ -108,14 +108,14 @@ def words(rtmi):
 
 @pytest.fixture(scope="module")
 def cases(rtmi, words):
-    """of(name) -> (scene, RefScene, g, kernel samples, (ref, stable, draws, tally)), rendered and traced once"""
+    """of(name) -> (scene, RefScene, kernel samples, (ref, stable, draws, tally)), rendered and traced once"""
     made = {}
 
     def of(name):
         if name not in made:
             sc = PH.scene(rtmi, name)
-            S, g = R.RefScene(sc), RP.stored_g(sc)
-            made[name] = (sc, S, g, PS.kernel_samples(rtmi, sc, PH.REF_SEED, PH.REF_K, MEDIA, MEDIA), RP.reference(S, g, words))
+            S = R.RefScene(sc)
+            made[name] = (sc, S, PS.kernel_samples(rtmi, sc, PH.REF_SEED, PH.REF_K, MEDIA, MEDIA), R.reference(S, words))
         return made[name]
     return of
 
@@ -123,27 +123,23 @@ def cases(rtmi, words):
 @pytest.mark.parametrize("name", list(PH.ref_cases()))
 def test_media_kernel_against_fp64(rtmi, words, cases, name):
     assert len(words) >= 16000
-    sc, S, g, got, (ref, stable, draws, tally) = cases(name)
+    sc, S, got, (ref, stable, draws, tally) = cases(name)
     assert draws.max() <= PH.REF_DRAWS, draws.max()
     assert tally["anisotropic_events"] >= 200 and tally["surface_after_anisotropic"] >= 50, tally
-    assert tally["media_with_events"] == list(range(len(g))), tally
+    assert tally["media_with_events"] == list(range(len(S.media))), tally
     if name == PH.OVERLAP:
         assert tally["both_on_one_path"] >= 50, tally
     plain = PH.plain_twin(sc)
     bref, bstable, _, _ = R.reference(R.RefScene(plain), words)
     b = R.judge(PS.kernel_samples(rtmi, plain, PH.REF_SEED, PH.REF_K, MEDIA, 0), bref, bstable)
     PS.assert_agreement(name, R.judge(got, ref, stable), b)                                 # (a), (b), (c)
-    print("    " + ", ".join(f"{k} {v}" for k, v in tally.items()))
+    print("    " + ", ".join(f"{k} {tally[k]}" for k in PH.TALLY_KEYS))
 
 
 @pytest.mark.parametrize("mistake", RP.PERTURBATIONS)
 @pytest.mark.parametrize("name", list(PH.ref_cases()))
 def test_a_mistake_of_the_phase_step_fails_the_agreement(words, cases, name, mistake):
-    sc, S, g, got, (ref, stable, _, _) = cases(name)
-    wrong, _, _ = RP.trace(S, g, words, perturb=(mistake,))
-    good, bad = R.judge(got, ref, stable), R.judge(got, wrong, stable)
-    print(f"\n{name}, {mistake}: within tolerance {100 * good['share']:.2f} % -> {100 * bad['share']:.2f} %")
-    PS.assert_perturbation_noticed(good, bad)
+    PS.check_a_mistake_fails_the_agreement(lambda name: (words, None), cases, name, mistake)
 
 
 # ---- 6 ---------------------------------------------------------------------------------------------------------------------

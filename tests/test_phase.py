@@ -1,7 +1,7 @@
 """Anisotropic media, host side (no GPU): the interface of a medium's asymmetry g through C, C++ and Python, JSON, the
-packed tables, the host evaluations of the device's phase function (csrc/rt_phase.h) against fp64, the new fp64 statement
-(ref64_phase.py) against the established one (ref64.py) where every g = 0, and the premises of the GPU comparison
-(test_gpu_phase.py) from the reference alone.
+packed tables, the host evaluations of the device's phase function (csrc/rt_phase.h) against fp64, the fp64 statement
+(ref64.trace with ref64_phase.py's model) against what it returned before the phase function joined its loop where every g = 0,
+and the premises of the GPU comparison (test_gpu_phase.py) from the reference alone.
 
 The tolerances of rt_phase_hg_sample, per |g|: the committed fp32 sequence measured on the CPU over the fixed inputs of
 sample_inputs() (MEASURED below; DESIGN 7y has the table), asserted at 4 x the measured maximum.  The inverse's numerator
@@ -16,7 +16,9 @@ import subprocess
 import numpy as np
 import pytest
 
+import media_nee_scenes as MN
 import media_scenes as MS
+import per_sample as PS
 import phase_scenes as PH
 import ref64 as R
 import ref64_phase as RP
@@ -323,42 +325,68 @@ def test_eval_against_the_closed_form_and_its_quadrature(rtmi):
         assert abs(integral - 1) <= 1e-4, (g, integral, at_nodes)
 
 
-# ---- ref64_phase against ref64, and the premises of the GPU comparison -------------------------------------------------------
+# ---- the phase step in ref64.trace: pinned where every g = 0, inert there, and the premises of the GPU comparison -------------------
 @pytest.fixture(scope="module")
 def words(rtmi):
     return R.uniforms(rtmi, PH.REF_SEED, PH.REF_W, PH.REF_H, 0, PH.REF_K, PH.REF_DRAWS)
 
 
 @pytest.mark.parametrize("name", list(PH.ref_cases()))
-def test_with_every_g_zero_the_statement_is_ref64s(rtmi, words, name):
+def test_with_every_g_zero_the_statement_is_ref64s(rtmi, golden_dir, name):
+    """... as ref64.trace stated it before the phase function joined its loop: the twins are held to golden/ref64_media_pin.npz"""
     sc = PH.isotropic_twin(PH.ref_cases()[name](rtmi))
     assert not RP.stored_g(sc).any()
-    want, stable, draws, tally = R.reference(R.RefScene(sc), words)
-    got, gstable, gdraws, gtally = RP.reference(R.RefScene(sc), RP.stored_g(sc), words)
-    assert np.abs(got - want).max() <= 1e-12 and np.array_equal(draws, gdraws) and np.array_equal(stable, gstable)
-    assert gtally["anisotropic_events"] == 0 and gtally["isotropic_events"] == tally["medium_events"] > 0
+    S, words, got, tally = PS.check_media_pin(rtmi, golden_dir, "twin/" + name, sc)
+    assert not S.media_g.any() and tally["anisotropic_events"] == 0 and tally["isotropic_events"] == tally["medium_events"] > 0
     # and a mistake of the phase step changes nothing where no vertex takes it
     for mistake in RP.PERTURBATIONS:
-        assert np.array_equal(RP.trace(R.RefScene(sc), RP.stored_g(sc), words[:3000], perturb=(mistake,))[0], got[:3000])
+        assert np.array_equal(R.trace(S, words[:3000], perturb=(mistake,))[0], got[:3000])
+
+
+def test_the_phase_block_is_inert_where_every_g_is_zero(rtmi, monkeypatch):
+    """on the pinned glossy-free cases, an isotropic twin and a media case with light samples whose g is 0, neither the
+    Henyey-Greenstein direction nor its density is ever called"""
+    from test_glossy import _existing_cases
+
+    def never(*a, **k):
+        raise AssertionError("the phase function was evaluated in a scene whose media are isotropic")
+    assert R.PH is RP
+    direction = RP.hg_direction
+    monkeypatch.setattr(RP, "hg_direction", never)
+    monkeypatch.setattr(RP, "hg_density", never)
+    fog = MN.scene(rtmi, "camera inside thin fog")
+    assert len(fog.lights()) and not RP.stored_g(fog).any()
+    scenes = dict(_existing_cases(rtmi), twin=(PH.isotropic_twin(PH.scene(rtmi, PH.OVERLAP)), PH.REF_SEED), lit=(fog, MN.REF_SEED))
+    for name, (sc, seed) in scenes.items():
+        words = R.uniforms(rtmi, seed, PH.REF_W, PH.REF_H, 0, 1, PH.REF_DRAWS)
+        rgb, sig, _ = R.trace(R.RefScene(sc), words)
+        assert rgb.any(), name
+    assert R.tally(sig)["medium_light_samples"] > 0
+    with pytest.raises(AssertionError, match="phase function"):  # ... and the swap does reach the tracer: the direction
+        R.trace(R.RefScene(PH.scene(rtmi, PH.OVERLAP)), words)
+    monkeypatch.setattr(RP, "hg_direction", direction)
+    with pytest.raises(AssertionError, match="phase function"):  # ... and, with the direction back, a light sample's density
+        R.trace(R.RefScene(MN.scene(rtmi, "thin fog, g = 0.7")), words)
 
 
 @pytest.mark.parametrize("name", list(PH.ref_cases()))
 def test_premises_of_the_gpu_comparison(rtmi, words, name):
     assert len(words) >= 16000
     sc = PH.ref_cases()[name](rtmi)
-    S, g = R.RefScene(sc), RP.stored_g(sc)
-    ref, stable, draws, tally = RP.reference(S, g, words)
-    r32, _, _ = RP.trace(S, g, words, dtype=np.float32)
-    print(f"\n{name:44s} flips {100 * (1 - stable.mean()):.3f} %   draws <= {draws.max()}   {tally}")
+    S = R.RefScene(sc)
+    assert np.array_equal(S.media_g, RP.stored_g(sc)) and S.media_g.any()
+    ref, stable, draws, tally = R.reference(S, words)
+    r32, _, _ = R.trace(S, words, dtype=np.float32)
+    print(f"\n{name:44s} flips {100 * (1 - stable.mean()):.3f} %   draws <= {draws.max()}   " + str({k: tally[k] for k in PH.TALLY_KEYS}))
     assert 1 - stable.mean() <= 0.01
     assert tally["anisotropic_events"] >= 200 and tally["surface_after_anisotropic"] >= 50, tally
-    assert tally["media_with_events"] == list(range(len(g))), tally
+    assert tally["media_with_events"] == list(range(len(S.media))), tally
     if name == PH.OVERLAP:
         assert tally["both_on_one_path"] >= 50 and tally["isotropic_events"] >= 200, tally
     assert draws.max() <= PH.REF_DRAWS
     assert R.judge(r32, ref, stable)["share"] >= 0.97
     for mistake in RP.PERTURBATIONS:
-        wrong, _, _ = RP.trace(S, g, words, perturb=(mistake,))
+        wrong, _, _ = R.trace(S, words, perturb=(mistake,))
         share = R.judge(r32, wrong, stable)["share"]
         print(f"    {mistake:22s} agrees on {100 * share:.2f} %")
         assert share < 0.97, (name, mistake, share)
